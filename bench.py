@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the IODINE refinement step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--mode infer|train] [--config clevr6|dsprites] [--graph 0|1]
+    python bench.py --gpus N --steps K --warmup W [--mode infer|train] [--config clevr6|dsprites] [--graph 0|1] [--full]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one synthetic batch resident in HBM:
   * mode train (default): ``loss = model(x); optimizer.zero_grad(); loss.backward(); optimizer.step()`` = the timed body of
@@ -18,11 +19,21 @@ one RCCL all-reduce of the flat gradient buffer per training step, no data-path 
 ``--gpus N`` with N>1 and no launcher environment starts its own N ranks (``torch.distributed.run``, one process per GPU);
 under the driver's ``python -m torch.distributed.run ... bench.py --gpus N`` the ranks are used as given.
 
-The timed region is EXACTLY ``--steps`` steps (``value``, ``ms_per_step``).  When that region is shorter than 6 s the same step
-keeps running afterwards until 6 s of continuous GPU work have passed (``sustained``: steps_run, ms_per_step - a second,
-longer measurement of the same loop, and long enough for an external utilisation sampler to see the GPU busy).
+The timed region is EXACTLY ``--steps`` steps (``value``, ``ms_per_step``).  A plain run does only what that headline needs: set-up,
+``--warmup`` steps, the timed steps, the outputs of ``--dump-outputs`` and the result line.  Its timed region records no HIP events.
 
-Extra objects on the JSON line:
+``--dump-outputs DIR`` writes what the last timed step handed its caller as ``DIR/<name>.npy`` (float32), at most 64 MB in all:
+train mode ``loss``, ``elbo_terms`` (T+1, 3), ``grads`` and ``params`` (every parameter flattened in named_parameters() order:
+the gradients of the step and the parameters after its Adam update); infer mode ``pred``, ``mask``, ``mean`` and ``elbo_terms``.
+An array that does not fit the budget keeps a fixed, seeded sample of its elements (the same on every run of the same shape).
+Weights, images and noise are seeded, so the same arguments give the same inputs on every run.
+
+Everything below is measured with ``--full`` only, which also brackets the dominant launches of the timed region with HIP events.
+When the timed region is shorter than 6 s the same step keeps running afterwards until 6 s of continuous GPU work have passed
+(``sustained``: steps_run, ms_per_step - a second, longer measurement of the same loop, and long enough for an external
+utilisation sampler to see the GPU busy).
+
+Extra objects on the JSON line of ``--full``:
   * ``roofline``: the dominant kernel (split-fp16 MFMA 3x3 conv C->C, forward / data-gradient / weight-gradient launches);
     duration from HIP events recorded on the launch stream inside the timed region; ``traffic`` from the tracked PMC file
     profiles/r*_pmc.json while its source digest still matches the tree;
@@ -63,6 +74,7 @@ PUBLISHED_TRAIN_ITERS_PER_S = 94.0  # 1.7 s / 32-image T=
 DOMINANT = ('conv_tile_fwd', 'conv_tile_dgrad', 'conv_tile_wgrad')
 FP32_KNAME = ('conv3x3_ws_f16x3_kernel<{C},EPI,F32=true> + conv3x3_wgrad_f32_ws_kernel<{C}> (decoder 3x3 conv {C}->{C}: fwd, dgrad, wgrad launches; '
               'weight-stationary / persistent, exact fp32 MFMA: v_mfma_f32_16x16x4_f32 and v_mfma_f32_32x32x2_f32)')
+DUMP_BUDGET = 64 * 10 ** 6         # --dump-outputs: bytes in all
 PROFILE_STRIDE = 7                 # timed region: every 7th launch of each dominant form is bracketed with HIP events (library option profile_stride)
 CATS = DOMINANT + ('dec_out', 'dec_out_dgrad', 'dec_out_wgrad', 'dec_out_bwd', 'dec_l0', 'l0_reduce', 'l0_slot_sum', 'pixel_pass1',
                    'pixel_pass2', 'refine_conv', 'refine_l0', 'refine_l0f', 'refine_head', 'refine_wgrad', 'refine_dgrad', 'refine_bwd01', 'refine_bias_grad', 'head_bwd')
@@ -91,7 +103,15 @@ def parse():
     ap.add_argument('--cpu-batch', type=int, default=None)
     ap.add_argument('--option', action='append', default=[], metavar='KEY=VALUE',
                     help='library option for the timed model (A/B of kernel selections, e.g. refine_l0_fused=0); recorded in config.options')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run every side measurement and check (rooflines, inference step, exact fp32, side configs, CPU baseline, '
+                         'RCCL figures); a plain run times the headline step only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def build_model(config, slots, iters, device):
@@ -248,6 +268,40 @@ def hbm_algorithmic_bytes(arch, B, mode, ran=None):
     return b
 
 
+def step_outputs(model, mode, ret):
+    """What the last timed step handed its caller, as host arrays: ``ret`` is the step's return value (train: the loss; infer:
+    reconstruct's pred, mask, mean); gradients and updated parameters are read off the model."""
+    import torch
+    t = lambda v: v.detach().float().cpu().numpy()
+    out = dict(elbo_terms=t(model.elbo_terms))
+    if mode == 'infer':
+        out.update(pred=t(ret[0]), mask=t(ret[1]), mean=t(ret[2]))
+    else:
+        params = list(model.parameters())
+        out['loss'] = t(ret)
+        out['grads'] = t(torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in params]))
+        out['params'] = t(torch.cat([p.reshape(-1) for p in params]))
+    return out
+
+
+def write_outputs(path, arrays, budget=DUMP_BUDGET):
+    """``path/<name>.npy`` per array.  Over ``budget`` bytes in all, every array of more than 4096 elements keeps the same fraction of
+    its elements: a fixed, seeded sample in index order (identical on every run of the same shapes)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32) for k, a in arrays.items()}
+    big = {k for k, a in arrays.items() if a.size > 4096}
+    small_bytes = sum(a.nbytes for k, a in arrays.items() if k not in big)
+    big_bytes = sum(arrays[k].nbytes for k in big)
+    frac = min(1.0, (budget - small_bytes) / big_bytes) if big_bytes else 1.0
+    for k in sorted(arrays):
+        a = arrays[k]
+        if k in big and frac < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + '.npy'), a)
+
+
 def main():
     args = parse()
     from iodine_amd import launch
@@ -309,9 +363,9 @@ def main():
     x = torch.from_numpy(synth.make_images(B, S, seed=0, first_index=rank * B)).to(device)
     model.manual_seed(1234 + rank)                # every rank draws its own noise (library Philox, inside the step)
     # replicas start from rank 0's parameters (DataParallel re-broadcasts them on every forward, lib/modeling/build.py:11-12)
-    # and are CHECKED to be bitwise identical before the first step and after the last one
+    # and are CHECKED (--full) to be bitwise identical before the first step and after the last one
     parallel.broadcast_parameters(model, 0)
-    replicas_before = parallel.replicas_identical(model.parameters())
+    replicas_before = parallel.replicas_identical(model.parameters()) if args.full else None
 
     def make_step(m, xb, mode, adam=True):
         if mode == 'infer':
@@ -345,13 +399,15 @@ def main():
         return float(t.item())
 
     local_dt = [0.0]                                     # this rank's own clock over the last timed() region
+    last_ret = [None]                                    # what the last call of the last timed() region returned
 
     def timed(fn, n):
         """n calls of fn bracketed by barrier + synchronize on both sides; seconds, max over ranks."""
         barrier()
         t0 = time.perf_counter()
-        for _ in range(n):
+        for _ in range(n - 1):
             fn()
+        last_ret[0] = fn()
         barrier()
         local_dt[0] = time.perf_counter() - t0
         return max_over_ranks(local_dt[0])
@@ -372,17 +428,66 @@ def main():
         model.set_option(k, float(v))
     for _ in range(args.warmup):
         step()
-    model.set_option('profile_stride', PROFILE_STRIDE)
-    model.set_option('profile', 0 if args.graph else 1)
+    if args.full:
+        model.set_option('profile_stride', PROFILE_STRIDE)
+        model.set_option('profile', 0 if args.graph else 1)
     dt = timed(step, args.steps)                                          # ---- THE timed region: exactly --steps steps ----
     ms_per_step = dt / args.steps * 1e3
+    value = world * B * T / (dt / args.steps)
+    # the last timed step's outputs, read before anything else runs on the model
+    dumped = step_outputs(model, args.mode, last_ret[0]) if args.dump_outputs and rank == 0 else None
+    last_ret[0] = None
+
+    cfg_name = 'CLEVR6 128x128' if args.config == 'clevr6' else 'multi-dSprites 64x64'
+    what = ('reconstruct: T iterations + final decode' if args.mode == 'infer'
+            else 'forward + backward' + ('' if args.no_adam else ' + fused Adam step') + ', noise drawn inside the step')
+    out = dict(metric='refinement_iters_per_s', value=round(value, 2), unit='image-refinement-iters/s',
+               n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(ms_per_step, 3),
+               higher_is_better=True, scaling='weak',
+               vs_baseline=(round(value / PUBLISHED_TRAIN_ITERS_PER_S, 3) if args.mode == 'train' and args.config == 'clevr6' else None),
+               dtype=('f32 tensors; conv products from 3 f16 MFMAs on hi+lo splits: >= 22 bits relative to the 8x16-cell maximum (tile-relative), f32 accumulate' if args.conv_precision == 1 else 'f32'), data='synthetic',
+               config=dict(workload=f'{cfg_name}, K={K}, T={T}, batch {B}/GPU, {args.mode} step ({what})',
+                           step=args.mode, global_batch=B * world, slots=K, iters=T, img_size=S, hip_graph=bool(args.graph),
+                           **({'options': args.option} if args.option else {}),
+                           conv_path=('split_fp16x3: fp32 tensors, conv operands split on the fly into fp16 hi+lo with one power-of-two scale per 8x16 cell, '
+                                      'three f16 MFMAs, fp32 accumulate - products carry >= 22 bits relative to the CELL maximum (tile-relative, not '
+                                      'element-relative: profiles/r04_split_cell_stats.md); library default; `exact_fp32` on this line is the same step on fp32 MFMA'
+                                      if args.conv_precision == 1 else 'exact_fp32: fp32 MFMA, v_mfma_f32_16x16x4_f32 / 32x32x2_f32 (option conv_precision=0)'),
+                           parallelism=f'dp{world} (images sharded over ranks; '
+                                       f'{"one RCCL all-reduce of the flat gradient buffer per step" if args.mode == "train" else "no data-path collective"})'),
+               batch_iters_per_s=round(T / (dt / args.steps), 3))
+    if share:
+        # test hook: all ranks drive ONE device and the collectives ran over gloo - this line is NOT a multi-GPU measurement
+        out['shared_device'] = True
+        out['n_devices'] = 1
+        out['scaling'] = 'none (ranks share one device: test hook IODINE_BENCH_SHARE_DEVICE=1)'
+
+    def finish():
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
+        if rank == 0:
+            # the one-number summaries first (a reader of a truncated tail still finds every config's ms and frac), the long objects behind them
+            head = ['metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data']
+            summ = [k for k in out if k.endswith(('_ms_per_step', '_roofline_frac', '_train_ms', '_infer_ms', '_train_roofline', '_infer_roofline'))]
+            summary = {k: out[k] for k in head if k in out}
+            if 'roofline' in out:
+                summary['roofline_frac'] = out['roofline']['frac']
+            summary.update({k: out[k] for k in summ})
+            summary.update({k: v for k, v in out.items() if k not in summary})
+            print(json.dumps(summary), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
     rank_ms = [local_dt[0] / args.steps * 1e3]
     if world > 1:                                        # every rank's own ms/step of the timed region (jitter between ranks)
         tl = torch.tensor([rank_ms[0]], device=device, dtype=torch.float64)
         tg = [torch.zeros_like(tl) for _ in range(world)]
         dist.all_gather(tg, tl)
         rank_ms = [float(t.item()) for t in tg]
-    value = world * B * T / (dt / args.steps)
     prof = read_prof()                                   # timed region: conv_tile_* only (graph mode: nothing)
     timed_events = bool(prof)
     model.set_option('profile', 0)
@@ -557,24 +662,7 @@ def main():
                      roofline=mfma_roofline(iprof if iprof else iprof_all, args.steps if iprof else ni2, ims, bool(iprof)),
                      roofline_hbm=hbm_roofline(iprof_all, 'infer', ni2), kernels=iprof_all)
 
-    cfg_name = 'CLEVR6 128x128' if args.config == 'clevr6' else 'multi-dSprites 64x64'
-    what = ('reconstruct: T iterations + final decode' if args.mode == 'infer'
-            else 'forward + backward' + ('' if args.no_adam else ' + fused Adam step') + ', noise drawn inside the step')
-    out = dict(metric='refinement_iters_per_s', value=round(value, 2), unit='image-refinement-iters/s',
-               n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(ms_per_step, 3),
-               higher_is_better=True, scaling='weak',
-               vs_baseline=(round(value / PUBLISHED_TRAIN_ITERS_PER_S, 3) if args.mode == 'train' and args.config == 'clevr6' else None),
-               dtype=('f32 tensors; conv products from 3 f16 MFMAs on hi+lo splits: >= 22 bits relative to the 8x16-cell maximum (tile-relative), f32 accumulate' if args.conv_precision == 1 else 'f32'), data='synthetic',
-               config=dict(workload=f'{cfg_name}, K={K}, T={T}, batch {B}/GPU, {args.mode} step ({what})',
-                           step=args.mode, global_batch=B * world, slots=K, iters=T, img_size=S, hip_graph=bool(args.graph),
-                           **({'options': args.option} if args.option else {}),
-                           conv_path=('split_fp16x3: fp32 tensors, conv operands split on the fly into fp16 hi+lo with one power-of-two scale per 8x16 cell, '
-                                      'three f16 MFMAs, fp32 accumulate - products carry >= 22 bits relative to the CELL maximum (tile-relative, not '
-                                      'element-relative: profiles/r04_split_cell_stats.md); library default; `exact_fp32` on this line is the same step on fp32 MFMA'
-                                      if args.conv_precision == 1 else 'exact_fp32: fp32 MFMA, v_mfma_f32_16x16x4_f32 / 32x32x2_f32 (option conv_precision=0)'),
-                           parallelism=f'dp{world} (images sharded over ranks; '
-                                       f'{"one RCCL all-reduce of the flat gradient buffer per step" if args.mode == "train" else "no data-path collective"})'),
-               batch_iters_per_s=round(T / (dt / args.steps), 3), roofline=roofline, roofline_hbm=roofline_hbm, kernels=prof)
+    out.update(roofline=roofline, roofline_hbm=roofline_hbm, kernels=prof)
     if sustained:
         out['sustained'] = sustained
     if other:
@@ -610,11 +698,6 @@ def main():
                            hsa_ipc_mode_legacy=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY'),
                            elbo_terms_global_mean=[[round(float(v), 4) for v in row] for row in terms.cpu().tolist()],
                            elbo_terms_columns=['elbo', 'kl', 'log_likelihood'])
-        if share:
-            # test hook: all ranks drive ONE device and the collectives ran over gloo - this line is NOT a multi-GPU measurement
-            out['shared_device'] = True
-            out['n_devices'] = 1
-            out['scaling'] = 'none (ranks share one device: test hook IODINE_BENCH_SHARE_DEVICE=1)'
 
     if rank == 0 and world == 1 and args.mode == 'train' and not args.no_exact_fp32 and args.conv_precision == 1:
         # The strict-precision number, first class: the same step with every conv on the exact fp32-MFMA path
@@ -786,17 +869,7 @@ def main():
         got = model.elbo_terms[:, 0].double().cpu().numpy()
         n = min(len(got), len(ref_elbos))
         out['elbo_rel_err_vs_cpu'] = float(abs(got[:n] - ref_elbos[:n]).max() / abs(ref_elbos[:n]).max())
-    if rank == 0:
-        # the one-number summaries first (a reader of a truncated tail still finds every config's ms and frac), the long objects behind them
-        head = ['metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data']
-        summ = [k for k in out if k.endswith(('_ms_per_step', '_roofline_frac', '_train_ms', '_infer_ms', '_train_roofline', '_infer_roofline'))]
-        summary = {k: out[k] for k in head if k in out}
-        summary['roofline_frac'] = out['roofline']['frac']
-        summary.update({k: out[k] for k in summ})
-        summary.update({k: v for k, v in out.items() if k not in summary})
-        print(json.dumps(summary), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == '__main__':

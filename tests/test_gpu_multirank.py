@@ -23,7 +23,7 @@ def _last_json(text):
 @two_devices
 def test_bench_two_ranks_over_rccl():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-exact-fp32'], capture_output=True, text=True, timeout=1500)
+                        '--full', '--no-cpu-baseline', '--no-exact-fp32'], capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _last_json(r.stdout)
     assert out['n_gpus'] == 2 and out['rccl']['world_size'] == 2 and out['rccl']['backend'] == 'nccl'
@@ -55,7 +55,7 @@ def _shared_env():
 
 def test_two_ranks_sharing_one_device_bench_path():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '8',
-                        '--no-cpu-baseline', '--no-exact-fp32', '--no-sustain'], capture_output=True, text=True, timeout=1500,
+                        '--full', '--no-cpu-baseline', '--no-exact-fp32', '--no-sustain'], capture_output=True, text=True, timeout=1500,
                        env=_shared_env())
     assert r.returncode == 0, r.stderr[-3000:]
     out = _last_json(r.stdout)

@@ -20,7 +20,7 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE";
   tag=$(echo $set | cut -d' ' -f1)
   rm -rf $OUT/$tag
   timeout 600 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/$tag -o p -- \
-      python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-exact-fp32 --no-extra-configs --no-sustain "$@" > $OUT/$tag.log 2>&1 \
+      python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-exact-fp32 --no-extra-configs --no-sustain "$@" > $OUT/$tag.log 2>&1 \
       || { echo "pass $tag failed"; tail -5 $OUT/$tag.log; }
 done
 cd $REPO
