@@ -96,6 +96,17 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev_pt
 size_t iodine_workspace_bytes(const iodine_handle* h, int batch, int mode);
 int iodine_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes);
 
+/* model.K = slots; model.n_iters = iters -- the reference reads both attributes on every call (Gaussian.init_unit(B, self.K),
+ * get_input_encoding's repeat over K, the loops of encode / forward: iodine.py:81-83,123-126,279,312); no parameter depends on
+ * them.  Sets the RUN shape of every following compute call (reconstruct, decode, elbo, train_forward); the constructor's
+ * SLOTS / ITERS are the initial one.  slots in 1..16, iters >= 1.  iodine_workspace_bytes, the workspace plan, the per-call
+ * 32-bit size checks, "stop_after_iters" and the kernel selection follow it; a compute call whose installed workspace is too
+ * small for it returns IODINE_ERR_WORKSPACE.  A change while a training forward is pending discards it (the backward then
+ * returns IODINE_ERR_STATE).  iodine_last_elbo_outputs / iodine_last_posterior / iodine_debug_copy keep reading the state of the
+ * last call at the shape that call ran with.  Buffers with a slot or iteration axis (eps, outputs, z, the posterior) are sized by
+ * the run shape of the call they are passed to. */
+int iodine_set_run_shape(iodine_handle* h, int slots, int iters);
+
 /* pred, mask, mean = model.reconstruct(x) -- iodine.py:107-112 (encode :73-105 + decode :59-71).
  * Outputs (any may be NULL): pred (B,3,S,S), mask (B,K,1,S,S), mean (B,K,3,S,S) NCHW; z (B,K,L) = the final
  * sample; post_mean / post_logvar (B,K,L) = lambda after T updates; elbo_iter (T,3) = {ELBO, KL, LL} of each

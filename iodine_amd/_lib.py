@@ -19,7 +19,7 @@ ENC_FULL = 0xFFF
 # every symbol include/iodine_hip.h declares
 EXPORTS = (
     'iodine_abi_version', 'iodine_create', 'iodine_destroy', 'iodine_last_error', 'iodine_num_params',
-    'iodine_param_info', 'iodine_set_params', 'iodine_workspace_bytes', 'iodine_set_workspace',
+    'iodine_param_info', 'iodine_set_params', 'iodine_workspace_bytes', 'iodine_set_workspace', 'iodine_set_run_shape',
     'iodine_reconstruct', 'iodine_decode', 'iodine_elbo', 'iodine_last_elbo_outputs', 'iodine_last_posterior', 'iodine_randn',
     'iodine_train_forward', 'iodine_train_backward', 'iodine_train_backward_flat', 'iodine_logger_scalars',
     'iodine_adam_step', 'iodine_ari_table', 'iodine_set_option', 'iodine_profile_read', 'iodine_debug_copy', 'iodine_linspace_host', 'iodine_op_conv3x3', 'iodine_op_dec_out',
@@ -75,6 +75,7 @@ def lib() -> C.CDLL:
     L.iodine_workspace_bytes.argtypes = [vp, ci, ci]
     L.iodine_workspace_bytes.restype = C.c_size_t
     L.iodine_set_workspace.argtypes = [vp, vp, C.c_size_t]
+    L.iodine_set_run_shape.argtypes = [vp, ci, ci]
     L.iodine_reconstruct.argtypes = [vp, vp, ci] + [vp] * 9
     L.iodine_decode.argtypes = [vp, vp, ci] + [vp] * 4
     L.iodine_elbo.argtypes = [vp, vp, ci] + [vp] * 5

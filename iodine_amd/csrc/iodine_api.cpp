@@ -34,8 +34,9 @@ struct Arena {
     }
 };
 
-struct Buffers {               // workspace carve-up for one batch size / mode
+struct Buffers {               // workspace carve-up for one batch size / mode / run shape
     int B = 0, mode = -1;
+    int K = 0, T = 0;                          // the run shape (slots, iterations) it was planned for: the shape of the state it holds
     size_t bytes = 0;
     float *x4, *V, *dec_out, *g, *lnstat, *ll_img, *img_terms, *scal, *rows, *rows_p, *Rc, *pm, *plv;
     double* part;
@@ -84,7 +85,8 @@ struct iodine_handle {
         for (auto& c : prof) if (c.name == name) return &c;
         prof.push_back(ProfCat()); prof.back().name = name; return &prof.back();
     }
-    int L, T, K, S, P, Cd, Dd, Cr, Dr, H;
+    int L, T, K, S, P, Cd, Dd, Cr, Dr, H;       // K / T: the RUN shape (iodine_set_run_shape; cfg.slots / cfg.iters initially) - the
+                                                // state a call leaves behind has the shape in buf.K / buf.T
     std::vector<ParamInfo> params;
     bool params_set = false;
     int stop_after = -1;
@@ -331,7 +333,7 @@ bool refine_f16_ok(const iodine_handle* h);
 void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
 {
     const int N = B * h->K, P = h->P, L = h->L, Cd = h->Cd, Cr = h->Cr, H = h->H, T = h->T;
-    b.B = B; b.mode = mode;
+    b.B = B; b.mode = mode; b.K = h->K; b.T = h->T;
     b.x4 = a.take<float>((size_t)B * P * 4);
     b.V = a.take<float>((size_t)N * 9 * Cd);
     b.dec_out = a.take<float>((size_t)N * P * 4);
@@ -472,14 +474,14 @@ void drop_graphs(iodine_handle* h)
 
 int ensure_workspace(iodine_handle* h, int B, int mode)
 {
-    if (h->buf.B == B && h->buf.mode == mode && h->buf.bytes > 0) return IODINE_OK;
+    if (h->buf.B == B && h->buf.mode == mode && h->buf.K == h->K && h->buf.T == h->T && h->buf.bytes > 0) return IODINE_OK;
     Arena q(nullptr); Buffers tmp; plan(h, B, mode, q, tmp);
     void* base = nullptr;
     if (h->ws_user) {
         if (h->ws_user_bytes < tmp.bytes) {
             char m[160];
-            snprintf(m, sizeof m, "workspace too small: need %zu bytes for batch %d mode %d, have %zu", tmp.bytes, B,
-                     mode, h->ws_user_bytes);
+            snprintf(m, sizeof m, "workspace too small: need %zu bytes for batch %d mode %d at %d slots / %d iterations, have %zu",
+                     tmp.bytes, B, mode, h->K, h->T, h->ws_user_bytes);
             return h->fail(IODINE_ERR_WORKSPACE, m);
         }
         base = h->ws_user;
@@ -496,8 +498,8 @@ int ensure_workspace(iodine_handle* h, int B, int mode)
     h->fwd_done = false;                 // a re-planned arena no longer holds the saved forward / the last elbo() outputs
     h->last_elbo_iter = -1;
     h->enc_valid = false;
-    // captured graphs stay: their key holds the arena's base address, the batch and (through the entry point) the mode, and the
-    // carve-up is a pure function of those - a step that alternates training and reconstruct calls keeps replaying both
+    // captured graphs stay: their key holds the arena's base address, the batch, the run shape and (through the entry point) the mode,
+    // and the carve-up is a pure function of those - a step that alternates training and reconstruct calls keeps replaying both
     return IODINE_OK;
 }
 
@@ -873,7 +875,7 @@ int run_graphed(iodine_handle* h, hipStream_t st, const std::vector<uintptr_t>& 
 
 std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, std::initializer_list<const void*> ptrs)
 {
-    std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->stop_after, (uintptr_t)h->precision,
+    std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->K, (uintptr_t)h->T, (uintptr_t)h->stop_after, (uintptr_t)h->precision,
                                 (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6)),
                                 (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own)};
     for (const void* p : ptrs) k.push_back((uintptr_t)p);
@@ -983,16 +985,25 @@ int shim_build(iodine_handle* h)
 }
 
 // scratch for (rows x Lp) tensors of a call; rows_eps = (T + 1) * N for the noise, N for the others
+// (the new set is allocated in full before the old one is released: a failed hipMalloc leaves the old set and `cap` as they were)
 int shim_scratch(iodine_handle* h, size_t floats)
 {
     PadShim* sh = h->shim;
     if (floats <= sh->cap) return IODINE_OK;
     float** bufs[6] = {&sh->eps, &sh->z, &sh->pm, &sh->plv, &sh->pm_in, &sh->plv_in};
-    for (float** b : bufs) {
-        if (*b) { HIPCHK(h, hipDeviceSynchronize()); HIPCHK(h, hipFree(*b)); *b = nullptr; }
-        void* q = nullptr;
-        HIPCHK(h, hipMalloc(&q, floats * sizeof(float)));
-        *b = (float*)q;
+    void* fresh[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i <= 6; ++i) {
+        // (i == 6: the old buffers may still be read by queued work)
+        const hipError_t e = i < 6 ? hipMalloc(&fresh[i], floats * sizeof(float)) : (sh->cap > 0 ? hipDeviceSynchronize() : hipSuccess);
+        if (e != hipSuccess) {
+            for (int j = 0; j < i; ++j) (void)hipFree(fresh[j]);
+            return h->fail(IODINE_ERR_HIP, std::string(i < 6 ? "hipMalloc" : "hipDeviceSynchronize") + " (padded-handle scratch): " +
+                                               hipGetErrorString(e));
+        }
+    }
+    for (int i = 0; i < 6; ++i) {
+        if (*bufs[i]) (void)hipFree(*bufs[i]);
+        *bufs[i] = (float*)fresh[i];
     }
     sh->cap = floats;
     return IODINE_OK;
@@ -1397,6 +1408,25 @@ int iodine_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes)
     return IODINE_OK;                    // graphs are keyed by the arena address (see ensure_workspace)
 }
 
+int iodine_set_run_shape(iodine_handle* h, int slots, int iters)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    if (slots < 1 || slots > 16)
+        return h->fail(IODINE_ERR_INVALID, "slots must be in 1..16 (the per-pixel kernels keep every slot of a pixel in registers: "
+                                           "instantiated for K <= 16)");
+    if (iters < 1) return h->fail(IODINE_ERR_INVALID, "iters must be >= 1");
+    if (h->shim) {
+        const int rc = iodine_set_run_shape(h->shim->inner, slots, iters);
+        if (rc) return shim_fail(h, rc);
+    } else if (slots != h->K || iters != h->T) {
+        h->fwd_done = false;             // a pending training forward ran at the old shape: its backward is refused (IODINE_ERR_STATE)
+    }
+    // the workspace is re-planned by the next compute call (ensure_workspace keys on the run shape); the state of the last call
+    // stays readable at the shape it was produced with (buf.K / buf.T)
+    h->K = slots; h->T = iters;
+    return IODINE_OK;
+}
+
 int iodine_set_option(iodine_handle* h, const char* key, double value)
 {
     if (!h || !key) return IODINE_ERR_INVALID;
@@ -1584,25 +1614,27 @@ int iodine_last_elbo_outputs(iodine_handle* h, void* stream, int count, float* z
                              float* mask_logits, float* pred)
 {
     if (!h) return IODINE_ERR_INVALID;
+    iodine_handle* const s = h->shim ? h->shim->inner : h;         // the handle that holds the state
+    if (s->last_elbo_iter < 0 || s->buf.bytes == 0)
+        return h->fail(IODINE_ERR_STATE, "iodine_last_elbo_outputs: no elbo() has run on the current workspace");
+    if (count < 1 || count > s->last_elbo_batch)
+        return h->fail(IODINE_ERR_INVALID, "iodine_last_elbo_outputs: count must be in 1..batch of the last call");
+    const int K = s->buf.K;                                         // the slots of the call that produced the state, not the run shape
     if (h->shim) {
         PadShim* sh = h->shim;
-        const long long N = (long long)std::max(count, 0) * h->K;
+        const long long N = (long long)count * K;
         if (z) if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
         const int rc = iodine_last_elbo_outputs(sh->inner, stream, count, z ? sh->z : nullptr, mean, mask, mask_logits, pred);
         if (rc) return shim_fail(h, rc);
         if (z) HIPCHK(h, launch_resize_rows((hipStream_t)stream, sh->z, z, N, sh->Lp, sh->L));
         return IODINE_OK;
     }
-    if (h->last_elbo_iter < 0 || h->buf.bytes == 0)
-        return h->fail(IODINE_ERR_STATE, "iodine_last_elbo_outputs: no elbo() has run on the current workspace");
-    if (count < 1 || count > h->last_elbo_batch)
-        return h->fail(IODINE_ERR_INVALID, "iodine_last_elbo_outputs: count must be in 1..batch of the last call");
     hipStream_t st = (hipStream_t)stream;
     Buffers& b = h->buf;
     if (mean || mask || mask_logits || pred)
-        HIPCHK(h, launch_final_out(st, b.dec_out, pred, mask, mean, mask_logits, count, h->K, h->P));
+        HIPCHK(h, launch_final_out(st, b.dec_out, pred, mask, mean, mask_logits, count, K, h->P));
     if (z)
-        HIPCHK(h, hipMemcpyAsync(z, b.z[h->last_elbo_iter], sizeof(float) * (size_t)count * h->K * h->L,
+        HIPCHK(h, hipMemcpyAsync(z, b.z[h->last_elbo_iter], sizeof(float) * (size_t)count * K * h->L,
                                  hipMemcpyDeviceToDevice, st));
     return IODINE_OK;
 }
@@ -1610,9 +1642,15 @@ int iodine_last_elbo_outputs(iodine_handle* h, void* stream, int count, float* z
 int iodine_last_posterior(iodine_handle* h, void* stream, int count, float* post_mean, float* post_logvar)
 {
     if (!h) return IODINE_ERR_INVALID;
+    iodine_handle* const s = h->shim ? h->shim->inner : h;         // the handle that holds the state
+    if (s->last_elbo_iter < 0 || s->buf.bytes == 0)
+        return h->fail(IODINE_ERR_STATE, "iodine_last_posterior: no refinement has run on the current workspace");
+    if (count < 1 || count > s->last_elbo_batch)
+        return h->fail(IODINE_ERR_INVALID, "iodine_last_posterior: count must be in 1..batch of the last call");
+    const int K = s->buf.K;                                         // the slots of the call that produced the state, not the run shape
     if (h->shim) {
         PadShim* sh = h->shim;
-        const long long N = (long long)std::max(count, 0) * h->K;
+        const long long N = (long long)count * K;
         if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
         const int rc = iodine_last_posterior(sh->inner, stream, count, post_mean ? sh->pm : nullptr, post_logvar ? sh->plv : nullptr);
         if (rc) return shim_fail(h, rc);
@@ -1620,12 +1658,8 @@ int iodine_last_posterior(iodine_handle* h, void* stream, int count, float* post
         if (post_logvar) HIPCHK(h, launch_resize_rows((hipStream_t)stream, sh->plv, post_logvar, N, sh->Lp, sh->L));
         return IODINE_OK;
     }
-    if (h->last_elbo_iter < 0 || h->buf.bytes == 0)
-        return h->fail(IODINE_ERR_STATE, "iodine_last_posterior: no refinement has run on the current workspace");
-    if (count < 1 || count > h->last_elbo_batch)
-        return h->fail(IODINE_ERR_INVALID, "iodine_last_posterior: count must be in 1..batch of the last call");
     hipStream_t st = (hipStream_t)stream;
-    const size_t n = sizeof(float) * (size_t)count * h->K * h->L;
+    const size_t n = sizeof(float) * (size_t)count * K * h->L;
     if (post_mean) HIPCHK(h, hipMemcpyAsync(post_mean, h->buf.pm, n, hipMemcpyDeviceToDevice, st));
     if (post_logvar) HIPCHK(h, hipMemcpyAsync(post_logvar, h->buf.plv, n, hipMemcpyDeviceToDevice, st));
     return IODINE_OK;
@@ -1708,7 +1742,7 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
     }
     if (!h->fwd_done) return h->fail(IODINE_ERR_STATE, "iodine_train_backward: no iodine_train_forward to differentiate");
     if (n != (int)h->params.size() || !param_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward: wrong parameter count");
-    if (h->buf.mode != 1 || h->buf.B != h->fwd_batch)
+    if (h->buf.mode != 1 || h->buf.B != h->fwd_batch || h->buf.K != h->K || h->buf.T != h->T)
         return h->fail(IODINE_ERR_STATE, "iodine_train_backward: the training workspace of the forward pass was re-planned");
     hipStream_t st = (hipStream_t)stream;
     std::vector<const void*> kp;
@@ -1891,8 +1925,8 @@ int iodine_debug_copy(iodine_handle* h, void* stream, const char* name, int iter
     if (h->shim) return shim_fail(h, iodine_debug_copy(h->shim->inner, stream, name, iter, dst, max_floats, n_floats));   // (padded widths)
     if (h->buf.bytes == 0) return h->fail(IODINE_ERR_STATE, "iodine_debug_copy: no workspace yet");
     Buffers& b = h->buf;
-    const size_t N = (size_t)b.B * h->K, P = h->P, L = h->L;
-    if (iter < 0 || iter > h->T) return h->fail(IODINE_ERR_INVALID, "iodine_debug_copy: bad iteration index");
+    const size_t N = (size_t)b.B * b.K, P = h->P, L = h->L;        // the shape of the call that left the buffers, not the run shape
+    if (iter < 0 || iter > b.T) return h->fail(IODINE_ERR_INVALID, "iodine_debug_copy: bad iteration index");
     const std::string s(name);
     const float* src = nullptr; size_t n = 0;
     if (s == "z") { src = b.z[iter]; n = N * L; }
@@ -1907,7 +1941,7 @@ int iodine_debug_copy(iodine_handle* h, void* stream, const char* name, int iter
             if (n_floats) *n_floats = n;
             if (!dst) return IODINE_OK;
             if (n > max_floats) return h->fail(IODINE_ERR_INVALID, "iodine_debug_copy: destination too small");
-            HIPCHK(h, launch_enc_join((hipStream_t)stream, b.enck[iter], b.encs[iter], dst, (int)N, h->K, (int)P));
+            HIPCHK(h, launch_enc_join((hipStream_t)stream, b.enck[iter], b.encs[iter], dst, (int)N, b.K, (int)P));
             return IODINE_OK;
         }
         src = b.enc[iter];
@@ -1922,8 +1956,8 @@ int iodine_debug_copy(iodine_handle* h, void* stream, const char* name, int iter
     else if (s == "c") { src = b.c[iter + 1]; n = N * h->H; }
     else if (s == "pm") { src = b.pm; n = N * L; }
     else if (s == "plv") { src = b.plv; n = N * L; }
-    else if (s == "scal") { src = b.scal; n = (size_t)(h->T + 1) * 3; }
-    else if (s == "img_terms") { src = b.img_terms; n = (size_t)(h->T + 1) * b.B * 2; }
+    else if (s == "scal") { src = b.scal; n = (size_t)(b.T + 1) * 3; }
+    else if (s == "img_terms") { src = b.img_terms; n = (size_t)(b.T + 1) * b.B * 2; }
     else if (s.rfind("act", 0) == 0) {
         const int l = atoi(s.c_str() + 3);
         if (l < 0 || l >= h->Dd) return h->fail(IODINE_ERR_INVALID, "bad decoder layer");

@@ -64,10 +64,24 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
     return losses
 
 
-def evaluate(model, dataloader, device, evaluator=None):
+def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None):
     """eval.py:14-28 with the ARI evaluator of lib/eval/ari_eval.py (works under no_grad, unlike the reference).  With
     several ranks every rank evaluates its shard; the samples DistributedSampler appended to pad the shards to equal length
-    are dropped (they duplicate the first images) and ``evaluator.global_mean`` holds the ARI over the whole dataset."""
+    are dropped (they duplicate the first images) and ``evaluator.global_mean`` holds the ARI over the whole dataset.
+    ``slots`` / ``iters``: evaluate at that K / T (``model.K`` / ``model.n_iters`` for the duration of the call, restored afterwards;
+    e.g. weights trained at K = 7, T = 5 evaluated at K = 11) - the ARI tables take K from the masks."""
+    saved = (model.K, model.n_iters)
+    if slots is not None:
+        model.K = slots
+    if iters is not None:
+        model.n_iters = iters
+    try:
+        return _evaluate(model, dataloader, device, evaluator)
+    finally:
+        model.K, model.n_iters = saved
+
+
+def _evaluate(model, dataloader, device, evaluator):
     evaluator = evaluator or ARIEvaluator()
     evaluator.reset()
     model.eval()

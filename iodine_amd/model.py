@@ -10,6 +10,11 @@ kernels behind the C ABI of include/iodine_hip.h; PyTorch only owns the tensors,
 stream and the autograd hook-up.  There is no CPU or eager fallback: tensors must live on
 a ROCm device and the shared library must be built.
 
+Like the reference, ``model.K`` and ``model.n_iters`` are plain attributes read when a call starts (iodine.py:81-83,123-126): set
+them to run the same weights at another slot count (1..16) or iteration count - the paper's generalisation setting, e.g. CLEVR6
+weights trained at K = 7, T = 5 evaluated at K = 11 - and ``decode(z)`` takes K from ``z`` (iodine.py:430).  The library handle
+follows through ``iodine_set_run_shape``; ``loss.backward()`` differentiates the forward at the shape it ran with.
+
 Extensions over the reference: every entry point takes an optional ``eps`` tensor of shape
 (T+1, B, K, L) replacing the ``torch.randn_like`` draws of ``Gaussian.sample``
 (iodine.py:632) in call order, so that results can be compared with the CPU oracle.  Without
@@ -180,6 +185,7 @@ class IODINE(nn.Module):
         self._param_versions = None
         self._workspace = None
         self._ws_key = None
+        self._shape = None              # (slots, iters) the handle runs at (iodine_set_run_shape); follows self.K / self.n_iters
         self._options: Dict[str, float] = {}
         self._seed = 0                  # Philox key of the library's normal generator (manual_seed)
         self._draws = 0                 # Philox stream id: one per eps draw
@@ -219,12 +225,13 @@ class IODINE(nn.Module):
         L = _lib.lib()
         if self._handle is not None and self._handle_device != device:
             L.iodine_destroy(self._handle)
-            self._handle, self._param_versions, self._workspace, self._ws_key = None, None, None, None
+            self._handle, self._param_versions, self._workspace, self._ws_key, self._shape = None, None, None, None, None
         if self._handle is None:
             with torch.cuda.device(device):
                 h = C.c_void_p()
                 _lib.check(L.iodine_create(C.byref(self._cfg), C.byref(h)), None, 'iodine_create')
             self._handle, self._handle_device = h, device
+            self._shape = (int(self._cfg.slots), int(self._cfg.iters))
             for k, v in self._options.items():
                 if k in _WRAPPER_OPTIONS:
                     continue
@@ -313,8 +320,26 @@ class IODINE(nn.Module):
             self._param_versions = versions
         return h
 
-    def _ensure_workspace(self, h, B, mode, device):
-        key = (B, mode, device)
+    # ``model.K`` / ``model.n_iters`` are read when a call starts, as the reference reads them on every call (Gaussian.init_unit(B,
+    # self.K), get_input_encoding's repeat over K, the loops of encode / forward: iodine.py:81-83,123-126,279,312).  No parameter
+    # depends on either, so one set of weights runs at any (K, T); the library handle follows through iodine_set_run_shape.
+    def _run_shape(self, K=None, T=None):
+        """(K, T) of the call that is starting: ``self.K`` / ``self.n_iters`` unless given, checked on the host before any device work."""
+        K = self.K if K is None else K
+        T = self.n_iters if T is None else T
+        if isinstance(K, bool) or int(K) != K or not 1 <= int(K) <= 16:
+            raise ValueError(f'IODINE: the slot count (model.K) must be an integer in 1..16 - the per-pixel kernels keep every slot of '
+                             f'a pixel in registers, instantiated for K <= 16; got {K!r}')
+        if isinstance(T, bool) or int(T) != T or int(T) < 1:
+            raise ValueError(f'IODINE: the iteration count (model.n_iters) must be an integer >= 1; got {T!r}')
+        return int(K), int(T)
+
+    def _ensure_workspace(self, h, B, mode, device, K, T):
+        """Run shape (K, T) and a workspace planned for (B, mode, K, T) on the handle."""
+        if self._shape != (K, T):
+            _lib.check(_lib.lib().iodine_set_run_shape(h, K, T), h, 'iodine_set_run_shape')
+            self._shape = (K, T)
+        key = (B, mode, K, T, device)
         if self._ws_key == key:
             return
         need = _lib.lib().iodine_workspace_bytes(h, B, mode)
@@ -378,11 +403,13 @@ class IODINE(nn.Module):
         return tot.value, cnt.value
 
     # ---- inference: iodine.py:59-112 ------------------------------------------------------------
-    def max_batch(self, training: bool = False) -> int:
+    def max_batch(self, training: bool = False, K: Optional[int] = None, T: Optional[int] = None) -> int:
         """Images one library call takes: the kernels index an activation tensor [B*K][pixels][channels] with 32-bit element
         offsets (iodine_api.cpp check_ready / iodine_train_forward).  Larger batches are run in chunks of at most this many
-        images by the methods below - images are independent.  The ``batch_cap`` option lowers it (tests)."""
-        P, K, T = self.img_size * self.img_size, self.K, self.n_iters
+        images by the methods below - images are independent.  The ``batch_cap`` option lowers it (tests).
+        K / T: the shape of the call (default ``self.K`` / ``self.n_iters``)."""
+        K, T = self._run_shape(K, T)
+        P = self.img_size * self.img_size
         cd, cr = int(self._cfg.dec_conv_chan), int(self._cfg.ref_conv_chan)
         lim = ((1 << 31) - 1) // (K * P * max(cd, cr, 20))
         if training:
@@ -445,6 +472,7 @@ class IODINE(nn.Module):
 
     @torch.no_grad()
     def _reconstruct(self, x, eps, want_images=True):
+        K, T = self._run_shape()
         x = self._check_x(x)
         dev, B = x.device, x.shape[0]
         cap = self.max_batch()
@@ -458,10 +486,10 @@ class IODINE(nn.Module):
             self._merge_chunk_state(parts, sizes, x)
             return tuple(None if outs[0][j] is None else torch.cat([o[j] for o in outs], 0) for j in range(4))
         h = self._sync_params(dev)
-        self._ensure_workspace(h, B, 0, dev)
+        self._ensure_workspace(h, B, 0, dev, K, T)
         eps = self._eps(eps, B, dev)
         xs = self._stage('x', x)
-        K, L, S, T = self.K, self.dim_latent, self.img_size, self.n_iters
+        L, S = self.dim_latent, self.img_size
         pred = self._out('r.pred', (B, 3, S, S), dev) if want_images else None
         mask = self._out('r.mask', (B, K, 1, S, S), dev) if want_images else None
         mean = self._out('r.mean', (B, K, 3, S, S), dev) if want_images else None
@@ -491,16 +519,23 @@ class IODINE(nn.Module):
 
     @torch.no_grad()
     def decode(self, z):
-        """iodine.py:59-71."""
+        """iodine.py:59-71: z (B, K', L) -> pred (B,3,S,S), mask (B,K',1,S,S), mean (B,K',3,S,S).  Like the reference (iodine.py:430)
+        the slot count comes from z itself - a single slot's latent decodes alone - and ``self.K`` is left as it is."""
+        if z.dim() != 3 or z.shape[2] != self.dim_latent or not 1 <= z.shape[1] <= 16:
+            raise ValueError(f'IODINE.decode: z must have shape (B, K, {self.dim_latent}) with 1 <= K <= 16 (the per-pixel kernels are '
+                             f'instantiated for K <= 16); got {tuple(z.shape)}')
+        K = int(z.shape[1])
+        # the iteration count plays no part in a decode: keep the handle's (no workspace re-plan for it)
+        T = self._shape[1] if self._shape is not None else int(self._cfg.iters)
         z = z.detach().to(torch.float32).contiguous()
         dev, B = z.device, z.shape[0]
-        cap = self.max_batch()
+        cap = self.max_batch(K=K, T=T)
         if B > cap:
             outs = [self.decode(z[s:e]) for s, e in self._chunks(B, cap)]
             return tuple(torch.cat([o[j] for o in outs], 0) for j in range(3))
         h = self._sync_params(dev)
-        self._ensure_workspace(h, B, 0, dev)
-        K, S = self.K, self.img_size
+        self._ensure_workspace(h, B, 0, dev, K, T)
+        S = self.img_size
         z = self._stage('d.z', z)
         pred, mask, mean = self._out('r.pred', (B, 3, S, S), dev), self._out('r.mask', (B, K, 1, S, S), dev), self._out('r.mean', (B, K, 3, S, S), dev)
         self._call_serial += 1
@@ -515,6 +550,7 @@ class IODINE(nn.Module):
         decode, mixture log-likelihood minus KL.  Sets ``self.z / mean / mask / mask_logits`` and the logger entries like the
         reference.  ``eps`` (B, K, L) replaces the ``torch.randn_like`` draw.  Returns the scalar ELBO (no autograd graph:
         the gradients the reference takes from it are what reconstruct / forward compute in closed form)."""
+        K, T = self._run_shape()
         x = self._check_x(x)
         dev, B = x.device, x.shape[0]
         cap = self.max_batch()
@@ -531,8 +567,8 @@ class IODINE(nn.Module):
             self._merge_chunk_state(parts, sizes, x)
             return self.elbo_terms[0, 0]
         h = self._sync_params(dev)
-        self._ensure_workspace(h, B, 0, dev)
-        shape = (B, self.K, self.dim_latent)
+        self._ensure_workspace(h, B, 0, dev, K, T)
+        shape = (B, K, self.dim_latent)
         eps = self._normals(eps, shape, dev)
         pm, plv = self.posterior.mean, self.posterior.logvar
         if pm is None or plv is None or tuple(pm.shape) != shape or pm.device != dev:
@@ -552,7 +588,9 @@ class IODINE(nn.Module):
 
     # ---- training: iodine.py:115-158 + lib/engine/train.py:60-63 -------------------------------------
     def forward(self, x, eps=None):
-        """-sum_i (i+1)/(T+1) ELBO_i, differentiable wrt every parameter."""
+        """-sum_i (i+1)/(T+1) ELBO_i, differentiable wrt every parameter.  ``loss.backward()`` differentiates the forward as it
+        ran, at the (K, T) it read - like the reference, whose autograd graph is fixed at forward time."""
+        self._run_shape()
         x = self._check_x(x)
         if x.shape[0] > self.max_batch(training=True):
             loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, *self._ordered_params())
@@ -572,10 +610,11 @@ class IODINE(nn.Module):
 
     def _train_forward(self, x, eps):
         dev, B = x.device, x.shape[0]
+        K, T = self._run_shape()
         h = self._sync_params(dev)
-        self._ensure_workspace(h, B, 1, dev)
+        self._ensure_workspace(h, B, 1, dev, K, T)
         loss = self._out('t.loss', (), dev)
-        elbo_iter = self._out('t.elbo', (self.n_iters + 1, 3), dev)
+        elbo_iter = self._out('t.elbo', (T + 1, 3), dev)
         xs, eps = self._stage('x', x), self._stage('eps', eps)
         self._call_serial += 1
         self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward(h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps),
