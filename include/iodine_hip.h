@@ -172,6 +172,38 @@ int iodine_randn(void* stream, float* out, long long n, unsigned long long seed,
 int iodine_adam_step(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
                      double lr, double beta1, double beta2, double eps, double weight_decay, int step);
 
+/* Global-norm gradient clipping -- the line the reference carries commented out at lib/engine/train.py:64,
+ * `clip_grad_norm_(model.parameters(), 5.0)`, with the semantics of torch.nn.utils.clip_grad_norm_ at norm_type = 2.
+ * All four entries take the tables of the Adam step above (the norm and the scale read only ptrs_dev[4*t + 1], the
+ * gradient), enqueue on `stream` and return: no call synchronises, no value comes back to the host.
+ *
+ * Bytes of scratch the norm over `total` elements needs (lib/engine/train.py:64; the caller allocates and owns it: device
+ * memory, 8-byte aligned; a function of `total` alone). */
+size_t iodine_grad_norm_scratch_bytes(long long total);
+
+/* total_norm and clip coefficient of lib/engine/train.py:64: out4_dev[0] = total_norm = 2-norm of all gradients taken together,
+ * out4_dev[1] = clip_coef = min(1, max_norm / (total_norm + 1e-6)) as torch computes it, out4_dev[2] = 1 if total_norm is
+ * inf / NaN else 0, out4_dev[3] += out4_dev[2] (a running count: the caller zeroes it once).  Sums run in fp64 in a fixed
+ * order without atomics: the same gradients give the same bits on every call.  The caller owns scratch_dev (at least the
+ * bytes the entry above reports) and out4_dev (4 floats); the library keeps neither.
+ * max_norm <= 0 or NaN is IODINE_ERR_INVALID; +inf is allowed and gives clip_coef = 1.  Does not synchronise. */
+int iodine_grad_norm(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                     double max_norm, void* scratch_dev, size_t scratch_bytes, float* out4_dev);
+
+/* The in-place half of lib/engine/train.py:64, `g.mul_(clip_coef)` of torch.nn.utils.clip_grad_norm_: every gradient of the
+ * table is multiplied by *coef_dev (one float in device memory the caller owns, e.g. out4_dev + 1).  Does not synchronise. */
+int iodine_grad_scale(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                      const float* coef_dev);
+
+/* lib/engine/train.py:64-65 in one launch: the Adam step above on gradients multiplied by out4_dev[1] (the clip comes
+ * before the weight-decay term, as torch clips .grad and Adam then adds weight_decay * param; the gradients themselves are NOT
+ * rewritten).  skip_nonfinite != 0: when out4_dev[2] != 0 (non-finite norm) parameters and both moments are left untouched;
+ * 0 is torch's behaviour (NaN / inf flow into the parameters).  out4_dev is the caller's, as the norm entry wrote it
+ * earlier on the same stream.  Does not synchronise. */
+int iodine_adam_step_clipped(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                             double lr, double beta1, double beta2, double eps, double weight_decay, int step,
+                             const float* out4_dev, int skip_nonfinite);
+
 /* ARI evaluation epilogue -- lib/eval/ari_eval.py:25-39 + lib/utils/ari.py:36-52: per-pixel argmax over the K slot masks and
  * the integer contingency table[b][i][k] = |gt_i AND (argmax == k)|.  mask (B,K,1,S,S) fp32 (device, as returned by
  * iodine_reconstruct), gt (B,G,S,S) uint8 0/1 (device, padded with empty masks), table (B,G,K) int32 (device, overwritten).

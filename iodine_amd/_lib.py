@@ -24,6 +24,7 @@ EXPORTS = (
     'iodine_train_forward', 'iodine_train_backward', 'iodine_train_backward_flat', 'iodine_logger_scalars',
     'iodine_adam_step', 'iodine_ari_table', 'iodine_set_option', 'iodine_profile_read', 'iodine_debug_copy', 'iodine_linspace_host', 'iodine_op_conv3x3', 'iodine_op_dec_out',
     'iodine_op_conv3x3_wgrad', 'iodine_op_conv3x3_wgrad_f32', 'iodine_op_dec_out_f16x3', 'iodine_op_gen_conv',
+    'iodine_grad_norm_scratch_bytes', 'iodine_grad_norm', 'iodine_grad_scale', 'iodine_adam_step_clipped',
 )
 
 
@@ -87,6 +88,11 @@ def lib() -> C.CDLL:
     L.iodine_train_backward_flat.argtypes = [vp, vp, vp, vp, ci]
     L.iodine_logger_scalars.argtypes = [vp, vp, vp]
     L.iodine_adam_step.argtypes = [vp, vp, vp, ci, C.c_longlong] + [C.c_double] * 5 + [ci]
+    L.iodine_grad_norm_scratch_bytes.argtypes = [C.c_longlong]
+    L.iodine_grad_norm_scratch_bytes.restype = C.c_size_t
+    L.iodine_grad_norm.argtypes = [vp, vp, vp, ci, C.c_longlong, C.c_double, vp, C.c_size_t, vp]
+    L.iodine_grad_scale.argtypes = [vp, vp, vp, ci, C.c_longlong, vp]
+    L.iodine_adam_step_clipped.argtypes = [vp, vp, vp, ci, C.c_longlong] + [C.c_double] * 5 + [ci, vp, ci]
     L.iodine_ari_table.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
     L.iodine_set_option.argtypes = [vp, C.c_char_p, C.c_double]
     L.iodine_profile_read.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), ci]

@@ -276,7 +276,14 @@ hipError_t launch_conv3x3_tile_f16x3(hipStream_t st, const float* in, const void
                                      const float* bias, const float* aux, float* out, int N, int S, int cin, int cout,
                                      int epi, int rev = 0);
 hipError_t launch_adam_multi(hipStream_t st, const long long* ptrs, const long long* offs, int n_tensors, long long total,
-                             double lr, double beta1, double beta2, double eps, double wd, int step);
+                             double lr, double beta1, double beta2, double eps, double wd, int step,
+                             const float* out4 = nullptr, int skip_nonfinite = 0);   // out4: clipped step, see kernels_clip.hip
+// kernels_clip.hip: global gradient norm + clip coefficient over the same tables (lib/engine/train.py:64)
+size_t grad_norm_scratch_bytes(long long total);
+hipError_t launch_grad_norm(hipStream_t st, const long long* ptrs, const long long* offs, int n_tensors, long long total,
+                            double max_norm, double* partials, float* out4);
+hipError_t launch_grad_scale(hipStream_t st, const long long* ptrs, const long long* offs, int n_tensors, long long total,
+                             const float* coef_dev);
 hipError_t launch_randn_philox(hipStream_t st, float* out, long long n, unsigned long long seed, unsigned long long stream_id);
 hipError_t launch_ari_table(hipStream_t st, const float* mask, const unsigned char* gt, int B, int K, int G, int P,
                             int* table);

@@ -2019,6 +2019,45 @@ int iodine_adam_step(void* stream, const long long* ptrs_dev, const long long* o
     return IODINE_OK;
 }
 
+size_t iodine_grad_norm_scratch_bytes(long long total)
+{
+    return total < 1 ? 0 : grad_norm_scratch_bytes(total);
+}
+
+int iodine_grad_norm(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                     double max_norm, void* scratch_dev, size_t scratch_bytes, float* out4_dev)
+{
+    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || !scratch_dev || !out4_dev || !(max_norm > 0.0) ||
+        scratch_bytes < grad_norm_scratch_bytes(total) || ((uintptr_t)scratch_dev & 7)) {
+        g_create_error = "iodine_grad_norm: bad argument (max_norm must be > 0; scratch of iodine_grad_norm_scratch_bytes, 8-byte aligned)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_grad_norm((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, max_norm,
+                                          (double*)scratch_dev, out4_dev);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_grad_norm: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_grad_scale(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                      const float* coef_dev)
+{
+    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || !coef_dev) { g_create_error = "iodine_grad_scale: bad argument"; return IODINE_ERR_INVALID; }
+    const hipError_t e = launch_grad_scale((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, coef_dev);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_grad_scale: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_adam_step_clipped(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                             double lr, double beta1, double beta2, double eps, double weight_decay, int step,
+                             const float* out4_dev, int skip_nonfinite)
+{
+    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || step < 1 || !out4_dev) { g_create_error = "iodine_adam_step_clipped: bad argument"; return IODINE_ERR_INVALID; }
+    const hipError_t e = launch_adam_multi((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, lr, beta1, beta2, eps,
+                                           weight_decay, step, out4_dev, skip_nonfinite ? 1 : 0);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_adam_step_clipped: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
 int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, int batch, int slots, int n_gt, int pixels,
                      int* table)
 {

@@ -980,11 +980,21 @@ hipError_t launch_pack_dec_out(hipStream_t st, const float* w, float* wk, int C)
 // ptrs[4*t + {0,1,2,3}] = {param, grad, exp_avg, exp_avg_sq} of tensor t, offs[t] = first flat element of tensor t.
 // Arithmetic follows torch.optim.Adam (amsgrad=False, maximize=False): weight decay added to the gradient,
 // bias corrections 1 - beta^step, denom = sqrt(v) / sqrt(bc2) + eps, p -= (lr / bc1) * m / denom.
+// CLIP (kernels_clip.hip; lib/engine/train.py:64, clip_grad_norm_ in front of the step): the gradient is multiplied by the
+// coefficient launch_grad_norm left in out4[1] BEFORE the weight-decay term (torch clips .grad, Adam then adds wd * p); the
+// clipped gradient is not written back.  skip_nonfinite: a non-finite norm (out4[2] != 0) leaves p, m and v untouched.
+// CLIP = false is the arithmetic without clipping, unchanged.
 // -----------------------------------------------------------------------------------------------
+template <bool CLIP>
 __global__ void adam_multi_kernel(const long long* __restrict__ ptrs, const long long* __restrict__ offs, int n_tensors,
                                   long long total, float step_size, float beta1, float beta2, float omb1, float omb2,
-                                  float eps, float wd, float bc2_sqrt)
+                                  float eps, float wd, float bc2_sqrt, const float* __restrict__ out4, int skip_nonfinite)
 {
+    float coef = 1.f;
+    if (CLIP) {
+        if (skip_nonfinite && out4[2] != 0.f) return;
+        coef = out4[1];
+    }
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         int lo = 0, hi = n_tensors - 1;                       // last tensor whose offset <= i
         while (lo < hi) {
@@ -997,6 +1007,7 @@ __global__ void adam_multi_kernel(const long long* __restrict__ ptrs, const long
         float* m = reinterpret_cast<float*>(ptrs[4 * lo + 2]);
         float* v = reinterpret_cast<float*>(ptrs[4 * lo + 3]);
         float grad = g[j];
+        if (CLIP) grad = __fmul_rn(grad, coef);
         const float pv = p[j];
         if (wd != 0.f) grad = fmaf(wd, pv, grad);
         const float mn = fmaf(omb1, grad, beta1 * m[j]);          // exp_avg.lerp_(grad, 1 - beta1)
@@ -1008,15 +1019,21 @@ __global__ void adam_multi_kernel(const long long* __restrict__ ptrs, const long
 }
 
 hipError_t launch_adam_multi(hipStream_t st, const long long* ptrs, const long long* offs, int n_tensors, long long total,
-                             double lr, double beta1, double beta2, double eps, double wd, int step)
+                             double lr, double beta1, double beta2, double eps, double wd, int step, const float* out4,
+                             int skip_nonfinite)
 {
     // scalar prefactors in double on the host, like the Python floats torch.optim.Adam derives them from
     const double bc1 = 1.0 - pow(beta1, (double)step);
     const double bc2_sqrt = sqrt(1.0 - pow(beta2, (double)step));
     const int blocks = (int)std::min<long long>((total + 255) / 256, 2048);
-    hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, st, ptrs, offs, n_tensors, total, (float)(lr / bc1),
-                       (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)wd,
-                       (float)bc2_sqrt);
+    if (out4)
+        hipLaunchKernelGGL(adam_multi_kernel<true>, dim3(blocks), dim3(256), 0, st, ptrs, offs, n_tensors, total, (float)(lr / bc1),
+                           (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)wd,
+                           (float)bc2_sqrt, out4, skip_nonfinite);
+    else
+        hipLaunchKernelGGL(adam_multi_kernel<false>, dim3(blocks), dim3(256), 0, st, ptrs, offs, n_tensors, total, (float)(lr / bc1),
+                           (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)wd,
+                           (float)bc2_sqrt, (const float*)nullptr, 0);
     return hipGetLastError();
 }
 

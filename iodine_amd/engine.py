@@ -16,7 +16,7 @@ import torch
 from . import parallel, synth
 from .ari import ARIEvaluator
 from .checkpoint import load_checkpoint, save_checkpoint
-from .optim import make_optimizer
+from .optim import FusedAdam, _check_max_norm, clip_grad_norm_, make_optimizer
 
 
 class SyntheticScenes(torch.utils.data.Dataset):
@@ -33,9 +33,20 @@ class SyntheticScenes(torch.utils.data.Dataset):
         return torch.from_numpy(imgs[0]), torch.from_numpy(masks[0].astype('float32'))
 
 
-def train(model, optimizer, dataloader, device, max_steps, print_every=10, checkpoint_path=None, log=print):
-    """train.py:44-108: loss = model(data); loss.mean(); zero_grad; backward; [all-reduce]; step.  Returns the losses."""
+def train(model, optimizer, dataloader, device, max_steps, print_every=10, checkpoint_path=None, log=print, max_grad_norm=None):
+    """train.py:44-108: loss = model(data); loss.mean(); zero_grad; backward; [all-reduce]; [clip]; step.  Returns the losses.
+    ``max_grad_norm``: the global gradient norm is clipped at this value (train.py:64, commented out in the reference; the paper
+    uses 5.0) AFTER the all-reduce, so every rank clips the same averaged gradient with the same coefficient - what
+    ``clip_grad_norm_`` after DataParallel's reduce would do - and the replicas stay bitwise identical.  A ``FusedAdam`` takes it
+    as its ``max_grad_norm`` (fused into the step, kept on the optimizer afterwards); in front of any other optimizer
+    ``iodine_amd.optim.clip_grad_norm_`` runs.  The log line gains ``grad-norm`` (one ``.item()`` per ``print_every`` steps)."""
     model.train()
+    fused_clip = isinstance(optimizer, FusedAdam)
+    if max_grad_norm is not None:
+        max_grad_norm = _check_max_norm(max_grad_norm, 'max_grad_norm')
+        if fused_clip:
+            optimizer.max_grad_norm = max_grad_norm
+    clipping = max_grad_norm is not None or (fused_clip and optimizer.max_grad_norm is not None)
     world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
     losses, step, epoch = [], 0, 0
     while step < max_steps:
@@ -51,12 +62,17 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
             loss.backward()
             if world > 1:
                 parallel.allreduce_gradients(model.parameters())            # replaces DataParallel's reduce
+            if clipping and not fused_clip:
+                grad_norm = clip_grad_norm_(model.parameters(), max_grad_norm)
             optimizer.step()
+            if clipping and fused_clip:
+                grad_norm = optimizer.last_grad_norm
             losses.append(loss.item())
             step += 1
             if step % print_every == 0:
-                log('iter: {}, loss: {:.4f}, batch-time: {:.4f}s, lr: {}'.format(
-                    step, losses[-1], time.perf_counter() - start, optimizer.param_groups[0]['lr']))
+                log('iter: {}, loss: {:.4f}, batch-time: {:.4f}s, lr: {}{}'.format(
+                    step, losses[-1], time.perf_counter() - start, optimizer.param_groups[0]['lr'],
+                    ', grad-norm: {:.4f}'.format(grad_norm.item()) if clipping else ''))
             if step >= max_steps:
                 break
     if checkpoint_path and (not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0):
@@ -111,6 +127,8 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--batch', type=int, default=8, help='images per GPU')
     ap.add_argument('--lr', type=float, default=3e-4)                        # configs/clevr6_prop.yaml:19
+    ap.add_argument('--clip', type=float, default=None, metavar='FLOAT',
+                    help='clip the global gradient norm at this value (train.py:64; the paper uses 5.0)')
     ap.add_argument('--clevr'); ap.add_argument('--dsprites')
     ap.add_argument('--resume'); ap.add_argument('--save')
     args = ap.parse_args(argv)
@@ -125,7 +143,7 @@ def main(argv=None):
     torch.manual_seed(0)                                                     # same initial replica on every rank
     model = IODINE(arch).to(device)
     model.manual_seed(1000 + rank)                                           # ... but its own reparameterisation noise
-    optimizer = make_optimizer(model, base_lr=args.lr)
+    optimizer = make_optimizer(model, base_lr=args.lr, max_grad_norm=args.clip)
     if args.resume:
         load_checkpoint(args.resume, model, optimizer)
     if args.clevr:

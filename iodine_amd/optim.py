@@ -1,25 +1,141 @@
-"""Fused Adam over all parameters in one launch.
+"""Fused Adam over all parameters in one launch, with optional global-norm gradient clipping.
 
 Mirrors ``make_optimizer`` of the reference (lib/solver/build.py:5-16): ``torch.optim.Adam`` over every parameter
 with ``lr = TRAIN.BASE_LR`` and ``weight_decay = TRAIN.WEIGHT_DECAY``; ``optimizer.step()`` is lib/engine/train.py:65.
 The state (``exp_avg``, ``exp_avg_sq``, ``step``) and the param-group layout (one group per parameter) are torch's /
 the reference's, so ``state_dict()`` round-trips with the ``'optimizer'`` entry of a reference checkpoint
 (lib/utils/checkpoint.py:36-54; tests/golden/ckpt_tiny is one written by the reference).  No CPU / eager fallback.
+
+Clipping is the line the reference carries commented out in front of the step, ``# clip_grad_norm_(model.parameters(), 5.0)``
+(lib/engine/train.py:64; the paper clips at 5.0): ``clip_grad_norm_`` below is the stand-alone form,
+``FusedAdam(max_grad_norm=...)`` the fused one (one deterministic norm over all gradients, the coefficient read from device
+memory by the Adam kernel: no host synchronisation, no extra pass over the gradients).
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
 from . import _lib
 
+_NONFINITE = ('propagate', 'skip')
+
+
+def _check_max_norm(max_norm, what):
+    max_norm = float(max_norm)
+    if math.isnan(max_norm) or max_norm <= 0.0:
+        raise ValueError(f'{what} must be a positive number (inf allowed), got {max_norm}')
+    return max_norm
+
+
+def _check_grad(p):
+    if p.device.type != 'cuda' or p.dtype != torch.float32 or p.grad.dtype != torch.float32 or p.grad.device != p.device:
+        raise RuntimeError('FusedAdam / clip_grad_norm_ need float32 parameters and gradients on a ROCm device (no CPU fallback)')
+    if not p.grad.is_contiguous():
+        p.grad = p.grad.contiguous()
+
+
+class _GradNorm:
+    """Device buffers of the norm: the partial-sum scratch, ``out4`` = (total_norm, clip_coef, non-finite flag, count of
+    non-finite norms) and the gradient table; rebuilt only when an address or a size changes."""
+
+    def __init__(self):
+        self.out4 = None
+        self.scratch = None
+        self._cached = None
+
+    def buffers(self, dev, total):
+        if self.out4 is None or self.out4.device != dev:
+            self.out4 = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.scratch = None
+        need = _lib.lib().iodine_grad_norm_scratch_bytes(total)
+        if self.scratch is None or self.scratch.numel() * 8 < need:
+            self.scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+
+    def table(self, grads):
+        """(ptrs, offsets, total) with only the gradient column filled (the norm and the scale read nothing else)."""
+        key = tuple((g.data_ptr(), g.numel()) for g in grads)
+        if self._cached is None or self._cached[0] != key:
+            ptrs, offs, tot = [], [], 0
+            for a, n in key:
+                ptrs.extend((0, a, 0, 0)); offs.append(tot); tot += n
+            dev = grads[0].device
+            self._cached = (key, torch.tensor(ptrs, dtype=torch.int64).to(dev), torch.tensor(offs, dtype=torch.int64).to(dev), tot)
+        return self._cached[1:]
+
+    def norm(self, ptrs, offs, n, total, max_norm, dev):
+        self.buffers(dev, total)
+        rc = _lib.lib().iodine_grad_norm(C.c_void_p(torch.cuda.current_stream().cuda_stream), _lib.ptr(ptrs), _lib.ptr(offs), n,
+                                         total, max_norm, _lib.ptr(self.scratch), self.scratch.numel() * 8, _lib.ptr(self.out4))
+        _lib.check(rc, None, 'iodine_grad_norm')
+
+
+_standalone = {}        # device -> _GradNorm of clip_grad_norm_
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0):
+    """``torch.nn.utils.clip_grad_norm_`` (lib/engine/train.py:64) on ROCm tensors: a deterministic fp64 norm over all
+    gradients, ``clip_coef = min(1, max_norm / (total_norm + 1e-6))`` and ``grad *= clip_coef`` in place - three launches,
+    no host synchronisation.  Returns the total norm as a 0-dim DEVICE tensor."""
+    if float(norm_type) != 2.0:
+        raise ValueError(f'clip_grad_norm_: only norm_type = 2 is implemented, got {norm_type}')
+    max_norm = _check_max_norm(max_norm, 'max_norm')
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    ps = [p for p in parameters if p.grad is not None and p.grad.numel() > 0]
+    if not ps:
+        raise ValueError('clip_grad_norm_: no parameter has a gradient')
+    for p in ps:
+        _check_grad(p)
+    dev = ps[0].device
+    if any(p.device != dev for p in ps):
+        raise RuntimeError('clip_grad_norm_: all gradients must live on one device')
+    gn = _standalone.setdefault(dev, _GradNorm())
+    ptrs, offs, total = gn.table([p.grad for p in ps])
+    with torch.cuda.device(dev):
+        gn.norm(ptrs, offs, len(ps), total, max_norm, dev)
+        rc = _lib.lib().iodine_grad_scale(C.c_void_p(torch.cuda.current_stream().cuda_stream), _lib.ptr(ptrs), _lib.ptr(offs),
+                                          len(ps), total, C.c_void_p(gn.out4.data_ptr() + 4))
+    _lib.check(rc, None, 'iodine_grad_scale')
+    for p in ps:
+        torch.autograd.graph.increment_version(p.grad)        # written through raw pointers
+    return gn.out4[0].clone()
+
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    """``torch.optim.Adam`` (amsgrad=False, maximize=False) as one HIP launch per bucket of equal hyper-parameters.
+
+    ``max_grad_norm``: clip the global 2-norm of ALL gradients (every param group, every bucket) like
+    ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` in front of the step (lib/engine/train.py:64), fused: one norm, then
+    the Adam kernel multiplies each gradient by the coefficient it reads from device memory; ``.grad`` itself is not rewritten.
+    ``last_grad_norm`` is the norm of the last step and ``skipped_steps`` the count of non-finite norms, both device scalars
+    (views of one buffer, overwritten by the next step; reading them with ``.item()`` is the caller's synchronisation).
+    ``nonfinite='propagate'`` is torch's behaviour (NaN / inf flow into the parameters); ``'skip'`` leaves parameters and both
+    moments untouched when the norm is inf / NaN - ``state['step']`` still advances, because the host cannot know without a
+    synchronisation.  Both are attributes of the optimizer, NOT entries of ``defaults`` / ``param_groups``: ``state_dict()``
+    keeps the reference's layout."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
+                 nonfinite='propagate'):
+        if nonfinite not in _NONFINITE:
+            raise ValueError(f'nonfinite must be one of {_NONFINITE}, got {nonfinite!r}')
+        self.max_grad_norm = None if max_grad_norm is None else _check_max_norm(max_grad_norm, 'max_grad_norm')
+        self.nonfinite = nonfinite
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._tables = {}
+        self._gradnorm = _GradNorm()
+
+    @property
+    def last_grad_norm(self):
+        return None if self._gradnorm.out4 is None else self._gradnorm.out4[0]
+
+    @property
+    def skipped_steps(self):
+        return None if self._gradnorm.out4 is None else self._gradnorm.out4[3]
 
     def _table(self, gi, ps):
         """(ptrs, offsets, total) device tables for one fused bucket; rebuilt when any address changes."""
@@ -57,14 +173,36 @@ class FusedAdam(torch.optim.Optimizer):
                     st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 key = (group['lr'], tuple(group['betas']), group['eps'], group['weight_decay'], int(st['step']), p.device)
                 buckets.setdefault(key, []).append(p)
+        clip = self.max_grad_norm is not None and bool(buckets)
+        if clip:
+            # lib/engine/train.py:64: ONE norm over every gradient, in front of all buckets.  A single bucket (the reference
+            # layout) lends its table; several buckets get a table of all gradients, cached like the buckets' own.
+            every = [p for ps in buckets.values() for p in ps]
+            dev = every[0].device
+            if any(p.device != dev for p in every):
+                raise RuntimeError('FusedAdam(max_grad_norm=...): all parameters must live on one device')
+            if any(p.grad.dtype != torch.float32 or p.grad.device != dev for p in every):
+                raise RuntimeError('FusedAdam needs float32 gradients on a ROCm device (no CPU fallback)')
+            if len(buckets) == 1:
+                key = next(iter(buckets))
+                ptrs, offs, total = self._table(key[:4] + (dev,), every)
+            else:
+                ptrs, offs, total = self._gradnorm.table([p.grad for p in every])
+            with torch.cuda.device(dev):
+                self._gradnorm.norm(ptrs, offs, len(every), total, self.max_grad_norm, dev)
+            out4, skip = _lib.ptr(self._gradnorm.out4), int(self.nonfinite == 'skip')
         for key, ps in buckets.items():
             lr, (b1, b2), eps, wd, t0, dev = key
             t = t0 + 1
             ptrs, offs, total = self._table(key[:4] + (dev,), ps)
             with torch.cuda.device(dev):
-                rc = L.iodine_adam_step(C.c_void_p(torch.cuda.current_stream().cuda_stream), _lib.ptr(ptrs), _lib.ptr(offs),
-                                        len(ps), total, lr, b1, b2, eps, wd, t)
-            _lib.check(rc, None, 'iodine_adam_step')
+                stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+                if clip:
+                    rc = L.iodine_adam_step_clipped(stream, _lib.ptr(ptrs), _lib.ptr(offs), len(ps), total, lr, b1, b2, eps, wd, t,
+                                                    out4, skip)
+                else:
+                    rc = L.iodine_adam_step(stream, _lib.ptr(ptrs), _lib.ptr(offs), len(ps), total, lr, b1, b2, eps, wd, t)
+            _lib.check(rc, None, 'iodine_adam_step_clipped' if clip else 'iodine_adam_step')
             for p in ps:
                 st = self.state[p]
                 st['step'] = st['step'] + 1 if torch.is_tensor(st['step']) else t     # int steps: checkpoints of old torch
@@ -74,10 +212,11 @@ class FusedAdam(torch.optim.Optimizer):
         return loss
 
 
-def make_optimizer(model, base_lr=3e-4, weight_decay=0.0):
+def make_optimizer(model, base_lr=3e-4, weight_decay=0.0, max_grad_norm=None, nonfinite='propagate'):
     """lib/solver/build.py:5-16: Adam with one param group per parameter (``params += [{'params': [value], 'lr': lr,
     'weight_decay': weight_decay}]``), so ``optimizer.state_dict()`` has the reference's layout and the ``'optimizer'``
-    entry of a reference checkpoint (lib/utils/checkpoint.py:36-54) loads with ``load_state_dict``."""
+    entry of a reference checkpoint (lib/utils/checkpoint.py:36-54) loads with ``load_state_dict``.  ``max_grad_norm`` /
+    ``nonfinite``: lib/engine/train.py:64 fused into the step (see ``FusedAdam``); they do not enter the state dict."""
     params = [{'params': [p], 'lr': base_lr, 'weight_decay': weight_decay}
               for _, p in model.named_parameters() if p.requires_grad]
-    return FusedAdam(params, lr=base_lr)
+    return FusedAdam(params, lr=base_lr, max_grad_norm=max_grad_norm, nonfinite=nonfinite)
