@@ -224,6 +224,18 @@ int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, i
  * scale per 8 x 16 cell, 3 fp16 MFMAs, fp32 accumulate: products carry >= 22 bits relative to the CELL maximum (tile-relative,
  * not element-relative) -- default; only the selected path's weight packs are maintained, so a change must be followed by
  * iodine_set_params before the next compute call),
+ * "gen_conv_precision" (the stride-1 convs C -> C of a decoder on the GENERIC path -- DEC.KERNEL_SIZE 5 / 7 or channel counts other than
+ * 32 / 64: 0 -- default = exact fp32 MFMA (v_mfma_f32_16x16x4_f32, kernels_generic.hip); 1 = forward and data gradient on the split-fp16
+ * kernel of kernels_gensplit.hip -- fp16 hi + lo operands, one power-of-two scale per staged 16 x 16-tile halo and channel chunk and per
+ * 16-output-channel weight slice, three v_mfma_f32_16x16x32_f16 per product, fp32 accumulation -- wherever it covers the layer: kernel
+ * size 3 / 5 / 7, a channel count that is a multiple of 16, weight slice + halo within the LDS (5 x 5 up to 64 channels, 7 x 7 up to 32).
+ * The weight + bias gradient of those layers runs on the split kernel of the same file (K = pixels; up to 64 channels, 7 x 7 up to 32).
+ * Every other launch keeps its fp32 kernel without an error: uncovered shapes, the broadcast layer, the output conv C -> 4, stride-2
+ * convs.  The packs are allocations of the handle (hipMalloc in the first iodine_set_params that runs with the option at 1, kept until
+ * iodine_destroy, also after the option returns to 0: 2 x (layers - 1) x the fp32 weight bytes); they are NOT part of the workspace, so
+ * iodine_workspace_bytes is the same for both settings.  Independent of conv_precision, which keeps selecting the tuned refinement kernels beside a generic decoder;
+ * ignored by a decoder on the tuned path.  Other values: IODINE_ERR_INVALID.  Like conv_precision a change must be followed by
+ * iodine_set_params, which builds the hi / lo weight packs only while the option is 1),
  * "conv_variant" (stride-1 conv C -> C of the decoder, either precision: 6 = weight-stationary persistent kernel, weights in
  * registers -- default for power-of-two image sizes; 1 = LDS-tiled kernel, 16x16 tiles, two blocks per CU -- the fallback for
  * other sizes; like conv_precision a change must be followed by iodine_set_params),
@@ -267,8 +279,8 @@ int iodine_set_option(iodine_handle* h, const char* key, double value);
  * "pixel_pass1", "pixel_pass2", "refine_l0" (first refinement layer), "refine_l0f" (encoding + first refinement layer in one
  * kernel, option refine_l0_fused), "refine_conv" (the others), "refine_head", "refine_wgrad", "refine_dgrad", "refine_bwd01"
  * (fused layer-1 data gradient + layer-0 weight gradient, option refine_bwd_fused), "refine_bias_grad", "head_bwd", "gen_conv"
- * (the convs of the generic path), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward).  "seen:<category>" returns in *launches the number of launches of <category> since the
- * last reset, bracketed or not (option profile_stride).  Synchronises on the recorded events.  Two more names report
+ * (the fp32 convs of the generic path), "gen_conv_f16x3" (its split-fp16 launches, option gen_conv_precision 1), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward).  "seen:<category>" returns in *launches the number of launches of <category> since the
+ * last reset, bracketed or not (option profile_stride; counted at profile levels 1 -- the bracketed categories -- and 2 -- all).  Synchronises on the recorded events.  Two more names report
  * the hipGraph bookkeeping of option "graph" in *launches: "graph_captures" (graphs instantiated) and "graph_replays". */
 int iodine_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset);
 /* Copy an internal buffer of the last call (name as listed in DESIGN.md "workspace") to dst (device). */
@@ -309,7 +321,8 @@ int iodine_op_conv3x3_wgrad(void* stream, const float* in_nhwc, const float* d_n
 int iodine_op_conv3x3_wgrad_f32(void* stream, const float* in_nhwc, const float* d_nhwc, float* gw_oihw, float* gb, int n,
                                 int s, int c);
 
-/* the generic path's convolution (any odd kernel size k, any stride s in {1, 2}; kernels_generic.hip / kernels_gens2.hip), one
+/* the generic path's convolution (kernel size k in {3, 5, 7}, stride s in {1, 2} -- the library itself runs REF.STRIDE 1..8 through the
+ * same launchers, this entry point takes the two it is tested at; kernels_generic.hip / kernels_gens2.hip), one
  * direction per call - mode 0: out_nhwc [n][so][so][co] = act(bias + conv(in_nhwc [n][si][si][ldc], w_oihw [co][ci][k][k])), elu = 1
  * applies ELU; mode 1: out_nhwc [n][si][si][ci] = ELU'(aux) * data gradient of the gradient in_nhwc [n][so][so][co]; mode 2: weight +
  * bias gradient of (in_nhwc, aux = gradient [n][so][so][co]) ADDED to out_nhwc = gw [co][ci][k][k] and gb [co].  so = (si - 1) / s + 1.
@@ -318,6 +331,13 @@ int iodine_op_conv3x3_wgrad_f32(void* stream, const float* in_nhwc, const float*
  * the input AND the weights are skipped; the result must equal the unmasked call. */
 int iodine_op_gen_conv(void* stream, int mode, const float* in_nhwc, const float* w_oihw, const float* bias, const float* aux,
                        float* out_nhwc, float* gb, int n, int si, int ci, int ldc, int co, int k, int s, int elu);
+
+/* the split-fp16 form of the same (kernels_gensplit.hip, option gen_conv_precision 1), same arguments: mode 0 forward, mode 1 data
+ * gradient x ELU'(aux), mode 2 weight + bias gradient ADDED to out_nhwc = gw and gb.  IODINE_ERR_INVALID -- never the fp32 kernel -- for
+ * everything the split kernels do not cover: s != 1, ci != co, ldc != ci, a channel count that is not a multiple of 16, a slice that does
+ * not fit the LDS (7 x 7 with 64 channels).  Kernel-level tests only: it allocates, synchronises and frees per call -- not for timing. */
+int iodine_op_gen_conv_f16x3(void* stream, int mode, const float* in_nhwc, const float* w_oihw, const float* bias, const float* aux,
+                             float* out_nhwc, float* gb, int n, int si, int ci, int ldc, int co, int k, int s, int elu);
 
 #ifdef __cplusplus
 }

@@ -364,6 +364,18 @@ hipError_t launch_gen_conv_dgrad(hipStream_t st, const float* dout, const float*
 size_t gen_wgrad_scratch_floats(int Ci, int Co, int k);
 hipError_t launch_gen_conv_wgrad(hipStream_t st, const float* in, const float* dout, float* scratch, int N, int Si, int Ci, int ldc,
                                  int Ci_dst, int Co, int k, int s, float alpha, float* gw, float* gb, unsigned chmask = 0xffffffffu);
+// kernels_gensplit.hip: split-fp16 (3 x v_mfma_f32_16x16x32_f16) form of the stride-1 conv C -> C, forward and data gradient (option
+// gen_conv_precision 1).  gen_split_cch: 32 / 16 = covered (k in {3, 5, 7}, C a multiple of 16, slice + halo fit the LDS), 0 = stays on fp32
+int gen_split_cch(int k, int C);
+size_t gen_split_pack_bytes(int k, int C);                  // one direction's slice images; the scales: C / 16 floats
+hipError_t launch_gen_split_pack(hipStream_t st, const float* wt, int k, int C, int dgrad, void* dst, float* meta);
+hipError_t launch_gen_split_conv(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias, const float* aux,
+                                 float* out, int N, int S, int C, int k, int elu);
+bool gen_split_wgrad_ok(int k, int C);
+hipError_t launch_gen_split_wgrad(hipStream_t st, const float* in, const float* dout, float* scratch, int N, int S, int C, int k, float alpha,
+                                  float* gw, float* gb);
+hipError_t launch_gen_wgrad_reduce(hipStream_t st, const float* part, int nslice, int Ci, int Ci_dst, int Co, int kk, float alpha, float* gw,
+                                   float* gb);
 // kernels_genl0.hip: the spatial-broadcast layer of the generic decoder without the broadcast tensor (prefix table of per-tap latent products
 // forward, tap-window sums of the gradient backward); any odd k <= GEN_L0_KMAX
 constexpr int GEN_L0_KMAX = 7;

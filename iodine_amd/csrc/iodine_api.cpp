@@ -148,6 +148,12 @@ struct iodine_handle {
     int rs = 2;                                            // REF.STRIDE (round 6: other strides run on the generic path's kernels)
     std::vector<float*> gen_wdec, gen_wref;                // [layer]: packed weights
     float *gen_wout = nullptr, *gen_cterm = nullptr, *gen_ident = nullptr;   // output conv pack, [P][Cd] bias + coordinate term of decoder layer 0, [9 Cd][L] identity
+    // option gen_conv_precision 1 (kernels_gensplit.hip): split-fp16 slice images + per-slice inverse scales of the decoder's C -> C layers,
+    // forward / data gradient; allocated by the first iodine_set_params that needs them.  gen_split: the packs are current and the shape is covered
+    int gen_precision = 0;
+    bool gen_split = false;
+    std::vector<void*> gs_wf, gs_wb;
+    std::vector<float*> gs_mf, gs_mb;
     std::vector<float*> gacc;                   // one per parameter, reference shapes (slices of gacc_arena)
     float* gacc_arena = nullptr;
     size_t gacc_total = 0;
@@ -199,7 +205,7 @@ hipError_t conv_f16x3(const iodine_handle* h, hipStream_t st, const float* in, c
     do {                                                                             \
         hipEvent_t e0_ = nullptr, e1_ = nullptr;                                     \
         ProfCat* pc_ = nullptr;                                                      \
-        if ((h)->profile > 1) pc_ = (h)->prof_cat(cat);                              \
+        if ((h)->profile > 1) { pc_ = (h)->prof_cat(cat); pc_->seen_win++; }         \
         else if ((h)->profile == 1 && !strncmp(cat, "conv_tile_", 10)) {             \
             pc_ = (h)->prof_cat(cat);                                                \
             pc_->seen_win++;                                                         \
@@ -514,7 +520,10 @@ int decoder_forward(iodine_handle* h, hipStream_t st, int N, const float* z, flo
         PROF(h, st, "gen_l0", launch_gen_l0_fwd(st, z, h->gen_wdec[0], h->gen_cterm, b.gen_l0, b.act[0], N, h->L, h->S, h->Cd, h->kd));
         const float* in = b.act[0];
         for (int l = 1; l < h->Dd; ++l) {
-            PROF(h, st, "gen_conv", launch_gen_conv_fwd(st, in, h->gen_wdec[l], h->dec_b[l], b.act[l], N, h->S, h->Cd, h->Cd, h->Cd, h->kd, 1, 1));
+            if (h->gen_split)
+                PROF(h, st, "gen_conv_f16x3", launch_gen_split_conv(st, in, h->gs_wf[l], h->gs_mf[l], h->dec_b[l], nullptr, b.act[l], N, h->S, h->Cd, h->kd, 1));
+            else
+                PROF(h, st, "gen_conv", launch_gen_conv_fwd(st, in, h->gen_wdec[l], h->dec_b[l], b.act[l], N, h->S, h->Cd, h->Cd, h->Cd, h->kd, 1, 1));
             in = b.act[l];
         }
         PROF(h, st, "gen_conv", launch_gen_conv_fwd(st, in, h->gen_wout, h->dec_out_b, out, N, h->S, h->Cd, h->Cd, 4, h->kd, 1, 0));
@@ -576,10 +585,16 @@ int decoder_backward_generic(iodine_handle* h, hipStream_t st, int N, float trai
                                                       G("decoder.conv.weight"), G("decoder.conv.bias")));
     for (int l = Dd - 1; l > 0; --l) {
         const std::string base = "decoder.mlc.layers." + std::to_string(l);
-        if (train_alpha != 0.f)
+        if (train_alpha != 0.f && h->gen_split && gen_split_wgrad_ok(k, Cd))
+            PROF(h, st, "gen_conv_f16x3", launch_gen_split_wgrad(st, b.act[l - 1], b.dpre[cur], b.gen_scr, N, S, Cd, k, train_alpha,
+                                                                 G(base + ".weight"), G(base + ".bias")));
+        else if (train_alpha != 0.f)
             PROF(h, st, "gen_conv", launch_gen_conv_wgrad(st, b.act[l - 1], b.dpre[cur], b.gen_scr, N, S, Cd, Cd, Cd, Cd, k, 1, train_alpha,
                                                           G(base + ".weight"), G(base + ".bias")));
-        PROF(h, st, "gen_conv", launch_gen_conv_dgrad(st, b.dpre[cur], h->gen_wdec[l], b.act[l - 1], b.dpre[cur ^ 1], N, S, Cd, Cd, Cd, k, 1));
+        if (h->gen_split)
+            PROF(h, st, "gen_conv_f16x3", launch_gen_split_conv(st, b.dpre[cur], h->gs_wb[l], h->gs_mb[l], nullptr, b.act[l - 1], b.dpre[cur ^ 1], N, S, Cd, k, 0));
+        else
+            PROF(h, st, "gen_conv", launch_gen_conv_dgrad(st, b.dpre[cur], h->gen_wdec[l], b.act[l - 1], b.dpre[cur ^ 1], N, S, Cd, Cd, Cd, k, 1));
         cur ^= 1;
     }
     HIPCHK(h, hipMemsetAsync(b.Rc, 0, sizeof(float) * (size_t)N * 9 * Cd, st));
@@ -876,7 +891,7 @@ int run_graphed(iodine_handle* h, hipStream_t st, const std::vector<uintptr_t>& 
 std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, std::initializer_list<const void*> ptrs)
 {
     std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->K, (uintptr_t)h->T, (uintptr_t)h->stop_after, (uintptr_t)h->precision,
-                                (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6)),
+                                (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7)),
                                 (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own)};
     for (const void* p : ptrs) k.push_back((uintptr_t)p);
     return k;
@@ -1262,6 +1277,27 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
         HIPCHK(h, launch_gen_pack_weights(st, P("decoder.conv.weight"), 4, Cd, h->kd, h->gen_wout));
         HIPCHK(h, queue_copy(h->dec_out_b, P("decoder.conv.bias"), 4));
         HIPCHK(h, launch_gen_identity(st, h->gen_ident, 9 * Cd, L));
+        // gen_conv_precision 1: hi / lo slice images of the C -> C layers, both directions (from the packs above; stream order)
+        h->gen_split = h->gen_precision == 1 && gen_split_cch(h->kd, Cd) != 0 && h->Dd > 1;
+        if (h->gen_split) {
+            if (h->gs_wf.empty()) {
+                h->gs_wf.assign(h->Dd, nullptr); h->gs_wb.assign(h->Dd, nullptr); h->gs_mf.assign(h->Dd, nullptr); h->gs_mb.assign(h->Dd, nullptr);
+                const size_t pb = gen_split_pack_bytes(h->kd, Cd), mb = sizeof(float) * (size_t)(Cd / 16);
+                for (int l = 1; l < h->Dd; ++l)
+                    for (void** q : {&h->gs_wf[l], &h->gs_wb[l], (void**)&h->gs_mf[l], (void**)&h->gs_mb[l]}) {
+                        const hipError_t e_ = hipMalloc(q, q == &h->gs_wf[l] || q == &h->gs_wb[l] ? pb : mb);
+                        if (e_ != hipSuccess) {                            // (what was allocated stays in `owned`; the next call starts over)
+                            h->gs_wf.clear(); h->gs_wb.clear(); h->gs_mf.clear(); h->gs_mb.clear();
+                            return h->fail(IODINE_ERR_HIP, std::string("hipMalloc of the split weight packs: ") + hipGetErrorString(e_));
+                        }
+                        h->owned.push_back(*q);
+                    }
+            }
+            for (int l = 1; l < h->Dd; ++l) {
+                HIPCHK(h, launch_gen_split_pack(st, h->gen_wdec[l], h->kd, Cd, 0, h->gs_wf[l], h->gs_mf[l]));
+                HIPCHK(h, launch_gen_split_pack(st, h->gen_wdec[l], h->kd, Cd, 1, h->gs_wb[l], h->gs_mb[l]));
+            }
+        }
     }
     if (h->gen_ref) {
         for (int l = 0; l < h->Dr; ++l) {
@@ -1464,6 +1500,12 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
         if (value != 0 && value != 1) return h->fail(IODINE_ERR_INVALID, "conv_precision must be 0 (f32) or 1 (f16x3)");
         if (h->precision != (int)value) h->params_set = false;    // the other path's weight packs are not kept up to date
         h->precision = (int)value;
+        return IODINE_OK;
+    }
+    if (!strcmp(key, "gen_conv_precision")) {
+        if (value != 0 && value != 1) return h->fail(IODINE_ERR_INVALID, "gen_conv_precision must be 0 (f32) or 1 (f16x3)");
+        if (h->gen_precision != (int)value) h->params_set = false;    // the split packs are built by iodine_set_params
+        h->gen_precision = (int)value;
         return IODINE_OK;
     }
     return h->fail(IODINE_ERR_INVALID, std::string("unknown option ") + key);
@@ -2291,6 +2333,44 @@ int iodine_op_gen_conv(void* stream, int mode, const float* in, const float* w, 
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(buf);
     if (e != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_gen_conv_f16x3(void* stream, int mode, const float* in, const float* w, const float* bias, const float* aux, float* out, float* gb,
+                             int n, int si, int ci, int ldc, int co, int k, int s, int elu)
+{
+    hipStream_t st = (hipStream_t)stream;
+    // (kernel-level tests only: allocates and frees its scratch around the launches and synchronises - not an entry point to time)
+    if (mode < 0 || mode > 2 || n < 1 || si < 1) { g_create_error = "iodine_op_gen_conv_f16x3: argument"; return IODINE_ERR_INVALID; }
+    if (s != 1 || ci != co || ldc != ci || !gen_split_cch(k, ci)) {
+        g_create_error = "iodine_op_gen_conv_f16x3: shape not covered by the split kernels (stride 1, ci = co = ldc a multiple of 16, k in {3, 5, 7}, slice fits LDS)";
+        return IODINE_ERR_INVALID;
+    }
+    if (mode == 2) {
+        if (!gen_split_wgrad_ok(k, ci) || !aux || !out || !gb) {
+            g_create_error = "iodine_op_gen_conv_f16x3: mode 2 needs aux (gradient), out (gw), gb and a shape the split weight gradient covers";
+            return IODINE_ERR_INVALID;
+        }
+        float* scr = nullptr;
+        if (hipMalloc((void**)&scr, gen_wgrad_scratch_floats(ci, co, k) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+        hipError_t e2 = launch_gen_split_wgrad(st, in, aux, scr, n, si, ci, k, 1.f, out, gb);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+        (void)hipFree(scr);
+        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv_f16x3: ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
+        return IODINE_OK;
+    }
+    if (ci / 16 > 64) { g_create_error = "iodine_op_gen_conv_f16x3: channel count"; return IODINE_ERR_INVALID; }   // (the 64-float scale slot below)
+    const size_t wfl = (size_t)k * k * ci * co, pbytes = gen_split_pack_bytes(k, ci);
+    float* buf = nullptr;
+    if (hipMalloc((void**)&buf, (wfl + 64) * sizeof(float) + pbytes) != hipSuccess) return IODINE_ERR_HIP;
+    float* meta = buf + wfl;
+    void* pk = buf + wfl + 64;
+    hipError_t e = launch_gen_pack_weights(st, w, co, ci, k, buf);
+    if (e == hipSuccess) e = launch_gen_split_pack(st, buf, k, ci, mode, pk, meta);
+    if (e == hipSuccess) e = launch_gen_split_conv(st, in, pk, meta, mode == 0 ? bias : nullptr, mode == 1 ? aux : nullptr, out, n, si, ci, k, mode == 0 ? (elu & 1) : 0);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv_f16x3: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
     return IODINE_OK;
 }
 

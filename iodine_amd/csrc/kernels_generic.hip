@@ -1022,6 +1022,14 @@ hipError_t launch_gen_conv_wgrad(hipStream_t st, const float* in, const float* d
     return hipGetLastError();
 }
 
+// the fixed-order reduction of partial tiles part[slice][tap][ci][co] (+ bias partials) for weight-gradient kernels of other files
+hipError_t launch_gen_wgrad_reduce(hipStream_t st, const float* part, int nslice, int Ci, int Ci_dst, int Co, int kk, float alpha, float* gw, float* gb)
+{
+    const size_t per = (size_t)kk * Ci * Co + Co;
+    hipLaunchKernelGGL(gen_conv_wgrad_reduce_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, part, nslice, Ci, Ci_dst, Co, kk, alpha, gw, gb);
+    return hipGetLastError();
+}
+
 hipError_t launch_gen_identity(hipStream_t st, float* m, int rows, int L)
 {
     hipLaunchKernelGGL(gen_identity_kernel, dim3(gen_blocks((size_t)rows * L)), dim3(256), 0, st, m, rows, L);

@@ -118,10 +118,7 @@ def _evaluate(model, dataloader, device, evaluator):
     return evaluator
 
 
-def main(argv=None):
-    from . import IODINE
-    from .data import CLEVR, MultiDSprites, make_dataloader
-    from .model import clevr6_arch, dsprites_arch
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', choices=['clevr6', 'dsprites'], default='dsprites')
     ap.add_argument('--steps', type=int, default=50)
@@ -131,7 +128,17 @@ def main(argv=None):
                     help='clip the global gradient norm at this value (train.py:64; the paper uses 5.0)')
     ap.add_argument('--clevr'); ap.add_argument('--dsprites')
     ap.add_argument('--resume'); ap.add_argument('--save')
-    args = ap.parse_args(argv)
+    ap.add_argument('--gen-conv-precision', type=int, choices=[0, 1], default=0,
+                    help='generic decoder convs C -> C (KERNEL_SIZE 5 / 7, other channel counts): 0 = exact fp32 MFMA, '
+                         '1 = split-fp16 (3 x f16 MFMA, fp32-class accuracy) forward and data gradient')
+    return ap
+
+
+def main(argv=None):
+    from . import IODINE
+    from .data import CLEVR, MultiDSprites, make_dataloader
+    from .model import clevr6_arch, dsprites_arch
+    args = make_parser().parse_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank, local = int(os.environ.get('RANK', '0')), int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:
@@ -143,6 +150,8 @@ def main(argv=None):
     torch.manual_seed(0)                                                     # same initial replica on every rank
     model = IODINE(arch).to(device)
     model.manual_seed(1000 + rank)                                           # ... but its own reparameterisation noise
+    if args.gen_conv_precision:
+        model.set_option('gen_conv_precision', args.gen_conv_precision)
     optimizer = make_optimizer(model, base_lr=args.lr, max_grad_norm=args.clip)
     if args.resume:
         load_checkpoint(args.resume, model, optimizer)

@@ -389,7 +389,7 @@ class IODINE(nn.Module):
             return
         if self._handle is not None:
             _lib.check(_lib.lib().iodine_set_option(self._handle, key.encode(), float(value)), self._handle)
-        if key in ('conv_precision', 'conv_variant'):
+        if key in ('conv_precision', 'conv_variant', 'gen_conv_precision'):
             self._param_versions = None          # the library keeps only the selected path's weight packs: re-send the parameters
         if key == 'wgrad_accum':
             self._ws_key = None                  # the workspace plan depends on it: ask the library again
