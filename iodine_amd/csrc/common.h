@@ -181,8 +181,6 @@ int pixel_blocks_per_image(int P);
 // strict = 1 (conv_precision 0): libm expf + IEEE division in the per-pixel mixture terms (pixel_terms.h), 0: v_exp_f32 / v_rcp_f32 where bounded
 hipError_t launch_pixel_pass1(hipStream_t st, const float* x4, const float* dec, float* g, double* part, int B,
                               int K, int P, float sigma, int strict = 0);
-hipError_t launch_pixel_finalize(hipStream_t st, const double* part, int B, int K, int P, int use_ln,
-                                 float* lnstat, float* ll_img);
 // finalize + KL + batch means in one launch; counter: one zero-initialised device word per handle
 hipError_t launch_pixel_finalize_elbo(hipStream_t st, const double* part, int B, int K, int P, int use_ln, float* lnstat, float* ll_img,
                                       const float* pm, const float* plv, int L, float* img_terms, float* scal, unsigned* counter);
@@ -218,16 +216,12 @@ hipError_t launch_l0_reduce(hipStream_t st, const float* dpre, float* rows, floa
                             float* Dacc, float alpha, int first);
 hipError_t launch_dz_latent(hipStream_t st, const float* Rc, const float* wclsT, const float* pm, const float* plv,
                             const float* eps, int N, int L, int C, int use_ln, float* g_pm, float* g_plv, float* latent, int Lreal = 0);
-hipError_t launch_elbo(hipStream_t st, const float* pm, const float* plv, const float* ll_img, int B, int K, int L,
-                       float* img_terms, float* scal);
 hipError_t launch_refine_head(hipStream_t st, const float* feat, int N, int PL, int C, int H, int L,
                               const float* mlp_wT, const float* mlp_b, const float* wihT, const float* whhT,
                               const float* lstm_b, const float* wmT, const float* bm, const float* wvT, const float* bv,
                               const float* latent, const float* h_prev, const float* c_prev, float* h_out, float* c_out,
                               float* pm, float* plv, float* sv_pooled, float* sv_s, float* sv_gates, float* sv_xin,
                               float* d_mean, float* d_logvar, float* xh = nullptr, float* gp = nullptr);
-hipError_t launch_transpose(hipStream_t st, const float* src, float* dst, int R, int Cc);
-hipError_t launch_add2(hipStream_t st, const float* a, const float* b, float* o, int n);
 hipError_t launch_pack_dec_out(hipStream_t st, const float* w, float* wk, int C);
 hipError_t launch_conv3x3_gather_dgrad(hipStream_t st, const float* d, const float* wpk, const float* aux, float* out,
                                        int N, int big_h, int big_w, int c, int stride);
@@ -251,13 +245,11 @@ bool sgemm_tn_mfma_ok(int M, int N, int K);
 hipError_t launch_sgemm_tn_mfma(hipStream_t st, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
                                 float beta, float* C, int ldc, int mode, int mode_c, int a_rowmajor = 0);
 hipError_t launch_l0_tap_sums(hipStream_t st, const float* Rc, float* RT, int N, int C);
-hipError_t launch_l0_scatter_z(hipStream_t st, const float* tmp, int L, int C, float alpha, float* gw);
 hipError_t launch_l0_latent_wgrad(hipStream_t st, const float* Rc, const float* z, int N, int L, int C, float alpha, float* gw);
 hipError_t launch_l0_coord_grads(hipStream_t st, const float* D, const float* lin, int S, int C, int L, float alpha,
                                  float* gw, float* gb, float* scratch);
 hipError_t launch_loss(hipStream_t st, const float* scal, int n, float* loss);
 hipError_t launch_scale(hipStream_t st, const float* a, float alpha, float* o, int n);
-hipError_t launch_axpy(hipStream_t st, const float* x, float alpha, float* y, int n);
 hipError_t launch_axpy_dev(hipStream_t st, const float* x, float alpha, const float* alpha_dev, float* y, int n, int accumulate);
 hipError_t launch_mean2(hipStream_t st, const float* a, const float* b, int n, float* out);
 hipError_t launch_lstm_bwd_pointwise(hipStream_t st, const float* gates, const float* c0, const float* c1,
@@ -305,7 +297,7 @@ hipError_t launch_pack_dec_out_rows32(hipStream_t st, const float* w, int C, flo
 hipError_t launch_pack_conv_weights_ws(hipStream_t st, const float* src, int C, int tflip, float* meta, void* dst);
 // kernels_pack.hip: the packs above for many tensors in two launches.  kind 0 = launch_pack_conv_weights_ws(src, C = p[0], tflip = p[1]),
 // kind 1 = launch_pack_conv_weights_f16(src, O = p[0], I = p[1], cin = p[2], cout = p[3], tflip = p[4]); meta / dst as there
-// round 5: kind 2 = launch_refine_l0_pack(src, O = p[0], cinw = p[1]), kind 3 = launch_pack_dec_out_gemm(src, C = p[0]),
+// round 5: kind 2 = the two operands of kernels_refl0.hip (src [O][cinw][9], O = p[0], cinw = p[1]; scale of its own), kind 3 = launch_pack_dec_out_gemm(src, C = p[0]),
 // kind 4 = launch_pack_dec_out_dgrad(src, C = p[0]) with the scale kind 3 of the same batch leaves in the shared meta (p[1] = 1: no scale of its own)
 constexpr int PACK_BATCH_MAX = 48;
 struct PackJob { const float* src; void* dst; float* meta; int kind; int p[5]; };
@@ -405,7 +397,6 @@ hipError_t launch_conv3x3_s2_wgrad_f16x3(hipStream_t st, const float* a, const f
                                          const float* a2 = nullptr, int kdiv = 0, int f32 = 0);
 // kernels_refl0.hip: encoding (pixel_pass2's channels) + first refinement layer (conv k3 s2 17 -> 64, ELU) for all slots of an image
 size_t refine_l0_wpk_bytes(int O);
-hipError_t launch_refine_l0_pack(hipStream_t st, const float* w, int O, int cinw, float* meta, void* dst);
 bool refine_l0_fused_ok(int S, int c, int K);
 hipError_t launch_refine_l0_fused(hipStream_t st, const float* x4, const float* dec, const float* lnstat, const float* lin, const void* wk,
                                   const float* wkmeta, const void* ws, const float* wsmeta, const float* bias, float* out, float* enck,

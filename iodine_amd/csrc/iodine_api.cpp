@@ -65,6 +65,15 @@ struct Buffers {               // workspace carve-up for one batch size / mode /
     float *gen_scr = nullptr, *gen_l0 = nullptr;                // generic path: wgrad partials; layer-0 scratch (kernels_genl0.hip)
 };
 
+// index of every parameter in the parameter table (= in gacc and in the caller's pointer array), resolved once by build_param_table
+struct ParamSlots {
+    std::vector<int> ref_w, ref_b;              // refine.mlc.layers.<l>
+    int mlp_w, mlp_b, wih, whh, bih, bhh, wm, bm, wv, bv;   // the refinement head
+    std::vector<int> dec_w, dec_b;              // decoder.mlc.layers.<l>
+    int out_w, out_b;                           // decoder.conv
+    int init_mean, init_logvar;
+};
+
 }  // namespace
 
 // HIP-event profiler: when enabled every launch of a category is bracketed by two events on the
@@ -88,6 +97,7 @@ struct iodine_handle {
     int L, T, K, S, P, Cd, Dd, Cr, Dr, H;       // K / T: the RUN shape (iodine_set_run_shape; cfg.slots / cfg.iters initially) - the
                                                 // state a call leaves behind has the shape in buf.K / buf.T
     std::vector<ParamInfo> params;
+    ParamSlots slot;
     bool params_set = false;
     int stop_after = -1;
 
@@ -189,10 +199,6 @@ int g_iod_xskip = 0;
 
 namespace {
 
-hipError_t conv_f16x3(const iodine_handle* h, hipStream_t st, const float* in, const void* wpk, const void* wpk_ws,
-                      const float* wmeta, const float* bias, const float* aux, float* out, const float* tmax_in, float* tmax_out,
-                      int N, int S, int cin, int cout, int epi, int layer);
-
 #define HIPCHK(h, expr)                                                                          \
     do {                                                                                         \
         hipError_t e_ = (expr);                                                                  \
@@ -225,22 +231,139 @@ hipError_t conv_f16x3(const iodine_handle* h, hipStream_t st, const float* in, c
         if (e1_) HIPCHK(h, hipEventRecord(e1_, st));                                 \
     } while (0)
 
-bool conv_ws_ok(const iodine_handle* h) { return !h->generic && h->variant == 6 && h->precision == 1 && h->S >= 16 && (h->S & (h->S - 1)) == 0; }
-// exact-fp32 path (conv_precision 0): the weight-stationary kernel's fp32 form (v_mfma_f32_16x16x4_f32, no tile scales / side buffers) under the same
-// conditions; conv_variant 1 keeps the round-1 LDS-tiled fp32 kernels
-bool conv_ws32_ok(const iodine_handle* h) { return !h->generic && h->variant == 6 && h->precision == 0 && h->S >= 16 && (h->S & (h->S - 1)) == 0 && (h->Cd == 64 || h->Cd == 32); }
+// Which kernels the decoder runs on.  Decided here and nowhere else: the launch sites below, the packs iodine_set_params refreshes and the
+// workspace plan all switch on it, so a weight pack that is read is a pack that was written.  A function, not a cached field: the options
+// may change between calls (conv_precision / conv_variant invalidate the parameters, and the graph key holds both).
+enum DecPath {
+    DEC_GENERIC,      // kernels_generic.hip: KERNEL_SIZE other than 3, CONV_CHAN other than 32 / 64, sizes that are no multiple of 16
+    DEC_WS_F16,       // split-fp16, weight-stationary persistent kernel (conv_variant 6, power-of-two image sizes >= 16)
+    DEC_TILE_F16,     // split-fp16, LDS-tiled 16 x 16 tiles
+    DEC_WS_F32,       // exact fp32 (conv_precision 0): the weight-stationary kernel's fp32 form (v_mfma_f32_16x16x4_f32, no tile scales / side buffers)
+    DEC_TILE_F32,     // exact fp32, the round-1 LDS-tiled kernels
+};
 
-hipError_t conv_f16x3(const iodine_handle* h, hipStream_t st, const float* in, const void* wpk, const void* wpk_ws,
-                      const float* wmeta, const float* bias, const float* aux, float* out, const float* tmax_in, float* tmax_out,
-                      int N, int S, int cin, int cout, int epi, int layer)
+DecPath dec_path(const iodine_handle* h)
 {
-    if (conv_ws_ok(h) && cin == cout)
-        return launch_conv3x3_ws_f16x3(st, in, wpk_ws, wmeta, bias, aux, out, tmax_in, tmax_out, N, S, cout, epi, layer & 1);
-    // zig-zag: odd decoder layers walk the slot-images backwards (forward pass: l0 writes forwards, layer 1 reads
-    // backwards, layer 2 forwards, ...; backward pass the same by layer), so a launch starts on the part of its input
-    // that the previous launch wrote last - still in the 256 MiB Infinity Cache - instead of the part written first.
-    // Tiles are independent: results do not depend on the order.  Measured -0.3 % on the cfg3 step (same-box A/B).
-    return launch_conv3x3_tile_f16x3(st, in, wpk, wmeta, bias, aux, out, N, S, cin, cout, epi, layer & 1);
+    if (h->generic) return DEC_GENERIC;
+    const bool ws = h->variant == 6 && h->S >= 16 && (h->S & (h->S - 1)) == 0;
+    if (h->precision == 1) return ws ? DEC_WS_F16 : DEC_TILE_F16;
+    return ws && (h->Cd == 64 || h->Cd == 32) ? DEC_WS_F32 : DEC_TILE_F32;
+}
+
+bool dec_f16(DecPath p) { return p == DEC_WS_F16 || p == DEC_TILE_F16; }
+
+// The per-layer launches of the tuned decoder (layers 1 .. Dd-1 are 3x3 convs Cd -> Cd, then the output conv Cd -> 4), one switch each.
+// zig-zag (`l & 1`): odd decoder layers walk the slot-images backwards (forward pass: l0 writes forwards, layer 1 reads
+// backwards, layer 2 forwards, ...; backward pass the same by layer), so a launch starts on the part of its input
+// that the previous launch wrote last - still in the 256 MiB Infinity Cache - instead of the part written first.
+// Tiles are independent: results do not depend on the order.  Measured -0.3 % on the cfg3 step (same-box A/B).
+// The per-cell maxima (tmax_*) exist on the weight-stationary split-fp16 path only.
+int dec_conv_fwd(iodine_handle* h, hipStream_t st, int N, int l)
+{
+    Buffers& b = h->buf;
+    const int S = h->S, Cd = h->Cd;
+    switch (dec_path(h)) {
+    case DEC_WS_F16:
+        PROF(h, st, "conv_tile_fwd", launch_conv3x3_ws_f16x3(st, b.act[l - 1], h->dec_wsf[l], h->dec_wmeta[l], h->dec_b[l], nullptr, b.act[l],
+                                                             b.tmax_act[l - 1], b.tmax_act[l], N, S, Cd, EPI_BIAS_ELU, l & 1));
+        break;
+    case DEC_TILE_F16:
+        PROF(h, st, "conv_tile_fwd", launch_conv3x3_tile_f16x3(st, b.act[l - 1], h->dec_wf16[l], h->dec_wmeta[l], h->dec_b[l], nullptr, b.act[l],
+                                                               N, S, Cd, Cd, EPI_BIAS_ELU, l & 1));
+        break;
+    case DEC_WS_F32:
+        PROF(h, st, "conv_tile_fwd", launch_conv3x3_ws_f32(st, b.act[l - 1], h->dec_wsf[l], h->dec_b[l], nullptr, b.act[l], N, S, Cd, EPI_BIAS_ELU, l & 1));
+        break;
+    case DEC_TILE_F32:
+        PROF(h, st, "conv_tile_fwd", launch_conv3x3_tile(st, b.act[l - 1], h->dec_wf[l], h->dec_b[l], nullptr, b.act[l], N, S, Cd, Cd, EPI_BIAS_ELU));
+        break;
+    case DEC_GENERIC: break;                               // (decoder_forward branches off before)
+    }
+    return IODINE_OK;
+}
+
+// data gradient of layer l: b.dpre[cur] -> out with epilogue epi (EPI_MUL_ELUGRAD into b.dpre[cur ^ 1], or the broadcast layer's row sums)
+int dec_conv_dgrad(iodine_handle* h, hipStream_t st, int N, int l, int cur, float* out, int epi)
+{
+    Buffers& b = h->buf;
+    const int S = h->S, Cd = h->Cd;
+    switch (dec_path(h)) {
+    case DEC_WS_F16:
+        PROF(h, st, "conv_tile_dgrad", launch_conv3x3_ws_f16x3(st, b.dpre[cur], h->dec_wsb[l], h->dec_wmeta[l] + 2, nullptr, b.act[l - 1], out,
+                                                               b.tmax_dpre[cur], b.tmax_dpre[cur ^ 1], N, S, Cd, epi, l & 1));
+        break;
+    case DEC_TILE_F16:
+        PROF(h, st, "conv_tile_dgrad", launch_conv3x3_tile_f16x3(st, b.dpre[cur], h->dec_wb16[l], h->dec_wmeta[l] + 2, nullptr, b.act[l - 1], out,
+                                                                 N, S, Cd, Cd, epi, l & 1));
+        break;
+    case DEC_WS_F32:
+        PROF(h, st, "conv_tile_dgrad", launch_conv3x3_ws_f32(st, b.dpre[cur], h->dec_wsb[l], nullptr, b.act[l - 1], out, N, S, Cd, epi, l & 1));
+        break;
+    case DEC_TILE_F32:                                     // (never asked for the row-sum epilogues: fused_l0 in decoder_backward_data)
+        PROF(h, st, "conv_tile_dgrad", launch_conv3x3_tile(st, b.dpre[cur], h->dec_wb[l], nullptr, b.act[l - 1], out, N, S, Cd, Cd, epi));
+        break;
+    case DEC_GENERIC: break;
+    }
+    return IODINE_OK;
+}
+
+// weight / bias gradient of layer l as partial tiles: part / part_b = (accum ? part : 0) + alpha x this launch
+int dec_conv_wgrad(iodine_handle* h, hipStream_t st, int N, int l, int cur, float* part, float* part_b, float alpha, int accum,
+                   int* nparts, int* ncop, int* nb)
+{
+    Buffers& b = h->buf;
+    const int S = h->S, Cd = h->Cd;
+    switch (dec_path(h)) {
+    case DEC_WS_F16:
+    case DEC_TILE_F16:
+        PROF(h, st, "conv_tile_wgrad", launch_conv3x3_wgrad_f16x3_ws(st, b.act[l - 1], b.dpre[cur], part, part_b, N, S, Cd, Cd, nparts, ncop, nb,
+                                                                      alpha, accum));
+        break;
+    case DEC_WS_F32:
+        PROF(h, st, "conv_tile_wgrad", launch_conv3x3_wgrad_f32_ws(st, b.act[l - 1], b.dpre[cur], part, part_b, N, S, Cd, nparts, ncop, nb, alpha, accum));
+        break;
+    case DEC_TILE_F32:                                     // takes no pass factor: alpha = 1, accum = 0 only (decoder_backward_data)
+        PROF(h, st, "conv_tile_wgrad", launch_conv3x3_wgrad_tile(st, b.act[l - 1], b.dpre[cur], part, part_b, N, S, Cd, Cd, nparts, ncop, nb));
+        break;
+    case DEC_GENERIC: break;
+    }
+    return IODINE_OK;
+}
+
+// the output conv's data gradient b.g -> b.dpre[cur] on its own (inference, option out_bwd_fused 0, the exact-fp32 paths)
+int dec_out_dgrad(iodine_handle* h, hipStream_t st, int N, int cur)
+{
+    Buffers& b = h->buf;
+    const DecPath path = dec_path(h);
+    if (dec_f16(path))
+        PROF(h, st, "dec_out_dgrad", launch_dec_out_dgrad_f16x3(st, b.g, h->dec_out_wb16, h->dec_out_meta, b.act[h->Dd - 1], b.dpre[cur], N, h->S,
+                                                                 h->Cd, path == DEC_WS_F16 ? b.tmax_dpre[cur] : nullptr));
+    else
+        PROF(h, st, "dec_out_dgrad", launch_conv3x3_tile(st, b.g, h->dec_out_wb, nullptr, b.act[h->Dd - 1], b.dpre[cur], N, h->S, 4, h->Cd,
+                                                         EPI_MUL_ELUGRAD));
+    return IODINE_OK;
+}
+
+// ... and its weight / bias gradient as partial tiles (none of these kernels takes a pass factor); *ncop: padded output channels of a tile
+int dec_out_wgrad(iodine_handle* h, hipStream_t st, int N, float* part, float* part_b, int* nparts, int* ncop, int* nb)
+{
+    Buffers& b = h->buf;
+    const float* a = b.act[h->Dd - 1];
+    *ncop = 4;
+    switch (dec_path(h)) {
+    case DEC_WS_F16:
+    case DEC_TILE_F16:                                     // GEMM form: rows (tap, co), no N = 4 -> 32 padding
+        PROF(h, st, "dec_out_wgrad", launch_dec_out_wgrad_gemm_f16x3(st, a, b.g, part, part_b, N, h->S, h->Cd, nparts, nb));
+        break;
+    case DEC_WS_F32:                                       // exact fp32, GEMM form (kernels_wgrad32.hip)
+        PROF(h, st, "dec_out_wgrad", launch_dec_out_wgrad_f32(st, a, b.g, part, part_b, N, h->S, h->Cd, nparts, nb));
+        break;
+    case DEC_TILE_F32:
+        PROF(h, st, "dec_out_wgrad", launch_conv3x3_wgrad_tile(st, a, b.g, part, part_b, N, h->S, h->Cd, 4, nparts, ncop, nb));
+        break;
+    case DEC_GENERIC: break;
+    }
+    return IODINE_OK;
 }
 
 template <typename T>
@@ -256,47 +379,43 @@ void build_param_table(iodine_handle* h)
 {
     // names / shapes of the reference module tree in named_parameters() order
     // (iodine.py:26-33, 412-423, 446-464, 543-557, 570-584, 596-604)
+    // (returns the parameter's index: h->slot keeps it, so nothing downstream looks a parameter up by name)
     auto add = [&](const std::string& n, std::initializer_list<long long> d) {
         ParamInfo p; p.name = n; p.ndim = (int)d.size(); int i = 0;
         for (long long v : d) p.dims[i++] = v;
         for (; i < 4; ++i) p.dims[i] = 1;
         h->params.push_back(p);
+        return (int)h->params.size() - 1;
     };
     const iodine_config& c = h->cfg;
+    ParamSlots& s = h->slot;
     int cin = h->n_in;
     for (int i = 0; i < c.ref_conv_layers; ++i) {
-        add("refine.mlc.layers." + std::to_string(i) + ".weight", {c.ref_conv_chan, cin, c.ref_kernel_size, c.ref_kernel_size});
-        add("refine.mlc.layers." + std::to_string(i) + ".bias", {c.ref_conv_chan});
+        s.ref_w.push_back(add("refine.mlc.layers." + std::to_string(i) + ".weight", {c.ref_conv_chan, cin, c.ref_kernel_size, c.ref_kernel_size}));
+        s.ref_b.push_back(add("refine.mlc.layers." + std::to_string(i) + ".bias", {c.ref_conv_chan}));
         cin = c.ref_conv_chan;
     }
     const long long H = c.ref_mlp_units, L = c.dim_latent;
-    add("refine.mlp.layers.0.weight", {H, c.ref_conv_chan});
-    add("refine.mlp.layers.0.bias", {H});
-    add("refine.lstm.weight_ih", {4 * H, H + 4 * L});
-    add("refine.lstm.weight_hh", {4 * H, H});
-    add("refine.lstm.bias_ih", {4 * H});
-    add("refine.lstm.bias_hh", {4 * H});
-    add("refine.mean_update.weight", {L, H});
-    add("refine.mean_update.bias", {L});
-    add("refine.logvar_update.weight", {L, H});
-    add("refine.logvar_update.bias", {L});
+    s.mlp_w = add("refine.mlp.layers.0.weight", {H, c.ref_conv_chan});
+    s.mlp_b = add("refine.mlp.layers.0.bias", {H});
+    s.wih = add("refine.lstm.weight_ih", {4 * H, H + 4 * L});
+    s.whh = add("refine.lstm.weight_hh", {4 * H, H});
+    s.bih = add("refine.lstm.bias_ih", {4 * H});
+    s.bhh = add("refine.lstm.bias_hh", {4 * H});
+    s.wm = add("refine.mean_update.weight", {L, H});
+    s.bm = add("refine.mean_update.bias", {L});
+    s.wv = add("refine.logvar_update.weight", {L, H});
+    s.bv = add("refine.logvar_update.bias", {L});
     cin = c.dim_latent + 2;
     for (int i = 0; i < c.dec_conv_layers; ++i) {
-        add("decoder.mlc.layers." + std::to_string(i) + ".weight", {c.dec_conv_chan, cin, c.dec_kernel_size, c.dec_kernel_size});
-        add("decoder.mlc.layers." + std::to_string(i) + ".bias", {c.dec_conv_chan});
+        s.dec_w.push_back(add("decoder.mlc.layers." + std::to_string(i) + ".weight", {c.dec_conv_chan, cin, c.dec_kernel_size, c.dec_kernel_size}));
+        s.dec_b.push_back(add("decoder.mlc.layers." + std::to_string(i) + ".bias", {c.dec_conv_chan}));
         cin = c.dec_conv_chan;
     }
-    add("decoder.conv.weight", {4, c.dec_conv_chan, c.dec_kernel_size, c.dec_kernel_size});
-    add("decoder.conv.bias", {4});
-    add("posterior.init_mean", {L});
-    add("posterior.init_logvar", {L});
-}
-
-int param_index(const iodine_handle* h, const std::string& name)
-{
-    for (size_t i = 0; i < h->params.size(); ++i)
-        if (h->params[i].name == name) return (int)i;
-    return -1;
+    s.out_w = add("decoder.conv.weight", {4, c.dec_conv_chan, c.dec_kernel_size, c.dec_kernel_size});
+    s.out_b = add("decoder.conv.bias", {4});
+    s.init_mean = add("posterior.init_mean", {L});
+    s.init_logvar = add("posterior.init_logvar", {L});
 }
 
 std::string validate(const iodine_config& c)
@@ -339,6 +458,7 @@ bool refine_f16_ok(const iodine_handle* h);
 void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
 {
     const int N = B * h->K, P = h->P, L = h->L, Cd = h->Cd, Cr = h->Cr, H = h->H, T = h->T;
+    const bool gen_dec = dec_path(h) == DEC_GENERIC;
     b.B = B; b.mode = mode; b.K = h->K; b.T = h->T;
     b.x4 = a.take<float>((size_t)B * P * 4);
     b.V = a.take<float>((size_t)N * 9 * Cd);
@@ -431,7 +551,7 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
         b.wg_part = a.take<float>(part_elems);
         b.wg_part_b = a.take<float>((size_t)512 * 64);
         b.wg_acc.assign(h->Dd, nullptr); b.wg_acc_b.assign(h->Dd, nullptr);
-        if (h->wgrad_accum && !h->generic) {
+        if (h->wgrad_accum && !gen_dec) {
             b.wg_acc[0] = a.take<float>((size_t)1024 * 2 * 9 * Cd * 4);       // dec_out_bwd_fused: <= 1024 blocks x KS <= 2 tiles of [9][Cd][4]
             b.wg_acc_b[0] = a.take<float>((size_t)1024 * 4);
             for (int l = 1; l < h->Dd; ++l) {
@@ -456,12 +576,12 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
         int s = h->S;
         for (int l = 0; l < h->Dr; ++l) { s = ref_out_size(h, s); b.rdpre[l] = a.take<float>((size_t)T * N * s * s * Cr); }
     }
-    if (h->generic) {
+    if (gen_dec) {
         b.gen_l0 = a.take<float>(gen_l0_scratch_floats(N, h->S, Cd, h->kd));   // row / tap sums, prefix table of the broadcast layer
     }
-    if ((h->generic || h->gen_ref) && mode == 1) {
+    if ((gen_dec || h->gen_ref) && mode == 1) {
         size_t scr = 0;
-        if (h->generic) scr = std::max(gen_wgrad_scratch_floats(Cd, 4, h->kd), gen_wgrad_scratch_floats(Cd, Cd, h->kd));
+        if (gen_dec) scr = std::max(gen_wgrad_scratch_floats(Cd, 4, h->kd), gen_wgrad_scratch_floats(Cd, Cd, h->kd));
         if (h->gen_ref) scr = std::max(scr, std::max(gen_wgrad_scratch_floats(17, Cr, h->kr), gen_wgrad_scratch_floats(Cr, Cr, h->kr)));
         b.gen_scr = a.take<float>(scr);
     }
@@ -514,7 +634,8 @@ int decoder_forward(iodine_handle* h, hipStream_t st, int N, const float* z, flo
 {
     Buffers& b = h->buf;
     if (!out) out = b.dec_out;
-    if (h->generic) {
+    const DecPath path = dec_path(h);
+    if (path == DEC_GENERIC) {
         // fallback: the broadcast layer from the prefix table of its per-tap latent products (kernels_genl0.hip: the broadcast tensor is
         // never built), every other layer a generic fp32 conv (kernels_generic.hip)
         PROF(h, st, "gen_l0", launch_gen_l0_fwd(st, z, h->gen_wdec[0], h->gen_cterm, b.gen_l0, b.act[0], N, h->L, h->S, h->Cd, h->kd));
@@ -529,40 +650,19 @@ int decoder_forward(iodine_handle* h, hipStream_t st, int N, const float* z, flo
         PROF(h, st, "gen_conv", launch_gen_conv_fwd(st, in, h->gen_wout, h->dec_out_b, out, N, h->S, h->Cd, h->Cd, 4, h->kd, 1, 0));
         return IODINE_OK;
     }
-    const bool ws = conv_ws_ok(h);
-    PROF(h, st, "dec_l0", launch_dec_l0(st, b.V, h->cmap, b.act[0], N, h->S, h->Cd, ws ? b.tmax_act[0] : nullptr));
-    for (int l = 1; l < h->Dd; ++l) {
-        if (h->precision == 1)
-            PROF(h, st, "conv_tile_fwd", conv_f16x3(h, st, b.act[l - 1], h->dec_wf16[l], h->dec_wsf[l], h->dec_wmeta[l], h->dec_b[l],
-                                                    nullptr, b.act[l], b.tmax_act[l - 1], b.tmax_act[l], N, h->S, h->Cd, h->Cd,
-                                                    EPI_BIAS_ELU, l));
-        else if (conv_ws32_ok(h))
-            PROF(h, st, "conv_tile_fwd", launch_conv3x3_ws_f32(st, b.act[l - 1], h->dec_wsf[l], h->dec_b[l], nullptr, b.act[l], N, h->S, h->Cd,
-                                                               EPI_BIAS_ELU, l & 1));
-        else
-            PROF(h, st, "conv_tile_fwd", launch_conv3x3_tile(st, b.act[l - 1], h->dec_wf[l], h->dec_b[l], nullptr,
-                                                             b.act[l], N, h->S, h->Cd, h->Cd, EPI_BIAS_ELU));
-    }
-    if (h->precision == 1 && h->dec_out_rows && ws && dec_out_rows_ok(h->S, h->Cd, b.tmax_act[h->Dd - 1]))
-        PROF(h, st, "dec_out", launch_dec_out_rows_f16x3(st, b.act[h->Dd - 1], h->dec_out_w16, h->dec_out_meta, h->dec_out_b, out, N, h->S, h->Cd,
-                                                         b.tmax_act[h->Dd - 1]));
-    else if (h->precision == 1)
-        PROF(h, st, "dec_out", launch_dec_out_stream_f16x3(st, b.act[h->Dd - 1], h->dec_out_w16, h->dec_out_meta, h->dec_out_b, out, N, h->S,
-                                                           h->Cd, ws ? b.tmax_act[h->Dd - 1] : nullptr));
-    else if (h->dec_out_rows && dec_out_rows_ok(h->S, h->Cd, b.act[h->Dd - 1]) && h->dec_out_w32)      // exact fp32 MFMA, row-streaming
-        PROF(h, st, "dec_out", launch_dec_out_rows_f16x3(st, b.act[h->Dd - 1], h->dec_out_w32, nullptr, h->dec_out_b, out, N, h->S, h->Cd, nullptr, 1));
+    const float* last = b.act[h->Dd - 1];
+    const float* tmax = path == DEC_WS_F16 ? b.tmax_act[h->Dd - 1] : nullptr;
+    PROF(h, st, "dec_l0", launch_dec_l0(st, b.V, h->cmap, b.act[0], N, h->S, h->Cd, path == DEC_WS_F16 ? b.tmax_act[0] : nullptr));
+    for (int l = 1; l < h->Dd; ++l)
+        if (int rc = dec_conv_fwd(h, st, N, l)) return rc;
+    if (path == DEC_WS_F16 && h->dec_out_rows && dec_out_rows_ok(h->S, h->Cd, tmax))
+        PROF(h, st, "dec_out", launch_dec_out_rows_f16x3(st, last, h->dec_out_w16, h->dec_out_meta, h->dec_out_b, out, N, h->S, h->Cd, tmax));
+    else if (dec_f16(path))
+        PROF(h, st, "dec_out", launch_dec_out_stream_f16x3(st, last, h->dec_out_w16, h->dec_out_meta, h->dec_out_b, out, N, h->S, h->Cd, tmax));
+    else if (h->dec_out_rows && dec_out_rows_ok(h->S, h->Cd, last) && h->dec_out_w32)      // exact fp32 MFMA, row-streaming
+        PROF(h, st, "dec_out", launch_dec_out_rows_f16x3(st, last, h->dec_out_w32, nullptr, h->dec_out_b, out, N, h->S, h->Cd, nullptr, 1));
     else
-        PROF(h, st, "dec_out", launch_dec_out(st, b.act[h->Dd - 1], h->dec_out_w, h->dec_out_b, out, N, h->S, h->Cd));
-    return IODINE_OK;
-}
-
-// reduce the partial tiles of the last wgrad launch into the accumulators of (weight, bias)
-int reduce_wgrad(iodine_handle* h, hipStream_t st, int nparts, int ci_pad, int co_pad, int O_real, int I_real,
-                 int I_dst, float alpha, int wparam, int bparam, int nbias_parts)
-{
-    Buffers& b = h->buf;
-    HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, ci_pad, co_pad, O_real, I_real, I_dst, alpha, h->gacc[wparam], b.wg_fold,
-                                  b.wg_part_b, nbias_parts, h->gacc[bparam]));
+        PROF(h, st, "dec_out", launch_dec_out(st, last, h->dec_out_w, h->dec_out_b, out, N, h->S, h->Cd));
     return IODINE_OK;
 }
 
@@ -576,21 +676,19 @@ int reduce_wgrad(iodine_handle* h, hipStream_t st, int nparts, int ci_pad, int c
 int decoder_backward_generic(iodine_handle* h, hipStream_t st, int N, float train_alpha, int it)
 {
     Buffers& b = h->buf;
+    const ParamSlots& ps = h->slot;
     const int Cd = h->Cd, Dd = h->Dd, L = h->L, S = h->S, k = h->kd;
-    auto G = [&](const std::string& name) { return h->gacc[param_index(h, name)]; };
     int cur = 0;
     PROF(h, st, "gen_conv", launch_gen_conv_dgrad(st, b.g, h->gen_wout, b.act[Dd - 1], b.dpre[cur], N, S, Cd, Cd, 4, k, 1));
     if (train_alpha != 0.f)
         PROF(h, st, "gen_conv", launch_gen_conv_wgrad(st, b.act[Dd - 1], b.g, b.gen_scr, N, S, Cd, Cd, Cd, 4, k, 1, train_alpha,
-                                                      G("decoder.conv.weight"), G("decoder.conv.bias")));
+                                                      h->gacc[ps.out_w], h->gacc[ps.out_b]));
     for (int l = Dd - 1; l > 0; --l) {
-        const std::string base = "decoder.mlc.layers." + std::to_string(l);
+        float *gw = h->gacc[ps.dec_w[l]], *gb = h->gacc[ps.dec_b[l]];
         if (train_alpha != 0.f && h->gen_split && gen_split_wgrad_ok(k, Cd))
-            PROF(h, st, "gen_conv_f16x3", launch_gen_split_wgrad(st, b.act[l - 1], b.dpre[cur], b.gen_scr, N, S, Cd, k, train_alpha,
-                                                                 G(base + ".weight"), G(base + ".bias")));
+            PROF(h, st, "gen_conv_f16x3", launch_gen_split_wgrad(st, b.act[l - 1], b.dpre[cur], b.gen_scr, N, S, Cd, k, train_alpha, gw, gb));
         else if (train_alpha != 0.f)
-            PROF(h, st, "gen_conv", launch_gen_conv_wgrad(st, b.act[l - 1], b.dpre[cur], b.gen_scr, N, S, Cd, Cd, Cd, Cd, k, 1, train_alpha,
-                                                          G(base + ".weight"), G(base + ".bias")));
+            PROF(h, st, "gen_conv", launch_gen_conv_wgrad(st, b.act[l - 1], b.dpre[cur], b.gen_scr, N, S, Cd, Cd, Cd, Cd, k, 1, train_alpha, gw, gb));
         if (h->gen_split)
             PROF(h, st, "gen_conv_f16x3", launch_gen_split_conv(st, b.dpre[cur], h->gs_wb[l], h->gs_mb[l], nullptr, b.act[l - 1], b.dpre[cur ^ 1], N, S, Cd, k, 0));
         else
@@ -599,118 +697,67 @@ int decoder_backward_generic(iodine_handle* h, hipStream_t st, int N, float trai
     }
     HIPCHK(h, hipMemsetAsync(b.Rc, 0, sizeof(float) * (size_t)N * 9 * Cd, st));
     PROF(h, st, "gen_l0", launch_gen_l0_bwd(st, b.dpre[cur], b.z[it], h->gen_wdec[0], h->lin, b.gen_l0, N, L, S, Cd, k, train_alpha,
-                                            G("decoder.mlc.layers.0.weight"), G("decoder.mlc.layers.0.bias"), b.Rc, 9 * Cd));
+                                            h->gacc[ps.dec_w[0]], h->gacc[ps.dec_b[0]], b.Rc, 9 * Cd));
     return IODINE_OK;
 }
+
+// where one weight-gradient launch of a decoder pass leaves its partial tiles and when they are reduced.  Option wgrad_accum (round 5): a
+// block's partial tile accumulates alpha_i x (pass i) in a per-layer buffer and is reduced once, after the last pass (it == T); otherwise
+// the shared scratch, reduced with the pass factor straight away
+struct WgradPass { float *part, *part_b; float alpha; int accum; float reduce_alpha; bool reduce; };
 
 int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0, float train_alpha, int it)
 {
     Buffers& b = h->buf;
+    const ParamSlots& ps = h->slot;
     const int Cd = h->Cd, Dd = h->Dd;
-    if (h->generic) { *dpre0 = nullptr; return decoder_backward_generic(h, st, N, train_alpha, it); }
-    int cur = 0, nparts = 0, ncop = 0, nb = 0, rc;
-    bool fused_l0 = false;
+    const DecPath path = dec_path(h);
+    if (path == DEC_GENERIC) { *dpre0 = nullptr; return decoder_backward_generic(h, st, N, train_alpha, it); }
+    const bool train = train_alpha != 0.f;
+    int cur = 0, nparts = 0, ncop = 4, nb = 0, rc;
     // training: one pass over the last hidden activation gives the data gradient AND the weight / bias gradient
-    const bool out_fused = train_alpha != 0.f && h->precision == 1 && h->out_bwd_fused;
-    // round 5: a block's partial tile accumulates alpha_i x (pass i) in a per-layer buffer; reduced once, after the last pass (it == T)
-    const bool acc_w = train_alpha != 0.f && h->wgrad_accum && !b.wg_acc.empty() && b.wg_acc[0];
+    const bool out_fused = train && dec_f16(path) && h->out_bwd_fused;
+    const bool acc_w = train && h->wgrad_accum && !b.wg_acc.empty() && b.wg_acc[0];
+    auto wgrad_pass = [&](bool acc, int l) {
+        return acc ? WgradPass{b.wg_acc[l], b.wg_acc_b[l], train_alpha, it != 0, 1.f, it == h->T}
+                   : WgradPass{b.wg_part, b.wg_part_b, 1.f, 0, train_alpha, true};
+    };
+    // output conv: only the fused kernel takes a pass factor, so the separate weight-gradient kernels reduce per pass
+    WgradPass wp = wgrad_pass(acc_w && out_fused, 0);
 #ifdef IODINE_XSKIP_HOOK
     if (!(g_iod_xskip & 256))
 #endif
-    if (out_fused) {
-        const int wi = param_index(h, "decoder.conv.weight"), bi = param_index(h, "decoder.conv.bias");
-        if (acc_w) {
-            PROF(h, st, "dec_out_bwd", launch_dec_out_bwd_fused_f16x3(st, b.act[Dd - 1], b.g, h->dec_out_wb16, h->dec_out_meta,
-                                                                       b.dpre[cur], conv_ws_ok(h) ? b.tmax_dpre[cur] : nullptr,
-                                                                       b.wg_acc[0], b.wg_acc_b[0], N, h->S, Cd, &nparts, &nb, train_alpha, it != 0));
-            if (it == h->T)
-                HIPCHK(h, launch_wgrad_reduce(st, b.wg_acc[0], nparts, Cd, 4, 4, Cd, Cd, 1.f, h->gacc[wi], b.wg_fold, b.wg_acc_b[0], nb, h->gacc[bi]));
-        } else {
-        PROF(h, st, "dec_out_bwd", launch_dec_out_bwd_fused_f16x3(st, b.act[Dd - 1], b.g, h->dec_out_wb16, h->dec_out_meta,
-                                                                   b.dpre[cur], conv_ws_ok(h) ? b.tmax_dpre[cur] : nullptr,
-                                                                   b.wg_part, b.wg_part_b, N, h->S, Cd, &nparts, &nb));
-        HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, Cd, 4, 4, Cd, Cd, train_alpha, h->gacc[wi], b.wg_fold,
-                                      b.wg_part_b, nb, h->gacc[bi]));
-        }
-    } else
-    {
-        if (h->precision == 1)
-            PROF(h, st, "dec_out_dgrad", launch_dec_out_dgrad_f16x3(st, b.g, h->dec_out_wb16, h->dec_out_meta, b.act[Dd - 1],
-                                                                     b.dpre[cur], N, h->S, Cd, conv_ws_ok(h) ? b.tmax_dpre[cur] : nullptr));
-        else {
-            PROF(h, st, "dec_out_dgrad", launch_conv3x3_tile(st, b.g, h->dec_out_wb, nullptr, b.act[Dd - 1], b.dpre[cur], N,
-                                                             h->S, 4, Cd, EPI_MUL_ELUGRAD));
-            // the generic kernel leaves no per-cell max for the weight-stationary conv that consumes its output
-            if (conv_ws_ok(h)) HIPCHK(h, launch_cell_max(st, b.dpre[cur], b.tmax_dpre[cur], N, h->S, Cd));
-        }
-    }
-    if (train_alpha != 0.f && !out_fused) {
-        const int wi = param_index(h, "decoder.conv.weight"), bi = param_index(h, "decoder.conv.bias");
-        if (h->precision == 1) {                           // GEMM form: rows (tap, co), no N = 4 -> 32 padding
-            PROF(h, st, "dec_out_wgrad", launch_dec_out_wgrad_gemm_f16x3(st, b.act[Dd - 1], b.g, b.wg_part, b.wg_part_b, N, h->S,
-                                                                          Cd, &nparts, &nb));
-            HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, Cd, 4, 4, Cd, Cd, train_alpha, h->gacc[wi], b.wg_fold,
-                                          b.wg_part_b, nb, h->gacc[bi]));
-        } else if (conv_ws32_ok(h)) {                      // exact fp32, GEMM form (kernels_wgrad32.hip)
-            PROF(h, st, "dec_out_wgrad", launch_dec_out_wgrad_f32(st, b.act[Dd - 1], b.g, b.wg_part, b.wg_part_b, N, h->S, Cd, &nparts, &nb));
-            HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, Cd, 4, 4, Cd, Cd, train_alpha, h->gacc[wi], b.wg_fold,
-                                          b.wg_part_b, nb, h->gacc[bi]));
-        } else {
-            PROF(h, st, "dec_out_wgrad", launch_conv3x3_wgrad_tile(st, b.act[Dd - 1], b.g, b.wg_part, b.wg_part_b, N,
-                                                                    h->S, Cd, 4, &nparts, &ncop, &nb));
-            rc = reduce_wgrad(h, st, nparts, Cd, ncop, 4, Cd, Cd, train_alpha, wi, bi, nb);
-            if (rc) return rc;
-        }
-    }
+    if (out_fused)
+        PROF(h, st, "dec_out_bwd", launch_dec_out_bwd_fused_f16x3(st, b.act[Dd - 1], b.g, h->dec_out_wb16, h->dec_out_meta, b.dpre[cur],
+                                                                   path == DEC_WS_F16 ? b.tmax_dpre[cur] : nullptr, wp.part, wp.part_b,
+                                                                   N, h->S, Cd, &nparts, &nb, wp.alpha, wp.accum));
+    else if ((rc = dec_out_dgrad(h, st, N, cur)))
+        return rc;
+    if (train && !out_fused && (rc = dec_out_wgrad(h, st, N, wp.part, wp.part_b, &nparts, &ncop, &nb))) return rc;
+    if (train && wp.reduce)
+        HIPCHK(h, launch_wgrad_reduce(st, wp.part, nparts, Cd, ncop, 4, Cd, Cd, wp.reduce_alpha, h->gacc[ps.out_w], b.wg_fold, wp.part_b, nb,
+                                      h->gacc[ps.out_b]));
+    bool fused_l0 = false;
     for (int l = Dd - 1; l >= 1; --l) {
-        if (train_alpha != 0.f && acc_w && (h->precision == 1 || conv_ws32_ok(h))) {
-            if (h->precision == 1)
-                PROF(h, st, "conv_tile_wgrad", launch_conv3x3_wgrad_f16x3_ws(st, b.act[l - 1], b.dpre[cur], b.wg_acc[l], b.wg_acc_b[l], N, h->S, Cd, Cd,
-                                                                              &nparts, &ncop, &nb, train_alpha, it != 0));
-            else
-                PROF(h, st, "conv_tile_wgrad", launch_conv3x3_wgrad_f32_ws(st, b.act[l - 1], b.dpre[cur], b.wg_acc[l], b.wg_acc_b[l], N, h->S, Cd,
-                                                                            &nparts, &ncop, &nb, train_alpha, it != 0));
-            if (it == h->T) {
-                const std::string base = "decoder.mlc.layers." + std::to_string(l);
-                HIPCHK(h, launch_wgrad_reduce(st, b.wg_acc[l], nparts, Cd, ncop, Cd, Cd, Cd, 1.f, h->gacc[param_index(h, base + ".weight")], b.wg_fold,
-                                              b.wg_acc_b[l], nb, h->gacc[param_index(h, base + ".bias")]));
-            }
-        } else if (train_alpha != 0.f) {
-            if (h->precision == 1)
-                PROF(h, st, "conv_tile_wgrad", launch_conv3x3_wgrad_f16x3_ws(st, b.act[l - 1], b.dpre[cur], b.wg_part,
-                                                                              b.wg_part_b, N, h->S, Cd, Cd, &nparts, &ncop, &nb));
-            else if (conv_ws32_ok(h))
-                PROF(h, st, "conv_tile_wgrad", launch_conv3x3_wgrad_f32_ws(st, b.act[l - 1], b.dpre[cur], b.wg_part, b.wg_part_b, N, h->S, Cd,
-                                                                            &nparts, &ncop, &nb));
-            else
-                PROF(h, st, "conv_tile_wgrad", launch_conv3x3_wgrad_tile(st, b.act[l - 1], b.dpre[cur], b.wg_part,
-                                                                          b.wg_part_b, N, h->S, Cd, Cd, &nparts, &ncop, &nb));
-            const std::string base = "decoder.mlc.layers." + std::to_string(l);
-            rc = reduce_wgrad(h, st, nparts, Cd, ncop, Cd, Cd, Cd, train_alpha, param_index(h, base + ".weight"),
-                              param_index(h, base + ".bias"), nb);
-            if (rc) return rc;
+        if (train) {
+            wp = wgrad_pass(acc_w && path != DEC_TILE_F32, l);      // (the LDS-tiled fp32 kernel takes no pass factor)
+            if ((rc = dec_conv_wgrad(h, st, N, l, cur, wp.part, wp.part_b, wp.alpha, wp.accum, &nparts, &ncop, &nb))) return rc;
+            if (wp.reduce)
+                HIPCHK(h, launch_wgrad_reduce(st, wp.part, nparts, Cd, ncop, Cd, Cd, Cd, wp.reduce_alpha, h->gacc[ps.dec_w[l]], b.wg_fold,
+                                              wp.part_b, nb, h->gacc[ps.dec_b[l]]));
         }
         // Inference: nothing but the broadcast layer's row / class sums needs d(pre-activation 0), so the last data gradient
         // reduces its tile to per-row sums in its epilogue (EPI_L0ROWS) and the 0.94 GB tensor is neither written nor re-read.
         // Training: the same with one more sum per row (EPI_L0ROWSX, weight-stationary kernel only): class sums for dz and the
         // latent-channel weights, slot-summed row sums for the coordinate-channel weights and the bias.
-        fused_l0 = l == 1 && h->fuse_l0 && (h->precision == 1 ? (train_alpha == 0.f || conv_ws_ok(h)) : conv_ws32_ok(h));
-        if (h->precision == 1)
-            PROF(h, st, "conv_tile_dgrad", conv_f16x3(h, st, b.dpre[cur], h->dec_wb16[l], h->dec_wsb[l], h->dec_wmeta[l] + 2, nullptr,
-                                                      b.act[l - 1], fused_l0 ? b.rows_p : b.dpre[cur ^ 1], b.tmax_dpre[cur],
-                                                      b.tmax_dpre[cur ^ 1], N, h->S, Cd, Cd,
-                                                      fused_l0 ? (train_alpha != 0.f ? EPI_L0ROWSX : EPI_L0ROWS) : EPI_MUL_ELUGRAD, l));
-        else if (conv_ws32_ok(h))
-            PROF(h, st, "conv_tile_dgrad", launch_conv3x3_ws_f32(st, b.dpre[cur], h->dec_wsb[l], nullptr, b.act[l - 1],
-                                                                 fused_l0 ? b.rows_p : b.dpre[cur ^ 1], N, h->S, Cd,
-                                                                 fused_l0 ? (train_alpha != 0.f ? EPI_L0ROWSX : EPI_L0ROWS) : EPI_MUL_ELUGRAD, l & 1));
-        else
-            PROF(h, st, "conv_tile_dgrad", launch_conv3x3_tile(st, b.dpre[cur], h->dec_wb[l], nullptr, b.act[l - 1],
-                                                               b.dpre[cur ^ 1], N, h->S, Cd, Cd, EPI_MUL_ELUGRAD));
+        fused_l0 = l == 1 && h->fuse_l0 && (dec_f16(path) ? (!train || path == DEC_WS_F16) : path == DEC_WS_F32);
+        if ((rc = dec_conv_dgrad(h, st, N, l, cur, fused_l0 ? b.rows_p : b.dpre[cur ^ 1],
+                                 fused_l0 ? (train ? EPI_L0ROWSX : EPI_L0ROWS) : EPI_MUL_ELUGRAD)))
+            return rc;
         cur ^= 1;
     }
     *dpre0 = b.dpre[cur];
-    if (fused_l0 && train_alpha == 0.f) {
+    if (fused_l0 && !train) {
         PROF(h, st, "l0_reduce", launch_l0_reduce_cls_tiles(st, b.rows_p, b.Rc, N, h->S, Cd, b.l0scr));
         return IODINE_OK;
     }
@@ -720,20 +767,20 @@ int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0
     } else
     // row / class sums of dpre0 for dz; in training the same read also feeds the slot-summed gradient map, which is
     // accumulated (with this pass's factor) over the T+1 passes and consumed once after the last one
-    PROF(h, st, "l0_reduce", launch_l0_reduce(st, *dpre0, b.rows, b.Rc, N, h->S, Cd, train_alpha != 0.f ? b.Dpart : nullptr,
+    PROF(h, st, "l0_reduce", launch_l0_reduce(st, *dpre0, b.rows, b.Rc, N, h->S, Cd, train ? b.Dpart : nullptr,
                                               b.Dsum, train_alpha, it == 0));
-    if (train_alpha != 0.f) {
+    if (train) {
         // layer 0 (spatial broadcast): latent-channel weights from z and the per-tap sums, coordinate channels
         // and bias from the slot-summed gradient map
-        const int wi = param_index(h, "decoder.mlc.layers.0.weight"), bi = param_index(h, "decoder.mlc.layers.0.bias");
+        float *gw = h->gacc[ps.dec_w[0]], *gb = h->gacc[ps.dec_b[0]];
         if (sgemm_tn_mfma_ok(h->L, 9 * Cd, N)) {            // z^T . RT on fp32 MFMA, accumulated straight into gw[co][ci][tap]
             HIPCHK(h, launch_l0_tap_sums(st, b.Rc, b.RT, N, Cd));
-            HIPCHK(h, launch_sgemm_tn_mfma(st, h->L, 9 * Cd, N, train_alpha, b.z[it], h->L, b.RT, 9 * Cd, 1.f, h->gacc[wi], h->L + 2, 1, Cd));
+            HIPCHK(h, launch_sgemm_tn_mfma(st, h->L, 9 * Cd, N, train_alpha, b.z[it], h->L, b.RT, 9 * Cd, 1.f, gw, h->L + 2, 1, Cd));
         } else                                              // (round 6) tap sums + product + scatter in one launch
-            HIPCHK(h, launch_l0_latent_wgrad(st, b.Rc, b.z[it], N, h->L, Cd, train_alpha, h->gacc[wi]));
+            HIPCHK(h, launch_l0_latent_wgrad(st, b.Rc, b.z[it], N, h->L, Cd, train_alpha, gw));
         if (it == h->T) {
-            if (fused_l0) HIPCHK(h, launch_l0_coord_grads_rows(st, b.Rsum, h->lin, h->S, Cd, h->L, 1.f, h->gacc[wi], h->gacc[bi]));
-            else HIPCHK(h, launch_l0_coord_grads(st, b.Dsum, h->lin, h->S, Cd, h->L, 1.f, h->gacc[wi], h->gacc[bi], b.wg_part));
+            if (fused_l0) HIPCHK(h, launch_l0_coord_grads_rows(st, b.Rsum, h->lin, h->S, Cd, h->L, 1.f, gw, gb));
+            else HIPCHK(h, launch_l0_coord_grads(st, b.Dsum, h->lin, h->S, Cd, h->L, 1.f, gw, gb, b.wg_part));
         }
     }
     return IODINE_OK;
@@ -760,7 +807,7 @@ int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps
     float* dpre0 = nullptr;
     rc = decoder_backward_data(h, st, N, &dpre0, train_alpha, i);
     if (rc) return rc;
-    HIPCHK(h, launch_dz_latent(st, b.Rc, h->generic ? h->gen_ident : h->wclsT, b.pm, b.plv, eps_i, N, h->L, h->Cd, h->cfg.layernorm,
+    HIPCHK(h, launch_dz_latent(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, b.pm, b.plv, eps_i, N, h->L, h->Cd, h->cfg.layernorm,
                                b.g_pm[i], b.g_plv[i], b.latent[i], h->Lreal));
     return IODINE_OK;
 }
@@ -1144,7 +1191,7 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
     if (Cr == 64)
         for (int l = 1; l < h->Dr; ++l) { ALLOC(h->ref_wsf[l], conv_ws_wpk_bytes(Cr) / 4); ALLOC(h->ref_wsf_meta[l], (size_t)4); }
     ALLOC(h->ref_w17, (size_t)Cr * 17 * h->kr * h->kr); ALLOC(h->ref_g17, (size_t)Cr * 17 * h->kr * h->kr);
-    if (h->generic) {
+    if (dec_path(h) == DEC_GENERIC) {
         const int kkd = h->kd * h->kd;
         h->gen_wdec.assign(h->Dd, nullptr);
         for (int l = 0; l < h->Dd; ++l) ALLOC(h->gen_wdec[l], (size_t)kkd * (l == 0 ? L + 2 : Cd) * Cd);
@@ -1229,7 +1276,7 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
         for (int i = 0; i < n; ++i) HIPCHK(h, launch_pad_gather(st, dev[i], sh->pmap[i], sh->pparam[i], sh->pnumel[i]));
         return shim_fail(h, iodine_set_params(sh->inner, stream, sh->pparam.data(), n));
     }
-    auto P = [&](const std::string& name) { return dev[param_index(h, name)]; };
+    const ParamSlots& ps = h->slot;
     // plain copies (biases, raw weights of the head backward) are collected and issued as one launch
     MultiCopy mc;
     mc.count = 0;
@@ -1265,17 +1312,17 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
         pj.push_back(PackJob{src, dst, meta, 1, {O, I, cin, cout, tflip}});
         return hipSuccess;
     };
-    if (h->generic) {
+    const DecPath path = dec_path(h);
+    if (path == DEC_GENERIC) {
         // fallback path: [tap][ci][co] packs of every conv, plain bias copies, the head below as on the tuned path
         for (int l = 0; l < h->Dd; ++l) {
-            const std::string base = "decoder.mlc.layers." + std::to_string(l);
-            HIPCHK(h, launch_gen_pack_weights(st, P(base + ".weight"), Cd, l == 0 ? L + 2 : Cd, h->kd, h->gen_wdec[l]));
-            if (l > 0) HIPCHK(h, queue_copy(h->dec_b[l], P(base + ".bias"), Cd));
+            HIPCHK(h, launch_gen_pack_weights(st, dev[ps.dec_w[l]], Cd, l == 0 ? L + 2 : Cd, h->kd, h->gen_wdec[l]));
+            if (l > 0) HIPCHK(h, queue_copy(h->dec_b[l], dev[ps.dec_b[l]], Cd));
         }
         // bias + the conv of the two coordinate channels of the broadcast layer: the same map for every slot-image
-        HIPCHK(h, launch_gen_l0_coord(st, h->gen_wdec[0], P("decoder.mlc.layers.0.bias"), h->lin, L, h->S, Cd, h->kd, h->gen_cterm));
-        HIPCHK(h, launch_gen_pack_weights(st, P("decoder.conv.weight"), 4, Cd, h->kd, h->gen_wout));
-        HIPCHK(h, queue_copy(h->dec_out_b, P("decoder.conv.bias"), 4));
+        HIPCHK(h, launch_gen_l0_coord(st, h->gen_wdec[0], dev[ps.dec_b[0]], h->lin, L, h->S, Cd, h->kd, h->gen_cterm));
+        HIPCHK(h, launch_gen_pack_weights(st, dev[ps.out_w], 4, Cd, h->kd, h->gen_wout));
+        HIPCHK(h, queue_copy(h->dec_out_b, dev[ps.out_b], 4));
         HIPCHK(h, launch_gen_identity(st, h->gen_ident, 9 * Cd, L));
         // gen_conv_precision 1: hi / lo slice images of the C -> C layers, both directions (from the packs above; stream order)
         h->gen_split = h->gen_precision == 1 && gen_split_cch(h->kd, Cd) != 0 && h->Dd > 1;
@@ -1301,70 +1348,74 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
     }
     if (h->gen_ref) {
         for (int l = 0; l < h->Dr; ++l) {
-            const std::string base = "refine.mlc.layers." + std::to_string(l);
-            const float* w = P(base + ".weight");
+            const float* w = dev[ps.ref_w[l]];
             if (l == 0 && h->n_in < 17) {
                 HIPCHK(h, launch_enc_expand_weights(st, w, Cr, h->n_in, h->enc_map, h->ref_w17, h->kr * h->kr));
                 w = h->ref_w17;
             }
             HIPCHK(h, launch_gen_pack_weights(st, w, Cr, l == 0 ? 17 : Cr, h->kr, h->gen_wref[l]));
-            HIPCHK(h, queue_copy(h->ref_b[l], P(base + ".bias"), Cr));
+            HIPCHK(h, queue_copy(h->ref_b[l], dev[ps.ref_b[l]], Cr));
         }
     }
-    if (!h->generic) {
+    if (path != DEC_GENERIC) {
     // decoder
-    HIPCHK(h, launch_dec_l0_prepare(st, P("decoder.mlc.layers.0.weight"), P("decoder.mlc.layers.0.bias"), h->lin, Cd, L,
-                                    h->S, h->wcls, h->wclsT, h->cmap));
+    HIPCHK(h, launch_dec_l0_prepare(st, dev[ps.dec_w[0]], dev[ps.dec_b[0]], h->lin, Cd, L, h->S, h->wcls, h->wclsT, h->cmap));
     for (int l = 1; l < h->Dd; ++l) {
-        const float* w = P("decoder.mlc.layers." + std::to_string(l) + ".weight");
-        if (conv_ws32_ok(h)) {                                 // exact-fp32 path, weight-stationary register layout (fp32)
-            HIPCHK(h, launch_pack_conv_weights_ws32(st, w, Cd, 0, h->dec_wsf[l]));
-            HIPCHK(h, launch_pack_conv_weights_ws32(st, w, Cd, 1, h->dec_wsb[l]));
-        } else if (h->precision == 0) {                        // exact-fp32 path, LDS-tiled kernels (conv_precision invalidates the params)
-            HIPCHK(h, launch_pack_conv_weights(st, w, Cd, Cd, Cd, Cd, 0, h->dec_wf[l]));
-            HIPCHK(h, launch_pack_conv_weights(st, w, Cd, Cd, Cd, Cd, 1, h->dec_wb[l]));
-        }
-        // only the selected kernel's packs are maintained (a change of conv_variant / conv_precision invalidates the parameters)
-        if (conv_ws_ok(h)) {                                   // weight-stationary register layout
+        // only the selected path's packs - the ones dec_conv_fwd / dec_conv_dgrad read - are maintained (a change of conv_variant /
+        // conv_precision invalidates the parameters)
+        const float* w = dev[ps.dec_w[l]];
+        switch (path) {
+        case DEC_WS_F16:                                       // weight-stationary register layout
             HIPCHK(h, pack_ws(w, Cd, 0, h->dec_wmeta[l], h->dec_wsf[l]));
             HIPCHK(h, pack_ws(w, Cd, 1, h->dec_wmeta[l] + 2, h->dec_wsb[l]));
-        } else {
+            break;
+        case DEC_TILE_F16:
             HIPCHK(h, pack_f16(w, Cd, Cd, Cd, Cd, 0, h->dec_wmeta[l], h->dec_wf16[l]));
             HIPCHK(h, pack_f16(w, Cd, Cd, Cd, Cd, 1, h->dec_wmeta[l] + 2, h->dec_wb16[l]));
+            break;
+        case DEC_WS_F32:                                       // the same register layout, fp32
+            HIPCHK(h, launch_pack_conv_weights_ws32(st, w, Cd, 0, h->dec_wsf[l]));
+            HIPCHK(h, launch_pack_conv_weights_ws32(st, w, Cd, 1, h->dec_wsb[l]));
+            break;
+        case DEC_TILE_F32:
+            HIPCHK(h, launch_pack_conv_weights(st, w, Cd, Cd, Cd, Cd, 0, h->dec_wf[l]));
+            HIPCHK(h, launch_pack_conv_weights(st, w, Cd, Cd, Cd, Cd, 1, h->dec_wb[l]));
+            break;
+        case DEC_GENERIC: break;
         }
-        HIPCHK(h, queue_copy(h->dec_b[l], P("decoder.mlc.layers." + std::to_string(l) + ".bias"), Cd));
+        HIPCHK(h, queue_copy(h->dec_b[l], dev[ps.dec_b[l]], Cd));
     }
-    HIPCHK(h, queue_copy(h->dec_out_b, P("decoder.conv.bias"), 4));
-    if (h->precision == 0) {                                   // exact-fp32 forms of the output conv (conv_precision invalidates the params)
-        HIPCHK(h, launch_pack_dec_out(st, P("decoder.conv.weight"), h->dec_out_w, Cd));
-        HIPCHK(h, launch_pack_conv_weights(st, P("decoder.conv.weight"), 4, Cd, 4, Cd, 1, h->dec_out_wb));
-        if (h->dec_out_w32) HIPCHK(h, launch_pack_dec_out_rows32(st, P("decoder.conv.weight"), Cd, h->dec_out_w32));
+    HIPCHK(h, queue_copy(h->dec_out_b, dev[ps.out_b], 4));
+    if (dec_f16(path)) {
+        // split-fp16 GEMM-form packs of the output conv, forward and data gradient (one scale): two more jobs of the batched pack
+        pj.push_back(PackJob{dev[ps.out_w], h->dec_out_w16, h->dec_out_meta, 3, {Cd, 0, 0, 0, 0}});
+        pj.push_back(PackJob{dev[ps.out_w], h->dec_out_wb16, h->dec_out_meta, 4, {Cd, 1, 0, 0, 0}});
+    } else {                                                   // exact-fp32 forms of the output conv
+        HIPCHK(h, launch_pack_dec_out(st, dev[ps.out_w], h->dec_out_w, Cd));
+        HIPCHK(h, launch_pack_conv_weights(st, dev[ps.out_w], 4, Cd, 4, Cd, 1, h->dec_out_wb));
+        if (h->dec_out_w32) HIPCHK(h, launch_pack_dec_out_rows32(st, dev[ps.out_w], Cd, h->dec_out_w32));
     }
-    // split-fp16 GEMM-form packs of the output conv, forward and data gradient (one scale): two more jobs of the batched pack
-    pj.push_back(PackJob{P("decoder.conv.weight"), h->dec_out_w16, h->dec_out_meta, 3, {Cd, 0, 0, 0, 0}});
-    pj.push_back(PackJob{P("decoder.conv.weight"), h->dec_out_wb16, h->dec_out_meta, 4, {Cd, 1, 0, 0, 0}});
-    }   // !generic (decoder)
+    }   // tuned decoder
     if (!h->gen_ref) {
     // refinement conv stack
     const bool ref_fp32 = !refine_f16_ok(h);                    // the round-1 gather kernels: only where the tuned stride-2 kernels do not apply
     // first layer: the reference weight has n_in input channels (ARCH.ENCODING subset); the kernels see 17
-    const float* w0 = P("refine.mlc.layers.0.weight");
+    const float* w0 = dev[ps.ref_w[0]];
     if (h->n_in < 17) {
         HIPCHK(h, launch_enc_expand_weights(st, w0, Cr, h->n_in, h->enc_map, h->ref_w17));
         w0 = h->ref_w17;
     }
     for (int l = 0; l < h->Dr; ++l) {
-        const float* w = l == 0 ? w0 : P("refine.mlc.layers." + std::to_string(l) + ".weight");
+        const float* w = l == 0 ? w0 : dev[ps.ref_w[l]];
         if (ref_fp32) HIPCHK(h, launch_pack_conv_weights(st, w, Cr, l == 0 ? 17 : Cr, l == 0 ? 20 : Cr, Cr, 0, h->ref_w[l]));
-        HIPCHK(h, queue_copy(h->ref_b[l], P("refine.mlc.layers." + std::to_string(l) + ".bias"), Cr));
+        HIPCHK(h, queue_copy(h->ref_b[l], dev[ps.ref_b[l]], Cr));
     }
     for (int l = 1; l < h->Dr && ref_fp32; ++l)
-        HIPCHK(h, launch_pack_conv_weights(st, P("refine.mlc.layers." + std::to_string(l) + ".weight"), Cr, Cr, Cr, Cr, 2,
-                                           h->ref_wb[l]));
+        HIPCHK(h, launch_pack_conv_weights(st, dev[ps.ref_w[l]], Cr, Cr, Cr, Cr, 2, h->ref_wb[l]));
     if (refine_f16_ok(h) && h->precision == 0) {
         // exact-fp32 path: fp32 weights in the same LDS-tile layouts (same buffers; conv_precision invalidates the parameters)
         for (int l = 0; l < h->Dr; ++l) {
-            const float* w = l == 0 ? w0 : P("refine.mlc.layers." + std::to_string(l) + ".weight");
+            const float* w = l == 0 ? w0 : dev[ps.ref_w[l]];
             HIPCHK(h, launch_pack_conv_weights_s2f32(st, w, Cr, l == 0 ? 17 : Cr, l == 0 ? 32 : Cr, Cr, 0, h->ref_wf16[l]));
             if (l > 0) HIPCHK(h, launch_pack_conv_weights_s2f32(st, w, Cr, Cr, Cr, Cr, 2, h->ref_wb16[l]));
         }
@@ -1373,10 +1424,10 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
         HIPCHK(h, launch_pack_conv_weights_s2f32(st, h->ref_wsh, Cr, 8, 16, Cr, 0, h->ref_wsh16));
         if (Cr == 64)                                           // weight-stationary forward of layers 1 .. (fp32 weights in the same registers)
             for (int l = 1; l < h->Dr; ++l)
-                HIPCHK(h, launch_pack_conv_weights_ws32(st, P("refine.mlc.layers." + std::to_string(l) + ".weight"), Cr, 0, h->ref_wsf[l]));
+                HIPCHK(h, launch_pack_conv_weights_ws32(st, dev[ps.ref_w[l]], Cr, 0, h->ref_wsf[l]));
     } else if (refine_f16_ok(h)) {
         for (int l = 0; l < h->Dr; ++l) {
-            const float* w = l == 0 ? w0 : P("refine.mlc.layers." + std::to_string(l) + ".weight");
+            const float* w = l == 0 ? w0 : dev[ps.ref_w[l]];
             HIPCHK(h, pack_f16(w, Cr, l == 0 ? 17 : Cr, l == 0 ? 32 : Cr, Cr, 0, h->ref_wmeta[l],
                                                    h->ref_wf16[l]));
             if (l > 0)
@@ -1392,31 +1443,29 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
         }
         if (Cr == 64)                                           // weight-stationary forward of layers 1 ..
             for (int l = 1; l < h->Dr; ++l)
-                HIPCHK(h, pack_ws(P("refine.mlc.layers." + std::to_string(l) + ".weight"), Cr, 0, h->ref_wsf_meta[l], h->ref_wsf[l]));
+                HIPCHK(h, pack_ws(dev[ps.ref_w[l]], Cr, 0, h->ref_wsf_meta[l], h->ref_wsf[l]));
         if (h->Dr >= 2 && refine_bwd01_ok(h->S, Cr))           // fused layer-1 / layer-0 backward: W1 as the transposed conv's A operand
-            HIPCHK(h, pack_ws(P("refine.mlc.layers.1.weight"), Cr, 1, h->ref_w1ws_meta, h->ref_w1ws));
+            HIPCHK(h, pack_ws(dev[ps.ref_w[1]], Cr, 1, h->ref_w1ws_meta, h->ref_w1ws));
     }
     }   // !gen_ref
-    auto copy_raw = [&](float* dst, const std::string& name) {
-        return queue_copy(dst, P(name), h->params[param_index(h, name)].numel());
-    };
-    HIPCHK(h, copy_raw(h->raw_mlp_w, "refine.mlp.layers.0.weight"));
-    HIPCHK(h, copy_raw(h->raw_wih, "refine.lstm.weight_ih"));
-    HIPCHK(h, copy_raw(h->raw_whh, "refine.lstm.weight_hh"));
-    HIPCHK(h, copy_raw(h->raw_wm, "refine.mean_update.weight"));
-    HIPCHK(h, copy_raw(h->raw_wv, "refine.logvar_update.weight"));
+    auto copy_raw = [&](float* dst, int slot) { return queue_copy(dst, dev[slot], h->params[slot].numel()); };
+    HIPCHK(h, copy_raw(h->raw_mlp_w, ps.mlp_w));
+    HIPCHK(h, copy_raw(h->raw_wih, ps.wih));
+    HIPCHK(h, copy_raw(h->raw_whh, ps.whh));
+    HIPCHK(h, copy_raw(h->raw_wm, ps.wm));
+    HIPCHK(h, copy_raw(h->raw_wv, ps.wv));
     // head
-    HIPCHK(h, queue_transpose(h->mlp_wT, P("refine.mlp.layers.0.weight"), H, Cr));
-    HIPCHK(h, queue_copy(h->mlp_b, P("refine.mlp.layers.0.bias"), H));
-    HIPCHK(h, queue_transpose(h->wihT, P("refine.lstm.weight_ih"), 4 * H, H + 4 * L));
-    HIPCHK(h, queue_transpose(h->whhT, P("refine.lstm.weight_hh"), 4 * H, H));
-    HIPCHK(h, queue_add2(h->lstm_b, P("refine.lstm.bias_ih"), P("refine.lstm.bias_hh"), 4 * H));
-    HIPCHK(h, queue_transpose(h->wmT, P("refine.mean_update.weight"), L, H));
-    HIPCHK(h, queue_transpose(h->wvT, P("refine.logvar_update.weight"), L, H));
-    HIPCHK(h, queue_copy(h->bm, P("refine.mean_update.bias"), L));
-    HIPCHK(h, queue_copy(h->bv, P("refine.logvar_update.bias"), L));
-    HIPCHK(h, queue_copy(h->init_mean, P("posterior.init_mean"), L));
-    HIPCHK(h, queue_copy(h->init_logvar, P("posterior.init_logvar"), L));
+    HIPCHK(h, queue_transpose(h->mlp_wT, dev[ps.mlp_w], H, Cr));
+    HIPCHK(h, queue_copy(h->mlp_b, dev[ps.mlp_b], H));
+    HIPCHK(h, queue_transpose(h->wihT, dev[ps.wih], 4 * H, H + 4 * L));
+    HIPCHK(h, queue_transpose(h->whhT, dev[ps.whh], 4 * H, H));
+    HIPCHK(h, queue_add2(h->lstm_b, dev[ps.bih], dev[ps.bhh], 4 * H));
+    HIPCHK(h, queue_transpose(h->wmT, dev[ps.wm], L, H));
+    HIPCHK(h, queue_transpose(h->wvT, dev[ps.wv], L, H));
+    HIPCHK(h, queue_copy(h->bm, dev[ps.bm], L));
+    HIPCHK(h, queue_copy(h->bv, dev[ps.bv], L));
+    HIPCHK(h, queue_copy(h->init_mean, dev[ps.init_mean], L));
+    HIPCHK(h, queue_copy(h->init_logvar, dev[ps.init_logvar], L));
     HIPCHK(h, launch_multi_copy(st, mc));
     if (!pj.empty()) HIPCHK(h, launch_pack_batch(st, pj.data(), (int)pj.size()));      // (behind ref_split / enc_expand: stream order)
     h->params_set = true;
@@ -1743,8 +1792,8 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
             if (i == 0) {
                 // lambda_0 = init_mean / init_logvar repeated over (B, K) (iodine.py:615-616): their gradient is the
                 // column sum of d loss / d lambda_0; later lambdas are detached from it (iodine.py:642-643)
-                HIPCHK(h, launch_colsum(st, b.g_pm[0], N, L, L, alpha, h->gacc[param_index(h, "posterior.init_mean")]));
-                HIPCHK(h, launch_colsum(st, b.g_plv[0], N, L, L, alpha, h->gacc[param_index(h, "posterior.init_logvar")]));
+                HIPCHK(h, launch_colsum(st, b.g_pm[0], N, L, L, alpha, h->gacc[h->slot.init_mean]));
+                HIPCHK(h, launch_colsum(st, b.g_plv[0], N, L, L, alpha, h->gacc[h->slot.init_logvar]));
             }
             if (i < T) {
                 r = refine_step(h, st, B, i, true);
@@ -1799,7 +1848,7 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
     auto body = [&]() -> int {
     Buffers& b = h->buf;
     const int B = h->fwd_batch, N = B * h->K, T = h->T, L = h->L, H = h->H, Cr = h->Cr, IN = H + 4 * L;
-    auto G = [&](const std::string& name) { return h->gacc[param_index(h, name)]; };
+    const ParamSlots& ps = h->slot;
     if (h->head_fused && head_bptt_fits(L, H, Cr)) {
         // the whole BPTT recurrence of the head in one launch (rows are independent: a block walks i = T-1 .. 0 for its rows)
         PROF(h, st, "head_bwd", launch_head_bptt(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->raw_wm, h->raw_wv, h->raw_whh,
@@ -1832,16 +1881,16 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
         // Weight gradients of the head: sums over the iterations of X_i^T D_i = ONE GEMM per parameter over all T * N rows
         // (the per-iteration operands lie back to back: c[1..T], xin[0..T-1], h[0..T-1], pooled[0..T-1] and ddm / ddv / dgates / ds)
         const int R = T * N;
-        HIPCHK(h, launch_sgemm(st, 1, 0, L, H, R, 1.f, b.ddm, L, b.c[1], H, 1.f, G("refine.mean_update.weight"), H));
-        HIPCHK(h, launch_sgemm(st, 1, 0, L, H, R, 1.f, b.ddv, L, b.c[1], H, 1.f, G("refine.logvar_update.weight"), H));
-        HIPCHK(h, launch_colsum(st, b.ddm, R, L, L, 1.f, G("refine.mean_update.bias")));
-        HIPCHK(h, launch_colsum(st, b.ddv, R, L, L, 1.f, G("refine.logvar_update.bias")));
-        HIPCHK(h, launch_sgemm(st, 1, 0, 4 * H, IN, R, 1.f, b.dgates, 4 * H, b.xin[0], IN, 1.f, G("refine.lstm.weight_ih"), IN));
-        HIPCHK(h, launch_sgemm(st, 1, 0, 4 * H, H, R, 1.f, b.dgates, 4 * H, b.h[0], H, 1.f, G("refine.lstm.weight_hh"), H));
-        HIPCHK(h, launch_colsum(st, b.dgates, R, 4 * H, 4 * H, 1.f, G("refine.lstm.bias_ih")));
-        HIPCHK(h, launch_colsum(st, b.dgates, R, 4 * H, 4 * H, 1.f, G("refine.lstm.bias_hh")));
-        HIPCHK(h, launch_sgemm(st, 1, 0, H, Cr, R, 1.f, b.ds, H, b.pooled[0], Cr, 1.f, G("refine.mlp.layers.0.weight"), Cr));
-        HIPCHK(h, launch_colsum(st, b.ds, R, H, H, 1.f, G("refine.mlp.layers.0.bias")));
+        HIPCHK(h, launch_sgemm(st, 1, 0, L, H, R, 1.f, b.ddm, L, b.c[1], H, 1.f, h->gacc[ps.wm], H));
+        HIPCHK(h, launch_sgemm(st, 1, 0, L, H, R, 1.f, b.ddv, L, b.c[1], H, 1.f, h->gacc[ps.wv], H));
+        HIPCHK(h, launch_colsum(st, b.ddm, R, L, L, 1.f, h->gacc[ps.bm]));
+        HIPCHK(h, launch_colsum(st, b.ddv, R, L, L, 1.f, h->gacc[ps.bv]));
+        HIPCHK(h, launch_sgemm(st, 1, 0, 4 * H, IN, R, 1.f, b.dgates, 4 * H, b.xin[0], IN, 1.f, h->gacc[ps.wih], IN));
+        HIPCHK(h, launch_sgemm(st, 1, 0, 4 * H, H, R, 1.f, b.dgates, 4 * H, b.h[0], H, 1.f, h->gacc[ps.whh], H));
+        HIPCHK(h, launch_colsum(st, b.dgates, R, 4 * H, 4 * H, 1.f, h->gacc[ps.bih]));
+        HIPCHK(h, launch_colsum(st, b.dgates, R, 4 * H, 4 * H, 1.f, h->gacc[ps.bhh]));
+        HIPCHK(h, launch_sgemm(st, 1, 0, H, Cr, R, 1.f, b.ds, H, b.pooled[0], Cr, 1.f, h->gacc[ps.mlp_w], Cr));
+        HIPCHK(h, launch_colsum(st, b.ds, R, H, H, 1.f, h->gacc[ps.mlp_b]));
     }
     {
         // Conv stack of the refinement network, last layer first, for ALL iterations at once: its inputs are detached
@@ -1862,47 +1911,42 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
             const float* in = l == 0 ? b.enc[0] : b.ract[0][l - 1];
             const int cip = l == 0 ? 20 : Cr, ireal = l == 0 ? 17 : Cr;
             int nparts = 0, cipad = 0;
-            const std::string base = "refine.mlc.layers." + std::to_string(l);
+            float* gb = h->gacc[ps.ref_b[l]];
             // the layer's weight-gradient destination: the accumulator itself, or (first layer of an ARCH.ENCODING subset) a
             // 17-channel scratch that is gathered into the n_in-channel accumulator afterwards
             const bool gather0 = l == 0 && h->n_in < 17;
-            float* gw_dst = gather0 ? h->ref_g17 : G(base + ".weight");
+            float* gw_dst = gather0 ? h->ref_g17 : h->gacc[ps.ref_w[l]];
             if (gather0) HIPCHK(h, hipMemsetAsync(h->ref_g17, 0, (size_t)Cr * 17 * h->kr * h->kr * sizeof(float), st));
             if (h->gen_ref) {
                 PROF(h, st, "gen_conv", launch_gen_conv_wgrad(st, in, b.rdpre[l], b.gen_scr, NT, sz[l], ireal, cip, ireal, Cr, h->kr, h->rs, 1.f,
-                                                              gw_dst, G(base + ".bias"), l == 0 ? h->enc_chmask : 0xffffffffu));
-            } else if (l == 0 && fuse01) {
-                int nb = 0;
-                PROF(h, st, "refine_bwd01", launch_refine_bwd01(st, b.rdpre[1], h->ref_w1ws, h->ref_w1ws_meta, b.ract[0][0], b.enck[0], b.encs[0],
-                                                                b.wg_part, b.wg_part_b, NT, sz[0], Cr, h->K, &nparts, &cipad, &nb));
-                HIPCHK(h, hipMemsetAsync(h->ref_g20, 0, (size_t)Cr * 20 * 9 * sizeof(float), st));
-                HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, 20, 20, 1.f, h->ref_g20, b.wg_fold,
-                                              b.wg_part_b, nb, G(base + ".bias")));
-                HIPCHK(h, launch_ref_unsplit_grad(st, h->ref_g20, Cr, gw_dst));
+                                                              gw_dst, gb, l == 0 ? h->enc_chmask : 0xffffffffu));
             } else if (l == 0 && h->fwd_split) {
-                // split first layer: 12 per-slot + 8 per-image channels from two tensors, gradient in the internal channel
-                // order, then added to the reference layout
+                // split first layer: 12 per-slot + 8 per-image channels from two tensors (fuse01: in the same launch as layer 1's data
+                // gradient), gradient in the internal channel order, then added to the reference layout
                 int nb = 0;
-                PROF(h, st, "refine_wgrad", launch_conv3x3_s2_wgrad_f16x3(st, b.enck[0], b.rdpre[0], b.wg_part, b.wg_part_b, NT, sz[0],
-                                                                          20, Cr, &nparts, &cipad, &nb, b.encs[0], h->K, h->precision == 0));
+                if (fuse01)
+                    PROF(h, st, "refine_bwd01", launch_refine_bwd01(st, b.rdpre[1], h->ref_w1ws, h->ref_w1ws_meta, b.ract[0][0], b.enck[0], b.encs[0],
+                                                                    b.wg_part, b.wg_part_b, NT, sz[0], Cr, h->K, &nparts, &cipad, &nb));
+                else
+                    PROF(h, st, "refine_wgrad", launch_conv3x3_s2_wgrad_f16x3(st, b.enck[0], b.rdpre[0], b.wg_part, b.wg_part_b, NT, sz[0],
+                                                                              20, Cr, &nparts, &cipad, &nb, b.encs[0], h->K, h->precision == 0));
                 HIPCHK(h, hipMemsetAsync(h->ref_g20, 0, (size_t)Cr * 20 * 9 * sizeof(float), st));
-                HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, 20, 20, 1.f, h->ref_g20, b.wg_fold,
-                                              b.wg_part_b, nb, G(base + ".bias")));
+                HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, 20, 20, 1.f, h->ref_g20, b.wg_fold, b.wg_part_b, nb, gb));
                 HIPCHK(h, launch_ref_unsplit_grad(st, h->ref_g20, Cr, gw_dst));
             } else if (refine_f16_ok(h)) {
                 int nb = 0;
                 PROF(h, st, "refine_wgrad", launch_conv3x3_s2_wgrad_f16x3(st, in, b.rdpre[l], b.wg_part, b.wg_part_b, NT, sz[l],
                                                                           cip, Cr, &nparts, &cipad, &nb, nullptr, 0, h->precision == 0));
                 HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, ireal, ireal, 1.f, gw_dst, b.wg_fold,
-                                              b.wg_part_b, nb, G(base + ".bias")));
+                                              b.wg_part_b, nb, gb));
             } else {
                 PROF(h, st, "refine_wgrad", launch_conv3x3_wgrad_gather(st, in, b.rdpre[l], b.wg_part, NT, sz[l], sz[l], cip, Cr, 2,
                                                                         &nparts, &cipad));
                 HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, ireal, ireal, 1.f, gw_dst, b.wg_fold));
                 PROF(h, st, "refine_bias_grad", launch_colsum_tall(st, b.rdpre[l], NT * sz[l + 1] * sz[l + 1], Cr, 1.f,
-                                                                   G(base + ".bias"), b.wg_part_b, (size_t)512 * 64));
+                                                                   gb, b.wg_part_b, (size_t)512 * 64));
             }
-            if (gather0) HIPCHK(h, launch_enc_gather_grad(st, h->ref_g17, Cr, h->n_in, h->enc_map, G(base + ".weight"), h->kr * h->kr));
+            if (gather0) HIPCHK(h, launch_enc_gather_grad(st, h->ref_g17, Cr, h->n_in, h->enc_map, h->gacc[ps.ref_w[l]], h->kr * h->kr));
             if (l > 0 && !(l == 1 && fuse01)) {
                 if (h->gen_ref)
                     PROF(h, st, "gen_conv", launch_gen_conv_dgrad(st, b.rdpre[l], h->gen_wref[l], b.ract[0][l - 1], b.rdpre[l - 1], NT, sz[l],

@@ -507,7 +507,7 @@ void conv3x3_tile_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
     const int lane = tid & 63, wv = tid >> 6, kh = lane >> 5, li = lane & 31;
     const int prow = li >> 4, pcol = li & 15;
 
-    int bid = rev ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;    // zig-zag launch order, see conv_f16x3()
+    int bid = rev ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;    // zig-zag launch order, see dec_conv_fwd()
     const int tx = bid % tiles; bid /= tiles;
     const int tiles_y = tiles * (16 / TH);
     const int ty = bid % tiles_y;

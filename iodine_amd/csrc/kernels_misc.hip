@@ -633,43 +633,6 @@ hipError_t launch_dz_latent(hipStream_t st, const float* Rc, const float* wclsT,
 }
 
 // -----------------------------------------------------------------------------------------------
-// KL against N(0,1) (iodine.py:653-659,191-193) + ELBO assembly.  One block per image; a second
-// single-block kernel forms the batch means in fixed order.
-//   img_terms[b] = {ll_b, kl_b};  scal = {elbo, kl, ll} (means over the B local images)
-// -----------------------------------------------------------------------------------------------
-__global__ void kl_image_kernel(const float* __restrict__ pm, const float* __restrict__ plv,
-                                const float* __restrict__ ll_img, int KL_, float* __restrict__ img_terms)
-{
-    __shared__ float s_buf[8];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    float s = 0.f;
-    for (int i = tid; i < KL_; i += blockDim.x) {
-        const float mu = pm[(size_t)b * KL_ + i], lv = plv[(size_t)b * KL_ + i];
-        s += 0.5f * (expf(lv) + mu * mu - 1.f - lv);
-    }
-    const float kl = block_sum_f(s, s_buf, tid, blockDim.x);
-    if (tid == 0) { img_terms[2 * b] = ll_img[b]; img_terms[2 * b + 1] = kl; }
-}
-
-__global__ void elbo_mean_kernel(const float* __restrict__ img_terms, int B, float* __restrict__ scal)
-{
-    if (threadIdx.x == 0) {
-        double ll = 0.0, kl = 0.0;
-        for (int b = 0; b < B; ++b) { ll += img_terms[2 * b]; kl += img_terms[2 * b + 1]; }
-        ll /= B; kl /= B;
-        scal[0] = (float)(ll - kl); scal[1] = (float)kl; scal[2] = (float)ll;
-    }
-}
-
-hipError_t launch_elbo(hipStream_t st, const float* pm, const float* plv, const float* ll_img, int B, int K, int L,
-                       float* img_terms, float* scal)
-{
-    hipLaunchKernelGGL(kl_image_kernel, dim3(B), dim3(256), 0, st, pm, plv, ll_img, K * L, img_terms);
-    hipLaunchKernelGGL(elbo_mean_kernel, dim3(1), dim3(64), 0, st, img_terms, B, scal);
-    return hipGetLastError();
-}
-
-// -----------------------------------------------------------------------------------------------
 // Refinement head (RefinementNetwork.forward after the conv stack, iodine.py:481-503):
 //   avg-pool -> Linear(C->H) -> ELU(ELU(.)) -> [u | latent] -> LSTMCell -> updates read from the CELL state c1
 //   (the reference's `(c, h) = lstm(...)` names h1 "c" and c1 "h") -> lambda += delta (iodine.py:642-643).
@@ -901,17 +864,8 @@ hipError_t launch_refine_head(hipStream_t st, const float* feat, int N, int PL, 
 }
 
 // -----------------------------------------------------------------------------------------------
-// small utilities: transpose [R][Cc] -> [Cc][R], vector add
+// small utilities: plain copies, transposes [R][Cc] -> [Cc][R] and vector adds of many tensors in one launch
 // -----------------------------------------------------------------------------------------------
-__global__ void transpose_kernel(const float* __restrict__ src, float* __restrict__ dst, int R, int Cc)
-{
-    const size_t total = (size_t)R * Cc;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int r = i / Cc, c = i % Cc;
-        dst[(size_t)c * R + r] = src[i];
-    }
-}
-
 __global__ void multi_copy_kernel(const MultiCopy mc)
 {
     const int j = blockIdx.y;
@@ -936,26 +890,6 @@ hipError_t launch_multi_copy(hipStream_t st, const MultiCopy& mc)
     for (int j = 0; j < mc.count; ++j) nmax = mc.n[j] > nmax ? mc.n[j] : nmax;
     const int bx = (nmax + 255) / 256 < 256 ? (nmax + 255) / 256 : 256;
     hipLaunchKernelGGL(multi_copy_kernel, dim3(bx, mc.count), dim3(256), 0, st, mc);
-    return hipGetLastError();
-}
-
-hipError_t launch_transpose(hipStream_t st, const float* src, float* dst, int R, int Cc)
-{
-    IOD_XSKIP(64);
-    const int blocks = (int)std::min<size_t>(((size_t)R * Cc + 255) / 256, 2048);
-    hipLaunchKernelGGL(transpose_kernel, dim3(blocks), dim3(256), 0, st, src, dst, R, Cc);
-    return hipGetLastError();
-}
-
-__global__ void add2_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ o, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) o[i] = a[i] + b[i];
-}
-
-hipError_t launch_add2(hipStream_t st, const float* a, const float* b, float* o, int n)
-{
-    hipLaunchKernelGGL(add2_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a, b, o, n);
     return hipGetLastError();
 }
 

@@ -112,50 +112,9 @@ void pixel_pass1_kernel(const float4* __restrict__ x4, const float4* __restrict_
     }
 }
 
-// ---- finalize: fixed-order sum of block partials -> per-image LL, per-slot LN (mean, 1/(std+1e-5)) ----
-// lnstat[n][8] = {g1.mean, g1.inv, g2.mean, g2.inv, loo.mean, loo.inv, like.mean, like.inv}
-__global__ void pixel_finalize_kernel(const double* __restrict__ part, int nblk, int K, int P, int use_ln,
-                                      float* __restrict__ lnstat, float* __restrict__ ll_img)
-{
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int NST = 6 * K + 3;
-    __shared__ double s_sum[6 * 16 + 3];
-    if (tid < NST) {
-        // fixed order, eight independent loads in flight (a plain running sum is a chain of nblk dependent HBM round trips: 11 us)
-        double v = 0.0;
-        int i = 0;
-        for (; i + 7 < nblk; i += 8) {
-            double q[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) q[j] = part[((size_t)b * nblk + i + j) * NST + tid];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v += q[j];
-        }
-        for (; i < nblk; ++i) v += part[((size_t)b * nblk + i) * NST + tid];
-        s_sum[tid] = v;
-    }
-    __syncthreads();
-    if (tid == 0) ll_img[b] = (float)s_sum[0];
-    if (tid < K) {
-        float* o = lnstat + ((size_t)b * K + tid) * 8;
-        const double cnt[4] = {3.0 * P, (double)P, (double)P, (double)P};
-        const double s1[4] = {s_sum[3 + 6 * tid + 0], s_sum[3 + 6 * tid + 2], s_sum[3 + 6 * tid + 4], s_sum[1]};
-        const double s2[4] = {s_sum[3 + 6 * tid + 1], s_sum[3 + 6 * tid + 3], s_sum[3 + 6 * tid + 5], s_sum[2]};
-        for (int j = 0; j < 4; ++j) {
-            const double mean = s1[j] / cnt[j];
-            double var = s2[j] / cnt[j] - mean * mean;
-            if (var < 0.0) var = 0.0;
-            const float sd = (float)sqrt(var);
-            o[2 * j + 0] = use_ln ? (float)mean : 0.f;
-            o[2 * j + 1] = use_ln ? 1.f / (sd + 1e-5f) : 1.f;
-        }
-    }
-}
-
 // ---- finalize + KL against N(0, 1) (iodine.py:653-659,191-193) + ELBO assembly in ONE launch (three until round 4: 5 us each behind a
 // 50 us kernel, six times per step).  Block b: image b.  img_terms[b] = {ll_b, kl_b}; the LAST block to finish (device-scope counter, reset by
-// that block) forms scal = {elbo, kl, ll} as the means over the images in fixed order - same arithmetic as kl_image_kernel /
-// elbo_mean_kernel (kernels_misc.hip), which remain for the public iodine_elbo path.
+// that block) forms scal = {elbo, kl, ll} as the means over the images in fixed order.
 __global__ __launch_bounds__(256)
 void pixel_finalize_elbo_kernel(const double* __restrict__ part, int nblk, int K, int P, int use_ln, float* __restrict__ lnstat,
                                 float* __restrict__ ll_img, const float* __restrict__ pm, const float* __restrict__ plv, int KL_,
@@ -214,7 +173,7 @@ void pixel_finalize_elbo_kernel(const double* __restrict__ part, int nblk, int K
         __threadfence();                                                      // acquire: the other blocks' terms
         __shared__ float s_t[2 * 256];
         double ll = 0.0, kl = 0.0;
-        for (int i0 = 0; i0 < B; i0 += 256) {                                 // loads in parallel, sums in image order (elbo_mean_kernel's)
+        for (int i0 = 0; i0 < B; i0 += 256) {                                 // loads in parallel, sums in image order
             if (i0 + tid < B) {
                 s_t[2 * tid] = __builtin_nontemporal_load(img_terms + 2 * (i0 + tid));
                 s_t[2 * tid + 1] = __builtin_nontemporal_load(img_terms + 2 * (i0 + tid) + 1);
@@ -396,15 +355,6 @@ hipError_t launch_pixel_pass1(hipStream_t st, const float* x4, const float* dec,
 #undef CASE
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_pixel_finalize(hipStream_t st, const double* part, int B, int K, int P, int use_ln,
-                                 float* lnstat, float* ll_img)
-{
-    IOD_XSKIP(8);
-    hipLaunchKernelGGL(pixel_finalize_kernel, dim3(B), dim3(128), 0, st, part, pixel_blocks_per_image(P), K, P,
-                       use_ln, lnstat, ll_img);
     return hipGetLastError();
 }
 

@@ -36,35 +36,6 @@ constexpr int L0_HR = 5, L0_HC = 33, L0_NPX = L0_HR * L0_HC;      // halo of a 2
 constexpr int L0_PXB = 48;                                         // bytes per staged pixel: 12 fp32 channels
 constexpr int L0_PLB = L0_NPX * L0_PXB;                            // one plane: 7920 bytes
 
-// w [O][CINW][9] -> [O / 16][9 taps][hi / lo][64 lanes] x 4 fp16: the A operand of v_mfma_f32_16x16x16_f16 (lane l: row = cout 16 g + l % 16,
-// k = cin 4 (l / 16) .. + 3, zero past CINW), pre-scaled by meta[0]
-__global__ void l0_pack_weights_kernel(const float* __restrict__ w, int O, int CINW, const float* __restrict__ meta, _Float16* __restrict__ dst)
-{
-    const float scale = meta[0];
-    const int total = (int)pack_l0_total(O);
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x)
-        dst[idx] = pack_l0_element(w, CINW, scale, (size_t)idx);             // (pack_bodies.h: shared with the batched form)
-}
-
-__global__ __launch_bounds__(1024) void l0_weight_scale_kernel(const float* __restrict__ w, int n, float* __restrict__ meta)
-{
-    __shared__ float s_red[16];
-    float m = 0.f;
-    for (int i = threadIdx.x; i < n; i += 1024) m = fmaxf(m, fabsf(w[i]));
-    m = wave_max_f32(m);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float mx = 0.f;
-        for (int k = 0; k < 16; ++k) mx = fmaxf(mx, s_red[k]);
-        int e = 0;
-        const bool ok = mx > 0.f && isfinite(mx);
-        if (ok) frexpf(mx, &e);
-        meta[0] = ok ? ldexpf(1.f, 13 - e) : 1.f;
-        meta[1] = 1.f / meta[0];
-    }
-}
-
 IOD_DEVINL float l0_fresh_scale(float mx)
 {
     if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.f;
@@ -433,15 +404,6 @@ hipError_t l0_launch(hipStream_t st, const float* x4, const float* dec, const fl
 }  // namespace
 
 size_t refine_l0_wpk_bytes(int O) { return (size_t)(O / 16) * 9 * 2 * 64 * 8; }
-
-// w [O][cinw][9] (cinw = 12: per-slot part, 8: per-image part; internal channel order of ref_split_weights) -> register layout + {scale, 1 / scale}
-hipError_t launch_refine_l0_pack(hipStream_t st, const float* w, int O, int cinw, float* meta, void* dst)
-{
-    hipLaunchKernelGGL(l0_weight_scale_kernel, dim3(1), dim3(1024), 0, st, w, O * cinw * 9, meta);
-    const int total = (O / 16) * 9 * 2 * 64 * 4;
-    hipLaunchKernelGGL(l0_pack_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, O, cinw, meta, (_Float16*)dst);
-    return hipGetLastError();
-}
 
 bool refine_l0_fused_ok(int S, int c, int K) { return c == 64 && S >= 32 && S % 32 == 0 && K >= 1 && K <= 9; }
 

@@ -707,21 +707,6 @@ hipError_t launch_l0_latent_wgrad(hipStream_t st, const float* Rc, const float* 
     return hipGetLastError();
 }
 
-// gw[co][ci][tap] += alpha * tmp[ci][tap*C + co]  for the latent channels (tmp = z^T . RT)
-__global__ void l0_scatter_z_kernel(const float* __restrict__ tmp, int L, int C, float alpha, float* __restrict__ gw)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= L * 9 * C) return;
-    const int co = i % C, tap = (i / C) % 9, ci = i / (9 * C);
-    gw[((size_t)co * (L + 2) + ci) * 9 + tap] += alpha * tmp[i];
-}
-
-hipError_t launch_l0_scatter_z(hipStream_t st, const float* tmp, int L, int C, float alpha, float* gw)
-{
-    hipLaunchKernelGGL(l0_scatter_z_kernel, dim3((L * 9 * C + 255) / 256), dim3(256), 0, st, tmp, L, C, alpha, gw);
-    return hipGetLastError();
-}
-
 // coordinate-channel weights and the bias of layer 0 from D[p][c].  Stage 1: block b walks the pixels p = b, b + NB, ...
 // with thread = (channel, pixel lane) so that D is read in full rows (the one-block-per-channel form read one float per
 // 256-byte row: 151 us for a 4 MB map); 19 sums per channel (9 taps x {x, y} + bias) -> partial[b][19][C].
@@ -876,12 +861,6 @@ hipError_t launch_scale(hipStream_t st, const float* a, float alpha, float* o, i
     return hipGetLastError();
 }
 
-__global__ void axpy_kernel(const float* __restrict__ x, float alpha, float* __restrict__ y, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) y[i] += alpha * x[i];
-}
-
 // y = (accumulate ? y : 0) + alpha * (*alpha_dev) * x : the hand-over of the accumulated gradients to the caller's flat
 // buffer with autograd's incoming grad_output read from device memory (no host round trip, no separate zero-fill)
 __global__ void axpy_dev_kernel(const float* __restrict__ x, float alpha, const float* __restrict__ alpha_dev,
@@ -912,13 +891,6 @@ __global__ void mean2_kernel(const float* __restrict__ a, const float* __restric
 hipError_t launch_mean2(hipStream_t st, const float* a, const float* b, int n, float* out)
 {
     hipLaunchKernelGGL(mean2_kernel, dim3(2), dim3(64), 0, st, a, b, n, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_axpy(hipStream_t st, const float* x, float alpha, float* y, int n)
-{
-    IOD_XSKIP(64);
-    hipLaunchKernelGGL(axpy_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x, alpha, y, n);
     return hipGetLastError();
 }
 
