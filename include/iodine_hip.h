@@ -91,8 +91,11 @@ int iodine_param_info(const iodine_handle* h, int index, const char** name, int*
  * dev_ptrs[i] is the i-th parameter (state_dict order, reference shapes, contiguous fp32). */
 int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev_ptrs, int n);
 
-/* Workspace: mode 0 = inference (reconstruct/decode), 1 = training.  If no workspace is installed the
- * library allocates one itself on first use (never inside the refinement loop). */
+/* Workspace: mode 0 = inference (reconstruct/decode/elbo), 1 = training, 2 = decoder backward: what a decode / elbo that runs with
+ * option "save_for_backward" and its iodine_decode_backward / iodine_elbo_backward need - the inference carve-up plus the scratch of
+ * ONE weight-gradient pass of the decoder (partial tiles, fold scratch, the broadcast layer's slot-summed maps); at the same shape
+ * bytes(0) <= bytes(2) <= bytes(1).  If no workspace is installed the library allocates one itself on first use (never inside the
+ * refinement loop). */
 size_t iodine_workspace_bytes(const iodine_handle* h, int batch, int mode);
 int iodine_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes);
 
@@ -125,6 +128,32 @@ int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, flo
  * iodine_last_elbo_outputs. */
 int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const float* post_mean, const float* post_logvar,
                 const float* eps, float* terms);
+
+/* Autograd through ONE decode / elbo (in the reference both are plain autograd code: model.decode(z) back-propagates into z and the
+ * decoder weights, model.elbo(x).backward() fills the decoder weight gradients and posterior.mean.grad / .logvar.grad,
+ * iodine.py:59-71,161-241).  Call order, as for the training pair: set option "save_for_backward" to 1, run iodine_decode /
+ * iodine_elbo (same launches and outputs, bit for bit; the workspace is planned in mode 2 and z, the decoder activations and the
+ * decoder output stay in it - after such a decode iodine_last_elbo_outputs has nothing to read), then call the matching backward
+ * ONCE.  Any compute call in between (reconstruct, decode, elbo, train_forward, a backward), iodine_set_params, a re-planned workspace
+ * or a changed run shape discards the saved pass: the backward then returns IODINE_ERR_STATE, as does a second backward or one with
+ * nothing to differentiate.
+ *
+ * iodine_decode_backward: g_pred (B,3,S,S), g_mask (B,K,1,S,S), g_mean (B,K,3,S,S) = the caller's gradients wrt the three outputs of
+ * the saved decode, NCHW, any of them NULL = zero.  Rendering backward, ONE decoder pass (data + every weight gradient), then
+ * dz (B,K,L) = d / dz (may be NULL) and flat_grads (may be NULL; the layout of iodine_train_backward_flat: all parameters back to
+ * back) = (accumulate ? flat_grads : 0) + d / d params.  Only decoder.* can be non-zero: the other parameters receive 0 when not
+ * accumulating and are not touched when accumulating. */
+int iodine_decode_backward(iodine_handle* h, void* stream, int batch, const float* g_pred, const float* g_mask, const float* g_mean,
+                           float* dz, float* flat_grads, int accumulate);
+
+/* model.elbo(x).backward() for the saved iodine_elbo.  grad_out_dev: autograd's incoming d(out) / d(ELBO), one float in DEVICE memory
+ * (NULL = 1; read by the final writes, no host round trip).  g_post_mean / g_post_logvar (B,K,L; either may be NULL) = grad_out x
+ * d ELBO / d (post_mean, post_logvar) with the batch-mean convention of iodine.py:193,220: (dz - mu) / B and
+ * (dz * 1/2 exp(logvar / 2) eps - 1/2 (exp(logvar) - 1)) / B, dz = d(B * ELBO) / dz.  flat_grads (may be NULL) as above, times
+ * grad_out; when the ELBO sampled from the initial posterior (post_mean = post_logvar = NULL) posterior.init_mean / init_logvar
+ * receive the sums of the two posterior gradients over (B, K). */
+int iodine_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_dev, float* g_post_mean, float* g_post_logvar,
+                         float* flat_grads, int accumulate);
 
 /* self.z / self.mean / self.mask / self.mask_logits and pred of the LAST elbo() call (iodine.py:171-187,225) -- the one made by
  * iodine_elbo, the last refinement iteration of iodine_reconstruct (NOT its final decode: the reference's logger shows the
@@ -215,6 +244,8 @@ int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, i
  * "graph" (1: replay the fixed-shape launch sequence of reconstruct / decode / elbo / train_forward / train_backward through a
  * hipGraph per distinct argument tuple -- first call eager, second captured, later ones one hipGraphLaunch; needs a non-default
  * stream; ignored while "profile" is on; 0 -- default),
+ * "save_for_backward" (1: the following iodine_decode / iodine_elbo calls keep their state for iodine_decode_backward /
+ * iodine_elbo_backward - workspace mode 2, see there; 0 -- default: the inference forms, unchanged),
  * "profile" (bracket kernel launches with HIP events on the launch stream: 1 = the dominant "conv_tile_*" launches only --
  * 54 of ~330 per training step, what bench.py keeps on inside its timed region; 2 = every category; 0 = off),
  * "conv_precision" (3x3 convs of the decoder and refinement stacks: 0 = exact fp32 MFMA -- IEEE fp32 products, fp32 accumulate,
@@ -279,7 +310,7 @@ int iodine_set_option(iodine_handle* h, const char* key, double value);
  * "pixel_pass1", "pixel_pass2", "refine_l0" (first refinement layer), "refine_l0f" (encoding + first refinement layer in one
  * kernel, option refine_l0_fused), "refine_conv" (the others), "refine_head", "refine_wgrad", "refine_dgrad", "refine_bwd01"
  * (fused layer-1 data gradient + layer-0 weight gradient, option refine_bwd_fused), "refine_bias_grad", "head_bwd", "gen_conv"
- * (the fp32 convs of the generic path), "gen_conv_f16x3" (its split-fp16 launches, option gen_conv_precision 1), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward).  "seen:<category>" returns in *launches the number of launches of <category> since the
+ * (the fp32 convs of the generic path), "gen_conv_f16x3" (its split-fp16 launches, option gen_conv_precision 1), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward), "render_bwd" (backward of the rendering - sigmoid, slot softmax, sum_k mask x mean - in iodine_decode_backward; the decoder pass behind it is booked under the categories of the training step).  "seen:<category>" returns in *launches the number of launches of <category> since the
  * last reset, bracketed or not (option profile_stride; counted at profile levels 1 -- the bracketed categories -- and 2 -- all).  Synchronises on the recorded events.  Two more names report
  * the hipGraph bookkeeping of option "graph" in *launches: "graph_captures" (graphs instantiated) and "graph_replays". */
 int iodine_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset);
@@ -338,6 +369,13 @@ int iodine_op_gen_conv(void* stream, int mode, const float* in_nhwc, const float
  * not fit the LDS (7 x 7 with 64 channels).  Kernel-level tests only: it allocates, synchronises and frees per call -- not for timing. */
 int iodine_op_gen_conv_f16x3(void* stream, int mode, const float* in_nhwc, const float* w_oihw, const float* bias, const float* aux,
                              float* out_nhwc, float* gb, int n, int si, int ci, int ldc, int co, int k, int s, int elu);
+
+/* backward of the rendering step of decode (kernels_render.hip): dec_out [batch * slots][pixels][4] as the decoder leaves it, g_pred
+ * (batch,3,pixels), g_mask (batch,slots,1,pixels), g_mean (batch,slots,3,pixels) NCHW (any may be NULL = zero) -> g_out
+ * [batch * slots][pixels][4] = gradient wrt dec_out; strict = 1: libm expf + IEEE division (conv_precision 0), 0: the default path's
+ * v_exp_f32 / v_rcp_f32.  Synchronises. */
+int iodine_op_render_bwd(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean, float* g_out,
+                         int batch, int slots, int pixels, int strict);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@ EXPORTS = (
     'iodine_adam_step', 'iodine_ari_table', 'iodine_set_option', 'iodine_profile_read', 'iodine_debug_copy', 'iodine_linspace_host', 'iodine_op_conv3x3', 'iodine_op_dec_out',
     'iodine_op_conv3x3_wgrad', 'iodine_op_conv3x3_wgrad_f32', 'iodine_op_dec_out_f16x3', 'iodine_op_gen_conv', 'iodine_op_gen_conv_f16x3',
     'iodine_grad_norm_scratch_bytes', 'iodine_grad_norm', 'iodine_grad_scale', 'iodine_adam_step_clipped',
+    'iodine_decode_backward', 'iodine_elbo_backward', 'iodine_op_render_bwd',
 )
 
 
@@ -87,6 +88,9 @@ def lib() -> C.CDLL:
     L.iodine_train_backward.argtypes = [vp, vp, cf, C.POINTER(vp), ci]
     L.iodine_train_backward_flat.argtypes = [vp, vp, vp, vp, ci]
     L.iodine_logger_scalars.argtypes = [vp, vp, vp]
+    L.iodine_decode_backward.argtypes = [vp, vp, ci] + [vp] * 5 + [ci]
+    L.iodine_elbo_backward.argtypes = [vp, vp] + [vp] * 4 + [ci]
+    L.iodine_op_render_bwd.argtypes = [vp] + [vp] * 5 + [ci] * 4
     L.iodine_adam_step.argtypes = [vp, vp, vp, ci, C.c_longlong] + [C.c_double] * 5 + [ci]
     L.iodine_grad_norm_scratch_bytes.argtypes = [C.c_longlong]
     L.iodine_grad_norm_scratch_bytes.restype = C.c_size_t

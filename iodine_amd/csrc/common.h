@@ -189,6 +189,13 @@ hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec,
                               int strict = 0);
 hipError_t launch_final_out(hipStream_t st, const float* dec, float* pred, float* mask, float* mean, float* logits,
                             int B, int K, int P);
+// kernels_render.hip: backward of the rendering (sigmoid, slot softmax, sum_k mask * mean) for the caller's gradients wrt pred (B,3,S,S),
+// mask (B,K,1,S,S), mean (B,K,3,S,S) - NCHW, any of them NULL = zero - into g [N][P][4]; strict as for launch_pixel_pass1
+hipError_t launch_render_bwd(hipStream_t st, const float* dec, const float* g_pred, const float* g_mask, const float* g_mean, float* g,
+                             int B, int K, int P, int strict);
+// dz = Rc . wclsT without the KL / layer-norm terms of launch_dz_latent; pm != NULL: the posterior gradients of one ELBO instead (scale = 1 / B)
+hipError_t launch_dz_plain(hipStream_t st, const float* Rc, const float* wclsT, int N, int L, int C, float* dz_out, const float* pm,
+                           const float* plv, const float* eps, float scale, float* g_pm, float* g_plv);
 // kernels_misc.hip
 hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P);
 hipError_t launch_posterior_init(hipStream_t st, const float* im, const float* ilv, float* pm, float* plv, float* h,

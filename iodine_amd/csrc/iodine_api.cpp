@@ -169,6 +169,12 @@ struct iodine_handle {
     size_t gacc_total = 0;
     bool fwd_done = false;
     int fwd_batch = 0;
+    // a single decode / elbo that ran "for backward" (option save_for_backward): its z, decoder activations and dec_out stay in the arena
+    // (workspace mode 2) until the next compute call; iodine_decode_backward / iodine_elbo_backward consume it
+    int save_bwd = 0;                           // the option
+    int diff_kind = 0;                          // 0 = nothing saved, 1 = a decode, 2 = an elbo
+    int diff_batch = 0;
+    bool diff_init = false;                     // the saved elbo sampled from the initial posterior (init_mean / init_logvar receive gradients)
     // last elbo() call (iodine.py:161-241): which z buffer / batch the decoder output in buf.dec_out belongs to
     int last_elbo_iter = -1, last_elbo_batch = 0;
     bool enc_valid = false;                     // the last call left the refinement input ("enc") of its iterations in the workspace
@@ -470,7 +476,7 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
     b.img_terms = a.take<float>((size_t)(T + 1) * B * 2);
     b.scal = a.take<float>((size_t)(T + 1) * 3 + 4);
     b.rows = a.take<float>((size_t)N * h->S * 3 * Cd);
-    b.rows_p = a.take<float>((size_t)N * h->S * (h->S / 16 > 0 ? h->S / 16 : 1) * (mode == 1 ? 4 : 3) * Cd);   // per-tile row sums (EPI_L0ROWS / EPI_L0ROWSX)
+    b.rows_p = a.take<float>((size_t)N * h->S * (h->S / 16 > 0 ? h->S / 16 : 1) * (mode != 0 ? 4 : 3) * Cd);   // per-tile row sums (EPI_L0ROWS / EPI_L0ROWSX)
     b.l0scr = a.take<float>(l0_rows_scratch_floats(N, Cd));
     b.Rc = a.take<float>((size_t)N * 9 * Cd);
     b.pm = a.take<float>((size_t)N * L);
@@ -544,14 +550,16 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
             for (int i = 0; i <= T; ++i) b.ract[i][l] = (mode == 1 && i < T) ? (base ? base + (size_t)i * n_l : nullptr) : base;
         }
     }
-    if (mode == 1) {
+    if (mode != 0) {
+        // what one weight-gradient pass of the decoder needs: training, and mode 2 = "decoder backward" (a single decode / elbo kept for
+        // iodine_decode_backward / iodine_elbo_backward): the inference carve-up plus this block
         const int Cmax = Cd > Cr ? Cd : Cr;
         const size_t part_elems = (size_t)512 * 4 * 9 * 32 * 32 > (size_t)512 * 9 * Cmax * Cmax
                                       ? (size_t)512 * 4 * 9 * 32 * 32 : (size_t)512 * 9 * Cmax * Cmax;
         b.wg_part = a.take<float>(part_elems);
         b.wg_part_b = a.take<float>((size_t)512 * 64);
         b.wg_acc.assign(h->Dd, nullptr); b.wg_acc_b.assign(h->Dd, nullptr);
-        if (h->wgrad_accum && !gen_dec) {
+        if (h->wgrad_accum && !gen_dec && mode == 1) {      // (a single pass has nothing to accumulate over: shared scratch)
             b.wg_acc[0] = a.take<float>((size_t)1024 * 2 * 9 * Cd * 4);       // dec_out_bwd_fused: <= 1024 blocks x KS <= 2 tiles of [9][Cd][4]
             b.wg_acc_b[0] = a.take<float>((size_t)1024 * 4);
             for (int l = 1; l < h->Dd; ++l) {
@@ -566,6 +574,8 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
         b.Rsum = a.take<float>((size_t)h->S * 4 * Cd);
         b.RT = a.take<float>((size_t)N * 9 * Cd);
         b.tmp_lz = a.take<float>((size_t)L * 9 * Cd);
+    }
+    if (mode == 1) {
         // ddm / ddv / dgates / ds: one instance per iteration (weight gradients of the head in one pass over all of them)
         b.ddm = a.take<float>((size_t)T * N * L); b.ddv = a.take<float>((size_t)T * N * L);
         b.dc1 = a.take<float>((size_t)N * H); b.dgates = a.take<float>((size_t)T * N * 4 * H);
@@ -579,10 +589,10 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
     if (gen_dec) {
         b.gen_l0 = a.take<float>(gen_l0_scratch_floats(N, h->S, Cd, h->kd));   // row / tap sums, prefix table of the broadcast layer
     }
-    if ((gen_dec || h->gen_ref) && mode == 1) {
+    if ((gen_dec || h->gen_ref) && mode != 0) {
         size_t scr = 0;
         if (gen_dec) scr = std::max(gen_wgrad_scratch_floats(Cd, 4, h->kd), gen_wgrad_scratch_floats(Cd, Cd, h->kd));
-        if (h->gen_ref) scr = std::max(scr, std::max(gen_wgrad_scratch_floats(17, Cr, h->kr), gen_wgrad_scratch_floats(Cr, Cr, h->kr)));
+        if (h->gen_ref && mode == 1) scr = std::max(scr, std::max(gen_wgrad_scratch_floats(17, Cr, h->kr), gen_wgrad_scratch_floats(Cr, Cr, h->kr)));
         b.gen_scr = a.take<float>(scr);
     }
     b.bytes = (a.off + 255) & ~(size_t)255;
@@ -621,7 +631,7 @@ int ensure_workspace(iodine_handle* h, int B, int mode)
     }
     Arena a(base);
     plan(h, B, mode, a, h->buf);
-    h->fwd_done = false;                 // a re-planned arena no longer holds the saved forward / the last elbo() outputs
+    h->fwd_done = false; h->diff_kind = 0;                 // a re-planned arena no longer holds the saved forward / the last elbo() outputs
     h->last_elbo_iter = -1;
     h->enc_valid = false;
     // captured graphs stay: their key holds the arena's base address, the batch, the run shape and (through the entry point) the mode,
@@ -673,7 +683,7 @@ int decoder_forward(iodine_handle* h, hipStream_t st, int N, const float* z, flo
 // the same on the generic fallback path: plain chain of data gradients (and, in training, weight gradients with the pass factor);
 // the broadcast layer's weight gradient and the gradient wrt z come from the tap-window sums of its pre-activation gradient
 // (kernels_genl0.hip); dz is left in the first L entries of every row of buf.Rc (dz_latent multiplies that by the identity in h->gen_ident)
-int decoder_backward_generic(iodine_handle* h, hipStream_t st, int N, float train_alpha, int it)
+int decoder_backward_generic(iodine_handle* h, hipStream_t st, int N, float train_alpha, int it)   // it: only b.z[it], the decoded z
 {
     Buffers& b = h->buf;
     const ParamSlots& ps = h->slot;
@@ -706,8 +716,11 @@ int decoder_backward_generic(iodine_handle* h, hipStream_t st, int N, float trai
 // the shared scratch, reduced with the pass factor straight away
 struct WgradPass { float *part, *part_b; float alpha; int accum; float reduce_alpha; bool reduce; };
 
-int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0, float train_alpha, int it)
+// single: the pass is the only one of its backward (iodine_decode_backward / iodine_elbo_backward) - first (overwrite the maps accumulated
+// over the passes) and last (emit the coordinate / bias gradients, reduce the kept partial tiles) at once; `it` then only names the z buffer
+int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0, float train_alpha, int it, bool single = false)
 {
+    const bool first = single || it == 0, last = single || it == h->T;
     Buffers& b = h->buf;
     const ParamSlots& ps = h->slot;
     const int Cd = h->Cd, Dd = h->Dd;
@@ -719,7 +732,7 @@ int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0
     const bool out_fused = train && dec_f16(path) && h->out_bwd_fused;
     const bool acc_w = train && h->wgrad_accum && !b.wg_acc.empty() && b.wg_acc[0];
     auto wgrad_pass = [&](bool acc, int l) {
-        return acc ? WgradPass{b.wg_acc[l], b.wg_acc_b[l], train_alpha, it != 0, 1.f, it == h->T}
+        return acc ? WgradPass{b.wg_acc[l], b.wg_acc_b[l], train_alpha, !first, 1.f, last}
                    : WgradPass{b.wg_part, b.wg_part_b, 1.f, 0, train_alpha, true};
     };
     // output conv: only the fused kernel takes a pass factor, so the separate weight-gradient kernels reduce per pass
@@ -763,12 +776,12 @@ int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0
     }
     if (fused_l0) {
         PROF(h, st, "l0_reduce", launch_l0_reduce_cls_tiles_x(st, b.rows_p, b.Rc, b.rown, N, h->S, Cd, b.l0scr));
-        HIPCHK(h, launch_l0_rowsum_acc(st, b.rown, N, h->S, Cd, train_alpha, it == 0, b.Rsum));
+        HIPCHK(h, launch_l0_rowsum_acc(st, b.rown, N, h->S, Cd, train_alpha, first, b.Rsum));
     } else
     // row / class sums of dpre0 for dz; in training the same read also feeds the slot-summed gradient map, which is
     // accumulated (with this pass's factor) over the T+1 passes and consumed once after the last one
     PROF(h, st, "l0_reduce", launch_l0_reduce(st, *dpre0, b.rows, b.Rc, N, h->S, Cd, train ? b.Dpart : nullptr,
-                                              b.Dsum, train_alpha, it == 0));
+                                              b.Dsum, train_alpha, first));
     if (train) {
         // layer 0 (spatial broadcast): latent-channel weights from z and the per-tap sums, coordinate channels
         // and bias from the slot-summed gradient map
@@ -778,7 +791,7 @@ int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0
             HIPCHK(h, launch_sgemm_tn_mfma(st, h->L, 9 * Cd, N, train_alpha, b.z[it], h->L, b.RT, 9 * Cd, 1.f, gw, h->L + 2, 1, Cd));
         } else                                              // (round 6) tap sums + product + scatter in one launch
             HIPCHK(h, launch_l0_latent_wgrad(st, b.Rc, b.z[it], N, h->L, Cd, train_alpha, gw));
-        if (it == h->T) {
+        if (last) {
             if (fused_l0) HIPCHK(h, launch_l0_coord_grads_rows(st, b.Rsum, h->lin, h->S, Cd, h->L, 1.f, gw, gb));
             else HIPCHK(h, launch_l0_coord_grads(st, b.Dsum, h->lin, h->S, Cd, h->L, 1.f, gw, gb, b.wg_part));
         }
@@ -934,6 +947,9 @@ int run_graphed(iodine_handle* h, hipStream_t st, const std::vector<uintptr_t>& 
     HIPCHK(h, hipGraphLaunch(ge.exec, st));
     return IODINE_OK;
 }
+
+// first element of a graph key: the entry point (1, 4, 5: reconstruct, train forward, train backward)
+enum { GK_DECODE = 2, GK_ELBO = 3, GK_DECODE_SAVED = 6, GK_ELBO_SAVED = 7, GK_DECODE_BWD = 8, GK_ELBO_BWD = 9 };
 
 std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, std::initializer_list<const void*> ptrs)
 {
@@ -1469,7 +1485,7 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
     HIPCHK(h, launch_multi_copy(st, mc));
     if (!pj.empty()) HIPCHK(h, launch_pack_batch(st, pj.data(), (int)pj.size()));      // (behind ref_split / enc_expand: stream order)
     h->params_set = true;
-    h->fwd_done = false;
+    h->fwd_done = false; h->diff_kind = 0;
     return IODINE_OK;
 }
 
@@ -1488,7 +1504,7 @@ int iodine_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes)
     if (h->shim) return shim_fail(h, iodine_set_workspace(h->shim->inner, dev_ptr, bytes));
     h->ws_user = dev_ptr; h->ws_user_bytes = dev_ptr ? bytes : 0;
     h->buf = Buffers();
-    h->fwd_done = false;
+    h->fwd_done = false; h->diff_kind = 0;
     h->last_elbo_iter = -1;
     return IODINE_OK;                    // graphs are keyed by the arena address (see ensure_workspace)
 }
@@ -1504,7 +1520,7 @@ int iodine_set_run_shape(iodine_handle* h, int slots, int iters)
         const int rc = iodine_set_run_shape(h->shim->inner, slots, iters);
         if (rc) return shim_fail(h, rc);
     } else if (slots != h->K || iters != h->T) {
-        h->fwd_done = false;             // a pending training forward ran at the old shape: its backward is refused (IODINE_ERR_STATE)
+        h->fwd_done = false; h->diff_kind = 0;             // a pending training forward ran at the old shape: its backward is refused (IODINE_ERR_STATE)
     }
     // the workspace is re-planned by the next compute call (ensure_workspace keys on the run shape); the state of the last call
     // stays readable at the shape it was produced with (buf.K / buf.T)
@@ -1523,6 +1539,7 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
     if (!strcmp(key, "xskip")) { g_iod_xskip = (int)value; return IODINE_OK; }       // timing-only ablation builds (common.h)
 #endif
     if (!strcmp(key, "out_bwd_fused")) { h->out_bwd_fused = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "save_for_backward")) { h->save_bwd = value != 0; return IODINE_OK; }
     if (!strcmp(key, "fuse_l0")) { h->fuse_l0 = value != 0; return IODINE_OK; }
     if (!strcmp(key, "refine_split")) { h->refine_split = value != 0; return IODINE_OK; }
     if (!strcmp(key, "head_fused")) { h->head_fused = value != 0; return IODINE_OK; }
@@ -1536,7 +1553,7 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
     if (!strcmp(key, "refine_ws")) { h->refine_ws = value != 0; return IODINE_OK; }
     if (!strcmp(key, "dec_out_rows")) { h->dec_out_rows = value != 0; return IODINE_OK; }
     if (!strcmp(key, "wgrad_accum")) {
-        if (h->wgrad_accum != (value != 0)) { h->buf = Buffers(); h->fwd_done = false; h->last_elbo_iter = -1; h->enc_valid = false; }   // the arena is re-planned
+        if (h->wgrad_accum != (value != 0)) { h->buf = Buffers(); h->fwd_done = false; h->diff_kind = 0; h->last_elbo_iter = -1; h->enc_valid = false; }   // the arena is re-planned
         h->wgrad_accum = value != 0; return IODINE_OK;
     }
     if (!strcmp(key, "conv_variant")) {
@@ -1583,7 +1600,7 @@ int iodine_reconstruct(iodine_handle* h, void* stream, int batch, const float* x
     if (!x || !eps) return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct: x and eps are required");
     rc = ensure_workspace(h, batch, 0);
     if (rc) return rc;
-    h->fwd_done = false;                                   // the arena is re-used: a saved training forward is gone
+    h->fwd_done = false; h->diff_kind = 0;                                   // the arena is re-used: a saved training forward is gone
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K, T = h->T;
     const bool partial = h->stop_after >= 0 && h->stop_after <= T;     // debug: stop before the final sample/decode
@@ -1636,20 +1653,29 @@ int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, flo
     int rc = check_ready(h, batch);
     if (rc) return rc;
     if (!z) return h->fail(IODINE_ERR_INVALID, "iodine_decode: z is required");
-    rc = ensure_workspace(h, batch, 0);
+    const bool save = h->save_bwd != 0;                    // option save_for_backward: keep what iodine_decode_backward reads (workspace mode 2)
+    rc = ensure_workspace(h, batch, save ? 2 : 0);
     if (rc) return rc;
-    h->fwd_done = false;
+    h->fwd_done = false; h->diff_kind = 0;
     hipStream_t st = (hipStream_t)stream;
     const int N = batch * h->K;
     auto body = [&]() -> int {
         Buffers& b = h->buf;
+        // plain: into the (free) gradient buffer - buf.dec_out belongs to the last elbo() call; saved: buf.dec_out (buf.g is the backward's)
+        // and z kept in buf.z[0].  The launches are the same.
+        float* out = save ? b.dec_out : b.g;
+        if (save) HIPCHK(h, hipMemcpyAsync(b.z[0], z, sizeof(float) * (size_t)N * h->L, hipMemcpyDeviceToDevice, st));
         HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, z, h->wcls, nullptr, b.V, N, h->L, h->Cd));
-        const int r = decoder_forward(h, st, N, z, b.g);      // not buf.dec_out: that belongs to the last elbo() call
+        const int r = decoder_forward(h, st, N, z, out);
         if (r) return r;
-        HIPCHK(h, launch_final_out(st, b.g, pred, mask, mean, nullptr, batch, h->K, h->P));
+        HIPCHK(h, launch_final_out(st, out, pred, mask, mean, nullptr, batch, h->K, h->P));
         return IODINE_OK;
     };
-    return run_graphed(h, st, graph_key(h, 2, batch, {z, pred, mask, mean}), body);
+    if (save) h->last_elbo_iter = -1;                      // buf.dec_out no longer belongs to an elbo() call
+    rc = run_graphed(h, st, graph_key(h, save ? GK_DECODE_SAVED : GK_DECODE, batch, {z, pred, mask, mean}), body);
+    if (rc) return rc;
+    if (save) { h->diff_kind = 1; h->diff_batch = batch; }
+    return IODINE_OK;
 }
 
 int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const float* post_mean, const float* post_logvar,
@@ -1675,9 +1701,10 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     if (!x || !eps) return h->fail(IODINE_ERR_INVALID, "iodine_elbo: x and eps are required");
     if ((post_mean == nullptr) != (post_logvar == nullptr))
         return h->fail(IODINE_ERR_INVALID, "iodine_elbo: pass both post_mean and post_logvar, or neither");
-    rc = ensure_workspace(h, batch, 0);
+    const bool save = h->save_bwd != 0;                    // option save_for_backward: keep what iodine_elbo_backward reads (workspace mode 2)
+    rc = ensure_workspace(h, batch, save ? 2 : 0);
     if (rc) return rc;
-    h->fwd_done = false;
+    h->fwd_done = false; h->diff_kind = 0;
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K;
     auto body = [&]() -> int {
@@ -1692,13 +1719,139 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
         const int r = elbo_and_gradients(h, st, B, eps, 0, false);
         if (r) return r;
         if (terms) HIPCHK(h, hipMemcpyAsync(terms, b.scal, sizeof(float) * 3, hipMemcpyDeviceToDevice, st));
+        // kept for iodine_elbo_backward: z (buf.z[0]), the activations, dec_out, d(B * ELBO) / d dec_out (buf.g), the posterior (buf.pm / plv)
+        // and the noise - the caller's tensor may be gone by then; buf.latent[0] has no other use in a single elbo
+        if (save) HIPCHK(h, hipMemcpyAsync(b.latent[0], eps, sizeof(float) * (size_t)N * h->L, hipMemcpyDeviceToDevice, st));
         return IODINE_OK;
     };
-    rc = run_graphed(h, st, graph_key(h, 3, B, {x, post_mean, post_logvar, eps, terms}), body);
+    rc = run_graphed(h, st, graph_key(h, save ? GK_ELBO_SAVED : GK_ELBO, B, {x, post_mean, post_logvar, eps, terms}), body);
     if (rc) return rc;
     h->last_elbo_iter = 0;
     h->last_elbo_batch = B;
+    if (save) { h->diff_kind = 2; h->diff_batch = B; h->diff_init = post_mean == nullptr; }
     return IODINE_OK;
+}
+
+namespace {
+
+// the state a single-pass backward needs: a decode / elbo that ran with option save_for_backward and nothing since
+int diff_ready(iodine_handle* h, int kind, const char* who)
+{
+    if (!h->params_set) return h->fail(IODINE_ERR_STATE, std::string(who) + ": iodine_set_params has not been called");
+    if (h->diff_kind != kind)
+        return h->fail(IODINE_ERR_STATE, std::string(who) + (kind == 1 ? ": no iodine_decode" : ": no iodine_elbo") +
+                                             " with option save_for_backward to differentiate (none has run, another compute call has re-used "
+                                             "the workspace since, or it was differentiated already)");
+    if (h->buf.mode != 2 || h->buf.B != h->diff_batch || h->buf.K != h->K)
+        return h->fail(IODINE_ERR_STATE, std::string(who) + ": the workspace of the forward pass was re-planned");
+    return IODINE_OK;
+}
+
+// caller's flat gradient buffer <- the accumulators.  Only the decoder and the initial posterior (the tail of the parameter table) can
+// have received anything: when accumulating, the refinement network's gradients are not touched at all; otherwise they are written as 0
+int diff_flat_out(iodine_handle* h, hipStream_t st, const float* scale_dev, float* flat, int accumulate)
+{
+    const size_t first = accumulate ? (size_t)(h->gacc[h->slot.dec_w[0]] - h->gacc_arena) : 0;
+    HIPCHK(h, launch_axpy_dev(st, h->gacc_arena + first, 1.f, scale_dev, flat + first, (int)(h->gacc_total - first), accumulate));
+    return IODINE_OK;
+}
+
+// the same for the boundary of a padded inner handle: padded flat gradient -> the caller's reference-shaped one
+int shim_flat_out(iodine_handle* h, hipStream_t st, float* flat, int accumulate)
+{
+    PadShim* sh = h->shim;
+    size_t off = 0;
+    for (size_t p = 0; p < h->params.size(); ++p) {
+        if (!accumulate || (int)p >= h->slot.dec_w[0])
+            HIPCHK(h, launch_pad_scatter(st, sh->pgrad + sh->poff[p], sh->pmap[p], flat + off, sh->pnumel[p], accumulate));
+        off += h->params[p].numel();
+    }
+    return IODINE_OK;
+}
+
+}  // namespace
+
+int iodine_decode_backward(iodine_handle* h, void* stream, int batch, const float* g_pred, const float* g_mask, const float* g_mean,
+                           float* dz, float* flat_grads, int accumulate)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (h->shim) {
+        PadShim* sh = h->shim;
+        const int rc = iodine_decode_backward(sh->inner, stream, batch, g_pred, g_mask, g_mean, dz ? sh->z : nullptr,
+                                              flat_grads ? sh->pgrad : nullptr, 0);
+        if (rc) return shim_fail(h, rc);
+        if (dz) HIPCHK(h, launch_resize_rows(st, sh->z, dz, (long long)batch * h->K, sh->Lp, sh->L));
+        return flat_grads ? shim_flat_out(h, st, flat_grads, accumulate) : IODINE_OK;
+    }
+    int rc = diff_ready(h, 1, "iodine_decode_backward");
+    if (rc) return rc;
+    if (batch != h->diff_batch) return h->fail(IODINE_ERR_INVALID, "iodine_decode_backward: batch differs from the decode it differentiates");
+    const int B = batch, N = B * h->K;
+    std::vector<uintptr_t> key = graph_key(h, GK_DECODE_BWD, B, {g_pred, g_mask, g_mean, dz, flat_grads});
+    key.push_back((uintptr_t)accumulate);
+    auto body = [&]() -> int {
+        Buffers& b = h->buf;
+        if (flat_grads) HIPCHK(h, hipMemsetAsync(h->gacc_arena, 0, sizeof(float) * h->gacc_total, st));
+        PROF(h, st, "render_bwd", launch_render_bwd(st, b.dec_out, g_pred, g_mask, g_mean, b.g, B, h->K, h->P, h->precision == 0));
+        float* dpre0 = nullptr;
+        // ONE decoder pass with factor 1: data gradient down to the class sums of the broadcast layer, every decoder weight gradient on the way
+        const int r = decoder_backward_data(h, st, N, &dpre0, flat_grads ? 1.f : 0.f, 0, true);
+        if (r) return r;
+        if (dz)
+            HIPCHK(h, launch_dz_plain(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, h->L, h->Cd, dz, nullptr, nullptr, nullptr,
+                                      1.f, nullptr, nullptr));
+        return flat_grads ? diff_flat_out(h, st, nullptr, flat_grads, accumulate) : IODINE_OK;
+    };
+    rc = run_graphed(h, st, key, body);
+    h->diff_kind = 0;                                      // consumed, like autograd without retain_graph (buf.g and the accumulators were overwritten)
+    return rc;
+}
+
+int iodine_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_dev, float* g_post_mean, float* g_post_logvar,
+                         float* flat_grads, int accumulate)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (h->shim) {
+        PadShim* sh = h->shim;
+        iodine_handle* in = sh->inner;
+        const long long N = (long long)in->diff_batch * in->buf.K;       // (checked by the inner call before anything is written)
+        const int rc = iodine_elbo_backward(in, stream, grad_out_dev, g_post_mean ? sh->pm : nullptr, g_post_logvar ? sh->plv : nullptr,
+                                            flat_grads ? sh->pgrad : nullptr, 0);
+        if (rc) return shim_fail(h, rc);
+        if (g_post_mean) HIPCHK(h, launch_resize_rows(st, sh->pm, g_post_mean, N, sh->Lp, sh->L));
+        if (g_post_logvar) HIPCHK(h, launch_resize_rows(st, sh->plv, g_post_logvar, N, sh->Lp, sh->L));
+        return flat_grads ? shim_flat_out(h, st, flat_grads, accumulate) : IODINE_OK;
+    }
+    int rc = diff_ready(h, 2, "iodine_elbo_backward");
+    if (rc) return rc;
+    const int B = h->diff_batch, N = B * h->K;
+    std::vector<uintptr_t> key = graph_key(h, GK_ELBO_BWD, B, {grad_out_dev, g_post_mean, g_post_logvar, flat_grads});
+    key.push_back((uintptr_t)accumulate);
+    key.push_back((uintptr_t)h->diff_init);
+    auto body = [&]() -> int {
+        Buffers& b = h->buf;
+        const ParamSlots& ps = h->slot;
+        if (flat_grads) HIPCHK(h, hipMemsetAsync(h->gacc_arena, 0, sizeof(float) * h->gacc_total, st));
+        // buf.g = d(B * ELBO) / d dec_out from pixel_pass1: ONE decoder pass, weight gradients with the factor 1 / B of the batch mean
+        float* dpre0 = nullptr;
+        const int r = decoder_backward_data(h, st, N, &dpre0, flat_grads ? 1.f / (float)B : 0.f, 0, true);
+        if (r) return r;
+        // d ELBO / d lambda (iodine.py:193,220: batch means) into the slots the refinement loop uses for them
+        HIPCHK(h, launch_dz_plain(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, h->L, h->Cd, nullptr, b.pm, b.plv, b.latent[0],
+                                  1.f / (float)B, b.g_pm[0], b.g_plv[0]));
+        if (flat_grads && h->diff_init) {                  // lambda = init_mean / init_logvar repeated over (B, K): iodine.py:615-616
+            HIPCHK(h, launch_colsum(st, b.g_pm[0], N, h->L, h->L, 1.f, h->gacc[ps.init_mean]));
+            HIPCHK(h, launch_colsum(st, b.g_plv[0], N, h->L, h->L, 1.f, h->gacc[ps.init_logvar]));
+        }
+        if (g_post_mean) HIPCHK(h, launch_axpy_dev(st, b.g_pm[0], 1.f, grad_out_dev, g_post_mean, N * h->L, 0));
+        if (g_post_logvar) HIPCHK(h, launch_axpy_dev(st, b.g_plv[0], 1.f, grad_out_dev, g_post_logvar, N * h->L, 0));
+        return flat_grads ? diff_flat_out(h, st, grad_out_dev, flat_grads, accumulate) : IODINE_OK;
+    };
+    rc = run_graphed(h, st, key, body);
+    h->diff_kind = 0;
+    return rc;
 }
 
 int iodine_last_elbo_outputs(iodine_handle* h, void* stream, int count, float* z, float* mean, float* mask,
@@ -1778,7 +1931,7 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K, T = h->T, L = h->L;
-    h->fwd_done = false;
+    h->fwd_done = false; h->diff_kind = 0;
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const size_t eps_stride = (size_t)N * L;
@@ -1976,7 +2129,7 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
     const int rc = run_graphed(h, st, key, body);
     // like autograd without retain_graph: the saved forward is consumed (a second backward would add the BPTT terms to the
     // accumulators twice); iodine_train_forward must run again first
-    h->fwd_done = false;
+    h->fwd_done = false; h->diff_kind = 0;
     return rc;
 }
 
@@ -2415,6 +2568,17 @@ int iodine_op_gen_conv_f16x3(void* stream, int mode, const float* in, const floa
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(buf);
     if (e != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv_f16x3: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_render_bwd(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean, float* g_out,
+                         int batch, int slots, int pixels, int strict)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!dec_out || !g_out || batch < 1 || slots < 1 || slots > 16 || pixels < 1) { g_create_error = "iodine_op_render_bwd: argument"; return IODINE_ERR_INVALID; }
+    hipError_t e = launch_render_bwd(st, dec_out, g_pred, g_mask, g_mean, g_out, batch, slots, pixels, strict ? 1 : 0);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_render_bwd: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
     return IODINE_OK;
 }
 

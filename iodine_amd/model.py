@@ -143,6 +143,100 @@ class _ChunkedTrainStep(torch.autograd.Function):
         return (None, None, None, *views)
 
 
+def _flat_views(module, flat, live):
+    """Per-parameter gradients for autograd: views of the one flat buffer for the parameters named by ``live`` (name prefixes), None for
+    the rest - the reference's autograd leaves .grad of a parameter the differentiated call never used at None too."""
+    views, off = [], 0
+    for n, p in module.named_parameters():
+        views.append(flat[off:off + p.numel()].view_as(p) if flat is not None and n.startswith(live) else None)
+        off += p.numel()
+    return views
+
+
+class _DecodeGrad(torch.autograd.Function):
+    """``pred, mask, mean = model.decode(z)`` with autograd into ``z`` and the decoder weights (iodine.py:59-71) through
+    iodine_decode (option save_for_backward) / iodine_decode_backward.  A batch above ``IODINE.max_batch`` is decoded in chunks and
+    each chunk is decoded AGAIN in the backward, its backward right behind it (the library keeps one saved pass)."""
+
+    @staticmethod
+    def forward(ctx, module, z, *params):
+        ctx.set_materialize_grads(False)                   # an output the loss does not use arrives as None -> a NULL pointer
+        K = int(z.shape[1])
+        T = module._shape[1] if module._shape is not None else int(module._cfg.iters)
+        ctx.module, ctx.K, ctx.T, ctx.z_dtype = module, K, T, z.dtype
+        ctx.chunks = module._chunks(z.shape[0], module.max_batch(K=K, T=T))
+        zc = z.detach().to(torch.float32).contiguous()
+        if len(ctx.chunks) == 1:
+            out = module._decode_call(zc, K, T, save=True)
+            ctx.serial = module._call_serial               # identity of the saved pass
+        else:
+            outs = [module._decode_call(zc[s:e], K, T, save=False) for s, e in ctx.chunks]
+            out = tuple(torch.cat([o[j] for o in outs], 0) for j in range(3))
+            ctx.z, ctx.versions = zc, module._param_versions
+        return out
+
+    @staticmethod
+    def backward(ctx, g_pred, g_mask, g_mean):
+        m = ctx.module
+        want_z, want_p = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+        if g_pred is None and g_mask is None and g_mean is None:
+            return (None,) * len(ctx.needs_input_grad)
+        if len(ctx.chunks) == 1:
+            dz, flat = m._decode_backward(ctx.serial, ctx.K, (g_pred, g_mask, g_mean), want_z, want_p, None)
+            flat = m._own(flat)
+        else:
+            m._sync_params(ctx.z.device)
+            if m._param_versions != ctx.versions:
+                raise RuntimeError('IODINE: backward of a stale decode - the parameters changed since the chunked decode ran (its chunks '
+                                   'are decoded again in the backward; call backward() before the optimizer step)')
+            dzs, flat = [], None
+            for s, e in ctx.chunks:
+                m._decode_call(ctx.z[s:e], ctx.K, ctx.T, save=True)
+                gs = tuple(None if g is None else g[s:e] for g in (g_pred, g_mask, g_mean))
+                dzc, flat = m._decode_backward(m._call_serial, ctx.K, gs, want_z, want_p, flat)
+                dzs.append(dzc)
+            dz = torch.cat(dzs, 0) if want_z else None
+            flat = m._own(flat)
+        return (None, None if dz is None else dz.to(ctx.z_dtype), *_flat_views(m, flat, ('decoder.',)))
+
+
+class _ElboGrad(torch.autograd.Function):
+    """``elbo = model.elbo(x)`` with autograd into ``model.posterior.mean / logvar`` (or, from the initial posterior, into
+    ``posterior.init_mean / init_logvar``) and the decoder weights (iodine.py:161-241) through iodine_elbo (option save_for_backward) /
+    iodine_elbo_backward.  The ELBO is a batch mean of independent images: a batch above ``IODINE.max_batch`` runs as chunks, each
+    chunk's forward and backward at once with its share of the batch, and ``backward`` only scales - like _ChunkedTrainStep."""
+
+    @staticmethod
+    def forward(ctx, module, x, eps, pm, plv, *params):
+        ctx.set_materialize_grads(False)
+        ctx.module, ctx.init = module, pm is None
+        want_p = any(p.requires_grad for p in params)
+        want_post = pm is not None and (pm.requires_grad or plv.requires_grad)
+        if x.shape[0] <= module.max_batch():
+            elbo = module._elbo_call(x, eps, pm, plv, save=True)
+            ctx.serial, ctx.pre, ctx.BK = module._call_serial, None, (x.shape[0], module.K)
+            return elbo
+        elbo, ctx.pre = module._elbo_chunked_grad(x, eps, pm, plv, want_post, want_p)
+        return elbo
+
+    @staticmethod
+    def backward(ctx, g):
+        m = ctx.module
+        n_in = len(ctx.needs_input_grad)
+        if g is None:
+            return (None,) * n_in
+        live = ('decoder.', 'posterior.') if ctx.init else ('decoder.',)
+        if ctx.pre is not None:                            # chunked: everything was computed with the forward
+            gs = g.to(torch.float32)
+            gpm, gplv, flat = (None if t is None else t * gs for t in ctx.pre)
+        else:
+            want_post = (not ctx.init) and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+            gpm, gplv, flat = m._elbo_backward(ctx.serial, ctx.BK, g, want_post, any(ctx.needs_input_grad[5:]))
+            flat = m._own(flat)
+        return (None, None, None, gpm if ctx.needs_input_grad[3] else None, gplv if ctx.needs_input_grad[4] else None,
+                *_flat_views(m, flat, live))
+
+
 class IODINE(nn.Module):
     def __init__(self, ARCH):
         super().__init__()
@@ -517,34 +611,107 @@ class IODINE(nn.Module):
         pred, mask, mean, _ = self._reconstruct(x, eps)
         return pred, mask, mean
 
-    @torch.no_grad()
-    def decode(self, z):
+    def decode(self, z, differentiable=None):
         """iodine.py:59-71: z (B, K', L) -> pred (B,3,S,S), mask (B,K',1,S,S), mean (B,K',3,S,S).  Like the reference (iodine.py:430)
-        the slot count comes from z itself - a single slot's latent decodes alone - and ``self.K`` is left as it is."""
+        the slot count comes from z itself - a single slot's latent decodes alone - and ``self.K`` is left as it is.
+
+        ``differentiable``: None (default) - the outputs carry an autograd graph into ``z`` and the ``decoder.*`` parameters iff grad
+        mode is on and ``z`` requires grad, as the reference's plain autograd code would; True - also when only the parameters do
+        (decoder-only fine-tuning); False - never.  The outputs are the same bits either way.  The library keeps the state of ONE
+        differentiable call: run ``backward()`` before the next model call (the error of a stale backward says so)."""
         if z.dim() != 3 or z.shape[2] != self.dim_latent or not 1 <= z.shape[1] <= 16:
             raise ValueError(f'IODINE.decode: z must have shape (B, K, {self.dim_latent}) with 1 <= K <= 16 (the per-pixel kernels are '
                              f'instantiated for K <= 16); got {tuple(z.shape)}')
+        if differentiable is None:
+            differentiable = z.requires_grad
+        if differentiable and torch.is_grad_enabled():
+            return _DecodeGrad.apply(self, z, *self._ordered_params())
+        return self._decode_nograd(z)
+
+    @torch.no_grad()
+    def _decode_nograd(self, z):
         K = int(z.shape[1])
         # the iteration count plays no part in a decode: keep the handle's (no workspace re-plan for it)
         T = self._shape[1] if self._shape is not None else int(self._cfg.iters)
         z = z.detach().to(torch.float32).contiguous()
-        dev, B = z.device, z.shape[0]
+        B = z.shape[0]
         cap = self.max_batch(K=K, T=T)
         if B > cap:
-            outs = [self.decode(z[s:e]) for s, e in self._chunks(B, cap)]
+            outs = [self._decode_nograd(z[s:e]) for s, e in self._chunks(B, cap)]
             return tuple(torch.cat([o[j] for o in outs], 0) for j in range(3))
+        return self._decode_call(z, K, T, save=False)
+
+    def _saving(self, h, on):
+        """Option save_for_backward of the library for the call that follows (workspace mode 2; see include/iodine_hip.h)."""
+        _lib.check(_lib.lib().iodine_set_option(h, b'save_for_backward', 1.0 if on else 0.0), h, 'iodine_set_option')
+
+    def _decode_call(self, z, K, T, save):
+        """One iodine_decode of at most ``max_batch`` slots-images; ``save``: kept for iodine_decode_backward."""
+        dev, B = z.device, z.shape[0]
         h = self._sync_params(dev)
-        self._ensure_workspace(h, B, 0, dev, K, T)
+        self._ensure_workspace(h, B, 2 if save else 0, dev, K, T)
         S = self.img_size
         z = self._stage('d.z', z)
         pred, mask, mean = self._out('r.pred', (B, 3, S, S), dev), self._out('r.mask', (B, K, 1, S, S), dev), self._out('r.mean', (B, K, 3, S, S), dev)
         self._call_serial += 1
-        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_decode(h, self._stream(), B, _lib.ptr(z), _lib.ptr(pred),
-                                                                      _lib.ptr(mask), _lib.ptr(mean)), h, 'iodine_decode'))
+        if save:
+            self._saving(h, True)
+        try:
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_decode(h, self._stream(), B, _lib.ptr(z), _lib.ptr(pred),
+                                                                          _lib.ptr(mask), _lib.ptr(mean)), h, 'iodine_decode'))
+        finally:
+            if save:
+                self._saving(h, False)
         return self._own(pred), self._own(mask), self._own(mean)
 
+    _STALE = ('IODINE: backward of a stale {0} - the library keeps the saved state of ONE differentiable call and another forward / '
+              'reconstruct / decode / elbo call has re-used it since, or it was differentiated already (the reference would hold a second '
+              'autograd graph; call backward() before the next model call)')
+
+    def _decode_backward(self, serial, K, grads, want_z, want_p, flat):
+        """iodine_decode_backward for the saved decode ``serial``: (dz or None, flat parameter gradients or None).  ``flat``: a buffer
+        of earlier chunks to accumulate into."""
+        if serial != self._call_serial:
+            raise RuntimeError(self._STALE.format('decode'))
+        h, dev = self._handle, self._handle_device
+        B = next(g for g in grads if g is not None).shape[0]
+        S, names = self.img_size, ('dg.pred', 'dg.mask', 'dg.mean')
+        shapes = ((B, 3, S, S), (B, K, 1, S, S), (B, K, 3, S, S))
+        gs = []
+        for g, n, shp in zip(grads, names, shapes):
+            if g is not None and tuple(g.shape) != shp:
+                raise RuntimeError(f'IODINE.decode backward: gradient of shape {tuple(g.shape)}, expected {shp}')
+            gs.append(None if g is None else self._stage(n, g.detach().to(device=dev, dtype=torch.float32).contiguous()))
+        dz = self._out('dg.dz', (B, K, self.dim_latent), dev) if want_z else None
+        acc = flat is not None
+        if want_p and flat is None:
+            flat = self._out('t.flat', (sum(p.numel() for p in self._ordered_params()),), dev)
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_decode_backward(
+            h, self._stream(), B, _lib.ptr(gs[0]), _lib.ptr(gs[1]), _lib.ptr(gs[2]), _lib.ptr(dz), _lib.ptr(flat) if want_p else None,
+            1 if acc else 0), h, 'iodine_decode_backward'))
+        self._call_serial += 1                      # the saved pass is consumed (no retain_graph)
+        return self._own(dz), flat                  # (flat: the caller takes its copy - graph mode - after its last chunk)
+
+    def elbo(self, x, eps=None, differentiable=None):
+        """Single-pass ELBO (iodine.py:161-241), see ``_elbo_nograd`` for what it computes and leaves on ``self``.
+
+        ``differentiable``: None (default) - the returned scalar carries an autograd graph iff grad mode is on and a caller-set
+        ``model.posterior.mean`` / ``.logvar`` of this batch's shape requires grad; True - also without (gradients then go to the
+        ``decoder.*`` parameters and, from the initial posterior, to ``posterior.init_mean / init_logvar``); False - never.
+        ``elbo.backward()`` fills ``posterior.mean.grad / .logvar.grad`` and the parameter gradients as the reference's autograd does
+        (iodine.py:90,137); the value is the same bits either way.  One differentiable call is kept: backward before the next call."""
+        pm, plv = self.posterior.mean, self.posterior.logvar
+        shape = (x.shape[0], self.K, self.dim_latent) if x.dim() == 4 else None
+        given = pm is not None and plv is not None and tuple(pm.shape) == shape and pm.device == x.device
+        if differentiable is None:
+            differentiable = given and (pm.requires_grad or plv.requires_grad)
+        if differentiable and torch.is_grad_enabled():
+            xc = self._check_x(x)                           # (model.K / n_iters are checked by _elbo_call, before any device work)
+            return _ElboGrad.apply(self, xc, eps, pm if given else None, plv if given else None, *self._ordered_params())
+        return self._elbo_nograd(x, eps)
+
     @torch.no_grad()
-    def elbo(self, x, eps=None):
+    def _elbo_nograd(self, x, eps=None):
         """Single-pass ELBO (iodine.py:161-241): one sample from the current posterior (``self.posterior.mean / logvar`` as
         left by the last call for this batch size; otherwise the initial posterior of ``init_unit``, iodine.py:607-618),
         decode, mixture log-likelihood minus KL.  Sets ``self.z / mean / mask / mask_logits`` and the logger entries like the
@@ -561,30 +728,83 @@ class IODINE(nn.Module):
             for s, e in self._chunks(B, cap):
                 # the chunk's slice of the current posterior (or the initial posterior, as for a whole batch)
                 self.posterior.mean, self.posterior.logvar = (pm0[s:e], plv0[s:e]) if whole else (None, None)
-                self.elbo(x[s:e], None if eps is None else eps[s:e])
+                self._elbo_nograd(x[s:e], None if eps is None else eps[s:e])
                 parts.append(self._chunk_state()); sizes.append(e - s)
             self.posterior.mean, self.posterior.logvar = pm0, plv0
             self._merge_chunk_state(parts, sizes, x)
             return self.elbo_terms[0, 0]
+        pm, plv = self.posterior.mean, self.posterior.logvar
+        if pm is None or plv is None or tuple(pm.shape) != (B, K, self.dim_latent) or pm.device != dev:
+            pm = plv = None
+        return self._elbo_call(x, eps, pm, plv, save=False)
+
+    def _elbo_call(self, x, eps, pm, plv, save):
+        """One iodine_elbo of at most ``max_batch`` images from the posterior (pm, plv) - None: the initial one; ``save``: kept for
+        iodine_elbo_backward.  x as ``_check_x`` returns it."""
+        K, T = self._run_shape()
+        dev, B = x.device, x.shape[0]
         h = self._sync_params(dev)
-        self._ensure_workspace(h, B, 0, dev, K, T)
+        self._ensure_workspace(h, B, 2 if save else 0, dev, K, T)
         shape = (B, K, self.dim_latent)
         eps = self._normals(eps, shape, dev)
-        pm, plv = self.posterior.mean, self.posterior.logvar
-        if pm is None or plv is None or tuple(pm.shape) != shape or pm.device != dev:
-            pm = plv = None
-        else:
+        if pm is not None:
             pm = self._stage('e.pm', pm.detach().to(torch.float32).contiguous())
             plv = self._stage('e.plv', plv.detach().to(torch.float32).contiguous())
         terms = self._out('e.terms', (3,), dev)
         xs = self._stage('x', x)
         self._call_serial += 1
-        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_elbo(h, self._stream(), B, _lib.ptr(xs), _lib.ptr(pm), _lib.ptr(plv),
-                                                                    _lib.ptr(eps), _lib.ptr(terms)), h, 'iodine_elbo'))
+        if save:
+            self._saving(h, True)
+        try:
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_elbo(h, self._stream(), B, _lib.ptr(xs), _lib.ptr(pm), _lib.ptr(plv),
+                                                                        _lib.ptr(eps), _lib.ptr(terms)), h, 'iodine_elbo'))
+        finally:
+            if save:
+                self._saving(h, False)
         terms = self._own(terms)
         self.elbo_terms = terms.view(1, 3)
         self._fetch_last_elbo(h, x, terms)
-        return terms[0]
+        return terms[0].clone() if save else terms[0]
+
+    def _elbo_backward(self, serial, BK, grad_out, want_post, want_p, flat=None):
+        """iodine_elbo_backward for the saved elbo ``serial``: (d / d posterior.mean, d / d posterior.logvar, flat parameter gradients),
+        each None when not asked for.  ``flat``: a buffer of earlier chunks to accumulate into."""
+        if serial != self._call_serial:
+            raise RuntimeError(self._STALE.format('elbo'))
+        h, dev = self._handle, self._handle_device
+        B, K = BK                                   # batch and slots of the saved call
+        gl = self._stage('e.gl', grad_out.detach().to(device=dev, dtype=torch.float32).reshape(()).contiguous())
+        gpm = self._out('e.gpm', (B, K, self.dim_latent), dev) if want_post else None
+        gplv = self._out('e.gplv', (B, K, self.dim_latent), dev) if want_post else None
+        acc = flat is not None
+        if want_p and flat is None:
+            flat = self._out('t.flat', (sum(p.numel() for p in self._ordered_params()),), dev)
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_elbo_backward(
+            h, self._stream(), _lib.ptr(gl), _lib.ptr(gpm), _lib.ptr(gplv), _lib.ptr(flat) if want_p else None, 1 if acc else 0),
+            h, 'iodine_elbo_backward'))
+        self._call_serial += 1                      # the saved pass is consumed (no retain_graph)
+        return self._own(gpm), self._own(gplv), flat          # (flat: the caller takes its copy - graph mode - after its last chunk)
+
+    def _elbo_chunked_grad(self, x, eps, pm, plv, want_post, want_p):
+        """Differentiable elbo of a batch above ``max_batch`` (see _ElboGrad): forward + backward of every chunk with its share of the
+        batch mean.  Returns the ELBO and (d / d posterior.mean, d / d posterior.logvar, flat parameter gradients) for grad_output 1."""
+        dev, B = x.device, x.shape[0]
+        parts, sizes, gpms, gplvs, flat = [], [], [], [], None
+        pm0, plv0 = self.posterior.mean, self.posterior.logvar
+        for s, e in self._chunks(B, self.max_batch()):
+            self._elbo_call(x[s:e].contiguous(), None if eps is None else eps[s:e], None if pm is None else pm[s:e],
+                            None if plv is None else plv[s:e], save=True)
+            parts.append(self._chunk_state()); sizes.append(e - s)
+            w = torch.full((), (e - s) / float(B), device=dev, dtype=torch.float32)
+            gpm, gplv, flat = self._elbo_backward(self._call_serial, (e - s, self.K), w, want_post, want_p, flat)
+            if not want_p:
+                flat = None
+            gpms.append(gpm); gplvs.append(gplv)
+        self.posterior.mean, self.posterior.logvar = pm0, plv0
+        self._merge_chunk_state(parts, sizes, x)
+        pre = (torch.cat(gpms, 0) if want_post else None, torch.cat(gplvs, 0) if want_post else None,
+               self._own(flat) if flat is not None else None)
+        return self.elbo_terms[0, 0].clone(), pre
 
     # ---- training: iodine.py:115-158 + lib/engine/train.py:60-63 -------------------------------------
     def forward(self, x, eps=None):
