@@ -8,7 +8,7 @@
  * torch.cuda.current_stream().cuda_stream).  Nothing throws across this ABI: every call
  * returns an int status and iodine_last_error() gives the message.
  *
- * Layouts at the boundary are the reference's: images (B,3,S,S) NCHW fp32 in [0,1];
+ * Layouts at the boundary are the reference's: images (B,3,S,S) NCHW fp32 in [0,1] (or, with iodine_set_frames, clips (B,E,3,S,S));
  * eps (T+1,B,K,L) standard normals, one slice per Gaussian.sample call
  * (iodine.py:620-634); parameters in state_dict order with state_dict shapes (OIHW convs).
  * A handle is bound to one device and is NOT re-entrant (neither is the reference module,
@@ -110,6 +110,18 @@ int iodine_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes);
  * the run shape of the call they are passed to. */
 int iodine_set_run_shape(iodine_handle* h, int slots, int iters);
 
+/* Video input: one frame per ELBO evaluation (the reference closes encode / forward over ONE x, iodine.py:73-105,115-158; nothing in the
+ * math needs that).  frames = 0 - default: x of iodine_reconstruct / iodine_train_forward is (B,3,S,S).  frames = E > 0: x is a clip
+ * (B,E,3,S,S), batch first as a loader of clips yields it, and ELBO evaluation i of the call uses x[:, i] for the likelihood, the
+ * closed-form inner gradients and the image-shaped channels of the refinement input.  E must equal the evaluations the call makes - T for
+ * iodine_reconstruct (its final sample + decode involves no image), T + 1 for iodine_train_forward (the loss stays
+ * -sum_i (i+1)/(T+1) ELBO_i, ELBO_i against frame i; the backward never reads x); any other count is IODINE_ERR_INVALID with a message
+ * naming the expected shape, before any launch - never clamped or repeated.  A setting like the run shape: it holds until changed,
+ * iodine_workspace_bytes, the workspace plan (the converted frames, [E][B][P][4], +16 bytes per pixel and frame) and the hipGraph key
+ * follow it, and a change while a training forward is pending discards it.  iodine_elbo takes one image (B,3,S,S) at any setting.
+ * E identical frames give the bits of the single-image call. */
+int iodine_set_frames(iodine_handle* h, int frames);
+
 /* pred, mask, mean = model.reconstruct(x) -- iodine.py:107-112 (encode :73-105 + decode :59-71).
  * Outputs (any may be NULL): pred (B,3,S,S), mask (B,K,1,S,S), mean (B,K,3,S,S) NCHW; z (B,K,L) = the final
  * sample; post_mean / post_logvar (B,K,L) = lambda after T updates; elbo_iter (T,3) = {ELBO, KL, LL} of each
@@ -117,6 +129,27 @@ int iodine_set_run_shape(iodine_handle* h, int slots, int iters);
 int iodine_reconstruct(iodine_handle* h, void* stream, int batch, const float* x, const float* eps,
                        float* pred, float* mask, float* mean, float* z, float* post_mean, float* post_logvar,
                        float* elbo_iter);
+
+/* iodine_reconstruct with two optional additions (both NULL: the same call, launch for launch).
+ *
+ * state_in: {post_mean, post_logvar (B,K,L), h, c (B,K,MLP_UNITS)} - the refinement starts from this (lambda, LSTM state) instead of
+ * Gaussian.init_unit + zeros (iodine.py:81-83) and runs T further iterations: T = 4 equals T = 2 followed by T = 2 from the state the
+ * first call left (post_mean / post_logvar outputs + iodine_last_refine_state), bit for bit, given the matching slices of x and eps.
+ * All four pointers are required.  The tensors are sized by (batch, run shape) of THIS call; nothing checks where they came from.
+ *
+ * traj: {pred (T+1,B,3,S,S), mask (T+1,B,K,1,S,S), mean (T+1,B,K,3,S,S), kl (T,B), ll (T,B)}, iteration first like eps and elbo_iter.
+ * Entry j < T = the decode ELBO evaluation j made (the sample from lambda_j, scored against frame j), written by one launch of the final
+ * decode's output kernel per iteration; entry T = the final decode = the pred / mask / mean outputs.  kl / ll: the per-image terms whose
+ * batch means are elbo_iter[:, 1:3].  All five pointers are required; not available with option stop_after_iters (no final decode). */
+int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps,
+                           float* pred, float* mask, float* mean, float* z, float* post_mean, float* post_logvar,
+                           float* elbo_iter, const float* const* state_in, float* const* traj);
+
+/* The LSTM state (h, c) after the last update of the last iodine_reconstruct / iodine_reconstruct_seq, in torch order as
+ * RefinementNetwork.forward returns it (iodine.py:503): lstm_h / lstm_c (count,K,MLP_UNITS) of the first `count` images; either may be
+ * NULL.  With iodine_last_posterior this is the state_in of a continuing call.  Any other compute call (decode excepted: it touches
+ * neither), a re-planned workspace or iodine_set_workspace discards it: IODINE_ERR_STATE. */
+int iodine_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c);
 
 /* pred, mask, mean = model.decode(z) -- iodine.py:59-71. */
 int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, float* pred, float* mask, float* mean);
@@ -310,7 +343,9 @@ int iodine_set_option(iodine_handle* h, const char* key, double value);
  * "pixel_pass1", "pixel_pass2", "refine_l0" (first refinement layer), "refine_l0f" (encoding + first refinement layer in one
  * kernel, option refine_l0_fused), "refine_conv" (the others), "refine_head", "refine_wgrad", "refine_dgrad", "refine_bwd01"
  * (fused layer-1 data gradient + layer-0 weight gradient, option refine_bwd_fused), "refine_bias_grad", "head_bwd", "gen_conv"
- * (the fp32 convs of the generic path), "gen_conv_f16x3" (its split-fp16 launches, option gen_conv_precision 1), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward), "render_bwd" (backward of the rendering - sigmoid, slot softmax, sum_k mask x mean - in iodine_decode_backward; the decoder pass behind it is booked under the categories of the training step).  "seen:<category>" returns in *launches the number of launches of <category> since the
+ * (the fp32 convs of the generic path), "gen_conv_f16x3" (its split-fp16 launches, option gen_conv_precision 1), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward), "render_bwd" (backward of the rendering - sigmoid, slot softmax, sum_k mask x mean - in iodine_decode_backward; the decoder pass behind it is booked under the categories of the training step), "frames_in" (the image / clip conversion at the head of
+ * iodine_reconstruct / iodine_train_forward: one launch for all frames), "traj_out" (the per-iteration output launches of a trajectory,
+ * iodine_reconstruct_seq).  "seen:<category>" returns in *launches the number of launches of <category> since the
  * last reset, bracketed or not (option profile_stride; counted at profile levels 1 -- the bracketed categories -- and 2 -- all).  Synchronises on the recorded events.  Two more names report
  * the hipGraph bookkeeping of option "graph" in *launches: "graph_captures" (graphs instantiated) and "graph_replays". */
 int iodine_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset);

@@ -26,6 +26,7 @@ EXPORTS = (
     'iodine_op_conv3x3_wgrad', 'iodine_op_conv3x3_wgrad_f32', 'iodine_op_dec_out_f16x3', 'iodine_op_gen_conv', 'iodine_op_gen_conv_f16x3',
     'iodine_grad_norm_scratch_bytes', 'iodine_grad_norm', 'iodine_grad_scale', 'iodine_adam_step_clipped',
     'iodine_decode_backward', 'iodine_elbo_backward', 'iodine_op_render_bwd',
+    'iodine_set_frames', 'iodine_reconstruct_seq', 'iodine_last_refine_state',
 )
 
 
@@ -114,6 +115,10 @@ def lib() -> C.CDLL:
         L.iodine_op_gen_conv_f16x3.argtypes = [vp, ci] + [vp] * 6 + [ci] * 8
     if hasattr(L, 'iodine_op_conv3x3_wgrad_f32'):       # (absent from older builds loaded through IODINE_HIP_LIB for same-box A/B)
         L.iodine_op_conv3x3_wgrad_f32.argtypes = [vp] + [vp] * 4 + [ci] * 3
+    if hasattr(L, 'iodine_set_frames'):                 # (video input / resumable refinement; absent from older A/B builds)
+        L.iodine_set_frames.argtypes = [vp, ci]
+        L.iodine_reconstruct_seq.argtypes = [vp, vp, ci] + [vp] * 9 + [C.POINTER(vp), C.POINTER(vp)]
+        L.iodine_last_refine_state.argtypes = [vp, vp, ci, vp, vp]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

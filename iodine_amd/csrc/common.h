@@ -197,7 +197,9 @@ hipError_t launch_render_bwd(hipStream_t st, const float* dec, const float* g_pr
 hipError_t launch_dz_plain(hipStream_t st, const float* Rc, const float* wclsT, int N, int L, int C, float* dz_out, const float* pm,
                            const float* plv, const float* eps, float scale, float* g_pm, float* g_plv);
 // kernels_misc.hip
-hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P);
+// F > 1: x is a clip (B,F,3,P), batch first; x4 [F][B][P][4], frame-major
+hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P, int F = 1);
+hipError_t launch_img_terms_split(hipStream_t st, const float* terms, float* kl, float* ll, int n);
 hipError_t launch_posterior_init(hipStream_t st, const float* im, const float* ilv, float* pm, float* plv, float* h,
                                  float* c, int N, int L, int H);
 hipError_t launch_dec_l0_prepare(hipStream_t st, const float* w, const float* bias, const float* lin, int C, int L,

@@ -37,6 +37,7 @@ struct Arena {
 struct Buffers {               // workspace carve-up for one batch size / mode / run shape
     int B = 0, mode = -1;
     int K = 0, T = 0;                          // the run shape (slots, iterations) it was planned for: the shape of the state it holds
+    int F = 0;                                 // frames x4 holds ([F][B][P][4]; iodine_set_frames, 1 = the single image)
     size_t bytes = 0;
     float *x4, *V, *dec_out, *g, *lnstat, *ll_img, *img_terms, *scal, *rows, *rows_p, *Rc, *pm, *plv;
     double* part;
@@ -100,6 +101,8 @@ struct iodine_handle {
     ParamSlots slot;
     bool params_set = false;
     int stop_after = -1;
+    int frames = 0;                             // iodine_set_frames: 0 = x is one image per batch entry, E = a clip of E frames, one per ELBO evaluation
+    int state_iter = -1;                        // buf.h / buf.c [state_iter] = LSTM state the last iodine_reconstruct left (-1: none to read)
 
     // parameter-derived device buffers (owned)
     float* lin = nullptr;                       // linspace(-1,1,S)
@@ -466,7 +469,8 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
     const int N = B * h->K, P = h->P, L = h->L, Cd = h->Cd, Cr = h->Cr, H = h->H, T = h->T;
     const bool gen_dec = dec_path(h) == DEC_GENERIC;
     b.B = B; b.mode = mode; b.K = h->K; b.T = h->T;
-    b.x4 = a.take<float>((size_t)B * P * 4);
+    b.F = h->frames > 0 ? h->frames : 1;
+    b.x4 = a.take<float>((size_t)b.F * B * P * 4);           // [F][B][P][4]: evaluation i reads frame i (x4_frame)
     b.V = a.take<float>((size_t)N * 9 * Cd);
     b.dec_out = a.take<float>((size_t)N * P * 4);
     b.g = a.take<float>((size_t)N * P * 4);
@@ -610,14 +614,16 @@ void drop_graphs(iodine_handle* h)
 
 int ensure_workspace(iodine_handle* h, int B, int mode)
 {
-    if (h->buf.B == B && h->buf.mode == mode && h->buf.K == h->K && h->buf.T == h->T && h->buf.bytes > 0) return IODINE_OK;
+    if (h->buf.B == B && h->buf.mode == mode && h->buf.K == h->K && h->buf.T == h->T && h->buf.F == (h->frames > 0 ? h->frames : 1) &&
+        h->buf.bytes > 0)
+        return IODINE_OK;
     Arena q(nullptr); Buffers tmp; plan(h, B, mode, q, tmp);
     void* base = nullptr;
     if (h->ws_user) {
         if (h->ws_user_bytes < tmp.bytes) {
-            char m[160];
-            snprintf(m, sizeof m, "workspace too small: need %zu bytes for batch %d mode %d at %d slots / %d iterations, have %zu",
-                     tmp.bytes, B, mode, h->K, h->T, h->ws_user_bytes);
+            char m[200];
+            snprintf(m, sizeof m, "workspace too small: need %zu bytes for batch %d mode %d at %d slots / %d iterations / %d frame(s), have %zu",
+                     tmp.bytes, B, mode, h->K, h->T, tmp.F, h->ws_user_bytes);
             return h->fail(IODINE_ERR_WORKSPACE, m);
         }
         base = h->ws_user;
@@ -633,6 +639,7 @@ int ensure_workspace(iodine_handle* h, int B, int mode)
     plan(h, B, mode, a, h->buf);
     h->fwd_done = false; h->diff_kind = 0;                 // a re-planned arena no longer holds the saved forward / the last elbo() outputs
     h->last_elbo_iter = -1;
+    h->state_iter = -1;
     h->enc_valid = false;
     // captured graphs stay: their key holds the arena's base address, the batch, the run shape and (through the entry point) the mode,
     // and the carve-up is a pure function of those - a step that alternates training and reconstruct calls keeps replaying both
@@ -799,6 +806,12 @@ int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0
     return IODINE_OK;
 }
 
+// the image ELBO evaluation i scores, differentiates and encodes: frame i of a clip (iodine_set_frames), else the one image
+const float* x4_frame(const iodine_handle* h, int i)
+{
+    return h->buf.x4 + (h->frames > 0 ? (size_t)i * h->buf.B * h->P * 4 : 0);
+}
+
 // elbo() + inner backward + get_input_encoding for iteration i (iodine.py:85-93 / 133-142)
 int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps_i, int i, bool need_grads,
                        float train_alpha = 0.f)
@@ -808,7 +821,7 @@ int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps
     HIPCHK(h, launch_dec_v(st, b.pm, b.plv, eps_i, nullptr, h->wcls, b.z[i], b.V, N, h->L, h->Cd));
     int rc = decoder_forward(h, st, N, b.z[i]);
     if (rc) return rc;
-    PROF(h, st, "pixel_pass1", launch_pixel_pass1(st, b.x4, b.dec_out, b.g, b.part, B, h->K, h->P, (float)h->cfg.sigma, h->precision == 0));
+    PROF(h, st, "pixel_pass1", launch_pixel_pass1(st, x4_frame(h, i), b.dec_out, b.g, b.part, B, h->K, h->P, (float)h->cfg.sigma, h->precision == 0));
     // the ticket of pixel_finalize_elbo_kernel is reset by the last block of every launch; the first launch of an entry point also
     // starts from a fresh 0 (a memset node under graph capture), whatever a failed call or a misuse of the handle from a second
     // stream left in it - once per call, not per launch (a memset is a launch of its own)
@@ -851,12 +864,12 @@ int refine_step(iodine_handle* h, hipStream_t st, int B, int i, bool save)
     const int f32 = h->precision == 0;         // exact fp32 products: the fp32-MFMA form of the same stride-2 kernels
     const bool keep_enc = save || h->stop_after >= 0;     // the backward / iodine_debug_copy("enc") read it
     if (l0f)
-        PROF(h, st, "refine_l0f", launch_refine_l0_fused(st, b.x4, b.dec_out, b.lnstat, h->lin, h->ref_l0k, h->ref_l0kmeta, h->ref_l0s,
+        PROF(h, st, "refine_l0f", launch_refine_l0_fused(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, h->ref_l0k, h->ref_l0kmeta, h->ref_l0s,
                                                          h->ref_l0smeta, h->ref_b[0], b.ract[i][0], keep_enc ? b.enck[i] : nullptr,
                                                          keep_enc ? b.encs[i] : nullptr, B, h->K, h->S, h->Cr, (float)h->cfg.sigma,
                                                          h->enc_chmask));
     else
-        PROF(h, st, "pixel_pass2", launch_pixel_pass2(st, b.x4, b.dec_out, b.lnstat, h->lin, split ? b.enck[i] : b.enc[i], B, h->K, h->S,
+        PROF(h, st, "pixel_pass2", launch_pixel_pass2(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, split ? b.enck[i] : b.enc[i], B, h->K, h->S,
                                                       (float)h->cfg.sigma, split ? b.encs[i] : nullptr, h->enc_chmask, h->precision == 0));
     int s = h->S;
     const float* in = b.enc[i];
@@ -955,7 +968,7 @@ std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, s
 {
     std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->K, (uintptr_t)h->T, (uintptr_t)h->stop_after, (uintptr_t)h->precision,
                                 (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7)),
-                                (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own)};
+                                (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own), (uintptr_t)h->frames};
     for (const void* p : ptrs) k.push_back((uintptr_t)p);
     return k;
 }
@@ -988,6 +1001,7 @@ struct PadShim {
     // scratch for one call's tensors with a latent axis: grown on demand (outside the refinement loop)
     size_t cap = 0;                        // floats per buffer
     float *eps = nullptr, *z = nullptr, *pm = nullptr, *plv = nullptr, *pm_in = nullptr, *plv_in = nullptr;
+    float *hs = nullptr, *cs = nullptr;    // LSTM state rows at the padded width (initial state in / state out)
     std::vector<void*> owned;
 };
 namespace {
@@ -1068,18 +1082,19 @@ int shim_scratch(iodine_handle* h, size_t floats)
 {
     PadShim* sh = h->shim;
     if (floats <= sh->cap) return IODINE_OK;
-    float** bufs[6] = {&sh->eps, &sh->z, &sh->pm, &sh->plv, &sh->pm_in, &sh->plv_in};
-    void* fresh[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i <= 6; ++i) {
-        // (i == 6: the old buffers may still be read by queued work)
-        const hipError_t e = i < 6 ? hipMalloc(&fresh[i], floats * sizeof(float)) : (sh->cap > 0 ? hipDeviceSynchronize() : hipSuccess);
+    constexpr int NB = 8;
+    float** bufs[NB] = {&sh->eps, &sh->z, &sh->pm, &sh->plv, &sh->pm_in, &sh->plv_in, &sh->hs, &sh->cs};
+    void* fresh[NB] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i <= NB; ++i) {
+        // (i == NB: the old buffers may still be read by queued work)
+        const hipError_t e = i < NB ? hipMalloc(&fresh[i], floats * sizeof(float)) : (sh->cap > 0 ? hipDeviceSynchronize() : hipSuccess);
         if (e != hipSuccess) {
-            for (int j = 0; j < i; ++j) (void)hipFree(fresh[j]);
-            return h->fail(IODINE_ERR_HIP, std::string(i < 6 ? "hipMalloc" : "hipDeviceSynchronize") + " (padded-handle scratch): " +
+            for (int j = 0; j < i && j < NB; ++j) (void)hipFree(fresh[j]);
+            return h->fail(IODINE_ERR_HIP, std::string(i < NB ? "hipMalloc" : "hipDeviceSynchronize") + " (padded-handle scratch): " +
                                                hipGetErrorString(e));
         }
     }
-    for (int i = 0; i < 6; ++i) {
+    for (int i = 0; i < NB; ++i) {
         if (*bufs[i]) (void)hipFree(*bufs[i]);
         *bufs[i] = (float*)fresh[i];
     }
@@ -1257,7 +1272,7 @@ void iodine_destroy(iodine_handle* h)
     if (h->shim) {
         if (h->shim->inner) iodine_destroy(h->shim->inner);
         for (void* p : h->shim->owned) (void)hipFree(p);
-        for (float* p : {h->shim->eps, h->shim->z, h->shim->pm, h->shim->plv, h->shim->pm_in, h->shim->plv_in}) if (p) (void)hipFree(p);
+        for (float* p : {h->shim->eps, h->shim->z, h->shim->pm, h->shim->plv, h->shim->pm_in, h->shim->plv_in, h->shim->hs, h->shim->cs}) if (p) (void)hipFree(p);
         delete h->shim;
         h->shim = nullptr;
     }
@@ -1506,6 +1521,7 @@ int iodine_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes)
     h->buf = Buffers();
     h->fwd_done = false; h->diff_kind = 0;
     h->last_elbo_iter = -1;
+    h->state_iter = -1;
     return IODINE_OK;                    // graphs are keyed by the arena address (see ensure_workspace)
 }
 
@@ -1525,6 +1541,20 @@ int iodine_set_run_shape(iodine_handle* h, int slots, int iters)
     // the workspace is re-planned by the next compute call (ensure_workspace keys on the run shape); the state of the last call
     // stays readable at the shape it was produced with (buf.K / buf.T)
     h->K = slots; h->T = iters;
+    return IODINE_OK;
+}
+
+int iodine_set_frames(iodine_handle* h, int frames)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    if (frames < 0) return h->fail(IODINE_ERR_INVALID, "frames must be >= 0 (0: one image per batch entry)");
+    if (h->shim) {
+        const int rc = iodine_set_frames(h->shim->inner, frames);
+        if (rc) return shim_fail(h, rc);
+    } else if (frames != h->frames) {
+        h->fwd_done = false; h->diff_kind = 0;             // the workspace is re-planned by the next compute call (ensure_workspace keys on it)
+    }
+    h->frames = frames;
     return IODINE_OK;
 }
 
@@ -1580,15 +1610,49 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
 int iodine_reconstruct(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* pred,
                        float* mask, float* mean, float* z, float* post_mean, float* post_logvar, float* elbo_iter)
 {
-    if (h && h->shim) {
+    return iodine_reconstruct_seq(h, stream, batch, x, eps, pred, mask, mean, z, post_mean, post_logvar, elbo_iter, nullptr, nullptr);
+}
+
+int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* pred,
+                           float* mask, float* mean, float* z, float* post_mean, float* post_logvar, float* elbo_iter,
+                           const float* const* state_in, float* const* traj)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    // refusals of the new arguments: on the host, before any launch (also of the padded boundary handle's resize launches)
+    if (state_in && !(state_in[0] && state_in[1] && state_in[2] && state_in[3]))
+        return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: an initial state needs all four tensors - post_mean, post_logvar (B,K,L) and "
+                                           "the LSTM state h, c (B,K,MLP_UNITS)");
+    if (traj && !(traj[0] && traj[1] && traj[2] && traj[3] && traj[4]))
+        return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: a trajectory needs all five buffers - pred, mask, mean (T+1,B,..) and kl, ll (T,B)");
+    {
+        const iodine_handle* const s = h->shim ? h->shim->inner : h;      // the handle that holds the settings
+        char m[256];
+        if (s->frames > 0 && s->frames != s->T) {
+            snprintf(m, sizeof m, "iodine_reconstruct: the frames setting is %d, but a call of %d iterations makes %d ELBO evaluations: it takes "
+                                  "x of shape (B, %d, 3, %d, %d), one frame per evaluation (or frames 0: one image (B, 3, %d, %d))",
+                     s->frames, s->T, s->T, s->T, s->S, s->S, s->S, s->S);
+            return h->fail(IODINE_ERR_INVALID, m);
+        }
+        if (traj && s->stop_after >= 0 && s->stop_after <= s->T)
+            return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: a trajectory has T + 1 entries, the last one the final decode - not "
+                                               "available with option stop_after_iters (which skips it)");
+    }
+    if (h->shim) {
         PadShim* sh = h->shim;
         if (batch < 1 || !x || !eps) return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct: batch >= 1, x and eps are required");
         hipStream_t st = (hipStream_t)stream;
         const long long N = (long long)batch * h->K, R = (long long)(h->T + 1) * N;
-        if (int r = shim_scratch(h, (size_t)R * sh->Lp)) return r;
+        if (int r = shim_scratch(h, std::max((size_t)R * sh->Lp, state_in ? (size_t)N * sh->Hp : (size_t)0))) return r;
         HIPCHK(h, launch_resize_rows(st, eps, sh->eps, R, sh->L, sh->Lp));
-        const int rc = iodine_reconstruct(sh->inner, stream, batch, x, sh->eps, pred, mask, mean, z ? sh->z : nullptr, post_mean ? sh->pm : nullptr,
-                                          post_logvar ? sh->plv : nullptr, elbo_iter);
+        const float* pstate[4] = {sh->pm_in, sh->plv_in, sh->hs, sh->cs};
+        if (state_in) {                                        // lambda: L -> padded L, LSTM state: MLP_UNITS -> padded, zero columns
+            HIPCHK(h, launch_resize_rows(st, state_in[0], sh->pm_in, N, sh->L, sh->Lp));
+            HIPCHK(h, launch_resize_rows(st, state_in[1], sh->plv_in, N, sh->L, sh->Lp));
+            HIPCHK(h, launch_resize_rows(st, state_in[2], sh->hs, N, sh->H, sh->Hp));
+            HIPCHK(h, launch_resize_rows(st, state_in[3], sh->cs, N, sh->H, sh->Hp));
+        }
+        const int rc = iodine_reconstruct_seq(sh->inner, stream, batch, x, sh->eps, pred, mask, mean, z ? sh->z : nullptr, post_mean ? sh->pm : nullptr,
+                                              post_logvar ? sh->plv : nullptr, elbo_iter, state_in ? pstate : nullptr, traj);
         if (rc) return shim_fail(h, rc);
         if (z) HIPCHK(h, launch_resize_rows(st, sh->z, z, N, sh->Lp, sh->L));
         if (post_mean) HIPCHK(h, launch_resize_rows(st, sh->pm, post_mean, N, sh->Lp, sh->L));
@@ -1601,6 +1665,7 @@ int iodine_reconstruct(iodine_handle* h, void* stream, int batch, const float* x
     rc = ensure_workspace(h, batch, 0);
     if (rc) return rc;
     h->fwd_done = false; h->diff_kind = 0;                                   // the arena is re-used: a saved training forward is gone
+    h->state_iter = -1;
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K, T = h->T;
     const bool partial = h->stop_after >= 0 && h->stop_after <= T;     // debug: stop before the final sample/decode
@@ -1608,11 +1673,23 @@ int iodine_reconstruct(iodine_handle* h, void* stream, int batch, const float* x
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const size_t eps_stride = (size_t)N * h->L;
-        HIPCHK(h, launch_x_to_nhwc4(st, x, b.x4, B, h->P));
-        HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, h->L, h->H));
+        PROF(h, st, "frames_in", launch_x_to_nhwc4(st, x, b.x4, B, h->P, h->frames > 0 ? h->frames : 1));
+        if (state_in) {
+            // continue from (lambda, h, c) of an earlier call instead of Gaussian.init_unit + zero LSTM state (iodine.py:81-83)
+            HIPCHK(h, hipMemcpyAsync(b.pm, state_in[0], sizeof(float) * eps_stride, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(b.plv, state_in[1], sizeof(float) * eps_stride, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(b.h[0], state_in[2], sizeof(float) * (size_t)N * h->H, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(b.c[0], state_in[3], sizeof(float) * (size_t)N * h->H, hipMemcpyDeviceToDevice, st));
+        } else
+            HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, h->L, h->H));
+        const size_t P = (size_t)h->P;
         for (int i = 0; i < n_it; ++i) {
             int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true);
             if (r) return r;
+            // trajectory entry i: the decode ELBO evaluation i made (the sample from lambda_i), through the final decode's kernel
+            if (traj)
+                PROF(h, st, "traj_out", launch_final_out(st, b.dec_out, traj[0] + (size_t)i * B * 3 * P, traj[1] + (size_t)i * N * P,
+                                                         traj[2] + (size_t)i * N * 3 * P, nullptr, B, h->K, h->P));
             r = refine_step(h, st, B, i, false);
             if (r) return r;
         }
@@ -1624,6 +1701,11 @@ int iodine_reconstruct(iodine_handle* h, void* stream, int batch, const float* x
             const int r = decoder_forward(h, st, N, b.z[T], b.g);
             if (r) return r;
             HIPCHK(h, launch_final_out(st, b.g, pred, mask, mean, nullptr, B, h->K, h->P));
+            if (traj) {
+                PROF(h, st, "traj_out", launch_final_out(st, b.g, traj[0] + (size_t)T * B * 3 * P, traj[1] + (size_t)T * N * P,
+                                                         traj[2] + (size_t)T * N * 3 * P, nullptr, B, h->K, h->P));
+                HIPCHK(h, launch_img_terms_split(st, b.img_terms, traj[3], traj[4], T * B));
+            }
             if (z) HIPCHK(h, hipMemcpyAsync(z, b.z[T], sizeof(float) * eps_stride, hipMemcpyDeviceToDevice, st));
         }
         if (post_mean) HIPCHK(h, hipMemcpyAsync(post_mean, b.pm, sizeof(float) * eps_stride, hipMemcpyDeviceToDevice, st));
@@ -1631,12 +1713,43 @@ int iodine_reconstruct(iodine_handle* h, void* stream, int batch, const float* x
         if (elbo_iter && n_it > 0) HIPCHK(h, hipMemcpyAsync(elbo_iter, b.scal, sizeof(float) * 3 * n_it, hipMemcpyDeviceToDevice, st));
         return IODINE_OK;
     };
-    rc = run_graphed(h, st, graph_key(h, 1, B, {x, eps, pred, mask, mean, z, post_mean, post_logvar, elbo_iter}), body);
+    std::vector<uintptr_t> key = graph_key(h, 1, B, {x, eps, pred, mask, mean, z, post_mean, post_logvar, elbo_iter});
+    for (int j = 0; j < 4; ++j) key.push_back((uintptr_t)(state_in ? state_in[j] : nullptr));
+    for (int j = 0; j < 5; ++j) key.push_back((uintptr_t)(traj ? traj[j] : nullptr));
+    rc = run_graphed(h, st, key, body);
     if (rc) return rc;
     h->last_elbo_iter = n_it > 0 ? n_it - 1 : -1;
     h->last_elbo_batch = B;
+    h->state_iter = n_it;                                  // buf.h / buf.c [n_it]: the LSTM state after the last update (iodine_last_refine_state)
     // (host state, outside the graphed body) did this call leave the encoding in the workspace?  refine_step: l0f && !keep_enc skips it
     h->enc_valid = n_it > 0 && (h->stop_after >= 0 || !(refine_split_on(h) && h->precision == 1 && h->refine_l0_fused && refine_l0_fused_ok(h->S, h->Cr, h->K)));
+    return IODINE_OK;
+}
+
+int iodine_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    iodine_handle* const s = h->shim ? h->shim->inner : h;         // the handle that holds the state
+    if (s->state_iter < 0 || s->buf.bytes == 0 || s->buf.mode != 0)
+        return h->fail(IODINE_ERR_STATE, "iodine_last_refine_state: no iodine_reconstruct has run on the current workspace, or another compute "
+                                         "call has re-used it since");
+    if (count < 1 || count > s->last_elbo_batch)
+        return h->fail(IODINE_ERR_INVALID, "iodine_last_refine_state: count must be in 1..batch of the last call");
+    const int K = s->buf.K;                                         // the slots of the call that produced the state, not the run shape
+    hipStream_t st = (hipStream_t)stream;
+    if (h->shim) {
+        PadShim* sh = h->shim;
+        const long long N = (long long)count * K;
+        if (int r = shim_scratch(h, (size_t)N * sh->Hp)) return r;
+        const int rc = iodine_last_refine_state(sh->inner, stream, count, lstm_h ? sh->hs : nullptr, lstm_c ? sh->cs : nullptr);
+        if (rc) return shim_fail(h, rc);
+        if (lstm_h) HIPCHK(h, launch_resize_rows(st, sh->hs, lstm_h, N, sh->Hp, sh->H));
+        if (lstm_c) HIPCHK(h, launch_resize_rows(st, sh->cs, lstm_c, N, sh->Hp, sh->H));
+        return IODINE_OK;
+    }
+    const size_t n = sizeof(float) * (size_t)count * K * h->H;
+    if (lstm_h) HIPCHK(h, hipMemcpyAsync(lstm_h, h->buf.h[h->state_iter], n, hipMemcpyDeviceToDevice, st));
+    if (lstm_c) HIPCHK(h, hipMemcpyAsync(lstm_c, h->buf.c[h->state_iter], n, hipMemcpyDeviceToDevice, st));
     return IODINE_OK;
 }
 
@@ -1705,6 +1818,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     rc = ensure_workspace(h, batch, save ? 2 : 0);
     if (rc) return rc;
     h->fwd_done = false; h->diff_kind = 0;
+    h->state_iter = -1;                                    // (the initial posterior below zeroes buf.h[0] / c[0])
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K;
     auto body = [&]() -> int {
@@ -1912,7 +2026,16 @@ int iodine_last_posterior(iodine_handle* h, void* stream, int count, float* post
 int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* loss,
                          float* elbo_iter)
 {
-    if (h && h->shim) {
+    if (!h) return IODINE_ERR_INVALID;
+    const iodine_handle* const s = h->shim ? h->shim->inner : h;          // the handle that holds the settings
+    if (s->frames > 0 && s->frames != s->T + 1) {
+        char m[256];
+        snprintf(m, sizeof m, "iodine_train_forward: the frames setting is %d, but a forward of %d iterations makes %d ELBO evaluations: it takes "
+                              "x of shape (B, %d, 3, %d, %d), one frame per evaluation (or frames 0: one image (B, 3, %d, %d))",
+                 s->frames, s->T, s->T + 1, s->T + 1, s->S, s->S, s->S, s->S);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    if (h->shim) {
         PadShim* sh = h->shim;
         if (batch < 1 || !x || !eps || !loss) return h->fail(IODINE_ERR_INVALID, "iodine_train_forward: batch >= 1, x, eps and loss are required");
         const long long R = (long long)(h->T + 1) * batch * h->K;
@@ -1932,11 +2055,12 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K, T = h->T, L = h->L;
     h->fwd_done = false; h->diff_kind = 0;
+    h->state_iter = -1;
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const size_t eps_stride = (size_t)N * L;
         HIPCHK(h, hipMemsetAsync(h->gacc_arena, 0, sizeof(float) * h->gacc_total, st));
-        HIPCHK(h, launch_x_to_nhwc4(st, x, b.x4, B, h->P));
+        PROF(h, st, "frames_in", launch_x_to_nhwc4(st, x, b.x4, B, h->P, h->frames > 0 ? h->frames : 1));
         HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, L, h->H));
         for (int i = 0; i <= T; ++i) {
             const float alpha = -((float)(i + 1) / (float)(T + 1)) / (float)B;      // d loss / d (B * ELBO_i)

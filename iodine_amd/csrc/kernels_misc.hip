@@ -5,22 +5,38 @@
 #include "common.h"
 
 // -----------------------------------------------------------------------------------------------
-// layout conversion: images NCHW (B,3,P) -> (B,P) float4 {r,g,b,0}
+// layout conversion: images NCHW (B,3,P) -> (B,P) float4 {r,g,b,0}; a clip (B,F,3,P), batch first as a loader yields it, goes to
+// [F][B][P] - frame-major, so that iteration i of the refinement loop reads frame i as one contiguous (B,P) image tensor.  F = 1: the
+// single image.  One launch for all frames.
 // -----------------------------------------------------------------------------------------------
-__global__ void x_to_nhwc4_kernel(const float* __restrict__ x, float4* __restrict__ x4, int B, int P)
+__global__ void x_to_nhwc4_kernel(const float* __restrict__ x, float4* __restrict__ x4, int B, int P, int F)
 {
-    const size_t total = (size_t)B * P;
+    const size_t BP = (size_t)B * P, total = BP * F;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = i / P, p = i % P;
-        const float* xb = x + b * 3 * P;
+        const size_t f = i / BP, r = i - f * BP, b = r / P, p = r % P;
+        const float* xb = x + (b * F + f) * 3 * P;
         x4[i] = make_float4(xb[p], xb[P + p], xb[2 * (size_t)P + p], 0.f);
     }
 }
 
-hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P)
+hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P, int F)
 {
-    const int blocks = (int)std::min<size_t>(((size_t)B * P + 255) / 256, 4096);
-    hipLaunchKernelGGL(x_to_nhwc4_kernel, dim3(blocks), dim3(256), 0, st, x, (float4*)x4, B, P);
+    const int blocks = (int)std::min<size_t>(((size_t)B * P * F + 255) / 256, 4096);
+    hipLaunchKernelGGL(x_to_nhwc4_kernel, dim3(blocks), dim3(256), 0, st, x, (float4*)x4, B, P, F);
+    return hipGetLastError();
+}
+
+// per-image ELBO terms of n = (iterations x images) evaluations, img_terms[n][2] = {ll, kl} as pixel_finalize_elbo_kernel writes them,
+// to the caller's two (T,B) tensors (trajectory outputs of iodine_reconstruct_seq)
+__global__ void img_terms_split_kernel(const float* __restrict__ terms, float* __restrict__ kl, float* __restrict__ ll, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { ll[i] = terms[2 * i]; kl[i] = terms[2 * i + 1]; }
+}
+
+hipError_t launch_img_terms_split(hipStream_t st, const float* terms, float* kl, float* ll, int n)
+{
+    hipLaunchKernelGGL(img_terms_split_kernel, dim3((n + 255) / 256), dim3(256), 0, st, terms, kl, ll, n);
     return hipGetLastError();
 }
 

@@ -15,6 +15,12 @@ them to run the same weights at another slot count (1..16) or iteration count - 
 weights trained at K = 7, T = 5 evaluated at K = 11 - and ``decode(z)`` takes K from ``z`` (iodine.py:430).  The library handle
 follows through ``iodine_set_run_shape``; ``loss.backward()`` differentiates the forward at the shape it ran with.
 
+Video input and resumable refinement (the paper's tracking use of the T-step loop; the reference closes ``encode`` / ``forward`` over
+one ``x``, iodine.py:73-105,115-158): ``x`` may be a clip ``(B, E, 3, S, S)`` with one frame per ELBO evaluation of the call (E = T for
+``encode`` / ``reconstruct``, T + 1 for ``forward``); ``reconstruct(x, trajectory=True)`` leaves the decode of every iteration in
+``model.trajectory``; ``model.refinement_state()`` / ``state=`` carry (lambda, h, c) from one call into the next, so a long clip runs
+in chunks of ``n_iters`` frames.
+
 Extensions over the reference: every entry point takes an optional ``eps`` tensor of shape
 (T+1, B, K, L) replacing the ``torch.randn_like`` draws of ``Gaussian.sample``
 (iodine.py:632) in call order, so that results can be compared with the CPU oracle.  Without
@@ -26,6 +32,7 @@ still shows from ATen are autograd's own fills: ``loss.backward()`` seeds the sc
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from typing import Dict, Optional
 
 import torch
@@ -98,6 +105,18 @@ class _Posterior(nn.Module):
         self.init_logvar = nn.Parameter(torch.zeros(dim_latent))
         self.mean = None
         self.logvar = None
+
+
+@dataclasses.dataclass
+class _RefineState:
+    """(lambda_T, h, c) after the last encode / reconstruct, for ``IODINE.refinement_state``.  ``h`` / ``c`` are None while they
+    are still in the library's workspace, which holds them until model call ``serial`` is followed by another; a chunked call that
+    was not asked to keep its state leaves ``serial`` None too: its chunks' LSTM states are gone."""
+    post_mean: torch.Tensor
+    post_logvar: torch.Tensor
+    h: Optional[torch.Tensor] = None
+    c: Optional[torch.Tensor] = None
+    serial: Optional[int] = None
 
 
 class _TrainStep(torch.autograd.Function):
@@ -273,6 +292,7 @@ class IODINE(nn.Module):
         self.mask_logits = None
         self.mask = None
         self.elbo_terms = None          # (n_elbo_calls, 3) = {ELBO, KL, LL} of the last call
+        self.trajectory = None          # reconstruct(x, trajectory=True): dict of per-iteration outputs, else None
 
         self._handle = None
         self._handle_device = None
@@ -280,6 +300,8 @@ class IODINE(nn.Module):
         self._workspace = None
         self._ws_key = None
         self._shape = None              # (slots, iters) the handle runs at (iodine_set_run_shape); follows self.K / self.n_iters
+        self._frames = 0                # frames per call the handle expects (iodine_set_frames; 0 = one image)
+        self._state = None              # _RefineState of the last encode / reconstruct: see refinement_state
         self._options: Dict[str, float] = {}
         self._seed = 0                  # Philox key of the library's normal generator (manual_seed)
         self._draws = 0                 # Philox stream id: one per eps draw
@@ -326,6 +348,7 @@ class IODINE(nn.Module):
                 _lib.check(L.iodine_create(C.byref(self._cfg), C.byref(h)), None, 'iodine_create')
             self._handle, self._handle_device = h, device
             self._shape = (int(self._cfg.slots), int(self._cfg.iters))
+            self._frames = 0
             for k, v in self._options.items():
                 if k in _WRAPPER_OPTIONS:
                     continue
@@ -428,12 +451,16 @@ class IODINE(nn.Module):
             raise ValueError(f'IODINE: the iteration count (model.n_iters) must be an integer >= 1; got {T!r}')
         return int(K), int(T)
 
-    def _ensure_workspace(self, h, B, mode, device, K, T):
-        """Run shape (K, T) and a workspace planned for (B, mode, K, T) on the handle."""
+    def _ensure_workspace(self, h, B, mode, device, K, T, frames=None):
+        """Run shape (K, T), frame count and a workspace planned for (B, mode, K, T, frames) on the handle.  ``frames``: 0 = one image
+        per batch entry, E = a clip of E frames (iodine_set_frames); None = whatever the handle has (decode / elbo: no re-plan)."""
         if self._shape != (K, T):
             _lib.check(_lib.lib().iodine_set_run_shape(h, K, T), h, 'iodine_set_run_shape')
             self._shape = (K, T)
-        key = (B, mode, K, T, device)
+        if frames is not None and frames != self._frames:
+            _lib.check(_lib.lib().iodine_set_frames(h, frames), h, 'iodine_set_frames')
+            self._frames = frames
+        key = (B, mode, K, T, self._frames, device)
         if self._ws_key == key:
             return
         need = _lib.lib().iodine_workspace_bytes(h, B, mode)
@@ -449,6 +476,30 @@ class IODINE(nn.Module):
             raise RuntimeError(f'expected images of shape (B, {self.img_channels}, {self.img_size}, {self.img_size}), '
                                f'got {tuple(x.shape)}')
         return x.detach().to(torch.float32).contiguous()
+
+    def _check_frames(self, x, E, what):
+        """``x`` of a call that makes ``E`` ELBO evaluations -> (x, frames): images (B, C, S, S) -> frames 0; a clip (B, E, C, S, S),
+        batch first, one frame per evaluation -> frames E.  Any other frame count is refused - never clamped or repeated."""
+        if x.dim() != 5:
+            return self._check_x(x), 0
+        c, s = self.img_channels, self.img_size
+        if tuple(x.shape[1:]) != (E, c, s, s):
+            raise RuntimeError(f'{what} at n_iters = {self.n_iters} makes {E} ELBO evaluations: expected a clip of shape '
+                               f'(B, {E}, {c}, {s}, {s}), one frame per evaluation, or images (B, {c}, {s}, {s}); got {tuple(x.shape)}')
+        return x.detach().to(torch.float32).contiguous(), E
+
+    def _check_state(self, state, B, K, device):
+        """``state=`` of encode / reconstruct: (post_mean, post_logvar (B, K, L), h, c (B, K, MLP_UNITS)) as refinement_state returns it."""
+        if state is None:
+            return None
+        L, H = self.dim_latent, int(self._cfg.ref_mlp_units)
+        want = ((B, K, L), (B, K, L), (B, K, H), (B, K, H))
+        if not isinstance(state, (tuple, list)) or len(state) != 4 or any(not torch.is_tensor(t) for t in state):
+            raise RuntimeError('state must be the tuple (post_mean, post_logvar, h, c) that model.refinement_state() returns')
+        got = tuple(tuple(t.shape) for t in state)
+        if got != want:
+            raise RuntimeError(f'state does not match this call: (B, K) = ({B}, {K}) needs tensors of shapes {want}, got {got}')
+        return tuple(t.detach().to(device=device, dtype=torch.float32).contiguous() for t in state)
 
     def _eps(self, eps, B, device):
         shape = (self.n_iters + 1, B, self.K, self.dim_latent)
@@ -539,9 +590,10 @@ class IODINE(nn.Module):
         return dict(z=self.z, mean=self.mean, mask=self.mask, mask_logits=self.mask_logits, elbo_terms=self.elbo_terms,
                     logger0={k: logger[k] for k in keep if k in logger})
 
-    def _fetch_last_elbo(self, h, x, terms, count=None):
+    def _fetch_last_elbo(self, h, x, terms, count=None, frame=-1):
         """State the reference leaves on ``self`` after an ``elbo()`` call (iodine.py:171-187) and its logger entries
-        (iodine.py:225-239): z, mean, mask, mask_logits of the whole batch and pred/image of image 0."""
+        (iodine.py:225-239): z, mean, mask, mask_logits of the whole batch and pred/image of image 0 (of a clip: its frame
+        ``frame``, the one that call scored)."""
         dev, B = x.device, x.shape[0]
         K, L, S = self.K, self.dim_latent, self.img_size
         f = dict(device=dev, dtype=torch.float32)
@@ -551,7 +603,7 @@ class IODINE(nn.Module):
             h, self._stream(), B, _lib.ptr(z), _lib.ptr(mean), _lib.ptr(mask), _lib.ptr(logits), _lib.ptr(pred)),
             h, 'iodine_last_elbo_outputs'))
         self.z, self.mean, self.mask, self.mask_logits = z, mean, mask, logits
-        logger.update(image=x[0], pred=pred[0], kl=terms[1], likelihood=terms[2])
+        logger.update(image=x[0] if x.dim() == 4 else x[0, frame], pred=pred[0], kl=terms[1], likelihood=terms[2])
         logger.update(**{f'mask_{i}': mask[0, i, 0] for i in range(K)})
         logger.update(**{f'pred_{i}': mean[0, i] for i in range(K)})
 
@@ -565,22 +617,41 @@ class IODINE(nn.Module):
         self.posterior.mean, self.posterior.logvar = pm, plv
 
     @torch.no_grad()
-    def _reconstruct(self, x, eps, want_images=True):
+    def _reconstruct(self, x, eps, want_images=True, state=None, trajectory=False, keep_state=False):
         K, T = self._run_shape()
-        x = self._check_x(x)
+        x, frames = self._check_frames(x, T, 'encode / reconstruct')
         dev, B = x.device, x.shape[0]
+        stop = int(self._options.get('stop_after_iters', -1))
+        n_it = stop if 0 <= stop <= T else T
+        if trajectory and n_it != T:
+            raise RuntimeError('trajectory=True needs the whole call: its last entry is the final decode, which option stop_after_iters '
+                               'skips (unset it with set_option("stop_after_iters", -1))')
+        state = self._check_state(state, B, K, dev)
+        self.trajectory, self._state = None, None
         cap = self.max_batch()
         if B > cap:                                   # chunks of independent images; eps (T+1, B, K, L) is cut along B
-            outs, parts, sizes, pms, plvs = [], [], [], [], []
+            # the next chunk re-uses the workspace, so the LSTM state of a chunk is fetched (two small copies) only where the caller
+            # uses the new arguments at all: a chunked call without them runs what it ran before
+            keep_state = keep_state or state is not None or trajectory
+            outs, parts, sizes, pms, plvs, trs, sts = [], [], [], [], [], [], []
             for s, e in self._chunks(B, cap):
-                outs.append(self._reconstruct(x[s:e], None if eps is None else eps[:, s:e], want_images))
+                outs.append(self._reconstruct(x[s:e], None if eps is None else eps[:, s:e], want_images,
+                                              None if state is None else tuple(t[s:e] for t in state), trajectory))
                 parts.append(self._chunk_state()); sizes.append(e - s)
                 pms.append(self.posterior.mean); plvs.append(self.posterior.logvar)
+                trs.append(self.trajectory)
+                if keep_state:
+                    sts.append(self.refinement_state())
             self.posterior.mean, self.posterior.logvar = torch.cat(pms, 0), torch.cat(plvs, 0)
             self._merge_chunk_state(parts, sizes, x)
+            if trajectory:                            # iteration first: the batch is axis 1
+                self.trajectory = {k: torch.cat([t[k] for t in trs], 1) for k in trs[0]}
+            self._state = _RefineState(self.posterior.mean, self.posterior.logvar)
+            if keep_state:
+                self._state.h, self._state.c = torch.cat([st[2] for st in sts], 0), torch.cat([st[3] for st in sts], 0)
             return tuple(None if outs[0][j] is None else torch.cat([o[j] for o in outs], 0) for j in range(4))
         h = self._sync_params(dev)
-        self._ensure_workspace(h, B, 0, dev, K, T)
+        self._ensure_workspace(h, B, 0, dev, K, T, frames)
         eps = self._eps(eps, B, dev)
         xs = self._stage('x', x)
         L, S = self.dim_latent, self.img_size
@@ -589,27 +660,85 @@ class IODINE(nn.Module):
         mean = self._out('r.mean', (B, K, 3, S, S), dev) if want_images else None
         z = self._out('r.z', (B, K, L), dev)
         pm, plv = self._out('r.pm', (B, K, L), dev), self._out('r.plv', (B, K, L), dev)
-        stop = int(self._options.get('stop_after_iters', -1))
-        n_it = stop if 0 <= stop <= T else T
         elbo = self._out('r.elbo', (n_it, 3), dev)
+        args = [_lib.ptr(t) for t in (xs, eps, pred, mask, mean, z, pm, plv, elbo)]
         self._call_serial += 1
-        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_reconstruct(
-            h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), _lib.ptr(pred), _lib.ptr(mask), _lib.ptr(mean), _lib.ptr(z),
-            _lib.ptr(pm), _lib.ptr(plv), _lib.ptr(elbo)), h, 'iodine_reconstruct'))
+        if state is None and not trajectory:
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_reconstruct(h, self._stream(), B, *args), h, 'iodine_reconstruct'))
+        else:
+            # the initial state and the trajectory buffers go through persistent staging buffers in graph mode, like every other tensor
+            state_in, state_ptrs, traj_out, traj_ptrs = None, None, None, None
+            traj_names = ('pred', 'mask', 'mean', 'kl', 'll')
+            if state is not None:
+                state_in = [self._stage('s.' + n, t) for n, t in zip(('pm', 'plv', 'h', 'c'), state)]
+                state_ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in state_in])
+            if trajectory:
+                shapes = ((T + 1, B, 3, S, S), (T + 1, B, K, 1, S, S), (T + 1, B, K, 3, S, S), (T, B), (T, B))
+                traj_out = [self._out('tr.' + n, shp, dev) for n, shp in zip(traj_names, shapes)]
+                traj_ptrs = (C.c_void_p * 5)(*[t.data_ptr() for t in traj_out])
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_reconstruct_seq(
+                h, self._stream(), B, *args, state_ptrs, traj_ptrs), h, 'iodine_reconstruct_seq'))
+            if trajectory:
+                self.trajectory = {n: self._own(t) for n, t in zip(traj_names, traj_out)}
         pred, mask, mean, z, pm, plv, elbo = (self._own(t) for t in (pred, mask, mean, z, pm, plv, elbo))
         self.posterior.mean, self.posterior.logvar, self.elbo_terms = pm, plv, elbo
+        self._state = _RefineState(pm, plv, serial=self._call_serial)   # h, c stay in the workspace until asked for (refinement_state)
         if n_it > 0:
-            self._fetch_last_elbo(h, x, elbo[-1])        # what the reference's last elbo() call left behind
+            self._fetch_last_elbo(h, x, elbo[-1], frame=n_it - 1)   # what the reference's last elbo() call left behind
         return pred, mask, mean, z
 
-    def encode(self, x, eps=None):
-        """z (B, K, L) after T refinement iterations.  iodine.py:73-105."""
-        return self._reconstruct(x, eps, want_images=False)[3]
+    def encode(self, x, eps=None, state=None, keep_state=False):
+        """z (B, K, L) after T refinement iterations.  iodine.py:73-105.  ``x``: images (B, 3, S, S) or a clip (B, T, 3, S, S) -
+        iteration i then scores, differentiates and encodes frame i.  ``state`` / ``keep_state``: see ``reconstruct``."""
+        return self._reconstruct(x, eps, want_images=False, state=state, keep_state=keep_state)[3]
 
-    def reconstruct(self, x, eps=None):
-        """pred (B,3,S,S), mask (B,K,1,S,S), mean (B,K,3,S,S).  iodine.py:107-112."""
-        pred, mask, mean, _ = self._reconstruct(x, eps)
+    def reconstruct(self, x, eps=None, trajectory=False, state=None, keep_state=False):
+        """pred (B,3,S,S), mask (B,K,1,S,S), mean (B,K,3,S,S).  iodine.py:107-112.
+
+        ``x``: images (B, 3, S, S), or a clip (B, T, 3, S, S), batch first: ELBO evaluation i uses frame ``x[:, i]`` for the
+        likelihood, the inner gradients and the image-shaped encoding channels (the final sample + decode involves no image); any
+        other frame count is a RuntimeError.  ``self.z / mean / mask / mask_logits`` and the logger entries are those of the last
+        ELBO evaluation as before; the logger's ``image`` is ``x[0, T-1]``.
+
+        ``trajectory=True`` leaves ``model.trajectory`` = dict(pred (T+1,B,3,S,S), mask (T+1,B,K,1,S,S), mean (T+1,B,K,3,S,S), kl (T,B),
+        ll (T,B)), iteration first like ``eps`` and ``elbo_terms``: entry j < T is the decode ELBO evaluation j made (the sample from
+        lambda_j, scored against frame j - with a clip the segmentation of frame j), entry T the final decode = the returned tuple;
+        kl / ll are the per-image terms behind ``elbo_terms[:, 1:3]``.  Otherwise no extra launch runs and ``model.trajectory`` is None.
+
+        ``state``: a tuple from ``model.refinement_state()`` for this (B, K) - the call starts from it instead of the initial posterior
+        and a zero LSTM state and runs ``n_iters`` FURTHER iterations: T = 4 equals T = 2 followed by T = 2 from the state, bit for
+        bit, given the matching slices of ``x`` and ``eps``.
+
+        ``keep_state``: matters only where the batch exceeds ``max_batch()`` and runs in chunks.  Every chunk re-uses the workspace,
+        so the LSTM state of a chunked call has to be copied out chunk by chunk; that is done when ``keep_state``, ``state`` or
+        ``trajectory`` is given, and ``refinement_state()`` after a chunked call without any of them is refused."""
+        pred, mask, mean, _ = self._reconstruct(x, eps, state=state, trajectory=trajectory, keep_state=keep_state)
         return pred, mask, mean
+
+    @torch.no_grad()
+    def refinement_state(self):
+        """Clones of (post_mean, post_logvar (B, K, L), h, c (B, K, MLP_UNITS)) after the last ``encode`` / ``reconstruct``: lambda_T
+        and the LSTM state in torch order, as RefinementNetwork.forward returns it (iodine.py:503) - the ``state=`` of a continuing
+        call.  The LSTM state of an un-chunked call stays in the library's workspace until asked for: the first call of this method
+        must come before the next model call (forward / reconstruct / encode / decode / elbo re-use the workspace).  A state once
+        fetched stays until the next ``encode`` / ``reconstruct`` replaces it or a training ``forward`` discards it."""
+        st = self._state
+        if st is None:
+            raise RuntimeError('IODINE.refinement_state: no encode / reconstruct has run since the module was made or trained')
+        if st.h is None:
+            if st.serial is None:
+                raise RuntimeError('IODINE.refinement_state: the last encode / reconstruct ran in chunks (batch > max_batch()), which '
+                                   're-use the workspace - pass keep_state=True to that call to have each chunk\'s LSTM state copied out')
+            if st.serial != self._call_serial:
+                raise RuntimeError('IODINE.refinement_state: another model call has re-used the workspace since the encode / reconstruct '
+                                   'whose state is asked for - call refinement_state() right after it')
+            h, dev = self._handle, self._handle_device
+            B, K = st.post_mean.shape[:2]
+            st.h = torch.empty((B, K, int(self._cfg.ref_mlp_units)), device=dev, dtype=torch.float32)
+            st.c = torch.empty_like(st.h)
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_last_refine_state(h, self._stream(), B, _lib.ptr(st.h), _lib.ptr(st.c)),
+                                                 h, 'iodine_last_refine_state'))
+        return tuple(t.clone() for t in (st.post_mean, st.post_logvar, st.h, st.c))
 
     def decode(self, z, differentiable=None):
         """iodine.py:59-71: z (B, K', L) -> pred (B,3,S,S), mask (B,K',1,S,S), mean (B,K',3,S,S).  Like the reference (iodine.py:430)
@@ -807,11 +936,17 @@ class IODINE(nn.Module):
         return self.elbo_terms[0, 0].clone(), pre
 
     # ---- training: iodine.py:115-158 + lib/engine/train.py:60-63 -------------------------------------
-    def forward(self, x, eps=None):
+    def forward(self, x, eps=None, state=None):
         """-sum_i (i+1)/(T+1) ELBO_i, differentiable wrt every parameter.  ``loss.backward()`` differentiates the forward as it
-        ran, at the (K, T) it read - like the reference, whose autograd graph is fixed at forward time."""
-        self._run_shape()
-        x = self._check_x(x)
+        ran, at the (K, T) it read - like the reference, whose autograd graph is fixed at forward time.  ``x``: images
+        (B, 3, S, S) or a clip (B, T+1, 3, S, S), ELBO_i then against frame i (no gradient flows to the frames).  A training forward
+        always starts from the initial posterior: ``state`` is refused (no truncated back-propagation across calls)."""
+        if state is not None:
+            raise RuntimeError('IODINE.forward takes no state=: a training forward starts from the initial posterior (continuing one '
+                               'across calls would need back-propagation through the earlier call); use encode / reconstruct')
+        _, T = self._run_shape()
+        x, _ = self._check_frames(x, T + 1, 'forward')
+        self._state = None                          # the state of an earlier encode / reconstruct ends here (refinement_state)
         if x.shape[0] > self.max_batch(training=True):
             loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, *self._ordered_params())
             self.elbo_terms = elbo_iter
@@ -821,7 +956,7 @@ class IODINE(nn.Module):
         self.elbo_terms = elbo_iter
         with torch.no_grad():
             h, dev = self._handle, x.device
-            self._fetch_last_elbo(h, x, elbo_iter[-1])                                 # final elbo(): iodine.py:226-239
+            self._fetch_last_elbo(h, x, elbo_iter[-1])                                 # final elbo(): iodine.py:226-239 (a clip: its last frame)
             self._fetch_posterior(h, x.shape[0], dev)
             stats = torch.empty((2,), device=dev, dtype=torch.float32)
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_logger_scalars(h, self._stream(), _lib.ptr(stats)), h))
@@ -832,7 +967,7 @@ class IODINE(nn.Module):
         dev, B = x.device, x.shape[0]
         K, T = self._run_shape()
         h = self._sync_params(dev)
-        self._ensure_workspace(h, B, 1, dev, K, T)
+        self._ensure_workspace(h, B, 1, dev, K, T, x.shape[1] if x.dim() == 5 else 0)
         loss = self._out('t.loss', (), dev)
         elbo_iter = self._out('t.elbo', (T + 1, 3), dev)
         xs, eps = self._stage('x', x), self._stage('eps', eps)
