@@ -219,6 +219,26 @@ int iodine_train_backward(iodine_handle* h, void* stream, float grad_scale, floa
  * end; no host round trip, no separate zero-fill. */
 int iodine_train_backward_flat(iodine_handle* h, void* stream, const float* grad_loss_dev, float* flat_grads, int accumulate);
 
+/* (loss + aux).backward() -- the backward of the saved iodine_train_forward with auxiliary cotangents on what the forward's FINAL elbo()
+ * leaves on the reference's module, still attached to the graph (iodine.py:137,171-187,642-651): g_mean (B,K,3,S,S), g_mask and g_logits
+ * (B,K,1,S,S), g_z (B,K,L) on self.mean / self.mask / self.mask_logits / self.z, g_post_mean / g_post_logvar (B,K,L) on
+ * posterior.mean / posterior.logvar = lambda_T -- the shapes of iodine_last_elbo_outputs / iodine_last_posterior, NCHW, device memory.
+ * Every one of them may be NULL (= zero), and so may grad_loss_dev (one float in device memory, autograd's d(out) / d(loss); NULL = 0:
+ * only the auxiliary terms).  flat_grads (required; the layout of iodine_train_backward_flat)
+ *   = (accumulate ? flat_grads : 0) + *grad_loss_dev * d loss / d params + sum_t <g_t, d t / d params>
+ * with the reference's detach points: mean / mask / mask_logits go through the final rendering (mask = softmax(mask_logits): g_mask and
+ * g_logits add at the logits) and ONE decoder pass -- the decoder.* gradients -- to z_T = mu_T + exp(logvar_T / 2) eps_T; from there
+ * d mu_T = dz + g_post_mean, d logvar_T = dz * 1/2 exp(logvar_T / 2) eps_T + g_post_logvar (no KL term: the final ELBO's KL is part of
+ * the loss) seed delta_{T-1} of the back-propagation through the T refinement iterations (lambda_T = detach(lambda_{T-1}) + delta_{T-1},
+ * iodine.py:642-643) -- the refine.* gradients; nothing reaches posterior.init_mean / init_logvar on this way (the refinement inputs are
+ * detached, iodine.py:343).  The auxiliary terms are NOT multiplied by *grad_loss_dev.  With every g_* NULL and grad_loss_dev given this is
+ * iodine_train_backward_flat itself, launch for launch and bit for bit.  The decoder activations of the final evaluation are read where
+ * the forward left them (no re-decode).  Consumes the saved forward and is refused with IODINE_ERR_STATE like the two entries above: no
+ * forward, a re-planned workspace, a changed run shape, a second backward. */
+int iodine_train_backward_aux(iodine_handle* h, void* stream, const float* grad_loss_dev, const float* g_mean, const float* g_mask,
+                              const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
+                              float* flat_grads, int accumulate);
+
 /* logger.update(init_mean=posterior.init_mean.mean(), init_logvar=posterior.init_logvar.mean()) -- iodine.py:156-157:
  * out2 (2, device) = the two means of the parameters last handed to iodine_set_params. */
 int iodine_logger_scalars(iodine_handle* h, void* stream, float* out2);
@@ -411,6 +431,11 @@ int iodine_op_gen_conv_f16x3(void* stream, int mode, const float* in_nhwc, const
  * v_exp_f32 / v_rcp_f32.  Synchronises. */
 int iodine_op_render_bwd(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean, float* g_out,
                          int batch, int slots, int pixels, int strict);
+
+/* the same with g_logits (batch,slots,1,pixels) = a gradient wrt the mask logits themselves (the fourth channel of dec_out), added behind
+ * the softmax backward -- the rendering backward of iodine_train_backward_aux; g_logits NULL: iodine_op_render_bwd, bit for bit. */
+int iodine_op_render_bwd_logits(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean,
+                                const float* g_logits, float* g_out, int batch, int slots, int pixels, int strict);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@ EXPORTS = (
     'iodine_grad_norm_scratch_bytes', 'iodine_grad_norm', 'iodine_grad_scale', 'iodine_adam_step_clipped',
     'iodine_decode_backward', 'iodine_elbo_backward', 'iodine_op_render_bwd',
     'iodine_set_frames', 'iodine_reconstruct_seq', 'iodine_last_refine_state',
+    'iodine_train_backward_aux', 'iodine_op_render_bwd_logits',
 )
 
 
@@ -119,6 +120,9 @@ def lib() -> C.CDLL:
         L.iodine_set_frames.argtypes = [vp, ci]
         L.iodine_reconstruct_seq.argtypes = [vp, vp, ci] + [vp] * 9 + [C.POINTER(vp), C.POINTER(vp)]
         L.iodine_last_refine_state.argtypes = [vp, vp, ci, vp, vp]
+    if hasattr(L, 'iodine_train_backward_aux'):         # (auxiliary cotangents on the training forward; absent from older A/B builds)
+        L.iodine_train_backward_aux.argtypes = [vp, vp] + [vp] * 8 + [ci]
+        L.iodine_op_render_bwd_logits.argtypes = [vp] + [vp] * 6 + [ci] * 4
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

@@ -193,6 +193,13 @@ hipError_t launch_final_out(hipStream_t st, const float* dec, float* pred, float
 // mask (B,K,1,S,S), mean (B,K,3,S,S) - NCHW, any of them NULL = zero - into g [N][P][4]; strict as for launch_pixel_pass1
 hipError_t launch_render_bwd(hipStream_t st, const float* dec, const float* g_pred, const float* g_mask, const float* g_mean, float* g,
                              int B, int K, int P, int strict);
+// the same with a gradient wrt the mask logits (B,K,1,S,S) added behind the softmax backward; g_logits == NULL: launch_render_bwd, bit for bit
+hipError_t launch_render_bwd_logits(hipStream_t st, const float* dec, const float* g_pred, const float* g_mask, const float* g_mean,
+                                    const float* g_logits, float* g, int B, int K, int P, int strict);
+// seeds [N][L] of the head BPTT's first step from cotangents on the final evaluation of a training forward: dz = Rc . wclsT (Rc NULL: 0) + c_z,
+// seed_m = dz + c_pm, seed_v = dz * (z - pm) / 2 + c_plv (z - pm = exp(logvar / 2) eps; no KL term); c_* may be NULL
+hipError_t launch_latent_seed(hipStream_t st, const float* Rc, const float* wclsT, int N, int L, int C, const float* c_z, const float* c_pm,
+                              const float* c_plv, const float* z, const float* pm, float* seed_m, float* seed_v);
 // dz = Rc . wclsT without the KL / layer-norm terms of launch_dz_latent; pm != NULL: the posterior gradients of one ELBO instead (scale = 1 / B)
 hipError_t launch_dz_plain(hipStream_t st, const float* Rc, const float* wclsT, int N, int L, int C, float* dz_out, const float* pm,
                            const float* plv, const float* eps, float scale, float* g_pm, float* g_plv);
@@ -260,6 +267,8 @@ hipError_t launch_l0_coord_grads(hipStream_t st, const float* D, const float* li
 hipError_t launch_loss(hipStream_t st, const float* scal, int n, float* loss);
 hipError_t launch_scale(hipStream_t st, const float* a, float alpha, float* o, int n);
 hipError_t launch_axpy_dev(hipStream_t st, const float* x, float alpha, const float* alpha_dev, float* y, int n, int accumulate);
+// y = *s_dev * y + add in place (s_dev NULL: factor 0; add NULL: nothing added)
+hipError_t launch_scale_dev_add(hipStream_t st, float* y, const float* s_dev, const float* add, int n);
 hipError_t launch_mean2(hipStream_t st, const float* a, const float* b, int n, float* out);
 hipError_t launch_lstm_bwd_pointwise(hipStream_t st, const float* gates, const float* c0, const float* c1,
                                      const float* dc1_read, const float* dh1, const float* dc1_carry, float* dgates,
@@ -269,7 +278,8 @@ hipError_t launch_pool_bwd(hipStream_t st, const float* dpooled, const float* ac
 bool head_bptt_fits(int L, int H, int Cr);
 hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_plv, const float* gates, const float* cst, const float* u,
                             const float* Wm, const float* Wv, const float* Whh, const float* Wih, const float* Wmlp, float* ddm,
-                            float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr);
+                            float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr,
+                            const float* seed_m = nullptr, const float* seed_v = nullptr, const float* gl_dev = nullptr);
 // split-precision (3 x fp16 MFMA) variant of the stride-1 tile conv
 hipError_t launch_pack_conv_weights_f16(hipStream_t st, const float* src, int O, int I, int cin, int cout, int tflip,
                                         float* meta, void* dst);

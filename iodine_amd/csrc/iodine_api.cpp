@@ -63,6 +63,7 @@ struct Buffers {               // workspace carve-up for one batch size / mode /
     float* carry_h[2] = {nullptr, nullptr};
     float* carry_c[2] = {nullptr, nullptr};
     std::vector<float*> rdpre;                 // gradient wrt refinement pre-activations, per layer
+    float* aux_seed = nullptr;                 // [2][N][L]: seeds of the head BPTT from auxiliary cotangents (iodine_train_backward_aux)
     float *gen_scr = nullptr, *gen_l0 = nullptr;                // generic path: wgrad partials; layer-0 scratch (kernels_genl0.hip)
 };
 
@@ -589,6 +590,7 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
         b.rdpre.resize(h->Dr);
         int s = h->S;
         for (int l = 0; l < h->Dr; ++l) { s = ref_out_size(h, s); b.rdpre[l] = a.take<float>((size_t)T * N * s * s * Cr); }
+        b.aux_seed = a.take<float>((size_t)2 * N * L);
     }
     if (gen_dec) {
         b.gen_l0 = a.take<float>(gen_l0_scratch_floats(N, h->S, Cd, h->kd));   // row / tap sums, prefix table of the broadcast layer
@@ -973,6 +975,10 @@ std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, s
     return k;
 }
 
+
+// cotangents of iodine_train_backward_aux (device pointers, each may be NULL): gl = d(out) / d(loss); the rest on the final evaluation's
+// mean / mask / mask_logits / z and on lambda_T
+struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv; };
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Round 6 - DIM_LATENT / REF.MLP_UNITS that are not multiples of 4 (the reference takes any: iodine.py:8-32, 446-464).
@@ -2092,8 +2098,10 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
     return IODINE_OK;
 }
 
+// aux != NULL: the backward with auxiliary cotangents (iodine_train_backward_aux) - grad_scale / grad_scale_dev are then not used, aux->gl
+// takes their place; aux == NULL: the plain backward, every launch as before
 static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev,
-                               float* const* param_grads, int n, int accumulate)
+                               float* const* param_grads, int n, int accumulate, const AuxCot* aux = nullptr)
 {
     if (!h) return IODINE_ERR_INVALID;
     if (h->shim) {
@@ -2102,7 +2110,20 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
         if (n != (int)h->params.size() || !param_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward: wrong parameter count");
         std::vector<float*> ptrs(h->params.size());
         for (size_t p = 0; p < ptrs.size(); ++p) ptrs[p] = sh->pgrad + sh->poff[p];
-        const int rc = train_backward_impl(sh->inner, stream, grad_scale, grad_scale_dev, ptrs.data(), n, 0);
+        AuxCot pa;
+        if (aux) {
+            // cotangents with a latent axis: rows widened to the padded width (zeros in the padded entries), like iodine_decode_backward's dz
+            const iodine_handle* in = sh->inner;
+            if (!in->fwd_done) return h->fail(IODINE_ERR_STATE, "iodine_train_backward: no iodine_train_forward to differentiate");
+            const long long N = (long long)in->fwd_batch * in->buf.K;
+            if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
+            pa = *aux;
+            hipStream_t st = (hipStream_t)stream;
+            if (aux->z) { HIPCHK(h, launch_resize_rows(st, aux->z, sh->z, N, sh->L, sh->Lp)); pa.z = sh->z; }
+            if (aux->pm) { HIPCHK(h, launch_resize_rows(st, aux->pm, sh->pm_in, N, sh->L, sh->Lp)); pa.pm = sh->pm_in; }
+            if (aux->plv) { HIPCHK(h, launch_resize_rows(st, aux->plv, sh->plv_in, N, sh->L, sh->Lp)); pa.plv = sh->plv_in; }
+        }
+        const int rc = train_backward_impl(sh->inner, stream, grad_scale, grad_scale_dev, ptrs.data(), n, 0, aux ? &pa : nullptr);
         if (rc) return shim_fail(h, rc);
         for (size_t p = 0; p < ptrs.size(); ++p)
             if (param_grads[p]) HIPCHK(h, launch_pad_scatter((hipStream_t)stream, ptrs[p], sh->pmap[p], param_grads[p], sh->pnumel[p], accumulate));
@@ -2122,14 +2143,39 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
     key.push_back((uintptr_t)grad_scale_dev);
     key.push_back((uintptr_t)accumulate);
     key.push_back((uintptr_t)h->fwd_split);                // the backward body reads the saved inputs in the forward's layout
+    if (aux) {
+        key.push_back(1);
+        for (const void* q : {aux->gl, aux->mean, aux->mask, aux->logits, aux->z, aux->pm, aux->plv}) key.push_back((uintptr_t)q);
+    }
     auto body = [&]() -> int {
     Buffers& b = h->buf;
     const int B = h->fwd_batch, N = B * h->K, T = h->T, L = h->L, H = h->H, Cr = h->Cr, IN = H + 4 * L;
     const ParamSlots& ps = h->slot;
+    float *seed_m = nullptr, *seed_v = nullptr;
+    if (aux) {
+        // Auxiliary cotangents on the final evaluation (iodine.py:171-187,642-651).  Order of the scaling: what the forward accumulated
+        // carries the ELBO weights and takes d(out) / d(loss) now, in place (the refinement part is still 0); the auxiliary terms join with
+        // factor 1; the ELBO seeds of the BPTT are multiplied on the device; the hand-over at the end runs with scale 1.
+        HIPCHK(h, launch_scale_dev_add(st, h->gacc_arena, aux->gl, nullptr, (int)h->gacc_total));
+        const bool dec = aux->mean || aux->mask || aux->logits;
+        if (dec) {
+            // evaluation T's decoder activations and dec_out are still in the arena: the forward's last launches were that evaluation's own
+            // decoder backward, which only reads them, and any compute call since would have cleared fwd_done.  ONE decoder pass with
+            // factor 1: every decoder weight gradient, and the class sums of the broadcast layer for dz
+            PROF(h, st, "render_bwd", launch_render_bwd_logits(st, b.dec_out, nullptr, aux->mask, aux->mean, aux->logits, b.g, B, h->K, h->P,
+                                                               h->precision == 0));
+            float* dpre0 = nullptr;
+            if (int r = decoder_backward_data(h, st, N, &dpre0, 1.f, T, true)) return r;
+        }
+        seed_m = b.aux_seed; seed_v = b.aux_seed + (size_t)N * L;
+        HIPCHK(h, launch_latent_seed(st, dec ? b.Rc : nullptr, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, L, h->Cd, aux->z, aux->pm,
+                                     aux->plv, b.z[T], b.pm, seed_m, seed_v));
+    }
     if (h->head_fused && head_bptt_fits(L, H, Cr)) {
         // the whole BPTT recurrence of the head in one launch (rows are independent: a block walks i = T-1 .. 0 for its rows)
         PROF(h, st, "head_bwd", launch_head_bptt(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->raw_wm, h->raw_wv, h->raw_whh,
-                                                 h->raw_wih, h->raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr));
+                                                 h->raw_wih, h->raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr,
+                                                 seed_m, seed_v, aux ? aux->gl : nullptr));
     } else {
     int cf = 0;                                            // carry buffer flip
     for (int i = T - 1; i >= 0; --i) {
@@ -2139,6 +2185,10 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
         float *dgates = b.dgates + (size_t)i * N * 4 * H, *ds = b.ds + (size_t)i * N * H;
         HIPCHK(h, launch_scale(st, b.g_pm[i + 1], alpha, ddm, N * L));
         HIPCHK(h, launch_scale(st, b.g_plv[i + 1], alpha, ddv, N * L));
+        if (aux) {                                         // ELBO seeds x d(out) / d(loss); lambda_T's cotangents join delta_{T-1} unscaled
+            HIPCHK(h, launch_scale_dev_add(st, ddm, aux->gl, i == T - 1 ? seed_m : nullptr, N * L));
+            HIPCHK(h, launch_scale_dev_add(st, ddv, aux->gl, i == T - 1 ? seed_v : nullptr, N * L));
+        }
         const float* c1 = b.c[i + 1];
         // read-out layers act on the cell state (iodine.py:488-492)
         HIPCHK(h, launch_sgemm(st, 0, 0, N, H, L, 1.f, ddm, L, h->raw_wm, H, 0.f, b.dc1, H));
@@ -2240,13 +2290,15 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
     bool flat = true;                                          // caller's gradients back to back in the same order?
     for (size_t p = 0; p < h->params.size() && flat; ++p)
         flat = param_grads[p] && param_grads[p] == param_grads[0] + (h->gacc[p] - h->gacc_arena);
+    const float out_scale = aux ? 1.f : grad_scale;            // (aux: d(out) / d(loss) was applied above)
+    const float* out_scale_dev = aux ? nullptr : grad_scale_dev;
     if (flat) {
-        HIPCHK(h, launch_axpy_dev(st, h->gacc_arena, grad_scale, grad_scale_dev, param_grads[0], (int)h->gacc_total, accumulate));
+        HIPCHK(h, launch_axpy_dev(st, h->gacc_arena, out_scale, out_scale_dev, param_grads[0], (int)h->gacc_total, accumulate));
         return IODINE_OK;
     }
     for (size_t p = 0; p < h->params.size(); ++p) {
         if (!param_grads[p]) continue;
-        HIPCHK(h, launch_axpy_dev(st, h->gacc[p], grad_scale, grad_scale_dev, param_grads[p], (int)h->params[p].numel(), accumulate));
+        HIPCHK(h, launch_axpy_dev(st, h->gacc[p], out_scale, out_scale_dev, param_grads[p], (int)h->params[p].numel(), accumulate));
     }
     return IODINE_OK;
     };
@@ -2270,6 +2322,22 @@ int iodine_train_backward_flat(iodine_handle* h, void* stream, const float* grad
     size_t off = 0;                                            // parameters back to back in named_parameters() order (= the gacc layout)
     for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
     return train_backward_impl(h, stream, 1.f, grad_loss_dev, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0);
+}
+
+int iodine_train_backward_aux(iodine_handle* h, void* stream, const float* grad_loss_dev, const float* g_mean, const float* g_mask,
+                              const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
+                              float* flat_grads, int accumulate)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    if (!flat_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward_aux: flat_grads is required");
+    // no auxiliary cotangent: the plain backward itself, launch for launch
+    if (grad_loss_dev && !g_mean && !g_mask && !g_logits && !g_z && !g_post_mean && !g_post_logvar)
+        return iodine_train_backward_flat(h, stream, grad_loss_dev, flat_grads, accumulate);
+    std::vector<float*> ptrs(h->params.size());
+    size_t off = 0;
+    for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
+    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar};
+    return train_backward_impl(h, stream, 1.f, nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, &aux);
 }
 
 int iodine_logger_scalars(iodine_handle* h, void* stream, float* out2)
@@ -2703,6 +2771,17 @@ int iodine_op_render_bwd(void* stream, const float* dec_out, const float* g_pred
     hipError_t e = launch_render_bwd(st, dec_out, g_pred, g_mask, g_mean, g_out, batch, slots, pixels, strict ? 1 : 0);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { g_create_error = std::string("iodine_op_render_bwd: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_render_bwd_logits(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean,
+                                const float* g_logits, float* g_out, int batch, int slots, int pixels, int strict)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!dec_out || !g_out || batch < 1 || slots < 1 || slots > 16 || pixels < 1) { g_create_error = "iodine_op_render_bwd_logits: argument"; return IODINE_ERR_INVALID; }
+    hipError_t e = launch_render_bwd_logits(st, dec_out, g_pred, g_mask, g_mean, g_logits, g_out, batch, slots, pixels, strict ? 1 : 0);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_render_bwd_logits: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
     return IODINE_OK;
 }
 

@@ -878,6 +878,23 @@ hipError_t launch_axpy_dev(hipStream_t st, const float* x, float alpha, const fl
     return hipGetLastError();
 }
 
+// y = (*s_dev) * y + add in place (s_dev == NULL: the factor is 0 and y is not read; add == NULL: nothing added) - the backward with
+// auxiliary cotangents (iodine_train_backward_aux) multiplies what carries the ELBO weights by autograd's d(out) / d(loss) BEFORE the
+// auxiliary terms join, which that factor must not reach
+__global__ void scale_dev_add_kernel(float* __restrict__ y, const float* __restrict__ s_dev, const float* __restrict__ add, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = s_dev ? s_dev[0] * y[i] : 0.f;
+    y[i] = add ? v + add[i] : v;
+}
+
+hipError_t launch_scale_dev_add(hipStream_t st, float* y, const float* s_dev, const float* add, int n)
+{
+    hipLaunchKernelGGL(scale_dev_add_kernel, dim3((n + 255) / 256), dim3(256), 0, st, y, s_dev, add, n);
+    return hipGetLastError();
+}
+
 // out[0] = mean(a[0..n)), out[1] = mean(b[0..n)): the two logger scalars of IODINE.forward (iodine.py:156-157)
 __global__ void mean2_kernel(const float* __restrict__ a, const float* __restrict__ b, int n, float* __restrict__ out)
 {
@@ -962,6 +979,9 @@ hipError_t launch_mlp_bwd_pointwise(hipStream_t st, const float* du, int ldu, co
 // It replaces 9 launches per iteration (2 scale, 4 + 1 SGEMM, 2 pointwise: 45 launches, ~0.45 ms per cfg3 step - each of them
 // tens of microseconds of latency for a few MFLOP) by one.  The row vectors sit in LDS, a weight element is read once per block and used
 // for all HB rows; the k loop is bound by that L2 stream, so the sixteen waves of a block split it and load 16 bytes per lane (head_matvec).
+// SEED (iodine_train_backward_aux): the ELBO seeds are multiplied by *gl_dev (autograd's d(out) / d(loss), device memory; NULL = 0) and
+// the first step, i = T - 1, adds seed_m / seed_v [N][L] = the cotangents that reach delta_{T-1} through lambda_T - unscaled by alpha and
+// by *gl_dev.  SEED = false is the kernel as it was.
 // =========================================================================================
 constexpr int HB = 2;      // rows per block
 constexpr int HKG = 16;    // k groups = waves of the 1024-thread block; a lane owns four adjacent output columns (16-byte weight loads)
@@ -1025,13 +1045,15 @@ IOD_DEVINL void head_matvec(const float* const (&W)[NW], const int (&ldw)[NW], i
     }
 }
 
+template <bool SEED>
 __global__ __launch_bounds__(1024)
 void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ g_plv, const float* __restrict__ gates,
                       const float* __restrict__ cst, const float* __restrict__ u, const float* __restrict__ Wm,
                       const float* __restrict__ Wv, const float* __restrict__ Whh, const float* __restrict__ Wih,
                       const float* __restrict__ Wmlp, float* __restrict__ ddm_o, float* __restrict__ ddv_o,
                       float* __restrict__ dgates_o, float* __restrict__ ds_o, float* __restrict__ dpooled_o, int T, int N, int B,
-                      int L, int H, int Cr)
+                      int L, int H, int Cr, const float* __restrict__ seed_m, const float* __restrict__ seed_v,
+                      const float* __restrict__ gl_dev)
 {
     extern __shared__ __attribute__((aligned(16))) float s_hb[];
     float* s_dd = s_hb;                              // [HB][2L]   ddm | ddv
@@ -1047,12 +1069,18 @@ void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ 
     const int IN = H + 4 * L;
     for (int idx = tid; idx < HB * H; idx += 1024) { s_dh[idx] = 0.f; s_dcc[idx] = 0.f; }
     __syncthreads();
+    float gl = 0.f;
+    if constexpr (SEED) gl = gl_dev ? gl_dev[0] : 0.f;
     for (int i = T - 1; i >= 0; --i) {
         const float alpha = -((float)(i + 2) / (float)(T + 1)) / (float)B;
         // 1. scaled posterior gradients of iteration i + 1
         for (int idx = tid; idx < HB * L; idx += 1024) {
             const int r = idx / L, l = idx % L, n = min(n0 + r, N - 1);
-            const float a = alpha * g_pm[((size_t)(i + 1) * N + n) * L + l], b = alpha * g_plv[((size_t)(i + 1) * N + n) * L + l];
+            float a = alpha * g_pm[((size_t)(i + 1) * N + n) * L + l], b = alpha * g_plv[((size_t)(i + 1) * N + n) * L + l];
+            if constexpr (SEED) {
+                a *= gl; b *= gl;
+                if (i == T - 1) { a += seed_m[(size_t)n * L + l]; b += seed_v[(size_t)n * L + l]; }
+            }
             s_dd[r * 2 * L + l] = a; s_dd[r * 2 * L + L + l] = b;
             if (n0 + r < N) { ddm_o[((size_t)i * N + n) * L + l] = a; ddv_o[((size_t)i * N + n) * L + l] = b; }
         }
@@ -1129,16 +1157,26 @@ bool head_bptt_fits(int L, int H, int Cr) { return Cr <= H && H % 4 == 0 && Cr %
 
 hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_plv, const float* gates, const float* cst, const float* u,
                             const float* Wm, const float* Wv, const float* Whh, const float* Wih, const float* Wmlp, float* ddm,
-                            float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr)
+                            float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr,
+                            const float* seed_m, const float* seed_v, const float* gl_dev)
 {
     IOD_XSKIP(2);
     if (Cr > H) return hipErrorInvalidValue;                                // (the pool gradient is staged in an [HB][H] buffer)
+    if ((seed_m == nullptr) != (seed_v == nullptr)) return hipErrorInvalidValue;
     const size_t lds = head_bptt_lds(L, H);
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel, 160 * 1024, attr_devs); e != hipSuccess) return e;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(head_bptt_kernel, dim3((N + HB - 1) / HB), dim3(64 * HKG), lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
-                       ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr);
+    const dim3 grid((N + HB - 1) / HB), block(64 * HKG);
+    if (seed_m) {                                                           // auxiliary cotangents: the seeded instance
+        static std::atomic<unsigned> attr_devs_seed{0};
+        if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<true>, 160 * 1024, attr_devs_seed); e != hipSuccess) return e;
+        hipLaunchKernelGGL(head_bptt_kernel<true>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
+                           ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, seed_m, seed_v, gl_dev);
+        return hipGetLastError();
+    }
+    static std::atomic<unsigned> attr_devs{0};
+    if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<false>, 160 * 1024, attr_devs); e != hipSuccess) return e;
+    hipLaunchKernelGGL(head_bptt_kernel<false>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
+                       ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
 

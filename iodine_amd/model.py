@@ -137,6 +137,30 @@ class _TrainStep(torch.autograd.Function):
         return (None, None, None, *grads)
 
 
+class _TrainStepAttached(torch.autograd.Function):
+    """``forward(x, attach_state=True)``: the loss AND what the forward's final ``elbo()`` leaves on the reference's module - z, mean, mask,
+    mask_logits, posterior.mean / .logvar, there still attached to the graph (iodine.py:137,171-187,642-651) - as outputs of ONE node, so a
+    single ``backward()`` of any combination of them goes through iodine_train_backward_aux.  Same library calls as the plain step."""
+
+    @staticmethod
+    def forward(ctx, module, x, eps, *params):
+        ctx.set_materialize_grads(False)                   # an output the loss does not use arrives as None -> a NULL pointer
+        loss, elbo_iter = module._train_forward(x, eps)
+        ctx.module, ctx.serial = module, module._call_serial
+        module._fetch_last_elbo(module._handle, x, elbo_iter[-1])      # (grad mode is off in here: the logger entries stay detached)
+        module._fetch_posterior(module._handle, x.shape[0], x.device)
+        ctx.mark_non_differentiable(elbo_iter)
+        return (loss, elbo_iter, module.z, module.mean, module.mask, module.mask_logits, module.posterior.mean, module.posterior.logvar)
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_elbo, g_z, g_mean, g_mask, g_logits, g_pm, g_plv):
+        aux = (g_mean, g_mask, g_logits, g_z, g_pm, g_plv)
+        if g_loss is None and all(g is None for g in aux):
+            return (None,) * len(ctx.needs_input_grad)
+        grads = ctx.module._train_backward(g_loss, ctx.serial, aux)
+        return (None, None, None, *grads)
+
+
 _WRAPPER_OPTIONS = ('batch_cap',)      # max images per library call (IODINE.max_batch); the rest go to iodine_set_option
 
 
@@ -936,28 +960,47 @@ class IODINE(nn.Module):
         return self.elbo_terms[0, 0].clone(), pre
 
     # ---- training: iodine.py:115-158 + lib/engine/train.py:60-63 -------------------------------------
-    def forward(self, x, eps=None, state=None):
+    def forward(self, x, eps=None, state=None, attach_state=False):
         """-sum_i (i+1)/(T+1) ELBO_i, differentiable wrt every parameter.  ``loss.backward()`` differentiates the forward as it
         ran, at the (K, T) it read - like the reference, whose autograd graph is fixed at forward time.  ``x``: images
         (B, 3, S, S) or a clip (B, T+1, 3, S, S), ELBO_i then against frame i (no gradient flows to the frames).  A training forward
-        always starts from the initial posterior: ``state`` is refused (no truncated back-propagation across calls)."""
+        always starts from the initial posterior: ``state`` is refused (no truncated back-propagation across calls).
+
+        ``attach_state=True`` (with grad mode on; under ``torch.no_grad()`` it changes nothing): ``model.z``, ``model.mean``,
+        ``model.mask``, ``model.mask_logits``, ``model.posterior.mean`` and ``model.posterior.logvar`` - the state of the final ELBO
+        evaluation (of a clip: frame T) - carry the autograd graph like in the reference (iodine.py:137,171-187,642-651), so auxiliary
+        terms on them (a supervised mask loss, a probe on ``z``, a slot regulariser) train the decoder and, back through all T
+        iterations, the refinement network: ``(loss + aux).backward()``.  The values are the same bits as without it; the logger entries
+        stay detached.  The library keeps ONE saved forward and its backward consumes it: sum the terms first and call ``backward()``
+        once - a second one (``aux.backward()`` followed by ``loss.backward()``) raises the stale-forward error.  A batch above
+        ``max_batch(training=True)`` is refused: its chunks' backward passes run inside the forward."""
         if state is not None:
             raise RuntimeError('IODINE.forward takes no state=: a training forward starts from the initial posterior (continuing one '
                                'across calls would need back-propagation through the earlier call); use encode / reconstruct')
         _, T = self._run_shape()
         x, _ = self._check_frames(x, T + 1, 'forward')
         self._state = None                          # the state of an earlier encode / reconstruct ends here (refinement_state)
+        attach = bool(attach_state) and torch.is_grad_enabled()
         if x.shape[0] > self.max_batch(training=True):
+            if attach:
+                raise RuntimeError(f'IODINE.forward(attach_state=True): a batch of {x.shape[0]} images exceeds max_batch(training=True) = '
+                                   f'{self.max_batch(training=True)}; such a batch runs in chunks, each chunk\'s backward inside the forward, '
+                                   'which leaves nothing for auxiliary cotangents to back-propagate through - use a smaller batch per call')
             loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, *self._ordered_params())
             self.elbo_terms = elbo_iter
             return loss
         eps = self._eps(eps, x.shape[0], x.device)
-        loss, elbo_iter = _TrainStep.apply(self, x, eps, *self._ordered_params())
+        if attach:
+            (loss, elbo_iter, self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean,
+             self.posterior.logvar) = _TrainStepAttached.apply(self, x, eps, *self._ordered_params())
+        else:
+            loss, elbo_iter = _TrainStep.apply(self, x, eps, *self._ordered_params())
         self.elbo_terms = elbo_iter
         with torch.no_grad():
             h, dev = self._handle, x.device
-            self._fetch_last_elbo(h, x, elbo_iter[-1])                                 # final elbo(): iodine.py:226-239 (a clip: its last frame)
-            self._fetch_posterior(h, x.shape[0], dev)
+            if not attach:
+                self._fetch_last_elbo(h, x, elbo_iter[-1])                             # final elbo(): iodine.py:226-239 (a clip: its last frame)
+                self._fetch_posterior(h, x.shape[0], dev)
             stats = torch.empty((2,), device=dev, dtype=torch.float32)
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_logger_scalars(h, self._stream(), _lib.ptr(stats)), h))
             logger.update(init_mean=stats[0], init_logvar=stats[1])                    # iodine.py:156-157
@@ -1009,7 +1052,9 @@ class IODINE(nn.Module):
             self.posterior.mean, self.posterior.logvar = torch.cat(pms, 0), torch.cat(plvs, 0)
         return loss, self.elbo_terms, self._own(flat)
 
-    def _train_backward(self, grad_loss, serial):
+    def _train_backward(self, grad_loss, serial, aux=None):
+        """``aux``: None, or the cotangents (mean, mask, mask_logits, z, posterior.mean, posterior.logvar) of an attached forward, each a
+        tensor or None - then ``grad_loss`` may be None too (iodine_train_backward_aux)."""
         if serial != self._call_serial:
             raise RuntimeError('IODINE: backward of a stale forward - the library keeps the saved state of ONE forward pass and '
                                'another forward / reconstruct / decode / elbo call has re-used it since (the reference would '
@@ -1018,9 +1063,17 @@ class IODINE(nn.Module):
         params = self._ordered_params()
         sizes = [p.numel() for p in params]
         flat = self._out('t.flat', (sum(sizes),), dev)
-        gl = self._stage('t.gl', grad_loss.detach().to(device=dev, dtype=torch.float32).contiguous())
-        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_flat(h, self._stream(), _lib.ptr(gl), _lib.ptr(flat), 0),
-                                             h, 'iodine_train_backward'))
+        as_f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        gl = None if grad_loss is None else self._stage('t.gl', as_f32(grad_loss))
+        if aux is None:
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_flat(h, self._stream(), _lib.ptr(gl), _lib.ptr(flat), 0),
+                                                 h, 'iodine_train_backward'))
+        else:
+            # (graph mode: the cotangents go through persistent staging buffers like every other tensor, so the graph key repeats)
+            names = ('a.mean', 'a.mask', 'a.logits', 'a.z', 'a.pm', 'a.plv')
+            cs = [None if g is None else self._stage(n, as_f32(g)) for n, g in zip(names, aux)]
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_aux(
+                h, self._stream(), _lib.ptr(gl), *[_lib.ptr(c) for c in cs], _lib.ptr(flat), 0), h, 'iodine_train_backward_aux'))
         self._call_serial += 1                      # the saved forward is consumed (no retain_graph)
         flat = self._own(flat)                      # graph mode: autograd may keep what we return as .grad; never the staging buffer
         views, off = [], 0
