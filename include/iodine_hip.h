@@ -122,6 +122,26 @@ int iodine_set_run_shape(iodine_handle* h, int slots, int iters);
  * E identical frames give the bits of the single-image call. */
 int iodine_set_frames(iodine_handle* h, int frames);
 
+/* model.sigma, and the two weights the reference hard-codes -- the objective of every following compute call (reconstruct, elbo,
+ * train_forward; decode does not depend on it).  The reference reads self.sigma on every elbo() call (iodine.py:210); beta is the KL weight
+ * as if iodine.py:223 read `elbo = log_likelihood - beta * kl`; iter_weights are the per-evaluation loss weights as if iodine.py:152-153
+ * used them instead of (i + 1) / (T + 1).  The constructor's ARCH.SIGMA, beta = 1 and the default weighting are the initial objective.
+ *   sigma > 0: the likelihood, the closed-form pixel gradients and the likelihood-shaped channels of the refinement input.
+ *   beta >= 0: the ELBO a call returns (elbo_iter[:, 0], terms[0], the loss), the -dKL / dlambda part of the inner gradient
+ *     d(B * ELBO) / d lambda -- a refinement input, through the latent layer-norm, so the inference trajectory follows it -- and every
+ *     outer gradient.  elbo_iter[:, 1:3], terms[1:3] and a trajectory's kl / ll stay the raw KL and log-likelihood.
+ *   iter_weights: n_weights finite numbers >= 0, not all zero (after rounding to fp32), copied by the call; n_weights = 0 (iter_weights may
+ *     be NULL) = the default (i + 1) / (T + 1), which keeps its closed form -- the launches and the arithmetic of a handle that never called
+ *     this entry.  A table is read by iodine_train_forward only, where n_weights must equal T + 1 of the run shape: otherwise that call
+ *     returns IODINE_ERR_INVALID naming both numbers (checked there, not here: the run shape may still change).  A weight of 0 is allowed
+ *     anywhere: the evaluation still runs -- later iterations depend on it -- and adds nothing to the loss or the gradients.
+ * A setting like the run shape: it holds until changed; invalid arguments are IODINE_ERR_INVALID and leave it as it was.  Unlike the run
+ * shape a change does NOT discard a pending forward: iodine_train_backward* / iodine_train_backward_aux / iodine_elbo_backward differentiate
+ * the saved pass with the objective IT ran with.  Call with the handle's device current (a new weight table is a small device allocation
+ * of the handle, uploaded synchronously; tables are never rewritten, so queued work keeps reading the one it was given).  The hipGraph key
+ * of option "graph" carries the bit patterns of sigma and beta and the identity of the weight table. */
+int iodine_set_objective(iodine_handle* h, double sigma, double beta, const double* iter_weights, int n_weights);
+
 /* pred, mask, mean = model.reconstruct(x) -- iodine.py:107-112 (encode :73-105 + decode :59-71).
  * Outputs (any may be NULL): pred (B,3,S,S), mask (B,K,1,S,S), mean (B,K,3,S,S) NCHW; z (B,K,L) = the final
  * sample; post_mean / post_logvar (B,K,L) = lambda after T updates; elbo_iter (T,3) = {ELBO, KL, LL} of each
@@ -296,7 +316,9 @@ int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, i
 /* Options: "stop_after_iters" (debug: run only the first v refinement iterations of reconstruct, no final decode),
  * "graph" (1: replay the fixed-shape launch sequence of reconstruct / decode / elbo / train_forward / train_backward through a
  * hipGraph per distinct argument tuple -- first call eager, second captured, later ones one hipGraphLaunch; needs a non-default
- * stream; ignored while "profile" is on; 0 -- default),
+ * stream; ignored while "profile" is on; 0 -- default.  Host-side scalars are baked into the captured nodes, so the tuple includes the
+ * objective of iodine_set_objective -- sigma, beta, the weight table: a schedule that changes beta every step sees each key once and
+ * simply runs eagerly, a repeated objective replays),
  * "save_for_backward" (1: the following iodine_decode / iodine_elbo calls keep their state for iodine_decode_backward /
  * iodine_elbo_backward - workspace mode 2, see there; 0 -- default: the inference forms, unchanged),
  * "profile" (bracket kernel launches with HIP events on the launch stream: 1 = the dominant "conv_tile_*" launches only --

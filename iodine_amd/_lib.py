@@ -28,6 +28,7 @@ EXPORTS = (
     'iodine_decode_backward', 'iodine_elbo_backward', 'iodine_op_render_bwd',
     'iodine_set_frames', 'iodine_reconstruct_seq', 'iodine_last_refine_state',
     'iodine_train_backward_aux', 'iodine_op_render_bwd_logits',
+    'iodine_set_objective',
 )
 
 
@@ -123,6 +124,8 @@ def lib() -> C.CDLL:
     if hasattr(L, 'iodine_train_backward_aux'):         # (auxiliary cotangents on the training forward; absent from older A/B builds)
         L.iodine_train_backward_aux.argtypes = [vp, vp] + [vp] * 8 + [ci]
         L.iodine_op_render_bwd_logits.argtypes = [vp] + [vp] * 6 + [ci] * 4
+    if hasattr(L, 'iodine_set_objective'):              # (model.sigma / beta / iter_weights; absent from older A/B builds, which run the default objective)
+        L.iodine_set_objective.argtypes = [vp, C.c_double, C.c_double, C.POINTER(C.c_double), ci]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

@@ -183,7 +183,7 @@ hipError_t launch_pixel_pass1(hipStream_t st, const float* x4, const float* dec,
                               int K, int P, float sigma, int strict = 0);
 // finalize + KL + batch means in one launch; counter: one zero-initialised device word per handle
 hipError_t launch_pixel_finalize_elbo(hipStream_t st, const double* part, int B, int K, int P, int use_ln, float* lnstat, float* ll_img,
-                                      const float* pm, const float* plv, int L, float* img_terms, float* scal, unsigned* counter);
+                                      const float* pm, const float* plv, int L, float* img_terms, float* scal, unsigned* counter, float beta);
 hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec, const float* lnstat,
                               const float* lin, float* enc, int B, int K, int S, float sigma, float* enc_sh = nullptr, unsigned chmask = 0x1ffffu,
                               int strict = 0);
@@ -202,7 +202,7 @@ hipError_t launch_latent_seed(hipStream_t st, const float* Rc, const float* wcls
                               const float* c_plv, const float* z, const float* pm, float* seed_m, float* seed_v);
 // dz = Rc . wclsT without the KL / layer-norm terms of launch_dz_latent; pm != NULL: the posterior gradients of one ELBO instead (scale = 1 / B)
 hipError_t launch_dz_plain(hipStream_t st, const float* Rc, const float* wclsT, int N, int L, int C, float* dz_out, const float* pm,
-                           const float* plv, const float* eps, float scale, float* g_pm, float* g_plv);
+                           const float* plv, const float* eps, float scale, float* g_pm, float* g_plv, float beta);
 // kernels_misc.hip
 // F > 1: x is a clip (B,F,3,P), batch first; x4 [F][B][P][4], frame-major
 hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P, int F = 1);
@@ -231,7 +231,7 @@ hipError_t launch_l0_coord_grads_rows(hipStream_t st, const float* Rsum, const f
 hipError_t launch_l0_reduce(hipStream_t st, const float* dpre, float* rows, float* Rc, int N, int S, int C, float* Dpart,
                             float* Dacc, float alpha, int first);
 hipError_t launch_dz_latent(hipStream_t st, const float* Rc, const float* wclsT, const float* pm, const float* plv,
-                            const float* eps, int N, int L, int C, int use_ln, float* g_pm, float* g_plv, float* latent, int Lreal = 0);
+                            const float* eps, int N, int L, int C, int use_ln, float* g_pm, float* g_plv, float* latent, int Lreal, float beta);
 hipError_t launch_refine_head(hipStream_t st, const float* feat, int N, int PL, int C, int H, int L,
                               const float* mlp_wT, const float* mlp_b, const float* wihT, const float* whhT,
                               const float* lstm_b, const float* wmT, const float* bm, const float* wvT, const float* bv,
@@ -264,8 +264,10 @@ hipError_t launch_l0_tap_sums(hipStream_t st, const float* Rc, float* RT, int N,
 hipError_t launch_l0_latent_wgrad(hipStream_t st, const float* Rc, const float* z, int N, int L, int C, float alpha, float* gw);
 hipError_t launch_l0_coord_grads(hipStream_t st, const float* D, const float* lin, int S, int C, int L, float alpha,
                                  float* gw, float* gb, float* scratch);
-hipError_t launch_loss(hipStream_t st, const float* scal, int n, float* loss);
+// wtab: device table of n loss weights (iodine_set_objective), NULL = the default (i + 1) / n
+hipError_t launch_loss(hipStream_t st, const float* scal, int n, float* loss, const float* wtab);
 hipError_t launch_scale(hipStream_t st, const float* a, float alpha, float* o, int n);
+hipError_t launch_zero_fill(hipStream_t st, float* p, size_t n);       // p[0 .. n) = 0 as a kernel (not a memset node: see kernels_train.hip)
 hipError_t launch_axpy_dev(hipStream_t st, const float* x, float alpha, const float* alpha_dev, float* y, int n, int accumulate);
 // y = *s_dev * y + add in place (s_dev NULL: factor 0; add NULL: nothing added)
 hipError_t launch_scale_dev_add(hipStream_t st, float* y, const float* s_dev, const float* add, int n);
@@ -279,7 +281,8 @@ bool head_bptt_fits(int L, int H, int Cr);
 hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_plv, const float* gates, const float* cst, const float* u,
                             const float* Wm, const float* Wv, const float* Whh, const float* Wih, const float* Wmlp, float* ddm,
                             float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr,
-                            const float* seed_m = nullptr, const float* seed_v = nullptr, const float* gl_dev = nullptr);
+                            const float* seed_m, const float* seed_v, const float* gl_dev,
+                            const float* wtab);       // wtab: T + 1 loss weights, NULL = the default (i + 2) / (T + 1)
 // split-precision (3 x fp16 MFMA) variant of the stride-1 tile conv
 hipError_t launch_pack_conv_weights_f16(hipStream_t st, const float* src, int O, int I, int cin, int cout, int tflip,
                                         float* meta, void* dst);

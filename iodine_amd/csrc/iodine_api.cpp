@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <list>
 #include <string>
 #include <vector>
 
@@ -84,8 +85,25 @@ struct ProfCat { std::string name; std::vector<std::pair<hipEvent_t, hipEvent_t>
 
 struct GraphEntry { std::vector<uintptr_t> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
 
+// The objective a call optimises (iodine_set_objective): likelihood scale, KL weight and the per-iteration loss weights.  Held by value:
+// a training forward / a saved elbo keeps the copy it ran with, its backward reads that copy and not the handle's current one.
+// wtab: device table of nw = T + 1 floats, nullptr = the default weighting w_i = (i + 1) / (T + 1), which stays the closed-form
+// expression in the kernels and on the host.  Tables are immutable once uploaded (WeightTable below), so a copy of the pointer is a snapshot;
+// wgen names the table in the hipGraph key (0 = default).
+struct Objective {
+    double sigma = 0.1, beta = 1.0;
+    const float* wtab = nullptr;
+    const float* whost = nullptr;               // the same weights on the host (owned by the handle's table list)
+    int nw = 0, wgen = 0;
+};
+struct WeightTable { std::vector<float> w; float* dev = nullptr; int gen = 0; };
+
 struct iodine_handle {
     iodine_config cfg;
+    Objective obj;                              // current; initially (ARCH.SIGMA, 1, default weighting)
+    Objective fwd_obj, diff_obj;                // what the saved training forward / the saved elbo ran with
+    std::list<WeightTable> wtabs;               // every distinct weight table this handle was given (content-addressed, never rewritten)
+    int wgen_next = 1;                          // generation of the next new table: counts up for the life of the handle, never re-used
     std::string err;
     int profile = 0;                            // 0 off, 1 the dominant conv kernels ("conv_tile_*") only, 2 every category
     int profile_stride = 1;                     // level 1: bracket every n-th launch of a category only - an event pair costs ~12 us of idle GPU
@@ -687,13 +705,17 @@ int decoder_forward(iodine_handle* h, hipStream_t st, int N, const float* z, flo
 
 // gradient of B*ELBO wrt the decoder input z through the whole decoder (replaces the autograd traversal of
 // (B*elbo).backward(), iodine.py:90,137).  Leaves d(pre-activation) of layer 0 in the returned buffer.
-// With train_alpha != 0 the decoder weight gradients of this pass are accumulated on the way with that factor
-// (= -w_i / B): they are what the outer loss.backward() (train.py:63) would compute for this decoder pass.
+// With train the decoder weight gradients of this pass are accumulated on the way with the factor train_alpha
+// (= -w_i / B): they are what the outer loss.backward() (train.py:63) would compute for this decoder pass.  The flag is separate from
+// the factor: a pass with loss weight 0 (iter_weights 'last', an explicit 0) is still a training pass - it takes part in the first-pass
+// overwrite of the maps accumulated over the passes (Dsum, Rsum, the kept partial tiles of wgrad_accum) and in the last pass's reduction /
+// coordinate and bias gradients; only launches that purely ADD alpha x (this pass) to an accumulator are skipped for it.
 // the same on the generic fallback path: plain chain of data gradients (and, in training, weight gradients with the pass factor);
 // the broadcast layer's weight gradient and the gradient wrt z come from the tap-window sums of its pre-activation gradient
 // (kernels_genl0.hip); dz is left in the first L entries of every row of buf.Rc (dz_latent multiplies that by the identity in h->gen_ident)
 int decoder_backward_generic(iodine_handle* h, hipStream_t st, int N, float train_alpha, int it)   // it: only b.z[it], the decoded z
 {
+    // (every weight gradient here is an accumulation gacc += alpha x ..., without first / last bookkeeping: a zero-weight pass skips them)
     Buffers& b = h->buf;
     const ParamSlots& ps = h->slot;
     const int Cd = h->Cd, Dd = h->Dd, L = h->L, S = h->S, k = h->kd;
@@ -714,7 +736,7 @@ int decoder_backward_generic(iodine_handle* h, hipStream_t st, int N, float trai
             PROF(h, st, "gen_conv", launch_gen_conv_dgrad(st, b.dpre[cur], h->gen_wdec[l], b.act[l - 1], b.dpre[cur ^ 1], N, S, Cd, Cd, Cd, k, 1));
         cur ^= 1;
     }
-    HIPCHK(h, hipMemsetAsync(b.Rc, 0, sizeof(float) * (size_t)N * 9 * Cd, st));
+    HIPCHK(h, launch_zero_fill(st, b.Rc, (size_t)N * 9 * Cd));
     PROF(h, st, "gen_l0", launch_gen_l0_bwd(st, b.dpre[cur], b.z[it], h->gen_wdec[0], h->lin, b.gen_l0, N, L, S, Cd, k, train_alpha,
                                             h->gacc[ps.dec_w[0]], h->gacc[ps.dec_b[0]], b.Rc, 9 * Cd));
     return IODINE_OK;
@@ -727,15 +749,16 @@ struct WgradPass { float *part, *part_b; float alpha; int accum; float reduce_al
 
 // single: the pass is the only one of its backward (iodine_decode_backward / iodine_elbo_backward) - first (overwrite the maps accumulated
 // over the passes) and last (emit the coordinate / bias gradients, reduce the kept partial tiles) at once; `it` then only names the z buffer
-int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0, float train_alpha, int it, bool single = false)
+int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0, bool train, float train_alpha, int it, bool single = false)
 {
     const bool first = single || it == 0, last = single || it == h->T;
     Buffers& b = h->buf;
     const ParamSlots& ps = h->slot;
     const int Cd = h->Cd, Dd = h->Dd;
     const DecPath path = dec_path(h);
-    if (path == DEC_GENERIC) { *dpre0 = nullptr; return decoder_backward_generic(h, st, N, train_alpha, it); }
-    const bool train = train_alpha != 0.f;
+    if (path == DEC_GENERIC) { *dpre0 = nullptr; return decoder_backward_generic(h, st, N, train ? train_alpha : 0.f, it); }
+    if (!train) train_alpha = 0.f;                         // (what the launches below were handed for an inference pass)
+    const bool zero_w = train && train_alpha == 0.f;       // a training pass whose loss weight is 0
     int cur = 0, nparts = 0, ncop = 4, nb = 0, rc;
     // training: one pass over the last hidden activation gives the data gradient AND the weight / bias gradient
     const bool out_fused = train && dec_f16(path) && h->out_bwd_fused;
@@ -761,7 +784,8 @@ int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0
                                       h->gacc[ps.out_b]));
     bool fused_l0 = false;
     for (int l = Dd - 1; l >= 1; --l) {
-        if (train) {
+        // (a zero-weight pass without kept partial tiles would reduce 0 x its tiles into the accumulator: skipped)
+        if (train && !(zero_w && !(acc_w && path != DEC_TILE_F32))) {
             wp = wgrad_pass(acc_w && path != DEC_TILE_F32, l);      // (the LDS-tiled fp32 kernel takes no pass factor)
             if ((rc = dec_conv_wgrad(h, st, N, l, cur, wp.part, wp.part_b, wp.alpha, wp.accum, &nparts, &ncop, &nb))) return rc;
             if (wp.reduce)
@@ -795,7 +819,8 @@ int decoder_backward_data(iodine_handle* h, hipStream_t st, int N, float** dpre0
         // layer 0 (spatial broadcast): latent-channel weights from z and the per-tap sums, coordinate channels
         // and bias from the slot-summed gradient map
         float *gw = h->gacc[ps.dec_w[0]], *gb = h->gacc[ps.dec_b[0]];
-        if (sgemm_tn_mfma_ok(h->L, 9 * Cd, N)) {            // z^T . RT on fp32 MFMA, accumulated straight into gw[co][ci][tap]
+        if (zero_w) {                                       // gw += 0 x (this pass)
+        } else if (sgemm_tn_mfma_ok(h->L, 9 * Cd, N)) {     // z^T . RT on fp32 MFMA, accumulated straight into gw[co][ci][tap]
             HIPCHK(h, launch_l0_tap_sums(st, b.Rc, b.RT, N, Cd));
             HIPCHK(h, launch_sgemm_tn_mfma(st, h->L, 9 * Cd, N, train_alpha, b.z[it], h->L, b.RT, 9 * Cd, 1.f, gw, h->L + 2, 1, Cd));
         } else                                              // (round 6) tap sums + product + scatter in one launch
@@ -816,27 +841,28 @@ const float* x4_frame(const iodine_handle* h, int i)
 
 // elbo() + inner backward + get_input_encoding for iteration i (iodine.py:85-93 / 133-142)
 int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps_i, int i, bool need_grads,
-                       float train_alpha = 0.f)
+                       bool train = false, float train_alpha = 0.f)
 {
+    const float sigma = (float)h->obj.sigma, beta = (float)h->obj.beta;     // the handle's current objective (iodine_set_objective)
     Buffers& b = h->buf;
     const int N = B * h->K;
     HIPCHK(h, launch_dec_v(st, b.pm, b.plv, eps_i, nullptr, h->wcls, b.z[i], b.V, N, h->L, h->Cd));
     int rc = decoder_forward(h, st, N, b.z[i]);
     if (rc) return rc;
-    PROF(h, st, "pixel_pass1", launch_pixel_pass1(st, x4_frame(h, i), b.dec_out, b.g, b.part, B, h->K, h->P, (float)h->cfg.sigma, h->precision == 0));
+    PROF(h, st, "pixel_pass1", launch_pixel_pass1(st, x4_frame(h, i), b.dec_out, b.g, b.part, B, h->K, h->P, sigma, h->precision == 0));
     // the ticket of pixel_finalize_elbo_kernel is reset by the last block of every launch; the first launch of an entry point also
     // starts from a fresh 0 (a memset node under graph capture), whatever a failed call or a misuse of the handle from a second
     // stream left in it - once per call, not per launch (a memset is a launch of its own)
     if (i == 0) HIPCHK(h, hipMemsetAsync(h->elbo_counter, 0, sizeof(unsigned), st));
     HIPCHK(h, launch_pixel_finalize_elbo(st, b.part, B, h->K, h->P, h->cfg.layernorm, b.lnstat, b.ll_img, b.pm, b.plv, h->L,
-                                         b.img_terms + (size_t)i * B * 2, b.scal + 3 * i, h->elbo_counter));
+                                         b.img_terms + (size_t)i * B * 2, b.scal + 3 * i, h->elbo_counter, beta));
     h->last_elbo_iter = i; h->last_elbo_batch = B;
     if (!need_grads) return IODINE_OK;
     float* dpre0 = nullptr;
-    rc = decoder_backward_data(h, st, N, &dpre0, train_alpha, i);
+    rc = decoder_backward_data(h, st, N, &dpre0, train, train_alpha, i);
     if (rc) return rc;
     HIPCHK(h, launch_dz_latent(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, b.pm, b.plv, eps_i, N, h->L, h->Cd, h->cfg.layernorm,
-                               b.g_pm[i], b.g_plv[i], b.latent[i], h->Lreal));
+                               b.g_pm[i], b.g_plv[i], b.latent[i], h->Lreal, beta));
     return IODINE_OK;
 }
 
@@ -868,11 +894,11 @@ int refine_step(iodine_handle* h, hipStream_t st, int B, int i, bool save)
     if (l0f)
         PROF(h, st, "refine_l0f", launch_refine_l0_fused(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, h->ref_l0k, h->ref_l0kmeta, h->ref_l0s,
                                                          h->ref_l0smeta, h->ref_b[0], b.ract[i][0], keep_enc ? b.enck[i] : nullptr,
-                                                         keep_enc ? b.encs[i] : nullptr, B, h->K, h->S, h->Cr, (float)h->cfg.sigma,
+                                                         keep_enc ? b.encs[i] : nullptr, B, h->K, h->S, h->Cr, (float)h->obj.sigma,
                                                          h->enc_chmask));
     else
         PROF(h, st, "pixel_pass2", launch_pixel_pass2(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, split ? b.enck[i] : b.enc[i], B, h->K, h->S,
-                                                      (float)h->cfg.sigma, split ? b.encs[i] : nullptr, h->enc_chmask, h->precision == 0));
+                                                      (float)h->obj.sigma, split ? b.encs[i] : nullptr, h->enc_chmask, h->precision == 0));
     int s = h->S;
     const float* in = b.enc[i];
     for (int l = 0; l < h->Dr; ++l) {
@@ -966,11 +992,17 @@ int run_graphed(iodine_handle* h, hipStream_t st, const std::vector<uintptr_t>& 
 // first element of a graph key: the entry point (1, 4, 5: reconstruct, train forward, train backward)
 enum { GK_DECODE = 2, GK_ELBO = 3, GK_DECODE_SAVED = 6, GK_ELBO_SAVED = 7, GK_DECODE_BWD = 8, GK_ELBO_BWD = 9 };
 
-std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, std::initializer_list<const void*> ptrs)
+// o: the objective the body runs with - host scalars are baked into the captured nodes, so the key carries the bit patterns of sigma and
+// beta and the generation of the weight table (the handle's current objective; a backward passes the one its forward saved)
+std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, std::initializer_list<const void*> ptrs, const Objective* o = nullptr)
 {
+    if (!o) o = &h->obj;
+    uint64_t sb, bb;
+    memcpy(&sb, &o->sigma, 8); memcpy(&bb, &o->beta, 8);
     std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->K, (uintptr_t)h->T, (uintptr_t)h->stop_after, (uintptr_t)h->precision,
                                 (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7)),
                                 (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own), (uintptr_t)h->frames};
+    k.push_back((uintptr_t)sb); k.push_back((uintptr_t)bb); k.push_back((uintptr_t)o->wgen);
     for (const void* p : ptrs) k.push_back((uintptr_t)p);
     return k;
 }
@@ -1124,6 +1156,7 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
     if (!why.empty()) { g_create_error = why; return IODINE_ERR_INVALID; }
     iodine_handle* h = new iodine_handle();
     h->cfg = *cfg;
+    h->obj.sigma = cfg->sigma;
     if (cfg->dim_latent % 4 != 0 || cfg->ref_mlp_units % 4 != 0) {
         // boundary handle of a zero-padded inner handle (PadShim above): owns the reference-shaped parameter table and the maps only
         h->L = cfg->dim_latent; h->T = cfg->iters; h->K = cfg->slots; h->S = cfg->img_size; h->P = h->S * h->S; h->H = cfg->ref_mlp_units;
@@ -1283,6 +1316,7 @@ void iodine_destroy(iodine_handle* h)
         h->shim = nullptr;
     }
     for (void* p : h->owned) (void)hipFree(p);
+    for (auto& t : h->wtabs) if (t.dev) (void)hipFree(t.dev);
     for (auto& c : h->prof) for (auto& e : c.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     if (h->ws_own) (void)hipFree(h->ws_own);
     drop_graphs(h);
@@ -1561,6 +1595,70 @@ int iodine_set_frames(iodine_handle* h, int frames)
         h->fwd_done = false; h->diff_kind = 0;             // the workspace is re-planned by the next compute call (ensure_workspace keys on it)
     }
     h->frames = frames;
+    return IODINE_OK;
+}
+
+int iodine_set_objective(iodine_handle* h, double sigma, double beta, const double* iter_weights, int n_weights)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    char m[256];
+    if (!(sigma > 0) || !std::isfinite(sigma)) {
+        snprintf(m, sizeof m, "iodine_set_objective: sigma must be a finite number > 0 (got %g)", sigma);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    if (!(beta >= 0) || !std::isfinite(beta)) {
+        snprintf(m, sizeof m, "iodine_set_objective: beta must be a finite number >= 0 (got %g)", beta);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    if (n_weights < 0 || (n_weights > 0 && !iter_weights))
+        return h->fail(IODINE_ERR_INVALID, "iodine_set_objective: n_weights must be >= 0 (0 = the default weighting) and the weights given");
+    std::vector<float> w((size_t)n_weights);
+    bool any = false;
+    for (int i = 0; i < n_weights; ++i) {
+        if (!(iter_weights[i] >= 0) || !std::isfinite(iter_weights[i])) {
+            snprintf(m, sizeof m, "iodine_set_objective: iteration weight %d must be a finite number >= 0 (got %g)", i, iter_weights[i]);
+            return h->fail(IODINE_ERR_INVALID, m);
+        }
+        w[i] = (float)iter_weights[i];
+        any = any || w[i] > 0.f;
+    }
+    if (n_weights > 0 && !any) return h->fail(IODINE_ERR_INVALID, "iodine_set_objective: the iteration weights are all zero (in fp32): no loss");
+    if (h->shim) {
+        const int rc = iodine_set_objective(h->shim->inner, sigma, beta, iter_weights, n_weights);
+        if (rc) return shim_fail(h, rc);
+        return IODINE_OK;                                  // (the inner handle holds the objective; every entry point reads it there)
+    }
+    Objective o;
+    o.sigma = sigma; o.beta = beta;
+    if (n_weights > 0) {
+        // content-addressed, immutable tables: work already queued (or a captured graph, or a saved forward's backward) that reads an
+        // earlier table keeps reading what it was given; a weighting that comes back finds its table - and its graphs - again
+        WeightTable* t = nullptr;
+        for (auto& c : h->wtabs) if (c.w == w) { t = &c; break; }
+        if (!t) {
+            if (h->wtabs.size() >= 64) {
+                // a long schedule of distinct weightings: let the queued work finish, then drop the graphs (they hold table addresses) and
+                // every table that neither the current objective nor a saved pass refers to
+                HIPCHK(h, hipDeviceSynchronize());
+                drop_graphs(h);
+                for (auto it = h->wtabs.begin(); it != h->wtabs.end();) {
+                    const float* d = it->dev;
+                    if (d == h->obj.wtab || d == h->fwd_obj.wtab || d == h->diff_obj.wtab) { ++it; continue; }
+                    (void)hipFree(it->dev);
+                    it = h->wtabs.erase(it);
+                }
+            }
+            void* d = nullptr;
+            HIPCHK(h, hipMalloc(&d, sizeof(float) * (size_t)n_weights));
+            const hipError_t e = hipMemcpy(d, w.data(), sizeof(float) * (size_t)n_weights, hipMemcpyHostToDevice);
+            if (e != hipSuccess) { (void)hipFree(d); return h->fail(IODINE_ERR_HIP, std::string("hipMemcpy (iteration weights): ") + hipGetErrorString(e)); }
+            h->wtabs.push_back(WeightTable());
+            t = &h->wtabs.back();
+            t->w = w; t->dev = (float*)d; t->gen = h->wgen_next++;
+        }
+        o.wtab = t->dev; o.whost = t->w.data(); o.nw = n_weights; o.wgen = t->gen;
+    }
+    h->obj = o;                                            // a pending forward keeps its own copy (fwd_obj / diff_obj): nothing is discarded
     return IODINE_OK;
 }
 
@@ -1848,7 +1946,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     if (rc) return rc;
     h->last_elbo_iter = 0;
     h->last_elbo_batch = B;
-    if (save) { h->diff_kind = 2; h->diff_batch = B; h->diff_init = post_mean == nullptr; }
+    if (save) { h->diff_kind = 2; h->diff_batch = B; h->diff_init = post_mean == nullptr; h->diff_obj = h->obj; }
     return IODINE_OK;
 }
 
@@ -1912,15 +2010,15 @@ int iodine_decode_backward(iodine_handle* h, void* stream, int batch, const floa
     key.push_back((uintptr_t)accumulate);
     auto body = [&]() -> int {
         Buffers& b = h->buf;
-        if (flat_grads) HIPCHK(h, hipMemsetAsync(h->gacc_arena, 0, sizeof(float) * h->gacc_total, st));
+        if (flat_grads) HIPCHK(h, launch_zero_fill(st, h->gacc_arena, h->gacc_total));
         PROF(h, st, "render_bwd", launch_render_bwd(st, b.dec_out, g_pred, g_mask, g_mean, b.g, B, h->K, h->P, h->precision == 0));
         float* dpre0 = nullptr;
         // ONE decoder pass with factor 1: data gradient down to the class sums of the broadcast layer, every decoder weight gradient on the way
-        const int r = decoder_backward_data(h, st, N, &dpre0, flat_grads ? 1.f : 0.f, 0, true);
+        const int r = decoder_backward_data(h, st, N, &dpre0, flat_grads != nullptr, 1.f, 0, true);
         if (r) return r;
         if (dz)
             HIPCHK(h, launch_dz_plain(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, h->L, h->Cd, dz, nullptr, nullptr, nullptr,
-                                      1.f, nullptr, nullptr));
+                                      1.f, nullptr, nullptr, 1.f));
         return flat_grads ? diff_flat_out(h, st, nullptr, flat_grads, accumulate) : IODINE_OK;
     };
     rc = run_graphed(h, st, key, body);
@@ -1947,20 +2045,21 @@ int iodine_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_d
     int rc = diff_ready(h, 2, "iodine_elbo_backward");
     if (rc) return rc;
     const int B = h->diff_batch, N = B * h->K;
-    std::vector<uintptr_t> key = graph_key(h, GK_ELBO_BWD, B, {grad_out_dev, g_post_mean, g_post_logvar, flat_grads});
+    const Objective obj = h->diff_obj;                     // the objective the saved elbo ran with (beta: the KL part of the posterior gradients)
+    std::vector<uintptr_t> key = graph_key(h, GK_ELBO_BWD, B, {grad_out_dev, g_post_mean, g_post_logvar, flat_grads}, &obj);
     key.push_back((uintptr_t)accumulate);
     key.push_back((uintptr_t)h->diff_init);
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const ParamSlots& ps = h->slot;
-        if (flat_grads) HIPCHK(h, hipMemsetAsync(h->gacc_arena, 0, sizeof(float) * h->gacc_total, st));
+        if (flat_grads) HIPCHK(h, launch_zero_fill(st, h->gacc_arena, h->gacc_total));
         // buf.g = d(B * ELBO) / d dec_out from pixel_pass1: ONE decoder pass, weight gradients with the factor 1 / B of the batch mean
         float* dpre0 = nullptr;
-        const int r = decoder_backward_data(h, st, N, &dpre0, flat_grads ? 1.f / (float)B : 0.f, 0, true);
+        const int r = decoder_backward_data(h, st, N, &dpre0, flat_grads != nullptr, 1.f / (float)B, 0, true);
         if (r) return r;
         // d ELBO / d lambda (iodine.py:193,220: batch means) into the slots the refinement loop uses for them
         HIPCHK(h, launch_dz_plain(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, h->L, h->Cd, nullptr, b.pm, b.plv, b.latent[0],
-                                  1.f / (float)B, b.g_pm[0], b.g_plv[0]));
+                                  1.f / (float)B, b.g_pm[0], b.g_plv[0], (float)obj.beta));
         if (flat_grads && h->diff_init) {                  // lambda = init_mean / init_logvar repeated over (B, K): iodine.py:615-616
             HIPCHK(h, launch_colsum(st, b.g_pm[0], N, h->L, h->L, 1.f, h->gacc[ps.init_mean]));
             HIPCHK(h, launch_colsum(st, b.g_plv[0], N, h->L, h->L, 1.f, h->gacc[ps.init_logvar]));
@@ -2041,6 +2140,13 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
                  s->frames, s->T, s->T + 1, s->T + 1, s->S, s->S, s->S, s->S);
         return h->fail(IODINE_ERR_INVALID, m);
     }
+    if (s->obj.nw != 0 && s->obj.nw != s->T + 1) {
+        char m[256];
+        snprintf(m, sizeof m, "iodine_train_forward: the objective has %d iteration weights, but a forward of %d iterations makes %d ELBO "
+                              "evaluations: it takes %d weights (iodine_set_objective; 0 weights = the default (i + 1) / (T + 1))",
+                 s->obj.nw, s->T, s->T + 1, s->T + 1);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
     if (h->shim) {
         PadShim* sh = h->shim;
         if (batch < 1 || !x || !eps || !loss) return h->fail(IODINE_ERR_INVALID, "iodine_train_forward: batch >= 1, x, eps and loss are required");
@@ -2065,12 +2171,13 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const size_t eps_stride = (size_t)N * L;
-        HIPCHK(h, hipMemsetAsync(h->gacc_arena, 0, sizeof(float) * h->gacc_total, st));
+        HIPCHK(h, launch_zero_fill(st, h->gacc_arena, h->gacc_total));
         PROF(h, st, "frames_in", launch_x_to_nhwc4(st, x, b.x4, B, h->P, h->frames > 0 ? h->frames : 1));
         HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, L, h->H));
         for (int i = 0; i <= T; ++i) {
-            const float alpha = -((float)(i + 1) / (float)(T + 1)) / (float)B;      // d loss / d (B * ELBO_i)
-            int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, alpha);
+            // d loss / d (B * ELBO_i) = -w_i / B; the default weighting keeps its closed form
+            const float alpha = h->obj.whost ? -h->obj.whost[i] / (float)B : -((float)(i + 1) / (float)(T + 1)) / (float)B;
+            int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, true, alpha);
             if (r) return r;
             if (i == 0) {
                 // lambda_0 = init_mean / init_logvar repeated over (B, K) (iodine.py:615-616): their gradient is the
@@ -2083,13 +2190,14 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
                 if (r) return r;
             }
         }
-        HIPCHK(h, launch_loss(st, b.scal, T + 1, loss));
+        HIPCHK(h, launch_loss(st, b.scal, T + 1, loss, h->obj.wtab));
         if (elbo_iter) HIPCHK(h, hipMemcpyAsync(elbo_iter, b.scal, sizeof(float) * 3 * (T + 1), hipMemcpyDeviceToDevice, st));
         return IODINE_OK;
     };
     rc = run_graphed(h, st, graph_key(h, 4, B, {x, eps, loss, elbo_iter}), body);
     if (rc) return rc;
     h->fwd_done = true;
+    h->fwd_obj = h->obj;                                   // the backward differentiates the forward as it ran (a replay ran the same objective: graph key)
     h->enc_valid = true;                                   // training keeps the encoding of every iteration (the backward reads it)
     h->fwd_batch = B;
     h->fwd_split = refine_split_on(h);     // layout of the saved refinement inputs (refine_split is part of the graph key)
@@ -2136,7 +2244,8 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
     hipStream_t st = (hipStream_t)stream;
     std::vector<const void*> kp;
     for (int i = 0; i < n; ++i) kp.push_back(param_grads[i]);
-    std::vector<uintptr_t> key = graph_key(h, 5, h->fwd_batch, {});
+    const Objective obj = h->fwd_obj;                      // the objective of the saved forward, whatever the handle holds by now
+    std::vector<uintptr_t> key = graph_key(h, 5, h->fwd_batch, {}, &obj);
     for (const void* q : kp) key.push_back((uintptr_t)q);
     uint32_t gs_bits; memcpy(&gs_bits, &grad_scale, 4);
     key.push_back(gs_bits);
@@ -2165,7 +2274,7 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
             PROF(h, st, "render_bwd", launch_render_bwd_logits(st, b.dec_out, nullptr, aux->mask, aux->mean, aux->logits, b.g, B, h->K, h->P,
                                                                h->precision == 0));
             float* dpre0 = nullptr;
-            if (int r = decoder_backward_data(h, st, N, &dpre0, 1.f, T, true)) return r;
+            if (int r = decoder_backward_data(h, st, N, &dpre0, true, 1.f, T, true)) return r;
         }
         seed_m = b.aux_seed; seed_v = b.aux_seed + (size_t)N * L;
         HIPCHK(h, launch_latent_seed(st, dec ? b.Rc : nullptr, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, L, h->Cd, aux->z, aux->pm,
@@ -2175,12 +2284,12 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
         // the whole BPTT recurrence of the head in one launch (rows are independent: a block walks i = T-1 .. 0 for its rows)
         PROF(h, st, "head_bwd", launch_head_bptt(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->raw_wm, h->raw_wv, h->raw_whh,
                                                  h->raw_wih, h->raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr,
-                                                 seed_m, seed_v, aux ? aux->gl : nullptr));
+                                                 seed_m, seed_v, aux ? aux->gl : nullptr, obj.wtab));
     } else {
     int cf = 0;                                            // carry buffer flip
     for (int i = T - 1; i >= 0; --i) {
         // d loss / d delta_i = -w_{i+1}/B * d(B*ELBO_{i+1})/d lambda_{i+1}   (lambda_{i+1} = detach(lambda_i) + delta_i)
-        const float alpha = -((float)(i + 2) / (float)(T + 1)) / (float)B;
+        const float alpha = obj.whost ? -obj.whost[i + 1] / (float)B : -((float)(i + 2) / (float)(T + 1)) / (float)B;
         float *ddm = b.ddm + (size_t)i * N * L, *ddv = b.ddv + (size_t)i * N * L;
         float *dgates = b.dgates + (size_t)i * N * 4 * H, *ds = b.ds + (size_t)i * N * H;
         HIPCHK(h, launch_scale(st, b.g_pm[i + 1], alpha, ddm, N * L));
@@ -2243,7 +2352,7 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
             // 17-channel scratch that is gathered into the n_in-channel accumulator afterwards
             const bool gather0 = l == 0 && h->n_in < 17;
             float* gw_dst = gather0 ? h->ref_g17 : h->gacc[ps.ref_w[l]];
-            if (gather0) HIPCHK(h, hipMemsetAsync(h->ref_g17, 0, (size_t)Cr * 17 * h->kr * h->kr * sizeof(float), st));
+            if (gather0) HIPCHK(h, launch_zero_fill(st, h->ref_g17, (size_t)Cr * 17 * h->kr * h->kr));
             if (h->gen_ref) {
                 PROF(h, st, "gen_conv", launch_gen_conv_wgrad(st, in, b.rdpre[l], b.gen_scr, NT, sz[l], ireal, cip, ireal, Cr, h->kr, h->rs, 1.f,
                                                               gw_dst, gb, l == 0 ? h->enc_chmask : 0xffffffffu));
@@ -2257,7 +2366,7 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
                 else
                     PROF(h, st, "refine_wgrad", launch_conv3x3_s2_wgrad_f16x3(st, b.enck[0], b.rdpre[0], b.wg_part, b.wg_part_b, NT, sz[0],
                                                                               20, Cr, &nparts, &cipad, &nb, b.encs[0], h->K, h->precision == 0));
-                HIPCHK(h, hipMemsetAsync(h->ref_g20, 0, (size_t)Cr * 20 * 9 * sizeof(float), st));
+                HIPCHK(h, launch_zero_fill(st, h->ref_g20, (size_t)Cr * 20 * 9));
                 HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, 20, 20, 1.f, h->ref_g20, b.wg_fold, b.wg_part_b, nb, gb));
                 HIPCHK(h, launch_ref_unsplit_grad(st, h->ref_g20, Cr, gw_dst));
             } else if (refine_f16_ok(h)) {

@@ -553,8 +553,8 @@ hipError_t launch_l0_reduce(hipStream_t st, const float* dpre, float* rows, floa
 
 // -----------------------------------------------------------------------------------------------
 // dz = Rc . Wcls^T, posterior gradients and the refinement "latent" vector
-//   g_mean   = dz - mean
-//   g_logvar = dz * 0.5 * exp(logvar/2) * eps - 0.5 * (exp(logvar) - 1)
+//   g_mean   = dz - beta * mean
+//   g_logvar = dz * 0.5 * exp(logvar/2) * eps - beta * 0.5 * (exp(logvar) - 1)      (beta: KL weight of the objective, iodine_set_objective)
 //   latent   = [mean | logvar | LN(g_mean) | LN(g_logvar)]   (iodine.py:253-275; 3-D layernorm :382-384,394)
 // One block (L threads rounded up to a wave multiple) per slot.
 // -----------------------------------------------------------------------------------------------
@@ -572,7 +572,7 @@ IOD_DEVINL float block_sum_f(float v, float* s_buf, int tid, int nthreads)
 __global__ void dz_latent_kernel(const float* __restrict__ Rc, const float* __restrict__ wclsT /*[9][C][L]*/,
                                  const float* __restrict__ pm, const float* __restrict__ plv,
                                  const float* __restrict__ eps, int L, int C, int use_ln,
-                                 float* __restrict__ g_pm, float* __restrict__ g_plv, float* __restrict__ latent, int Lreal)
+                                 float* __restrict__ g_pm, float* __restrict__ g_plv, float* __restrict__ latent, int Lreal, float beta)
 {
     // Lreal <= L: the layer-norm of iodine.py:376-395 (3-D case: mean and UNBIASED std over the latent axis) runs over the first Lreal
     // entries - the reference's DIM_LATENT; entries Lreal .. L - 1 exist only when the host padded the latent axis to a multiple of 4
@@ -613,8 +613,13 @@ __global__ void dz_latent_kernel(const float* __restrict__ Rc, const float* __re
         for (int q = 0; q < NS; ++q) dz += s_dz[q * Lp + l];
         mu = pm[(size_t)n * L + tid]; lv = plv[(size_t)n * L + tid];
         const float e = eps[(size_t)n * L + tid];
-        gm = dz - mu;
-        gl = dz * 0.5f * expf(0.5f * lv) * e - 0.5f * (expf(lv) - 1.f);
+        if (beta == 1.f) {                                  // (uniform) the default keeps its expression - and its fused multiply-adds - as it was
+            gm = dz - mu;
+            gl = dz * 0.5f * expf(0.5f * lv) * e - 0.5f * (expf(lv) - 1.f);
+        } else {
+            gm = dz - beta * mu;
+            gl = dz * 0.5f * expf(0.5f * lv) * e - beta * (0.5f * (expf(lv) - 1.f));
+        }
         g_pm[(size_t)n * L + tid] = gm;
         g_plv[(size_t)n * L + tid] = gl;
     }
@@ -636,7 +641,7 @@ __global__ void dz_latent_kernel(const float* __restrict__ Rc, const float* __re
 }
 
 hipError_t launch_dz_latent(hipStream_t st, const float* Rc, const float* wclsT, const float* pm, const float* plv,
-                            const float* eps, int N, int L, int C, int use_ln, float* g_pm, float* g_plv, float* latent, int Lreal)
+                            const float* eps, int N, int L, int C, int use_ln, float* g_pm, float* g_plv, float* latent, int Lreal, float beta)
 {
     if (Lreal <= 0 || Lreal > L) Lreal = L;
     IOD_XSKIP(32);
@@ -644,7 +649,7 @@ hipError_t launch_dz_latent(hipStream_t st, const float* Rc, const float* wclsT,
     if (Lp > 512) return hipErrorInvalidValue;                   // block_sum_f: at most 8 waves
     const int nth = (512 / Lp) * Lp;                             // 8 slices for L <= 64, 4 for L <= 128, ...
     hipLaunchKernelGGL(dz_latent_kernel, dim3(N), dim3(nth), (9 * C + nth) * sizeof(float), st, Rc, wclsT, pm, plv, eps, L, C,
-                       use_ln, g_pm, g_plv, latent, Lreal);
+                       use_ln, g_pm, g_plv, latent, Lreal, beta);
     return hipGetLastError();
 }
 

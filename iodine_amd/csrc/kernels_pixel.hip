@@ -114,11 +114,12 @@ void pixel_pass1_kernel(const float4* __restrict__ x4, const float4* __restrict_
 
 // ---- finalize + KL against N(0, 1) (iodine.py:653-659,191-193) + ELBO assembly in ONE launch (three until round 4: 5 us each behind a
 // 50 us kernel, six times per step).  Block b: image b.  img_terms[b] = {ll_b, kl_b}; the LAST block to finish (device-scope counter, reset by
-// that block) forms scal = {elbo, kl, ll} as the means over the images in fixed order.
+// that block) forms scal = {elbo, kl, ll} as the means over the images in fixed order; elbo = ll - beta x kl (beta: the KL weight of the
+// objective, iodine_set_objective; the product by beta = 1 is exact, so the default gives the bits of ll - kl), kl and ll stay raw.
 __global__ __launch_bounds__(256)
 void pixel_finalize_elbo_kernel(const double* __restrict__ part, int nblk, int K, int P, int use_ln, float* __restrict__ lnstat,
                                 float* __restrict__ ll_img, const float* __restrict__ pm, const float* __restrict__ plv, int KL_,
-                                float* __restrict__ img_terms, float* __restrict__ scal, unsigned* __restrict__ counter)
+                                float* __restrict__ img_terms, float* __restrict__ scal, unsigned* __restrict__ counter, float beta)
 {
     const int b = blockIdx.x, tid = threadIdx.x, B = gridDim.x;
     const int NST = 6 * K + 3;
@@ -185,7 +186,7 @@ void pixel_finalize_elbo_kernel(const double* __restrict__ part, int nblk, int K
         }
         if (tid == 0) {
             ll /= B; kl /= B;
-            scal[0] = (float)(ll - kl); scal[1] = (float)kl; scal[2] = (float)ll;
+            scal[0] = (float)(ll - (double)beta * kl); scal[1] = (float)kl; scal[2] = (float)ll;
             *counter = 0u;                                                    // (next launch: stream order)
         }
     }
@@ -359,12 +360,12 @@ hipError_t launch_pixel_pass1(hipStream_t st, const float* x4, const float* dec,
 }
 
 hipError_t launch_pixel_finalize_elbo(hipStream_t st, const double* part, int B, int K, int P, int use_ln, float* lnstat, float* ll_img,
-                                      const float* pm, const float* plv, int L, float* img_terms, float* scal, unsigned* counter)
+                                      const float* pm, const float* plv, int L, float* img_terms, float* scal, unsigned* counter, float beta)
 {
     IOD_XSKIP(8);
     if (6 * K + 3 > 99 || !counter) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pixel_finalize_elbo_kernel, dim3(B), dim3(256), 0, st, part, pixel_blocks_per_image(P), K, P, use_ln, lnstat, ll_img,
-                       pm, plv, K * L, img_terms, scal, counter);
+                       pm, plv, K * L, img_terms, scal, counter, beta);
     return hipGetLastError();
 }
 

@@ -99,8 +99,9 @@ hipError_t launch_render_bwd(hipStream_t st, const float* dec, const float* g_pr
 // dz[n][l] = sum_j Rc[n][j] * wclsT[j][l], j < 9 C: the class sums of d(pre-activation 0) through the broadcast layer's latent weights
 // (what dz_latent_kernel computes in front of its KL / layer-norm terms, which a single differentiated pass does not want).
 //   pm == NULL:  dz_out[n][l] = dz                                                                     (iodine_decode_backward)
-//   otherwise:   g_pm  = scale * (dz - mu)                                                             (iodine_elbo_backward: scale = 1 / B,
-//                g_plv = scale * (dz * 1/2 exp(logvar / 2) * eps - 1/2 (exp(logvar) - 1))               the batch mean of iodine.py:193,220)
+//   otherwise:   g_pm  = scale * (dz - beta mu)                                                        (iodine_elbo_backward: scale = 1 / B,
+//                g_plv = scale * (dz * 1/2 exp(logvar / 2) * eps - beta 1/2 (exp(logvar) - 1))          the batch mean of iodine.py:193,220;
+//                                                                                                       beta: the objective's KL weight)
 // One block per slot; blockDim = NS * Lp (Lp = L rounded up to 64): the contraction is cut into NS slices with four independent partial
 // sums each, combined in fixed order.
 // the contraction, shared by the two kernels below: s_rc = 9 * C class sums of slot n, then NS * Lp partial sums; the result is valid in
@@ -135,7 +136,7 @@ IOD_DEVINL float dz_contract(const float* __restrict__ Rc, const float* __restri
 
 __global__ void dz_plain_kernel(const float* __restrict__ Rc, const float* __restrict__ wclsT, int L, int C, float* __restrict__ dz_out,
                                 const float* __restrict__ pm, const float* __restrict__ plv, const float* __restrict__ eps, float scale,
-                                float* __restrict__ g_pm, float* __restrict__ g_plv)
+                                float* __restrict__ g_pm, float* __restrict__ g_plv, float beta)
 {
     extern __shared__ float s_rc[];                     // 9 * C, then NS * Lp partial sums
     const int n = blockIdx.x, Lp = (L + 63) / 64 * 64, l = threadIdx.x % Lp, slice = threadIdx.x / Lp;
@@ -144,18 +145,23 @@ __global__ void dz_plain_kernel(const float* __restrict__ Rc, const float* __res
     const size_t i = (size_t)n * L + l;
     if (!pm) { dz_out[i] = dz; return; }
     const float mu = pm[i], lv = plv[i];
-    g_pm[i] = scale * (dz - mu);
-    g_plv[i] = scale * (dz * 0.5f * expf(0.5f * lv) * eps[i] - 0.5f * (expf(lv) - 1.f));
+    if (beta == 1.f) {                                      // (uniform) the default keeps its expression as it was
+        g_pm[i] = scale * (dz - mu);
+        g_plv[i] = scale * (dz * 0.5f * expf(0.5f * lv) * eps[i] - 0.5f * (expf(lv) - 1.f));
+    } else {
+        g_pm[i] = scale * (dz - beta * mu);
+        g_plv[i] = scale * (dz * 0.5f * expf(0.5f * lv) * eps[i] - beta * (0.5f * (expf(lv) - 1.f)));
+    }
 }
 
 hipError_t launch_dz_plain(hipStream_t st, const float* Rc, const float* wclsT, int N, int L, int C, float* dz_out, const float* pm,
-                           const float* plv, const float* eps, float scale, float* g_pm, float* g_plv)
+                           const float* plv, const float* eps, float scale, float* g_pm, float* g_plv, float beta)
 {
     const int Lp = (L + 63) / 64 * 64;
     if (Lp > 512 || N < 1 || (pm ? (!plv || !eps || !g_pm || !g_plv) : !dz_out)) return hipErrorInvalidValue;
     const int nth = (512 / Lp) * Lp;
     hipLaunchKernelGGL(dz_plain_kernel, dim3(N), dim3(nth), (9 * C + nth) * sizeof(float), st, Rc, wclsT, L, C, dz_out, pm, plv, eps, scale,
-                       g_pm, g_plv);
+                       g_pm, g_plv, beta);
     return hipGetLastError();
 }
 

@@ -832,19 +832,39 @@ hipError_t launch_l0_coord_grads_rows(hipStream_t st, const float* Rsum, const f
 // =========================================================================================
 // loss and pointwise pieces of the head backward
 // =========================================================================================
-// loss = -sum_i (i+1)/(T+1) * ELBO_i   (iodine.py:151-158)
-__global__ void loss_kernel(const float* __restrict__ scal, int n, float* __restrict__ loss)
+// loss = -sum_i w_i * ELBO_i, w_i = (i+1)/(T+1) (iodine.py:151-158) or - wtab != NULL - the objective's table of n weights
+__global__ void loss_kernel(const float* __restrict__ scal, int n, float* __restrict__ loss, const float* __restrict__ wtab)
 {
     if (threadIdx.x == 0) {
         double s = 0.0;
-        for (int i = 0; i < n; ++i) s += (double)(i + 1) / n * scal[3 * i];
+        if (wtab) {
+            for (int i = 0; i < n; ++i) s += (double)wtab[i] * scal[3 * i];
+        } else {
+            for (int i = 0; i < n; ++i) s += (double)(i + 1) / n * scal[3 * i];
+        }
         *loss = (float)(-s);
     }
 }
 
-hipError_t launch_loss(hipStream_t st, const float* scal, int n, float* loss)
+hipError_t launch_loss(hipStream_t st, const float* scal, int n, float* loss, const float* wtab)
 {
-    hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(64), 0, st, scal, n, loss);
+    hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(64), 0, st, scal, n, loss, wtab);
+    return hipGetLastError();
+}
+
+// p[0 .. n) = 0.  Stands where hipMemsetAsync stood in the launch sequences that option "graph" captures: a memset NODE of a replayed
+// hipGraph was seen to fill the gradient accumulators with a stale 16-byte pattern instead of zeros (every parameter gradient of the
+// replayed step off by the same four values, period 4 floats) - a kernel node carries its arguments by value.
+__global__ void zero_fill_kernel(float* __restrict__ p, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0.f;
+}
+
+hipError_t launch_zero_fill(hipStream_t st, float* p, size_t n)
+{
+    if (n == 0) return hipSuccess;
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, p, n);
     return hipGetLastError();
 }
 
@@ -1053,8 +1073,9 @@ void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ 
                       const float* __restrict__ Wmlp, float* __restrict__ ddm_o, float* __restrict__ ddv_o,
                       float* __restrict__ dgates_o, float* __restrict__ ds_o, float* __restrict__ dpooled_o, int T, int N, int B,
                       int L, int H, int Cr, const float* __restrict__ seed_m, const float* __restrict__ seed_v,
-                      const float* __restrict__ gl_dev)
+                      const float* __restrict__ gl_dev, const float* __restrict__ wtab)
 {
+    // wtab: the objective's table of T + 1 loss weights (one uniform 4-byte load per iteration), NULL = the default (i + 1) / (T + 1)
     extern __shared__ __attribute__((aligned(16))) float s_hb[];
     float* s_dd = s_hb;                              // [HB][2L]   ddm | ddv
     float* s_dc1 = s_dd + HB * 2 * L;                // [HB][H]    (two halves summed: see below)
@@ -1072,7 +1093,7 @@ void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ 
     float gl = 0.f;
     if constexpr (SEED) gl = gl_dev ? gl_dev[0] : 0.f;
     for (int i = T - 1; i >= 0; --i) {
-        const float alpha = -((float)(i + 2) / (float)(T + 1)) / (float)B;
+        const float alpha = wtab ? -wtab[i + 1] / (float)B : -((float)(i + 2) / (float)(T + 1)) / (float)B;
         // 1. scaled posterior gradients of iteration i + 1
         for (int idx = tid; idx < HB * L; idx += 1024) {
             const int r = idx / L, l = idx % L, n = min(n0 + r, N - 1);
@@ -1158,7 +1179,7 @@ bool head_bptt_fits(int L, int H, int Cr) { return Cr <= H && H % 4 == 0 && Cr %
 hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_plv, const float* gates, const float* cst, const float* u,
                             const float* Wm, const float* Wv, const float* Whh, const float* Wih, const float* Wmlp, float* ddm,
                             float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr,
-                            const float* seed_m, const float* seed_v, const float* gl_dev)
+                            const float* seed_m, const float* seed_v, const float* gl_dev, const float* wtab)
 {
     IOD_XSKIP(2);
     if (Cr > H) return hipErrorInvalidValue;                                // (the pool gradient is staged in an [HB][H] buffer)
@@ -1170,13 +1191,13 @@ hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_pl
         static std::atomic<unsigned> attr_devs_seed{0};
         if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<true>, 160 * 1024, attr_devs_seed); e != hipSuccess) return e;
         hipLaunchKernelGGL(head_bptt_kernel<true>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
-                           ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, seed_m, seed_v, gl_dev);
+                           ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, seed_m, seed_v, gl_dev, wtab);
         return hipGetLastError();
     }
     static std::atomic<unsigned> attr_devs{0};
     if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<false>, 160 * 1024, attr_devs); e != hipSuccess) return e;
     hipLaunchKernelGGL(head_bptt_kernel<false>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
-                       ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr);
+                       ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr, wtab);
     return hipGetLastError();
 }
 

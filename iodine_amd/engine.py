@@ -33,13 +33,24 @@ class SyntheticScenes(torch.utils.data.Dataset):
         return torch.from_numpy(imgs[0]), torch.from_numpy(masks[0].astype('float32'))
 
 
-def train(model, optimizer, dataloader, device, max_steps, print_every=10, checkpoint_path=None, log=print, max_grad_norm=None):
+def beta_warmup(step, beta, warmup_steps):
+    """KL weight of training step ``step`` (counted from 0) under ``--beta-warmup``: a linear ramp from 0 at step 0 to ``beta`` at step
+    ``warmup_steps``, ``beta`` from there on; ``warmup_steps`` <= 0: ``beta`` throughout."""
+    if warmup_steps <= 0 or step >= warmup_steps:
+        return float(beta)
+    return float(beta) * step / warmup_steps
+
+
+def train(model, optimizer, dataloader, device, max_steps, print_every=10, checkpoint_path=None, log=print, max_grad_norm=None,
+          beta=None, beta_warmup_steps=0):
     """train.py:44-108: loss = model(data); loss.mean(); zero_grad; backward; [all-reduce]; [clip]; step.  Returns the losses.
     ``max_grad_norm``: the global gradient norm is clipped at this value (train.py:64, commented out in the reference; the paper
     uses 5.0) AFTER the all-reduce, so every rank clips the same averaged gradient with the same coefficient - what
     ``clip_grad_norm_`` after DataParallel's reduce would do - and the replicas stay bitwise identical.  A ``FusedAdam`` takes it
     as its ``max_grad_norm`` (fused into the step, kept on the optimizer afterwards); in front of any other optimizer
-    ``iodine_amd.optim.clip_grad_norm_`` runs.  The log line gains ``grad-norm`` (one ``.item()`` per ``print_every`` steps)."""
+    ``iodine_amd.optim.clip_grad_norm_`` runs.  The log line gains ``grad-norm`` (one ``.item()`` per ``print_every`` steps).
+    ``beta`` / ``beta_warmup_steps``: with ``beta`` given, ``model.beta`` is set before every step to ``beta_warmup(step, beta,
+    beta_warmup_steps)`` and is left at ``beta`` afterwards; None leaves ``model.beta`` alone."""
     model.train()
     fused_clip = isinstance(optimizer, FusedAdam)
     if max_grad_norm is not None:
@@ -57,6 +68,8 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
         for data in dataloader:
             start = time.perf_counter()
             x = data[0].to(device, non_blocking=True)                        # "first one is image" (train.py:49)
+            if beta is not None:
+                model.beta = beta_warmup(step, beta, beta_warmup_steps)
             loss = model(x).mean()
             optimizer.zero_grad()
             loss.backward()
@@ -75,6 +88,8 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
                     ', grad-norm: {:.4f}'.format(grad_norm.item()) if clipping else ''))
             if step >= max_steps:
                 break
+    if beta is not None:
+        model.beta = float(beta)
     if checkpoint_path and (not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0):
         save_checkpoint(checkpoint_path, model, optimizer, epoch=0, iteration=step)
     return losses
@@ -131,6 +146,13 @@ def make_parser():
     ap.add_argument('--gen-conv-precision', type=int, choices=[0, 1], default=0,
                     help='generic decoder convs C -> C (KERNEL_SIZE 5 / 7, other channel counts): 0 = exact fp32 MFMA, '
                          '1 = split-fp16 (3 x f16 MFMA, fp32-class accuracy) forward and data gradient')
+    ap.add_argument('--sigma', type=float, default=None, metavar='FLOAT',
+                    help='likelihood scale (model.sigma); default: ARCH.SIGMA of the config')
+    ap.add_argument('--beta', type=float, default=1.0, metavar='FLOAT', help='weight of the KL term (model.beta)')
+    ap.add_argument('--beta-warmup', type=int, default=0, metavar='STEPS',
+                    help='ramp the KL weight linearly from 0 to --beta over the first STEPS training steps')
+    ap.add_argument('--iter-weights', choices=['linspace', 'uniform', 'last'], default='linspace',
+                    help='per-iteration loss weights (model.iter_weights): (i+1)/(T+1), 1/(T+1) each, or the final ELBO only')
     return ap
 
 
@@ -152,6 +174,9 @@ def main(argv=None):
     model.manual_seed(1000 + rank)                                           # ... but its own reparameterisation noise
     if args.gen_conv_precision:
         model.set_option('gen_conv_precision', args.gen_conv_precision)
+    if args.sigma is not None:
+        model.sigma = args.sigma
+    model.beta, model.iter_weights = args.beta, args.iter_weights
     optimizer = make_optimizer(model, base_lr=args.lr, max_grad_norm=args.clip)
     if args.resume:
         load_checkpoint(args.resume, model, optimizer)
@@ -163,7 +188,7 @@ def main(argv=None):
         ds = SyntheticScenes(args.batch * world * 8, arch.IMG_SIZE)
     dl = make_dataloader(ds, args.batch, shuffle=True, rank=rank, world_size=world)
     losses = train(model, optimizer, dl, device, args.steps, checkpoint_path=args.save,
-                   log=print if rank == 0 else (lambda *a: None))
+                   log=print if rank == 0 else (lambda *a: None), beta=args.beta, beta_warmup_steps=args.beta_warmup)
     ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device)
     if rank == 0:
         print('first loss {:.2f} -> last loss {:.2f}; Ari over all ranks: {}'.format(losses[0], losses[-1], ev.global_mean))

@@ -15,6 +15,12 @@ them to run the same weights at another slot count (1..16) or iteration count - 
 weights trained at K = 7, T = 5 evaluated at K = 11 - and ``decode(z)`` takes K from ``z`` (iodine.py:430).  The library handle
 follows through ``iodine_set_run_shape``; ``loss.backward()`` differentiates the forward at the shape it ran with.
 
+The objective is read the same way: ``model.sigma`` (the reference reads ``self.sigma`` on every ``elbo()`` call, iodine.py:210),
+``model.beta`` - the weight of the KL term, as if iodine.py:223 read ``elbo = log_likelihood - self.beta * kl`` - and
+``model.iter_weights`` - the per-iteration loss weights of iodine.py:152-153: None / 'linspace' = (i+1)/(T+1), 'uniform', 'last' or a
+sequence of T + 1 numbers.  They are checked on the host when a call starts and reach the handle through ``iodine_set_objective``;
+``loss.backward()`` differentiates the forward with the objective it ran with.
+
 Video input and resumable refinement (the paper's tracking use of the T-step loop; the reference closes ``encode`` / ``forward`` over
 one ``x``, iodine.py:73-105,115-158): ``x`` may be a clip ``(B, E, 3, S, S)`` with one frame per ELBO evaluation of the call (E = T for
 ``encode`` / ``reconstruct``, T + 1 for ``forward``); ``reconstruct(x, trajectory=True)`` leaves the decode of every iteration in
@@ -290,7 +296,9 @@ class IODINE(nn.Module):
         self.encodings = list(ARCH.ENCODING)
         self.img_channels = ARCH.IMG_CHANNELS
         self.img_size = ARCH.IMG_SIZE
-        self.sigma = ARCH.SIGMA
+        self.sigma = ARCH.SIGMA         # likelihood scale, read when a call starts (iodine.py:210)
+        self.beta = 1.0                 # weight of the KL term: ELBO = LL - beta * KL; elbo_terms[:, 1] and the logger's kl stay the raw KL
+        self.iter_weights = None        # loss weights of the T + 1 ELBO evaluations of forward: None / 'linspace', 'uniform', 'last', a sequence
         self.use_layernorm = ARCH.LAYERNORM
         self.use_stop_gradient = _arch_get(ARCH, 'STOP_GRADIENT', False)
 
@@ -325,6 +333,7 @@ class IODINE(nn.Module):
         self._ws_key = None
         self._shape = None              # (slots, iters) the handle runs at (iodine_set_run_shape); follows self.K / self.n_iters
         self._frames = 0                # frames per call the handle expects (iodine_set_frames; 0 = one image)
+        self._objective = None          # (sigma, beta, weights) the handle holds (iodine_set_objective); None: the constructor's
         self._state = None              # _RefineState of the last encode / reconstruct: see refinement_state
         self._options: Dict[str, float] = {}
         self._seed = 0                  # Philox key of the library's normal generator (manual_seed)
@@ -373,6 +382,7 @@ class IODINE(nn.Module):
             self._handle, self._handle_device = h, device
             self._shape = (int(self._cfg.slots), int(self._cfg.iters))
             self._frames = 0
+            self._objective = (float(self._cfg.sigma), 1.0, ())
             for k, v in self._options.items():
                 if k in _WRAPPER_OPTIONS:
                     continue
@@ -408,7 +418,9 @@ class IODINE(nn.Module):
     # With option ``graph`` the library keys its hipGraphs on the full argument tuple, device addresses included.  Tensors the
     # caching allocator hands out per call (inputs made contiguous, noise, outputs, the flat gradient buffer) would change that
     # key from step to step - every call an eager run or a re-capture instead of a replay.  So in graph mode the library only
-    # ever sees persistent staging buffers owned by the module: inputs are copied in, outputs are cloned out.
+    # ever sees persistent staging buffers owned by the module: inputs are copied in, outputs are cloned out.  Host-side scalars are baked
+    # into captured nodes, so the key also holds the objective (sigma, beta, the weight table): a schedule that changes ``model.beta`` every
+    # step sees each key once and simply runs eagerly, a repeated objective is captured and replayed.
     def _graph_on(self):
         return bool(self._options.get('graph'))
 
@@ -474,6 +486,65 @@ class IODINE(nn.Module):
         if isinstance(T, bool) or int(T) != T or int(T) < 1:
             raise ValueError(f'IODINE: the iteration count (model.n_iters) must be an integer >= 1; got {T!r}')
         return int(K), int(T)
+
+    # ``model.sigma`` / ``model.beta`` / ``model.iter_weights``: read when a call starts, like K / n_iters, and checked on the host before
+    # any device work.  The handle follows through ONE iodine_set_objective call whenever any of the three differs from what it holds.
+    def _read_objective(self, T):
+        """(sigma, beta, weights) of the call that is starting at ``T`` iterations; weights: () = the default (i+1)/(T+1), else T + 1
+        floats.  ValueError for anything the library would refuse.  Every entry point reads all three "at call time", so explicit
+        ``iter_weights`` of the training length make encode / reconstruct / elbo at ANOTHER ``n_iters`` raise the length error although
+        inference never uses the weights, and a named weighting sends its table for the T of an inference call too - set
+        ``iter_weights = None`` (or a name) around evaluation at another iteration count."""
+        import math
+        import numbers
+
+        def number(v, name, rule, ok):
+            # a Python or numpy real number, or a tensor / array with one element - what a schedule usually produces
+            if torch.is_tensor(v) and v.numel() == 1 and not v.is_complex():
+                v = v.item()
+            elif not isinstance(v, numbers.Real) and getattr(v, 'size', None) == 1 and hasattr(v, 'item'):
+                v = v.item()
+            if isinstance(v, bool) or not isinstance(v, numbers.Real):
+                raise ValueError(f'IODINE: model.{name} must be a finite number {rule}, given as a real number or a one-element '
+                                 f'tensor; got {v!r} of type {type(v).__name__}')
+            if not math.isfinite(v) or not ok(v):
+                raise ValueError(f'IODINE: model.{name} must be a finite number {rule}; got {v!r}')
+            return float(v)
+        sigma = number(self.sigma, 'sigma', '> 0 (the likelihood scale)', lambda v: v > 0)
+        beta = number(self.beta, 'beta', '>= 0 (the weight of the KL term)', lambda v: v >= 0)
+        w = self.iter_weights
+        if w is None or (isinstance(w, str) and w == 'linspace'):
+            return sigma, beta, ()
+        if isinstance(w, str):
+            if w == 'uniform':
+                return sigma, beta, (1.0 / (T + 1),) * (T + 1)
+            if w == 'last':
+                return sigma, beta, (0.0,) * T + (1.0,)
+            raise ValueError(f"IODINE: model.iter_weights must be None, 'linspace', 'uniform', 'last' or a sequence of T + 1 numbers; "
+                             f'got {w!r}')
+        if torch.is_tensor(w):
+            w = w.detach().reshape(-1).tolist()
+        try:
+            w = tuple(w)
+        except TypeError:
+            raise ValueError(f"IODINE: model.iter_weights must be None, 'linspace', 'uniform', 'last' or a sequence of T + 1 numbers; "
+                             f'got {w!r}') from None
+        if len(w) != T + 1:
+            raise ValueError(f'IODINE: model.iter_weights has {len(w)} entries, but a call at n_iters = {T} makes {T + 1} ELBO '
+                             f'evaluations and takes {T + 1} weights (or one of the names, which follow n_iters)')
+        w = tuple(number(v, 'iter_weights[%d]' % i, '>= 0' , lambda v: v >= 0) for i, v in enumerate(w))
+        if not any(C.c_float(v).value > 0 for v in w):
+            raise ValueError(f'IODINE: model.iter_weights are all zero (as float32) - no evaluation would carry any loss; got {w!r}')
+        return sigma, beta, w
+
+    def _ensure_objective(self, h, obj, device):
+        if obj == self._objective:
+            return
+        sigma, beta, w = obj
+        arr = (C.c_double * len(w))(*w) if w else None
+        with torch.cuda.device(device):                     # (a new weight table is a small device allocation of the handle)
+            _lib.check(_lib.lib().iodine_set_objective(h, sigma, beta, arr, len(w)), h, 'iodine_set_objective')
+        self._objective = obj
 
     def _ensure_workspace(self, h, B, mode, device, K, T, frames=None):
         """Run shape (K, T), frame count and a workspace planned for (B, mode, K, T, frames) on the handle.  ``frames``: 0 = one image
@@ -552,7 +623,9 @@ class IODINE(nn.Module):
         return out
 
     def set_option(self, key: str, value: float):
-        """Debug/test options of the library (e.g. ``stop_after_iters``); applied to the live handle."""
+        """Debug/test options of the library (e.g. ``stop_after_iters``); applied to the live handle.  ``graph``: hipGraph replay of the
+        fixed-shape launch sequences, one graph per distinct argument tuple - which includes ``model.sigma`` / ``beta`` / ``iter_weights``:
+        an objective that changes every step (a beta warm-up) runs eagerly until it repeats."""
         self._options[key] = float(value)
         if key in _WRAPPER_OPTIONS:                 # handled by this wrapper, unknown to the library
             return
@@ -643,6 +716,7 @@ class IODINE(nn.Module):
     @torch.no_grad()
     def _reconstruct(self, x, eps, want_images=True, state=None, trajectory=False, keep_state=False):
         K, T = self._run_shape()
+        obj = self._read_objective(T)
         x, frames = self._check_frames(x, T, 'encode / reconstruct')
         dev, B = x.device, x.shape[0]
         stop = int(self._options.get('stop_after_iters', -1))
@@ -676,6 +750,7 @@ class IODINE(nn.Module):
             return tuple(None if outs[0][j] is None else torch.cat([o[j] for o in outs], 0) for j in range(4))
         h = self._sync_params(dev)
         self._ensure_workspace(h, B, 0, dev, K, T, frames)
+        self._ensure_objective(h, obj, dev)
         eps = self._eps(eps, B, dev)
         xs = self._stage('x', x)
         L, S = self.dim_latent, self.img_size
@@ -871,6 +946,7 @@ class IODINE(nn.Module):
         reference.  ``eps`` (B, K, L) replaces the ``torch.randn_like`` draw.  Returns the scalar ELBO (no autograd graph:
         the gradients the reference takes from it are what reconstruct / forward compute in closed form)."""
         K, T = self._run_shape()
+        self._read_objective(T)
         x = self._check_x(x)
         dev, B = x.device, x.shape[0]
         cap = self.max_batch()
@@ -895,9 +971,11 @@ class IODINE(nn.Module):
         """One iodine_elbo of at most ``max_batch`` images from the posterior (pm, plv) - None: the initial one; ``save``: kept for
         iodine_elbo_backward.  x as ``_check_x`` returns it."""
         K, T = self._run_shape()
+        obj = self._read_objective(T)
         dev, B = x.device, x.shape[0]
         h = self._sync_params(dev)
         self._ensure_workspace(h, B, 2 if save else 0, dev, K, T)
+        self._ensure_objective(h, obj, dev)
         shape = (B, K, self.dim_latent)
         eps = self._normals(eps, shape, dev)
         if pm is not None:
@@ -961,7 +1039,8 @@ class IODINE(nn.Module):
 
     # ---- training: iodine.py:115-158 + lib/engine/train.py:60-63 -------------------------------------
     def forward(self, x, eps=None, state=None, attach_state=False):
-        """-sum_i (i+1)/(T+1) ELBO_i, differentiable wrt every parameter.  ``loss.backward()`` differentiates the forward as it
+        """-sum_i w_i ELBO_i (w = ``model.iter_weights``, by default (i+1)/(T+1); ELBO_i = LL_i - ``model.beta`` KL_i at ``model.sigma``),
+        differentiable wrt every parameter.  ``loss.backward()`` differentiates the forward as it
         ran, at the (K, T) it read - like the reference, whose autograd graph is fixed at forward time.  ``x``: images
         (B, 3, S, S) or a clip (B, T+1, 3, S, S), ELBO_i then against frame i (no gradient flows to the frames).  A training forward
         always starts from the initial posterior: ``state`` is refused (no truncated back-propagation across calls).
@@ -978,6 +1057,7 @@ class IODINE(nn.Module):
             raise RuntimeError('IODINE.forward takes no state=: a training forward starts from the initial posterior (continuing one '
                                'across calls would need back-propagation through the earlier call); use encode / reconstruct')
         _, T = self._run_shape()
+        self._read_objective(T)                      # (refusals before any device work; _train_forward hands it to the handle)
         x, _ = self._check_frames(x, T + 1, 'forward')
         self._state = None                          # the state of an earlier encode / reconstruct ends here (refinement_state)
         attach = bool(attach_state) and torch.is_grad_enabled()
@@ -1009,8 +1089,10 @@ class IODINE(nn.Module):
     def _train_forward(self, x, eps):
         dev, B = x.device, x.shape[0]
         K, T = self._run_shape()
+        obj = self._read_objective(T)
         h = self._sync_params(dev)
         self._ensure_workspace(h, B, 1, dev, K, T, x.shape[1] if x.dim() == 5 else 0)
+        self._ensure_objective(h, obj, dev)
         loss = self._out('t.loss', (), dev)
         elbo_iter = self._out('t.elbo', (T + 1, 3), dev)
         xs, eps = self._stage('x', x), self._stage('eps', eps)
