@@ -1,26 +1,11 @@
-// Host side of libiodine_hip.so: handle, parameter repacking, workspace planning and the
-// T-step refinement loop (kernel launch sequence).  See include/iodine_hip.h for the ABI and the
-// reference call sites each entry point replaces.
-#include "../../include/iodine_hip.h"
-#include "common.h"
-
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <list>
-#include <string>
-#include <vector>
-
-namespace {
+// The compute handle of libiodine_hip.so: parameter repacking, workspace planning, kernel dispatch and the T-step refinement loop
+// (kernel launch sequence), settings.  See include/iodine_hip.h for the ABI and the reference call sites each entry point replaces;
+// iodine_pad.cpp for handles at a padded width, iodine_ops.cpp for the entry points that take no handle.
+#include "iodine_internal.h"
 
 std::string g_create_error;
 
-struct ParamInfo {
-    std::string name;
-    int ndim;
-    long long dims[4];
-    size_t numel() const { size_t n = 1; for (int i = 0; i < ndim; ++i) n *= (size_t)dims[i]; return n; }
-};
+namespace {
 
 // bump allocator over a (possibly NULL = size query) base pointer
 struct Arena {
@@ -35,204 +20,13 @@ struct Arena {
     }
 };
 
-struct Buffers {               // workspace carve-up for one batch size / mode / run shape
-    int B = 0, mode = -1;
-    int K = 0, T = 0;                          // the run shape (slots, iterations) it was planned for: the shape of the state it holds
-    int F = 0;                                 // frames x4 holds ([F][B][P][4]; iodine_set_frames, 1 = the single image)
-    size_t bytes = 0;
-    float *x4, *V, *dec_out, *g, *lnstat, *ll_img, *img_terms, *scal, *rows, *rows_p, *Rc, *pm, *plv;
-    double* part;
-    std::vector<float*> act;                   // decoder activations a[0..Dd-1]   (N,P,Cd)
-    float *head_xh = nullptr, *head_gp = nullptr;   // refinement head in three launches: LSTM input rows, gate pre-activations
-    float* dpre[2];                            // ping-pong gradient wrt pre-activations
-    std::vector<float*> tmax_act;              // per-cell max |act[l]| (4 floats per 8 x 16 cell): tile scales of the weight-stationary conv
-    float* tmax_dpre[2] = {nullptr, nullptr};  // the same for the two gradient buffers
-    // per-iteration buffers: index i (training keeps all T(+1) copies, inference aliases them)
-    std::vector<float*> z, g_pm, g_plv, latent, enc, pooled, u, gates, xin, h, c;
-    std::vector<float*> enck, encs;             // split refinement input: per-slot [N][P][12], per-image [B][P][8] (alias enc's memory)
-    float* rmap = nullptr;                      // split first refinement layer: conv of the per-image channels, [B][S/2][S/2][Cr]
-    std::vector<std::vector<float*>> ract;     // [iter][layer] refinement activations
-    // training only
-    float *wg_part = nullptr, *wg_part_b = nullptr, *wg_fold = nullptr, *Dsum = nullptr, *Dpart = nullptr, *RT = nullptr, *tmp_lz = nullptr;
-    // round 5 (option wgrad_accum): per-layer partial weight-gradient tiles kept over the T + 1 decoder passes of a step (one reduction
-    // per layer and step); [0] = the output conv, [l] = decoder layer l
-    std::vector<float*> wg_acc, wg_acc_b;
-    float *rown = nullptr, *Rsum = nullptr;     // training row-sum form of the broadcast layer's backward (EPI_L0ROWSX)
-    float* l0scr = nullptr;                     // partial class sums of the row-sum reductions (l0_rows_scratch_floats)
-    float *ddm = nullptr, *ddv = nullptr, *dc1 = nullptr, *dgates = nullptr, *dxin = nullptr, *ds = nullptr,
-          *dpooled = nullptr;
-    float* carry_h[2] = {nullptr, nullptr};
-    float* carry_c[2] = {nullptr, nullptr};
-    std::vector<float*> rdpre;                 // gradient wrt refinement pre-activations, per layer
-    float* aux_seed = nullptr;                 // [2][N][L]: seeds of the head BPTT from auxiliary cotangents (iodine_train_backward_aux)
-    float *gen_scr = nullptr, *gen_l0 = nullptr;                // generic path: wgrad partials; layer-0 scratch (kernels_genl0.hip)
-};
-
-// index of every parameter in the parameter table (= in gacc and in the caller's pointer array), resolved once by build_param_table
-struct ParamSlots {
-    std::vector<int> ref_w, ref_b;              // refine.mlc.layers.<l>
-    int mlp_w, mlp_b, wih, whh, bih, bhh, wm, bm, wv, bv;   // the refinement head
-    std::vector<int> dec_w, dec_b;              // decoder.mlc.layers.<l>
-    int out_w, out_b;                           // decoder.conv
-    int init_mean, init_logvar;
-};
-
 }  // namespace
-
-// HIP-event profiler: when enabled every launch of a category is bracketed by two events on the
-// launch stream; totals are read back (after a sync) with iodine_profile_read.
-struct ProfCat { std::string name; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; unsigned long long seen = 0, seen_win = 0; };
-
-struct GraphEntry { std::vector<uintptr_t> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
-
-// The objective a call optimises (iodine_set_objective): likelihood scale, KL weight and the per-iteration loss weights.  Held by value:
-// a training forward / a saved elbo keeps the copy it ran with, its backward reads that copy and not the handle's current one.
-// wtab: device table of nw = T + 1 floats, nullptr = the default weighting w_i = (i + 1) / (T + 1), which stays the closed-form
-// expression in the kernels and on the host.  Tables are immutable once uploaded (WeightTable below), so a copy of the pointer is a snapshot;
-// wgen names the table in the hipGraph key (0 = default).
-struct Objective {
-    double sigma = 0.1, beta = 1.0;
-    const float* wtab = nullptr;
-    const float* whost = nullptr;               // the same weights on the host (owned by the handle's table list)
-    int nw = 0, wgen = 0;
-};
-struct WeightTable { std::vector<float> w; float* dev = nullptr; int gen = 0; };
-
-struct iodine_handle {
-    iodine_config cfg;
-    Objective obj;                              // current; initially (ARCH.SIGMA, 1, default weighting)
-    Objective fwd_obj, diff_obj;                // what the saved training forward / the saved elbo ran with
-    std::list<WeightTable> wtabs;               // every distinct weight table this handle was given (content-addressed, never rewritten)
-    int wgen_next = 1;                          // generation of the next new table: counts up for the life of the handle, never re-used
-    std::string err;
-    int profile = 0;                            // 0 off, 1 the dominant conv kernels ("conv_tile_*") only, 2 every category
-    int profile_stride = 1;                     // level 1: bracket every n-th launch of a category only - an event pair costs ~12 us of idle GPU
-                                                // (a barrier packet in front of the kernel and one behind it: tools/step_timeline.py), 54 pairs per cfg3
-                                                // training step = 0.8 ms of the step being measured; a stride coprime to the layer count samples every layer
-    std::vector<ProfCat> prof;
-    ProfCat* prof_cat(const char* name) {
-        for (auto& c : prof) if (c.name == name) return &c;
-        prof.push_back(ProfCat()); prof.back().name = name; return &prof.back();
-    }
-    int L, T, K, S, P, Cd, Dd, Cr, Dr, H;       // K / T: the RUN shape (iodine_set_run_shape; cfg.slots / cfg.iters initially) - the
-                                                // state a call leaves behind has the shape in buf.K / buf.T
-    std::vector<ParamInfo> params;
-    ParamSlots slot;
-    bool params_set = false;
-    int stop_after = -1;
-    int frames = 0;                             // iodine_set_frames: 0 = x is one image per batch entry, E = a clip of E frames, one per ELBO evaluation
-    int state_iter = -1;                        // buf.h / buf.c [state_iter] = LSTM state the last iodine_reconstruct left (-1: none to read)
-
-    // parameter-derived device buffers (owned)
-    float* lin = nullptr;                       // linspace(-1,1,S)
-    float *wcls = nullptr, *wclsT = nullptr, *cmap = nullptr;
-    std::vector<float*> dec_wf, dec_wb, dec_b;  // packed fwd / dgrad weights + bias copies for layers 1..Dd-1
-    std::vector<float*> dec_wf16, dec_wb16, dec_wmeta;   // split-fp16 packs (+ {scale, 1/scale, scale_b, 1/scale_b})
-    std::vector<float*> dec_wsf, dec_wsb;                // the same weights in the register layout of the weight-stationary conv
-    int precision = 1;                          // 0: exact fp32 MFMA, 1: 3 x fp16 MFMA split (fp32-class accuracy)
-    int out_bwd_fused = 1;                      // training: output conv data + weight gradient in one pass over the activation
-    int fuse_l0 = 1;                            // inference: layer-1 data gradient reduces straight to the layer-0 row sums
-    int refine_split = 1;                       // first refinement layer split into a per-slot and a per-image part (split-fp16 path)
-    int head_fused = 1;                         // training backward: the head's BPTT recurrence as ONE launch (0 = 9 launches per iteration)
-    int refine_bwd_fused = 1;                   // training backward: data gradient of refinement layer 1 + weight gradient of layer 0 in one
-                                                // launch, d(pre-activation 0) never stored (kernels_refbwd.hip; 0 = the two launches)
-    bool fwd_split = false;                     // the form the saved training forward used
-    int variant = 6;                            // split-fp16 stride-1 conv: 6 = weight-stationary persistent kernel (power-of-two image sizes;
-                                                // other sizes use 1), 1 = LDS-tiled 16x16 tiles (2 blocks/CU)
-    float* dec_out_w32 = nullptr;               // fp32 operand of the row-streaming output conv (conv_precision 0)
-    float *dec_out_w = nullptr, *dec_out_b = nullptr, *dec_out_wb = nullptr, *dec_out_w16 = nullptr, *dec_out_meta = nullptr,
-          *dec_out_wb16 = nullptr;               // split-fp16 pack of the output conv for its data gradient
-    std::vector<float*> ref_w, ref_b;
-    float *mlp_wT = nullptr, *mlp_b = nullptr, *wihT = nullptr, *whhT = nullptr, *lstm_b = nullptr;
-    float *wmT = nullptr, *bm = nullptr, *wvT = nullptr, *bv = nullptr, *init_mean = nullptr, *init_logvar = nullptr;
-    // training: raw copies used by the head backward GEMMs, strided-dgrad packs, gradient accumulators
-    float *raw_mlp_w = nullptr, *raw_wih = nullptr, *raw_whh = nullptr, *raw_wm = nullptr, *raw_wv = nullptr;
-    std::vector<float*> ref_wb;
-    std::vector<float*> ref_wf16, ref_wb16, ref_wmeta;     // split-fp16 packs of the stride-2 convs (+ {scale, 1/scale} x {fwd, dgrad})
-    float *ref_wk = nullptr, *ref_wsh = nullptr;           // split first layer: weights in the internal channel order [Cr][12][9], [Cr][8][9]
-    float *ref_wk16 = nullptr, *ref_wsh16 = nullptr, *ref_wkmeta = nullptr, *ref_wshmeta = nullptr;   // and their packs
-    float* ref_g20 = nullptr;                              // [Cr][20][9] weight gradient in the internal order
-    unsigned* elbo_counter = nullptr;                      // ticket of pixel_finalize_elbo_kernel (zero between launches)
-    int head_mfma = 1;                                     // LSTM gate pre-activations of the refinement head as one fp32-MFMA GEMM over all slots
-    int refine_l0_fused = 1;                               // encoding + first refinement layer in one kernel (kernels_refl0.hip); 0: pixel_pass2 + two convs
-    void *ref_l0k = nullptr, *ref_l0s = nullptr; float *ref_l0kmeta = nullptr, *ref_l0smeta = nullptr;     // its weight packs
-    int wgrad_accum = 0;                                   // 1: the decoder's partial weight-gradient tiles accumulate over the T + 1 passes of a training
-                                                           // step (alpha = pass weight) and are reduced once per layer and step.  Measured (round 5, same
-                                                           // process A/B): cfg3 48.197 vs 48.200 ms, cfg2 6.55 vs 6.53 ms - the read-modify-write of the
-                                                           // partial tiles in the kernels' tails costs what the 20 saved reduce launches cost: NOT adopted,
-                                                           // kept as an option (off: no extra workspace)
-    int dec_out_rows = 1;                                  // output conv forward: row-streaming kernel without halo recompute (S in {32, 64, 128}); 0 = 16 x 16 tiles
-    int refine_ws = 1;                                     // forward stride-2 convs of refinement layers 1 .. on the weight-stationary kernel (kernels_refws.hip)
-    std::vector<float*> ref_wsf, ref_wsf_meta;             // their weights in its register layout
-    float *ref_w1ws = nullptr, *ref_w1ws_meta = nullptr;   // layer 1's weights in the register layout of the fused layer-1/0 backward
-    // ARCH.ENCODING subsets: reference input channel j of the first refinement layer = internal channel enc_map[j] (code order of
-    // iodine.py:277-340); n_in < 17 -> weights expanded to / gradients gathered from the 17 internal channels
-    int n_in = 17;
-    int enc_map[17];
-    unsigned enc_chmask = 0x1ffffu;                        // bit c: internal channel c is part of the encoding (absent ones are written as 0)
-    float *ref_w17 = nullptr, *ref_g17 = nullptr;          // [Cr][17][kr * kr]
-    // GENERIC fallback path (kernels_generic.hip): KERNEL_SIZE other than 3 or CONV_CHAN other than 32 / 64.  Weights re-packed to
-    // [tap][ci][co]; the broadcast layer is materialised; nothing of the tuned conv kernels runs.
-    bool generic = false;                                  // the DECODER runs on the generic path
-    bool gen_ref = false;                                  // the REFINEMENT conv stack runs on the generic path (round 5: decided separately -
-                                                           // the reference's default ARCH has REF.KERNEL_SIZE 3 / 32 channels beside DEC.KERNEL_SIZE 5)
-    int kd = 3, kr = 3;                                    // DEC / REF kernel sizes
-    int rs = 2;                                            // REF.STRIDE (round 6: other strides run on the generic path's kernels)
-    std::vector<float*> gen_wdec, gen_wref;                // [layer]: packed weights
-    float *gen_wout = nullptr, *gen_cterm = nullptr, *gen_ident = nullptr;   // output conv pack, [P][Cd] bias + coordinate term of decoder layer 0, [9 Cd][L] identity
-    // option gen_conv_precision 1 (kernels_gensplit.hip): split-fp16 slice images + per-slice inverse scales of the decoder's C -> C layers,
-    // forward / data gradient; allocated by the first iodine_set_params that needs them.  gen_split: the packs are current and the shape is covered
-    int gen_precision = 0;
-    bool gen_split = false;
-    std::vector<void*> gs_wf, gs_wb;
-    std::vector<float*> gs_mf, gs_mb;
-    std::vector<float*> gacc;                   // one per parameter, reference shapes (slices of gacc_arena)
-    float* gacc_arena = nullptr;
-    size_t gacc_total = 0;
-    bool fwd_done = false;
-    int fwd_batch = 0;
-    // a single decode / elbo that ran "for backward" (option save_for_backward): its z, decoder activations and dec_out stay in the arena
-    // (workspace mode 2) until the next compute call; iodine_decode_backward / iodine_elbo_backward consume it
-    int save_bwd = 0;                           // the option
-    int diff_kind = 0;                          // 0 = nothing saved, 1 = a decode, 2 = an elbo
-    int diff_batch = 0;
-    bool diff_init = false;                     // the saved elbo sampled from the initial posterior (init_mean / init_logvar receive gradients)
-    // last elbo() call (iodine.py:161-241): which z buffer / batch the decoder output in buf.dec_out belongs to
-    int last_elbo_iter = -1, last_elbo_batch = 0;
-    bool enc_valid = false;                     // the last call left the refinement input ("enc") of its iterations in the workspace
-    // hipGraph replay of the fixed-shape launch sequences (option "graph"): one instantiated graph per distinct argument tuple
-    int graph = 0;
-    std::vector<GraphEntry> graphs;
-    std::vector<std::vector<uintptr_t>> seen_keys;       // argument tuples that ran eagerly once (the next call captures)
-    unsigned long long graph_clock = 0;
-    long long graph_replays = 0, graph_captures = 0;
-    std::vector<void*> owned;
-    // round 6: DIM_LATENT / REF.MLP_UNITS that are not multiples of 4.  Lreal: the reference's DIM_LATENT when this handle runs at a padded
-    // latent width (the 3-D layer-norm and the logger means are taken over the real entries); shim: this handle is only the boundary of a
-    // padded INNER handle (see PadShim below)
-    int Lreal = 0;
-    struct PadShim* shim = nullptr;
-
-    // workspace
-    void* ws_user = nullptr; size_t ws_user_bytes = 0;
-    void* ws_own = nullptr; size_t ws_own_bytes = 0;
-    Buffers buf;
-
-    int fail(int code, const std::string& m) { err = m; return code; }
-};
 
 #ifdef IODINE_XSKIP_HOOK
 int g_iod_xskip = 0;
 #endif
 
 namespace {
-
-#define HIPCHK(h, expr)                                                                          \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return (h)->fail(IODINE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // bracket one launch expression with profiler events (no-op unless profiling is on)
 #define PROF(h, st, cat, expr)                                                       \
@@ -657,10 +451,7 @@ int ensure_workspace(iodine_handle* h, int B, int mode)
     }
     Arena a(base);
     plan(h, B, mode, a, h->buf);
-    h->fwd_done = false; h->diff_kind = 0;                 // a re-planned arena no longer holds the saved forward / the last elbo() outputs
-    h->last_elbo_iter = -1;
-    h->state_iter = -1;
-    h->enc_valid = false;
+    h->calls.arena_gone();                                 // a re-planned arena no longer holds the saved forward / the last elbo() outputs
     // captured graphs stay: their key holds the arena's base address, the batch, the run shape and (through the entry point) the mode,
     // and the carve-up is a pure function of those - a step that alternates training and reconstruct calls keeps replaying both
     return IODINE_OK;
@@ -856,7 +647,6 @@ int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps
     if (i == 0) HIPCHK(h, hipMemsetAsync(h->elbo_counter, 0, sizeof(unsigned), st));
     HIPCHK(h, launch_pixel_finalize_elbo(st, b.part, B, h->K, h->P, h->cfg.layernorm, b.lnstat, b.ll_img, b.pm, b.plv, h->L,
                                          b.img_terms + (size_t)i * B * 2, b.scal + 3 * i, h->elbo_counter, beta));
-    h->last_elbo_iter = i; h->last_elbo_batch = B;
     if (!need_grads) return IODINE_OK;
     float* dpre0 = nullptr;
     rc = decoder_backward_data(h, st, N, &dpre0, train, train_alpha, i);
@@ -885,7 +675,7 @@ int refine_step(iodine_handle* h, hipStream_t st, int B, int i, bool save)
     Buffers& b = h->buf;
     const int N = B * h->K;
     // split first layer: the channels every slot of an image shares are written and convolved once per image
-    const bool split = refine_split_on(h);     // (training: iodine_train_forward records the form in h->fwd_split - host state must
+    const bool split = refine_split_on(h);     // (training: iodine_train_forward records the form in calls.fwd_split - host state must
                                                //  not be written here, a hipGraph replay does not execute this body)
     // ... and with refine_l0_fused the encoding is not written at all (inference): one kernel from the decoder output to layer 0's output
     const bool l0f = split && h->precision == 1 && h->refine_l0_fused && refine_l0_fused_ok(h->S, h->Cr, h->K);
@@ -1007,140 +797,129 @@ std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, s
     return k;
 }
 
-
-// cotangents of iodine_train_backward_aux (device pointers, each may be NULL): gl = d(out) / d(loss); the rest on the final evaluation's
-// mean / mask / mask_logits / z and on lambda_T
-struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv; };
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Round 6 - DIM_LATENT / REF.MLP_UNITS that are not multiples of 4 (the reference takes any: iodine.py:8-32, 446-464).
-// The refinement-head kernels move weight rows as 16-byte vectors, so such a model runs on an INNER handle created at Lp = ceil4(L),
-// Hp = ceil4(H) with every parameter zero-padded into the wider shapes.  Padding is exact, not approximate:
-//   * padded latent entries have init_mean = init_logvar = 0, their decoder-input weights and the rows of mean_update / logvar_update
-//     that produce them are 0, eps is padded with 0: z = mu = 0, logvar = 0 for the whole loop, KL contribution 1/2 (0 + 1 - 0 - 1) = 0,
-//     d ELBO / d lambda = 0, and the LSTM reads them through zero columns of weight_ih;
-//   * padded hidden units: zero MLP row and bias -> u = ELU(ELU(0)) = 0; zero gate rows and biases -> i = f = o = 1/2, g = 0 -> c1 = h1 = 0
-//     from c0 = h0 = 0; the read-out and weight_hh see them through zero columns;
-//   * the one place where the WIDTH itself enters the arithmetic - the layer-norm of the lambda gradients over the latent axis
-//     (iodine.py:263-272, 376-384: mean and unbiased std over L) - runs over the real L (inner->Lreal, dz_latent_kernel), and so does the
-//     logger's mean of init_mean / init_logvar.
-// The outer handle owns the reference-shaped boundary: parameter table, padded copies of the parameters, the element maps, scratch for the
-// tensors with a latent axis (eps, z, posterior), and the gradient in padded shape; every entry point forwards to the inner handle.
 }  // namespace
-struct PadShim {
-    iodine_handle* inner = nullptr;
-    int L = 0, H = 0, Lp = 0, Hp = 0;
-    std::vector<float*> pparam;            // padded parameter copies [param]
-    std::vector<int*> pmap;                // [param][padded element] -> element of the reference-shaped tensor, or -1 (zero)
-    std::vector<int> pnumel;               // padded element counts
-    float* pgrad = nullptr;                // flat gradient in padded shapes (the inner handle's named_parameters() order)
-    std::vector<size_t> poff;
-    size_t pgrad_total = 0;
-    // scratch for one call's tensors with a latent axis: grown on demand (outside the refinement loop)
-    size_t cap = 0;                        // floats per buffer
-    float *eps = nullptr, *z = nullptr, *pm = nullptr, *plv = nullptr, *pm_in = nullptr, *plv_in = nullptr;
-    float *hs = nullptr, *cs = nullptr;    // LSTM state rows at the padded width (initial state in / state out)
-    std::vector<void*> owned;
-};
-namespace {
 
-int shim_fail(iodine_handle* h, int rc)
-{
-    if (rc && h->shim && h->shim->inner) h->err = h->shim->inner->err.empty() ? std::string(iodine_last_error(nullptr)) : h->shim->inner->err;
-    return rc;
-}
+// ---- the host-only refusals of the entry points (see iodine_internal.h): nothing below launches, allocates or changes state
 
-// per-dimension index map of a concatenation of segments (real length -> padded length): padded index -> real index or -1
-std::vector<int> seg_map(std::initializer_list<std::pair<int, int>> segs)
+int set_params_check(iodine_handle* h, const float* const* dev, int n)
 {
-    std::vector<int> m;
-    int real0 = 0;
-    for (const auto& sg : segs) {
-        for (int i = 0; i < sg.second; ++i) m.push_back(i < sg.first ? real0 + i : -1);
-        real0 += sg.first;
-    }
-    return m;
-}
-
-int shim_build(iodine_handle* h)
-{
-    PadShim* sh = h->shim;
-    const int L = sh->L, H = sh->H, Lp = sh->Lp, Hp = sh->Hp;
-    iodine_handle* in = sh->inner;
-    const size_t np = h->params.size();
-    if (in->params.size() != np) return h->fail(IODINE_ERR_INVALID, "padded inner handle: parameter tables differ");
-    sh->pparam.assign(np, nullptr); sh->pmap.assign(np, nullptr); sh->pnumel.assign(np, 0); sh->poff.assign(np, 0);
-    auto ident = [](int n) { std::vector<int> m(n); for (int i = 0; i < n; ++i) m[i] = i; return m; };
-    const std::vector<int> mH = seg_map({{H, Hp}}), mL = seg_map({{L, Lp}}), m4H = seg_map({{H, Hp}, {H, Hp}, {H, Hp}, {H, Hp}}),
-                           mIN = seg_map({{H, Hp}, {L, Lp}, {L, Lp}, {L, Lp}, {L, Lp}}), mL2 = seg_map({{L, Lp}, {2, 2}});
-    size_t off = 0;
-    for (size_t i = 0; i < np; ++i) {
-        const ParamInfo &pr = h->params[i], &pp = in->params[i];
-        if (pr.name != pp.name || pr.ndim != pp.ndim) return h->fail(IODINE_ERR_INVALID, "padded inner handle: parameter " + pr.name + " differs");
-        std::vector<int> dm[4];
-        for (int d = 0; d < 4; ++d) dm[d] = ident((int)pp.dims[d]);
-        const std::string& n = pr.name;
-        if (n == "refine.mlp.layers.0.weight" || n == "refine.mlp.layers.0.bias") dm[0] = mH;
-        else if (n == "refine.lstm.weight_ih") { dm[0] = m4H; dm[1] = mIN; }
-        else if (n == "refine.lstm.weight_hh") { dm[0] = m4H; dm[1] = mH; }
-        else if (n == "refine.lstm.bias_ih" || n == "refine.lstm.bias_hh") dm[0] = m4H;
-        else if (n == "refine.mean_update.weight" || n == "refine.logvar_update.weight") { dm[0] = mL; dm[1] = mH; }
-        else if (n == "refine.mean_update.bias" || n == "refine.logvar_update.bias" || n == "posterior.init_mean" || n == "posterior.init_logvar") dm[0] = mL;
-        else if (n == "decoder.mlc.layers.0.weight") dm[1] = mL2;          // [Cd][L latent channels | x, y][k][k]
-        for (int d = 0; d < 4; ++d)
-            if ((long long)dm[d].size() != pp.dims[d]) return h->fail(IODINE_ERR_INVALID, "padded inner handle: shape of " + n);
-        const size_t numel = pp.numel();
-        std::vector<int> map(numel);
-        size_t e = 0;
-        for (int a = 0; a < (int)pp.dims[0]; ++a)
-            for (int b2 = 0; b2 < (int)pp.dims[1]; ++b2)
-                for (int c = 0; c < (int)pp.dims[2]; ++c)
-                    for (int d = 0; d < (int)pp.dims[3]; ++d, ++e) {
-                        const int ia = dm[0][a], ib = dm[1][b2], ic = dm[2][c], id = dm[3][d];
-                        map[e] = (ia < 0 || ib < 0 || ic < 0 || id < 0) ? -1
-                                 : (int)((((size_t)ia * pr.dims[1] + ib) * pr.dims[2] + ic) * pr.dims[3] + id);
-                    }
-        void *dmap = nullptr, *dpar = nullptr;
-        HIPCHK(h, hipMalloc(&dmap, numel * sizeof(int))); sh->owned.push_back(dmap);
-        HIPCHK(h, hipMemcpy(dmap, map.data(), numel * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMalloc(&dpar, numel * sizeof(float))); sh->owned.push_back(dpar);
-        sh->pmap[i] = (int*)dmap; sh->pparam[i] = (float*)dpar; sh->pnumel[i] = (int)numel; sh->poff[i] = off;
-        off += numel;
-    }
-    sh->pgrad_total = off;
-    void* g = nullptr;
-    HIPCHK(h, hipMalloc(&g, off * sizeof(float))); sh->owned.push_back(g);
-    sh->pgrad = (float*)g;
+    if (n != (int)h->params.size() || !dev) return h->fail(IODINE_ERR_INVALID, "iodine_set_params: wrong parameter count");
+    for (int i = 0; i < n; ++i)
+        if (!dev[i]) return h->fail(IODINE_ERR_INVALID, "iodine_set_params: null pointer for " + h->params[i].name);
     return IODINE_OK;
 }
 
-// scratch for (rows x Lp) tensors of a call; rows_eps = (T + 1) * N for the noise, N for the others
-// (the new set is allocated in full before the old one is released: a failed hipMalloc leaves the old set and `cap` as they were)
-int shim_scratch(iodine_handle* h, size_t floats)
+int reconstruct_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* const* state_in, float* const* traj)
 {
-    PadShim* sh = h->shim;
-    if (floats <= sh->cap) return IODINE_OK;
-    constexpr int NB = 8;
-    float** bufs[NB] = {&sh->eps, &sh->z, &sh->pm, &sh->plv, &sh->pm_in, &sh->plv_in, &sh->hs, &sh->cs};
-    void* fresh[NB] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i <= NB; ++i) {
-        // (i == NB: the old buffers may still be read by queued work)
-        const hipError_t e = i < NB ? hipMalloc(&fresh[i], floats * sizeof(float)) : (sh->cap > 0 ? hipDeviceSynchronize() : hipSuccess);
-        if (e != hipSuccess) {
-            for (int j = 0; j < i && j < NB; ++j) (void)hipFree(fresh[j]);
-            return h->fail(IODINE_ERR_HIP, std::string(i < NB ? "hipMalloc" : "hipDeviceSynchronize") + " (padded-handle scratch): " +
-                                               hipGetErrorString(e));
-        }
+    if (state_in && !(state_in[0] && state_in[1] && state_in[2] && state_in[3]))
+        return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: an initial state needs all four tensors - post_mean, post_logvar (B,K,L) and "
+                                           "the LSTM state h, c (B,K,MLP_UNITS)");
+    if (traj && !(traj[0] && traj[1] && traj[2] && traj[3] && traj[4]))
+        return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: a trajectory needs all five buffers - pred, mask, mean (T+1,B,..) and kl, ll (T,B)");
+    if (h->frames > 0 && h->frames != h->T) {
+        char m[256];
+        snprintf(m, sizeof m, "iodine_reconstruct: the frames setting is %d, but a call of %d iterations makes %d ELBO evaluations: it takes "
+                              "x of shape (B, %d, 3, %d, %d), one frame per evaluation (or frames 0: one image (B, 3, %d, %d))",
+                 h->frames, h->T, h->T, h->T, h->S, h->S, h->S, h->S);
+        return h->fail(IODINE_ERR_INVALID, m);
     }
-    for (int i = 0; i < NB; ++i) {
-        if (*bufs[i]) (void)hipFree(*bufs[i]);
-        *bufs[i] = (float*)fresh[i];
-    }
-    sh->cap = floats;
+    if (traj && h->stop_after >= 0 && h->stop_after <= h->T)
+        return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: a trajectory has T + 1 entries, the last one the final decode - not "
+                                           "available with option stop_after_iters (which skips it)");
+    if (int rc = check_ready(h, batch)) return rc;
+    if (!x || !eps) return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct: x and eps are required");
     return IODINE_OK;
 }
 
-}  // namespace
+int decode_check(iodine_handle* h, int batch, const float* z)
+{
+    if (int rc = check_ready(h, batch)) return rc;
+    if (!z) return h->fail(IODINE_ERR_INVALID, "iodine_decode: z is required");
+    return IODINE_OK;
+}
+
+int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* post_mean, const float* post_logvar)
+{
+    if (int rc = check_ready(h, batch)) return rc;
+    if (!x || !eps) return h->fail(IODINE_ERR_INVALID, "iodine_elbo: x and eps are required");
+    if ((post_mean == nullptr) != (post_logvar == nullptr))
+        return h->fail(IODINE_ERR_INVALID, "iodine_elbo: pass both post_mean and post_logvar, or neither");
+    return IODINE_OK;
+}
+
+int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss)
+{
+    char m[256];
+    if (h->frames > 0 && h->frames != h->T + 1) {
+        snprintf(m, sizeof m, "iodine_train_forward: the frames setting is %d, but a forward of %d iterations makes %d ELBO evaluations: it takes "
+                              "x of shape (B, %d, 3, %d, %d), one frame per evaluation (or frames 0: one image (B, 3, %d, %d))",
+                 h->frames, h->T, h->T + 1, h->T + 1, h->S, h->S, h->S, h->S);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    if (h->obj.nw != 0 && h->obj.nw != h->T + 1) {
+        snprintf(m, sizeof m, "iodine_train_forward: the objective has %d iteration weights, but a forward of %d iterations makes %d ELBO "
+                              "evaluations: it takes %d weights (iodine_set_objective; 0 weights = the default (i + 1) / (T + 1))",
+                 h->obj.nw, h->T, h->T + 1, h->T + 1);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    if (int rc = check_ready(h, batch)) return rc;
+    if (!x || !eps || !loss) return h->fail(IODINE_ERR_INVALID, "iodine_train_forward: x, eps and loss are required");
+    // the backward pass runs the refinement conv stack over all T iterations as one batch of T * N slot-images
+    if ((size_t)batch * h->K * h->T * h->P * 20 >= ((size_t)1 << 31) || (size_t)batch * h->K * h->T * (size_t)ref_out_size(h, h->S) * ref_out_size(h, h->S) * h->Cr >= ((size_t)1 << 31))
+        return h->fail(IODINE_ERR_INVALID, "batch too large for one device in training: batch * slots * iters * pixels * 20 must stay below "
+                                           "2^31 (shard the images over ranks, iodine_amd.parallel)");
+    return IODINE_OK;
+}
+
+int train_backward_check(iodine_handle* h, float* const* param_grads, int n)
+{
+    if (!h->calls.fwd_done) return h->fail(IODINE_ERR_STATE, "iodine_train_backward: no iodine_train_forward to differentiate");
+    if (n != (int)h->params.size() || !param_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward: wrong parameter count");
+    if (h->buf.mode != 1 || h->buf.B != h->calls.fwd_batch || h->buf.K != h->K || h->buf.T != h->T)
+        return h->fail(IODINE_ERR_STATE, "iodine_train_backward: the training workspace of the forward pass was re-planned");
+    return IODINE_OK;
+}
+
+// the state a single-pass backward needs: a decode / elbo that ran with option save_for_backward and nothing since
+int diff_ready(iodine_handle* h, int kind, const char* who)
+{
+    if (!h->params_set) return h->fail(IODINE_ERR_STATE, std::string(who) + ": iodine_set_params has not been called");
+    if (h->calls.diff_kind != kind)
+        return h->fail(IODINE_ERR_STATE, std::string(who) + (kind == 1 ? ": no iodine_decode" : ": no iodine_elbo") +
+                                             " with option save_for_backward to differentiate (none has run, another compute call has re-used "
+                                             "the workspace since, or it was differentiated already)");
+    if (h->buf.mode != 2 || h->buf.B != h->calls.diff_batch || h->buf.K != h->K)
+        return h->fail(IODINE_ERR_STATE, std::string(who) + ": the workspace of the forward pass was re-planned");
+    return IODINE_OK;
+}
+
+int decode_backward_check(iodine_handle* h, int batch)
+{
+    if (int rc = diff_ready(h, 1, "iodine_decode_backward")) return rc;
+    if (batch != h->calls.diff_batch) return h->fail(IODINE_ERR_INVALID, "iodine_decode_backward: batch differs from the decode it differentiates");
+    return IODINE_OK;
+}
+
+// the iodine_last_* readers: is what they read still in the arena, and is count within the batch that left it
+static int last_check(iodine_handle* h, bool stale, const char* who, const char* why, int count)
+{
+    if (stale || h->buf.bytes == 0) return h->fail(IODINE_ERR_STATE, std::string(who) + why);
+    if (count < 1 || count > h->calls.last_elbo_batch) return h->fail(IODINE_ERR_INVALID, std::string(who) + ": count must be in 1..batch of the last call");
+    return IODINE_OK;
+}
+int last_elbo_outputs_check(iodine_handle* h, int count)
+{
+    return last_check(h, h->calls.last_elbo_iter < 0, "iodine_last_elbo_outputs", ": no elbo() has run on the current workspace", count);
+}
+int last_posterior_check(iodine_handle* h, int count)
+{
+    return last_check(h, h->calls.last_elbo_iter < 0, "iodine_last_posterior", ": no refinement has run on the current workspace", count);
+}
+int last_refine_state_check(iodine_handle* h, int count)
+{
+    return last_check(h, h->calls.state_iter < 0 || h->buf.mode != 0, "iodine_last_refine_state",
+                      ": no iodine_reconstruct has run on the current workspace, or another compute call has re-used it since", count);
+}
 
 extern "C" {
 
@@ -1158,26 +937,15 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
     h->cfg = *cfg;
     h->obj.sigma = cfg->sigma;
     if (cfg->dim_latent % 4 != 0 || cfg->ref_mlp_units % 4 != 0) {
-        // boundary handle of a zero-padded inner handle (PadShim above): owns the reference-shaped parameter table and the maps only
-        h->L = cfg->dim_latent; h->T = cfg->iters; h->K = cfg->slots; h->S = cfg->img_size; h->P = h->S * h->S; h->H = cfg->ref_mlp_units;
-        h->Cd = cfg->dec_conv_chan; h->Dd = cfg->dec_conv_layers; h->Cr = cfg->ref_conv_chan; h->Dr = cfg->ref_conv_layers;
-        h->kd = cfg->dec_kernel_size; h->kr = cfg->ref_kernel_size; h->rs = cfg->ref_stride;
+        // boundary handle of a zero-padded inner handle (iodine_pad.cpp): owns the reference-shaped parameter table and the maps only
         h->n_in = 0;
         for (unsigned bit = 0; bit < 12; ++bit) {
             static const int cnt[12] = {0, 0, 3, 3, 1, 1, 1, 3, 1, 1, 1, 2};      // channels per ENCODING entry, order of the IODINE_ENC_* bits
             if (cfg->encoding & (1u << bit)) h->n_in += cnt[bit];
         }
         build_param_table(h);
-        h->shim = new PadShim();
-        h->shim->L = cfg->dim_latent; h->shim->H = cfg->ref_mlp_units;
-        h->shim->Lp = (cfg->dim_latent + 3) / 4 * 4; h->shim->Hp = (cfg->ref_mlp_units + 3) / 4 * 4;
-        iodine_config pc = *cfg;
-        pc.dim_latent = h->shim->Lp; pc.ref_mlp_units = h->shim->Hp;
-        const int rc = iodine_create(&pc, &h->shim->inner);
-        if (rc) { iodine_destroy(h); return rc; }                           // (g_create_error holds the inner message)
-        h->shim->inner->Lreal = cfg->dim_latent;
-        const int rb = shim_build(h);
-        if (rb) { g_create_error = h->err; iodine_destroy(h); return rb; }
+        const int rc = pad_create(h);
+        if (rc) { iodine_destroy(h); return rc; }
         *out = h;
         return IODINE_OK;
     }
@@ -1308,13 +1076,7 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
 void iodine_destroy(iodine_handle* h)
 {
     if (!h) return;
-    if (h->shim) {
-        if (h->shim->inner) iodine_destroy(h->shim->inner);
-        for (void* p : h->shim->owned) (void)hipFree(p);
-        for (float* p : {h->shim->eps, h->shim->z, h->shim->pm, h->shim->plv, h->shim->pm_in, h->shim->plv_in, h->shim->hs, h->shim->cs}) if (p) (void)hipFree(p);
-        delete h->shim;
-        h->shim = nullptr;
-    }
+    if (h->shim) pad_destroy(h);
     for (void* p : h->owned) (void)hipFree(p);
     for (auto& t : h->wtabs) if (t.dev) (void)hipFree(t.dev);
     for (auto& c : h->prof) for (auto& e : c.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1338,15 +1100,9 @@ int iodine_param_info(const iodine_handle* h, int index, const char** name, int*
 int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, int n)
 {
     if (!h) return IODINE_ERR_INVALID;
-    if (n != (int)h->params.size() || !dev) return h->fail(IODINE_ERR_INVALID, "iodine_set_params: wrong parameter count");
-    for (int i = 0; i < n; ++i)
-        if (!dev[i]) return h->fail(IODINE_ERR_INVALID, "iodine_set_params: null pointer for " + h->params[i].name);
+    if (h->shim) return pad_set_params(h, stream, dev, n);
+    if (int rc = set_params_check(h, dev, n)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (h->shim) {                                             // reference shapes -> zero-padded copies -> the inner handle
-        PadShim* sh = h->shim;
-        for (int i = 0; i < n; ++i) HIPCHK(h, launch_pad_gather(st, dev[i], sh->pmap[i], sh->pparam[i], sh->pnumel[i]));
-        return shim_fail(h, iodine_set_params(sh->inner, stream, sh->pparam.data(), n));
-    }
     const ParamSlots& ps = h->slot;
     // plain copies (biases, raw weights of the head backward) are collected and issued as one launch
     MultiCopy mc;
@@ -1540,14 +1296,14 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
     HIPCHK(h, launch_multi_copy(st, mc));
     if (!pj.empty()) HIPCHK(h, launch_pack_batch(st, pj.data(), (int)pj.size()));      // (behind ref_split / enc_expand: stream order)
     h->params_set = true;
-    h->fwd_done = false; h->diff_kind = 0;
+    h->calls.saved_passes_gone();
     return IODINE_OK;
 }
 
 size_t iodine_workspace_bytes(const iodine_handle* h, int batch, int mode)
 {
     if (!h || batch < 1) return 0;
-    if (h->shim) return iodine_workspace_bytes(h->shim->inner, batch, mode);
+    if (h->shim) return pad_workspace_bytes(h, batch, mode);
     Arena q(nullptr); Buffers tmp; plan(h, batch, mode, q, tmp);
     return tmp.bytes;
 }
@@ -1555,29 +1311,23 @@ size_t iodine_workspace_bytes(const iodine_handle* h, int batch, int mode)
 int iodine_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes)
 {
     if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_set_workspace(h, dev_ptr, bytes);
     if (((uintptr_t)dev_ptr & 255) != 0) return h->fail(IODINE_ERR_INVALID, "workspace must be 256-byte aligned");
-    if (h->shim) return shim_fail(h, iodine_set_workspace(h->shim->inner, dev_ptr, bytes));
     h->ws_user = dev_ptr; h->ws_user_bytes = dev_ptr ? bytes : 0;
     h->buf = Buffers();
-    h->fwd_done = false; h->diff_kind = 0;
-    h->last_elbo_iter = -1;
-    h->state_iter = -1;
+    h->calls.arena_gone();
     return IODINE_OK;                    // graphs are keyed by the arena address (see ensure_workspace)
 }
 
 int iodine_set_run_shape(iodine_handle* h, int slots, int iters)
 {
     if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_set_run_shape(h, slots, iters);
     if (slots < 1 || slots > 16)
         return h->fail(IODINE_ERR_INVALID, "slots must be in 1..16 (the per-pixel kernels keep every slot of a pixel in registers: "
                                            "instantiated for K <= 16)");
     if (iters < 1) return h->fail(IODINE_ERR_INVALID, "iters must be >= 1");
-    if (h->shim) {
-        const int rc = iodine_set_run_shape(h->shim->inner, slots, iters);
-        if (rc) return shim_fail(h, rc);
-    } else if (slots != h->K || iters != h->T) {
-        h->fwd_done = false; h->diff_kind = 0;             // a pending training forward ran at the old shape: its backward is refused (IODINE_ERR_STATE)
-    }
+    if (slots != h->K || iters != h->T) h->calls.saved_passes_gone();   // a pending forward ran at the old shape: its backward is refused (IODINE_ERR_STATE)
     // the workspace is re-planned by the next compute call (ensure_workspace keys on the run shape); the state of the last call
     // stays readable at the shape it was produced with (buf.K / buf.T)
     h->K = slots; h->T = iters;
@@ -1587,13 +1337,9 @@ int iodine_set_run_shape(iodine_handle* h, int slots, int iters)
 int iodine_set_frames(iodine_handle* h, int frames)
 {
     if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_set_frames(h, frames);
     if (frames < 0) return h->fail(IODINE_ERR_INVALID, "frames must be >= 0 (0: one image per batch entry)");
-    if (h->shim) {
-        const int rc = iodine_set_frames(h->shim->inner, frames);
-        if (rc) return shim_fail(h, rc);
-    } else if (frames != h->frames) {
-        h->fwd_done = false; h->diff_kind = 0;             // the workspace is re-planned by the next compute call (ensure_workspace keys on it)
-    }
+    if (frames != h->frames) h->calls.saved_passes_gone();   // the workspace is re-planned by the next compute call (ensure_workspace keys on it)
     h->frames = frames;
     return IODINE_OK;
 }
@@ -1601,6 +1347,7 @@ int iodine_set_frames(iodine_handle* h, int frames)
 int iodine_set_objective(iodine_handle* h, double sigma, double beta, const double* iter_weights, int n_weights)
 {
     if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_set_objective(h, sigma, beta, iter_weights, n_weights);   // (the inner handle holds the objective)
     char m[256];
     if (!(sigma > 0) || !std::isfinite(sigma)) {
         snprintf(m, sizeof m, "iodine_set_objective: sigma must be a finite number > 0 (got %g)", sigma);
@@ -1623,11 +1370,6 @@ int iodine_set_objective(iodine_handle* h, double sigma, double beta, const doub
         any = any || w[i] > 0.f;
     }
     if (n_weights > 0 && !any) return h->fail(IODINE_ERR_INVALID, "iodine_set_objective: the iteration weights are all zero (in fp32): no loss");
-    if (h->shim) {
-        const int rc = iodine_set_objective(h->shim->inner, sigma, beta, iter_weights, n_weights);
-        if (rc) return shim_fail(h, rc);
-        return IODINE_OK;                                  // (the inner handle holds the objective; every entry point reads it there)
-    }
     Objective o;
     o.sigma = sigma; o.beta = beta;
     if (n_weights > 0) {
@@ -1643,7 +1385,7 @@ int iodine_set_objective(iodine_handle* h, double sigma, double beta, const doub
                 drop_graphs(h);
                 for (auto it = h->wtabs.begin(); it != h->wtabs.end();) {
                     const float* d = it->dev;
-                    if (d == h->obj.wtab || d == h->fwd_obj.wtab || d == h->diff_obj.wtab) { ++it; continue; }
+                    if (d == h->obj.wtab || d == h->calls.fwd_obj.wtab || d == h->calls.diff_obj.wtab) { ++it; continue; }
                     (void)hipFree(it->dev);
                     it = h->wtabs.erase(it);
                 }
@@ -1665,7 +1407,7 @@ int iodine_set_objective(iodine_handle* h, double sigma, double beta, const doub
 int iodine_set_option(iodine_handle* h, const char* key, double value)
 {
     if (!h || !key) return IODINE_ERR_INVALID;
-    if (h->shim) return shim_fail(h, iodine_set_option(h->shim->inner, key, value));
+    if (h->shim) return pad_set_option(h, key, value);
     if (!strcmp(key, "stop_after_iters")) { h->stop_after = (int)value; return IODINE_OK; }
     if (!strcmp(key, "profile")) { h->profile = (int)value; return IODINE_OK; }
     if (!strcmp(key, "graph")) { h->graph = value != 0; if (!h->graph) drop_graphs(h); return IODINE_OK; }
@@ -1687,7 +1429,7 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
     if (!strcmp(key, "refine_ws")) { h->refine_ws = value != 0; return IODINE_OK; }
     if (!strcmp(key, "dec_out_rows")) { h->dec_out_rows = value != 0; return IODINE_OK; }
     if (!strcmp(key, "wgrad_accum")) {
-        if (h->wgrad_accum != (value != 0)) { h->buf = Buffers(); h->fwd_done = false; h->diff_kind = 0; h->last_elbo_iter = -1; h->enc_valid = false; }   // the arena is re-planned
+        if (h->wgrad_accum != (value != 0)) { h->buf = Buffers(); h->calls.arena_gone(); }   // the arena is re-planned
         h->wgrad_accum = value != 0; return IODINE_OK;
     }
     if (!strcmp(key, "conv_variant")) {
@@ -1722,54 +1464,12 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
                            const float* const* state_in, float* const* traj)
 {
     if (!h) return IODINE_ERR_INVALID;
-    // refusals of the new arguments: on the host, before any launch (also of the padded boundary handle's resize launches)
-    if (state_in && !(state_in[0] && state_in[1] && state_in[2] && state_in[3]))
-        return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: an initial state needs all four tensors - post_mean, post_logvar (B,K,L) and "
-                                           "the LSTM state h, c (B,K,MLP_UNITS)");
-    if (traj && !(traj[0] && traj[1] && traj[2] && traj[3] && traj[4]))
-        return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: a trajectory needs all five buffers - pred, mask, mean (T+1,B,..) and kl, ll (T,B)");
-    {
-        const iodine_handle* const s = h->shim ? h->shim->inner : h;      // the handle that holds the settings
-        char m[256];
-        if (s->frames > 0 && s->frames != s->T) {
-            snprintf(m, sizeof m, "iodine_reconstruct: the frames setting is %d, but a call of %d iterations makes %d ELBO evaluations: it takes "
-                                  "x of shape (B, %d, 3, %d, %d), one frame per evaluation (or frames 0: one image (B, 3, %d, %d))",
-                     s->frames, s->T, s->T, s->T, s->S, s->S, s->S, s->S);
-            return h->fail(IODINE_ERR_INVALID, m);
-        }
-        if (traj && s->stop_after >= 0 && s->stop_after <= s->T)
-            return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: a trajectory has T + 1 entries, the last one the final decode - not "
-                                               "available with option stop_after_iters (which skips it)");
-    }
-    if (h->shim) {
-        PadShim* sh = h->shim;
-        if (batch < 1 || !x || !eps) return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct: batch >= 1, x and eps are required");
-        hipStream_t st = (hipStream_t)stream;
-        const long long N = (long long)batch * h->K, R = (long long)(h->T + 1) * N;
-        if (int r = shim_scratch(h, std::max((size_t)R * sh->Lp, state_in ? (size_t)N * sh->Hp : (size_t)0))) return r;
-        HIPCHK(h, launch_resize_rows(st, eps, sh->eps, R, sh->L, sh->Lp));
-        const float* pstate[4] = {sh->pm_in, sh->plv_in, sh->hs, sh->cs};
-        if (state_in) {                                        // lambda: L -> padded L, LSTM state: MLP_UNITS -> padded, zero columns
-            HIPCHK(h, launch_resize_rows(st, state_in[0], sh->pm_in, N, sh->L, sh->Lp));
-            HIPCHK(h, launch_resize_rows(st, state_in[1], sh->plv_in, N, sh->L, sh->Lp));
-            HIPCHK(h, launch_resize_rows(st, state_in[2], sh->hs, N, sh->H, sh->Hp));
-            HIPCHK(h, launch_resize_rows(st, state_in[3], sh->cs, N, sh->H, sh->Hp));
-        }
-        const int rc = iodine_reconstruct_seq(sh->inner, stream, batch, x, sh->eps, pred, mask, mean, z ? sh->z : nullptr, post_mean ? sh->pm : nullptr,
-                                              post_logvar ? sh->plv : nullptr, elbo_iter, state_in ? pstate : nullptr, traj);
-        if (rc) return shim_fail(h, rc);
-        if (z) HIPCHK(h, launch_resize_rows(st, sh->z, z, N, sh->Lp, sh->L));
-        if (post_mean) HIPCHK(h, launch_resize_rows(st, sh->pm, post_mean, N, sh->Lp, sh->L));
-        if (post_logvar) HIPCHK(h, launch_resize_rows(st, sh->plv, post_logvar, N, sh->Lp, sh->L));
-        return IODINE_OK;
-    }
-    int rc = check_ready(h, batch);
+    if (h->shim) return pad_reconstruct_seq(h, stream, batch, x, eps, pred, mask, mean, z, post_mean, post_logvar, elbo_iter, state_in, traj);
+    int rc = reconstruct_check(h, batch, x, eps, state_in, traj);
     if (rc) return rc;
-    if (!x || !eps) return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct: x and eps are required");
     rc = ensure_workspace(h, batch, 0);
     if (rc) return rc;
-    h->fwd_done = false; h->diff_kind = 0;                                   // the arena is re-used: a saved training forward is gone
-    h->state_iter = -1;
+    h->calls.compute_begins();                             // the arena is re-used: a saved training forward is gone
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K, T = h->T;
     const bool partial = h->stop_after >= 0 && h->stop_after <= T;     // debug: stop before the final sample/decode
@@ -1822,58 +1522,35 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
     for (int j = 0; j < 5; ++j) key.push_back((uintptr_t)(traj ? traj[j] : nullptr));
     rc = run_graphed(h, st, key, body);
     if (rc) return rc;
-    h->last_elbo_iter = n_it > 0 ? n_it - 1 : -1;
-    h->last_elbo_batch = B;
-    h->state_iter = n_it;                                  // buf.h / buf.c [n_it]: the LSTM state after the last update (iodine_last_refine_state)
+    h->calls.last_elbo_iter = n_it > 0 ? n_it - 1 : -1;
+    h->calls.last_elbo_batch = B;
+    h->calls.state_iter = n_it;                                  // buf.h / buf.c [n_it]: the LSTM state after the last update (iodine_last_refine_state)
     // (host state, outside the graphed body) did this call leave the encoding in the workspace?  refine_step: l0f && !keep_enc skips it
-    h->enc_valid = n_it > 0 && (h->stop_after >= 0 || !(refine_split_on(h) && h->precision == 1 && h->refine_l0_fused && refine_l0_fused_ok(h->S, h->Cr, h->K)));
+    h->calls.enc_valid = n_it > 0 && (h->stop_after >= 0 || !(refine_split_on(h) && h->precision == 1 && h->refine_l0_fused && refine_l0_fused_ok(h->S, h->Cr, h->K)));
     return IODINE_OK;
 }
 
 int iodine_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c)
 {
     if (!h) return IODINE_ERR_INVALID;
-    iodine_handle* const s = h->shim ? h->shim->inner : h;         // the handle that holds the state
-    if (s->state_iter < 0 || s->buf.bytes == 0 || s->buf.mode != 0)
-        return h->fail(IODINE_ERR_STATE, "iodine_last_refine_state: no iodine_reconstruct has run on the current workspace, or another compute "
-                                         "call has re-used it since");
-    if (count < 1 || count > s->last_elbo_batch)
-        return h->fail(IODINE_ERR_INVALID, "iodine_last_refine_state: count must be in 1..batch of the last call");
-    const int K = s->buf.K;                                         // the slots of the call that produced the state, not the run shape
+    if (h->shim) return pad_last_refine_state(h, stream, count, lstm_h, lstm_c);
+    if (int rc = last_refine_state_check(h, count)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (h->shim) {
-        PadShim* sh = h->shim;
-        const long long N = (long long)count * K;
-        if (int r = shim_scratch(h, (size_t)N * sh->Hp)) return r;
-        const int rc = iodine_last_refine_state(sh->inner, stream, count, lstm_h ? sh->hs : nullptr, lstm_c ? sh->cs : nullptr);
-        if (rc) return shim_fail(h, rc);
-        if (lstm_h) HIPCHK(h, launch_resize_rows(st, sh->hs, lstm_h, N, sh->Hp, sh->H));
-        if (lstm_c) HIPCHK(h, launch_resize_rows(st, sh->cs, lstm_c, N, sh->Hp, sh->H));
-        return IODINE_OK;
-    }
-    const size_t n = sizeof(float) * (size_t)count * K * h->H;
-    if (lstm_h) HIPCHK(h, hipMemcpyAsync(lstm_h, h->buf.h[h->state_iter], n, hipMemcpyDeviceToDevice, st));
-    if (lstm_c) HIPCHK(h, hipMemcpyAsync(lstm_c, h->buf.c[h->state_iter], n, hipMemcpyDeviceToDevice, st));
+    const size_t n = sizeof(float) * (size_t)count * h->buf.K * h->H;   // the slots of the call that produced the state, not the run shape
+    if (lstm_h) HIPCHK(h, hipMemcpyAsync(lstm_h, h->buf.h[h->calls.state_iter], n, hipMemcpyDeviceToDevice, st));
+    if (lstm_c) HIPCHK(h, hipMemcpyAsync(lstm_c, h->buf.c[h->calls.state_iter], n, hipMemcpyDeviceToDevice, st));
     return IODINE_OK;
 }
 
 int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, float* pred, float* mask, float* mean)
 {
-    if (h && h->shim) {
-        PadShim* sh = h->shim;
-        if (batch < 1 || !z) return h->fail(IODINE_ERR_INVALID, "iodine_decode: batch >= 1 and z are required");
-        const long long N = (long long)batch * h->K;
-        if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
-        HIPCHK(h, launch_resize_rows((hipStream_t)stream, z, sh->z, N, sh->L, sh->Lp));
-        return shim_fail(h, iodine_decode(sh->inner, stream, batch, sh->z, pred, mask, mean));
-    }
-    int rc = check_ready(h, batch);
+    if (h && h->shim) return pad_decode(h, stream, batch, z, pred, mask, mean);
+    int rc = decode_check(h, batch, z);
     if (rc) return rc;
-    if (!z) return h->fail(IODINE_ERR_INVALID, "iodine_decode: z is required");
     const bool save = h->save_bwd != 0;                    // option save_for_backward: keep what iodine_decode_backward reads (workspace mode 2)
     rc = ensure_workspace(h, batch, save ? 2 : 0);
     if (rc) return rc;
-    h->fwd_done = false; h->diff_kind = 0;
+    h->calls.compute_begins(true);                         // (a decode touches neither buf.h / buf.c nor the posterior)
     hipStream_t st = (hipStream_t)stream;
     const int N = batch * h->K;
     auto body = [&]() -> int {
@@ -1888,41 +1565,23 @@ int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, flo
         HIPCHK(h, launch_final_out(st, out, pred, mask, mean, nullptr, batch, h->K, h->P));
         return IODINE_OK;
     };
-    if (save) h->last_elbo_iter = -1;                      // buf.dec_out no longer belongs to an elbo() call
+    if (save) h->calls.last_elbo_iter = -1;                      // buf.dec_out no longer belongs to an elbo() call
     rc = run_graphed(h, st, graph_key(h, save ? GK_DECODE_SAVED : GK_DECODE, batch, {z, pred, mask, mean}), body);
     if (rc) return rc;
-    if (save) { h->diff_kind = 1; h->diff_batch = batch; }
+    if (save) { h->calls.diff_kind = 1; h->calls.diff_batch = batch; }
     return IODINE_OK;
 }
 
 int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const float* post_mean, const float* post_logvar,
                 const float* eps, float* terms)
 {
-    if (h && h->shim) {
-        PadShim* sh = h->shim;
-        if (batch < 1 || !x || !eps) return h->fail(IODINE_ERR_INVALID, "iodine_elbo: batch >= 1, x and eps are required");
-        if ((post_mean == nullptr) != (post_logvar == nullptr))
-            return h->fail(IODINE_ERR_INVALID, "iodine_elbo: pass both post_mean and post_logvar, or neither");
-        hipStream_t st = (hipStream_t)stream;
-        const long long N = (long long)batch * h->K;
-        if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
-        HIPCHK(h, launch_resize_rows(st, eps, sh->eps, N, sh->L, sh->Lp));
-        if (post_mean) {
-            HIPCHK(h, launch_resize_rows(st, post_mean, sh->pm_in, N, sh->L, sh->Lp));
-            HIPCHK(h, launch_resize_rows(st, post_logvar, sh->plv_in, N, sh->L, sh->Lp));
-        }
-        return shim_fail(h, iodine_elbo(sh->inner, stream, batch, x, post_mean ? sh->pm_in : nullptr, post_mean ? sh->plv_in : nullptr, sh->eps, terms));
-    }
-    int rc = check_ready(h, batch);
+    if (h && h->shim) return pad_elbo(h, stream, batch, x, post_mean, post_logvar, eps, terms);
+    int rc = elbo_check(h, batch, x, eps, post_mean, post_logvar);
     if (rc) return rc;
-    if (!x || !eps) return h->fail(IODINE_ERR_INVALID, "iodine_elbo: x and eps are required");
-    if ((post_mean == nullptr) != (post_logvar == nullptr))
-        return h->fail(IODINE_ERR_INVALID, "iodine_elbo: pass both post_mean and post_logvar, or neither");
     const bool save = h->save_bwd != 0;                    // option save_for_backward: keep what iodine_elbo_backward reads (workspace mode 2)
     rc = ensure_workspace(h, batch, save ? 2 : 0);
     if (rc) return rc;
-    h->fwd_done = false; h->diff_kind = 0;
-    h->state_iter = -1;                                    // (the initial posterior below zeroes buf.h[0] / c[0])
+    h->calls.compute_begins();                             // (the initial posterior below zeroes buf.h[0] / c[0])
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K;
     auto body = [&]() -> int {
@@ -1944,26 +1603,14 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     };
     rc = run_graphed(h, st, graph_key(h, save ? GK_ELBO_SAVED : GK_ELBO, B, {x, post_mean, post_logvar, eps, terms}), body);
     if (rc) return rc;
-    h->last_elbo_iter = 0;
-    h->last_elbo_batch = B;
-    if (save) { h->diff_kind = 2; h->diff_batch = B; h->diff_init = post_mean == nullptr; h->diff_obj = h->obj; }
+    CallState& cs = h->calls;
+    cs.last_elbo_iter = 0;
+    cs.last_elbo_batch = B;
+    if (save) { cs.diff_kind = 2; cs.diff_batch = B; cs.diff_init = post_mean == nullptr; cs.diff_obj = h->obj; }
     return IODINE_OK;
 }
 
 namespace {
-
-// the state a single-pass backward needs: a decode / elbo that ran with option save_for_backward and nothing since
-int diff_ready(iodine_handle* h, int kind, const char* who)
-{
-    if (!h->params_set) return h->fail(IODINE_ERR_STATE, std::string(who) + ": iodine_set_params has not been called");
-    if (h->diff_kind != kind)
-        return h->fail(IODINE_ERR_STATE, std::string(who) + (kind == 1 ? ": no iodine_decode" : ": no iodine_elbo") +
-                                             " with option save_for_backward to differentiate (none has run, another compute call has re-used "
-                                             "the workspace since, or it was differentiated already)");
-    if (h->buf.mode != 2 || h->buf.B != h->diff_batch || h->buf.K != h->K)
-        return h->fail(IODINE_ERR_STATE, std::string(who) + ": the workspace of the forward pass was re-planned");
-    return IODINE_OK;
-}
 
 // caller's flat gradient buffer <- the accumulators.  Only the decoder and the initial posterior (the tail of the parameter table) can
 // have received anything: when accumulating, the refinement network's gradients are not touched at all; otherwise they are written as 0
@@ -1974,37 +1621,16 @@ int diff_flat_out(iodine_handle* h, hipStream_t st, const float* scale_dev, floa
     return IODINE_OK;
 }
 
-// the same for the boundary of a padded inner handle: padded flat gradient -> the caller's reference-shaped one
-int shim_flat_out(iodine_handle* h, hipStream_t st, float* flat, int accumulate)
-{
-    PadShim* sh = h->shim;
-    size_t off = 0;
-    for (size_t p = 0; p < h->params.size(); ++p) {
-        if (!accumulate || (int)p >= h->slot.dec_w[0])
-            HIPCHK(h, launch_pad_scatter(st, sh->pgrad + sh->poff[p], sh->pmap[p], flat + off, sh->pnumel[p], accumulate));
-        off += h->params[p].numel();
-    }
-    return IODINE_OK;
-}
-
 }  // namespace
 
 int iodine_decode_backward(iodine_handle* h, void* stream, int batch, const float* g_pred, const float* g_mask, const float* g_mean,
                            float* dz, float* flat_grads, int accumulate)
 {
     if (!h) return IODINE_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    if (h->shim) {
-        PadShim* sh = h->shim;
-        const int rc = iodine_decode_backward(sh->inner, stream, batch, g_pred, g_mask, g_mean, dz ? sh->z : nullptr,
-                                              flat_grads ? sh->pgrad : nullptr, 0);
-        if (rc) return shim_fail(h, rc);
-        if (dz) HIPCHK(h, launch_resize_rows(st, sh->z, dz, (long long)batch * h->K, sh->Lp, sh->L));
-        return flat_grads ? shim_flat_out(h, st, flat_grads, accumulate) : IODINE_OK;
-    }
-    int rc = diff_ready(h, 1, "iodine_decode_backward");
+    if (h->shim) return pad_decode_backward(h, stream, batch, g_pred, g_mask, g_mean, dz, flat_grads, accumulate);
+    int rc = decode_backward_check(h, batch);
     if (rc) return rc;
-    if (batch != h->diff_batch) return h->fail(IODINE_ERR_INVALID, "iodine_decode_backward: batch differs from the decode it differentiates");
+    hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K;
     std::vector<uintptr_t> key = graph_key(h, GK_DECODE_BWD, B, {g_pred, g_mask, g_mean, dz, flat_grads});
     key.push_back((uintptr_t)accumulate);
@@ -2022,7 +1648,7 @@ int iodine_decode_backward(iodine_handle* h, void* stream, int batch, const floa
         return flat_grads ? diff_flat_out(h, st, nullptr, flat_grads, accumulate) : IODINE_OK;
     };
     rc = run_graphed(h, st, key, body);
-    h->diff_kind = 0;                                      // consumed, like autograd without retain_graph (buf.g and the accumulators were overwritten)
+    h->calls.saved_passes_gone();                          // consumed, like autograd without retain_graph (buf.g and the accumulators were overwritten)
     return rc;
 }
 
@@ -2030,25 +1656,15 @@ int iodine_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_d
                          float* flat_grads, int accumulate)
 {
     if (!h) return IODINE_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    if (h->shim) {
-        PadShim* sh = h->shim;
-        iodine_handle* in = sh->inner;
-        const long long N = (long long)in->diff_batch * in->buf.K;       // (checked by the inner call before anything is written)
-        const int rc = iodine_elbo_backward(in, stream, grad_out_dev, g_post_mean ? sh->pm : nullptr, g_post_logvar ? sh->plv : nullptr,
-                                            flat_grads ? sh->pgrad : nullptr, 0);
-        if (rc) return shim_fail(h, rc);
-        if (g_post_mean) HIPCHK(h, launch_resize_rows(st, sh->pm, g_post_mean, N, sh->Lp, sh->L));
-        if (g_post_logvar) HIPCHK(h, launch_resize_rows(st, sh->plv, g_post_logvar, N, sh->Lp, sh->L));
-        return flat_grads ? shim_flat_out(h, st, flat_grads, accumulate) : IODINE_OK;
-    }
+    if (h->shim) return pad_elbo_backward(h, stream, grad_out_dev, g_post_mean, g_post_logvar, flat_grads, accumulate);
     int rc = diff_ready(h, 2, "iodine_elbo_backward");
     if (rc) return rc;
-    const int B = h->diff_batch, N = B * h->K;
-    const Objective obj = h->diff_obj;                     // the objective the saved elbo ran with (beta: the KL part of the posterior gradients)
+    hipStream_t st = (hipStream_t)stream;
+    const int B = h->calls.diff_batch, N = B * h->K;
+    const Objective obj = h->calls.diff_obj;                     // the objective the saved elbo ran with (beta: the KL part of the posterior gradients)
     std::vector<uintptr_t> key = graph_key(h, GK_ELBO_BWD, B, {grad_out_dev, g_post_mean, g_post_logvar, flat_grads}, &obj);
     key.push_back((uintptr_t)accumulate);
-    key.push_back((uintptr_t)h->diff_init);
+    key.push_back((uintptr_t)h->calls.diff_init);
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const ParamSlots& ps = h->slot;
@@ -2060,7 +1676,7 @@ int iodine_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_d
         // d ELBO / d lambda (iodine.py:193,220: batch means) into the slots the refinement loop uses for them
         HIPCHK(h, launch_dz_plain(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, h->L, h->Cd, nullptr, b.pm, b.plv, b.latent[0],
                                   1.f / (float)B, b.g_pm[0], b.g_plv[0], (float)obj.beta));
-        if (flat_grads && h->diff_init) {                  // lambda = init_mean / init_logvar repeated over (B, K): iodine.py:615-616
+        if (flat_grads && h->calls.diff_init) {                  // lambda = init_mean / init_logvar repeated over (B, K): iodine.py:615-616
             HIPCHK(h, launch_colsum(st, b.g_pm[0], N, h->L, h->L, 1.f, h->gacc[ps.init_mean]));
             HIPCHK(h, launch_colsum(st, b.g_plv[0], N, h->L, h->L, 1.f, h->gacc[ps.init_logvar]));
         }
@@ -2069,7 +1685,7 @@ int iodine_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_d
         return flat_grads ? diff_flat_out(h, st, grad_out_dev, flat_grads, accumulate) : IODINE_OK;
     };
     rc = run_graphed(h, st, key, body);
-    h->diff_kind = 0;
+    h->calls.saved_passes_gone();
     return rc;
 }
 
@@ -2077,27 +1693,15 @@ int iodine_last_elbo_outputs(iodine_handle* h, void* stream, int count, float* z
                              float* mask_logits, float* pred)
 {
     if (!h) return IODINE_ERR_INVALID;
-    iodine_handle* const s = h->shim ? h->shim->inner : h;         // the handle that holds the state
-    if (s->last_elbo_iter < 0 || s->buf.bytes == 0)
-        return h->fail(IODINE_ERR_STATE, "iodine_last_elbo_outputs: no elbo() has run on the current workspace");
-    if (count < 1 || count > s->last_elbo_batch)
-        return h->fail(IODINE_ERR_INVALID, "iodine_last_elbo_outputs: count must be in 1..batch of the last call");
-    const int K = s->buf.K;                                         // the slots of the call that produced the state, not the run shape
-    if (h->shim) {
-        PadShim* sh = h->shim;
-        const long long N = (long long)count * K;
-        if (z) if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
-        const int rc = iodine_last_elbo_outputs(sh->inner, stream, count, z ? sh->z : nullptr, mean, mask, mask_logits, pred);
-        if (rc) return shim_fail(h, rc);
-        if (z) HIPCHK(h, launch_resize_rows((hipStream_t)stream, sh->z, z, N, sh->Lp, sh->L));
-        return IODINE_OK;
-    }
+    if (h->shim) return pad_last_elbo_outputs(h, stream, count, z, mean, mask, mask_logits, pred);
+    if (int rc = last_elbo_outputs_check(h, count)) return rc;
+    const int K = h->buf.K;                                         // the slots of the call that produced the state, not the run shape
     hipStream_t st = (hipStream_t)stream;
     Buffers& b = h->buf;
     if (mean || mask || mask_logits || pred)
         HIPCHK(h, launch_final_out(st, b.dec_out, pred, mask, mean, mask_logits, count, K, h->P));
     if (z)
-        HIPCHK(h, hipMemcpyAsync(z, b.z[h->last_elbo_iter], sizeof(float) * (size_t)count * K * h->L,
+        HIPCHK(h, hipMemcpyAsync(z, b.z[h->calls.last_elbo_iter], sizeof(float) * (size_t)count * K * h->L,
                                  hipMemcpyDeviceToDevice, st));
     return IODINE_OK;
 }
@@ -2105,22 +1709,9 @@ int iodine_last_elbo_outputs(iodine_handle* h, void* stream, int count, float* z
 int iodine_last_posterior(iodine_handle* h, void* stream, int count, float* post_mean, float* post_logvar)
 {
     if (!h) return IODINE_ERR_INVALID;
-    iodine_handle* const s = h->shim ? h->shim->inner : h;         // the handle that holds the state
-    if (s->last_elbo_iter < 0 || s->buf.bytes == 0)
-        return h->fail(IODINE_ERR_STATE, "iodine_last_posterior: no refinement has run on the current workspace");
-    if (count < 1 || count > s->last_elbo_batch)
-        return h->fail(IODINE_ERR_INVALID, "iodine_last_posterior: count must be in 1..batch of the last call");
-    const int K = s->buf.K;                                         // the slots of the call that produced the state, not the run shape
-    if (h->shim) {
-        PadShim* sh = h->shim;
-        const long long N = (long long)count * K;
-        if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
-        const int rc = iodine_last_posterior(sh->inner, stream, count, post_mean ? sh->pm : nullptr, post_logvar ? sh->plv : nullptr);
-        if (rc) return shim_fail(h, rc);
-        if (post_mean) HIPCHK(h, launch_resize_rows((hipStream_t)stream, sh->pm, post_mean, N, sh->Lp, sh->L));
-        if (post_logvar) HIPCHK(h, launch_resize_rows((hipStream_t)stream, sh->plv, post_logvar, N, sh->Lp, sh->L));
-        return IODINE_OK;
-    }
+    if (h->shim) return pad_last_posterior(h, stream, count, post_mean, post_logvar);
+    if (int rc = last_posterior_check(h, count)) return rc;
+    const int K = h->buf.K;                                         // the slots of the call that produced the state, not the run shape
     hipStream_t st = (hipStream_t)stream;
     const size_t n = sizeof(float) * (size_t)count * K * h->L;
     if (post_mean) HIPCHK(h, hipMemcpyAsync(post_mean, h->buf.pm, n, hipMemcpyDeviceToDevice, st));
@@ -2132,42 +1723,14 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
                          float* elbo_iter)
 {
     if (!h) return IODINE_ERR_INVALID;
-    const iodine_handle* const s = h->shim ? h->shim->inner : h;          // the handle that holds the settings
-    if (s->frames > 0 && s->frames != s->T + 1) {
-        char m[256];
-        snprintf(m, sizeof m, "iodine_train_forward: the frames setting is %d, but a forward of %d iterations makes %d ELBO evaluations: it takes "
-                              "x of shape (B, %d, 3, %d, %d), one frame per evaluation (or frames 0: one image (B, 3, %d, %d))",
-                 s->frames, s->T, s->T + 1, s->T + 1, s->S, s->S, s->S, s->S);
-        return h->fail(IODINE_ERR_INVALID, m);
-    }
-    if (s->obj.nw != 0 && s->obj.nw != s->T + 1) {
-        char m[256];
-        snprintf(m, sizeof m, "iodine_train_forward: the objective has %d iteration weights, but a forward of %d iterations makes %d ELBO "
-                              "evaluations: it takes %d weights (iodine_set_objective; 0 weights = the default (i + 1) / (T + 1))",
-                 s->obj.nw, s->T, s->T + 1, s->T + 1);
-        return h->fail(IODINE_ERR_INVALID, m);
-    }
-    if (h->shim) {
-        PadShim* sh = h->shim;
-        if (batch < 1 || !x || !eps || !loss) return h->fail(IODINE_ERR_INVALID, "iodine_train_forward: batch >= 1, x, eps and loss are required");
-        const long long R = (long long)(h->T + 1) * batch * h->K;
-        if (int r = shim_scratch(h, (size_t)R * sh->Lp)) return r;
-        HIPCHK(h, launch_resize_rows((hipStream_t)stream, eps, sh->eps, R, sh->L, sh->Lp));
-        return shim_fail(h, iodine_train_forward(sh->inner, stream, batch, x, sh->eps, loss, elbo_iter));
-    }
-    int rc = check_ready(h, batch);
+    if (h->shim) return pad_train_forward(h, stream, batch, x, eps, loss, elbo_iter);
+    int rc = train_forward_check(h, batch, x, eps, loss);
     if (rc) return rc;
-    if (!x || !eps || !loss) return h->fail(IODINE_ERR_INVALID, "iodine_train_forward: x, eps and loss are required");
-    // the backward pass runs the refinement conv stack over all T iterations as one batch of T * N slot-images
-    if ((size_t)batch * h->K * h->T * h->P * 20 >= ((size_t)1 << 31) || (size_t)batch * h->K * h->T * (size_t)ref_out_size(h, h->S) * ref_out_size(h, h->S) * h->Cr >= ((size_t)1 << 31))
-        return h->fail(IODINE_ERR_INVALID, "batch too large for one device in training: batch * slots * iters * pixels * 20 must stay below "
-                                           "2^31 (shard the images over ranks, iodine_amd.parallel)");
     rc = ensure_workspace(h, batch, 1);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K, T = h->T, L = h->L;
-    h->fwd_done = false; h->diff_kind = 0;
-    h->state_iter = -1;
+    h->calls.compute_begins();
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const size_t eps_stride = (size_t)N * L;
@@ -2196,69 +1759,45 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
     };
     rc = run_graphed(h, st, graph_key(h, 4, B, {x, eps, loss, elbo_iter}), body);
     if (rc) return rc;
-    h->fwd_done = true;
-    h->fwd_obj = h->obj;                                   // the backward differentiates the forward as it ran (a replay ran the same objective: graph key)
-    h->enc_valid = true;                                   // training keeps the encoding of every iteration (the backward reads it)
-    h->fwd_batch = B;
-    h->fwd_split = refine_split_on(h);     // layout of the saved refinement inputs (refine_split is part of the graph key)
-    h->last_elbo_iter = T;
-    h->last_elbo_batch = B;
+    CallState& cs = h->calls;
+    cs.fwd_done = true;
+    cs.fwd_obj = h->obj;                                   // the backward differentiates the forward as it ran (a replay ran the same objective: graph key)
+    cs.enc_valid = true;                                   // training keeps the encoding of every iteration (the backward reads it)
+    cs.fwd_batch = B;
+    cs.fwd_split = refine_split_on(h);     // layout of the saved refinement inputs (refine_split is part of the graph key)
+    cs.last_elbo_iter = T;
+    cs.last_elbo_batch = B;
     return IODINE_OK;
 }
 
+}  // extern "C"
+
 // aux != NULL: the backward with auxiliary cotangents (iodine_train_backward_aux) - grad_scale / grad_scale_dev are then not used, aux->gl
 // takes their place; aux == NULL: the plain backward, every launch as before
-static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev,
-                               float* const* param_grads, int n, int accumulate, const AuxCot* aux = nullptr)
+int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev, float* const* param_grads, int n,
+                        int accumulate, const AuxCot* aux)
 {
     if (!h) return IODINE_ERR_INVALID;
-    if (h->shim) {
-        // the inner handle writes its (scaled) gradient in padded shapes; the real entries are scattered (or added) into the caller's tensors
-        PadShim* sh = h->shim;
-        if (n != (int)h->params.size() || !param_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward: wrong parameter count");
-        std::vector<float*> ptrs(h->params.size());
-        for (size_t p = 0; p < ptrs.size(); ++p) ptrs[p] = sh->pgrad + sh->poff[p];
-        AuxCot pa;
-        if (aux) {
-            // cotangents with a latent axis: rows widened to the padded width (zeros in the padded entries), like iodine_decode_backward's dz
-            const iodine_handle* in = sh->inner;
-            if (!in->fwd_done) return h->fail(IODINE_ERR_STATE, "iodine_train_backward: no iodine_train_forward to differentiate");
-            const long long N = (long long)in->fwd_batch * in->buf.K;
-            if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
-            pa = *aux;
-            hipStream_t st = (hipStream_t)stream;
-            if (aux->z) { HIPCHK(h, launch_resize_rows(st, aux->z, sh->z, N, sh->L, sh->Lp)); pa.z = sh->z; }
-            if (aux->pm) { HIPCHK(h, launch_resize_rows(st, aux->pm, sh->pm_in, N, sh->L, sh->Lp)); pa.pm = sh->pm_in; }
-            if (aux->plv) { HIPCHK(h, launch_resize_rows(st, aux->plv, sh->plv_in, N, sh->L, sh->Lp)); pa.plv = sh->plv_in; }
-        }
-        const int rc = train_backward_impl(sh->inner, stream, grad_scale, grad_scale_dev, ptrs.data(), n, 0, aux ? &pa : nullptr);
-        if (rc) return shim_fail(h, rc);
-        for (size_t p = 0; p < ptrs.size(); ++p)
-            if (param_grads[p]) HIPCHK(h, launch_pad_scatter((hipStream_t)stream, ptrs[p], sh->pmap[p], param_grads[p], sh->pnumel[p], accumulate));
-        return IODINE_OK;
-    }
-    if (!h->fwd_done) return h->fail(IODINE_ERR_STATE, "iodine_train_backward: no iodine_train_forward to differentiate");
-    if (n != (int)h->params.size() || !param_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward: wrong parameter count");
-    if (h->buf.mode != 1 || h->buf.B != h->fwd_batch || h->buf.K != h->K || h->buf.T != h->T)
-        return h->fail(IODINE_ERR_STATE, "iodine_train_backward: the training workspace of the forward pass was re-planned");
+    if (h->shim) return pad_train_backward(h, stream, grad_scale, grad_scale_dev, param_grads, n, accumulate, aux);
+    if (int rc = train_backward_check(h, param_grads, n)) return rc;
     hipStream_t st = (hipStream_t)stream;
     std::vector<const void*> kp;
     for (int i = 0; i < n; ++i) kp.push_back(param_grads[i]);
-    const Objective obj = h->fwd_obj;                      // the objective of the saved forward, whatever the handle holds by now
-    std::vector<uintptr_t> key = graph_key(h, 5, h->fwd_batch, {}, &obj);
+    const Objective obj = h->calls.fwd_obj;                      // the objective of the saved forward, whatever the handle holds by now
+    std::vector<uintptr_t> key = graph_key(h, 5, h->calls.fwd_batch, {}, &obj);
     for (const void* q : kp) key.push_back((uintptr_t)q);
     uint32_t gs_bits; memcpy(&gs_bits, &grad_scale, 4);
     key.push_back(gs_bits);
     key.push_back((uintptr_t)grad_scale_dev);
     key.push_back((uintptr_t)accumulate);
-    key.push_back((uintptr_t)h->fwd_split);                // the backward body reads the saved inputs in the forward's layout
+    key.push_back((uintptr_t)h->calls.fwd_split);                // the backward body reads the saved inputs in the forward's layout
     if (aux) {
         key.push_back(1);
         for (const void* q : {aux->gl, aux->mean, aux->mask, aux->logits, aux->z, aux->pm, aux->plv}) key.push_back((uintptr_t)q);
     }
     auto body = [&]() -> int {
     Buffers& b = h->buf;
-    const int B = h->fwd_batch, N = B * h->K, T = h->T, L = h->L, H = h->H, Cr = h->Cr, IN = H + 4 * L;
+    const int B = h->calls.fwd_batch, N = B * h->K, T = h->T, L = h->L, H = h->H, Cr = h->Cr, IN = H + 4 * L;
     const ParamSlots& ps = h->slot;
     float *seed_m = nullptr, *seed_v = nullptr;
     if (aux) {
@@ -2341,7 +1880,7 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
         HIPCHK(h, launch_pool_bwd(st, b.dpooled, b.ract[0][h->Dr - 1], b.rdpre[h->Dr - 1], NT, sl * sl, Cr));
         // round 4: the data gradient of layer 1 and the weight / bias gradient of layer 0 in ONE launch - d(pre-activation 0), the
         // largest tensor of this backward (T * N x 64 x 64 x 64 floats at cfg3), is produced and consumed on chip
-        const bool fuse01 = h->refine_bwd_fused && h->fwd_split && !h->gen_ref && h->precision == 1 && refine_f16_ok(h) && h->Dr >= 2 &&
+        const bool fuse01 = h->refine_bwd_fused && h->calls.fwd_split && !h->gen_ref && h->precision == 1 && refine_f16_ok(h) && h->Dr >= 2 &&
                             refine_bwd01_ok(h->S, Cr);
         for (int l = h->Dr - 1; l >= 0; --l) {
             const float* in = l == 0 ? b.enc[0] : b.ract[0][l - 1];
@@ -2356,7 +1895,7 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
             if (h->gen_ref) {
                 PROF(h, st, "gen_conv", launch_gen_conv_wgrad(st, in, b.rdpre[l], b.gen_scr, NT, sz[l], ireal, cip, ireal, Cr, h->kr, h->rs, 1.f,
                                                               gw_dst, gb, l == 0 ? h->enc_chmask : 0xffffffffu));
-            } else if (l == 0 && h->fwd_split) {
+            } else if (l == 0 && h->calls.fwd_split) {
                 // split first layer: 12 per-slot + 8 per-image channels from two tensors (fuse01: in the same launch as layer 1's data
                 // gradient), gradient in the internal channel order, then added to the reference layout
                 int nb = 0;
@@ -2414,9 +1953,11 @@ static int train_backward_impl(iodine_handle* h, void* stream, float grad_scale,
     const int rc = run_graphed(h, st, key, body);
     // like autograd without retain_graph: the saved forward is consumed (a second backward would add the BPTT terms to the
     // accumulators twice); iodine_train_forward must run again first
-    h->fwd_done = false; h->diff_kind = 0;
+    h->calls.saved_passes_gone();
     return rc;
 }
+
+extern "C" {
 
 int iodine_train_backward(iodine_handle* h, void* stream, float grad_scale, float* const* param_grads, int n)
 {
@@ -2452,7 +1993,7 @@ int iodine_train_backward_aux(iodine_handle* h, void* stream, const float* grad_
 int iodine_logger_scalars(iodine_handle* h, void* stream, float* out2)
 {
     if (!h || !out2) return IODINE_ERR_INVALID;
-    if (h->shim) return shim_fail(h, iodine_logger_scalars(h->shim->inner, stream, out2));
+    if (h->shim) return pad_logger_scalars(h, stream, out2);
     if (!h->params_set) return h->fail(IODINE_ERR_STATE, "iodine_set_params has not been called");
     HIPCHK(h, launch_mean2((hipStream_t)stream, h->init_mean, h->init_logvar, h->Lreal > 0 ? h->Lreal : h->L, out2));
     return IODINE_OK;
@@ -2462,7 +2003,7 @@ int iodine_debug_copy(iodine_handle* h, void* stream, const char* name, int iter
                       size_t* n_floats)
 {
     if (!h || !name) return IODINE_ERR_INVALID;
-    if (h->shim) return shim_fail(h, iodine_debug_copy(h->shim->inner, stream, name, iter, dst, max_floats, n_floats));   // (padded widths)
+    if (h->shim) return pad_debug_copy(h, stream, name, iter, dst, max_floats, n_floats);
     if (h->buf.bytes == 0) return h->fail(IODINE_ERR_STATE, "iodine_debug_copy: no workspace yet");
     Buffers& b = h->buf;
     const size_t N = (size_t)b.B * b.K, P = h->P, L = h->L;        // the shape of the call that left the buffers, not the run shape
@@ -2475,7 +2016,7 @@ int iodine_debug_copy(iodine_handle* h, void* stream, const char* name, int iter
     else if (s == "enc") {
         n = N * P * 20;
         // with refine_l0_fused the inference loop never writes the encoding (kernels_refl0.hip keeps it on chip) unless stop_after_iters asks
-        if (!h->enc_valid)
+        if (!h->calls.enc_valid)
             return h->fail(IODINE_ERR_STATE, "iodine_debug_copy: enc was not materialised by the last call (set stop_after_iters >= 0 or refine_l0_fused=0)");
         if (refine_split_on(h)) {                          // joined back into the reference's 17 (+3 pad) channel order
             if (n_floats) *n_floats = n;
@@ -2519,7 +2060,7 @@ int iodine_debug_copy(iodine_handle* h, void* stream, const char* name, int iter
 int iodine_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset)
 {
     if (!h || !category) return IODINE_ERR_INVALID;
-    if (h->shim) return shim_fail(h, iodine_profile_read(h->shim->inner, category, total_ms, launches, reset));
+    if (h->shim) return pad_profile_read(h, category, total_ms, launches, reset);
     double tot = 0.0; long long cnt = 0;
     if (!strcmp(category, "graph_captures") || !strcmp(category, "graph_replays")) {    // hipGraph bookkeeping (option "graph")
         if (total_ms) *total_ms = 0.0;
@@ -2546,376 +2087,6 @@ int iodine_profile_read(iodine_handle* h, const char* category, double* total_ms
     }
     if (total_ms) *total_ms = tot;
     if (launches) *launches = cnt;
-    return IODINE_OK;
-}
-
-int iodine_adam_step(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
-                     double lr, double beta1, double beta2, double eps, double weight_decay, int step)
-{
-    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || step < 1) { g_create_error = "iodine_adam_step: bad argument"; return IODINE_ERR_INVALID; }
-    const hipError_t e = launch_adam_multi((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, lr, beta1, beta2, eps,
-                                           weight_decay, step);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_adam_step: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-size_t iodine_grad_norm_scratch_bytes(long long total)
-{
-    return total < 1 ? 0 : grad_norm_scratch_bytes(total);
-}
-
-int iodine_grad_norm(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
-                     double max_norm, void* scratch_dev, size_t scratch_bytes, float* out4_dev)
-{
-    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || !scratch_dev || !out4_dev || !(max_norm > 0.0) ||
-        scratch_bytes < grad_norm_scratch_bytes(total) || ((uintptr_t)scratch_dev & 7)) {
-        g_create_error = "iodine_grad_norm: bad argument (max_norm must be > 0; scratch of iodine_grad_norm_scratch_bytes, 8-byte aligned)";
-        return IODINE_ERR_INVALID;
-    }
-    const hipError_t e = launch_grad_norm((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, max_norm,
-                                          (double*)scratch_dev, out4_dev);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_grad_norm: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_grad_scale(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
-                      const float* coef_dev)
-{
-    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || !coef_dev) { g_create_error = "iodine_grad_scale: bad argument"; return IODINE_ERR_INVALID; }
-    const hipError_t e = launch_grad_scale((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, coef_dev);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_grad_scale: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_adam_step_clipped(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
-                             double lr, double beta1, double beta2, double eps, double weight_decay, int step,
-                             const float* out4_dev, int skip_nonfinite)
-{
-    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || step < 1 || !out4_dev) { g_create_error = "iodine_adam_step_clipped: bad argument"; return IODINE_ERR_INVALID; }
-    const hipError_t e = launch_adam_multi((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, lr, beta1, beta2, eps,
-                                           weight_decay, step, out4_dev, skip_nonfinite ? 1 : 0);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_adam_step_clipped: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, int batch, int slots, int n_gt, int pixels,
-                     int* table)
-{
-    if (!mask || !gt || !table || batch < 1 || slots < 1 || n_gt < 1 || pixels < 1 || (size_t)n_gt * slots > 8192) {
-        g_create_error = "iodine_ari_table: bad argument";
-        return IODINE_ERR_INVALID;
-    }
-    const hipError_t e = launch_ari_table((hipStream_t)stream, mask, gt, batch, slots, n_gt, pixels, table);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_ari_table: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_randn(void* stream, float* out, long long n, unsigned long long seed, unsigned long long stream_id)
-{
-    if (!out || n < 1) { g_create_error = "iodine_randn: bad argument"; return IODINE_ERR_INVALID; }
-    const hipError_t e = launch_randn_philox((hipStream_t)stream, out, n, seed, stream_id);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_randn: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-void iodine_linspace_host(int n, float* out)
-{
-    // ATen's CPU linspace for float: step = (end - start) / (n - 1); first half counts up from start,
-    // second half counts down from end (symmetric), all in fp32.
-    const float start = -1.f, end = 1.f;
-    if (n == 1) { out[0] = start; return; }
-    const float step = (end - start) / (float)(n - 1);
-    const int halfway = n / 2;
-    for (int i = 0; i < n; ++i)
-        out[i] = i < halfway ? start + step * (float)i : end - step * (float)(n - i - 1);
-}
-
-// ---- operator-level test entry points ---------------------------------------------------------
-static std::string g_op_error;
-
-int iodine_op_conv3x3(void* stream, int mode, const float* in, const float* w, const float* bias, const float* aux,
-                      float* out, int n, int ih, int iw, int w_o, int w_i, int cin_pad, int cout, int stride, int epi,
-                      int tflip)
-{
-    hipStream_t st = (hipStream_t)stream;
-    float* wpk = nullptr;
-    if (mode == 5 || mode == 6 || mode == 13 || mode == 14) {   // stride-2 forward (5) / data gradient (6), split-fp16; 13 / 14: their exact-fp32 forms; ih = fine size
-        float* meta = nullptr;
-        const bool fwd = mode == 5 || mode == 13;
-        const int f32 = mode >= 13;
-        const int cp = fwd ? (cin_pad == 20 ? 32 : (cin_pad == 12 || cin_pad == 8 ? 16 : cin_pad)) : cin_pad;   // floats per pixel -> packed chunks
-        const size_t bytes = (size_t)(cp / 16) * 9 * 2 * 2 * cout * 16;
-        if (hipMalloc((void**)&wpk, bytes + 64) != hipSuccess) return IODINE_ERR_HIP;
-        meta = (float*)((char*)wpk + bytes);
-        hipError_t e2 = f32 ? launch_pack_conv_weights_s2f32(st, w, w_o, w_i, cp, cout, fwd ? 0 : 2, wpk)
-                            : launch_pack_conv_weights_f16(st, w, w_o, w_i, cp, cout, fwd ? 0 : 2, meta, wpk);
-        if (e2 == hipSuccess)
-            e2 = fwd ? launch_conv3x3_s2_f16x3(st, in, wpk, meta, bias, out, n, ih, cin_pad, cout, nullptr, 0, f32)
-                     : launch_conv3x3_s2_dgrad_f16x3(st, in, wpk, meta, aux, out, n, ih, cout, f32);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-        (void)hipFree(wpk);
-        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(s2 f16x3): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
-        return IODINE_OK;
-    }
-    if (mode == 9 || mode == 10) {  // weight-stationary split-fp16 kernel (per-cell max side buffer from launch_cell_max)
-        if (cin_pad != cout || w_o != cout || w_i != cout || ih != iw || ih % 16 != 0) { g_create_error = "iodine_op_conv3x3(ws): shape"; return IODINE_ERR_INVALID; }
-        const size_t wb = conv_ws_wpk_bytes(cout), tf = conv_ws_tmax_floats(n, ih);
-        char* buf = nullptr;
-        if (hipMalloc((void**)&buf, wb + 64 + 2 * tf * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
-        float* meta = (float*)(buf + wb);
-        float *tin = (float*)(buf + wb + 64), *tout = tin + tf;
-        hipError_t e2 = launch_pack_conv_weights_ws(st, w, cout, tflip, meta, buf);
-        if (e2 == hipSuccess) e2 = launch_cell_max(st, in, tin, n, ih, cout);
-        if (e2 == hipSuccess) e2 = launch_conv3x3_ws_f16x3(st, in, buf, meta, bias, aux, out, tin, tout, n, ih, cout, epi, 0);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-        (void)hipFree(buf);
-        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(ws): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
-        return IODINE_OK;
-    }
-    if (mode == 15 || mode == 16) { // weight-stationary STRIDE-2 conv c -> c + bias + ELU (kernels_refws.hip): split-fp16 (15) / exact fp32 (16); ih = fine size
-        if (cin_pad != cout || w_o != cout || w_i != cout || ih != iw || !conv3x3_s2ws_ok(ih, cout)) { g_create_error = "iodine_op_conv3x3(s2ws): shape"; return IODINE_ERR_INVALID; }
-        char* buf = nullptr;
-        const size_t wb = conv_ws_wpk_bytes(cout);
-        if (hipMalloc((void**)&buf, wb + 64) != hipSuccess) return IODINE_ERR_HIP;
-        float* meta = (float*)(buf + wb);
-        hipError_t e2 = mode == 16 ? launch_pack_conv_weights_ws32(st, w, cout, 0, buf) : launch_pack_conv_weights_ws(st, w, cout, 0, meta, buf);
-        if (e2 == hipSuccess) e2 = launch_conv3x3_s2ws_f16x3(st, in, buf, meta, bias, out, n, ih, cout, mode == 16);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-        (void)hipFree(buf);
-        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(s2ws): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
-        return IODINE_OK;
-    }
-    if (mode == 12) {               // exact-fp32 form of the weight-stationary kernel (v_mfma_f32_16x16x4_f32)
-        if (cin_pad != cout || w_o != cout || w_i != cout || ih != iw || ih % 16 != 0) { g_create_error = "iodine_op_conv3x3(ws f32): shape"; return IODINE_ERR_INVALID; }
-        char* buf = nullptr;
-        if (hipMalloc((void**)&buf, conv_ws_wpk_bytes(cout)) != hipSuccess) return IODINE_ERR_HIP;
-        hipError_t e2 = launch_pack_conv_weights_ws32(st, w, cout, tflip, buf);
-        if (e2 == hipSuccess) e2 = launch_conv3x3_ws_f32(st, in, buf, bias, aux, out, n, ih, cout, epi, 0);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-        (void)hipFree(buf);
-        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(ws f32): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
-        return IODINE_OK;
-    }
-#ifdef IODINE_WITH_WINO
-    if (mode == 11) {               // Winograd F(2x2, 3x3) split-fp16 kernel (C = 64): experiment libraries only (tools/wino_variants.sh)
-        if (cin_pad != cout || w_o != cout || w_i != cout || ih != iw || ih % 16 != 0) { g_create_error = "iodine_op_conv3x3(wino): shape"; return IODINE_ERR_INVALID; }
-        const size_t wb = conv_wino_wpk_bytes(cout), tf = conv_ws_tmax_floats(n, ih), sf = conv_wino_scratch_floats(cout);
-        char* buf = nullptr;
-        if (hipMalloc((void**)&buf, wb + 64 + (2 * tf + sf) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
-        float* meta = (float*)(buf + wb);
-        float *tin = (float*)(buf + wb + 64), *tout = tin + tf, *scr = tout + tf;
-        hipError_t e2 = launch_pack_conv_weights_wino(st, w, cout, tflip, meta, buf, scr);
-        if (e2 == hipSuccess) e2 = launch_cell_max(st, in, tin, n, ih, cout);
-        if (e2 == hipSuccess) e2 = launch_conv3x3_wino_f16x3(st, in, buf, meta, bias, aux, out, tin, tout, n, ih, cout, epi, 0);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-        (void)hipFree(buf);
-        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(wino): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
-        return IODINE_OK;
-    }
-#endif
-    if (mode == 2) {                // split-fp16 LDS-tiled kernel
-        float* meta = nullptr;
-        const size_t bytes = (size_t)(cin_pad / 16) * 9 * 2 * 2 * cout * 16;
-        if (hipMalloc((void**)&wpk, bytes + 64) != hipSuccess) return IODINE_ERR_HIP;
-        meta = (float*)((char*)wpk + bytes);
-        hipError_t e2 = launch_pack_conv_weights_f16(st, w, w_o, w_i, cin_pad, cout, tflip, meta, wpk);
-        if (e2 == hipSuccess)
-            e2 = launch_conv3x3_tile_f16x3(st, in, wpk, meta, bias, aux, out, n, ih, cin_pad, cout, epi, 0);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-        (void)hipFree(wpk);
-        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(f16x3): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
-        return IODINE_OK;
-    }
-    if (hipMalloc((void**)&wpk, conv_wpk_elems(cin_pad, cout) * 16) != hipSuccess) return IODINE_ERR_HIP;
-    hipError_t e = launch_pack_conv_weights(st, w, w_o, w_i, cin_pad, cout, tflip, wpk);
-    if (e == hipSuccess) {
-        if (mode == 0) e = (ih == iw && stride == 1) ? launch_conv3x3_tile(st, in, wpk, bias, aux, out, n, ih, cin_pad, cout, epi)
-                                                     : hipErrorInvalidValue;
-        else e = launch_conv3x3_gather(st, in, wpk, bias, out, n, ih, iw, cin_pad, cout, stride);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(wpk);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_op_dec_out(void* stream, const float* in, const float* w, const float* bias, float* out, int n, int s, int c)
-{
-    hipStream_t st = (hipStream_t)stream;
-    float* wk = nullptr;
-    if (hipMalloc((void**)&wk, (size_t)9 * c * 4 * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
-    hipError_t e = launch_pack_dec_out(st, w, wk, c);
-    if (e == hipSuccess) e = launch_dec_out(st, in, wk, bias, out, n, s, c);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(wk);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_op_dec_out: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_op_dec_out_f16x3(void* stream, const float* in, const float* w, const float* bias, float* out, int n, int s, int c, int variant)
-{
-    hipStream_t st = (hipStream_t)stream;
-    const size_t wb = (size_t)(c / 16) * 2 * 2 * 64 * 16, tf = conv_ws_tmax_floats(n, s);
-    char* buf = nullptr;
-    if (s % 16 != 0 || (c != 64 && c != 32)) { g_create_error = "iodine_op_dec_out_f16x3: shape"; return IODINE_ERR_INVALID; }
-    if (hipMalloc((void**)&buf, wb + 64 + tf * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
-    float* meta = (float*)(buf + wb);
-    float* tin = (float*)(buf + wb + 64);
-    hipError_t e = launch_pack_dec_out_gemm(st, w, c, meta, buf);
-    if (e == hipSuccess) e = launch_cell_max(st, in, tin, n, s, c);
-    if (e == hipSuccess && variant == 3) {          // exact-fp32 row-streaming form: its own weight operand (the buffer is large enough)
-        e = launch_pack_dec_out_rows32(st, w, c, (float*)buf);
-        if (e == hipSuccess) e = launch_dec_out_rows_f16x3(st, in, buf, nullptr, bias, out, n, s, c, nullptr, 1);
-    } else if (e == hipSuccess)
-        e = variant == 1 ? launch_dec_out_rows_f16x3(st, in, buf, meta, bias, out, n, s, c, tin)
-                         : launch_dec_out_stream_f16x3(st, in, buf, meta, bias, out, n, s, c, variant == 2 ? nullptr : tin);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_op_dec_out_f16x3: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_op_conv3x3_wgrad(void* stream, const float* in, const float* d, float* gw, float* gb, int n, int s, int ci_pad,
-                            int ci_real, int co, int stride)
-{
-    hipStream_t st = (hipStream_t)stream;
-    const int cmax = std::max(std::max(ci_pad, co), 32);
-    const size_t part_elems = (size_t)512 * 4 * 9 * cmax * cmax, fold_elems = (size_t)WGRAD_FOLD * 9 * cmax * cmax;
-    float* buf = nullptr;
-    if (hipMalloc((void**)&buf, (part_elems + fold_elems + (size_t)512 * 64) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
-    float *part = buf, *fold = buf + part_elems, *part_b = fold + fold_elems;
-    int nparts = 0, cip = 0, nb = 0;
-    hipError_t e;
-    if (stride == 1 && co == 4) {
-        e = launch_dec_out_wgrad_gemm_f16x3(st, in, d, part, part_b, n, s, ci_pad, &nparts, &nb);
-        if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, ci_pad, 4, 4, ci_real, ci_real, 1.f, gw, fold);
-    } else if (stride == 1) {
-        e = launch_conv3x3_wgrad_f16x3_ws(st, in, d, part, part_b, n, s, ci_pad, co, &nparts, &cip, &nb);
-        // stride-1 partial tiles are [9][ci][co padded to 32]
-        if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, ci_pad, cip, co, ci_real, ci_real, 1.f, gw, fold);
-    } else {                                           // stride 2; stride -2: the exact-fp32 form of the same kernel
-        e = launch_conv3x3_s2_wgrad_f16x3(st, in, d, part, part_b, n, s, ci_pad, co, &nparts, &cip, &nb, nullptr, 0, stride == -2);
-        if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, cip, co, co, ci_real, ci_real, 1.f, gw, fold);
-    }
-    if (e == hipSuccess) e = launch_colsum(st, part_b, nb, co, co, 1.f, gb);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3_wgrad: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_op_gen_conv(void* stream, int mode, const float* in, const float* w, const float* bias, const float* aux, float* out, float* gb,
-                       int n, int si, int ci, int ldc, int co, int k, int s, int elu)
-{
-    hipStream_t st = (hipStream_t)stream;
-    if (mode < 0 || mode > 2 || (s != 1 && s != 2) || (k != 3 && k != 5 && k != 7) || ldc < ci) { g_create_error = "iodine_op_gen_conv: argument"; return IODINE_ERR_INVALID; }
-    // tests only: elu bit 8 set = bits 9.. carry a per-channel mask of the input channels that can be non-zero (what the library hands
-    // the stride-2 kernels for an ARCH.ENCODING subset: all-zero 4- / 16-channel groups are skipped) - the masked form must equal the plain one
-    const unsigned chmask = (elu & 0x100) ? ((unsigned)elu >> 9) : 0xffffffffu;
-    elu &= 1;
-    float* buf = nullptr;
-    // weights [tap][ci][co]: the forward pack has ci rows, the data-gradient pack ldc rows (the packed input-channel count is din's stride)
-    const size_t wfl = (size_t)k * k * ldc * co, scr = mode == 2 ? gen_wgrad_scratch_floats(ci, co, k) : 0;
-    if (hipMalloc((void**)&buf, (wfl + scr) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
-    hipError_t e = hipSuccess;
-    if (mode == 0) {
-        e = launch_gen_pack_weights(st, w, co, ci, k, buf);
-        if (e == hipSuccess) e = launch_gen_conv_fwd(st, in, buf, bias, out, n, si, ci, ldc, co, k, s, elu, chmask);
-    } else if (mode == 1) {
-        if (ci != ldc) { (void)hipFree(buf); g_create_error = "iodine_op_gen_conv: mode 1 needs ldc == ci"; return IODINE_ERR_INVALID; }
-        e = launch_gen_pack_weights(st, w, co, ci, k, buf);
-        if (e == hipSuccess) e = launch_gen_conv_dgrad(st, in, buf, aux, out, n, si, ci, ldc, co, k, s);
-    } else {
-        e = launch_gen_conv_wgrad(st, in, aux, buf + wfl, n, si, ci, ldc, ci, co, k, s, 1.f, out, gb, chmask);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_op_gen_conv_f16x3(void* stream, int mode, const float* in, const float* w, const float* bias, const float* aux, float* out, float* gb,
-                             int n, int si, int ci, int ldc, int co, int k, int s, int elu)
-{
-    hipStream_t st = (hipStream_t)stream;
-    // (kernel-level tests only: allocates and frees its scratch around the launches and synchronises - not an entry point to time)
-    if (mode < 0 || mode > 2 || n < 1 || si < 1) { g_create_error = "iodine_op_gen_conv_f16x3: argument"; return IODINE_ERR_INVALID; }
-    if (s != 1 || ci != co || ldc != ci || !gen_split_cch(k, ci)) {
-        g_create_error = "iodine_op_gen_conv_f16x3: shape not covered by the split kernels (stride 1, ci = co = ldc a multiple of 16, k in {3, 5, 7}, slice fits LDS)";
-        return IODINE_ERR_INVALID;
-    }
-    if (mode == 2) {
-        if (!gen_split_wgrad_ok(k, ci) || !aux || !out || !gb) {
-            g_create_error = "iodine_op_gen_conv_f16x3: mode 2 needs aux (gradient), out (gw), gb and a shape the split weight gradient covers";
-            return IODINE_ERR_INVALID;
-        }
-        float* scr = nullptr;
-        if (hipMalloc((void**)&scr, gen_wgrad_scratch_floats(ci, co, k) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
-        hipError_t e2 = launch_gen_split_wgrad(st, in, aux, scr, n, si, ci, k, 1.f, out, gb);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-        (void)hipFree(scr);
-        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv_f16x3: ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
-        return IODINE_OK;
-    }
-    if (ci / 16 > 64) { g_create_error = "iodine_op_gen_conv_f16x3: channel count"; return IODINE_ERR_INVALID; }   // (the 64-float scale slot below)
-    const size_t wfl = (size_t)k * k * ci * co, pbytes = gen_split_pack_bytes(k, ci);
-    float* buf = nullptr;
-    if (hipMalloc((void**)&buf, (wfl + 64) * sizeof(float) + pbytes) != hipSuccess) return IODINE_ERR_HIP;
-    float* meta = buf + wfl;
-    void* pk = buf + wfl + 64;
-    hipError_t e = launch_gen_pack_weights(st, w, co, ci, k, buf);
-    if (e == hipSuccess) e = launch_gen_split_pack(st, buf, k, ci, mode, pk, meta);
-    if (e == hipSuccess) e = launch_gen_split_conv(st, in, pk, meta, mode == 0 ? bias : nullptr, mode == 1 ? aux : nullptr, out, n, si, ci, k, mode == 0 ? (elu & 1) : 0);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv_f16x3: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_op_render_bwd(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean, float* g_out,
-                         int batch, int slots, int pixels, int strict)
-{
-    hipStream_t st = (hipStream_t)stream;
-    if (!dec_out || !g_out || batch < 1 || slots < 1 || slots > 16 || pixels < 1) { g_create_error = "iodine_op_render_bwd: argument"; return IODINE_ERR_INVALID; }
-    hipError_t e = launch_render_bwd(st, dec_out, g_pred, g_mask, g_mean, g_out, batch, slots, pixels, strict ? 1 : 0);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_op_render_bwd: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_op_render_bwd_logits(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean,
-                                const float* g_logits, float* g_out, int batch, int slots, int pixels, int strict)
-{
-    hipStream_t st = (hipStream_t)stream;
-    if (!dec_out || !g_out || batch < 1 || slots < 1 || slots > 16 || pixels < 1) { g_create_error = "iodine_op_render_bwd_logits: argument"; return IODINE_ERR_INVALID; }
-    hipError_t e = launch_render_bwd_logits(st, dec_out, g_pred, g_mask, g_mean, g_logits, g_out, batch, slots, pixels, strict ? 1 : 0);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_op_render_bwd_logits: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
-}
-
-int iodine_op_conv3x3_wgrad_f32(void* stream, const float* in, const float* d, float* gw, float* gb, int n, int s, int c)
-{
-    hipStream_t st = (hipStream_t)stream;
-    const size_t part_elems = (size_t)512 * 4 * 9 * 32 * 32, fold_elems = (size_t)WGRAD_FOLD * 9 * 64 * 64;
-    float* buf = nullptr;
-    if (hipMalloc((void**)&buf, (part_elems + fold_elems + (size_t)512 * 64) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
-    float *part = buf, *fold = buf + part_elems, *part_b = fold + fold_elems;
-    int nparts = 0, cop = 0, nb = 0;
-    hipError_t e;
-    if (c < 0) {                                    // the output conv |c| -> 4 in GEMM form (d has 4 channels; gw [4][|c|][3][3], gb [4])
-        c = -c;
-        e = launch_dec_out_wgrad_f32(st, in, d, part, part_b, n, s, c, &nparts, &nb);
-        if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, c, 4, 4, c, c, 1.f, gw, fold);
-        if (e == hipSuccess) e = launch_colsum(st, part_b, nb, 4, 4, 1.f, gb);
-    } else {
-    e = launch_conv3x3_wgrad_f32_ws(st, in, d, part, part_b, n, s, c, &nparts, &cop, &nb);
-    if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, c, cop, c, c, c, 1.f, gw, fold);
-    if (e == hipSuccess) e = launch_colsum(st, part_b, nb, c, c, 1.f, gb);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3_wgrad_f32: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
     return IODINE_OK;
 }
 

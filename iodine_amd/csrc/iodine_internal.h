@@ -1,0 +1,294 @@
+// What the translation units of libiodine_hip.so share: the handle, its workspace carve-up and call state, and the declarations the
+// padded-handle adapter (iodine_pad.cpp) needs from the compute handle (iodine_api.cpp).  Not part of the ABI (include/iodine_hip.h).
+#pragma once
+#include "../../include/iodine_hip.h"
+#include "common.h"
+
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <list>
+#include <string>
+#include <vector>
+
+// (hidden: nothing declared here is part of the library's dynamic symbol table)
+#pragma GCC visibility push(hidden)
+
+extern std::string g_create_error;          // message of a failed iodine_create / handle-free entry point (iodine_last_error(NULL))
+
+struct ParamInfo {
+    std::string name;
+    int ndim;
+    long long dims[4];
+    size_t numel() const { size_t n = 1; for (int i = 0; i < ndim; ++i) n *= (size_t)dims[i]; return n; }
+};
+
+struct Buffers {               // workspace carve-up for one batch size / mode / run shape
+    int B = 0, mode = -1;
+    int K = 0, T = 0;                          // the run shape (slots, iterations) it was planned for: the shape of the state it holds
+    int F = 0;                                 // frames x4 holds ([F][B][P][4]; iodine_set_frames, 1 = the single image)
+    size_t bytes = 0;
+    float *x4, *V, *dec_out, *g, *lnstat, *ll_img, *img_terms, *scal, *rows, *rows_p, *Rc, *pm, *plv;
+    double* part;
+    std::vector<float*> act;                   // decoder activations a[0..Dd-1]   (N,P,Cd)
+    float *head_xh = nullptr, *head_gp = nullptr;   // refinement head in three launches: LSTM input rows, gate pre-activations
+    float* dpre[2];                            // ping-pong gradient wrt pre-activations
+    std::vector<float*> tmax_act;              // per-cell max |act[l]| (4 floats per 8 x 16 cell): tile scales of the weight-stationary conv
+    float* tmax_dpre[2] = {nullptr, nullptr};  // the same for the two gradient buffers
+    // per-iteration buffers: index i (training keeps all T(+1) copies, inference aliases them)
+    std::vector<float*> z, g_pm, g_plv, latent, enc, pooled, u, gates, xin, h, c;
+    std::vector<float*> enck, encs;             // split refinement input: per-slot [N][P][12], per-image [B][P][8] (alias enc's memory)
+    float* rmap = nullptr;                      // split first refinement layer: conv of the per-image channels, [B][S/2][S/2][Cr]
+    std::vector<std::vector<float*>> ract;     // [iter][layer] refinement activations
+    // training only
+    float *wg_part = nullptr, *wg_part_b = nullptr, *wg_fold = nullptr, *Dsum = nullptr, *Dpart = nullptr, *RT = nullptr, *tmp_lz = nullptr;
+    // round 5 (option wgrad_accum): per-layer partial weight-gradient tiles kept over the T + 1 decoder passes of a step (one reduction
+    // per layer and step); [0] = the output conv, [l] = decoder layer l
+    std::vector<float*> wg_acc, wg_acc_b;
+    float *rown = nullptr, *Rsum = nullptr;     // training row-sum form of the broadcast layer's backward (EPI_L0ROWSX)
+    float* l0scr = nullptr;                     // partial class sums of the row-sum reductions (l0_rows_scratch_floats)
+    float *ddm = nullptr, *ddv = nullptr, *dc1 = nullptr, *dgates = nullptr, *dxin = nullptr, *ds = nullptr,
+          *dpooled = nullptr;
+    float* carry_h[2] = {nullptr, nullptr};
+    float* carry_c[2] = {nullptr, nullptr};
+    std::vector<float*> rdpre;                 // gradient wrt refinement pre-activations, per layer
+    float* aux_seed = nullptr;                 // [2][N][L]: seeds of the head BPTT from auxiliary cotangents (iodine_train_backward_aux)
+    float *gen_scr = nullptr, *gen_l0 = nullptr;                // generic path: wgrad partials; layer-0 scratch (kernels_genl0.hip)
+};
+
+// index of every parameter in the parameter table (= in gacc and in the caller's pointer array), resolved once by build_param_table
+struct ParamSlots {
+    std::vector<int> ref_w, ref_b;              // refine.mlc.layers.<l>
+    int mlp_w, mlp_b, wih, whh, bih, bhh, wm, bm, wv, bv;   // the refinement head
+    std::vector<int> dec_w, dec_b;              // decoder.mlc.layers.<l>
+    int out_w, out_b;                           // decoder.conv
+    int init_mean, init_logvar;
+};
+
+#pragma GCC visibility pop
+
+// HIP-event profiler: when enabled every launch of a category is bracketed by two events on the
+// launch stream; totals are read back (after a sync) with iodine_profile_read.
+struct ProfCat { std::string name; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; unsigned long long seen = 0, seen_win = 0; };
+
+struct GraphEntry { std::vector<uintptr_t> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; unsigned long long used = 0; };
+
+// The objective a call optimises (iodine_set_objective): likelihood scale, KL weight and the per-iteration loss weights.  Held by value:
+// a training forward / a saved elbo keeps the copy it ran with, its backward reads that copy and not the handle's current one.
+// wtab: device table of nw = T + 1 floats, nullptr = the default weighting w_i = (i + 1) / (T + 1), which stays the closed-form
+// expression in the kernels and on the host.  Tables are immutable once uploaded (WeightTable below), so a copy of the pointer is a snapshot;
+// wgen names the table in the hipGraph key (0 = default).
+struct Objective {
+    double sigma = 0.1, beta = 1.0;
+    const float* wtab = nullptr;
+    const float* whost = nullptr;               // the same weights on the host (owned by the handle's table list)
+    int nw = 0, wgen = 0;
+};
+struct WeightTable { std::vector<float> w; float* dev = nullptr; int gen = 0; };
+
+#pragma GCC visibility push(hidden)
+// What the calls so far have left in the arena.  A call SETS its fields on success, next to its run_graphed and outside the graphed body;
+// they are CLEARED by the three transitions below and nowhere else.
+struct CallState {
+    bool fwd_done = false;                      // a training forward is saved: iodine_train_backward* may run
+    int fwd_batch = 0;
+    bool fwd_split = false;                     // the form the saved training forward used
+    Objective fwd_obj, diff_obj;                // what the saved training forward / the saved elbo ran with
+    // a single decode / elbo that ran "for backward" (option save_for_backward): its z, decoder activations and dec_out stay in the arena
+    // (workspace mode 2) until the next compute call; iodine_decode_backward / iodine_elbo_backward consume it
+    int diff_kind = 0;                          // 0 = nothing saved, 1 = a decode, 2 = an elbo
+    int diff_batch = 0;
+    bool diff_init = false;                     // the saved elbo sampled from the initial posterior (init_mean / init_logvar receive gradients)
+    // last elbo() call (iodine.py:161-241): which z buffer / batch the decoder output in buf.dec_out belongs to
+    int last_elbo_iter = -1, last_elbo_batch = 0;
+    int state_iter = -1;                        // buf.h / buf.c [state_iter] = LSTM state the last iodine_reconstruct left (-1: none to read)
+    bool enc_valid = false;                     // the last call left the refinement input ("enc") of its iterations in the workspace
+
+    // iodine_set_params, a changed run shape or frames setting, a consumed backward (like autograd without retain_graph)
+    void saved_passes_gone() { fwd_done = false; diff_kind = 0; }
+    // a compute call re-uses the arena.  keep_lstm_state: a plain iodine_decode does not touch buf.h / buf.c
+    void compute_begins(bool keep_lstm_state = false) { saved_passes_gone(); if (!keep_lstm_state) state_iter = -1; }
+    // a re-plan (ensure_workspace), iodine_set_workspace, a wgrad_accum toggle: nothing the arena held can be read any more.
+    // (iodine_set_workspace used to leave enc_valid and the wgrad_accum toggle state_iter: unobservable, every reader of the two also
+    // refuses while buf.bytes == 0, and the next compute call re-plans)
+    void arena_gone() { saved_passes_gone(); last_elbo_iter = -1; state_iter = -1; enc_valid = false; }
+};
+#pragma GCC visibility pop
+
+struct iodine_handle {
+    iodine_config cfg;
+    Objective obj;                              // current; initially (ARCH.SIGMA, 1, default weighting)
+    CallState calls;                            // what the calls so far have left in the arena
+    std::list<WeightTable> wtabs;               // every distinct weight table this handle was given (content-addressed, never rewritten)
+    int wgen_next = 1;                          // generation of the next new table: counts up for the life of the handle, never re-used
+    std::string err;
+    int profile = 0;                            // 0 off, 1 the dominant conv kernels ("conv_tile_*") only, 2 every category
+    int profile_stride = 1;                     // level 1: bracket every n-th launch of a category only - an event pair costs ~12 us of idle GPU
+                                                // (a barrier packet in front of the kernel and one behind it: tools/step_timeline.py), 54 pairs per cfg3
+                                                // training step = 0.8 ms of the step being measured; a stride coprime to the layer count samples every layer
+    std::vector<ProfCat> prof;
+    ProfCat* prof_cat(const char* name) {
+        for (auto& c : prof) if (c.name == name) return &c;
+        prof.push_back(ProfCat()); prof.back().name = name; return &prof.back();
+    }
+    int L, T, K, S, P, Cd, Dd, Cr, Dr, H;       // K / T: the RUN shape (iodine_set_run_shape; cfg.slots / cfg.iters initially) - the
+                                                // state a call leaves behind has the shape in buf.K / buf.T
+    std::vector<ParamInfo> params;
+    ParamSlots slot;
+    bool params_set = false;
+    int stop_after = -1;
+    int frames = 0;                             // iodine_set_frames: 0 = x is one image per batch entry, E = a clip of E frames, one per ELBO evaluation
+
+    // parameter-derived device buffers (owned)
+    float* lin = nullptr;                       // linspace(-1,1,S)
+    float *wcls = nullptr, *wclsT = nullptr, *cmap = nullptr;
+    std::vector<float*> dec_wf, dec_wb, dec_b;  // packed fwd / dgrad weights + bias copies for layers 1..Dd-1
+    std::vector<float*> dec_wf16, dec_wb16, dec_wmeta;   // split-fp16 packs (+ {scale, 1/scale, scale_b, 1/scale_b})
+    std::vector<float*> dec_wsf, dec_wsb;                // the same weights in the register layout of the weight-stationary conv
+    int precision = 1;                          // 0: exact fp32 MFMA, 1: 3 x fp16 MFMA split (fp32-class accuracy)
+    int out_bwd_fused = 1;                      // training: output conv data + weight gradient in one pass over the activation
+    int fuse_l0 = 1;                            // inference: layer-1 data gradient reduces straight to the layer-0 row sums
+    int refine_split = 1;                       // first refinement layer split into a per-slot and a per-image part (split-fp16 path)
+    int head_fused = 1;                         // training backward: the head's BPTT recurrence as ONE launch (0 = 9 launches per iteration)
+    int refine_bwd_fused = 1;                   // training backward: data gradient of refinement layer 1 + weight gradient of layer 0 in one
+                                                // launch, d(pre-activation 0) never stored (kernels_refbwd.hip; 0 = the two launches)
+    int variant = 6;                            // split-fp16 stride-1 conv: 6 = weight-stationary persistent kernel (power-of-two image sizes;
+                                                // other sizes use 1), 1 = LDS-tiled 16x16 tiles (2 blocks/CU)
+    float* dec_out_w32 = nullptr;               // fp32 operand of the row-streaming output conv (conv_precision 0)
+    float *dec_out_w = nullptr, *dec_out_b = nullptr, *dec_out_wb = nullptr, *dec_out_w16 = nullptr, *dec_out_meta = nullptr,
+          *dec_out_wb16 = nullptr;               // split-fp16 pack of the output conv for its data gradient
+    std::vector<float*> ref_w, ref_b;
+    float *mlp_wT = nullptr, *mlp_b = nullptr, *wihT = nullptr, *whhT = nullptr, *lstm_b = nullptr;
+    float *wmT = nullptr, *bm = nullptr, *wvT = nullptr, *bv = nullptr, *init_mean = nullptr, *init_logvar = nullptr;
+    // training: raw copies used by the head backward GEMMs, strided-dgrad packs, gradient accumulators
+    float *raw_mlp_w = nullptr, *raw_wih = nullptr, *raw_whh = nullptr, *raw_wm = nullptr, *raw_wv = nullptr;
+    std::vector<float*> ref_wb;
+    std::vector<float*> ref_wf16, ref_wb16, ref_wmeta;     // split-fp16 packs of the stride-2 convs (+ {scale, 1/scale} x {fwd, dgrad})
+    float *ref_wk = nullptr, *ref_wsh = nullptr;           // split first layer: weights in the internal channel order [Cr][12][9], [Cr][8][9]
+    float *ref_wk16 = nullptr, *ref_wsh16 = nullptr, *ref_wkmeta = nullptr, *ref_wshmeta = nullptr;   // and their packs
+    float* ref_g20 = nullptr;                              // [Cr][20][9] weight gradient in the internal order
+    unsigned* elbo_counter = nullptr;                      // ticket of pixel_finalize_elbo_kernel (zero between launches)
+    int head_mfma = 1;                                     // LSTM gate pre-activations of the refinement head as one fp32-MFMA GEMM over all slots
+    int refine_l0_fused = 1;                               // encoding + first refinement layer in one kernel (kernels_refl0.hip); 0: pixel_pass2 + two convs
+    void *ref_l0k = nullptr, *ref_l0s = nullptr; float *ref_l0kmeta = nullptr, *ref_l0smeta = nullptr;     // its weight packs
+    int wgrad_accum = 0;                                   // 1: the decoder's partial weight-gradient tiles accumulate over the T + 1 passes of a training
+                                                           // step (alpha = pass weight) and are reduced once per layer and step.  Measured (round 5, same
+                                                           // process A/B): cfg3 48.197 vs 48.200 ms, cfg2 6.55 vs 6.53 ms - the read-modify-write of the
+                                                           // partial tiles in the kernels' tails costs what the 20 saved reduce launches cost: NOT adopted,
+                                                           // kept as an option (off: no extra workspace)
+    int dec_out_rows = 1;                                  // output conv forward: row-streaming kernel without halo recompute (S in {32, 64, 128}); 0 = 16 x 16 tiles
+    int refine_ws = 1;                                     // forward stride-2 convs of refinement layers 1 .. on the weight-stationary kernel (kernels_refws.hip)
+    std::vector<float*> ref_wsf, ref_wsf_meta;             // their weights in its register layout
+    float *ref_w1ws = nullptr, *ref_w1ws_meta = nullptr;   // layer 1's weights in the register layout of the fused layer-1/0 backward
+    // ARCH.ENCODING subsets: reference input channel j of the first refinement layer = internal channel enc_map[j] (code order of
+    // iodine.py:277-340); n_in < 17 -> weights expanded to / gradients gathered from the 17 internal channels
+    int n_in = 17;
+    int enc_map[17];
+    unsigned enc_chmask = 0x1ffffu;                        // bit c: internal channel c is part of the encoding (absent ones are written as 0)
+    float *ref_w17 = nullptr, *ref_g17 = nullptr;          // [Cr][17][kr * kr]
+    // GENERIC fallback path (kernels_generic.hip): KERNEL_SIZE other than 3 or CONV_CHAN other than 32 / 64.  Weights re-packed to
+    // [tap][ci][co]; the broadcast layer is materialised; nothing of the tuned conv kernels runs.
+    bool generic = false;                                  // the DECODER runs on the generic path
+    bool gen_ref = false;                                  // the REFINEMENT conv stack runs on the generic path (round 5: decided separately -
+                                                           // the reference's default ARCH has REF.KERNEL_SIZE 3 / 32 channels beside DEC.KERNEL_SIZE 5)
+    int kd = 3, kr = 3;                                    // DEC / REF kernel sizes
+    int rs = 2;                                            // REF.STRIDE (round 6: other strides run on the generic path's kernels)
+    std::vector<float*> gen_wdec, gen_wref;                // [layer]: packed weights
+    float *gen_wout = nullptr, *gen_cterm = nullptr, *gen_ident = nullptr;   // output conv pack, [P][Cd] bias + coordinate term of decoder layer 0, [9 Cd][L] identity
+    // option gen_conv_precision 1 (kernels_gensplit.hip): split-fp16 slice images + per-slice inverse scales of the decoder's C -> C layers,
+    // forward / data gradient; allocated by the first iodine_set_params that needs them.  gen_split: the packs are current and the shape is covered
+    int gen_precision = 0;
+    bool gen_split = false;
+    std::vector<void*> gs_wf, gs_wb;
+    std::vector<float*> gs_mf, gs_mb;
+    std::vector<float*> gacc;                   // one per parameter, reference shapes (slices of gacc_arena)
+    float* gacc_arena = nullptr;
+    size_t gacc_total = 0;
+    int save_bwd = 0;                           // option save_for_backward: a decode / elbo keeps what its backward reads (calls.diff_*)
+    // hipGraph replay of the fixed-shape launch sequences (option "graph"): one instantiated graph per distinct argument tuple
+    int graph = 0;
+    std::vector<GraphEntry> graphs;
+    std::vector<std::vector<uintptr_t>> seen_keys;       // argument tuples that ran eagerly once (the next call captures)
+    unsigned long long graph_clock = 0;
+    long long graph_replays = 0, graph_captures = 0;
+    std::vector<void*> owned;
+    // round 6: DIM_LATENT / REF.MLP_UNITS that are not multiples of 4.  Lreal: the reference's DIM_LATENT when this handle runs at a padded
+    // latent width (the 3-D layer-norm and the logger means are taken over the real entries); shim: this handle is only the boundary of a
+    // padded INNER handle (iodine_pad.cpp)
+    int Lreal = 0;
+    struct PadShim* shim = nullptr;
+
+    // workspace
+    void* ws_user = nullptr; size_t ws_user_bytes = 0;
+    void* ws_own = nullptr; size_t ws_own_bytes = 0;
+    Buffers buf;
+
+    int fail(int code, const std::string& m) { err = m; return code; }
+};
+
+#define HIPCHK(h, expr)                                                                          \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return (h)->fail(IODINE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// (diff_ready and the adapter's shim_flat_out have C names in the library's dynamic symbol table since they were written; kept, so that the
+// table does not change.  Everything else below is hidden.)
+extern "C" int diff_ready(iodine_handle* h, int kind, const char* who);      // a check like those below; kind 1: a saved decode, 2: a saved elbo
+extern "C" int shim_flat_out(iodine_handle* h, hipStream_t st, float* flat, int accumulate);
+
+#pragma GCC visibility push(hidden)
+
+// cotangents of iodine_train_backward_aux (device pointers, each may be NULL): gl = d(out) / d(loss); the rest on the final evaluation's
+// mean / mask / mask_logits / z and on lambda_T
+struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv; };
+
+// The host-only refusals of the entry points (iodine_api.cpp): null and batch checks, params_set, the 2^31 limits, the frames and
+// iteration-weight counts, the stop_after / trajectory rule, stale state.  They launch nothing, allocate nothing and change nothing but the
+// handle's message.  An entry point calls its check first; the padded boundary calls it on the inner handle with the caller's pointers (only
+// their nullness matters) before it allocates scratch or launches a resize, so both kinds of handle refuse the same calls in the same words.
+int set_params_check(iodine_handle* h, const float* const* dev, int n);
+int reconstruct_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* const* state_in, float* const* traj);
+int decode_check(iodine_handle* h, int batch, const float* z);
+int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* post_mean, const float* post_logvar);
+int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss);
+int train_backward_check(iodine_handle* h, float* const* param_grads, int n);
+int decode_backward_check(iodine_handle* h, int batch);
+int last_elbo_outputs_check(iodine_handle* h, int count);
+int last_posterior_check(iodine_handle* h, int count);
+int last_refine_state_check(iodine_handle* h, int count);
+
+int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev, float* const* param_grads, int n,
+                        int accumulate, const AuxCot* aux = nullptr);
+
+// The boundary of a zero-padded inner handle (iodine_pad.cpp), one function per entry point: h->shim != nullptr
+int pad_create(iodine_handle* h);               // h: cfg and the reference-shaped parameter table are set
+void pad_destroy(iodine_handle* h);
+int pad_set_params(iodine_handle* h, void* stream, const float* const* dev, int n);
+size_t pad_workspace_bytes(const iodine_handle* h, int batch, int mode);
+int pad_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes);
+int pad_set_run_shape(iodine_handle* h, int slots, int iters);
+int pad_set_frames(iodine_handle* h, int frames);
+int pad_set_objective(iodine_handle* h, double sigma, double beta, const double* iter_weights, int n_weights);
+int pad_set_option(iodine_handle* h, const char* key, double value);
+int pad_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* pred, float* mask, float* mean,
+                        float* z, float* post_mean, float* post_logvar, float* elbo_iter, const float* const* state_in, float* const* traj);
+int pad_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c);
+int pad_decode(iodine_handle* h, void* stream, int batch, const float* z, float* pred, float* mask, float* mean);
+int pad_elbo(iodine_handle* h, void* stream, int batch, const float* x, const float* post_mean, const float* post_logvar, const float* eps,
+             float* terms);
+int pad_decode_backward(iodine_handle* h, void* stream, int batch, const float* g_pred, const float* g_mask, const float* g_mean, float* dz,
+                        float* flat_grads, int accumulate);
+int pad_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_dev, float* g_post_mean, float* g_post_logvar, float* flat_grads,
+                      int accumulate);
+int pad_last_elbo_outputs(iodine_handle* h, void* stream, int count, float* z, float* mean, float* mask, float* mask_logits, float* pred);
+int pad_last_posterior(iodine_handle* h, void* stream, int count, float* post_mean, float* post_logvar);
+int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* loss, float* elbo_iter);
+int pad_train_backward(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev, float* const* param_grads, int n,
+                       int accumulate, const AuxCot* aux);
+int pad_logger_scalars(iodine_handle* h, void* stream, float* out2);
+int pad_debug_copy(iodine_handle* h, void* stream, const char* name, int iter, float* dst, size_t max_floats, size_t* n_floats);
+int pad_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset);
+
+#pragma GCC visibility pop

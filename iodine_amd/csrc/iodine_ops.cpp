@@ -1,0 +1,377 @@
+// Handle-free entry points of libiodine_hip.so: the optimizer and metric launches, the Philox sampler, the host linspace and the
+// operator-level test entry points (iodine_op_*).  See include/iodine_hip.h.
+#include "iodine_internal.h"
+
+extern "C" {
+
+int iodine_adam_step(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                     double lr, double beta1, double beta2, double eps, double weight_decay, int step)
+{
+    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || step < 1) { g_create_error = "iodine_adam_step: bad argument"; return IODINE_ERR_INVALID; }
+    const hipError_t e = launch_adam_multi((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, lr, beta1, beta2, eps,
+                                           weight_decay, step);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_adam_step: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+size_t iodine_grad_norm_scratch_bytes(long long total)
+{
+    return total < 1 ? 0 : grad_norm_scratch_bytes(total);
+}
+
+int iodine_grad_norm(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                     double max_norm, void* scratch_dev, size_t scratch_bytes, float* out4_dev)
+{
+    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || !scratch_dev || !out4_dev || !(max_norm > 0.0) ||
+        scratch_bytes < grad_norm_scratch_bytes(total) || ((uintptr_t)scratch_dev & 7)) {
+        g_create_error = "iodine_grad_norm: bad argument (max_norm must be > 0; scratch of iodine_grad_norm_scratch_bytes, 8-byte aligned)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_grad_norm((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, max_norm,
+                                          (double*)scratch_dev, out4_dev);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_grad_norm: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_grad_scale(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                      const float* coef_dev)
+{
+    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || !coef_dev) { g_create_error = "iodine_grad_scale: bad argument"; return IODINE_ERR_INVALID; }
+    const hipError_t e = launch_grad_scale((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, coef_dev);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_grad_scale: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_adam_step_clipped(void* stream, const long long* ptrs_dev, const long long* offsets_dev, int n_tensors, long long total,
+                             double lr, double beta1, double beta2, double eps, double weight_decay, int step,
+                             const float* out4_dev, int skip_nonfinite)
+{
+    if (!ptrs_dev || !offsets_dev || n_tensors < 1 || total < 1 || step < 1 || !out4_dev) { g_create_error = "iodine_adam_step_clipped: bad argument"; return IODINE_ERR_INVALID; }
+    const hipError_t e = launch_adam_multi((hipStream_t)stream, ptrs_dev, offsets_dev, n_tensors, total, lr, beta1, beta2, eps,
+                                           weight_decay, step, out4_dev, skip_nonfinite ? 1 : 0);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_adam_step_clipped: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, int batch, int slots, int n_gt, int pixels,
+                     int* table)
+{
+    if (!mask || !gt || !table || batch < 1 || slots < 1 || n_gt < 1 || pixels < 1 || (size_t)n_gt * slots > 8192) {
+        g_create_error = "iodine_ari_table: bad argument";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_ari_table((hipStream_t)stream, mask, gt, batch, slots, n_gt, pixels, table);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_ari_table: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_randn(void* stream, float* out, long long n, unsigned long long seed, unsigned long long stream_id)
+{
+    if (!out || n < 1) { g_create_error = "iodine_randn: bad argument"; return IODINE_ERR_INVALID; }
+    const hipError_t e = launch_randn_philox((hipStream_t)stream, out, n, seed, stream_id);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_randn: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+void iodine_linspace_host(int n, float* out)
+{
+    // ATen's CPU linspace for float: step = (end - start) / (n - 1); first half counts up from start,
+    // second half counts down from end (symmetric), all in fp32.
+    const float start = -1.f, end = 1.f;
+    if (n == 1) { out[0] = start; return; }
+    const float step = (end - start) / (float)(n - 1);
+    const int halfway = n / 2;
+    for (int i = 0; i < n; ++i)
+        out[i] = i < halfway ? start + step * (float)i : end - step * (float)(n - i - 1);
+}
+
+// ---- operator-level test entry points ---------------------------------------------------------
+static std::string g_op_error;
+
+int iodine_op_conv3x3(void* stream, int mode, const float* in, const float* w, const float* bias, const float* aux,
+                      float* out, int n, int ih, int iw, int w_o, int w_i, int cin_pad, int cout, int stride, int epi,
+                      int tflip)
+{
+    hipStream_t st = (hipStream_t)stream;
+    float* wpk = nullptr;
+    if (mode == 5 || mode == 6 || mode == 13 || mode == 14) {   // stride-2 forward (5) / data gradient (6), split-fp16; 13 / 14: their exact-fp32 forms; ih = fine size
+        float* meta = nullptr;
+        const bool fwd = mode == 5 || mode == 13;
+        const int f32 = mode >= 13;
+        const int cp = fwd ? (cin_pad == 20 ? 32 : (cin_pad == 12 || cin_pad == 8 ? 16 : cin_pad)) : cin_pad;   // floats per pixel -> packed chunks
+        const size_t bytes = (size_t)(cp / 16) * 9 * 2 * 2 * cout * 16;
+        if (hipMalloc((void**)&wpk, bytes + 64) != hipSuccess) return IODINE_ERR_HIP;
+        meta = (float*)((char*)wpk + bytes);
+        hipError_t e2 = f32 ? launch_pack_conv_weights_s2f32(st, w, w_o, w_i, cp, cout, fwd ? 0 : 2, wpk)
+                            : launch_pack_conv_weights_f16(st, w, w_o, w_i, cp, cout, fwd ? 0 : 2, meta, wpk);
+        if (e2 == hipSuccess)
+            e2 = fwd ? launch_conv3x3_s2_f16x3(st, in, wpk, meta, bias, out, n, ih, cin_pad, cout, nullptr, 0, f32)
+                     : launch_conv3x3_s2_dgrad_f16x3(st, in, wpk, meta, aux, out, n, ih, cout, f32);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+        (void)hipFree(wpk);
+        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(s2 f16x3): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
+        return IODINE_OK;
+    }
+    if (mode == 9 || mode == 10) {  // weight-stationary split-fp16 kernel (per-cell max side buffer from launch_cell_max)
+        if (cin_pad != cout || w_o != cout || w_i != cout || ih != iw || ih % 16 != 0) { g_create_error = "iodine_op_conv3x3(ws): shape"; return IODINE_ERR_INVALID; }
+        const size_t wb = conv_ws_wpk_bytes(cout), tf = conv_ws_tmax_floats(n, ih);
+        char* buf = nullptr;
+        if (hipMalloc((void**)&buf, wb + 64 + 2 * tf * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+        float* meta = (float*)(buf + wb);
+        float *tin = (float*)(buf + wb + 64), *tout = tin + tf;
+        hipError_t e2 = launch_pack_conv_weights_ws(st, w, cout, tflip, meta, buf);
+        if (e2 == hipSuccess) e2 = launch_cell_max(st, in, tin, n, ih, cout);
+        if (e2 == hipSuccess) e2 = launch_conv3x3_ws_f16x3(st, in, buf, meta, bias, aux, out, tin, tout, n, ih, cout, epi, 0);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+        (void)hipFree(buf);
+        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(ws): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
+        return IODINE_OK;
+    }
+    if (mode == 15 || mode == 16) { // weight-stationary STRIDE-2 conv c -> c + bias + ELU (kernels_refws.hip): split-fp16 (15) / exact fp32 (16); ih = fine size
+        if (cin_pad != cout || w_o != cout || w_i != cout || ih != iw || !conv3x3_s2ws_ok(ih, cout)) { g_create_error = "iodine_op_conv3x3(s2ws): shape"; return IODINE_ERR_INVALID; }
+        char* buf = nullptr;
+        const size_t wb = conv_ws_wpk_bytes(cout);
+        if (hipMalloc((void**)&buf, wb + 64) != hipSuccess) return IODINE_ERR_HIP;
+        float* meta = (float*)(buf + wb);
+        hipError_t e2 = mode == 16 ? launch_pack_conv_weights_ws32(st, w, cout, 0, buf) : launch_pack_conv_weights_ws(st, w, cout, 0, meta, buf);
+        if (e2 == hipSuccess) e2 = launch_conv3x3_s2ws_f16x3(st, in, buf, meta, bias, out, n, ih, cout, mode == 16);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+        (void)hipFree(buf);
+        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(s2ws): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
+        return IODINE_OK;
+    }
+    if (mode == 12) {               // exact-fp32 form of the weight-stationary kernel (v_mfma_f32_16x16x4_f32)
+        if (cin_pad != cout || w_o != cout || w_i != cout || ih != iw || ih % 16 != 0) { g_create_error = "iodine_op_conv3x3(ws f32): shape"; return IODINE_ERR_INVALID; }
+        char* buf = nullptr;
+        if (hipMalloc((void**)&buf, conv_ws_wpk_bytes(cout)) != hipSuccess) return IODINE_ERR_HIP;
+        hipError_t e2 = launch_pack_conv_weights_ws32(st, w, cout, tflip, buf);
+        if (e2 == hipSuccess) e2 = launch_conv3x3_ws_f32(st, in, buf, bias, aux, out, n, ih, cout, epi, 0);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+        (void)hipFree(buf);
+        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(ws f32): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
+        return IODINE_OK;
+    }
+#ifdef IODINE_WITH_WINO
+    if (mode == 11) {               // Winograd F(2x2, 3x3) split-fp16 kernel (C = 64): experiment libraries only (tools/wino_variants.sh)
+        if (cin_pad != cout || w_o != cout || w_i != cout || ih != iw || ih % 16 != 0) { g_create_error = "iodine_op_conv3x3(wino): shape"; return IODINE_ERR_INVALID; }
+        const size_t wb = conv_wino_wpk_bytes(cout), tf = conv_ws_tmax_floats(n, ih), sf = conv_wino_scratch_floats(cout);
+        char* buf = nullptr;
+        if (hipMalloc((void**)&buf, wb + 64 + (2 * tf + sf) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+        float* meta = (float*)(buf + wb);
+        float *tin = (float*)(buf + wb + 64), *tout = tin + tf, *scr = tout + tf;
+        hipError_t e2 = launch_pack_conv_weights_wino(st, w, cout, tflip, meta, buf, scr);
+        if (e2 == hipSuccess) e2 = launch_cell_max(st, in, tin, n, ih, cout);
+        if (e2 == hipSuccess) e2 = launch_conv3x3_wino_f16x3(st, in, buf, meta, bias, aux, out, tin, tout, n, ih, cout, epi, 0);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+        (void)hipFree(buf);
+        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(wino): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
+        return IODINE_OK;
+    }
+#endif
+    if (mode == 2) {                // split-fp16 LDS-tiled kernel
+        float* meta = nullptr;
+        const size_t bytes = (size_t)(cin_pad / 16) * 9 * 2 * 2 * cout * 16;
+        if (hipMalloc((void**)&wpk, bytes + 64) != hipSuccess) return IODINE_ERR_HIP;
+        meta = (float*)((char*)wpk + bytes);
+        hipError_t e2 = launch_pack_conv_weights_f16(st, w, w_o, w_i, cin_pad, cout, tflip, meta, wpk);
+        if (e2 == hipSuccess)
+            e2 = launch_conv3x3_tile_f16x3(st, in, wpk, meta, bias, aux, out, n, ih, cin_pad, cout, epi, 0);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+        (void)hipFree(wpk);
+        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(f16x3): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
+        return IODINE_OK;
+    }
+    if (hipMalloc((void**)&wpk, conv_wpk_elems(cin_pad, cout) * 16) != hipSuccess) return IODINE_ERR_HIP;
+    hipError_t e = launch_pack_conv_weights(st, w, w_o, w_i, cin_pad, cout, tflip, wpk);
+    if (e == hipSuccess) {
+        if (mode == 0) e = (ih == iw && stride == 1) ? launch_conv3x3_tile(st, in, wpk, bias, aux, out, n, ih, cin_pad, cout, epi)
+                                                     : hipErrorInvalidValue;
+        else e = launch_conv3x3_gather(st, in, wpk, bias, out, n, ih, iw, cin_pad, cout, stride);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(wpk);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_dec_out(void* stream, const float* in, const float* w, const float* bias, float* out, int n, int s, int c)
+{
+    hipStream_t st = (hipStream_t)stream;
+    float* wk = nullptr;
+    if (hipMalloc((void**)&wk, (size_t)9 * c * 4 * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+    hipError_t e = launch_pack_dec_out(st, w, wk, c);
+    if (e == hipSuccess) e = launch_dec_out(st, in, wk, bias, out, n, s, c);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(wk);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_dec_out: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_dec_out_f16x3(void* stream, const float* in, const float* w, const float* bias, float* out, int n, int s, int c, int variant)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const size_t wb = (size_t)(c / 16) * 2 * 2 * 64 * 16, tf = conv_ws_tmax_floats(n, s);
+    char* buf = nullptr;
+    if (s % 16 != 0 || (c != 64 && c != 32)) { g_create_error = "iodine_op_dec_out_f16x3: shape"; return IODINE_ERR_INVALID; }
+    if (hipMalloc((void**)&buf, wb + 64 + tf * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+    float* meta = (float*)(buf + wb);
+    float* tin = (float*)(buf + wb + 64);
+    hipError_t e = launch_pack_dec_out_gemm(st, w, c, meta, buf);
+    if (e == hipSuccess) e = launch_cell_max(st, in, tin, n, s, c);
+    if (e == hipSuccess && variant == 3) {          // exact-fp32 row-streaming form: its own weight operand (the buffer is large enough)
+        e = launch_pack_dec_out_rows32(st, w, c, (float*)buf);
+        if (e == hipSuccess) e = launch_dec_out_rows_f16x3(st, in, buf, nullptr, bias, out, n, s, c, nullptr, 1);
+    } else if (e == hipSuccess)
+        e = variant == 1 ? launch_dec_out_rows_f16x3(st, in, buf, meta, bias, out, n, s, c, tin)
+                         : launch_dec_out_stream_f16x3(st, in, buf, meta, bias, out, n, s, c, variant == 2 ? nullptr : tin);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_dec_out_f16x3: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_conv3x3_wgrad(void* stream, const float* in, const float* d, float* gw, float* gb, int n, int s, int ci_pad,
+                            int ci_real, int co, int stride)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const int cmax = std::max(std::max(ci_pad, co), 32);
+    const size_t part_elems = (size_t)512 * 4 * 9 * cmax * cmax, fold_elems = (size_t)WGRAD_FOLD * 9 * cmax * cmax;
+    float* buf = nullptr;
+    if (hipMalloc((void**)&buf, (part_elems + fold_elems + (size_t)512 * 64) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+    float *part = buf, *fold = buf + part_elems, *part_b = fold + fold_elems;
+    int nparts = 0, cip = 0, nb = 0;
+    hipError_t e;
+    if (stride == 1 && co == 4) {
+        e = launch_dec_out_wgrad_gemm_f16x3(st, in, d, part, part_b, n, s, ci_pad, &nparts, &nb);
+        if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, ci_pad, 4, 4, ci_real, ci_real, 1.f, gw, fold);
+    } else if (stride == 1) {
+        e = launch_conv3x3_wgrad_f16x3_ws(st, in, d, part, part_b, n, s, ci_pad, co, &nparts, &cip, &nb);
+        // stride-1 partial tiles are [9][ci][co padded to 32]
+        if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, ci_pad, cip, co, ci_real, ci_real, 1.f, gw, fold);
+    } else {                                           // stride 2; stride -2: the exact-fp32 form of the same kernel
+        e = launch_conv3x3_s2_wgrad_f16x3(st, in, d, part, part_b, n, s, ci_pad, co, &nparts, &cip, &nb, nullptr, 0, stride == -2);
+        if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, cip, co, co, ci_real, ci_real, 1.f, gw, fold);
+    }
+    if (e == hipSuccess) e = launch_colsum(st, part_b, nb, co, co, 1.f, gb);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3_wgrad: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_gen_conv(void* stream, int mode, const float* in, const float* w, const float* bias, const float* aux, float* out, float* gb,
+                       int n, int si, int ci, int ldc, int co, int k, int s, int elu)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (mode < 0 || mode > 2 || (s != 1 && s != 2) || (k != 3 && k != 5 && k != 7) || ldc < ci) { g_create_error = "iodine_op_gen_conv: argument"; return IODINE_ERR_INVALID; }
+    // tests only: elu bit 8 set = bits 9.. carry a per-channel mask of the input channels that can be non-zero (what the library hands
+    // the stride-2 kernels for an ARCH.ENCODING subset: all-zero 4- / 16-channel groups are skipped) - the masked form must equal the plain one
+    const unsigned chmask = (elu & 0x100) ? ((unsigned)elu >> 9) : 0xffffffffu;
+    elu &= 1;
+    float* buf = nullptr;
+    // weights [tap][ci][co]: the forward pack has ci rows, the data-gradient pack ldc rows (the packed input-channel count is din's stride)
+    const size_t wfl = (size_t)k * k * ldc * co, scr = mode == 2 ? gen_wgrad_scratch_floats(ci, co, k) : 0;
+    if (hipMalloc((void**)&buf, (wfl + scr) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+    hipError_t e = hipSuccess;
+    if (mode == 0) {
+        e = launch_gen_pack_weights(st, w, co, ci, k, buf);
+        if (e == hipSuccess) e = launch_gen_conv_fwd(st, in, buf, bias, out, n, si, ci, ldc, co, k, s, elu, chmask);
+    } else if (mode == 1) {
+        if (ci != ldc) { (void)hipFree(buf); g_create_error = "iodine_op_gen_conv: mode 1 needs ldc == ci"; return IODINE_ERR_INVALID; }
+        e = launch_gen_pack_weights(st, w, co, ci, k, buf);
+        if (e == hipSuccess) e = launch_gen_conv_dgrad(st, in, buf, aux, out, n, si, ci, ldc, co, k, s);
+    } else {
+        e = launch_gen_conv_wgrad(st, in, aux, buf + wfl, n, si, ci, ldc, ci, co, k, s, 1.f, out, gb, chmask);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_gen_conv_f16x3(void* stream, int mode, const float* in, const float* w, const float* bias, const float* aux, float* out, float* gb,
+                             int n, int si, int ci, int ldc, int co, int k, int s, int elu)
+{
+    hipStream_t st = (hipStream_t)stream;
+    // (kernel-level tests only: allocates and frees its scratch around the launches and synchronises - not an entry point to time)
+    if (mode < 0 || mode > 2 || n < 1 || si < 1) { g_create_error = "iodine_op_gen_conv_f16x3: argument"; return IODINE_ERR_INVALID; }
+    if (s != 1 || ci != co || ldc != ci || !gen_split_cch(k, ci)) {
+        g_create_error = "iodine_op_gen_conv_f16x3: shape not covered by the split kernels (stride 1, ci = co = ldc a multiple of 16, k in {3, 5, 7}, slice fits LDS)";
+        return IODINE_ERR_INVALID;
+    }
+    if (mode == 2) {
+        if (!gen_split_wgrad_ok(k, ci) || !aux || !out || !gb) {
+            g_create_error = "iodine_op_gen_conv_f16x3: mode 2 needs aux (gradient), out (gw), gb and a shape the split weight gradient covers";
+            return IODINE_ERR_INVALID;
+        }
+        float* scr = nullptr;
+        if (hipMalloc((void**)&scr, gen_wgrad_scratch_floats(ci, co, k) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+        hipError_t e2 = launch_gen_split_wgrad(st, in, aux, scr, n, si, ci, k, 1.f, out, gb);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+        (void)hipFree(scr);
+        if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv_f16x3: ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
+        return IODINE_OK;
+    }
+    if (ci / 16 > 64) { g_create_error = "iodine_op_gen_conv_f16x3: channel count"; return IODINE_ERR_INVALID; }   // (the 64-float scale slot below)
+    const size_t wfl = (size_t)k * k * ci * co, pbytes = gen_split_pack_bytes(k, ci);
+    float* buf = nullptr;
+    if (hipMalloc((void**)&buf, (wfl + 64) * sizeof(float) + pbytes) != hipSuccess) return IODINE_ERR_HIP;
+    float* meta = buf + wfl;
+    void* pk = buf + wfl + 64;
+    hipError_t e = launch_gen_pack_weights(st, w, co, ci, k, buf);
+    if (e == hipSuccess) e = launch_gen_split_pack(st, buf, k, ci, mode, pk, meta);
+    if (e == hipSuccess) e = launch_gen_split_conv(st, in, pk, meta, mode == 0 ? bias : nullptr, mode == 1 ? aux : nullptr, out, n, si, ci, k, mode == 0 ? (elu & 1) : 0);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv_f16x3: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_render_bwd(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean, float* g_out,
+                         int batch, int slots, int pixels, int strict)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!dec_out || !g_out || batch < 1 || slots < 1 || slots > 16 || pixels < 1) { g_create_error = "iodine_op_render_bwd: argument"; return IODINE_ERR_INVALID; }
+    hipError_t e = launch_render_bwd(st, dec_out, g_pred, g_mask, g_mean, g_out, batch, slots, pixels, strict ? 1 : 0);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_render_bwd: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_render_bwd_logits(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean,
+                                const float* g_logits, float* g_out, int batch, int slots, int pixels, int strict)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!dec_out || !g_out || batch < 1 || slots < 1 || slots > 16 || pixels < 1) { g_create_error = "iodine_op_render_bwd_logits: argument"; return IODINE_ERR_INVALID; }
+    hipError_t e = launch_render_bwd_logits(st, dec_out, g_pred, g_mask, g_mean, g_logits, g_out, batch, slots, pixels, strict ? 1 : 0);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_render_bwd_logits: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_conv3x3_wgrad_f32(void* stream, const float* in, const float* d, float* gw, float* gb, int n, int s, int c)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const size_t part_elems = (size_t)512 * 4 * 9 * 32 * 32, fold_elems = (size_t)WGRAD_FOLD * 9 * 64 * 64;
+    float* buf = nullptr;
+    if (hipMalloc((void**)&buf, (part_elems + fold_elems + (size_t)512 * 64) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+    float *part = buf, *fold = buf + part_elems, *part_b = fold + fold_elems;
+    int nparts = 0, cop = 0, nb = 0;
+    hipError_t e;
+    if (c < 0) {                                    // the output conv |c| -> 4 in GEMM form (d has 4 channels; gw [4][|c|][3][3], gb [4])
+        c = -c;
+        e = launch_dec_out_wgrad_f32(st, in, d, part, part_b, n, s, c, &nparts, &nb);
+        if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, c, 4, 4, c, c, 1.f, gw, fold);
+        if (e == hipSuccess) e = launch_colsum(st, part_b, nb, 4, 4, 1.f, gb);
+    } else {
+    e = launch_conv3x3_wgrad_f32_ws(st, in, d, part, part_b, n, s, c, &nparts, &cop, &nb);
+    if (e == hipSuccess) e = launch_wgrad_reduce(st, part, nparts, c, cop, c, c, c, 1.f, gw, fold);
+    if (e == hipSuccess) e = launch_colsum(st, part_b, nb, c, c, 1.f, gb);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3_wgrad_f32: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+}  // extern "C"

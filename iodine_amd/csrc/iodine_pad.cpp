@@ -1,0 +1,358 @@
+// The reference-shaped boundary of a zero-padded inner handle: everything libiodine_hip.so knows about padding.
+// Round 6 - DIM_LATENT / REF.MLP_UNITS that are not multiples of 4 (the reference takes any: iodine.py:8-32, 446-464).
+// The refinement-head kernels move weight rows as 16-byte vectors, so such a model runs on an INNER handle created at Lp = ceil4(L),
+// Hp = ceil4(H) with every parameter zero-padded into the wider shapes.  Padding is exact, not approximate:
+//   * padded latent entries have init_mean = init_logvar = 0, their decoder-input weights and the rows of mean_update / logvar_update
+//     that produce them are 0, eps is padded with 0: z = mu = 0, logvar = 0 for the whole loop, KL contribution 1/2 (0 + 1 - 0 - 1) = 0,
+//     d ELBO / d lambda = 0, and the LSTM reads them through zero columns of weight_ih;
+//   * padded hidden units: zero MLP row and bias -> u = ELU(ELU(0)) = 0; zero gate rows and biases -> i = f = o = 1/2, g = 0 -> c1 = h1 = 0
+//     from c0 = h0 = 0; the read-out and weight_hh see them through zero columns;
+//   * the one place where the WIDTH itself enters the arithmetic - the layer-norm of the lambda gradients over the latent axis
+//     (iodine.py:263-272, 376-384: mean and unbiased std over L) - runs over the real L (inner->Lreal, dz_latent_kernel), and so does the
+//     logger's mean of init_mean / init_logvar.
+// The outer handle owns the reference-shaped boundary: parameter table, padded copies of the parameters, the element maps, scratch for the
+// tensors with a latent axis (eps, z, posterior), and the gradient in padded shape; every entry point forwards to the inner handle.
+#include "iodine_internal.h"
+
+struct PadShim {
+    iodine_handle* inner = nullptr;
+    int L = 0, H = 0, Lp = 0, Hp = 0;
+    std::vector<float*> pparam;            // padded parameter copies [param]
+    std::vector<int*> pmap;                // [param][padded element] -> element of the reference-shaped tensor, or -1 (zero)
+    std::vector<int> pnumel;               // padded element counts
+    float* pgrad = nullptr;                // flat gradient in padded shapes (the inner handle's named_parameters() order)
+    std::vector<size_t> poff;
+    size_t pgrad_total = 0;
+    // scratch for one call's tensors with a latent axis: grown on demand (outside the refinement loop)
+    size_t cap = 0;                        // floats per buffer
+    float *eps = nullptr, *z = nullptr, *pm = nullptr, *plv = nullptr, *pm_in = nullptr, *plv_in = nullptr;
+    float *hs = nullptr, *cs = nullptr;    // LSTM state rows at the padded width (initial state in / state out)
+    std::vector<void*> owned;
+};
+
+namespace {
+
+int shim_fail(iodine_handle* h, int rc)
+{
+    if (rc && h->shim && h->shim->inner) h->err = h->shim->inner->err.empty() ? std::string(iodine_last_error(nullptr)) : h->shim->inner->err;
+    return rc;
+}
+
+// per-dimension index map of a concatenation of segments (real length -> padded length): padded index -> real index or -1
+std::vector<int> seg_map(std::initializer_list<std::pair<int, int>> segs)
+{
+    std::vector<int> m;
+    int real0 = 0;
+    for (const auto& sg : segs) {
+        for (int i = 0; i < sg.second; ++i) m.push_back(i < sg.first ? real0 + i : -1);
+        real0 += sg.first;
+    }
+    return m;
+}
+
+int shim_build(iodine_handle* h)
+{
+    PadShim* sh = h->shim;
+    const int L = sh->L, H = sh->H, Lp = sh->Lp, Hp = sh->Hp;
+    iodine_handle* in = sh->inner;
+    const size_t np = h->params.size();
+    if (in->params.size() != np) return h->fail(IODINE_ERR_INVALID, "padded inner handle: parameter tables differ");
+    sh->pparam.assign(np, nullptr); sh->pmap.assign(np, nullptr); sh->pnumel.assign(np, 0); sh->poff.assign(np, 0);
+    auto ident = [](int n) { std::vector<int> m(n); for (int i = 0; i < n; ++i) m[i] = i; return m; };
+    const std::vector<int> mH = seg_map({{H, Hp}}), mL = seg_map({{L, Lp}}), m4H = seg_map({{H, Hp}, {H, Hp}, {H, Hp}, {H, Hp}}),
+                           mIN = seg_map({{H, Hp}, {L, Lp}, {L, Lp}, {L, Lp}, {L, Lp}}), mL2 = seg_map({{L, Lp}, {2, 2}});
+    size_t off = 0;
+    for (size_t i = 0; i < np; ++i) {
+        const ParamInfo &pr = h->params[i], &pp = in->params[i];
+        if (pr.name != pp.name || pr.ndim != pp.ndim) return h->fail(IODINE_ERR_INVALID, "padded inner handle: parameter " + pr.name + " differs");
+        std::vector<int> dm[4];
+        for (int d = 0; d < 4; ++d) dm[d] = ident((int)pp.dims[d]);
+        const std::string& n = pr.name;
+        if (n == "refine.mlp.layers.0.weight" || n == "refine.mlp.layers.0.bias") dm[0] = mH;
+        else if (n == "refine.lstm.weight_ih") { dm[0] = m4H; dm[1] = mIN; }
+        else if (n == "refine.lstm.weight_hh") { dm[0] = m4H; dm[1] = mH; }
+        else if (n == "refine.lstm.bias_ih" || n == "refine.lstm.bias_hh") dm[0] = m4H;
+        else if (n == "refine.mean_update.weight" || n == "refine.logvar_update.weight") { dm[0] = mL; dm[1] = mH; }
+        else if (n == "refine.mean_update.bias" || n == "refine.logvar_update.bias" || n == "posterior.init_mean" || n == "posterior.init_logvar") dm[0] = mL;
+        else if (n == "decoder.mlc.layers.0.weight") dm[1] = mL2;          // [Cd][L latent channels | x, y][k][k]
+        for (int d = 0; d < 4; ++d)
+            if ((long long)dm[d].size() != pp.dims[d]) return h->fail(IODINE_ERR_INVALID, "padded inner handle: shape of " + n);
+        const size_t numel = pp.numel();
+        std::vector<int> map(numel);
+        size_t e = 0;
+        for (int a = 0; a < (int)pp.dims[0]; ++a)
+            for (int b2 = 0; b2 < (int)pp.dims[1]; ++b2)
+                for (int c = 0; c < (int)pp.dims[2]; ++c)
+                    for (int d = 0; d < (int)pp.dims[3]; ++d, ++e) {
+                        const int ia = dm[0][a], ib = dm[1][b2], ic = dm[2][c], id = dm[3][d];
+                        map[e] = (ia < 0 || ib < 0 || ic < 0 || id < 0) ? -1
+                                 : (int)((((size_t)ia * pr.dims[1] + ib) * pr.dims[2] + ic) * pr.dims[3] + id);
+                    }
+        void *dmap = nullptr, *dpar = nullptr;
+        HIPCHK(h, hipMalloc(&dmap, numel * sizeof(int))); sh->owned.push_back(dmap);
+        HIPCHK(h, hipMemcpy(dmap, map.data(), numel * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMalloc(&dpar, numel * sizeof(float))); sh->owned.push_back(dpar);
+        sh->pmap[i] = (int*)dmap; sh->pparam[i] = (float*)dpar; sh->pnumel[i] = (int)numel; sh->poff[i] = off;
+        off += numel;
+    }
+    sh->pgrad_total = off;
+    void* g = nullptr;
+    HIPCHK(h, hipMalloc(&g, off * sizeof(float))); sh->owned.push_back(g);
+    sh->pgrad = (float*)g;
+    return IODINE_OK;
+}
+
+// scratch for (rows x Lp) tensors of a call; rows_eps = (T + 1) * N for the noise, N for the others
+// (the new set is allocated in full before the old one is released: a failed hipMalloc leaves the old set and `cap` as they were)
+int shim_scratch(iodine_handle* h, size_t floats)
+{
+    PadShim* sh = h->shim;
+    if (floats <= sh->cap) return IODINE_OK;
+    constexpr int NB = 8;
+    float** bufs[NB] = {&sh->eps, &sh->z, &sh->pm, &sh->plv, &sh->pm_in, &sh->plv_in, &sh->hs, &sh->cs};
+    void* fresh[NB] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i <= NB; ++i) {
+        // (i == NB: the old buffers may still be read by queued work)
+        const hipError_t e = i < NB ? hipMalloc(&fresh[i], floats * sizeof(float)) : (sh->cap > 0 ? hipDeviceSynchronize() : hipSuccess);
+        if (e != hipSuccess) {
+            for (int j = 0; j < i && j < NB; ++j) (void)hipFree(fresh[j]);
+            return h->fail(IODINE_ERR_HIP, std::string(i < NB ? "hipMalloc" : "hipDeviceSynchronize") + " (padded-handle scratch): " +
+                                               hipGetErrorString(e));
+        }
+    }
+    for (int i = 0; i < NB; ++i) {
+        if (*bufs[i]) (void)hipFree(*bufs[i]);
+        *bufs[i] = (float*)fresh[i];
+    }
+    sh->cap = floats;
+    return IODINE_OK;
+}
+
+}  // namespace
+
+// padded flat gradient -> the caller's reference-shaped one (diff_flat_out of the compute handle: only the decoder and the initial
+// posterior can have received anything; when accumulating, the refinement network's gradients are not touched)
+int shim_flat_out(iodine_handle* h, hipStream_t st, float* flat, int accumulate)
+{
+    PadShim* sh = h->shim;
+    size_t off = 0;
+    for (size_t p = 0; p < h->params.size(); ++p) {
+        if (!accumulate || (int)p >= h->slot.dec_w[0])
+            HIPCHK(h, launch_pad_scatter(st, sh->pgrad + sh->poff[p], sh->pmap[p], flat + off, sh->pnumel[p], accumulate));
+        off += h->params[p].numel();
+    }
+    return IODINE_OK;
+}
+
+// ---- the entry points.  Each reads the run shape, the frames setting and the batch of the last call from the inner handle, asks the inner
+// handle's check (iodine_internal.h) before its first scratch allocation or launch, and forwards a refusal's message with shim_fail.
+
+int pad_create(iodine_handle* h)
+{
+    PadShim* sh = h->shim = new PadShim();
+    sh->L = h->cfg.dim_latent; sh->H = h->cfg.ref_mlp_units;
+    sh->Lp = (sh->L + 3) / 4 * 4; sh->Hp = (sh->H + 3) / 4 * 4;
+    iodine_config pc = h->cfg;
+    pc.dim_latent = sh->Lp; pc.ref_mlp_units = sh->Hp;
+    const int rc = iodine_create(&pc, &sh->inner);
+    if (rc) return rc;                                                  // (g_create_error holds the inner message)
+    sh->inner->Lreal = sh->L;
+    const int rb = shim_build(h);
+    if (rb) g_create_error = h->err;
+    return rb;
+}
+
+void pad_destroy(iodine_handle* h)
+{
+    PadShim* sh = h->shim;
+    if (sh->inner) iodine_destroy(sh->inner);
+    for (void* p : sh->owned) (void)hipFree(p);
+    for (float* p : {sh->eps, sh->z, sh->pm, sh->plv, sh->pm_in, sh->plv_in, sh->hs, sh->cs}) if (p) (void)hipFree(p);
+    delete sh;
+    h->shim = nullptr;
+}
+
+int pad_set_params(iodine_handle* h, void* stream, const float* const* dev, int n)
+{
+    PadShim* sh = h->shim;                                     // reference shapes -> zero-padded copies -> the inner handle
+    if (int rc = set_params_check(sh->inner, dev, n)) return shim_fail(h, rc);
+    for (int i = 0; i < n; ++i) HIPCHK(h, launch_pad_gather((hipStream_t)stream, dev[i], sh->pmap[i], sh->pparam[i], sh->pnumel[i]));
+    return shim_fail(h, iodine_set_params(sh->inner, stream, sh->pparam.data(), n));
+}
+
+// settings and read-outs without a latent axis: the inner handle's own
+size_t pad_workspace_bytes(const iodine_handle* h, int batch, int mode) { return iodine_workspace_bytes(h->shim->inner, batch, mode); }
+int pad_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes) { return shim_fail(h, iodine_set_workspace(h->shim->inner, dev_ptr, bytes)); }
+int pad_set_run_shape(iodine_handle* h, int slots, int iters) { return shim_fail(h, iodine_set_run_shape(h->shim->inner, slots, iters)); }
+int pad_set_frames(iodine_handle* h, int frames) { return shim_fail(h, iodine_set_frames(h->shim->inner, frames)); }
+int pad_set_objective(iodine_handle* h, double sigma, double beta, const double* iter_weights, int n_weights)
+{
+    return shim_fail(h, iodine_set_objective(h->shim->inner, sigma, beta, iter_weights, n_weights));
+}
+int pad_set_option(iodine_handle* h, const char* key, double value) { return shim_fail(h, iodine_set_option(h->shim->inner, key, value)); }
+int pad_logger_scalars(iodine_handle* h, void* stream, float* out2) { return shim_fail(h, iodine_logger_scalars(h->shim->inner, stream, out2)); }
+int pad_debug_copy(iodine_handle* h, void* stream, const char* name, int iter, float* dst, size_t max_floats, size_t* n_floats)
+{
+    return shim_fail(h, iodine_debug_copy(h->shim->inner, stream, name, iter, dst, max_floats, n_floats));   // (padded widths)
+}
+int pad_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset)
+{
+    return shim_fail(h, iodine_profile_read(h->shim->inner, category, total_ms, launches, reset));
+}
+
+int pad_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* pred, float* mask, float* mean,
+                        float* z, float* post_mean, float* post_logvar, float* elbo_iter, const float* const* state_in, float* const* traj)
+{
+    PadShim* sh = h->shim;
+    iodine_handle* in = sh->inner;
+    if (int rc = reconstruct_check(in, batch, x, eps, state_in, traj)) return shim_fail(h, rc);
+    hipStream_t st = (hipStream_t)stream;
+    const long long N = (long long)batch * in->K, R = (long long)(in->T + 1) * N;
+    if (int r = shim_scratch(h, std::max((size_t)R * sh->Lp, state_in ? (size_t)N * sh->Hp : (size_t)0))) return r;
+    HIPCHK(h, launch_resize_rows(st, eps, sh->eps, R, sh->L, sh->Lp));
+    const float* pstate[4] = {sh->pm_in, sh->plv_in, sh->hs, sh->cs};
+    if (state_in) {                                        // lambda: L -> padded L, LSTM state: MLP_UNITS -> padded, zero columns
+        HIPCHK(h, launch_resize_rows(st, state_in[0], sh->pm_in, N, sh->L, sh->Lp));
+        HIPCHK(h, launch_resize_rows(st, state_in[1], sh->plv_in, N, sh->L, sh->Lp));
+        HIPCHK(h, launch_resize_rows(st, state_in[2], sh->hs, N, sh->H, sh->Hp));
+        HIPCHK(h, launch_resize_rows(st, state_in[3], sh->cs, N, sh->H, sh->Hp));
+    }
+    const int rc = iodine_reconstruct_seq(in, stream, batch, x, sh->eps, pred, mask, mean, z ? sh->z : nullptr, post_mean ? sh->pm : nullptr,
+                                          post_logvar ? sh->plv : nullptr, elbo_iter, state_in ? pstate : nullptr, traj);
+    if (rc) return shim_fail(h, rc);
+    if (z) HIPCHK(h, launch_resize_rows(st, sh->z, z, N, sh->Lp, sh->L));
+    if (post_mean) HIPCHK(h, launch_resize_rows(st, sh->pm, post_mean, N, sh->Lp, sh->L));
+    if (post_logvar) HIPCHK(h, launch_resize_rows(st, sh->plv, post_logvar, N, sh->Lp, sh->L));
+    return IODINE_OK;
+}
+
+int pad_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c)
+{
+    PadShim* sh = h->shim;
+    if (int rc = last_refine_state_check(sh->inner, count)) return shim_fail(h, rc);
+    hipStream_t st = (hipStream_t)stream;
+    const long long N = (long long)count * sh->inner->buf.K;        // the slots of the call that produced the state, not the run shape
+    if (int r = shim_scratch(h, (size_t)N * sh->Hp)) return r;
+    const int rc = iodine_last_refine_state(sh->inner, stream, count, lstm_h ? sh->hs : nullptr, lstm_c ? sh->cs : nullptr);
+    if (rc) return shim_fail(h, rc);
+    if (lstm_h) HIPCHK(h, launch_resize_rows(st, sh->hs, lstm_h, N, sh->Hp, sh->H));
+    if (lstm_c) HIPCHK(h, launch_resize_rows(st, sh->cs, lstm_c, N, sh->Hp, sh->H));
+    return IODINE_OK;
+}
+
+int pad_decode(iodine_handle* h, void* stream, int batch, const float* z, float* pred, float* mask, float* mean)
+{
+    PadShim* sh = h->shim;
+    if (int rc = decode_check(sh->inner, batch, z)) return shim_fail(h, rc);
+    const long long N = (long long)batch * sh->inner->K;
+    if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
+    HIPCHK(h, launch_resize_rows((hipStream_t)stream, z, sh->z, N, sh->L, sh->Lp));
+    return shim_fail(h, iodine_decode(sh->inner, stream, batch, sh->z, pred, mask, mean));
+}
+
+int pad_elbo(iodine_handle* h, void* stream, int batch, const float* x, const float* post_mean, const float* post_logvar, const float* eps,
+             float* terms)
+{
+    PadShim* sh = h->shim;
+    if (int rc = elbo_check(sh->inner, batch, x, eps, post_mean, post_logvar)) return shim_fail(h, rc);
+    hipStream_t st = (hipStream_t)stream;
+    const long long N = (long long)batch * sh->inner->K;
+    if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
+    HIPCHK(h, launch_resize_rows(st, eps, sh->eps, N, sh->L, sh->Lp));
+    if (post_mean) {
+        HIPCHK(h, launch_resize_rows(st, post_mean, sh->pm_in, N, sh->L, sh->Lp));
+        HIPCHK(h, launch_resize_rows(st, post_logvar, sh->plv_in, N, sh->L, sh->Lp));
+    }
+    return shim_fail(h, iodine_elbo(sh->inner, stream, batch, x, post_mean ? sh->pm_in : nullptr, post_mean ? sh->plv_in : nullptr, sh->eps, terms));
+}
+
+// (the two single-pass backwards write into the scratch their forward sized: the inner call is their first launch, and checks first)
+int pad_decode_backward(iodine_handle* h, void* stream, int batch, const float* g_pred, const float* g_mask, const float* g_mean, float* dz,
+                        float* flat_grads, int accumulate)
+{
+    PadShim* sh = h->shim;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = iodine_decode_backward(sh->inner, stream, batch, g_pred, g_mask, g_mean, dz ? sh->z : nullptr, flat_grads ? sh->pgrad : nullptr, 0);
+    if (rc) return shim_fail(h, rc);
+    if (dz) HIPCHK(h, launch_resize_rows(st, sh->z, dz, (long long)batch * sh->inner->K, sh->Lp, sh->L));
+    return flat_grads ? shim_flat_out(h, st, flat_grads, accumulate) : IODINE_OK;
+}
+
+int pad_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_dev, float* g_post_mean, float* g_post_logvar, float* flat_grads,
+                      int accumulate)
+{
+    PadShim* sh = h->shim;
+    iodine_handle* in = sh->inner;
+    if (int rc = diff_ready(in, 2, "iodine_elbo_backward")) return shim_fail(h, rc);
+    hipStream_t st = (hipStream_t)stream;
+    const long long N = (long long)in->calls.diff_batch * in->buf.K;
+    const int rc = iodine_elbo_backward(in, stream, grad_out_dev, g_post_mean ? sh->pm : nullptr, g_post_logvar ? sh->plv : nullptr,
+                                        flat_grads ? sh->pgrad : nullptr, 0);
+    if (rc) return shim_fail(h, rc);
+    if (g_post_mean) HIPCHK(h, launch_resize_rows(st, sh->pm, g_post_mean, N, sh->Lp, sh->L));
+    if (g_post_logvar) HIPCHK(h, launch_resize_rows(st, sh->plv, g_post_logvar, N, sh->Lp, sh->L));
+    return flat_grads ? shim_flat_out(h, st, flat_grads, accumulate) : IODINE_OK;
+}
+
+int pad_last_elbo_outputs(iodine_handle* h, void* stream, int count, float* z, float* mean, float* mask, float* mask_logits, float* pred)
+{
+    PadShim* sh = h->shim;
+    if (int rc = last_elbo_outputs_check(sh->inner, count)) return shim_fail(h, rc);
+    const long long N = (long long)count * sh->inner->buf.K;        // the slots of the call that produced the state, not the run shape
+    if (z) if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
+    const int rc = iodine_last_elbo_outputs(sh->inner, stream, count, z ? sh->z : nullptr, mean, mask, mask_logits, pred);
+    if (rc) return shim_fail(h, rc);
+    if (z) HIPCHK(h, launch_resize_rows((hipStream_t)stream, sh->z, z, N, sh->Lp, sh->L));
+    return IODINE_OK;
+}
+
+int pad_last_posterior(iodine_handle* h, void* stream, int count, float* post_mean, float* post_logvar)
+{
+    PadShim* sh = h->shim;
+    if (int rc = last_posterior_check(sh->inner, count)) return shim_fail(h, rc);
+    const long long N = (long long)count * sh->inner->buf.K;
+    if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
+    const int rc = iodine_last_posterior(sh->inner, stream, count, post_mean ? sh->pm : nullptr, post_logvar ? sh->plv : nullptr);
+    if (rc) return shim_fail(h, rc);
+    if (post_mean) HIPCHK(h, launch_resize_rows((hipStream_t)stream, sh->pm, post_mean, N, sh->Lp, sh->L));
+    if (post_logvar) HIPCHK(h, launch_resize_rows((hipStream_t)stream, sh->plv, post_logvar, N, sh->Lp, sh->L));
+    return IODINE_OK;
+}
+
+int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* loss, float* elbo_iter)
+{
+    PadShim* sh = h->shim;
+    iodine_handle* in = sh->inner;
+    if (int rc = train_forward_check(in, batch, x, eps, loss)) return shim_fail(h, rc);
+    const long long R = (long long)(in->T + 1) * batch * in->K;
+    if (int r = shim_scratch(h, (size_t)R * sh->Lp)) return r;
+    HIPCHK(h, launch_resize_rows((hipStream_t)stream, eps, sh->eps, R, sh->L, sh->Lp));
+    return shim_fail(h, iodine_train_forward(in, stream, batch, x, sh->eps, loss, elbo_iter));
+}
+
+// the inner handle writes its (scaled) gradient in padded shapes; the real entries are scattered (or added) into the caller's tensors
+int pad_train_backward(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev, float* const* param_grads, int n,
+                       int accumulate, const AuxCot* aux)
+{
+    PadShim* sh = h->shim;
+    iodine_handle* in = sh->inner;
+    if (int rc = train_backward_check(in, param_grads, n)) return shim_fail(h, rc);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<float*> ptrs(h->params.size());
+    for (size_t p = 0; p < ptrs.size(); ++p) ptrs[p] = sh->pgrad + sh->poff[p];
+    AuxCot pa;
+    if (aux) {
+        // cotangents with a latent axis: rows widened to the padded width (zeros in the padded entries), like iodine_decode_backward's dz
+        const long long N = (long long)in->calls.fwd_batch * in->buf.K;
+        if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
+        pa = *aux;
+        if (aux->z) { HIPCHK(h, launch_resize_rows(st, aux->z, sh->z, N, sh->L, sh->Lp)); pa.z = sh->z; }
+        if (aux->pm) { HIPCHK(h, launch_resize_rows(st, aux->pm, sh->pm_in, N, sh->L, sh->Lp)); pa.pm = sh->pm_in; }
+        if (aux->plv) { HIPCHK(h, launch_resize_rows(st, aux->plv, sh->plv_in, N, sh->L, sh->Lp)); pa.plv = sh->plv_in; }
+    }
+    const int rc = train_backward_impl(in, stream, grad_scale, grad_scale_dev, ptrs.data(), n, 0, aux ? &pa : nullptr);
+    if (rc) return shim_fail(h, rc);
+    for (size_t p = 0; p < ptrs.size(); ++p)
+        if (param_grads[p]) HIPCHK(h, launch_pad_scatter(st, ptrs[p], sh->pmap[p], param_grads[p], sh->pnumel[p], accumulate));
+    return IODINE_OK;
+}

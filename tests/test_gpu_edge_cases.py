@@ -93,7 +93,7 @@ def test_unsupported_configurations_fail_loudly():
                                                (10, 30, 1, 0, 5)])       # dk 5: the generic decoder (its broadcast layer takes any latent width) behind the padded handle
 def test_latent_and_mlp_widths_that_are_not_multiples_of_4(L, H, prec, graph, dk):
     """iodine.py:8-32,446-464 take any DIM_LATENT / REF.MLP_UNITS; the library's refinement head moves weight rows as 16-byte vectors and
-    refused other widths until round 6.  Now such a model runs on a zero-padded inner handle (iodine_api.cpp PadShim;
+    refused other widths until round 6.  Now such a model runs on a zero-padded inner handle (iodine_pad.cpp PadShim;
     the layer-norm over the latent axis keeps the real width) with the reference's shapes at the boundary: a whole training step, reconstruct,
     elbo() from the posterior the call left, and decode against the oracle; every parameter gradient in its reference shape."""
     arch = dataclasses.replace(O.tiny_arch(slots=3, iters=2, img_size=16), dim_latent=L, ref_mlp=H, dec_kernel=dk)
