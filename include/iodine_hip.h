@@ -259,6 +259,43 @@ int iodine_train_backward_aux(iodine_handle* h, void* stream, const float* grad_
                               const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
                               float* flat_grads, int accumulate);
 
+/* Training from a carried state: truncated and exact back-propagation through time over a clip that is longer than one call.
+ *
+ * iodine_train_forward_seq: iodine_train_forward with an optional initial state (state_in NULL: the same call, launch for launch).
+ * state_in = {post_mean, post_logvar (B,K,L), h, c (B,K,MLP_UNITS)}, torch order, as iodine_reconstruct_seq takes it; all four pointers are
+ * required.  ELBO evaluation 0 samples from the given lambda and the LSTM starts from (h, c) instead of posterior.init_mean / init_logvar and
+ * zeros (iodine.py:123-126); the call still makes T + 1 evaluations with the same objective and frames.  T = 4 equals T = 2 followed by
+ * T = 2 from the state the first call left (iodine_last_posterior + iodine_last_train_state), evaluation by evaluation and bit for bit, given
+ * the matching slices of x and eps; the boundary evaluation is made by both calls (the last of the first, evaluation 0 of the second), so the
+ * second call usually runs with iter_weights[0] = 0.  posterior.init_mean / init_logvar are not part of such a forward: its backward hands
+ * them nothing (zeros when not accumulating, untouched when accumulating). */
+int iodine_train_forward_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in,
+                             float* loss, float* elbo_iter);
+
+/* The LSTM state (h, c) after the last update of the last iodine_train_forward / iodine_train_forward_seq (the reference keeps it on the
+ * module as self.lstm_hidden, iodine.py:37,124,144): lstm_h / lstm_c (count,K,MLP_UNITS) of the first `count` images, torch order; either may
+ * be NULL.  With iodine_last_posterior this is the state_in of the call that continues the clip.  It stays readable after the backward of
+ * that forward; any other compute call, a re-planned workspace or iodine_set_workspace discards it: IODINE_ERR_STATE.  (A separate entry:
+ * iodine_last_refine_state keeps answering for iodine_reconstruct alone, as it always has.) */
+int iodine_last_train_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c);
+
+/* iodine_train_backward_aux with what crosses the two ends of the saved forward (g_lstm_h, g_lstm_c and g_state all NULL: that entry, bit for
+ * bit).
+ *   g_lstm_h / g_lstm_c (B,K,MLP_UNITS; either may be NULL = zero): cotangents on the LSTM state after the last update - what
+ *     iodine_last_train_state reads, torch order (h = o tanh(c), the read-out layers act on c).  They start the carries of iteration T - 1
+ *     of the back-propagation through the head and, like the other auxiliary terms, are NOT multiplied by *grad_loss_dev.
+ *   g_state: NULL, or four output pointers {g_post_mean, g_post_logvar (B,K,L), g_h, g_c (B,K,MLP_UNITS)}, each of which may be NULL - the
+ *     gradient wrt the state_in the saved iodine_train_forward_seq started from.  The first two are *grad_loss_dev x (-w_0 / B) x
+ *     d(B ELBO_0) / d lambda_0 (w_0 = the loss weight of evaluation 0; nothing else reaches lambda_0: lambda_1 = detach(lambda_0) + delta_0
+ *     and the refinement inputs are detached, iodine.py:343,642-643), the last two the carries left after iteration 0.  Overwritten, never
+ *     accumulated into.  After a forward that ran without a state: IODINE_ERR_STATE with a message, and the saved forward stays.
+ * Exact BPTT over chunks: run the chunks' forwards once to collect each chunk's entry state, then walk them in reverse - forward again from
+ * the entry state, backward with the cotangents on (lambda_T via g_post_mean / g_post_logvar, h_T, c_T) that the following chunk's g_state
+ * returned, accumulate = 1.  Consumes the saved forward and is refused like the entries above. */
+int iodine_train_backward_seq(iodine_handle* h, void* stream, const float* grad_loss_dev, const float* g_mean, const float* g_mask,
+                              const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
+                              const float* g_lstm_h, const float* g_lstm_c, float* flat_grads, int accumulate, float* const* g_state);
+
 /* logger.update(init_mean=posterior.init_mean.mean(), init_logvar=posterior.init_logvar.mean()) -- iodine.py:156-157:
  * out2 (2, device) = the two means of the parameters last handed to iodine_set_params. */
 int iodine_logger_scalars(iodine_handle* h, void* stream, float* out2);

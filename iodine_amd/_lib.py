@@ -29,6 +29,7 @@ EXPORTS = (
     'iodine_set_frames', 'iodine_reconstruct_seq', 'iodine_last_refine_state',
     'iodine_train_backward_aux', 'iodine_op_render_bwd_logits',
     'iodine_set_objective',
+    'iodine_train_forward_seq', 'iodine_train_backward_seq', 'iodine_last_train_state',
 )
 
 
@@ -126,6 +127,10 @@ def lib() -> C.CDLL:
         L.iodine_op_render_bwd_logits.argtypes = [vp] + [vp] * 6 + [ci] * 4
     if hasattr(L, 'iodine_set_objective'):              # (model.sigma / beta / iter_weights; absent from older A/B builds, which run the default objective)
         L.iodine_set_objective.argtypes = [vp, C.c_double, C.c_double, C.POINTER(C.c_double), ci]
+    if hasattr(L, 'iodine_train_forward_seq'):          # (training from a carried state; absent from older A/B builds)
+        L.iodine_train_forward_seq.argtypes = [vp, vp, ci, vp, vp, C.POINTER(vp), vp, vp]
+        L.iodine_train_backward_seq.argtypes = [vp, vp] + [vp] * 10 + [ci, C.POINTER(vp)]
+        L.iodine_last_train_state.argtypes = [vp, vp, ci, vp, vp]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

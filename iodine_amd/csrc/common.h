@@ -282,7 +282,9 @@ hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_pl
                             const float* Wm, const float* Wv, const float* Whh, const float* Wih, const float* Wmlp, float* ddm,
                             float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr,
                             const float* seed_m, const float* seed_v, const float* gl_dev,
-                            const float* wtab);       // wtab: T + 1 loss weights, NULL = the default (i + 2) / (T + 1)
+                            const float* wtab,        // wtab: T + 1 loss weights, NULL = the default (i + 2) / (T + 1)
+                            const float* dh_in = nullptr, const float* dc_in = nullptr,    // [N][H] cotangents on (h_T, c_T): initial carries
+                            float* dh_out = nullptr, float* dc_out = nullptr);             // [N][H] d / d (h_0, c_0): the carries left (seeded instance only)
 // split-precision (3 x fp16 MFMA) variant of the stride-1 tile conv
 hipError_t launch_pack_conv_weights_f16(hipStream_t st, const float* src, int O, int I, int cin, int cout, int tflip,
                                         float* meta, void* dst);

@@ -847,9 +847,12 @@ int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, co
     return IODINE_OK;
 }
 
-int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss)
+int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss, const float* const* state_in)
 {
     char m[256];
+    if (state_in && !(state_in[0] && state_in[1] && state_in[2] && state_in[3]))
+        return h->fail(IODINE_ERR_INVALID, "iodine_train_forward_seq: an initial state needs all four tensors - post_mean, post_logvar (B,K,L) and "
+                                           "the LSTM state h, c (B,K,MLP_UNITS)");
     if (h->frames > 0 && h->frames != h->T + 1) {
         snprintf(m, sizeof m, "iodine_train_forward: the frames setting is %d, but a forward of %d iterations makes %d ELBO evaluations: it takes "
                               "x of shape (B, %d, 3, %d, %d), one frame per evaluation (or frames 0: one image (B, 3, %d, %d))",
@@ -871,12 +874,16 @@ int train_forward_check(iodine_handle* h, int batch, const float* x, const float
     return IODINE_OK;
 }
 
-int train_backward_check(iodine_handle* h, float* const* param_grads, int n)
+int train_backward_check(iodine_handle* h, float* const* param_grads, int n, const AuxCot* aux)
 {
     if (!h->calls.fwd_done) return h->fail(IODINE_ERR_STATE, "iodine_train_backward: no iodine_train_forward to differentiate");
     if (n != (int)h->params.size() || !param_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward: wrong parameter count");
     if (h->buf.mode != 1 || h->buf.B != h->calls.fwd_batch || h->buf.K != h->K || h->buf.T != h->T)
         return h->fail(IODINE_ERR_STATE, "iodine_train_backward: the training workspace of the forward pass was re-planned");
+    if (aux && aux->g_state && !h->calls.fwd_from_state)
+        return h->fail(IODINE_ERR_STATE, "iodine_train_backward_seq: g_state asks for the gradient of an initial state, but the saved forward ran "
+                                         "without one (iodine_train_forward / iodine_train_forward_seq with state_in = NULL start from "
+                                         "posterior.init_mean / init_logvar, which receive that gradient as parameters)");
     return IODINE_OK;
 }
 
@@ -919,6 +926,11 @@ int last_refine_state_check(iodine_handle* h, int count)
 {
     return last_check(h, h->calls.state_iter < 0 || h->buf.mode != 0, "iodine_last_refine_state",
                       ": no iodine_reconstruct has run on the current workspace, or another compute call has re-used it since", count);
+}
+int last_train_state_check(iodine_handle* h, int count)
+{
+    return last_check(h, h->calls.state_iter < 0 || h->buf.mode != 1, "iodine_last_train_state",
+                      ": no iodine_train_forward has run on the current workspace, or another compute call has re-used it since", count);
 }
 
 extern "C" {
@@ -1542,6 +1554,18 @@ int iodine_last_refine_state(iodine_handle* h, void* stream, int count, float* l
     return IODINE_OK;
 }
 
+int iodine_last_train_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_last_refine_state(h, stream, count, lstm_h, lstm_c, true);
+    if (int rc = last_train_state_check(h, count)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = sizeof(float) * (size_t)count * h->buf.K * h->H;
+    if (lstm_h) HIPCHK(h, hipMemcpyAsync(lstm_h, h->buf.h[h->calls.state_iter], n, hipMemcpyDeviceToDevice, st));
+    if (lstm_c) HIPCHK(h, hipMemcpyAsync(lstm_c, h->buf.c[h->calls.state_iter], n, hipMemcpyDeviceToDevice, st));
+    return IODINE_OK;
+}
+
 int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, float* pred, float* mask, float* mean)
 {
     if (h && h->shim) return pad_decode(h, stream, batch, z, pred, mask, mean);
@@ -1722,9 +1746,15 @@ int iodine_last_posterior(iodine_handle* h, void* stream, int count, float* post
 int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* loss,
                          float* elbo_iter)
 {
+    return iodine_train_forward_seq(h, stream, batch, x, eps, nullptr, loss, elbo_iter);
+}
+
+int iodine_train_forward_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in,
+                             float* loss, float* elbo_iter)
+{
     if (!h) return IODINE_ERR_INVALID;
-    if (h->shim) return pad_train_forward(h, stream, batch, x, eps, loss, elbo_iter);
-    int rc = train_forward_check(h, batch, x, eps, loss);
+    if (h->shim) return pad_train_forward(h, stream, batch, x, eps, state_in, loss, elbo_iter);
+    int rc = train_forward_check(h, batch, x, eps, loss, state_in);
     if (rc) return rc;
     rc = ensure_workspace(h, batch, 1);
     if (rc) return rc;
@@ -1736,15 +1766,23 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
         const size_t eps_stride = (size_t)N * L;
         HIPCHK(h, launch_zero_fill(st, h->gacc_arena, h->gacc_total));
         PROF(h, st, "frames_in", launch_x_to_nhwc4(st, x, b.x4, B, h->P, h->frames > 0 ? h->frames : 1));
-        HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, L, h->H));
+        if (state_in) {
+            // continue from (lambda, h, c) of an earlier call (truncated / exact BPTT over a clip): evaluation 0 samples from the given lambda
+            HIPCHK(h, hipMemcpyAsync(b.pm, state_in[0], sizeof(float) * eps_stride, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(b.plv, state_in[1], sizeof(float) * eps_stride, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(b.h[0], state_in[2], sizeof(float) * (size_t)N * h->H, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(b.c[0], state_in[3], sizeof(float) * (size_t)N * h->H, hipMemcpyDeviceToDevice, st));
+        } else
+            HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, L, h->H));
         for (int i = 0; i <= T; ++i) {
             // d loss / d (B * ELBO_i) = -w_i / B; the default weighting keeps its closed form
             const float alpha = h->obj.whost ? -h->obj.whost[i] / (float)B : -((float)(i + 1) / (float)(T + 1)) / (float)B;
             int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, true, alpha);
             if (r) return r;
-            if (i == 0) {
+            if (i == 0 && !state_in) {
                 // lambda_0 = init_mean / init_logvar repeated over (B, K) (iodine.py:615-616): their gradient is the
-                // column sum of d loss / d lambda_0; later lambdas are detached from it (iodine.py:642-643)
+                // column sum of d loss / d lambda_0; later lambdas are detached from it (iodine.py:642-643).  From a caller's state the two
+                // parameters are not part of the graph: d loss / d lambda_0 goes to the state instead (iodine_train_backward_seq, g_state)
                 HIPCHK(h, launch_colsum(st, b.g_pm[0], N, L, L, alpha, h->gacc[h->slot.init_mean]));
                 HIPCHK(h, launch_colsum(st, b.g_plv[0], N, L, L, alpha, h->gacc[h->slot.init_logvar]));
             }
@@ -1757,10 +1795,14 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
         if (elbo_iter) HIPCHK(h, hipMemcpyAsync(elbo_iter, b.scal, sizeof(float) * 3 * (T + 1), hipMemcpyDeviceToDevice, st));
         return IODINE_OK;
     };
-    rc = run_graphed(h, st, graph_key(h, 4, B, {x, eps, loss, elbo_iter}), body);
+    std::vector<uintptr_t> key = graph_key(h, 4, B, {x, eps, loss, elbo_iter});
+    for (int j = 0; j < 4; ++j) key.push_back((uintptr_t)(state_in ? state_in[j] : nullptr));     // (all four NULL: no state)
+    rc = run_graphed(h, st, key, body);
     if (rc) return rc;
     CallState& cs = h->calls;
     cs.fwd_done = true;
+    cs.fwd_from_state = state_in != nullptr;
+    cs.state_iter = T;                                     // buf.h / buf.c [T]: the LSTM state after the last update (iodine_last_train_state)
     cs.fwd_obj = h->obj;                                   // the backward differentiates the forward as it ran (a replay ran the same objective: graph key)
     cs.enc_valid = true;                                   // training keeps the encoding of every iteration (the backward reads it)
     cs.fwd_batch = B;
@@ -1779,7 +1821,7 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
 {
     if (!h) return IODINE_ERR_INVALID;
     if (h->shim) return pad_train_backward(h, stream, grad_scale, grad_scale_dev, param_grads, n, accumulate, aux);
-    if (int rc = train_backward_check(h, param_grads, n)) return rc;
+    if (int rc = train_backward_check(h, param_grads, n, aux)) return rc;
     hipStream_t st = (hipStream_t)stream;
     std::vector<const void*> kp;
     for (int i = 0; i < n; ++i) kp.push_back(param_grads[i]);
@@ -1793,13 +1835,18 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
     key.push_back((uintptr_t)h->calls.fwd_split);                // the backward body reads the saved inputs in the forward's layout
     if (aux) {
         key.push_back(1);
-        for (const void* q : {aux->gl, aux->mean, aux->mask, aux->logits, aux->z, aux->pm, aux->plv}) key.push_back((uintptr_t)q);
+        for (const void* q : {aux->gl, aux->mean, aux->mask, aux->logits, aux->z, aux->pm, aux->plv, aux->lstm_h, aux->lstm_c}) key.push_back((uintptr_t)q);
+        for (int j = 0; j < 4; ++j) key.push_back((uintptr_t)(aux->g_state ? aux->g_state[j] : nullptr));
     }
     auto body = [&]() -> int {
     Buffers& b = h->buf;
     const int B = h->calls.fwd_batch, N = B * h->K, T = h->T, L = h->L, H = h->H, Cr = h->Cr, IN = H + 4 * L;
     const ParamSlots& ps = h->slot;
     float *seed_m = nullptr, *seed_v = nullptr;
+    // iodine_train_backward_seq: cotangents on (h_T, c_T) start the carries of iteration T - 1, the carries left after iteration 0 are
+    // d / d (h_0, c_0) of the state the forward started from
+    const float *cot_h = aux ? aux->lstm_h : nullptr, *cot_c = aux ? aux->lstm_c : nullptr;
+    float *gs_h = aux && aux->g_state ? aux->g_state[2] : nullptr, *gs_c = aux && aux->g_state ? aux->g_state[3] : nullptr;
     if (aux) {
         // Auxiliary cotangents on the final evaluation (iodine.py:171-187,642-651).  Order of the scaling: what the forward accumulated
         // carries the ELBO weights and takes d(out) / d(loss) now, in place (the refinement part is still 0); the auxiliary terms join with
@@ -1823,7 +1870,7 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
         // the whole BPTT recurrence of the head in one launch (rows are independent: a block walks i = T-1 .. 0 for its rows)
         PROF(h, st, "head_bwd", launch_head_bptt(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->raw_wm, h->raw_wv, h->raw_whh,
                                                  h->raw_wih, h->raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr,
-                                                 seed_m, seed_v, aux ? aux->gl : nullptr, obj.wtab));
+                                                 seed_m, seed_v, aux ? aux->gl : nullptr, obj.wtab, cot_h, cot_c, gs_h, gs_c));
     } else {
     int cf = 0;                                            // carry buffer flip
     for (int i = T - 1; i >= 0; --i) {
@@ -1842,8 +1889,8 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
         HIPCHK(h, launch_sgemm(st, 0, 0, N, H, L, 1.f, ddm, L, h->raw_wm, H, 0.f, b.dc1, H));
         HIPCHK(h, launch_sgemm(st, 0, 0, N, H, L, 1.f, ddv, L, h->raw_wv, H, 1.f, b.dc1, H));
         const bool last = (i == T - 1);
-        HIPCHK(h, launch_lstm_bwd_pointwise(st, b.gates[i], b.c[i], c1, b.dc1, last ? nullptr : b.carry_h[cf],
-                                            last ? nullptr : b.carry_c[cf], dgates, b.carry_c[cf ^ 1], N, H));
+        HIPCHK(h, launch_lstm_bwd_pointwise(st, b.gates[i], b.c[i], c1, b.dc1, last ? cot_h : b.carry_h[cf],
+                                            last ? cot_c : b.carry_c[cf], dgates, b.carry_c[cf ^ 1], N, H));
         HIPCHK(h, launch_sgemm(st, 0, 0, N, H, 4 * H, 1.f, dgates, 4 * H, h->raw_whh, H, 0.f, b.carry_h[cf ^ 1], H));
         cf ^= 1;
         // MLP (double ELU) and average pool
@@ -1851,6 +1898,21 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
         HIPCHK(h, launch_mlp_bwd_pointwise(st, b.dxin, H, b.u[i], ds, N, H));
         HIPCHK(h, launch_sgemm(st, 0, 0, N, Cr, H, 1.f, ds, H, h->raw_mlp_w, Cr, 0.f, b.dpooled + (size_t)i * N * Cr, Cr));
     }
+    if (gs_h) HIPCHK(h, hipMemcpyAsync(gs_h, b.carry_h[cf], sizeof(float) * (size_t)N * H, hipMemcpyDeviceToDevice, st));
+    if (gs_c) HIPCHK(h, hipMemcpyAsync(gs_c, b.carry_c[cf], sizeof(float) * (size_t)N * H, hipMemcpyDeviceToDevice, st));
+    }
+    if (aux && aux->g_state) {
+        // d loss / d lambda_0 of the state: d(out) / d(loss) x (-w_0 / B) x d(B ELBO_0) / d lambda_0 - the term the forward hands to init_mean /
+        // init_logvar as a column sum when it starts from them.  Nothing else reaches lambda_0: lambda_1 = detach(lambda_0) + delta_0, and the
+        // refinement inputs are detached (iodine.py:343,642-643)
+        const float alpha0 = obj.whost ? -obj.whost[0] / (float)B : -(1.f / (float)(T + 1)) / (float)B;
+        float* const dst[2] = {aux->g_state[0], aux->g_state[1]};
+        const float* const src[2] = {b.g_pm[0], b.g_plv[0]};
+        for (int j = 0; j < 2; ++j) {
+            if (!dst[j]) continue;
+            HIPCHK(h, launch_scale(st, src[j], alpha0, dst[j], N * L));
+            HIPCHK(h, launch_scale_dev_add(st, dst[j], aux->gl, nullptr, N * L));
+        }
     }
     {
         // Weight gradients of the head: sums over the iterations of X_i^T D_i = ONE GEMM per parameter over all T * N rows
@@ -1986,7 +2048,23 @@ int iodine_train_backward_aux(iodine_handle* h, void* stream, const float* grad_
     std::vector<float*> ptrs(h->params.size());
     size_t off = 0;
     for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
-    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar};
+    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, nullptr, nullptr, nullptr};
+    return train_backward_impl(h, stream, 1.f, nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, &aux);
+}
+
+int iodine_train_backward_seq(iodine_handle* h, void* stream, const float* grad_loss_dev, const float* g_mean, const float* g_mask,
+                              const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
+                              const float* g_lstm_h, const float* g_lstm_c, float* flat_grads, int accumulate, float* const* g_state)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    // nothing crosses the ends of the saved forward: the backward with auxiliary cotangents itself, launch for launch
+    if (!g_lstm_h && !g_lstm_c && !g_state)
+        return iodine_train_backward_aux(h, stream, grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, flat_grads, accumulate);
+    if (!flat_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward_seq: flat_grads is required");
+    std::vector<float*> ptrs(h->params.size());
+    size_t off = 0;
+    for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
+    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c, g_state};
     return train_backward_impl(h, stream, 1.f, nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, &aux);
 }
 

@@ -93,6 +93,7 @@ struct CallState {
     bool fwd_done = false;                      // a training forward is saved: iodine_train_backward* may run
     int fwd_batch = 0;
     bool fwd_split = false;                     // the form the saved training forward used
+    bool fwd_from_state = false;                // the saved training forward started from a caller's (lambda, h, c) (iodine_train_forward_seq)
     Objective fwd_obj, diff_obj;                // what the saved training forward / the saved elbo ran with
     // a single decode / elbo that ran "for backward" (option save_for_backward): its z, decoder activations and dec_out stay in the arena
     // (workspace mode 2) until the next compute call; iodine_decode_backward / iodine_elbo_backward consume it
@@ -101,7 +102,8 @@ struct CallState {
     bool diff_init = false;                     // the saved elbo sampled from the initial posterior (init_mean / init_logvar receive gradients)
     // last elbo() call (iodine.py:161-241): which z buffer / batch the decoder output in buf.dec_out belongs to
     int last_elbo_iter = -1, last_elbo_batch = 0;
-    int state_iter = -1;                        // buf.h / buf.c [state_iter] = LSTM state the last iodine_reconstruct left (-1: none to read)
+    int state_iter = -1;                        // buf.h / buf.c [state_iter] = LSTM state the last iodine_reconstruct (buf.mode 0) or training
+                                                // forward (buf.mode 1) left (-1: none to read)
     bool enc_valid = false;                     // the last call left the refinement input ("enc") of its iterations in the workspace
 
     // iodine_set_params, a changed run shape or frames setting, a consumed backward (like autograd without retain_graph)
@@ -242,7 +244,9 @@ extern "C" int shim_flat_out(iodine_handle* h, hipStream_t st, float* flat, int 
 
 // cotangents of iodine_train_backward_aux (device pointers, each may be NULL): gl = d(out) / d(loss); the rest on the final evaluation's
 // mean / mask / mask_logits / z and on lambda_T
-struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv; };
+// iodine_train_backward_seq adds lstm_h / lstm_c = cotangents on the LSTM state after the last update and g_state = NULL or four output
+// pointers (each may be NULL): d / d (post_mean, post_logvar, h, c) of the state the forward started from
+struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv, *lstm_h, *lstm_c; float* const* g_state; };
 
 // The host-only refusals of the entry points (iodine_api.cpp): null and batch checks, params_set, the 2^31 limits, the frames and
 // iteration-weight counts, the stop_after / trajectory rule, stale state.  They launch nothing, allocate nothing and change nothing but the
@@ -252,12 +256,13 @@ int set_params_check(iodine_handle* h, const float* const* dev, int n);
 int reconstruct_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* const* state_in, float* const* traj);
 int decode_check(iodine_handle* h, int batch, const float* z);
 int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* post_mean, const float* post_logvar);
-int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss);
-int train_backward_check(iodine_handle* h, float* const* param_grads, int n);
+int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss, const float* const* state_in = nullptr);
+int train_backward_check(iodine_handle* h, float* const* param_grads, int n, const AuxCot* aux = nullptr);
 int decode_backward_check(iodine_handle* h, int batch);
 int last_elbo_outputs_check(iodine_handle* h, int count);
 int last_posterior_check(iodine_handle* h, int count);
 int last_refine_state_check(iodine_handle* h, int count);
+int last_train_state_check(iodine_handle* h, int count);
 
 int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev, float* const* param_grads, int n,
                         int accumulate, const AuxCot* aux = nullptr);
@@ -274,7 +279,7 @@ int pad_set_objective(iodine_handle* h, double sigma, double beta, const double*
 int pad_set_option(iodine_handle* h, const char* key, double value);
 int pad_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* pred, float* mask, float* mean,
                         float* z, float* post_mean, float* post_logvar, float* elbo_iter, const float* const* state_in, float* const* traj);
-int pad_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c);
+int pad_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c, bool train = false);
 int pad_decode(iodine_handle* h, void* stream, int batch, const float* z, float* pred, float* mask, float* mean);
 int pad_elbo(iodine_handle* h, void* stream, int batch, const float* x, const float* post_mean, const float* post_logvar, const float* eps,
              float* terms);
@@ -284,7 +289,8 @@ int pad_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_dev,
                       int accumulate);
 int pad_last_elbo_outputs(iodine_handle* h, void* stream, int count, float* z, float* mean, float* mask, float* mask_logits, float* pred);
 int pad_last_posterior(iodine_handle* h, void* stream, int count, float* post_mean, float* post_logvar);
-int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* loss, float* elbo_iter);
+int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in, float* loss,
+                      float* elbo_iter);
 int pad_train_backward(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev, float* const* param_grads, int n,
                        int accumulate, const AuxCot* aux);
 int pad_logger_scalars(iodine_handle* h, void* stream, float* out2);

@@ -26,7 +26,8 @@ struct PadShim {
     // scratch for one call's tensors with a latent axis: grown on demand (outside the refinement loop)
     size_t cap = 0;                        // floats per buffer
     float *eps = nullptr, *z = nullptr, *pm = nullptr, *plv = nullptr, *pm_in = nullptr, *plv_in = nullptr;
-    float *hs = nullptr, *cs = nullptr;    // LSTM state rows at the padded width (initial state in / state out)
+    float *hs = nullptr, *cs = nullptr;    // LSTM state rows at the padded width (initial state in / state out; cotangents on the final state)
+    float *gh = nullptr, *gc = nullptr;    // gradient of the initial LSTM state at the padded width (iodine_train_backward_seq, g_state)
     std::vector<void*> owned;
 };
 
@@ -108,9 +109,9 @@ int shim_scratch(iodine_handle* h, size_t floats)
 {
     PadShim* sh = h->shim;
     if (floats <= sh->cap) return IODINE_OK;
-    constexpr int NB = 8;
-    float** bufs[NB] = {&sh->eps, &sh->z, &sh->pm, &sh->plv, &sh->pm_in, &sh->plv_in, &sh->hs, &sh->cs};
-    void* fresh[NB] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    constexpr int NB = 10;
+    float** bufs[NB] = {&sh->eps, &sh->z, &sh->pm, &sh->plv, &sh->pm_in, &sh->plv_in, &sh->hs, &sh->cs, &sh->gh, &sh->gc};
+    void* fresh[NB] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i <= NB; ++i) {
         // (i == NB: the old buffers may still be read by queued work)
         const hipError_t e = i < NB ? hipMalloc(&fresh[i], floats * sizeof(float)) : (sh->cap > 0 ? hipDeviceSynchronize() : hipSuccess);
@@ -167,7 +168,7 @@ void pad_destroy(iodine_handle* h)
     PadShim* sh = h->shim;
     if (sh->inner) iodine_destroy(sh->inner);
     for (void* p : sh->owned) (void)hipFree(p);
-    for (float* p : {sh->eps, sh->z, sh->pm, sh->plv, sh->pm_in, sh->plv_in, sh->hs, sh->cs}) if (p) (void)hipFree(p);
+    for (float* p : {sh->eps, sh->z, sh->pm, sh->plv, sh->pm_in, sh->plv_in, sh->hs, sh->cs, sh->gh, sh->gc}) if (p) (void)hipFree(p);
     delete sh;
     h->shim = nullptr;
 }
@@ -226,14 +227,16 @@ int pad_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* 
     return IODINE_OK;
 }
 
-int pad_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c)
+// (train: iodine_last_train_state - the same read-out after a training forward)
+int pad_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c, bool train)
 {
     PadShim* sh = h->shim;
-    if (int rc = last_refine_state_check(sh->inner, count)) return shim_fail(h, rc);
+    if (int rc = train ? last_train_state_check(sh->inner, count) : last_refine_state_check(sh->inner, count)) return shim_fail(h, rc);
     hipStream_t st = (hipStream_t)stream;
     const long long N = (long long)count * sh->inner->buf.K;        // the slots of the call that produced the state, not the run shape
     if (int r = shim_scratch(h, (size_t)N * sh->Hp)) return r;
-    const int rc = iodine_last_refine_state(sh->inner, stream, count, lstm_h ? sh->hs : nullptr, lstm_c ? sh->cs : nullptr);
+    const int rc = (train ? iodine_last_train_state : iodine_last_refine_state)(sh->inner, stream, count, lstm_h ? sh->hs : nullptr,
+                                                                                 lstm_c ? sh->cs : nullptr);
     if (rc) return shim_fail(h, rc);
     if (lstm_h) HIPCHK(h, launch_resize_rows(st, sh->hs, lstm_h, N, sh->Hp, sh->H));
     if (lstm_c) HIPCHK(h, launch_resize_rows(st, sh->cs, lstm_c, N, sh->Hp, sh->H));
@@ -319,15 +322,24 @@ int pad_last_posterior(iodine_handle* h, void* stream, int count, float* post_me
     return IODINE_OK;
 }
 
-int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* loss, float* elbo_iter)
+int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in, float* loss,
+                      float* elbo_iter)
 {
     PadShim* sh = h->shim;
     iodine_handle* in = sh->inner;
-    if (int rc = train_forward_check(in, batch, x, eps, loss)) return shim_fail(h, rc);
-    const long long R = (long long)(in->T + 1) * batch * in->K;
-    if (int r = shim_scratch(h, (size_t)R * sh->Lp)) return r;
-    HIPCHK(h, launch_resize_rows((hipStream_t)stream, eps, sh->eps, R, sh->L, sh->Lp));
-    return shim_fail(h, iodine_train_forward(in, stream, batch, x, sh->eps, loss, elbo_iter));
+    if (int rc = train_forward_check(in, batch, x, eps, loss, state_in)) return shim_fail(h, rc);
+    hipStream_t st = (hipStream_t)stream;
+    const long long N = (long long)batch * in->K, R = (long long)(in->T + 1) * N;
+    if (int r = shim_scratch(h, std::max((size_t)R * sh->Lp, state_in ? (size_t)N * sh->Hp : (size_t)0))) return r;
+    HIPCHK(h, launch_resize_rows(st, eps, sh->eps, R, sh->L, sh->Lp));
+    const float* pstate[4] = {sh->pm_in, sh->plv_in, sh->hs, sh->cs};
+    if (state_in) {                                        // as pad_reconstruct_seq: zero columns at the padded widths
+        HIPCHK(h, launch_resize_rows(st, state_in[0], sh->pm_in, N, sh->L, sh->Lp));
+        HIPCHK(h, launch_resize_rows(st, state_in[1], sh->plv_in, N, sh->L, sh->Lp));
+        HIPCHK(h, launch_resize_rows(st, state_in[2], sh->hs, N, sh->H, sh->Hp));
+        HIPCHK(h, launch_resize_rows(st, state_in[3], sh->cs, N, sh->H, sh->Hp));
+    }
+    return shim_fail(h, iodine_train_forward_seq(in, stream, batch, x, sh->eps, state_in ? pstate : nullptr, loss, elbo_iter));
 }
 
 // the inner handle writes its (scaled) gradient in padded shapes; the real entries are scattered (or added) into the caller's tensors
@@ -336,22 +348,34 @@ int pad_train_backward(iodine_handle* h, void* stream, float grad_scale, const f
 {
     PadShim* sh = h->shim;
     iodine_handle* in = sh->inner;
-    if (int rc = train_backward_check(in, param_grads, n)) return shim_fail(h, rc);
+    if (int rc = train_backward_check(in, param_grads, n, aux)) return shim_fail(h, rc);
     hipStream_t st = (hipStream_t)stream;
     std::vector<float*> ptrs(h->params.size());
     for (size_t p = 0; p < ptrs.size(); ++p) ptrs[p] = sh->pgrad + sh->poff[p];
     AuxCot pa;
+    float* pgs[4] = {nullptr, nullptr, nullptr, nullptr};
+    const long long N = (long long)in->calls.fwd_batch * in->buf.K;
     if (aux) {
         // cotangents with a latent axis: rows widened to the padded width (zeros in the padded entries), like iodine_decode_backward's dz
-        const long long N = (long long)in->calls.fwd_batch * in->buf.K;
-        if (int r = shim_scratch(h, (size_t)N * sh->Lp)) return r;
+        const bool hid = aux->lstm_h || aux->lstm_c || aux->g_state;
+        if (int r = shim_scratch(h, std::max((size_t)N * sh->Lp, hid ? (size_t)N * sh->Hp : (size_t)0))) return r;
         pa = *aux;
+        // ... and those on the LSTM state after the last update; the gradient of the initial state comes back at the padded widths
+        if (aux->lstm_h) { HIPCHK(h, launch_resize_rows(st, aux->lstm_h, sh->hs, N, sh->H, sh->Hp)); pa.lstm_h = sh->hs; }
+        if (aux->lstm_c) { HIPCHK(h, launch_resize_rows(st, aux->lstm_c, sh->cs, N, sh->H, sh->Hp)); pa.lstm_c = sh->cs; }
+        if (aux->g_state) {
+            float* const scr[4] = {sh->pm, sh->plv, sh->gh, sh->gc};
+            for (int j = 0; j < 4; ++j) pgs[j] = aux->g_state[j] ? scr[j] : nullptr;
+            pa.g_state = pgs;
+        }
         if (aux->z) { HIPCHK(h, launch_resize_rows(st, aux->z, sh->z, N, sh->L, sh->Lp)); pa.z = sh->z; }
         if (aux->pm) { HIPCHK(h, launch_resize_rows(st, aux->pm, sh->pm_in, N, sh->L, sh->Lp)); pa.pm = sh->pm_in; }
         if (aux->plv) { HIPCHK(h, launch_resize_rows(st, aux->plv, sh->plv_in, N, sh->L, sh->Lp)); pa.plv = sh->plv_in; }
     }
     const int rc = train_backward_impl(in, stream, grad_scale, grad_scale_dev, ptrs.data(), n, 0, aux ? &pa : nullptr);
     if (rc) return shim_fail(h, rc);
+    for (int j = 0; j < 4; ++j)                              // the state's gradient, sliced back to the real widths
+        if (pgs[j]) HIPCHK(h, launch_resize_rows(st, pgs[j], aux->g_state[j], N, j < 2 ? sh->Lp : sh->Hp, j < 2 ? sh->L : sh->H));
     for (size_t p = 0; p < ptrs.size(); ++p)
         if (param_grads[p]) HIPCHK(h, launch_pad_scatter(st, ptrs[p], sh->pmap[p], param_grads[p], sh->pnumel[p], accumulate));
     return IODINE_OK;

@@ -1002,6 +1002,10 @@ hipError_t launch_mlp_bwd_pointwise(hipStream_t st, const float* du, int ldu, co
 // SEED (iodine_train_backward_aux): the ELBO seeds are multiplied by *gl_dev (autograd's d(out) / d(loss), device memory; NULL = 0) and
 // the first step, i = T - 1, adds seed_m / seed_v [N][L] = the cotangents that reach delta_{T-1} through lambda_T - unscaled by alpha and
 // by *gl_dev.  SEED = false is the kernel as it was.
+// The seeded instance also takes the carries across the ends of the saved forward (iodine_train_backward_seq), each pointer optional and
+// tested once outside the iteration loop: dh_in / dc_in [N][H] = cotangents on the LSTM state (h_T, c_T) after the last update - they take
+// the place of the zero carries iteration T - 1 starts from; dh_out / dc_out [N][H] receive the carries left after iteration 0 =
+// d / d (h_0, c_0), the initial LSTM state (rows of the tail block beyond N are not written, as everywhere in this kernel).
 // =========================================================================================
 constexpr int HB = 2;      // rows per block
 constexpr int HKG = 16;    // k groups = waves of the 1024-thread block; a lane owns four adjacent output columns (16-byte weight loads)
@@ -1073,7 +1077,8 @@ void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ 
                       const float* __restrict__ Wmlp, float* __restrict__ ddm_o, float* __restrict__ ddv_o,
                       float* __restrict__ dgates_o, float* __restrict__ ds_o, float* __restrict__ dpooled_o, int T, int N, int B,
                       int L, int H, int Cr, const float* __restrict__ seed_m, const float* __restrict__ seed_v,
-                      const float* __restrict__ gl_dev, const float* __restrict__ wtab)
+                      const float* __restrict__ gl_dev, const float* __restrict__ wtab, const float* __restrict__ dh_in,
+                      const float* __restrict__ dc_in, float* __restrict__ dh_out, float* __restrict__ dc_out)
 {
     // wtab: the objective's table of T + 1 loss weights (one uniform 4-byte load per iteration), NULL = the default (i + 1) / (T + 1)
     extern __shared__ __attribute__((aligned(16))) float s_hb[];
@@ -1089,6 +1094,12 @@ void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ 
     const int tid = threadIdx.x, n0 = blockIdx.x * HB;
     const int IN = H + 4 * L;
     for (int idx = tid; idx < HB * H; idx += 1024) { s_dh[idx] = 0.f; s_dcc[idx] = 0.f; }
+    if constexpr (SEED) {
+        if (dh_in)
+            for (int idx = tid; idx < HB * H; idx += 1024) s_dh[idx] = dh_in[(size_t)min(n0 + idx / H, N - 1) * H + idx % H];
+        if (dc_in)
+            for (int idx = tid; idx < HB * H; idx += 1024) s_dcc[idx] = dc_in[(size_t)min(n0 + idx / H, N - 1) * H + idx % H];
+    }
     __syncthreads();
     float gl = 0.f;
     if constexpr (SEED) gl = gl_dev ? gl_dev[0] : 0.f;
@@ -1169,6 +1180,15 @@ void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ 
         }
         __syncthreads();
     }
+    if constexpr (SEED) {
+        // the carries iteration 0 left (its last barrier is behind every write of s_dh / s_dcc)
+        if (dh_out)
+            for (int idx = tid; idx < HB * H; idx += 1024)
+                if (n0 + idx / H < N) dh_out[(size_t)(n0 + idx / H) * H + idx % H] = s_dh[idx];
+        if (dc_out)
+            for (int idx = tid; idx < HB * H; idx += 1024)
+                if (n0 + idx / H < N) dc_out[(size_t)(n0 + idx / H) * H + idx % H] = s_dcc[idx];
+    }
 }
 
 // does the fused kernel's LDS footprint fit (it does for every shipped configuration; MLP_UNITS >= 512 falls back to the launch sequence)
@@ -1179,11 +1199,13 @@ bool head_bptt_fits(int L, int H, int Cr) { return Cr <= H && H % 4 == 0 && Cr %
 hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_plv, const float* gates, const float* cst, const float* u,
                             const float* Wm, const float* Wv, const float* Whh, const float* Wih, const float* Wmlp, float* ddm,
                             float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr,
-                            const float* seed_m, const float* seed_v, const float* gl_dev, const float* wtab)
+                            const float* seed_m, const float* seed_v, const float* gl_dev, const float* wtab, const float* dh_in,
+                            const float* dc_in, float* dh_out, float* dc_out)
 {
     IOD_XSKIP(2);
     if (Cr > H) return hipErrorInvalidValue;                                // (the pool gradient is staged in an [HB][H] buffer)
     if ((seed_m == nullptr) != (seed_v == nullptr)) return hipErrorInvalidValue;
+    if (!seed_m && (dh_in || dc_in || dh_out || dc_out)) return hipErrorInvalidValue;   // (the carries across the ends: the seeded instance only)
     const size_t lds = head_bptt_lds(L, H);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid((N + HB - 1) / HB), block(64 * HKG);
@@ -1191,13 +1213,13 @@ hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_pl
         static std::atomic<unsigned> attr_devs_seed{0};
         if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<true>, 160 * 1024, attr_devs_seed); e != hipSuccess) return e;
         hipLaunchKernelGGL(head_bptt_kernel<true>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
-                           ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, seed_m, seed_v, gl_dev, wtab);
+                           ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, seed_m, seed_v, gl_dev, wtab, dh_in, dc_in, dh_out, dc_out);
         return hipGetLastError();
     }
     static std::atomic<unsigned> attr_devs{0};
     if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<false>, 160 * 1024, attr_devs); e != hipSuccess) return e;
     hipLaunchKernelGGL(head_bptt_kernel<false>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
-                       ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr, wtab);
+                       ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr, wtab, nullptr, nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
 

@@ -25,7 +25,10 @@ Video input and resumable refinement (the paper's tracking use of the T-step loo
 one ``x``, iodine.py:73-105,115-158): ``x`` may be a clip ``(B, E, 3, S, S)`` with one frame per ELBO evaluation of the call (E = T for
 ``encode`` / ``reconstruct``, T + 1 for ``forward``); ``reconstruct(x, trajectory=True)`` leaves the decode of every iteration in
 ``model.trajectory``; ``model.refinement_state()`` / ``state=`` carry (lambda, h, c) from one call into the next, so a long clip runs
-in chunks of ``n_iters`` frames.
+in chunks of ``n_iters`` frames.  Training carries the state the same way: ``forward(x, state=..., keep_state=True)`` continues a clip
+from the state the last chunk left - detached tensors give truncated back-propagation through time, tensors that require grad receive the
+gradient of the chunk (``iodine_train_backward_seq``), and ``attach_state=True`` leaves ``model.lstm_hidden`` attached to the graph like
+the reference, so that ``iodine_amd.engine.clip_backward`` computes the exact gradient of a long clip chunk by chunk.
 
 Extensions over the reference: every entry point takes an optional ``eps`` tensor of shape
 (T+1, B, K, L) replacing the ``torch.randn_like`` draws of ``Gaussian.sample``
@@ -145,26 +148,44 @@ class _TrainStep(torch.autograd.Function):
 
 class _TrainStepAttached(torch.autograd.Function):
     """``forward(x, attach_state=True)``: the loss AND what the forward's final ``elbo()`` leaves on the reference's module - z, mean, mask,
-    mask_logits, posterior.mean / .logvar, there still attached to the graph (iodine.py:137,171-187,642-651) - as outputs of ONE node, so a
-    single ``backward()`` of any combination of them goes through iodine_train_backward_aux.  Same library calls as the plain step."""
+    mask_logits, posterior.mean / .logvar and the LSTM state ``lstm_hidden``, there still attached to the graph (iodine.py:37,137,144,
+    171-187,642-651) - as outputs of ONE node, so a single ``backward()`` of any combination of them goes through
+    iodine_train_backward_aux / iodine_train_backward_seq.  Also the node of every ``forward(x, state=...)``: the four state tensors are its
+    inputs (None: a forward from the initial posterior, the same library calls as the plain step) and receive the gradient the chunk hands
+    back when they require grad; ``attach`` False: loss and ELBO terms are the only outputs."""
 
     @staticmethod
-    def forward(ctx, module, x, eps, *params):
+    def forward(ctx, module, x, eps, attach, s_pm, s_plv, s_h, s_c, *params):
         ctx.set_materialize_grads(False)                   # an output the loss does not use arrives as None -> a NULL pointer
-        loss, elbo_iter = module._train_forward(x, eps)
-        ctx.module, ctx.serial = module, module._call_serial
+        state = None if s_pm is None else (s_pm, s_plv, s_h, s_c)
+        loss, elbo_iter = module._train_forward(x, eps, state)
+        ctx.module, ctx.serial, ctx.from_state = module, module._call_serial, state is not None
+        ctx.BK = (x.shape[0], module.K)
+        ctx.mark_non_differentiable(elbo_iter)
+        if not attach:
+            return loss, elbo_iter
         module._fetch_last_elbo(module._handle, x, elbo_iter[-1])      # (grad mode is off in here: the logger entries stay detached)
         module._fetch_posterior(module._handle, x.shape[0], x.device)
-        ctx.mark_non_differentiable(elbo_iter)
-        return (loss, elbo_iter, module.z, module.mean, module.mask, module.mask_logits, module.posterior.mean, module.posterior.logvar)
+        h, c = module._fetch_train_state(x.shape[0], x.device)
+        H = h.shape[-1]
+        return (loss, elbo_iter, module.z, module.mean, module.mask, module.mask_logits, module.posterior.mean, module.posterior.logvar,
+                h.view(-1, H), c.view(-1, H))
 
     @staticmethod
-    def backward(ctx, g_loss, _g_elbo, g_z, g_mean, g_mask, g_logits, g_pm, g_plv):
+    def backward(ctx, g_loss, _g_elbo, g_z=None, g_mean=None, g_mask=None, g_logits=None, g_pm=None, g_plv=None, g_h=None, g_c=None):
         aux = (g_mean, g_mask, g_logits, g_z, g_pm, g_plv)
-        if g_loss is None and all(g is None for g in aux):
-            return (None,) * len(ctx.needs_input_grad)
-        grads = ctx.module._train_backward(g_loss, ctx.serial, aux)
-        return (None, None, None, *grads)
+        n_in = len(ctx.needs_input_grad)
+        if g_loss is None and all(g is None for g in aux) and g_h is None and g_c is None:
+            return (None,) * n_in
+        want = tuple(ctx.from_state and ctx.needs_input_grad[4 + j] for j in range(4))
+        if g_h is None and g_c is None and not any(want):
+            gstate = (None,) * 4
+            grads = ctx.module._train_backward(g_loss, ctx.serial, aux)
+        else:
+            grads, gstate = ctx.module._train_backward_seq(g_loss, ctx.serial, aux, (g_h, g_c), want, ctx.BK)
+        if ctx.from_state:                                 # the initial posterior is not part of a forward from a state: unused parameters
+            grads = [None if n.startswith('posterior.') else g for (n, _), g in zip(ctx.module.named_parameters(), grads)]
+        return (None, None, None, None, *gstate, *grads)
 
 
 _WRAPPER_OPTIONS = ('batch_cap',)      # max images per library call (IODINE.max_batch); the rest go to iodine_set_option
@@ -176,9 +197,9 @@ class _ChunkedTrainStep(torch.autograd.Function):
     the parameter gradients accumulated with the chunk's share of the batch; ``loss.backward()`` then only scales them."""
 
     @staticmethod
-    def forward(ctx, module, x, eps, *params):
-        loss, elbo_iter, flat = module._train_chunked(x, eps)
-        ctx.module, ctx.flat = module, flat
+    def forward(ctx, module, x, eps, state, keep_state, *params):
+        loss, elbo_iter, flat = module._train_chunked(x, eps, state, keep_state)
+        ctx.module, ctx.flat, ctx.from_state = module, flat, state is not None
         ctx.mark_non_differentiable(elbo_iter)
         return loss, elbo_iter
 
@@ -186,10 +207,11 @@ class _ChunkedTrainStep(torch.autograd.Function):
     def backward(ctx, grad_loss, _grad_elbo):
         flat = ctx.flat * grad_loss.to(ctx.flat.dtype)
         views, off = [], 0
-        for p in ctx.module._ordered_params():
-            views.append(flat[off:off + p.numel()].view_as(p))
+        for n, p in ctx.module.named_parameters():
+            # (from a detached state the initial posterior is not part of the forward: None, like unused parameters elsewhere)
+            views.append(None if ctx.from_state and n.startswith('posterior.') else flat[off:off + p.numel()].view_as(p))
             off += p.numel()
-        return (None, None, None, *views)
+        return (None, None, None, None, None, *views)
 
 
 def _flat_views(module, flat, live):
@@ -596,6 +618,22 @@ class IODINE(nn.Module):
             raise RuntimeError(f'state does not match this call: (B, K) = ({B}, {K}) needs tensors of shapes {want}, got {got}')
         return tuple(t.detach().to(device=device, dtype=torch.float32).contiguous() for t in state)
 
+    def _check_train_state(self, state, B, K, device):
+        """``state=`` of forward: the tuple of ``_check_state`` with h / c given as (B, K, MLP_UNITS) or as the reference's (B * K,
+        MLP_UNITS) (``lstm_hidden``, iodine.py:37).  NOT detached: tensors that require grad stay connected to the caller's graph."""
+        if state is None:
+            return None
+        L, H = self.dim_latent, int(self._cfg.ref_mlp_units)
+        if not isinstance(state, (tuple, list)) or len(state) != 4 or any(not torch.is_tensor(t) for t in state):
+            raise RuntimeError('state must be the tuple (post_mean, post_logvar, h, c) that model.refinement_state() returns')
+        got = tuple(tuple(t.shape) for t in state)
+        ok = got[0] == (B, K, L) and got[1] == (B, K, L) and all(g in ((B, K, H), (B * K, H)) for g in got[2:])
+        if not ok:
+            raise RuntimeError(f'state does not match this call: (B, K) = ({B}, {K}) needs post_mean, post_logvar of shape {(B, K, L)} and '
+                               f'h, c of shape {(B, K, H)} (or {(B * K, H)}, as model.lstm_hidden); got {got}')
+        shapes = ((B, K, L), (B, K, L), (B, K, H), (B, K, H))
+        return tuple(t.to(device=device, dtype=torch.float32).reshape(shp).contiguous() for t, shp in zip(state, shapes))
+
     def _eps(self, eps, B, device):
         shape = (self.n_iters + 1, B, self.K, self.dim_latent)
         return self._normals(eps, shape, device)
@@ -820,10 +858,13 @@ class IODINE(nn.Module):
         and the LSTM state in torch order, as RefinementNetwork.forward returns it (iodine.py:503) - the ``state=`` of a continuing
         call.  The LSTM state of an un-chunked call stays in the library's workspace until asked for: the first call of this method
         must come before the next model call (forward / reconstruct / encode / decode / elbo re-use the workspace).  A state once
-        fetched stays until the next ``encode`` / ``reconstruct`` replaces it or a training ``forward`` discards it."""
+        fetched stays until the next ``encode`` / ``reconstruct`` replaces it or a training ``forward`` discards it.  After
+        ``forward(..., keep_state=True)`` it returns (lambda_T, h_T, c_T) of that training forward, detached - the ``state=`` of the next
+        chunk of a clip."""
         st = self._state
         if st is None:
-            raise RuntimeError('IODINE.refinement_state: no encode / reconstruct has run since the module was made or trained')
+            raise RuntimeError('IODINE.refinement_state: no encode / reconstruct has run since the module was made or trained (a training '
+                               'forward keeps its final state only when called with keep_state=True)')
         if st.h is None:
             if st.serial is None:
                 raise RuntimeError('IODINE.refinement_state: the last encode / reconstruct ran in chunks (batch > max_batch()), which '
@@ -1038,41 +1079,62 @@ class IODINE(nn.Module):
         return self.elbo_terms[0, 0].clone(), pre
 
     # ---- training: iodine.py:115-158 + lib/engine/train.py:60-63 -------------------------------------
-    def forward(self, x, eps=None, state=None, attach_state=False):
+    def forward(self, x, eps=None, state=None, attach_state=False, keep_state=False):
         """-sum_i w_i ELBO_i (w = ``model.iter_weights``, by default (i+1)/(T+1); ELBO_i = LL_i - ``model.beta`` KL_i at ``model.sigma``),
         differentiable wrt every parameter.  ``loss.backward()`` differentiates the forward as it
         ran, at the (K, T) it read - like the reference, whose autograd graph is fixed at forward time.  ``x``: images
-        (B, 3, S, S) or a clip (B, T+1, 3, S, S), ELBO_i then against frame i (no gradient flows to the frames).  A training forward
-        always starts from the initial posterior: ``state`` is refused (no truncated back-propagation across calls).
+        (B, 3, S, S) or a clip (B, T+1, 3, S, S), ELBO_i then against frame i (no gradient flows to the frames).
+
+        ``state``: a tuple (post_mean, post_logvar, h, c) as ``refinement_state()`` returns it (h / c also as the reference's (B * K,
+        MLP_UNITS) of ``lstm_hidden``): evaluation 0 samples from the given lambda and the LSTM starts from (h, c) instead of the initial
+        posterior and zeros; the call still makes T + 1 evaluations.  T = 4 equals T = 2 followed by T = 2 from the state, evaluation by
+        evaluation and bit for bit, given the matching slices of ``x`` and ``eps``; the boundary frame is evaluated by both calls, so the
+        continuing call usually runs with ``iter_weights[0] = 0`` (``iodine_amd.engine.clip_backward`` does all of this).  Detached
+        tensors give truncated back-propagation through time.  Tensors that require grad (under grad mode) receive their gradient from
+        ``backward()``: d / d (h, c) through all T iterations, d / d lambda through evaluation 0 alone (lambda_1 = detach(lambda_0) +
+        delta_0, iodine.py:642-643).  ``posterior.init_mean / init_logvar`` are not part of such a forward and get ``None`` from autograd.
+
+        ``keep_state=True``: ``model.refinement_state()`` after the call returns detached clones of (lambda_T, h_T, c_T) - the ``state``
+        of the next chunk (two small copies, made only then).  Without it a training forward leaves no state to fetch, as before.
 
         ``attach_state=True`` (with grad mode on; under ``torch.no_grad()`` it changes nothing): ``model.z``, ``model.mean``,
-        ``model.mask``, ``model.mask_logits``, ``model.posterior.mean`` and ``model.posterior.logvar`` - the state of the final ELBO
-        evaluation (of a clip: frame T) - carry the autograd graph like in the reference (iodine.py:137,171-187,642-651), so auxiliary
-        terms on them (a supervised mask loss, a probe on ``z``, a slot regulariser) train the decoder and, back through all T
-        iterations, the refinement network: ``(loss + aux).backward()``.  The values are the same bits as without it; the logger entries
-        stay detached.  The library keeps ONE saved forward and its backward consumes it: sum the terms first and call ``backward()``
-        once - a second one (``aux.backward()`` followed by ``loss.backward()``) raises the stale-forward error.  A batch above
-        ``max_batch(training=True)`` is refused: its chunks' backward passes run inside the forward."""
-        if state is not None:
-            raise RuntimeError('IODINE.forward takes no state=: a training forward starts from the initial posterior (continuing one '
-                               'across calls would need back-propagation through the earlier call); use encode / reconstruct')
-        _, T = self._run_shape()
+        ``model.mask``, ``model.mask_logits``, ``model.posterior.mean``, ``model.posterior.logvar`` - the state of the final ELBO
+        evaluation (of a clip: frame T) - and ``model.lstm_hidden`` = (h, c) after the last update, shaped (B * K, MLP_UNITS), carry the
+        autograd graph like in the reference (iodine.py:37,137,144,171-187,642-651), so auxiliary
+        terms on them (a supervised mask loss, a probe on ``z``, a slot regulariser, the cotangents of a following chunk) train the decoder
+        and, back through all T iterations, the refinement network: ``(loss + aux).backward()``.  The values are the same bits as without
+        it; the logger entries stay detached.  The library keeps ONE saved forward and its backward consumes it: sum the terms first and
+        call ``backward()`` once - a second one (``aux.backward()`` followed by ``loss.backward()``) raises the stale-forward error.
+
+        A batch above ``max_batch(training=True)`` runs in chunks, each chunk's backward inside the forward: a detached ``state`` is sliced
+        per chunk and ``keep_state`` gathers the chunks' states; ``attach_state`` and a ``state`` that requires grad are refused there."""
+        K, T = self._run_shape()
         self._read_objective(T)                      # (refusals before any device work; _train_forward hands it to the handle)
-        x, _ = self._check_frames(x, T + 1, 'forward')
+        x, _ = self._check_frames(x, T + 1, 'forward' if state is None else 'forward from a state')
+        B = x.shape[0]
+        state = self._check_train_state(state, B, K, x.device)
         self._state = None                          # the state of an earlier encode / reconstruct ends here (refinement_state)
         attach = bool(attach_state) and torch.is_grad_enabled()
-        if x.shape[0] > self.max_batch(training=True):
-            if attach:
-                raise RuntimeError(f'IODINE.forward(attach_state=True): a batch of {x.shape[0]} images exceeds max_batch(training=True) = '
-                                   f'{self.max_batch(training=True)}; such a batch runs in chunks, each chunk\'s backward inside the forward, '
-                                   'which leaves nothing for auxiliary cotangents to back-propagate through - use a smaller batch per call')
-            loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, *self._ordered_params())
+        state_grad = state is not None and torch.is_grad_enabled() and any(t.requires_grad for t in state)
+        if B > self.max_batch(training=True):
+            for on, what in ((attach, 'attach_state=True'), (state_grad, 'a state that requires grad')):
+                if on:
+                    raise RuntimeError(f'IODINE.forward({what}): a batch of {B} images exceeds max_batch(training=True) = '
+                                       f'{self.max_batch(training=True)}; such a batch runs in chunks, each chunk\'s backward inside the forward, '
+                                       'which leaves nothing for cotangents that arrive later to back-propagate through - use a smaller '
+                                       'batch per call')
+            if state is not None:
+                state = tuple(t.detach() for t in state)
+            loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, state, bool(keep_state), *self._ordered_params())
             self.elbo_terms = elbo_iter
             return loss
-        eps = self._eps(eps, x.shape[0], x.device)
+        eps = self._eps(eps, B, x.device)
         if attach:
-            (loss, elbo_iter, self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean,
-             self.posterior.logvar) = _TrainStepAttached.apply(self, x, eps, *self._ordered_params())
+            (loss, elbo_iter, self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc
+             ) = _TrainStepAttached.apply(self, x, eps, True, *(state or (None,) * 4), *self._ordered_params())
+            self.lstm_hidden = (lh, lc)
+        elif state is not None:
+            loss, elbo_iter = _TrainStepAttached.apply(self, x, eps, False, *state, *self._ordered_params())
         else:
             loss, elbo_iter = _TrainStep.apply(self, x, eps, *self._ordered_params())
         self.elbo_terms = elbo_iter
@@ -1080,13 +1142,25 @@ class IODINE(nn.Module):
             h, dev = self._handle, x.device
             if not attach:
                 self._fetch_last_elbo(h, x, elbo_iter[-1])                             # final elbo(): iodine.py:226-239 (a clip: its last frame)
-                self._fetch_posterior(h, x.shape[0], dev)
+                self._fetch_posterior(h, B, dev)
+            if keep_state:
+                hc = (t.detach().view(B, K, -1) for t in self.lstm_hidden) if attach else self._fetch_train_state(B, dev)
+                self._state = _RefineState(self.posterior.mean.detach(), self.posterior.logvar.detach(), *hc)
             stats = torch.empty((2,), device=dev, dtype=torch.float32)
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_logger_scalars(h, self._stream(), _lib.ptr(stats)), h))
             logger.update(init_mean=stats[0], init_logvar=stats[1])                    # iodine.py:156-157
         return loss
 
-    def _train_forward(self, x, eps):
+    def _fetch_train_state(self, B, dev):
+        """(h, c) (B, K, MLP_UNITS) after the last update of the training forward that just ran (iodine_last_train_state)."""
+        hh = torch.empty((B, self.K, int(self._cfg.ref_mlp_units)), device=dev, dtype=torch.float32)
+        cc = torch.empty_like(hh)
+        h = self._handle
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_last_train_state(h, self._stream(), B, _lib.ptr(hh), _lib.ptr(cc)),
+                                             h, 'iodine_last_train_state'))
+        return hh, cc
+
+    def _train_forward(self, x, eps, state=None):
         dev, B = x.device, x.shape[0]
         K, T = self._run_shape()
         obj = self._read_objective(T)
@@ -1097,21 +1171,29 @@ class IODINE(nn.Module):
         elbo_iter = self._out('t.elbo', (T + 1, 3), dev)
         xs, eps = self._stage('x', x), self._stage('eps', eps)
         self._call_serial += 1
-        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward(h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps),
-                                                                             _lib.ptr(loss), _lib.ptr(elbo_iter)),
-                                             h, 'iodine_train_forward'))
+        if state is None:
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward(h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps),
+                                                                                 _lib.ptr(loss), _lib.ptr(elbo_iter)),
+                                                 h, 'iodine_train_forward'))
+        else:
+            # (graph mode: the state goes through persistent staging buffers like reconstruct's, so the graph key repeats)
+            st = [self._stage('ts.' + n, t.detach()) for n, t in zip(('pm', 'plv', 'h', 'c'), state)]
+            ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in st])
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward_seq(
+                h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), ptrs, _lib.ptr(loss), _lib.ptr(elbo_iter)), h, 'iodine_train_forward_seq'))
         return self._own(loss), self._own(elbo_iter)
 
-    def _train_chunked(self, x, eps):
+    def _train_chunked(self, x, eps, state=None, keep_state=False):
         """Forward + backward of every chunk (see _ChunkedTrainStep): returns the batch loss, the (T+1, 3) ELBO terms of the whole
-        batch and d loss / d parameters as one flat buffer in named_parameters() order."""
+        batch and d loss / d parameters as one flat buffer in named_parameters() order.  ``state``: a detached initial state, cut along
+        the batch; ``keep_state``: every chunk's LSTM state is copied out for ``refinement_state``."""
         dev, B = x.device, x.shape[0]
         flat = self._out('t.flat', (sum(p.numel() for p in self._ordered_params()),), dev)
-        loss, terms, parts, sizes, pms, plvs = None, None, [], [], [], []
+        loss, terms, parts, sizes, pms, plvs, hcs = None, None, [], [], [], [], []
         for c, (s, e) in enumerate(self._chunks(B, self.max_batch(training=True))):
             xc = x[s:e].contiguous()
             ec = self._eps(None if eps is None else eps[:, s:e], e - s, dev)
-            lc, tc = self._train_forward(xc, ec)
+            lc, tc = self._train_forward(xc, ec, None if state is None else tuple(t[s:e].contiguous() for t in state))
             h = self._handle
             w = torch.full((), (e - s) / float(B), device=dev, dtype=torch.float32)
             ws = self._stage('t.gl', w)
@@ -1121,6 +1203,8 @@ class IODINE(nn.Module):
                 self._fetch_last_elbo(h, xc, tc[-1])
                 self._fetch_posterior(h, e - s, dev)
                 pms.append(self.posterior.mean); plvs.append(self.posterior.logvar)
+                if keep_state:
+                    hcs.append(self._fetch_train_state(e - s, dev))
                 self.elbo_terms = tc
                 parts.append(self._chunk_state()); sizes.append(e - s)
                 if c == 0:
@@ -1132,6 +1216,9 @@ class IODINE(nn.Module):
         with torch.no_grad():
             self._merge_chunk_state(parts, sizes, x)
             self.posterior.mean, self.posterior.logvar = torch.cat(pms, 0), torch.cat(plvs, 0)
+            if keep_state:
+                self._state = _RefineState(self.posterior.mean, self.posterior.logvar, torch.cat([hc[0] for hc in hcs], 0),
+                                           torch.cat([hc[1] for hc in hcs], 0))
         return loss, self.elbo_terms, self._own(flat)
 
     def _train_backward(self, grad_loss, serial, aux=None):
@@ -1163,6 +1250,34 @@ class IODINE(nn.Module):
             views.append(flat[off:off + n].view_as(p))
             off += n
         return views
+
+    def _train_backward_seq(self, grad_loss, serial, aux, hc, want, BK):
+        """iodine_train_backward_seq for the saved forward ``serial``: ``aux`` as for ``_train_backward``, ``hc`` = cotangents on the LSTM
+        state after the last update ((B * K, H) or None each), ``want`` = which of d / d (post_mean, post_logvar, h, c) of the initial
+        state to return.  -> (per-parameter views, the four state gradients or None each)."""
+        if serial != self._call_serial:
+            raise RuntimeError(self._STALE.format('forward'))
+        h, dev = self._handle, self._handle_device
+        B, K = BK
+        L, H = self.dim_latent, int(self._cfg.ref_mlp_units)
+        params = self._ordered_params()
+        flat = self._out('t.flat', (sum(p.numel() for p in params),), dev)
+        as_f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        gl = None if grad_loss is None else self._stage('t.gl', as_f32(grad_loss))
+        names = ('a.mean', 'a.mask', 'a.logits', 'a.z', 'a.pm', 'a.plv', 'a.h', 'a.c')
+        cs = [None if g is None else self._stage(n, as_f32(g)) for n, g in zip(names, tuple(aux) + tuple(hc))]
+        outs = [self._out('ts.g' + n, shp, dev) if w else None
+                for n, shp, w in zip(('pm', 'plv', 'h', 'c'), ((B, K, L), (B, K, L), (B, K, H), (B, K, H)), want)]
+        gptrs = (C.c_void_p * 4)(*[None if t is None else t.data_ptr() for t in outs]) if any(want) else None
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_seq(
+            h, self._stream(), _lib.ptr(gl), *[_lib.ptr(c) for c in cs], _lib.ptr(flat), 0, gptrs), h, 'iodine_train_backward_seq'))
+        self._call_serial += 1                      # the saved forward is consumed (no retain_graph)
+        flat = self._own(flat)
+        views, off = [], 0
+        for p in params:
+            views.append(flat[off:off + p.numel()].view_as(p))
+            off += p.numel()
+        return views, tuple(self._own(t) for t in outs)
 
 
 def arch_namespace(dim_latent, iters, slots, img_size, ref, dec, sigma=0.10, layernorm=True,
