@@ -466,16 +466,34 @@ int iodine_op_conv3x3_wgrad(void* stream, const float* in_nhwc, const float* d_n
 int iodine_op_conv3x3_wgrad_f32(void* stream, const float* in_nhwc, const float* d_nhwc, float* gw_oihw, float* gb, int n,
                                 int s, int c);
 
-/* the generic path's convolution (kernel size k in {3, 5, 7}, stride s in {1, 2} -- the library itself runs REF.STRIDE 1..8 through the
- * same launchers, this entry point takes the two it is tested at; kernels_generic.hip / kernels_gens2.hip), one
+/* the generic path's convolution (kernel size k in {3, 5, 7}, stride s in 1..8 as REF.STRIDE may be: s = 1 on the stride-1 MFMA kernels
+ * of kernels_generic.hip, s = 2 on kernels_gens2.hip, s >= 3 and what neither covers on the scalar kernels -- the launchers the library runs), one
  * direction per call - mode 0: out_nhwc [n][so][so][co] = act(bias + conv(in_nhwc [n][si][si][ldc], w_oihw [co][ci][k][k])), elu = 1
- * applies ELU; mode 1: out_nhwc [n][si][si][ci] = ELU'(aux) * data gradient of the gradient in_nhwc [n][so][so][co]; mode 2: weight +
+ * applies ELU; mode 1: out_nhwc [n][si][si][ldc] = ELU'(aux [n][si][si][ldc]) * data gradient of the gradient in_nhwc [n][so][so][co], the first
+ * ci channels of every pixel (the rest is neither read nor written), with w_oihw [co][ldc][k][k] in this mode; mode 2: weight +
  * bias gradient of (in_nhwc, aux = gradient [n][so][so][co]) ADDED to out_nhwc = gw [co][ci][k][k] and gb [co].  so = (si - 1) / s + 1.
  * Modes 0 / 2, tests only: elu | 0x100 | (mask << 9) hands the kernels the per-channel mask of input channels that can be non-zero (bit c =
  * channel c; ci <= 22), as the library does for the first refinement layer of an ARCH.ENCODING subset - channel groups that are zero in
  * the input AND the weights are skipped; the result must equal the unmasked call. */
 int iodine_op_gen_conv(void* stream, int mode, const float* in_nhwc, const float* w_oihw, const float* bias, const float* aux,
                        float* out_nhwc, float* gb, int n, int si, int ci, int ldc, int co, int k, int s, int elu);
+
+/* which kernel iodine_op_gen_conv (= the library, through the same launchers) runs for these arguments: host arithmetic only, no HIP call,
+ * no GPU needed.  Returns tier | np << 8 | seg << 16, or -1 for arguments iodine_op_gen_conv rejects.  tier, modes 0 / 1: 0 / 1 / 2 = the stride-1 MFMA
+ * kernel with 16- / 8- / 4-channel chunks, 3 = the stride-2 MFMA kernels, 4 = the scalar kernels; mode 2: 5 = the GEMM form of a
+ * 4-output-channel conv (np = its NP instantiation 1 / 2 / 4 / 8, otherwise 0), 6 = the row-staged form, 7 = the per-tap MFMA form,
+ * 3 = stride-2 MFMA, 4 = scalar.  seg, modes 0 / 1: 0 = every output is one fp32 fmaf chain over its products (up to 1600 of them: 5 x 5 x 64
+ * channels); otherwise the chain is summed in segments of about 800 products and seg is the segment length, in staged chunks (MFMA kernel)
+ * or products (scalar kernels).  The kernel-level tests assert the tier each of their cases is meant to hit. */
+int iodine_op_gen_conv_tier(int mode, int si, int ci, int ldc, int co, int k, int s);
+
+/* the generic path's spatial-broadcast layer (kernels_genl0.hip: SpatialBroadcast + the first decoder conv without the broadcast tensor),
+ * kernel-level tests only -- it packs w_oihw [co][L + 2][k][k] (input channels: L latents, then the x and the y coordinate plane), builds
+ * the coordinates with iodine_linspace_host, allocates, synchronises and frees per call.  mode 0: out [n][s][s][co] = ELU(bias + conv) of
+ * z [n][L] broadcast over s x s (odd k <= 7, padding k / 2).  mode 1: dpre [n][s][s][co] = gradient wrt the pre-activation -> dz [n][ld]
+ * (L entries per row written, ld >= L), and gw [co][L + 2][k][k] += alpha dW, gb [co] += alpha db; alpha = 0 leaves gw / gb alone. */
+int iodine_op_gen_l0(void* stream, int mode, const float* z, const float* w_oihw, const float* bias, const float* dpre, float* out,
+                     float* gw, float* gb, float* dz, int n, int L, int s, int co, int k, int ld, float alpha);
 
 /* the split-fp16 form of the same (kernels_gensplit.hip, option gen_conv_precision 1), same arguments: mode 0 forward, mode 1 data
  * gradient x ELU'(aux), mode 2 weight + bias gradient ADDED to out_nhwc = gw and gb.  IODINE_ERR_INVALID -- never the fp32 kernel -- for

@@ -24,6 +24,7 @@ EXPORTS = (
     'iodine_train_forward', 'iodine_train_backward', 'iodine_train_backward_flat', 'iodine_logger_scalars',
     'iodine_adam_step', 'iodine_ari_table', 'iodine_set_option', 'iodine_profile_read', 'iodine_debug_copy', 'iodine_linspace_host', 'iodine_op_conv3x3', 'iodine_op_dec_out',
     'iodine_op_conv3x3_wgrad', 'iodine_op_conv3x3_wgrad_f32', 'iodine_op_dec_out_f16x3', 'iodine_op_gen_conv', 'iodine_op_gen_conv_f16x3',
+    'iodine_op_gen_conv_tier', 'iodine_op_gen_l0',
     'iodine_grad_norm_scratch_bytes', 'iodine_grad_norm', 'iodine_grad_scale', 'iodine_adam_step_clipped',
     'iodine_decode_backward', 'iodine_elbo_backward', 'iodine_op_render_bwd',
     'iodine_set_frames', 'iodine_reconstruct_seq', 'iodine_last_refine_state',
@@ -116,6 +117,9 @@ def lib() -> C.CDLL:
         L.iodine_op_gen_conv.argtypes = [vp, ci] + [vp] * 6 + [ci] * 8
     if hasattr(L, 'iodine_op_gen_conv_f16x3'):
         L.iodine_op_gen_conv_f16x3.argtypes = [vp, ci] + [vp] * 6 + [ci] * 8
+    if hasattr(L, 'iodine_op_gen_conv_tier'):           # (kernel-level tests of the generic stride-1 convs and broadcast layer; absent from older A/B builds)
+        L.iodine_op_gen_conv_tier.argtypes = [ci] * 7
+        L.iodine_op_gen_l0.argtypes = [vp, ci] + [vp] * 8 + [ci] * 6 + [cf]
     if hasattr(L, 'iodine_op_conv3x3_wgrad_f32'):       # (absent from older builds loaded through IODINE_HIP_LIB for same-box A/B)
         L.iodine_op_conv3x3_wgrad_f32.argtypes = [vp] + [vp] * 4 + [ci] * 3
     if hasattr(L, 'iodine_set_frames'):                 # (video input / resumable refinement; absent from older A/B builds)

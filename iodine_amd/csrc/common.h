@@ -371,6 +371,18 @@ constexpr int GEN_WGRAD_SLICES = 64;
 constexpr int GEN_WGRAD_OUT_SLICES_MAX = 512;   // row slices of the 4-output-channel GEMM form (one per resident block)
 constexpr int GEN_WGRAD_SLICES_MAX = 128;  // the row-staged form sizes its slices to the chip (two blocks per CU): scratch is sized for this many
 hipError_t launch_gen_pack_weights(hipStream_t st, const float* w, int Co, int Ci, int k, float* wt);
+// the kernel a generic conv runs on (gen_conv_tier: the launchers switch on it, iodine_op_gen_conv_tier reports it to the tests).  Forward and
+// data gradient: MFMA_CCH16 / 8 / 4 (stride-1 MFMA kernel by chunk width), S2_MFMA, SCALAR; weight gradient: WGRAD_OUT (np = its NP
+// instantiation 1 / 2 / 4 / 8), WGRAD_ROWS, WGRAD_MFMA, S2_MFMA, SCALAR.  The values are part of the C ABI (include/iodine_hip.h).
+enum GenTier { GEN_TIER_MFMA_CCH16 = 0, GEN_TIER_MFMA_CCH8 = 1, GEN_TIER_MFMA_CCH4 = 2, GEN_TIER_S2_MFMA = 3, GEN_TIER_SCALAR = 4,
+               GEN_TIER_WGRAD_OUT = 5, GEN_TIER_WGRAD_ROWS = 6, GEN_TIER_WGRAD_MFMA = 7 };
+// seg: an output of the forward / data gradient is ONE fp32 fmaf chain over its Ck k^2 products, whose rounding grows with the chain; chains
+// of more than GEN_CHAIN_MAX products (the default decoder's 5 x 5 x 64 stays one chain: its results do not change) are summed in nseg =
+// ceil(products / GEN_CHAIN_SEG) segments that are added at the end.  seg = the segment length - staged chunks (MFMA kernel) or products
+// (scalar kernels) -, 0 = one chain.
+constexpr int GEN_CHAIN_MAX = 1600, GEN_CHAIN_SEG = 800;
+struct GenTierSel { GenTier tier; int np; size_t lds; int seg; };  // lds: dynamic LDS bytes of the chosen kernel (0: none)
+GenTierSel gen_conv_tier(int mode, int Si, int Ci, int ldc, int Co, int k, int s);
 // chmask (stride-2 MFMA forms only): bit c = input channel c can be non-zero - groups of channels whose weights AND inputs are zero (an
 // ARCH.ENCODING subset: absent encoding channels) are skipped; all ones = every channel
 hipError_t launch_gen_conv_fwd(hipStream_t st, const float* in, const float* wt, const float* bias, float* out, int N, int Si, int Ci,

@@ -263,7 +263,7 @@ int iodine_op_gen_conv(void* stream, int mode, const float* in, const float* w, 
                        int n, int si, int ci, int ldc, int co, int k, int s, int elu)
 {
     hipStream_t st = (hipStream_t)stream;
-    if (mode < 0 || mode > 2 || (s != 1 && s != 2) || (k != 3 && k != 5 && k != 7) || ldc < ci) { g_create_error = "iodine_op_gen_conv: argument"; return IODINE_ERR_INVALID; }
+    if (mode < 0 || mode > 2 || s < 1 || s > 8 || (k != 3 && k != 5 && k != 7) || ldc < ci) { g_create_error = "iodine_op_gen_conv: argument"; return IODINE_ERR_INVALID; }
     // tests only: elu bit 8 set = bits 9.. carry a per-channel mask of the input channels that can be non-zero (what the library hands
     // the stride-2 kernels for an ARCH.ENCODING subset: all-zero 4- / 16-channel groups are skipped) - the masked form must equal the plain one
     const unsigned chmask = (elu & 0x100) ? ((unsigned)elu >> 9) : 0xffffffffu;
@@ -277,8 +277,7 @@ int iodine_op_gen_conv(void* stream, int mode, const float* in, const float* w, 
         e = launch_gen_pack_weights(st, w, co, ci, k, buf);
         if (e == hipSuccess) e = launch_gen_conv_fwd(st, in, buf, bias, out, n, si, ci, ldc, co, k, s, elu, chmask);
     } else if (mode == 1) {
-        if (ci != ldc) { (void)hipFree(buf); g_create_error = "iodine_op_gen_conv: mode 1 needs ldc == ci"; return IODINE_ERR_INVALID; }
-        e = launch_gen_pack_weights(st, w, co, ci, k, buf);
+        e = launch_gen_pack_weights(st, w, co, ldc, k, buf);    // (w has ldc input channels here: ci of them are computed)
         if (e == hipSuccess) e = launch_gen_conv_dgrad(st, in, buf, aux, out, n, si, ci, ldc, co, k, s);
     } else {
         e = launch_gen_conv_wgrad(st, in, aux, buf + wfl, n, si, ci, ldc, ci, co, k, s, 1.f, out, gb, chmask);
@@ -286,6 +285,48 @@ int iodine_op_gen_conv(void* stream, int mode, const float* in, const float* w, 
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(buf);
     if (e != hipSuccess) { g_create_error = std::string("iodine_op_gen_conv: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_op_gen_conv_tier(int mode, int si, int ci, int ldc, int co, int k, int s)
+{
+    // (host arithmetic only: runs without a GPU)
+    if (mode < 0 || mode > 2 || si < 1 || ci < 1 || co < 1 || s < 1 || s > 8 || (k != 3 && k != 5 && k != 7) || ldc < ci) return -1;
+    const GenTierSel sel = gen_conv_tier(mode, si, ci, ldc, co, k, s);
+    return (int)sel.tier | (sel.np << 8) | (sel.seg << 16);
+}
+
+int iodine_op_gen_l0(void* stream, int mode, const float* z, const float* w, const float* bias, const float* dpre, float* out, float* gw,
+                     float* gb, float* dz, int n, int L, int s, int co, int k, int ld, float alpha)
+{
+    hipStream_t st = (hipStream_t)stream;
+    // (kernel-level tests only: allocates and frees its scratch around the launches and synchronises - not an entry point to time)
+    if (mode < 0 || mode > 1 || n < 1 || L < 1 || s < 1 || co < 1 || k < 1 || k > GEN_L0_KMAX || k % 2 == 0 || !z || !w
+        || (mode == 0 && (!bias || !out)) || (mode == 1 && (!dpre || !dz || ld < L || (alpha != 0.f && (!gw || !gb))))) {
+        g_create_error = "iodine_op_gen_l0: argument";
+        return IODINE_ERR_INVALID;
+    }
+    // (every region starts on 16 bytes, as in the library's workspace: the forward reads cterm and the prefix table with 16-byte loads)
+    const auto r4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
+    const size_t wfl = r4((size_t)k * k * (L + 2) * co), lfl = r4((size_t)s), cfl = mode == 0 ? r4((size_t)s * s * co) : 0,
+                 sfl = gen_l0_scratch_floats(n, s, co, k);
+    float* buf = nullptr;
+    if (hipMalloc((void**)&buf, (wfl + lfl + cfl + sfl) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+    float *wt = buf, *lin = wt + wfl, *cterm = lin + lfl, *scr = cterm + cfl;
+    std::vector<float> hlin((size_t)s);
+    iodine_linspace_host(s, hlin.data());
+    hipError_t e = hipMemcpyAsync(lin, hlin.data(), (size_t)s * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);         // (hlin is pageable host memory)
+    if (e == hipSuccess) e = launch_gen_pack_weights(st, w, co, L + 2, k, wt);
+    if (e == hipSuccess && mode == 0) {
+        e = launch_gen_l0_coord(st, wt, bias, lin, L, s, co, k, cterm);
+        if (e == hipSuccess) e = launch_gen_l0_fwd(st, z, wt, cterm, scr, out, n, L, s, co, k);
+    } else if (e == hipSuccess) {
+        e = launch_gen_l0_bwd(st, dpre, z, wt, lin, scr, n, L, s, co, k, alpha, gw, gb, dz, ld);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_gen_l0: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
     return IODINE_OK;
 }
 

@@ -32,7 +32,7 @@ __global__ void gen_pack_weights_kernel(const float* __restrict__ w, int Co, int
 
 // out[n][oy][ox][co] = act(bias[co] + sum_{tap, ci} in[n][oy*s + ky - pad][ox*s + kx - pad][ci] * wt[tap][ci][co])
 __global__ void gen_conv_fwd_kernel(const float* __restrict__ in, const float* __restrict__ wt, const float* __restrict__ bias,
-                                    float* __restrict__ out, int Si, int So, int Ci, int ldc, int Co, int k, int s, int elu, size_t total)
+                                    float* __restrict__ out, int Si, int So, int Ci, int ldc, int Co, int k, int s, int elu, int seg, size_t total)
 {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
@@ -42,7 +42,8 @@ __global__ void gen_conv_fwd_kernel(const float* __restrict__ in, const float* _
     const int oy = (int)(r % So);
     const size_t n = r / So;
     const int pad = k / 2;
-    float acc = bias ? bias[co] : 0.f;
+    float acc = bias ? bias[co] : 0.f, tot = 0.f;              // seg != 0: a long chain in segments of seg products (common.h, GenTierSel)
+    int cnt = 0;
     for (int ky = 0; ky < k; ++ky) {
         const int iy = oy * s + ky - pad;
         if (iy < 0 || iy >= Si) continue;
@@ -51,9 +52,13 @@ __global__ void gen_conv_fwd_kernel(const float* __restrict__ in, const float* _
             if (ix < 0 || ix >= Si) continue;
             const float* ip = in + ((n * Si + iy) * Si + ix) * (size_t)ldc;
             const float* wp = wt + ((size_t)(ky * k + kx) * Ci) * Co + co;
-            for (int ci = 0; ci < Ci; ++ci) acc = fmaf(ip[ci], wp[(size_t)ci * Co], acc);
+            for (int ci = 0; ci < Ci; ++ci) {
+                acc = fmaf(ip[ci], wp[(size_t)ci * Co], acc);
+                if (seg && ++cnt == seg) { tot += acc; acc = 0.f; cnt = 0; }
+            }
         }
     }
+    if (seg) acc += tot;
     out[idx] = elu ? gen_elu(acc) : acc;
 }
 
@@ -61,7 +66,7 @@ __global__ void gen_conv_fwd_kernel(const float* __restrict__ in, const float* _
 // aux = the layer's INPUT activation (an ELU output): f' = aux > 0 ? 1 : aux + 1; aux = NULL: no factor.  ldi = channel stride of din
 // = input channels of the PACKED weight; Ci <= ldi channels are computed (the broadcast layer needs only its L latent channels).
 __global__ void gen_conv_dgrad_kernel(const float* __restrict__ dout, const float* __restrict__ wt, const float* __restrict__ aux,
-                                      float* __restrict__ din, int Si, int So, int Ci, int ldi, int Co, int k, int s, size_t total)
+                                      float* __restrict__ din, int Si, int So, int Ci, int ldi, int Co, int k, int s, int seg, size_t total)
 {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
@@ -71,7 +76,8 @@ __global__ void gen_conv_dgrad_kernel(const float* __restrict__ dout, const floa
     const int y = (int)(r % Si);
     const size_t n = r / Si;
     const int pad = k / 2;
-    float acc = 0.f;
+    float acc = 0.f, tot = 0.f;                                // seg != 0: a long chain in segments of seg products (common.h, GenTierSel)
+    int cnt = 0;
     for (int ky = 0; ky < k; ++ky) {
         const int ty = y + pad - ky;
         if (ty < 0 || ty % s != 0 || ty / s >= So) continue;
@@ -80,9 +86,13 @@ __global__ void gen_conv_dgrad_kernel(const float* __restrict__ dout, const floa
             if (tx < 0 || tx % s != 0 || tx / s >= So) continue;
             const float* dp = dout + ((n * So + ty / s) * So + tx / s) * (size_t)Co;
             const float* wp = wt + ((size_t)(ky * k + kx) * ldi + ci) * Co;
-            for (int co = 0; co < Co; ++co) acc = fmaf(dp[co], wp[co], acc);
+            for (int co = 0; co < Co; ++co) {
+                acc = fmaf(dp[co], wp[co], acc);
+                if (seg && ++cnt == seg) { tot += acc; acc = 0.f; cnt = 0; }
+            }
         }
     }
+    if (seg) acc += tot;
     const size_t o = ((n * Si + y) * Si + x) * (size_t)ldi + ci;
     if (aux) { const float a = aux[o]; acc *= a > 0.f ? 1.f : a + 1.f; }
     din[o] = acc;
@@ -170,11 +180,13 @@ __device__ unsigned g_gen_prof[TP_MAXBLK * 8];
 __device__ unsigned g_genw_prof[TP_MAXBLK * 8];
 #endif
 
-template <int KS, int CCH>                                     // CCH: reduction channels per staged chunk (16, 8 or 4: the largest that fits the LDS)
+// SPLIT: the reduction is summed in segments of `seg` chunks (chains of more than GEN_CHAIN_MAX products, common.h); the plain instantiation
+// is the kernel as it was
+template <int KS, int CCH, bool SPLIT>                         // CCH: reduction channels per staged chunk (16, 8 or 4: the largest that fits the LDS)
 __global__ __launch_bounds__(256)
 void gen_conv_mfma_kernel(const float* __restrict__ in, const float* __restrict__ wt, const float* __restrict__ bias,
                           const float* __restrict__ aux, float* __restrict__ out, int S, int Ck, int ldin, int Cn, int ldout,
-                          int flip, int sT, int sK, int sN, int elu, int ncg, int tiles, int ntiles)
+                          int flip, int sT, int sK, int sN, int elu, int ncg, int tiles, int ntiles, int seg)
 {
     constexpr int KK = KS * KS, PAD = KS / 2, TW = 16 + KS - 1, NPX = TW * TW;
     // Round 5: the staged chunk is CHANNEL-major, one plane of NPXP floats per channel with NPXP = 16 (mod 32): the 16 pixels x 4 channels a
@@ -270,9 +282,10 @@ void gen_conv_mfma_kernel(const float* __restrict__ in, const float* __restrict_
             d[2 * NPXP] = __uint_as_float(rin[i].z); d[3 * NPXP] = __uint_as_float(rin[i].w);
         }
     };
-    f32x4 acc[4];
+    f32x4 acc[4], tot[4];                                      // tot (SPLIT): the finished segments of the tile
 #pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int r = 0; r < 4; ++r) { acc[r] = f32x4{0.f, 0.f, 0.f, 0.f}; tot[r] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    int cseg = 0;
     // ---- deferred epilogue: the finished tile's accumulators, store offsets and (data gradient) the activation-derivative operand; the
     // arithmetic and the stores are issued between the MFMAs of the next tile's first k-step (block's first tile: every offset is "outside") ----
     const bool vec_all = (ldout & 3) == 0 && (Cn & 3) == 0;   // 16-byte stores for every lane (else: the plain epilogue at the end of the tile)
@@ -429,6 +442,17 @@ void gen_conv_mfma_kernel(const float* __restrict__ in, const float* __restrict_
         TP_STAMP(3);
         __syncthreads();
         TP_STAMP(5);
+        if constexpr (SPLIT) {                                 // (uniform; outside the hand-scheduled k-steps)
+            if (last_chunk) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { acc[r] += tot[r]; tot[r] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+                cseg = 0;
+            } else if (++cseg == seg) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { tot[r] += acc[r]; acc[r] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+                cseg = 0;
+            }
+        }
         if (last_chunk) {
             if (DEFER && vec_all) retire_tile(t);
             else {
@@ -837,35 +861,37 @@ hipError_t gen_wgrad_out_launch_np(hipStream_t st, const float* in, const float*
     return hipGetLastError();
 }
 template <int KS>
-hipError_t gen_wgrad_out_launch_ks(hipStream_t st, const float* in, const float* g, float* part, int N, int S, int Ci, int ldc, int nsl, int np4,
+hipError_t gen_wgrad_out_launch_ks(hipStream_t st, const float* in, const float* g, float* part, int N, int S, int Ci, int ldc, int nsl, int np,
                                    size_t lds)
 {
-    if (np4 <= 1) return gen_wgrad_out_launch_np<KS, 1>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
-    if (np4 <= 2) return gen_wgrad_out_launch_np<KS, 2>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
-    if (np4 <= 4) return gen_wgrad_out_launch_np<KS, 4>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
-    return gen_wgrad_out_launch_np<KS, 8>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
+    switch (np) {
+    case 1: return gen_wgrad_out_launch_np<KS, 1>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
+    case 2: return gen_wgrad_out_launch_np<KS, 2>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
+    case 4: return gen_wgrad_out_launch_np<KS, 4>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
+    default: return gen_wgrad_out_launch_np<KS, 8>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
+    }
 }
 inline hipError_t gen_wgrad_out_launch(hipStream_t st, const float* in, const float* g, float* part, int N, int S, int Ci, int ldc, int k, int nsl,
-                                       int np4, size_t lds)
+                                       int np, size_t lds)
 {
-    if (k == 3) return gen_wgrad_out_launch_ks<3>(st, in, g, part, N, S, Ci, ldc, nsl, np4, lds);
-    if (k == 5) return gen_wgrad_out_launch_ks<5>(st, in, g, part, N, S, Ci, ldc, nsl, np4, lds);
-    return gen_wgrad_out_launch_ks<7>(st, in, g, part, N, S, Ci, ldc, nsl, np4, lds);
+    if (k == 3) return gen_wgrad_out_launch_ks<3>(st, in, g, part, N, S, Ci, ldc, nsl, np, lds);
+    if (k == 5) return gen_wgrad_out_launch_ks<5>(st, in, g, part, N, S, Ci, ldc, nsl, np, lds);
+    return gen_wgrad_out_launch_ks<7>(st, in, g, part, N, S, Ci, ldc, nsl, np, lds);
 }
 
-template <int KS, int CCH>
+template <int KS, int CCH, bool SPLIT>
 hipError_t gen_mfma_launch_cch(hipStream_t st, const float* in, const float* wt, const float* bias, const float* aux, float* out, int N, int S,
-                               int Ck, int ldin, int Cn, int ldout, int flip, int sT, int sK, int sN, int elu, size_t lds)
+                               int Ck, int ldin, int Cn, int ldout, int flip, int sT, int sK, int sN, int elu, size_t lds, int seg)
 {
     static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)gen_conv_mfma_kernel<KS, CCH>, 160 * 1024, attr_devs); e != hipSuccess) return e;
+    if (hipError_t e = iod_set_max_lds((const void*)gen_conv_mfma_kernel<KS, CCH, SPLIT>, 160 * 1024, attr_devs); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int ncg = (Cn + 15) / 16, tiles = (S + 15) / 16, ntiles = N * tiles * tiles;
     const int per_cu = lds <= 80 * 1024 ? 2 : 1;
     const int nb = std::max(1, std::min(ntiles, per_cu * n_cu / ncg));
-    hipLaunchKernelGGL((gen_conv_mfma_kernel<KS, CCH>), dim3(ncg * nb), dim3(256), lds, st, in, wt, bias, aux, out, S, Ck, ldin, Cn, ldout, flip,
-                       sT, sK, sN, elu, ncg, tiles, ntiles);
+    hipLaunchKernelGGL((gen_conv_mfma_kernel<KS, CCH, SPLIT>), dim3(ncg * nb), dim3(256), lds, st, in, wt, bias, aux, out, S, Ck, ldin, Cn, ldout,
+                       flip, sT, sK, sN, elu, ncg, tiles, ntiles, seg);
 #ifdef IODINE_TILE_PROF
     if (getenv("IODINE_GEN_PROF")) {
         const int nbk = std::min(ncg * nb, TP_MAXBLK);
@@ -884,21 +910,69 @@ hipError_t gen_mfma_launch_cch(hipStream_t st, const float* in, const float* wt,
     return hipGetLastError();
 }
 
-template <int KS>
-hipError_t gen_mfma_launch(hipStream_t st, const float* in, const float* wt, const float* bias, const float* aux, float* out, int N, int S,
-                           int Ck, int ldin, int Cn, int ldout, int flip, int sT, int sK, int sN, int elu, size_t lds)
+template <int KS, bool SPLIT>
+hipError_t gen_mfma_launch_split(hipStream_t st, const float* in, const float* wt, const float* bias, const float* aux, float* out, int N, int S,
+                                 int Ck, int ldin, int Cn, int ldout, int flip, int sT, int sK, int sN, int elu, const GenTierSel& sel)
 {
-    switch (gen_mfma_cch(KS, Ck, 1)) {
-    case 16:
-        if constexpr (KS < 7) return gen_mfma_launch_cch<KS, 16>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, lds);
+    switch (sel.tier) {
+    case GEN_TIER_MFMA_CCH16:
+        if constexpr (KS < 7)
+            return gen_mfma_launch_cch<KS, 16, SPLIT>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel.lds, sel.seg);
         return hipErrorInvalidValue;
-    case 8: return gen_mfma_launch_cch<KS, 8>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, lds);
-    default: return gen_mfma_launch_cch<KS, 4>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, lds);
+    case GEN_TIER_MFMA_CCH8:
+        return gen_mfma_launch_cch<KS, 8, SPLIT>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel.lds, sel.seg);
+    default:
+        return gen_mfma_launch_cch<KS, 4, SPLIT>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel.lds, sel.seg);
     }
 }
+template <int KS>
+hipError_t gen_mfma_launch(hipStream_t st, const float* in, const float* wt, const float* bias, const float* aux, float* out, int N, int S,
+                           int Ck, int ldin, int Cn, int ldout, int flip, int sT, int sK, int sN, int elu, const GenTierSel& sel)
+{
+    if (sel.seg) return gen_mfma_launch_split<KS, true>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel);
+    return gen_mfma_launch_split<KS, false>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel);
+}
 
+inline GenTier gen_mfma_tier(int cch) { return cch == 16 ? GEN_TIER_MFMA_CCH16 : cch == 8 ? GEN_TIER_MFMA_CCH8 : GEN_TIER_MFMA_CCH4; }
 
 }  // namespace
+
+// Which kernel a generic conv runs on - the ONE place that decides it: the three launchers below switch on the result, and
+// iodine_op_gen_conv_tier hands it to the tests, which assert the tier every case is meant to hit.  Host arithmetic only (no HIP call).
+// Arguments as the launchers take them: mode 0 forward (Ci input channels with stride ldc -> Co), mode 1 data gradient (gradient of Co
+// channels -> Ci channels with stride ldc), mode 2 weight gradient.
+GenTierSel gen_conv_tier(int mode, int Si, int Ci, int ldc, int Co, int k, int s)
+{
+    GenTierSel r{GEN_TIER_SCALAR, 0, 0, 0};
+    if (mode == 0 || mode == 1) {
+        const int Ck = mode == 0 ? Ci : Co, ldin = mode == 0 ? ldc : Co;   // reduction channels and their stride
+        const int products = Ck * k * k, nseg = products > GEN_CHAIN_MAX ? (products + GEN_CHAIN_SEG - 1) / GEN_CHAIN_SEG : 1;
+        if (nseg > 1) r.seg = (products + nseg - 1) / nseg;    // scalar kernels: products per segment
+        if (const size_t lds = gen_mfma_lds(k, Ck, ldin, s)) {
+            const int cch = gen_mfma_cch(k, Ck, 1), nchunk = (Ck + cch - 1) / cch;
+            r.tier = gen_mfma_tier(cch);
+            r.lds = lds;
+            if (nseg > 1) r.seg = (nchunk + nseg - 1) / nseg;  // MFMA kernel: chunks per segment
+        } else if (s == 2 && (mode == 0 ? gen_s2_fwd_ok(k, Ci, ldc, Co) : gen_s2_dgrad_ok(k, Ci, ldc, Co)))
+            r.tier = GEN_TIER_S2_MFMA, r.seg = 0;              // stride 2 on the matrix pipe (kernels_gens2.hip, round 5): its own summation
+        return r;
+    }
+    if (s == 1 && (k == 3 || k == 5 || k == 7)) {
+        if (const size_t lds = gen_wgrad_out_lds(Si, Ci, ldc, Co, k)) {        // four output channels: GEMM form, the taps on the gradient
+            const int np4 = (npair_out(Ci, k) + 3) / 4;
+            r.tier = GEN_TIER_WGRAD_OUT;
+            r.np = np4 <= 1 ? 1 : np4 <= 2 ? 2 : np4 <= 4 ? 4 : 8;
+            r.lds = lds;
+        } else if (const size_t lds2 = gen_wgrad_rows_lds(Si, Ci, ldc, Co, k)) { // operands staged once per kernel row (round 5)
+            r.tier = GEN_TIER_WGRAD_ROWS;
+            r.lds = lds2;
+        } else
+            r.tier = GEN_TIER_WGRAD_MFMA;
+        return r;
+    }
+    if (s == 2 && gen_s2_wgrad_ok(k, Ci, ldc, Co)) r.tier = GEN_TIER_S2_MFMA;
+    return r;
+}
 
 hipError_t launch_gen_pack_weights(hipStream_t st, const float* w, int Co, int Ci, int k, float* wt)
 {
@@ -909,34 +983,40 @@ hipError_t launch_gen_pack_weights(hipStream_t st, const float* w, int Co, int C
 hipError_t launch_gen_conv_fwd(hipStream_t st, const float* in, const float* wt, const float* bias, float* out, int N, int Si, int Ci,
                                int ldc, int Co, int k, int s, int elu, unsigned chmask)
 {
-    if (const size_t lds = gen_mfma_lds(k, Ci, ldc, s)) {
+    const GenTierSel sel = gen_conv_tier(0, Si, Ci, ldc, Co, k, s);
+    switch (sel.tier) {
+    case GEN_TIER_MFMA_CCH16: case GEN_TIER_MFMA_CCH8: case GEN_TIER_MFMA_CCH4:
         // [tap][ci][co] pack: W(tap, k = ci, n = co)
-        if (k == 3) return gen_mfma_launch<3>(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, lds);
-        if (k == 5) return gen_mfma_launch<5>(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, lds);
-        return gen_mfma_launch<7>(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, lds);
-    }
-    if (s == 2 && gen_s2_fwd_ok(k, Ci, ldc, Co))         // stride 2 on the matrix pipe (kernels_gens2.hip, round 5)
+        if (k == 3) return gen_mfma_launch<3>(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, sel);
+        if (k == 5) return gen_mfma_launch<5>(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, sel);
+        return gen_mfma_launch<7>(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, sel);
+    case GEN_TIER_S2_MFMA:
         return launch_gen_s2_fwd(st, in, wt, bias, out, N, Si, Ci, ldc, Co, k, elu, chmask);
+    default: break;                                            // the scalar kernel
+    }
     const int So = (Si - 1) / s + 1;
     const size_t total = (size_t)N * So * So * Co;
-    hipLaunchKernelGGL(gen_conv_fwd_kernel, dim3(gen_blocks(total)), dim3(256), 0, st, in, wt, bias, out, Si, So, Ci, ldc, Co, k, s, elu, total);
+    hipLaunchKernelGGL(gen_conv_fwd_kernel, dim3(gen_blocks(total)), dim3(256), 0, st, in, wt, bias, out, Si, So, Ci, ldc, Co, k, s, elu, sel.seg, total);
     return hipGetLastError();
 }
 
 hipError_t launch_gen_conv_dgrad(hipStream_t st, const float* dout, const float* wt, const float* aux, float* din, int N, int Si, int Ci,
                                  int ldi, int Co, int k, int s)
 {
-    if (const size_t lds = gen_mfma_lds(k, Co, Co, s)) {
+    const GenTierSel sel = gen_conv_tier(1, Si, Ci, ldi, Co, k, s);
+    switch (sel.tier) {
+    case GEN_TIER_MFMA_CCH16: case GEN_TIER_MFMA_CCH8: case GEN_TIER_MFMA_CCH4:
         // correlation of dout with the flipped kernel: reduction over co, W(tap, k = co, n = ci) = wt[(KK - 1 - tap)][ci][co]
-        if (k == 3) return gen_mfma_launch<3>(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, lds);
-        if (k == 5) return gen_mfma_launch<5>(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, lds);
-        return gen_mfma_launch<7>(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, lds);
-    }
-    if (s == 2 && gen_s2_dgrad_ok(k, Ci, ldi, Co))
+        if (k == 3) return gen_mfma_launch<3>(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, sel);
+        if (k == 5) return gen_mfma_launch<5>(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, sel);
+        return gen_mfma_launch<7>(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, sel);
+    case GEN_TIER_S2_MFMA:
         return launch_gen_s2_dgrad(st, dout, wt, aux, din, N, Si, Ci, ldi, Co, k);
+    default: break;                                            // the scalar kernel
+    }
     const int So = (Si - 1) / s + 1;
     const size_t total = (size_t)N * Si * Si * Ci;
-    hipLaunchKernelGGL(gen_conv_dgrad_kernel, dim3(gen_blocks(total)), dim3(256), 0, st, dout, wt, aux, din, Si, So, Ci, ldi, Co, k, s, total);
+    hipLaunchKernelGGL(gen_conv_dgrad_kernel, dim3(gen_blocks(total)), dim3(256), 0, st, dout, wt, aux, din, Si, So, Ci, ldi, Co, k, s, sel.seg, total);
     return hipGetLastError();
 }
 
@@ -951,55 +1031,57 @@ hipError_t launch_gen_conv_wgrad(hipStream_t st, const float* in, const float* d
 {
     const int So = (Si - 1) / s + 1;
     const size_t per = (size_t)k * k * Ci * Co + Co;
-    if (s == 1 && (k == 3 || k == 5 || k == 7)) {
-        const int npair = ((Ci + 31) / 32) * ((Co + 31) / 32), ngrp = (npair + 3) / 4;
-        if (const size_t lds = gen_wgrad_out_lds(Si, Ci, ldc, Co, k)) {        // four output channels: GEMM form, the taps on the gradient
-            int n_cu = 0;
-            if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
-            const long long R = (long long)N * Si;
-            const int nsl = (int)std::max<long long>(1, std::min<long long>(std::min(GEN_WGRAD_OUT_SLICES_MAX, 2 * n_cu), R));
-            const int np4 = (npair_out(Ci, k) + 3) / 4;
-            if (hipError_t e = gen_wgrad_out_launch(st, in, dout, scratch, N, Si, Ci, ldc, k, nsl, np4, lds); e != hipSuccess) return e;
-            hipLaunchKernelGGL(gen_conv_wgrad_reduce_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, scratch, nsl, Ci, Ci_dst, Co,
-                               k * k, alpha, gw, gb);
-            return hipGetLastError();
-        }
-        if (const size_t lds = gen_wgrad_rows_lds(Si, Ci, ldc, Co, k)) {       // operands staged once per kernel row (round 5)
-            // as many row slices as fill the chip with two blocks per CU (k x nsl x ngrp blocks; 64 slices left a third of the slots empty)
-            int n_cu = 0;
-            if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
-            const int nsl = std::max(1, std::min(GEN_WGRAD_SLICES_MAX, 2 * n_cu / (k * ngrp)));
-            const dim3 grid_r((unsigned)(k * nsl * ngrp));
-            static std::atomic<unsigned> d3{0}, d5{0}, d7{0};
-            if (k == 3) {
-                if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_rows_kernel<3>, 80 * 1024, d3); e != hipSuccess) return e;
-                hipLaunchKernelGGL((gen_wgrad_rows_kernel<3>), grid_r, dim3(256), lds, st, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
-            } else if (k == 5) {
-                if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_rows_kernel<5>, 80 * 1024, d5); e != hipSuccess) return e;
-                hipLaunchKernelGGL((gen_wgrad_rows_kernel<5>), grid_r, dim3(256), lds, st, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
+    const GenTierSel sel = gen_conv_tier(2, Si, Ci, ldc, Co, k, s);
+    const size_t lds = sel.lds;
+    const int npair = ((Ci + 31) / 32) * ((Co + 31) / 32), ngrp = (npair + 3) / 4;
+    switch (sel.tier) {
+    case GEN_TIER_WGRAD_OUT: {                                 // four output channels: GEMM form, the taps on the gradient
+        int n_cu = 0;
+        if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
+        const long long R = (long long)N * Si;
+        const int nsl = (int)std::max<long long>(1, std::min<long long>(std::min(GEN_WGRAD_OUT_SLICES_MAX, 2 * n_cu), R));
+        if (hipError_t e = gen_wgrad_out_launch(st, in, dout, scratch, N, Si, Ci, ldc, k, nsl, sel.np, lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(gen_conv_wgrad_reduce_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, scratch, nsl, Ci, Ci_dst, Co,
+                           k * k, alpha, gw, gb);
+        return hipGetLastError();
+    }
+    case GEN_TIER_WGRAD_ROWS: {                                // operands staged once per kernel row (round 5)
+        // as many row slices as fill the chip with two blocks per CU (k x nsl x ngrp blocks; 64 slices left a third of the slots empty)
+        int n_cu = 0;
+        if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
+        const int nsl = std::max(1, std::min(GEN_WGRAD_SLICES_MAX, 2 * n_cu / (k * ngrp)));
+        const dim3 grid_r((unsigned)(k * nsl * ngrp));
+        static std::atomic<unsigned> d3{0}, d5{0}, d7{0};
+        if (k == 3) {
+            if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_rows_kernel<3>, 80 * 1024, d3); e != hipSuccess) return e;
+            hipLaunchKernelGGL((gen_wgrad_rows_kernel<3>), grid_r, dim3(256), lds, st, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
+        } else if (k == 5) {
+            if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_rows_kernel<5>, 80 * 1024, d5); e != hipSuccess) return e;
+            hipLaunchKernelGGL((gen_wgrad_rows_kernel<5>), grid_r, dim3(256), lds, st, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
 #ifdef IODINE_TILE_PROF
-                if (getenv("IODINE_GEN_PROF")) {
-                    const int nbk = std::min((int)grid_r.x, TP_MAXBLK);
-                    std::vector<unsigned> hp((size_t)nbk * 8);
-                    (void)hipStreamSynchronize(st);
-                    (void)hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(g_genw_prof), hp.size() * sizeof(unsigned));
-                    static const char* names[8] = {"prologue", "commit", "barrier 1", "fetch issue", "MFMA blocks", "barrier 2", "-", "-"};
-                    double sum[8] = {0}, tot = 0;
-                    for (int b2 = 0; b2 < nbk; ++b2) for (int i = 0; i < 8; ++i) sum[i] += hp[(size_t)b2 * 8 + i];
-                    for (int i = 0; i < 8; ++i) tot += sum[i] / nbk;
-                    fprintf(stderr, "[gen wgrad rows prof] ticks per block (%d slices), total %.0f:", nsl, tot);
-                    for (int i = 0; i < 6; ++i) fprintf(stderr, " %s %.0f |", names[i], sum[i] / nbk);
-                    fprintf(stderr, "\n");
-                }
-#endif
-            } else {
-                if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_rows_kernel<7>, 80 * 1024, d7); e != hipSuccess) return e;
-                hipLaunchKernelGGL((gen_wgrad_rows_kernel<7>), grid_r, dim3(256), lds, st, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
+            if (getenv("IODINE_GEN_PROF")) {
+                const int nbk = std::min((int)grid_r.x, TP_MAXBLK);
+                std::vector<unsigned> hp((size_t)nbk * 8);
+                (void)hipStreamSynchronize(st);
+                (void)hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(g_genw_prof), hp.size() * sizeof(unsigned));
+                static const char* names[8] = {"prologue", "commit", "barrier 1", "fetch issue", "MFMA blocks", "barrier 2", "-", "-"};
+                double sum[8] = {0}, tot = 0;
+                for (int b2 = 0; b2 < nbk; ++b2) for (int i = 0; i < 8; ++i) sum[i] += hp[(size_t)b2 * 8 + i];
+                for (int i = 0; i < 8; ++i) tot += sum[i] / nbk;
+                fprintf(stderr, "[gen wgrad rows prof] ticks per block (%d slices), total %.0f:", nsl, tot);
+                for (int i = 0; i < 6; ++i) fprintf(stderr, " %s %.0f |", names[i], sum[i] / nbk);
+                fprintf(stderr, "\n");
             }
-            hipLaunchKernelGGL(gen_conv_wgrad_reduce_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, scratch, nsl, Ci, Ci_dst, Co,
-                               k * k, alpha, gw, gb);
-            return hipGetLastError();
+#endif
+        } else {
+            if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_rows_kernel<7>, 80 * 1024, d7); e != hipSuccess) return e;
+            hipLaunchKernelGGL((gen_wgrad_rows_kernel<7>), grid_r, dim3(256), lds, st, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
         }
+        hipLaunchKernelGGL(gen_conv_wgrad_reduce_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, scratch, nsl, Ci, Ci_dst, Co,
+                           k * k, alpha, gw, gb);
+        return hipGetLastError();
+    }
+    case GEN_TIER_WGRAD_MFMA: {
         const dim3 grid((unsigned)(k * k * GEN_WGRAD_SLICES * ngrp));
         if (k == 3) hipLaunchKernelGGL((gen_wgrad_mfma_kernel<3>), grid, dim3(256), 0, st, in, dout, scratch, N, Si, Ci, ldc, Co, GEN_WGRAD_SLICES);
         else if (k == 5) hipLaunchKernelGGL((gen_wgrad_mfma_kernel<5>), grid, dim3(256), 0, st, in, dout, scratch, N, Si, Ci, ldc, Co, GEN_WGRAD_SLICES);
@@ -1008,12 +1090,14 @@ hipError_t launch_gen_conv_wgrad(hipStream_t st, const float* in, const float* d
                            k * k, alpha, gw, gb);
         return hipGetLastError();
     }
-    if (s == 2 && gen_s2_wgrad_ok(k, Ci, ldc, Co)) {
+    case GEN_TIER_S2_MFMA: {
         int nsl = 0;
         if (hipError_t e = launch_gen_s2_wgrad(st, in, dout, scratch, N, Si, Ci, ldc, Co, k, GEN_WGRAD_SLICES_MAX, &nsl, chmask); e != hipSuccess) return e;
         hipLaunchKernelGGL(gen_conv_wgrad_reduce_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, scratch, nsl, Ci, Ci_dst, Co,
                            k * k, alpha, gw, gb);
         return hipGetLastError();
+    }
+    default: break;                                            // the scalar kernel
     }
     hipLaunchKernelGGL(gen_conv_wgrad_partial_kernel, dim3(gen_blocks(per * GEN_WGRAD_SLICES)), dim3(256), 0, st, in, dout, scratch, N, Si,
                        So, Ci, ldc, Co, k, s, GEN_WGRAD_SLICES);

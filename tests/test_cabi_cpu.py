@@ -24,6 +24,16 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert L.iodine_abi_version() == 3
 
 
+def test_gen_conv_tier_query_is_host_only():
+    """iodine_op_gen_conv_tier (the kernel selector of the generic convs, for the kernel-level tests) answers without a GPU: the default
+    decoder layer 64 -> 64, 5 x 5 runs on the MFMA kernel with 16-channel chunks (0) and the row-staged weight gradient (6); the output conv
+    64 -> 4 on the GEMM-form weight gradient (5) at NP = 2.  tests/test_gen_tiers_cpu.py holds the whole table."""
+    L = _lib.lib()
+    assert [L.iodine_op_gen_conv_tier(m, 32, 64, 64, 64, 5, 1) for m in range(3)] == [0, 0, 6]
+    assert L.iodine_op_gen_conv_tier(2, 32, 64, 64, 4, 5, 1) == 5 | 2 << 8
+    assert L.iodine_op_gen_conv_tier(0, 32, 64, 64, 64, 5, 0) == -1
+
+
 def test_header_documents_every_option_and_profile_category():
     """include/iodine_hip.h is the contract: every key iodine_set_option accepts, every category a launch is profiled under and the
     `seen:` query must be named in it (five options and two categories had been added to the library only)."""
