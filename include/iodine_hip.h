@@ -142,6 +142,27 @@ int iodine_set_frames(iodine_handle* h, int frames);
  * of option "graph" carries the bit patterns of sigma and beta and the identity of the weight table. */
 int iodine_set_objective(iodine_handle* h, double sigma, double beta, const double* iter_weights, int n_weights);
 
+/* Per-pixel observation weights w >= 0 of the likelihood, for the NEXT compute call that takes x:
+ *     LL = mean_b sum_p w_p sum_c logsumexp_k(log(m_k + 1e-12) + l_kc),   ELBO = LL - beta * KL
+ * (iodine.py:213-220 with w in front of the pixel sum; NOT normalised by sum(w) or mean(w)).  w_dev: device pointer, fp32, (B,S,S) with
+ * per_frame = 0 -- with a clip (iodine_set_frames) the same weights for every frame -- or (B,E,S,S) with per_frame = 1, frame i weighting
+ * ELBO evaluation i.  NULL = no weights.  per_frame = 1 while the frames setting is 0 is IODINE_ERR_INVALID (host only, nothing is set).
+ *   weighted:      the LL / ELBO a call reports (elbo_iter[:, 0] and [:, 2], terms[0] and terms[2], the loss, iodine_logger_scalars'
+ *                  likelihood, a trajectory's per-image ll); the closed-form gradients d(B * ELBO) / d mean and / d mask and with them
+ *                  everything downstream, as autograd gives for the weighted objective: grad_post, the layer-normed gradient channels
+ *                  9 - 12 of the refinement input (normalised from the weighted gradients), every outer gradient.
+ *   not weighted:  the channels that describe the scene -- 8 mask_posterior, 13 likelihood, 14 leave_one_out_likelihood --, the image
+ *                  channels, and the KL.
+ * ONE-SHOT: the pointer is consumed by the next iodine_reconstruct[_seq] / iodine_elbo / iodine_train_forward[_seq] and cleared by it,
+ * whether that call succeeds or is refused, so a stale pointer is never read; the call after it runs unweighted unless this entry is
+ * called again.  iodine_decode takes no x and neither reads nor clears it.  The memory is the caller's: it is read on the compute call's
+ * stream (packed next to the image, no extra buffer) and must stay valid until that work has run -- with option "graph" for as long as
+ * the call is replayed: the pointer and the flag are part of the hipGraph key.  The backward passes need nothing: they differentiate
+ * what the forward saved.  Values are the caller's contract -- finite, >= 0, not checked on the device; zeros are allowed, an image of
+ * all zeros included (its gradients are exactly 0).  Weights are data: they receive no gradient.  A call without weights, and a call
+ * whose weights are all 1, compute the bits of a library that never had this entry (the multiply is by an exact 1). */
+int iodine_set_pixel_weights(iodine_handle* h, const float* w_dev, int per_frame);
+
 /* pred, mask, mean = model.reconstruct(x) -- iodine.py:107-112 (encode :73-105 + decode :59-71).
  * Outputs (any may be NULL): pred (B,3,S,S), mask (B,K,1,S,S), mean (B,K,3,S,S) NCHW; z (B,K,L) = the final
  * sample; post_mean / post_logvar (B,K,L) = lambda after T updates; elbo_iter (T,3) = {ELBO, KL, LL} of each

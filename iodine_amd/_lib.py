@@ -31,6 +31,7 @@ EXPORTS = (
     'iodine_train_backward_aux', 'iodine_op_render_bwd_logits',
     'iodine_set_objective',
     'iodine_train_forward_seq', 'iodine_train_backward_seq', 'iodine_last_train_state',
+    'iodine_set_pixel_weights',
 )
 
 
@@ -135,6 +136,8 @@ def lib() -> C.CDLL:
         L.iodine_train_forward_seq.argtypes = [vp, vp, ci, vp, vp, C.POINTER(vp), vp, vp]
         L.iodine_train_backward_seq.argtypes = [vp, vp] + [vp] * 10 + [ci, C.POINTER(vp)]
         L.iodine_last_train_state.argtypes = [vp, vp, ci, vp, vp]
+    if hasattr(L, 'iodine_set_pixel_weights'):          # (weights=; absent from older A/B builds, which refuse the keyword)
+        L.iodine_set_pixel_weights.argtypes = [vp, vp, ci]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

@@ -205,7 +205,8 @@ hipError_t launch_dz_plain(hipStream_t st, const float* Rc, const float* wclsT, 
                            const float* plv, const float* eps, float scale, float* g_pm, float* g_plv, float beta);
 // kernels_misc.hip
 // F > 1: x is a clip (B,F,3,P), batch first; x4 [F][B][P][4], frame-major
-hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P, int F = 1);
+// lane 3 of x4: the pixel weight w[b][f][p] (w_per_frame) / w[b][p] (every frame), 1.f where w is NULL
+hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P, int F = 1, const float* w = nullptr, int w_per_frame = 0);
 hipError_t launch_img_terms_split(hipStream_t st, const float* terms, float* kl, float* ll, int n);
 hipError_t launch_posterior_init(hipStream_t st, const float* im, const float* ilv, float* pm, float* plv, float* h,
                                  float* c, int N, int L, int H);

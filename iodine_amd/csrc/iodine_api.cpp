@@ -784,7 +784,9 @@ enum { GK_DECODE = 2, GK_ELBO = 3, GK_DECODE_SAVED = 6, GK_ELBO_SAVED = 7, GK_DE
 
 // o: the objective the body runs with - host scalars are baked into the captured nodes, so the key carries the bit patterns of sigma and
 // beta and the generation of the weight table (the handle's current objective; a backward passes the one its forward saved)
-std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, std::initializer_list<const void*> ptrs, const Objective* o = nullptr)
+// pw: the pixel weights of a call that packs x - the captured pack kernel bakes the pointer and the flag like every other address
+std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, std::initializer_list<const void*> ptrs, const Objective* o = nullptr,
+                                 const PixelWeights* pw = nullptr)
 {
     if (!o) o = &h->obj;
     uint64_t sb, bb;
@@ -793,6 +795,7 @@ std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, s
                                 (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7)),
                                 (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own), (uintptr_t)h->frames};
     k.push_back((uintptr_t)sb); k.push_back((uintptr_t)bb); k.push_back((uintptr_t)o->wgen);
+    k.push_back((uintptr_t)(pw ? pw->w : nullptr)); k.push_back((uintptr_t)(pw ? pw->per_frame : 0));
     for (const void* p : ptrs) k.push_back((uintptr_t)p);
     return k;
 }
@@ -1356,6 +1359,18 @@ int iodine_set_frames(iodine_handle* h, int frames)
     return IODINE_OK;
 }
 
+int iodine_set_pixel_weights(iodine_handle* h, const float* w_dev, int per_frame)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_set_pixel_weights(h, w_dev, per_frame);
+    if (w_dev && per_frame && h->frames == 0)
+        return h->fail(IODINE_ERR_INVALID, "iodine_set_pixel_weights: per_frame = 1 is one weight image per frame of a clip (B, E, S, S), but the "
+                                           "frames setting is 0: x is one image per batch entry (iodine_set_frames; per_frame = 0: weights (B, S, S))");
+    h->pix_w = w_dev;
+    h->pix_w_per_frame = w_dev && per_frame ? 1 : 0;
+    return IODINE_OK;
+}
+
 int iodine_set_objective(iodine_handle* h, double sigma, double beta, const double* iter_weights, int n_weights)
 {
     if (!h) return IODINE_ERR_INVALID;
@@ -1477,6 +1492,7 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
 {
     if (!h) return IODINE_ERR_INVALID;
     if (h->shim) return pad_reconstruct_seq(h, stream, batch, x, eps, pred, mask, mean, z, post_mean, post_logvar, elbo_iter, state_in, traj);
+    const PixelWeights pw(h);                              // one-shot: taken before the first refusal
     int rc = reconstruct_check(h, batch, x, eps, state_in, traj);
     if (rc) return rc;
     rc = ensure_workspace(h, batch, 0);
@@ -1489,7 +1505,7 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const size_t eps_stride = (size_t)N * h->L;
-        PROF(h, st, "frames_in", launch_x_to_nhwc4(st, x, b.x4, B, h->P, h->frames > 0 ? h->frames : 1));
+        PROF(h, st, "frames_in", launch_x_to_nhwc4(st, x, b.x4, B, h->P, h->frames > 0 ? h->frames : 1, pw.w, pw.per_frame && h->frames > 0));
         if (state_in) {
             // continue from (lambda, h, c) of an earlier call instead of Gaussian.init_unit + zero LSTM state (iodine.py:81-83)
             HIPCHK(h, hipMemcpyAsync(b.pm, state_in[0], sizeof(float) * eps_stride, hipMemcpyDeviceToDevice, st));
@@ -1529,7 +1545,7 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
         if (elbo_iter && n_it > 0) HIPCHK(h, hipMemcpyAsync(elbo_iter, b.scal, sizeof(float) * 3 * n_it, hipMemcpyDeviceToDevice, st));
         return IODINE_OK;
     };
-    std::vector<uintptr_t> key = graph_key(h, 1, B, {x, eps, pred, mask, mean, z, post_mean, post_logvar, elbo_iter});
+    std::vector<uintptr_t> key = graph_key(h, 1, B, {x, eps, pred, mask, mean, z, post_mean, post_logvar, elbo_iter}, nullptr, &pw);
     for (int j = 0; j < 4; ++j) key.push_back((uintptr_t)(state_in ? state_in[j] : nullptr));
     for (int j = 0; j < 5; ++j) key.push_back((uintptr_t)(traj ? traj[j] : nullptr));
     rc = run_graphed(h, st, key, body);
@@ -1600,6 +1616,8 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
                 const float* eps, float* terms)
 {
     if (h && h->shim) return pad_elbo(h, stream, batch, x, post_mean, post_logvar, eps, terms);
+    if (!h) return IODINE_ERR_INVALID;
+    const PixelWeights pw(h);                              // (one image per batch entry: weights (B, P) either way)
     int rc = elbo_check(h, batch, x, eps, post_mean, post_logvar);
     if (rc) return rc;
     const bool save = h->save_bwd != 0;                    // option save_for_backward: keep what iodine_elbo_backward reads (workspace mode 2)
@@ -1610,7 +1628,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     const int B = batch, N = B * h->K;
     auto body = [&]() -> int {
         Buffers& b = h->buf;
-        HIPCHK(h, launch_x_to_nhwc4(st, x, b.x4, B, h->P));
+        HIPCHK(h, launch_x_to_nhwc4(st, x, b.x4, B, h->P, 1, pw.w, 0));
         if (post_mean) {
             HIPCHK(h, hipMemcpyAsync(b.pm, post_mean, sizeof(float) * (size_t)N * h->L, hipMemcpyDeviceToDevice, st));
             HIPCHK(h, hipMemcpyAsync(b.plv, post_logvar, sizeof(float) * (size_t)N * h->L, hipMemcpyDeviceToDevice, st));
@@ -1625,7 +1643,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
         if (save) HIPCHK(h, hipMemcpyAsync(b.latent[0], eps, sizeof(float) * (size_t)N * h->L, hipMemcpyDeviceToDevice, st));
         return IODINE_OK;
     };
-    rc = run_graphed(h, st, graph_key(h, save ? GK_ELBO_SAVED : GK_ELBO, B, {x, post_mean, post_logvar, eps, terms}), body);
+    rc = run_graphed(h, st, graph_key(h, save ? GK_ELBO_SAVED : GK_ELBO, B, {x, post_mean, post_logvar, eps, terms}, nullptr, &pw), body);
     if (rc) return rc;
     CallState& cs = h->calls;
     cs.last_elbo_iter = 0;
@@ -1754,6 +1772,7 @@ int iodine_train_forward_seq(iodine_handle* h, void* stream, int batch, const fl
 {
     if (!h) return IODINE_ERR_INVALID;
     if (h->shim) return pad_train_forward(h, stream, batch, x, eps, state_in, loss, elbo_iter);
+    const PixelWeights pw(h);
     int rc = train_forward_check(h, batch, x, eps, loss, state_in);
     if (rc) return rc;
     rc = ensure_workspace(h, batch, 1);
@@ -1765,7 +1784,7 @@ int iodine_train_forward_seq(iodine_handle* h, void* stream, int batch, const fl
         Buffers& b = h->buf;
         const size_t eps_stride = (size_t)N * L;
         HIPCHK(h, launch_zero_fill(st, h->gacc_arena, h->gacc_total));
-        PROF(h, st, "frames_in", launch_x_to_nhwc4(st, x, b.x4, B, h->P, h->frames > 0 ? h->frames : 1));
+        PROF(h, st, "frames_in", launch_x_to_nhwc4(st, x, b.x4, B, h->P, h->frames > 0 ? h->frames : 1, pw.w, pw.per_frame && h->frames > 0));
         if (state_in) {
             // continue from (lambda, h, c) of an earlier call (truncated / exact BPTT over a clip): evaluation 0 samples from the given lambda
             HIPCHK(h, hipMemcpyAsync(b.pm, state_in[0], sizeof(float) * eps_stride, hipMemcpyDeviceToDevice, st));
@@ -1795,7 +1814,7 @@ int iodine_train_forward_seq(iodine_handle* h, void* stream, int batch, const fl
         if (elbo_iter) HIPCHK(h, hipMemcpyAsync(elbo_iter, b.scal, sizeof(float) * 3 * (T + 1), hipMemcpyDeviceToDevice, st));
         return IODINE_OK;
     };
-    std::vector<uintptr_t> key = graph_key(h, 4, B, {x, eps, loss, elbo_iter});
+    std::vector<uintptr_t> key = graph_key(h, 4, B, {x, eps, loss, elbo_iter}, nullptr, &pw);
     for (int j = 0; j < 4; ++j) key.push_back((uintptr_t)(state_in ? state_in[j] : nullptr));     // (all four NULL: no state)
     rc = run_graphed(h, st, key, body);
     if (rc) return rc;

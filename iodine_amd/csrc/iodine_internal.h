@@ -140,6 +140,10 @@ struct iodine_handle {
     bool params_set = false;
     int stop_after = -1;
     int frames = 0;                             // iodine_set_frames: 0 = x is one image per batch entry, E = a clip of E frames, one per ELBO evaluation
+    // iodine_set_pixel_weights: per-pixel observation weights of the NEXT compute call that takes x.  One-shot: that call takes them
+    // (PixelWeights below) before anything else, so they are gone whether it succeeds or not.  The caller's memory, read on the call's stream.
+    const float* pix_w = nullptr;
+    int pix_w_per_frame = 0;                    // 1: (B, frames, P), one weight image per frame; 0: (B, P), the same for every frame
 
     // parameter-derived device buffers (owned)
     float* lin = nullptr;                       // linspace(-1,1,S)
@@ -228,6 +232,14 @@ struct iodine_handle {
     int fail(int code, const std::string& m) { err = m; return code; }
 };
 
+// the pending pixel weights, taken (and cleared) by the compute call that packs x
+#pragma GCC visibility push(hidden)
+struct PixelWeights {
+    const float* w; int per_frame;
+    explicit PixelWeights(iodine_handle* h) : w(h->pix_w), per_frame(h->pix_w ? h->pix_w_per_frame : 0) { h->pix_w = nullptr; h->pix_w_per_frame = 0; }
+};
+#pragma GCC visibility pop
+
 #define HIPCHK(h, expr)                                                                          \
     do {                                                                                         \
         hipError_t e_ = (expr);                                                                  \
@@ -275,6 +287,7 @@ size_t pad_workspace_bytes(const iodine_handle* h, int batch, int mode);
 int pad_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes);
 int pad_set_run_shape(iodine_handle* h, int slots, int iters);
 int pad_set_frames(iodine_handle* h, int frames);
+int pad_set_pixel_weights(iodine_handle* h, const float* w_dev, int per_frame);
 int pad_set_objective(iodine_handle* h, double sigma, double beta, const double* iter_weights, int n_weights);
 int pad_set_option(iodine_handle* h, const char* key, double value);
 int pad_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* pred, float* mask, float* mean,

@@ -148,6 +148,14 @@ int shim_flat_out(iodine_handle* h, hipStream_t st, float* flat, int accumulate)
 // ---- the entry points.  Each reads the run shape, the frames setting and the batch of the last call from the inner handle, asks the inner
 // handle's check (iodine_internal.h) before its first scratch allocation or launch, and forwards a refusal's message with shim_fail.
 
+// pixel weights are one-shot: whatever way a call that takes x leaves the boundary, the inner handle holds none afterwards (the inner
+// call takes them first; this covers the boundary's own refusals and failures before it)
+struct PendingWeights {
+    iodine_handle* in;
+    explicit PendingWeights(iodine_handle* inner) : in(inner) {}
+    ~PendingWeights() { in->pix_w = nullptr; in->pix_w_per_frame = 0; }
+};
+
 int pad_create(iodine_handle* h)
 {
     PadShim* sh = h->shim = new PadShim();
@@ -186,6 +194,10 @@ size_t pad_workspace_bytes(const iodine_handle* h, int batch, int mode) { return
 int pad_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes) { return shim_fail(h, iodine_set_workspace(h->shim->inner, dev_ptr, bytes)); }
 int pad_set_run_shape(iodine_handle* h, int slots, int iters) { return shim_fail(h, iodine_set_run_shape(h->shim->inner, slots, iters)); }
 int pad_set_frames(iodine_handle* h, int frames) { return shim_fail(h, iodine_set_frames(h->shim->inner, frames)); }
+int pad_set_pixel_weights(iodine_handle* h, const float* w_dev, int per_frame)
+{
+    return shim_fail(h, iodine_set_pixel_weights(h->shim->inner, w_dev, per_frame));      // (the inner handle packs x: it holds them)
+}
 int pad_set_objective(iodine_handle* h, double sigma, double beta, const double* iter_weights, int n_weights)
 {
     return shim_fail(h, iodine_set_objective(h->shim->inner, sigma, beta, iter_weights, n_weights));
@@ -206,6 +218,7 @@ int pad_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* 
 {
     PadShim* sh = h->shim;
     iodine_handle* in = sh->inner;
+    PendingWeights once(in);
     if (int rc = reconstruct_check(in, batch, x, eps, state_in, traj)) return shim_fail(h, rc);
     hipStream_t st = (hipStream_t)stream;
     const long long N = (long long)batch * in->K, R = (long long)(in->T + 1) * N;
@@ -257,6 +270,7 @@ int pad_elbo(iodine_handle* h, void* stream, int batch, const float* x, const fl
              float* terms)
 {
     PadShim* sh = h->shim;
+    PendingWeights once(sh->inner);
     if (int rc = elbo_check(sh->inner, batch, x, eps, post_mean, post_logvar)) return shim_fail(h, rc);
     hipStream_t st = (hipStream_t)stream;
     const long long N = (long long)batch * sh->inner->K;
@@ -327,6 +341,7 @@ int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x,
 {
     PadShim* sh = h->shim;
     iodine_handle* in = sh->inner;
+    PendingWeights once(in);
     if (int rc = train_forward_check(in, batch, x, eps, loss, state_in)) return shim_fail(h, rc);
     hipStream_t st = (hipStream_t)stream;
     const long long N = (long long)batch * in->K, R = (long long)(in->T + 1) * N;

@@ -5,24 +5,27 @@
 #include "common.h"
 
 // -----------------------------------------------------------------------------------------------
-// layout conversion: images NCHW (B,3,P) -> (B,P) float4 {r,g,b,0}; a clip (B,F,3,P), batch first as a loader yields it, goes to
+// layout conversion: images NCHW (B,3,P) -> (B,P) float4 {r,g,b,w}; a clip (B,F,3,P), batch first as a loader yields it, goes to
 // [F][B][P] - frame-major, so that iteration i of the refinement loop reads frame i as one contiguous (B,P) image tensor.  F = 1: the
-// single image.  One launch for all frames.
+// single image.  One launch for all frames.  Lane 3 is the pixel's observation weight (iodine_set_pixel_weights; pixel_terms.h is its one
+// reader): w[b][f][p] (w_per_frame) or w[b][p] for every frame of the clip, and an exact 1.f when no weights are given.
 // -----------------------------------------------------------------------------------------------
-__global__ void x_to_nhwc4_kernel(const float* __restrict__ x, float4* __restrict__ x4, int B, int P, int F)
+__global__ void x_to_nhwc4_kernel(const float* __restrict__ x, float4* __restrict__ x4, int B, int P, int F, const float* __restrict__ w,
+                                  int w_per_frame)
 {
     const size_t BP = (size_t)B * P, total = BP * F;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t f = i / BP, r = i - f * BP, b = r / P, p = r % P;
         const float* xb = x + (b * F + f) * 3 * P;
-        x4[i] = make_float4(xb[p], xb[P + p], xb[2 * (size_t)P + p], 0.f);
+        const float wp = w ? w[(w_per_frame ? b * F + f : b) * P + p] : 1.f;
+        x4[i] = make_float4(xb[p], xb[P + p], xb[2 * (size_t)P + p], wp);
     }
 }
 
-hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P, int F)
+hipError_t launch_x_to_nhwc4(hipStream_t st, const float* x, float* x4, int B, int P, int F, const float* w, int w_per_frame)
 {
     const int blocks = (int)std::min<size_t>(((size_t)B * P * F + 255) / 256, 4096);
-    hipLaunchKernelGGL(x_to_nhwc4_kernel, dim3(blocks), dim3(256), 0, st, x, (float4*)x4, B, P, F);
+    hipLaunchKernelGGL(x_to_nhwc4_kernel, dim3(blocks), dim3(256), 0, st, x, (float4*)x4, B, P, F, w, w_per_frame);
     return hipGetLastError();
 }
 

@@ -43,7 +43,7 @@ IOD_DEVINL double wave_sum_d(double v)
 }
 
 // ---- pass 1: ELBO log-likelihood partials, gradient wrt decoder output, layer-norm partial sums ----
-// part layout per (b, block): [0] ll, [1] like.s1, [2] like.s2, then per k: g1.s1, g1.s2, g2.s1, g2.s2, loo.s1, loo.s2
+// part layout per (b, block): [0] ll (sum_p w_p ll_sum: the pixel weights of iodine_set_pixel_weights enter here), [1] like.s1, [2] like.s2, then per k: g1.s1, g1.s2, g2.s1, g2.s2, loo.s1, loo.s2
 template <int K, bool STRICT>
 __global__ __launch_bounds__(PIX_BLOCK)
 void pixel_pass1_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec, float4* __restrict__ g,
@@ -62,7 +62,8 @@ void pixel_pass1_kernel(const float4* __restrict__ x4, const float4* __restrict_
     const int pend = min(P, (blk + 1) * ppb);
     for (int p = blk * ppb + tid; p < pend; p += PIX_BLOCK) {
         PixelTerms<K> t;
-        pixel_terms<K, STRICT>(x4[(size_t)b * P + p], dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
+        const float4 xv = x4[(size_t)b * P + p];
+        pixel_terms<K, STRICT>(xv, dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
         float tg = 0.f;
 #pragma unroll
         for (int k = 0; k < K; ++k) tg += t.m[k] * t.g2[k];
@@ -82,7 +83,7 @@ void pixel_pass1_kernel(const float4* __restrict__ x4, const float4* __restrict_
             st[3 + 6 * k + 4] += loo;
             st[3 + 6 * k + 5] += loo * loo;
         }
-        st[0] += t.ll_sum;
+        st[0] += xv.w * t.ll_sum;                              // the weighted log-likelihood; like / loo below describe the scene: raw
         st[1] += t.like;
         st[2] += t.like * t.like;
     }

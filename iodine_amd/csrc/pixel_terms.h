@@ -9,10 +9,10 @@ struct PixelTerms {
     float mu[K][3];       // sigmoid(rgb)
     float m[K];           // mask = softmax_k(logit)
     float logit[K];
-    float g1[K][3];       // d(B*ELBO)/d mean
-    float g2[K];          // d(B*ELBO)/d mask
+    float g1[K][3];       // d(B*ELBO)/d mean   (of the WEIGHTED objective: pixel weight w = lane 3 of the packed image)
+    float g2[K];          // d(B*ELBO)/d mask   (weighted too)
     float pk[K];          // exp(sum_c l_kc)  (un-stabilised, as the reference)
-    float ll_sum;         // sum_c logsumexp_k(log(m_k + 1e-12) + l_kc)
+    float ll_sum;         // sum_c logsumexp_k(log(m_k + 1e-12) + l_kc)   (raw, like pk / like / loo: they describe the scene, not the objective)
     float like;           // exp(ll_sum)
     float mix;            // sum_k m_k * pk_k
     float loo[K];         // leave-one-out likelihood (iodine.py:321-328), see pixel_terms
@@ -32,7 +32,10 @@ template <bool STRICT> IOD_DEVINL float pt_exp_bounded(float x) { if constexpr (
 template <bool STRICT> IOD_DEVINL float pt_rcp(float d) { if constexpr (STRICT) return 1.f / d; else return __builtin_amdgcn_rcpf(d); }
 template <bool STRICT> IOD_DEVINL float pt_sigmoid(float v) { return pt_rcp<STRICT>(1.f + pt_exp_bounded<STRICT>(-v)); }
 
-// dv[k] = decoder output (rgb logits, mask logit) of slot k at this pixel
+// dv[k] = decoder output (rgb logits, mask logit) of slot k at this pixel; xv = {r, g, b, w}: the image and the pixel's observation weight
+// (iodine_set_pixel_weights; x_to_nhwc4_kernel writes an exact 1.f without weights).  LL = mean_b sum_p w_p sum_c logsumexp_k(..), so w
+// multiplies the two gradients and nothing else in here: it is folded into the per-channel 1 / s that both are built from (three
+// multiplies per pixel; by 1.f they are exact, so unweighted calls keep their bits).  The caller weights its own sum of ll_sum.
 template <int K, bool STRICT = false>
 IOD_DEVINL void pixel_terms_core(const float4 xv, const float4 (&dv)[K], float inv2s2, float invs2, float lconst, PixelTerms<K>& t)
 {
@@ -84,10 +87,10 @@ IOD_DEVINL void pixel_terms_core(const float4 xv, const float4 (&dv)[K], float i
 #pragma unroll
         for (int k = 0; k < K; ++k) { a[k] = pt_exp_bounded<STRICT>(a[k] - amax); s += a[k]; }
         t.ll_sum += amax + logf(s);
-        const float rs = pt_rcp<STRICT>(s);
+        const float rs = pt_rcp<STRICT>(s) * xv.w;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const float r = a[k] * rs;                         // responsibility of slot k for channel c
+            const float r = a[k] * rs;                         // w x responsibility of slot k for channel c
             t.g1[k][c] = r * (xs[c] - t.mu[k][c]) * invs2;
             t.g2[k] += r * rme[k];
         }

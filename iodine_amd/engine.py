@@ -61,7 +61,35 @@ def clip_chunks(F, T):
     return [(c * T, c * T + T + 1) for c in range((int(F) - 1) // int(T))]
 
 
-def clip_backward(model, clip, eps=None, bptt='truncated'):
+def clip_weights(weights, clip_shape, chunk):
+    """The per-pixel weights of chunk ``chunk`` = (first frame, one past the last) of a clip of shape ``clip_shape`` (B, F, C, S, S):
+    ``weights`` (B, F, 1, S, S) / (B, F, S, S) - one weight image per frame - cut to the chunk's frames, the boundary frame included like
+    in the clip itself; (B, 1, S, S) / (B, S, S) - the same weights for every frame - as they are; None -> None.  Host only."""
+    if weights is None:
+        return None
+    if not torch.is_tensor(weights):
+        raise ValueError(f'clip_backward: weights must be a tensor or None; got {type(weights).__name__}')
+    B, F, S = clip_shape[0], clip_shape[1], clip_shape[-1]
+    got = tuple(weights.shape)
+    if got in ((B, 1, S, S), (B, S, S)):
+        return weights
+    if got in ((B, F, 1, S, S), (B, F, S, S)):
+        return weights[:, chunk[0]:chunk[1]]
+    raise ValueError(f'clip_backward: weights must have shape ({B}, {F}, 1, {S}, {S}) / ({B}, {F}, {S}, {S}), one weight image per frame of '
+                     f'the clip {tuple(clip_shape)}, or ({B}, 1, {S}, {S}) / ({B}, {S}, {S}) for every frame; got {got}')
+
+
+def border_weights(B, S, n, device=None):
+    """Weights (B, 1, S, S) that take an ``n``-pixel frame around every image out of the objective (``--ignore-border``): 0 there, 1
+    inside."""
+    if isinstance(n, bool) or int(n) != n or not 0 <= n or 2 * n >= S:
+        raise ValueError(f'border_weights: the border must be an integer with 0 <= 2 n < {S} (something must stay observed); got {n!r}')
+    w = torch.zeros((B, 1, S, S), dtype=torch.float32, device=device)
+    w[:, :, n:S - n, n:S - n] = 1.0
+    return w
+
+
+def clip_backward(model, clip, eps=None, bptt='truncated', weights=None):
     """Gradient of one clip (B, F, 3, S, S), F = c * n_iters + 1, accumulated into ``.grad`` chunk by chunk (``clip_chunks``); the caller
     zeroes the gradients before and steps the optimizer after.  Returns (clip loss, (F, 3) ELBO terms, one row per frame).
 
@@ -74,7 +102,11 @@ def clip_backward(model, clip, eps=None, bptt='truncated'):
     ``bptt='exact'``: the gradient of that one long forward, at the memory of one chunk.  Pass 1 runs the training forwards under
     ``no_grad`` and keeps every chunk's entry state; pass 2 walks the chunks in reverse, runs each forward again from its entry state (the
     same bits) and back-propagates loss + <cotangents of the following chunk, (lambda_T, h_T, c_T)>; the gradient of the entry state is the
-    cotangent handed to the chunk before.  About two forwards and one backward per chunk."""
+    cotangent handed to the chunk before.  About two forwards and one backward per chunk.
+
+    ``weights``: per-pixel observation weights of the clip (``IODINE.forward``): (B, F, 1, S, S) / (B, F, S, S), one weight image per frame -
+    every chunk, and every re-run of a chunk in the exact mode, gets the slice of its frames (``clip_weights``) - or (B, 1, S, S) /
+    (B, S, S) for all frames."""
     if bptt not in ('truncated', 'exact'):
         raise ValueError(f"clip_backward: bptt must be 'truncated' or 'exact'; got {bptt!r}")
     if clip.dim() != 5:
@@ -93,14 +125,16 @@ def clip_backward(model, clip, eps=None, bptt='truncated'):
         eps = model._normals(None, shape, clip.device).clone()
     elif tuple(eps.shape) != shape:
         raise RuntimeError(f'clip_backward: eps must have shape {shape}, one slice per frame; got {tuple(eps.shape)}')
+    clip_weights(weights, clip.shape, chunks[0])                             # (a wrong shape is refused before any device work)
     part = lambda c: (clip[:, chunks[c][0]:chunks[c][1]], eps[chunks[c][0]:chunks[c][1]])
+    wpart = lambda c: clip_weights(weights, clip.shape, chunks[c])
     total, terms = None, [None] * len(chunks)
     try:
         if bptt == 'truncated':
             state = None
             for c in range(len(chunks)):
                 model.iter_weights = saved if c == 0 else later
-                loss = model(*part(c), state=state, keep_state=True)
+                loss = model(*part(c), state=state, keep_state=True, weights=wpart(c))
                 loss.backward()
                 state = model.refinement_state()
                 total = loss.detach() if total is None else total + loss.detach()
@@ -110,13 +144,13 @@ def clip_backward(model, clip, eps=None, bptt='truncated'):
             with torch.no_grad():                                            # pass 1: the entry state of every chunk
                 for c in range(len(chunks) - 1):
                     model.iter_weights = saved if c == 0 else later
-                    model(*part(c), state=entry[c], keep_state=True)
+                    model(*part(c), state=entry[c], keep_state=True, weights=wpart(c))
                     entry.append(model.refinement_state())
             cot = None
             for c in reversed(range(len(chunks))):                           # pass 2: recompute, back-propagate, hand the cotangents on
                 model.iter_weights = saved if c == 0 else later
                 leaves = None if c == 0 else tuple(t.clone().requires_grad_(True) for t in entry[c])
-                loss = model(*part(c), state=leaves, attach_state=True)
+                loss = model(*part(c), state=leaves, attach_state=True, weights=wpart(c))
                 out = loss
                 if cot is not None:
                     ends = (model.posterior.mean, model.posterior.logvar) + tuple(t.view_as(cot[2]) for t in model.lstm_hidden)
@@ -139,7 +173,7 @@ def beta_warmup(step, beta, warmup_steps):
 
 
 def train(model, optimizer, dataloader, device, max_steps, print_every=10, checkpoint_path=None, log=print, max_grad_norm=None,
-          beta=None, beta_warmup_steps=0, bptt=None):
+          beta=None, beta_warmup_steps=0, bptt=None, ignore_border=0):
     """train.py:44-108: loss = model(data); loss.mean(); zero_grad; backward; [all-reduce]; [clip]; step.  Returns the losses.
     ``max_grad_norm``: the global gradient norm is clipped at this value (train.py:64, commented out in the reference; the paper
     uses 5.0) AFTER the all-reduce, so every rank clips the same averaged gradient with the same coefficient - what
@@ -149,7 +183,9 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
     ``beta`` / ``beta_warmup_steps``: with ``beta`` given, ``model.beta`` is set before every step to ``beta_warmup(step, beta,
     beta_warmup_steps)`` and is left at ``beta`` afterwards; None leaves ``model.beta`` alone.
     ``bptt``: 'truncated' or 'exact' - the loader yields clips (B, F, 3, S, S) with F = c * n_iters + 1 frames (``SyntheticClips``) and a step
-    is ``clip_backward`` over the clip's chunks: ONE optimizer step per clip, the all-reduce and the clipping after the last chunk."""
+    is ``clip_backward`` over the clip's chunks: ONE optimizer step per clip, the all-reduce and the clipping after the last chunk.
+    ``ignore_border``: n > 0 trains with zero observation weight on an n-pixel frame around every image (``border_weights``, the
+    ``weights=`` of ``IODINE.forward``)."""
     model.train()
     fused_clip = isinstance(optimizer, FusedAdam)
     if max_grad_norm is not None:
@@ -169,11 +205,12 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
             x = data[0].to(device, non_blocking=True)                        # "first one is image" (train.py:49)
             if beta is not None:
                 model.beta = beta_warmup(step, beta, beta_warmup_steps)
+            w = border_weights(x.shape[0], x.shape[-1], ignore_border, device) if ignore_border else None
             if bptt is not None:
                 optimizer.zero_grad()
-                loss, _ = clip_backward(model, x, bptt=bptt)
+                loss, _ = clip_backward(model, x, bptt=bptt, weights=w)
             else:
-                loss = model(x).mean()
+                loss = (model(x) if w is None else model(x, weights=w)).mean()
                 optimizer.zero_grad()
                 loss.backward()
             if world > 1:
@@ -261,6 +298,9 @@ def make_parser():
                          'step per clip, the refinement state carried from chunk to chunk')
     ap.add_argument('--bptt', choices=['truncated', 'exact'], default='truncated',
                     help='with --clip-frames: no gradient across chunk boundaries, or the exact gradient of the whole clip by recomputation')
+    ap.add_argument('--ignore-border', type=int, default=0, metavar='N',
+                    help='train with zero observation weight on an N-pixel frame around every image (per-pixel weights: the border is not '
+                         'part of the objective, the reconstruction still covers it)')
     return ap
 
 
@@ -303,7 +343,7 @@ def main(argv=None):
     dl = make_dataloader(train_ds, args.batch, shuffle=True, rank=rank, world_size=world)
     losses = train(model, optimizer, dl, device, args.steps, checkpoint_path=args.save,
                    log=print if rank == 0 else (lambda *a: None), beta=args.beta, beta_warmup_steps=args.beta_warmup,
-                   bptt=args.bptt if args.clip_frames else None)
+                   bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border)
     ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device)
     if rank == 0:
         print('first loss {:.2f} -> last loss {:.2f}; Ari over all ranks: {}'.format(losses[0], losses[-1], ev.global_mean))

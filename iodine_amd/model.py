@@ -30,6 +30,24 @@ from the state the last chunk left - detached tensors give truncated back-propag
 gradient of the chunk (``iodine_train_backward_seq``), and ``attach_state=True`` leaves ``model.lstm_hidden`` attached to the graph like
 the reference, so that ``iodine_amd.engine.clip_backward`` computes the exact gradient of a long clip chunk by chunk.
 
+Per-pixel observation weights: ``forward`` / ``encode`` / ``reconstruct`` take ``weights=`` (the single-pass ELBO: ``weighted_elbo(x, weights)``; ``elbo`` keeps
+the reference's signature), a tensor ``(B, 1, S, S)`` or
+``(B, S, S)`` of numbers >= 0 (bool / uint8 / any float dtype; with a clip also ``(B, E, 1, S, S)`` / ``(B, E, S, S)``, one weight image per
+frame - a 4-D weight is used for every frame), for padded or invalid regions, inpainting ("explain what I observed, show ``pred``
+everywhere"), region-of-interest training, down-weighting a background:
+
+    LL = mean_b sum_p w_p sum_c logsumexp_k(log(m_k + 1e-12) + l_kc),    ELBO = LL - beta * KL     (not normalised by sum(w) or mean(w))
+
+    weighted      the reported LL / ELBO / loss (``elbo_terms[:, 0]`` and ``[:, 2]``, the logger's ``likelihood``, ``trajectory['ll']``);
+                  the closed-form inner gradients d(B ELBO)/d mean and /d mask and everything downstream of them, as autograd gives for
+                  the weighted objective: ``grad_post``, the layer-normed gradient channels of the refinement input, every outer gradient
+    not weighted  the refinement-input channels that describe the scene (``mask_posterior``, ``likelihood``,
+                  ``leave_one_out_likelihood``), the image channels, the KL
+
+Weights are data (no gradient; a tensor that requires grad is detached), their values the caller's contract (finite, >= 0, not checked on
+the device); zeros are allowed, an all-zero image included.  They hold for the one call they are passed to (``iodine_set_pixel_weights``
+is one-shot); ``weights=None`` and weights of all ones compute the same bits.
+
 Extensions over the reference: every entry point takes an optional ``eps`` tensor of shape
 (T+1, B, K, L) replacing the ``torch.randn_like`` draws of ``Gaussian.sample``
 (iodine.py:632) in call order, so that results can be compared with the CPU oracle.  Without
@@ -132,8 +150,8 @@ class _TrainStep(torch.autograd.Function):
     """``loss = model(x)`` / ``loss.backward()`` through iodine_train_forward / iodine_train_backward."""
 
     @staticmethod
-    def forward(ctx, module, x, eps, *params):
-        loss, elbo_iter = module._train_forward(x, eps)
+    def forward(ctx, module, x, eps, w, *params):
+        loss, elbo_iter = module._train_forward(x, eps, weights=w)
         ctx.module = module
         ctx.serial = module._call_serial            # identity of the saved forward (the library keeps exactly one)
         ctx.n = len(params)
@@ -143,7 +161,7 @@ class _TrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss, _grad_elbo):
         grads = ctx.module._train_backward(grad_loss, ctx.serial)
-        return (None, None, None, *grads)
+        return (None, None, None, None, *grads)
 
 
 class _TrainStepAttached(torch.autograd.Function):
@@ -155,10 +173,10 @@ class _TrainStepAttached(torch.autograd.Function):
     back when they require grad; ``attach`` False: loss and ELBO terms are the only outputs."""
 
     @staticmethod
-    def forward(ctx, module, x, eps, attach, s_pm, s_plv, s_h, s_c, *params):
+    def forward(ctx, module, x, eps, w, attach, s_pm, s_plv, s_h, s_c, *params):
         ctx.set_materialize_grads(False)                   # an output the loss does not use arrives as None -> a NULL pointer
         state = None if s_pm is None else (s_pm, s_plv, s_h, s_c)
-        loss, elbo_iter = module._train_forward(x, eps, state)
+        loss, elbo_iter = module._train_forward(x, eps, state, weights=w)
         ctx.module, ctx.serial, ctx.from_state = module, module._call_serial, state is not None
         ctx.BK = (x.shape[0], module.K)
         ctx.mark_non_differentiable(elbo_iter)
@@ -177,7 +195,7 @@ class _TrainStepAttached(torch.autograd.Function):
         n_in = len(ctx.needs_input_grad)
         if g_loss is None and all(g is None for g in aux) and g_h is None and g_c is None:
             return (None,) * n_in
-        want = tuple(ctx.from_state and ctx.needs_input_grad[4 + j] for j in range(4))
+        want = tuple(ctx.from_state and ctx.needs_input_grad[5 + j] for j in range(4))
         if g_h is None and g_c is None and not any(want):
             gstate = (None,) * 4
             grads = ctx.module._train_backward(g_loss, ctx.serial, aux)
@@ -185,7 +203,7 @@ class _TrainStepAttached(torch.autograd.Function):
             grads, gstate = ctx.module._train_backward_seq(g_loss, ctx.serial, aux, (g_h, g_c), want, ctx.BK)
         if ctx.from_state:                                 # the initial posterior is not part of a forward from a state: unused parameters
             grads = [None if n.startswith('posterior.') else g for (n, _), g in zip(ctx.module.named_parameters(), grads)]
-        return (None, None, None, None, *gstate, *grads)
+        return (None, None, None, None, None, *gstate, *grads)
 
 
 _WRAPPER_OPTIONS = ('batch_cap',)      # max images per library call (IODINE.max_batch); the rest go to iodine_set_option
@@ -197,8 +215,8 @@ class _ChunkedTrainStep(torch.autograd.Function):
     the parameter gradients accumulated with the chunk's share of the batch; ``loss.backward()`` then only scales them."""
 
     @staticmethod
-    def forward(ctx, module, x, eps, state, keep_state, *params):
-        loss, elbo_iter, flat = module._train_chunked(x, eps, state, keep_state)
+    def forward(ctx, module, x, eps, w, state, keep_state, *params):
+        loss, elbo_iter, flat = module._train_chunked(x, eps, state, keep_state, w)
         ctx.module, ctx.flat, ctx.from_state = module, flat, state is not None
         ctx.mark_non_differentiable(elbo_iter)
         return loss, elbo_iter
@@ -211,7 +229,7 @@ class _ChunkedTrainStep(torch.autograd.Function):
             # (from a detached state the initial posterior is not part of the forward: None, like unused parameters elsewhere)
             views.append(None if ctx.from_state and n.startswith('posterior.') else flat[off:off + p.numel()].view_as(p))
             off += p.numel()
-        return (None, None, None, None, None, *views)
+        return (None, None, None, None, None, None, *views)
 
 
 def _flat_views(module, flat, live):
@@ -278,16 +296,16 @@ class _ElboGrad(torch.autograd.Function):
     chunk's forward and backward at once with its share of the batch, and ``backward`` only scales - like _ChunkedTrainStep."""
 
     @staticmethod
-    def forward(ctx, module, x, eps, pm, plv, *params):
+    def forward(ctx, module, x, eps, w, pm, plv, *params):
         ctx.set_materialize_grads(False)
         ctx.module, ctx.init = module, pm is None
         want_p = any(p.requires_grad for p in params)
         want_post = pm is not None and (pm.requires_grad or plv.requires_grad)
         if x.shape[0] <= module.max_batch():
-            elbo = module._elbo_call(x, eps, pm, plv, save=True)
+            elbo = module._elbo_call(x, eps, pm, plv, save=True, weights=w)
             ctx.serial, ctx.pre, ctx.BK = module._call_serial, None, (x.shape[0], module.K)
             return elbo
-        elbo, ctx.pre = module._elbo_chunked_grad(x, eps, pm, plv, want_post, want_p)
+        elbo, ctx.pre = module._elbo_chunked_grad(x, eps, pm, plv, want_post, want_p, w)
         return elbo
 
     @staticmethod
@@ -301,10 +319,10 @@ class _ElboGrad(torch.autograd.Function):
             gs = g.to(torch.float32)
             gpm, gplv, flat = (None if t is None else t * gs for t in ctx.pre)
         else:
-            want_post = (not ctx.init) and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
-            gpm, gplv, flat = m._elbo_backward(ctx.serial, ctx.BK, g, want_post, any(ctx.needs_input_grad[5:]))
+            want_post = (not ctx.init) and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
+            gpm, gplv, flat = m._elbo_backward(ctx.serial, ctx.BK, g, want_post, any(ctx.needs_input_grad[6:]))
             flat = m._own(flat)
-        return (None, None, None, gpm if ctx.needs_input_grad[3] else None, gplv if ctx.needs_input_grad[4] else None,
+        return (None, None, None, None, gpm if ctx.needs_input_grad[4] else None, gplv if ctx.needs_input_grad[5] else None,
                 *_flat_views(m, flat, live))
 
 
@@ -605,6 +623,48 @@ class IODINE(nn.Module):
                                f'(B, {E}, {c}, {s}, {s}), one frame per evaluation, or images (B, {c}, {s}, {s}); got {tuple(x.shape)}')
         return x.detach().to(torch.float32).contiguous(), E
 
+    def _check_weights(self, weights, x, what):
+        """``weights=`` of a call on ``x`` (as given: images (B, C, S, S) or a clip (B, E, C, S, S)) -> None, or contiguous float32 on
+        x's device: (B, S, S), or (B, E, S, S) for one weight image per frame.  Accepted: (B, 1, S, S) / (B, S, S), with a clip also
+        (B, E, 1, S, S) / (B, E, S, S) - a 4-D (B, 1, S, S) weight goes to every frame.  Refused before any device work, like
+        ``_check_frames``; the values (finite, >= 0) are the caller's contract.  Weights are data: detached."""
+        if weights is None:
+            return None
+        if not torch.is_tensor(weights):
+            raise RuntimeError(f'IODINE.{what}: weights must be a tensor of per-pixel weights (bool, uint8 or a float dtype), or None; got '
+                               f'{type(weights).__name__}')
+        if not (weights.dtype in (torch.bool, torch.uint8) or weights.is_floating_point()):
+            raise RuntimeError(f'IODINE.{what}: weights must have dtype bool, uint8 or a float dtype; got {weights.dtype}')
+        B, s = x.shape[0], self.img_size
+        E = x.shape[1] if x.dim() == 5 else None
+        got = tuple(weights.shape)
+        per_frame = False
+        if got in ((B, 1, s, s), (B, s, s)):
+            pass
+        elif E is not None and got in ((B, E, 1, s, s), (B, E, s, s)):
+            per_frame = True
+        else:
+            if weights.dim() == 5 and E is None:
+                raise RuntimeError(f'IODINE.{what}: weights of shape {got} hold one weight image per frame, but x {tuple(x.shape)} is a '
+                                   f'batch of single images: expected weights ({B}, 1, {s}, {s}) or ({B}, {s}, {s})')
+            clip = f', or ({B}, {E}, 1, {s}, {s}) / ({B}, {E}, {s}, {s}) - one weight image per frame' if E is not None else ''
+            raise RuntimeError(f'IODINE.{what}: weights must have shape ({B}, 1, {s}, {s}) or ({B}, {s}, {s}){clip}, matching x '
+                               f'{tuple(x.shape)}; got {got}')
+        w = weights.detach().to(device=x.device, dtype=torch.float32)
+        return w.reshape((B, E, s, s) if per_frame else (B, s, s)).contiguous()
+
+    def _send_weights(self, h, w):
+        """Hand ``w`` (``_check_weights``; None: nothing to do, the library's default is no weights) to the handle for the compute call
+        that follows (iodine_set_pixel_weights: consumed and cleared by that call).  Graph mode: through the staging buffer 'w', like x."""
+        if w is None:
+            return None
+        L = _lib.lib()
+        if not hasattr(L, 'iodine_set_pixel_weights'):
+            raise RuntimeError('IODINE: weights= needs iodine_set_pixel_weights, which this build of libiodine_hip.so does not have')
+        ws = self._stage('w', w)
+        _lib.check(L.iodine_set_pixel_weights(h, _lib.ptr(ws), 1 if ws.dim() == 4 else 0), h, 'iodine_set_pixel_weights')
+        return ws
+
     def _check_state(self, state, B, K, device):
         """``state=`` of encode / reconstruct: (post_mean, post_logvar (B, K, L), h, c (B, K, MLP_UNITS)) as refinement_state returns it."""
         if state is None:
@@ -752,10 +812,11 @@ class IODINE(nn.Module):
         self.posterior.mean, self.posterior.logvar = pm, plv
 
     @torch.no_grad()
-    def _reconstruct(self, x, eps, want_images=True, state=None, trajectory=False, keep_state=False):
+    def _reconstruct(self, x, eps, want_images=True, state=None, trajectory=False, keep_state=False, weights=None):
         K, T = self._run_shape()
         obj = self._read_objective(T)
         x, frames = self._check_frames(x, T, 'encode / reconstruct')
+        weights = self._check_weights(weights, x, 'encode / reconstruct')
         dev, B = x.device, x.shape[0]
         stop = int(self._options.get('stop_after_iters', -1))
         n_it = stop if 0 <= stop <= T else T
@@ -772,7 +833,8 @@ class IODINE(nn.Module):
             outs, parts, sizes, pms, plvs, trs, sts = [], [], [], [], [], [], []
             for s, e in self._chunks(B, cap):
                 outs.append(self._reconstruct(x[s:e], None if eps is None else eps[:, s:e], want_images,
-                                              None if state is None else tuple(t[s:e] for t in state), trajectory))
+                                              None if state is None else tuple(t[s:e] for t in state), trajectory,
+                                              weights=None if weights is None else weights[s:e]))
                 parts.append(self._chunk_state()); sizes.append(e - s)
                 pms.append(self.posterior.mean); plvs.append(self.posterior.logvar)
                 trs.append(self.trajectory)
@@ -800,6 +862,7 @@ class IODINE(nn.Module):
         elbo = self._out('r.elbo', (n_it, 3), dev)
         args = [_lib.ptr(t) for t in (xs, eps, pred, mask, mean, z, pm, plv, elbo)]
         self._call_serial += 1
+        ws = self._send_weights(h, weights)                 # (ws: alive until the call is queued)
         if state is None and not trajectory:
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_reconstruct(h, self._stream(), B, *args), h, 'iodine_reconstruct'))
         else:
@@ -824,12 +887,12 @@ class IODINE(nn.Module):
             self._fetch_last_elbo(h, x, elbo[-1], frame=n_it - 1)   # what the reference's last elbo() call left behind
         return pred, mask, mean, z
 
-    def encode(self, x, eps=None, state=None, keep_state=False):
+    def encode(self, x, eps=None, state=None, keep_state=False, weights=None):
         """z (B, K, L) after T refinement iterations.  iodine.py:73-105.  ``x``: images (B, 3, S, S) or a clip (B, T, 3, S, S) -
-        iteration i then scores, differentiates and encodes frame i.  ``state`` / ``keep_state``: see ``reconstruct``."""
-        return self._reconstruct(x, eps, want_images=False, state=state, keep_state=keep_state)[3]
+        iteration i then scores, differentiates and encodes frame i.  ``state`` / ``keep_state`` / ``weights``: see ``reconstruct``."""
+        return self._reconstruct(x, eps, want_images=False, state=state, keep_state=keep_state, weights=weights)[3]
 
-    def reconstruct(self, x, eps=None, trajectory=False, state=None, keep_state=False):
+    def reconstruct(self, x, eps=None, trajectory=False, state=None, keep_state=False, weights=None):
         """pred (B,3,S,S), mask (B,K,1,S,S), mean (B,K,3,S,S).  iodine.py:107-112.
 
         ``x``: images (B, 3, S, S), or a clip (B, T, 3, S, S), batch first: ELBO evaluation i uses frame ``x[:, i]`` for the
@@ -848,8 +911,12 @@ class IODINE(nn.Module):
 
         ``keep_state``: matters only where the batch exceeds ``max_batch()`` and runs in chunks.  Every chunk re-uses the workspace,
         so the LSTM state of a chunked call has to be copied out chunk by chunk; that is done when ``keep_state``, ``state`` or
-        ``trajectory`` is given, and ``refinement_state()`` after a chunked call without any of them is refused."""
-        pred, mask, mean, _ = self._reconstruct(x, eps, state=state, trajectory=trajectory, keep_state=keep_state)
+        ``trajectory`` is given, and ``refinement_state()`` after a chunked call without any of them is refused.
+
+        ``weights``: per-pixel observation weights >= 0 of this call, (B, 1, S, S) / (B, S, S), with a clip also (B, T, 1, S, S) /
+        (B, T, S, S); see the module docstring for what is weighted.  The refinement then explains the weighted pixels only - a weight
+        of 0 takes a pixel out of the objective - while ``pred`` / ``mask`` / ``mean`` are still rendered everywhere (inpainting)."""
+        pred, mask, mean, _ = self._reconstruct(x, eps, state=state, trajectory=trajectory, keep_state=keep_state, weights=weights)
         return pred, mask, mean
 
     @torch.no_grad()
@@ -968,7 +1035,14 @@ class IODINE(nn.Module):
         ``model.posterior.mean`` / ``.logvar`` of this batch's shape requires grad; True - also without (gradients then go to the
         ``decoder.*`` parameters and, from the initial posterior, to ``posterior.init_mean / init_logvar``); False - never.
         ``elbo.backward()`` fills ``posterior.mean.grad / .logvar.grad`` and the parameter gradients as the reference's autograd does
-        (iodine.py:90,137); the value is the same bits either way.  One differentiable call is kept: backward before the next call."""
+        (iodine.py:90,137); the value is the same bits either way.  One differentiable call is kept: backward before the next call.
+        With per-pixel observation weights: ``weighted_elbo``."""
+        return self.weighted_elbo(x, None, eps, differentiable)
+
+    def weighted_elbo(self, x, weights, eps=None, differentiable=None):
+        """``elbo(x, eps, differentiable)`` under per-pixel observation weights (B, 1, S, S) / (B, S, S) of the log-likelihood (module
+        docstring; None: no weights): value, ``elbo_terms`` and the gradients are those of the weighted ELBO.  ``elbo`` keeps the
+        reference's signature, so the weights of a single-pass ELBO are an argument of this method."""
         pm, plv = self.posterior.mean, self.posterior.logvar
         shape = (x.shape[0], self.K, self.dim_latent) if x.dim() == 4 else None
         given = pm is not None and plv is not None and tuple(pm.shape) == shape and pm.device == x.device
@@ -976,11 +1050,12 @@ class IODINE(nn.Module):
             differentiable = given and (pm.requires_grad or plv.requires_grad)
         if differentiable and torch.is_grad_enabled():
             xc = self._check_x(x)                           # (model.K / n_iters are checked by _elbo_call, before any device work)
-            return _ElboGrad.apply(self, xc, eps, pm if given else None, plv if given else None, *self._ordered_params())
-        return self._elbo_nograd(x, eps)
+            w = self._check_weights(weights, xc, 'weighted_elbo')
+            return _ElboGrad.apply(self, xc, eps, w, pm if given else None, plv if given else None, *self._ordered_params())
+        return self._elbo_nograd(x, eps, weights)
 
     @torch.no_grad()
-    def _elbo_nograd(self, x, eps=None):
+    def _elbo_nograd(self, x, eps=None, weights=None):
         """Single-pass ELBO (iodine.py:161-241): one sample from the current posterior (``self.posterior.mean / logvar`` as
         left by the last call for this batch size; otherwise the initial posterior of ``init_unit``, iodine.py:607-618),
         decode, mixture log-likelihood minus KL.  Sets ``self.z / mean / mask / mask_logits`` and the logger entries like the
@@ -989,6 +1064,7 @@ class IODINE(nn.Module):
         K, T = self._run_shape()
         self._read_objective(T)
         x = self._check_x(x)
+        weights = self._check_weights(weights, x, 'weighted_elbo')
         dev, B = x.device, x.shape[0]
         cap = self.max_batch()
         if B > cap:
@@ -998,7 +1074,7 @@ class IODINE(nn.Module):
             for s, e in self._chunks(B, cap):
                 # the chunk's slice of the current posterior (or the initial posterior, as for a whole batch)
                 self.posterior.mean, self.posterior.logvar = (pm0[s:e], plv0[s:e]) if whole else (None, None)
-                self._elbo_nograd(x[s:e], None if eps is None else eps[s:e])
+                self._elbo_nograd(x[s:e], None if eps is None else eps[s:e], None if weights is None else weights[s:e])
                 parts.append(self._chunk_state()); sizes.append(e - s)
             self.posterior.mean, self.posterior.logvar = pm0, plv0
             self._merge_chunk_state(parts, sizes, x)
@@ -1006,11 +1082,11 @@ class IODINE(nn.Module):
         pm, plv = self.posterior.mean, self.posterior.logvar
         if pm is None or plv is None or tuple(pm.shape) != (B, K, self.dim_latent) or pm.device != dev:
             pm = plv = None
-        return self._elbo_call(x, eps, pm, plv, save=False)
+        return self._elbo_call(x, eps, pm, plv, save=False, weights=weights)
 
-    def _elbo_call(self, x, eps, pm, plv, save):
+    def _elbo_call(self, x, eps, pm, plv, save, weights=None):
         """One iodine_elbo of at most ``max_batch`` images from the posterior (pm, plv) - None: the initial one; ``save``: kept for
-        iodine_elbo_backward.  x as ``_check_x`` returns it."""
+        iodine_elbo_backward.  x as ``_check_x``, weights as ``_check_weights`` return them."""
         K, T = self._run_shape()
         obj = self._read_objective(T)
         dev, B = x.device, x.shape[0]
@@ -1025,6 +1101,7 @@ class IODINE(nn.Module):
         terms = self._out('e.terms', (3,), dev)
         xs = self._stage('x', x)
         self._call_serial += 1
+        ws = self._send_weights(h, weights)
         if save:
             self._saving(h, True)
         try:
@@ -1057,7 +1134,7 @@ class IODINE(nn.Module):
         self._call_serial += 1                      # the saved pass is consumed (no retain_graph)
         return self._own(gpm), self._own(gplv), flat          # (flat: the caller takes its copy - graph mode - after its last chunk)
 
-    def _elbo_chunked_grad(self, x, eps, pm, plv, want_post, want_p):
+    def _elbo_chunked_grad(self, x, eps, pm, plv, want_post, want_p, weights=None):
         """Differentiable elbo of a batch above ``max_batch`` (see _ElboGrad): forward + backward of every chunk with its share of the
         batch mean.  Returns the ELBO and (d / d posterior.mean, d / d posterior.logvar, flat parameter gradients) for grad_output 1."""
         dev, B = x.device, x.shape[0]
@@ -1065,7 +1142,7 @@ class IODINE(nn.Module):
         pm0, plv0 = self.posterior.mean, self.posterior.logvar
         for s, e in self._chunks(B, self.max_batch()):
             self._elbo_call(x[s:e].contiguous(), None if eps is None else eps[s:e], None if pm is None else pm[s:e],
-                            None if plv is None else plv[s:e], save=True)
+                            None if plv is None else plv[s:e], save=True, weights=None if weights is None else weights[s:e].contiguous())
             parts.append(self._chunk_state()); sizes.append(e - s)
             w = torch.full((), (e - s) / float(B), device=dev, dtype=torch.float32)
             gpm, gplv, flat = self._elbo_backward(self._call_serial, (e - s, self.K), w, want_post, want_p, flat)
@@ -1079,7 +1156,7 @@ class IODINE(nn.Module):
         return self.elbo_terms[0, 0].clone(), pre
 
     # ---- training: iodine.py:115-158 + lib/engine/train.py:60-63 -------------------------------------
-    def forward(self, x, eps=None, state=None, attach_state=False, keep_state=False):
+    def forward(self, x, eps=None, state=None, attach_state=False, keep_state=False, weights=None):
         """-sum_i w_i ELBO_i (w = ``model.iter_weights``, by default (i+1)/(T+1); ELBO_i = LL_i - ``model.beta`` KL_i at ``model.sigma``),
         differentiable wrt every parameter.  ``loss.backward()`` differentiates the forward as it
         ran, at the (K, T) it read - like the reference, whose autograd graph is fixed at forward time.  ``x``: images
@@ -1107,10 +1184,14 @@ class IODINE(nn.Module):
         call ``backward()`` once - a second one (``aux.backward()`` followed by ``loss.backward()``) raises the stale-forward error.
 
         A batch above ``max_batch(training=True)`` runs in chunks, each chunk's backward inside the forward: a detached ``state`` is sliced
-        per chunk and ``keep_state`` gathers the chunks' states; ``attach_state`` and a ``state`` that requires grad are refused there."""
+        per chunk and ``keep_state`` gathers the chunks' states; ``attach_state`` and a ``state`` that requires grad are refused there.
+
+        ``weights``: per-pixel observation weights >= 0 of this call, (B, 1, S, S) / (B, S, S), with a clip also (B, T+1, 1, S, S) /
+        (B, T+1, S, S): the loss and every gradient are those of the weighted ELBO (module docstring).  No gradient flows to them."""
         K, T = self._run_shape()
         self._read_objective(T)                      # (refusals before any device work; _train_forward hands it to the handle)
         x, _ = self._check_frames(x, T + 1, 'forward' if state is None else 'forward from a state')
+        weights = self._check_weights(weights, x, 'forward')
         B = x.shape[0]
         state = self._check_train_state(state, B, K, x.device)
         self._state = None                          # the state of an earlier encode / reconstruct ends here (refinement_state)
@@ -1125,18 +1206,18 @@ class IODINE(nn.Module):
                                        'batch per call')
             if state is not None:
                 state = tuple(t.detach() for t in state)
-            loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, state, bool(keep_state), *self._ordered_params())
+            loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, weights, state, bool(keep_state), *self._ordered_params())
             self.elbo_terms = elbo_iter
             return loss
         eps = self._eps(eps, B, x.device)
         if attach:
             (loss, elbo_iter, self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc
-             ) = _TrainStepAttached.apply(self, x, eps, True, *(state or (None,) * 4), *self._ordered_params())
+             ) = _TrainStepAttached.apply(self, x, eps, weights, True, *(state or (None,) * 4), *self._ordered_params())
             self.lstm_hidden = (lh, lc)
         elif state is not None:
-            loss, elbo_iter = _TrainStepAttached.apply(self, x, eps, False, *state, *self._ordered_params())
+            loss, elbo_iter = _TrainStepAttached.apply(self, x, eps, weights, False, *state, *self._ordered_params())
         else:
-            loss, elbo_iter = _TrainStep.apply(self, x, eps, *self._ordered_params())
+            loss, elbo_iter = _TrainStep.apply(self, x, eps, weights, *self._ordered_params())
         self.elbo_terms = elbo_iter
         with torch.no_grad():
             h, dev = self._handle, x.device
@@ -1160,7 +1241,7 @@ class IODINE(nn.Module):
                                              h, 'iodine_last_train_state'))
         return hh, cc
 
-    def _train_forward(self, x, eps, state=None):
+    def _train_forward(self, x, eps, state=None, weights=None):
         dev, B = x.device, x.shape[0]
         K, T = self._run_shape()
         obj = self._read_objective(T)
@@ -1171,6 +1252,7 @@ class IODINE(nn.Module):
         elbo_iter = self._out('t.elbo', (T + 1, 3), dev)
         xs, eps = self._stage('x', x), self._stage('eps', eps)
         self._call_serial += 1
+        ws = self._send_weights(h, weights)                 # (ws: alive until the call is queued)
         if state is None:
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward(h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps),
                                                                                  _lib.ptr(loss), _lib.ptr(elbo_iter)),
@@ -1183,7 +1265,7 @@ class IODINE(nn.Module):
                 h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), ptrs, _lib.ptr(loss), _lib.ptr(elbo_iter)), h, 'iodine_train_forward_seq'))
         return self._own(loss), self._own(elbo_iter)
 
-    def _train_chunked(self, x, eps, state=None, keep_state=False):
+    def _train_chunked(self, x, eps, state=None, keep_state=False, weights=None):
         """Forward + backward of every chunk (see _ChunkedTrainStep): returns the batch loss, the (T+1, 3) ELBO terms of the whole
         batch and d loss / d parameters as one flat buffer in named_parameters() order.  ``state``: a detached initial state, cut along
         the batch; ``keep_state``: every chunk's LSTM state is copied out for ``refinement_state``."""
@@ -1193,7 +1275,8 @@ class IODINE(nn.Module):
         for c, (s, e) in enumerate(self._chunks(B, self.max_batch(training=True))):
             xc = x[s:e].contiguous()
             ec = self._eps(None if eps is None else eps[:, s:e], e - s, dev)
-            lc, tc = self._train_forward(xc, ec, None if state is None else tuple(t[s:e].contiguous() for t in state))
+            lc, tc = self._train_forward(xc, ec, None if state is None else tuple(t[s:e].contiguous() for t in state),
+                                         None if weights is None else weights[s:e].contiguous())
             h = self._handle
             w = torch.full((), (e - s) / float(B), device=dev, dtype=torch.float32)
             ws = self._stage('t.gl', w)
