@@ -317,6 +317,41 @@ int iodine_train_backward_seq(iodine_handle* h, void* stream, const float* grad_
                               const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
                               const float* g_lstm_h, const float* g_lstm_c, float* flat_grads, int accumulate, float* const* g_state);
 
+/* Per-frame auxiliary losses: chosen ELBO evaluations of the training forward, attached (the reference leaves self.z / mean / mask /
+ * mask_logits and posterior.mean / logvar of EVERY elbo() call of IODINE.forward on the graph; a tracker trained one frame per evaluation
+ * puts a loss on each of them).
+ *
+ * iodine_train_forward_frames: iodine_train_forward_seq (state_in NULL or given) that also writes out what the listed evaluations decoded.
+ *   frame_idx: n_frames evaluation indices in HOST memory, ascending, unique, each in 0..T (T = the final evaluation).
+ *   frames_out: six device pointers {z (n_frames,B,K,L), mean (n_frames,B,K,3,S,S), mask, mask_logits (n_frames,B,K,1,S,S), post_mean,
+ *     post_logvar (n_frames,B,K,L)}, evaluation first, NCHW, like the traj buffers of iodine_reconstruct_seq; each may be NULL.  Entry j is
+ *     what evaluation frame_idx[j] decoded and the lambda it sampled z from.
+ * n_frames = 0: iodine_train_forward_seq, launch for launch.  Loss, ELBO terms and everything the forward saves are the same bits for any
+ * list; per listed evaluation the call adds one rendering launch and three small copies.
+ *
+ * iodine_train_backward_frames: iodine_train_backward_seq plus cotangents on chosen evaluations (n_frames = 0, or every g_frames pointer
+ * NULL: that entry, bit for bit).
+ *   frame_idx / n_frames: as above; the list is independent of the forward's (every z_i is kept by a training forward).
+ *   g_frames: six device pointers in the order {g_z, g_mean, g_mask, g_logits, g_post_mean, g_post_logvar}, each (n_frames, B, ..) as above
+ *     or NULL (= zero).
+ * For a listed evaluation i < T the decoder runs again from the saved z_i with the launches the forward ran; the rendering backward of
+ * (g_mean, g_mask, g_logits) and ONE decoder pass with factor 1 give the decoder.* gradients and dz_i; d mu_i = dz_i + g_z + g_post_mean,
+ * d logvar_i = (dz_i + g_z) * 1/2 exp(logvar_i / 2) eps_i + g_post_logvar (no KL term).  For i >= 1 the two join d loss / d delta_{i-1}
+ * (lambda_i = detach(lambda_{i-1}) + delta_{i-1}) and follow the head, the LSTM carries and the refinement convs back to iteration 0; for
+ * i = 0 they go to posterior.init_mean / init_logvar as column sums, or - after a forward from a state - are added to g_state[0] / [1], and
+ * nothing of them reaches refine.*.  An evaluation whose three image-shaped cotangents are all NULL takes no decoder pass.  Evaluation T
+ * takes the path of the final state's cotangents (kept activations, no re-decode); given both ways, the two sets add.  Like them, none of
+ * these terms is multiplied by *grad_loss_dev.  Cost: one decoder forward (i < T) and one decoder backward pass per listed evaluation with an
+ * image-shaped cotangent.  The re-decode overwrites the decoder output of the final elbo(): iodine_last_elbo_outputs then answers
+ * IODINE_ERR_STATE until the next compute call; iodine_last_posterior and iodine_last_train_state stay valid.  Refused before any launch
+ * with IODINE_ERR_INVALID: indices out of range, unsorted or repeated, n_frames < 0, a NULL array with n_frames > 0. */
+int iodine_train_forward_frames(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in,
+                                float* loss, float* elbo_iter, const int* frame_idx, int n_frames, float* const* frames_out);
+int iodine_train_backward_frames(iodine_handle* h, void* stream, const float* grad_loss_dev, const float* g_mean, const float* g_mask,
+                                 const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
+                                 const float* g_lstm_h, const float* g_lstm_c, float* flat_grads, int accumulate, float* const* g_state,
+                                 const int* frame_idx, int n_frames, const float* const* g_frames);
+
 /* logger.update(init_mean=posterior.init_mean.mean(), init_logvar=posterior.init_logvar.mean()) -- iodine.py:156-157:
  * out2 (2, device) = the two means of the parameters last handed to iodine_set_params. */
 int iodine_logger_scalars(iodine_handle* h, void* stream, float* out2);

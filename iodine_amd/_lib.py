@@ -32,6 +32,7 @@ EXPORTS = (
     'iodine_set_objective',
     'iodine_train_forward_seq', 'iodine_train_backward_seq', 'iodine_last_train_state',
     'iodine_set_pixel_weights',
+    'iodine_train_forward_frames', 'iodine_train_backward_frames',
 )
 
 
@@ -138,6 +139,9 @@ def lib() -> C.CDLL:
         L.iodine_last_train_state.argtypes = [vp, vp, ci, vp, vp]
     if hasattr(L, 'iodine_set_pixel_weights'):          # (weights=; absent from older A/B builds, which refuse the keyword)
         L.iodine_set_pixel_weights.argtypes = [vp, vp, ci]
+    if hasattr(L, 'iodine_train_forward_frames'):       # (attach_frames=; absent from older A/B builds, which refuse the keyword)
+        L.iodine_train_forward_frames.argtypes = [vp, vp, ci, vp, vp, C.POINTER(vp), vp, vp, C.POINTER(ci), ci, C.POINTER(vp)]
+        L.iodine_train_backward_frames.argtypes = [vp, vp] + [vp] * 10 + [ci, C.POINTER(vp), C.POINTER(ci), ci, C.POINTER(vp)]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

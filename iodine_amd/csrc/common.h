@@ -199,7 +199,9 @@ hipError_t launch_render_bwd_logits(hipStream_t st, const float* dec, const floa
 // seeds [N][L] of the head BPTT's first step from cotangents on the final evaluation of a training forward: dz = Rc . wclsT (Rc NULL: 0) + c_z,
 // seed_m = dz + c_pm, seed_v = dz * (z - pm) / 2 + c_plv (z - pm = exp(logvar / 2) eps; no KL term); c_* may be NULL
 hipError_t launch_latent_seed(hipStream_t st, const float* Rc, const float* wclsT, int N, int L, int C, const float* c_z, const float* c_pm,
-                              const float* c_plv, const float* z, const float* pm, float* seed_m, float* seed_v);
+                              const float* c_plv, const float* z, const float* pm, float* seed_m, float* seed_v,
+                              int ldpm = 0,             // row stride of pm (0 = L): mu_i inside the saved refinement input [N][4 L]
+                              const float* c_z2 = nullptr, const float* c_pm2 = nullptr, const float* c_plv2 = nullptr);   // a second set, added
 // dz = Rc . wclsT without the KL / layer-norm terms of launch_dz_latent; pm != NULL: the posterior gradients of one ELBO instead (scale = 1 / B)
 hipError_t launch_dz_plain(hipStream_t st, const float* Rc, const float* wclsT, int N, int L, int C, float* dz_out, const float* pm,
                            const float* plv, const float* eps, float scale, float* g_pm, float* g_plv, float beta);
@@ -285,7 +287,8 @@ hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_pl
                             const float* seed_m, const float* seed_v, const float* gl_dev,
                             const float* wtab,        // wtab: T + 1 loss weights, NULL = the default (i + 2) / (T + 1)
                             const float* dh_in = nullptr, const float* dc_in = nullptr,    // [N][H] cotangents on (h_T, c_T): initial carries
-                            float* dh_out = nullptr, float* dc_out = nullptr);             // [N][H] d / d (h_0, c_0): the carries left (seeded instance only)
+                            float* dh_out = nullptr, float* dc_out = nullptr,              // [N][H] d / d (h_0, c_0): the carries left (seeded instance only)
+                            size_t seed_stride = 0);  // != 0: seed_m / seed_v are [T][N][L] (stride in floats), slice i joins step i; 0: step T - 1 alone
 // split-precision (3 x fp16 MFMA) variant of the stride-1 tile conv
 hipError_t launch_pack_conv_weights_f16(hipStream_t st, const float* src, int O, int I, int cin, int cout, int tflip,
                                         float* meta, void* dst);

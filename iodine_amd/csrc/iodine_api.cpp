@@ -402,7 +402,7 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
         b.rdpre.resize(h->Dr);
         int s = h->S;
         for (int l = 0; l < h->Dr; ++l) { s = ref_out_size(h, s); b.rdpre[l] = a.take<float>((size_t)T * N * s * s * Cr); }
-        b.aux_seed = a.take<float>((size_t)2 * N * L);
+        b.aux_seed = a.take<float>((size_t)2 * (T + 1) * N * L);
     }
     if (gen_dec) {
         b.gen_l0 = a.take<float>(gen_l0_scratch_floats(N, h->S, Cd, h->kd));   // row / tap sums, prefix table of the broadcast layer
@@ -850,9 +850,27 @@ int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, co
     return IODINE_OK;
 }
 
-int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss, const float* const* state_in)
+// the list of chosen evaluations of iodine_train_forward_frames / iodine_train_backward_frames (n == 0: nothing to check)
+int train_frames_check(iodine_handle* h, const char* who, const int* idx, int n, const void* ptrs)
+{
+    if (n < 0) return h->fail(IODINE_ERR_INVALID, std::string(who) + ": n_frames must be >= 0");
+    if (n == 0) return IODINE_OK;
+    if (!idx || !ptrs) return h->fail(IODINE_ERR_INVALID, std::string(who) + ": frame_idx and the array of six pointers are required with n_frames > 0");
+    for (int j = 0; j < n; ++j)
+        if (idx[j] < 0 || idx[j] > h->T || (j > 0 && idx[j] <= idx[j - 1])) {
+            char m[256];
+            snprintf(m, sizeof m, ": frame_idx must be ascending and unique with values in 0..%d (a forward of %d iterations makes %d ELBO "
+                                  "evaluations); entry %d is %d", h->T, h->T, h->T + 1, j, idx[j]);
+            return h->fail(IODINE_ERR_INVALID, std::string(who) + m);
+        }
+    return IODINE_OK;
+}
+
+int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss, const float* const* state_in,
+                        const FrameSet* fr)
 {
     char m[256];
+    if (fr) if (int rc = train_frames_check(h, "iodine_train_forward_frames", fr->idx, fr->n, fr->out)) return rc;
     if (state_in && !(state_in[0] && state_in[1] && state_in[2] && state_in[3]))
         return h->fail(IODINE_ERR_INVALID, "iodine_train_forward_seq: an initial state needs all four tensors - post_mean, post_logvar (B,K,L) and "
                                            "the LSTM state h, c (B,K,MLP_UNITS)");
@@ -883,6 +901,10 @@ int train_backward_check(iodine_handle* h, float* const* param_grads, int n, con
     if (n != (int)h->params.size() || !param_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward: wrong parameter count");
     if (h->buf.mode != 1 || h->buf.B != h->calls.fwd_batch || h->buf.K != h->K || h->buf.T != h->T)
         return h->fail(IODINE_ERR_STATE, "iodine_train_backward: the training workspace of the forward pass was re-planned");
+    if (aux && aux->frames)
+        if (int rc = train_frames_check(h, "iodine_train_backward_frames", aux->frames->idx, aux->frames->n, aux->frames->g)) return rc;
+    if (aux && aux->frames && aux->frames->n > 0 && h->Cd < 4)
+        return h->fail(IODINE_ERR_INVALID, "iodine_train_backward_frames: needs DEC.CONV_CHAN >= 4");
     if (aux && aux->g_state && !h->calls.fwd_from_state)
         return h->fail(IODINE_ERR_STATE, "iodine_train_backward_seq: g_state asks for the gradient of an initial state, but the saved forward ran "
                                          "without one (iodine_train_forward / iodine_train_forward_seq with state_in = NULL start from "
@@ -919,6 +941,9 @@ static int last_check(iodine_handle* h, bool stale, const char* who, const char*
 }
 int last_elbo_outputs_check(iodine_handle* h, int count)
 {
+    if (h->calls.redecoded && h->calls.last_elbo_iter >= 0 && h->buf.bytes != 0)
+        return h->fail(IODINE_ERR_STATE, "iodine_last_elbo_outputs: iodine_train_backward_frames has decoded an earlier evaluation again since, "
+                                         "the decoder output of the forward's final elbo() is gone (read it before the backward)");
     return last_check(h, h->calls.last_elbo_iter < 0, "iodine_last_elbo_outputs", ": no elbo() has run on the current workspace", count);
 }
 int last_posterior_check(iodine_handle* h, int count)
@@ -1770,10 +1795,28 @@ int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float*
 int iodine_train_forward_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in,
                              float* loss, float* elbo_iter)
 {
+    return train_forward_impl(h, stream, batch, x, eps, state_in, loss, elbo_iter, nullptr);
+}
+
+int iodine_train_forward_frames(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in,
+                                float* loss, float* elbo_iter, const int* frame_idx, int n_frames, float* const* frames_out)
+{
     if (!h) return IODINE_ERR_INVALID;
-    if (h->shim) return pad_train_forward(h, stream, batch, x, eps, state_in, loss, elbo_iter);
+    if (n_frames == 0) return train_forward_impl(h, stream, batch, x, eps, state_in, loss, elbo_iter, nullptr);
+    FrameSet fr; fr.idx = frame_idx; fr.n = n_frames; fr.out = frames_out;
+    return train_forward_impl(h, stream, batch, x, eps, state_in, loss, elbo_iter, &fr);
+}
+
+}  // extern "C"
+
+// fr == NULL: iodine_train_forward_seq, every launch as before; otherwise the listed evaluations are also written out
+int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in, float* loss,
+                       float* elbo_iter, const FrameSet* fr)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_train_forward(h, stream, batch, x, eps, state_in, loss, elbo_iter, fr);
     const PixelWeights pw(h);
-    int rc = train_forward_check(h, batch, x, eps, loss, state_in);
+    int rc = train_forward_check(h, batch, x, eps, loss, state_in, fr);
     if (rc) return rc;
     rc = ensure_workspace(h, batch, 1);
     if (rc) return rc;
@@ -1793,11 +1836,26 @@ int iodine_train_forward_seq(iodine_handle* h, void* stream, int batch, const fl
             HIPCHK(h, hipMemcpyAsync(b.c[0], state_in[3], sizeof(float) * (size_t)N * h->H, hipMemcpyDeviceToDevice, st));
         } else
             HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, L, h->H));
+        int fj = 0;                                        // next entry of the list of chosen evaluations
         for (int i = 0; i <= T; ++i) {
             // d loss / d (B * ELBO_i) = -w_i / B; the default weighting keeps its closed form
             const float alpha = h->obj.whost ? -h->obj.whost[i] / (float)B : -((float)(i + 1) / (float)(T + 1)) / (float)B;
             int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, true, alpha);
             if (r) return r;
+            if (fr && fj < fr->n && fr->idx[fj] == i) {
+                // what this evaluation decoded and the lambda it sampled from (buf.pm / plv: the refinement step below moves them on);
+                // its decoder backward above only read dec_out
+                float* const* o = fr->out;
+                const size_t NP = (size_t)N * h->P;
+                if (o[1] || o[2] || o[3])
+                    HIPCHK(h, launch_final_out(st, b.dec_out, nullptr, o[2] ? o[2] + fj * NP : nullptr, o[1] ? o[1] + fj * NP * 3 : nullptr,
+                                               o[3] ? o[3] + fj * NP : nullptr, B, h->K, h->P));
+                float* const dst[3] = {o[0], o[4], o[5]};
+                const float* const src[3] = {b.z[i], b.pm, b.plv};
+                for (int q = 0; q < 3; ++q)
+                    if (dst[q]) HIPCHK(h, hipMemcpyAsync(dst[q] + fj * eps_stride, src[q], sizeof(float) * eps_stride, hipMemcpyDeviceToDevice, st));
+                ++fj;
+            }
             if (i == 0 && !state_in) {
                 // lambda_0 = init_mean / init_logvar repeated over (B, K) (iodine.py:615-616): their gradient is the
                 // column sum of d loss / d lambda_0; later lambdas are detached from it (iodine.py:642-643).  From a caller's state the two
@@ -1816,6 +1874,11 @@ int iodine_train_forward_seq(iodine_handle* h, void* stream, int batch, const fl
     };
     std::vector<uintptr_t> key = graph_key(h, 4, B, {x, eps, loss, elbo_iter}, nullptr, &pw);
     for (int j = 0; j < 4; ++j) key.push_back((uintptr_t)(state_in ? state_in[j] : nullptr));     // (all four NULL: no state)
+    if (fr) {                                              // the list is baked into the captured launches like every address
+        key.push_back((uintptr_t)fr->n);
+        for (int j = 0; j < fr->n; ++j) key.push_back((uintptr_t)fr->idx[j]);
+        for (int j = 0; j < 6; ++j) key.push_back((uintptr_t)fr->out[j]);
+    }
     rc = run_graphed(h, st, key, body);
     if (rc) return rc;
     CallState& cs = h->calls;
@@ -1830,8 +1893,6 @@ int iodine_train_forward_seq(iodine_handle* h, void* stream, int batch, const fl
     cs.last_elbo_batch = B;
     return IODINE_OK;
 }
-
-}  // extern "C"
 
 // aux != NULL: the backward with auxiliary cotangents (iodine_train_backward_aux) - grad_scale / grad_scale_dev are then not used, aux->gl
 // takes their place; aux == NULL: the plain backward, every launch as before
@@ -1857,11 +1918,25 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
         for (const void* q : {aux->gl, aux->mean, aux->mask, aux->logits, aux->z, aux->pm, aux->plv, aux->lstm_h, aux->lstm_c}) key.push_back((uintptr_t)q);
         for (int j = 0; j < 4; ++j) key.push_back((uintptr_t)(aux->g_state ? aux->g_state[j] : nullptr));
     }
+    // iodine_train_backward_frames: cotangents on chosen evaluations (kinds in the order of FrameSet)
+    const FrameSet* fr = aux && aux->frames && aux->frames->n > 0 ? aux->frames : nullptr;
+    bool redecode = false;                                       // does an evaluation i < T take a decoder pass?
+    if (fr) {
+        key.push_back(2); key.push_back((uintptr_t)fr->n);
+        for (int j = 0; j < fr->n; ++j) key.push_back((uintptr_t)fr->idx[j]);
+        for (int j = 0; j < 6; ++j) key.push_back((uintptr_t)fr->g[j]);
+        for (int j = 0; j < fr->n; ++j) redecode = redecode || (fr->idx[j] < h->T && (fr->g[1] || fr->g[2] || fr->g[3]));
+    }
     auto body = [&]() -> int {
     Buffers& b = h->buf;
     const int B = h->calls.fwd_batch, N = B * h->K, T = h->T, L = h->L, H = h->H, Cr = h->Cr, IN = H + 4 * L;
     const ParamSlots& ps = h->slot;
     float *seed_m = nullptr, *seed_v = nullptr;
+    size_t seed_stride = 0;
+    const float *seed0_m = nullptr, *seed0_v = nullptr;           // seeds of evaluation 0: d / d lambda_0
+    const size_t NL = (size_t)N * L, NP = (size_t)N * h->P;
+    // cotangent of kind q on entry j of the list
+    auto fg = [&](int q, int j, size_t per) -> const float* { return fr->g[q] ? fr->g[q] + (size_t)j * per : nullptr; };
     // iodine_train_backward_seq: cotangents on (h_T, c_T) start the carries of iteration T - 1, the carries left after iteration 0 are
     // d / d (h_0, c_0) of the state the forward started from
     const float *cot_h = aux ? aux->lstm_h : nullptr, *cot_c = aux ? aux->lstm_c : nullptr;
@@ -1872,6 +1947,59 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
         // factor 1; the ELBO seeds of the BPTT are multiplied on the device; the hand-over at the end runs with scale 1.
         HIPCHK(h, launch_scale_dev_add(st, h->gacc_arena, aux->gl, nullptr, (int)h->gacc_total));
         const bool dec = aux->mean || aux->mask || aux->logits;
+        const float* const wl = dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT;
+        if (fr) {
+            // Cotangents on chosen evaluations.  Evaluation T (last in the list) first, on the kept activations like the final state's
+            // cotangents above - and added to them where both are given: the rendering backward is linear in the cotangents, so the second
+            // set is rendered into the (free) ping-pong buffer and added before the ONE decoder pass.
+            const int jT = fr->idx[fr->n - 1] == T ? fr->n - 1 : -1;
+            const float *t_mean = jT >= 0 ? fg(1, jT, NP * 3) : nullptr, *t_mask = jT >= 0 ? fg(2, jT, NP) : nullptr,
+                        *t_logits = jT >= 0 ? fg(3, jT, NP) : nullptr;
+            const bool decf = t_mean || t_mask || t_logits;
+            if (dec)
+                PROF(h, st, "render_bwd", launch_render_bwd_logits(st, b.dec_out, nullptr, aux->mask, aux->mean, aux->logits, b.g, B, h->K, h->P,
+                                                                   h->precision == 0));
+            if (decf)
+                PROF(h, st, "render_bwd", launch_render_bwd_logits(st, b.dec_out, nullptr, t_mask, t_mean, t_logits, dec ? b.dpre[0] : b.g, B, h->K,
+                                                                   h->P, h->precision == 0));
+            if (dec && decf) HIPCHK(h, launch_axpy_dev(st, b.dpre[0], 1.f, nullptr, b.g, (int)(NP * 4), 1));
+            float* dpre0 = nullptr;
+            if (dec || decf)
+                if (int r = decoder_backward_data(h, st, N, &dpre0, true, 1.f, T, true)) return r;
+            // seeds of every evaluation: slice e of [T + 1][N][L]; slices 1 .. T are what the head's BPTT adds at iteration e - 1
+            float *m_all = b.aux_seed, *v_all = b.aux_seed + (size_t)(T + 1) * NL;
+            HIPCHK(h, launch_zero_fill(st, b.aux_seed, (size_t)2 * (T + 1) * NL));
+            HIPCHK(h, launch_latent_seed(st, dec || decf ? b.Rc : nullptr, wl, N, L, h->Cd, aux->z, aux->pm, aux->plv, b.z[T], b.pm,
+                                         m_all + (size_t)T * NL, v_all + (size_t)T * NL, L, jT >= 0 ? fg(0, jT, NL) : nullptr,
+                                         jT >= 0 ? fg(4, jT, NL) : nullptr, jT >= 0 ? fg(5, jT, NL) : nullptr));
+            // every other listed evaluation: decoded again from the saved z_i with the launches the forward ran (they overwrite V, the
+            // activations, dec_out and g), rendering backward, ONE decoder pass with factor 1, seeds from (z_i, mu_i); mu_i is the first L
+            // of every row of the saved refinement input latent[i], written from buf.pm before the head moved it on
+            for (int j = 0; j < fr->n; ++j) {
+                const int i = fr->idx[j];
+                if (i == T) continue;
+                const float *c_mean = fg(1, j, NP * 3), *c_mask = fg(2, j, NP), *c_logits = fg(3, j, NP), *c_z = fg(0, j, NL),
+                            *c_pm = fg(4, j, NL), *c_plv = fg(5, j, NL);
+                const bool deci = c_mean || c_mask || c_logits;
+                if (!deci && !c_z && !c_pm && !c_plv) continue;
+                if (deci) {
+                    HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, b.z[i], h->wcls, nullptr, b.V, N, L, h->Cd));
+                    if (int r = decoder_forward(h, st, N, b.z[i])) return r;
+                    PROF(h, st, "render_bwd", launch_render_bwd_logits(st, b.dec_out, nullptr, c_mask, c_mean, c_logits, b.g, B, h->K, h->P,
+                                                                       h->precision == 0));
+                    if (int r = decoder_backward_data(h, st, N, &dpre0, true, 1.f, i, true)) return r;
+                }
+                HIPCHK(h, launch_latent_seed(st, deci ? b.Rc : nullptr, wl, N, L, h->Cd, c_z, c_pm, c_plv, b.z[i], b.latent[i],
+                                             m_all + (size_t)i * NL, v_all + (size_t)i * NL, 4 * L));
+                if (i == 0) { seed0_m = m_all; seed0_v = v_all; }
+            }
+            seed_m = m_all + NL; seed_v = v_all + NL; seed_stride = NL;
+            if (seed0_m && !h->calls.fwd_from_state) {
+                // lambda_0 = init_mean / init_logvar repeated over (B, K): column sums, factor 1 (from a state: g_state, below)
+                HIPCHK(h, launch_colsum(st, seed0_m, N, L, L, 1.f, h->gacc[ps.init_mean]));
+                HIPCHK(h, launch_colsum(st, seed0_v, N, L, L, 1.f, h->gacc[ps.init_logvar]));
+            }
+        } else {
         if (dec) {
             // evaluation T's decoder activations and dec_out are still in the arena: the forward's last launches were that evaluation's own
             // decoder backward, which only reads them, and any compute call since would have cleared fwd_done.  ONE decoder pass with
@@ -1882,14 +2010,15 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
             if (int r = decoder_backward_data(h, st, N, &dpre0, true, 1.f, T, true)) return r;
         }
         seed_m = b.aux_seed; seed_v = b.aux_seed + (size_t)N * L;
-        HIPCHK(h, launch_latent_seed(st, dec ? b.Rc : nullptr, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, L, h->Cd, aux->z, aux->pm,
-                                     aux->plv, b.z[T], b.pm, seed_m, seed_v));
+        HIPCHK(h, launch_latent_seed(st, dec ? b.Rc : nullptr, wl, N, L, h->Cd, aux->z, aux->pm, aux->plv, b.z[T], b.pm, seed_m, seed_v));
+        }
     }
     if (h->head_fused && head_bptt_fits(L, H, Cr)) {
         // the whole BPTT recurrence of the head in one launch (rows are independent: a block walks i = T-1 .. 0 for its rows)
         PROF(h, st, "head_bwd", launch_head_bptt(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->raw_wm, h->raw_wv, h->raw_whh,
                                                  h->raw_wih, h->raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr,
-                                                 seed_m, seed_v, aux ? aux->gl : nullptr, obj.wtab, cot_h, cot_c, gs_h, gs_c));
+                                                 seed_m, seed_v, aux ? aux->gl : nullptr, obj.wtab, cot_h, cot_c, gs_h, gs_c,
+                                                 seed_stride));
     } else {
     int cf = 0;                                            // carry buffer flip
     for (int i = T - 1; i >= 0; --i) {
@@ -1900,8 +2029,11 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
         HIPCHK(h, launch_scale(st, b.g_pm[i + 1], alpha, ddm, N * L));
         HIPCHK(h, launch_scale(st, b.g_plv[i + 1], alpha, ddv, N * L));
         if (aux) {                                         // ELBO seeds x d(out) / d(loss); lambda_T's cotangents join delta_{T-1} unscaled
-            HIPCHK(h, launch_scale_dev_add(st, ddm, aux->gl, i == T - 1 ? seed_m : nullptr, N * L));
-            HIPCHK(h, launch_scale_dev_add(st, ddv, aux->gl, i == T - 1 ? seed_v : nullptr, N * L));
+            // (cotangents on chosen evaluations: those of lambda_{i+1} join delta_i, every i)
+            const float *sm = seed_stride ? seed_m + (size_t)i * seed_stride : i == T - 1 ? seed_m : nullptr;
+            const float *sv = seed_stride ? seed_v + (size_t)i * seed_stride : i == T - 1 ? seed_v : nullptr;
+            HIPCHK(h, launch_scale_dev_add(st, ddm, aux->gl, sm, N * L));
+            HIPCHK(h, launch_scale_dev_add(st, ddv, aux->gl, sv, N * L));
         }
         const float* c1 = b.c[i + 1];
         // read-out layers act on the cell state (iodine.py:488-492)
@@ -1927,10 +2059,11 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
         const float alpha0 = obj.whost ? -obj.whost[0] / (float)B : -(1.f / (float)(T + 1)) / (float)B;
         float* const dst[2] = {aux->g_state[0], aux->g_state[1]};
         const float* const src[2] = {b.g_pm[0], b.g_plv[0]};
+        const float* const add0[2] = {seed0_m, seed0_v};         // cotangents on evaluation 0 (iodine_train_backward_frames), unscaled
         for (int j = 0; j < 2; ++j) {
             if (!dst[j]) continue;
             HIPCHK(h, launch_scale(st, src[j], alpha0, dst[j], N * L));
-            HIPCHK(h, launch_scale_dev_add(st, dst[j], aux->gl, nullptr, N * L));
+            HIPCHK(h, launch_scale_dev_add(st, dst[j], aux->gl, add0[j], N * L));
         }
     }
     {
@@ -2035,6 +2168,7 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
     // like autograd without retain_graph: the saved forward is consumed (a second backward would add the BPTT terms to the
     // accumulators twice); iodine_train_forward must run again first
     h->calls.saved_passes_gone();
+    if (redecode) h->calls.redecoded = true;                   // buf.dec_out is no longer the final elbo()'s (iodine_last_elbo_outputs refuses)
     return rc;
 }
 
@@ -2067,7 +2201,7 @@ int iodine_train_backward_aux(iodine_handle* h, void* stream, const float* grad_
     std::vector<float*> ptrs(h->params.size());
     size_t off = 0;
     for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
-    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, nullptr, nullptr, nullptr};
+    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, nullptr, nullptr, nullptr, nullptr};
     return train_backward_impl(h, stream, 1.f, nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, &aux);
 }
 
@@ -2083,7 +2217,31 @@ int iodine_train_backward_seq(iodine_handle* h, void* stream, const float* grad_
     std::vector<float*> ptrs(h->params.size());
     size_t off = 0;
     for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
-    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c, g_state};
+    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c, g_state, nullptr};
+    return train_backward_impl(h, stream, 1.f, nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, &aux);
+}
+
+int iodine_train_backward_frames(iodine_handle* h, void* stream, const float* grad_loss_dev, const float* g_mean, const float* g_mask,
+                                 const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
+                                 const float* g_lstm_h, const float* g_lstm_c, float* flat_grads, int accumulate, float* const* g_state,
+                                 const int* frame_idx, int n_frames, const float* const* g_frames)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    iodine_handle* const shaped = h->shim ? pad_inner(h) : h;  // (the handle that holds the run shape)
+    if (int rc = train_frames_check(shaped, "iodine_train_backward_frames", frame_idx, n_frames, g_frames)) {
+        if (shaped != h) h->err = shaped->err;
+        return rc;
+    }
+    // no chosen evaluation, or no cotangent on any of them: iodine_train_backward_seq itself, launch for launch
+    if (n_frames == 0 || !(g_frames[0] || g_frames[1] || g_frames[2] || g_frames[3] || g_frames[4] || g_frames[5]))
+        return iodine_train_backward_seq(h, stream, grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c,
+                                         flat_grads, accumulate, g_state);
+    if (!flat_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward_frames: flat_grads is required");
+    std::vector<float*> ptrs(h->params.size());
+    size_t off = 0;
+    for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
+    FrameSet fr; fr.idx = frame_idx; fr.n = n_frames; fr.g = g_frames;
+    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c, g_state, &fr};
     return train_backward_impl(h, stream, 1.f, nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, &aux);
 }
 

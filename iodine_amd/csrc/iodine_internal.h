@@ -52,7 +52,8 @@ struct Buffers {               // workspace carve-up for one batch size / mode /
     float* carry_h[2] = {nullptr, nullptr};
     float* carry_c[2] = {nullptr, nullptr};
     std::vector<float*> rdpre;                 // gradient wrt refinement pre-activations, per layer
-    float* aux_seed = nullptr;                 // [2][N][L]: seeds of the head BPTT from auxiliary cotangents (iodine_train_backward_aux)
+    float* aux_seed = nullptr;                 // [2][T + 1][N][L]: seeds of the head BPTT from auxiliary cotangents (iodine_train_backward_aux:
+                                               // the first [2][N][L]; iodine_train_backward_frames: slice e = the seeds of evaluation e)
     float *gen_scr = nullptr, *gen_l0 = nullptr;                // generic path: wgrad partials; layer-0 scratch (kernels_genl0.hip)
 };
 
@@ -105,15 +106,17 @@ struct CallState {
     int state_iter = -1;                        // buf.h / buf.c [state_iter] = LSTM state the last iodine_reconstruct (buf.mode 0) or training
                                                 // forward (buf.mode 1) left (-1: none to read)
     bool enc_valid = false;                     // the last call left the refinement input ("enc") of its iterations in the workspace
+    bool redecoded = false;                     // a backward decoded an earlier evaluation again (iodine_train_backward_frames): buf.dec_out no
+                                                // longer belongs to the last elbo(); the posterior and the LSTM state are untouched
 
     // iodine_set_params, a changed run shape or frames setting, a consumed backward (like autograd without retain_graph)
     void saved_passes_gone() { fwd_done = false; diff_kind = 0; }
     // a compute call re-uses the arena.  keep_lstm_state: a plain iodine_decode does not touch buf.h / buf.c
-    void compute_begins(bool keep_lstm_state = false) { saved_passes_gone(); if (!keep_lstm_state) state_iter = -1; }
+    void compute_begins(bool keep_lstm_state = false) { saved_passes_gone(); redecoded = false; if (!keep_lstm_state) state_iter = -1; }
     // a re-plan (ensure_workspace), iodine_set_workspace, a wgrad_accum toggle: nothing the arena held can be read any more.
     // (iodine_set_workspace used to leave enc_valid and the wgrad_accum toggle state_iter: unobservable, every reader of the two also
     // refuses while buf.bytes == 0, and the next compute call re-plans)
-    void arena_gone() { saved_passes_gone(); last_elbo_iter = -1; state_iter = -1; enc_valid = false; }
+    void arena_gone() { saved_passes_gone(); last_elbo_iter = -1; state_iter = -1; enc_valid = false; redecoded = false; }
 };
 #pragma GCC visibility pop
 
@@ -258,7 +261,12 @@ extern "C" int shim_flat_out(iodine_handle* h, hipStream_t st, float* flat, int 
 // mean / mask / mask_logits / z and on lambda_T
 // iodine_train_backward_seq adds lstm_h / lstm_c = cotangents on the LSTM state after the last update and g_state = NULL or four output
 // pointers (each may be NULL): d / d (post_mean, post_logvar, h, c) of the state the forward started from
-struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv, *lstm_h, *lstm_c; float* const* g_state; };
+// chosen evaluations of a training forward (iodine_train_forward_frames / iodine_train_backward_frames): idx = n ascending, unique indices
+// in 0..T (host memory); six device pointers in the order {z, mean, mask, mask_logits, post_mean, post_logvar}, each (n, B, ..) or NULL -
+// `out` of the forward, `g` = the cotangents of the backward
+struct FrameSet { const int* idx = nullptr; int n = 0; float* const* out = nullptr; const float* const* g = nullptr; };
+// (frames: NULL or the cotangents on chosen evaluations)
+struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv, *lstm_h, *lstm_c; float* const* g_state; const FrameSet* frames; };
 
 // The host-only refusals of the entry points (iodine_api.cpp): null and batch checks, params_set, the 2^31 limits, the frames and
 // iteration-weight counts, the stop_after / trajectory rule, stale state.  They launch nothing, allocate nothing and change nothing but the
@@ -268,8 +276,10 @@ int set_params_check(iodine_handle* h, const float* const* dev, int n);
 int reconstruct_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* const* state_in, float* const* traj);
 int decode_check(iodine_handle* h, int batch, const float* z);
 int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* post_mean, const float* post_logvar);
-int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss, const float* const* state_in = nullptr);
+int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss, const float* const* state_in = nullptr,
+                        const FrameSet* fr = nullptr);
 int train_backward_check(iodine_handle* h, float* const* param_grads, int n, const AuxCot* aux = nullptr);
+int train_frames_check(iodine_handle* h, const char* who, const int* idx, int n, const void* ptrs);   // the list of chosen evaluations
 int decode_backward_check(iodine_handle* h, int batch);
 int last_elbo_outputs_check(iodine_handle* h, int count);
 int last_posterior_check(iodine_handle* h, int count);
@@ -278,9 +288,12 @@ int last_train_state_check(iodine_handle* h, int count);
 
 int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev, float* const* param_grads, int n,
                         int accumulate, const AuxCot* aux = nullptr);
+int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in, float* loss,
+                       float* elbo_iter, const FrameSet* fr);
 
 // The boundary of a zero-padded inner handle (iodine_pad.cpp), one function per entry point: h->shim != nullptr
 int pad_create(iodine_handle* h);               // h: cfg and the reference-shaped parameter table are set
+iodine_handle* pad_inner(iodine_handle* h);     // the padded handle behind the boundary (it holds the run shape)
 void pad_destroy(iodine_handle* h);
 int pad_set_params(iodine_handle* h, void* stream, const float* const* dev, int n);
 size_t pad_workspace_bytes(const iodine_handle* h, int batch, int mode);
@@ -303,7 +316,7 @@ int pad_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_dev,
 int pad_last_elbo_outputs(iodine_handle* h, void* stream, int count, float* z, float* mean, float* mask, float* mask_logits, float* pred);
 int pad_last_posterior(iodine_handle* h, void* stream, int count, float* post_mean, float* post_logvar);
 int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in, float* loss,
-                      float* elbo_iter);
+                      float* elbo_iter, const FrameSet* fr);
 int pad_train_backward(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev, float* const* param_grads, int n,
                        int accumulate, const AuxCot* aux);
 int pad_logger_scalars(iodine_handle* h, void* stream, float* out2);

@@ -192,6 +192,7 @@ int pad_set_params(iodine_handle* h, void* stream, const float* const* dev, int 
 // settings and read-outs without a latent axis: the inner handle's own
 size_t pad_workspace_bytes(const iodine_handle* h, int batch, int mode) { return iodine_workspace_bytes(h->shim->inner, batch, mode); }
 int pad_set_workspace(iodine_handle* h, void* dev_ptr, size_t bytes) { return shim_fail(h, iodine_set_workspace(h->shim->inner, dev_ptr, bytes)); }
+iodine_handle* pad_inner(iodine_handle* h) { return h->shim->inner; }
 int pad_set_run_shape(iodine_handle* h, int slots, int iters) { return shim_fail(h, iodine_set_run_shape(h->shim->inner, slots, iters)); }
 int pad_set_frames(iodine_handle* h, int frames) { return shim_fail(h, iodine_set_frames(h->shim->inner, frames)); }
 int pad_set_pixel_weights(iodine_handle* h, const float* w_dev, int per_frame)
@@ -337,12 +338,12 @@ int pad_last_posterior(iodine_handle* h, void* stream, int count, float* post_me
 }
 
 int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const float* const* state_in, float* loss,
-                      float* elbo_iter)
+                      float* elbo_iter, const FrameSet* fr)
 {
     PadShim* sh = h->shim;
     iodine_handle* in = sh->inner;
     PendingWeights once(in);
-    if (int rc = train_forward_check(in, batch, x, eps, loss, state_in)) return shim_fail(h, rc);
+    if (int rc = train_forward_check(in, batch, x, eps, loss, state_in, fr)) return shim_fail(h, rc);
     hipStream_t st = (hipStream_t)stream;
     const long long N = (long long)batch * in->K, R = (long long)(in->T + 1) * N;
     if (int r = shim_scratch(h, std::max((size_t)R * sh->Lp, state_in ? (size_t)N * sh->Hp : (size_t)0))) return r;
@@ -354,7 +355,15 @@ int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x,
         HIPCHK(h, launch_resize_rows(st, state_in[2], sh->hs, N, sh->H, sh->Hp));
         HIPCHK(h, launch_resize_rows(st, state_in[3], sh->cs, N, sh->H, sh->Hp));
     }
-    return shim_fail(h, iodine_train_forward_seq(in, stream, batch, x, sh->eps, state_in ? pstate : nullptr, loss, elbo_iter));
+    if (!fr) return shim_fail(h, iodine_train_forward_seq(in, stream, batch, x, sh->eps, state_in ? pstate : nullptr, loss, elbo_iter));
+    // chosen evaluations: the tensors with a latent axis come back at the padded width (at most (T + 1) * N rows each: the scratch holds them)
+    float* const pout[6] = {fr->out[0] ? sh->z : nullptr, fr->out[1], fr->out[2], fr->out[3], fr->out[4] ? sh->pm : nullptr,
+                            fr->out[5] ? sh->plv : nullptr};
+    FrameSet pf = *fr; pf.out = pout;
+    if (int rc = train_forward_impl(in, stream, batch, x, sh->eps, state_in ? pstate : nullptr, loss, elbo_iter, &pf)) return shim_fail(h, rc);
+    for (int q : {0, 4, 5})
+        if (fr->out[q]) HIPCHK(h, launch_resize_rows(st, pout[q], fr->out[q], (long long)fr->n * N, sh->Lp, sh->L));
+    return IODINE_OK;
 }
 
 // the inner handle writes its (scaled) gradient in padded shapes; the real entries are scattered (or added) into the caller's tensors
@@ -368,13 +377,31 @@ int pad_train_backward(iodine_handle* h, void* stream, float grad_scale, const f
     std::vector<float*> ptrs(h->params.size());
     for (size_t p = 0; p < ptrs.size(); ++p) ptrs[p] = sh->pgrad + sh->poff[p];
     AuxCot pa;
+    FrameSet pf;
+    const float* pfg[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float* pgs[4] = {nullptr, nullptr, nullptr, nullptr};
     const long long N = (long long)in->calls.fwd_batch * in->buf.K;
     if (aux) {
         // cotangents with a latent axis: rows widened to the padded width (zeros in the padded entries), like iodine_decode_backward's dz
         const bool hid = aux->lstm_h || aux->lstm_c || aux->g_state;
-        if (int r = shim_scratch(h, std::max((size_t)N * sh->Lp, hid ? (size_t)N * sh->Hp : (size_t)0))) return r;
+        const size_t nf = aux->frames && aux->frames->n > 0 ? (size_t)aux->frames->n : 0;
+        if (int r = shim_scratch(h, std::max(std::max((size_t)N * sh->Lp, hid ? (size_t)N * sh->Hp : (size_t)0), (size_t)(3 * nf * N * sh->Lp)))) return r;
         pa = *aux;
+        if (nf) {
+            // ... those on chosen evaluations too: three kinds of (n_frames * N) rows, back to back in the (free) noise scratch
+            pf = *aux->frames;
+            int slot = 0;
+            for (int q = 0; q < 6; ++q) {
+                pfg[q] = aux->frames->g[q];
+                if ((q == 0 || q >= 4) && pfg[q]) {
+                    float* dst = sh->eps + (size_t)slot * nf * N * sh->Lp;
+                    HIPCHK(h, launch_resize_rows(st, pfg[q], dst, (long long)nf * N, sh->L, sh->Lp));
+                    pfg[q] = dst;
+                }
+                if (q == 0 || q >= 4) ++slot;
+            }
+            pf.g = pfg; pa.frames = &pf;
+        }
         // ... and those on the LSTM state after the last update; the gradient of the initial state comes back at the padded widths
         if (aux->lstm_h) { HIPCHK(h, launch_resize_rows(st, aux->lstm_h, sh->hs, N, sh->H, sh->Hp)); pa.lstm_h = sh->hs; }
         if (aux->lstm_c) { HIPCHK(h, launch_resize_rows(st, aux->lstm_c, sh->cs, N, sh->H, sh->Hp)); pa.lstm_c = sh->cs; }

@@ -177,9 +177,14 @@ hipError_t launch_dz_plain(hipStream_t st, const float* Rc, const float* wclsT, 
 // the cancellation loses about log2(|mu_T| / sigma_T) bits (sigma = 0.01, |mu| = 3: ~2e-5 relative on the dz part of d logvar_T).
 // Keeping the noise instead would cost the plain training forward a copy per step.
 // One launch over N * L: the block layout of dz_plain_kernel.
+// The same for any evaluation i of the forward (iodine_train_backward_frames), one launch per evaluation right behind its decoder pass:
+// z = z_i, pm = mu_i with row stride ldpm (the forward keeps lambda_i as the first L of the 4 L entries of a row of its saved refinement
+// input), seeds = d / d delta_{i-1}.  c_z2 / c_pm2 / c_plv2: a second, optional set of cotangents on the same evaluation, added behind the
+// first (evaluation T named both as the final state and as an attached frame); all NULL and ldpm = L is the launch as it was.
 __global__ void latent_seed_kernel(const float* __restrict__ Rc, const float* __restrict__ wclsT, int L, int C, const float* __restrict__ c_z,
                                    const float* __restrict__ c_pm, const float* __restrict__ c_plv, const float* __restrict__ z,
-                                   const float* __restrict__ pm, float* __restrict__ seed_m, float* __restrict__ seed_v)
+                                   const float* __restrict__ pm, float* __restrict__ seed_m, float* __restrict__ seed_v, int ldpm,
+                                   const float* __restrict__ c_z2, const float* __restrict__ c_pm2, const float* __restrict__ c_plv2)
 {
     extern __shared__ float s_rc[];
     const int n = blockIdx.x, Lp = (L + 63) / 64 * 64, l = threadIdx.x % Lp, slice = threadIdx.x / Lp;
@@ -187,17 +192,24 @@ __global__ void latent_seed_kernel(const float* __restrict__ Rc, const float* __
     if (slice != 0 || l >= L) return;
     const size_t i = (size_t)n * L + l;
     if (c_z) dz += c_z[i];
-    seed_m[i] = dz + (c_pm ? c_pm[i] : 0.f);
-    seed_v[i] = dz * 0.5f * (z[i] - pm[i]) + (c_plv ? c_plv[i] : 0.f);
+    if (c_z2) dz += c_z2[i];
+    float sm = dz + (c_pm ? c_pm[i] : 0.f);
+    float sv = dz * 0.5f * (z[i] - pm[(size_t)n * ldpm + l]) + (c_plv ? c_plv[i] : 0.f);
+    if (c_pm2) sm += c_pm2[i];
+    if (c_plv2) sv += c_plv2[i];
+    seed_m[i] = sm;
+    seed_v[i] = sv;
 }
 
 hipError_t launch_latent_seed(hipStream_t st, const float* Rc, const float* wclsT, int N, int L, int C, const float* c_z, const float* c_pm,
-                              const float* c_plv, const float* z, const float* pm, float* seed_m, float* seed_v)
+                              const float* c_plv, const float* z, const float* pm, float* seed_m, float* seed_v, int ldpm, const float* c_z2,
+                              const float* c_pm2, const float* c_plv2)
 {
     const int Lp = (L + 63) / 64 * 64;
-    if (Lp > 512 || N < 1 || !z || !pm || !seed_m || !seed_v || (Rc && !wclsT)) return hipErrorInvalidValue;
+    if (ldpm <= 0) ldpm = L;
+    if (Lp > 512 || N < 1 || !z || !pm || !seed_m || !seed_v || (Rc && !wclsT) || ldpm < L) return hipErrorInvalidValue;
     const int nth = (512 / Lp) * Lp;
     hipLaunchKernelGGL(latent_seed_kernel, dim3(N), dim3(nth), (9 * C + nth) * sizeof(float), st, Rc, wclsT, L, C, c_z, c_pm, c_plv, z, pm,
-                       seed_m, seed_v);
+                       seed_m, seed_v, ldpm, c_z2, c_pm2, c_plv2);
     return hipGetLastError();
 }

@@ -1002,6 +1002,8 @@ hipError_t launch_mlp_bwd_pointwise(hipStream_t st, const float* du, int ldu, co
 // SEED (iodine_train_backward_aux): the ELBO seeds are multiplied by *gl_dev (autograd's d(out) / d(loss), device memory; NULL = 0) and
 // the first step, i = T - 1, adds seed_m / seed_v [N][L] = the cotangents that reach delta_{T-1} through lambda_T - unscaled by alpha and
 // by *gl_dev.  SEED = false is the kernel as it was.
+// seed_stride (floats) != 0: seed_m / seed_v are [T][N][L], one slice per iteration, and EVERY step i adds slice i = the cotangents that reach
+// delta_i through lambda_{i+1} (iodine_train_backward_frames: auxiliary terms on chosen evaluations); 0: the one slice of step T - 1 above.
 // The seeded instance also takes the carries across the ends of the saved forward (iodine_train_backward_seq), each pointer optional and
 // tested once outside the iteration loop: dh_in / dc_in [N][H] = cotangents on the LSTM state (h_T, c_T) after the last update - they take
 // the place of the zero carries iteration T - 1 starts from; dh_out / dc_out [N][H] receive the carries left after iteration 0 =
@@ -1078,7 +1080,7 @@ void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ 
                       float* __restrict__ dgates_o, float* __restrict__ ds_o, float* __restrict__ dpooled_o, int T, int N, int B,
                       int L, int H, int Cr, const float* __restrict__ seed_m, const float* __restrict__ seed_v,
                       const float* __restrict__ gl_dev, const float* __restrict__ wtab, const float* __restrict__ dh_in,
-                      const float* __restrict__ dc_in, float* __restrict__ dh_out, float* __restrict__ dc_out)
+                      const float* __restrict__ dc_in, float* __restrict__ dh_out, float* __restrict__ dc_out, size_t seed_stride)
 {
     // wtab: the objective's table of T + 1 loss weights (one uniform 4-byte load per iteration), NULL = the default (i + 1) / (T + 1)
     extern __shared__ __attribute__((aligned(16))) float s_hb[];
@@ -1111,7 +1113,10 @@ void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ 
             float a = alpha * g_pm[((size_t)(i + 1) * N + n) * L + l], b = alpha * g_plv[((size_t)(i + 1) * N + n) * L + l];
             if constexpr (SEED) {
                 a *= gl; b *= gl;
-                if (i == T - 1) { a += seed_m[(size_t)n * L + l]; b += seed_v[(size_t)n * L + l]; }
+                if (seed_stride != 0 || i == T - 1) {
+                    const size_t so = seed_stride * (size_t)i + (size_t)n * L + l;
+                    a += seed_m[so]; b += seed_v[so];
+                }
             }
             s_dd[r * 2 * L + l] = a; s_dd[r * 2 * L + L + l] = b;
             if (n0 + r < N) { ddm_o[((size_t)i * N + n) * L + l] = a; ddv_o[((size_t)i * N + n) * L + l] = b; }
@@ -1200,12 +1205,12 @@ hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_pl
                             const float* Wm, const float* Wv, const float* Whh, const float* Wih, const float* Wmlp, float* ddm,
                             float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr,
                             const float* seed_m, const float* seed_v, const float* gl_dev, const float* wtab, const float* dh_in,
-                            const float* dc_in, float* dh_out, float* dc_out)
+                            const float* dc_in, float* dh_out, float* dc_out, size_t seed_stride)
 {
     IOD_XSKIP(2);
     if (Cr > H) return hipErrorInvalidValue;                                // (the pool gradient is staged in an [HB][H] buffer)
     if ((seed_m == nullptr) != (seed_v == nullptr)) return hipErrorInvalidValue;
-    if (!seed_m && (dh_in || dc_in || dh_out || dc_out)) return hipErrorInvalidValue;   // (the carries across the ends: the seeded instance only)
+    if (!seed_m && (dh_in || dc_in || dh_out || dc_out || seed_stride)) return hipErrorInvalidValue;   // (the carries across the ends: the seeded instance only)
     const size_t lds = head_bptt_lds(L, H);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid((N + HB - 1) / HB), block(64 * HKG);
@@ -1213,13 +1218,13 @@ hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_pl
         static std::atomic<unsigned> attr_devs_seed{0};
         if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<true>, 160 * 1024, attr_devs_seed); e != hipSuccess) return e;
         hipLaunchKernelGGL(head_bptt_kernel<true>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
-                           ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, seed_m, seed_v, gl_dev, wtab, dh_in, dc_in, dh_out, dc_out);
+                           ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, seed_m, seed_v, gl_dev, wtab, dh_in, dc_in, dh_out, dc_out, seed_stride);
         return hipGetLastError();
     }
     static std::atomic<unsigned> attr_devs{0};
     if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<false>, 160 * 1024, attr_devs); e != hipSuccess) return e;
     hipLaunchKernelGGL(head_bptt_kernel<false>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
-                       ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr, wtab, nullptr, nullptr, nullptr, nullptr);
+                       ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr, wtab, nullptr, nullptr, nullptr, nullptr, (size_t)0);
     return hipGetLastError();
 }
 

@@ -89,7 +89,7 @@ def border_weights(B, S, n, device=None):
     return w
 
 
-def clip_backward(model, clip, eps=None, bptt='truncated', weights=None):
+def clip_backward(model, clip, eps=None, bptt='truncated', weights=None, frame_loss=None):
     """Gradient of one clip (B, F, 3, S, S), F = c * n_iters + 1, accumulated into ``.grad`` chunk by chunk (``clip_chunks``); the caller
     zeroes the gradients before and steps the optimizer after.  Returns (clip loss, (F, 3) ELBO terms, one row per frame).
 
@@ -106,7 +106,14 @@ def clip_backward(model, clip, eps=None, bptt='truncated', weights=None):
 
     ``weights``: per-pixel observation weights of the clip (``IODINE.forward``): (B, F, 1, S, S) / (B, F, S, S), one weight image per frame -
     every chunk, and every re-run of a chunk in the exact mode, gets the slice of its frames (``clip_weights``) - or (B, 1, S, S) /
-    (B, S, S) for all frames."""
+    (B, S, S) for all frames.
+
+    ``frame_loss``: per-frame auxiliary terms.  ``frame_loss(f, t)`` gets the clip frame index ``f`` and a dict of what the evaluation that
+    scores frame ``f`` decoded - ``z``, ``post_mean``, ``post_logvar`` (B, K, L), ``mean`` (B, K, 3, S, S), ``mask``, ``mask_logits``
+    (B, K, 1, S, S), attached (``IODINE.forward(attach_frames=...)``) - and returns a scalar tensor or None.  Every frame is scored exactly
+    once, where its ELBO weight sits: chunk 0 attaches evaluations 0..T, later chunks 1..T.  The terms join the chunk's loss in its one
+    ``backward()``; in the exact mode they are added in pass 2 only and their gradient crosses the chunk boundaries through the same
+    cotangent hand-over as the loss's.  The call then returns (clip loss, ELBO terms, the detached sum of the terms)."""
     if bptt not in ('truncated', 'exact'):
         raise ValueError(f"clip_backward: bptt must be 'truncated' or 'exact'; got {bptt!r}")
     if clip.dim() != 5:
@@ -129,13 +136,29 @@ def clip_backward(model, clip, eps=None, bptt='truncated', weights=None):
     part = lambda c: (clip[:, chunks[c][0]:chunks[c][1]], eps[chunks[c][0]:chunks[c][1]])
     wpart = lambda c: clip_weights(weights, clip.shape, chunks[c])
     total, terms = None, [None] * len(chunks)
+    aux_total = None
+    attach = lambda c: None if frame_loss is None else tuple(range(0 if c == 0 else 1, T + 1))
+
+    def scored(c, out):
+        # out + the terms of the frames chunk c scores
+        nonlocal aux_total
+        if frame_loss is None:
+            return out
+        fr = model.frames
+        for j, i in enumerate(fr['index']):
+            term = frame_loss(chunks[c][0] + i, {k: fr[k][j] for k in ('z', 'mean', 'mask', 'mask_logits', 'post_mean', 'post_logvar')})
+            if term is not None:
+                out = out + term
+                aux_total = term.detach() if aux_total is None else aux_total + term.detach()
+        return out
+
     try:
         if bptt == 'truncated':
             state = None
             for c in range(len(chunks)):
                 model.iter_weights = saved if c == 0 else later
-                loss = model(*part(c), state=state, keep_state=True, weights=wpart(c))
-                loss.backward()
+                loss = model(*part(c), state=state, keep_state=True, weights=wpart(c), attach_frames=attach(c))
+                scored(c, loss).backward()
                 state = model.refinement_state()
                 total = loss.detach() if total is None else total + loss.detach()
                 terms[c] = model.elbo_terms if c == 0 else model.elbo_terms[1:]
@@ -150,17 +173,19 @@ def clip_backward(model, clip, eps=None, bptt='truncated', weights=None):
             for c in reversed(range(len(chunks))):                           # pass 2: recompute, back-propagate, hand the cotangents on
                 model.iter_weights = saved if c == 0 else later
                 leaves = None if c == 0 else tuple(t.clone().requires_grad_(True) for t in entry[c])
-                loss = model(*part(c), state=leaves, attach_state=True, weights=wpart(c))
-                out = loss
+                loss = model(*part(c), state=leaves, attach_state=True, weights=wpart(c), attach_frames=attach(c))
+                out = scored(c, loss)
                 if cot is not None:
                     ends = (model.posterior.mean, model.posterior.logvar) + tuple(t.view_as(cot[2]) for t in model.lstm_hidden)
-                    out = loss + sum((g * t).sum() for g, t in zip(cot, ends) if g is not None)
+                    out = out + sum((g * t).sum() for g, t in zip(cot, ends) if g is not None)
                 out.backward()
                 cot = None if leaves is None else tuple(t.grad for t in leaves)
                 total = loss.detach() if total is None else total + loss.detach()
                 terms[c] = model.elbo_terms if c == 0 else model.elbo_terms[1:]
     finally:
         model.iter_weights = saved
+    if frame_loss is not None:
+        return total, torch.cat(terms, 0), aux_total if aux_total is not None else torch.zeros((), device=clip.device)
     return total, torch.cat(terms, 0)
 
 

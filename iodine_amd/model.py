@@ -29,6 +29,8 @@ in chunks of ``n_iters`` frames.  Training carries the state the same way: ``for
 from the state the last chunk left - detached tensors give truncated back-propagation through time, tensors that require grad receive the
 gradient of the chunk (``iodine_train_backward_seq``), and ``attach_state=True`` leaves ``model.lstm_hidden`` attached to the graph like
 the reference, so that ``iodine_amd.engine.clip_backward`` computes the exact gradient of a long clip chunk by chunk.
+``forward(x, attach_frames=...)`` leaves chosen ELBO evaluations of the call attached in ``model.frames`` - a loss on every frame of a
+clip in one ``(loss + aux).backward()`` (``iodine_train_forward_frames`` / ``iodine_train_backward_frames``).
 
 Per-pixel observation weights: ``forward`` / ``encode`` / ``reconstruct`` take ``weights=`` (the single-pass ELBO: ``weighted_elbo(x, weights)``; ``elbo`` keeps
 the reference's signature), a tensor ``(B, 1, S, S)`` or
@@ -206,6 +208,47 @@ class _TrainStepAttached(torch.autograd.Function):
         return (None, None, None, None, None, *gstate, *grads)
 
 
+_FRAME_KEYS = ('z', 'mean', 'mask', 'mask_logits', 'post_mean', 'post_logvar')     # the order of the library's six pointers
+
+
+class _TrainStepFrames(torch.autograd.Function):
+    """``forward(x, attach_frames=...)``: the node of ``_TrainStepAttached`` with six more outputs, what the chosen ELBO evaluations
+    decoded - z, mean, mask, mask_logits and the lambda they sampled from, each (F, B, K, ...) - so one ``backward()`` of the loss, of
+    terms on the final state (``attach`` True) and of terms on any listed evaluation goes through iodine_train_backward_frames."""
+
+    @staticmethod
+    def forward(ctx, module, x, eps, w, attach, index, s_pm, s_plv, s_h, s_c, *params):
+        ctx.set_materialize_grads(False)                   # an unused kind arrives as None -> a NULL pointer
+        state = None if s_pm is None else (s_pm, s_plv, s_h, s_c)
+        loss, elbo_iter, frames = module._train_forward(x, eps, state, weights=w, frames=index)
+        ctx.module, ctx.serial, ctx.from_state = module, module._call_serial, state is not None
+        ctx.BK, ctx.attach, ctx.index = (x.shape[0], module.K), attach, index
+        ctx.mark_non_differentiable(elbo_iter)
+        if not attach:
+            return (loss, elbo_iter, *frames)
+        module._fetch_last_elbo(module._handle, x, elbo_iter[-1])
+        module._fetch_posterior(module._handle, x.shape[0], x.device)
+        h, c = module._fetch_train_state(x.shape[0], x.device)
+        H = h.shape[-1]
+        return (loss, elbo_iter, module.z, module.mean, module.mask, module.mask_logits, module.posterior.mean, module.posterior.logvar,
+                h.view(-1, H), c.view(-1, H), *frames)
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_elbo, *gs):
+        g_z, g_mean, g_mask, g_logits, g_pm, g_plv, g_h, g_c = gs[:8] if ctx.attach else (None,) * 8
+        gf = tuple(gs[8:14] if ctx.attach else gs[:6])
+        aux = (g_mean, g_mask, g_logits, g_z, g_pm, g_plv)
+        n_in = len(ctx.needs_input_grad)
+        if g_loss is None and all(g is None for g in aux + gf) and g_h is None and g_c is None:
+            return (None,) * n_in
+        want = tuple(ctx.from_state and ctx.needs_input_grad[6 + j] for j in range(4))
+        grads, gstate = ctx.module._train_backward_seq(g_loss, ctx.serial, aux, (g_h, g_c), want, ctx.BK,
+                                                       frames=(ctx.index, gf) if any(g is not None for g in gf) else None)
+        if ctx.from_state:                                 # the initial posterior is not part of a forward from a state: unused parameters
+            grads = [None if n.startswith('posterior.') else g for (n, _), g in zip(ctx.module.named_parameters(), grads)]
+        return (None, None, None, None, None, None, *gstate, *grads)
+
+
 _WRAPPER_OPTIONS = ('batch_cap',)      # max images per library call (IODINE.max_batch); the rest go to iodine_set_option
 
 
@@ -359,6 +402,7 @@ class IODINE(nn.Module):
 
         # per-call state the reference keeps on self (iodine.py:36-52)
         self.lstm_hidden = None
+        self.frames = None              # forward(x, attach_frames=...): the chosen ELBO evaluations (see forward)
         self.z = None
         self.mean = None
         self.mask_logits = None
@@ -1156,7 +1200,25 @@ class IODINE(nn.Module):
         return self.elbo_terms[0, 0].clone(), pre
 
     # ---- training: iodine.py:115-158 + lib/engine/train.py:60-63 -------------------------------------
-    def forward(self, x, eps=None, state=None, attach_state=False, keep_state=False, weights=None):
+    def _check_attach_frames(self, attach_frames, T):
+        """``attach_frames`` of ``forward`` -> None (off) or the sorted tuple of evaluation indices.  Host only."""
+        if attach_frames is None or attach_frames is False:
+            return None
+        if attach_frames is True:
+            return tuple(range(T + 1))
+        try:
+            vals = list(attach_frames)
+        except TypeError:
+            raise ValueError(f'IODINE.forward: attach_frames must be None, a bool or an iterable of evaluation indices in 0..{T}; got '
+                             f'{attach_frames!r}') from None
+        for v in vals:
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= T:
+                raise ValueError(f'IODINE.forward: attach_frames holds {v!r}; a forward of {T} iterations makes the ELBO evaluations 0..{T}')
+        if len(set(vals)) != len(vals):
+            raise ValueError(f'IODINE.forward: attach_frames names an evaluation twice: {vals!r}')
+        return tuple(sorted(vals))
+
+    def forward(self, x, eps=None, state=None, attach_state=False, keep_state=False, weights=None, attach_frames=None):
         """-sum_i w_i ELBO_i (w = ``model.iter_weights``, by default (i+1)/(T+1); ELBO_i = LL_i - ``model.beta`` KL_i at ``model.sigma``),
         differentiable wrt every parameter.  ``loss.backward()`` differentiates the forward as it
         ran, at the (K, T) it read - like the reference, whose autograd graph is fixed at forward time.  ``x``: images
@@ -1183,8 +1245,19 @@ class IODINE(nn.Module):
         it; the logger entries stay detached.  The library keeps ONE saved forward and its backward consumes it: sum the terms first and
         call ``backward()`` once - a second one (``aux.backward()`` followed by ``loss.backward()``) raises the stale-forward error.
 
+        ``attach_frames``: per-frame auxiliary losses.  ``True`` attaches all T + 1 ELBO evaluations, an iterable of ints in 0..T the
+        chosen ones (sorted; a repeated or out-of-range index raises ``ValueError`` before any device work), ``None`` / ``False`` none.
+        ``model.frames`` is then a dict: ``index`` (the attached evaluations) and ``z``, ``post_mean``, ``post_logvar`` (F, B, K, L),
+        ``mean`` (F, B, K, 3, S, S), ``mask``, ``mask_logits`` (F, B, K, 1, S, S) - entry j is what evaluation ``index[j]`` decoded and
+        the lambda it sampled from, attached to the graph like in the reference, whose every ``elbo()`` call of ``forward`` leaves them so
+        (iodine.py:171-187): a mask loss per frame, a consistency term between z_i and z_{i+1}, a probe on a frame's posterior, all in
+        one ``(loss + aux).backward()``.  Each attached evaluation with a term on mean / mask / mask_logits costs one decoder forward
+        and backward in that ``backward()``; evaluation T costs what ``attach_state`` costs.  Under ``torch.no_grad()`` the same values
+        come detached (a training-time trajectory).  Any ``forward`` without it sets ``model.frames = None``.
+
         A batch above ``max_batch(training=True)`` runs in chunks, each chunk's backward inside the forward: a detached ``state`` is sliced
-        per chunk and ``keep_state`` gathers the chunks' states; ``attach_state`` and a ``state`` that requires grad are refused there.
+        per chunk and ``keep_state`` gathers the chunks' states; ``attach_state``, ``attach_frames`` and a ``state`` that requires grad are
+        refused there.
 
         ``weights``: per-pixel observation weights >= 0 of this call, (B, 1, S, S) / (B, S, S), with a clip also (B, T+1, 1, S, S) /
         (B, T+1, S, S): the loss and every gradient are those of the weighted ELBO (module docstring).  No gradient flows to them."""
@@ -1194,11 +1267,14 @@ class IODINE(nn.Module):
         weights = self._check_weights(weights, x, 'forward')
         B = x.shape[0]
         state = self._check_train_state(state, B, K, x.device)
+        index = self._check_attach_frames(attach_frames, T)
         self._state = None                          # the state of an earlier encode / reconstruct ends here (refinement_state)
+        self.frames = None
         attach = bool(attach_state) and torch.is_grad_enabled()
         state_grad = state is not None and torch.is_grad_enabled() and any(t.requires_grad for t in state)
         if B > self.max_batch(training=True):
-            for on, what in ((attach, 'attach_state=True'), (state_grad, 'a state that requires grad')):
+            for on, what in ((attach, 'attach_state=True'), (state_grad, 'a state that requires grad'),
+                             (index is not None, 'attach_frames')):
                 if on:
                     raise RuntimeError(f'IODINE.forward({what}): a batch of {B} images exceeds max_batch(training=True) = '
                                        f'{self.max_batch(training=True)}; such a batch runs in chunks, each chunk\'s backward inside the forward, '
@@ -1210,7 +1286,14 @@ class IODINE(nn.Module):
             self.elbo_terms = elbo_iter
             return loss
         eps = self._eps(eps, B, x.device)
-        if attach:
+        if index is not None:
+            out = _TrainStepFrames.apply(self, x, eps, weights, attach, index, *(state or (None,) * 4), *self._ordered_params())
+            loss, elbo_iter = out[:2]
+            if attach:
+                self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc = out[2:10]
+                self.lstm_hidden = (lh, lc)
+            self.frames = dict(index=index, **dict(zip(_FRAME_KEYS, out[-6:])))
+        elif attach:
             (loss, elbo_iter, self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc
              ) = _TrainStepAttached.apply(self, x, eps, weights, True, *(state or (None,) * 4), *self._ordered_params())
             self.lstm_hidden = (lh, lc)
@@ -1241,7 +1324,9 @@ class IODINE(nn.Module):
                                              h, 'iodine_last_train_state'))
         return hh, cc
 
-    def _train_forward(self, x, eps, state=None, weights=None):
+    def _train_forward(self, x, eps, state=None, weights=None, frames=None):
+        """-> (loss, ELBO terms); with ``frames`` (a tuple of evaluation indices, possibly empty) also the six (F, B, K, ...) tensors of
+        those evaluations in the order of ``_FRAME_KEYS`` (iodine_train_forward_frames)."""
         dev, B = x.device, x.shape[0]
         K, T = self._run_shape()
         obj = self._read_objective(T)
@@ -1253,6 +1338,18 @@ class IODINE(nn.Module):
         xs, eps = self._stage('x', x), self._stage('eps', eps)
         self._call_serial += 1
         ws = self._send_weights(h, weights)                 # (ws: alive until the call is queued)
+        if frames is not None:
+            F, L, S = len(frames), self.dim_latent, self.img_size
+            shapes = ((F, B, K, L), (F, B, K, 3, S, S), (F, B, K, 1, S, S), (F, B, K, 1, S, S), (F, B, K, L), (F, B, K, L))
+            outs = [self._out('tf.' + n, shp, dev) for n, shp in zip(_FRAME_KEYS, shapes)]
+            st = None if state is None else [self._stage('ts.' + n, t.detach()) for n, t in zip(('pm', 'plv', 'h', 'c'), state)]
+            sptrs = None if st is None else (C.c_void_p * 4)(*[t.data_ptr() for t in st])
+            optrs = (C.c_void_p * 6)(*[t.data_ptr() if F else None for t in outs])
+            idx = (C.c_int * max(F, 1))(*frames)
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward_frames(
+                h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), sptrs, _lib.ptr(loss), _lib.ptr(elbo_iter), idx, F, optrs),
+                h, 'iodine_train_forward_frames'))
+            return self._own(loss), self._own(elbo_iter), tuple(self._own(t) for t in outs)
         if state is None:
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward(h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps),
                                                                                  _lib.ptr(loss), _lib.ptr(elbo_iter)),
@@ -1334,10 +1431,11 @@ class IODINE(nn.Module):
             off += n
         return views
 
-    def _train_backward_seq(self, grad_loss, serial, aux, hc, want, BK):
+    def _train_backward_seq(self, grad_loss, serial, aux, hc, want, BK, frames=None):
         """iodine_train_backward_seq for the saved forward ``serial``: ``aux`` as for ``_train_backward``, ``hc`` = cotangents on the LSTM
         state after the last update ((B * K, H) or None each), ``want`` = which of d / d (post_mean, post_logvar, h, c) of the initial
-        state to return.  -> (per-parameter views, the four state gradients or None each)."""
+        state to return.  ``frames``: None, or (evaluation indices, the six cotangents (F, B, K, ...) in the order of ``_FRAME_KEYS``, None
+        each) - iodine_train_backward_frames.  -> (per-parameter views, the four state gradients or None each)."""
         if serial != self._call_serial:
             raise RuntimeError(self._STALE.format('forward'))
         h, dev = self._handle, self._handle_device
@@ -1352,8 +1450,17 @@ class IODINE(nn.Module):
         outs = [self._out('ts.g' + n, shp, dev) if w else None
                 for n, shp, w in zip(('pm', 'plv', 'h', 'c'), ((B, K, L), (B, K, L), (B, K, H), (B, K, H)), want)]
         gptrs = (C.c_void_p * 4)(*[None if t is None else t.data_ptr() for t in outs]) if any(want) else None
-        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_seq(
-            h, self._stream(), _lib.ptr(gl), *[_lib.ptr(c) for c in cs], _lib.ptr(flat), 0, gptrs), h, 'iodine_train_backward_seq'))
+        if frames is None:
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_seq(
+                h, self._stream(), _lib.ptr(gl), *[_lib.ptr(c) for c in cs], _lib.ptr(flat), 0, gptrs), h, 'iodine_train_backward_seq'))
+        else:
+            index, gf = frames
+            fs = [None if g is None else self._stage('f.' + n, as_f32(g)) for n, g in zip(_FRAME_KEYS, gf)]
+            fptrs = (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in fs])
+            idx = (C.c_int * len(index))(*index)
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_frames(
+                h, self._stream(), _lib.ptr(gl), *[_lib.ptr(c) for c in cs], _lib.ptr(flat), 0, gptrs, idx, len(index), fptrs),
+                h, 'iodine_train_backward_frames'))
         self._call_serial += 1                      # the saved forward is consumed (no retain_graph)
         flat = self._own(flat)
         views, off = [], 0
