@@ -352,6 +352,19 @@ int iodine_train_backward_frames(iodine_handle* h, void* stream, const float* gr
                                  const float* g_lstm_h, const float* g_lstm_c, float* flat_grads, int accumulate, float* const* g_state,
                                  const int* frame_idx, int n_frames, const float* const* g_frames);
 
+/* A learned observation scale: d LL_e / d sigma of every ELBO evaluation e of the last call that ran with option "sigma_grad" 1 -- the
+ * batch mean over the images of  sum_p ( sum_{k,c} g1_kc (x_c - mu_kc) - 3 w_p ) / sigma  with g1_kc = w_p r_kc (x_c - mu_kc) / sigma^2 the
+ * closed-form d(B * ELBO) / d mean of the per-pixel terms (r: responsibilities, w_p: the pixel weight of iodine_set_pixel_weights, 1
+ * without), i.e. the derivative of the LL the call reports (elbo_iter[e][2] / terms[2]), weighted exactly like it, summed like it (fp64
+ * partial sums in a fixed order).  Sigma reaches the loss only through this direct term: the refinement inputs are detached
+ * (iodine.py:343).  The values are RAW, like elbo_iter: not multiplied by the iteration weights, beta or a sign -- d loss / d sigma of a
+ * training forward is  -sum_e w_e out[e]  with the weights it ran with, d ELBO / d sigma of an elbo is out[0].
+ *   n = T + 1 after iodine_train_forward / _seq / _frames (from a state and over a clip alike), n = 1 after an iodine_elbo that ran with
+ *   option "save_for_backward"; out: n floats of device memory, written on `stream`.  Another n: IODINE_ERR_INVALID.
+ * IODINE_ERR_STATE when the last compute call did not produce the values: the option was off, the call was of another kind
+ * (reconstruct, decode, a plain elbo), or the workspace was re-planned since.  The values survive the backward of that forward. */
+int iodine_last_sigma_grad(iodine_handle* h, void* stream, float* out, int n);
+
 /* logger.update(init_mean=posterior.init_mean.mean(), init_logvar=posterior.init_logvar.mean()) -- iodine.py:156-157:
  * out2 (2, device) = the two means of the parameters last handed to iodine_set_params. */
 int iodine_logger_scalars(iodine_handle* h, void* stream, float* out2);
@@ -414,6 +427,16 @@ int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, i
  * simply runs eagerly, a repeated objective replays),
  * "save_for_backward" (1: the following iodine_decode / iodine_elbo calls keep their state for iodine_decode_backward /
  * iodine_elbo_backward - workspace mode 2, see there; 0 -- default: the inference forms, unchanged),
+ * "sigma_grad" (1: iodine_train_forward* and an iodine_elbo under "save_for_backward" also compute d LL / d sigma of every ELBO
+ * evaluation -- one more per-pixel kernel and a one-block reduction per evaluation, read back with iodine_last_sigma_grad; part of the
+ * hipGraph key; 0 -- default: no launch differs.  The two small buffers behind it -- 8 bytes per image and 512 pixels, 4 per evaluation --
+ * are part of every workspace plan, option on or off, so iodine_workspace_bytes does not depend on it),
+ * "stable_encoding" (channel 8 of the refinement input, mask_posterior.  0 -- default, the reference: exp(s_k) / sum_j exp(s_j) with
+ * s_k = sum_c log N(x_c; mu_kc, sigma) and NO max-subtraction (iodine.py:286-293), which is 0 / 0 = NaN at a pixel every slot misses by
+ * about 8.5 sigma in all three channels (float32 exp returns 0 below s_k = -103.98) and then poisons that image's refinement; 1: q_k / sum_j q_j with q_k = exp(s_k - max_j s_j), the softmax over the
+ * slots the channel was meant to be -- the same value wherever the reference's is finite up to rounding, finite everywhere; libm expf
+ * and IEEE division either way, one definition for every kernel that writes the channel (pixel_terms.h).  The likelihood and
+ * leave-one-out channels, the ELBO and every backward are unchanged.  Part of the hipGraph key; takes effect with the next call),
  * "profile" (bracket kernel launches with HIP events on the launch stream: 1 = the dominant "conv_tile_*" launches only --
  * 54 of ~330 per training step, what bench.py keeps on inside its timed region; 2 = every category; 0 = off),
  * "conv_precision" (3x3 convs of the decoder and refinement stacks: 0 = exact fp32 MFMA -- IEEE fp32 products, fp32 accumulate,
@@ -475,7 +498,7 @@ int iodine_set_option(iodine_handle* h, const char* key, double value);
 /* Sum of event-measured durations (ms) and number of launches of one kernel category since the last reset:
  * "conv_tile_fwd", "conv_tile_dgrad", "conv_tile_wgrad", "dec_out", "dec_out_dgrad", "dec_out_wgrad", "dec_out_bwd", "dec_l0",
  * "l0_reduce",
- * "pixel_pass1", "pixel_pass2", "refine_l0" (first refinement layer), "refine_l0f" (encoding + first refinement layer in one
+ * "pixel_pass1", "pixel_pass2", "pixel_sigma_grad" (option sigma_grad), "refine_l0" (first refinement layer), "refine_l0f" (encoding + first refinement layer in one
  * kernel, option refine_l0_fused), "refine_conv" (the others), "refine_head", "refine_wgrad", "refine_dgrad", "refine_bwd01"
  * (fused layer-1 data gradient + layer-0 weight gradient, option refine_bwd_fused), "refine_bias_grad", "head_bwd", "gen_conv"
  * (the fp32 convs of the generic path), "gen_conv_f16x3" (its split-fp16 launches, option gen_conv_precision 1), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward), "render_bwd" (backward of the rendering - sigmoid, slot softmax, sum_k mask x mean - in iodine_decode_backward; the decoder pass behind it is booked under the categories of the training step), "frames_in" (the image / clip conversion at the head of

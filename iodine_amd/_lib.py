@@ -33,6 +33,7 @@ EXPORTS = (
     'iodine_train_forward_seq', 'iodine_train_backward_seq', 'iodine_last_train_state',
     'iodine_set_pixel_weights',
     'iodine_train_forward_frames', 'iodine_train_backward_frames',
+    'iodine_last_sigma_grad',
 )
 
 
@@ -142,6 +143,8 @@ def lib() -> C.CDLL:
     if hasattr(L, 'iodine_train_forward_frames'):       # (attach_frames=; absent from older A/B builds, which refuse the keyword)
         L.iodine_train_forward_frames.argtypes = [vp, vp, ci, vp, vp, C.POINTER(vp), vp, vp, C.POINTER(ci), ci, C.POINTER(vp)]
         L.iodine_train_backward_frames.argtypes = [vp, vp] + [vp] * 10 + [ci, C.POINTER(vp), C.POINTER(ci), ci, C.POINTER(vp)]
+    if hasattr(L, 'iodine_last_sigma_grad'):            # (a sigma that requires grad; absent from older A/B builds, which raise on one)
+        L.iodine_last_sigma_grad.argtypes = [vp, vp, vp, ci]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

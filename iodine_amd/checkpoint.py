@@ -29,8 +29,9 @@ def last_checkpoint(save_dir):
 
 
 def load_checkpoint(path, model, optimizer=None, strict=True):
-    """Load a reference-format checkpoint into ``model`` (and ``optimizer``).  Returns the extra entries (epoch, iter...)."""
-    ckpt = torch.load(path, map_location=torch.device('cpu'))
+    """Load a reference-format checkpoint into ``model`` (and ``optimizer``).  Returns the extra entries (epoch, iter...).
+    ``path``: the file, or its content as the dict ``torch.load`` returned (a caller that had to look inside first)."""
+    ckpt = dict(path) if isinstance(path, dict) else torch.load(path, map_location=torch.device('cpu'))
     if 'model' not in ckpt:
         raise KeyError("not a reference checkpoint: no 'model' entry")
     model.load_state_dict(strip_module_prefix(ckpt.pop('model')), strict=strict)

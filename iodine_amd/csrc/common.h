@@ -186,7 +186,10 @@ hipError_t launch_pixel_finalize_elbo(hipStream_t st, const double* part, int B,
                                       const float* pm, const float* plv, int L, float* img_terms, float* scal, unsigned* counter, float beta);
 hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec, const float* lnstat,
                               const float* lin, float* enc, int B, int K, int S, float sigma, float* enc_sh = nullptr, unsigned chmask = 0x1ffffu,
-                              int strict = 0);
+                              int strict = 0, int stable = 0);       // stable: option stable_encoding (mask_post, pixel_terms.h)
+// option sigma_grad: out[0] = d LL / d sigma of the evaluation whose decoder output is dec (kernels_pixel.hip); part: B x blocks doubles
+hipError_t launch_pixel_sigma_grad(hipStream_t st, const float* x4, const float* dec, double* part, float* out, int B, int K, int P,
+                                   double sigma, int strict);
 hipError_t launch_final_out(hipStream_t st, const float* dec, float* pred, float* mask, float* mean, float* logits,
                             int B, int K, int P);
 // kernels_render.hip: backward of the rendering (sigmoid, slot softmax, sum_k mask * mean) for the caller's gradients wrt pred (B,3,S,S),
@@ -440,7 +443,7 @@ size_t refine_l0_wpk_bytes(int O);
 bool refine_l0_fused_ok(int S, int c, int K);
 hipError_t launch_refine_l0_fused(hipStream_t st, const float* x4, const float* dec, const float* lnstat, const float* lin, const void* wk,
                                   const float* wkmeta, const void* ws, const float* wsmeta, const float* bias, float* out, float* enck,
-                                  float* encs, int B, int K, int S, int c, float sigma, unsigned chmask);
+                                  float* encs, int B, int K, int S, int c, float sigma, unsigned chmask, int stable = 0);
 // kernels_refws.hip: weight-stationary stride-2 conv C -> C + bias + ELU (refinement layers 1 ..), wpk = launch_pack_conv_weights_ws(w, C, 0)
 bool conv3x3_s2ws_ok(int S, int c);
 hipError_t launch_conv3x3_s2ws_f16x3(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias, float* out,

@@ -413,6 +413,9 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
         if (h->gen_ref && mode == 1) scr = std::max(scr, std::max(gen_wgrad_scratch_floats(17, Cr, h->kr), gen_wgrad_scratch_floats(Cr, Cr, h->kr)));
         b.gen_scr = a.take<float>(scr);
     }
+    // option sigma_grad (at the end: the carve-up in front of it is the same with or without a reader of these two)
+    b.sg_part = a.take<double>((size_t)B * pixel_blocks_per_image(P));
+    b.sgrad = a.take<float>((size_t)T + 1);
     b.bytes = (a.off + 255) & ~(size_t)255;
 }
 
@@ -631,8 +634,9 @@ const float* x4_frame(const iodine_handle* h, int i)
 }
 
 // elbo() + inner backward + get_input_encoding for iteration i (iodine.py:85-93 / 133-142)
+// sgrad: also leave d LL_i / d sigma in buf.sgrad[i] (option sigma_grad; the callers that offer it: training forward, saved elbo)
 int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps_i, int i, bool need_grads,
-                       bool train = false, float train_alpha = 0.f)
+                       bool train = false, float train_alpha = 0.f, bool sgrad = false)
 {
     const float sigma = (float)h->obj.sigma, beta = (float)h->obj.beta;     // the handle's current objective (iodine_set_objective)
     Buffers& b = h->buf;
@@ -647,6 +651,9 @@ int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps
     if (i == 0) HIPCHK(h, hipMemsetAsync(h->elbo_counter, 0, sizeof(unsigned), st));
     HIPCHK(h, launch_pixel_finalize_elbo(st, b.part, B, h->K, h->P, h->cfg.layernorm, b.lnstat, b.ll_img, b.pm, b.plv, h->L,
                                          b.img_terms + (size_t)i * B * 2, b.scal + 3 * i, h->elbo_counter, beta));
+    if (sgrad)
+        PROF(h, st, "pixel_sigma_grad", launch_pixel_sigma_grad(st, x4_frame(h, i), b.dec_out, b.sg_part, b.sgrad + i, B, h->K, h->P, h->obj.sigma,
+                                                                h->precision == 0));
     if (!need_grads) return IODINE_OK;
     float* dpre0 = nullptr;
     rc = decoder_backward_data(h, st, N, &dpre0, train, train_alpha, i);
@@ -685,10 +692,10 @@ int refine_step(iodine_handle* h, hipStream_t st, int B, int i, bool save)
         PROF(h, st, "refine_l0f", launch_refine_l0_fused(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, h->ref_l0k, h->ref_l0kmeta, h->ref_l0s,
                                                          h->ref_l0smeta, h->ref_b[0], b.ract[i][0], keep_enc ? b.enck[i] : nullptr,
                                                          keep_enc ? b.encs[i] : nullptr, B, h->K, h->S, h->Cr, (float)h->obj.sigma,
-                                                         h->enc_chmask));
+                                                         h->enc_chmask, h->stable_enc));
     else
         PROF(h, st, "pixel_pass2", launch_pixel_pass2(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, split ? b.enck[i] : b.enc[i], B, h->K, h->S,
-                                                      (float)h->obj.sigma, split ? b.encs[i] : nullptr, h->enc_chmask, h->precision == 0));
+                                                      (float)h->obj.sigma, split ? b.encs[i] : nullptr, h->enc_chmask, h->precision == 0, h->stable_enc));
     int s = h->S;
     const float* in = b.enc[i];
     for (int l = 0; l < h->Dr; ++l) {
@@ -792,7 +799,7 @@ std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, s
     uint64_t sb, bb;
     memcpy(&sb, &o->sigma, 8); memcpy(&bb, &o->beta, 8);
     std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->K, (uintptr_t)h->T, (uintptr_t)h->stop_after, (uintptr_t)h->precision,
-                                (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7)),
+                                (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7) | (h->sigma_grad << 8) | (h->stable_enc << 9)),
                                 (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own), (uintptr_t)h->frames};
     k.push_back((uintptr_t)sb); k.push_back((uintptr_t)bb); k.push_back((uintptr_t)o->wgen);
     k.push_back((uintptr_t)(pw ? pw->w : nullptr)); k.push_back((uintptr_t)(pw ? pw->per_frame : 0));
@@ -1469,6 +1476,8 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
     if (!strcmp(key, "out_bwd_fused")) { h->out_bwd_fused = value != 0; return IODINE_OK; }
     if (!strcmp(key, "save_for_backward")) { h->save_bwd = value != 0; return IODINE_OK; }
     if (!strcmp(key, "fuse_l0")) { h->fuse_l0 = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "sigma_grad")) { h->sigma_grad = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "stable_encoding")) { h->stable_enc = value != 0; return IODINE_OK; }
     if (!strcmp(key, "refine_split")) { h->refine_split = value != 0; return IODINE_OK; }
     if (!strcmp(key, "head_fused")) { h->head_fused = value != 0; return IODINE_OK; }
     if (!strcmp(key, "refine_bwd_fused")) { h->refine_bwd_fused = value != 0; return IODINE_OK; }
@@ -1660,7 +1669,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
         } else {
             HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, h->L, h->H));
         }
-        const int r = elbo_and_gradients(h, st, B, eps, 0, false);
+        const int r = elbo_and_gradients(h, st, B, eps, 0, false, false, 0.f, save && h->sigma_grad);
         if (r) return r;
         if (terms) HIPCHK(h, hipMemcpyAsync(terms, b.scal, sizeof(float) * 3, hipMemcpyDeviceToDevice, st));
         // kept for iodine_elbo_backward: z (buf.z[0]), the activations, dec_out, d(B * ELBO) / d dec_out (buf.g), the posterior (buf.pm / plv)
@@ -1674,6 +1683,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     cs.last_elbo_iter = 0;
     cs.last_elbo_batch = B;
     if (save) { cs.diff_kind = 2; cs.diff_batch = B; cs.diff_init = post_mean == nullptr; cs.diff_obj = h->obj; }
+    cs.sgrad_n = save && h->sigma_grad ? 1 : 0;
     return IODINE_OK;
 }
 
@@ -1786,6 +1796,23 @@ int iodine_last_posterior(iodine_handle* h, void* stream, int count, float* post
     return IODINE_OK;
 }
 
+int iodine_last_sigma_grad(iodine_handle* h, void* stream, float* out, int n)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_last_sigma_grad(h, stream, out, n);
+    if (h->calls.sgrad_n == 0 || h->buf.bytes == 0)
+        return h->fail(IODINE_ERR_STATE, "iodine_last_sigma_grad: the last compute call left no d LL / d sigma - it needs option sigma_grad and an "
+                                         "iodine_train_forward* or an iodine_elbo with option save_for_backward, with no compute call since");
+    if (!out || n != h->calls.sgrad_n) {
+        char m[200];
+        snprintf(m, sizeof m, "iodine_last_sigma_grad: the last call left %d value(s) (one per ELBO evaluation); out must hold n = %d floats",
+                 h->calls.sgrad_n, h->calls.sgrad_n);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    HIPCHK(h, hipMemcpyAsync(out, h->buf.sgrad, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return IODINE_OK;
+}
+
 int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* loss,
                          float* elbo_iter)
 {
@@ -1840,7 +1867,7 @@ int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x
         for (int i = 0; i <= T; ++i) {
             // d loss / d (B * ELBO_i) = -w_i / B; the default weighting keeps its closed form
             const float alpha = h->obj.whost ? -h->obj.whost[i] / (float)B : -((float)(i + 1) / (float)(T + 1)) / (float)B;
-            int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, true, alpha);
+            int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, true, alpha, h->sigma_grad != 0);
             if (r) return r;
             if (fr && fj < fr->n && fr->idx[fj] == i) {
                 // what this evaluation decoded and the lambda it sampled from (buf.pm / plv: the refinement step below moves them on);
@@ -1891,6 +1918,7 @@ int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x
     cs.fwd_split = refine_split_on(h);     // layout of the saved refinement inputs (refine_split is part of the graph key)
     cs.last_elbo_iter = T;
     cs.last_elbo_batch = B;
+    cs.sgrad_n = h->sigma_grad ? T + 1 : 0;
     return IODINE_OK;
 }
 

@@ -30,6 +30,8 @@ struct Buffers {               // workspace carve-up for one batch size / mode /
     size_t bytes = 0;
     float *x4, *V, *dec_out, *g, *lnstat, *ll_img, *img_terms, *scal, *rows, *rows_p, *Rc, *pm, *plv;
     double* part;
+    double* sg_part = nullptr;                 // option sigma_grad: per-block partials of one evaluation, [B][pixel_blocks_per_image]
+    float* sgrad = nullptr;                    // ... and d LL_e / d sigma of the T + 1 evaluations of the call (iodine_last_sigma_grad)
     std::vector<float*> act;                   // decoder activations a[0..Dd-1]   (N,P,Cd)
     float *head_xh = nullptr, *head_gp = nullptr;   // refinement head in three launches: LSTM input rows, gate pre-activations
     float* dpre[2];                            // ping-pong gradient wrt pre-activations
@@ -106,17 +108,19 @@ struct CallState {
     int state_iter = -1;                        // buf.h / buf.c [state_iter] = LSTM state the last iodine_reconstruct (buf.mode 0) or training
                                                 // forward (buf.mode 1) left (-1: none to read)
     bool enc_valid = false;                     // the last call left the refinement input ("enc") of its iterations in the workspace
+    int sgrad_n = 0;                            // values buf.sgrad holds: T + 1 after a training forward, 1 after a saved elbo - that ran with
+                                                // option sigma_grad; 0: the last compute call produced none (iodine_last_sigma_grad refuses)
     bool redecoded = false;                     // a backward decoded an earlier evaluation again (iodine_train_backward_frames): buf.dec_out no
                                                 // longer belongs to the last elbo(); the posterior and the LSTM state are untouched
 
     // iodine_set_params, a changed run shape or frames setting, a consumed backward (like autograd without retain_graph)
     void saved_passes_gone() { fwd_done = false; diff_kind = 0; }
     // a compute call re-uses the arena.  keep_lstm_state: a plain iodine_decode does not touch buf.h / buf.c
-    void compute_begins(bool keep_lstm_state = false) { saved_passes_gone(); redecoded = false; if (!keep_lstm_state) state_iter = -1; }
+    void compute_begins(bool keep_lstm_state = false) { saved_passes_gone(); redecoded = false; sgrad_n = 0; if (!keep_lstm_state) state_iter = -1; }
     // a re-plan (ensure_workspace), iodine_set_workspace, a wgrad_accum toggle: nothing the arena held can be read any more.
     // (iodine_set_workspace used to leave enc_valid and the wgrad_accum toggle state_iter: unobservable, every reader of the two also
     // refuses while buf.bytes == 0, and the next compute call re-plans)
-    void arena_gone() { saved_passes_gone(); last_elbo_iter = -1; state_iter = -1; enc_valid = false; redecoded = false; }
+    void arena_gone() { saved_passes_gone(); last_elbo_iter = -1; state_iter = -1; enc_valid = false; redecoded = false; sgrad_n = 0; }
 };
 #pragma GCC visibility pop
 
@@ -213,6 +217,9 @@ struct iodine_handle {
     std::vector<float*> gacc;                   // one per parameter, reference shapes (slices of gacc_arena)
     float* gacc_arena = nullptr;
     size_t gacc_total = 0;
+    int sigma_grad = 0;                         // option sigma_grad: a training forward / a saved elbo also leaves d LL_e / d sigma of every
+                                                // evaluation (one more per-pixel kernel per evaluation; off: no launch differs)
+    int stable_enc = 0;                         // option stable_encoding: channel 8 of the encoding as a max-subtracted softmax (pixel_terms.h)
     int save_bwd = 0;                           // option save_for_backward: a decode / elbo keeps what its backward reads (calls.diff_*)
     // hipGraph replay of the fixed-shape launch sequences (option "graph"): one instantiated graph per distinct argument tuple
     int graph = 0;
@@ -320,6 +327,7 @@ int pad_train_forward(iodine_handle* h, void* stream, int batch, const float* x,
 int pad_train_backward(iodine_handle* h, void* stream, float grad_scale, const float* grad_scale_dev, float* const* param_grads, int n,
                        int accumulate, const AuxCot* aux);
 int pad_logger_scalars(iodine_handle* h, void* stream, float* out2);
+int pad_last_sigma_grad(iodine_handle* h, void* stream, float* out, int n);
 int pad_debug_copy(iodine_handle* h, void* stream, const char* name, int iter, float* dst, size_t max_floats, size_t* n_floats);
 int pad_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset);
 

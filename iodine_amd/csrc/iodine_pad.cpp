@@ -205,6 +205,7 @@ int pad_set_objective(iodine_handle* h, double sigma, double beta, const double*
 }
 int pad_set_option(iodine_handle* h, const char* key, double value) { return shim_fail(h, iodine_set_option(h->shim->inner, key, value)); }
 int pad_logger_scalars(iodine_handle* h, void* stream, float* out2) { return shim_fail(h, iodine_logger_scalars(h->shim->inner, stream, out2)); }
+int pad_last_sigma_grad(iodine_handle* h, void* stream, float* out, int n) { return shim_fail(h, iodine_last_sigma_grad(h->shim->inner, stream, out, n)); }
 int pad_debug_copy(iodine_handle* h, void* stream, const char* name, int iter, float* dst, size_t max_floats, size_t* n_floats)
 {
     return shim_fail(h, iodine_debug_copy(h->shim->inner, stream, name, iter, dst, max_floats, n_floats));   // (padded widths)

@@ -199,7 +199,8 @@ void pixel_finalize_elbo_kernel(const double* __restrict__ part, int nblk, int K
 // and the 6 channels every slot of an image shares, once per image, to
 //   enc_sh[b][p][8]  = image rgb, LN(pixel likelihood), coordinate x, coordinate y, 0, 0
 // (294 -> 176 + 17 MB per iteration at cfg3; the shared part is convolved once per image instead of once per slot).
-template <int K, bool SPLIT, bool STRICT>
+// STABLE: option stable_encoding, channel 8 as the max-subtracted softmax (mask_post, pixel_terms.h); false: the reference's p_k / sum p_j
+template <int K, bool SPLIT, bool STRICT, bool STABLE>
 __global__ __launch_bounds__(PIX_BLOCK)
 void pixel_pass2_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec,
                         const float* __restrict__ lnstat, const float* __restrict__ lin, float* __restrict__ enc,
@@ -228,9 +229,8 @@ void pixel_pass2_kernel(const float4* __restrict__ x4, const float4* __restrict_
         PixelTerms<K> t;
         const float4 xv = x4[(size_t)b * P + p];
         pixel_terms<K, STRICT>(xv, dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
-        float psum = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) psum += t.pk[k];
+        float smax;
+        const float psum = mask_post_den<K, STABLE>(t, smax);
         const float cx = lin[p % S], cy = lin[p / S];
         if constexpr (SPLIT) {
             float4* tw8 = reinterpret_cast<float4*>(s_tr[wv] + lane * 8);
@@ -254,7 +254,7 @@ void pixel_pass2_kernel(const float4* __restrict__ x4, const float4* __restrict_
                 const float loo = t.loo[k];
                 float4* tw12 = reinterpret_cast<float4*>(s_tr[wv] + lane * 12);
                 tw12[0] = make_float4(on(3, t.mu[k][0]), on(4, t.mu[k][1]), on(5, t.mu[k][2]), on(6, t.m[k]));
-                tw12[1] = make_float4(on(7, t.logit[k]), on(8, t.pk[k] / psum), on(9, (t.g1[k][0] - ln[0]) * ln[1]), on(10, (t.g1[k][1] - ln[0]) * ln[1]));
+                tw12[1] = make_float4(on(7, t.logit[k]), on(8, mask_post<K, STABLE>(t, k, smax, psum)), on(9, (t.g1[k][0] - ln[0]) * ln[1]), on(10, (t.g1[k][1] - ln[0]) * ln[1]));
                 tw12[2] = make_float4(on(11, (t.g1[k][2] - ln[0]) * ln[1]), on(12, (t.g2[k] - ln[2]) * ln[3]), on(14, (loo - ln[4]) * ln[5]), 0.f);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
@@ -277,7 +277,7 @@ void pixel_pass2_kernel(const float4* __restrict__ x4, const float4* __restrict_
             const float loo = t.loo[k];
             tw[0] = make_float4(on(0, xv.x), on(1, xv.y), on(2, xv.z), on(3, t.mu[k][0]));
             tw[1] = make_float4(on(4, t.mu[k][1]), on(5, t.mu[k][2]), on(6, t.m[k]), on(7, t.logit[k]));
-            tw[2] = make_float4(on(8, t.pk[k] / psum), on(9, (t.g1[k][0] - ln[0]) * ln[1]), on(10, (t.g1[k][1] - ln[0]) * ln[1]),
+            tw[2] = make_float4(on(8, mask_post<K, STABLE>(t, k, smax, psum)), on(9, (t.g1[k][0] - ln[0]) * ln[1]), on(10, (t.g1[k][1] - ln[0]) * ln[1]),
                                 on(11, (t.g1[k][2] - ln[0]) * ln[1]));
             tw[3] = make_float4(on(12, (t.g2[k] - ln[2]) * ln[3]), on(13, (t.like - ln[6]) * ln[7]), on(14, (loo - ln[4]) * ln[5]), on(15, cx));
             tw[4] = make_float4(on(16, cy), 0.f, 0.f, 0.f);
@@ -295,6 +295,66 @@ void pixel_pass2_kernel(const float4* __restrict__ x4, const float4* __restrict_
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
     }
+}
+
+// ---- option sigma_grad: d LL / d sigma of one ELBO evaluation ---------------------------------------
+// A kernel of its own (the per-pixel terms once more, no stores but one double per block), so that pass 1 - its 6 K + 3 statistics, its
+// LDS and its registers - is the same code with the option off.  part[b][blk] = sum over the block's pixels of sigma_grad_term, the
+// per-thread fp32 partials (two pixels) added in fp64 in the fixed order pass 1 uses.
+template <int K, bool STRICT>
+__global__ __launch_bounds__(PIX_BLOCK)
+void pixel_sigma_grad_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec, double* __restrict__ part, int P, int ppb,
+                             float inv2s2, float invs2, float lconst)
+{
+    const int nblk = gridDim.x, b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
+    const float4* dec_b = dec + (size_t)b * K * P;
+    float acc = 0.f;
+    const int pend = min(P, (blk + 1) * ppb);
+    for (int p = blk * ppb + tid; p < pend; p += PIX_BLOCK) {
+        PixelTerms<K> t;
+        const float4 xv = x4[(size_t)b * P + p];
+        pixel_terms<K, STRICT>(xv, dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
+        acc += sigma_grad_term<K>(xv, t);
+    }
+    __shared__ float s_part[PIX_BLOCK];
+    __shared__ double s_red[PIX_BLOCK / 64];
+    s_part[tid] = acc;
+    __syncthreads();
+    if (tid < PIX_BLOCK / 64) {
+        const float* row = s_part + tid * 64;
+        double v = 0.0;
+        for (int j = 0; j < 64; ++j) v += (double)row[(j + 16 * tid) & 63];
+        s_red[tid] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double v = 0.0;
+#pragma unroll
+        for (int w = 0; w < PIX_BLOCK / 64; ++w) v += s_red[w];
+        part[(size_t)b * nblk + blk] = v;
+    }
+}
+
+// out[0] = mean_b (float)(sum_blk part[b][blk]) / sigma: per image the block partials in block order, rounded to fp32 like ll_img, then the
+// images in image order in fp64 - the order and the roundings of the reported LL (pixel_finalize_elbo_kernel).  One block.
+__global__ __launch_bounds__(256)
+void pixel_sigma_grad_finalize_kernel(const double* __restrict__ part, int nblk, int B, double sigma, float* __restrict__ out)
+{
+    const int tid = threadIdx.x;
+    __shared__ float s_t[256];
+    double acc = 0.0;
+    for (int i0 = 0; i0 < B; i0 += 256) {
+        if (i0 + tid < B) {
+            double v = 0.0;
+            for (int i = 0; i < nblk; ++i) v += part[(size_t)(i0 + tid) * nblk + i];
+            s_t[tid] = (float)v;
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int i = 0; i < min(256, B - i0); ++i) acc += s_t[i];
+        __syncthreads();
+    }
+    if (tid == 0) out[0] = (float)(acc / ((double)B * sigma));
 }
 
 // ---- final decode outputs (IODINE.decode, lib/modeling/iodine.py:59-71): NCHW pred / mask / mean ----
@@ -360,6 +420,30 @@ hipError_t launch_pixel_pass1(hipStream_t st, const float* x4, const float* dec,
     return hipGetLastError();
 }
 
+// part: B x pixel_blocks_per_image(P) doubles of scratch; out: one float, d LL / d sigma of this evaluation (batch mean, pixel weights in)
+hipError_t launch_pixel_sigma_grad(hipStream_t st, const float* x4, const float* dec, double* part, float* out, int B, int K, int P,
+                                   double sigma_d, int strict)
+{
+    const int nblk = pixel_blocks_per_image(P), ppb = (P + nblk - 1) / nblk;
+    const float sigma = (float)sigma_d;
+    const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
+    const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
+    switch (K) {
+#define CASE(KK) case KK: \
+        if (strict) hipLaunchKernelGGL((pixel_sigma_grad_kernel<KK, true>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
+            (const float4*)x4, (const float4*)dec, part, P, ppb, inv2s2, invs2, lconst); \
+        else hipLaunchKernelGGL((pixel_sigma_grad_kernel<KK, false>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
+            (const float4*)x4, (const float4*)dec, part, P, ppb, inv2s2, invs2, lconst); \
+        break;
+        FOR_EACH_K(CASE)
+#undef CASE
+        default: return hipErrorInvalidValue;
+    }
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(pixel_sigma_grad_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nblk, B, (double)sigma, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_pixel_finalize_elbo(hipStream_t st, const double* part, int B, int K, int P, int use_ln, float* lnstat, float* ll_img,
                                       const float* pm, const float* plv, int L, float* img_terms, float* scal, unsigned* counter, float beta)
 {
@@ -371,7 +455,8 @@ hipError_t launch_pixel_finalize_elbo(hipStream_t st, const double* part, int B,
 }
 
 hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec, const float* lnstat,
-                              const float* lin, float* enc, int B, int K, int S, float sigma, float* enc_sh, unsigned chmask, int strict)
+                              const float* lin, float* enc, int B, int K, int S, float sigma, float* enc_sh, unsigned chmask, int strict,
+                              int stable)
 {
     IOD_XSKIP(8);
     const int P = S * S;
@@ -379,8 +464,9 @@ hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec,
     const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
     switch (K) {
-#define P2(KQ, SP, ST) hipLaunchKernelGGL((pixel_pass2_kernel<KQ, SP, ST>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
+#define P2S(KQ, SP, ST, SB) hipLaunchKernelGGL((pixel_pass2_kernel<KQ, SP, ST, SB>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
             (const float4*)x4, (const float4*)dec, lnstat, lin, enc, enc_sh, P, S, ppb, inv2s2, invs2, lconst, chmask)
+#define P2(KQ, SP, ST) do { if (stable) P2S(KQ, SP, ST, true); else P2S(KQ, SP, ST, false); } while (0)
 #define CASE(KK) case KK: \
         if (enc_sh) { if (strict) P2(KK, true, true); else P2(KK, true, false); } \
         else { if (strict) P2(KK, false, true); else P2(KK, false, false); } \
@@ -388,6 +474,7 @@ hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec,
         FOR_EACH_K(CASE)
 #undef CASE
 #undef P2
+#undef P2S
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -60,7 +60,8 @@ IOD_DEVINL void l0_store12(unsigned char* dst, const float (&v)[12], float scale
     *reinterpret_cast<uint4*>(dst + 32) = make_uint4(lo[2], lo[3], lo[4], lo[5]);
 }
 
-template <int K, bool ALLCH>                                 // ALLCH: every encoding channel present (chmask = 0x1ffff) - no per-channel selects
+template <int K, bool ALLCH, bool STABLE>                    // ALLCH: every encoding channel present (chmask = 0x1ffff) - no per-channel selects
+                                                             // STABLE: option stable_encoding (mask_post, pixel_terms.h)
 __global__ __launch_bounds__(448)
 void refine_l0_fused_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec, const float* __restrict__ lnstat,
                             const float* __restrict__ lin, const uint2* __restrict__ wk, const float* __restrict__ wkmeta,
@@ -272,13 +273,13 @@ void refine_l0_fused_kernel(const float4* __restrict__ x4, const float4* __restr
         l0_lds_barrier();                                     // the consumers' in-place conversion of the previous unit (they wait for every wave)
         PixelTerms<K> tm;
         const float4 xv = nxv;
-        float psum = 1.f;
+        float psum = 1.f, smax = 0.f;
         const float cxy[2] = {ncxy[0], ncxy[1]};
         // channel values of slot k / of the shared plane from the pixel terms (evaluated twice: for the plane maxima, then for the stores)
         auto slot_vals = [&](int k, float (&v)[12]) {
             const float* ln = lnv[k];
             v[0] = on(3, tm.mu[k][0]); v[1] = on(4, tm.mu[k][1]); v[2] = on(5, tm.mu[k][2]);
-            v[3] = on(6, tm.m[k]); v[4] = on(7, tm.logit[k]); v[5] = on(8, tm.pk[k] / psum);
+            v[3] = on(6, tm.m[k]); v[4] = on(7, tm.logit[k]); v[5] = on(8, mask_post<K, STABLE>(tm, k, smax, psum));
             v[6] = on(9, (tm.g1[k][0] - ln[0]) * ln[1]); v[7] = on(10, (tm.g1[k][1] - ln[0]) * ln[1]);
             v[8] = on(11, (tm.g1[k][2] - ln[0]) * ln[1]); v[9] = on(12, (tm.g2[k] - ln[2]) * ln[3]);
             v[10] = on(14, (tm.loo[k] - ln[4]) * ln[5]); v[11] = 0.f;
@@ -300,16 +301,14 @@ void refine_l0_fused_kernel(const float4* __restrict__ x4, const float4* __restr
 #ifdef L0_DBG_NOPROD
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
-                        tm.mu[k][0] = dv[k].x; tm.mu[k][1] = dv[k].y; tm.mu[k][2] = dv[k].z; tm.m[k] = dv[k].w; tm.logit[k] = dv[k].w; tm.pk[k] = 1.f;
+                        tm.mu[k][0] = dv[k].x; tm.mu[k][1] = dv[k].y; tm.mu[k][2] = dv[k].z; tm.m[k] = dv[k].w; tm.logit[k] = dv[k].w; tm.pk[k] = 1.f; tm.ls[k] = 0.f;
                         tm.g1[k][0] = dv[k].x; tm.g1[k][1] = dv[k].y; tm.g1[k][2] = dv[k].z; tm.g2[k] = dv[k].w; tm.loo[k] = dv[k].x;
                     }
                     tm.like = xv.x;
 #else
                     pixel_terms_core<K>(xv, dv, inv2s2, invs2, lconst, tm);
 #endif
-                    psum = 0.f;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) psum += tm.pk[k];
+                    psum = mask_post_den<K, STABLE>(tm, smax);
                 }
                 // the planes hold the fp32 values (the consumers scale and split them: the scale needs the maxima of all producer waves)
                 const bool wr = inside && enck && pr >= 1 && ph >= 1;     // training: the tile's own 4 x 32 pixels also go to HBM (pixel_pass2's layout)
@@ -360,15 +359,15 @@ void refine_l0_fused_kernel(const float4* __restrict__ x4, const float4* __restr
 #endif
 }
 
-template <int K>
+template <int K, bool STABLE>
 hipError_t l0_launch(hipStream_t st, const float* x4, const float* dec, const float* lnstat, const float* lin, const void* wk, const float* wkmeta,
                      const void* ws, const float* wsmeta, const float* bias, float* out, float* enck, float* encs, int B, int S, float sigma,
                      unsigned chmask)
 {
     constexpr size_t lds = (size_t)2 * (K + 1) * L0_PLB + 16 + (size_t)3 * (K + 1) * 64 + 64 * 4 + 64 * 4 + 64;
     static std::atomic<unsigned> attr_devs{0}, attr_devs2{0};
-    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, true>, (int)lds, attr_devs); e != hipSuccess) return e;
-    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, false>, (int)lds, attr_devs2); e != hipSuccess) return e;
+    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, true, STABLE>, (int)lds, attr_devs); e != hipSuccess) return e;
+    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, false, STABLE>, (int)lds, attr_devs2); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int Sc = S / 2, nunits = B * (Sc / 16) * (Sc / 2);
@@ -376,10 +375,10 @@ hipError_t l0_launch(hipStream_t st, const float* x4, const float* dec, const fl
     const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
     if ((chmask & 0x1ffffu) == 0x1ffffu)
-        hipLaunchKernelGGL((refine_l0_fused_kernel<K, true>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
+        hipLaunchKernelGGL((refine_l0_fused_kernel<K, true, STABLE>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
                            (const uint2*)wk, wkmeta, (const uint2*)ws, wsmeta, bias, out, enck, encs, S, nunits, inv2s2, invs2, lconst, chmask);
     else
-        hipLaunchKernelGGL((refine_l0_fused_kernel<K, false>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
+        hipLaunchKernelGGL((refine_l0_fused_kernel<K, false, STABLE>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
                            (const uint2*)wk, wkmeta, (const uint2*)ws, wsmeta, bias, out, enck, encs, S, nunits, inv2s2, invs2, lconst, chmask);
 #ifdef IODINE_TILE_PROF
     {
@@ -411,12 +410,14 @@ bool refine_l0_fused_ok(int S, int c, int K) { return c == 64 && S >= 32 && S % 
 // enck / encs (both or neither): also write the split encoding (pixel_pass2's layout) - training.
 hipError_t launch_refine_l0_fused(hipStream_t st, const float* x4, const float* dec, const float* lnstat, const float* lin, const void* wk,
                                   const float* wkmeta, const void* ws, const float* wsmeta, const float* bias, float* out, float* enck,
-                                  float* encs, int B, int K, int S, int c, float sigma, unsigned chmask)
+                                  float* encs, int B, int K, int S, int c, float sigma, unsigned chmask, int stable)
 {
     IOD_XSKIP(512);
     if (!refine_l0_fused_ok(S, c, K) || (enck == nullptr) != (encs == nullptr)) return hipErrorInvalidValue;
     switch (K) {
-#define L0_CASE(KK) case KK: return l0_launch<KK>(st, x4, dec, lnstat, lin, wk, wkmeta, ws, wsmeta, bias, out, enck, encs, B, S, sigma, chmask);
+#define L0_CASE(KK) case KK: \
+        return stable ? l0_launch<KK, true>(st, x4, dec, lnstat, lin, wk, wkmeta, ws, wsmeta, bias, out, enck, encs, B, S, sigma, chmask) \
+                      : l0_launch<KK, false>(st, x4, dec, lnstat, lin, wk, wkmeta, ws, wsmeta, bias, out, enck, encs, B, S, sigma, chmask);
         L0_CASE(1) L0_CASE(2) L0_CASE(3) L0_CASE(4) L0_CASE(5) L0_CASE(6) L0_CASE(7) L0_CASE(8) L0_CASE(9)
 #undef L0_CASE
         default: return hipErrorInvalidValue;

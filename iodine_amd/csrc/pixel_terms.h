@@ -12,6 +12,7 @@ struct PixelTerms {
     float g1[K][3];       // d(B*ELBO)/d mean   (of the WEIGHTED objective: pixel weight w = lane 3 of the packed image)
     float g2[K];          // d(B*ELBO)/d mask   (weighted too)
     float pk[K];          // exp(sum_c l_kc)  (un-stabilised, as the reference)
+    float ls[K];          // sum_c l_kc as rounded: the argument pk was built from (option stable_encoding, mask_post below)
     float ll_sum;         // sum_c logsumexp_k(log(m_k + 1e-12) + l_kc)   (raw, like pk / like / loo: they describe the scene, not the objective)
     float like;           // exp(ll_sum)
     float mix;            // sum_k m_k * pk_k
@@ -111,12 +112,57 @@ IOD_DEVINL void pixel_terms_core(const float4 xv, const float4 (&dv)[K], float i
     t.mix = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
+        t.ls[k] = lsum[k];
         t.pk[k] = expf(lsum[k]);
         prod[k] = t.m[k] * t.pk[k];
         t.mix = k == 0 ? prod[0] : t.mix + prod[k];
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) t.loo[k] = (t.mix - prod[k]) / ((1.f - t.m[k]) + 1e-5f);
+}
+
+// Channel 8 of the encoding, mask_posterior (iodine.py:286-293), for every kernel that writes it (pixel_pass2_kernel plain and SPLIT,
+// refine_l0_fused_kernel).  STABLE false - the reference: p_k / sum_j p_j WITHOUT max-subtraction, 0 / 0 = NaN where every p_k underflows.
+// STABLE true (option stable_encoding): q_k / sum_j q_j with q_k = exp(s_k - max_j s_j), s_k = t.ls[k] - the softmax over the slots the
+// channel was meant to be; the largest q is exactly 1, so the denominator is >= 1.  libm expf and the IEEE division either way, sums in slot
+// order.  mask_post_den returns the denominator (and the maximum through smax, unused when !STABLE), mask_post the value of slot k.
+template <int K, bool STABLE>
+IOD_DEVINL float mask_post_den(const PixelTerms<K>& t, float& smax)
+{
+    float den = 0.f;
+    if constexpr (STABLE) {
+        smax = t.ls[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) smax = fmaxf(smax, t.ls[k]);
+#pragma unroll
+        for (int k = 0; k < K; ++k) den += expf(t.ls[k] - smax);
+    } else {
+        smax = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) den += t.pk[k];
+    }
+    return den;
+}
+template <int K, bool STABLE>
+IOD_DEVINL float mask_post(const PixelTerms<K>& t, int k, float smax, float den)
+{
+    if constexpr (STABLE) return expf(t.ls[k] - smax) / den;
+    else return t.pk[k] / den;
+}
+
+// The statistic of option sigma_grad: d/dsigma [ w sum_c logsumexp_k(log(m_k + 1e-12) + l_kc) ] x sigma
+//   = sum_{k,c} g1_kc (x_c - mu_kc) - 3 w        (g1 already holds w r_kc (x_c - mu_kc) / sigma^2; the -3 w is d(-3 log sigma) x sigma)
+// The caller sums it over the pixels and divides by sigma once.
+template <int K>
+IOD_DEVINL float sigma_grad_term(const float4 xv, const PixelTerms<K>& t)
+{
+    const float xs[3] = {xv.x, xv.y, xv.z};
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) q += t.g1[k][c] * (xs[c] - t.mu[k][c]);
+    return q - 3.f * xv.w;
 }
 
 template <int K, bool STRICT = false>

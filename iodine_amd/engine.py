@@ -198,7 +198,7 @@ def beta_warmup(step, beta, warmup_steps):
 
 
 def train(model, optimizer, dataloader, device, max_steps, print_every=10, checkpoint_path=None, log=print, max_grad_norm=None,
-          beta=None, beta_warmup_steps=0, bptt=None, ignore_border=0):
+          beta=None, beta_warmup_steps=0, bptt=None, ignore_border=0, log_sigma=None):
     """train.py:44-108: loss = model(data); loss.mean(); zero_grad; backward; [all-reduce]; [clip]; step.  Returns the losses.
     ``max_grad_norm``: the global gradient norm is clipped at this value (train.py:64, commented out in the reference; the paper
     uses 5.0) AFTER the all-reduce, so every rank clips the same averaged gradient with the same coefficient - what
@@ -210,7 +210,13 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
     ``bptt``: 'truncated' or 'exact' - the loader yields clips (B, F, 3, S, S) with F = c * n_iters + 1 frames (``SyntheticClips``) and a step
     is ``clip_backward`` over the clip's chunks: ONE optimizer step per clip, the all-reduce and the clipping after the last chunk.
     ``ignore_border``: n > 0 trains with zero observation weight on an n-pixel frame around every image (``border_weights``, the
-    ``weights=`` of ``IODINE.forward``)."""
+    ``weights=`` of ``IODINE.forward``).
+    ``log_sigma``: a learned observation scale (``--learn-sigma``) - a float32 device scalar that requires grad and sits in a param group of
+    ``optimizer``, kept outside the module (whose ``state_dict`` names are the reference's): ``model.sigma = log_sigma.exp()`` before
+    every step, so ``loss.backward()`` fills ``log_sigma.grad``; the log line gains ``sigma``, the checkpoint an entry ``log_sigma``, and
+    ``model.sigma`` is left at the learned value as a plain float.  Every step then costs one ``.item()`` and runs eagerly in graph mode.
+    Its gradient is part of the global norm that ``max_grad_norm`` clips, with the fused optimizer (which takes the norm over all its param
+    groups) and in front of any other alike."""
     model.train()
     fused_clip = isinstance(optimizer, FusedAdam)
     if max_grad_norm is not None:
@@ -230,6 +236,8 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
             x = data[0].to(device, non_blocking=True)                        # "first one is image" (train.py:49)
             if beta is not None:
                 model.beta = beta_warmup(step, beta, beta_warmup_steps)
+            if log_sigma is not None:
+                model.sigma = log_sigma.exp()
             w = border_weights(x.shape[0], x.shape[-1], ignore_border, device) if ignore_border else None
             if bptt is not None:
                 optimizer.zero_grad()
@@ -239,25 +247,63 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
                 optimizer.zero_grad()
                 loss.backward()
             if world > 1:
-                parallel.allreduce_gradients(model.parameters())            # replaces DataParallel's reduce
+                parallel.allreduce_gradients(list(model.parameters()) + ([log_sigma] if log_sigma is not None else []))   # replaces DataParallel's reduce
             if clipping and not fused_clip:
-                grad_norm = clip_grad_norm_(model.parameters(), max_grad_norm)
+                grad_norm = clip_grad_norm_(list(model.parameters()) + ([log_sigma] if log_sigma is not None else []), max_grad_norm)
             optimizer.step()
             if clipping and fused_clip:
                 grad_norm = optimizer.last_grad_norm
             losses.append(loss.item())
             step += 1
             if step % print_every == 0:
-                log('iter: {}, loss: {:.4f}, batch-time: {:.4f}s, lr: {}{}'.format(
+                log('iter: {}, loss: {:.4f}, batch-time: {:.4f}s, lr: {}{}{}'.format(
                     step, losses[-1], time.perf_counter() - start, optimizer.param_groups[0]['lr'],
-                    ', grad-norm: {:.4f}'.format(grad_norm.item()) if clipping else ''))
+                    ', grad-norm: {:.4f}'.format(grad_norm.item()) if clipping else '',
+                    ', sigma: {:.5f}'.format(log_sigma.detach().exp().item()) if log_sigma is not None else ''))
             if step >= max_steps:
                 break
     if beta is not None:
         model.beta = float(beta)
+    extra = {}
+    if log_sigma is not None:
+        model.sigma = float(log_sigma.detach().exp().item())
+        extra['log_sigma'] = log_sigma.detach().cpu()
     if checkpoint_path and (not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0):
-        save_checkpoint(checkpoint_path, model, optimizer, epoch=0, iteration=step)
+        save_checkpoint(checkpoint_path, model, optimizer, epoch=0, iteration=step, **extra)
     return losses
+
+
+def add_sigma_group(optimizer, log_sigma, lr):
+    """``log_sigma`` as a param group of its own, behind the model's (the layout ``resume`` expects)"""
+    optimizer.add_param_group({'params': [log_sigma], 'lr': lr, 'weight_decay': 0.0})
+
+
+def resume(path, model, optimizer, log_sigma=None, lr=3e-4):
+    """``load_checkpoint`` for a run with or without ``--learn-sigma``; the file is read once.  A checkpoint written with ``--learn-sigma``
+    holds the entry ``log_sigma`` and, in its optimizer state, the param group of that scalar: ``log_sigma`` joins ``optimizer`` before the
+    state loads and takes the saved value.  An older checkpoint has neither: the state loads into the model's groups and a fresh group is added
+    behind them.  Such a checkpoint resumed WITHOUT a ``log_sigma`` is refused in words - its optimizer state would not fit, and dropping the
+    learned scale silently would train on at another sigma.  Returns the extra entries (epoch, iteration, ...)."""
+    ckpt = torch.load(path, map_location=torch.device('cpu'))
+    saved = 'log_sigma' in ckpt
+    if saved and log_sigma is None:
+        raise ValueError(f'{path} was written with --learn-sigma: it holds a learned log_sigma = {float(ckpt["log_sigma"]):.5f} (sigma '
+                         f'{float(ckpt["log_sigma"].exp()):.5f}) and the optimizer state of its param group - resume it with --learn-sigma')
+    if saved:
+        add_sigma_group(optimizer, log_sigma, lr)
+    extra = load_checkpoint(ckpt, model, optimizer)
+    if saved:
+        with torch.no_grad():
+            log_sigma.copy_(extra['log_sigma'].to(log_sigma.device))
+    elif log_sigma is not None:
+        add_sigma_group(optimizer, log_sigma, lr)
+    return extra
+
+
+def make_log_sigma(sigma, device):
+    """The parameter of ``--learn-sigma``: log(sigma) as a float32 scalar on ``device`` that requires grad"""
+    import math
+    return torch.full((), math.log(float(sigma)), dtype=torch.float32, device=device, requires_grad=True)
 
 
 def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None):
@@ -326,6 +372,12 @@ def make_parser():
     ap.add_argument('--ignore-border', type=int, default=0, metavar='N',
                     help='train with zero observation weight on an N-pixel frame around every image (per-pixel weights: the border is not '
                          'part of the objective, the reconstruction still covers it)')
+    ap.add_argument('--learn-sigma', action='store_true',
+                    help='learn the likelihood scale: a parameter log_sigma (initially log of --sigma / ARCH.SIGMA) in its own param group, '
+                         'model.sigma = exp(log_sigma) before every step; saved as the checkpoint entry log_sigma')
+    ap.add_argument('--stable-encoding', action='store_true',
+                    help='mask_posterior channel of the refinement input as a max-subtracted softmax (model.stable_encoding): finite where the '
+                         "reference's un-stabilised form is 0 / 0, which a small or shrinking sigma reaches")
     return ap
 
 
@@ -350,9 +402,13 @@ def main(argv=None):
     if args.sigma is not None:
         model.sigma = args.sigma
     model.beta, model.iter_weights = args.beta, args.iter_weights
+    model.stable_encoding = args.stable_encoding
     optimizer = make_optimizer(model, base_lr=args.lr, max_grad_norm=args.clip)
+    log_sigma = make_log_sigma(model.sigma, device) if args.learn_sigma else None
     if args.resume:
-        load_checkpoint(args.resume, model, optimizer)
+        resume(args.resume, model, optimizer, log_sigma, args.lr)
+    elif log_sigma is not None:
+        add_sigma_group(optimizer, log_sigma, args.lr)
     if args.clevr:
         ds = CLEVR(args.clevr)
     elif args.dsprites:
@@ -368,7 +424,7 @@ def main(argv=None):
     dl = make_dataloader(train_ds, args.batch, shuffle=True, rank=rank, world_size=world)
     losses = train(model, optimizer, dl, device, args.steps, checkpoint_path=args.save,
                    log=print if rank == 0 else (lambda *a: None), beta=args.beta, beta_warmup_steps=args.beta_warmup,
-                   bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border)
+                   bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border, log_sigma=log_sigma)
     ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device)
     if rank == 0:
         print('first loss {:.2f} -> last loss {:.2f}; Ari over all ranks: {}'.format(losses[0], losses[-1], ev.global_mean))

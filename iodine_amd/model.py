@@ -148,12 +148,40 @@ class _RefineState:
     serial: Optional[int] = None
 
 
+# A ``model.sigma`` that requires grad is the LAST input of the autograd nodes below, behind the module's parameters (otherwise they take the
+# inputs they always took).  Sigma reaches the loss only through the direct likelihood term of each ELBO evaluation - the refinement inputs
+# are detached (iodine.py:343) - so its gradient is one scalar that the forward returns next to its other outputs when asked
+# (``sigma_grad=True``; iodine_last_sigma_grad): S = sum_e w_e dLL_e/dsigma of a training forward, dLL/dsigma of an elbo.  Auxiliary
+# cotangents (attach_state, attach_frames, a carried state) add nothing to it.
+def _split_sigma(module, params):
+    """in ``forward``: (the module's parameters, the trailing sigma input or None)"""
+    n = len(module._ordered_params())
+    return params[:n], (params[n] if len(params) > n else None)
+
+
+def _sigma_keep(ctx, sigma, s):
+    """in ``forward``: keep S (None when sigma is not an input) for ``_sigma_tail``"""
+    ctx.sigma_s = s if sigma is not None else None
+    ctx.sigma_shape = sigma.shape if sigma is not None else None
+
+
+def _sigma_tail(ctx, g, sign):
+    """in ``backward``: the gradient of the trailing sigma input - sign * g * S -, or nothing when sigma was not an input"""
+    if ctx.sigma_s is None:
+        return ()
+    if g is None:
+        return (None,)
+    return ((sign * g.to(torch.float32) * ctx.sigma_s).reshape(ctx.sigma_shape),)
+
+
 class _TrainStep(torch.autograd.Function):
     """``loss = model(x)`` / ``loss.backward()`` through iodine_train_forward / iodine_train_backward."""
 
     @staticmethod
     def forward(ctx, module, x, eps, w, *params):
-        loss, elbo_iter = module._train_forward(x, eps, weights=w)
+        params, sigma = _split_sigma(module, params)
+        loss, elbo_iter, *sg = module._train_forward(x, eps, weights=w, sigma_grad=sigma is not None)
+        _sigma_keep(ctx, sigma, sg[0] if sg else None)
         ctx.module = module
         ctx.serial = module._call_serial            # identity of the saved forward (the library keeps exactly one)
         ctx.n = len(params)
@@ -163,7 +191,7 @@ class _TrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss, _grad_elbo):
         grads = ctx.module._train_backward(grad_loss, ctx.serial)
-        return (None, None, None, None, *grads)
+        return (None, None, None, None, *grads, *_sigma_tail(ctx, grad_loss, -1.0))
 
 
 class _TrainStepAttached(torch.autograd.Function):
@@ -178,7 +206,9 @@ class _TrainStepAttached(torch.autograd.Function):
     def forward(ctx, module, x, eps, w, attach, s_pm, s_plv, s_h, s_c, *params):
         ctx.set_materialize_grads(False)                   # an output the loss does not use arrives as None -> a NULL pointer
         state = None if s_pm is None else (s_pm, s_plv, s_h, s_c)
-        loss, elbo_iter = module._train_forward(x, eps, state, weights=w)
+        params, sigma = _split_sigma(module, params)
+        loss, elbo_iter, *sg = module._train_forward(x, eps, state, weights=w, sigma_grad=sigma is not None)
+        _sigma_keep(ctx, sigma, sg[0] if sg else None)
         ctx.module, ctx.serial, ctx.from_state = module, module._call_serial, state is not None
         ctx.BK = (x.shape[0], module.K)
         ctx.mark_non_differentiable(elbo_iter)
@@ -205,7 +235,7 @@ class _TrainStepAttached(torch.autograd.Function):
             grads, gstate = ctx.module._train_backward_seq(g_loss, ctx.serial, aux, (g_h, g_c), want, ctx.BK)
         if ctx.from_state:                                 # the initial posterior is not part of a forward from a state: unused parameters
             grads = [None if n.startswith('posterior.') else g for (n, _), g in zip(ctx.module.named_parameters(), grads)]
-        return (None, None, None, None, None, *gstate, *grads)
+        return (None, None, None, None, None, *gstate, *grads, *_sigma_tail(ctx, g_loss, -1.0))
 
 
 _FRAME_KEYS = ('z', 'mean', 'mask', 'mask_logits', 'post_mean', 'post_logvar')     # the order of the library's six pointers
@@ -220,7 +250,9 @@ class _TrainStepFrames(torch.autograd.Function):
     def forward(ctx, module, x, eps, w, attach, index, s_pm, s_plv, s_h, s_c, *params):
         ctx.set_materialize_grads(False)                   # an unused kind arrives as None -> a NULL pointer
         state = None if s_pm is None else (s_pm, s_plv, s_h, s_c)
-        loss, elbo_iter, frames = module._train_forward(x, eps, state, weights=w, frames=index)
+        params, sigma = _split_sigma(module, params)
+        loss, elbo_iter, frames, *sg = module._train_forward(x, eps, state, weights=w, frames=index, sigma_grad=sigma is not None)
+        _sigma_keep(ctx, sigma, sg[0] if sg else None)
         ctx.module, ctx.serial, ctx.from_state = module, module._call_serial, state is not None
         ctx.BK, ctx.attach, ctx.index = (x.shape[0], module.K), attach, index
         ctx.mark_non_differentiable(elbo_iter)
@@ -246,7 +278,7 @@ class _TrainStepFrames(torch.autograd.Function):
                                                        frames=(ctx.index, gf) if any(g is not None for g in gf) else None)
         if ctx.from_state:                                 # the initial posterior is not part of a forward from a state: unused parameters
             grads = [None if n.startswith('posterior.') else g for (n, _), g in zip(ctx.module.named_parameters(), grads)]
-        return (None, None, None, None, None, None, *gstate, *grads)
+        return (None, None, None, None, None, None, *gstate, *grads, *_sigma_tail(ctx, g_loss, -1.0))
 
 
 _WRAPPER_OPTIONS = ('batch_cap',)      # max images per library call (IODINE.max_batch); the rest go to iodine_set_option
@@ -259,7 +291,9 @@ class _ChunkedTrainStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, x, eps, w, state, keep_state, *params):
-        loss, elbo_iter, flat = module._train_chunked(x, eps, state, keep_state, w)
+        params, sigma = _split_sigma(module, params)
+        loss, elbo_iter, flat, sg = module._train_chunked(x, eps, state, keep_state, w, sigma_grad=sigma is not None)
+        _sigma_keep(ctx, sigma, sg)                         # (S: every chunk's share of the batch, added up by _train_chunked)
         ctx.module, ctx.flat, ctx.from_state = module, flat, state is not None
         ctx.mark_non_differentiable(elbo_iter)
         return loss, elbo_iter
@@ -272,7 +306,7 @@ class _ChunkedTrainStep(torch.autograd.Function):
             # (from a detached state the initial posterior is not part of the forward: None, like unused parameters elsewhere)
             views.append(None if ctx.from_state and n.startswith('posterior.') else flat[off:off + p.numel()].view_as(p))
             off += p.numel()
-        return (None, None, None, None, None, None, *views)
+        return (None, None, None, None, None, None, *views, *_sigma_tail(ctx, grad_loss, -1.0))
 
 
 def _flat_views(module, flat, live):
@@ -342,13 +376,17 @@ class _ElboGrad(torch.autograd.Function):
     def forward(ctx, module, x, eps, w, pm, plv, *params):
         ctx.set_materialize_grads(False)
         ctx.module, ctx.init = module, pm is None
+        params, sigma = _split_sigma(module, params)
+        ctx.n = len(params)
         want_p = any(p.requires_grad for p in params)
         want_post = pm is not None and (pm.requires_grad or plv.requires_grad)
         if x.shape[0] <= module.max_batch():
-            elbo = module._elbo_call(x, eps, pm, plv, save=True, weights=w)
+            r = module._elbo_call(x, eps, pm, plv, save=True, weights=w, sigma_grad=sigma is not None)
+            elbo, sg = r if sigma is not None else (r, None)
             ctx.serial, ctx.pre, ctx.BK = module._call_serial, None, (x.shape[0], module.K)
-            return elbo
-        elbo, ctx.pre = module._elbo_chunked_grad(x, eps, pm, plv, want_post, want_p, w)
+        else:
+            elbo, ctx.pre, sg = module._elbo_chunked_grad(x, eps, pm, plv, want_post, want_p, w, sigma_grad=sigma is not None)
+        _sigma_keep(ctx, sigma, sg)
         return elbo
 
     @staticmethod
@@ -363,10 +401,10 @@ class _ElboGrad(torch.autograd.Function):
             gpm, gplv, flat = (None if t is None else t * gs for t in ctx.pre)
         else:
             want_post = (not ctx.init) and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
-            gpm, gplv, flat = m._elbo_backward(ctx.serial, ctx.BK, g, want_post, any(ctx.needs_input_grad[6:]))
+            gpm, gplv, flat = m._elbo_backward(ctx.serial, ctx.BK, g, want_post, any(ctx.needs_input_grad[6:6 + ctx.n]))
             flat = m._own(flat)
         return (None, None, None, None, gpm if ctx.needs_input_grad[4] else None, gplv if ctx.needs_input_grad[5] else None,
-                *_flat_views(m, flat, live))
+                *_flat_views(m, flat, live), *_sigma_tail(ctx, g, 1.0))
 
 
 class IODINE(nn.Module):
@@ -382,6 +420,8 @@ class IODINE(nn.Module):
         self.sigma = ARCH.SIGMA         # likelihood scale, read when a call starts (iodine.py:210)
         self.beta = 1.0                 # weight of the KL term: ELBO = LL - beta * KL; elbo_terms[:, 1] and the logger's kl stay the raw KL
         self.iter_weights = None        # loss weights of the T + 1 ELBO evaluations of forward: None / 'linspace', 'uniform', 'last', a sequence
+        self.stable_encoding = False    # True: the mask_posterior channel of the refinement input as a max-subtracted softmax over the slots
+                                        # (option stable_encoding) - finite where the reference's exp(s_k) / sum_j exp(s_j) is 0 / 0
         self.use_layernorm = ARCH.LAYERNORM
         self.use_stop_gradient = _arch_get(ARCH, 'STOP_GRADIENT', False)
 
@@ -418,6 +458,7 @@ class IODINE(nn.Module):
         self._shape = None              # (slots, iters) the handle runs at (iodine_set_run_shape); follows self.K / self.n_iters
         self._frames = 0                # frames per call the handle expects (iodine_set_frames; 0 = one image)
         self._objective = None          # (sigma, beta, weights) the handle holds (iodine_set_objective); None: the constructor's
+        self._modes = {}                # options stable_encoding / sigma_grad as the handle holds them (_ensure_objective)
         self._state = None              # _RefineState of the last encode / reconstruct: see refinement_state
         self._options: Dict[str, float] = {}
         self._seed = 0                  # Philox key of the library's normal generator (manual_seed)
@@ -471,6 +512,7 @@ class IODINE(nn.Module):
                 if k in _WRAPPER_OPTIONS:
                     continue
                 _lib.check(L.iodine_set_option(h, k.encode(), v), h)
+            self._modes = {k: bool(self._options.get(k)) for k in ('stable_encoding', 'sigma_grad')}
             names = []
             for i in range(L.iodine_num_params(h)):
                 nm, nd, dims = C.c_char_p(), C.c_int(), (C.c_longlong * 4)()
@@ -585,7 +627,7 @@ class IODINE(nn.Module):
         def number(v, name, rule, ok):
             # a Python or numpy real number, or a tensor / array with one element - what a schedule usually produces
             if torch.is_tensor(v) and v.numel() == 1 and not v.is_complex():
-                v = v.item()
+                v = v.detach().item()
             elif not isinstance(v, numbers.Real) and getattr(v, 'size', None) == 1 and hasattr(v, 'item'):
                 v = v.item()
             if isinstance(v, bool) or not isinstance(v, numbers.Real):
@@ -621,7 +663,13 @@ class IODINE(nn.Module):
             raise ValueError(f'IODINE: model.iter_weights are all zero (as float32) - no evaluation would carry any loss; got {w!r}')
         return sigma, beta, w
 
-    def _ensure_objective(self, h, obj, device):
+    def _ensure_objective(self, h, obj, device, sigma_grad=False):
+        """The objective of the call that is starting, ``model.stable_encoding`` and whether the call differentiates sigma (option
+        sigma_grad; ``set_option('sigma_grad', 1)`` keeps it on for every call) on the handle - each sent only when it differs."""
+        for key, want in (('stable_encoding', bool(self.stable_encoding)), ('sigma_grad', bool(sigma_grad or self._options.get('sigma_grad')))):
+            if self._modes.get(key, False) != want:
+                _lib.check(_lib.lib().iodine_set_option(h, key.encode(), float(want)), h, 'iodine_set_option')
+                self._modes[key] = want
         if obj == self._objective:
             return
         sigma, beta, w = obj
@@ -629,6 +677,26 @@ class IODINE(nn.Module):
         with torch.cuda.device(device):                     # (a new weight table is a small device allocation of the handle)
             _lib.check(_lib.lib().iodine_set_objective(h, sigma, beta, arr, len(w)), h, 'iodine_set_objective')
         self._objective = obj
+
+    # ``model.sigma`` as a tensor that requires grad (a leaf, or e.g. ``log_sigma.exp()``): the value handed to the library is still a host
+    # number - one ``.item()`` per call, and a sigma that changes every step runs eagerly in graph mode, like a beta schedule - and the
+    # call also computes d LL / d sigma (option sigma_grad), which ``backward()`` turns into ``sigma.grad``.
+    def _sigma_input(self):
+        """() or (model.sigma,): the extra autograd input of a call that must differentiate sigma (grad mode on)"""
+        s = self.sigma
+        live = torch.is_tensor(s) and s.requires_grad and s.numel() == 1 and torch.is_grad_enabled()
+        return (s,) if live else ()
+
+    def _fetch_sigma_grad(self, h, dev, n, weights=None):
+        """After a library call that ran with sigma_grad: sum_e w_e dLL_e/dsigma over its n evaluations (weights: the iteration weights it
+        ran with, () = the default; None: n = 1, the value itself) as a device scalar."""
+        out = self._out('t.dll', (n,), dev)
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_last_sigma_grad(h, self._stream(), _lib.ptr(out), n), h,
+                                             'iodine_last_sigma_grad'))
+        if weights is None:
+            return out[0].clone()
+        wv = torch.tensor(list(weights) or [(i + 1) / n for i in range(n)], dtype=torch.float32, device=dev)
+        return (wv * out).sum()
 
     def _ensure_workspace(self, h, B, mode, device, K, T, frames=None):
         """Run shape (K, T), frame count and a workspace planned for (B, mode, K, T, frames) on the handle.  ``frames``: 0 = one image
@@ -771,8 +839,12 @@ class IODINE(nn.Module):
         self._options[key] = float(value)
         if key in _WRAPPER_OPTIONS:                 # handled by this wrapper, unknown to the library
             return
+        if key == 'stable_encoding':                # the same switch as the attribute, which every call reads
+            self.stable_encoding = bool(value)
         if self._handle is not None:
             _lib.check(_lib.lib().iodine_set_option(self._handle, key.encode(), float(value)), self._handle)
+            if key in self._modes:
+                self._modes[key] = bool(value)
         if key in ('conv_precision', 'conv_variant', 'gen_conv_precision'):
             self._param_versions = None          # the library keeps only the selected path's weight packs: re-send the parameters
         if key == 'wgrad_accum':
@@ -1090,12 +1162,13 @@ class IODINE(nn.Module):
         pm, plv = self.posterior.mean, self.posterior.logvar
         shape = (x.shape[0], self.K, self.dim_latent) if x.dim() == 4 else None
         given = pm is not None and plv is not None and tuple(pm.shape) == shape and pm.device == x.device
+        sg = self._sigma_input()
         if differentiable is None:
-            differentiable = given and (pm.requires_grad or plv.requires_grad)
+            differentiable = (given and (pm.requires_grad or plv.requires_grad)) or bool(sg)
         if differentiable and torch.is_grad_enabled():
             xc = self._check_x(x)                           # (model.K / n_iters are checked by _elbo_call, before any device work)
             w = self._check_weights(weights, xc, 'weighted_elbo')
-            return _ElboGrad.apply(self, xc, eps, w, pm if given else None, plv if given else None, *self._ordered_params())
+            return _ElboGrad.apply(self, xc, eps, w, pm if given else None, plv if given else None, *self._ordered_params(), *sg)
         return self._elbo_nograd(x, eps, weights)
 
     @torch.no_grad()
@@ -1128,15 +1201,16 @@ class IODINE(nn.Module):
             pm = plv = None
         return self._elbo_call(x, eps, pm, plv, save=False, weights=weights)
 
-    def _elbo_call(self, x, eps, pm, plv, save, weights=None):
+    def _elbo_call(self, x, eps, pm, plv, save, weights=None, sigma_grad=False):
         """One iodine_elbo of at most ``max_batch`` images from the posterior (pm, plv) - None: the initial one; ``save``: kept for
-        iodine_elbo_backward.  x as ``_check_x``, weights as ``_check_weights`` return them."""
+        iodine_elbo_backward.  x as ``_check_x``, weights as ``_check_weights`` return them.  -> the ELBO; with ``sigma_grad`` (a saved call
+        only) -> (ELBO, d LL / d sigma)."""
         K, T = self._run_shape()
         obj = self._read_objective(T)
         dev, B = x.device, x.shape[0]
         h = self._sync_params(dev)
         self._ensure_workspace(h, B, 2 if save else 0, dev, K, T)
-        self._ensure_objective(h, obj, dev)
+        self._ensure_objective(h, obj, dev, save and sigma_grad)
         shape = (B, K, self.dim_latent)
         eps = self._normals(eps, shape, dev)
         if pm is not None:
@@ -1156,8 +1230,10 @@ class IODINE(nn.Module):
                 self._saving(h, False)
         terms = self._own(terms)
         self.elbo_terms = terms.view(1, 3)
+        sg = self._fetch_sigma_grad(h, dev, 1) if save and sigma_grad else None
         self._fetch_last_elbo(h, x, terms)
-        return terms[0].clone() if save else terms[0]
+        elbo = terms[0].clone() if save else terms[0]
+        return (elbo, sg) if sigma_grad else elbo
 
     def _elbo_backward(self, serial, BK, grad_out, want_post, want_p, flat=None):
         """iodine_elbo_backward for the saved elbo ``serial``: (d / d posterior.mean, d / d posterior.logvar, flat parameter gradients),
@@ -1178,17 +1254,22 @@ class IODINE(nn.Module):
         self._call_serial += 1                      # the saved pass is consumed (no retain_graph)
         return self._own(gpm), self._own(gplv), flat          # (flat: the caller takes its copy - graph mode - after its last chunk)
 
-    def _elbo_chunked_grad(self, x, eps, pm, plv, want_post, want_p, weights=None):
+    def _elbo_chunked_grad(self, x, eps, pm, plv, want_post, want_p, weights=None, sigma_grad=False):
         """Differentiable elbo of a batch above ``max_batch`` (see _ElboGrad): forward + backward of every chunk with its share of the
-        batch mean.  Returns the ELBO and (d / d posterior.mean, d / d posterior.logvar, flat parameter gradients) for grad_output 1."""
+        batch mean.  Returns the ELBO, (d / d posterior.mean, d / d posterior.logvar, flat parameter gradients) for grad_output 1 and, with
+        ``sigma_grad``, d LL / d sigma of the batch (else None)."""
         dev, B = x.device, x.shape[0]
-        parts, sizes, gpms, gplvs, flat = [], [], [], [], None
+        parts, sizes, gpms, gplvs, flat, sig = [], [], [], [], None, None
         pm0, plv0 = self.posterior.mean, self.posterior.logvar
         for s, e in self._chunks(B, self.max_batch()):
-            self._elbo_call(x[s:e].contiguous(), None if eps is None else eps[s:e], None if pm is None else pm[s:e],
-                            None if plv is None else plv[s:e], save=True, weights=None if weights is None else weights[s:e].contiguous())
+            r = self._elbo_call(x[s:e].contiguous(), None if eps is None else eps[s:e], None if pm is None else pm[s:e],
+                                None if plv is None else plv[s:e], save=True, weights=None if weights is None else weights[s:e].contiguous(),
+                                sigma_grad=sigma_grad)
+            sc = r[1] if sigma_grad else None
             parts.append(self._chunk_state()); sizes.append(e - s)
             w = torch.full((), (e - s) / float(B), device=dev, dtype=torch.float32)
+            if sc is not None:                              # this chunk's share of the batch mean
+                sig = sc * w if sig is None else sig + sc * w
             gpm, gplv, flat = self._elbo_backward(self._call_serial, (e - s, self.K), w, want_post, want_p, flat)
             if not want_p:
                 flat = None
@@ -1197,7 +1278,7 @@ class IODINE(nn.Module):
         self._merge_chunk_state(parts, sizes, x)
         pre = (torch.cat(gpms, 0) if want_post else None, torch.cat(gplvs, 0) if want_post else None,
                self._own(flat) if flat is not None else None)
-        return self.elbo_terms[0, 0].clone(), pre
+        return self.elbo_terms[0, 0].clone(), pre, sig
 
     # ---- training: iodine.py:115-158 + lib/engine/train.py:60-63 -------------------------------------
     def _check_attach_frames(self, attach_frames, T):
@@ -1271,6 +1352,7 @@ class IODINE(nn.Module):
         self._state = None                          # the state of an earlier encode / reconstruct ends here (refinement_state)
         self.frames = None
         attach = bool(attach_state) and torch.is_grad_enabled()
+        sg = self._sigma_input()
         state_grad = state is not None and torch.is_grad_enabled() and any(t.requires_grad for t in state)
         if B > self.max_batch(training=True):
             for on, what in ((attach, 'attach_state=True'), (state_grad, 'a state that requires grad'),
@@ -1282,25 +1364,11 @@ class IODINE(nn.Module):
                                        'batch per call')
             if state is not None:
                 state = tuple(t.detach() for t in state)
-            loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, weights, state, bool(keep_state), *self._ordered_params())
+            loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, weights, state, bool(keep_state), *self._ordered_params(), *sg)
             self.elbo_terms = elbo_iter
             return loss
         eps = self._eps(eps, B, x.device)
-        if index is not None:
-            out = _TrainStepFrames.apply(self, x, eps, weights, attach, index, *(state or (None,) * 4), *self._ordered_params())
-            loss, elbo_iter = out[:2]
-            if attach:
-                self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc = out[2:10]
-                self.lstm_hidden = (lh, lc)
-            self.frames = dict(index=index, **dict(zip(_FRAME_KEYS, out[-6:])))
-        elif attach:
-            (loss, elbo_iter, self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc
-             ) = _TrainStepAttached.apply(self, x, eps, weights, True, *(state or (None,) * 4), *self._ordered_params())
-            self.lstm_hidden = (lh, lc)
-        elif state is not None:
-            loss, elbo_iter = _TrainStepAttached.apply(self, x, eps, weights, False, *state, *self._ordered_params())
-        else:
-            loss, elbo_iter = _TrainStep.apply(self, x, eps, weights, *self._ordered_params())
+        loss, elbo_iter = self._apply_train_step(x, eps, weights, attach, index, state, sg)
         self.elbo_terms = elbo_iter
         with torch.no_grad():
             h, dev = self._handle, x.device
@@ -1315,6 +1383,25 @@ class IODINE(nn.Module):
             logger.update(init_mean=stats[0], init_logvar=stats[1])                    # iodine.py:156-157
         return loss
 
+    def _apply_train_step(self, x, eps, weights, attach, index, state, sg):
+        """The autograd node of one un-chunked ``forward`` (sg: ``_sigma_input()``, the trailing input) -> (loss, ELBO terms)"""
+        if index is not None:
+            out = _TrainStepFrames.apply(self, x, eps, weights, attach, index, *(state or (None,) * 4), *self._ordered_params(), *sg)
+            loss, elbo_iter = out[:2]
+            if attach:
+                self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc = out[2:10]
+                self.lstm_hidden = (lh, lc)
+            self.frames = dict(index=index, **dict(zip(_FRAME_KEYS, out[-6:])))
+        elif attach:
+            (loss, elbo_iter, self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc
+             ) = _TrainStepAttached.apply(self, x, eps, weights, True, *(state or (None,) * 4), *self._ordered_params(), *sg)
+            self.lstm_hidden = (lh, lc)
+        elif state is not None:
+            loss, elbo_iter = _TrainStepAttached.apply(self, x, eps, weights, False, *state, *self._ordered_params(), *sg)
+        else:
+            loss, elbo_iter = _TrainStep.apply(self, x, eps, weights, *self._ordered_params(), *sg)
+        return loss, elbo_iter
+
     def _fetch_train_state(self, B, dev):
         """(h, c) (B, K, MLP_UNITS) after the last update of the training forward that just ran (iodine_last_train_state)."""
         hh = torch.empty((B, self.K, int(self._cfg.ref_mlp_units)), device=dev, dtype=torch.float32)
@@ -1324,15 +1411,17 @@ class IODINE(nn.Module):
                                              h, 'iodine_last_train_state'))
         return hh, cc
 
-    def _train_forward(self, x, eps, state=None, weights=None, frames=None):
+    def _train_forward(self, x, eps, state=None, weights=None, frames=None, sigma_grad=False):
         """-> (loss, ELBO terms); with ``frames`` (a tuple of evaluation indices, possibly empty) also the six (F, B, K, ...) tensors of
-        those evaluations in the order of ``_FRAME_KEYS`` (iodine_train_forward_frames)."""
+        those evaluations in the order of ``_FRAME_KEYS`` (iodine_train_forward_frames); with ``sigma_grad`` also, last, the device scalar
+        sum_e w_e dLL_e/dsigma (the forward then runs with option sigma_grad)."""
         dev, B = x.device, x.shape[0]
         K, T = self._run_shape()
         obj = self._read_objective(T)
         h = self._sync_params(dev)
         self._ensure_workspace(h, B, 1, dev, K, T, x.shape[1] if x.dim() == 5 else 0)
-        self._ensure_objective(h, obj, dev)
+        self._ensure_objective(h, obj, dev, sigma_grad)
+        sg = lambda: (self._fetch_sigma_grad(h, dev, T + 1, obj[2]),) if sigma_grad else ()
         loss = self._out('t.loss', (), dev)
         elbo_iter = self._out('t.elbo', (T + 1, 3), dev)
         xs, eps = self._stage('x', x), self._stage('eps', eps)
@@ -1349,7 +1438,7 @@ class IODINE(nn.Module):
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward_frames(
                 h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), sptrs, _lib.ptr(loss), _lib.ptr(elbo_iter), idx, F, optrs),
                 h, 'iodine_train_forward_frames'))
-            return self._own(loss), self._own(elbo_iter), tuple(self._own(t) for t in outs)
+            return (self._own(loss), self._own(elbo_iter), tuple(self._own(t) for t in outs), *sg())
         if state is None:
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward(h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps),
                                                                                  _lib.ptr(loss), _lib.ptr(elbo_iter)),
@@ -1360,23 +1449,26 @@ class IODINE(nn.Module):
             ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in st])
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward_seq(
                 h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), ptrs, _lib.ptr(loss), _lib.ptr(elbo_iter)), h, 'iodine_train_forward_seq'))
-        return self._own(loss), self._own(elbo_iter)
+        return (self._own(loss), self._own(elbo_iter), *sg())
 
-    def _train_chunked(self, x, eps, state=None, keep_state=False, weights=None):
+    def _train_chunked(self, x, eps, state=None, keep_state=False, weights=None, sigma_grad=False):
         """Forward + backward of every chunk (see _ChunkedTrainStep): returns the batch loss, the (T+1, 3) ELBO terms of the whole
-        batch and d loss / d parameters as one flat buffer in named_parameters() order.  ``state``: a detached initial state, cut along
-        the batch; ``keep_state``: every chunk's LSTM state is copied out for ``refinement_state``."""
+        batch, d loss / d parameters as one flat buffer in named_parameters() order and, with ``sigma_grad``, sum_e w_e dLL_e/dsigma of
+        the batch (else None).  ``state``: a detached initial state, cut along the batch; ``keep_state``: every chunk's LSTM state is
+        copied out for ``refinement_state``."""
         dev, B = x.device, x.shape[0]
         flat = self._out('t.flat', (sum(p.numel() for p in self._ordered_params()),), dev)
-        loss, terms, parts, sizes, pms, plvs, hcs = None, None, [], [], [], [], []
+        loss, terms, parts, sizes, pms, plvs, hcs, sig = None, None, [], [], [], [], [], None
         for c, (s, e) in enumerate(self._chunks(B, self.max_batch(training=True))):
             xc = x[s:e].contiguous()
             ec = self._eps(None if eps is None else eps[:, s:e], e - s, dev)
-            lc, tc = self._train_forward(xc, ec, None if state is None else tuple(t[s:e].contiguous() for t in state),
-                                         None if weights is None else weights[s:e].contiguous())
+            lc, tc, *sc = self._train_forward(xc, ec, None if state is None else tuple(t[s:e].contiguous() for t in state),
+                                              None if weights is None else weights[s:e].contiguous(), sigma_grad=sigma_grad)
             h = self._handle
             w = torch.full((), (e - s) / float(B), device=dev, dtype=torch.float32)
             ws = self._stage('t.gl', w)
+            if sc:                                      # this chunk's share of the batch mean
+                sig = sc[0] * w if sig is None else sig + sc[0] * w
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_flat(h, self._stream(), _lib.ptr(ws), _lib.ptr(flat),
                                                                                        1 if c else 0), h, 'iodine_train_backward'))
             with torch.no_grad():
@@ -1399,7 +1491,7 @@ class IODINE(nn.Module):
             if keep_state:
                 self._state = _RefineState(self.posterior.mean, self.posterior.logvar, torch.cat([hc[0] for hc in hcs], 0),
                                            torch.cat([hc[1] for hc in hcs], 0))
-        return loss, self.elbo_terms, self._own(flat)
+        return loss, self.elbo_terms, self._own(flat), sig
 
     def _train_backward(self, grad_loss, serial, aux=None):
         """``aux``: None, or the cotangents (mean, mask, mask_logits, z, posterior.mean, posterior.logvar) of an attached forward, each a
