@@ -365,6 +365,33 @@ int iodine_train_backward_frames(iodine_handle* h, void* stream, const float* gr
  * (reconstruct, decode, a plain elbo), or the workspace was re-planned since.  The values survive the backward of that forward. */
 int iodine_last_sigma_grad(iodine_handle* h, void* stream, float* out, int n);
 
+/* Gradients into the image and the pixel weights (kernels_pixmap.hip): what the last compute call that ran with option "input_grad"
+ * accumulated.  With log_likelihood = logsumexp_k(log(mask + 1e-12) + K_log_likelihood) and LL = log_likelihood.mean(0).sum()
+ * (iodine.py:210-220), weighted per pixel by w_p (iodine_set_pixel_weights, 1 without):
+ *   d LL / d x[b,c,p] = -(1 / B) sum_k g1_kc,  g1_kc = w_p r_kc (x_c - mu_kc) / sigma^2  (r: responsibilities; the weight is inside)
+ *   d LL / d w[b,p]   =  (1 / B) sum_c log_likelihood[b,c,p]                             (raw: NOT multiplied by w)
+ * The refinement inputs are detached (iodine.py:343) and the KL term does not see the image: these direct terms are all of d ELBO / d x.
+ * The reference treats weights it does not have as data; here they are differentiable on request.
+ *   after iodine_train_forward / _seq / _frames:  sum_e a_e d LL_e / d (x, w)  with a_e the iteration weights the call ran with
+ *   (iodine_set_objective; beta does not enter; a_e = 0 adds an exact 0), added in evaluation order in fp32 -- d loss / d x is MINUS g_x.
+ *   A clip: frame e belongs to evaluation e alone, g_x (B, T + 1, 3, S, S) holds a_e d LL_e / d x_e, in the batch-first layout the entry
+ *   point took the clip in; g_w likewise (B, T + 1, S, S) when the call's weights were per frame, else (B, S, S) summed over the frames.
+ *   after an iodine_elbo that ran with option "save_for_backward":  d LL / d (x, w), g_x (B, 3, S, S), g_w (B, S, S).
+ * Either pointer may be NULL; device memory, written on `stream`.  IODINE_ERR_STATE when the last compute call left nothing: the option
+ * was off (or lacked the bit an output needs: 1 image, 2 weights), the call was of another kind (reconstruct, decode, a plain elbo), or the
+ * workspace was re-planned since.  The values survive the backward of that forward. */
+int iodine_last_input_grad(iodine_handle* h, void* stream, float* g_x, float* g_w);
+
+/* The per-pixel likelihood maps the reference leaves on the module after every elbo() (iodine.py:210-216), of the evaluation
+ * iodine_last_elbo_outputs reads -- computed on request from its decoder output and its image (its frame of a clip):
+ *   k_log_likelihood (count, K, 3, S, S) = gaussian_log_likelihood(x[:, None], mean, sigma),
+ *   log_likelihood   (count, 3, S, S)    = logsumexp_k(log(mask + 1e-12) + k_log_likelihood);     either may be NULL.
+ * K = the slots of that call; sigma = the handle's current objective.  RAW: pixel weights do not enter (the weighted LL the call reported is
+ * sum_p w_p sum_c log_likelihood).  The kernel is apart from the one that sums the reported LL: sum_c of the map agrees with
+ * elbo_iter[..][2] to fp32 rounding, not bitwise.  Plain outputs: nothing is attached to a graph (the reference's attributes are).
+ * Same count rule and refusals as iodine_last_elbo_outputs (IODINE_ERR_STATE when no elbo() has run on the current workspace). */
+int iodine_last_likelihood(iodine_handle* h, void* stream, int count, float* log_likelihood, float* k_log_likelihood);
+
 /* logger.update(init_mean=posterior.init_mean.mean(), init_logvar=posterior.init_logvar.mean()) -- iodine.py:156-157:
  * out2 (2, device) = the two means of the parameters last handed to iodine_set_params. */
 int iodine_logger_scalars(iodine_handle* h, void* stream, float* out2);
@@ -431,6 +458,11 @@ int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, i
  * evaluation -- one more per-pixel kernel and a one-block reduction per evaluation, read back with iodine_last_sigma_grad; part of the
  * hipGraph key; 0 -- default: no launch differs.  The two small buffers behind it -- 8 bytes per image and 512 pixels, 4 per evaluation --
  * are part of every workspace plan, option on or off, so iodine_workspace_bytes does not depend on it),
+ * "input_grad" (bit 1 = image, bit 2 = pixel weights; with a bit set iodine_train_forward* and an iodine_elbo under "save_for_backward"
+ * also accumulate sum_e a_e d LL_e / d x (d w) -- one more per-pixel kernel per evaluation, read back with iodine_last_input_grad; part of
+ * the hipGraph key.  The accumulators are carved behind everything else and only while a bit is set: with 0 -- default -- no launch
+ * differs and iodine_workspace_bytes returns what it returned before the option existed; a change re-plans the workspace at the next
+ * compute call),
  * "stable_encoding" (channel 8 of the refinement input, mask_posterior.  0 -- default, the reference: exp(s_k) / sum_j exp(s_j) with
  * s_k = sum_c log N(x_c; mu_kc, sigma) and NO max-subtraction (iodine.py:286-293), which is 0 / 0 = NaN at a pixel every slot misses by
  * about 8.5 sigma in all three channels (float32 exp returns 0 below s_k = -103.98) and then poisons that image's refinement; 1: q_k / sum_j q_j with q_k = exp(s_k - max_j s_j), the softmax over the
@@ -498,7 +530,7 @@ int iodine_set_option(iodine_handle* h, const char* key, double value);
 /* Sum of event-measured durations (ms) and number of launches of one kernel category since the last reset:
  * "conv_tile_fwd", "conv_tile_dgrad", "conv_tile_wgrad", "dec_out", "dec_out_dgrad", "dec_out_wgrad", "dec_out_bwd", "dec_l0",
  * "l0_reduce",
- * "pixel_pass1", "pixel_pass2", "pixel_sigma_grad" (option sigma_grad), "refine_l0" (first refinement layer), "refine_l0f" (encoding + first refinement layer in one
+ * "pixel_pass1", "pixel_pass2", "pixel_sigma_grad" (option sigma_grad), "pixel_input_grad" (option input_grad), "refine_l0" (first refinement layer), "refine_l0f" (encoding + first refinement layer in one
  * kernel, option refine_l0_fused), "refine_conv" (the others), "refine_head", "refine_wgrad", "refine_dgrad", "refine_bwd01"
  * (fused layer-1 data gradient + layer-0 weight gradient, option refine_bwd_fused), "refine_bias_grad", "head_bwd", "gen_conv"
  * (the fp32 convs of the generic path), "gen_conv_f16x3" (its split-fp16 launches, option gen_conv_precision 1), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward), "render_bwd" (backward of the rendering - sigmoid, slot softmax, sum_k mask x mean - in iodine_decode_backward; the decoder pass behind it is booked under the categories of the training step), "frames_in" (the image / clip conversion at the head of
@@ -592,6 +624,15 @@ int iodine_op_render_bwd(void* stream, const float* dec_out, const float* g_pred
  * the softmax backward -- the rendering backward of iodine_train_backward_aux; g_logits NULL: iodine_op_render_bwd, bit for bit. */
 int iodine_op_render_bwd_logits(void* stream, const float* dec_out, const float* g_pred, const float* g_mask, const float* g_mean,
                                 const float* g_logits, float* g_out, int batch, int slots, int pixels, int strict);
+
+/* the two per-pixel kernels of kernels_pixmap.hip (iodine.py:210-220) on a caller's decoder output, for kernel-level tests at any pixel
+ * count: x_nchw (batch,3,pixels), w (batch,pixels) or NULL (= 1), dec_out [batch * slots][pixels][4]; slots 1..16.
+ *   ll (batch,3,pixels), kll (batch,slots,3,pixels): the raw maps (iodine_last_likelihood);
+ *   gx (batch,3,pixels) = (first ? 0 : gx) + coef * -sum_k g1_kc,  gw (batch,pixels) = (first ? 0 : gw) + coef * sum_c ll_c
+ *   (iodine_last_input_grad with coef = a_e / B).  Any of the four may be NULL.  strict as for iodine_op_render_bwd.  Allocates,
+ * synchronises and frees per call -- not for timing.  IODINE_ERR_INVALID, without a launch, for a bad argument. */
+int iodine_op_pixel_maps(void* stream, const float* x_nchw, const float* w_or_null, const float* dec_out_nhwc4, int batch, int slots,
+                         int pixels, float sigma, int strict, float coef, float* ll, float* kll, float* gx, float* gw, int first);
 
 #ifdef __cplusplus
 }

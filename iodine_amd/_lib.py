@@ -34,6 +34,7 @@ EXPORTS = (
     'iodine_set_pixel_weights',
     'iodine_train_forward_frames', 'iodine_train_backward_frames',
     'iodine_last_sigma_grad',
+    'iodine_last_input_grad', 'iodine_last_likelihood', 'iodine_op_pixel_maps',
 )
 
 
@@ -145,6 +146,10 @@ def lib() -> C.CDLL:
         L.iodine_train_backward_frames.argtypes = [vp, vp] + [vp] * 10 + [ci, C.POINTER(vp), C.POINTER(ci), ci, C.POINTER(vp)]
     if hasattr(L, 'iodine_last_sigma_grad'):            # (a sigma that requires grad; absent from older A/B builds, which raise on one)
         L.iodine_last_sigma_grad.argtypes = [vp, vp, vp, ci]
+    if hasattr(L, 'iodine_last_input_grad'):            # (x / weights that require grad, likelihood maps; absent from older A/B builds, which raise on them)
+        L.iodine_last_input_grad.argtypes = [vp, vp, vp, vp]
+        L.iodine_last_likelihood.argtypes = [vp, vp, ci, vp, vp]
+        L.iodine_op_pixel_maps.argtypes = [vp, vp, vp, vp, ci, ci, ci, cf, ci, cf, vp, vp, vp, vp, ci]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

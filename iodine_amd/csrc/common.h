@@ -190,6 +190,14 @@ hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec,
 // option sigma_grad: out[0] = d LL / d sigma of the evaluation whose decoder output is dec (kernels_pixel.hip); part: B x blocks doubles
 hipError_t launch_pixel_sigma_grad(hipStream_t st, const float* x4, const float* dec, double* part, float* out, int B, int K, int P,
                                    double sigma, int strict);
+// kernels_pixmap.hip (iodine.py:210-220).  The raw per-pixel maps of the evaluation whose decoder output is dec: ll (B,3,P) = log_likelihood,
+// kll (B,K,3,P) = K_log_likelihood, NCHW, either may be NULL; the pixel weight in lane 3 of x4 is not read
+hipError_t launch_pixel_like_maps(hipStream_t st, const float* x4, const float* dec, float* ll, float* kll, int B, int K, int P, float sigma,
+                                  int strict);
+// option input_grad: gx[b * gx_bs + c * P + p] (=, first_x, or +=) coef * -sum_k g1_kc; gw[b * gw_bs + p] (=, first_w, or +=) coef * sum_c ll_c;
+// either pointer may be NULL.  g1 / ll_sum come from pixel_terms_core: the pixel weight is inside g1, gw is raw
+hipError_t launch_pixel_input_grad(hipStream_t st, const float* x4, const float* dec, float* gx, size_t gx_bs, float* gw, size_t gw_bs, int B,
+                                   int K, int P, float sigma, int strict, float coef, int first_x, int first_w);
 hipError_t launch_final_out(hipStream_t st, const float* dec, float* pred, float* mask, float* mean, float* logits,
                             int B, int K, int P);
 // kernels_render.hip: backward of the rendering (sigmoid, slot softmax, sum_k mask * mean) for the caller's gradients wrt pred (B,3,S,S),

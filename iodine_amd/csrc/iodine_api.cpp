@@ -416,6 +416,10 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
     // option sigma_grad (at the end: the carve-up in front of it is the same with or without a reader of these two)
     b.sg_part = a.take<double>((size_t)B * pixel_blocks_per_image(P));
     b.sgrad = a.take<float>((size_t)T + 1);
+    // option input_grad: carved only while a bit is set, behind everything else - with the option off the plan is what it was
+    b.ig = h->input_grad;
+    b.ig_x = (b.ig & 1) ? a.take<float>((size_t)b.F * B * 3 * P) : nullptr;
+    b.ig_w = (b.ig & 2) ? a.take<float>((size_t)b.F * B * P) : nullptr;
     b.bytes = (a.off + 255) & ~(size_t)255;
 }
 
@@ -432,7 +436,7 @@ void drop_graphs(iodine_handle* h)
 int ensure_workspace(iodine_handle* h, int B, int mode)
 {
     if (h->buf.B == B && h->buf.mode == mode && h->buf.K == h->K && h->buf.T == h->T && h->buf.F == (h->frames > 0 ? h->frames : 1) &&
-        h->buf.bytes > 0)
+        h->buf.ig == h->input_grad && h->buf.bytes > 0)
         return IODINE_OK;
     Arena q(nullptr); Buffers tmp; plan(h, B, mode, q, tmp);
     void* base = nullptr;
@@ -636,7 +640,7 @@ const float* x4_frame(const iodine_handle* h, int i)
 // elbo() + inner backward + get_input_encoding for iteration i (iodine.py:85-93 / 133-142)
 // sgrad: also leave d LL_i / d sigma in buf.sgrad[i] (option sigma_grad; the callers that offer it: training forward, saved elbo)
 int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps_i, int i, bool need_grads,
-                       bool train = false, float train_alpha = 0.f, bool sgrad = false)
+                       bool train = false, float train_alpha = 0.f, bool sgrad = false, int igrad = 0, float ig_coef = 0.f)
 {
     const float sigma = (float)h->obj.sigma, beta = (float)h->obj.beta;     // the handle's current objective (iodine_set_objective)
     Buffers& b = h->buf;
@@ -654,6 +658,17 @@ int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps
     if (sgrad)
         PROF(h, st, "pixel_sigma_grad", launch_pixel_sigma_grad(st, x4_frame(h, i), b.dec_out, b.sg_part, b.sgrad + i, B, h->K, h->P, h->obj.sigma,
                                                                 h->precision == 0));
+    if (igrad) {
+        // igrad: the bits of option input_grad; buf.ig_x / ig_w += ig_coef x d (B LL_i) / d (x, w).  A still image (and a weight map shared
+        // by the frames of a clip) is met by every evaluation: the first one writes, the others add, in evaluation order.  Frame i of a clip
+        // (per-frame weights alike) is met by evaluation i alone, and is written in the caller's batch-first layout
+        const size_t P = (size_t)h->P, F = train && h->frames > 0 ? (size_t)h->frames : 0;       // (a single elbo takes one image)
+        const bool wpf = F && h->ig_call_wpf;
+        PROF(h, st, "pixel_input_grad", launch_pixel_input_grad(st, x4_frame(h, i), b.dec_out, (igrad & 1) ? b.ig_x + (F ? i * 3 * P : 0) : nullptr,
+                                                                F ? F * 3 * P : 3 * P, (igrad & 2) ? b.ig_w + (wpf ? i * P : 0) : nullptr,
+                                                                wpf ? F * P : P, B, h->K, h->P, sigma, h->precision == 0, ig_coef,
+                                                                F || i == 0, wpf || i == 0));
+    }
     if (!need_grads) return IODINE_OK;
     float* dpre0 = nullptr;
     rc = decoder_backward_data(h, st, N, &dpre0, train, train_alpha, i);
@@ -799,7 +814,7 @@ std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, s
     uint64_t sb, bb;
     memcpy(&sb, &o->sigma, 8); memcpy(&bb, &o->beta, 8);
     std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->K, (uintptr_t)h->T, (uintptr_t)h->stop_after, (uintptr_t)h->precision,
-                                (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7) | (h->sigma_grad << 8) | (h->stable_enc << 9)),
+                                (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7) | (h->sigma_grad << 8) | (h->stable_enc << 9) | (h->input_grad << 10)),
                                 (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own), (uintptr_t)h->frames};
     k.push_back((uintptr_t)sb); k.push_back((uintptr_t)bb); k.push_back((uintptr_t)o->wgen);
     k.push_back((uintptr_t)(pw ? pw->w : nullptr)); k.push_back((uintptr_t)(pw ? pw->per_frame : 0));
@@ -1477,6 +1492,11 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
     if (!strcmp(key, "save_for_backward")) { h->save_bwd = value != 0; return IODINE_OK; }
     if (!strcmp(key, "fuse_l0")) { h->fuse_l0 = value != 0; return IODINE_OK; }
     if (!strcmp(key, "sigma_grad")) { h->sigma_grad = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "input_grad")) {
+        if (value != 0 && value != 1 && value != 2 && value != 3) return h->fail(IODINE_ERR_INVALID, "option input_grad: 0, 1 (image), 2 (pixel weights) or 3 (both)");
+        h->input_grad = (int)value;                    // (the next compute call re-plans the workspace: ensure_workspace keys on it)
+        return IODINE_OK;
+    }
     if (!strcmp(key, "stable_encoding")) { h->stable_enc = value != 0; return IODINE_OK; }
     if (!strcmp(key, "refine_split")) { h->refine_split = value != 0; return IODINE_OK; }
     if (!strcmp(key, "head_fused")) { h->head_fused = value != 0; return IODINE_OK; }
@@ -1658,6 +1678,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     rc = ensure_workspace(h, batch, save ? 2 : 0);
     if (rc) return rc;
     h->calls.compute_begins();                             // (the initial posterior below zeroes buf.h[0] / c[0])
+    h->ig_call_wpf = 0;
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K;
     auto body = [&]() -> int {
@@ -1669,7 +1690,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
         } else {
             HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, h->L, h->H));
         }
-        const int r = elbo_and_gradients(h, st, B, eps, 0, false, false, 0.f, save && h->sigma_grad);
+        const int r = elbo_and_gradients(h, st, B, eps, 0, false, false, 0.f, save && h->sigma_grad, save ? h->input_grad : 0, 1.f / (float)B);
         if (r) return r;
         if (terms) HIPCHK(h, hipMemcpyAsync(terms, b.scal, sizeof(float) * 3, hipMemcpyDeviceToDevice, st));
         // kept for iodine_elbo_backward: z (buf.z[0]), the activations, dec_out, d(B * ELBO) / d dec_out (buf.g), the posterior (buf.pm / plv)
@@ -1684,6 +1705,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     cs.last_elbo_batch = B;
     if (save) { cs.diff_kind = 2; cs.diff_batch = B; cs.diff_init = post_mean == nullptr; cs.diff_obj = h->obj; }
     cs.sgrad_n = save && h->sigma_grad ? 1 : 0;
+    cs.ig_bits = save ? h->input_grad : 0; cs.ig_frames = 0; cs.ig_wpf = 0;
     return IODINE_OK;
 }
 
@@ -1813,6 +1835,38 @@ int iodine_last_sigma_grad(iodine_handle* h, void* stream, float* out, int n)
     return IODINE_OK;
 }
 
+int iodine_last_input_grad(iodine_handle* h, void* stream, float* g_x, float* g_w)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_last_input_grad(h, stream, g_x, g_w);
+    const CallState& cs = h->calls;
+    if (cs.ig_bits == 0 || h->buf.bytes == 0)
+        return h->fail(IODINE_ERR_STATE, "iodine_last_input_grad: the last compute call left no d LL / d x or d LL / d w - it needs option input_grad and an "
+                                         "iodine_train_forward* or an iodine_elbo with option save_for_backward, with no compute call since");
+    if ((g_x && !(cs.ig_bits & 1)) || (g_w && !(cs.ig_bits & 2)))
+        return h->fail(IODINE_ERR_STATE, "iodine_last_input_grad: the last call ran without the bit of option input_grad that this output needs "
+                                         "(1: g_x, the image; 2: g_w, the pixel weights)");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t BP = (size_t)cs.last_elbo_batch * h->P, F = cs.ig_frames > 0 ? (size_t)cs.ig_frames : 1;
+    if (g_x) HIPCHK(h, hipMemcpyAsync(g_x, h->buf.ig_x, sizeof(float) * 3 * BP * F, hipMemcpyDeviceToDevice, st));
+    if (g_w) HIPCHK(h, hipMemcpyAsync(g_w, h->buf.ig_w, sizeof(float) * BP * (cs.ig_wpf ? F : 1), hipMemcpyDeviceToDevice, st));
+    return IODINE_OK;
+}
+
+int iodine_last_likelihood(iodine_handle* h, void* stream, int count, float* log_likelihood, float* k_log_likelihood)
+{
+    if (!h) return IODINE_ERR_INVALID;
+    if (h->shim) return pad_last_likelihood(h, stream, count, log_likelihood, k_log_likelihood);
+    if (int rc = last_elbo_outputs_check(h, count)) return rc;
+    const int K = h->buf.K;                                         // the slots of the call that produced the state, not the run shape
+    const Buffers& b = h->buf;
+    // the image that evaluation scored: frame last_elbo_iter of a clip (x4 is frame-major), else the one image
+    const float* x4 = b.x4 + (b.F > 1 ? (size_t)h->calls.last_elbo_iter * b.B * h->P * 4 : 0);
+    HIPCHK(h, launch_pixel_like_maps((hipStream_t)stream, x4, b.dec_out, log_likelihood, k_log_likelihood, count, K, h->P, (float)h->obj.sigma,
+                                     h->precision == 0));
+    return IODINE_OK;
+}
+
 int iodine_train_forward(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* loss,
                          float* elbo_iter)
 {
@@ -1850,6 +1904,7 @@ int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K, T = h->T, L = h->L;
     h->calls.compute_begins();
+    h->ig_call_wpf = pw.per_frame && h->frames > 0;
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const size_t eps_stride = (size_t)N * L;
@@ -1867,7 +1922,7 @@ int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x
         for (int i = 0; i <= T; ++i) {
             // d loss / d (B * ELBO_i) = -w_i / B; the default weighting keeps its closed form
             const float alpha = h->obj.whost ? -h->obj.whost[i] / (float)B : -((float)(i + 1) / (float)(T + 1)) / (float)B;
-            int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, true, alpha, h->sigma_grad != 0);
+            int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, true, alpha, h->sigma_grad != 0, h->input_grad, -alpha);
             if (r) return r;
             if (fr && fj < fr->n && fr->idx[fj] == i) {
                 // what this evaluation decoded and the lambda it sampled from (buf.pm / plv: the refinement step below moves them on);
@@ -1919,6 +1974,7 @@ int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x
     cs.last_elbo_iter = T;
     cs.last_elbo_batch = B;
     cs.sgrad_n = h->sigma_grad ? T + 1 : 0;
+    cs.ig_bits = h->input_grad; cs.ig_frames = h->frames > 0 ? h->frames : 0; cs.ig_wpf = h->ig_call_wpf;
     return IODINE_OK;
 }
 

@@ -32,6 +32,9 @@ struct Buffers {               // workspace carve-up for one batch size / mode /
     double* part;
     double* sg_part = nullptr;                 // option sigma_grad: per-block partials of one evaluation, [B][pixel_blocks_per_image]
     float* sgrad = nullptr;                    // ... and d LL_e / d sigma of the T + 1 evaluations of the call (iodine_last_sigma_grad)
+    int ig = 0;                                // option input_grad as planned (bit 1: ig_x, bit 2: ig_w; 0: neither is carved)
+    float* ig_x = nullptr;                     // sum_e a_e d LL_e / d x, (B,3,P); a clip: (B,F,3,P), one frame per evaluation
+    float* ig_w = nullptr;                     // sum_e a_e d LL_e / d w, (B,P) (a clip with per-frame weights: (B,F,P))
     std::vector<float*> act;                   // decoder activations a[0..Dd-1]   (N,P,Cd)
     float *head_xh = nullptr, *head_gp = nullptr;   // refinement head in three launches: LSTM input rows, gate pre-activations
     float* dpre[2];                            // ping-pong gradient wrt pre-activations
@@ -110,17 +113,20 @@ struct CallState {
     bool enc_valid = false;                     // the last call left the refinement input ("enc") of its iterations in the workspace
     int sgrad_n = 0;                            // values buf.sgrad holds: T + 1 after a training forward, 1 after a saved elbo - that ran with
                                                 // option sigma_grad; 0: the last compute call produced none (iodine_last_sigma_grad refuses)
+    int ig_bits = 0;                            // what buf.ig_x / ig_w hold of the last compute call (option input_grad; 0: nothing -
+    int ig_frames = 0, ig_wpf = 0;              // iodine_last_input_grad refuses), the frames of that call (0: a still image) and whether its
+                                                // weight gradient is per frame
     bool redecoded = false;                     // a backward decoded an earlier evaluation again (iodine_train_backward_frames): buf.dec_out no
                                                 // longer belongs to the last elbo(); the posterior and the LSTM state are untouched
 
     // iodine_set_params, a changed run shape or frames setting, a consumed backward (like autograd without retain_graph)
     void saved_passes_gone() { fwd_done = false; diff_kind = 0; }
     // a compute call re-uses the arena.  keep_lstm_state: a plain iodine_decode does not touch buf.h / buf.c
-    void compute_begins(bool keep_lstm_state = false) { saved_passes_gone(); redecoded = false; sgrad_n = 0; if (!keep_lstm_state) state_iter = -1; }
+    void compute_begins(bool keep_lstm_state = false) { saved_passes_gone(); redecoded = false; sgrad_n = 0; ig_bits = 0; if (!keep_lstm_state) state_iter = -1; }
     // a re-plan (ensure_workspace), iodine_set_workspace, a wgrad_accum toggle: nothing the arena held can be read any more.
     // (iodine_set_workspace used to leave enc_valid and the wgrad_accum toggle state_iter: unobservable, every reader of the two also
     // refuses while buf.bytes == 0, and the next compute call re-plans)
-    void arena_gone() { saved_passes_gone(); last_elbo_iter = -1; state_iter = -1; enc_valid = false; redecoded = false; sgrad_n = 0; }
+    void arena_gone() { saved_passes_gone(); last_elbo_iter = -1; state_iter = -1; enc_valid = false; redecoded = false; sgrad_n = 0; ig_bits = 0; }
 };
 #pragma GCC visibility pop
 
@@ -219,6 +225,9 @@ struct iodine_handle {
     size_t gacc_total = 0;
     int sigma_grad = 0;                         // option sigma_grad: a training forward / a saved elbo also leaves d LL_e / d sigma of every
                                                 // evaluation (one more per-pixel kernel per evaluation; off: no launch differs)
+    int input_grad = 0;                         // option input_grad: bit 1 image, bit 2 pixel weights - a training forward / a saved elbo also
+                                                // accumulates sum_e a_e d LL_e / d x (d w) (kernels_pixmap.hip; 0: no launch, no buffer)
+    int ig_call_wpf = 0;                        // (the running call's pixel weights are per frame: read by elbo_and_gradients inside the call)
     int stable_enc = 0;                         // option stable_encoding: channel 8 of the encoding as a max-subtracted softmax (pixel_terms.h)
     int save_bwd = 0;                           // option save_for_backward: a decode / elbo keeps what its backward reads (calls.diff_*)
     // hipGraph replay of the fixed-shape launch sequences (option "graph"): one instantiated graph per distinct argument tuple
@@ -328,6 +337,8 @@ int pad_train_backward(iodine_handle* h, void* stream, float grad_scale, const f
                        int accumulate, const AuxCot* aux);
 int pad_logger_scalars(iodine_handle* h, void* stream, float* out2);
 int pad_last_sigma_grad(iodine_handle* h, void* stream, float* out, int n);
+int pad_last_input_grad(iodine_handle* h, void* stream, float* g_x, float* g_w);
+int pad_last_likelihood(iodine_handle* h, void* stream, int count, float* log_likelihood, float* k_log_likelihood);
 int pad_debug_copy(iodine_handle* h, void* stream, const char* name, int iter, float* dst, size_t max_floats, size_t* n_floats);
 int pad_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset);
 

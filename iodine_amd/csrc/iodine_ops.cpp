@@ -390,6 +390,28 @@ int iodine_op_render_bwd_logits(void* stream, const float* dec_out, const float*
     return IODINE_OK;
 }
 
+int iodine_op_pixel_maps(void* stream, const float* x_nchw, const float* w_or_null, const float* dec_out_nhwc4, int batch, int slots,
+                         int pixels, float sigma, int strict, float coef, float* ll, float* kll, float* gx, float* gw, int first)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!x_nchw || !dec_out_nhwc4 || batch < 1 || slots < 1 || slots > 16 || pixels < 1 || !(sigma > 0.f) ||
+        (size_t)batch * slots * pixels >= ((size_t)1 << 31)) {
+        g_create_error = "iodine_op_pixel_maps: argument";
+        return IODINE_ERR_INVALID;
+    }
+    float* x4 = nullptr;
+    if (hipMalloc((void**)&x4, (size_t)batch * pixels * 4 * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+    hipError_t e = launch_x_to_nhwc4(st, x_nchw, x4, batch, pixels, 1, w_or_null, 0);
+    if (e == hipSuccess) e = launch_pixel_like_maps(st, x4, dec_out_nhwc4, ll, kll, batch, slots, pixels, sigma, strict ? 1 : 0);
+    if (e == hipSuccess)
+        e = launch_pixel_input_grad(st, x4, dec_out_nhwc4, gx, (size_t)3 * pixels, gw, (size_t)pixels, batch, slots, pixels, sigma, strict ? 1 : 0,
+                                    coef, first ? 1 : 0, first ? 1 : 0);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(x4);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_pixel_maps: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
 int iodine_op_conv3x3_wgrad_f32(void* stream, const float* in, const float* d, float* gw, float* gb, int n, int s, int c)
 {
     hipStream_t st = (hipStream_t)stream;

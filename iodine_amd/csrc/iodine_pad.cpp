@@ -206,6 +206,12 @@ int pad_set_objective(iodine_handle* h, double sigma, double beta, const double*
 int pad_set_option(iodine_handle* h, const char* key, double value) { return shim_fail(h, iodine_set_option(h->shim->inner, key, value)); }
 int pad_logger_scalars(iodine_handle* h, void* stream, float* out2) { return shim_fail(h, iodine_logger_scalars(h->shim->inner, stream, out2)); }
 int pad_last_sigma_grad(iodine_handle* h, void* stream, float* out, int n) { return shim_fail(h, iodine_last_sigma_grad(h->shim->inner, stream, out, n)); }
+// (per-pixel quantities: the padding is in the latent and channel widths, the slots and pixels are the caller's)
+int pad_last_input_grad(iodine_handle* h, void* stream, float* g_x, float* g_w) { return shim_fail(h, iodine_last_input_grad(h->shim->inner, stream, g_x, g_w)); }
+int pad_last_likelihood(iodine_handle* h, void* stream, int count, float* log_likelihood, float* k_log_likelihood)
+{
+    return shim_fail(h, iodine_last_likelihood(h->shim->inner, stream, count, log_likelihood, k_log_likelihood));
+}
 int pad_debug_copy(iodine_handle* h, void* stream, const char* name, int iter, float* dst, size_t max_floats, size_t* n_floats)
 {
     return shim_fail(h, iodine_debug_copy(h->shim->inner, stream, name, iter, dst, max_floats, n_floats));   // (padded widths)

@@ -198,7 +198,7 @@ def beta_warmup(step, beta, warmup_steps):
 
 
 def train(model, optimizer, dataloader, device, max_steps, print_every=10, checkpoint_path=None, log=print, max_grad_norm=None,
-          beta=None, beta_warmup_steps=0, bptt=None, ignore_border=0, log_sigma=None):
+          beta=None, beta_warmup_steps=0, bptt=None, ignore_border=0, log_sigma=None, input_gain=None):
     """train.py:44-108: loss = model(data); loss.mean(); zero_grad; backward; [all-reduce]; [clip]; step.  Returns the losses.
     ``max_grad_norm``: the global gradient norm is clipped at this value (train.py:64, commented out in the reference; the paper
     uses 5.0) AFTER the all-reduce, so every rank clips the same averaged gradient with the same coefficient - what
@@ -216,7 +216,14 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
     every step, so ``loss.backward()`` fills ``log_sigma.grad``; the log line gains ``sigma``, the checkpoint an entry ``log_sigma``, and
     ``model.sigma`` is left at the learned value as a plain float.  Every step then costs one ``.item()`` and runs eagerly in graph mode.
     Its gradient is part of the global norm that ``max_grad_norm`` clips, with the fused optimizer (which takes the norm over all its param
-    groups) and in front of any other alike."""
+    groups) and in front of any other alike.
+    ``input_gain``: a learned front end (``--learn-input-gain``, ``InputGain``) whose parameters sit in a param group of ``optimizer``: the
+    batch goes through it before the model, so ``loss.backward()`` reaches its parameters through ``x.grad`` - the gradient the model returns
+    for an image that requires grad.  Its gradients join the all-reduce and the clipped global norm; the checkpoint gains the entry
+    ``input_gain`` (its ``state_dict``).  Not combined with ``bptt``."""
+    if input_gain is not None and bptt is not None:
+        raise ValueError('train: input_gain is not combined with bptt (clip_backward differentiates its chunks itself)')
+    extra_params = ([log_sigma] if log_sigma is not None else []) + (list(input_gain.parameters()) if input_gain is not None else [])
     model.train()
     fused_clip = isinstance(optimizer, FusedAdam)
     if max_grad_norm is not None:
@@ -238,6 +245,8 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
                 model.beta = beta_warmup(step, beta, beta_warmup_steps)
             if log_sigma is not None:
                 model.sigma = log_sigma.exp()
+            if input_gain is not None:
+                x = input_gain(x)
             w = border_weights(x.shape[0], x.shape[-1], ignore_border, device) if ignore_border else None
             if bptt is not None:
                 optimizer.zero_grad()
@@ -247,9 +256,9 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
                 optimizer.zero_grad()
                 loss.backward()
             if world > 1:
-                parallel.allreduce_gradients(list(model.parameters()) + ([log_sigma] if log_sigma is not None else []))   # replaces DataParallel's reduce
+                parallel.allreduce_gradients(list(model.parameters()) + extra_params)   # replaces DataParallel's reduce
             if clipping and not fused_clip:
-                grad_norm = clip_grad_norm_(list(model.parameters()) + ([log_sigma] if log_sigma is not None else []), max_grad_norm)
+                grad_norm = clip_grad_norm_(list(model.parameters()) + extra_params, max_grad_norm)
             optimizer.step()
             if clipping and fused_clip:
                 grad_norm = optimizer.last_grad_norm
@@ -268,6 +277,8 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
     if log_sigma is not None:
         model.sigma = float(log_sigma.detach().exp().item())
         extra['log_sigma'] = log_sigma.detach().cpu()
+    if input_gain is not None:
+        extra['input_gain'] = {k: v.detach().cpu() for k, v in input_gain.state_dict().items()}
     if checkpoint_path and (not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0):
         save_checkpoint(checkpoint_path, model, optimizer, epoch=0, iteration=step, **extra)
     return losses
@@ -298,6 +309,21 @@ def resume(path, model, optimizer, log_sigma=None, lr=3e-4):
     elif log_sigma is not None:
         add_sigma_group(optimizer, log_sigma, lr)
     return extra
+
+
+class InputGain(torch.nn.Module):
+    """The front end of ``--learn-input-gain``: a per-channel gain and offset in front of the model, six parameters, the identity at the
+    start.  It is trained through the gradient the model returns for an image that requires grad (``x.grad``), by the same optimiser step -
+    the smallest front end that shows that gradient arriving (``main`` evaluates on the raw images afterwards: the six parameters belong to
+    the training loop, the checkpoint entry ``input_gain`` carries them).  ``x``: images (B, 3, S, S) or a clip (B, E, 3, S, S)."""
+
+    def __init__(self, device, channels=3):
+        super().__init__()
+        self.gain = torch.nn.Parameter(torch.ones(channels, device=device))
+        self.offset = torch.nn.Parameter(torch.zeros(channels, device=device))
+
+    def forward(self, x):
+        return x * self.gain.view(-1, 1, 1) + self.offset.view(-1, 1, 1)
 
 
 def make_log_sigma(sigma, device):
@@ -378,6 +404,9 @@ def make_parser():
     ap.add_argument('--stable-encoding', action='store_true',
                     help='mask_posterior channel of the refinement input as a max-subtracted softmax (model.stable_encoding): finite where the '
                          "reference's un-stabilised form is 0 / 0, which a small or shrinking sigma reaches")
+    ap.add_argument('--learn-input-gain', action='store_true',
+                    help='learn a per-channel gain and offset applied to every batch before the model (six parameters in their own param '
+                         'group, trained through the gradient into the image); saved as the checkpoint entry input_gain')
     return ap
 
 
@@ -409,6 +438,12 @@ def main(argv=None):
         resume(args.resume, model, optimizer, log_sigma, args.lr)
     elif log_sigma is not None:
         add_sigma_group(optimizer, log_sigma, args.lr)
+    input_gain = None
+    if args.learn_input_gain:
+        if args.resume or args.clip_frames:
+            raise SystemExit('--learn-input-gain starts a fresh run on still images; it cannot be combined with --resume / --clip-frames')
+        input_gain = InputGain(device)
+        optimizer.add_param_group({'params': list(input_gain.parameters()), 'lr': args.lr, 'weight_decay': 0.0})
     if args.clevr:
         ds = CLEVR(args.clevr)
     elif args.dsprites:
@@ -424,7 +459,8 @@ def main(argv=None):
     dl = make_dataloader(train_ds, args.batch, shuffle=True, rank=rank, world_size=world)
     losses = train(model, optimizer, dl, device, args.steps, checkpoint_path=args.save,
                    log=print if rank == 0 else (lambda *a: None), beta=args.beta, beta_warmup_steps=args.beta_warmup,
-                   bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border, log_sigma=log_sigma)
+                   bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border, log_sigma=log_sigma,
+                   input_gain=input_gain)
     ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device)
     if rank == 0:
         print('first loss {:.2f} -> last loss {:.2f}; Ari over all ranks: {}'.format(losses[0], losses[-1], ev.global_mean))

@@ -46,9 +46,24 @@ everywhere"), region-of-interest training, down-weighting a background:
     not weighted  the refinement-input channels that describe the scene (``mask_posterior``, ``likelihood``,
                   ``leave_one_out_likelihood``), the image channels, the KL
 
-Weights are data (no gradient; a tensor that requires grad is detached), their values the caller's contract (finite, >= 0, not checked on
-the device); zeros are allowed, an all-zero image included.  They hold for the one call they are passed to (``iodine_set_pixel_weights``
+A weight tensor that requires grad receives ``d loss / d w``; otherwise weights are data.  Their values are the caller's contract (finite, >= 0,
+not checked on the device); zeros are allowed, an all-zero image included.  They hold for the one call they are passed to (``iodine_set_pixel_weights``
 is one-shot); ``weights=None`` and weights of all ones compute the same bits.
+
+Gradients into the image and the weights: an ``x`` that requires grad (grad mode on) is a differentiable input of ``forward`` / ``elbo`` /
+``weighted_elbo``, like in the reference, whose refinement input is detached (iodine.py:343) - ``d loss / d x`` is the direct likelihood
+term of each ELBO evaluation, ``-sum_e a_e dLL_e/dx`` with ``dLL/dx[b,c,p] = -(1/B) sum_k w_p r_kc (x_c - mu_kc) / sigma^2``; frame e of a clip
+gets its own evaluation's term.  A floating-point ``weights=`` tensor that requires grad gets ``dLL/dw[b,p] = (1/B) sum_c log_likelihood[b,c,p]``
+(raw, not multiplied by w), in whichever accepted shape it was passed; a 4-D weight used for every frame of a clip gets the sum over the
+frames.  The reference has no weights; that they are differentiable is ours.  ``encode`` / ``reconstruct`` outputs stay detached (through
+them ``x`` has a zero gradient in the reference too).  Without either, no launch and no copy is added.
+
+Likelihood maps: with ``model.likelihood_maps = True`` every call that evaluates an ELBO (``elbo``, ``weighted_elbo``, ``forward``,
+``encode``, ``reconstruct``) leaves ``model.log_likelihood`` (B, 3, S, S) and ``model.K_log_likelihood`` (B, K, 3, S, S) of its last
+evaluation, the two attributes of iodine.py:210-216 - an anomaly map, a per-slot "who explains this pixel" view, a way to choose
+``weights=``.  Three deliberate differences from the reference: the maps are detached (the reference's are part of its graph), they are
+raw under ``weights=`` (the weighted LL is ``sum_p w_p sum_c log_likelihood``), and they come from a kernel of their own, so their sum
+over channels and pixels matches the reported LL to float32 rounding, not bitwise.  ``False`` (default): both are None, no launch runs.
 
 Extensions over the reference: every entry point takes an optional ``eps`` tensor of shape
 (T+1, B, K, L) replacing the ``torch.randn_like`` draws of ``Gaussian.sample``
@@ -174,14 +189,50 @@ def _sigma_tail(ctx, g, sign):
     return ((sign * g.to(torch.float32) * ctx.sigma_s).reshape(ctx.sigma_shape),)
 
 
+# The image and a floating-point ``weights=`` tensor that require grad are inputs 1 and 3 of the nodes below AS THE CALLER GAVE THEM (otherwise
+# the nodes take the checked, detached forms they always took).  Like sigma they reach the loss only through the direct likelihood term of each
+# ELBO evaluation - the refinement inputs are detached (iodine.py:343) -: the forward runs with option input_grad, reads
+# G = sum_e a_e dLL_e/d(x, w) back once (iodine_last_input_grad) and ``backward`` returns -g_loss * G (training) / +g * G (elbo), cast to
+# the caller's dtype and shape.  Auxiliary cotangents (attach_state, attach_frames, a carried state) add nothing to it.
+def _ig_inputs(ctx, module, x, w, what='forward'):
+    """in ``forward``: (x, w) in the library's form and the bits of option input_grad this call needs (1 image, 2 weights)"""
+    need = ctx.needs_input_grad
+    bits = (1 if need[1] else 0) | (2 if w is not None and need[3] else 0)
+    ctx.ig, ctx.ig_meta = None, None
+    if bits:
+        ctx.ig_meta = (x.dtype, x.shape, None if w is None else (w.dtype, w.shape, w.device))
+        x = x.detach().to(torch.float32).contiguous()
+        if bits & 2:
+            w = module._check_weights(w, x, what)
+    return x, w, bits
+
+
+def _ig_keep(ctx, module, bits):
+    """in ``forward``, after the library call(s): keep G = (d / d x, d / d w) for ``_ig_grads``"""
+    ctx.ig = module._last_ig if bits else None
+
+
+def _ig_grads(ctx, g, sign):
+    """in ``backward``: the gradients of inputs 1 (x) and 3 (w) - sign * g * G -, None where they were not asked for"""
+    if ctx.ig is None or g is None:
+        return None, None
+    sc = sign * g.to(torch.float32)
+    (xd, xs, wm), (Gx, Gw) = ctx.ig_meta, ctx.ig
+    gx = None if Gx is None else (sc * Gx).reshape(xs).to(xd)
+    gw = None if Gw is None else (sc * Gw).reshape(wm[1]).to(device=wm[2], dtype=wm[0])
+    return gx, gw
+
+
 class _TrainStep(torch.autograd.Function):
     """``loss = model(x)`` / ``loss.backward()`` through iodine_train_forward / iodine_train_backward."""
 
     @staticmethod
     def forward(ctx, module, x, eps, w, *params):
         params, sigma = _split_sigma(module, params)
-        loss, elbo_iter, *sg = module._train_forward(x, eps, weights=w, sigma_grad=sigma is not None)
+        x, w, ig = _ig_inputs(ctx, module, x, w)
+        loss, elbo_iter, *sg = module._train_forward(x, eps, weights=w, sigma_grad=sigma is not None, input_grad=ig)
         _sigma_keep(ctx, sigma, sg[0] if sg else None)
+        _ig_keep(ctx, module, ig)
         ctx.module = module
         ctx.serial = module._call_serial            # identity of the saved forward (the library keeps exactly one)
         ctx.n = len(params)
@@ -191,7 +242,8 @@ class _TrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss, _grad_elbo):
         grads = ctx.module._train_backward(grad_loss, ctx.serial)
-        return (None, None, None, None, *grads, *_sigma_tail(ctx, grad_loss, -1.0))
+        gx, gw = _ig_grads(ctx, grad_loss, -1.0)
+        return (None, gx, None, gw, *grads, *_sigma_tail(ctx, grad_loss, -1.0))
 
 
 class _TrainStepAttached(torch.autograd.Function):
@@ -207,8 +259,10 @@ class _TrainStepAttached(torch.autograd.Function):
         ctx.set_materialize_grads(False)                   # an output the loss does not use arrives as None -> a NULL pointer
         state = None if s_pm is None else (s_pm, s_plv, s_h, s_c)
         params, sigma = _split_sigma(module, params)
-        loss, elbo_iter, *sg = module._train_forward(x, eps, state, weights=w, sigma_grad=sigma is not None)
+        x, w, ig = _ig_inputs(ctx, module, x, w)
+        loss, elbo_iter, *sg = module._train_forward(x, eps, state, weights=w, sigma_grad=sigma is not None, input_grad=ig)
         _sigma_keep(ctx, sigma, sg[0] if sg else None)
+        _ig_keep(ctx, module, ig)
         ctx.module, ctx.serial, ctx.from_state = module, module._call_serial, state is not None
         ctx.BK = (x.shape[0], module.K)
         ctx.mark_non_differentiable(elbo_iter)
@@ -235,7 +289,8 @@ class _TrainStepAttached(torch.autograd.Function):
             grads, gstate = ctx.module._train_backward_seq(g_loss, ctx.serial, aux, (g_h, g_c), want, ctx.BK)
         if ctx.from_state:                                 # the initial posterior is not part of a forward from a state: unused parameters
             grads = [None if n.startswith('posterior.') else g for (n, _), g in zip(ctx.module.named_parameters(), grads)]
-        return (None, None, None, None, None, *gstate, *grads, *_sigma_tail(ctx, g_loss, -1.0))
+        gx, gw = _ig_grads(ctx, g_loss, -1.0)
+        return (None, gx, None, gw, None, *gstate, *grads, *_sigma_tail(ctx, g_loss, -1.0))
 
 
 _FRAME_KEYS = ('z', 'mean', 'mask', 'mask_logits', 'post_mean', 'post_logvar')     # the order of the library's six pointers
@@ -251,8 +306,10 @@ class _TrainStepFrames(torch.autograd.Function):
         ctx.set_materialize_grads(False)                   # an unused kind arrives as None -> a NULL pointer
         state = None if s_pm is None else (s_pm, s_plv, s_h, s_c)
         params, sigma = _split_sigma(module, params)
-        loss, elbo_iter, frames, *sg = module._train_forward(x, eps, state, weights=w, frames=index, sigma_grad=sigma is not None)
+        x, w, ig = _ig_inputs(ctx, module, x, w)
+        loss, elbo_iter, frames, *sg = module._train_forward(x, eps, state, weights=w, frames=index, sigma_grad=sigma is not None, input_grad=ig)
         _sigma_keep(ctx, sigma, sg[0] if sg else None)
+        _ig_keep(ctx, module, ig)
         ctx.module, ctx.serial, ctx.from_state = module, module._call_serial, state is not None
         ctx.BK, ctx.attach, ctx.index = (x.shape[0], module.K), attach, index
         ctx.mark_non_differentiable(elbo_iter)
@@ -278,7 +335,8 @@ class _TrainStepFrames(torch.autograd.Function):
                                                        frames=(ctx.index, gf) if any(g is not None for g in gf) else None)
         if ctx.from_state:                                 # the initial posterior is not part of a forward from a state: unused parameters
             grads = [None if n.startswith('posterior.') else g for (n, _), g in zip(ctx.module.named_parameters(), grads)]
-        return (None, None, None, None, None, None, *gstate, *grads, *_sigma_tail(ctx, g_loss, -1.0))
+        gx, gw = _ig_grads(ctx, g_loss, -1.0)
+        return (None, gx, None, gw, None, None, *gstate, *grads, *_sigma_tail(ctx, g_loss, -1.0))
 
 
 _WRAPPER_OPTIONS = ('batch_cap',)      # max images per library call (IODINE.max_batch); the rest go to iodine_set_option
@@ -292,8 +350,10 @@ class _ChunkedTrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, x, eps, w, state, keep_state, *params):
         params, sigma = _split_sigma(module, params)
-        loss, elbo_iter, flat, sg = module._train_chunked(x, eps, state, keep_state, w, sigma_grad=sigma is not None)
+        x, w, ig = _ig_inputs(ctx, module, x, w)
+        loss, elbo_iter, flat, sg = module._train_chunked(x, eps, state, keep_state, w, sigma_grad=sigma is not None, input_grad=ig)
         _sigma_keep(ctx, sigma, sg)                         # (S: every chunk's share of the batch, added up by _train_chunked)
+        _ig_keep(ctx, module, ig)                           # (G: every chunk's scaled by its share, concatenated along the batch)
         ctx.module, ctx.flat, ctx.from_state = module, flat, state is not None
         ctx.mark_non_differentiable(elbo_iter)
         return loss, elbo_iter
@@ -306,7 +366,8 @@ class _ChunkedTrainStep(torch.autograd.Function):
             # (from a detached state the initial posterior is not part of the forward: None, like unused parameters elsewhere)
             views.append(None if ctx.from_state and n.startswith('posterior.') else flat[off:off + p.numel()].view_as(p))
             off += p.numel()
-        return (None, None, None, None, None, None, *views, *_sigma_tail(ctx, grad_loss, -1.0))
+        gx, gw = _ig_grads(ctx, grad_loss, -1.0)
+        return (None, gx, None, gw, None, None, *views, *_sigma_tail(ctx, grad_loss, -1.0))
 
 
 def _flat_views(module, flat, live):
@@ -377,16 +438,18 @@ class _ElboGrad(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.module, ctx.init = module, pm is None
         params, sigma = _split_sigma(module, params)
+        x, w, ig = _ig_inputs(ctx, module, x, w, 'weighted_elbo')
         ctx.n = len(params)
         want_p = any(p.requires_grad for p in params)
         want_post = pm is not None and (pm.requires_grad or plv.requires_grad)
         if x.shape[0] <= module.max_batch():
-            r = module._elbo_call(x, eps, pm, plv, save=True, weights=w, sigma_grad=sigma is not None)
+            r = module._elbo_call(x, eps, pm, plv, save=True, weights=w, sigma_grad=sigma is not None, input_grad=ig)
             elbo, sg = r if sigma is not None else (r, None)
             ctx.serial, ctx.pre, ctx.BK = module._call_serial, None, (x.shape[0], module.K)
         else:
-            elbo, ctx.pre, sg = module._elbo_chunked_grad(x, eps, pm, plv, want_post, want_p, w, sigma_grad=sigma is not None)
+            elbo, ctx.pre, sg = module._elbo_chunked_grad(x, eps, pm, plv, want_post, want_p, w, sigma_grad=sigma is not None, input_grad=ig)
         _sigma_keep(ctx, sigma, sg)
+        _ig_keep(ctx, module, ig)
         return elbo
 
     @staticmethod
@@ -403,7 +466,8 @@ class _ElboGrad(torch.autograd.Function):
             want_post = (not ctx.init) and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
             gpm, gplv, flat = m._elbo_backward(ctx.serial, ctx.BK, g, want_post, any(ctx.needs_input_grad[6:6 + ctx.n]))
             flat = m._own(flat)
-        return (None, None, None, None, gpm if ctx.needs_input_grad[4] else None, gplv if ctx.needs_input_grad[5] else None,
+        gx, gw = _ig_grads(ctx, g, 1.0)
+        return (None, gx, None, gw, gpm if ctx.needs_input_grad[4] else None, gplv if ctx.needs_input_grad[5] else None,
                 *_flat_views(m, flat, live), *_sigma_tail(ctx, g, 1.0))
 
 
@@ -449,6 +513,9 @@ class IODINE(nn.Module):
         self.mask = None
         self.elbo_terms = None          # (n_elbo_calls, 3) = {ELBO, KL, LL} of the last call
         self.trajectory = None          # reconstruct(x, trajectory=True): dict of per-iteration outputs, else None
+        self.likelihood_maps = False    # True: every call that evaluates an ELBO also leaves the two per-pixel maps below (iodine.py:210-216)
+        self.log_likelihood = None      # (B, 3, S, S)    logsumexp_k(log(mask + 1e-12) + K_log_likelihood) of the last ELBO evaluation
+        self.K_log_likelihood = None    # (B, K, 3, S, S) gaussian_log_likelihood(x[:, None], mean, sigma); both float32, detached, raw
 
         self._handle = None
         self._handle_device = None
@@ -459,6 +526,8 @@ class IODINE(nn.Module):
         self._frames = 0                # frames per call the handle expects (iodine_set_frames; 0 = one image)
         self._objective = None          # (sigma, beta, weights) the handle holds (iodine_set_objective); None: the constructor's
         self._modes = {}                # options stable_encoding / sigma_grad as the handle holds them (_ensure_objective)
+        self._ig = 0                    # option input_grad as the handle holds it (_ensure_input_grad)
+        self._last_ig = None            # (d / d x, d / d w) the last differentiable call accumulated, for its autograd node
         self._state = None              # _RefineState of the last encode / reconstruct: see refinement_state
         self._options: Dict[str, float] = {}
         self._seed = 0                  # Philox key of the library's normal generator (manual_seed)
@@ -513,6 +582,7 @@ class IODINE(nn.Module):
                     continue
                 _lib.check(L.iodine_set_option(h, k.encode(), v), h)
             self._modes = {k: bool(self._options.get(k)) for k in ('stable_encoding', 'sigma_grad')}
+            self._ig = int(self._options.get('input_grad', 0))
             names = []
             for i in range(L.iodine_num_params(h)):
                 nm, nd, dims = C.c_char_p(), C.c_int(), (C.c_longlong * 4)()
@@ -677,6 +747,37 @@ class IODINE(nn.Module):
         with torch.cuda.device(device):                     # (a new weight table is a small device allocation of the handle)
             _lib.check(_lib.lib().iodine_set_objective(h, sigma, beta, arr, len(w)), h, 'iodine_set_objective')
         self._objective = obj
+
+    def _ensure_input_grad(self, h, bits):
+        """Option input_grad (bit 1: image, bit 2: pixel weights) of the call that is starting, sent only when it differs;
+        ``set_option('input_grad', bits)`` keeps bits on for every call.  Before ``_ensure_workspace``: the two accumulators are part of
+        the workspace plan while a bit is set, so a change asks the library for the size again."""
+        want = int(bits) | int(self._options.get('input_grad', 0))
+        if want != self._ig:
+            _lib.check(_lib.lib().iodine_set_option(h, b'input_grad', float(want)), h, 'iodine_set_option')
+            self._ig, self._ws_key = want, None
+
+    def _fetch_input_grad(self, h, dev, x, w, bits):
+        """After a library call that ran with input_grad ``bits``: (G_x shaped like x, G_w shaped like w - ``_check_weights`` form), None
+        where the bit is off - fresh tensors (iodine_last_input_grad)."""
+        gx = torch.empty(x.shape, device=dev, dtype=torch.float32) if bits & 1 else None
+        if not bits & 2:
+            gw = None
+        elif w is not None:
+            gw = torch.empty(w.shape, device=dev, dtype=torch.float32)
+        else:
+            gw = torch.empty((x.shape[0], self.img_size, self.img_size), device=dev, dtype=torch.float32)
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_last_input_grad(h, self._stream(), _lib.ptr(gx), _lib.ptr(gw)), h,
+                                             'iodine_last_input_grad'))
+        return gx, gw
+
+    def _grad_inputs(self, x, weights, xc, wc):
+        """What the autograd node of a call takes as image and weights: the caller's own tensors where they require grad (grad mode on) -
+        the node converts them and returns their gradient -, else the checked, detached forms ``xc`` / ``wc``."""
+        on = torch.is_grad_enabled()
+        xi = x if on and x.requires_grad else xc
+        wi = weights if on and wc is not None and weights.requires_grad else wc
+        return xi, wi
 
     # ``model.sigma`` as a tensor that requires grad (a leaf, or e.g. ``log_sigma.exp()``): the value handed to the library is still a host
     # number - one ``.item()`` per call, and a sigma that changes every step runs eagerly in graph mode, like a beta schedule - and the
@@ -847,7 +948,9 @@ class IODINE(nn.Module):
                 self._modes[key] = bool(value)
         if key in ('conv_precision', 'conv_variant', 'gen_conv_precision'):
             self._param_versions = None          # the library keeps only the selected path's weight packs: re-send the parameters
-        if key == 'wgrad_accum':
+        if key == 'input_grad':
+            self._ig = int(value)
+        if key in ('wgrad_accum', 'input_grad'):
             self._ws_key = None                  # the workspace plan depends on it: ask the library again
 
     def profile_read(self, category: str, reset: bool = True):
@@ -891,6 +994,8 @@ class IODINE(nn.Module):
         B = float(sum(sizes))
         cat = lambda key: torch.cat([p[key] for p in parts], 0)
         self.z, self.mean, self.mask, self.mask_logits = cat('z'), cat('mean'), cat('mask'), cat('mask_logits')
+        maps = parts[0]['ll'] is not None
+        self.log_likelihood, self.K_log_likelihood = (cat('ll'), cat('kll')) if maps else (None, None)
         self.elbo_terms = sum(p['elbo_terms'] * (n / B) for p, n in zip(parts, sizes))
         logger.update(**parts[0]['logger0'])
         if self.elbo_terms.shape[0] > 0:
@@ -899,6 +1004,7 @@ class IODINE(nn.Module):
     def _chunk_state(self):
         keep = ('image', 'pred') + tuple(f'mask_{i}' for i in range(self.K)) + tuple(f'pred_{i}' for i in range(self.K))
         return dict(z=self.z, mean=self.mean, mask=self.mask, mask_logits=self.mask_logits, elbo_terms=self.elbo_terms,
+                    ll=self.log_likelihood, kll=self.K_log_likelihood,
                     logger0={k: logger[k] for k in keep if k in logger})
 
     def _fetch_last_elbo(self, h, x, terms, count=None, frame=-1):
@@ -914,6 +1020,12 @@ class IODINE(nn.Module):
             h, self._stream(), B, _lib.ptr(z), _lib.ptr(mean), _lib.ptr(mask), _lib.ptr(logits), _lib.ptr(pred)),
             h, 'iodine_last_elbo_outputs'))
         self.z, self.mean, self.mask, self.mask_logits = z, mean, mask, logits
+        self.log_likelihood = self.K_log_likelihood = None
+        if self.likelihood_maps:                            # (one more per-pixel launch; off: none)
+            ll, kll = torch.empty((B, 3, S, S), **f), torch.empty((B, K, 3, S, S), **f)
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_last_likelihood(h, self._stream(), B, _lib.ptr(ll), _lib.ptr(kll)),
+                                                 h, 'iodine_last_likelihood'))
+            self.log_likelihood, self.K_log_likelihood = ll, kll
         logger.update(image=x[0] if x.dim() == 4 else x[0, frame], pred=pred[0], kl=terms[1], likelihood=terms[2])
         logger.update(**{f'mask_{i}': mask[0, i, 0] for i in range(K)})
         logger.update(**{f'pred_{i}': mean[0, i] for i in range(K)})
@@ -1163,12 +1275,14 @@ class IODINE(nn.Module):
         shape = (x.shape[0], self.K, self.dim_latent) if x.dim() == 4 else None
         given = pm is not None and plv is not None and tuple(pm.shape) == shape and pm.device == x.device
         sg = self._sigma_input()
+        in_grad = x.requires_grad or (torch.is_tensor(weights) and weights.requires_grad)
         if differentiable is None:
-            differentiable = (given and (pm.requires_grad or plv.requires_grad)) or bool(sg)
+            differentiable = (given and (pm.requires_grad or plv.requires_grad)) or bool(sg) or in_grad
         if differentiable and torch.is_grad_enabled():
             xc = self._check_x(x)                           # (model.K / n_iters are checked by _elbo_call, before any device work)
             w = self._check_weights(weights, xc, 'weighted_elbo')
-            return _ElboGrad.apply(self, xc, eps, w, pm if given else None, plv if given else None, *self._ordered_params(), *sg)
+            xi, wi = self._grad_inputs(x, weights, xc, w)
+            return _ElboGrad.apply(self, xi, eps, wi, pm if given else None, plv if given else None, *self._ordered_params(), *sg)
         return self._elbo_nograd(x, eps, weights)
 
     @torch.no_grad()
@@ -1201,7 +1315,7 @@ class IODINE(nn.Module):
             pm = plv = None
         return self._elbo_call(x, eps, pm, plv, save=False, weights=weights)
 
-    def _elbo_call(self, x, eps, pm, plv, save, weights=None, sigma_grad=False):
+    def _elbo_call(self, x, eps, pm, plv, save, weights=None, sigma_grad=False, input_grad=0):
         """One iodine_elbo of at most ``max_batch`` images from the posterior (pm, plv) - None: the initial one; ``save``: kept for
         iodine_elbo_backward.  x as ``_check_x``, weights as ``_check_weights`` return them.  -> the ELBO; with ``sigma_grad`` (a saved call
         only) -> (ELBO, d LL / d sigma)."""
@@ -1209,6 +1323,8 @@ class IODINE(nn.Module):
         obj = self._read_objective(T)
         dev, B = x.device, x.shape[0]
         h = self._sync_params(dev)
+        input_grad = input_grad if save else 0
+        self._ensure_input_grad(h, input_grad)
         self._ensure_workspace(h, B, 2 if save else 0, dev, K, T)
         self._ensure_objective(h, obj, dev, save and sigma_grad)
         shape = (B, K, self.dim_latent)
@@ -1231,6 +1347,7 @@ class IODINE(nn.Module):
         terms = self._own(terms)
         self.elbo_terms = terms.view(1, 3)
         sg = self._fetch_sigma_grad(h, dev, 1) if save and sigma_grad else None
+        self._last_ig = self._fetch_input_grad(h, dev, x, weights, input_grad) if input_grad else None
         self._fetch_last_elbo(h, x, terms)
         elbo = terms[0].clone() if save else terms[0]
         return (elbo, sg) if sigma_grad else elbo
@@ -1254,20 +1371,22 @@ class IODINE(nn.Module):
         self._call_serial += 1                      # the saved pass is consumed (no retain_graph)
         return self._own(gpm), self._own(gplv), flat          # (flat: the caller takes its copy - graph mode - after its last chunk)
 
-    def _elbo_chunked_grad(self, x, eps, pm, plv, want_post, want_p, weights=None, sigma_grad=False):
+    def _elbo_chunked_grad(self, x, eps, pm, plv, want_post, want_p, weights=None, sigma_grad=False, input_grad=0):
         """Differentiable elbo of a batch above ``max_batch`` (see _ElboGrad): forward + backward of every chunk with its share of the
         batch mean.  Returns the ELBO, (d / d posterior.mean, d / d posterior.logvar, flat parameter gradients) for grad_output 1 and, with
         ``sigma_grad``, d LL / d sigma of the batch (else None)."""
         dev, B = x.device, x.shape[0]
-        parts, sizes, gpms, gplvs, flat, sig = [], [], [], [], None, None
+        parts, sizes, gpms, gplvs, flat, sig, igs = [], [], [], [], None, None, []
         pm0, plv0 = self.posterior.mean, self.posterior.logvar
         for s, e in self._chunks(B, self.max_batch()):
             r = self._elbo_call(x[s:e].contiguous(), None if eps is None else eps[s:e], None if pm is None else pm[s:e],
                                 None if plv is None else plv[s:e], save=True, weights=None if weights is None else weights[s:e].contiguous(),
-                                sigma_grad=sigma_grad)
+                                sigma_grad=sigma_grad, input_grad=input_grad)
             sc = r[1] if sigma_grad else None
             parts.append(self._chunk_state()); sizes.append(e - s)
             w = torch.full((), (e - s) / float(B), device=dev, dtype=torch.float32)
+            if input_grad:                                  # this chunk's share of the batch mean
+                igs.append(tuple(None if t is None else t * w for t in self._last_ig))
             if sc is not None:                              # this chunk's share of the batch mean
                 sig = sc * w if sig is None else sig + sc * w
             gpm, gplv, flat = self._elbo_backward(self._call_serial, (e - s, self.K), w, want_post, want_p, flat)
@@ -1276,6 +1395,7 @@ class IODINE(nn.Module):
             gpms.append(gpm); gplvs.append(gplv)
         self.posterior.mean, self.posterior.logvar = pm0, plv0
         self._merge_chunk_state(parts, sizes, x)
+        self._last_ig = tuple(None if igs[0][j] is None else torch.cat([g[j] for g in igs], 0) for j in range(2)) if input_grad else None
         pre = (torch.cat(gpms, 0) if want_post else None, torch.cat(gplvs, 0) if want_post else None,
                self._own(flat) if flat is not None else None)
         return self.elbo_terms[0, 0].clone(), pre, sig
@@ -1303,7 +1423,7 @@ class IODINE(nn.Module):
         """-sum_i w_i ELBO_i (w = ``model.iter_weights``, by default (i+1)/(T+1); ELBO_i = LL_i - ``model.beta`` KL_i at ``model.sigma``),
         differentiable wrt every parameter.  ``loss.backward()`` differentiates the forward as it
         ran, at the (K, T) it read - like the reference, whose autograd graph is fixed at forward time.  ``x``: images
-        (B, 3, S, S) or a clip (B, T+1, 3, S, S), ELBO_i then against frame i (no gradient flows to the frames).
+        (B, 3, S, S) or a clip (B, T+1, 3, S, S), ELBO_i then against frame i (frame i of a clip that requires grad gets the gradient of evaluation i).
 
         ``state``: a tuple (post_mean, post_logvar, h, c) as ``refinement_state()`` returns it (h / c also as the reference's (B * K,
         MLP_UNITS) of ``lstm_hidden``): evaluation 0 samples from the given lambda and the LSTM starts from (h, c) instead of the initial
@@ -1341,11 +1461,14 @@ class IODINE(nn.Module):
         refused there.
 
         ``weights``: per-pixel observation weights >= 0 of this call, (B, 1, S, S) / (B, S, S), with a clip also (B, T+1, 1, S, S) /
-        (B, T+1, S, S): the loss and every gradient are those of the weighted ELBO (module docstring).  No gradient flows to them."""
+        (B, T+1, S, S): the loss and every gradient are those of the weighted ELBO (module docstring).  A floating-point weight tensor that
+        requires grad receives d loss / d w, and an ``x`` that requires grad d loss / d x (module docstring); otherwise both are data."""
         K, T = self._run_shape()
         self._read_objective(T)                      # (refusals before any device work; _train_forward hands it to the handle)
+        x_given, w_given = x, weights
         x, _ = self._check_frames(x, T + 1, 'forward' if state is None else 'forward from a state')
         weights = self._check_weights(weights, x, 'forward')
+        xi, wi = self._grad_inputs(x_given, w_given, x, weights)   # (the nodes' inputs 1 and 3: the caller's tensors where they require grad)
         B = x.shape[0]
         state = self._check_train_state(state, B, K, x.device)
         index = self._check_attach_frames(attach_frames, T)
@@ -1364,11 +1487,11 @@ class IODINE(nn.Module):
                                        'batch per call')
             if state is not None:
                 state = tuple(t.detach() for t in state)
-            loss, elbo_iter = _ChunkedTrainStep.apply(self, x, eps, weights, state, bool(keep_state), *self._ordered_params(), *sg)
+            loss, elbo_iter = _ChunkedTrainStep.apply(self, xi, eps, wi, state, bool(keep_state), *self._ordered_params(), *sg)
             self.elbo_terms = elbo_iter
             return loss
         eps = self._eps(eps, B, x.device)
-        loss, elbo_iter = self._apply_train_step(x, eps, weights, attach, index, state, sg)
+        loss, elbo_iter = self._apply_train_step(xi, eps, wi, attach, index, state, sg)
         self.elbo_terms = elbo_iter
         with torch.no_grad():
             h, dev = self._handle, x.device
@@ -1411,7 +1534,7 @@ class IODINE(nn.Module):
                                              h, 'iodine_last_train_state'))
         return hh, cc
 
-    def _train_forward(self, x, eps, state=None, weights=None, frames=None, sigma_grad=False):
+    def _train_forward(self, x, eps, state=None, weights=None, frames=None, sigma_grad=False, input_grad=0):
         """-> (loss, ELBO terms); with ``frames`` (a tuple of evaluation indices, possibly empty) also the six (F, B, K, ...) tensors of
         those evaluations in the order of ``_FRAME_KEYS`` (iodine_train_forward_frames); with ``sigma_grad`` also, last, the device scalar
         sum_e w_e dLL_e/dsigma (the forward then runs with option sigma_grad)."""
@@ -1419,9 +1542,13 @@ class IODINE(nn.Module):
         K, T = self._run_shape()
         obj = self._read_objective(T)
         h = self._sync_params(dev)
+        self._ensure_input_grad(h, input_grad)
         self._ensure_workspace(h, B, 1, dev, K, T, x.shape[1] if x.dim() == 5 else 0)
         self._ensure_objective(h, obj, dev, sigma_grad)
-        sg = lambda: (self._fetch_sigma_grad(h, dev, T + 1, obj[2]),) if sigma_grad else ()
+
+        def sg():                                           # (what is read back once after the call, in stream order)
+            self._last_ig = self._fetch_input_grad(h, dev, x, weights, input_grad) if input_grad else None
+            return (self._fetch_sigma_grad(h, dev, T + 1, obj[2]),) if sigma_grad else ()
         loss = self._out('t.loss', (), dev)
         elbo_iter = self._out('t.elbo', (T + 1, 3), dev)
         xs, eps = self._stage('x', x), self._stage('eps', eps)
@@ -1451,21 +1578,24 @@ class IODINE(nn.Module):
                 h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), ptrs, _lib.ptr(loss), _lib.ptr(elbo_iter)), h, 'iodine_train_forward_seq'))
         return (self._own(loss), self._own(elbo_iter), *sg())
 
-    def _train_chunked(self, x, eps, state=None, keep_state=False, weights=None, sigma_grad=False):
+    def _train_chunked(self, x, eps, state=None, keep_state=False, weights=None, sigma_grad=False, input_grad=0):
         """Forward + backward of every chunk (see _ChunkedTrainStep): returns the batch loss, the (T+1, 3) ELBO terms of the whole
         batch, d loss / d parameters as one flat buffer in named_parameters() order and, with ``sigma_grad``, sum_e w_e dLL_e/dsigma of
         the batch (else None).  ``state``: a detached initial state, cut along the batch; ``keep_state``: every chunk's LSTM state is
         copied out for ``refinement_state``."""
         dev, B = x.device, x.shape[0]
         flat = self._out('t.flat', (sum(p.numel() for p in self._ordered_params()),), dev)
-        loss, terms, parts, sizes, pms, plvs, hcs, sig = None, None, [], [], [], [], [], None
+        loss, terms, parts, sizes, pms, plvs, hcs, sig, igs = None, None, [], [], [], [], [], None, []
         for c, (s, e) in enumerate(self._chunks(B, self.max_batch(training=True))):
             xc = x[s:e].contiguous()
             ec = self._eps(None if eps is None else eps[:, s:e], e - s, dev)
             lc, tc, *sc = self._train_forward(xc, ec, None if state is None else tuple(t[s:e].contiguous() for t in state),
-                                              None if weights is None else weights[s:e].contiguous(), sigma_grad=sigma_grad)
+                                              None if weights is None else weights[s:e].contiguous(), sigma_grad=sigma_grad,
+                                              input_grad=input_grad)
             h = self._handle
             w = torch.full((), (e - s) / float(B), device=dev, dtype=torch.float32)
+            if input_grad:                              # this chunk's share of the batch mean
+                igs.append(tuple(None if t is None else t * w for t in self._last_ig))
             ws = self._stage('t.gl', w)
             if sc:                                      # this chunk's share of the batch mean
                 sig = sc[0] * w if sig is None else sig + sc[0] * w
@@ -1491,6 +1621,7 @@ class IODINE(nn.Module):
             if keep_state:
                 self._state = _RefineState(self.posterior.mean, self.posterior.logvar, torch.cat([hc[0] for hc in hcs], 0),
                                            torch.cat([hc[1] for hc in hcs], 0))
+        self._last_ig = tuple(None if igs[0][j] is None else torch.cat([g[j] for g in igs], 0) for j in range(2)) if input_grad else None
         return loss, self.elbo_terms, self._own(flat), sig
 
     def _train_backward(self, grad_loss, serial, aux=None):
