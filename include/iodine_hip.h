@@ -64,7 +64,7 @@ typedef struct iodine_config {
     unsigned encoding;     /* ARCH.ENCODING as IODINE_ENC_* bits (see above for what is accepted) */
     int ref_conv_chan;     /* ARCH.REF.CONV_CHAN   (32 or 64: tuned kernels; other divisors of 256: generic fallback path) */
     int ref_conv_layers;   /* ARCH.REF.CONV_LAYERS */
-    int ref_mlp_units;     /* ARCH.REF.MLP_UNITS   (1..1024; not a multiple of 4: zero-padded inside, iodine_debug_copy then shows the padded widths) */
+    int ref_mlp_units;     /* ARCH.REF.MLP_UNITS   (1..1024, above about 356 only widths that are a multiple of 8 once rounded up to a multiple of 4: iodine_create names the bound; not a multiple of 4: zero-padded inside, iodine_debug_copy then shows the padded widths) */
     int ref_kernel_size;   /* ARCH.REF.KERNEL_SIZE (3: tuned kernels; 5, 7: generic fallback path, kernels_generic.hip) */
     int ref_stride;        /* ARCH.REF.STRIDE      (2: tuned kernels; 1, 3 .. 8: the refinement stack on the generic path) */
     int dec_conv_chan;     /* ARCH.DEC.CONV_CHAN   (32 or 64: tuned kernels; other multiples of 4 in 8..256: generic path) */
@@ -512,7 +512,8 @@ int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, i
  * layer in ONE kernel (kernels_refl0.hip) -- in inference the encoding is never written, so iodine_debug_copy("enc") then
  * needs "stop_after_iters" >= 0 or this option 0; 0 = pixel_pass2 writes the encoding, two convs read it),
  * "head_mfma" (1 -- default: the LSTM gate pre-activations of the refinement head as one fp32-MFMA GEMM over all slots,
- * three launches; 0 = the one-launch head kernel),
+ * three launches; 0 = the one-launch head kernel; the option chooses only where both forms can run -- 4 * MLP_UNITS not a multiple of 32
+ * runs in one launch, MLP_UNITS above about 356 in three, whatever it says),
  * "dec_out_rows" (1 -- default: the output conv's forward runs as a row-streaming kernel -- a block walks a strip of image
  * rows, every row of the [pixels x 36] product is computed once and kept in an LDS ring until the rows above and below are
  * there -- for image sizes 32 / 64 / 128 on the split path; 0 = 16 x 16 tiles, each recomputing its 18 x 18 halo),
@@ -633,6 +634,42 @@ int iodine_op_render_bwd_logits(void* stream, const float* dec_out, const float*
  * synchronises and frees per call -- not for timing.  IODINE_ERR_INVALID, without a launch, for a bad argument. */
 int iodine_op_pixel_maps(void* stream, const float* x_nchw, const float* w_or_null, const float* dec_out_nhwc4, int batch, int slots,
                          int pixels, float sigma, int strict, float coef, float* ll, float* kll, float* gx, float* gw, int first);
+
+/* ---- the refinement head, kernel-level tests only: each call allocates and frees its scratch around the launches and synchronises -- not
+ * for timing.  IODINE_ERR_INVALID, without a launch, for arguments or shapes the requested form does not take (never another form). */
+
+/* C = alpha op(A) op(B) + beta C, row-major.  form 0: the library's dispatch (launch_sgemm), op(A) [M][K] = A or A^T (ta), op(B) [K][N] = B
+ * or B^T (tb).  forms 1 - 3: the fp32-MFMA kernel for A^T B with B [K][N] and M, N multiples of 32 -- 1: A [K][M]; 2: A row-major [M][K];
+ * 3: A [K][M] and C written through the broadcast layer's weight map, row = latent channel, column = tap * mode_c + co ->
+ * C[(co * ldc + row) * 9 + tap] with N = 9 mode_c and ldc = L + 2.  beta = 0: C is not read. */
+int iodine_op_sgemm(void* stream, int form, int ta, int tb, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
+                    float beta, float* C, int ldc, int mode_c);
+
+/* dst[c] += alpha * sum_r src[r * ld + c].  form 0: one block per column; form 1: the streaming form for tall contiguous matrices, only
+ * where the library takes it (ld == cols, rows >= 8192, cols % 4 == 0, cols <= 256, 256 % (cols / 4) == 0). */
+int iodine_op_colsum(void* stream, int form, const float* src, int rows, int cols, int ld, float alpha, float* dst);
+
+/* one step of the refinement head (iodine.py:481-503, 642-643) from reference-shaped parameters.  in[14]: mlp.weight [H][C], mlp.bias [H],
+ * lstm.weight_ih [4H][H + 4L], weight_hh [4H][H], bias_ih, bias_hh [4H], mean_update.weight [L][H], .bias [L], logvar_update.weight, .bias,
+ * feat [N][PL][C], latent [N][4L], h_prev, c_prev [N][H].  out[10]: h, c [N][H], pm, plv [N][L] (IN / OUT: the update is added),
+ * d_mean, d_logvar [N][L], pooled [N][C], s [N][H] (MLP pre-activation), gates [N][4H] (post-activation i, f, g, o), xin [N][H + 4L]; the last
+ * six may be NULL.  H, L multiples of 4, C divides 256.  form 0: single launch; form 1: three launches (pre, gate GEMM, post). */
+int iodine_op_refine_head(void* stream, int form, const float* const* in, float* const* out, int N, int PL, int C, int H, int L);
+
+/* which form the library runs at these (padded) widths: 0 single launch, 1 three launches, -1 refused at create time.  Host arithmetic. */
+int iodine_op_refine_head_form(int C, int H, int L, int prefer_split);
+
+/* back-propagation through time of the head over T saved steps.  form 0: the fused kernel (Cr <= H; L, H, Cr multiples of 4); form 1: the
+ * launch sequence.  in[16]: g_pm, g_plv [T + 1][N][L], gates [T][N][4H], c [T + 1][N][H], s [T][N][H], mean_update.weight,
+ * logvar_update.weight [L][H], weight_hh [4H][H], weight_ih [4H][H + 4L], mlp.weight [H][Cr], then optional (NULL): seed_m, seed_v ([N][L] joining
+ * step T - 1, or [T][N][L] with seed_stride = N L floats), gl (device scalar; NULL = 0), wtab (device, T + 1 loss weights), dh_in, dc_in [N][H].
+ * out[7]: ddm, ddv [T][N][L], dgates [T][N][4H], ds [T][N][H], dpooled [T][N][Cr], optional dh_out, dc_out [N][H].  gl, the carries and
+ * seed_stride need seed_m / seed_v.  B: the batch size in the loss weight -(i + 2) / (T + 1) / B. */
+int iodine_op_head_bptt(void* stream, int form, const float* const* in, float* const* out, int T, int N, int B, int L, int H, int Cr,
+                        long long seed_stride);
+
+/* dpre [N][PL][C] = dpooled [N][C] / PL * ELU'(act), act = ELU output of the last refinement conv layer */
+int iodine_op_pool_bwd(void* stream, const float* dpooled, const float* act, float* dpre, int N, int PL, int C);
 
 #ifdef __cplusplus
 }

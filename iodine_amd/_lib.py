@@ -35,6 +35,7 @@ EXPORTS = (
     'iodine_train_forward_frames', 'iodine_train_backward_frames',
     'iodine_last_sigma_grad',
     'iodine_last_input_grad', 'iodine_last_likelihood', 'iodine_op_pixel_maps',
+    'iodine_op_sgemm', 'iodine_op_colsum', 'iodine_op_refine_head', 'iodine_op_refine_head_form', 'iodine_op_head_bptt', 'iodine_op_pool_bwd',
 )
 
 
@@ -150,6 +151,13 @@ def lib() -> C.CDLL:
         L.iodine_last_input_grad.argtypes = [vp, vp, vp, vp]
         L.iodine_last_likelihood.argtypes = [vp, vp, ci, vp, vp]
         L.iodine_op_pixel_maps.argtypes = [vp, vp, vp, vp, ci, ci, ci, cf, ci, cf, vp, vp, vp, vp, ci]
+    if hasattr(L, 'iodine_op_refine_head'):             # (kernel-level tests of the refinement head; absent from older A/B builds)
+        L.iodine_op_sgemm.argtypes = [vp] + [ci] * 6 + [cf, vp, ci, vp, ci, cf, vp, ci, ci]
+        L.iodine_op_colsum.argtypes = [vp, ci, vp, ci, ci, ci, cf, vp]
+        L.iodine_op_refine_head.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(vp)] + [ci] * 5
+        L.iodine_op_refine_head_form.argtypes = [ci] * 4
+        L.iodine_op_head_bptt.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(vp)] + [ci] * 6 + [C.c_longlong]
+        L.iodine_op_pool_bwd.argtypes = [vp, vp, vp, vp, ci, ci, ci]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

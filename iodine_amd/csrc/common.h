@@ -251,7 +251,11 @@ hipError_t launch_refine_head(hipStream_t st, const float* feat, int N, int PL, 
                               const float* lstm_b, const float* wmT, const float* bm, const float* wvT, const float* bv,
                               const float* latent, const float* h_prev, const float* c_prev, float* h_out, float* c_out,
                               float* pm, float* plv, float* sv_pooled, float* sv_s, float* sv_gates, float* sv_xin,
-                              float* d_mean, float* d_logvar, float* xh = nullptr, float* gp = nullptr);
+                              float* d_mean, float* d_logvar, float* xh = nullptr, float* gp = nullptr, int prefer_split = 1);
+// which form launch_refine_head runs for these widths (multiples of 4) when it is given the xh / gp scratch: 0 = single launch, 1 = three
+// launches (pre, gate GEMM, post), -1 = neither fits.  prefer_split picks between the two only where both can run.  Host arithmetic only.
+int refine_head_form(int C, int H, int L, int prefer_split);
+size_t refine_head_lds_bytes(int C, int H, int L, int split);
 hipError_t launch_pack_dec_out(hipStream_t st, const float* w, float* wk, int C);
 hipError_t launch_conv3x3_gather_dgrad(hipStream_t st, const float* d, const float* wpk, const float* aux, float* out,
                                        int N, int big_h, int big_w, int c, int stride);
@@ -300,6 +304,13 @@ hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_pl
                             const float* dh_in = nullptr, const float* dc_in = nullptr,    // [N][H] cotangents on (h_T, c_T): initial carries
                             float* dh_out = nullptr, float* dc_out = nullptr,              // [N][H] d / d (h_0, c_0): the carries left (seeded instance only)
                             size_t seed_stride = 0);  // != 0: seed_m / seed_v are [T][N][L] (stride in floats), slice i joins step i; 0: step T - 1 alone
+// the same recurrence as a launch sequence; whost: HOST table of T + 1 loss weights or NULL; scratch dc1, dxin, carry_h[2], carry_c[2]: [N][H] each
+hipError_t launch_head_bptt_unfused(hipStream_t st, const float* g_pm, const float* g_plv, const float* gates, const float* cst, const float* u,
+                                    const float* Wm, const float* Wv, const float* Whh, const float* Wih, const float* Wmlp, float* ddm,
+                                    float* ddv, float* dgates, float* ds, float* dpooled, int T, int N, int B, int L, int H, int Cr,
+                                    int seeded, const float* seed_m, const float* seed_v, const float* gl_dev, const float* whost,
+                                    const float* dh_in, const float* dc_in, float* dh_out, float* dc_out, size_t seed_stride,
+                                    float* dc1, float* dxin, float* const carry_h[2], float* const carry_c[2]);
 // split-precision (3 x fp16 MFMA) variant of the stride-1 tile conv
 hipError_t launch_pack_conv_weights_f16(hipStream_t st, const float* src, int O, int I, int cin, int cout, int tflip,
                                         float* meta, void* dst);

@@ -242,7 +242,7 @@ void build_param_table(iodine_handle* h)
 
 std::string validate(const iodine_config& c)
 {
-    char m[256];
+    char m[384];
     if (c.encoding & ~IODINE_ENC_FULL) return "ARCH.ENCODING has unknown entries";
     if ((c.encoding & (IODINE_ENC_POSTERIOR | IODINE_ENC_GRAD_POST)) != (IODINE_ENC_POSTERIOR | IODINE_ENC_GRAD_POST))
         return "ARCH.ENCODING must contain 'posterior' and 'grad_post' (the LSTM input of the refinement head is built for both; every "
@@ -267,6 +267,17 @@ std::string validate(const iodine_config& c)
     // PadShim - round 6)
     if (c.dim_latent < 2 || c.dim_latent > 256) return "ARCH.DIM_LATENT must be in 2..256";
     if (c.ref_mlp_units < 1 || c.ref_mlp_units > 1024) return "REF.MLP_UNITS must be in 1..1024";
+    {
+        // the head's LDS budget, on the widths it runs at (rounded up to multiples of 4): its single-launch form keeps 16 slices of the 4H gate
+        // partial sums on chip; beyond that only the three-launch form (gate GEMM on fp32 MFMA: 4H a multiple of 32) can run
+        const int Hp = (c.ref_mlp_units + 3) / 4 * 4, Lp = (c.dim_latent + 3) / 4 * 4;
+        if (refine_head_form(c.ref_conv_chan, Hp, Lp, 1) < 0) {
+            snprintf(m, sizeof m, "REF.MLP_UNITS = %d (run at %d) must be a multiple of 8 after rounding up to a multiple of 4, or small enough for the "
+                     "refinement head's single-launch form: it needs %zu bytes of LDS, the limit is 98304 (MLP_UNITS up to about 356)",
+                     c.ref_mlp_units, Hp, refine_head_lds_bytes(c.ref_conv_chan, Hp, Lp, 0));
+            return m;
+        }
+    }
     if (!(c.sigma > 0)) { snprintf(m, sizeof m, "ARCH.SIGMA must be > 0 (got %g)", c.sigma); return m; }
     return "";
 }
@@ -738,7 +749,7 @@ int refine_step(iodine_handle* h, hipStream_t st, int B, int i, bool save)
                                  h->wmT, h->bm, h->wvT, h->bv, b.latent[i], b.h[i], b.c[i], b.h[i + 1], b.c[i + 1], b.pm,
                                  b.plv, save ? b.pooled[i] : nullptr, save ? b.u[i] : nullptr,
                                  save ? b.gates[i] : nullptr, save ? b.xin[i] : nullptr, nullptr, nullptr,
-                                 h->head_mfma ? b.head_xh : nullptr, h->head_mfma ? b.head_gp : nullptr));
+                                 b.head_xh, b.head_gp, h->head_mfma));                // (the form: refine_head_form; head_mfma where both fit)
     return IODINE_OK;
 }
 
@@ -2104,37 +2115,12 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
                                                  seed_m, seed_v, aux ? aux->gl : nullptr, obj.wtab, cot_h, cot_c, gs_h, gs_c,
                                                  seed_stride));
     } else {
-    int cf = 0;                                            // carry buffer flip
-    for (int i = T - 1; i >= 0; --i) {
-        // d loss / d delta_i = -w_{i+1}/B * d(B*ELBO_{i+1})/d lambda_{i+1}   (lambda_{i+1} = detach(lambda_i) + delta_i)
-        const float alpha = obj.whost ? -obj.whost[i + 1] / (float)B : -((float)(i + 2) / (float)(T + 1)) / (float)B;
-        float *ddm = b.ddm + (size_t)i * N * L, *ddv = b.ddv + (size_t)i * N * L;
-        float *dgates = b.dgates + (size_t)i * N * 4 * H, *ds = b.ds + (size_t)i * N * H;
-        HIPCHK(h, launch_scale(st, b.g_pm[i + 1], alpha, ddm, N * L));
-        HIPCHK(h, launch_scale(st, b.g_plv[i + 1], alpha, ddv, N * L));
-        if (aux) {                                         // ELBO seeds x d(out) / d(loss); lambda_T's cotangents join delta_{T-1} unscaled
-            // (cotangents on chosen evaluations: those of lambda_{i+1} join delta_i, every i)
-            const float *sm = seed_stride ? seed_m + (size_t)i * seed_stride : i == T - 1 ? seed_m : nullptr;
-            const float *sv = seed_stride ? seed_v + (size_t)i * seed_stride : i == T - 1 ? seed_v : nullptr;
-            HIPCHK(h, launch_scale_dev_add(st, ddm, aux->gl, sm, N * L));
-            HIPCHK(h, launch_scale_dev_add(st, ddv, aux->gl, sv, N * L));
-        }
-        const float* c1 = b.c[i + 1];
-        // read-out layers act on the cell state (iodine.py:488-492)
-        HIPCHK(h, launch_sgemm(st, 0, 0, N, H, L, 1.f, ddm, L, h->raw_wm, H, 0.f, b.dc1, H));
-        HIPCHK(h, launch_sgemm(st, 0, 0, N, H, L, 1.f, ddv, L, h->raw_wv, H, 1.f, b.dc1, H));
-        const bool last = (i == T - 1);
-        HIPCHK(h, launch_lstm_bwd_pointwise(st, b.gates[i], b.c[i], c1, b.dc1, last ? cot_h : b.carry_h[cf],
-                                            last ? cot_c : b.carry_c[cf], dgates, b.carry_c[cf ^ 1], N, H));
-        HIPCHK(h, launch_sgemm(st, 0, 0, N, H, 4 * H, 1.f, dgates, 4 * H, h->raw_whh, H, 0.f, b.carry_h[cf ^ 1], H));
-        cf ^= 1;
-        // MLP (double ELU) and average pool
-        HIPCHK(h, launch_sgemm(st, 0, 0, N, H, 4 * H, 1.f, dgates, 4 * H, h->raw_wih, IN, 0.f, b.dxin, H));
-        HIPCHK(h, launch_mlp_bwd_pointwise(st, b.dxin, H, b.u[i], ds, N, H));
-        HIPCHK(h, launch_sgemm(st, 0, 0, N, Cr, H, 1.f, ds, H, h->raw_mlp_w, Cr, 0.f, b.dpooled + (size_t)i * N * Cr, Cr));
-    }
-    if (gs_h) HIPCHK(h, hipMemcpyAsync(gs_h, b.carry_h[cf], sizeof(float) * (size_t)N * H, hipMemcpyDeviceToDevice, st));
-    if (gs_c) HIPCHK(h, hipMemcpyAsync(gs_c, b.carry_c[cf], sizeof(float) * (size_t)N * H, hipMemcpyDeviceToDevice, st));
+        // the same recurrence as a launch sequence (9 launches per iteration)
+        float* const ch[2] = {b.carry_h[0], b.carry_h[1]};
+        float* const cc[2] = {b.carry_c[0], b.carry_c[1]};
+        HIPCHK(h, launch_head_bptt_unfused(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->raw_wm, h->raw_wv, h->raw_whh, h->raw_wih,
+                                           h->raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr, aux != nullptr, seed_m, seed_v,
+                                           aux ? aux->gl : nullptr, obj.whost, cot_h, cot_c, gs_h, gs_c, seed_stride, b.dc1, b.dxin, ch, cc));
     }
     if (aux && aux->g_state) {
         // d loss / d lambda_0 of the state: d(out) / d(loss) x (-w_0 / B) x d(B ELBO_0) / d lambda_0 - the term the forward hands to init_mean /

@@ -437,4 +437,164 @@ int iodine_op_conv3x3_wgrad_f32(void* stream, const float* in, const float* d, f
     return IODINE_OK;
 }
 
+// ---- the refinement head and its backward, kernel-level (tests/test_gpu_head.py, tests/test_gpu_sgemm.py) --------------------------------
+// (kernel-level tests only: these allocate and free their scratch around the launches and synchronise - not entry points to time)
+static int op_fail(const char* who, hipError_t e)
+{
+    g_create_error = std::string(who) + ": " + hipGetErrorString(e);
+    return IODINE_ERR_HIP;
+}
+
+int iodine_op_sgemm(void* stream, int form, int ta, int tb, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
+                    float beta, float* Cm, int ldc, int mode_c)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (form < 0 || form > 3 || M < 1 || N < 1 || K < 1 || !A || !B || !Cm || lda < 1 || ldb < 1 || ldc < 1) {
+        g_create_error = "iodine_op_sgemm: argument";
+        return IODINE_ERR_INVALID;
+    }
+    hipError_t e;
+    if (form == 0) {
+        if (lda < (ta ? M : K) || ldb < (tb ? K : N) || ldc < N) { g_create_error = "iodine_op_sgemm: leading dimension"; return IODINE_ERR_INVALID; }
+        e = launch_sgemm(st, ta, tb, M, N, K, alpha, A, lda, B, ldb, beta, Cm, ldc);
+    } else {
+        // A [K][M] (form 2: [M][K] row-major), B [K][N]; form 3 writes through the broadcast layer's map: N = 9 mode_c, ldc = L + 2 >= M
+        const bool bad = !sgemm_tn_mfma_ok(M, N, K) || lda < (form == 2 ? K : M) || ldb < N ||
+                         (form == 3 ? (mode_c < 1 || N != 9 * mode_c || ldc < M) : ldc < N);
+        if (bad) { g_create_error = "iodine_op_sgemm: shape not covered by the MFMA form (M, N multiples of 32; form 3: N = 9 mode_c, ldc >= M)"; return IODINE_ERR_INVALID; }
+        e = launch_sgemm_tn_mfma(st, M, N, K, alpha, A, lda, B, ldb, beta, Cm, ldc, form == 3 ? 1 : 0, form == 3 ? mode_c : 0, form == 2 ? 1 : 0);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return op_fail("iodine_op_sgemm", e);
+    return IODINE_OK;
+}
+
+int iodine_op_colsum(void* stream, int form, const float* src, int rows, int cols, int ld, float alpha, float* dst)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (form < 0 || form > 1 || !src || !dst || rows < 1 || cols < 1 || ld < cols) { g_create_error = "iodine_op_colsum: argument"; return IODINE_ERR_INVALID; }
+    hipError_t e;
+    if (form == 0) {
+        e = launch_colsum(st, src, rows, cols, ld, alpha, dst);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    } else {
+        // the streaming form, only where launch_colsum_tall itself takes it (elsewhere it forwards to launch_colsum = form 0)
+        if (ld != cols || cols % 4 != 0 || cols > 256 || 256 % (cols / 4) != 0 || rows < 8192) {
+            g_create_error = "iodine_op_colsum: the tall form takes contiguous rows >= 8192, cols a multiple of 4 with 256 % (cols / 4) == 0";
+            return IODINE_ERR_INVALID;
+        }
+        const size_t tmp_elems = (size_t)512 * 64;                       // (the library's partial-bias scratch)
+        float* tmp = nullptr;
+        if (hipMalloc((void**)&tmp, tmp_elems * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+        e = launch_colsum_tall(st, src, rows, cols, alpha, dst, tmp, tmp_elems);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        (void)hipFree(tmp);
+    }
+    if (e != hipSuccess) return op_fail("iodine_op_colsum", e);
+    return IODINE_OK;
+}
+
+int iodine_op_refine_head(void* stream, int form, const float* const* in, float* const* out, int N, int PL, int C, int H, int L)
+{
+    hipStream_t st = (hipStream_t)stream;
+    bool ok = in && out && (form == 0 || form == 1) && N >= 1 && PL >= 1 && C >= 4 && C <= 256 && 256 % C == 0 && H >= 4 && H <= 1024 && H % 4 == 0 &&
+              L >= 4 && L <= 256 && L % 4 == 0;
+    for (int j = 0; ok && j < 14; ++j) ok = in[j] != nullptr;
+    for (int j = 0; ok && j < 4; ++j) ok = out[j] != nullptr;              // (h, c, pm, plv; the rest optional)
+    if (!ok) { g_create_error = "iodine_op_refine_head: argument"; return IODINE_ERR_INVALID; }
+    if (form == 0 ? refine_head_lds_bytes(C, H, L, 0) > 96 * 1024 : refine_head_form(C, H, L, 1) != 1) {
+        g_create_error = form == 0 ? "iodine_op_refine_head: the single-launch form does not fit the LDS at these widths"
+                                   : "iodine_op_refine_head: the three-launch form needs 4 * MLP_UNITS to be a multiple of 32";
+        return IODINE_ERR_INVALID;
+    }
+    const float *mlp_w = in[0], *mlp_b = in[1], *wih = in[2], *whh = in[3], *bih = in[4], *bhh = in[5], *wm = in[6], *bm = in[7], *wv = in[8],
+                *bv = in[9], *feat = in[10], *latent = in[11], *h_prev = in[12], *c_prev = in[13];
+    const size_t IN = (size_t)H + 4 * L, Kg = IN + H, Np = ((size_t)N + 31) / 32 * 32;
+    const size_t n_mlp = (size_t)C * H, n_w = Kg * 4 * H, n_b = (size_t)4 * H, n_u = (size_t)H * L, n_xh = form == 1 ? Np * Kg : 0,
+                 n_gp = form == 1 ? Np * 4 * H : 0;
+    float* buf = nullptr;
+    if (hipMalloc((void**)&buf, (n_mlp + n_w + n_b + 2 * n_u + n_xh + n_gp) * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+    float *mlp_wT = buf, *wihT = mlp_wT + n_mlp, *whhT = wihT + IN * 4 * H, *lstm_b = wihT + n_w, *wmT = lstm_b + n_b, *wvT = wmT + n_u,
+          *xh = wvT + n_u, *gp = xh + n_xh;
+    // the operands as iodine_set_params builds them: transposes to [in][out], [W_ih^T ; W_hh^T] back to back, b_ih + b_hh
+    MultiCopy mc;
+    mc.count = 0;
+    auto queue = [&](float* dst, const float* src, const float* src2, size_t n, int op, int cols) {
+        mc.src[mc.count] = src; mc.src2[mc.count] = src2; mc.dst[mc.count] = dst; mc.n[mc.count] = (int)n; mc.op[mc.count] = op;
+        mc.cols[mc.count] = cols; ++mc.count;
+    };
+    queue(mlp_wT, mlp_w, nullptr, n_mlp, 1, C);
+    queue(wihT, wih, nullptr, IN * 4 * H, 1, (int)IN);
+    queue(whhT, whh, nullptr, (size_t)H * 4 * H, 1, H);
+    queue(lstm_b, bih, bhh, n_b, 2, 0);
+    queue(wmT, wm, nullptr, n_u, 1, H);
+    queue(wvT, wv, nullptr, n_u, 1, H);
+    hipError_t e = launch_multi_copy(st, mc);
+    if (e == hipSuccess && form == 1) e = launch_zero_fill(st, xh, n_xh + n_gp);      // (rows N .. Np of the gate GEMM: the workspace's are finite too)
+    if (e == hipSuccess)
+        e = launch_refine_head(st, feat, N, PL, C, H, L, mlp_wT, mlp_b, wihT, whhT, lstm_b, wmT, bm, wvT, bv, latent, h_prev, c_prev, out[0], out[1],
+                               out[2], out[3], out[6], out[7], out[8], out[9], out[4], out[5], form == 1 ? xh : nullptr, form == 1 ? gp : nullptr, 1);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return op_fail("iodine_op_refine_head", e);
+    return IODINE_OK;
+}
+
+int iodine_op_head_bptt(void* stream, int form, const float* const* in, float* const* out, int T, int N, int B, int L, int H, int Cr,
+                        long long seed_stride)
+{
+    hipStream_t st = (hipStream_t)stream;
+    bool ok = in && out && (form == 0 || form == 1) && T >= 1 && N >= 1 && B >= 1 && L >= 1 && H >= 1 && Cr >= 1 && seed_stride >= 0;
+    for (int j = 0; ok && j < 10; ++j) ok = in[j] != nullptr;
+    for (int j = 0; ok && j < 5; ++j) ok = out[j] != nullptr;
+    if (!ok) { g_create_error = "iodine_op_head_bptt: argument"; return IODINE_ERR_INVALID; }
+    const float *seed_m = in[10], *seed_v = in[11], *gl = in[12], *wtab = in[13], *dh_in = in[14], *dc_in = in[15];
+    if ((seed_m == nullptr) != (seed_v == nullptr) || (!seed_m && (gl || dh_in || dc_in || out[5] || out[6] || seed_stride))) {
+        g_create_error = "iodine_op_head_bptt: gl, the carries and seed_stride belong to the seeded form (seed_m and seed_v given)";
+        return IODINE_ERR_INVALID;
+    }
+    hipError_t e;
+    if (form == 0) {
+        if (!head_bptt_fits(L, H, Cr)) {
+            g_create_error = "iodine_op_head_bptt: the fused kernel takes Cr <= H, and L, H, Cr multiples of 4";
+            return IODINE_ERR_INVALID;
+        }
+        e = launch_head_bptt(st, in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8], in[9], out[0], out[1], out[2], out[3], out[4],
+                             T, N, B, L, H, Cr, seed_m, seed_v, gl, wtab, dh_in, dc_in, out[5], out[6], (size_t)seed_stride);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    } else {
+        std::vector<float> whost;
+        if (wtab) {                                                      // the launch sequence takes the loss weights from the host
+            whost.resize((size_t)T + 1);
+            e = hipMemcpyAsync(whost.data(), wtab, sizeof(float) * ((size_t)T + 1), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return op_fail("iodine_op_head_bptt", e);
+        }
+        const size_t NH = (size_t)N * H;
+        float* buf = nullptr;
+        if (hipMalloc((void**)&buf, 6 * NH * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
+        float* const ch[2] = {buf + 2 * NH, buf + 3 * NH};
+        float* const cc[2] = {buf + 4 * NH, buf + 5 * NH};
+        e = launch_head_bptt_unfused(st, in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8], in[9], out[0], out[1], out[2], out[3], out[4],
+                                     T, N, B, L, H, Cr, seed_m != nullptr, seed_m, seed_v, gl, wtab ? whost.data() : nullptr, dh_in, dc_in, out[5],
+                                     out[6], (size_t)seed_stride, buf, buf + NH, ch, cc);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        (void)hipFree(buf);
+    }
+    if (e != hipSuccess) return op_fail("iodine_op_head_bptt", e);
+    return IODINE_OK;
+}
+
+int iodine_op_pool_bwd(void* stream, const float* dpooled, const float* act, float* dpre, int N, int PL, int C)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!dpooled || !act || !dpre || N < 1 || PL < 1 || C < 1) { g_create_error = "iodine_op_pool_bwd: argument"; return IODINE_ERR_INVALID; }
+    hipError_t e = launch_pool_bwd(st, dpooled, act, dpre, N, PL, C);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return op_fail("iodine_op_pool_bwd", e);
+    return IODINE_OK;
+}
+
+int iodine_op_refine_head_form(int C, int H, int L, int prefer_split) { return refine_head_form(C, H, L, prefer_split); }
+
 }  // extern "C"

@@ -690,7 +690,7 @@ void refine_head_kernel(const float* __restrict__ feat /*[N][PL][C]*/, int PL, i
     float* s_h = s_x + H + 4 * L;       // H   (h_prev)
     float* s_c = s_h + H;               // H   (c1)
     float* s_red = s_c + H;             // 256
-    float* s_part = s_red + 256;        // [16][4H]: LSTM partial gate sums of the K slices
+    float* s_part = s_red + 256;        // partial sums of the K slices: MLP, LSTM gates [16][4H], posterior update [2][16][L] (refine_head_lds_bytes)
     // 1024 threads: the LSTM reduction (H + 4L + H = 768 terms per gate) is split over 4 K slices (tid >> 8); everything
     // else runs on the first 256 threads.  One block per slot: the serial depth of the gate loop set this kernel's time.
     const int n = blockIdx.x, tid = threadIdx.x & 255, ksl = threadIdx.x >> 8;
@@ -854,29 +854,55 @@ void refine_head_kernel(const float* __restrict__ feat /*[N][PL][C]*/, int PL, i
     }
 }
 
+// LDS of one block, in bytes: the vectors s_pool [C], s_x [H + 4L], s_h [H], s_c [H], s_red [256] and the partial sums s_part, which three
+// products share in turn - the MLP (NS_mlp slices of H), the gate pre-activations (single-launch form only: up to 16 slices of 4H) and the
+// two posterior-update products side by side (2 x 16 slices of L; the larger of the three once DIM_LATENT > 2 MLP_UNITS).  The single-launch
+// form keeps 16 x 4H for the gates whatever their slice count, as it always has.
+size_t refine_head_lds_bytes(int C, int H, int L, int split)
+{
+    const size_t ns_mlp = (size_t)std::min(16, 1024 / std::max(1, H / 4));
+    const size_t part = std::max(split ? ns_mlp * (size_t)H : (size_t)16 * 4 * H, (size_t)32 * L);
+    return ((size_t)C + (H + 4 * L) + H + H + 256 + part) * sizeof(float);
+}
+
+constexpr size_t HEAD_LDS_MAX = 96 * 1024;
+
+int refine_head_form(int C, int H, int L, int prefer_split)
+{
+    const bool single_ok = refine_head_lds_bytes(C, H, L, 0) <= HEAD_LDS_MAX;
+    const bool split_ok = sgemm_tn_mfma_ok(32, 4 * H, H + 4 * L + H) && refine_head_lds_bytes(C, H, L, 1) <= HEAD_LDS_MAX;
+    if (split_ok && (prefer_split || !single_ok)) return 1;
+    return single_ok ? 0 : -1;
+}
+
 // xh / gp (both or neither): scratch [roundup32(N)][H + 4L + H] / [roundup32(N)][4H] for the three-launch form (pre, gate GEMM on fp32 MFMA,
-// post); wihT must then be followed in memory by whhT ([H + 4L + H][4H] contiguous: the GEMM's B operand)
+// post); wihT must then be followed in memory by whhT ([H + 4L + H][4H] contiguous: the GEMM's B operand).  With the scratch the form is
+// refine_head_form's: prefer_split (option head_mfma) decides where both fit, and a width whose gate partial sums do not fit the LDS of one
+// launch (MLP_UNITS above about 356) takes the three-launch form regardless.  Without it only the single-launch form can run.
 hipError_t launch_refine_head(hipStream_t st, const float* feat, int N, int PL, int C, int H, int L,
                               const float* mlp_wT, const float* mlp_b, const float* wihT, const float* whhT,
                               const float* lstm_b, const float* wmT, const float* bm, const float* wvT, const float* bv,
                               const float* latent, const float* h_prev, const float* c_prev, float* h_out, float* c_out,
                               float* pm, float* plv, float* sv_pooled, float* sv_s, float* sv_gates, float* sv_xin,
-                              float* d_mean, float* d_logvar, float* xh, float* gp)
+                              float* d_mean, float* d_logvar, float* xh, float* gp, int prefer_split)
 {
     IOD_XSKIP(4);
-    if (256 % C != 0) return hipErrorInvalidValue;
+    if (C < 1 || C > 256 || 256 % C != 0 || H < 4 || L < 4) return hipErrorInvalidValue;
     if ((H + 4 * L) % 4 != 0 || H % 4 != 0 || L % 4 != 0 || C % 4 != 0) return hipErrorInvalidValue;
-    const size_t lds = (size_t)(C + (H + 4 * L) + H + H + 256 + 16 * 4 * H) * sizeof(float);
+    const bool have_scratch = xh && gp && whhT == wihT + (size_t)(H + 4 * L) * 4 * H;
+    const int form = have_scratch ? refine_head_form(C, H, L, prefer_split)
+                                  : (refine_head_lds_bytes(C, H, L, 0) <= HEAD_LDS_MAX ? 0 : -1);
+    if (form < 0) return hipErrorInvalidValue;
+    const size_t lds = refine_head_lds_bytes(C, H, L, form);
     static std::atomic<unsigned> attr_devs[3];                             // devices each instance is configured on
-    if (lds > 96 * 1024) return hipErrorInvalidValue;
 #define HEAD_LAUNCH(STG) do {                                                                                                        \
-        if (hipError_t e = iod_set_max_lds((const void*)refine_head_kernel<STG>, 96 * 1024, attr_devs[STG]); e != hipSuccess) return e;  \
+        if (hipError_t e = iod_set_max_lds((const void*)refine_head_kernel<STG>, (int)HEAD_LDS_MAX, attr_devs[STG]); e != hipSuccess) return e;  \
         hipLaunchKernelGGL(refine_head_kernel<STG>, dim3(N), dim3(1024), lds, st, feat, PL, C, H, L, mlp_wT, mlp_b, wihT, whhT,      \
                            lstm_b, wmT, bm, wvT, bv, latent, h_prev, c_prev, h_out, c_out, pm, plv, sv_pooled, sv_s,                 \
                            sv_gates, sv_xin, d_mean, d_logvar, xh, gp);                                                              \
     } while (0)
     const int Kg = H + 4 * L + H, Np = (N + 31) / 32 * 32;
-    if (xh && gp && whhT == wihT + (size_t)(H + 4 * L) * 4 * H && sgemm_tn_mfma_ok(Np, 4 * H, Kg)) {
+    if (form == 1) {
         HEAD_LAUNCH(1);
         if (hipError_t e = launch_sgemm_tn_mfma(st, Np, 4 * H, Kg, 1.f, xh, Kg, wihT, 4 * H, 0.f, gp, 4 * H, 0, 0, 1); e != hipSuccess) return e;
         HEAD_LAUNCH(2);

@@ -1196,7 +1196,8 @@ void head_bptt_kernel(const float* __restrict__ g_pm, const float* __restrict__ 
     }
 }
 
-// does the fused kernel's LDS footprint fit (it does for every shipped configuration; MLP_UNITS >= 512 falls back to the launch sequence)
+// does the fused kernel's LDS footprint fit: 2 (2L + 10H) + 16384 floats <= 160 KB holds for every accepted width (151.5 KB at L = 256, H = 1024);
+// what sends a configuration to the launch sequence is REF.CONV_CHAN > MLP_UNITS
 static size_t head_bptt_lds(int L, int H) { return ((size_t)HB * (2 * L + 10 * H) + (size_t)HKG * 2 * HB * 256) * sizeof(float); }
 // (head_matvec reads the weights as 16-byte f32x4 rows: every row length / leading dimension - H, H + 4L, Cr, L - must be a multiple of 4)
 bool head_bptt_fits(int L, int H, int Cr) { return Cr <= H && H % 4 == 0 && Cr % 4 == 0 && L % 4 == 0 && head_bptt_lds(L, H) <= 160 * 1024; }
@@ -1226,6 +1227,54 @@ hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_pl
     hipLaunchKernelGGL(head_bptt_kernel<false>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
                        ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr, wtab, nullptr, nullptr, nullptr, nullptr, (size_t)0);
     return hipGetLastError();
+}
+
+// The same recurrence as a launch sequence: per iteration 2 scale (+ 2 seed adds), 5 SGEMMs and the two pointwise kernels; what runs when
+// head_bptt_fits says no (REF.CONV_CHAN > MLP_UNITS) or option head_fused is 0.  Arguments as launch_head_bptt, except: whost = the loss
+// weights as a HOST table (NULL = default), seeded = the aux backward (gl_dev scales the ELBO seeds, seed_m / seed_v may be NULL), and the
+// scratch dc1, dxin, carry_h[2], carry_c[2], each [N][H].  The per-iteration tensors lie back to back as in the fused kernel.
+hipError_t launch_head_bptt_unfused(hipStream_t st, const float* g_pm, const float* g_plv, const float* gates, const float* cst, const float* u,
+                                    const float* Wm, const float* Wv, const float* Whh, const float* Wih, const float* Wmlp, float* ddm_all,
+                                    float* ddv_all, float* dgates_all, float* ds_all, float* dpooled_all, int T, int N, int B, int L, int H, int Cr,
+                                    int seeded, const float* seed_m, const float* seed_v, const float* gl_dev, const float* whost,
+                                    const float* dh_in, const float* dc_in, float* dh_out, float* dc_out, size_t seed_stride,
+                                    float* dc1, float* dxin, float* const carry_h[2], float* const carry_c[2])
+{
+#define HBU(call) do { if (hipError_t e_ = (call); e_ != hipSuccess) return e_; } while (0)
+    const int IN = H + 4 * L;
+    int cf = 0;                                            // carry buffer flip
+    for (int i = T - 1; i >= 0; --i) {
+        // d loss / d delta_i = -w_{i+1}/B * d(B*ELBO_{i+1})/d lambda_{i+1}   (lambda_{i+1} = detach(lambda_i) + delta_i)
+        const float alpha = whost ? -whost[i + 1] / (float)B : -((float)(i + 2) / (float)(T + 1)) / (float)B;
+        float *ddm = ddm_all + (size_t)i * N * L, *ddv = ddv_all + (size_t)i * N * L;
+        float *dgates = dgates_all + (size_t)i * N * 4 * H, *ds = ds_all + (size_t)i * N * H;
+        HBU(launch_scale(st, g_pm + (size_t)(i + 1) * N * L, alpha, ddm, N * L));
+        HBU(launch_scale(st, g_plv + (size_t)(i + 1) * N * L, alpha, ddv, N * L));
+        if (seeded) {                                      // ELBO seeds x d(out) / d(loss); lambda_T's cotangents join delta_{T-1} unscaled
+            // (cotangents on chosen evaluations: those of lambda_{i+1} join delta_i, every i)
+            const float *sm = seed_stride ? seed_m + (size_t)i * seed_stride : i == T - 1 ? seed_m : nullptr;
+            const float *sv = seed_stride ? seed_v + (size_t)i * seed_stride : i == T - 1 ? seed_v : nullptr;
+            HBU(launch_scale_dev_add(st, ddm, gl_dev, sm, N * L));
+            HBU(launch_scale_dev_add(st, ddv, gl_dev, sv, N * L));
+        }
+        const float *c0 = cst + (size_t)i * N * H, *c1 = cst + (size_t)(i + 1) * N * H;
+        // read-out layers act on the cell state (iodine.py:488-492)
+        HBU(launch_sgemm(st, 0, 0, N, H, L, 1.f, ddm, L, Wm, H, 0.f, dc1, H));
+        HBU(launch_sgemm(st, 0, 0, N, H, L, 1.f, ddv, L, Wv, H, 1.f, dc1, H));
+        const bool last = (i == T - 1);
+        HBU(launch_lstm_bwd_pointwise(st, gates + (size_t)i * N * 4 * H, c0, c1, dc1, last ? dh_in : carry_h[cf],
+                                      last ? dc_in : carry_c[cf], dgates, carry_c[cf ^ 1], N, H));
+        HBU(launch_sgemm(st, 0, 0, N, H, 4 * H, 1.f, dgates, 4 * H, Whh, H, 0.f, carry_h[cf ^ 1], H));
+        cf ^= 1;
+        // MLP (double ELU) and average pool
+        HBU(launch_sgemm(st, 0, 0, N, H, 4 * H, 1.f, dgates, 4 * H, Wih, IN, 0.f, dxin, H));
+        HBU(launch_mlp_bwd_pointwise(st, dxin, H, u + (size_t)i * N * H, ds, N, H));
+        HBU(launch_sgemm(st, 0, 0, N, Cr, H, 1.f, ds, H, Wmlp, Cr, 0.f, dpooled_all + (size_t)i * N * Cr, Cr));
+    }
+    if (dh_out) HBU(hipMemcpyAsync(dh_out, carry_h[cf], sizeof(float) * (size_t)N * H, hipMemcpyDeviceToDevice, st));
+    if (dc_out) HBU(hipMemcpyAsync(dc_out, carry_c[cf], sizeof(float) * (size_t)N * H, hipMemcpyDeviceToDevice, st));
+#undef HBU
+    return hipSuccess;
 }
 
 // avg-pool backward fused with the ELU derivative of the last refinement conv layer

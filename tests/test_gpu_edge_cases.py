@@ -320,3 +320,37 @@ def test_reference_default_arch():
     params, x, eps = _case(arch, 2, seed=21)
     m = _step_vs_oracle(arch, params, x, eps)
     assert m.get_input_size() == (15, 512) and tuple(m.decoder.conv.weight.shape) == (4, 64, 5, 5)
+
+
+@pytest.mark.parametrize('L,H,head_mfma', [(16, 4, 1), (24, 8, 1), (24, 8, 0), (8, 512, 1), (8, 512, 0), (8, 1024, 1)])
+def test_head_widths_at_the_edges_of_its_lds_budget(L, H, head_mfma):
+    """DIM_LATENT > 2 MLP_UNITS: the two posterior-update products' partial sums (32 L floats) are larger than the gate partial sums the head's
+    LDS used to be sized by (64 H) and ran past the allocation.  MLP_UNITS 512 / 1024: the single-launch form does not fit 96 KB; the
+    three-launch form runs, with option head_mfma = 0 as well (the option only chooses where both fit).  Whole training step, reconstruct and
+    every gradient against the oracle, as test_latent_and_mlp_widths_that_are_not_multiples_of_4.  REF.CONV_CHAN > MLP_UNITS (the first two
+    widths) takes the backward's launch sequence, the others its fused kernel."""
+    arch = dataclasses.replace(O.tiny_arch(slots=3, iters=2, img_size=16), dim_latent=L, ref_mlp=H)
+    params, x, eps = _case(arch, 2, seed=61)
+    m = make_hip_model(arch, params, options={'head_mfma': head_mfma})
+    xd, ed = x.to(DEV), eps.to(DEV)
+    m.zero_grad(set_to_none=True)
+    loss = m(xd, ed)
+    loss.backward()
+    out, rg = O.train_step_grads(x, eps, params, arch)
+    assert abs(loss.item() - float(out['loss'])) <= 1e-4 * abs(float(out['loss']))
+    assert rel_err(m.elbo_terms[:, 0].cpu(), out['elbos']) < 1e-4
+    bad = [(n, rel_l2(*grad_views(n, p.grad.cpu().numpy(), rg[n].numpy()))) for n, p in m.named_parameters()
+           if not rel_l2(*grad_views(n, p.grad.cpu().numpy(), rg[n].numpy())) < 2e-3]
+    assert not bad, bad
+    assert rel_err(m.posterior.mean.cpu(), out['post_mean']) < 2e-4
+    ref = O.reconstruct(x, eps, params, arch)
+    pred, mask, mean = m.reconstruct(xd, ed)
+    assert rel_err(m.elbo_terms[:, 0].cpu(), ref['elbos']) < 1e-4
+    assert rel_err(pred.cpu(), ref['pred']) < 2e-4 and rel_err(mask.cpu(), ref['mask']) < 2e-4
+
+
+def test_mlp_units_no_head_form_can_run_are_refused_with_the_bound():
+    from iodine_amd import IODINE
+    from iodine_amd.model import arch_namespace
+    with pytest.raises((RuntimeError, ValueError), match='REF.MLP_UNITS = 364'):
+        IODINE(arch_namespace(8, 2, 3, 16, (32, 2, 364), (32, 2))).to(DEV).reconstruct(torch.rand(1, 3, 16, 16, device=DEV))
