@@ -446,6 +446,35 @@ int iodine_adam_step_clipped(void* stream, const long long* ptrs_dev, const long
 int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, int batch, int slots, int n_gt, int pixels,
                      int* table);
 
+/* Per-slot object table and segmentation map of one decode: what a user of the masks computes first (count, crop, follow the slots).
+ * Stateless like the ARI entry above: no handle, no workspace, one launch, no synchronise.
+ *   mask (B,K,1,S,S) fp32 (device, as iodine_reconstruct / iodine_decode / a trajectory entry returns it), mean_or_null (B,K,3,S,S) fp32,
+ *   table (B,K,14) fp32 (device, overwritten), seg_or_null (B,S,S) uint8 (device, overwritten): seg[b][p] = argmax_k mask[b][k][p].
+ * The argmax compares `v > best` from slot 0 upwards: on a tie the LOWEST index wins, as in iodine_ari_table, and a NaN never wins.
+ * Pixel p has col = p % S, row = p / S; "hard" pixels of slot k are those whose seg equals k.  Columns of table[b][k]:
+ *    0      soft_area          sum_p m
+ *    1      hard_area          number of hard pixels
+ *    2, 3   soft_cx, soft_cy   sum m col / soft_area, sum m row / soft_area            (0 where soft_area == 0)
+ *    4, 5   hard_cx, hard_cy   mean col, mean row of the hard pixels                    (-1 where there are none)
+ *    6..9   x0, y0, x1, y1     inclusive bounding box of the hard pixels                (all -1 where there are none)
+ *   10..12  r, g, b            sum m mean_c / soft_area                                 (0 where soft_area == 0 or mean_or_null is NULL)
+ *   13      peak               max_p m
+ * An empty slot therefore reads hard_area 0 and -1 in columns 4..9; a slot whose mask is identically 0 also has 0 in columns 0, 2, 3 and
+ * 10..12.  Counts, coordinate sums and the box are integer arithmetic, converted once ((float)((double)sum / (double)count)); the soft sums
+ * run in fp64 over fixed-order fp32 groups of four and use no atomics, so the same input gives the same bits on every call.
+ * IODINE_ERR_INVALID, before anything touches the device: mask or table NULL, batch < 1, slots outside 1..16, size outside 1..1024. */
+int iodine_slot_table(void* stream, const float* mask, const float* mean_or_null, int batch, int slots, int size,
+                      float* table, unsigned char* seg_or_null);
+
+/* Contingency table of two segmentations (two runs of a multi-stable model, two frames of a clip): seg_a, seg_b (B,P) uint8 (device, e.g.
+ * the seg of iodine_slot_table), table (B,Ka,Kb) int32 (device, overwritten), table[b][i][j] = #{p : seg_a[b][p] == i and seg_b[b][p] == j}.
+ * It is the table the ARI formula takes; IoU of slot i with slot j is table[i][j] / (rowsum_i + colsum_j - table[i][j]).  A pixel whose
+ * label is >= slots_a in seg_a or >= slots_b in seg_b is left out of every count (the labels are the caller's and are never used as an
+ * index unchecked).  Integer atomics only: exact and reproducible.  IODINE_ERR_INVALID, before anything touches the device: a NULL
+ * pointer, batch < 1, slots_a or slots_b outside 1..16, pixels outside 1..1024 * 1024.  Does not synchronise. */
+int iodine_seg_overlap(void* stream, const unsigned char* seg_a, const unsigned char* seg_b, int batch, int slots_a, int slots_b,
+                       int pixels, int* table);
+
 /* Options: "stop_after_iters" (debug: run only the first v refinement iterations of reconstruct, no final decode),
  * "graph" (1: replay the fixed-shape launch sequence of reconstruct / decode / elbo / train_forward / train_backward through a
  * hipGraph per distinct argument tuple -- first call eager, second captured, later ones one hipGraphLaunch; needs a non-default

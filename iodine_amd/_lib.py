@@ -36,6 +36,7 @@ EXPORTS = (
     'iodine_last_sigma_grad',
     'iodine_last_input_grad', 'iodine_last_likelihood', 'iodine_op_pixel_maps',
     'iodine_op_sgemm', 'iodine_op_colsum', 'iodine_op_refine_head', 'iodine_op_refine_head_form', 'iodine_op_head_bptt', 'iodine_op_pool_bwd',
+    'iodine_slot_table', 'iodine_seg_overlap',
 )
 
 
@@ -158,6 +159,9 @@ def lib() -> C.CDLL:
         L.iodine_op_refine_head_form.argtypes = [ci] * 4
         L.iodine_op_head_bptt.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(vp)] + [ci] * 6 + [C.c_longlong]
         L.iodine_op_pool_bwd.argtypes = [vp, vp, vp, vp, ci, ci, ci]
+    if hasattr(L, 'iodine_slot_table'):                 # (object tables, iodine_amd.objects; absent from older A/B builds)
+        L.iodine_slot_table.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
+        L.iodine_seg_overlap.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

@@ -329,6 +329,11 @@ hipError_t launch_grad_scale(hipStream_t st, const long long* ptrs, const long l
 hipError_t launch_randn_philox(hipStream_t st, float* out, long long n, unsigned long long seed, unsigned long long stream_id);
 hipError_t launch_ari_table(hipStream_t st, const float* mask, const unsigned char* gt, int B, int K, int G, int P,
                             int* table);
+// kernels_objects.hip: per-slot object table + segmentation map, contingency table of two segmentations (stateless, like launch_ari_table)
+hipError_t launch_slot_table(hipStream_t st, const float* mask, const float* mean, int B, int K, int S, float* table,
+                             unsigned char* seg);
+hipError_t launch_seg_overlap(hipStream_t st, const unsigned char* seg_a, const unsigned char* seg_b, int B, int Ka, int Kb, int P,
+                              int* table);
 hipError_t launch_pack_dec_out_gemm(hipStream_t st, const float* w, int C, float* meta, void* dst);
 hipError_t launch_pack_dec_out_dgrad(hipStream_t st, const float* w, int C, const float* meta, void* dst);
 hipError_t launch_dec_out_dgrad_f16x3(hipStream_t st, const float* g, const void* wpk, const float* wmeta, const float* aux,

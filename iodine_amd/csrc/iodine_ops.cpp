@@ -65,6 +65,31 @@ int iodine_ari_table(void* stream, const float* mask, const unsigned char* gt, i
     return IODINE_OK;
 }
 
+int iodine_slot_table(void* stream, const float* mask, const float* mean_or_null, int batch, int slots, int size,
+                      float* table, unsigned char* seg_or_null)
+{
+    if (!mask || !table || batch < 1 || slots < 1 || slots > 16 || size < 1 || size > 1024) {
+        g_create_error = "iodine_slot_table: bad argument (mask and table required, batch >= 1, slots in 1..16, size in 1..1024)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_slot_table((hipStream_t)stream, mask, mean_or_null, batch, slots, size, table, seg_or_null);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_slot_table: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_seg_overlap(void* stream, const unsigned char* seg_a, const unsigned char* seg_b, int batch, int slots_a, int slots_b,
+                       int pixels, int* table)
+{
+    if (!seg_a || !seg_b || !table || batch < 1 || slots_a < 1 || slots_a > 16 || slots_b < 1 || slots_b > 16 || pixels < 1 ||
+        pixels > 1024 * 1024) {
+        g_create_error = "iodine_seg_overlap: bad argument (three pointers required, batch >= 1, slots_a / slots_b in 1..16, pixels in 1..1024^2)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_seg_overlap((hipStream_t)stream, seg_a, seg_b, batch, slots_a, slots_b, pixels, table);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_seg_overlap: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
 int iodine_randn(void* stream, float* out, long long n, unsigned long long seed, unsigned long long stream_id)
 {
     if (!out || n < 1) { g_create_error = "iodine_randn: bad argument"; return IODINE_ERR_INVALID; }

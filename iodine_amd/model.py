@@ -24,7 +24,8 @@ sequence of T + 1 numbers.  They are checked on the host when a call starts and 
 Video input and resumable refinement (the paper's tracking use of the T-step loop; the reference closes ``encode`` / ``forward`` over
 one ``x``, iodine.py:73-105,115-158): ``x`` may be a clip ``(B, E, 3, S, S)`` with one frame per ELBO evaluation of the call (E = T for
 ``encode`` / ``reconstruct``, T + 1 for ``forward``); ``reconstruct(x, trajectory=True)`` leaves the decode of every iteration in
-``model.trajectory``; ``model.refinement_state()`` / ``state=`` carry (lambda, h, c) from one call into the next, so a long clip runs
+``model.trajectory``; ``reconstruct(x, objects=True)`` leaves the per-slot object table, the segmentation map and the per-slot KL in
+``model.objects`` (``iodine_amd.objects``); ``model.refinement_state()`` / ``state=`` carry (lambda, h, c) from one call into the next, so a long clip runs
 in chunks of ``n_iters`` frames.  Training carries the state the same way: ``forward(x, state=..., keep_state=True)`` continues a clip
 from the state the last chunk left - detached tensors give truncated back-propagation through time, tensors that require grad receive the
 gradient of the chunk (``iodine_train_backward_seq``), and ``attach_state=True`` leaves ``model.lstm_hidden`` attached to the graph like
@@ -513,6 +514,7 @@ class IODINE(nn.Module):
         self.mask = None
         self.elbo_terms = None          # (n_elbo_calls, 3) = {ELBO, KL, LL} of the last call
         self.trajectory = None          # reconstruct(x, trajectory=True): dict of per-iteration outputs, else None
+        self.objects = None             # reconstruct(x, objects=True): dict(table, segmentation, kl) of the returned decode, else None
         self.likelihood_maps = False    # True: every call that evaluates an ELBO also leaves the two per-pixel maps below (iodine.py:210-216)
         self.log_likelihood = None      # (B, 3, S, S)    logsumexp_k(log(mask + 1e-12) + K_log_likelihood) of the last ELBO evaluation
         self.K_log_likelihood = None    # (B, K, 3, S, S) gaussian_log_likelihood(x[:, None], mean, sigma); both float32, detached, raw
@@ -1052,7 +1054,7 @@ class IODINE(nn.Module):
             raise RuntimeError('trajectory=True needs the whole call: its last entry is the final decode, which option stop_after_iters '
                                'skips (unset it with set_option("stop_after_iters", -1))')
         state = self._check_state(state, B, K, dev)
-        self.trajectory, self._state = None, None
+        self.trajectory, self._state, self.objects = None, None, None
         cap = self.max_batch()
         if B > cap:                                   # chunks of independent images; eps (T+1, B, K, L) is cut along B
             # the next chunk re-uses the workspace, so the LSTM state of a chunk is fetched (two small copies) only where the caller
@@ -1120,7 +1122,7 @@ class IODINE(nn.Module):
         iteration i then scores, differentiates and encodes frame i.  ``state`` / ``keep_state`` / ``weights``: see ``reconstruct``."""
         return self._reconstruct(x, eps, want_images=False, state=state, keep_state=keep_state, weights=weights)[3]
 
-    def reconstruct(self, x, eps=None, trajectory=False, state=None, keep_state=False, weights=None):
+    def reconstruct(self, x, eps=None, trajectory=False, state=None, keep_state=False, weights=None, objects=False):
         """pred (B,3,S,S), mask (B,K,1,S,S), mean (B,K,3,S,S).  iodine.py:107-112.
 
         ``x``: images (B, 3, S, S), or a clip (B, T, 3, S, S), batch first: ELBO evaluation i uses frame ``x[:, i]`` for the
@@ -1143,9 +1145,32 @@ class IODINE(nn.Module):
 
         ``weights``: per-pixel observation weights >= 0 of this call, (B, 1, S, S) / (B, S, S), with a clip also (B, T, 1, S, S) /
         (B, T, S, S); see the module docstring for what is weighted.  The refinement then explains the weighted pixels only - a weight
-        of 0 takes a pixel out of the objective - while ``pred`` / ``mask`` / ``mean`` are still rendered everywhere (inpainting)."""
+        of 0 takes a pixel out of the objective - while ``pred`` / ``mask`` / ``mean`` are still rendered everywhere (inpainting).
+
+        ``objects=True`` leaves ``model.objects`` = dict(table (B,K,14), segmentation (B,S,S) uint8, kl (B,K)): the per-slot table and
+        argmax map of ``iodine_amd.objects.slot_table`` on the returned ``mask`` / ``mean`` (one more launch, after the call, so a chunked
+        batch needs nothing special) and the per-slot KL of the final posterior against N(0, 1), ``0.5 sum_L(exp(lv) + m^2 - 1 - lv)`` -
+        the usual "is this slot used" signal.  With ``trajectory=True`` as well, ``model.trajectory`` gains ``table (T+1,B,K,14)`` and
+        ``segmentation (T+1,B,S,S)`` of every entry; entry T is ``model.objects``.  Every encode / reconstruct without it sets
+        ``model.objects = None``, adds no launch and returns the same bits."""
         pred, mask, mean, _ = self._reconstruct(x, eps, state=state, trajectory=trajectory, keep_state=keep_state, weights=weights)
+        if objects:
+            self._read_objects(mask, mean, trajectory)
         return pred, mask, mean
+
+    @torch.no_grad()
+    def _read_objects(self, mask, mean, trajectory):
+        """``model.objects`` (and the trajectory's tables) of a finished reconstruct: see there."""
+        from .objects import slot_table
+        pm, plv = self.posterior.mean.double(), self.posterior.logvar.double()    # (B, K, L): tiny; fp64 keeps exp(lv) - 1 - lv near lv = 0
+        kl = (0.5 * (plv.exp() + pm * pm - 1.0 - plv).sum(-1)).float()
+        if trajectory:                                # one launch over all T + 1 entries; the last is the returned decode
+            table, seg = slot_table(self.trajectory['mask'], self.trajectory['mean'], segmentation=True)
+            self.trajectory['table'], self.trajectory['segmentation'] = table, seg
+            table, seg = table[-1], seg[-1]
+        else:
+            table, seg = slot_table(mask, mean, segmentation=True)
+        self.objects = {'table': table, 'segmentation': seg, 'kl': kl}
 
     @torch.no_grad()
     def refinement_state(self):
