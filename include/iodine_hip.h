@@ -195,6 +195,35 @@ int iodine_last_refine_state(iodine_handle* h, void* stream, int count, float* l
 /* pred, mask, mean = model.decode(z) -- iodine.py:59-71. */
 int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, float* pred, float* mask, float* mean);
 
+/* Scene edits: n_edits renderings of the scene decode(z), each with ONE slot of one image replaced by the decode of another latent or
+ * removed -- latent traversals, object removal, slots moved between scenes.  The decoder treats slot-images independently and only the last
+ * per-pixel step (softmax over the K slots, pred = sum_k mask x mean) couples the slots of an image, so the call decodes the base once
+ * (B x K slot-images), then one slot-image per replace edit and none per removal, and renders every edit with one per-pixel pass over
+ * the base and the edit decodes: B K + E slot-image decodes where E calls of iodine_decode on the edited scenes take E K.
+ *   z (B,K,L) device, K = the run shape's slot count; image / slot / kind: HOST arrays of n_edits ints -- edit e acts on slot slot[e] of
+ *   image image[e]; kind 0 = replace it by decode(z_new[e]), kind 1 = remove it (its logit becomes -inf: the other K - 1 slots are
+ *   re-normalised, the removed slot's mask is exactly 0); z_new (n_edits,L) device, row e belongs to edit e, rows of removals are not
+ *   read, NULL is allowed when every edit is a removal.
+ *   Per edit, each may be NULL: pred (n_edits,3,S,S), mask (n_edits,K,1,S,S), mean (n_edits,3,S,S) = the sigmoid rgb of the slot-image put
+ *   into slot slot[e] (of a removal: of the slot that was removed).  base_pred / base_mask / base_mean = the outputs of iodine_decode(z),
+ *   each may be NULL.  A replace edit returns the bits iodine_decode returns for the edited z: same decoder kernels, same per-pixel
+ *   operation order.
+ * chunk_images: the size of the arena in images, >= batch; 0 = batch.  The workspace is planned for inference (mode 0) at
+ * W = max(batch, chunk_images) images -- iodine_workspace_bytes(h, W, 0) -- and the edits run in chunks of consecutive edits with at most
+ * W K replacements each: per chunk the z_new rows are gathered, decoded in one decoder pass and rendered by launches of at most 256 edits,
+ * whose indices travel in the kernel arguments.  No host synchronisation, no allocation, everything on `stream`.
+ * IODINE_ERR_INVALID, before anything is launched, with a message that names the offending edit: n_edits < 1, an image outside
+ * 0..batch-1, a slot outside 0..K-1, a kind other than 0 / 1, a removal at K = 1, a replacement while z_new is NULL, chunk_images < batch
+ * (and non-zero), batch or chunk_images beyond the 2^31 limit of iodine_decode.  The indices are host memory and never reach a kernel unchecked.
+ * Call state: the call counts as an iodine_decode at batch W -- a saved training forward or saved decode / elbo is discarded, the LSTM
+ * state of the last reconstruct stays -- and, because the base decode is kept in the buffer the last elbo() wrote, iodine_last_elbo_outputs
+ * has nothing to read afterwards (IODINE_ERR_STATE), as after a decode under "save_for_backward".  Not differentiable.  The entry is NOT
+ * captured under option "graph": its launch sequence depends on the edit list, so it always runs eagerly.  Profile category: "scene_edit"
+ * (the per-pixel launches; the decoder passes are booked under the decoder's categories). */
+int iodine_scene_edit(iodine_handle* h, void* stream, int batch, const float* z, int n_edits, const int* image, const int* slot, const int* kind,
+                      const float* z_new, int chunk_images, float* pred, float* mask, float* mean, float* base_pred, float* base_mask,
+                      float* base_mean);
+
 /* elbo = model.elbo(x) -- IODINE.elbo, iodine.py:161-241: ONE sample z = mu + exp(logvar/2) * eps from the given posterior
  * (post_mean / post_logvar (B,K,L); both NULL = the initial posterior of Gaussian.init_unit, iodine.py:607-618), decode,
  * mixture log-likelihood and KL.  eps (B,K,L); terms (3) = {ELBO, KL, LL} (device, may be NULL).  The tensors the reference
@@ -565,7 +594,7 @@ int iodine_set_option(iodine_handle* h, const char* key, double value);
  * (fused layer-1 data gradient + layer-0 weight gradient, option refine_bwd_fused), "refine_bias_grad", "head_bwd", "gen_conv"
  * (the fp32 convs of the generic path), "gen_conv_f16x3" (its split-fp16 launches, option gen_conv_precision 1), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward), "render_bwd" (backward of the rendering - sigmoid, slot softmax, sum_k mask x mean - in iodine_decode_backward; the decoder pass behind it is booked under the categories of the training step), "frames_in" (the image / clip conversion at the head of
  * iodine_reconstruct / iodine_train_forward: one launch for all frames), "traj_out" (the per-iteration output launches of a trajectory,
- * iodine_reconstruct_seq).  "seen:<category>" returns in *launches the number of launches of <category> since the
+ * iodine_reconstruct_seq), "scene_edit" (the per-pixel rendering launches of iodine_scene_edit).  "seen:<category>" returns in *launches the number of launches of <category> since the
  * last reset, bracketed or not (option profile_stride; counted at profile levels 1 -- the bracketed categories -- and 2 -- all).  Synchronises on the recorded events.  Two more names report
  * the hipGraph bookkeeping of option "graph" in *launches: "graph_captures" (graphs instantiated) and "graph_replays". */
 int iodine_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset);

@@ -2,8 +2,8 @@
 ``IODINE.forward / reconstruct`` module API.  Heavy imports are lazy so that
 ``iodine_amd.synth`` can be used without the HIP library being built."""
 
-__all__ = ['IODINE', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects',
-           'slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS']
+__all__ = ['IODINE', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse',
+           'slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS', 'latent_kl', 'rank_dims', 'Traversal']
 
 
 def __getattr__(name):
@@ -13,4 +13,7 @@ def __getattr__(name):
     if name in ('slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS'):
         from . import objects
         return getattr(objects, name)
+    if name in ('latent_kl', 'rank_dims', 'Traversal'):      # (``iodine_amd.traverse`` is the module; the function is ``traverse.traverse``)
+        from . import traverse
+        return getattr(traverse, name)
     raise AttributeError(name)

@@ -37,6 +37,7 @@ EXPORTS = (
     'iodine_last_input_grad', 'iodine_last_likelihood', 'iodine_op_pixel_maps',
     'iodine_op_sgemm', 'iodine_op_colsum', 'iodine_op_refine_head', 'iodine_op_refine_head_form', 'iodine_op_head_bptt', 'iodine_op_pool_bwd',
     'iodine_slot_table', 'iodine_seg_overlap',
+    'iodine_scene_edit',
 )
 
 
@@ -162,6 +163,8 @@ def lib() -> C.CDLL:
     if hasattr(L, 'iodine_slot_table'):                 # (object tables, iodine_amd.objects; absent from older A/B builds)
         L.iodine_slot_table.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
         L.iodine_seg_overlap.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
+    if hasattr(L, 'iodine_scene_edit'):                 # (IODINE.edit, iodine_amd.traverse; absent from older A/B builds, which raise on them)
+        L.iodine_scene_edit.argtypes = [vp, vp, ci, vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp, ci] + [vp] * 6
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

@@ -200,6 +200,12 @@ hipError_t launch_pixel_input_grad(hipStream_t st, const float* x4, const float*
                                    int K, int P, float sigma, int strict, float coef, int first_x, int first_w);
 hipError_t launch_final_out(hipStream_t st, const float* dec, float* pred, float* mask, float* mean, float* logits,
                             int B, int K, int P);
+// kernels_edit.hip: final_out for edits that each replace (src = row of `edit` [rows][P][4]) or remove (src < 0) ONE slot of an image of
+// `base` [B K][P][4]; the per-edit host indices travel by value in the kernel arguments.  bs = image * 16 + slot
+constexpr int SCENE_EDIT_MAX = 256;             // edits of one launch (2 KB of kernel arguments)
+struct SceneEditList { int n; int bs[SCENE_EDIT_MAX]; int src[SCENE_EDIT_MAX]; };
+hipError_t launch_scene_edit_out(hipStream_t st, const float* base, const float* edit, const SceneEditList& list, float* pred, float* mask,
+                                 float* mean, int K, int P);
 // kernels_render.hip: backward of the rendering (sigmoid, slot softmax, sum_k mask * mean) for the caller's gradients wrt pred (B,3,S,S),
 // mask (B,K,1,S,S), mean (B,K,3,S,S) - NCHW, any of them NULL = zero - into g [N][P][4]; strict as for launch_pixel_pass1
 hipError_t launch_render_bwd(hipStream_t st, const float* dec, const float* g_pred, const float* g_mask, const float* g_mean, float* g,

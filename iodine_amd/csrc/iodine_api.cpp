@@ -874,6 +874,33 @@ int decode_check(iodine_handle* h, int batch, const float* z)
     return IODINE_OK;
 }
 
+// every index of the host arrays is checked here, before anything is launched: none reaches a kernel unchecked
+int scene_edit_check(iodine_handle* h, int batch, const float* z, int n_edits, const int* image, const int* slot, const int* kind,
+                     const float* z_new, int chunk_images)
+{
+    if (int rc = check_ready(h, batch)) return rc;
+    char m[256];
+    if (!z) return h->fail(IODINE_ERR_INVALID, "iodine_scene_edit: z is required");
+    if (n_edits < 1 || !image || !slot || !kind)
+        return h->fail(IODINE_ERR_INVALID, "iodine_scene_edit: n_edits must be >= 1, with the host arrays image, slot and kind of n_edits entries each");
+    if (chunk_images != 0 && chunk_images < batch) {
+        snprintf(m, sizeof m, "iodine_scene_edit: chunk_images = %d is smaller than the batch of %d images (the arena holds the base decode; "
+                              "0 = the batch)", chunk_images, batch);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    for (int e = 0; e < n_edits; ++e) {
+        const char* bad = nullptr;
+        if (image[e] < 0 || image[e] >= batch) { snprintf(m, sizeof m, "iodine_scene_edit: edit %d: image %d is outside 0..%d", e, image[e], batch - 1); bad = m; }
+        else if (slot[e] < 0 || slot[e] >= h->K) { snprintf(m, sizeof m, "iodine_scene_edit: edit %d: slot %d is outside 0..%d (the run shape has %d slots)", e, slot[e], h->K - 1, h->K); bad = m; }
+        else if (kind[e] != 0 && kind[e] != 1) { snprintf(m, sizeof m, "iodine_scene_edit: edit %d: kind %d is neither 0 (replace) nor 1 (remove)", e, kind[e]); bad = m; }
+        else if (kind[e] == 1 && h->K == 1) { snprintf(m, sizeof m, "iodine_scene_edit: edit %d: removes the only slot of image %d (K = 1 leaves nothing to render)", e, image[e]); bad = m; }
+        else if (kind[e] == 0 && !z_new) { snprintf(m, sizeof m, "iodine_scene_edit: edit %d: replaces slot %d of image %d, but z_new is NULL", e, slot[e], image[e]); bad = m; }
+        if (bad) return h->fail(IODINE_ERR_INVALID, bad);
+    }
+    if (chunk_images > batch) return check_ready(h, chunk_images);      // the arena (and the edit decodes) run at chunk_images
+    return IODINE_OK;
+}
+
 int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* post_mean, const float* post_logvar)
 {
     if (int rc = check_ready(h, batch)) return rc;
@@ -1674,6 +1701,60 @@ int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, flo
     rc = run_graphed(h, st, graph_key(h, save ? GK_DECODE_SAVED : GK_DECODE, batch, {z, pred, mask, mean}), body);
     if (rc) return rc;
     if (save) { h->calls.diff_kind = 1; h->calls.diff_batch = batch; }
+    return IODINE_OK;
+}
+
+int iodine_scene_edit(iodine_handle* h, void* stream, int batch, const float* z, int n_edits, const int* image, const int* slot, const int* kind,
+                      const float* z_new, int chunk_images, float* pred, float* mask, float* mean, float* base_pred, float* base_mask,
+                      float* base_mean)
+{
+    if (h && h->shim)
+        return pad_scene_edit(h, stream, batch, z, n_edits, image, slot, kind, z_new, chunk_images, pred, mask, mean, base_pred, base_mask, base_mean);
+    int rc = scene_edit_check(h, batch, z, n_edits, image, slot, kind, z_new, chunk_images);
+    if (rc) return rc;
+    const int W = chunk_images > batch ? chunk_images : batch;
+    rc = ensure_workspace(h, W, 0);
+    if (rc) return rc;
+    // an iodine_decode at batch W as far as the arena goes, except that the base takes buf.dec_out (the chunk decodes write buf.g): the
+    // last elbo()'s outputs are gone, as after a saved decode.  Not captured under option graph: the launch sequence depends on the list
+    h->calls.compute_begins(true);
+    h->calls.last_elbo_iter = -1;
+    hipStream_t st = (hipStream_t)stream;
+    Buffers& b = h->buf;
+    const int K = h->K, L = h->L;
+    const size_t P = (size_t)h->P;
+    HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, z, h->wcls, nullptr, b.V, batch * K, L, h->Cd));
+    if (int r = decoder_forward(h, st, batch * K, z, b.dec_out)) return r;
+    if (base_pred || base_mask || base_mean) HIPCHK(h, launch_final_out(st, b.dec_out, base_pred, base_mask, base_mean, nullptr, batch, K, h->P));
+    // chunks of consecutive edits with at most W * K replacements each (removals ride along: they need no decode)
+    const int cap = W * K;
+    SceneEditList list;
+    for (int e0 = 0; e0 < n_edits;) {
+        int e1 = e0, rows = 0;
+        for (; e1 < n_edits && (kind[e1] == 1 || rows < cap); ++e1) rows += kind[e1] == 0;
+        if (rows > 0) {
+            // gather the chunk's z_new rows into buf.z[0] (rows of removals are not read): one copy per run of consecutive replacements
+            for (int e = e0, r = 0; e < e1;) {
+                if (kind[e] == 1) { ++e; continue; }
+                int f = e;
+                while (f < e1 && kind[f] == 0) ++f;
+                HIPCHK(h, hipMemcpyAsync(b.z[0] + (size_t)r * L, z_new + (size_t)e * L, sizeof(float) * (size_t)(f - e) * L, hipMemcpyDeviceToDevice, st));
+                r += f - e; e = f;
+            }
+            HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, b.z[0], h->wcls, nullptr, b.V, rows, L, h->Cd));
+            if (int r = decoder_forward(h, st, rows, b.z[0], b.g)) return r;
+        }
+        for (int f0 = e0, r = 0; f0 < e1; f0 += SCENE_EDIT_MAX) {
+            list.n = std::min(SCENE_EDIT_MAX, e1 - f0);
+            for (int j = 0; j < list.n; ++j) {
+                list.bs[j] = image[f0 + j] * 16 + slot[f0 + j];
+                list.src[j] = kind[f0 + j] == 0 ? r++ : -1;
+            }
+            PROF(h, st, "scene_edit", launch_scene_edit_out(st, b.dec_out, b.g, list, pred ? pred + (size_t)f0 * 3 * P : nullptr,
+                                                           mask ? mask + (size_t)f0 * K * P : nullptr, mean ? mean + (size_t)f0 * 3 * P : nullptr, K, h->P));
+        }
+        e0 = e1;
+    }
     return IODINE_OK;
 }
 

@@ -291,6 +291,8 @@ struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv, *lstm_h, 
 int set_params_check(iodine_handle* h, const float* const* dev, int n);
 int reconstruct_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* const* state_in, float* const* traj);
 int decode_check(iodine_handle* h, int batch, const float* z);
+int scene_edit_check(iodine_handle* h, int batch, const float* z, int n_edits, const int* image, const int* slot, const int* kind,
+                     const float* z_new, int chunk_images);
 int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* post_mean, const float* post_logvar);
 int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss, const float* const* state_in = nullptr,
                         const FrameSet* fr = nullptr);
@@ -323,6 +325,9 @@ int pad_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* 
                         float* z, float* post_mean, float* post_logvar, float* elbo_iter, const float* const* state_in, float* const* traj);
 int pad_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c, bool train = false);
 int pad_decode(iodine_handle* h, void* stream, int batch, const float* z, float* pred, float* mask, float* mean);
+int pad_scene_edit(iodine_handle* h, void* stream, int batch, const float* z, int n_edits, const int* image, const int* slot, const int* kind,
+                   const float* z_new, int chunk_images, float* pred, float* mask, float* mean, float* base_pred, float* base_mask,
+                   float* base_mean);
 int pad_elbo(iodine_handle* h, void* stream, int batch, const float* x, const float* post_mean, const float* post_logvar, const float* eps,
              float* terms);
 int pad_decode_backward(iodine_handle* h, void* stream, int batch, const float* g_pred, const float* g_mask, const float* g_mean, float* dz,

@@ -274,6 +274,28 @@ int pad_decode(iodine_handle* h, void* stream, int batch, const float* z, float*
     return shim_fail(h, iodine_decode(sh->inner, stream, batch, sh->z, pred, mask, mean));
 }
 
+int pad_scene_edit(iodine_handle* h, void* stream, int batch, const float* z, int n_edits, const int* image, const int* slot, const int* kind,
+                   const float* z_new, int chunk_images, float* pred, float* mask, float* mean, float* base_pred, float* base_mask,
+                   float* base_mean)
+{
+    PadShim* sh = h->shim;
+    if (int rc = scene_edit_check(sh->inner, batch, z, n_edits, image, slot, kind, z_new, chunk_images)) return shim_fail(h, rc);
+    const long long N = (long long)batch * sh->inner->K;
+    if (int r = shim_scratch(h, (size_t)std::max(N, (long long)n_edits) * sh->Lp)) return r;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(h, launch_resize_rows(st, z, sh->z, N, sh->L, sh->Lp));
+    // z_new (n_edits, L) -> sh->pm (n_edits, Lp), row for row; the rows of removals are not read (and stay as they are: never decoded)
+    for (int e = 0; e < n_edits;) {
+        if (kind[e] == 1) { ++e; continue; }
+        int f = e;
+        while (f < n_edits && kind[f] == 0) ++f;
+        HIPCHK(h, launch_resize_rows(st, z_new + (size_t)e * sh->L, sh->pm + (size_t)e * sh->Lp, f - e, sh->L, sh->Lp));
+        e = f;
+    }
+    return shim_fail(h, iodine_scene_edit(sh->inner, stream, batch, sh->z, n_edits, image, slot, kind, z_new ? sh->pm : nullptr, chunk_images,
+                                          pred, mask, mean, base_pred, base_mask, base_mean));
+}
+
 int pad_elbo(iodine_handle* h, void* stream, int batch, const float* x, const float* post_mean, const float* post_logvar, const float* eps,
              float* terms)
 {

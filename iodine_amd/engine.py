@@ -370,6 +370,25 @@ def _evaluate(model, dataloader, device, evaluator):
     return evaluator
 
 
+@torch.no_grad()
+def save_traversal(model, x, path, top=8, n_values=7, log=print):
+    """The disentanglement figure of image 0 of ``x``: reconstruct the batch, rank each slot's latent units by KL, move the ``top`` of them
+    one at a time along the posterior (``mu + v sigma``, ``n_values`` values of v in [-2, 2]) and save ``grids (K, 3, top S, n_values S)`` -
+    rows are units, columns values -, ``dims (K, top)``, ``values`` and ``kl (K, L)`` as an .npz.  One ``IODINE.edit`` call behind
+    ``iodine_amd.traverse.traverse``: the scene is decoded once, every variation decodes one slot-image."""
+    import numpy as np
+
+    from .traverse import latent_kl, traverse
+    model.eval()
+    model.reconstruct(x)
+    post = (model.posterior.mean, model.posterior.logvar)
+    t = traverse(model, model.z, image=0, posterior=post, top=top, values=torch.linspace(-2.0, 2.0, n_values), mode='sigma')
+    grids = torch.stack([t.grid(i) for i in range(len(t.slots))])
+    np.savez(path, grids=grids.cpu().numpy(), dims=t.dims.numpy(), values=t.values.numpy(), kl=latent_kl(post[0][0], post[1][0]).cpu().numpy())
+    log(f'traversal of image 0: {len(t.slots)} slots x {t.dims.shape[1]} units x {n_values} values -> {path}')
+    return t
+
+
 def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', choices=['clevr6', 'dsprites'], default='dsprites')
@@ -407,6 +426,11 @@ def make_parser():
     ap.add_argument('--learn-input-gain', action='store_true',
                     help='learn a per-channel gain and offset applied to every batch before the model (six parameters in their own param '
                          'group, trained through the gradient into the image); saved as the checkpoint entry input_gain')
+    ap.add_argument('--traverse', metavar='OUT.npz',
+                    help='instead of training: after loading (--resume), reconstruct the first batch, traverse the latent units of image 0 '
+                         '(each slot, the units with the largest KL, moved along the posterior) and save the grids; see save_traversal')
+    ap.add_argument('--traverse-top', type=int, default=8, metavar='N', help='with --traverse: units per slot, by descending KL')
+    ap.add_argument('--traverse-values', type=int, default=7, metavar='V', help='with --traverse: values per unit, linspace(-2, 2, V) posterior sigmas')
     return ap
 
 
@@ -450,6 +474,11 @@ def main(argv=None):
         ds = MultiDSprites(args.dsprites)
     else:
         ds = SyntheticScenes(args.batch * world * 8, arch.IMG_SIZE)
+    if args.traverse:
+        image = next(iter(make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world)))[0]
+        if rank == 0:
+            save_traversal(model, image.to(device), args.traverse, args.traverse_top, args.traverse_values)
+        return
     train_ds = ds
     if args.clip_frames:
         clip_chunks(args.clip_frames, arch.ITERS)                            # (refuse a frame count that does not split before any work)

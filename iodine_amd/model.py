@@ -153,6 +153,17 @@ class _Posterior(nn.Module):
 
 
 @dataclasses.dataclass
+class SceneEdit:
+    """What ``IODINE.edit`` returns: the renderings of E single-slot edits of one decoded scene.  ``pred (E, 3, S, S)``; ``mask (E, K, 1, S,
+    S)`` and ``mean (E, 3, S, S)`` - the sigmoid rgb of the slot-image put into the edited slot, of a removal that of the removed slot -
+    where asked for, else None; ``base`` = ``(pred, mask, mean)`` of the unedited ``decode(z)`` or None.  Detached tensors."""
+    pred: torch.Tensor
+    mask: Optional[torch.Tensor] = None
+    mean: Optional[torch.Tensor] = None
+    base: Optional[tuple] = None
+
+
+@dataclasses.dataclass
 class _RefineState:
     """(lambda_T, h, c) after the last encode / reconstruct, for ``IODINE.refinement_state``.  ``h`` / ``c`` are None while they
     are still in the library's workspace, which holds them until model call ``serial`` is followed by another; a chunked call that
@@ -1252,6 +1263,95 @@ class IODINE(nn.Module):
             if save:
                 self._saving(h, False)
         return self._own(pred), self._own(mask), self._own(mean)
+
+    @staticmethod
+    def _int_list(v, name, E=None):
+        """An int sequence or integer tensor of edits -> list of Python ints (host values: the library checks them before any launch)."""
+        if torch.is_tensor(v):
+            if v.dim() != 1 or v.is_floating_point() or v.is_complex() or v.dtype == torch.bool:
+                raise ValueError(f'IODINE.edit: {name} must be a 1-D integer tensor or a sequence of ints; got {v.dtype} of shape {tuple(v.shape)}')
+            v = v.detach().cpu().tolist()
+        else:
+            try:
+                v = list(v)
+            except TypeError:
+                raise ValueError(f'IODINE.edit: {name} must be a sequence of ints or a 1-D integer tensor; got {type(v).__name__}') from None
+            if any(isinstance(i, bool) or int(i) != i for i in v):
+                raise ValueError(f'IODINE.edit: {name} must hold integers; got {v!r}')
+            v = [int(i) for i in v]
+        if E is not None and len(v) != E:
+            raise ValueError(f'IODINE.edit: {name} has {len(v)} entries, but there are {E} edits (one entry per edit)')
+        return v
+
+    @torch.no_grad()
+    def edit(self, z, image, slot, z_new=None, remove=None, *, return_mask=False, return_mean=False, return_base=False):
+        """E renderings of the scene ``decode(z)`` that each differ from it in ONE slot: edit e replaces slot ``slot[e]`` of image
+        ``image[e]`` by the decode of ``z_new[e]``, or - where ``remove[e]`` - takes it out of the scene (the other K - 1 masks are
+        re-normalised, the removed slot's mask is exactly 0).  The base is decoded once and every replacement decodes one slot-image, B K + E
+        slot-image decodes where ``decode`` on the E edited scenes takes E K; a removal needs no decoder work at all.  A replace edit
+        returns the bits ``decode`` returns for the edited ``z``.
+
+        ``z`` (B, K, L) with 1 <= K <= 16, K taken from ``z`` as in ``decode``; ``image`` / ``slot``: int sequences or integer tensors of
+        length E; ``z_new`` (E, L), row e for edit e (rows of removals are not read; None is allowed when every edit is a removal);
+        ``remove``: E bools, default all False.  Returns a ``SceneEdit`` with ``pred (E, 3, S, S)`` and, on request, ``mask (E, K, 1, S, S)``,
+        ``mean (E, 3, S, S)`` = the rgb of the slot-image put into the edited slot, ``base`` = ``decode(z)`` as (pred, mask, mean).
+
+        NOT differentiable: the outputs are detached whatever ``z`` requires - gradients go through ``decode``.  One library call covers
+        any E (it runs in chunks of ``max_batch()`` images' worth of slot-images without decoding the base again) and counts as a decode
+        for the call order: a saved differentiable call is discarded, ``refinement_state()`` must be read before it."""
+        L = self.dim_latent
+        if not torch.is_tensor(z) or z.dim() != 3 or z.shape[2] != L or not 1 <= z.shape[1] <= 16 or z.shape[0] < 1:
+            raise ValueError(f'IODINE.edit: z must have shape (B, K, {L}) with B >= 1 and 1 <= K <= 16 (the per-pixel kernels are '
+                             f'instantiated for K <= 16); got {tuple(z.shape) if torch.is_tensor(z) else type(z).__name__}')
+        B, K = int(z.shape[0]), int(z.shape[1])
+        image = self._int_list(image, 'image')
+        E = len(image)
+        if E < 1:
+            raise ValueError('IODINE.edit: the edit list is empty (image has no entries)')
+        slot = self._int_list(slot, 'slot', E)
+        if remove is None:
+            remove = [False] * E
+        else:
+            remove = [bool(r) for r in (remove.detach().cpu().tolist() if torch.is_tensor(remove) else list(remove))]
+            if len(remove) != E:
+                raise ValueError(f'IODINE.edit: remove has {len(remove)} entries, but there are {E} edits (one entry per edit)')
+        for e in range(E):
+            if not 0 <= image[e] < B:
+                raise ValueError(f'IODINE.edit: edit {e}: image {image[e]} is outside 0..{B - 1} (z has shape {tuple(z.shape)})')
+            if not 0 <= slot[e] < K:
+                raise ValueError(f'IODINE.edit: edit {e}: slot {slot[e]} is outside 0..{K - 1} (z has shape {tuple(z.shape)})')
+            if remove[e] and K == 1:
+                raise ValueError(f'IODINE.edit: edit {e}: removes the only slot of image {image[e]} (z has K = 1: nothing would be left to render)')
+        n_rep = E - sum(remove)
+        if n_rep > 0 and (not torch.is_tensor(z_new) or tuple(z_new.shape) != (E, L)):
+            raise ValueError(f'IODINE.edit: z_new must have shape ({E}, {L}), one row per edit (rows of removals are not read); got '
+                             f'{tuple(z_new.shape) if torch.is_tensor(z_new) else type(z_new).__name__}')
+        if n_rep > 0 and z_new.device != z.device:
+            raise ValueError(f'IODINE.edit: z_new is on {z_new.device}, z on {z.device}')
+        T = self._shape[1] if self._shape is not None else int(self._cfg.iters)      # plays no part, as in decode
+        cap = self.max_batch(K=K, T=T)
+        if B > cap:
+            raise ValueError(f'IODINE.edit: z has {B} images, one call takes at most max_batch() = {cap} at K = {K}: edit the scenes in groups')
+        dev = z.device
+        z = z.detach().to(torch.float32).contiguous()
+        zn = z_new.detach().to(torch.float32).contiguous() if n_rep > 0 else None
+        W = min(cap, max(B, -(-n_rep // K)))
+        h = self._sync_params(dev)
+        if not hasattr(_lib.lib(), 'iodine_scene_edit'):
+            raise RuntimeError('IODINE.edit: this build of libiodine_hip.so has no iodine_scene_edit')
+        self._ensure_workspace(h, W, 0, dev, K, T)
+        S = self.img_size
+        f = dict(device=dev, dtype=torch.float32)
+        pred = torch.empty((E, 3, S, S), **f)
+        mask = torch.empty((E, K, 1, S, S), **f) if return_mask else None
+        mean = torch.empty((E, 3, S, S), **f) if return_mean else None
+        base = (torch.empty((B, 3, S, S), **f), torch.empty((B, K, 1, S, S), **f), torch.empty((B, K, 3, S, S), **f)) if return_base else (None,) * 3
+        arr = lambda v: (C.c_int * E)(*v)
+        self._call_serial += 1
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_scene_edit(
+            h, self._stream(), B, _lib.ptr(z), E, arr(image), arr(slot), arr([int(r) for r in remove]), _lib.ptr(zn), W,
+            _lib.ptr(pred), _lib.ptr(mask), _lib.ptr(mean), *[_lib.ptr(t) for t in base]), h, 'iodine_scene_edit'))
+        return SceneEdit(pred, mask, mean, base if return_base else None)
 
     _STALE = ('IODINE: backward of a stale {0} - the library keeps the saved state of ONE differentiable call and another forward / '
               'reconstruct / decode / elbo call has re-used it since, or it was differentiated already (the reference would hold a second '
