@@ -693,6 +693,24 @@ int iodine_op_render_bwd_logits(void* stream, const float* dec_out, const float*
 int iodine_op_pixel_maps(void* stream, const float* x_nchw, const float* w_or_null, const float* dec_out_nhwc4, int batch, int slots,
                          int pixels, float sigma, int strict, float coef, float* ll, float* kll, float* gx, float* gw, int first);
 
+/* the per-pixel mixture kernels of one ELBO evaluation (kernels_pixel.hip, pixel_terms.h; iodine.py:185-220, 277-340, 385-394) on a caller's
+ * decoder output, for kernel-level tests at any image size: the library's launchers in the library's order --
+ *   x_to_nhwc4 (w NULL = 1), { pixel_pass1, pixel_finalize_elbo } x repeat on ONE zero-initialised ticket counter (scal is set to NaN in
+ *   front of every launch but the first: a finalize that elects no last block shows), pixel_sigma_grad (if out[5]), pixel_pass2 (if out[6];
+ *   the split form if out[7]), final_out.
+ * x_nchw (batch,3,size^2), w (batch,size^2) or NULL, dec_out [batch * slots][size^2][4], pm / plv (batch,slots,latent), lin [size] (the
+ * coordinate table, iodine_linspace_host).  flags: bit 0 strict (as for iodine_op_render_bwd), bit 1 layer-norm statistics (0: lnstat = {0, 1}),
+ * bit 2 stable_encoding.  chmask: bit c = internal channel c of the encoding is written, an absent one is 0.  out[12]:
+ *   g [batch * slots][size^2][4] = d(B ELBO) / d dec_out, lnstat (batch,slots,8) = {mean, 1 / (sd + 1e-5)} of g_mean, g_mask, leave-one-out,
+ *   likelihood, ll_img [batch], img_terms (batch,2) = {ll, kl}, scal [3] = {elbo, kl, ll}                         -- required;
+ *   sgrad [1] = d LL / d sigma; enc [batch * slots][size^2][20] (split: [..][12]); enc_sh [batch][size^2][8];
+ *   pred (batch,3,size^2), mask (batch,slots,size^2), mean (batch,slots,3,size^2), logits (batch,slots,size^2)    -- each may be NULL.
+ * Allocates, synchronises and frees per call -- not for timing.  IODINE_ERR_INVALID, without a launch, for a bad argument: slots outside
+ * 1..16, size / batch / latent / repeat < 1, sigma <= 0, a required pointer NULL, enc_sh without enc, an index product >= 2^31. */
+int iodine_op_pixel_encode(void* stream, const float* x_nchw, const float* w_or_null, const float* dec_out_nhwc4, const float* pm, const float* plv,
+                           const float* lin, int batch, int slots, int size, int latent, float sigma, float beta, int flags, unsigned chmask,
+                           int repeat, float* const* out);
+
 /* ---- the refinement head, kernel-level tests only: each call allocates and frees its scratch around the launches and synchronises -- not
  * for timing.  IODINE_ERR_INVALID, without a launch, for arguments or shapes the requested form does not take (never another form). */
 

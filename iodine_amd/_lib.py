@@ -38,6 +38,7 @@ EXPORTS = (
     'iodine_op_sgemm', 'iodine_op_colsum', 'iodine_op_refine_head', 'iodine_op_refine_head_form', 'iodine_op_head_bptt', 'iodine_op_pool_bwd',
     'iodine_slot_table', 'iodine_seg_overlap',
     'iodine_scene_edit',
+    'iodine_op_pixel_encode',
 )
 
 
@@ -165,6 +166,8 @@ def lib() -> C.CDLL:
         L.iodine_seg_overlap.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
     if hasattr(L, 'iodine_scene_edit'):                 # (IODINE.edit, iodine_amd.traverse; absent from older A/B builds, which raise on them)
         L.iodine_scene_edit.argtypes = [vp, vp, ci, vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp, ci] + [vp] * 6
+    if hasattr(L, 'iodine_op_pixel_encode'):            # (kernel-level tests of the per-pixel mixture kernels; absent from older A/B builds)
+        L.iodine_op_pixel_encode.argtypes = [vp] * 7 + [ci] * 4 + [cf, cf, ci, C.c_uint, ci, C.POINTER(vp)]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

@@ -437,6 +437,51 @@ int iodine_op_pixel_maps(void* stream, const float* x_nchw, const float* w_or_nu
     return IODINE_OK;
 }
 
+// the per-pixel mixture kernels of one ELBO evaluation, kernel-level (tests/test_gpu_pixel.py): the production launchers in the order
+// elbo_and_gradients / refine_step / iodine_reconstruct run them.  (kernel-level tests only: allocates, synchronises and frees per call)
+int iodine_op_pixel_encode(void* stream, const float* x_nchw, const float* w_or_null, const float* dec_out_nhwc4, const float* pm, const float* plv,
+                           const float* lin, int batch, int slots, int size, int latent, float sigma, float beta, int flags, unsigned chmask,
+                           int repeat, float* const* out)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const size_t B = (size_t)(batch > 0 ? batch : 0), K = (size_t)(slots > 0 ? slots : 0), S = (size_t)(size > 0 ? size : 0), P = S * S;
+    bool ok = x_nchw && dec_out_nhwc4 && pm && plv && lin && out && batch >= 1 && slots >= 1 && slots <= 16 && size >= 1 && size <= 46340 &&
+              latent >= 1 && sigma > 0.f && repeat >= 1 && B * K * P * 20 < ((size_t)1 << 31) && B * K * (size_t)latent < ((size_t)1 << 31);
+    for (int j = 0; ok && j < 5; ++j) ok = out[j] != nullptr;              // (g, lnstat, ll_img, img_terms, scal: pass 1 and the finalize write them all)
+    if (ok && out[7] && !out[6]) ok = false;                               // (enc_sh belongs to the split form of enc)
+    if (!ok) {
+        g_create_error = "iodine_op_pixel_encode: argument (x, dec_out, pm, plv, lin and out[0..4] required; batch, size, latent, repeat >= 1; slots "
+                         "in 1..16; sigma > 0; enc_sh only with enc; batch * slots * size^2 * 20 and batch * slots * latent below 2^31)";
+        return IODINE_ERR_INVALID;
+    }
+    float *g = out[0], *lnstat = out[1], *ll_img = out[2], *img_terms = out[3], *scal = out[4], *sgrad = out[5], *enc = out[6], *enc_sh = out[7];
+    const int Pi = (int)P, strict = flags & 1, use_ln = (flags >> 1) & 1, stable = (flags >> 2) & 1;
+    const size_t nblk = (size_t)pixel_blocks_per_image(Pi);
+    // [x4: B P float4][part: B nblk (6 K + 3) doubles][sg_part: B nblk doubles][counter: one word, 16 bytes]
+    const size_t x4_bytes = B * P * 4 * sizeof(float), part_bytes = B * nblk * (6 * K + 3) * sizeof(double), sg_bytes = B * nblk * sizeof(double);
+    char* buf = nullptr;
+    if (hipMalloc((void**)&buf, x4_bytes + part_bytes + sg_bytes + 16) != hipSuccess) return IODINE_ERR_HIP;
+    float* x4 = (float*)buf;
+    double *part = (double*)(buf + x4_bytes), *sg_part = (double*)(buf + x4_bytes + part_bytes);
+    unsigned* counter = (unsigned*)(buf + x4_bytes + part_bytes + sg_bytes);
+    hipError_t e = hipMemsetAsync(counter, 0, 16, st);
+    if (e == hipSuccess) e = launch_x_to_nhwc4(st, x_nchw, x4, batch, Pi, 1, w_or_null, 0);
+    for (int r = 0; e == hipSuccess && r < repeat; ++r) {                  // (repeat > 1: the finalize finds the counter its last launch left)
+        // ... and scal as NaN: a launch whose ticket elects no last block would otherwise leave the previous launch's (equal) values
+        if (r > 0 && (e = hipMemsetAsync(scal, 0xff, 3 * sizeof(float), st)) != hipSuccess) break;
+        e = launch_pixel_pass1(st, x4, dec_out_nhwc4, g, part, batch, slots, Pi, sigma, strict);
+        if (e == hipSuccess)
+            e = launch_pixel_finalize_elbo(st, part, batch, slots, Pi, use_ln, lnstat, ll_img, pm, plv, latent, img_terms, scal, counter, beta);
+    }
+    if (e == hipSuccess && sgrad) e = launch_pixel_sigma_grad(st, x4, dec_out_nhwc4, sg_part, sgrad, batch, slots, Pi, (double)sigma, strict);
+    if (e == hipSuccess && enc) e = launch_pixel_pass2(st, x4, dec_out_nhwc4, lnstat, lin, enc, batch, slots, size, sigma, enc_sh, chmask, strict, stable);
+    if (e == hipSuccess) e = launch_final_out(st, dec_out_nhwc4, out[8], out[9], out[10], out[11], batch, slots, Pi);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_op_pixel_encode: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
 int iodine_op_conv3x3_wgrad_f32(void* stream, const float* in, const float* d, float* gw, float* gb, int n, int s, int c)
 {
     hipStream_t st = (hipStream_t)stream;
