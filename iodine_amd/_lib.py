@@ -145,7 +145,7 @@ def lib() -> C.CDLL:
         L.iodine_last_train_state.argtypes = [vp, vp, ci, vp, vp]
     if hasattr(L, 'iodine_set_pixel_weights'):          # (weights=; absent from older A/B builds, which refuse the keyword)
         L.iodine_set_pixel_weights.argtypes = [vp, vp, ci]
-    if hasattr(L, 'iodine_train_forward_frames'):       # (attach_frames=; absent from older A/B builds, which refuse the keyword)
+    if hasattr(L, 'iodine_train_forward_frames'):       # (the wrapper's one training forward / backward; older A/B builds without them cannot train)
         L.iodine_train_forward_frames.argtypes = [vp, vp, ci, vp, vp, C.POINTER(vp), vp, vp, C.POINTER(ci), ci, C.POINTER(vp)]
         L.iodine_train_backward_frames.argtypes = [vp, vp] + [vp] * 10 + [ci, C.POINTER(vp), C.POINTER(ci), ci, C.POINTER(vp)]
     if hasattr(L, 'iodine_last_sigma_grad'):            # (a sigma that requires grad; absent from older A/B builds, which raise on one)

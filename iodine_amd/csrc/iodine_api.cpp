@@ -2323,6 +2323,27 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
     return rc;
 }
 
+// The entries that write one flat gradient buffer.  ``entry``: 0 iodine_train_backward_flat, 1 _aux, 2 _seq, 3 _frames - the arguments it
+// does not have are NULL in ``aux``.  NULL / 0 arguments narrow a call frames -> seq -> aux -> flat, to the narrower entry itself, launch for
+// launch: no chosen evaluation or no cotangent on any of them; nothing that crosses the ends of the saved forward; no auxiliary cotangent.
+static int train_backward_flat(iodine_handle* h, void* stream, int entry, AuxCot aux, float* flat_grads, int accumulate)
+{
+    static const char* const who[4] = {"iodine_train_backward_flat", "iodine_train_backward_aux", "iodine_train_backward_seq", "iodine_train_backward_frames"};
+    if (!h) return IODINE_ERR_INVALID;
+    if (entry == 3) {
+        const float* const* g = aux.frames->g;
+        if (aux.frames->n == 0 || !(g[0] || g[1] || g[2] || g[3] || g[4] || g[5])) { entry = 2; aux.frames = nullptr; }
+    }
+    if (entry == 2 && !aux.lstm_h && !aux.lstm_c && !aux.g_state) entry = 1;
+    if (entry == 1 && flat_grads && aux.gl && !aux.mean && !aux.mask && !aux.logits && !aux.z && !aux.pm && !aux.plv) entry = 0;
+    if (!flat_grads) return h->fail(IODINE_ERR_INVALID, std::string(who[entry]) + ": flat_grads is required");
+    std::vector<float*> ptrs(h->params.size());
+    size_t off = 0;                                            // parameters back to back in named_parameters() order (= the gacc layout)
+    for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
+    // (the loss cotangent: the plain backward scales its output by grad_scale_dev, with auxiliary cotangents it is aux.gl)
+    return train_backward_impl(h, stream, 1.f, entry == 0 ? aux.gl : nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, entry == 0 ? nullptr : &aux);
+}
+
 extern "C" {
 
 int iodine_train_backward(iodine_handle* h, void* stream, float grad_scale, float* const* param_grads, int n)
@@ -2332,44 +2353,22 @@ int iodine_train_backward(iodine_handle* h, void* stream, float grad_scale, floa
 
 int iodine_train_backward_flat(iodine_handle* h, void* stream, const float* grad_loss_dev, float* flat_grads, int accumulate)
 {
-    if (!h) return IODINE_ERR_INVALID;
-    if (!flat_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward_flat: flat_grads is required");
-    std::vector<float*> ptrs(h->params.size());
-    size_t off = 0;                                            // parameters back to back in named_parameters() order (= the gacc layout)
-    for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
-    return train_backward_impl(h, stream, 1.f, grad_loss_dev, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0);
+    return train_backward_flat(h, stream, 0, AuxCot{grad_loss_dev}, flat_grads, accumulate);
 }
 
 int iodine_train_backward_aux(iodine_handle* h, void* stream, const float* grad_loss_dev, const float* g_mean, const float* g_mask,
                               const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
                               float* flat_grads, int accumulate)
 {
-    if (!h) return IODINE_ERR_INVALID;
-    if (!flat_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward_aux: flat_grads is required");
-    // no auxiliary cotangent: the plain backward itself, launch for launch
-    if (grad_loss_dev && !g_mean && !g_mask && !g_logits && !g_z && !g_post_mean && !g_post_logvar)
-        return iodine_train_backward_flat(h, stream, grad_loss_dev, flat_grads, accumulate);
-    std::vector<float*> ptrs(h->params.size());
-    size_t off = 0;
-    for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
-    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, nullptr, nullptr, nullptr, nullptr};
-    return train_backward_impl(h, stream, 1.f, nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, &aux);
+    return train_backward_flat(h, stream, 1, AuxCot{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar}, flat_grads, accumulate);
 }
 
 int iodine_train_backward_seq(iodine_handle* h, void* stream, const float* grad_loss_dev, const float* g_mean, const float* g_mask,
                               const float* g_logits, const float* g_z, const float* g_post_mean, const float* g_post_logvar,
                               const float* g_lstm_h, const float* g_lstm_c, float* flat_grads, int accumulate, float* const* g_state)
 {
-    if (!h) return IODINE_ERR_INVALID;
-    // nothing crosses the ends of the saved forward: the backward with auxiliary cotangents itself, launch for launch
-    if (!g_lstm_h && !g_lstm_c && !g_state)
-        return iodine_train_backward_aux(h, stream, grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, flat_grads, accumulate);
-    if (!flat_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward_seq: flat_grads is required");
-    std::vector<float*> ptrs(h->params.size());
-    size_t off = 0;
-    for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
-    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c, g_state, nullptr};
-    return train_backward_impl(h, stream, 1.f, nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, &aux);
+    return train_backward_flat(h, stream, 2, AuxCot{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c, g_state},
+                               flat_grads, accumulate);
 }
 
 int iodine_train_backward_frames(iodine_handle* h, void* stream, const float* grad_loss_dev, const float* g_mean, const float* g_mask,
@@ -2383,17 +2382,9 @@ int iodine_train_backward_frames(iodine_handle* h, void* stream, const float* gr
         if (shaped != h) h->err = shaped->err;
         return rc;
     }
-    // no chosen evaluation, or no cotangent on any of them: iodine_train_backward_seq itself, launch for launch
-    if (n_frames == 0 || !(g_frames[0] || g_frames[1] || g_frames[2] || g_frames[3] || g_frames[4] || g_frames[5]))
-        return iodine_train_backward_seq(h, stream, grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c,
-                                         flat_grads, accumulate, g_state);
-    if (!flat_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward_frames: flat_grads is required");
-    std::vector<float*> ptrs(h->params.size());
-    size_t off = 0;
-    for (size_t p = 0; p < h->params.size(); ++p) { ptrs[p] = flat_grads + off; off += h->params[p].numel(); }
     FrameSet fr; fr.idx = frame_idx; fr.n = n_frames; fr.g = g_frames;
-    const AuxCot aux{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c, g_state, &fr};
-    return train_backward_impl(h, stream, 1.f, nullptr, ptrs.data(), (int)ptrs.size(), accumulate ? 1 : 0, &aux);
+    return train_backward_flat(h, stream, 3, AuxCot{grad_loss_dev, g_mean, g_mask, g_logits, g_z, g_post_mean, g_post_logvar, g_lstm_h, g_lstm_c, g_state, &fr},
+                               flat_grads, accumulate);
 }
 
 int iodine_logger_scalars(iodine_handle* h, void* stream, float* out2)

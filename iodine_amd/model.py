@@ -235,99 +235,35 @@ def _ig_grads(ctx, g, sign):
     return gx, gw
 
 
+_FRAME_KEYS = ('z', 'mean', 'mask', 'mask_logits', 'post_mean', 'post_logvar')     # the order of the library's six pointers
+_ALL, _FROM_STATE = ('',), ('refine.', 'decoder.')    # ``live`` of _flat_views: every parameter / those of a forward from a state
+
+
 class _TrainStep(torch.autograd.Function):
-    """``loss = model(x)`` / ``loss.backward()`` through iodine_train_forward / iodine_train_backward."""
+    """``loss = model(x)`` / ``loss.backward()`` through iodine_train_forward_frames / iodine_train_backward_frames, the node of every
+    un-chunked ``forward``.  Outputs: the loss and the ELBO terms; with ``attach`` (``attach_state=True``) also what the forward's final
+    ``elbo()`` leaves on the reference's module - z, mean, mask, mask_logits, posterior.mean / .logvar and the LSTM state ``lstm_hidden``,
+    there still attached to the graph (iodine.py:37,137,144,171-187,642-651); with ``index`` (``attach_frames``, a tuple of evaluations)
+    also what those evaluations decoded - z, mean, mask, mask_logits and the lambda they sampled from, each (F, B, K, ...).  So one
+    ``backward()`` of any combination of them is ONE library call.  The four state tensors (``state=``; None: a forward from the initial
+    posterior) receive the gradient the chunk hands back when they require grad."""
 
     @staticmethod
-    def forward(ctx, module, x, eps, w, *params):
-        params, sigma = _split_sigma(module, params)
-        x, w, ig = _ig_inputs(ctx, module, x, w)
-        loss, elbo_iter, *sg = module._train_forward(x, eps, weights=w, sigma_grad=sigma is not None, input_grad=ig)
-        _sigma_keep(ctx, sigma, sg[0] if sg else None)
-        _ig_keep(ctx, module, ig)
-        ctx.module = module
-        ctx.serial = module._call_serial            # identity of the saved forward (the library keeps exactly one)
-        ctx.n = len(params)
-        ctx.mark_non_differentiable(elbo_iter)
-        return loss, elbo_iter
-
-    @staticmethod
-    def backward(ctx, grad_loss, _grad_elbo):
-        grads = ctx.module._train_backward(grad_loss, ctx.serial)
-        gx, gw = _ig_grads(ctx, grad_loss, -1.0)
-        return (None, gx, None, gw, *grads, *_sigma_tail(ctx, grad_loss, -1.0))
-
-
-class _TrainStepAttached(torch.autograd.Function):
-    """``forward(x, attach_state=True)``: the loss AND what the forward's final ``elbo()`` leaves on the reference's module - z, mean, mask,
-    mask_logits, posterior.mean / .logvar and the LSTM state ``lstm_hidden``, there still attached to the graph (iodine.py:37,137,144,
-    171-187,642-651) - as outputs of ONE node, so a single ``backward()`` of any combination of them goes through
-    iodine_train_backward_aux / iodine_train_backward_seq.  Also the node of every ``forward(x, state=...)``: the four state tensors are its
-    inputs (None: a forward from the initial posterior, the same library calls as the plain step) and receive the gradient the chunk hands
-    back when they require grad; ``attach`` False: loss and ELBO terms are the only outputs."""
-
-    @staticmethod
-    def forward(ctx, module, x, eps, w, attach, s_pm, s_plv, s_h, s_c, *params):
+    def forward(ctx, module, x, eps, w, attach, index, s_pm, s_plv, s_h, s_c, *params):
         ctx.set_materialize_grads(False)                   # an output the loss does not use arrives as None -> a NULL pointer
         state = None if s_pm is None else (s_pm, s_plv, s_h, s_c)
         params, sigma = _split_sigma(module, params)
         x, w, ig = _ig_inputs(ctx, module, x, w)
-        loss, elbo_iter, *sg = module._train_forward(x, eps, state, weights=w, sigma_grad=sigma is not None, input_grad=ig)
-        _sigma_keep(ctx, sigma, sg[0] if sg else None)
+        loss, elbo_iter, frames, sg = module._train_forward(x, eps, state, weights=w, frames=index, sigma_grad=sigma is not None, input_grad=ig)
+        _sigma_keep(ctx, sigma, sg)
         _ig_keep(ctx, module, ig)
-        ctx.module, ctx.serial, ctx.from_state = module, module._call_serial, state is not None
-        ctx.BK = (x.shape[0], module.K)
-        ctx.mark_non_differentiable(elbo_iter)
-        if not attach:
-            return loss, elbo_iter
-        module._fetch_last_elbo(module._handle, x, elbo_iter[-1])      # (grad mode is off in here: the logger entries stay detached)
-        module._fetch_posterior(module._handle, x.shape[0], x.device)
-        h, c = module._fetch_train_state(x.shape[0], x.device)
-        H = h.shape[-1]
-        return (loss, elbo_iter, module.z, module.mean, module.mask, module.mask_logits, module.posterior.mean, module.posterior.logvar,
-                h.view(-1, H), c.view(-1, H))
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_elbo, g_z=None, g_mean=None, g_mask=None, g_logits=None, g_pm=None, g_plv=None, g_h=None, g_c=None):
-        aux = (g_mean, g_mask, g_logits, g_z, g_pm, g_plv)
-        n_in = len(ctx.needs_input_grad)
-        if g_loss is None and all(g is None for g in aux) and g_h is None and g_c is None:
-            return (None,) * n_in
-        want = tuple(ctx.from_state and ctx.needs_input_grad[5 + j] for j in range(4))
-        if g_h is None and g_c is None and not any(want):
-            gstate = (None,) * 4
-            grads = ctx.module._train_backward(g_loss, ctx.serial, aux)
-        else:
-            grads, gstate = ctx.module._train_backward_seq(g_loss, ctx.serial, aux, (g_h, g_c), want, ctx.BK)
-        if ctx.from_state:                                 # the initial posterior is not part of a forward from a state: unused parameters
-            grads = [None if n.startswith('posterior.') else g for (n, _), g in zip(ctx.module.named_parameters(), grads)]
-        gx, gw = _ig_grads(ctx, g_loss, -1.0)
-        return (None, gx, None, gw, None, *gstate, *grads, *_sigma_tail(ctx, g_loss, -1.0))
-
-
-_FRAME_KEYS = ('z', 'mean', 'mask', 'mask_logits', 'post_mean', 'post_logvar')     # the order of the library's six pointers
-
-
-class _TrainStepFrames(torch.autograd.Function):
-    """``forward(x, attach_frames=...)``: the node of ``_TrainStepAttached`` with six more outputs, what the chosen ELBO evaluations
-    decoded - z, mean, mask, mask_logits and the lambda they sampled from, each (F, B, K, ...) - so one ``backward()`` of the loss, of
-    terms on the final state (``attach`` True) and of terms on any listed evaluation goes through iodine_train_backward_frames."""
-
-    @staticmethod
-    def forward(ctx, module, x, eps, w, attach, index, s_pm, s_plv, s_h, s_c, *params):
-        ctx.set_materialize_grads(False)                   # an unused kind arrives as None -> a NULL pointer
-        state = None if s_pm is None else (s_pm, s_plv, s_h, s_c)
-        params, sigma = _split_sigma(module, params)
-        x, w, ig = _ig_inputs(ctx, module, x, w)
-        loss, elbo_iter, frames, *sg = module._train_forward(x, eps, state, weights=w, frames=index, sigma_grad=sigma is not None, input_grad=ig)
-        _sigma_keep(ctx, sigma, sg[0] if sg else None)
-        _ig_keep(ctx, module, ig)
-        ctx.module, ctx.serial, ctx.from_state = module, module._call_serial, state is not None
+        ctx.module, ctx.from_state = module, state is not None
+        ctx.serial = module._call_serial                   # identity of the saved forward (the library keeps exactly one)
         ctx.BK, ctx.attach, ctx.index = (x.shape[0], module.K), attach, index
         ctx.mark_non_differentiable(elbo_iter)
         if not attach:
             return (loss, elbo_iter, *frames)
-        module._fetch_last_elbo(module._handle, x, elbo_iter[-1])
+        module._fetch_last_elbo(module._handle, x, elbo_iter[-1])      # (grad mode is off in here: the logger entries stay detached)
         module._fetch_posterior(module._handle, x.shape[0], x.device)
         h, c = module._fetch_train_state(x.shape[0], x.device)
         H = h.shape[-1]
@@ -336,17 +272,15 @@ class _TrainStepFrames(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _g_elbo, *gs):
-        g_z, g_mean, g_mask, g_logits, g_pm, g_plv, g_h, g_c = gs[:8] if ctx.attach else (None,) * 8
-        gf = tuple(gs[8:14] if ctx.attach else gs[:6])
-        aux = (g_mean, g_mask, g_logits, g_z, g_pm, g_plv)
-        n_in = len(ctx.needs_input_grad)
-        if g_loss is None and all(g is None for g in aux + gf) and g_h is None and g_c is None:
-            return (None,) * n_in
+        n = 8 if ctx.attach else 0
+        g_z, g_mean, g_mask, g_logits, g_pm, g_plv, g_h, g_c = gs[:n] or (None,) * 8
+        cot, gf = (g_mean, g_mask, g_logits, g_z, g_pm, g_plv, g_h, g_c), gs[n:] or (None,) * 6
+        if g_loss is None and all(g is None for g in cot + gf):
+            return (None,) * len(ctx.needs_input_grad)
         want = tuple(ctx.from_state and ctx.needs_input_grad[6 + j] for j in range(4))
-        grads, gstate = ctx.module._train_backward_seq(g_loss, ctx.serial, aux, (g_h, g_c), want, ctx.BK,
-                                                       frames=(ctx.index, gf) if any(g is not None for g in gf) else None)
-        if ctx.from_state:                                 # the initial posterior is not part of a forward from a state: unused parameters
-            grads = [None if n.startswith('posterior.') else g for (n, _), g in zip(ctx.module.named_parameters(), grads)]
+        flat, gstate = ctx.module._train_backward(g_loss, ctx.serial, cot, want, ctx.BK, ctx.index, gf)
+        # (the initial posterior is not part of a forward from a state: unused parameters)
+        grads = _flat_views(ctx.module, flat, _FROM_STATE if ctx.from_state else _ALL)
         gx, gw = _ig_grads(ctx, g_loss, -1.0)
         return (None, gx, None, gw, None, None, *gstate, *grads, *_sigma_tail(ctx, g_loss, -1.0))
 
@@ -372,12 +306,8 @@ class _ChunkedTrainStep(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss, _grad_elbo):
-        flat = ctx.flat * grad_loss.to(ctx.flat.dtype)
-        views, off = [], 0
-        for n, p in ctx.module.named_parameters():
-            # (from a detached state the initial posterior is not part of the forward: None, like unused parameters elsewhere)
-            views.append(None if ctx.from_state and n.startswith('posterior.') else flat[off:off + p.numel()].view_as(p))
-            off += p.numel()
+        # (from a detached state the initial posterior is not part of the forward: None, like unused parameters elsewhere)
+        views = _flat_views(ctx.module, ctx.flat * grad_loss.to(ctx.flat.dtype), _FROM_STATE if ctx.from_state else _ALL)
         gx, gw = _ig_grads(ctx, grad_loss, -1.0)
         return (None, gx, None, gw, None, None, *views, *_sigma_tail(ctx, grad_loss, -1.0))
 
@@ -1616,39 +1546,35 @@ class IODINE(nn.Module):
             self.elbo_terms = elbo_iter
             return loss
         eps = self._eps(eps, B, x.device)
-        loss, elbo_iter = self._apply_train_step(xi, eps, wi, attach, index, state, sg)
-        self.elbo_terms = elbo_iter
-        with torch.no_grad():
-            h, dev = self._handle, x.device
-            if not attach:
-                self._fetch_last_elbo(h, x, elbo_iter[-1])                             # final elbo(): iodine.py:226-239 (a clip: its last frame)
-                self._fetch_posterior(h, B, dev)
-            if keep_state:
-                hc = (t.detach().view(B, K, -1) for t in self.lstm_hidden) if attach else self._fetch_train_state(B, dev)
-                self._state = _RefineState(self.posterior.mean.detach(), self.posterior.logvar.detach(), *hc)
-            stats = torch.empty((2,), device=dev, dtype=torch.float32)
-            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_logger_scalars(h, self._stream(), _lib.ptr(stats)), h))
-            logger.update(init_mean=stats[0], init_logvar=stats[1])                    # iodine.py:156-157
+        out = _TrainStep.apply(self, xi, eps, wi, attach, index, *(state or (None,) * 4), *self._ordered_params(), *sg)
+        loss, self.elbo_terms = out[:2]
+        if attach:
+            self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc = out[2:10]
+            self.lstm_hidden = (lh, lc)
+        if index is not None:
+            self.frames = dict(index=index, **dict(zip(_FRAME_KEYS, out[-6:])))
+        hc = self._train_tail(x, self.elbo_terms, attach, keep_state)
+        if keep_state:
+            self._state = _RefineState(self.posterior.mean.detach(), self.posterior.logvar.detach(), *hc)
         return loss
 
-    def _apply_train_step(self, x, eps, weights, attach, index, state, sg):
-        """The autograd node of one un-chunked ``forward`` (sg: ``_sigma_input()``, the trailing input) -> (loss, ELBO terms)"""
-        if index is not None:
-            out = _TrainStepFrames.apply(self, x, eps, weights, attach, index, *(state or (None,) * 4), *self._ordered_params(), *sg)
-            loss, elbo_iter = out[:2]
-            if attach:
-                self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc = out[2:10]
-                self.lstm_hidden = (lh, lc)
-            self.frames = dict(index=index, **dict(zip(_FRAME_KEYS, out[-6:])))
-        elif attach:
-            (loss, elbo_iter, self.z, self.mean, self.mask, self.mask_logits, self.posterior.mean, self.posterior.logvar, lh, lc
-             ) = _TrainStepAttached.apply(self, x, eps, weights, True, *(state or (None,) * 4), *self._ordered_params(), *sg)
-            self.lstm_hidden = (lh, lc)
-        elif state is not None:
-            loss, elbo_iter = _TrainStepAttached.apply(self, x, eps, weights, False, *state, *self._ordered_params(), *sg)
-        else:
-            loss, elbo_iter = _TrainStep.apply(self, x, eps, weights, *self._ordered_params(), *sg)
-        return loss, elbo_iter
+    @torch.no_grad()
+    def _train_tail(self, x, terms, attach=False, keep_state=False, scalars=True):
+        """What a training forward leaves behind its library call: the state and logger entries of its final elbo() (iodine.py:226-239; a
+        clip: its last frame) and lambda_T unless the node attached them (``attach``), the logger scalars of iodine.py:156-157
+        (``scalars``) and, returned with ``keep_state``, the LSTM state (h, c) (B, K, MLP_UNITS)."""
+        h, dev, B = self._handle, x.device, x.shape[0]
+        hc = None
+        if not attach:
+            self._fetch_last_elbo(h, x, terms[-1])
+            self._fetch_posterior(h, B, dev)
+        if keep_state:
+            hc = tuple(t.detach().view(B, self.K, -1) for t in self.lstm_hidden) if attach else self._fetch_train_state(B, dev)
+        if scalars:
+            stats = torch.empty((2,), device=dev, dtype=torch.float32)
+            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_logger_scalars(h, self._stream(), _lib.ptr(stats)), h))
+            logger.update(init_mean=stats[0], init_logvar=stats[1])
+        return hc
 
     def _fetch_train_state(self, B, dev):
         """(h, c) (B, K, MLP_UNITS) after the last update of the training forward that just ran (iodine_last_train_state)."""
@@ -1660,9 +1586,10 @@ class IODINE(nn.Module):
         return hh, cc
 
     def _train_forward(self, x, eps, state=None, weights=None, frames=None, sigma_grad=False, input_grad=0):
-        """-> (loss, ELBO terms); with ``frames`` (a tuple of evaluation indices, possibly empty) also the six (F, B, K, ...) tensors of
-        those evaluations in the order of ``_FRAME_KEYS`` (iodine_train_forward_frames); with ``sigma_grad`` also, last, the device scalar
-        sum_e w_e dLL_e/dsigma (the forward then runs with option sigma_grad)."""
+        """iodine_train_forward_frames -> (loss, ELBO terms, frames, S).  ``state``: None or the initial (post_mean, post_logvar, h, c);
+        ``frames``: None -> (), or a tuple of evaluation indices, possibly empty -> the six (F, B, K, ...) tensors of those evaluations in
+        the order of ``_FRAME_KEYS``; S: with ``sigma_grad`` the device scalar sum_e w_e dLL_e/dsigma (the forward then runs with option
+        sigma_grad), else None.  NULL / 0 for what is not asked for: the library then runs the plain forward, launch for launch."""
         dev, B = x.device, x.shape[0]
         K, T = self._run_shape()
         obj = self._read_objective(T)
@@ -1670,38 +1597,29 @@ class IODINE(nn.Module):
         self._ensure_input_grad(h, input_grad)
         self._ensure_workspace(h, B, 1, dev, K, T, x.shape[1] if x.dim() == 5 else 0)
         self._ensure_objective(h, obj, dev, sigma_grad)
-
-        def sg():                                           # (what is read back once after the call, in stream order)
-            self._last_ig = self._fetch_input_grad(h, dev, x, weights, input_grad) if input_grad else None
-            return (self._fetch_sigma_grad(h, dev, T + 1, obj[2]),) if sigma_grad else ()
         loss = self._out('t.loss', (), dev)
         elbo_iter = self._out('t.elbo', (T + 1, 3), dev)
         xs, eps = self._stage('x', x), self._stage('eps', eps)
         self._call_serial += 1
         ws = self._send_weights(h, weights)                 # (ws: alive until the call is queued)
+        outs, sptrs, optrs, idx, F = (), None, None, None, len(frames or ())
         if frames is not None:
-            F, L, S = len(frames), self.dim_latent, self.img_size
+            L, S = self.dim_latent, self.img_size
             shapes = ((F, B, K, L), (F, B, K, 3, S, S), (F, B, K, 1, S, S), (F, B, K, 1, S, S), (F, B, K, L), (F, B, K, L))
             outs = [self._out('tf.' + n, shp, dev) for n, shp in zip(_FRAME_KEYS, shapes)]
-            st = None if state is None else [self._stage('ts.' + n, t.detach()) for n, t in zip(('pm', 'plv', 'h', 'c'), state)]
-            sptrs = None if st is None else (C.c_void_p * 4)(*[t.data_ptr() for t in st])
-            optrs = (C.c_void_p * 6)(*[t.data_ptr() if F else None for t in outs])
-            idx = (C.c_int * max(F, 1))(*frames)
-            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward_frames(
-                h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), sptrs, _lib.ptr(loss), _lib.ptr(elbo_iter), idx, F, optrs),
-                h, 'iodine_train_forward_frames'))
-            return (self._own(loss), self._own(elbo_iter), tuple(self._own(t) for t in outs), *sg())
-        if state is None:
-            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward(h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps),
-                                                                                 _lib.ptr(loss), _lib.ptr(elbo_iter)),
-                                                 h, 'iodine_train_forward'))
-        else:
+        if F:
+            optrs, idx = (C.c_void_p * 6)(*[t.data_ptr() for t in outs]), (C.c_int * F)(*frames)
+        if state is not None:
             # (graph mode: the state goes through persistent staging buffers like reconstruct's, so the graph key repeats)
             st = [self._stage('ts.' + n, t.detach()) for n, t in zip(('pm', 'plv', 'h', 'c'), state)]
-            ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in st])
-            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward_seq(
-                h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), ptrs, _lib.ptr(loss), _lib.ptr(elbo_iter)), h, 'iodine_train_forward_seq'))
-        return (self._own(loss), self._own(elbo_iter), *sg())
+            sptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in st])
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_forward_frames(
+            h, self._stream(), B, _lib.ptr(xs), _lib.ptr(eps), sptrs, _lib.ptr(loss), _lib.ptr(elbo_iter), idx, F, optrs),
+            h, 'iodine_train_forward_frames'))
+        out = (self._own(loss), self._own(elbo_iter), tuple(self._own(t) for t in outs))
+        # (what is read back once after the call, in stream order)
+        self._last_ig = self._fetch_input_grad(h, dev, x, weights, input_grad) if input_grad else None
+        return (*out, self._fetch_sigma_grad(h, dev, T + 1, obj[2]) if sigma_grad else None)
 
     def _train_chunked(self, x, eps, state=None, keep_state=False, weights=None, sigma_grad=False, input_grad=0):
         """Forward + backward of every chunk (see _ChunkedTrainStep): returns the batch loss, the (T+1, 3) ELBO terms of the whole
@@ -1714,30 +1632,24 @@ class IODINE(nn.Module):
         for c, (s, e) in enumerate(self._chunks(B, self.max_batch(training=True))):
             xc = x[s:e].contiguous()
             ec = self._eps(None if eps is None else eps[:, s:e], e - s, dev)
-            lc, tc, *sc = self._train_forward(xc, ec, None if state is None else tuple(t[s:e].contiguous() for t in state),
-                                              None if weights is None else weights[s:e].contiguous(), sigma_grad=sigma_grad,
-                                              input_grad=input_grad)
+            lc, tc, _, sc = self._train_forward(xc, ec, None if state is None else tuple(t[s:e].contiguous() for t in state),
+                                                None if weights is None else weights[s:e].contiguous(), sigma_grad=sigma_grad,
+                                                input_grad=input_grad)
             h = self._handle
             w = torch.full((), (e - s) / float(B), device=dev, dtype=torch.float32)
             if input_grad:                              # this chunk's share of the batch mean
                 igs.append(tuple(None if t is None else t * w for t in self._last_ig))
             ws = self._stage('t.gl', w)
-            if sc:                                      # this chunk's share of the batch mean
-                sig = sc[0] * w if sig is None else sig + sc[0] * w
+            if sc is not None:                          # this chunk's share of the batch mean
+                sig = sc * w if sig is None else sig + sc * w
             self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_flat(h, self._stream(), _lib.ptr(ws), _lib.ptr(flat),
                                                                                        1 if c else 0), h, 'iodine_train_backward'))
-            with torch.no_grad():
-                self._fetch_last_elbo(h, xc, tc[-1])
-                self._fetch_posterior(h, e - s, dev)
-                pms.append(self.posterior.mean); plvs.append(self.posterior.logvar)
-                if keep_state:
-                    hcs.append(self._fetch_train_state(e - s, dev))
-                self.elbo_terms = tc
-                parts.append(self._chunk_state()); sizes.append(e - s)
-                if c == 0:
-                    stats = torch.empty((2,), device=dev, dtype=torch.float32)
-                    self._launch(dev, lambda: _lib.check(_lib.lib().iodine_logger_scalars(h, self._stream(), _lib.ptr(stats)), h))
-                    logger.update(init_mean=stats[0], init_logvar=stats[1])
+            hc = self._train_tail(xc, tc, keep_state=keep_state, scalars=c == 0)
+            pms.append(self.posterior.mean); plvs.append(self.posterior.logvar)
+            if keep_state:
+                hcs.append(hc)
+            self.elbo_terms = tc
+            parts.append(self._chunk_state()); sizes.append(e - s)
             self._call_serial += 1                  # this chunk's saved forward is consumed
             loss = lc * w if loss is None else loss + lc * w
         with torch.no_grad():
@@ -1749,73 +1661,37 @@ class IODINE(nn.Module):
         self._last_ig = tuple(None if igs[0][j] is None else torch.cat([g[j] for g in igs], 0) for j in range(2)) if input_grad else None
         return loss, self.elbo_terms, self._own(flat), sig
 
-    def _train_backward(self, grad_loss, serial, aux=None):
-        """``aux``: None, or the cotangents (mean, mask, mask_logits, z, posterior.mean, posterior.logvar) of an attached forward, each a
-        tensor or None - then ``grad_loss`` may be None too (iodine_train_backward_aux)."""
-        if serial != self._call_serial:
-            raise RuntimeError('IODINE: backward of a stale forward - the library keeps the saved state of ONE forward pass and '
-                               'another forward / reconstruct / decode / elbo call has re-used it since (the reference would '
-                               'hold a second autograd graph; call loss.backward() before the next model call)')
-        h, dev = self._handle, self._handle_device
-        params = self._ordered_params()
-        sizes = [p.numel() for p in params]
-        flat = self._out('t.flat', (sum(sizes),), dev)
-        as_f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        gl = None if grad_loss is None else self._stage('t.gl', as_f32(grad_loss))
-        if aux is None:
-            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_flat(h, self._stream(), _lib.ptr(gl), _lib.ptr(flat), 0),
-                                                 h, 'iodine_train_backward'))
-        else:
-            # (graph mode: the cotangents go through persistent staging buffers like every other tensor, so the graph key repeats)
-            names = ('a.mean', 'a.mask', 'a.logits', 'a.z', 'a.pm', 'a.plv')
-            cs = [None if g is None else self._stage(n, as_f32(g)) for n, g in zip(names, aux)]
-            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_aux(
-                h, self._stream(), _lib.ptr(gl), *[_lib.ptr(c) for c in cs], _lib.ptr(flat), 0), h, 'iodine_train_backward_aux'))
-        self._call_serial += 1                      # the saved forward is consumed (no retain_graph)
-        flat = self._own(flat)                      # graph mode: autograd may keep what we return as .grad; never the staging buffer
-        views, off = [], 0
-        for p, n in zip(params, sizes):
-            views.append(flat[off:off + n].view_as(p))
-            off += n
-        return views
-
-    def _train_backward_seq(self, grad_loss, serial, aux, hc, want, BK, frames=None):
-        """iodine_train_backward_seq for the saved forward ``serial``: ``aux`` as for ``_train_backward``, ``hc`` = cotangents on the LSTM
-        state after the last update ((B * K, H) or None each), ``want`` = which of d / d (post_mean, post_logvar, h, c) of the initial
-        state to return.  ``frames``: None, or (evaluation indices, the six cotangents (F, B, K, ...) in the order of ``_FRAME_KEYS``, None
-        each) - iodine_train_backward_frames.  -> (per-parameter views, the four state gradients or None each)."""
+    def _train_backward(self, grad_loss, serial, cot, want, BK, index, gf):
+        """iodine_train_backward_frames for the saved forward ``serial`` -> (d loss / d parameters as one flat buffer, the four state
+        gradients or None each).  ``cot``: the cotangents (mean, mask, mask_logits, z, posterior.mean, posterior.logvar) on the final
+        elbo() of an attached forward and (h, c) (B * K, H) on the LSTM state after the last update; ``gf``: the six cotangents
+        (F, B, K, ...) on the evaluations ``index`` in the order of ``_FRAME_KEYS``; each a tensor or None, ``grad_loss`` too.  ``want``:
+        which of d / d (post_mean, post_logvar, h, c) of the initial state to return.  NULL / 0 for what is not asked for: the library
+        then runs the narrower backward - without any of it the plain one -, launch for launch."""
         if serial != self._call_serial:
             raise RuntimeError(self._STALE.format('forward'))
         h, dev = self._handle, self._handle_device
-        B, K = BK
-        L, H = self.dim_latent, int(self._cfg.ref_mlp_units)
-        params = self._ordered_params()
-        flat = self._out('t.flat', (sum(p.numel() for p in params),), dev)
-        as_f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        gl = None if grad_loss is None else self._stage('t.gl', as_f32(grad_loss))
-        names = ('a.mean', 'a.mask', 'a.logits', 'a.z', 'a.pm', 'a.plv', 'a.h', 'a.c')
-        cs = [None if g is None else self._stage(n, as_f32(g)) for n, g in zip(names, tuple(aux) + tuple(hc))]
-        outs = [self._out('ts.g' + n, shp, dev) if w else None
-                for n, shp, w in zip(('pm', 'plv', 'h', 'c'), ((B, K, L), (B, K, L), (B, K, H), (B, K, H)), want)]
-        gptrs = (C.c_void_p * 4)(*[None if t is None else t.data_ptr() for t in outs]) if any(want) else None
-        if frames is None:
-            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_seq(
-                h, self._stream(), _lib.ptr(gl), *[_lib.ptr(c) for c in cs], _lib.ptr(flat), 0, gptrs), h, 'iodine_train_backward_seq'))
-        else:
-            index, gf = frames
-            fs = [None if g is None else self._stage('f.' + n, as_f32(g)) for n, g in zip(_FRAME_KEYS, gf)]
-            fptrs = (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in fs])
-            idx = (C.c_int * len(index))(*index)
-            self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_frames(
-                h, self._stream(), _lib.ptr(gl), *[_lib.ptr(c) for c in cs], _lib.ptr(flat), 0, gptrs, idx, len(index), fptrs),
-                h, 'iodine_train_backward_frames'))
+        flat = self._out('t.flat', (sum(p.numel() for p in self._ordered_params()),), dev)
+        # (graph mode: the cotangents go through persistent staging buffers like every other tensor, so the graph key repeats)
+        stage = lambda names, gs: [None if g is None else self._stage(n, g.detach().to(device=dev, dtype=torch.float32).contiguous())
+                                   for n, g in zip(names, gs)]
+        addr = lambda ts: [None if t is None else t.data_ptr() for t in ts]
+        cs = stage(('t.gl', 'a.mean', 'a.mask', 'a.logits', 'a.z', 'a.pm', 'a.plv', 'a.h', 'a.c'), (grad_loss, *cot))
+        fs = stage(['f.' + n for n in _FRAME_KEYS], gf)
+        outs, gptrs, fptrs, idx, F = (None,) * 4, None, None, None, 0
+        if any(want):
+            (B, K), L, H = BK, self.dim_latent, int(self._cfg.ref_mlp_units)
+            outs = [self._out('ts.g' + n, shp, dev) if w else None
+                    for n, shp, w in zip(('pm', 'plv', 'h', 'c'), ((B, K, L), (B, K, L), (B, K, H), (B, K, H)), want)]
+            gptrs = (C.c_void_p * 4)(*addr(outs))
+        if any(t is not None for t in fs):
+            F = len(index)
+            fptrs, idx = (C.c_void_p * 6)(*addr(fs)), (C.c_int * F)(*index)
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_train_backward_frames(
+            h, self._stream(), *[_lib.ptr(c) for c in cs], _lib.ptr(flat), 0, gptrs, idx, F, fptrs), h, 'iodine_train_backward_frames'))
         self._call_serial += 1                      # the saved forward is consumed (no retain_graph)
-        flat = self._own(flat)
-        views, off = [], 0
-        for p in params:
-            views.append(flat[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        return views, tuple(self._own(t) for t in outs)
+        # (graph mode: autograd may keep what we return as .grad; never the staging buffer)
+        return self._own(flat), tuple(self._own(t) for t in outs)
 
 
 def arch_namespace(dim_latent, iters, slots, img_size, ref, dec, sigma=0.10, layernorm=True,

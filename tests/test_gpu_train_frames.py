@@ -197,6 +197,72 @@ def test_cotangents_on_final_state_and_on_frame_T_add(base_case):
         assert e < 1e-6, (n, e)
 
 
+# One autograd node serves every un-chunked forward: whatever outputs are asked for, ``loss.backward()`` alone computes the plain step.
+MATRIX = [(a, f, s) for s in (False, True) for a in (False, True) for f in (None, (), (1,), True)]
+MATRIX_IDS = [f"{'state' if s else 'init'}-{'attach' if a else 'plain'}-frames_{f}" for a, f, s in MATRIX]
+
+
+def _step(m, x, eps, state, **kw):
+    """(loss, ELBO terms, {name: .grad or None}) of one forward + ``loss.backward()``"""
+    m.zero_grad(set_to_none=True)
+    loss = m(x.to(DEV), eps.to(DEV), state=state, **kw)
+    loss.backward()
+    torch.cuda.synchronize()
+    return loss.detach().clone(), m.elbo_terms.clone(), {n: None if p.grad is None else p.grad.clone() for n, p in m.named_parameters()}
+
+
+def _same_step(got, ref, tag):
+    assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1]), tag
+    for n, g in ref[2].items():
+        assert (got[2][n] is None) == (g is None), (tag, n)
+        assert g is None or torch.equal(got[2][n], g), (tag, n)
+
+
+@pytest.fixture(scope='module')
+def matrix_case(base_case):
+    """an eager and a graph-mode model, a detached state a forward over other inputs kept, the plain step from it and from the initial posterior"""
+    params, x, eps, _, _ = base_case
+    m = make_hip_model(BASE, params)
+    _, x2, eps2 = _inputs(BASE, seed=90)
+    with torch.no_grad():
+        m(x2.to(DEV), eps2.to(DEV), keep_state=True)
+    state = tuple(t.detach() for t in m.refinement_state())
+    plain = {s: _step(m, x, eps, state if s else None) for s in (False, True)}
+    for s, (_, _, g) in plain.items():
+        assert all((g[n] is None) == (s and n.startswith('posterior.')) for n in g)
+        assert all(bool(t.any()) for n, t in g.items() if t is not None and (n.endswith('.weight') or n.startswith('posterior.')))
+    assert not torch.equal(plain[False][0], plain[True][0])
+    return m, make_hip_model(BASE, params, options={'graph': 1}), state, plain
+
+
+def _frames_as_asked(m, frames):
+    if frames is None:
+        assert m.frames is None
+        return
+    index = tuple(range(BASE.iters + 1)) if frames is True else frames
+    assert m.frames['index'] == index and all(m.frames[k].shape[0] == len(index) for k in KEYS)
+
+
+@pytest.mark.parametrize('attach,frames,from_state', MATRIX, ids=MATRIX_IDS)
+def test_outputs_asked_for_change_no_bit_of_the_plain_step(base_case, matrix_case, attach, frames, from_state):
+    _, x, eps, _, _ = base_case
+    m, _, state, plain = matrix_case
+    got = _step(m, x, eps, state if from_state else None, attach_state=attach, attach_frames=frames)
+    _frames_as_asked(m, frames)
+    _same_step(got, plain[from_state], 'eager')
+
+
+@pytest.mark.parametrize('attach,frames,from_state', MATRIX, ids=MATRIX_IDS)
+def test_outputs_asked_for_change_no_bit_under_graph_replay(base_case, matrix_case, attach, frames, from_state):
+    _, x, eps, _, _ = base_case
+    _, mg, state, plain = matrix_case
+    for step in range(3):                                                    # eager or captured, then replayed
+        got = _step(mg, x, eps, state if from_state else None, attach_state=attach, attach_frames=frames)
+        _frames_as_asked(mg, frames)
+        _same_step(got, plain[from_state], f'graph step {step}')
+    assert mg.profile_read('graph_replays')[1] > 0
+
+
 # ---- 5. values ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('arch', [BASE, WS], ids=['base', 'ws'])
 def test_attached_values_match_the_fp32_oracle(arch):
