@@ -74,6 +74,41 @@ DecPath dec_path(const iodine_handle* h)
 
 bool dec_f16(DecPath p) { return p == DEC_WS_F16 || p == DEC_TILE_F16; }
 
+// Which kernels the refinement conv stack runs on, decided the same way.  The family depends on the configuration and conv_precision only:
+// iodine_set_params switches on it alone and keeps every pack of the family current - the per-form options do not invalidate the parameters.
+enum RefFamily {
+    REF_GENERIC,      // kernels_generic.hip: KERNEL_SIZE other than 3, CONV_CHAN other than 32 / 64, sizes that are no multiple of 16, stride != 2
+    REF_S2_F16,       // the tuned stride-2 kernels, split fp16
+    REF_S2_F32,       // the same kernels in their fp32-MFMA form (conv_precision 0): same buffers, fp32 weights in the same layouts
+    REF_GATHER,       // the gather kernels: some layer has an odd input size, which the tuned kernels do not take
+};
+RefFamily ref_family(const iodine_handle* h)
+{
+    if (h->gen_ref) return REF_GENERIC;
+    for (int l = 0, s = h->S; l < h->Dr; ++l, s /= 2) if (s % 2 != 0) return REF_GATHER;
+    return h->precision == 1 ? REF_S2_F16 : REF_S2_F32;
+}
+bool ref_s2(RefFamily f) { return f == REF_S2_F16 || f == REF_S2_F32; }
+// Which optional packs exist at these shapes: iodine_set_params writes a pack where its predicate holds, a launch site reads it only behind it.
+bool ref_pack_ws(const iodine_handle* h) { return h->Cr == 64; }                                               // ref_wsf[1 ..]
+bool ref_pack_bwd01(const iodine_handle* h) { return h->Dr >= 2 && refine_bwd01_ok(h->S, h->Cr); }             // ref_w1ws
+bool ref_pack_l0f(const iodine_handle* h) { return h->ref_l0k != nullptr; }                                    // ref_l0k / ref_l0s
+// The form of a forward pass: the family with the options and the kernels' own shape limits.  A pure function of the handle: it is evaluated
+// inside graphed bodies, which a replay does not execute - what a later call needs of it (CallState) is stored outside of them.
+// split: the channels every slot of an image shares are written and convolved once per image (split first layer); l0f: ... and encoding +
+// layer 0 are one kernel, the encoding stays on chip unless a reader asks for it
+struct RefForm { RefFamily fam; bool split, l0f; };
+RefForm ref_form(const iodine_handle* h)
+{
+    const RefFamily fam = ref_family(h);
+    const bool split = h->refine_split && ref_s2(fam);
+    return {fam, split, split && fam == REF_S2_F16 && h->refine_l0_fused && ref_pack_l0f(h) && refine_l0_fused_ok(h->S, h->Cr, h->K)};
+}
+// layer l (input size s) on the weight-stationary kernel?
+bool ref_layer_ws(const iodine_handle* h, const RefForm& f, int l, int s) { return l > 0 && h->refine_ws && ref_s2(f.fam) && ref_pack_ws(h) && conv3x3_s2ws_ok(s, h->Cr); }
+// layer 1's data gradient + layer 0's weight gradient in one launch?  fwd_split: what the saved forward left (CallState), not the current option
+bool ref_bwd01(const iodine_handle* h, bool fwd_split) { return h->refine_bwd_fused && fwd_split && ref_family(h) == REF_S2_F16 && ref_pack_bwd01(h); }
+
 // The per-layer launches of the tuned decoder (layers 1 .. Dd-1 are 3x3 convs Cd -> Cd, then the output conv Cd -> 4), one switch each.
 // zig-zag (`l & 1`): odd decoder layers walk the slot-images backwards (forward pass: l0 writes forwards, layer 1 reads
 // backwards, layer 2 forwards, ...; backward pass the same by layer), so a launch starts on the part of its input
@@ -285,13 +320,11 @@ std::string validate(const iodine_config& c)
 // spatial size of refinement layer l's OUTPUT
 // (k x k, pad k // 2, stride rs: floor((s + 2 (k // 2) - k) / rs) + 1 = (s - 1) / rs + 1 for odd k)
 int ref_out_size(const iodine_handle* h, int s) { return (s - 1) / h->rs + 1; }
-// the split-fp16 stride-2 kernels cover the shipped refinement stacks: 32 or 64 channels, even sizes at every layer
-bool refine_f16_ok(const iodine_handle* h);
 
 void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
 {
     const int N = B * h->K, P = h->P, L = h->L, Cd = h->Cd, Cr = h->Cr, H = h->H, T = h->T;
-    const bool gen_dec = dec_path(h) == DEC_GENERIC;
+    const bool gen_dec = dec_path(h) == DEC_GENERIC, gen_ref = ref_family(h) == REF_GENERIC;
     b.B = B; b.mode = mode; b.K = h->K; b.T = h->T;
     b.F = h->frames > 0 ? h->frames : 1;
     b.x4 = a.take<float>((size_t)b.F * B * P * 4);           // [F][B][P][4]: evaluation i reads frame i (x4_frame)
@@ -418,10 +451,10 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
     if (gen_dec) {
         b.gen_l0 = a.take<float>(gen_l0_scratch_floats(N, h->S, Cd, h->kd));   // row / tap sums, prefix table of the broadcast layer
     }
-    if ((gen_dec || h->gen_ref) && mode != 0) {
+    if ((gen_dec || gen_ref) && mode != 0) {
         size_t scr = 0;
         if (gen_dec) scr = std::max(gen_wgrad_scratch_floats(Cd, 4, h->kd), gen_wgrad_scratch_floats(Cd, Cd, h->kd));
-        if (h->gen_ref && mode == 1) scr = std::max(scr, std::max(gen_wgrad_scratch_floats(17, Cr, h->kr), gen_wgrad_scratch_floats(Cr, Cr, h->kr)));
+        if (gen_ref && mode == 1) scr = std::max(scr, std::max(gen_wgrad_scratch_floats(17, Cr, h->kr), gen_wgrad_scratch_floats(Cr, Cr, h->kr)));
         b.gen_scr = a.take<float>(scr);
     }
     // option sigma_grad (at the end: the carve-up in front of it is the same with or without a reader of these two)
@@ -689,67 +722,132 @@ int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps
     return IODINE_OK;
 }
 
-bool refine_split_on(const iodine_handle* h);
-
-bool refine_f16_ok(const iodine_handle* h)
+// The per-layer launches of the refinement conv stack, one switch each like the decoder's; none of them writes host state.
+// Layer l of iteration i: b.ract[i][l] from an input of size s.  Layer 0 starts from the decoder output and writes the encoding on the way;
+// its fused form keeps the encoding on chip unless keep_enc (the backward / iodine_debug_copy("enc") read it).
+int ref_conv_fwd(iodine_handle* h, hipStream_t st, const RefForm& f, int i, int l, int s, int B, bool keep_enc)
 {
-    if (h->gen_ref || (h->Cr != 64 && h->Cr != 32)) return false;
-    int s = h->S;
-    for (int l = 0; l < h->Dr; ++l) { if (s % 2 != 0) return false; s /= 2; }
-    return true;
+    Buffers& b = h->buf;
+    const int N = B * h->K, Cr = h->Cr, cip = l == 0 ? 20 : Cr, f32 = f.fam == REF_S2_F32;
+    const float* in = l == 0 ? b.enc[i] : b.ract[i][l - 1];
+    const char* cat = l == 0 ? "refine_l0" : "refine_conv";
+    if (l == 0 && f.l0f) {
+        PROF(h, st, "refine_l0f", launch_refine_l0_fused(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, h->ref_l0k, h->ref_l0kmeta, h->ref_l0s, h->ref_l0smeta,
+                                                         h->ref_b[0], b.ract[i][0], keep_enc ? b.enck[i] : nullptr, keep_enc ? b.encs[i] : nullptr, B, h->K,
+                                                         h->S, Cr, (float)h->obj.sigma, h->enc_chmask, h->stable_enc));
+        return IODINE_OK;
+    }
+    if (l == 0)
+        PROF(h, st, "pixel_pass2", launch_pixel_pass2(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, f.split ? b.enck[i] : b.enc[i], B, h->K, h->S,
+                                                      (float)h->obj.sigma, f.split ? b.encs[i] : nullptr, h->enc_chmask, h->precision == 0, h->stable_enc));
+    switch (f.fam) {
+    case REF_GENERIC:
+        PROF(h, st, "gen_conv", launch_gen_conv_fwd(st, in, h->gen_wref[l], h->ref_b[l], b.ract[i][l], N, s, l == 0 ? 17 : Cr, cip, Cr, h->kr, h->rs, 1,
+                                                    l == 0 ? h->enc_chmask : 0xffffffffu));
+        break;
+    case REF_S2_F16: case REF_S2_F32:
+        if (l == 0 && f.split) {                           // the per-image channels once per image, then the per-slot ones on top
+            PROF(h, st, cat, launch_conv3x3_s2_f16x3(st, b.encs[i], h->ref_wsh16, h->ref_wshmeta, nullptr, b.rmap, B, s, 8, Cr, nullptr, 0, f32));
+            PROF(h, st, cat, launch_conv3x3_s2_f16x3(st, b.enck[i], h->ref_wk16, h->ref_wkmeta, h->ref_b[0], b.ract[i][0], N, s, 12, Cr, b.rmap, h->K, f32));
+        } else if (ref_layer_ws(h, f, l, s))
+            PROF(h, st, cat, launch_conv3x3_s2ws_f16x3(st, in, h->ref_wsf[l], h->ref_wsf_meta[l], h->ref_b[l], b.ract[i][l], N, s, Cr, f32));
+        else
+            PROF(h, st, cat, launch_conv3x3_s2_f16x3(st, in, h->ref_wf16[l], h->ref_wmeta[l], h->ref_b[l], b.ract[i][l], N, s, cip, Cr, nullptr, 0, f32));
+        break;
+    case REF_GATHER: PROF(h, st, cat, launch_conv3x3_gather(st, in, h->ref_w[l], h->ref_b[l], b.ract[i][l], N, s, s, cip, Cr, 2)); break;
+    }
+    return IODINE_OK;
 }
 
-// (round 5: the exact-fp32 path runs the same tuned stride-2 kernels in their fp32-MFMA form, so it takes the split first layer too)
-bool refine_split_on(const iodine_handle* h) { return h->refine_split && refine_f16_ok(h); }
+// weight / bias gradient of layer l (input size s) over all NT slot-images into the accumulators.  split: the saved forward left layer 0's
+// input in the split layout; fuse01: layer 1's data gradient rides in layer 0's launch (ref_bwd01)
+int ref_conv_wgrad(iodine_handle* h, hipStream_t st, int NT, int l, int s, bool split, bool fuse01)
+{
+    Buffers& b = h->buf;
+    const int Cr = h->Cr, cip = l == 0 ? 20 : Cr, ireal = l == 0 ? 17 : Cr, so = ref_out_size(h, s), f32 = h->precision == 0;
+    const float* in = l == 0 ? b.enc[0] : b.ract[0][l - 1];
+    int nparts = 0, cipad = 0, nb = 0;
+    float *gb = h->gacc[h->slot.ref_b[l]], *gw = h->gacc[h->slot.ref_w[l]];
+    // the destination: the accumulator itself, or (first layer of an ARCH.ENCODING subset) a 17-channel scratch gathered into it afterwards
+    const bool gather0 = l == 0 && h->n_in < 17;
+    float* gw_dst = gather0 ? h->ref_g17 : gw;
+    if (gather0) HIPCHK(h, launch_zero_fill(st, h->ref_g17, (size_t)Cr * 17 * h->kr * h->kr));
+    switch (ref_family(h)) {
+    case REF_GENERIC:
+        PROF(h, st, "gen_conv", launch_gen_conv_wgrad(st, in, b.rdpre[l], b.gen_scr, NT, s, ireal, cip, ireal, Cr, h->kr, h->rs, 1.f, gw_dst, gb,
+                                                      l == 0 ? h->enc_chmask : 0xffffffffu));
+        break;
+    case REF_S2_F16: case REF_S2_F32: {
+        // split first layer: 12 per-slot + 8 per-image channels from two tensors, gradient in the internal channel order, then unsplit
+        const bool split0 = l == 0 && split;
+        if (split0 && fuse01)
+            PROF(h, st, "refine_bwd01", launch_refine_bwd01(st, b.rdpre[1], h->ref_w1ws, h->ref_w1ws_meta, b.ract[0][0], b.enck[0], b.encs[0], b.wg_part,
+                                                            b.wg_part_b, NT, s, Cr, h->K, &nparts, &cipad, &nb));
+        else
+            PROF(h, st, "refine_wgrad", launch_conv3x3_s2_wgrad_f16x3(st, split0 ? b.enck[0] : in, b.rdpre[l], b.wg_part, b.wg_part_b, NT, s, cip, Cr, &nparts,
+                                                                      &cipad, &nb, split0 ? b.encs[0] : nullptr, split0 ? h->K : 0, f32));
+        const int ir = split0 ? 20 : ireal;
+        if (split0) HIPCHK(h, launch_zero_fill(st, h->ref_g20, (size_t)Cr * 20 * 9));
+        HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, ir, ir, 1.f, split0 ? h->ref_g20 : gw_dst, b.wg_fold, b.wg_part_b, nb, gb));
+        if (split0) HIPCHK(h, launch_ref_unsplit_grad(st, h->ref_g20, Cr, gw_dst));
+        break;
+    }
+    case REF_GATHER:
+        PROF(h, st, "refine_wgrad", launch_conv3x3_wgrad_gather(st, in, b.rdpre[l], b.wg_part, NT, s, s, cip, Cr, 2, &nparts, &cipad));
+        HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, ireal, ireal, 1.f, gw_dst, b.wg_fold));
+        PROF(h, st, "refine_bias_grad", launch_colsum_tall(st, b.rdpre[l], NT * so * so, Cr, 1.f, gb, b.wg_part_b, (size_t)512 * 64));
+        break;
+    }
+    if (gather0) HIPCHK(h, launch_enc_gather_grad(st, h->ref_g17, Cr, h->n_in, h->enc_map, gw, h->kr * h->kr));
+    return IODINE_OK;
+}
+
+// data gradient of layer l >= 1 (input size s): b.rdpre[l] -> b.rdpre[l - 1]
+int ref_conv_dgrad(iodine_handle* h, hipStream_t st, int NT, int l, int s)
+{
+    Buffers& b = h->buf;
+    float *d = b.rdpre[l], *out = b.rdpre[l - 1], *act = b.ract[0][l - 1];
+    switch (ref_family(h)) {
+    case REF_GENERIC: PROF(h, st, "gen_conv", launch_gen_conv_dgrad(st, d, h->gen_wref[l], act, out, NT, s, h->Cr, h->Cr, h->Cr, h->kr, h->rs)); break;
+    case REF_S2_F16: case REF_S2_F32:
+        PROF(h, st, "refine_dgrad", launch_conv3x3_s2_dgrad_f16x3(st, d, h->ref_wb16[l], h->ref_wmeta[l] + 2, act, out, NT, s, h->Cr, h->precision == 0));
+        break;
+    case REF_GATHER: PROF(h, st, "refine_dgrad", launch_conv3x3_gather_dgrad(st, d, h->ref_wb[l], act, out, NT, s, s, h->Cr, 2)); break;
+    }
+    return IODINE_OK;
+}
+
+// Backward of the conv stack, last layer first, for ALL iterations at once: its inputs are detached (iodine.py:343), so the T passes only meet
+// in the weight gradients - one batch of NT = T * N slot-images per layer (the saved inputs / activations lie back to back, plan()) instead
+// of T launches over N each.  fwd_split: the layout the saved forward left its inputs in (CallState::fwd_split).
+int refine_stack_backward(iodine_handle* h, hipStream_t st, int NT, bool fwd_split)
+{
+    Buffers& b = h->buf;
+    std::vector<int> sz(h->Dr + 1, h->S);
+    for (int l = 0; l < h->Dr; ++l) sz[l + 1] = ref_out_size(h, sz[l]);
+    HIPCHK(h, launch_pool_bwd(st, b.dpooled, b.ract[0][h->Dr - 1], b.rdpre[h->Dr - 1], NT, sz[h->Dr] * sz[h->Dr], h->Cr));
+    const bool fuse01 = ref_bwd01(h, fwd_split);           // d(pre-activation 0), the largest tensor of this backward, never leaves the chip
+    for (int l = h->Dr - 1; l >= 0; --l) {
+        if (int r = ref_conv_wgrad(h, st, NT, l, sz[l], fwd_split, fuse01)) return r;
+        if (l > 1 || (l == 1 && !fuse01))
+            if (int r = ref_conv_dgrad(h, st, NT, l, sz[l])) return r;
+    }
+    return IODINE_OK;
+}
 
 // refine() + posterior.update() for iteration i (iodine.py:95-100 / 144-145)
 int refine_step(iodine_handle* h, hipStream_t st, int B, int i, bool save)
 {
     Buffers& b = h->buf;
     const int N = B * h->K;
-    // split first layer: the channels every slot of an image shares are written and convolved once per image
-    const bool split = refine_split_on(h);     // (training: iodine_train_forward records the form in calls.fwd_split - host state must
-                                               //  not be written here, a hipGraph replay does not execute this body)
-    // ... and with refine_l0_fused the encoding is not written at all (inference): one kernel from the decoder output to layer 0's output
-    const bool l0f = split && h->precision == 1 && h->refine_l0_fused && refine_l0_fused_ok(h->S, h->Cr, h->K);
-    const int f32 = h->precision == 0;         // exact fp32 products: the fp32-MFMA form of the same stride-2 kernels
-    const bool keep_enc = save || h->stop_after >= 0;     // the backward / iodine_debug_copy("enc") read it
-    if (l0f)
-        PROF(h, st, "refine_l0f", launch_refine_l0_fused(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, h->ref_l0k, h->ref_l0kmeta, h->ref_l0s,
-                                                         h->ref_l0smeta, h->ref_b[0], b.ract[i][0], keep_enc ? b.enck[i] : nullptr,
-                                                         keep_enc ? b.encs[i] : nullptr, B, h->K, h->S, h->Cr, (float)h->obj.sigma,
-                                                         h->enc_chmask, h->stable_enc));
-    else
-        PROF(h, st, "pixel_pass2", launch_pixel_pass2(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, split ? b.enck[i] : b.enc[i], B, h->K, h->S,
-                                                      (float)h->obj.sigma, split ? b.encs[i] : nullptr, h->enc_chmask, h->precision == 0, h->stable_enc));
+    const RefForm f = ref_form(h);
     int s = h->S;
-    const float* in = b.enc[i];
-    for (int l = 0; l < h->Dr; ++l) {
-        if (h->gen_ref) {
-            PROF(h, st, "gen_conv", launch_gen_conv_fwd(st, in, h->gen_wref[l], h->ref_b[l], b.ract[i][l], N, s, l == 0 ? 17 : h->Cr,
-                                                        l == 0 ? 20 : h->Cr, h->Cr, h->kr, h->rs, 1, l == 0 ? h->enc_chmask : 0xffffffffu));
-        } else if (l == 0 && l0f) {
-        } else if (l == 0 && split) {
-            PROF(h, st, "refine_l0", launch_conv3x3_s2_f16x3(st, b.encs[i], h->ref_wsh16, h->ref_wshmeta, nullptr, b.rmap, B, s, 8,
-                                                             h->Cr, nullptr, 0, f32));
-            PROF(h, st, "refine_l0", launch_conv3x3_s2_f16x3(st, b.enck[i], h->ref_wk16, h->ref_wkmeta, h->ref_b[0], b.ract[i][0], N,
-                                                             s, 12, h->Cr, b.rmap, h->K, f32));
-        } else if (l > 0 && h->refine_ws && refine_f16_ok(h) && conv3x3_s2ws_ok(s, h->Cr)) {
-            PROF(h, st, "refine_conv", launch_conv3x3_s2ws_f16x3(st, in, h->ref_wsf[l], h->ref_wsf_meta[l], h->ref_b[l], b.ract[i][l], N, s, h->Cr, f32));
-        } else if (refine_f16_ok(h))
-            PROF(h, st, l == 0 ? "refine_l0" : "refine_conv", launch_conv3x3_s2_f16x3(st, in, h->ref_wf16[l], h->ref_wmeta[l], h->ref_b[l],
-                                                               b.ract[i][l], N, s, l == 0 ? 20 : h->Cr, h->Cr, nullptr, 0, f32));
-        else
-            PROF(h, st, l == 0 ? "refine_l0" : "refine_conv", launch_conv3x3_gather(st, in, h->ref_w[l], h->ref_b[l], b.ract[i][l], N, s, s,
-                                                             l == 0 ? 20 : h->Cr, h->Cr, 2));
-        in = b.ract[i][l];
-        s = ref_out_size(h, s);
-    }
-    PROF(h, st, "refine_head", launch_refine_head(st, in, N, s * s, h->Cr, h->H, h->L, h->mlp_wT, h->mlp_b, h->wihT, h->whhT, h->lstm_b,
-                                 h->wmT, h->bm, h->wvT, h->bv, b.latent[i], b.h[i], b.c[i], b.h[i + 1], b.c[i + 1], b.pm,
-                                 b.plv, save ? b.pooled[i] : nullptr, save ? b.u[i] : nullptr,
-                                 save ? b.gates[i] : nullptr, save ? b.xin[i] : nullptr, nullptr, nullptr,
-                                 b.head_xh, b.head_gp, h->head_mfma));                // (the form: refine_head_form; head_mfma where both fit)
+    for (int l = 0; l < h->Dr; ++l, s = ref_out_size(h, s))
+        if (int r = ref_conv_fwd(h, st, f, i, l, s, B, save || h->stop_after >= 0)) return r;
+    PROF(h, st, "refine_head", launch_refine_head(st, b.ract[i][h->Dr - 1], N, s * s, h->Cr, h->H, h->L, h->mlp_wT, h->mlp_b, h->wihT, h->whhT, h->lstm_b,
+                                 h->wmT, h->bm, h->wvT, h->bv, b.latent[i], b.h[i], b.c[i], b.h[i + 1], b.c[i + 1], b.pm, b.plv,
+                                 save ? b.pooled[i] : nullptr, save ? b.u[i] : nullptr, save ? b.gates[i] : nullptr, save ? b.xin[i] : nullptr,
+                                 nullptr, nullptr, b.head_xh, b.head_gp, h->head_mfma));   // (the form: refine_head_form; head_mfma where both fit)
     return IODINE_OK;
 }
 
@@ -1101,10 +1199,14 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
     ALLOC(h->dec_out_w16, (size_t)(Cd / 16) * 2 * 2 * 64 * 4);            // GEMM-form pack: [chunk][hi/lo][kh][64][8 fp16]
     ALLOC(h->dec_out_meta, (size_t)4);
     ALLOC(h->dec_out_wb16, (size_t)3 * 2 * 2 * Cd * 4);
-    h->ref_w.assign(h->Dr, nullptr); h->ref_b.assign(h->Dr, nullptr);
+    // refinement conv stack: the packs of every tuned family (ref_family() changes with conv_precision), the optional ones by ref_pack_*()
+    for (auto* v : {&h->ref_w, &h->ref_b, &h->ref_wb, &h->ref_wf16, &h->ref_wb16, &h->ref_wmeta, &h->ref_wsf, &h->ref_wsf_meta}) v->assign(h->Dr, nullptr);
     for (int l = 0; l < h->Dr; ++l) {
-        ALLOC(h->ref_w[l], conv_wpk_elems(l == 0 ? 20 : Cr, Cr) * 4);
-        ALLOC(h->ref_b[l], (size_t)Cr);
+        ALLOC(h->ref_w[l], conv_wpk_elems(l == 0 ? 20 : Cr, Cr) * 4); ALLOC(h->ref_b[l], (size_t)Cr);
+        ALLOC(h->ref_wf16[l], (size_t)((l == 0 ? 32 : Cr) / 16) * 9 * 2 * 2 * Cr * 4); ALLOC(h->ref_wmeta[l], (size_t)4);
+        if (l == 0) continue;
+        ALLOC(h->ref_wb[l], conv_wpk_elems(Cr, Cr) * 4); ALLOC(h->ref_wb16[l], (size_t)(Cr / 16) * 9 * 2 * 2 * Cr * 4);
+        if (ref_pack_ws(h)) { ALLOC(h->ref_wsf[l], conv_ws_wpk_bytes(Cr) / 4); ALLOC(h->ref_wsf_meta[l], (size_t)4); }
     }
     ALLOC(h->mlp_wT, (size_t)Cr * H); ALLOC(h->mlp_b, (size_t)H);
     ALLOC(h->wihT, (size_t)(H + 4 * L + H) * 4 * H);         // [W_ih^T ; W_hh^T] contiguous: one K-major operand for the gate GEMM (head_mfma)
@@ -1114,20 +1216,9 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
     ALLOC(h->init_mean, (size_t)L); ALLOC(h->init_logvar, (size_t)L);
     ALLOC(h->raw_mlp_w, (size_t)H * Cr); ALLOC(h->raw_wih, (size_t)4 * H * (H + 4 * L)); ALLOC(h->raw_whh, (size_t)4 * H * H);
     ALLOC(h->raw_wm, (size_t)L * H); ALLOC(h->raw_wv, (size_t)L * H);
-    h->ref_wb.assign(h->Dr, nullptr);
-    for (int l = 1; l < h->Dr; ++l) ALLOC(h->ref_wb[l], conv_wpk_elems(Cr, Cr) * 4);
-    h->ref_wf16.assign(h->Dr, nullptr); h->ref_wb16.assign(h->Dr, nullptr); h->ref_wmeta.assign(h->Dr, nullptr);
-    for (int l = 0; l < h->Dr; ++l) {
-        ALLOC(h->ref_wf16[l], (size_t)((l == 0 ? 32 : Cr) / 16) * 9 * 2 * 2 * Cr * 4);
-        ALLOC(h->ref_wmeta[l], (size_t)4);
-        if (l > 0) ALLOC(h->ref_wb16[l], (size_t)(Cr / 16) * 9 * 2 * 2 * Cr * 4);
-    }
     // split first layer: one 16-channel chunk each for the per-slot (12 real) and the per-image (8 real) channels
     ALLOC(h->ref_wk, (size_t)Cr * 12 * 9); ALLOC(h->ref_wsh, (size_t)Cr * 8 * 9); ALLOC(h->ref_g20, (size_t)Cr * 20 * 9);
-    if (Cr % 32 == 0) { ALLOC(h->ref_w1ws, conv_ws_wpk_bytes(Cr) / 4); ALLOC(h->ref_w1ws_meta, (size_t)4); }
-    h->ref_wsf.assign(h->Dr, nullptr); h->ref_wsf_meta.assign(h->Dr, nullptr);
-    if (Cr == 64)
-        for (int l = 1; l < h->Dr; ++l) { ALLOC(h->ref_wsf[l], conv_ws_wpk_bytes(Cr) / 4); ALLOC(h->ref_wsf_meta[l], (size_t)4); }
+    if (ref_pack_bwd01(h)) { ALLOC(h->ref_w1ws, conv_ws_wpk_bytes(Cr) / 4); ALLOC(h->ref_w1ws_meta, (size_t)4); }
     ALLOC(h->ref_w17, (size_t)Cr * 17 * h->kr * h->kr); ALLOC(h->ref_g17, (size_t)Cr * 17 * h->kr * h->kr);
     if (dec_path(h) == DEC_GENERIC) {
         const int kkd = h->kd * h->kd;
@@ -1135,7 +1226,7 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
         for (int l = 0; l < h->Dd; ++l) ALLOC(h->gen_wdec[l], (size_t)kkd * (l == 0 ? L + 2 : Cd) * Cd);
         ALLOC(h->gen_wout, (size_t)kkd * Cd * 4); ALLOC(h->gen_cterm, (size_t)h->P * Cd); ALLOC(h->gen_ident, (size_t)9 * Cd * L);
     }
-    if (h->gen_ref) {
+    if (ref_family(h) == REF_GENERIC) {
         const int kkr = h->kr * h->kr;
         h->gen_wref.assign(h->Dr, nullptr);
         for (int l = 0; l < h->Dr; ++l) ALLOC(h->gen_wref[l], (size_t)kkr * (l == 0 ? 17 : Cr) * Cr);
@@ -1150,9 +1241,8 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
     }
     if (Cr % 16 == 0) {
         float *pk = nullptr, *ps = nullptr;
-        ALLOC(pk, refine_l0_wpk_bytes(Cr) / 4); ALLOC(ps, refine_l0_wpk_bytes(Cr) / 4);
+        ALLOC(pk, refine_l0_wpk_bytes(Cr) / 4); ALLOC(ps, refine_l0_wpk_bytes(Cr) / 4); ALLOC(h->ref_l0kmeta, (size_t)4); ALLOC(h->ref_l0smeta, (size_t)4);
         h->ref_l0k = pk; h->ref_l0s = ps;
-        ALLOC(h->ref_l0kmeta, (size_t)4); ALLOC(h->ref_l0smeta, (size_t)4);
     }
     // gradient accumulators: ONE buffer, parameters back to back in named_parameters() order (the layout the wrapper's
     // flat gradient buffer has too), so that zeroing and the final scale-and-add are one launch each
@@ -1273,16 +1363,12 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
             }
         }
     }
-    if (h->gen_ref) {
-        for (int l = 0; l < h->Dr; ++l) {
-            const float* w = dev[ps.ref_w[l]];
-            if (l == 0 && h->n_in < 17) {
-                HIPCHK(h, launch_enc_expand_weights(st, w, Cr, h->n_in, h->enc_map, h->ref_w17, h->kr * h->kr));
-                w = h->ref_w17;
-            }
-            HIPCHK(h, launch_gen_pack_weights(st, w, Cr, l == 0 ? 17 : Cr, h->kr, h->gen_wref[l]));
-            HIPCHK(h, queue_copy(h->ref_b[l], dev[ps.ref_b[l]], Cr));
-        }
+    const RefFamily fam = ref_family(h);
+    for (int l = 0; l < h->Dr && fam == REF_GENERIC; ++l) {   // (the generic stack's packs in front of the decoder's, the other families' behind)
+        const float* w = dev[ps.ref_w[l]];
+        if (l == 0 && h->n_in < 17) { HIPCHK(h, launch_enc_expand_weights(st, w, Cr, h->n_in, h->enc_map, h->ref_w17, h->kr * h->kr)); w = h->ref_w17; }
+        HIPCHK(h, launch_gen_pack_weights(st, w, Cr, l == 0 ? 17 : Cr, h->kr, h->gen_wref[l]));
+        HIPCHK(h, queue_copy(h->ref_b[l], dev[ps.ref_b[l]], Cr));
     }
     if (path != DEC_GENERIC) {
     // decoder
@@ -1323,58 +1409,45 @@ int iodine_set_params(iodine_handle* h, void* stream, const float* const* dev, i
         if (h->dec_out_w32) HIPCHK(h, launch_pack_dec_out_rows32(st, dev[ps.out_w], Cd, h->dec_out_w32));
     }
     }   // tuned decoder
-    if (!h->gen_ref) {
-    // refinement conv stack
-    const bool ref_fp32 = !refine_f16_ok(h);                    // the round-1 gather kernels: only where the tuned stride-2 kernels do not apply
+    if (fam != REF_GENERIC) {
+    // refinement conv stack: every pack of the family, whatever the per-form options say (they do not invalidate the parameters)
     // first layer: the reference weight has n_in input channels (ARCH.ENCODING subset); the kernels see 17
     const float* w0 = dev[ps.ref_w[0]];
-    if (h->n_in < 17) {
-        HIPCHK(h, launch_enc_expand_weights(st, w0, Cr, h->n_in, h->enc_map, h->ref_w17));
-        w0 = h->ref_w17;
-    }
+    if (h->n_in < 17) { HIPCHK(h, launch_enc_expand_weights(st, w0, Cr, h->n_in, h->enc_map, h->ref_w17)); w0 = h->ref_w17; }
     for (int l = 0; l < h->Dr; ++l) {
-        const float* w = l == 0 ? w0 : dev[ps.ref_w[l]];
-        if (ref_fp32) HIPCHK(h, launch_pack_conv_weights(st, w, Cr, l == 0 ? 17 : Cr, l == 0 ? 20 : Cr, Cr, 0, h->ref_w[l]));
+        if (fam == REF_GATHER) HIPCHK(h, launch_pack_conv_weights(st, l == 0 ? w0 : dev[ps.ref_w[l]], Cr, l == 0 ? 17 : Cr, l == 0 ? 20 : Cr, Cr, 0, h->ref_w[l]));
         HIPCHK(h, queue_copy(h->ref_b[l], dev[ps.ref_b[l]], Cr));
     }
-    for (int l = 1; l < h->Dr && ref_fp32; ++l)
-        HIPCHK(h, launch_pack_conv_weights(st, dev[ps.ref_w[l]], Cr, Cr, Cr, Cr, 2, h->ref_wb[l]));
-    if (refine_f16_ok(h) && h->precision == 0) {
-        // exact-fp32 path: fp32 weights in the same LDS-tile layouts (same buffers; conv_precision invalidates the parameters)
+    switch (fam) {
+    case REF_GATHER: for (int l = 1; l < h->Dr; ++l) HIPCHK(h, launch_pack_conv_weights(st, dev[ps.ref_w[l]], Cr, Cr, Cr, Cr, 2, h->ref_wb[l])); break;
+    case REF_S2_F16: case REF_S2_F32: {
+        // split fp16: jobs of the batched pack; exact fp32: fp32 weights in the same LDS-tile / register layouts, in the same buffers
+        const bool f16 = fam == REF_S2_F16;
+        auto tile = [&](const float* w, int I, int cin, int tflip, float* meta, void* dst) {
+            return f16 ? pack_f16(w, Cr, I, cin, Cr, tflip, meta, dst) : launch_pack_conv_weights_s2f32(st, w, Cr, I, cin, Cr, tflip, dst);
+        };
         for (int l = 0; l < h->Dr; ++l) {
             const float* w = l == 0 ? w0 : dev[ps.ref_w[l]];
-            HIPCHK(h, launch_pack_conv_weights_s2f32(st, w, Cr, l == 0 ? 17 : Cr, l == 0 ? 32 : Cr, Cr, 0, h->ref_wf16[l]));
-            if (l > 0) HIPCHK(h, launch_pack_conv_weights_s2f32(st, w, Cr, Cr, Cr, Cr, 2, h->ref_wb16[l]));
-        }
-        HIPCHK(h, launch_ref_split_weights(st, w0, Cr, h->ref_wk, h->ref_wsh));
-        HIPCHK(h, launch_pack_conv_weights_s2f32(st, h->ref_wk, Cr, 12, 16, Cr, 0, h->ref_wk16));
-        HIPCHK(h, launch_pack_conv_weights_s2f32(st, h->ref_wsh, Cr, 8, 16, Cr, 0, h->ref_wsh16));
-        if (Cr == 64)                                           // weight-stationary forward of layers 1 .. (fp32 weights in the same registers)
-            for (int l = 1; l < h->Dr; ++l)
-                HIPCHK(h, launch_pack_conv_weights_ws32(st, dev[ps.ref_w[l]], Cr, 0, h->ref_wsf[l]));
-    } else if (refine_f16_ok(h)) {
-        for (int l = 0; l < h->Dr; ++l) {
-            const float* w = l == 0 ? w0 : dev[ps.ref_w[l]];
-            HIPCHK(h, pack_f16(w, Cr, l == 0 ? 17 : Cr, l == 0 ? 32 : Cr, Cr, 0, h->ref_wmeta[l],
-                                                   h->ref_wf16[l]));
-            if (l > 0)
-                HIPCHK(h, pack_f16(w, Cr, Cr, Cr, Cr, 2, h->ref_wmeta[l] + 2, h->ref_wb16[l]));
+            HIPCHK(h, tile(w, l == 0 ? 17 : Cr, l == 0 ? 32 : Cr, 0, h->ref_wmeta[l], h->ref_wf16[l]));
+            if (l > 0) HIPCHK(h, tile(w, Cr, Cr, 2, h->ref_wmeta[l] + 2, h->ref_wb16[l]));
         }
         // split first layer (refine_split): the same weights in the internal channel order, packed as two 16-channel convs
         HIPCHK(h, launch_ref_split_weights(st, w0, Cr, h->ref_wk, h->ref_wsh));
-        HIPCHK(h, pack_f16(h->ref_wk, Cr, 12, 16, Cr, 0, h->ref_wkmeta, h->ref_wk16));
-        HIPCHK(h, pack_f16(h->ref_wsh, Cr, 8, 16, Cr, 0, h->ref_wshmeta, h->ref_wsh16));
-        if (h->ref_l0k) {                                      // fused encoding + layer 0: both parts as K = 16 MFMA operands
+        HIPCHK(h, tile(h->ref_wk, 12, 16, 0, h->ref_wkmeta, h->ref_wk16));
+        HIPCHK(h, tile(h->ref_wsh, 8, 16, 0, h->ref_wshmeta, h->ref_wsh16));
+        if (f16 && ref_pack_l0f(h)) {                          // fused encoding + layer 0: both parts as K = 16 MFMA operands
             pj.push_back(PackJob{h->ref_wk, h->ref_l0k, h->ref_l0kmeta, 2, {Cr, 12, 0, 0, 0}});
             pj.push_back(PackJob{h->ref_wsh, h->ref_l0s, h->ref_l0smeta, 2, {Cr, 8, 0, 0, 0}});
         }
-        if (Cr == 64)                                           // weight-stationary forward of layers 1 ..
-            for (int l = 1; l < h->Dr; ++l)
-                HIPCHK(h, pack_ws(dev[ps.ref_w[l]], Cr, 0, h->ref_wsf_meta[l], h->ref_wsf[l]));
-        if (h->Dr >= 2 && refine_bwd01_ok(h->S, Cr))           // fused layer-1 / layer-0 backward: W1 as the transposed conv's A operand
+        for (int l = 1; l < h->Dr && ref_pack_ws(h); ++l)       // weight-stationary forward of layers 1 ..
+            HIPCHK(h, f16 ? pack_ws(dev[ps.ref_w[l]], Cr, 0, h->ref_wsf_meta[l], h->ref_wsf[l]) : launch_pack_conv_weights_ws32(st, dev[ps.ref_w[l]], Cr, 0, h->ref_wsf[l]));
+        if (f16 && ref_pack_bwd01(h))                          // fused layer-1 / layer-0 backward: W1 as the transposed conv's A operand
             HIPCHK(h, pack_ws(dev[ps.ref_w[1]], Cr, 1, h->ref_w1ws_meta, h->ref_w1ws));
+        break;
     }
-    }   // !gen_ref
+    case REF_GENERIC: break;                                   // (packed above, in front of the decoder)
+    }
+    }
     auto copy_raw = [&](float* dst, int slot) { return queue_copy(dst, dev[slot], h->params[slot].numel()); };
     HIPCHK(h, copy_raw(h->raw_mlp_w, ps.mlp_w));
     HIPCHK(h, copy_raw(h->raw_wih, ps.wih));
@@ -1645,8 +1718,8 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
     h->calls.last_elbo_iter = n_it > 0 ? n_it - 1 : -1;
     h->calls.last_elbo_batch = B;
     h->calls.state_iter = n_it;                                  // buf.h / buf.c [n_it]: the LSTM state after the last update (iodine_last_refine_state)
-    // (host state, outside the graphed body) did this call leave the encoding in the workspace?  refine_step: l0f && !keep_enc skips it
-    h->calls.enc_valid = n_it > 0 && (h->stop_after >= 0 || !(refine_split_on(h) && h->precision == 1 && h->refine_l0_fused && refine_l0_fused_ok(h->S, h->Cr, h->K)));
+    // (host state, outside the graphed body) did this call leave the encoding in the workspace?  ref_conv_fwd: l0f && !keep_enc skips it
+    h->calls.enc_valid = n_it > 0 && (h->stop_after >= 0 || !ref_form(h).l0f);
     return IODINE_OK;
 }
 
@@ -2062,7 +2135,7 @@ int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x
     cs.fwd_obj = h->obj;                                   // the backward differentiates the forward as it ran (a replay ran the same objective: graph key)
     cs.enc_valid = true;                                   // training keeps the encoding of every iteration (the backward reads it)
     cs.fwd_batch = B;
-    cs.fwd_split = refine_split_on(h);     // layout of the saved refinement inputs (refine_split is part of the graph key)
+    cs.fwd_split = ref_form(h).split;      // layout of the saved refinement inputs (refine_split is part of the graph key)
     cs.last_elbo_iter = T;
     cs.last_elbo_batch = B;
     cs.sgrad_n = h->sigma_grad ? T + 1 : 0;
@@ -2232,74 +2305,7 @@ int train_backward_impl(iodine_handle* h, void* stream, float grad_scale, const 
         HIPCHK(h, launch_sgemm(st, 1, 0, H, Cr, R, 1.f, b.ds, H, b.pooled[0], Cr, 1.f, h->gacc[ps.mlp_w], Cr));
         HIPCHK(h, launch_colsum(st, b.ds, R, H, H, 1.f, h->gacc[ps.mlp_b]));
     }
-    {
-        // Conv stack of the refinement network, last layer first, for ALL iterations at once: its inputs are detached
-        // (iodine.py:343), so the T passes only meet in the weight gradients - one batch of T * N slot-images per layer
-        // (saved inputs / activations of the iterations lie back to back, plan()) instead of T launches over N each: the
-        // 8 x 8 ... 64 x 64 layers fill the chip 5x better and 4 (T - 1) x 3 launches disappear.
-        const int NT = T * N;
-        std::vector<int> sz(h->Dr + 1);
-        sz[0] = h->S;
-        for (int l = 0; l < h->Dr; ++l) sz[l + 1] = ref_out_size(h, sz[l]);
-        const int sl = sz[h->Dr];
-        HIPCHK(h, launch_pool_bwd(st, b.dpooled, b.ract[0][h->Dr - 1], b.rdpre[h->Dr - 1], NT, sl * sl, Cr));
-        // round 4: the data gradient of layer 1 and the weight / bias gradient of layer 0 in ONE launch - d(pre-activation 0), the
-        // largest tensor of this backward (T * N x 64 x 64 x 64 floats at cfg3), is produced and consumed on chip
-        const bool fuse01 = h->refine_bwd_fused && h->calls.fwd_split && !h->gen_ref && h->precision == 1 && refine_f16_ok(h) && h->Dr >= 2 &&
-                            refine_bwd01_ok(h->S, Cr);
-        for (int l = h->Dr - 1; l >= 0; --l) {
-            const float* in = l == 0 ? b.enc[0] : b.ract[0][l - 1];
-            const int cip = l == 0 ? 20 : Cr, ireal = l == 0 ? 17 : Cr;
-            int nparts = 0, cipad = 0;
-            float* gb = h->gacc[ps.ref_b[l]];
-            // the layer's weight-gradient destination: the accumulator itself, or (first layer of an ARCH.ENCODING subset) a
-            // 17-channel scratch that is gathered into the n_in-channel accumulator afterwards
-            const bool gather0 = l == 0 && h->n_in < 17;
-            float* gw_dst = gather0 ? h->ref_g17 : h->gacc[ps.ref_w[l]];
-            if (gather0) HIPCHK(h, launch_zero_fill(st, h->ref_g17, (size_t)Cr * 17 * h->kr * h->kr));
-            if (h->gen_ref) {
-                PROF(h, st, "gen_conv", launch_gen_conv_wgrad(st, in, b.rdpre[l], b.gen_scr, NT, sz[l], ireal, cip, ireal, Cr, h->kr, h->rs, 1.f,
-                                                              gw_dst, gb, l == 0 ? h->enc_chmask : 0xffffffffu));
-            } else if (l == 0 && h->calls.fwd_split) {
-                // split first layer: 12 per-slot + 8 per-image channels from two tensors (fuse01: in the same launch as layer 1's data
-                // gradient), gradient in the internal channel order, then added to the reference layout
-                int nb = 0;
-                if (fuse01)
-                    PROF(h, st, "refine_bwd01", launch_refine_bwd01(st, b.rdpre[1], h->ref_w1ws, h->ref_w1ws_meta, b.ract[0][0], b.enck[0], b.encs[0],
-                                                                    b.wg_part, b.wg_part_b, NT, sz[0], Cr, h->K, &nparts, &cipad, &nb));
-                else
-                    PROF(h, st, "refine_wgrad", launch_conv3x3_s2_wgrad_f16x3(st, b.enck[0], b.rdpre[0], b.wg_part, b.wg_part_b, NT, sz[0],
-                                                                              20, Cr, &nparts, &cipad, &nb, b.encs[0], h->K, h->precision == 0));
-                HIPCHK(h, launch_zero_fill(st, h->ref_g20, (size_t)Cr * 20 * 9));
-                HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, 20, 20, 1.f, h->ref_g20, b.wg_fold, b.wg_part_b, nb, gb));
-                HIPCHK(h, launch_ref_unsplit_grad(st, h->ref_g20, Cr, gw_dst));
-            } else if (refine_f16_ok(h)) {
-                int nb = 0;
-                PROF(h, st, "refine_wgrad", launch_conv3x3_s2_wgrad_f16x3(st, in, b.rdpre[l], b.wg_part, b.wg_part_b, NT, sz[l],
-                                                                          cip, Cr, &nparts, &cipad, &nb, nullptr, 0, h->precision == 0));
-                HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, ireal, ireal, 1.f, gw_dst, b.wg_fold,
-                                              b.wg_part_b, nb, gb));
-            } else {
-                PROF(h, st, "refine_wgrad", launch_conv3x3_wgrad_gather(st, in, b.rdpre[l], b.wg_part, NT, sz[l], sz[l], cip, Cr, 2,
-                                                                        &nparts, &cipad));
-                HIPCHK(h, launch_wgrad_reduce(st, b.wg_part, nparts, cipad, Cr, Cr, ireal, ireal, 1.f, gw_dst, b.wg_fold));
-                PROF(h, st, "refine_bias_grad", launch_colsum_tall(st, b.rdpre[l], NT * sz[l + 1] * sz[l + 1], Cr, 1.f,
-                                                                   gb, b.wg_part_b, (size_t)512 * 64));
-            }
-            if (gather0) HIPCHK(h, launch_enc_gather_grad(st, h->ref_g17, Cr, h->n_in, h->enc_map, h->gacc[ps.ref_w[l]], h->kr * h->kr));
-            if (l > 0 && !(l == 1 && fuse01)) {
-                if (h->gen_ref)
-                    PROF(h, st, "gen_conv", launch_gen_conv_dgrad(st, b.rdpre[l], h->gen_wref[l], b.ract[0][l - 1], b.rdpre[l - 1], NT, sz[l],
-                                                                  Cr, Cr, Cr, h->kr, h->rs));
-                else if (refine_f16_ok(h))
-                    PROF(h, st, "refine_dgrad", launch_conv3x3_s2_dgrad_f16x3(st, b.rdpre[l], h->ref_wb16[l], h->ref_wmeta[l] + 2,
-                                                                              b.ract[0][l - 1], b.rdpre[l - 1], NT, sz[l], Cr, h->precision == 0));
-                else
-                    PROF(h, st, "refine_dgrad", launch_conv3x3_gather_dgrad(st, b.rdpre[l], h->ref_wb[l], b.ract[0][l - 1],
-                                                                            b.rdpre[l - 1], NT, sz[l], sz[l], Cr, 2));
-            }
-        }
-    }
+    if (int r = refine_stack_backward(h, st, T * N, h->calls.fwd_split)) return r;
     bool flat = true;                                          // caller's gradients back to back in the same order?
     for (size_t p = 0; p < h->params.size() && flat; ++p)
         flat = param_grads[p] && param_grads[p] == param_grads[0] + (h->gacc[p] - h->gacc_arena);
@@ -2406,7 +2412,7 @@ int iodine_debug_copy(iodine_handle* h, void* stream, const char* name, int iter
     const size_t N = (size_t)b.B * b.K, P = h->P, L = h->L;        // the shape of the call that left the buffers, not the run shape
     if (iter < 0 || iter > b.T) return h->fail(IODINE_ERR_INVALID, "iodine_debug_copy: bad iteration index");
     const std::string s(name);
-    const float* src = nullptr; size_t n = 0;
+    const float* src = nullptr; size_t n = 0; bool join = false;      // join: enc in the split layout, back into the reference's 17 (+3 pad) channel order
     if (s == "z") { src = b.z[iter]; n = N * L; }
     else if (s == "dec_out") { src = b.dec_out; n = N * P * 4; }
     else if (s == "g") { src = b.g; n = N * P * 4; }
@@ -2415,14 +2421,7 @@ int iodine_debug_copy(iodine_handle* h, void* stream, const char* name, int iter
         // with refine_l0_fused the inference loop never writes the encoding (kernels_refl0.hip keeps it on chip) unless stop_after_iters asks
         if (!h->calls.enc_valid)
             return h->fail(IODINE_ERR_STATE, "iodine_debug_copy: enc was not materialised by the last call (set stop_after_iters >= 0 or refine_l0_fused=0)");
-        if (refine_split_on(h)) {                          // joined back into the reference's 17 (+3 pad) channel order
-            if (n_floats) *n_floats = n;
-            if (!dst) return IODINE_OK;
-            if (n > max_floats) return h->fail(IODINE_ERR_INVALID, "iodine_debug_copy: destination too small");
-            HIPCHK(h, launch_enc_join((hipStream_t)stream, b.enck[iter], b.encs[iter], dst, (int)N, b.K, (int)P));
-            return IODINE_OK;
-        }
-        src = b.enc[iter];
+        src = b.enc[iter]; join = ref_form(h).split;
     }
     else if (s == "latent") { src = b.latent[iter]; n = N * 4 * L; }
     else if (s == "g_pm") { src = b.g_pm[iter]; n = N * L; }
@@ -2449,7 +2448,8 @@ int iodine_debug_copy(iodine_handle* h, void* stream, const char* name, int iter
     if (n_floats) *n_floats = n;
     if (dst) {
         if (n > max_floats) return h->fail(IODINE_ERR_INVALID, "iodine_debug_copy: destination too small");
-        HIPCHK(h, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        if (join) HIPCHK(h, launch_enc_join((hipStream_t)stream, b.enck[iter], b.encs[iter], dst, (int)N, b.K, (int)P));
+        else HIPCHK(h, hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     return IODINE_OK;
 }

@@ -14,7 +14,7 @@
 // after round 5 (what each kernel below gained and where its remaining time goes).
 //
 // Layouts: activations NHWC with a channel stride `ldc` >= Ci (the 17-of-20 refinement input); weights re-packed at set_params to
-// [tap = ky * k + kx][ci][co] (co fastest: coalesced over the threads of a pixel); stride s in {1, 2}, padding k / 2.
+// [tap = ky * k + kx][ci][co] (co fastest: coalesced over the threads of a pixel); stride s in 1..8 (REF.STRIDE), padding k / 2.
 #include "common.h"
 
 namespace {

@@ -64,6 +64,19 @@ def test_reconstruct_and_train_step_match_oracle(name):
     assert not bad, bad
 
 
+def test_gather_family_reconstruct_matches_oracle():
+    """A refinement stack with an odd layer input (48 pixels, five layers: 48, 24, 12, 6, 3) runs on the gather kernels, the one family of
+    the stack that no entry of CASES reaches.  Reconstruct only: the family has no data gradient at odd sizes, a training step is refused
+    (test_gpu_dispatch.py::test_gather_family_launch_counts)."""
+    arch = O.tiny_arch(slots=2, iters=1, img_size=48, ref_layers=5)
+    params, x, eps = _case(arch, 1, seed=120)
+    ref = O.reconstruct(x, eps, params, arch)
+    m = make_hip_model(arch, params)
+    pred, mask, mean = m.reconstruct(x.to(DEV), eps.to(DEV))
+    assert rel_err(m.elbo_terms.cpu()[:, 0], ref['elbos']) < 1e-4
+    assert rel_err(pred.cpu(), ref['pred']) < 2e-4 and rel_err(mask.cpu(), ref['mask']) < 2e-4
+
+
 def test_unsupported_configurations_fail_loudly():
     from iodine_amd import IODINE
     from iodine_amd.model import arch_namespace
