@@ -6,6 +6,7 @@ box with the source snapshot (it is git-ignored, not gpurun-ignored).
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -15,8 +16,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, 'libiodine_hip.so')
-SOURCES = ['kernels_conv.hip', 'kernels_convws.hip', 'kernels_out.hip', 'kernels_pixel.hip', 'kernels_pixmap.hip', 'kernels_render.hip', 'kernels_misc.hip', 'kernels_clip.hip', 'kernels_objects.hip', 'kernels_edit.hip', 'kernels_train.hip', 'kernels_wgrad32.hip', 'kernels_refine.hip', 'kernels_refbwd.hip', 'kernels_refws.hip', 'kernels_refl0.hip', 'kernels_pack.hip', 'kernels_generic.hip', 'kernels_gensplit.hip', 'kernels_gens2.hip', 'kernels_genl0.hip', 'iodine_api.cpp', 'iodine_pad.cpp', 'iodine_ops.cpp']
-HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'iodine_internal.h'), os.path.join(CSRC, 'pixel_terms.h'), os.path.join(CSRC, 'pack_bodies.h'), os.path.join(ROOT, 'include', 'iodine_hip.h')]
+SOURCES = ['kernels_conv.hip', 'kernels_convws.hip', 'kernels_out.hip', 'kernels_pixel.hip', 'kernels_pixmap.hip', 'kernels_render.hip', 'kernels_misc.hip', 'kernels_clip.hip', 'kernels_objects.hip', 'kernels_edit.hip', 'kernels_train.hip', 'kernels_wgrad.hip', 'kernels_gemm.hip', 'kernels_headbwd.hip', 'kernels_outbwd.hip', 'kernels_wgradws.hip', 'kernels_wgrad32.hip', 'kernels_refine.hip', 'kernels_refbwd.hip', 'kernels_refws.hip', 'kernels_refl0.hip', 'kernels_pack.hip', 'kernels_generic.hip', 'kernels_gensplit.hip', 'kernels_gens2.hip', 'kernels_genl0.hip', 'iodine_api.cpp', 'iodine_pad.cpp', 'iodine_ops.cpp']
+
+
+def _headers():
+    """Every header a source can include: csrc/*.h and the ABI header.  Taken from the directory, so a new header is a dependency of
+    every object and part of source_digest() without being listed anywhere."""
+    return sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [os.path.join(ROOT, 'include', 'iodine_hip.h')]
+
+
+HEADERS = _headers()
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function',
          '-Wno-unused-result'] + os.environ.get('IODINE_EXTRA_HIPCC_FLAGS', '').split()   # e.g. -DIODINE_TILE_PROF (tools only)
 
@@ -75,12 +84,12 @@ def source_digest() -> str:
     under profiles/ (PMC traffic per launch) carry this digest; bench.py quotes them only while it still matches."""
     import hashlib
     h = hashlib.sha256()
-    for s in sorted(SOURCES) + ['common.h', 'iodine_internal.h', 'pixel_terms.h', 'pack_bodies.h']:
-        p = os.path.join(CSRC, s)
+    headers = _headers()                            # (not HEADERS: CSRC as it is now)
+    for p in [os.path.join(CSRC, s) for s in sorted(SOURCES)] + headers[:-1]:
         if os.path.exists(p):
-            h.update(s.encode())
+            h.update(os.path.basename(p).encode())
             h.update(open(p, 'rb').read())
-    h.update(open(os.path.join(ROOT, 'include', 'iodine_hip.h'), 'rb').read())
+    h.update(open(headers[-1], 'rb').read())
     return h.hexdigest()
 
 

@@ -1,15 +1,9 @@
-// Shared device helpers and launcher declarations for libiodine_hip.so (gfx950 only).
+// Host-side declarations of libiodine_hip.so (gfx950 only): the kernel launchers, the packed-weight geometry and the small
+// per-device caches.  Device-side helpers are in device.h.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "device.h"
 #include <algorithm>
 #include <atomic>
-#include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define IOD_DEVINL __device__ __forceinline__
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) belongs to (function, device): every launcher instance keeps a bit mask of
 // the devices it has configured (`devs`, a function-local static) instead of one process-wide flag, so a second device in the
@@ -53,97 +47,6 @@ extern int g_iod_xskip;
 #else
 #define IOD_XSKIP(bit) do { } while (0)
 #endif
-
-// ELU with alpha = 1 (torch.nn.functional.elu): x > 0 ? x : expm1(x)
-IOD_DEVINL float elu1(float v) { return v > 0.f ? v : expm1f(v); }
-// the same through v_exp_f32 (absolute error ~1e-7, as in the conv epilogues): the streaming kernels are otherwise VALU-bound on expm1f
-IOD_DEVINL float elu1_fast(float v) { return v > 0.f ? v : __expf(v) - 1.f; }
-// derivative of ELU expressed through its OUTPUT a = ELU(x): a > 0 ? 1 : a + 1
-IOD_DEVINL float elu1_grad_from_out(float a) { return a > 0.f ? 1.f : a + 1.f; }
-IOD_DEVINL float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-
-// max over the 64 lanes of a wave, returned to every lane.  DPP steps inside the 16-lane rows, row broadcasts across
-// them and one v_readlane - about a dozen VALU instructions; the __shfl_xor butterfly it replaces is six dependent
-// ds_bpermute round trips (~100 cycles each), which sat on the staging path of every tile chunk.
-IOD_DEVINL float wave_max_f32(float v)
-{
-    auto dpp = [](float x, auto ctrl, auto rmask) {
-        const int r = __builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), decltype(ctrl)::value,
-                                                  decltype(rmask)::value, 0xf, false);
-        return __int_as_float(r);
-    };
-    using std::integral_constant;
-    v = fmaxf(v, dpp(v, integral_constant<int, 0xB1>{}, integral_constant<int, 0xf>{}));     // quad_perm [1,0,3,2]
-    v = fmaxf(v, dpp(v, integral_constant<int, 0x4E>{}, integral_constant<int, 0xf>{}));     // quad_perm [2,3,0,1]
-    v = fmaxf(v, dpp(v, integral_constant<int, 0x141>{}, integral_constant<int, 0xf>{}));    // row_half_mirror
-    v = fmaxf(v, dpp(v, integral_constant<int, 0x140>{}, integral_constant<int, 0xf>{}));    // row_mirror: row max in all 16 lanes
-    v = fmaxf(v, dpp(v, integral_constant<int, 0x142>{}, integral_constant<int, 0xa>{}));    // row_bcast:15 into rows 1, 3
-    v = fmaxf(v, dpp(v, integral_constant<int, 0x143>{}, integral_constant<int, 0xc>{}));    // row_bcast:31 into rows 2, 3
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
-// Phase timing of the tile / weight-gradient kernels (tools/tile_phase_prof.md; build with IODINE_EXTRA_HIPCC_FLAGS=-DIODINE_TILE_PROF): thread 0 of every
-// block accumulates the s_memtime deltas between phase boundaries and writes them to a per-kernel __device__ buffer
-// [block][8]; compiled out of the product library.
-#ifdef IODINE_TILE_PROF
-constexpr int TP_MAXBLK = 16384;
-#define TP_DECL unsigned long long tp_last = __builtin_amdgcn_s_memtime(); unsigned tp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define TP_STAMP(slot)                                                                      \
-    do {                                                                                    \
-        const unsigned long long tp_now = __builtin_amdgcn_s_memtime();                     \
-        tp_acc[slot] += (unsigned)(tp_now - tp_last);                                       \
-        tp_last = tp_now;                                                                   \
-    } while (0)
-#define TP_FLUSH(buf)                                                                       \
-    if (threadIdx.x == 0 && blockIdx.x < TP_MAXBLK)                                         \
-        for (int i_ = 0; i_ < 8; ++i_) buf[blockIdx.x * 8 + i_] = tp_acc[i_]
-#else
-#define TP_DECL
-#define TP_STAMP(slot)
-#define TP_FLUSH(buf)
-#endif
-
-
-// ---- helpers of the split-fp16 weight-gradient kernels (transposing stagers) ----------
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
-// out[e] = in[(e + r) & 3] with conditional moves only (a runtime-indexed vector would be demoted to scratch)
-IOD_DEVINL float4 rot4(const float4 v, int r)
-{
-    const bool b0 = r & 1, b1 = r & 2;
-    float4 t;
-    t.x = b0 ? v.y : v.x; t.y = b0 ? v.z : v.y; t.z = b0 ? v.w : v.z; t.w = b0 ? v.x : v.w;
-    float4 o;
-    o.x = b1 ? t.z : t.x; o.y = b1 ? t.w : t.y; o.z = b1 ? t.x : t.z; o.w = b1 ? t.y : t.w;
-    return o;
-}
-
-// (x0, x1) -> packed fp16 pairs hi, lo with x = hi + lo: hi = x rounded toward zero to fp16 (v_cvt_pkrtz: the 11 leading bits for the scaled
-// range), lo = x - hi (exact in fp32; hipcc emits v_fma_mix_f32 with the fp16 hi as a source and folds the caller's power-of-two scale multiply
-// into it), each pair packed by one v_cvt_pkrtz: 6 VALU instructions per pair where the mask-and-subtract form took 8 - every split site was
-// instruction-issue-bound (one VALU instruction per 4 cycles and wave).  Same bits as the mask form except below the fp16 normal range, where
-// lo now also carries what the conversion of hi dropped.
-IOD_DEVINL unsigned pack_hi_lo(float x0, float x1, unsigned& lo_out)
-{
-    typedef __fp16 h2_ __attribute__((ext_vector_type(2)));
-    const h2_ hi = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-    const h2_ lo = __builtin_amdgcn_cvt_pkrtz(x0 - (float)hi.x, x1 - (float)hi.y);
-    unsigned uh;
-    __builtin_memcpy(&uh, &hi, 4); __builtin_memcpy(&lo_out, &lo, 4);
-    return uh;
-}
-
-// power-of-two scale for a tile with max |x| = mx, keeping the current one while mx*cur stays in [2^9, 2^14.5)
-IOD_DEVINL float tile_scale(float mx, float cur)
-{
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return cur;
-    const float t = mx * cur;
-    if (t >= 512.f && t < 23170.f) return cur;
-    const int e = (int)((__float_as_uint(mx) >> 23) & 0xffu) - 127;
-    int se = 12 - e;
-    se = se > 100 ? 100 : (se < -100 ? -100 : se);
-    return __uint_as_float((unsigned)(127 + se) << 23);
-}
 
 // ---- packed conv-weight geometry (shared by host packer and kernels) ------------------
 // A 3x3 conv with CIN (padded) input channels is cut into chunks of CC channels.  Inside a
@@ -265,7 +168,7 @@ size_t refine_head_lds_bytes(int C, int H, int L, int split);
 hipError_t launch_pack_dec_out(hipStream_t st, const float* w, float* wk, int C);
 hipError_t launch_conv3x3_gather_dgrad(hipStream_t st, const float* d, const float* wpk, const float* aux, float* out,
                                        int N, int big_h, int big_w, int c, int stride);
-// kernels_train.hip
+// kernels_wgrad.hip
 int wgrad_tile_blocks(int N, int S);
 hipError_t launch_conv3x3_wgrad_tile(hipStream_t st, const float* a, const float* d, float* part, float* part_b, int N,
                                      int S, int ci, int nco, int* nparts, int* ncop, int* nbias_parts);
@@ -275,6 +178,7 @@ constexpr int WGRAD_FOLD = 32;    // tiles left after the first reduction stage;
 hipError_t launch_wgrad_reduce(hipStream_t st, const float* part, int nparts, int ci_pad, int co_pad, int O_real,
                                int I_real, int I_dst, float alpha, float* dst, float* fold = nullptr,
                                const float* part_b = nullptr, int nb = 0, float* dst_b = nullptr);
+// kernels_gemm.hip
 hipError_t launch_colsum(hipStream_t st, const float* src, int rows, int cols, int ld, float alpha, float* dst);
 hipError_t launch_colsum_tall(hipStream_t st, const float* src, int rows, int cols, float alpha, float* dst, float* tmp,
                               size_t tmp_elems);
@@ -284,6 +188,7 @@ hipError_t launch_sgemm(hipStream_t st, int ta, int tb, int M, int N, int K, flo
 bool sgemm_tn_mfma_ok(int M, int N, int K);
 hipError_t launch_sgemm_tn_mfma(hipStream_t st, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
                                 float beta, float* C, int ldc, int mode, int mode_c, int a_rowmajor = 0);
+// kernels_train.hip
 hipError_t launch_l0_tap_sums(hipStream_t st, const float* Rc, float* RT, int N, int C);
 hipError_t launch_l0_latent_wgrad(hipStream_t st, const float* Rc, const float* z, int N, int L, int C, float alpha, float* gw);
 hipError_t launch_l0_coord_grads(hipStream_t st, const float* D, const float* lin, int S, int C, int L, float alpha,
@@ -296,6 +201,7 @@ hipError_t launch_axpy_dev(hipStream_t st, const float* x, float alpha, const fl
 // y = *s_dev * y + add in place (s_dev NULL: factor 0; add NULL: nothing added)
 hipError_t launch_scale_dev_add(hipStream_t st, float* y, const float* s_dev, const float* add, int n);
 hipError_t launch_mean2(hipStream_t st, const float* a, const float* b, int n, float* out);
+// kernels_headbwd.hip
 hipError_t launch_lstm_bwd_pointwise(hipStream_t st, const float* gates, const float* c0, const float* c1,
                                      const float* dc1_read, const float* dh1, const float* dc1_carry, float* dgates,
                                      float* dc0, int N, int H);
@@ -483,11 +389,13 @@ bool refine_bwd01_ok(int S, int c);
 hipError_t launch_refine_bwd01(hipStream_t st, const float* rd1, const void* wpk, const float* wmeta, const float* act0, const float* enck,
                                const float* encs, float* part, float* part_b, int NT, int S, int c, int kdiv, int* nparts, int* cipad,
                                int* nbias_parts);
+// kernels_outbwd.hip
 hipError_t launch_dec_out_wgrad_gemm_f16x3(hipStream_t st, const float* a, const float* g, float* part, float* part_b, int N,
                                            int S, int c, int* nparts, int* nbias_parts);
 hipError_t launch_dec_out_bwd_fused_f16x3(hipStream_t st, const float* a, const float* g, const void* wpk, const float* wmeta,
                                           float* out, float* tmax, float* part, float* part_b, int N, int S, int c,
                                           int* nparts, int* nbias_parts, float alpha = 1.f, int accum = 0);
 // alpha / accum (round 5): part / part_b = (accum ? part : 0) + alpha x this launch - a block's partial tile kept over the decoder passes
+// kernels_wgradws.hip
 hipError_t launch_conv3x3_wgrad_f16x3_ws(hipStream_t st, const float* a, const float* d, float* part, float* part_b, int N,
                                          int S, int ci, int nco, int* nparts, int* ncop, int* nbias_parts, float alpha = 1.f, int accum = 0);

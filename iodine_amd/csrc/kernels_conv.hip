@@ -422,10 +422,6 @@ hipError_t launch_dec_out(hipStream_t st, const float* in, const float* wk, cons
 // subnormals otherwise); activations are split while being staged into LDS.
 //   wpk16[chunk][tap][term hi/lo][kh][co] = 8 fp16 (channels chunk*16 + kh*8 .. +7) * wscale
 // =========================================================================================
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 // max |w| of a tensor -> meta[0] = scale (power of two with max*scale in [2^12, 2^13)), meta[1] = 1/scale
 __global__ __launch_bounds__(1024)
 void weight_scale_kernel(const float* __restrict__ w, int n, float* __restrict__ meta)
@@ -519,19 +515,8 @@ void conv3x3_tile_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
     //   * halo pixels outside the image and idle lanes carry the offset 0x80000000 (>= num_records): the hardware returns
     //     0, there is no select after the load;
     //   * hipcc does not count asm loads, so the waits below are explicit counted vmcnt (loads return in order).
-    typedef int i32x4_ __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-    auto make_rsrc = [&](const void* base, unsigned bytes) {
-        const unsigned long long p = (unsigned long long)base;
-        i32x4_ r;
-        r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-        r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32));          // stride 0, no swizzle
-        r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-        r.w = 0x00020000;                                                         // raw dword buffer (gfx9 / CDNA)
-        return r;
-    };
-    const i32x4_ rsrc_in = make_rsrc(in + (size_t)n * S * S * CIN, (unsigned)(S * S * CIN * 4));
-    const i32x4_ rsrc_w = make_rsrc(wpk, (unsigned)(NCHUNK * W_U4 * 16));
+    const i32x4 rsrc_in = iod_make_rsrc(in + (size_t)n * S * S * CIN, (unsigned)(S * S * CIN * 4));
+    const i32x4 rsrc_w = iod_make_rsrc(wpk, (unsigned)(NCHUNK * W_U4 * 16));
 // (IOD_SGPR_SETTLE before a group of asm memory instructions: an SGPR written by the SALU needs 5 wait states before a
 //  VMEM instruction reads it, and hipcc's hazard recognizer does not look inside inline asm; naming the SGPR operands as
 //  inputs of the s_nop puts their producers in front of it)
@@ -570,7 +555,7 @@ void conv3x3_tile_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
     // drain vmcnt(0), i.e. wait for the prefetch it has just issued).  Input chunks are fetched two steps ahead into two
     // alternating register sets, the (L2-resident) packed weights one step ahead.
     f32x4 rinA[NIN], rinB[NIN];                          // native vectors: they are inline-asm operands
-    u32x4_ rw[NW];
+    u32x4 rw[NW];
     auto prefetch_in = [&](int chunk, f32x4 (&rin)[NIN]) {
         const int soff = chunk * 64;                         // 16 channels
         IOD_SGPR_SETTLE(rsrc_in, soff);
@@ -742,7 +727,7 @@ void conv3x3_tile_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
     f32x4 ax[NEP];
     auto prefetch_aux = [&]() {
         if constexpr (EPI == EPI_MUL_ELUGRAD || EPI == EPI_L0ROWS) {
-            const i32x4_ rsrc_aux = make_rsrc(aux + (size_t)n * S * S * COUT, (unsigned)(S * S * COUT * 4));
+            const i32x4 rsrc_aux = iod_make_rsrc(aux + (size_t)n * S * S * COUT, (unsigned)(S * S * COUT * 4));
 #pragma unroll
             for (int j = 0; j < NEP; ++j) {
                 const int soff = (((j * PPI) / 16) * S + (j * PPI) % 16) * COUT * 4;
@@ -791,7 +776,7 @@ void conv3x3_tile_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
     // operations on the slot-image: one byte offset per 32-pixel tile and lane, channel group in the scalar offset.
     static_assert(EPI == EPI_BIAS_ELU || EPI == EPI_MUL_ELUGRAD || EPI == EPI_L0ROWS, "the C -> 4 output conv has its own GEMM-form kernel");
     {
-        const i32x4_ rsrc_out = make_rsrc(out + (size_t)n * S * S * COUT, (unsigned)(S * S * COUT * 4));
+        const i32x4 rsrc_out = iod_make_rsrc(out + (size_t)n * S * S * COUT, (unsigned)(S * S * COUT * 4));
         f32x4 b4 = f32x4{0.f, 0.f, 0.f, 0.f};
         if constexpr (EPI == EPI_BIAS_ELU) {
             const float4 t = *reinterpret_cast<const float4*>(bias + seg * 4);

@@ -23,8 +23,6 @@
 #include <cstdio>
 #include <vector>
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 // ---- packed weights: [cout group][chunk of 32 cin][tap][hi/lo][lane][8 fp16] = the A operand of v_mfma_f32_16x16x32_f16
 // (lane l: row = cout 16 cg + l % 16, k = cin 32 c + 8 (l / 16) .. + 7), pre-scaled by meta[0] (weight_scale_kernel) -------
 __global__ void pack_conv_weights_ws_kernel(const float* __restrict__ src, int C, int tflip, const float* __restrict__ meta,
@@ -85,26 +83,6 @@ __device__ unsigned long long g_ws_ts[TP_MAXBLK * 16];
 __device__ unsigned long long g_ws_se[TP_MAXBLK * 2];       // [block]: s_memtime at the block's start / end
 #endif
 
-template <int I, int N, typename F>
-IOD_DEVINL void ws_static_for(F&& f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        ws_static_for<I + 1, N>(f);
-    }
-}
-
-// power-of-two scale that puts max |x| = mx into [2^12, 2^13) (a pure function of mx: results must not depend on which
-// block processed which tile before)
-IOD_DEVINL float fresh_scale(float mx)
-{
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.f;
-    const int e = (int)((__float_as_uint(mx) >> 23) & 0xffu) - 127;
-    int se = 12 - e;
-    se = se > 100 ? 100 : (se < -100 ? -100 : se);
-    return __uint_as_float((unsigned)(127 + se) << 23);
-}
-
 // sum over the pixel lanes of the whole-pixel layout (lane = pl * SEGS + seg): all lanes with the same seg, result in every
 // lane.  gfx950 lane swaps / DPP, no LDS: v_permlane32_swap (halves), v_permlane16_swap (odd / even rows of 16), row_ror:8.
 template <int SEGS>
@@ -158,21 +136,11 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
 
     using std::integral_constant;
-    typedef int i32x4_ __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cg = wv % NCG, pg = wv / NCG;
     const int lpx = lane & 15, lkb = lane >> 4;
 
-    auto make_rsrc = [&](const void* base, unsigned bytes) {
-        const unsigned long long p = (unsigned long long)base;
-        i32x4_ r;
-        r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-        r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32));
-        r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-        r.w = 0x00020000;
-        return r;
-    };
 #define WS_BLOAD4(dst, voff, rsrc, soff) \
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory")
 // cache policy of the output stores (experiment hook): 0 default, 1 nt, 2 sc1, 3 sc0 sc1
@@ -255,7 +223,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
     auto issue_loads = [&](int t, int chunk) {
         int n, ty, tx;
         tile_coords(t, n, ty, tx);
-        const i32x4_ rsrc = make_rsrc(in + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
+        const i32x4 rsrc = iod_make_rsrc(in + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
         unsigned goff[NIN];
 #pragma unroll
         for (int k = 0; k < NIN; ++k) {
@@ -404,7 +372,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
             }
             __builtin_amdgcn_sched_barrier(0);
         };
-        ws_static_for<0, NS>(step);                          // straight-line code, literal LDS offsets
+        static_for<NS>(step);                          // straight-line code, literal LDS offsets
     };
 #undef WS_DSR128
 
@@ -447,7 +415,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
     vm_wait(integral_constant<int, 0>{});
     float cur_scale = 1.f;
     if constexpr (!F32) cur_scale = fresh_scale(wave_max_f32(lane < 36 ? tmv : 0.f));
-    ws_static_for<0, NIN>([&](auto kc) { convert_k(kc, 0, cur_scale); });
+    static_for<NIN>([&](auto kc) { convert_k(kc, 0, cur_scale); });
     if (nstage > 1) issue_stage(1);
     bool first = true;
     float next_scale = cur_scale;
@@ -502,7 +470,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
         // ---- epilogue ----
         const float inv = inv_w / cur_scale;
         cur_scale = next_scale;                              // (the scale of the tile whose chunk 0 was just staged)
-        const i32x4_ rsrc_out = make_rsrc(out + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
+        const i32x4 rsrc_out = iod_make_rsrc(out + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
         if constexpr (XPOSE) {
             // Through LDS, so that global traffic is whole pixels (1 KB contiguous per instruction; the direct form - 16 pixels
             // x 64 bytes per instruction - cost 7 % of the kernel in partial-line stores).  The tile goes into the buffer the last
@@ -517,7 +485,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
                 // the ELU' operand (whole pixels, like the stores) is requested before the barriers: in the training step it
                 // comes from HBM, not from a cache
                 // (first half now - the fragment registers are free -, second half once the accumulators are in LDS)
-                const i32x4_ rsrc_aux = make_rsrc(aux + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
+                const i32x4 rsrc_aux = iod_make_rsrc(aux + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
 #pragma unroll
                 for (int j = 0; j < NEP / 2; ++j) {
                     const int soff = ((((j * PPI) / 16) << lgS) + (j * PPI) % 16) * C * 4;
@@ -531,7 +499,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
             for (int y = 0; y < RW; ++y)
                 *reinterpret_cast<f32x4*>(sb + ((pg * RW + y) * 16 + lpx) * EPS + (16 * cg + 4 * lkb) * 4) = acc[y] * inv;
             if constexpr (GRADF) {
-                const i32x4_ rsrc_aux = make_rsrc(aux + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
+                const i32x4 rsrc_aux = iod_make_rsrc(aux + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
 #pragma unroll
                 for (int j = NEP / 2; j < NEP; ++j) {
                     const int soff = ((((j * PPI) / 16) << lgS) + (j * PPI) % 16) * C * 4;
@@ -575,7 +543,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
             f32x4 pv[PB];
             f32x4 rtot = f32x4{0.f, 0.f, 0.f, 0.f};                    // (row-sum forms) running interior sum of the current tile row
             (void)rtot;
-            ws_static_for<0, NEP>([&](auto jc) {
+            static_for<NEP>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 if constexpr (j % PB == 0) {
 #pragma unroll
@@ -645,7 +613,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
                     }
                 } else {
                     vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-                    const unsigned vb = vbase; const i32x4_ ro = rsrc_out;
+                    const unsigned vb = vbase; const i32x4 ro = rsrc_out;
                     const int soff = ((((j * PPI) / 16) << lgS) + (j * PPI) % 16) * C * 4;
 #ifdef WS_ABL_NOSTORE
                     asm volatile("" :: "v"(v), "v"(vb), "s"(ro), "s"(soff) : "memory");

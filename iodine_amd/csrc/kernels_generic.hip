@@ -19,8 +19,6 @@
 
 namespace {
 
-IOD_DEVINL float gen_elu(float v) { return v > 0.f ? v : expm1f(v); }
-
 // w [Co][Ci][k][k] -> wt [k*k][Ci][Co]
 __global__ void gen_pack_weights_kernel(const float* __restrict__ w, int Co, int Ci, int kk, float* __restrict__ wt)
 {
@@ -59,7 +57,7 @@ __global__ void gen_conv_fwd_kernel(const float* __restrict__ in, const float* _
         }
     }
     if (seg) acc += tot;
-    out[idx] = elu ? gen_elu(acc) : acc;
+    out[idx] = elu ? elu1(acc) : acc;
 }
 
 // din[n][y][x][ci] = f'(aux) * sum_{tap, co} dout[n][oy][ox][co] * wt[tap][ci][co]   with oy * s + ky - pad = y (ox likewise);
@@ -242,7 +240,6 @@ void gen_conv_mfma_kernel(const float* __restrict__ in, const float* __restrict_
     // once per kernel, the bounds once per tile (byte offsets into the slot-image, 0x80000000 = outside: the buffer load returns zeros), and a
     // chunk's loads are one select and one buffer load each, issued BETWEEN the MFMAs of the chunk's first k-step (hand-placed with
     // sched_group_barrier); so are the LDS writes of the staged chunk (last k-step) and the previous tile's epilogue (first k-step).
-    typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
     int rel[NLD], pyx[NLD], lw[NLD];
     const int q4 = 4 * (tid % NQ);                            // first channel of this thread's quad within a chunk (256 % NQ == 0: the same for every i)
 #pragma unroll
@@ -252,7 +249,7 @@ void gen_conv_mfma_kernel(const float* __restrict__ in, const float* __restrict_
         pyx[i] = e < NPX * NQ ? (py | pxx << 8) : (255 | 255 << 8);             // (255: never inside)
         lw[i] = e < NPX * NQ ? q4 * NPXP + px : 2 * CCH * NPXP;                  // (threads past the end of the table: the dump area)
     }
-    u32x4_ rin[NLD];
+    u32x4 rin[NLD];
     unsigned tvo[NLD];                                         // tile being fetched: byte offsets of the table's elements
     __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, 0, 0x00020000);
     const int img_bytes = S * S * ldin * 4;
@@ -291,10 +288,10 @@ void gen_conv_mfma_kernel(const float* __restrict__ in, const float* __restrict_
     const bool vec_all = (ldout & 3) == 0 && (Cn & 3) == 0;   // 16-byte stores for every lane (else: the plain epilogue at the end of the tile)
     constexpr bool DEFER = NH > 1 && KS < 7;                  // (7 x 7: the two operand sets leave no registers for it - plain order, no spills)
     f32x4 res[4];
-    u32x4_ ax[4];
+    u32x4 ax[4];
     unsigned evo[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { res[r] = f32x4{0.f, 0.f, 0.f, 0.f}; ax[r] = u32x4_{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u}; evo[r] = 0x80000000u; }
+    for (int r = 0; r < 4; ++r) { res[r] = f32x4{0.f, 0.f, 0.f, 0.f}; ax[r] = u32x4{0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u}; evo[r] = 0x80000000u; }
     __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0, 0x00020000);
     const int out_bytes = S * S * ldout * 4;
     auto epilogue_math = [&]() {
@@ -308,7 +305,7 @@ void gen_conv_mfma_kernel(const float* __restrict__ in, const float* __restrict_
                 v[j] = elu ? ev : v[j];
                 v[j] *= elu1_grad_from_out(__uint_as_float(ax[r][j]));
             }
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4_{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])},
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])},
                                                    rs_out, (int)evo[r], 0, 0);
         }
     };
@@ -588,8 +585,7 @@ void gen_wgrad_rows_kernel(const float* __restrict__ in, const float* __restrict
             if (f < nd) { voff[k] = (unsigned)((x * Co + c4 * 4) * 4); loff[k] = nit * Wp * 32 + ((c4 >> 3) * Sd + x) * 32 + (c4 & 7) * 4; }
         }
     }
-    typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-    u32x4_ rv[MAXV];
+    u32x4 rv[MAXV];
     auto fetch = [&](long long row) {
         const int y = (int)(row % S);
         const long long n = row / S;
@@ -607,7 +603,7 @@ void gen_wgrad_rows_kernel(const float* __restrict__ in, const float* __restrict
     };
     auto commit = [&]() {
 #pragma unroll
-        for (int k = 0; k < MAXV; ++k) *reinterpret_cast<u32x4_*>(smem_gw + loff[k]) = rv[k];
+        for (int k = 0; k < MAXV; ++k) *reinterpret_cast<u32x4*>(smem_gw + loff[k]) = rv[k];
     };
     f32x16 acc[KS];
 #pragma unroll

@@ -20,8 +20,6 @@ namespace {
 
 constexpr int KMAX = GEN_L0_KMAX;
 
-IOD_DEVINL float l0_elu(float v) { return v > 0.f ? v : expm1f(v); }
-
 // cterm[p][co] = bias[co] + sum_{valid taps} (wt[tap][L][co] lin[x + kx - PAD] + wt[tap][L + 1][co] lin[y + ky - PAD])
 __global__ void gen_l0_coord_kernel(const float* __restrict__ wt, const float* __restrict__ bias, const float* __restrict__ lin, int L, int S,
                                     int Co, int k, float* __restrict__ cterm)
@@ -110,13 +108,13 @@ __global__ __launch_bounds__(256) void gen_l0_fwd_kernel(const float* __restrict
         const float4 c = *reinterpret_cast<const float4*>(ct), s11 = *reinterpret_cast<const float4*>(q11), s01 = *reinterpret_cast<const float4*>(q01),
                      s10 = *reinterpret_cast<const float4*>(q10), s00 = *reinterpret_cast<const float4*>(q00);
         float4 r;
-        r.x = l0_elu(c.x + ((s11.x - s01.x) - (s10.x - s00.x)));
-        r.y = l0_elu(c.y + ((s11.y - s01.y) - (s10.y - s00.y)));
-        r.z = l0_elu(c.z + ((s11.z - s01.z) - (s10.z - s00.z)));
-        r.w = l0_elu(c.w + ((s11.w - s01.w) - (s10.w - s00.w)));
+        r.x = elu1(c.x + ((s11.x - s01.x) - (s10.x - s00.x)));
+        r.y = elu1(c.y + ((s11.y - s01.y) - (s10.y - s00.y)));
+        r.z = elu1(c.z + ((s11.z - s01.z) - (s10.z - s00.z)));
+        r.w = elu1(c.w + ((s11.w - s01.w) - (s10.w - s00.w)));
         *reinterpret_cast<float4*>(o) = r;
     } else {
-        o[0] = l0_elu(ct[0] + ((q11[0] - q01[0]) - (q10[0] - q00[0])));
+        o[0] = elu1(ct[0] + ((q11[0] - q01[0]) - (q10[0] - q00[0])));
     }
 }
 

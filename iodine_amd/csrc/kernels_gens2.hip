@@ -22,8 +22,6 @@
 
 namespace {
 
-IOD_DEVINL float gs2_elu(float v) { return v > 0.f ? v : expm1f(v); }
-
 constexpr int GS2_TR = 4, GS2_TC = 16;                       // output positions per block: rows x columns (wave = row)
 
 struct Gs2Geom {
@@ -194,7 +192,7 @@ void gen_s2_conv_kernel(const float* __restrict__ in, const float* __restrict__ 
         float* o = out + opix * g.ldn + c;
         if (MODE == 0) {
             if (bias) { const float4 b4 = *reinterpret_cast<const float4*>(bias + c); v += f32x4{b4.x, b4.y, b4.z, b4.w}; }
-            if (g.elu) v = f32x4{gs2_elu(v.x), gs2_elu(v.y), gs2_elu(v.z), gs2_elu(v.w)};
+            if (g.elu) v = f32x4{elu1(v.x), elu1(v.y), elu1(v.z), elu1(v.w)};
         } else if (aux) {
             const float4 a4 = *reinterpret_cast<const float4*>(aux + opix * g.ldn + c);
             v.x *= elu1_grad_from_out(a4.x); v.y *= elu1_grad_from_out(a4.y);

@@ -27,8 +27,6 @@
 
 namespace {
 
-typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-
 template <int KS, int CCH>
 struct GSplitGeo {
     static constexpr int KK = KS * KS, PAD = KS / 2, TW = 16 + KS - 1, NPX = TW * TW;
@@ -134,7 +132,7 @@ void gsplit_conv_kernel(const float* __restrict__ in, const uint4* __restrict__ 
         pyx[i] = px < NPX ? ((px / TW) | (px % TW) << 8) : (255 | 255 << 8);     // (255: never inside the image)
         lw[i] = px < NPX ? skg * PLANE + px * 16 + (lane & 1) * 8 : -1;
     }
-    u32x4_ rin[NLD];
+    u32x4 rin[NLD];
     unsigned tvo[NLD];
     __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, 0, 0x00020000);
     const int img_bytes = S * S * C * 4;
@@ -222,16 +220,16 @@ void gsplit_conv_kernel(const float* __restrict__ in, const uint4* __restrict__ 
             // one tap per MFMA: the (4 + KS - 1) halo rows of a kernel column kx are read once and shared by the taps (ky, kx) of the four tile rows
 #pragma unroll
             for (int kx = 0; kx < KS; ++kx) {
-                h16x8 bh[4 + KS - 1], bl[4 + KS - 1];
+                f16x8 bh[4 + KS - 1], bl[4 + KS - 1];
 #pragma unroll
                 for (int rr = 0; rr < 4 + KS - 1; ++rr) {
-                    bh[rr] = *reinterpret_cast<const h16x8*>(sb + (rr * TW + kx) * 16);
-                    bl[rr] = *reinterpret_cast<const h16x8*>(sb + HALF + (rr * TW + kx) * 16);
+                    bh[rr] = *reinterpret_cast<const f16x8*>(sb + (rr * TW + kx) * 16);
+                    bl[rr] = *reinterpret_cast<const f16x8*>(sb + HALF + (rr * TW + kx) * 16);
                 }
 #pragma unroll
                 for (int ky = 0; ky < KS; ++ky) {
-                    const h16x8 ah = *reinterpret_cast<const h16x8*>(wh + (ky * KS + kx) * 1024);
-                    const h16x8 al = *reinterpret_cast<const h16x8*>(wl + (ky * KS + kx) * 1024);
+                    const f16x8 ah = *reinterpret_cast<const f16x8*>(wh + (ky * KS + kx) * 1024);
+                    const f16x8 al = *reinterpret_cast<const f16x8*>(wl + (ky * KS + kx) * 1024);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         tacc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[r + ky], tacc[r], 0, 0, 0);
@@ -246,12 +244,12 @@ void gsplit_conv_kernel(const float* __restrict__ in, const uint4* __restrict__ 
                 const int tA = g * TPM, tB = g * TPM + 1 < KK ? g * TPM + 1 : tA;      // (a padded second tap: zero weights, any valid address)
                 const int offA = ((tA / KS) * TW + tA % KS) * 16, offB = ((tB / KS) * TW + tB % KS) * 16;
                 const int off = th ? offB : offA;
-                const h16x8 ah = *reinterpret_cast<const h16x8*>(wh + g * 1024);
-                const h16x8 al = *reinterpret_cast<const h16x8*>(wl + g * 1024);
+                const f16x8 ah = *reinterpret_cast<const f16x8*>(wh + g * 1024);
+                const f16x8 al = *reinterpret_cast<const f16x8*>(wl + g * 1024);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const h16x8 bh = *reinterpret_cast<const h16x8*>(sb + off + r * TW * 16);
-                    const h16x8 bl = *reinterpret_cast<const h16x8*>(sb + HALF + off + r * TW * 16);
+                    const f16x8 bh = *reinterpret_cast<const f16x8*>(sb + off + r * TW * 16);
+                    const f16x8 bl = *reinterpret_cast<const f16x8*>(sb + HALF + off + r * TW * 16);
                     tacc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, tacc[r], 0, 0, 0);
                     tacc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, tacc[r], 0, 0, 0);
                     tacc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, tacc[r], 0, 0, 0);
@@ -416,7 +414,7 @@ void gsplit_wgrad_kernel(const float* __restrict__ in, const float* __restrict__
 #pragma unroll
         for (int kx = 0; kx < KS; ++kx) acc[i][kx] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    h16x8 ones;
+    f16x8 ones;
 #pragma unroll
     for (int j = 0; j < 8; ++j) ones[j] = (_Float16)1.0f;
     if (u0 < u1) fetch(u0);
@@ -433,12 +431,12 @@ void gsplit_wgrad_kernel(const float* __restrict__ in, const float* __restrict__
             for (int kx = 0; kx < KS; ++kx) tacc[kx] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int x0 = 0; x0 < SEG; x0 += 4) {
-                const h16x8 bh = *reinterpret_cast<const h16x8*>(smem_gsw + boff[i] + x0 * 16);
-                const h16x8 bl = *reinterpret_cast<const h16x8*>(smem_gsw + boff[i] + b_img + x0 * 16);
+                const f16x8 bh = *reinterpret_cast<const f16x8*>(smem_gsw + boff[i] + x0 * 16);
+                const f16x8 bl = *reinterpret_cast<const f16x8*>(smem_gsw + boff[i] + b_img + x0 * 16);
 #pragma unroll
                 for (int kx = 0; kx < KS; ++kx) {
-                    const h16x8 ah = *reinterpret_cast<const h16x8*>(s_ah + aoff[i] + (x0 + kx) * 16);
-                    const h16x8 al = *reinterpret_cast<const h16x8*>(s_ah + aoff[i] + a_img + (x0 + kx) * 16);
+                    const f16x8 ah = *reinterpret_cast<const f16x8*>(s_ah + aoff[i] + (x0 + kx) * 16);
+                    const f16x8 al = *reinterpret_cast<const f16x8*>(s_ah + aoff[i] + a_img + (x0 + kx) * 16);
                     tacc[kx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, tacc[kx], 0, 0, 0);
                     tacc[kx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, tacc[kx], 0, 0, 0);
                     tacc[kx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, tacc[kx], 0, 0, 0);

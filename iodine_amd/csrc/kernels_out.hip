@@ -16,12 +16,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-namespace {
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4_ __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-}  // namespace
-
 // TM: the power-of-two scale of a tile comes from the producer's per-cell max side buffer (tmax: 4 floats per 8 x 16 cell, written by the
 // weight-stationary conv / the broadcast layer; max over the 4 x 3 cells the 18 x 18 halo touches) instead of a max over every row-block's
 // own values: the kernel is VALU-issue-bound (compute alone 214 us, loads alone 220 us, together 266 us at cfg3: ~300 instructions per
@@ -51,10 +45,11 @@ void dec_out_stream_f16x3_kernel(const float* __restrict__ in, const uint4* __re
                                                                     //  above would otherwise wait for them as well)
     // persistent blocks: tile t, t + gridDim.x, ...; the descriptor and the lane's row-block offsets are per tile
     int tx = 0, ty = 0, n = 0;
-    i32x4_ rsrc;
+    i32x4 rsrc;
     auto set_tile = [&](int t) {
         tx = t % tiles; t /= tiles;
         ty = t % tiles; n = t / tiles;
+        // (written out, not iod_make_rsrc: through the helper hipcc allocates this kernel's scalar registers differently)
         const unsigned long long p = (unsigned long long)(in + (size_t)n * S * S * C);
         rsrc.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
         rsrc.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32));
@@ -102,7 +97,7 @@ void dec_out_stream_f16x3_kernel(const float* __restrict__ in, const uint4* __re
             unsigned l0, l1, l2, l3;
             const unsigned h0 = pack_hi_lo(a.x, a.y, l0), h1 = pack_hi_lo(a.z, a.w, l1);
             const unsigned h2 = pack_hi_lo(b.x, b.y, l2), h3 = pack_hi_lo(b.z, b.w, l3);
-            const u32x4_ uh = {h0, h1, h2, h3}, ul = {l0, l1, l2, l3};
+            const u32x4 uh = {h0, h1, h2, h3}, ul = {l0, l1, l2, l3};
             f16x8 ah, al;
             __builtin_memcpy(&ah, &uh, 16); __builtin_memcpy(&al, &ul, 16);
 #pragma unroll
@@ -282,7 +277,7 @@ void dec_out_rows_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
 
     f32x4 v0[NLD], v1[NLD], v2[NLD];
     float t0 = 0.f, t1 = 0.f, t2 = 0.f;
-    i32x4_ rsrc;
+    i32x4 rsrc;
     const int tcx = S >> 4, tcy = S >> 3;                           // cells per row / column of the side buffer
 
     for (int ra = r0; ra < r1;) {
@@ -291,7 +286,7 @@ void dec_out_rows_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
         const int yb = min(S, ya + (r1 - ra));
         ra += yb - ya;
         const int G = (yb - ya) / SPR, J = G + 2;                   // output groups, P steps (one group of rows above, one below)
-        {
+        {   // (written out, not iod_make_rsrc: through the helper hipcc orders two scalar additions of this kernel differently)
             const unsigned long long p = (unsigned long long)(in + (size_t)n * S * S * C);
             rsrc.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
             rsrc.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32));
@@ -345,7 +340,7 @@ void dec_out_rows_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
                 unsigned l0, l1, l2, l3;
                 const unsigned h0 = pack_hi_lo(a.x, a.y, l0), h1 = pack_hi_lo(a.z, a.w, l1);
                 const unsigned h2 = pack_hi_lo(b.x, b.y, l2), h3 = pack_hi_lo(b.z, b.w, l3);
-                const u32x4_ uh = {h0, h1, h2, h3}, ul = {l0, l1, l2, l3};
+                const u32x4 uh = {h0, h1, h2, h3}, ul = {l0, l1, l2, l3};
                 f16x8 ah, al;
                 __builtin_memcpy(&ah, &uh, 16); __builtin_memcpy(&al, &ul, 16);
 #pragma unroll
@@ -559,7 +554,7 @@ void dec_out_dgrad_f16x3_kernel(const float4* __restrict__ g, const uint4* __res
             unsigned l0, l1, l2, l3;
             const unsigned h0 = pack_hi_lo(q0.x * scale, q0.y * scale, l0), h1 = pack_hi_lo(q0.z * scale, q0.w * scale, l1);
             const unsigned h2 = pack_hi_lo(q1.x * scale, q1.y * scale, l2), h3 = pack_hi_lo(q1.z * scale, q1.w * scale, l3);
-            const u32x4_ uh = {h0, h1, h2, h3}, ul = {l0, l1, l2, l3};
+            const u32x4 uh = {h0, h1, h2, h3}, ul = {l0, l1, l2, l3};
             f16x8 ah, al;
             __builtin_memcpy(&ah, &uh, 16); __builtin_memcpy(&al, &ul, 16);
 #pragma unroll

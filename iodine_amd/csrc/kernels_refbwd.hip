@@ -26,8 +26,6 @@
 #include <cstdio>
 #include <vector>
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int RB_TH = 4;                         // tile rows (64 x 64 grid); 16 columns
@@ -41,15 +39,6 @@ constexpr int RB_D_DW = 2 * RB_CO * RB_DPL;      // one buffer of gradient plane
 constexpr int RB_RPX = 68;                       // dwords per staged coarse-gradient pixel (64 + 4 pad: spreads the fragment reads over the banks)
 constexpr int RB_R_DW = 27 * RB_RPX;             // one buffer of raw fp32 dpre1 values: the 3 x 9 coarse neighbourhood of a tile
 constexpr size_t RB_LDS = (size_t)(2 * RB_A_DW + 2 * RB_D_DW + 2 * RB_R_DW) * 4 + 192;
-
-IOD_DEVINL float rb_fresh_scale(float mx)
-{
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.f;
-    const int e = (int)((__float_as_uint(mx) >> 23) & 0xffu) - 127;
-    int se = 12 - e;
-    se = se > 100 ? 100 : (se < -100 ? -100 : se);
-    return __uint_as_float((unsigned)(127 + se) << 23);
-}
 
 struct RbFrag { f16x8 h, l; };
 
@@ -70,12 +59,10 @@ IOD_DEVINL RbFrag rb_split8(const float4 a, const float4 b, float scale)
     return f;
 }
 
-typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-
 // raw buffer load of 16 bytes: an offset with bit 31 set is out of range of the 2 GB descriptor and returns zeros in hardware (no branch)
 IOD_DEVINL float4 rb_bload(__amdgpu_buffer_rsrc_t r, int voff)
 {
-    const u32x4_ v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
 IOD_DEVINL __amdgpu_buffer_rsrc_t rb_rsrc(const float* p) { return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, 0x7fffffff, 0x00020000); }
@@ -270,7 +257,7 @@ void refine_bwd01_kernel(const float* __restrict__ rd1, const uint4* __restrict_
 #pragma unroll
                 for (int rr = 0; rr < 2; ++rr) {
                     const int r = ks * 2 + rr;
-                    h16x8 bh, bl;
+                    f16x8 bh, bl;
                     {
                         const uint4 vb_h = *reinterpret_cast<const uint4*>(sd_p + (0 * RB_CO + co) * RB_DPL + r * 8 + 4 * kh);
                         const uint4 vb_l = *reinterpret_cast<const uint4*>(sd_p + (1 * RB_CO + co) * RB_DPL + r * 8 + 4 * kh);
@@ -279,7 +266,7 @@ void refine_bwd01_kernel(const float* __restrict__ rd1, const uint4* __restrict_
 #pragma unroll
                     for (int rb = 0; rb < 6; ++rb) {
                         const int kx = rb >> 1;                  // block-uniform column tap: 0 -> odd plane shifted by one pixel, 1 -> even plane, 2 -> odd plane
-                        h16x8 A[2];
+                        f16x8 A[2];
 #pragma unroll
                         for (int term = 0; term < 2; ++term) {
                             const unsigned* pl = sa_p + term * RB_CI * RB_APL + offA[rb & 1] + (2 * r) * 20;
@@ -389,7 +376,7 @@ void refine_bwd01_kernel(const float* __restrict__ rd1, const uint4* __restrict_
         const float* rdl = s_rd + (j & 1) * RB_R_DW + f_off;
         const float* smr = s_max + (j & 1) * 12 + 8;
         // scale of the staged neighbourhood: a pure function of the data (its max, published by the consumers with the values)
-        const float sc = rb_fresh_scale(fmaxf(fmaxf(smr[0], smr[1]), fmaxf(smr[2], smr[3])));
+        const float sc = fresh_scale(fmaxf(fmaxf(smr[0], smr[1]), fmaxf(smr[2], smr[3])));
         f32x4 acc[2][2];
 #pragma unroll
         for (int py = 0; py < 2; ++py)

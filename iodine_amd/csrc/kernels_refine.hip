@@ -14,16 +14,7 @@
 #include "common.h"
 #include <utility>
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
-
-IOD_DEVINL float elu1_fast_r(float v) { return v > 0.f ? v : __expf(v) - 1.f; }
-
-template <class F, int... Is>
-IOD_DEVINL void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-IOD_DEVINL void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 // tap slot j of parity class sb = py*2+px
 __host__ __device__ constexpr int s2_ntaps(int sb) { return (1 + (sb >> 1)) * (1 + (sb & 1)); }
@@ -335,7 +326,7 @@ IOD_DEVINL void conv_s2_body(const float* __restrict__ in, const uint4* __restri
                 v.x += mv.x; v.y += mv.y; v.z += mv.z; v.w += mv.w;
             }
             if constexpr (F32) *dst = make_float4(elu1(v.x), elu1(v.y), elu1(v.z), elu1(v.w));      // (expm1f: the VALU is idle beside fp32 MFMA)
-            else *dst = make_float4(elu1_fast_r(v.x), elu1_fast_r(v.y), elu1_fast_r(v.z), elu1_fast_r(v.w));
+            else *dst = make_float4(elu1_fast(v.x), elu1_fast(v.y), elu1_fast(v.z), elu1_fast(v.w));
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -458,7 +449,7 @@ hipError_t launch_conv3x3_s2_dgrad_f16x3(hipStream_t st, const float* d, const v
 // =========================================================================================
 // Weight gradient of the stride-2 conv, split-fp16:  dW[tap][ci][co] = sum_px a[2oy+ky-1][2ox+kx-1][ci] * d[oy][ox][co]
 //   M = ci, N = co, K = coarse pixels (16 per MFMA = one coarse tile row), as in the stride-1 kernel of
-//   kernels_train.hip; the fine input is staged TRANSPOSED (one fp16 plane per channel) and DE-INTERLEAVED by column
+//   kernels_wgradws.hip; the fine input is staged TRANSPOSED (one fp16 plane per channel) and DE-INTERLEAVED by column
 //   parity, so that the K-consecutive operand of every tap is contiguous:
 //     kx = 1 -> even plane at X,  kx = 2 -> odd plane at X,  kx = 0 -> odd plane at X-1 (register shift, v_alignbit)
 //   plane row (20 dwords, 2 px each): [3] = odd (X=-2,-1) | [4..11] odd X=0..15 | [12..19] even X=0..15
@@ -613,7 +604,7 @@ void conv3x3_s2_wgrad_f16x3_kernel(const float* __restrict__ a, const float* __r
 #pragma unroll
         for (int rr = 0; rr < RW; ++rr) {
             const int r = ks * RW + rr;
-            h16x8 bh, bl;
+            f16x8 bh, bl;
             {
                 const uint4 vb_h = *reinterpret_cast<const uint4*>(s_d + (0 * NCO + co) * DPL + r * 8 + 4 * kh);
                 const uint4 vb_l = *reinterpret_cast<const uint4*>(s_d + (1 * NCO + co) * DPL + r * 8 + 4 * kh);
@@ -621,7 +612,7 @@ void conv3x3_s2_wgrad_f16x3_kernel(const float* __restrict__ a, const float* __r
             }
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
-                h16x8 A[2][3];                               // [term][kx]
+                f16x8 A[2][3];                               // [term][kx]
 #pragma unroll
                 for (int term = 0; term < 2; ++term) {
                     const unsigned* pl = s_a + (term * CI + ci) * APL + (2 * r + ky) * 20;

@@ -24,8 +24,6 @@
 #include <vector>
 #include <cstdio>
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 #ifdef IODINE_TILE_PROF
@@ -35,15 +33,6 @@ __device__ unsigned g_l0_prof[2 * TP_MAXBLK * 8];            // [role][block][ph
 constexpr int L0_HR = 5, L0_HC = 33, L0_NPX = L0_HR * L0_HC;      // halo of a 2 x 16 output tile: fine pixels
 constexpr int L0_PXB = 48;                                         // bytes per staged pixel: 12 fp32 channels
 constexpr int L0_PLB = L0_NPX * L0_PXB;                            // one plane: 7920 bytes
-
-IOD_DEVINL float l0_fresh_scale(float mx)
-{
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.f;
-    const int e = (int)((__float_as_uint(mx) >> 23) & 0xffu) - 127;
-    int se = 12 - e;
-    se = se > 100 ? 100 : (se < -100 ? -100 : se);
-    return __uint_as_float((unsigned)(127 + se) << 23);
-}
 
 // Block barrier that orders LDS traffic only: __syncthreads() is a full fence, i.e. s_waitcnt vmcnt(0) as well - on gfx9 that also drains the
 // wave's global STORES (the consumers' output) and the producers' prefetch loads twice per unit.
@@ -118,7 +107,7 @@ void refine_l0_fused_kernel(const float4* __restrict__ x4, const float4* __restr
             const uint4 a = q[0], b2 = q[1], c = q[2], d = q[3];
             const unsigned m = max(max(max(max(a.x, a.y), max(a.z, a.w)), max(max(b2.x, b2.y), max(b2.z, b2.w))),
                                    max(max(max(c.x, c.y), max(c.z, c.w)), max(max(d.x, d.y), max(d.z, d.w))));
-            return l0_fresh_scale(__uint_as_float(m));
+            return fresh_scale(__uint_as_float(m));
         };
         auto convert_share = [&](unsigned bbase, const unsigned* mxp) {
             // lanes 0 .. NPL - 1: the scale of plane `lane` -> this wave's table (wave-private: LDS operations of a wave complete in order)

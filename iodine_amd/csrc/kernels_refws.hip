@@ -20,34 +20,12 @@
 #include "common.h"
 #include <utility>
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int RW_HR = 5, RW_HC = 33, RW_NPX = RW_HR * RW_HC;   // halo of a 2 x 16 output tile, fine pixels
 constexpr int RW_PXB = 160;                                    // bytes per staged pixel: 64 hi | 64 lo | 32 pad
 constexpr int RW_BUFB = (RW_NPX + 1) * RW_PXB;                 // + dump slot for idle lanes
 constexpr int RW_NIN = (RW_NPX * 8 + 255) / 256;               // float4 loads per thread and chunk (6)
-
-typedef unsigned u32x4r __attribute__((ext_vector_type(4)));
-
-template <int I, int N, typename F>
-IOD_DEVINL void rw_static_for(F&& f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rw_static_for<I + 1, N>(f);
-    }
-}
-
-IOD_DEVINL float rw_fresh_scale(float mx)
-{
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.f;
-    const int e = (int)((__float_as_uint(mx) >> 23) & 0xffu) - 127;
-    int se = 12 - e;
-    se = se > 100 ? 100 : (se < -100 ? -100 : se);
-    return __uint_as_float((unsigned)(127 + se) << 23);
-}
 
 // F32 (conv_precision 0, round 5): the staged pixel is its 32 fp32 channels (128 of the same 160 bytes), the 144 weight registers hold fp32
 // (launch_pack_conv_weights_ws32: element j of a lane's 16 bytes = the A operand of the j-th v_mfma_f32_16x16x4_f32 over the fragment's 16
@@ -110,23 +88,13 @@ void conv3x3_s2ws_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
     // conservatism), which exposed a full HBM round trip per stage.  Loads and stores are issued for EVERY stage / tile (all lanes out of
     // range past the end), so the counts are uniform: in front of a stage's first use there are 6 younger loads + 2 younger stores in
     // flight (6 loads in the first iteration).
-    typedef int i32x4r __attribute__((ext_vector_type(4)));
-    auto make_rsrc = [&](const void* base) {
-        const unsigned long long p = (unsigned long long)base;
-        i32x4r r;
-        r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-        r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32));
-        r.z = 0x7fffffff;
-        r.w = 0x00020000;
-        return r;
-    };
     f32x4 rin[NCHUNK][RW_NIN];                                // [chunk]: stage s lives in set s % NCHUNK, requested two stages ahead
     auto issue = [&](int s, f32x4 (&rr)[RW_NIN]) {            // loads of stage s = (tile, chunk): block-uniform scalar part + per-thread part
         const bool live = s < nstage;
         const int t = (int)blockIdx.x + ((live ? s : 0) / NCHUNK) * nblk, c = s % NCHUNK;
         const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, n = t / (tiles_x * tiles_y);
         const float* org = in + (size_t)n * Sf * Sf * C + ((long long)(4 * ty - 1) * Sf + 32 * tx - 1) * C + c * 32;
-        const i32x4r rs = make_rsrc(org);
+        const i32x4 rs = iod_make_rsrc(org, 0x7fffffffu);
         const int rmax = live ? Sf - (4 * ty - 1) : 0, cmax = Sf - (32 * tx - 1);           // rows / columns of the halo inside the image
         const bool top = ty == 0, left = tx == 0;
         unsigned vo[RW_NIN];
@@ -205,7 +173,7 @@ void conv3x3_s2ws_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
             }
         };
         LOADF(std::integral_constant<int, 0>{}, f[0], base);
-        rw_static_for<0, 15>([&](auto sc) {
+        static_for<15>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
             if constexpr (s + 1 < 15) {
                 LOADF(std::integral_constant<int, (s + 1 < 15 ? s + 1 : 0)>{}, f[(s + 1) & 1], base);
@@ -219,10 +187,10 @@ void conv3x3_s2ws_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
     };
 #undef RW_DSR128
 
-    rw_static_for<0, NCHUNK>([&](auto cc) { issue(decltype(cc)::value, rin[decltype(cc)::value]); });
+    static_for<NCHUNK>([&](auto cc) { issue(decltype(cc)::value, rin[decltype(cc)::value]); });
     float tile_scale_cur = 1.f;
     for (int s0 = 0; s0 < nstage; s0 += NCHUNK) {
-        rw_static_for<0, NCHUNK>([&](auto cc) {
+        static_for<NCHUNK>([&](auto cc) {
             constexpr int c = decltype(cc)::value;
             const int s = s0 + c, par = c & 1;
             // ---- stage s: max of the staged values -> block-wide scale -> split into LDS buffer c ----
@@ -239,7 +207,7 @@ void conv3x3_s2ws_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
             m = wave_max_f32(m);
             if (lane == 0) s_max[par * 4 + wv] = m;
             __syncthreads();                                  // (also: every wave is done with the MFMAs of stage s - 2 = this buffer's last readers)
-            scale = rw_fresh_scale(fmaxf(fmaxf(s_max[par * 4], s_max[par * 4 + 1]), fmaxf(s_max[par * 4 + 2], s_max[par * 4 + 3])));
+            scale = fresh_scale(fmaxf(fmaxf(s_max[par * 4], s_max[par * 4 + 1]), fmaxf(s_max[par * 4 + 2], s_max[par * 4 + 3])));
             }
             convert(c, scale, rin[c]);
             issue(s + NCHUNK, rin[c]);                            // two stages ahead, into the set just converted (masked past the end)
@@ -259,7 +227,7 @@ void conv3x3_s2ws_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
             const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, n = t / (tiles_x * tiles_y);
             const float inv = inv_w / tile_scale_cur;
             const int X = 16 * tx + lpx;
-            const i32x4r ro = make_rsrc(out + (size_t)n * Sc * Sc * C);
+            const i32x4 ro = iod_make_rsrc(out + (size_t)n * Sc * Sc * C, 0x7fffffffu);
             const float4 bq = *reinterpret_cast<const float4*>(s_bias + 16 * cg + 4 * lkb);
             asm volatile("s_nop 4" :: "s"(ro) : "memory");
 #pragma unroll

@@ -5,7 +5,7 @@
 // GEMM view per tap: M = ci, N = co, K = pixels, v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulate; 64 cycles per MFMA
 // and SIMD = the fp32 matrix peak of 157.3 TF/s when the pipe never idles).  Both operands are K-major in NHWC - lane (half, li) of a
 // k-step reads channel li of pixel 2 s + half: no transposition, one ds_read_b32 per operand.  The round-1 kernel
-// (conv3x3_wgrad_tile_kernel, kernels_train.hip) loaded a tile, synchronised, multiplied, synchronised: its global loads were fully
+// (conv3x3_wgrad_tile_kernel, kernels_wgrad.hip) loaded a tile, synchronised, multiplied, synchronised: its global loads were fully
 // exposed (0.70 of the peak).  Here
 //   * a wave keeps the nine 32 x 32 tap accumulators of its (ci half, co half) in 144 VGPRs for the life of a persistent block;
 //   * the NEXT 4 x 16 tile (6 x 18 halo of a, 4 x 16 of d) is fetched into registers (raw buffer loads: halo pixels outside the
@@ -17,21 +17,6 @@
 // Partial tiles part[(block * KS + ks)][tap][ci][co] are reduced in fixed order by launch_wgrad_reduce (deterministic).
 #include "common.h"
 #include <type_traits>
-
-namespace {
-
-typedef int i32x4w_ __attribute__((ext_vector_type(4)));
-
-template <int I, int N, typename F>
-IOD_DEVINL void w32_static_for(F&& f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        w32_static_for<I + 1, N>(f);
-    }
-}
-
-}  // namespace
 
 template <int C>
 __global__ __launch_bounds__(256, 2)
@@ -58,15 +43,6 @@ void conv3x3_wgrad_f32_ws_kernel(const float* __restrict__ a, const float* __res
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mi = wv % MT, ni = (wv / MT) % NTT, ks = wv / (MT * NTT);
 
-    auto make_rsrc = [&](const void* base, unsigned bytes) {
-        const unsigned long long p = (unsigned long long)base;
-        i32x4w_ r;
-        r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-        r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32));
-        r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-        r.w = 0x00020000;
-        return r;
-    };
 #define W32_BLOAD4(dst, voff, rsrc, soff) \
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory")
 #define W32_SGPR_SETTLE(rsrc) asm volatile("s_nop 4" :: "s"(rsrc) : "memory")
@@ -101,8 +77,8 @@ void conv3x3_wgrad_f32_ws_kernel(const float* __restrict__ a, const float* __res
     auto issue_tile = [&](int t) {
         const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, n = t / (tiles_x * tiles_y);
         const unsigned img_bytes = (unsigned)(S * S * C * 4);
-        const i32x4w_ rs_a = make_rsrc(a + (size_t)n * S * S * C, img_bytes);
-        const i32x4w_ rs_d = make_rsrc(d + (size_t)n * S * S * C, img_bytes);
+        const i32x4 rs_a = iod_make_rsrc(a + (size_t)n * S * S * C, img_bytes);
+        const i32x4 rs_d = iod_make_rsrc(d + (size_t)n * S * S * C, img_bytes);
         // (scalar) borders this tile touches, replicated for every k; byte offset of the halo origin (may be "negative": wraps)
         const unsigned tb = (ty == 0 ? 1u : 0u) | (ty == tiles_y - 1 ? 2u : 0u) | (tx == 0 ? 4u : 0u) | (tx == tiles_x - 1 ? 8u : 0u);
         const unsigned out = bmask & (tb * 0x11111111u);
@@ -160,7 +136,7 @@ void conv3x3_wgrad_f32_ws_kernel(const float* __restrict__ a, const float* __res
             const bool has_next = t + bpx < t_end;
             if (has_next) issue_tile(t + bpx);
             // ---- 9 x STEPS MFMAs of this tile from LDS: straight-line code, literal LDS offsets ----
-            w32_static_for<0, STEPS>([&](auto sc) {
+            static_for<STEPS>([&](auto sc) {
                 constexpr int s = decltype(sc)::value;
                 constexpr int r = (2 * s) / TW, c = (2 * s) % TW;
                 const float bval = dp[(2 * s) * 32];
@@ -276,15 +252,6 @@ void dec_out_wgrad_f32_kernel(const float* __restrict__ a, const float* __restri
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mi = wv % MT, nt = (wv / MT) & 1, ks = wv / (MT * 2);
 
-    auto make_rsrc = [&](const void* base, unsigned bytes) {
-        const unsigned long long p = (unsigned long long)base;
-        i32x4w_ r;
-        r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-        r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32));
-        r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-        r.w = 0x00020000;
-        return r;
-    };
 #define OW_BLOAD4(dst, voff, rsrc, soff) \
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory")
 
@@ -308,8 +275,8 @@ void dec_out_wgrad_f32_kernel(const float* __restrict__ a, const float* __restri
     f32x4 ra[NA], rg;
     auto issue_tile = [&](int t) {
         const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, n = t / (tiles_x * tiles_y);
-        const i32x4w_ rs_a = make_rsrc(a + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
-        const i32x4w_ rs_g = make_rsrc(g + (size_t)n * S * S * 4, (unsigned)(S * S * 16));
+        const i32x4 rs_a = iod_make_rsrc(a + (size_t)n * S * S * C, (unsigned)(S * S * C * 4));
+        const i32x4 rs_g = iod_make_rsrc(g + (size_t)n * S * S * 4, (unsigned)(S * S * 16));
         const unsigned tb = (ty == 0 ? 1u : 0u) | (ty == tiles_y - 1 ? 2u : 0u) | (tx == 0 ? 4u : 0u) | (tx == tiles_x - 1 ? 8u : 0u);
         const unsigned oa = rel_a + (unsigned)((((ty * TH) * S + tx * TW) * C) * 4);
         const unsigned og = (gmask & tb) ? 0x80000000u : rel_g + (unsigned)(((ty * TH - 1) * S + tx * TW - 1) * 16);
@@ -354,7 +321,7 @@ void dec_out_wgrad_f32_kernel(const float* __restrict__ a, const float* __restri
         for (int t = t0; t < t_end; t += bpx) {
             const bool has_next = t + bpx < t_end;
             if (has_next) issue_tile(t + bpx);
-            w32_static_for<0, STEPS>([&](auto sc) {
+            static_for<STEPS>([&](auto sc) {
                 constexpr int s = decltype(sc)::value;
                 constexpr int r = (2 * s) / TW, c = (2 * s) % TW;
                 const float aval = ap[(2 * s) * 32];

@@ -2,7 +2,7 @@
 // form (kernels_pack.hip: every pack of iodine_set_params in two launches).  One definition each: the batched and the one-tensor form
 // write the same bits.
 #pragma once
-#include "common.h"
+#include "device.h"
 
 // element idx of the weight-stationary register layout (kernels_convws.hip): [cout group][chunk of 32 cin][tap][hi/lo][lane][8 fp16]
 IOD_DEVINL _Float16 pack_ws_element(const float* __restrict__ src, int C, int tflip, float scale, size_t idx)

@@ -2,7 +2,7 @@
 // ONE definition, so that every kernel that needs the 17-channel encoding computes bit-identical values (the function switches fp
 // contraction off for exactly that reason - see the comments inside).  Reference: lib/modeling/iodine.py:185-216, 277-331.
 #pragma once
-#include "common.h"
+#include "device.h"
 
 template <int K>
 struct PixelTerms {

@@ -1,4 +1,4 @@
-"""Kernel-level parity of the refinement head's GEMMs and column sums (kernels_train.hip: sgemm_kernel<64 | 256>, sgemm_tn_mfma_kernel
+"""Kernel-level parity of the refinement head's GEMMs and column sums (kernels_gemm.hip: sgemm_kernel<64 | 256>, sgemm_tn_mfma_kernel
 <SPLITK, MODE, AROW>, colsum / colsum_tall) against float64, through iodine_op_sgemm / iodine_op_colsum.  C carries a sentinel ring (ldc > N,
 rows past M); beta = 0 runs over a NaN-filled C, which must not be read; beta = 1 over a known C with alpha != 1.  The gate is the project's
 gate of exact-fp32 kernels, 2e-6 of the largest reference element (test_gpu_gen_s2.py); test_head_cpu.py shows for every case that the

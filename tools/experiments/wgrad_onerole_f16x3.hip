@@ -158,7 +158,7 @@ void conv3x3_wgrad_f16x3_kernel(const float* __restrict__ a, const float* __rest
 #pragma unroll
         for (int rr = 0; rr < RW; ++rr) {
             const int r = ks * RW + rr;
-            h16x8 bh, bl;
+            f16x8 bh, bl;
             {
                 uint4 vb_h = make_uint4(0, 0, 0, 0), vb_l = make_uint4(0, 0, 0, 0);
                 if (co_ok) {
@@ -169,7 +169,7 @@ void conv3x3_wgrad_f16x3_kernel(const float* __restrict__ a, const float* __rest
             }
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
-                h16x8 A[2][3];                               // [term][dx]
+                f16x8 A[2][3];                               // [term][dx]
 #pragma unroll
                 for (int term = 0; term < 2; ++term) {
                     const unsigned* pl = s_a + (term * CI + ci) * APL + (r + dy) * 12;
