@@ -224,6 +224,38 @@ int iodine_scene_edit(iodine_handle* h, void* stream, int batch, const float* z,
                       const float* z_new, int chunk_images, float* pred, float* mask, float* mean, float* base_pred, float* base_mask,
                       float* base_mean);
 
+/* Multi-sample evaluation: n_samples draws z_s = mu + exp(logvar/2) * eps[s] from ONE posterior (post_mean / post_logvar (B,K,L); both
+ * NULL = the initial posterior, as in iodine_elbo), each decoded, and reduced per pixel WITHOUT writing any sample's planes: running mean
+ * and sum of squared deviations (Welford, fp32, in sample order) of the rendered image and of the masks, the number of samples in which
+ * each slot wins a pixel, and -- with x -- the per-image weighted log-likelihood of every sample (what the importance-weighted bound and
+ * the Monte-Carlo ELBO are built from).  The decoder treats slot-images independently, so the S B K slot-images run on the decoder
+ * kernels the path selector picks, unchanged; everything new is one per-pixel kernel that keeps one pixel of one image per thread for all
+ * samples of a launch.
+ *   eps (n_samples,B,K,L) device; x (B,3,S,S) or NULL.  Outputs, each may be NULL: z (n_samples,B,K,L) -- z[s] is bit for bit what
+ *   iodine_elbo(x, post_mean, post_logvar, eps[s]) samples; pred_mean, pred_m2 (B,3,S,S) and mask_mean, mask_m2 (B,K,1,S,S): mean and M2 =
+ *   sum_s (v_s - mean)^2 (population variance = M2 / n_samples; exactly 0 for one sample) of the per-sample pred / mask, which are the bits
+ *   iodine_decode(z[s]) returns; votes (B,K,S,S) int32: samples whose mask arg-max at the pixel is slot k (the lowest index wins a tie, as in
+ *   iodine_slot_table's segmentation map; sums to n_samples over k); ll (n_samples,B) = sum_p w_p sum_c logsumexp_k(..) of sample s and
+ *   image b, needs x.  sigma is the objective's (iodine_set_objective), beta plays no part; a pending iodine_set_pixel_weights is
+ *   consumed by this call like by any call that reads x.
+ * chunk_images: the size of the arena in images, >= batch; 0 = batch.  The workspace is planned for inference (mode 0) at
+ * W = max(batch, chunk_images) images -- iodine_workspace_bytes(h, W, 0) -- and the samples run in chunks of floor(W / batch) >= 1 whole
+ * samples: per chunk one sampling launch, one decoder pass over n_s B K slot-images and one accumulate launch, which reads the running
+ * state from the output buffers and writes it back.  The update is strictly sequential in the sample index, so every output is bitwise
+ * independent of chunk_images.  No host synchronisation, no allocation, everything on `stream`; the likelihood is reduced through fp64
+ * block partials in a fixed order (no float atomics).
+ * IODINE_ERR_INVALID, before anything is launched, with a message that names the argument: n_samples < 1 or above 2^24 (the sample index
+ * enters the moments as an fp32 number; int32 votes could wrap only far beyond), eps NULL, one of post_mean / post_logvar without the
+ * other, chunk_images < batch (and non-zero), ll without x, batch above 65535, batch or chunk_images beyond the 2^31 limit of iodine_decode.
+ * Call state: the call counts as an iodine_decode at batch W -- a saved training forward or saved decode / elbo is discarded, the LSTM
+ * state of the last reconstruct stays -- and, because the chunk's samples and the packed image take buffers the last elbo() wrote,
+ * iodine_last_elbo_outputs has nothing to read afterwards (IODINE_ERR_STATE), as after iodine_scene_edit.  Not differentiable.  The entry
+ * is NOT captured under option "graph": its launch sequence depends on the sample count, so it always runs eagerly.  Profile category:
+ * "predictive" (the accumulate launches; the decoder passes are booked under the decoder's categories). */
+int iodine_predictive(iodine_handle* h, void* stream, int batch, int n_samples, const float* post_mean, const float* post_logvar,
+                      const float* eps, const float* x, int chunk_images, float* z, float* pred_mean, float* pred_m2, float* mask_mean,
+                      float* mask_m2, int* votes, float* ll);
+
 /* elbo = model.elbo(x) -- IODINE.elbo, iodine.py:161-241: ONE sample z = mu + exp(logvar/2) * eps from the given posterior
  * (post_mean / post_logvar (B,K,L); both NULL = the initial posterior of Gaussian.init_unit, iodine.py:607-618), decode,
  * mixture log-likelihood and KL.  eps (B,K,L); terms (3) = {ELBO, KL, LL} (device, may be NULL).  The tensors the reference
@@ -594,7 +626,7 @@ int iodine_set_option(iodine_handle* h, const char* key, double value);
  * (fused layer-1 data gradient + layer-0 weight gradient, option refine_bwd_fused), "refine_bias_grad", "head_bwd", "gen_conv"
  * (the fp32 convs of the generic path), "gen_conv_f16x3" (its split-fp16 launches, option gen_conv_precision 1), "gen_l0" (its spatial-broadcast layer: prefix-table forward, tap-sum backward), "render_bwd" (backward of the rendering - sigmoid, slot softmax, sum_k mask x mean - in iodine_decode_backward; the decoder pass behind it is booked under the categories of the training step), "frames_in" (the image / clip conversion at the head of
  * iodine_reconstruct / iodine_train_forward: one launch for all frames), "traj_out" (the per-iteration output launches of a trajectory,
- * iodine_reconstruct_seq), "scene_edit" (the per-pixel rendering launches of iodine_scene_edit).  "seen:<category>" returns in *launches the number of launches of <category> since the
+ * iodine_reconstruct_seq), "scene_edit" (the per-pixel rendering launches of iodine_scene_edit), "predictive" (the per-pixel accumulate launches of iodine_predictive).  "seen:<category>" returns in *launches the number of launches of <category> since the
  * last reset, bracketed or not (option profile_stride; counted at profile levels 1 -- the bracketed categories -- and 2 -- all).  Synchronises on the recorded events.  Two more names report
  * the hipGraph bookkeeping of option "graph" in *launches: "graph_captures" (graphs instantiated) and "graph_replays". */
 int iodine_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset);

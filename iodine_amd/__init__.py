@@ -2,7 +2,7 @@
 ``IODINE.forward / reconstruct`` module API.  Heavy imports are lazy so that
 ``iodine_amd.synth`` can be used without the HIP library being built."""
 
-__all__ = ['IODINE', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse',
+__all__ = ['IODINE', 'Predictive', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse',
            'slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS', 'latent_kl', 'rank_dims', 'Traversal']
 
 
@@ -10,6 +10,9 @@ def __getattr__(name):
     if name == 'IODINE':
         from .model import IODINE
         return IODINE
+    if name == 'Predictive':                                  # (what ``IODINE.predictive`` returns)
+        from .model import Predictive
+        return Predictive
     if name in ('slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS'):
         from . import objects
         return getattr(objects, name)

@@ -39,6 +39,7 @@ EXPORTS = (
     'iodine_slot_table', 'iodine_seg_overlap',
     'iodine_scene_edit',
     'iodine_op_pixel_encode',
+    'iodine_predictive',
 )
 
 
@@ -168,6 +169,8 @@ def lib() -> C.CDLL:
         L.iodine_scene_edit.argtypes = [vp, vp, ci, vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), vp, ci] + [vp] * 6
     if hasattr(L, 'iodine_op_pixel_encode'):            # (kernel-level tests of the per-pixel mixture kernels; absent from older A/B builds)
         L.iodine_op_pixel_encode.argtypes = [vp] * 7 + [ci] * 4 + [cf, cf, ci, C.c_uint, ci, C.POINTER(vp)]
+    if hasattr(L, 'iodine_predictive'):                 # (IODINE.predictive; absent from older A/B builds, which raise on it)
+        L.iodine_predictive.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, ci] + [vp] * 7
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

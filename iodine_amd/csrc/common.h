@@ -109,6 +109,16 @@ constexpr int SCENE_EDIT_MAX = 256;             // edits of one launch (2 KB of 
 struct SceneEditList { int n; int bs[SCENE_EDIT_MAX]; int src[SCENE_EDIT_MAX]; };
 hipError_t launch_scene_edit_out(hipStream_t st, const float* base, const float* edit, const SceneEditList& list, float* pred, float* mask,
                                  float* mean, int K, int P);
+// kernels_predictive.hip (iodine_predictive): z [n_s][rows][L] = mean + exp(logvar / 2) eps for the samples of a chunk (post_stride L: a
+// posterior (rows, L); 0: one row for all), and the per-pixel accumulation over those samples' decoder output dec [n_s B K][P][4] -
+// Welford moments of pred (B,3,P) / mask (B,K,P), int votes (B,K,P), all five required (read when s0 > 0, written always); x4 != NULL:
+// also ll [n_s][B] through part = n_s * B * predictive_blocks_per_image(P) doubles.  s0 = global index of the chunk's first sample
+int predictive_blocks_per_image(int P);
+hipError_t launch_predictive_sample(hipStream_t st, const float* pm, const float* plv, const float* eps, float* z, int n_s, int rows, int L,
+                                    int post_stride);
+hipError_t launch_predictive_accum(hipStream_t st, const float* dec, const float* x4, int B, int K, int P, int s0, int n_s, float* pred_mean,
+                                   float* pred_m2, float* mask_mean, float* mask_m2, int* votes, double* part, float* ll, float sigma,
+                                   int strict);
 // kernels_render.hip: backward of the rendering (sigmoid, slot softmax, sum_k mask * mean) for the caller's gradients wrt pred (B,3,S,S),
 // mask (B,K,1,S,S), mean (B,K,3,S,S) - NCHW, any of them NULL = zero - into g [N][P][4]; strict as for launch_pixel_pass1
 hipError_t launch_render_bwd(hipStream_t st, const float* dec, const float* g_pred, const float* g_mask, const float* g_mean, float* g,

@@ -999,6 +999,34 @@ int scene_edit_check(iodine_handle* h, int batch, const float* z, int n_edits, c
     return IODINE_OK;
 }
 
+int predictive_check(iodine_handle* h, int batch, int n_samples, const float* post_mean, const float* post_logvar, const float* eps,
+                     const float* x, int chunk_images, const float* ll)
+{
+    if (int rc = check_ready(h, batch)) return rc;
+    char m[256];
+    if (n_samples < 1) {
+        snprintf(m, sizeof m, "iodine_predictive: n_samples must be >= 1 (got %d)", n_samples);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    if (n_samples > PREDICTIVE_MAX_SAMPLES) {
+        snprintf(m, sizeof m, "iodine_predictive: n_samples = %d is above %d: the running moments divide by the sample index as an fp32 number, "
+                              "exact up to 2^24 - far below the count at which the int32 votes could wrap", n_samples, PREDICTIVE_MAX_SAMPLES);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    if (!eps) return h->fail(IODINE_ERR_INVALID, "iodine_predictive: eps (n_samples, B, K, L) is required");
+    if ((post_mean == nullptr) != (post_logvar == nullptr))
+        return h->fail(IODINE_ERR_INVALID, "iodine_predictive: pass both post_mean and post_logvar, or neither");
+    if (chunk_images != 0 && chunk_images < batch) {
+        snprintf(m, sizeof m, "iodine_predictive: chunk_images = %d is smaller than the batch of %d images (a chunk holds every image of at "
+                              "least one sample; 0 = the batch)", chunk_images, batch);
+        return h->fail(IODINE_ERR_INVALID, m);
+    }
+    if (ll && !x) return h->fail(IODINE_ERR_INVALID, "iodine_predictive: ll is the likelihood of x under every sample, but x is NULL");
+    if (batch > 65535) return h->fail(IODINE_ERR_INVALID, "iodine_predictive: batch above 65535 images (one grid row per image): run the images in groups");
+    if (chunk_images > batch) return check_ready(h, chunk_images);      // the arena (and the chunk decodes) run at chunk_images
+    return IODINE_OK;
+}
+
 int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* post_mean, const float* post_logvar)
 {
     if (int rc = check_ready(h, batch)) return rc;
@@ -1827,6 +1855,55 @@ int iodine_scene_edit(iodine_handle* h, void* stream, int batch, const float* z,
                                                            mask ? mask + (size_t)f0 * K * P : nullptr, mean ? mean + (size_t)f0 * 3 * P : nullptr, K, h->P));
         }
         e0 = e1;
+    }
+    return IODINE_OK;
+}
+
+int iodine_predictive(iodine_handle* h, void* stream, int batch, int n_samples, const float* post_mean, const float* post_logvar,
+                      const float* eps, const float* x, int chunk_images, float* z, float* pred_mean, float* pred_m2, float* mask_mean,
+                      float* mask_m2, int* votes, float* ll)
+{
+    if (h && h->shim)
+        return pad_predictive(h, stream, batch, n_samples, post_mean, post_logvar, eps, x, chunk_images, z, pred_mean, pred_m2, mask_mean, mask_m2,
+                              votes, ll);
+    if (!h) return IODINE_ERR_INVALID;
+    const PixelWeights pw(h);                              // one-shot, like every call that takes x: gone whether the call succeeds or not
+    int rc = predictive_check(h, batch, n_samples, post_mean, post_logvar, eps, x, chunk_images, ll);
+    if (rc) return rc;
+    const int W = chunk_images > batch ? chunk_images : batch;
+    rc = ensure_workspace(h, W, 0);
+    if (rc) return rc;
+    // an iodine_decode at batch W as far as the arena goes (the chunk decodes write buf.g), except that the samples take buf.z[0] and the
+    // packed image buf.x4: the last elbo()'s outputs are gone, as after iodine_scene_edit.  Not captured under option graph: the launch
+    // sequence depends on the sample count
+    h->calls.compute_begins(true);
+    h->calls.last_elbo_iter = -1;
+    hipStream_t st = (hipStream_t)stream;
+    Buffers& b = h->buf;
+    const int B = batch, K = h->K, L = h->L, N = B * K;
+    const size_t P = (size_t)h->P;
+    // running state of an output the caller did not ask for: carved from the (free) refinement input, [W K][P][20] floats >= (3 K + 6) B P
+    float* spare = b.enc[0];
+    bool used_spare = false;
+    auto state = [&](float* out, size_t n) { if (out) return out; float* q = spare; spare += n; used_spare = true; return q; };
+    float* s_pm = state(pred_mean, (size_t)B * 3 * P);
+    float* s_p2 = state(pred_m2, (size_t)B * 3 * P);
+    float* s_mm = state(mask_mean, (size_t)N * P);
+    float* s_m2 = state(mask_m2, (size_t)N * P);
+    int* s_vt = votes ? votes : (int*)state(nullptr, (size_t)N * P);
+    if (used_spare) h->calls.enc_valid = false;
+    const bool like = x && ll;                             // (x without ll: nothing to score)
+    if (like) HIPCHK(h, launch_x_to_nhwc4(st, x, b.x4, B, h->P, 1, pw.w, 0));
+    const float *pm = post_mean ? post_mean : h->init_mean, *plv = post_mean ? post_logvar : h->init_logvar;
+    const int per_chunk = W / B;                           // >= 1 whole samples per chunk
+    for (int s0 = 0; s0 < n_samples; s0 += per_chunk) {
+        const int n_s = std::min(per_chunk, n_samples - s0);
+        float* zc = z ? z + (size_t)s0 * N * L : b.z[0];  // (buf.z[0] holds W K rows)
+        HIPCHK(h, launch_predictive_sample(st, pm, plv, eps + (size_t)s0 * N * L, zc, n_s, N, L, post_mean ? L : 0));
+        HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, zc, h->wcls, nullptr, b.V, n_s * N, L, h->Cd));
+        if (int r = decoder_forward(h, st, n_s * N, zc, b.g)) return r;
+        PROF(h, st, "predictive", launch_predictive_accum(st, b.g, like ? b.x4 : nullptr, B, K, h->P, s0, n_s, s_pm, s_p2, s_mm, s_m2, s_vt, b.part,
+                                                         like ? ll + (size_t)s0 * B : nullptr, (float)h->obj.sigma, h->precision == 0));
     }
     return IODINE_OK;
 }

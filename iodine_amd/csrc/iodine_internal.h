@@ -294,6 +294,9 @@ int decode_check(iodine_handle* h, int batch, const float* z);
 int scene_edit_check(iodine_handle* h, int batch, const float* z, int n_edits, const int* image, const int* slot, const int* kind,
                      const float* z_new, int chunk_images);
 int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* post_mean, const float* post_logvar);
+constexpr int PREDICTIVE_MAX_SAMPLES = 1 << 24;    // iodine_predictive: the sample index enters the running moments as an fp32 number
+int predictive_check(iodine_handle* h, int batch, int n_samples, const float* post_mean, const float* post_logvar, const float* eps,
+                     const float* x, int chunk_images, const float* ll);
 int train_forward_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* loss, const float* const* state_in = nullptr,
                         const FrameSet* fr = nullptr);
 int train_backward_check(iodine_handle* h, float* const* param_grads, int n, const AuxCot* aux = nullptr);
@@ -330,6 +333,9 @@ int pad_scene_edit(iodine_handle* h, void* stream, int batch, const float* z, in
                    float* base_mean);
 int pad_elbo(iodine_handle* h, void* stream, int batch, const float* x, const float* post_mean, const float* post_logvar, const float* eps,
              float* terms);
+int pad_predictive(iodine_handle* h, void* stream, int batch, int n_samples, const float* post_mean, const float* post_logvar, const float* eps,
+                   const float* x, int chunk_images, float* z, float* pred_mean, float* pred_m2, float* mask_mean, float* mask_m2, int* votes,
+                   float* ll);
 int pad_decode_backward(iodine_handle* h, void* stream, int batch, const float* g_pred, const float* g_mask, const float* g_mean, float* dz,
                         float* flat_grads, int accumulate);
 int pad_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_dev, float* g_post_mean, float* g_post_logvar, float* flat_grads,

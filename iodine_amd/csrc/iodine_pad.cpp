@@ -313,6 +313,29 @@ int pad_elbo(iodine_handle* h, void* stream, int batch, const float* x, const fl
     return shim_fail(h, iodine_elbo(sh->inner, stream, batch, x, post_mean ? sh->pm_in : nullptr, post_mean ? sh->plv_in : nullptr, sh->eps, terms));
 }
 
+// (the per-pixel outputs have no latent axis: the caller's own buffers; padded latent entries have mean = logvar = eps = 0, so z = 0 there)
+int pad_predictive(iodine_handle* h, void* stream, int batch, int n_samples, const float* post_mean, const float* post_logvar, const float* eps,
+                   const float* x, int chunk_images, float* z, float* pred_mean, float* pred_m2, float* mask_mean, float* mask_m2, int* votes,
+                   float* ll)
+{
+    PadShim* sh = h->shim;
+    PendingWeights once(sh->inner);
+    if (int rc = predictive_check(sh->inner, batch, n_samples, post_mean, post_logvar, eps, x, chunk_images, ll)) return shim_fail(h, rc);
+    hipStream_t st = (hipStream_t)stream;
+    const long long N = (long long)batch * sh->inner->K, R = (long long)n_samples * N;
+    if (int r = shim_scratch(h, (size_t)R * sh->Lp)) return r;
+    HIPCHK(h, launch_resize_rows(st, eps, sh->eps, R, sh->L, sh->Lp));
+    if (post_mean) {
+        HIPCHK(h, launch_resize_rows(st, post_mean, sh->pm_in, N, sh->L, sh->Lp));
+        HIPCHK(h, launch_resize_rows(st, post_logvar, sh->plv_in, N, sh->L, sh->Lp));
+    }
+    const int rc = iodine_predictive(sh->inner, stream, batch, n_samples, post_mean ? sh->pm_in : nullptr, post_mean ? sh->plv_in : nullptr, sh->eps,
+                                     x, chunk_images, z ? sh->z : nullptr, pred_mean, pred_m2, mask_mean, mask_m2, votes, ll);
+    if (rc) return shim_fail(h, rc);
+    if (z) HIPCHK(h, launch_resize_rows(st, sh->z, z, R, sh->Lp, sh->L));
+    return IODINE_OK;
+}
+
 // (the two single-pass backwards write into the scratch their forward sized: the inner call is their first launch, and checks first)
 int pad_decode_backward(iodine_handle* h, void* stream, int batch, const float* g_pred, const float* g_mask, const float* g_mean, float* dz,
                         float* flat_grads, int accumulate)

@@ -332,26 +332,33 @@ def make_log_sigma(sigma, device):
     return torch.full((), math.log(float(sigma)), dtype=torch.float32, device=device, requires_grad=True)
 
 
-def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None):
+def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, bound_samples=0):
     """eval.py:14-28 with the ARI evaluator of lib/eval/ari_eval.py (works under no_grad, unlike the reference).  With
     several ranks every rank evaluates its shard; the samples DistributedSampler appended to pad the shards to equal length
     are dropped (they duplicate the first images) and ``evaluator.global_mean`` holds the ARI over the whole dataset.
     ``slots`` / ``iters``: evaluate at that K / T (``model.K`` / ``model.n_iters`` for the duration of the call, restored afterwards;
-    e.g. weights trained at K = 7, T = 5 evaluated at K = 11) - the ARI tables take K from the masks."""
+    e.g. weights trained at K = 7, T = 5 evaluated at K = 11) - the ARI tables take K from the masks.
+    ``bound_samples`` = S > 0: after each batch's ``reconstruct`` one ``model.predictive(x, samples=S)`` from the posterior it left; the
+    dataset means of the S-sample importance-weighted bound and of the S-sample Monte-Carlo ELBO (per image, nats) are left in
+    ``evaluator.iwae`` / ``evaluator.elbo_mc`` (over all ranks, like ``global_mean``).  0 (default): no launch is added and neither
+    attribute is set."""
+    if isinstance(bound_samples, bool) or int(bound_samples) != bound_samples or bound_samples < 0:
+        raise ValueError(f'evaluate: bound_samples must be an integer >= 0; got {bound_samples!r}')
     saved = (model.K, model.n_iters)
     if slots is not None:
         model.K = slots
     if iters is not None:
         model.n_iters = iters
     try:
-        return _evaluate(model, dataloader, device, evaluator)
+        return _evaluate(model, dataloader, device, evaluator, int(bound_samples))
     finally:
         model.K, model.n_iters = saved
 
 
-def _evaluate(model, dataloader, device, evaluator):
+def _evaluate(model, dataloader, device, evaluator, bound_samples=0):
     evaluator = evaluator or ARIEvaluator()
     evaluator.reset()
+    bounds = []                                                              # per image: (iwae, elbo_mc)
     model.eval()
     dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
     world = torch.distributed.get_world_size() if dist_on else 1
@@ -361,7 +368,18 @@ def _evaluate(model, dataloader, device, evaluator):
     with torch.no_grad():
         for image, masks in dataloader:
             evaluator.evaluate(model, (image.to(device), [m.numpy() for m in masks]))
+            if bound_samples:
+                out = model.predictive(image.to(device), samples=bound_samples)
+                bounds.extend(zip(out.iwae.tolist(), out.elbo_mc.tolist()))
     del evaluator.aris[mine:]
+    if bound_samples:
+        del bounds[mine:]
+        tot = torch.tensor([sum(q[0] for q in bounds), sum(q[1] for q in bounds), float(len(bounds))], dtype=torch.float64,
+                           device=device if dist_on and torch.distributed.get_backend() == 'nccl' else 'cpu')
+        if world > 1:
+            torch.distributed.all_reduce(tot)
+        n = max(float(tot[2]), 1.0)
+        evaluator.iwae, evaluator.elbo_mc = float(tot[0]) / n, float(tot[1]) / n
     stats = torch.tensor([float(sum(evaluator.aris)), float(len(evaluator.aris))], dtype=torch.float64,
                          device=device if dist_on and torch.distributed.get_backend() == 'nccl' else 'cpu')
     if world > 1:
@@ -426,6 +444,9 @@ def make_parser():
     ap.add_argument('--learn-input-gain', action='store_true',
                     help='learn a per-channel gain and offset applied to every batch before the model (six parameters in their own param '
                          'group, trained through the gradient into the image); saved as the checkpoint entry input_gain')
+    ap.add_argument('--eval-samples', type=int, default=0, metavar='S',
+                    help='also report the S-sample importance-weighted bound (IWAE) and the S-sample Monte-Carlo ELBO of the evaluation set, '
+                         'per image in nats (one model.predictive call per batch; 0: off)')
     ap.add_argument('--traverse', metavar='OUT.npz',
                     help='instead of training: after loading (--resume), reconstruct the first batch, traverse the latent units of image 0 '
                          '(each slot, the units with the largest KL, moved along the posterior) and save the grids; see save_traversal')
@@ -490,9 +511,11 @@ def main(argv=None):
                    log=print if rank == 0 else (lambda *a: None), beta=args.beta, beta_warmup_steps=args.beta_warmup,
                    bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border, log_sigma=log_sigma,
                    input_gain=input_gain)
-    ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device)
+    ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, bound_samples=args.eval_samples)
     if rank == 0:
         print('first loss {:.2f} -> last loss {:.2f}; Ari over all ranks: {}'.format(losses[0], losses[-1], ev.global_mean))
+        if args.eval_samples:
+            print('{}-sample bounds per image: IWAE {:.3f}, Monte-Carlo ELBO {:.3f}'.format(args.eval_samples, ev.iwae, ev.elbo_mc))
 
 
 if __name__ == '__main__':

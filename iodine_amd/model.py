@@ -66,6 +66,12 @@ evaluation, the two attributes of iodine.py:210-216 - an anomaly map, a per-slot
 raw under ``weights=`` (the weighted LL is ``sum_p w_p sum_c log_likelihood``), and they come from a kernel of their own, so their sum
 over channels and pixels matches the reported LL to float32 rounding, not bitwise.  ``False`` (default): both are None, no launch runs.
 
+Multi-sample evaluation: ``model.predictive(x, samples=S)`` draws S latents from one posterior (default: the one the last ``reconstruct`` /
+``encode`` / ``forward`` left) and returns a ``Predictive`` - per-pixel mean and variance of the rendered image and of the masks, per-slot vote
+counts with their arg-max and agreement, and with an image the per-sample log-likelihoods, the importance-weighted bound, the Monte-Carlo ELBO and
+the closed-form-KL ELBO per image (``iodine_predictive``: the samples share one decoder pass per chunk and one per-pixel kernel keeps the running
+moments; nothing per sample is written).  Not in the reference, which scores and renders one draw (iodine.py:103, 171).
+
 Extensions over the reference: every entry point takes an optional ``eps`` tensor of shape
 (T+1, B, K, L) replacing the ``torch.randn_like`` draws of ``Gaussian.sample``
 (iodine.py:632) in call order, so that results can be compared with the CPU oracle.  Without
@@ -161,6 +167,46 @@ class SceneEdit:
     mask: Optional[torch.Tensor] = None
     mean: Optional[torch.Tensor] = None
     base: Optional[tuple] = None
+
+
+@dataclasses.dataclass
+class Predictive:
+    """What ``IODINE.predictive`` returns: read-outs over ``samples`` draws from one posterior.  ``z (S, B, K, L)``; ``pred_mean`` /
+    ``pred_var (B, 3, S, S)`` and ``mask_mean`` / ``mask_var (B, K, 1, S, S)`` - mean and population variance (M2 / S, exactly 0 for one
+    sample) of the per-sample ``decode(z[s])``; ``votes (B, K, S, S)`` int32 - samples in which slot k wins the pixel; ``segmentation (B, S,
+    S)`` uint8 - the arg-max of the votes (lowest index on a tie) - and ``agreement (B, S, S)`` - its share of the samples.  With an image
+    also ``ll (S, B)`` - the (weighted) log-likelihood of each sample and image -, ``log_w (S, B)`` float64 = log p(x|z) + log p(z) - log q(z),
+    ``iwae (B)`` = logsumexp_s(log_w) - log S, ``elbo_mc (B)`` = mean_s log_w, ``elbo (B)`` = mean_s ll - KL(q || N(0, 1)) in closed form;
+    else None.  Detached tensors."""
+    z: torch.Tensor
+    pred_mean: torch.Tensor
+    pred_var: torch.Tensor
+    mask_mean: torch.Tensor
+    mask_var: torch.Tensor
+    votes: torch.Tensor
+    segmentation: torch.Tensor
+    agreement: torch.Tensor
+    samples: int
+    ll: Optional[torch.Tensor] = None
+    log_w: Optional[torch.Tensor] = None
+    iwae: Optional[torch.Tensor] = None
+    elbo_mc: Optional[torch.Tensor] = None
+    elbo: Optional[torch.Tensor] = None
+
+
+def sample_bounds(ll, z, eps, post_mean, post_logvar):
+    """The float64 host arithmetic behind ``Predictive``: per-sample log-likelihoods ``ll (S, B)``, the samples ``z`` and their noise ``eps
+    (S, B, K, L)`` and the posterior (B, K, L) -> (log_w (S, B), iwae, elbo_mc, elbo (B)).  With z = mu + exp(logvar / 2) eps the
+    densities are log p(z) - log q(z) = sum_{k,l} (-z^2 / 2 + eps^2 / 2 + logvar / 2) (the 2 pi terms cancel); the importance-weighted bound
+    is taken around the maximum: max_s log_w + log mean_s exp(log_w - max), i.e. logsumexp_s(log_w) - log S, exactly log_w[0] for one sample."""
+    S = ll.shape[0]
+    z, eps, lv, mu = z.double(), eps.double(), post_logvar.double(), post_mean.double()
+    log_w = ll.double() + (-0.5 * z * z + 0.5 * eps * eps + 0.5 * lv.unsqueeze(0)).sum((-2, -1))
+    top = log_w.max(0).values
+    iwae = top + torch.log(torch.exp(log_w - top).sum(0) / S)
+    elbo_mc = log_w.sum(0) / S
+    kl = 0.5 * (lv.exp() + mu * mu - 1.0 - lv).sum((-2, -1))
+    return log_w, iwae, elbo_mc, ll.double().sum(0) / S - kl
 
 
 @dataclasses.dataclass
@@ -1282,6 +1328,106 @@ class IODINE(nn.Module):
             h, self._stream(), B, _lib.ptr(z), E, arr(image), arr(slot), arr([int(r) for r in remove]), _lib.ptr(zn), W,
             _lib.ptr(pred), _lib.ptr(mask), _lib.ptr(mean), *[_lib.ptr(t) for t in base]), h, 'iodine_scene_edit'))
         return SceneEdit(pred, mask, mean, base if return_base else None)
+
+    _PREDICTIVE_IMAGES = 256                    # images' worth of slot-images one chunk of ``predictive`` decodes at most (or one sample)
+
+    @torch.no_grad()
+    def predictive(self, x=None, samples=16, posterior=None, eps=None, weights=None):
+        """Read-outs over ``samples`` draws z_s = mu + exp(logvar / 2) eps_s from ONE posterior: the per-pixel mean and variance of the
+        rendered image and of every mask, how often each slot wins a pixel, and - with an image ``x (B, 3, S, S)`` - the per-image
+        log-likelihood of every sample with the S-sample importance-weighted bound (IWAE), the Monte-Carlo ELBO and the closed-form-KL ELBO
+        built from it.  Returns a ``Predictive``.  The S B K slot-images are decoded by the decoder's own kernels in chunks; one per-pixel
+        kernel folds each chunk into the running moments, so no sample's planes are ever written, and every field is bit for bit
+        independent of how the samples were cut into chunks (``batch_cap`` bounds the arena as it does for ``edit``).
+
+        ``posterior``: ``(mean, logvar)`` of shape (B, K, L), 1 <= K <= 16 taken from it as in ``decode``; default
+        ``model.posterior.mean / logvar`` - what the last ``reconstruct`` / ``encode`` / ``forward`` left (none: RuntimeError).  ``eps``:
+        (S, B, K, L), or None for the library's generator, one draw per sample.  ``weights``: per-pixel observation weights of this call, as
+        everywhere else; needs ``x``.  ``model.sigma`` is read as everywhere else, ``model.beta`` plays no part.  ``z[s]`` is what
+        ``elbo(x, eps=eps[s])`` samples from that posterior, and each sample's image and masks are the bits ``decode(z[s])`` returns.
+
+        NOT differentiable (gradients go through ``decode`` / ``elbo``).  A batch above ``max_batch()`` runs in groups of independent
+        images.  The call counts as a decode for the call order: a saved differentiable call is discarded, ``refinement_state()`` still
+        works after it; the logger and ``self.z / mean / mask`` are not touched."""
+        import numbers
+        L, Si = self.dim_latent, self.img_size
+        if isinstance(samples, bool) or not isinstance(samples, numbers.Integral) or samples < 1:
+            raise ValueError(f'IODINE.predictive: samples must be an integer >= 1; got {samples!r}')
+        S = int(samples)
+        if weights is not None and x is None:
+            raise ValueError('IODINE.predictive: weights= weigh the likelihood of an image, but x is None')
+        if posterior is None:
+            posterior = (self.posterior.mean, self.posterior.logvar)
+            if posterior[0] is None or posterior[1] is None:
+                raise RuntimeError('IODINE.predictive: no posterior - pass posterior=(mean, logvar) or call reconstruct / encode / forward '
+                                   'first (they leave model.posterior.mean / logvar)')
+        if (not isinstance(posterior, (tuple, list)) or len(posterior) != 2 or any(not torch.is_tensor(t) for t in posterior)
+                or posterior[0].dim() != 3 or posterior[0].shape != posterior[1].shape or posterior[0].shape[2] != L
+                or not 1 <= posterior[0].shape[1] <= 16 or posterior[0].shape[0] < 1):
+            got = tuple(tuple(t.shape) if torch.is_tensor(t) else type(t).__name__ for t in posterior) if isinstance(posterior, (tuple, list)) else type(posterior).__name__
+            raise ValueError(f'IODINE.predictive: posterior must be (mean, logvar), both of shape (B, K, {L}) with B >= 1 and 1 <= K <= 16; got {got}')
+        pm, plv = posterior
+        B, K = int(pm.shape[0]), int(pm.shape[1])
+        if eps is not None and (not torch.is_tensor(eps) or tuple(eps.shape) != (S, B, K, L)):
+            raise RuntimeError(f'IODINE.predictive: eps must have shape {(S, B, K, L)} (samples, B, K, L); got '
+                               f'{tuple(eps.shape) if torch.is_tensor(eps) else type(eps).__name__}')
+        if x is not None:
+            x = self._check_x(x)
+            if x.shape[0] != B:
+                raise ValueError(f'IODINE.predictive: x has {x.shape[0]} images, the posterior {B}')
+            weights = self._check_weights(weights, x, 'predictive')
+        T = self._shape[1] if self._shape is not None else int(self._cfg.iters)      # plays no part, as in decode
+        sigma = self._read_objective(T)[0]
+        dev = pm.device
+        self._ensure_handle(dev)                            # (a CPU tensor is refused here, after the argument checks)
+        if plv.device != dev or (x is not None and x.device != dev):
+            raise ValueError('IODINE.predictive: the posterior and x must be on the same device')
+        pm, plv = pm.detach().to(torch.float32).contiguous(), plv.detach().to(torch.float32).contiguous()
+        cap = self.max_batch(K=K, T=T)
+        if B > cap:                                         # groups of independent images; the noise is cut along its batch axis
+            parts = [self.predictive(None if x is None else x[s:e], S, (pm[s:e], plv[s:e]), None if eps is None else eps[:, s:e],
+                                     None if weights is None else weights[s:e]) for s, e in self._chunks(B, cap)]
+            cat = lambda name, dim: None if getattr(parts[0], name) is None else torch.cat([getattr(q, name) for q in parts], dim)
+            return Predictive(cat('z', 1), cat('pred_mean', 0), cat('pred_var', 0), cat('mask_mean', 0), cat('mask_var', 0), cat('votes', 0),
+                              cat('segmentation', 0), cat('agreement', 0), S, cat('ll', 1), cat('log_w', 1), cat('iwae', 0), cat('elbo_mc', 0),
+                              cat('elbo', 0))
+        if not hasattr(_lib.lib(), 'iodine_predictive'):
+            raise RuntimeError('IODINE.predictive: this build of libiodine_hip.so has no iodine_predictive')
+        if eps is None:                                     # one draw id per sample
+            eps = torch.empty((S, B, K, L), device=dev, dtype=torch.float32)
+            for s in range(S):
+                eps[s].copy_(self._normals(None, (B, K, L), dev))
+        else:
+            eps = eps.detach().to(device=dev, dtype=torch.float32).contiguous()
+        W = min(cap, max(B, min(S * B, self._PREDICTIVE_IMAGES)))
+        st = self._state                                    # the arena is re-planned for W images: an LSTM state still in it is fetched first
+        if st is not None and st.h is None and st.serial is not None and st.serial == self._call_serial:
+            self.refinement_state()
+        h = self._sync_params(dev)
+        self._ensure_workspace(h, W, 0, dev, K, T)
+        self._ensure_objective(h, (sigma,) + tuple(self._objective[1:]), dev)     # sigma of this call; beta / iteration weights play no part
+        f = dict(device=dev, dtype=torch.float32)
+        z = torch.empty((S, B, K, L), **f)
+        pmean, pm2 = torch.empty((B, 3, Si, Si), **f), torch.empty((B, 3, Si, Si), **f)
+        mmean, mm2 = torch.empty((B, K, 1, Si, Si), **f), torch.empty((B, K, 1, Si, Si), **f)
+        votes = torch.empty((B, K, Si, Si), device=dev, dtype=torch.int32)
+        ll = torch.empty((S, B), **f) if x is not None else None
+        self._call_serial += 1
+        ws = self._send_weights(h, weights)                 # (ws: alive until the call is queued)
+        self._launch(dev, lambda: _lib.check(_lib.lib().iodine_predictive(
+            h, self._stream(), B, S, _lib.ptr(pm), _lib.ptr(plv), _lib.ptr(eps), _lib.ptr(x), W, _lib.ptr(z), _lib.ptr(pmean), _lib.ptr(pm2),
+            _lib.ptr(mmean), _lib.ptr(mm2), _lib.ptr(votes), _lib.ptr(ll)), h, 'iodine_predictive'))
+        del ws
+        # arg-max of the votes with the lowest index on a tie: the largest of votes * K + (K - 1 - k)
+        key = votes.to(torch.int64) * K + torch.arange(K - 1, -1, -1, device=dev).view(1, K, 1, 1)
+        top = key.max(1).values
+        seg = (K - 1 - top % K).to(torch.uint8)
+        agreement = (top // K).to(torch.float32) / S
+        out = Predictive(z, pmean, pm2 / S, mmean, mm2 / S, votes, seg, agreement, S)
+        if x is not None:
+            out.ll = ll
+            out.log_w, out.iwae, out.elbo_mc, out.elbo = sample_bounds(ll, z, eps, pm, plv)
+        return out
 
     _STALE = ('IODINE: backward of a stale {0} - the library keeps the saved state of ONE differentiable call and another forward / '
               'reconstruct / decode / elbo call has re-used it since, or it was differentiated already (the reference would hold a second '
