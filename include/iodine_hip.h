@@ -566,8 +566,16 @@ int iodine_seg_overlap(void* stream, const unsigned char* seg_a, const unsigned 
  * responsibilities: iodine.py:185-216) on libm expf + IEEE division like ATen, where the default path uses v_exp_f32 / v_rcp_f32
  * on their bounded arguments (pixel_terms.h); 1 = fp32 operands split into fp16 hi+lo with one power-of-two
  * scale per 8 x 16 cell, 3 fp16 MFMAs, fp32 accumulate: products carry >= 22 bits relative to the CELL maximum (tile-relative,
- * not element-relative) -- default; only the selected path's weight packs are maintained, so a change must be followed by
- * iodine_set_params before the next compute call),
+ * not element-relative) -- default; 2 = 1 everywhere except in the weight-stationary decoder kernel (3 x 3 convs C -> C, C = 32 / 64,
+ * power-of-two image sizes >= 16, conv_variant 6): there the forward, the data gradient and its two row-sum forms take each product
+ * from ONE fp16 MFMA -- the hi half of the same weight pack (round to nearest) times the activations rounded to fp16 to NEAREST EVEN at
+ * the same per-cell scale (no lo halves are loaded, computed or staged); fp32 accumulate, bias, ELU / ELU', side buffers and row sums
+ * as before.  Products then carry 11 bits: fp16-class results (ELBO ~2e-4, reconstruction ~5e-3 abs. against fp64), meant for
+ * evaluation; training works and is differentiated consistently, outside the 1e-3 gradient budget.  Weight gradients, the broadcast
+ * layer, the output conv, the refinement stack, the per-pixel kernels and the LDS-tiled / generic decoder kernels keep the
+ * arithmetic and bits of 1: where the weight-stationary kernel does not run (other image sizes, conv_variant 1) 2 computes exactly
+ * what 1 computes.  Other values: IODINE_ERR_INVALID.  Only the selected path's weight packs are maintained, so a change must be
+ * followed by iodine_set_params before the next compute call (1 and 2 read the same packs; a change between them asks for it too)),
  * "gen_conv_precision" (the stride-1 convs C -> C of a decoder on the GENERIC path -- DEC.KERNEL_SIZE 5 / 7 or channel counts other than
  * 32 / 64: 0 -- default = exact fp32 MFMA (v_mfma_f32_16x16x4_f32, kernels_generic.hip); 1 = forward and data gradient on the split-fp16
  * kernel of kernels_gensplit.hip -- fp16 hi + lo operands, one power-of-two scale per staged 16 x 16-tile halo and channel chunk and per
@@ -643,7 +651,8 @@ void iodine_linspace_host(int n, float* out);
  * mode 12: its exact-fp32 form (weights as fp32 in the same registers, v_mfma_f32_16x16x4_f32; conv_precision 0),
  * modes 5 / 6: split-fp16 stride-2 forward / data gradient of the refinement stack, modes 13 / 14: their exact-fp32 forms
  * (v_mfma_f32_32x32x2_f32, conv_precision 0), modes 15 / 16: the weight-stationary stride-2 conv c -> c of refinement layers 1 ..
- * (c = 64; split-fp16 / exact fp32). */
+ * (c = 64; split-fp16 / exact fp32), mode 17: mode 10 with ONE fp16 MFMA per product (conv_precision 2: same arguments, epilogues
+ * and launch_cell_max side buffer). */
 int iodine_op_conv3x3(void* stream, int mode, const float* in_nhwc, const float* w_oihw, const float* bias,
                       const float* aux, float* out_nhwc, int n, int ih, int iw, int w_o, int w_i, int cin_pad,
                       int cout, int stride, int epi, int transpose_flip);

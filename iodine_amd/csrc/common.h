@@ -286,7 +286,9 @@ hipError_t launch_resize_rows(hipStream_t st, const float* src, float* dst, long
 hipError_t launch_cell_max(hipStream_t st, const float* x, float* tmax, int N, int S, int C);
 hipError_t launch_conv3x3_ws_f16x3(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias,
                                    const float* aux, float* out, const float* tmax_in, float* tmax_out, int N, int S, int c,
-                                   int epi, int rev);
+                                   int epi, int rev, int products = 3);
+// (products: fp16 MFMAs per product - 3 = the split, fp32-class; 1 = hi.hi alone with the activations rounded to nearest even, fp16-class:
+// option conv_precision 2.  Same pack, same side buffers.)
 // exact-fp32 form of the same kernel (conv_precision 0): fp32 weights in the register layout (same byte count), v_mfma_f32_16x16x4_f32
 hipError_t launch_pack_conv_weights_ws32(hipStream_t st, const float* src, int C, int tflip, void* dst);
 hipError_t launch_conv3x3_ws_f32(hipStream_t st, const float* in, const void* wpk, const float* bias, const float* aux, float* out,

@@ -68,11 +68,13 @@ DecPath dec_path(const iodine_handle* h)
 {
     if (h->generic) return DEC_GENERIC;
     const bool ws = h->variant == 6 && h->S >= 16 && (h->S & (h->S - 1)) == 0;
-    if (h->precision == 1) return ws ? DEC_WS_F16 : DEC_TILE_F16;
+    if (h->precision != 0) return ws ? DEC_WS_F16 : DEC_TILE_F16;
     return ws && (h->Cd == 64 || h->Cd == 32) ? DEC_WS_F32 : DEC_TILE_F32;
 }
 
 bool dec_f16(DecPath p) { return p == DEC_WS_F16 || p == DEC_TILE_F16; }
+// fp16 MFMAs per product on DEC_WS_F16: the split's three, or hi.hi alone (conv_precision 2, the only kernel that option changes)
+int dec_ws_products(const iodine_handle* h) { return h->precision == 2 ? 1 : 3; }
 
 // Which kernels the refinement conv stack runs on, decided the same way.  The family depends on the configuration and conv_precision only:
 // iodine_set_params switches on it alone and keeps every pack of the family current - the per-form options do not invalidate the parameters.
@@ -86,7 +88,7 @@ RefFamily ref_family(const iodine_handle* h)
 {
     if (h->gen_ref) return REF_GENERIC;
     for (int l = 0, s = h->S; l < h->Dr; ++l, s /= 2) if (s % 2 != 0) return REF_GATHER;
-    return h->precision == 1 ? REF_S2_F16 : REF_S2_F32;
+    return h->precision != 0 ? REF_S2_F16 : REF_S2_F32;
 }
 bool ref_s2(RefFamily f) { return f == REF_S2_F16 || f == REF_S2_F32; }
 // Which optional packs exist at these shapes: iodine_set_params writes a pack where its predicate holds, a launch site reads it only behind it.
@@ -122,7 +124,7 @@ int dec_conv_fwd(iodine_handle* h, hipStream_t st, int N, int l)
     switch (dec_path(h)) {
     case DEC_WS_F16:
         PROF(h, st, "conv_tile_fwd", launch_conv3x3_ws_f16x3(st, b.act[l - 1], h->dec_wsf[l], h->dec_wmeta[l], h->dec_b[l], nullptr, b.act[l],
-                                                             b.tmax_act[l - 1], b.tmax_act[l], N, S, Cd, EPI_BIAS_ELU, l & 1));
+                                                             b.tmax_act[l - 1], b.tmax_act[l], N, S, Cd, EPI_BIAS_ELU, l & 1, dec_ws_products(h)));
         break;
     case DEC_TILE_F16:
         PROF(h, st, "conv_tile_fwd", launch_conv3x3_tile_f16x3(st, b.act[l - 1], h->dec_wf16[l], h->dec_wmeta[l], h->dec_b[l], nullptr, b.act[l],
@@ -147,7 +149,7 @@ int dec_conv_dgrad(iodine_handle* h, hipStream_t st, int N, int l, int cur, floa
     switch (dec_path(h)) {
     case DEC_WS_F16:
         PROF(h, st, "conv_tile_dgrad", launch_conv3x3_ws_f16x3(st, b.dpre[cur], h->dec_wsb[l], h->dec_wmeta[l] + 2, nullptr, b.act[l - 1], out,
-                                                               b.tmax_dpre[cur], b.tmax_dpre[cur ^ 1], N, S, Cd, epi, l & 1));
+                                                               b.tmax_dpre[cur], b.tmax_dpre[cur ^ 1], N, S, Cd, epi, l & 1, dec_ws_products(h)));
         break;
     case DEC_TILE_F16:
         PROF(h, st, "conv_tile_dgrad", launch_conv3x3_tile_f16x3(st, b.dpre[cur], h->dec_wb16[l], h->dec_wmeta[l] + 2, nullptr, b.act[l - 1], out,
@@ -1659,8 +1661,11 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
         return IODINE_OK;
     }
     if (!strcmp(key, "conv_precision")) {
-        if (value != 0 && value != 1) return h->fail(IODINE_ERR_INVALID, "conv_precision must be 0 (f32) or 1 (f16x3)");
-        if (h->precision != (int)value) h->params_set = false;    // the other path's weight packs are not kept up to date
+        if (value != 0 && value != 1 && value != 2)
+            return h->fail(IODINE_ERR_INVALID, "conv_precision must be 0 (f32), 1 (f16x3) or 2 (f16x3 with single-product fp16 weight-stationary decoder convs)");
+        // the other path's weight packs are not kept up to date (1 and 2 read the same packs; a switch between them invalidates the parameters
+        // all the same, so that a saved forward pass is never finished at another precision)
+        if (h->precision != (int)value) h->params_set = false;
         h->precision = (int)value;
         return IODINE_OK;
     }

@@ -137,7 +137,7 @@ int iodine_op_conv3x3(void* stream, int mode, const float* in, const float* w, c
         if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(s2 f16x3): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }
         return IODINE_OK;
     }
-    if (mode == 9 || mode == 10) {  // weight-stationary split-fp16 kernel (per-cell max side buffer from launch_cell_max)
+    if (mode == 9 || mode == 10 || mode == 17) {  // weight-stationary split-fp16 kernel (per-cell max side buffer from launch_cell_max); 17: its one-product form (conv_precision 2)
         if (cin_pad != cout || w_o != cout || w_i != cout || ih != iw || ih % 16 != 0) { g_create_error = "iodine_op_conv3x3(ws): shape"; return IODINE_ERR_INVALID; }
         const size_t wb = conv_ws_wpk_bytes(cout), tf = conv_ws_tmax_floats(n, ih);
         char* buf = nullptr;
@@ -146,7 +146,7 @@ int iodine_op_conv3x3(void* stream, int mode, const float* in, const float* w, c
         float *tin = (float*)(buf + wb + 64), *tout = tin + tf;
         hipError_t e2 = launch_pack_conv_weights_ws(st, w, cout, tflip, meta, buf);
         if (e2 == hipSuccess) e2 = launch_cell_max(st, in, tin, n, ih, cout);
-        if (e2 == hipSuccess) e2 = launch_conv3x3_ws_f16x3(st, in, buf, meta, bias, aux, out, tin, tout, n, ih, cout, epi, 0);
+        if (e2 == hipSuccess) e2 = launch_conv3x3_ws_f16x3(st, in, buf, meta, bias, aux, out, tin, tout, n, ih, cout, epi, 0, mode == 17 ? 1 : 3);
         if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
         (void)hipFree(buf);
         if (e2 != hipSuccess) { g_create_error = std::string("iodine_op_conv3x3(ws): ") + hipGetErrorString(e2); return IODINE_ERR_HIP; }

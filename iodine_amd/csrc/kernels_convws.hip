@@ -108,7 +108,11 @@ IOD_DEVINL float pixel_lane_sum(float v)
 constexpr int ws_pxb(int c) { return 160; }
 constexpr int ws_bpc(int c, int epi) { return 2; }
 
-template <int C, int EPI, bool F32 = false>
+// NPROD: fp16 MFMAs per product of the split-fp16 form.  3 = hi.lo + lo.hi + hi.hi (conv_precision 1).  1 = hi.hi alone (conv_precision 2):
+// the lo halves of the weights are never loaded, the activations are rounded to NEAREST EVEN at the same tile scale (with no lo half behind
+// it, the truncation of the split would bias every sum toward zero) and their lo half is neither computed nor staged; accumulation, epilogues
+// and side buffers are the same code.  The staged pixel keeps its 160-byte stride (the lo slot stays unused).
+template <int C, int EPI, bool F32 = false, int NPROD = 3>
 __global__ __launch_bounds__(256, ws_bpc(C, EPI))
 void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restrict__ wpk, const float* __restrict__ wmeta,
                              const float* __restrict__ bias, const float* __restrict__ aux, float* __restrict__ out,
@@ -132,6 +136,8 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
     constexpr int SEGS = C / 4, PPI = 64 / SEGS, NEP = 32 / PPI;      // whole-pixel layout: float4 segments, pixels / instruction
     static_assert(C == 64 || C == 32, "channel counts of the shipped decoders");
     static_assert(EPI == EPI_BIAS_ELU || EPI == EPI_MUL_ELUGRAD || ROWS, "epilogue");
+    static_assert(NPROD == 3 || (NPROD == 1 && !F32), "products per term: the split (3) or hi.hi alone (1, fp16 form only)");
+    constexpr bool ONE = NPROD == 1;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
 
@@ -173,14 +179,22 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
         for (int c = 0; c < NCHUNK; ++c)
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
+                if constexpr (ONE) {                         // (the lo halves of the pack are not read)
+                    const uint4 h = wp[((c * 9 + t) * 2 + 0) * 64];
+                    __builtin_memcpy(&wh[c][t], &h, 16);
+                } else {
                 const uint4 h = wp[((c * 9 + t) * 2 + 0) * 64], l = wp[((c * 9 + t) * 2 + 1) * 64];
                 __builtin_memcpy(&wh[c][t], &h, 16);
                 __builtin_memcpy(&wl[c][t], &l, 16);
+                }
             }
 #pragma unroll
         for (int c = 0; c < NCHUNK; ++c)
 #pragma unroll
-            for (int t = 0; t < 9; ++t) asm volatile("" : "+v"(wh[c][t]), "+v"(wl[c][t]));      // opaque: stay in registers
+            for (int t = 0; t < 9; ++t) {
+                if constexpr (ONE) asm volatile("" : "+v"(wh[c][t]));
+                else asm volatile("" : "+v"(wh[c][t]), "+v"(wl[c][t]));      // opaque: stay in registers
+            }
     };
     float inv_w = 1.f;
     if constexpr (!F32) inv_w = wmeta[1];
@@ -265,6 +279,14 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
         if constexpr (F32) {                                 // exact fp32: the float4 goes to LDS as it is
             const unsigned o32 = (k == NIN - 1 && last_idle) ? (unsigned)(NPX * PXB) : lw0 + (unsigned)(k * 32 * PXB);
             *reinterpret_cast<f32x4*>(sb + o32) = v;
+        } else if constexpr (ONE) {                          // one product: fp16 to nearest even (v_cvt_pk_f16_f32), no lo half
+            v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
+            typedef _Float16 hr2 __attribute__((ext_vector_type(2)));
+            const hr2 h01 = {(_Float16)v.x, (_Float16)v.y}, h23 = {(_Float16)v.z, (_Float16)v.w};
+            uint2 hi;
+            __builtin_memcpy(&hi.x, &h01, 4); __builtin_memcpy(&hi.y, &h23, 4);
+            const unsigned o = (k == NIN - 1 && last_idle) ? (unsigned)(NPX * PXB) : lw0 + (unsigned)(k * 32 * PXB);
+            *reinterpret_cast<uint2*>(sb + o) = hi;
         } else {
         v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
         typedef __fp16 h2 __attribute__((ext_vector_type(2)));
@@ -300,7 +322,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
             constexpr int hr = s / 3, dx = s % 3;
             constexpr int off = (hr * HC + dx) * PXB;
             WS_DSR128(fr.h, b, off);
-            WS_DSR128(fr.l, b, off + 64);
+            if constexpr (!ONE) WS_DSR128(fr.l, b, off + 64);
         };
         auto MMA = [&](auto sc, const Frag& fr) {
             constexpr int s = decltype(sc)::value;
@@ -322,6 +344,13 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
                         const int y = hr - dy;
                         if (y >= 0 && y < RW) acc[y] = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[c][dy * 3 + dx][j], fr.l[j], acc[y], 0, 0, 0);
                     }
+            } else if constexpr (ONE) {
+                // hi.hi alone: the three dy accumulators are the independent chains between two fragment reads
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy) {
+                    const int y = hr - dy;
+                    if (y >= 0 && y < RW) acc[y] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[c][dy * 3 + dx], fr.h, acc[y], 0, 0, 0);
+                }
             } else {
             // three passes, accumulators interleaved (consecutive MFMAs never share an accumulator)
 #pragma unroll
@@ -346,11 +375,13 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
             constexpr int s = decltype(sc)::value;
             if constexpr (s + 1 < NS) {
                 LOADF(integral_constant<int, (s + 1 < NS ? s + 1 : 0)>{}, f[(s + 1) & 1], base);
-                asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
+                if constexpr (ONE) asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory");     // (one read per fragment in flight)
+                else asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
             } else {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
-            asm volatile("" : "+v"(f[s & 1].h), "+v"(f[s & 1].l));
+            if constexpr (ONE) asm volatile("" : "+v"(f[s & 1].h));
+            else asm volatile("" : "+v"(f[s & 1].h), "+v"(f[s & 1].l));
             __builtin_amdgcn_sched_barrier(0);
 #ifndef WS_ABL_NOMFMA
             MMA(sc, f[s & 1]);
@@ -663,14 +694,14 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
 #undef WS_SGPR_SETTLE
 }
 
-template <int C, int EPI, bool F32 = false>
+template <int C, int EPI, bool F32 = false, int NPROD = 3>
 static hipError_t launch_ws_inst(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias,
                                  const float* aux, float* out, const float* tmax_in, float* tmax_out, int N, int S, int rev)
 {
     constexpr size_t buf_in = (size_t)(18 * 10 + 1) * ws_pxb(C), buf_out = (size_t)128 * (C * 4 + 32);
     constexpr size_t lds = 2 * (buf_in > buf_out ? buf_in : buf_out);
     static std::atomic<unsigned> attr_devs{0};                             // devices this instance is configured on
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_ws_f16x3_kernel<C, EPI, F32>, (int)lds, attr_devs); e != hipSuccess) return e;
+    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_ws_f16x3_kernel<C, EPI, F32, NPROD>, (int)lds, attr_devs); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     int lgS = 0;
@@ -682,7 +713,7 @@ static hipError_t launch_ws_inst(hipStream_t st, const float* in, const void* wp
     if (const char* e = getenv("IODINE_WS_BPC")) bpc = atoi(e);
 #endif
     const int bpx = std::min(per_xcd, std::max(1, bpc * n_cu / 8));
-    hipLaunchKernelGGL((conv3x3_ws_f16x3_kernel<C, EPI, F32>), dim3(8 * bpx), dim3(256), lds, st, in,
+    hipLaunchKernelGGL((conv3x3_ws_f16x3_kernel<C, EPI, F32, NPROD>), dim3(8 * bpx), dim3(256), lds, st, in,
                        reinterpret_cast<const uint4*>(wpk), wmeta, bias, aux, out, tmax_in, tmax_out, S, lgS, ntiles, rev);
 #ifdef IODINE_TILE_PROF
     {
@@ -748,11 +779,13 @@ static hipError_t launch_ws_inst(hipStream_t st, const float* in, const void* wp
 
 hipError_t launch_conv3x3_ws_f16x3(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias,
                                    const float* aux, float* out, const float* tmax_in, float* tmax_out, int N, int S, int c,
-                                   int epi, int rev)
+                                   int epi, int rev, int products)
 {
     // power-of-two image sizes only; the per-cell max of the INPUT (tmax_in, launch_cell_max or the producer's epilogue) is required
     if (S < 16 || (S & (S - 1)) != 0 || !tmax_in || (epi != EPI_L0ROWS && epi != EPI_L0ROWSX && !tmax_out)) return hipErrorInvalidValue;
-#define WS_CASE(CC, EP) if (c == CC && epi == EP) return launch_ws_inst<CC, EP>(st, in, wpk, wmeta, bias, aux, out, tmax_in, tmax_out, N, S, rev);
+    if (products != 1 && products != 3) return hipErrorInvalidValue;
+#define WS_CASE(CC, EP) if (c == CC && epi == EP) return products == 1 ? launch_ws_inst<CC, EP, false, 1>(st, in, wpk, wmeta, bias, aux, out, tmax_in, tmax_out, N, S, rev) \
+                                                                      : launch_ws_inst<CC, EP>(st, in, wpk, wmeta, bias, aux, out, tmax_in, tmax_out, N, S, rev);
     WS_CASE(64, EPI_BIAS_ELU) WS_CASE(64, EPI_MUL_ELUGRAD) WS_CASE(64, EPI_L0ROWS) WS_CASE(64, EPI_L0ROWSX)
     WS_CASE(32, EPI_BIAS_ELU) WS_CASE(32, EPI_MUL_ELUGRAD) WS_CASE(32, EPI_L0ROWS) WS_CASE(32, EPI_L0ROWSX)
 #undef WS_CASE

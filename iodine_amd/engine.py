@@ -417,6 +417,10 @@ def make_parser():
                     help='clip the global gradient norm at this value (train.py:64; the paper uses 5.0)')
     ap.add_argument('--clevr'); ap.add_argument('--dsprites')
     ap.add_argument('--resume'); ap.add_argument('--save')
+    ap.add_argument('--conv-precision', type=int, choices=[0, 1, 2], default=1,
+                    help='3x3 convs of the tuned decoder and refinement stacks: 0 = exact fp32 MFMA, 1 = split-fp16 (3 x f16 MFMA, fp32-class '
+                         'accuracy; default), 2 = as 1 with the weight-stationary decoder convs on ONE fp16 MFMA per product (fp16-class: '
+                         'meant for evaluation - --resume with --eval-samples / --traverse; training runs, outside the 1e-3 gradient budget)')
     ap.add_argument('--gen-conv-precision', type=int, choices=[0, 1], default=0,
                     help='generic decoder convs C -> C (KERNEL_SIZE 5 / 7, other channel counts): 0 = exact fp32 MFMA, '
                          '1 = split-fp16 (3 x f16 MFMA, fp32-class accuracy) forward and data gradient')
@@ -471,6 +475,8 @@ def main(argv=None):
     torch.manual_seed(0)                                                     # same initial replica on every rank
     model = IODINE(arch).to(device)
     model.manual_seed(1000 + rank)                                           # ... but its own reparameterisation noise
+    if args.conv_precision != 1:
+        model.set_option('conv_precision', args.conv_precision)
     if args.gen_conv_precision:
         model.set_option('gen_conv_precision', args.gen_conv_precision)
     if args.sigma is not None:

@@ -925,7 +925,12 @@ class IODINE(nn.Module):
     def set_option(self, key: str, value: float):
         """Debug/test options of the library (e.g. ``stop_after_iters``); applied to the live handle.  ``graph``: hipGraph replay of the
         fixed-shape launch sequences, one graph per distinct argument tuple - which includes ``model.sigma`` / ``beta`` / ``iter_weights``:
-        an objective that changes every step (a beta warm-up) runs eagerly until it repeats."""
+        an objective that changes every step (a beta warm-up) runs eagerly until it repeats.  ``conv_precision``: 0 = exact fp32 MFMA (the
+        strict path), 1 = split fp16, three MFMAs per product, fp32-class (default), 2 = as 1 except that the weight-stationary decoder
+        convs (3 x 3, 32 / 64 channels, power-of-two image sizes >= 16, ``conv_variant`` 6) form each product from ONE fp16 MFMA of operands
+        rounded to nearest even at their cell / tensor scale: fp16-class forward and data gradient for faster evaluation (``reconstruct``,
+        ``predictive``, ``edit``, ``decode``); every other kernel, and every shape that kernel does not run, computes what 1 computes.
+        Training at 2 is differentiated consistently, its gradients are outside the 1e-3 budget.  tests/f16x1_reference.py defines the mode."""
         self._options[key] = float(value)
         if key in _WRAPPER_OPTIONS:                 # handled by this wrapper, unknown to the library
             return
