@@ -1,5 +1,7 @@
 // What the translation units of libiodine_hip.so share: the handle, its workspace carve-up and call state, and the declarations the
-// padded-handle adapter (iodine_pad.cpp) needs from the compute handle (iodine_api.cpp).  Not part of the ABI (include/iodine_hip.h).
+// padded-handle adapter (iodine_pad.cpp) needs from the compute handle (iodine_checks.cpp, iodine_train.cpp).  What the compute handle's own
+// files share - selectors, launch sequences, the planning layer - is in iodine_host.h, included at the end.  Not part of the ABI
+// (include/iodine_hip.h).
 #pragma once
 #include "../../include/iodine_hip.h"
 #include "common.h"
@@ -284,7 +286,7 @@ struct FrameSet { const int* idx = nullptr; int n = 0; float* const* out = nullp
 // (frames: NULL or the cotangents on chosen evaluations)
 struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv, *lstm_h, *lstm_c; float* const* g_state; const FrameSet* frames; };
 
-// The host-only refusals of the entry points (iodine_api.cpp): null and batch checks, params_set, the 2^31 limits, the frames and
+// The host-only refusals of the entry points (iodine_checks.cpp): null and batch checks, params_set, the 2^31 limits, the frames and
 // iteration-weight counts, the stop_after / trajectory rule, stale state.  They launch nothing, allocate nothing and change nothing but the
 // handle's message.  An entry point calls its check first; the padded boundary calls it on the inner handle with the caller's pointers (only
 // their nullness matters) before it allocates scratch or launches a resize, so both kinds of handle refuse the same calls in the same words.
@@ -354,3 +356,5 @@ int pad_debug_copy(iodine_handle* h, void* stream, const char* name, int iter, f
 int pad_profile_read(iodine_handle* h, const char* category, double* total_ms, long long* launches, int reset);
 
 #pragma GCC visibility pop
+
+#include "iodine_host.h"

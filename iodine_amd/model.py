@@ -958,7 +958,7 @@ class IODINE(nn.Module):
     # ---- inference: iodine.py:59-112 ------------------------------------------------------------
     def max_batch(self, training: bool = False, K: Optional[int] = None, T: Optional[int] = None) -> int:
         """Images one library call takes: the kernels index an activation tensor [B*K][pixels][channels] with 32-bit element
-        offsets (iodine_api.cpp check_ready / iodine_train_forward).  Larger batches are run in chunks of at most this many
+        offsets (check_ready in iodine_plan.cpp / train_forward_check in iodine_checks.cpp).  Larger batches are run in chunks of at most this many
         images by the methods below - images are independent.  The ``batch_cap`` option lowers it (tests).
         K / T: the shape of the call (default ``self.K`` / ``self.n_iters``)."""
         K, T = self._run_shape(K, T)

@@ -44,7 +44,10 @@ def test_header_documents_every_option_and_profile_category():
     assert {'conv_precision', 'refine_l0_fused', 'profile_stride'} <= options            # the scan itself works
     missing = sorted(o for o in options if f'"{o}"' not in header)
     assert not missing, f'options accepted by iodine_set_option but absent from the header: {missing}'
-    cats = set(re.findall(r'PROF\(h, st, (?:[^",;]*\? *)?"([a-z_0-9]+)"', api)) | set(re.findall(r'\? "([a-z_0-9]+)" : "([a-z_0-9]+)"', api)[0])
+    # (the launch sites are spread over the host files: iodine_dispatch.cpp holds most, the entry points a few of their own)
+    csrc = os.path.join(ROOT, 'iodine_amd', 'csrc')
+    host = ''.join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith('.cpp'))
+    cats = set(re.findall(r'PROF\(h, st, (?:[^",;]*\? *)?"([a-z_0-9]+)"', host)) | set(re.findall(r'\? "([a-z_0-9]+)" : "([a-z_0-9]+)"', host)[0])
     assert {'conv_tile_fwd', 'refine_l0f', 'refine_bwd01', 'dec_out_bwd'} <= cats
     missing = sorted(c for c in cats if f'"{c}"' not in header)
     assert not missing, f'profile categories absent from the header: {missing}'
@@ -104,7 +107,7 @@ def test_module_surface_matches_reference_names():
 
 
 def test_max_batch_and_chunking_plan():
-    """IODINE.max_batch mirrors the library's 32-bit offset limits (iodine_api.cpp check_ready / iodine_train_forward); larger
+    """IODINE.max_batch mirrors the library's 32-bit offset limits (check_ready in iodine_plan.cpp / train_forward_check in iodine_checks.cpp); larger
     batches are cut into balanced runs of independent images."""
     from iodine_amd import IODINE
     from iodine_amd.model import clevr6_arch
@@ -148,13 +151,31 @@ def test_reference_checkpoint_loads_on_cpu_side(tmp_path):
 
 def test_ablation_hook_build_of_the_host_file_compiles():
     """tools/helper_cost.py and the DESIGN.md helper-cost figures come from a -DIODINE_XSKIP_HOOK build; the guard sits in front of
-    an if / else in decoder_backward_data and once swallowed a declaration: keep that build compiling."""
+    an if / else in decoder_backward_data (iodine_dispatch.cpp) and once swallowed a declaration: keep that build compiling,
+    in every host file that mentions the hook (the launch sequences, and iodine_api.cpp for the option)."""
     import shutil
     import subprocess
     hipcc = '/opt/rocm/bin/hipcc' if os.path.exists('/opt/rocm/bin/hipcc') else shutil.which('hipcc')
     if not hipcc:
         pytest.skip('hipcc not installed')
-    src = os.path.join(ROOT, 'iodine_amd', 'csrc', 'iodine_api.cpp')
-    r = subprocess.run([hipcc, '-fsyntax-only', '--cuda-host-only', '--offload-arch=gfx950', '-std=c++17', '-x', 'hip', '-Wno-dangling-else',
-                        '-Wno-unused-command-line-argument', '-DIODINE_XSKIP_HOOK', src], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    csrc = os.path.join(ROOT, 'iodine_amd', 'csrc')
+    srcs = [f for f in sorted(os.listdir(csrc)) if f.endswith('.cpp') and 'IODINE_XSKIP_HOOK' in open(os.path.join(csrc, f)).read()]
+    assert {'iodine_dispatch.cpp', 'iodine_api.cpp'} <= set(srcs)
+    for f in srcs:
+        r = subprocess.run([hipcc, '-fsyntax-only', '--cuda-host-only', '--offload-arch=gfx950', '-std=c++17', '-x', 'hip', '-Wno-dangling-else',
+                            '-Wno-unused-command-line-argument', '-DIODINE_XSKIP_HOOK', os.path.join(csrc, f)], capture_output=True, text=True)
+        assert r.returncode == 0, f + '\n' + r.stderr[-2000:]
+
+
+def test_exported_table_is_exactly_the_contract():
+    """The dynamic symbol table of the built library: its `iodine_` functions are _lib.EXPORTS, no more (a helper that left an anonymous
+    namespace for another host file must be hidden, not exported) and no less."""
+    import shutil
+    import subprocess
+    nm = shutil.which('nm')
+    if not nm:
+        pytest.skip('nm not installed')
+    _lib.lib()                                                  # (raises if the library has not been built)
+    out = subprocess.run([nm, '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] == 'T' and ln.split()[2].startswith('iodine_')}
+    assert exported == set(_lib.EXPORTS), exported ^ set(_lib.EXPORTS)

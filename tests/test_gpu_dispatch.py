@@ -1,5 +1,5 @@
 """Which kernels a setting selects: the launch counts of one training step per profile category (``seen:<category>`` of
-iodine_profile_read at profile 2), as formulas in the layer counts and T read off the launch sequence in iodine_api.cpp.  The parity
+iodine_profile_read at profile 2), as formulas in the layer counts and T read off the launch sequences in iodine_dispatch.cpp.  The parity
 tests say the numbers are right under every option; this one says the option reached the launch sites it is meant to reach."""
 import pytest
 
@@ -63,7 +63,7 @@ REF_CATEGORIES = ('refine_l0f', 'pixel_pass2', 'refine_l0', 'refine_conv', 'refi
 
 def expected_refine_launches(Dr, T, family, split=True, l0_fused=True, bwd_fused=True):
     """The refinement conv stack of one training step: T forward passes, one backward over all iterations as one batch.
-    family: 's2_f16' (tuned stride-2 kernels, split fp16) or 's2_f32' (the same kernels, exact fp32), see ref_family() in iodine_api.cpp;
+    family: 's2_f16' (tuned stride-2 kernels, split fp16) or 's2_f32' (the same kernels, exact fp32), see ref_family() in iodine_dispatch.cpp;
     split / l0_fused / bwd_fused: the options refine_split / refine_l0_fused / refine_bwd_fused.
     The fused forms exist in split fp16 only and need the split first layer; the shapes below allow both (64 channels, 64 pixels)."""
     l0f = family == 's2_f16' and split and l0_fused        # encoding + layer 0 in one kernel: no pixel_pass2, no refine_l0
