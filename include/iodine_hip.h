@@ -536,6 +536,53 @@ int iodine_slot_table(void* stream, const float* mask, const float* mean_or_null
 int iodine_seg_overlap(void* stream, const unsigned char* seg_a, const unsigned char* seg_b, int batch, int slots_a, int slots_b,
                        int pixels, int* table);
 
+/* Slots matched to ground-truth masks: the K slots are exchangeable, so a loss (or a metric) against G object masks needs a minimum-cost
+ * assignment of objects to slots per image.  Five stateless entries - no handle, no workspace, no synchronise - of which a training step
+ * uses three: a per-pixel pass (iodine_mask_overlap), a tiny pass (iodine_mask_match), a per-pixel pass (iodine_mask_match_backward).
+ *   mask (B,K,1,S,S) fp32 (device, as iodine_reconstruct / iodine_decode / a trajectory or frames entry returns it), gt (B,G,S,S) uint8
+ *   (device; a byte != 0 counts as 1), P = S * S.  Per image:
+ *     n_g = sum_p gt_gp (gt_area, int32, exact)    a_k = sum_p m_kp (mask_area)
+ *     I_gk = sum_p gt_gp m_kp (inter)              N_gk = -sum_p gt_gp logf(m_kp + eps) (nll; left out when nll_or_null is NULL)
+ *   A row with n_g = 0 is padding wherever it sits (the convention of iodine_ari_table's callers); R = the rows with n_g > 0.
+ *   Pair values, kind 0 = 'iou': 1 - I_gk / U_gk with U_gk = n_g + a_k - I_gk; kind 1 = 'ce': N_gk / n_g.
+ * Statistics: every term is an exact fp32 number (m + eps is one fp32 add, logf the accurate 1-ulp one) added in fp64 in a fixed order -
+ * per thread in pixel order, per wave in a fixed butterfly, across waves in index order - and rounded to fp32 once: inter and mask_area are
+ * within 2^-23 relative of the exact sums, and the same input gives the same bits on every call (no float atomics, no scratch buffer).
+ * Assignment: M = min(|R|, K); an injective map pi from exactly M rows of R to slots that minimises the sum of the pair values of
+ * match_kind; unmatched and padding rows read -1.  Among equal-cost optima the choice is unspecified but a fixed function of the input
+ * (shortest augmenting paths, potentials in fp64, the lowest column on a tie; csrc/assign.h).  Every loop of the solver is bounded by G and
+ * K alone; an image with a NaN or +-inf cost in a real row is refused before the search: its assign is all -1 and its total / loss NaN.
+ * Loss: loss[b] = (1 / M) sum over matched rows of the pair value of loss_kind (chosen independently of match_kind), 0 when M = 0; formed
+ * in fp64 from the fp32 statistics, rounded once.  Gradient, the assignment held constant, for k = pi(g):
+ *   'ce':  d loss_b / d m_kp = -gt_gp / (M n_g (m_kp + eps))         'iou': -(gt_gp U - I (1 - gt_gp)) / (M U^2)
+ * and exactly 0 for a slot that is no row's match.  coef (B,G,2) fp32 carries the per-row factors {on, off} between the two passes:
+ * 'ce' {-1 / (M n_g), 0}, 'iou' {-1 / (M U), I / (M U^2)}, zeros for an unmatched row.
+ *
+ * iodine_mask_overlap: one launch, each mask plane read once; outputs inter (B,G,K), nll_or_null (B,G,K), mask_area (B,K) fp32 and
+ *   gt_area (B,G) int32, all overwritten.  16-byte loads where P % 4 == 0 and mask / gt are 16- / 4-byte aligned, scalar loads otherwise.
+ * iodine_assign: any cost (B,G,K) fp32 on the device (hard IoU for the matched metrics, 1 - IoU of two segmentations to follow slots);
+ *   row_valid_or_null (B,G) uint8, NULL = every row is real; assign (B,G) int32, total (B) fp32 = sum of the matched costs (fp64, row order,
+ *   rounded once; 0 when no row is real).
+ * iodine_assign_host: one matrix on host pointers through the same function as the device kernel runs: the same bits.
+ * iodine_mask_match: statistics -> assign (B,G) int32, loss (B) fp32, coef (B,G,2) fp32, and optionally the pair values of match_kind
+ *   (cost_or_null) and I / U (iou_or_null), both (B,G,K) fp32 with 0 in padding rows.
+ * iodine_mask_match_backward: grad_loss (B) fp32 on the device = d L / d loss_b; grad_mask (B,K,1,S,S) fp32 is written completely, zeros
+ *   included.  assign is only compared against slot indices, never used as an index.
+ * IODINE_ERR_INVALID, before anything touches the device, with the entry's name in iodine_last_error(NULL): a NULL required pointer,
+ * batch < 1, slots / n_gt / n_rows / n_cols outside 1..16, size outside 1..1024, eps <= 0 (or NaN), a kind other than 0 / 1, kind 1
+ * without nll. */
+int iodine_mask_overlap(void* stream, const float* mask, const unsigned char* gt, int batch, int slots, int n_gt, int size, float eps,
+                        float* inter, float* nll_or_null, float* mask_area, int* gt_area);
+int iodine_assign(void* stream, const float* cost, const unsigned char* row_valid_or_null, int batch, int n_rows, int n_cols,
+                  int* assign, float* total);
+int iodine_assign_host(const float* cost, const unsigned char* row_valid_or_null, int n_rows, int n_cols, int* assign, float* total);
+int iodine_mask_match(void* stream, const float* inter, const float* nll_or_null, const float* mask_area, const int* gt_area, int batch,
+                      int slots, int n_gt, int match_kind, int loss_kind, int* assign, float* loss, float* coef, float* cost_or_null,
+                      float* iou_or_null);
+int iodine_mask_match_backward(void* stream, const float* mask, const unsigned char* gt, const int* assign, const float* coef,
+                               const float* grad_loss, int batch, int slots, int n_gt, int size, int loss_kind, float eps,
+                               float* grad_mask);
+
 /* Options: "stop_after_iters" (debug: run only the first v refinement iterations of reconstruct, no final decode),
  * "graph" (1: replay the fixed-shape launch sequence of reconstruct / decode / elbo / train_forward / train_backward through a
  * hipGraph per distinct argument tuple -- first call eager, second captured, later ones one hipGraphLaunch; needs a non-default

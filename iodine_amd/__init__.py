@@ -2,8 +2,9 @@
 ``IODINE.forward / reconstruct`` module API.  Heavy imports are lazy so that
 ``iodine_amd.synth`` can be used without the HIP library being built."""
 
-__all__ = ['IODINE', 'Predictive', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse',
-           'slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS', 'latent_kl', 'rank_dims', 'Traversal']
+__all__ = ['IODINE', 'Predictive', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse', 'matching',
+           'slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS', 'latent_kl', 'rank_dims', 'Traversal',
+           'pack_gt', 'overlap', 'assign', 'match_masks', 'matched_mask_loss', 'segmentation_scores', 'SegmentationEvaluator']
 
 
 def __getattr__(name):
@@ -19,4 +20,7 @@ def __getattr__(name):
     if name in ('latent_kl', 'rank_dims', 'Traversal'):      # (``iodine_amd.traverse`` is the module; the function is ``traverse.traverse``)
         from . import traverse
         return getattr(traverse, name)
+    if name in ('pack_gt', 'overlap', 'assign', 'match_masks', 'matched_mask_loss', 'segmentation_scores', 'SegmentationEvaluator'):
+        from . import matching
+        return getattr(matching, name)
     raise AttributeError(name)

@@ -40,6 +40,7 @@ EXPORTS = (
     'iodine_scene_edit',
     'iodine_op_pixel_encode',
     'iodine_predictive',
+    'iodine_mask_overlap', 'iodine_assign', 'iodine_assign_host', 'iodine_mask_match', 'iodine_mask_match_backward',
 )
 
 
@@ -171,6 +172,12 @@ def lib() -> C.CDLL:
         L.iodine_op_pixel_encode.argtypes = [vp] * 7 + [ci] * 4 + [cf, cf, ci, C.c_uint, ci, C.POINTER(vp)]
     if hasattr(L, 'iodine_predictive'):                 # (IODINE.predictive; absent from older A/B builds, which raise on it)
         L.iodine_predictive.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, ci] + [vp] * 7
+    if hasattr(L, 'iodine_mask_overlap'):               # (matched masks, iodine_amd.matching; absent from older A/B builds)
+        L.iodine_mask_overlap.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp]
+        L.iodine_assign.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
+        L.iodine_assign_host.argtypes = [vp, vp, ci, ci, vp, vp]
+        L.iodine_mask_match.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+        L.iodine_mask_match_backward.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

@@ -256,6 +256,16 @@ hipError_t launch_slot_table(hipStream_t st, const float* mask, const float* mea
                              unsigned char* seg);
 hipError_t launch_seg_overlap(hipStream_t st, const unsigned char* seg_a, const unsigned char* seg_b, int B, int Ka, int Kb, int P,
                               int* table);
+// kernels_match.hip: slots matched to ground-truth masks - statistics, assignment (assign.h), loss and its gradient (stateless)
+hipError_t launch_mask_overlap(hipStream_t st, const float* mask, const unsigned char* gt, int B, int K, int G, int S, float eps,
+                               float* inter, float* nll, float* mask_area, int* gt_area);
+hipError_t launch_assign(hipStream_t st, const float* cost, const unsigned char* row_valid, int B, int G, int K, int* assign,
+                         float* total);
+hipError_t launch_mask_match(hipStream_t st, const float* inter, const float* nll, const float* mask_area, const int* gt_area, int B,
+                             int K, int G, int match_kind, int loss_kind, int* assign, float* loss, float* coef, float* cost_out,
+                             float* iou_out);
+hipError_t launch_mask_match_bwd(hipStream_t st, const float* mask, const unsigned char* gt, const int* assign, const float* coef,
+                                 const float* grad_loss, int B, int K, int G, int S, int loss_kind, float eps, float* grad);
 hipError_t launch_pack_dec_out_gemm(hipStream_t st, const float* w, int C, float* meta, void* dst);
 hipError_t launch_pack_dec_out_dgrad(hipStream_t st, const float* w, int C, const float* meta, void* dst);
 hipError_t launch_dec_out_dgrad_f16x3(hipStream_t st, const float* g, const void* wpk, const float* wmeta, const float* aux,

@@ -1,6 +1,7 @@
 // Handle-free entry points of libiodine_hip.so: the optimizer and metric launches, the Philox sampler, the host linspace and the
 // operator-level test entry points (iodine_op_*).  See include/iodine_hip.h.
 #include "iodine_internal.h"
+#include "assign.h"
 
 extern "C" {
 
@@ -87,6 +88,77 @@ int iodine_seg_overlap(void* stream, const unsigned char* seg_a, const unsigned 
     }
     const hipError_t e = launch_seg_overlap((hipStream_t)stream, seg_a, seg_b, batch, slots_a, slots_b, pixels, table);
     if (e != hipSuccess) { g_create_error = std::string("iodine_seg_overlap: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_mask_overlap(void* stream, const float* mask, const unsigned char* gt, int batch, int slots, int n_gt, int size, float eps,
+                        float* inter, float* nll_or_null, float* mask_area, int* gt_area)
+{
+    if (!mask || !gt || !inter || !mask_area || !gt_area || batch < 1 || slots < 1 || slots > 16 || n_gt < 1 || n_gt > 16 || size < 1 ||
+        size > 1024 || !(eps > 0.f)) {
+        g_create_error = "iodine_mask_overlap: bad argument (mask, gt, inter, mask_area, gt_area required, batch >= 1, slots and n_gt in 1..16, "
+                         "size in 1..1024, eps > 0)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_mask_overlap((hipStream_t)stream, mask, gt, batch, slots, n_gt, size, eps, inter, nll_or_null, mask_area,
+                                             gt_area);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_mask_overlap: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_assign(void* stream, const float* cost, const unsigned char* row_valid_or_null, int batch, int n_rows, int n_cols,
+                  int* assign, float* total)
+{
+    if (!cost || !assign || !total || batch < 1 || n_rows < 1 || n_rows > 16 || n_cols < 1 || n_cols > 16) {
+        g_create_error = "iodine_assign: bad argument (cost, assign, total required, batch >= 1, n_rows and n_cols in 1..16)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_assign((hipStream_t)stream, cost, row_valid_or_null, batch, n_rows, n_cols, assign, total);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_assign: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_assign_host(const float* cost, const unsigned char* row_valid_or_null, int n_rows, int n_cols, int* assign, float* total)
+{
+    if (!cost || !assign || !total || n_rows < 1 || n_rows > 16 || n_cols < 1 || n_cols > 16) {
+        g_create_error = "iodine_assign_host: bad argument (cost, assign, total required, n_rows and n_cols in 1..16)";
+        return IODINE_ERR_INVALID;
+    }
+    IodAssignWork work;
+    iod_assign_solve(cost, row_valid_or_null, n_rows, n_cols, assign, total, &work);
+    return IODINE_OK;
+}
+
+int iodine_mask_match(void* stream, const float* inter, const float* nll_or_null, const float* mask_area, const int* gt_area, int batch,
+                      int slots, int n_gt, int match_kind, int loss_kind, int* assign, float* loss, float* coef, float* cost_or_null,
+                      float* iou_or_null)
+{
+    const bool kinds = (match_kind == 0 || match_kind == 1) && (loss_kind == 0 || loss_kind == 1);
+    if (!inter || !mask_area || !gt_area || !assign || !loss || !coef || batch < 1 || slots < 1 || slots > 16 || n_gt < 1 || n_gt > 16 ||
+        !kinds || ((match_kind == 1 || loss_kind == 1) && !nll_or_null)) {
+        g_create_error = "iodine_mask_match: bad argument (inter, mask_area, gt_area, assign, loss, coef required, batch >= 1, slots and n_gt in "
+                         "1..16, kinds 0 = iou / 1 = ce, and nll with either kind 1)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_mask_match((hipStream_t)stream, inter, nll_or_null, mask_area, gt_area, batch, slots, n_gt, match_kind,
+                                           loss_kind, assign, loss, coef, cost_or_null, iou_or_null);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_mask_match: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_mask_match_backward(void* stream, const float* mask, const unsigned char* gt, const int* assign, const float* coef,
+                               const float* grad_loss, int batch, int slots, int n_gt, int size, int loss_kind, float eps,
+                               float* grad_mask)
+{
+    if (!mask || !gt || !assign || !coef || !grad_loss || !grad_mask || batch < 1 || slots < 1 || slots > 16 || n_gt < 1 || n_gt > 16 ||
+        size < 1 || size > 1024 || (loss_kind != 0 && loss_kind != 1) || !(eps > 0.f)) {
+        g_create_error = "iodine_mask_match_backward: bad argument (six pointers required, batch >= 1, slots and n_gt in 1..16, size in 1..1024, "
+                         "loss_kind 0 = iou / 1 = ce, eps > 0)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_mask_match_bwd((hipStream_t)stream, mask, gt, assign, coef, grad_loss, batch, slots, n_gt, size, loss_kind,
+                                               eps, grad_mask);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_mask_match_backward: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
     return IODINE_OK;
 }
 

@@ -198,7 +198,8 @@ def beta_warmup(step, beta, warmup_steps):
 
 
 def train(model, optimizer, dataloader, device, max_steps, print_every=10, checkpoint_path=None, log=print, max_grad_norm=None,
-          beta=None, beta_warmup_steps=0, bptt=None, ignore_border=0, log_sigma=None, input_gain=None):
+          beta=None, beta_warmup_steps=0, bptt=None, ignore_border=0, log_sigma=None, input_gain=None,
+          mask_loss=0.0, mask_loss_kind='ce', mask_match='iou'):
     """train.py:44-108: loss = model(data); loss.mean(); zero_grad; backward; [all-reduce]; [clip]; step.  Returns the losses.
     ``max_grad_norm``: the global gradient norm is clipped at this value (train.py:64, commented out in the reference; the paper
     uses 5.0) AFTER the all-reduce, so every rank clips the same averaged gradient with the same coefficient - what
@@ -220,9 +221,22 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
     ``input_gain``: a learned front end (``--learn-input-gain``, ``InputGain``) whose parameters sit in a param group of ``optimizer``: the
     batch goes through it before the model, so ``loss.backward()`` reaches its parameters through ``x.grad`` - the gradient the model returns
     for an image that requires grad.  Its gradients join the all-reduce and the clipped global norm; the checkpoint gains the entry
-    ``input_gain`` (its ``state_dict``).  Not combined with ``bptt``."""
+    ``input_gain`` (its ``state_dict``).  Not combined with ``bptt``.
+    ``mask_loss`` = w > 0: supervised masks.  A step is ``model(x, attach_state=True)`` plus ``w * matched_mask_loss(model.mask,
+    pack_gt(data[1]), loss=mask_loss_kind, match=mask_match)`` (``iodine_amd.matching``: ground-truth objects assigned to slots on the device,
+    three launches, no synchronise) and one ``backward()``; the log line gains ``mask-loss``.  A batch whose masks are all ``None`` / empty
+    trains unsupervised - the semi-supervised case.  Not combined with ``bptt``.  With 0 (default) no launch, copy or attribute is added."""
     if input_gain is not None and bptt is not None:
         raise ValueError('train: input_gain is not combined with bptt (clip_backward differentiates its chunks itself)')
+    mask_loss = float(mask_loss)
+    if mask_loss < 0.0 or mask_loss != mask_loss:
+        raise ValueError(f'train: mask_loss must be >= 0; got {mask_loss!r}')
+    if mask_loss > 0.0:
+        if bptt is not None:
+            raise ValueError('train: mask_loss is not combined with bptt (clip_backward differentiates its chunks itself; use its frame_loss)')
+        from . import matching
+        matching._kind(mask_loss_kind, 'train: mask_loss_kind'), matching._kind(mask_match, 'train: mask_match')
+    mask_term = None
     extra_params = ([log_sigma] if log_sigma is not None else []) + (list(input_gain.parameters()) if input_gain is not None else [])
     model.train()
     fused_clip = isinstance(optimizer, FusedAdam)
@@ -251,10 +265,18 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
             if bptt is not None:
                 optimizer.zero_grad()
                 loss, _ = clip_backward(model, x, bptt=bptt, weights=w)
+            elif mask_loss > 0.0 and _has_masks(data):
+                loss = (model(x, attach_state=True) if w is None else model(x, weights=w, attach_state=True)).mean()
+                gt = matching.pack_gt(data[1], x.shape[-1], device)
+                mask_term = matching.matched_mask_loss(model.mask, gt, loss=mask_loss_kind, match=mask_match)
+                optimizer.zero_grad()
+                (loss + mask_loss * mask_term).backward()
+                mask_term = mask_term.detach()
             else:
                 loss = (model(x) if w is None else model(x, weights=w)).mean()
                 optimizer.zero_grad()
                 loss.backward()
+                mask_term = None
             if world > 1:
                 parallel.allreduce_gradients(list(model.parameters()) + extra_params)   # replaces DataParallel's reduce
             if clipping and not fused_clip:
@@ -265,10 +287,11 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
             losses.append(loss.item())
             step += 1
             if step % print_every == 0:
-                log('iter: {}, loss: {:.4f}, batch-time: {:.4f}s, lr: {}{}{}'.format(
+                log('iter: {}, loss: {:.4f}, batch-time: {:.4f}s, lr: {}{}{}{}'.format(
                     step, losses[-1], time.perf_counter() - start, optimizer.param_groups[0]['lr'],
                     ', grad-norm: {:.4f}'.format(grad_norm.item()) if clipping else '',
-                    ', sigma: {:.5f}'.format(log_sigma.detach().exp().item()) if log_sigma is not None else ''))
+                    ', sigma: {:.5f}'.format(log_sigma.detach().exp().item()) if log_sigma is not None else '',
+                    ', mask-loss: {:.4f}'.format(mask_term.item() if mask_term is not None else 0.0) if mask_loss > 0.0 else ''))
             if step >= max_steps:
                 break
     if beta is not None:
@@ -282,6 +305,15 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
     if checkpoint_path and (not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0):
         save_checkpoint(checkpoint_path, model, optimizer, epoch=0, iteration=step, **extra)
     return losses
+
+
+def _has_masks(data):
+    """whether a batch (image, masks) carries at least one ground-truth mask"""
+    if len(data) < 2 or data[1] is None:
+        return False
+    if torch.is_tensor(data[1]):
+        return data[1].numel() > 0
+    return any(m is not None and len(m) > 0 for m in data[1])
 
 
 def add_sigma_group(optimizer, log_sigma, lr):
@@ -371,7 +403,9 @@ def _evaluate(model, dataloader, device, evaluator, bound_samples=0):
             if bound_samples:
                 out = model.predictive(image.to(device), samples=bound_samples)
                 bounds.extend(zip(out.iwae.tolist(), out.elbo_mc.tolist()))
-    del evaluator.aris[mine:]
+    lists = tuple(getattr(evaluator, 'per_image', ('aris',)))                # every per-image list the evaluator declares
+    for name in lists:
+        del getattr(evaluator, name)[mine:]
     if bound_samples:
         del bounds[mine:]
         tot = torch.tensor([sum(q[0] for q in bounds), sum(q[1] for q in bounds), float(len(bounds))], dtype=torch.float64,
@@ -385,6 +419,13 @@ def _evaluate(model, dataloader, device, evaluator, bound_samples=0):
     if world > 1:
         torch.distributed.all_reduce(stats)
     evaluator.global_mean = float(stats[0] / stats[1]) if float(stats[1]) > 0 else 0.0
+    if lists != ('aris',):                                                   # means of the other lists over all ranks; NaN = no score
+        kept = [[v for v in getattr(evaluator, name) if v == v] for name in lists]
+        more = torch.tensor([[float(sum(v)), float(len(v))] for v in kept], dtype=torch.float64, device=stats.device)
+        if world > 1:
+            torch.distributed.all_reduce(more)
+        evaluator.global_means = {name: (float(s / c) if float(c) > 0 else 0.0) for name, (s, c) in zip(lists, more)}
+        evaluator.global_means['aris'] = evaluator.global_mean
     return evaluator
 
 
@@ -451,6 +492,13 @@ def make_parser():
     ap.add_argument('--eval-samples', type=int, default=0, metavar='S',
                     help='also report the S-sample importance-weighted bound (IWAE) and the S-sample Monte-Carlo ELBO of the evaluation set, '
                          'per image in nats (one model.predictive call per batch; 0: off)')
+    ap.add_argument('--mask-loss', type=float, default=0.0, metavar='W',
+                    help='supervised masks: add W * matched_mask_loss(model.mask, ground truth) to every step whose batch carries masks '
+                         '(ground-truth objects assigned to slots on the device; 0: off)')
+    ap.add_argument('--mask-loss-kind', choices=['ce', 'iou'], default='ce', help='with --mask-loss: the loss of a matched (object, slot) pair')
+    ap.add_argument('--mask-match', choices=['iou', 'ce'], default='iou', help='with --mask-loss: the cost the assignment minimises')
+    ap.add_argument('--metrics', action='store_true',
+                    help='evaluate with SegmentationEvaluator: matched mIoU, segmentation covering (SC) and mSC beside the ARI')
     ap.add_argument('--traverse', metavar='OUT.npz',
                     help='instead of training: after loading (--resume), reconstruct the first batch, traverse the latent units of image 0 '
                          '(each slot, the units with the largest KL, moved along the posterior) and save the grids; see save_traversal')
@@ -507,8 +555,10 @@ def main(argv=None):
             save_traversal(model, image.to(device), args.traverse, args.traverse_top, args.traverse_values)
         return
     train_ds = ds
+    if args.clip_frames and args.mask_loss:
+        raise SystemExit('--mask-loss trains on still images; it cannot be combined with --clip-frames')
     if args.clip_frames:
-        clip_chunks(args.clip_frames, arch.ITERS)                            # (refuse a frame count that does not split before any work)
+        clip_chunks(args.clip_frames, arch.ITERS)                           # (refuse a frame count that does not split before any work)
         if args.clevr or args.dsprites:
             raise SystemExit('--clip-frames trains on synthetic clips; it cannot be combined with --clevr / --dsprites')
         train_ds = SyntheticClips(args.batch * world * 8, arch.IMG_SIZE, args.clip_frames)
@@ -516,10 +566,17 @@ def main(argv=None):
     losses = train(model, optimizer, dl, device, args.steps, checkpoint_path=args.save,
                    log=print if rank == 0 else (lambda *a: None), beta=args.beta, beta_warmup_steps=args.beta_warmup,
                    bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border, log_sigma=log_sigma,
-                   input_gain=input_gain)
-    ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, bound_samples=args.eval_samples)
+                   input_gain=input_gain, mask_loss=args.mask_loss, mask_loss_kind=args.mask_loss_kind, mask_match=args.mask_match)
+    evaluator = None
+    if args.metrics:
+        from .matching import SegmentationEvaluator
+        evaluator = SegmentationEvaluator()
+    ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
+                  bound_samples=args.eval_samples)
     if rank == 0:
         print('first loss {:.2f} -> last loss {:.2f}; Ari over all ranks: {}'.format(losses[0], losses[-1], ev.global_mean))
+        if args.metrics:
+            print('mIoU {:.4f}, SC {:.4f}, mSC {:.4f} over all ranks'.format(*[ev.global_means[n] for n in ('mious', 'scs', 'mscs')]))
         if args.eval_samples:
             print('{}-sample bounds per image: IWAE {:.3f}, Monte-Carlo ELBO {:.3f}'.format(args.eval_samples, ev.iwae, ev.elbo_mc))
 

@@ -4,7 +4,8 @@
 ``mean (*, K, 3, S, S)`` - into one row of ``SLOT_COLUMNS`` per slot and, on request, the argmax segmentation map, in one launch of
 ``iodine_slot_table``.  ``overlap_table`` counts the co-occurrences of two such maps (``iodine_seg_overlap``): the contingency table
 ``ari.compute_ari`` takes, between two runs or two frames instead of against ground truth; ``slot_iou`` is the intersection over union
-that follows from its row and column sums.  The kernels are stateless and need no model; like ``ari.ari_tables`` there is no CPU path.
+that follows from its row and column sums, and ``matching.assign(1 - slot_iou(overlap_table(a, b, K, K)).float())`` (on the device) is the
+slot permutation between the two segmentations - what following the slots from frame to frame needs.  The kernels are stateless and need no model; like ``ari.ari_tables`` there is no CPU path.
 """
 from __future__ import annotations
 
