@@ -583,6 +583,37 @@ int iodine_mask_match_backward(void* stream, const float* mask, const unsigned c
                                const float* grad_loss, int batch, int slots, int n_gt, int size, int loss_kind, float eps,
                                float* grad_mask);
 
+/* Device-resident datasets (iodine_amd/resident.py): the whole data set sits in device memory and a batch is assembled there.  Two stateless
+ * entries - no handle, no workspace, one launch, no synchronise.
+ *
+ * iodine_batch_gather: item j of the batch is store entry index[j]; index (count) int64 in device memory.  A frame of a clip is an entry:
+ *   the caller resolves (clip n, frame f) to n F + f, so count = B F for a batch of clips.
+ *   images, image_kind 0: uint8 (N,S,S,3), HWC as decoded;  x[j][c][p] = (float)u / 255.f with an IEEE division - the bits of ToTensor's
+ *                         .float().div_(255.0);
+ *           image_kind 1: float32 (N,3,S,S); copied.
+ *   masks_or_null uint16 (N,S,S): bit g of a word is set where the pixel lies inside ground-truth mask g (overlapping masks are exact).
+ *   x (count,3,S,S) fp32 and gt_or_null (count,planes,S,S) uint8 0/1 are written completely: gt[j][g][p] = bit g of the word, which is 0 for
+ *   g at or beyond the image's number of masks - the layout iodine_mask_overlap and iodine_ari_table take.  gt is left alone when either
+ *   of masks_or_null / gt_or_null is NULL.
+ *   Where S * S % 4 == 0 and the pointers are aligned for it (x 16, images 4 / 16, masks 8, gt 4 bytes) a thread takes four consecutive
+ *   pixels, with 16-byte stores per channel plane and 4-byte stores per mask plane; element-wise otherwise.  Traffic per pixel: 3 (kind 1:
+ *   12) + 2 bytes read, 12 + planes written.  Offsets are 64-bit throughout.
+ *   THE INDICES ARE NOT CHECKED ON THE DEVICE: the caller validates them against [0, N) on the host before the launch.
+ *
+ * iodine_synth_scenes: the deterministic test scenes of iodine_amd/synth.py (make_images) generated in device memory, bit for bit: splitmix64
+ *   hashing in 64-bit integers, object parameters and the inside test in fp64 without contraction, painter's order (the last object wins a
+ *   pixel), colours rounded to fp32 once.  Item i draws from uniform01(seed + i seed_step, stream + i stream_step).  kind 0 = 'uniform'
+ *   (every element a uniform; masks_or_null / n_gt_or_null are not touched), 1 = 'blobs' (grey background, 3..max_objects discs / squares).
+ *   frames = 0: images (n,3,S,S), masks_or_null (n,S,S) uint16 - bit o where object o owns the pixel -, n_gt_or_null (n) uint8 = the
+ *   number of objects.  frames = F >= 1: images (n,F,3,S,S), masks (n,F,S,S); frame f is the scene rolled by (f, 2 f) pixels (rows, columns).
+ * IODINE_ERR_INVALID, before anything touches the device, with the entry's name in iodine_last_error(NULL): a NULL required pointer,
+ * count / n < 1, size outside 1..4096 (synth: 1..1024), planes / max_objects outside 1..16, a kind other than 0 / 1, frames < 0. */
+int iodine_batch_gather(void* stream, const long long* index, int count, const void* images, int image_kind,
+                        const unsigned short* masks_or_null, int size, int planes, float* x, unsigned char* gt_or_null);
+int iodine_synth_scenes(void* stream, int n, int size, unsigned long long seed, unsigned long long seed_step, unsigned long long stream_id,
+                        unsigned long long stream_step, int kind, int max_objects, int frames, float* images,
+                        unsigned short* masks_or_null, unsigned char* n_gt_or_null);
+
 /* Options: "stop_after_iters" (debug: run only the first v refinement iterations of reconstruct, no final decode),
  * "graph" (1: replay the fixed-shape launch sequence of reconstruct / decode / elbo / train_forward / train_backward through a
  * hipGraph per distinct argument tuple -- first call eager, second captured, later ones one hipGraphLaunch; needs a non-default

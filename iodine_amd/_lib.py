@@ -41,6 +41,7 @@ EXPORTS = (
     'iodine_op_pixel_encode',
     'iodine_predictive',
     'iodine_mask_overlap', 'iodine_assign', 'iodine_assign_host', 'iodine_mask_match', 'iodine_mask_match_backward',
+    'iodine_batch_gather', 'iodine_synth_scenes',
 )
 
 
@@ -178,6 +179,9 @@ def lib() -> C.CDLL:
         L.iodine_assign_host.argtypes = [vp, vp, ci, ci, vp, vp]
         L.iodine_mask_match.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
         L.iodine_mask_match_backward.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp]
+    if hasattr(L, 'iodine_batch_gather'):               # (device-resident datasets, iodine_amd.resident; absent from older A/B builds)
+        L.iodine_batch_gather.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp, vp]
+        L.iodine_synth_scenes.argtypes = [vp, ci, ci] + [C.c_ulonglong] * 4 + [ci, ci, ci, vp, vp, vp]
     if L.iodine_abi_version() != 3:
         raise RuntimeError('libiodine_hip.so ABI version mismatch')
     _lib = L

@@ -259,6 +259,12 @@ hipError_t launch_seg_overlap(hipStream_t st, const unsigned char* seg_a, const 
 // kernels_match.hip: slots matched to ground-truth masks - statistics, assignment (assign.h), loss and its gradient (stateless)
 hipError_t launch_mask_overlap(hipStream_t st, const float* mask, const unsigned char* gt, int B, int K, int G, int S, float eps,
                                float* inter, float* nll, float* mask_area, int* gt_area);
+// kernels_batch.hip: device-resident datasets - a batch gathered from the store, synth.make_images on the device (stateless)
+hipError_t launch_batch_gather(hipStream_t st, const long long* index, int count, const void* images, int kind, const unsigned short* masks,
+                               int S, int planes, float* x, unsigned char* gt);
+hipError_t launch_synth_scenes(hipStream_t st, int n, int S, unsigned long long seed, unsigned long long seed_step, unsigned long long stream,
+                               unsigned long long stream_step, int kind, int max_objects, int frames, float* images, unsigned short* masks,
+                               unsigned char* n_gt);
 hipError_t launch_assign(hipStream_t st, const float* cost, const unsigned char* row_valid, int B, int G, int K, int* assign,
                          float* total);
 hipError_t launch_mask_match(hipStream_t st, const float* inter, const float* nll, const float* mask_area, const int* gt_area, int B,

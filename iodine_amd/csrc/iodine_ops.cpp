@@ -162,6 +162,35 @@ int iodine_mask_match_backward(void* stream, const float* mask, const unsigned c
     return IODINE_OK;
 }
 
+int iodine_batch_gather(void* stream, const long long* index, int count, const void* images, int image_kind,
+                        const unsigned short* masks_or_null, int size, int planes, float* x, unsigned char* gt_or_null)
+{
+    if (!index || !images || !x || count < 1 || size < 1 || size > 4096 || planes < 1 || planes > 16 || (image_kind != 0 && image_kind != 1)) {
+        g_create_error = "iodine_batch_gather: bad argument (index, images, x required, count >= 1, size in 1..4096, planes in 1..16, "
+                         "image_kind 0 = uint8 HWC / 1 = float32 CHW)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_batch_gather((hipStream_t)stream, index, count, images, image_kind, masks_or_null, size, planes, x, gt_or_null);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_batch_gather: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
+int iodine_synth_scenes(void* stream, int n, int size, unsigned long long seed, unsigned long long seed_step, unsigned long long stream_id,
+                        unsigned long long stream_step, int kind, int max_objects, int frames, float* images,
+                        unsigned short* masks_or_null, unsigned char* n_gt_or_null)
+{
+    if (!images || n < 1 || size < 1 || size > 1024 || (kind != 0 && kind != 1) || max_objects < 1 || max_objects > 16 || frames < 0 ||
+        (long long)n * (frames > 0 ? frames : 1) > 0x7FFFFFFFll) {
+        g_create_error = "iodine_synth_scenes: bad argument (images required, n >= 1, size in 1..1024, kind 0 = uniform / 1 = blobs, "
+                         "max_objects in 1..16, frames >= 0, n * frames < 2^31)";
+        return IODINE_ERR_INVALID;
+    }
+    const hipError_t e = launch_synth_scenes((hipStream_t)stream, n, size, seed, seed_step, stream_id, stream_step, kind, max_objects, frames,
+                                             images, masks_or_null, n_gt_or_null);
+    if (e != hipSuccess) { g_create_error = std::string("iodine_synth_scenes: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
+    return IODINE_OK;
+}
+
 int iodine_randn(void* stream, float* out, long long n, unsigned long long seed, unsigned long long stream_id)
 {
     if (!out || n < 1) { g_create_error = "iodine_randn: bad argument"; return IODINE_ERR_INVALID; }

@@ -201,6 +201,9 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
           beta=None, beta_warmup_steps=0, bptt=None, ignore_border=0, log_sigma=None, input_gain=None,
           mask_loss=0.0, mask_loss_kind='ce', mask_match='iou'):
     """train.py:44-108: loss = model(data); loss.mean(); zero_grad; backward; [all-reduce]; [clip]; step.  Returns the losses.
+    ``dataloader``: a ``DataLoader`` (``make_dataloader``) or ``ResidentDataset.batches(...)`` (``iodine_amd.resident``), whose batches
+    ``(x, gt, n_gt)`` are already on the device - ``gt`` packed ``(B, G, S, S)``, which ``pack_gt`` passes through - and whose epoch is set
+    like a ``DistributedSampler``'s.
     ``max_grad_norm``: the global gradient norm is clipped at this value (train.py:64, commented out in the reference; the paper
     uses 5.0) AFTER the all-reduce, so every rank clips the same averaged gradient with the same coefficient - what
     ``clip_grad_norm_`` after DataParallel's reduce would do - and the replicas stay bitwise identical.  A ``FusedAdam`` takes it
@@ -398,8 +401,12 @@ def _evaluate(model, dataloader, device, evaluator, bound_samples=0):
     n_total = len(dataloader.dataset)
     mine = len(range(rank, n_total, world)) if world > 1 else n_total       # un-padded share of this rank (sampler stride = world)
     with torch.no_grad():
-        for image, masks in dataloader:
-            evaluator.evaluate(model, (image.to(device), [m.numpy() for m in masks]))
+        for data in dataloader:
+            image, masks = data[0], data[1]
+            if torch.is_tensor(masks):                                       # a ResidentDataset batch: packed on the device, with counts
+                evaluator.evaluate(model, (image.to(device), masks, data[2]))
+            else:
+                evaluator.evaluate(model, (image.to(device), [m.numpy() for m in masks]))
             if bound_samples:
                 out = model.predictive(image.to(device), samples=bound_samples)
                 bounds.extend(zip(out.iwae.tolist(), out.elbo_mc.tolist()))
@@ -499,6 +506,11 @@ def make_parser():
     ap.add_argument('--mask-match', choices=['iou', 'ce'], default='iou', help='with --mask-loss: the cost the assignment minimises')
     ap.add_argument('--metrics', action='store_true',
                     help='evaluate with SegmentationEvaluator: matched mIoU, segmentation covering (SC) and mSC beside the ARI')
+    ap.add_argument('--resident', nargs='?', const='', default=None, metavar='CACHE.npz',
+                    help='keep the data set in device memory and assemble every batch there (iodine_amd.resident): --clevr / --dsprites are '
+                         'ingested once - and written to CACHE.npz, or loaded from it when it exists -, without a data set the synthetic scenes '
+                         '(or, with --clip-frames, clips) are generated on the device; training and evaluation then run without host work '
+                         'per batch')
     ap.add_argument('--traverse', metavar='OUT.npz',
                     help='instead of training: after loading (--resume), reconstruct the first batch, traverse the latent units of image 0 '
                          '(each slot, the units with the largest KL, moved along the posterior) and save the grids; see save_traversal')
@@ -549,6 +561,8 @@ def main(argv=None):
         ds = MultiDSprites(args.dsprites)
     else:
         ds = SyntheticScenes(args.batch * world * 8, arch.IMG_SIZE)
+    if args.resident is not None and not args.traverse:
+        return _main_resident(args, arch, model, optimizer, ds, device, rank, world, log_sigma, input_gain)
     if args.traverse:
         image = next(iter(make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world)))[0]
         if rank == 0:
@@ -573,6 +587,54 @@ def main(argv=None):
         evaluator = SegmentationEvaluator()
     ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
                   bound_samples=args.eval_samples)
+    _report(args, rank, losses, ev)
+
+
+def _resident_store(args, arch, ds, device, rank, frames=0):
+    """the store of ``--resident``: the data set ingested (or its cache loaded), or the synthetic scenes / clips generated on the device"""
+    from .resident import ResidentDataset
+    log = print if rank == 0 else (lambda *a: None)
+    if not (args.clevr or args.dsprites):
+        return ResidentDataset.synthetic(len(ds), arch.IMG_SIZE, frames=frames, device=device)
+    cache = args.resident or None
+    if cache and os.path.exists(cache):
+        log(f'resident: loading {cache}')
+        return ResidentDataset.load(cache, device)
+    store = ResidentDataset.from_dataset(ds, device, log=log)                # (no workers: this process has the device open by now)
+    if cache and rank == 0:
+        store.save(cache)
+        log(f'resident: wrote {cache}')
+    return store
+
+
+def _main_resident(args, arch, model, optimizer, ds, device, rank, world, log_sigma, input_gain):
+    """``main`` from a device-resident store: the same training and evaluation calls, batches from ``ResidentDataset.batches``"""
+    if args.clip_frames and args.mask_loss:
+        raise SystemExit('--mask-loss trains on still images; it cannot be combined with --clip-frames')
+    if args.clip_frames:
+        clip_chunks(args.clip_frames, arch.ITERS)
+        if args.clevr or args.dsprites:
+            raise SystemExit('--clip-frames trains on synthetic clips; it cannot be combined with --clevr / --dsprites')
+    store = _resident_store(args, arch, ds, device, rank)
+    train_store = _resident_store(args, arch, ds, device, rank, frames=args.clip_frames) if args.clip_frames else store
+    if rank == 0:
+        print('resident: {} items of {} x {}, {} images, {:.1f} MiB on {}'.format(len(store), store.size, store.size,
+              'uint8' if store.image_kind == 0 else 'float32', (store.nbytes() + (train_store.nbytes() if train_store is not store else 0)) / 2 ** 20, device))
+    losses = train(model, optimizer, train_store.batches(args.batch, shuffle=True, rank=rank, world_size=world), device, args.steps,
+                   checkpoint_path=args.save, log=print if rank == 0 else (lambda *a: None), beta=args.beta,
+                   beta_warmup_steps=args.beta_warmup, bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border,
+                   log_sigma=log_sigma, input_gain=input_gain, mask_loss=args.mask_loss, mask_loss_kind=args.mask_loss_kind,
+                   mask_match=args.mask_match)
+    evaluator = None
+    if args.metrics:
+        from .matching import SegmentationEvaluator
+        evaluator = SegmentationEvaluator()
+    ev = evaluate(model, store.batches(args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
+                  bound_samples=args.eval_samples)
+    _report(args, rank, losses, ev)
+
+
+def _report(args, rank, losses, ev):
     if rank == 0:
         print('first loss {:.2f} -> last loss {:.2f}; Ari over all ranks: {}'.format(losses[0], losses[-1], ev.global_mean))
         if args.metrics:

@@ -294,12 +294,12 @@ class SegmentationEvaluator:
         self.reset()
 
     def evaluate(self, model, data):
-        from .ari import ari_tables
-        image, gt_masks = data
+        from .ari import ari_tables, gt_counts
+        image, gt_masks = data[0], data[1]
         pred, pred_mask, mean = model.reconstruct(image)
         tables = ari_tables(pred_mask, gt_masks)
-        for b, m in enumerate(gt_masks):
-            self.aris.append(compute_ari(tables[b, :m.shape[0]]))
+        for b, n in enumerate(gt_counts(data)):
+            self.aris.append(compute_ari(tables[b, :n]))
         hard = slot_table(pred_mask)[..., SLOT_COLUMNS.index('hard_area')].cpu()
         s = scores_from_tables(tables, hard, pred_mask.device)
         self.mious.extend(s.miou.tolist()); self.scs.extend(s.sc.tolist()); self.mscs.extend(s.msc.tolist())
