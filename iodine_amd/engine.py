@@ -13,7 +13,7 @@ import time
 
 import torch
 
-from . import parallel, synth
+from . import _args, parallel, synth
 from .ari import ARIEvaluator
 from .checkpoint import load_checkpoint, save_checkpoint
 from .optim import FusedAdam, _check_max_norm, clip_grad_norm_, make_optimizer
@@ -118,11 +118,11 @@ def clip_backward(model, clip, eps=None, bptt='truncated', weights=None, frame_l
         raise ValueError(f"clip_backward: bptt must be 'truncated' or 'exact'; got {bptt!r}")
     if clip.dim() != 5:
         raise ValueError(f'clip_backward: expected a clip (B, F, 3, S, S); got {tuple(clip.shape)}')
-    K, T = model._run_shape()
+    K, T = _args.run_shape(model.K, model.n_iters)
     chunks = clip_chunks(clip.shape[1], T)
     B, F = clip.shape[0], clip.shape[1]
     saved = model.iter_weights
-    w = model._read_objective(T)[2] or tuple((i + 1) / (T + 1) for i in range(T + 1))
+    w = _args.read_objective(model.sigma, model.beta, model.iter_weights, T)[2] or tuple((i + 1) / (T + 1) for i in range(T + 1))
     later = (0.0,) + tuple(w[1:])
     if len(chunks) > 1 and not any(torch.tensor(later, dtype=torch.float32).tolist()):
         raise ValueError(f'clip_backward: model.iter_weights = {saved!r} puts all weight on evaluation 0, which chunks after the first do not '

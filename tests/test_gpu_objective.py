@@ -13,7 +13,7 @@ import functools
 import pytest
 import torch
 
-from iodine_amd import _lib
+from iodine_amd import _args, _lib
 from oracle import iodine_oracle as O
 from util import grad_views, make_hip_model, rel_err, rel_l2
 
@@ -346,7 +346,7 @@ def test_graph_mode_keys_on_the_objective():
 
 
 # ---- 10. shape change ---------------------------------------------------------------------------------------------------------------
-def test_explicit_weights_do_not_follow_n_iters_but_names_do():
+def test_explicit_weights_do_not_follow_n_iters_but_names_do(monkeypatch):
     params, x, _ = _inputs('tiny')
     m = make_hip_model(BASE, params)
     m.iter_weights = [1.0, 1.0, 1.0]
@@ -360,10 +360,10 @@ def test_explicit_weights_do_not_follow_n_iters_but_names_do():
     wl = (_lib.C.c_double * 3)(1.0, 1.0, 1.0)
     _lib.check(_lib.lib().iodine_set_objective(m._handle, 0.1, 1.0, wl, 3), m._handle)
     m._objective, m.iter_weights = None, 'uniform'
-    m._read_objective = lambda T, _f=m._read_objective: (_f(T)[0], _f(T)[1], (1.0, 1.0, 1.0))
+    monkeypatch.setattr(_args, 'read_objective', lambda *a, _f=_args.read_objective: (*_f(*a)[:2], (1.0, 1.0, 1.0)))
     with pytest.raises(RuntimeError, match=r'3 iteration weights.*4 ELBO'):
         m(x.to(DEV), eps3.to(DEV))
-    del m._read_objective
+    monkeypatch.undo()
     m._objective = None
     p64 = {k: v.double() for k, v in params.items()}
     a3 = dataclasses.replace(BASE, iters=3)

@@ -8,7 +8,7 @@ import re
 import pytest
 import torch
 
-from iodine_amd import IODINE, _lib, engine
+from iodine_amd import IODINE, _args, _lib, engine
 from oracle import iodine_oracle as O
 from util import hip_arch, rel_l2
 
@@ -152,16 +152,16 @@ def test_module_defaults_and_detached_helpers():
     S = ARCH.img_size
     x = torch.rand(B, 3, S, S, requires_grad=True)
     w = torch.rand(B, 1, S, S, requires_grad=True)
-    wc = m._check_weights(w, x, 'forward')
+    wc = _args.check_weights(w, x, S, 'forward')
     assert not wc.requires_grad and wc.dtype == torch.float32 and wc.shape == (B, S, S)          # the helper keeps returning data
-    assert not m._check_x(x).requires_grad
-    xi, wi = m._grad_inputs(x, w, m._check_x(x), wc)
+    assert not _args.check_x(x, 3, S).requires_grad
+    xi, wi = m._grad_inputs(x, w, _args.check_x(x, 3, S), wc)
     assert xi is x and wi is w                                              # the node takes the caller's tensors ...
     with torch.no_grad():
-        xi, wi = m._grad_inputs(x, w, m._check_x(x), wc)
+        xi, wi = m._grad_inputs(x, w, _args.check_x(x, 3, S), wc)
         assert xi is not x and wi is wc                                     # ... under grad mode only
     mask = torch.ones(B, S, S, dtype=torch.bool)
-    assert m._grad_inputs(x.detach(), mask, x.detach(), m._check_weights(mask, x, 'forward'))[1].dtype == torch.float32
+    assert m._grad_inputs(x.detach(), mask, x.detach(), _args.check_weights(mask, x, S, 'forward'))[1].dtype == torch.float32
     assert 'receives ``d loss / d w``; otherwise weights are data' in __import__('iodine_amd.model').model.__doc__
 
 

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from iodine_amd import IODINE, _lib
+from iodine_amd import IODINE, _args, _lib
 from iodine_amd.model import arch_namespace
 from oracle import iodine_oracle as O
 from util import rel_err, rel_l2
@@ -136,26 +136,30 @@ def test_bad_iter_weights_are_refused_on_the_host(value, match):
     _refused(m, match)
 
 
+def _objective(m, T):
+    return _args.read_objective(m.sigma, m.beta, m.iter_weights, T)
+
+
 def test_valid_objectives_pass_the_host_checks():
     m = _module(T=2)
     assert m.beta == 1.0 and m.iter_weights is None and m.sigma == 0.10
-    assert m._read_objective(2) == (0.10, 1.0, ())
+    assert _objective(m, 2) == (0.10, 1.0, ())
     m.sigma, m.beta, m.iter_weights = 0.3, 0, 'uniform'
-    assert m._read_objective(2) == (0.3, 0.0, (1 / 3,) * 3) and m._read_objective(4)[2] == (0.2,) * 5      # names follow n_iters
+    assert _objective(m, 2) == (0.3, 0.0, (1 / 3,) * 3) and _objective(m, 4)[2] == (0.2,) * 5      # names follow n_iters
     m.iter_weights = 'last'
-    assert m._read_objective(3)[2] == (0.0, 0.0, 0.0, 1.0)
+    assert _objective(m, 3)[2] == (0.0, 0.0, 0.0, 1.0)
     m.iter_weights = torch.tensor([0.0, 0.5, 1.0])
-    assert m._read_objective(2)[2] == (0.0, 0.5, 1.0)
+    assert _objective(m, 2)[2] == (0.0, 0.5, 1.0)
     m.iter_weights = 'linspace'
-    assert m._read_objective(2)[2] == ()
+    assert _objective(m, 2)[2] == ()
     # what a schedule produces: numpy scalars and one-element tensors are numbers too
     m.sigma, m.beta = np.float32(0.5), torch.tensor(2.0)
-    assert m._read_objective(2)[:2] == (0.5, 2.0)
+    assert _objective(m, 2)[:2] == (0.5, 2.0)
     m.sigma, m.beta, m.iter_weights = np.float64(0.3), np.int64(1), np.array([0.0, 0.5, 1.0], dtype=np.float32)
-    assert m._read_objective(2) == (0.3, 1.0, (0.0, 0.5, 1.0))
+    assert _objective(m, 2) == (0.3, 1.0, (0.0, 0.5, 1.0))
     m.beta = torch.tensor([1.0, 2.0])
     with pytest.raises(ValueError, match=r'model\.beta.*type Tensor'):
-        m._read_objective(2)
+        _objective(m, 2)
     m.beta, m.iter_weights = 1.0, None
     with pytest.raises(RuntimeError, match='ROCm device'):              # a valid objective goes on to the device check
         m.reconstruct(torch.zeros(1, 3, 16, 16))

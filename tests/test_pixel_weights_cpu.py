@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-from iodine_amd import IODINE, _lib, engine
+from iodine_amd import IODINE, _args, _lib, engine
 from iodine_amd.model import arch_namespace
 from oracle import iodine_oracle as O
 from util import grad_views, rel_err, rel_l2
@@ -186,15 +186,15 @@ def test_valid_weights_pass_the_host_checks():
     for w in (torch.ones(2, 1, 16, 16), torch.ones(2, 16, 16, dtype=torch.float64), torch.ones(2, 16, 16, dtype=torch.bool),
               torch.ones(2, 1, 16, 16, dtype=torch.uint8), torch.ones(2, 16, 16, dtype=torch.float16),
               torch.ones(2, 1, 16, 16, requires_grad=True)):
-        out = m._check_weights(w, x, 'forward')
+        out = _args.check_weights(w, x, 16, 'forward')
         assert out.dtype == torch.float32 and tuple(out.shape) == (2, 16, 16) and out.is_contiguous() and not out.requires_grad
     clip = torch.zeros(2, 3, 3, 16, 16)
-    assert tuple(m._check_weights(torch.ones(2, 3, 1, 16, 16), clip, 'forward').shape) == (2, 3, 16, 16)
-    assert tuple(m._check_weights(torch.ones(2, 3, 16, 16), clip, 'forward').shape) == (2, 3, 16, 16)
-    assert tuple(m._check_weights(torch.ones(2, 1, 16, 16), clip, 'forward').shape) == (2, 16, 16)     # a 4-D weight: every frame
-    assert m._check_weights(None, x, 'forward') is None
+    assert tuple(_args.check_weights(torch.ones(2, 3, 1, 16, 16), clip, 16, 'forward').shape) == (2, 3, 16, 16)
+    assert tuple(_args.check_weights(torch.ones(2, 3, 16, 16), clip, 16, 'forward').shape) == (2, 3, 16, 16)
+    assert tuple(_args.check_weights(torch.ones(2, 1, 16, 16), clip, 16, 'forward').shape) == (2, 16, 16)     # a 4-D weight: every frame
+    assert _args.check_weights(None, x, 16, 'forward') is None
     v = torch.rand(2, 3, 1, 16, 16)
-    assert torch.equal(m._check_weights(v.transpose(3, 4), clip, 'forward'), v.transpose(3, 4)[:, :, 0])
+    assert torch.equal(_args.check_weights(v.transpose(3, 4), clip, 16, 'forward'), v.transpose(3, 4)[:, :, 0])
     with pytest.raises(RuntimeError, match='ROCm device'):              # valid weights go on to the device check
         m.reconstruct(x, weights=torch.ones(2, 1, 16, 16))
 

@@ -9,7 +9,7 @@ import re
 import pytest
 import torch
 
-from iodine_amd import IODINE, _lib, engine
+from iodine_amd import IODINE, _args, _lib, engine
 from oracle import iodine_oracle as O
 from util import hip_arch, rel_err
 
@@ -133,7 +133,7 @@ def test_module_reads_a_tensor_sigma_and_the_attribute():
     assert [n for n, _ in m.named_parameters()] == list(O.param_shapes(ARCH).keys())       # no new module parameter
     log_sigma = torch.tensor(-2.0, requires_grad=True)
     m.sigma = log_sigma.exp()
-    assert m._sigma_input() == (m.sigma,) and abs(m._read_objective(2)[0] - 0.1353352832) < 1e-7
+    assert m._sigma_input() == (m.sigma,) and abs(_args.read_objective(m.sigma, m.beta, m.iter_weights, 2)[0] - 0.1353352832) < 1e-7
     with torch.no_grad():
         assert m._sigma_input() == ()
     m.sigma = m.sigma.detach()
