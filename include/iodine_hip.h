@@ -614,6 +614,80 @@ int iodine_synth_scenes(void* stream, int n, int size, unsigned long long seed, 
                         unsigned long long stream_step, int kind, int max_objects, int frames, float* images,
                         unsigned short* masks_or_null, unsigned char* n_gt_or_null);
 
+/* Decomposition figures (iodine_amd/figures.py): image, reconstruction, segmentation and one panel per slot, for a few scenes or for the
+ * refinement iterations of one scene, assembled on the device into one uint8 picture.  Stateless: no handle, no workspace, one launch, no
+ * atomics, no scratch, no synchronise.
+ *
+ * A sheet has `rows` rows (one scene each: a batch, the T + 1 entries of a trajectory, the frames of a clip) of `n_panels` panels.  A panel
+ * is size * scale pixels square (nearest-neighbour replication by the integer `scale`); `pad` pixels of pad_value surround and separate the
+ * panels:  H = pad + rows (size scale + pad),  W = pad + n_panels (size scale + pad).  The sheet is uint8 (H, W, 3), HWC, contiguous.
+ * Panel c is (panel_kind[c], panel_slot[c]); the slot is read by the three slot kinds only.  R = rows, K = slots, G = n_gt, S = size:
+ *   IODINE_SHEET_IMAGE        x                                                          x (R,3,S,S)
+ *   IODINE_SHEET_PRED         pred                                                       pred (R,3,S,S)
+ *   IODINE_SHEET_SEG          palette[slot_color[r][argmax_k mask]]                      mask (R,K,1,S,S)
+ *   IODINE_SHEET_OVERLAY      (1 - alpha) x + alpha (palette colour of the label); with draw_edges a pixel whose label differs from that of
+ *                             its right or lower neighbour inside the image takes `edge` instead      x, mask
+ *   IODINE_SHEET_GT           palette[gt_color[r][g]], g the lowest ground-truth row with a non-zero byte at the pixel; palette[16]
+ *                             ("none") where no row has one                              gt (R,G,S,S) uint8
+ *   IODINE_SHEET_ERROR        grey gain ((|x0 - p0| + |x1 - p1|) + |x2 - p2|) / 3        x, pred
+ *   IODINE_SHEET_SLOT_MASKED  m_k mean_k + (1 - m_k) background                          mask, mean (R,K,3,S,S)
+ *   IODINE_SHEET_SLOT_MEAN    mean_k                                                     mean
+ *   IODINE_SHEET_SLOT_MASK    grey m_k                                                   mask
+ * palette: 17 RGB triples, 16 slot colours and "none".  slot_color (R,K) / gt_color (R,G): uint8 palette indices in device memory, NULL =
+ * the identity; an index above 16 reads entry 16.
+ * Arithmetic, so that float32 code without fused operations gives the same bytes: the argmax compares `v > best` from -inf, slot 0 upwards
+ * (the lowest index wins a tie, a NaN never wins: the rule of iodine_slot_table); a channel value v becomes
+ * (uint8)(int)(clamp(v) * 255 + 0.5) with clamp(v) = v > 0 ? (v < 1 ? v : 1) : 0, so a NaN becomes 0; every multiply, add, subtract and
+ * divide of a blend, of the error panel and of the quantisation is one IEEE float32 operation rounded on its own; a palette colour enters
+ * a blend as (float)c / 255.f; 1 - alpha and the error's gain * sum / 3.f are evaluated in that order.
+ * One block takes a band of source rows of one panel: it reads the planes once per SOURCE pixel (16-byte loads where size % 4 == 0 and
+ * every plane pointer is 16-byte aligned - gt 4 -, element loads otherwise), keeps the band's colours in LDS, and writes the band's output
+ * rows with the padding left of and above the panel (right of / below it for the last panel / row): every byte of the sheet is written
+ * exactly once.  The rows are stored as aligned 32-bit words, with byte stores at the two ends of a run, where W % 4 == 0 and the sheet is
+ * 4-byte aligned; byte by byte otherwise.  iodine_sheet_form tells which forms a call takes: bit 0 = 16-byte loads, bit 1 = word stores
+ * (-1 for arguments iodine_render_sheet refuses).  Host only.
+ * iodine_sheet_size: H and W of the sheet.  Host only.
+ * IODINE_ERR_INVALID, before anything touches the device, with the entry's name in iodine_last_error(NULL): a NULL spec, mask or sheet (the
+ * size query: a NULL spec or result pointer), rows < 1, slots outside 1..16, n_gt outside 0..16, size outside 1..1024, scale outside 1..8, pad
+ * outside 0..16, n_panels outside 1..64, an unknown kind, a slot index outside 0..slots - 1, a panel whose input is NULL (gt also: n_gt = 0),
+ * H W 3 >= 2^31 (the kernel indexes the sheet in 32 bits). */
+#define IODINE_SHEET_IMAGE 0
+#define IODINE_SHEET_PRED 1
+#define IODINE_SHEET_SEG 2
+#define IODINE_SHEET_OVERLAY 3
+#define IODINE_SHEET_GT 4
+#define IODINE_SHEET_ERROR 5
+#define IODINE_SHEET_SLOT_MASKED 6
+#define IODINE_SHEET_SLOT_MEAN 7
+#define IODINE_SHEET_SLOT_MASK 8
+#define IODINE_SHEET_MAX_PANELS 64
+
+typedef struct iodine_sheet_spec {
+    int rows;                        /* R: scenes, one sheet row each */
+    int slots;                       /* K */
+    int n_gt;                        /* G, 0 = no ground truth */
+    int size;                        /* S */
+    int scale;                       /* 1..8 */
+    int pad;                         /* 0..16 */
+    int n_panels;                    /* 1..64 */
+    int draw_edges;                  /* overlay: 0 / 1 */
+    float background[3];             /* slot_masked: what shows where the mask is 0 */
+    float alpha;                     /* overlay: weight of the label colour */
+    float error_gain;
+    unsigned char pad_value[3];
+    unsigned char edge[3];
+    unsigned char panel_kind[IODINE_SHEET_MAX_PANELS];
+    unsigned char panel_slot[IODINE_SHEET_MAX_PANELS];
+    unsigned char palette[51];       /* 17 x RGB */
+} iodine_sheet_spec;
+
+int iodine_sheet_size(const iodine_sheet_spec* spec, int* height, int* width);
+int iodine_sheet_form(const iodine_sheet_spec* spec, const float* x, const float* pred, const float* mask, const float* mean,
+                      const unsigned char* gt, const unsigned char* sheet);
+int iodine_render_sheet(void* stream, const iodine_sheet_spec* spec, const float* x, const float* pred, const float* mask,
+                        const float* mean, const unsigned char* gt, const unsigned char* slot_color, const unsigned char* gt_color,
+                        unsigned char* sheet);
+
 /* Options: "stop_after_iters" (debug: run only the first v refinement iterations of reconstruct, no final decode),
  * "graph" (1: replay the fixed-shape launch sequence of reconstruct / decode / elbo / train_forward / train_backward through a
  * hipGraph per distinct argument tuple -- first call eager, second captured, later ones one hipGraphLaunch; needs a non-default

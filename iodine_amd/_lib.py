@@ -26,6 +26,16 @@ class Config(C.Structure):
     ]
 
 
+class SheetSpec(C.Structure):
+    """``iodine_sheet_spec`` (include/iodine_hip.h): sizes, panel list and colours of one decomposition sheet"""
+    _fields_ = [
+        ('rows', C.c_int), ('slots', C.c_int), ('n_gt', C.c_int), ('size', C.c_int), ('scale', C.c_int), ('pad', C.c_int),
+        ('n_panels', C.c_int), ('draw_edges', C.c_int), ('background', C.c_float * 3), ('alpha', C.c_float), ('error_gain', C.c_float),
+        ('pad_value', C.c_ubyte * 3), ('edge', C.c_ubyte * 3), ('panel_kind', C.c_ubyte * 64), ('panel_slot', C.c_ubyte * 64),
+        ('palette', C.c_ubyte * 51),
+    ]
+
+
 _vp, _ci, _cf, _dbl, _ll, _ull, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong, C.c_ulonglong, C.c_size_t
 _FP, _VPP, _CIP = C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.POINTER(C.c_int)
 
@@ -126,6 +136,10 @@ _SYMBOLS = {
     # device-resident datasets, iodine_amd.resident
     'iodine_batch_gather': ([_vp, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _vp],),
     'iodine_synth_scenes': ([_vp, _ci, _ci] + [_ull] * 4 + [_ci, _ci, _ci, _vp, _vp, _vp],),
+    # decomposition sheets, iodine_amd.figures
+    'iodine_sheet_size': ([C.POINTER(SheetSpec), _CIP, _CIP],),
+    'iodine_sheet_form': ([C.POINTER(SheetSpec)] + [_vp] * 6,),
+    'iodine_render_sheet': ([_vp, C.POINTER(SheetSpec)] + [_vp] * 8,),
 }
 EXPORTS = tuple(_SYMBOLS)
 

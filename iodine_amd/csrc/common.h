@@ -256,6 +256,14 @@ hipError_t launch_slot_table(hipStream_t st, const float* mask, const float* mea
                              unsigned char* seg);
 hipError_t launch_seg_overlap(hipStream_t st, const unsigned char* seg_a, const unsigned char* seg_b, int B, int Ka, int Kb, int P,
                               int* table);
+// kernels_sheet.hip: decomposition sheets - panels of a few scenes as one uint8 HWC picture (stateless).  W = the sheet's width;
+// sheet_form: bit 0 = 16-byte loads, bit 1 = word stores, what the launcher will take for these pointers.
+struct iodine_sheet_spec;
+int sheet_form(const iodine_sheet_spec& sp, const float* x, const float* pred, const float* mask, const float* mean,
+               const unsigned char* gt, const unsigned char* sheet, int W);
+hipError_t launch_render_sheet(hipStream_t st, const iodine_sheet_spec& sp, const float* x, const float* pred, const float* mask,
+                               const float* mean, const unsigned char* gt, const unsigned char* slot_color, const unsigned char* gt_color,
+                               unsigned char* sheet, int W);
 // kernels_match.hip: slots matched to ground-truth masks - statistics, assignment (assign.h), loss and its gradient (stateless)
 hipError_t launch_mask_overlap(hipStream_t st, const float* mask, const unsigned char* gt, int B, int K, int G, int S, float eps,
                                float* inter, float* nll, float* mask_area, int* gt_area);

@@ -199,7 +199,7 @@ def beta_warmup(step, beta, warmup_steps):
 
 def train(model, optimizer, dataloader, device, max_steps, print_every=10, checkpoint_path=None, log=print, max_grad_norm=None,
           beta=None, beta_warmup_steps=0, bptt=None, ignore_border=0, log_sigma=None, input_gain=None,
-          mask_loss=0.0, mask_loss_kind='ce', mask_match='iou'):
+          mask_loss=0.0, mask_loss_kind='ce', mask_match='iou', sheet_every=0, sheet_path=None, sheet_images=8, sheet_scale=1):
     """train.py:44-108: loss = model(data); loss.mean(); zero_grad; backward; [all-reduce]; [clip]; step.  Returns the losses.
     ``dataloader``: a ``DataLoader`` (``make_dataloader``) or ``ResidentDataset.batches(...)`` (``iodine_amd.resident``), whose batches
     ``(x, gt, n_gt)`` are already on the device - ``gt`` packed ``(B, G, S, S)``, which ``pack_gt`` passes through - and whose epoch is set
@@ -228,7 +228,15 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
     ``mask_loss`` = w > 0: supervised masks.  A step is ``model(x, attach_state=True)`` plus ``w * matched_mask_loss(model.mask,
     pack_gt(data[1]), loss=mask_loss_kind, match=mask_match)`` (``iodine_amd.matching``: ground-truth objects assigned to slots on the device,
     three launches, no synchronise) and one ``backward()``; the log line gains ``mask-loss``.  A batch whose masks are all ``None`` / empty
-    trains unsupervised - the semi-supervised case.  Not combined with ``bptt``.  With 0 (default) no launch, copy or attribute is added."""
+    trains unsupervised - the semi-supervised case.  Not combined with ``bptt``.  With 0 (default) no launch, copy or attribute is added.
+    ``sheet_every`` = n > 0 with ``sheet_path`` = ``OUT.png``: after every n-th optimizer step the decomposition sheet of the first
+    ``sheet_images`` images of the current batch is written to ``OUT_<step:07d>.png`` (``save_sheet``; rank 0 only).  Its reconstruct draws
+    its normals from a Philox stream training never uses, so the sequence of losses is bit-identical with and without it; with 0 (default)
+    nothing is launched or copied."""
+    sheet_every = int(sheet_every or 0)
+    if sheet_every < 0 or (sheet_every and not sheet_path):
+        raise ValueError(f'train: sheet_every must be >= 0 and needs sheet_path; got {sheet_every!r}, {sheet_path!r}')
+    sheet_rank0 = not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0
     if input_gain is not None and bptt is not None:
         raise ValueError('train: input_gain is not combined with bptt (clip_backward differentiates its chunks itself)')
     mask_loss = float(mask_loss)
@@ -289,6 +297,11 @@ def train(model, optimizer, dataloader, device, max_steps, print_every=10, check
                 grad_norm = optimizer.last_grad_norm
             losses.append(loss.item())
             step += 1
+            if sheet_every and step % sheet_every == 0 and sheet_rank0:
+                root, ext = os.path.splitext(sheet_path)
+                save_sheet(model, data, '{}_{:07d}{}'.format(root, step, ext or '.png'), device, images=sheet_images, scale=sheet_scale,
+                           draw=step, log=lambda *a: None)
+                model.train()
             if step % print_every == 0:
                 log('iter: {}, loss: {:.4f}, batch-time: {:.4f}s, lr: {}{}{}{}'.format(
                     step, losses[-1], time.perf_counter() - start, optimizer.param_groups[0]['lr'],
@@ -455,6 +468,35 @@ def save_traversal(model, x, path, top=8, n_values=7, log=print):
     return t
 
 
+SHEET_STREAM = 1 << 63      # Philox stream ids of the sheets' normals: training counts its draws up from 0 and never gets here
+
+
+@torch.no_grad()
+def save_sheet(model, data, path, device, images=8, scale=1, trajectory=None, draw=0, log=print):
+    """The decomposition sheet (``iodine_amd.figures.decomposition``) of the first ``images`` images of a batch - a ``DataLoader`` batch
+    ``(image, masks)`` or a ``ResidentDataset`` batch ``(x, gt, n_gt)``; of a clip, frame 0 - as a PNG: image, reconstruction,
+    segmentation and the slots, with the ``gt`` panel and matched colours when the batch carries masks.  ``trajectory=b``: the refinement
+    figure of image b instead, one row per decode.  The normals come from ``iodine_randn(model seed, SHEET_STREAM + draw)`` and are passed
+    as an explicit ``eps``, so the model's own stream of draws - and with it a training run around this call - is untouched."""
+    from . import _lib, figures
+    x = data[0].to(device)
+    if x.dim() == 5:
+        x = x[:, 0]
+    n = 1 if trajectory is not None else max(1, min(int(images), int(x.shape[0])))
+    eps = torch.empty((model.n_iters + 1, n, model.K, model.dim_latent), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        rc = _lib.lib().iodine_randn(torch.cuda.current_stream().cuda_stream, _lib.ptr(eps), eps.numel(), model._seed,
+                                     (SHEET_STREAM + int(draw)) & (2 ** 64 - 1))
+    _lib.check(rc, None, 'iodine_randn')
+    gt = data[1] if _has_masks(data) and x.dim() == 4 and data[0].dim() == 4 else None
+    model.eval()
+    out = figures.decomposition(model, x, gt=gt, n=n, trajectory=trajectory, eps=eps, scale=scale)
+    figures.write_png(path, out)
+    log('sheet: {} x {} pixels, {} -> {}'.format(out.shape[0], out.shape[1],
+        'refinement of image {}'.format(trajectory) if trajectory is not None else '{} images'.format(n), path))
+    return out
+
+
 def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', choices=['clevr6', 'dsprites'], default='dsprites')
@@ -516,7 +558,31 @@ def make_parser():
                          '(each slot, the units with the largest KL, moved along the posterior) and save the grids; see save_traversal')
     ap.add_argument('--traverse-top', type=int, default=8, metavar='N', help='with --traverse: units per slot, by descending KL')
     ap.add_argument('--traverse-values', type=int, default=7, metavar='V', help='with --traverse: values per unit, linspace(-2, 2, V) posterior sigmas')
+    ap.add_argument('--sheet', metavar='OUT.png',
+                    help='write the decomposition sheet of the first evaluation batch after training / --resume: image, reconstruction, '
+                         'ground truth (when the batch carries masks, with matched colours), segmentation and one panel per slot, a row per '
+                         'image, rendered on the device (iodine_amd.figures)')
+    ap.add_argument('--sheet-images', type=int, default=8, metavar='N', help='with --sheet / --sheet-every: images (rows) per sheet')
+    ap.add_argument('--sheet-scale', type=int, default=1, metavar='Z', help='with --sheet / --sheet-every: integer magnification 1..8')
+    ap.add_argument('--sheet-trajectory', type=int, default=None, metavar='B',
+                    help='with --sheet: the refinement figure of image B of the batch instead, one row per decode (ITERS + 1 rows)')
+    ap.add_argument('--sheet-every', type=int, default=0, metavar='STEPS',
+                    help='with --sheet OUT.png: also write OUT_<step>.png from the first images of the current batch every STEPS training '
+                         'steps; the training losses are bit-identical with and without it')
     return ap
+
+
+def _sheet_kw(args):
+    if args.sheet_every and not args.sheet:
+        raise SystemExit('--sheet-every needs --sheet OUT.png (the step files are named after it)')
+    return dict(sheet_every=args.sheet_every, sheet_path=args.sheet, sheet_images=args.sheet_images, sheet_scale=args.sheet_scale)
+
+
+def _final_sheet(args, model, batches, device, rank):
+    """``--sheet``: the sheet of the first batch of ``batches``, rank 0 only"""
+    if args.sheet and rank == 0:
+        save_sheet(model, next(iter(batches)), args.sheet, device, images=args.sheet_images, scale=args.sheet_scale,
+                   trajectory=args.sheet_trajectory)
 
 
 def main(argv=None):
@@ -580,7 +646,8 @@ def main(argv=None):
     losses = train(model, optimizer, dl, device, args.steps, checkpoint_path=args.save,
                    log=print if rank == 0 else (lambda *a: None), beta=args.beta, beta_warmup_steps=args.beta_warmup,
                    bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border, log_sigma=log_sigma,
-                   input_gain=input_gain, mask_loss=args.mask_loss, mask_loss_kind=args.mask_loss_kind, mask_match=args.mask_match)
+                   input_gain=input_gain, mask_loss=args.mask_loss, mask_loss_kind=args.mask_loss_kind, mask_match=args.mask_match,
+                   **_sheet_kw(args))
     evaluator = None
     if args.metrics:
         from .matching import SegmentationEvaluator
@@ -588,6 +655,7 @@ def main(argv=None):
     ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
                   bound_samples=args.eval_samples)
     _report(args, rank, losses, ev)
+    _final_sheet(args, model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, rank)
 
 
 def _resident_store(args, arch, ds, device, rank, frames=0):
@@ -624,7 +692,7 @@ def _main_resident(args, arch, model, optimizer, ds, device, rank, world, log_si
                    checkpoint_path=args.save, log=print if rank == 0 else (lambda *a: None), beta=args.beta,
                    beta_warmup_steps=args.beta_warmup, bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border,
                    log_sigma=log_sigma, input_gain=input_gain, mask_loss=args.mask_loss, mask_loss_kind=args.mask_loss_kind,
-                   mask_match=args.mask_match)
+                   mask_match=args.mask_match, **_sheet_kw(args))
     evaluator = None
     if args.metrics:
         from .matching import SegmentationEvaluator
@@ -632,6 +700,7 @@ def _main_resident(args, arch, model, optimizer, ds, device, rank, world, log_si
     ev = evaluate(model, store.batches(args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
                   bound_samples=args.eval_samples)
     _report(args, rank, losses, ev)
+    _final_sheet(args, model, store.batches(args.batch, shuffle=False, rank=rank, world_size=world), device, rank)
 
 
 def _report(args, rank, losses, ev):

@@ -98,6 +98,12 @@ class Traversal:
         r, c, ch, S, _ = t.shape
         return t.permute(2, 0, 3, 1, 4).reshape(ch, r * S, c * S)
 
+    def save_png(self, path, i: int, transpose: bool = False) -> None:
+        """``grid(i, transpose)`` as an 8-bit RGB PNG: every channel value quantised by the rule of the decomposition sheets
+        (``figures.quantise``: clamp to [0, 1], ``int(v * 255 + 0.5)``, NaN -> 0), one copy to the host."""
+        from .figures import quantise, write_png
+        write_png(path, quantise(self.grid(i, transpose)).permute(1, 2, 0).contiguous())
+
 
 def traverse(model, z, *, image: int = 0, slots=None, dims=None, values=None, mode: str = 'set', posterior=None, top: int = 8,
              return_mask: bool = False) -> Traversal:
