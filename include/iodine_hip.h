@@ -431,6 +431,10 @@ int iodine_last_sigma_grad(iodine_handle* h, void* stream, float* out, int n);
  * (iodine.py:210-220), weighted per pixel by w_p (iodine_set_pixel_weights, 1 without):
  *   d LL / d x[b,c,p] = -(1 / B) sum_k g1_kc,  g1_kc = w_p r_kc (x_c - mu_kc) / sigma^2  (r: responsibilities; the weight is inside)
  *   d LL / d w[b,p]   =  (1 / B) sum_c log_likelihood[b,c,p]                             (raw: NOT multiplied by w)
+ * Option "joint_likelihood": log_likelihood = logsumexp_k(log(mask + 1e-12) + sum_c K_log_likelihood), one plane per image, and
+ *   d LL / d x[b,c,p] = -(1 / B) sum_k g1_kc,  g1_kc = w_p r_k (x_c - mu_kc) / sigma^2   (ONE responsibility r_k per slot and pixel,
+ *                                                                                         r_k = softmax_k(log(mask_k + 1e-12) + sum_c l_kc))
+ *   d LL / d w[b,p]   =  (1 / B) log_likelihood[b,0,p]
  * The refinement inputs are detached (iodine.py:343) and the KL term does not see the image: these direct terms are all of d ELBO / d x.
  * The reference treats weights it does not have as data; here they are differentiable on request.
  *   after iodine_train_forward / _seq / _frames:  sum_e a_e d LL_e / d (x, w)  with a_e the iteration weights the call ran with
@@ -447,6 +451,8 @@ int iodine_last_input_grad(iodine_handle* h, void* stream, float* g_x, float* g_
  * iodine_last_elbo_outputs reads -- computed on request from its decoder output and its image (its frame of a clip):
  *   k_log_likelihood (count, K, 3, S, S) = gaussian_log_likelihood(x[:, None], mean, sigma),
  *   log_likelihood   (count, 3, S, S)    = logsumexp_k(log(mask + 1e-12) + k_log_likelihood);     either may be NULL.
+ * With option "joint_likelihood" log_likelihood is (count,1,S,S) = logsumexp_k(log(mask + 1e-12) + k_log_likelihood.sum(2)), one plane
+ * per image (a third of the floats: size the buffer by the option); k_log_likelihood is unchanged.
  * K = the slots of that call; sigma = the handle's current objective.  RAW: pixel weights do not enter (the weighted LL the call reported is
  * sum_p w_p sum_c log_likelihood).  The kernel is apart from the one that sums the reported LL: sum_c of the map agrees with
  * elbo_iter[..][2] to fp32 rounding, not bitwise.  Plain outputs: nothing is attached to a graph (the reference's attributes are).
@@ -711,6 +717,16 @@ int iodine_render_sheet(void* stream, const iodine_sheet_spec* spec, const float
  * slots the channel was meant to be -- the same value wherever the reference's is finite up to rounding, finite everywhere; libm expf
  * and IEEE division either way, one definition for every kernel that writes the channel (pixel_terms.h).  The likelihood and
  * leave-one-out channels, the ELBO and every backward are unchanged.  Part of the hipGraph key; takes effect with the next call),
+ * "joint_likelihood" (the form of the pixel likelihood.  0 -- default, the reference (iodine.py:210-216): a K-component mixture for each
+ * colour channel, LL_p = sum_c log sum_k (m_k + 1e-12) N(x_c; mu_kc, sigma); 1: the IODINE paper's, ONE mixture per pixel over the RGB
+ * vector, LL_p = log sum_k (m_k + 1e-12) prod_c N(x_c; mu_kc, sigma) = logsumexp_k(log(m_k + 1e-12) + sum_c l_kc).  Every kernel that
+ * evaluates the per-pixel terms takes the form (pixel_terms.h): the ELBO and LL every call reports, the inner gradients and channels 9-13
+ * of the refinement input, d LL / d sigma, d LL / d x and d LL / d w, iodine_predictive's ll, iodine_last_likelihood (whose log_likelihood
+ * is then (count,1,S,S)).  Channels 8 and 14 (mask_posterior, leave-one-out: products over RGB in the reference already), K_log_likelihood,
+ * the decode and the KL are the same bits in both forms; with 0 every launch and every bit is what it was before the option existed.
+ * Part of the hipGraph key.  A change while a training forward or a decode / elbo under "save_for_backward" is saved DISCARDS that
+ * pass -- iodine_train_backward_frames decodes earlier evaluations again and would mix the forms: the backward that follows returns
+ * IODINE_ERR_STATE with a message that says so.  Other values: IODINE_ERR_INVALID),
  * "profile" (bracket kernel launches with HIP events on the launch stream: 1 = the dominant "conv_tile_*" launches only --
  * 54 of ~330 per training step, what bench.py keeps on inside its timed region; 2 = every category; 0 = off),
  * "conv_precision" (3x3 convs of the decoder and refinement stacks: 0 = exact fp32 MFMA -- IEEE fp32 products, fp32 accumulate,
@@ -881,7 +897,9 @@ int iodine_op_render_bwd_logits(void* stream, const float* dec_out, const float*
  * count: x_nchw (batch,3,pixels), w (batch,pixels) or NULL (= 1), dec_out [batch * slots][pixels][4]; slots 1..16.
  *   ll (batch,3,pixels), kll (batch,slots,3,pixels): the raw maps (iodine_last_likelihood);
  *   gx (batch,3,pixels) = (first ? 0 : gx) + coef * -sum_k g1_kc,  gw (batch,pixels) = (first ? 0 : gw) + coef * sum_c ll_c
- *   (iodine_last_input_grad with coef = a_e / B).  Any of the four may be NULL.  strict as for iodine_op_render_bwd.  Allocates,
+ *   (iodine_last_input_grad with coef = a_e / B).  Any of the four may be NULL.  `strict` is a flag word: bit 0 strict as for
+ *   iodine_op_render_bwd, bit 1 joint (option "joint_likelihood"): ll is then (batch,1,pixels), gx is built from the joint
+ *   responsibilities and gw = (first ? 0 : gw) + coef * ll.  Allocates,
  * synchronises and frees per call -- not for timing.  IODINE_ERR_INVALID, without a launch, for a bad argument. */
 int iodine_op_pixel_maps(void* stream, const float* x_nchw, const float* w_or_null, const float* dec_out_nhwc4, int batch, int slots,
                          int pixels, float sigma, int strict, float coef, float* ll, float* kll, float* gx, float* gw, int first);
@@ -893,7 +911,7 @@ int iodine_op_pixel_maps(void* stream, const float* x_nchw, const float* w_or_nu
  *   the split form if out[7]), final_out.
  * x_nchw (batch,3,size^2), w (batch,size^2) or NULL, dec_out [batch * slots][size^2][4], pm / plv (batch,slots,latent), lin [size] (the
  * coordinate table, iodine_linspace_host).  flags: bit 0 strict (as for iodine_op_render_bwd), bit 1 layer-norm statistics (0: lnstat = {0, 1}),
- * bit 2 stable_encoding.  chmask: bit c = internal channel c of the encoding is written, an absent one is 0.  out[12]:
+ * bit 2 stable_encoding, bit 3 joint (option "joint_likelihood": pass 1, sigma-grad and pass 2 in the joint form).  chmask: bit c = internal channel c of the encoding is written, an absent one is 0.  out[12]:
  *   g [batch * slots][size^2][4] = d(B ELBO) / d dec_out, lnstat (batch,slots,8) = {mean, 1 / (sd + 1e-5)} of g_mean, g_mask, leave-one-out,
  *   likelihood, ll_img [batch], img_terms (batch,2) = {ll, kl}, scal [3] = {elbo, kl, ll}                         -- required;
  *   sgrad [1] = d LL / d sigma; enc [batch * slots][size^2][20] (split: [..][12]); enc_sh [batch][size^2][8];

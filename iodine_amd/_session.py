@@ -24,7 +24,9 @@ class Session:
         self.frames = 0                             # frames per call the handle expects (iodine_set_frames; 0 = one image)
         self.objective = (float(cfg.sigma), 1.0, ())        # (sigma, beta, weights) the handle holds (iodine_set_objective)
         self.modes = {k: bool(self.options.get(k)) for k in ('stable_encoding', 'sigma_grad')}     # these options as the handle holds them
+                                                                                                   # (a third mode of the same kind: self.joint below)
         self.ig = int(self.options.get('input_grad', 0))    # option input_grad as the handle holds it
+        self.joint = bool(self.options.get('joint_likelihood'))     # option joint_likelihood as the handle holds it (IODINE.likelihood)
         self.graph_stream, self.graph_bufs = None, {}
         self.call_serial = call_serial              # bumped by every compute call; a backward must match the forward that saved state
 
@@ -85,6 +87,8 @@ class Session:
             self.param_versions = None      # the library keeps only the selected path's weight packs: re-send the parameters
         if key == 'input_grad':
             self.ig = int(value)
+        if key == 'joint_likelihood':
+            self.joint = bool(value)
         if key in ('wgrad_accum', 'input_grad'):
             self.ws_key = None              # the workspace plan depends on it: ask the library again
 
@@ -102,12 +106,14 @@ class Session:
             self.param_versions = versions
         return self.handle
 
-    def prepare(self, device, B, mode, K, T, frames=None, objective=None, sigma_grad=False, input_grad=None, stable_encoding=False):
+    def prepare(self, device, B, mode, K, T, frames=None, objective=None, sigma_grad=False, input_grad=None, stable_encoding=False,
+                joint_likelihood=False):
         """Everything the compute call that follows needs on the handle, each step sent only when it differs from what the handle holds,
         in this order: the parameters; option input_grad (bit 1: image, bit 2: pixel weights - its accumulators are part of the workspace
         plan, so it comes before the workspace; ``set_option('input_grad', bits)`` keeps bits on for every call); the run shape (K, T);
         the frame count (0 = one image per batch entry, E = a clip of E frames); a workspace planned for (B, mode, K, T, frames); the
-        modes stable_encoding / sigma_grad (``set_option('sigma_grad', 1)`` keeps it on) and the objective (sigma, beta, weights).
+        modes stable_encoding / sigma_grad (``set_option('sigma_grad', 1)`` keeps it on), the form of the likelihood (option
+        joint_likelihood) and the objective (sigma, beta, weights).
         A None ``input_grad`` / ``frames`` / ``objective`` skips its step: the handle keeps what it has.  -> the handle."""
         h = self.open(device)
         self.sync_params()
@@ -135,6 +141,9 @@ class Session:
                 if self.modes[k] != want:
                     self._set('iodine_set_option', k.encode(), float(want))
                     self.modes[k] = want
+            if self.joint != bool(joint_likelihood):        # (the handle discards a saved pass of the other form: its backward is refused)
+                self._set('iodine_set_option', b'joint_likelihood', float(bool(joint_likelihood)))
+                self.joint = bool(joint_likelihood)
             if objective != self.objective:
                 sigma, beta, w = objective
                 with torch.cuda.device(device):             # (a new weight table is a small device allocation of the handle)

@@ -82,25 +82,28 @@ hipError_t launch_dec_out(hipStream_t st, const float* in, const float* wk, cons
 // kernels_pixel.hip
 int pixel_blocks_per_image(int P);
 // strict = 1 (conv_precision 0): libm expf + IEEE division in the per-pixel mixture terms (pixel_terms.h), 0: v_exp_f32 / v_rcp_f32 where bounded
+// joint = 1 (option joint_likelihood): one mixture per pixel over the RGB vector, 0: the reference's mixture per colour channel - the same
+// argument of every launcher below that evaluates the terms (pixel_terms_core, pixel_terms.h); never defaulted: a launch site that forgot it
+// would silently evaluate the per-channel form in joint mode
 hipError_t launch_pixel_pass1(hipStream_t st, const float* x4, const float* dec, float* g, double* part, int B,
-                              int K, int P, float sigma, int strict = 0);
+                              int K, int P, float sigma, int strict, int joint);
 // finalize + KL + batch means in one launch; counter: one zero-initialised device word per handle
 hipError_t launch_pixel_finalize_elbo(hipStream_t st, const double* part, int B, int K, int P, int use_ln, float* lnstat, float* ll_img,
                                       const float* pm, const float* plv, int L, float* img_terms, float* scal, unsigned* counter, float beta);
 hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec, const float* lnstat,
-                              const float* lin, float* enc, int B, int K, int S, float sigma, float* enc_sh = nullptr, unsigned chmask = 0x1ffffu,
-                              int strict = 0, int stable = 0);       // stable: option stable_encoding (mask_post, pixel_terms.h)
+                              const float* lin, float* enc, int B, int K, int S, float sigma, float* enc_sh, unsigned chmask,
+                              int strict, int stable, int joint);               // stable: option stable_encoding (mask_post, pixel_terms.h)
 // option sigma_grad: out[0] = d LL / d sigma of the evaluation whose decoder output is dec (kernels_pixel.hip); part: B x blocks doubles
 hipError_t launch_pixel_sigma_grad(hipStream_t st, const float* x4, const float* dec, double* part, float* out, int B, int K, int P,
-                                   double sigma, int strict);
-// kernels_pixmap.hip (iodine.py:210-220).  The raw per-pixel maps of the evaluation whose decoder output is dec: ll (B,3,P) = log_likelihood,
-// kll (B,K,3,P) = K_log_likelihood, NCHW, either may be NULL; the pixel weight in lane 3 of x4 is not read
+                                   double sigma, int strict, int joint);
+// kernels_pixmap.hip (iodine.py:210-220).  The raw per-pixel maps of the evaluation whose decoder output is dec: ll (B,3,P) = log_likelihood
+// (joint: (B,1,P), one plane per image), kll (B,K,3,P) = K_log_likelihood, NCHW, either may be NULL; the pixel weight in lane 3 of x4 is not read
 hipError_t launch_pixel_like_maps(hipStream_t st, const float* x4, const float* dec, float* ll, float* kll, int B, int K, int P, float sigma,
-                                  int strict);
+                                  int strict, int joint);
 // option input_grad: gx[b * gx_bs + c * P + p] (=, first_x, or +=) coef * -sum_k g1_kc; gw[b * gw_bs + p] (=, first_w, or +=) coef * sum_c ll_c;
 // either pointer may be NULL.  g1 / ll_sum come from pixel_terms_core: the pixel weight is inside g1, gw is raw
 hipError_t launch_pixel_input_grad(hipStream_t st, const float* x4, const float* dec, float* gx, size_t gx_bs, float* gw, size_t gw_bs, int B,
-                                   int K, int P, float sigma, int strict, float coef, int first_x, int first_w);
+                                   int K, int P, float sigma, int strict, float coef, int first_x, int first_w, int joint);
 hipError_t launch_final_out(hipStream_t st, const float* dec, float* pred, float* mask, float* mean, float* logits,
                             int B, int K, int P);
 // kernels_edit.hip: final_out for edits that each replace (src = row of `edit` [rows][P][4]) or remove (src < 0) ONE slot of an image of
@@ -118,7 +121,7 @@ hipError_t launch_predictive_sample(hipStream_t st, const float* pm, const float
                                     int post_stride);
 hipError_t launch_predictive_accum(hipStream_t st, const float* dec, const float* x4, int B, int K, int P, int s0, int n_s, float* pred_mean,
                                    float* pred_m2, float* mask_mean, float* mask_m2, int* votes, double* part, float* ll, float sigma,
-                                   int strict);
+                                   int strict, int joint);
 // kernels_render.hip: backward of the rendering (sigmoid, slot softmax, sum_k mask * mean) for the caller's gradients wrt pred (B,3,S,S),
 // mask (B,K,1,S,S), mean (B,K,3,S,S) - NCHW, any of them NULL = zero - into g [N][P][4]; strict as for launch_pixel_pass1
 hipError_t launch_render_bwd(hipStream_t st, const float* dec, const float* g_pred, const float* g_mask, const float* g_mean, float* g,
@@ -415,7 +418,7 @@ size_t refine_l0_wpk_bytes(int O);
 bool refine_l0_fused_ok(int S, int c, int K);
 hipError_t launch_refine_l0_fused(hipStream_t st, const float* x4, const float* dec, const float* lnstat, const float* lin, const void* wk,
                                   const float* wkmeta, const void* ws, const float* wsmeta, const float* bias, float* out, float* enck,
-                                  float* encs, int B, int K, int S, int c, float sigma, unsigned chmask, int stable = 0);
+                                  float* encs, int B, int K, int S, int c, float sigma, unsigned chmask, int stable, int joint);
 // kernels_refws.hip: weight-stationary stride-2 conv C -> C + bias + ELU (refinement layers 1 ..), wpk = launch_pack_conv_weights_ws(w, C, 0)
 bool conv3x3_s2ws_ok(int S, int c);
 hipError_t launch_conv3x3_s2ws_f16x3(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias, float* out,

@@ -148,6 +148,13 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
         return IODINE_OK;
     }
     if (!strcmp(key, "stable_encoding")) { h->stable_enc = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "joint_likelihood")) {
+        if (value != 0 && value != 1) return h->fail(IODINE_ERR_INVALID, "option joint_likelihood: 0 (a mixture per colour channel, the reference) or 1 (one mixture per pixel over RGB)");
+        // a saved pass ran in the other form and iodine_train_backward_frames decodes earlier evaluations again: it is discarded, not mixed
+        if (h->joint_ll != (int)value && (h->calls.fwd_done || h->calls.diff_kind)) { h->calls.saved_passes_gone(); h->calls.form_changed = true; }
+        h->joint_ll = (int)value;
+        return IODINE_OK;
+    }
     if (!strcmp(key, "refine_split")) { h->refine_split = value != 0; return IODINE_OK; }
     if (!strcmp(key, "head_fused")) { h->head_fused = value != 0; return IODINE_OK; }
     if (!strcmp(key, "refine_bwd_fused")) { h->refine_bwd_fused = value != 0; return IODINE_OK; }
@@ -417,7 +424,7 @@ int iodine_predictive(iodine_handle* h, void* stream, int batch, int n_samples, 
         HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, zc, h->wcls, nullptr, b.V, n_s * N, L, h->Cd));
         if (int r = decoder_forward(h, st, n_s * N, zc, b.g)) return r;
         PROF(h, st, "predictive", launch_predictive_accum(st, b.g, like ? b.x4 : nullptr, B, K, h->P, s0, n_s, s_pm, s_p2, s_mm, s_m2, s_vt, b.part,
-                                                         like ? ll + (size_t)s0 * B : nullptr, (float)h->obj.sigma, h->precision == 0));
+                                                         like ? ll + (size_t)s0 * B : nullptr, (float)h->obj.sigma, h->precision == 0, h->joint_ll));
     }
     return IODINE_OK;
 }
@@ -619,7 +626,7 @@ int iodine_last_likelihood(iodine_handle* h, void* stream, int count, float* log
     // the image that evaluation scored: frame last_elbo_iter of a clip (x4 is frame-major), else the one image
     const float* x4 = b.x4 + (b.F > 1 ? (size_t)h->calls.last_elbo_iter * b.B * h->P * 4 : 0);
     HIPCHK(h, launch_pixel_like_maps((hipStream_t)stream, x4, b.dec_out, log_likelihood, k_log_likelihood, count, K, h->P, (float)h->obj.sigma,
-                                     h->precision == 0));
+                                     h->precision == 0, h->joint_ll));
     return IODINE_OK;
 }
 

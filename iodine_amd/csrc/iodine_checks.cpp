@@ -150,6 +150,9 @@ int train_forward_check(iodine_handle* h, int batch, const float* x, const float
 
 int train_backward_check(iodine_handle* h, float* const* param_grads, int n, const AuxCot* aux)
 {
+    if (!h->calls.fwd_done && h->calls.form_changed)
+        return h->fail(IODINE_ERR_STATE, "iodine_train_backward: option joint_likelihood changed after the forward pass, which discarded it - "
+                                         "run the forward again in the form its backward is wanted in");
     if (!h->calls.fwd_done) return h->fail(IODINE_ERR_STATE, "iodine_train_backward: no iodine_train_forward to differentiate");
     if (n != (int)h->params.size() || !param_grads) return h->fail(IODINE_ERR_INVALID, "iodine_train_backward: wrong parameter count");
     if (h->buf.mode != 1 || h->buf.B != h->calls.fwd_batch || h->buf.K != h->K || h->buf.T != h->T)
@@ -169,6 +172,9 @@ int train_backward_check(iodine_handle* h, float* const* param_grads, int n, con
 int diff_ready(iodine_handle* h, int kind, const char* who)
 {
     if (!h->params_set) return h->fail(IODINE_ERR_STATE, std::string(who) + ": iodine_set_params has not been called");
+    if (h->calls.diff_kind != kind && h->calls.form_changed)
+        return h->fail(IODINE_ERR_STATE, std::string(who) + ": option joint_likelihood changed after the forward pass, which discarded it - run "
+                                             "the forward again in the form its backward is wanted in");
     if (h->calls.diff_kind != kind)
         return h->fail(IODINE_ERR_STATE, std::string(who) + (kind == 1 ? ": no iodine_decode" : ": no iodine_elbo") +
                                              " with option save_for_backward to differentiate (none has run, another compute call has re-used "

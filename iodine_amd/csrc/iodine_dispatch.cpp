@@ -343,7 +343,7 @@ int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps
     HIPCHK(h, launch_dec_v(st, b.pm, b.plv, eps_i, nullptr, h->wcls, b.z[i], b.V, N, h->L, h->Cd));
     int rc = decoder_forward(h, st, N, b.z[i]);
     if (rc) return rc;
-    PROF(h, st, "pixel_pass1", launch_pixel_pass1(st, x4_frame(h, i), b.dec_out, b.g, b.part, B, h->K, h->P, sigma, h->precision == 0));
+    PROF(h, st, "pixel_pass1", launch_pixel_pass1(st, x4_frame(h, i), b.dec_out, b.g, b.part, B, h->K, h->P, sigma, h->precision == 0, h->joint_ll));
     // the ticket of pixel_finalize_elbo_kernel is reset by the last block of every launch; the first launch of an entry point also
     // starts from a fresh 0 (a memset node under graph capture), whatever a failed call or a misuse of the handle from a second
     // stream left in it - once per call, not per launch (a memset is a launch of its own)
@@ -352,7 +352,7 @@ int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps
                                          b.img_terms + (size_t)i * B * 2, b.scal + 3 * i, h->elbo_counter, beta));
     if (sgrad)
         PROF(h, st, "pixel_sigma_grad", launch_pixel_sigma_grad(st, x4_frame(h, i), b.dec_out, b.sg_part, b.sgrad + i, B, h->K, h->P, h->obj.sigma,
-                                                                h->precision == 0));
+                                                                h->precision == 0, h->joint_ll));
     if (igrad) {
         // igrad: the bits of option input_grad; buf.ig_x / ig_w += ig_coef x d (B LL_i) / d (x, w).  A still image (and a weight map shared
         // by the frames of a clip) is met by every evaluation: the first one writes, the others add, in evaluation order.  Frame i of a clip
@@ -362,7 +362,7 @@ int elbo_and_gradients(iodine_handle* h, hipStream_t st, int B, const float* eps
         PROF(h, st, "pixel_input_grad", launch_pixel_input_grad(st, x4_frame(h, i), b.dec_out, (igrad & 1) ? b.ig_x + (F ? i * 3 * P : 0) : nullptr,
                                                                 F ? F * 3 * P : 3 * P, (igrad & 2) ? b.ig_w + (wpf ? i * P : 0) : nullptr,
                                                                 wpf ? F * P : P, B, h->K, h->P, sigma, h->precision == 0, ig_coef,
-                                                                F || i == 0, wpf || i == 0));
+                                                                F || i == 0, wpf || i == 0, h->joint_ll));
     }
     if (!need_grads) return IODINE_OK;
     float* dpre0 = nullptr;
@@ -387,12 +387,12 @@ int ref_conv_fwd(iodine_handle* h, hipStream_t st, const RefForm& f, int i, int 
     if (l == 0 && f.l0f) {
         PROF(h, st, "refine_l0f", launch_refine_l0_fused(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, h->ref_l0k, h->ref_l0kmeta, h->ref_l0s, h->ref_l0smeta,
                                                          h->ref_b[0], b.ract[i][0], keep_enc ? b.enck[i] : nullptr, keep_enc ? b.encs[i] : nullptr, B, h->K,
-                                                         h->S, Cr, (float)h->obj.sigma, h->enc_chmask, h->stable_enc));
+                                                         h->S, Cr, (float)h->obj.sigma, h->enc_chmask, h->stable_enc, h->joint_ll));
         return IODINE_OK;
     }
     if (l == 0)
         PROF(h, st, "pixel_pass2", launch_pixel_pass2(st, x4_frame(h, i), b.dec_out, b.lnstat, h->lin, f.split ? b.enck[i] : b.enc[i], B, h->K, h->S,
-                                                      (float)h->obj.sigma, f.split ? b.encs[i] : nullptr, h->enc_chmask, h->precision == 0, h->stable_enc));
+                                                      (float)h->obj.sigma, f.split ? b.encs[i] : nullptr, h->enc_chmask, h->precision == 0, h->stable_enc, h->joint_ll));
     switch (f.fam) {
     case REF_GENERIC:
         PROF(h, st, "gen_conv", launch_gen_conv_fwd(st, in, h->gen_wref[l], h->ref_b[l], b.ract[i][l], N, s, l == 0 ? 17 : Cr, cip, Cr, h->kr, h->rs, 1,

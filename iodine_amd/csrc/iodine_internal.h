@@ -118,17 +118,18 @@ struct CallState {
     int ig_bits = 0;                            // what buf.ig_x / ig_w hold of the last compute call (option input_grad; 0: nothing -
     int ig_frames = 0, ig_wpf = 0;              // iodine_last_input_grad refuses), the frames of that call (0: a still image) and whether its
                                                 // weight gradient is per frame
+    bool form_changed = false;                  // option joint_likelihood changed while a pass was saved: that pass is gone, and its backward says why
     bool redecoded = false;                     // a backward decoded an earlier evaluation again (iodine_train_backward_frames): buf.dec_out no
                                                 // longer belongs to the last elbo(); the posterior and the LSTM state are untouched
 
     // iodine_set_params, a changed run shape or frames setting, a consumed backward (like autograd without retain_graph)
     void saved_passes_gone() { fwd_done = false; diff_kind = 0; }
     // a compute call re-uses the arena.  keep_lstm_state: a plain iodine_decode does not touch buf.h / buf.c
-    void compute_begins(bool keep_lstm_state = false) { saved_passes_gone(); redecoded = false; sgrad_n = 0; ig_bits = 0; if (!keep_lstm_state) state_iter = -1; }
+    void compute_begins(bool keep_lstm_state = false) { saved_passes_gone(); form_changed = false; redecoded = false; sgrad_n = 0; ig_bits = 0; if (!keep_lstm_state) state_iter = -1; }
     // a re-plan (ensure_workspace), iodine_set_workspace, a wgrad_accum toggle: nothing the arena held can be read any more.
     // (iodine_set_workspace used to leave enc_valid and the wgrad_accum toggle state_iter: unobservable, every reader of the two also
     // refuses while buf.bytes == 0, and the next compute call re-plans)
-    void arena_gone() { saved_passes_gone(); last_elbo_iter = -1; state_iter = -1; enc_valid = false; redecoded = false; sgrad_n = 0; ig_bits = 0; }
+    void arena_gone() { saved_passes_gone(); form_changed = false; last_elbo_iter = -1; state_iter = -1; enc_valid = false; redecoded = false; sgrad_n = 0; ig_bits = 0; }
 };
 #pragma GCC visibility pop
 
@@ -231,6 +232,8 @@ struct iodine_handle {
                                                 // accumulates sum_e a_e d LL_e / d x (d w) (kernels_pixmap.hip; 0: no launch, no buffer)
     int ig_call_wpf = 0;                        // (the running call's pixel weights are per frame: read by elbo_and_gradients inside the call)
     int stable_enc = 0;                         // option stable_encoding: channel 8 of the encoding as a max-subtracted softmax (pixel_terms.h)
+    int joint_ll = 0;                           // option joint_likelihood: one mixture per pixel over the RGB vector (pixel_terms.h), every launch
+                                                // of the per-pixel terms takes it; a change discards the saved passes (iodine_set_option)
     int save_bwd = 0;                           // option save_for_backward: a decode / elbo keeps what its backward reads (calls.diff_*)
     // hipGraph replay of the fixed-shape launch sequences (option "graph"): one instantiated graph per distinct argument tuple
     int graph = 0;

@@ -528,10 +528,11 @@ int iodine_op_pixel_maps(void* stream, const float* x_nchw, const float* w_or_nu
     float* x4 = nullptr;
     if (hipMalloc((void**)&x4, (size_t)batch * pixels * 4 * sizeof(float)) != hipSuccess) return IODINE_ERR_HIP;
     hipError_t e = launch_x_to_nhwc4(st, x_nchw, x4, batch, pixels, 1, w_or_null, 0);
-    if (e == hipSuccess) e = launch_pixel_like_maps(st, x4, dec_out_nhwc4, ll, kll, batch, slots, pixels, sigma, strict ? 1 : 0);
+    const int st_ = strict & 1, joint = (strict >> 1) & 1;                 // the flag word: bit 0 strict, bit 1 joint_likelihood
+    if (e == hipSuccess) e = launch_pixel_like_maps(st, x4, dec_out_nhwc4, ll, kll, batch, slots, pixels, sigma, st_, joint);
     if (e == hipSuccess)
-        e = launch_pixel_input_grad(st, x4, dec_out_nhwc4, gx, (size_t)3 * pixels, gw, (size_t)pixels, batch, slots, pixels, sigma, strict ? 1 : 0,
-                                    coef, first ? 1 : 0, first ? 1 : 0);
+        e = launch_pixel_input_grad(st, x4, dec_out_nhwc4, gx, (size_t)3 * pixels, gw, (size_t)pixels, batch, slots, pixels, sigma, st_,
+                                    coef, first ? 1 : 0, first ? 1 : 0, joint);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(x4);
     if (e != hipSuccess) { g_create_error = std::string("iodine_op_pixel_maps: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
@@ -556,7 +557,7 @@ int iodine_op_pixel_encode(void* stream, const float* x_nchw, const float* w_or_
         return IODINE_ERR_INVALID;
     }
     float *g = out[0], *lnstat = out[1], *ll_img = out[2], *img_terms = out[3], *scal = out[4], *sgrad = out[5], *enc = out[6], *enc_sh = out[7];
-    const int Pi = (int)P, strict = flags & 1, use_ln = (flags >> 1) & 1, stable = (flags >> 2) & 1;
+    const int Pi = (int)P, strict = flags & 1, use_ln = (flags >> 1) & 1, stable = (flags >> 2) & 1, joint = (flags >> 3) & 1;
     const size_t nblk = (size_t)pixel_blocks_per_image(Pi);
     // [x4: B P float4][part: B nblk (6 K + 3) doubles][sg_part: B nblk doubles][counter: one word, 16 bytes]
     const size_t x4_bytes = B * P * 4 * sizeof(float), part_bytes = B * nblk * (6 * K + 3) * sizeof(double), sg_bytes = B * nblk * sizeof(double);
@@ -570,12 +571,12 @@ int iodine_op_pixel_encode(void* stream, const float* x_nchw, const float* w_or_
     for (int r = 0; e == hipSuccess && r < repeat; ++r) {                  // (repeat > 1: the finalize finds the counter its last launch left)
         // ... and scal as NaN: a launch whose ticket elects no last block would otherwise leave the previous launch's (equal) values
         if (r > 0 && (e = hipMemsetAsync(scal, 0xff, 3 * sizeof(float), st)) != hipSuccess) break;
-        e = launch_pixel_pass1(st, x4, dec_out_nhwc4, g, part, batch, slots, Pi, sigma, strict);
+        e = launch_pixel_pass1(st, x4, dec_out_nhwc4, g, part, batch, slots, Pi, sigma, strict, joint);
         if (e == hipSuccess)
             e = launch_pixel_finalize_elbo(st, part, batch, slots, Pi, use_ln, lnstat, ll_img, pm, plv, latent, img_terms, scal, counter, beta);
     }
-    if (e == hipSuccess && sgrad) e = launch_pixel_sigma_grad(st, x4, dec_out_nhwc4, sg_part, sgrad, batch, slots, Pi, (double)sigma, strict);
-    if (e == hipSuccess && enc) e = launch_pixel_pass2(st, x4, dec_out_nhwc4, lnstat, lin, enc, batch, slots, size, sigma, enc_sh, chmask, strict, stable);
+    if (e == hipSuccess && sgrad) e = launch_pixel_sigma_grad(st, x4, dec_out_nhwc4, sg_part, sgrad, batch, slots, Pi, (double)sigma, strict, joint);
+    if (e == hipSuccess && enc) e = launch_pixel_pass2(st, x4, dec_out_nhwc4, lnstat, lin, enc, batch, slots, size, sigma, enc_sh, chmask, strict, stable, joint);
     if (e == hipSuccess) e = launch_final_out(st, dec_out_nhwc4, out[8], out[9], out[10], out[11], batch, slots, Pi);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(buf);

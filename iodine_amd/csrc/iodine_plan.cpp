@@ -259,7 +259,7 @@ std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, s
     uint64_t sb, bb;
     memcpy(&sb, &o->sigma, 8); memcpy(&bb, &o->beta, 8);
     std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->K, (uintptr_t)h->T, (uintptr_t)h->stop_after, (uintptr_t)h->precision,
-                                (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7) | (h->sigma_grad << 8) | (h->stable_enc << 9) | (h->input_grad << 10)),
+                                (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7) | (h->sigma_grad << 8) | (h->stable_enc << 9) | (h->input_grad << 10) | (h->joint_ll << 12)),
                                 (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own), (uintptr_t)h->frames};
     k.push_back((uintptr_t)sb); k.push_back((uintptr_t)bb); k.push_back((uintptr_t)o->wgen);
     k.push_back((uintptr_t)(pw ? pw->w : nullptr)); k.push_back((uintptr_t)(pw ? pw->per_frame : 0));

@@ -44,7 +44,8 @@ IOD_DEVINL double wave_sum_d(double v)
 
 // ---- pass 1: ELBO log-likelihood partials, gradient wrt decoder output, layer-norm partial sums ----
 // part layout per (b, block): [0] ll (sum_p w_p ll_sum: the pixel weights of iodine_set_pixel_weights enter here), [1] like.s1, [2] like.s2, then per k: g1.s1, g1.s2, g2.s1, g2.s2, loo.s1, loo.s2
-template <int K, bool STRICT>
+// JOINT: option joint_likelihood, the form of the per-pixel terms (pixel_terms.h) - here and in every kernel below that takes it
+template <int K, bool STRICT, bool JOINT>
 __global__ __launch_bounds__(PIX_BLOCK)
 void pixel_pass1_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec, float4* __restrict__ g,
                         double* __restrict__ part, int P, int ppb, float inv2s2, float invs2, float lconst)
@@ -63,7 +64,7 @@ void pixel_pass1_kernel(const float4* __restrict__ x4, const float4* __restrict_
     for (int p = blk * ppb + tid; p < pend; p += PIX_BLOCK) {
         PixelTerms<K> t;
         const float4 xv = x4[(size_t)b * P + p];
-        pixel_terms<K, STRICT>(xv, dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
+        pixel_terms<K, STRICT, JOINT>(xv, dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
         float tg = 0.f;
 #pragma unroll
         for (int k = 0; k < K; ++k) tg += t.m[k] * t.g2[k];
@@ -200,7 +201,7 @@ void pixel_finalize_elbo_kernel(const double* __restrict__ part, int nblk, int K
 //   enc_sh[b][p][8]  = image rgb, LN(pixel likelihood), coordinate x, coordinate y, 0, 0
 // (294 -> 176 + 17 MB per iteration at cfg3; the shared part is convolved once per image instead of once per slot).
 // STABLE: option stable_encoding, channel 8 as the max-subtracted softmax (mask_post, pixel_terms.h); false: the reference's p_k / sum p_j
-template <int K, bool SPLIT, bool STRICT, bool STABLE>
+template <int K, bool SPLIT, bool STRICT, bool STABLE, bool JOINT>
 __global__ __launch_bounds__(PIX_BLOCK)
 void pixel_pass2_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec,
                         const float* __restrict__ lnstat, const float* __restrict__ lin, float* __restrict__ enc,
@@ -228,7 +229,7 @@ void pixel_pass2_kernel(const float4* __restrict__ x4, const float4* __restrict_
         const int p = p0 + min(lane, nvalid - 1);                          // idle lanes recompute the last pixel
         PixelTerms<K> t;
         const float4 xv = x4[(size_t)b * P + p];
-        pixel_terms<K, STRICT>(xv, dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
+        pixel_terms<K, STRICT, JOINT>(xv, dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
         float smax;
         const float psum = mask_post_den<K, STABLE>(t, smax);
         const float cx = lin[p % S], cy = lin[p / S];
@@ -301,7 +302,7 @@ void pixel_pass2_kernel(const float4* __restrict__ x4, const float4* __restrict_
 // A kernel of its own (the per-pixel terms once more, no stores but one double per block), so that pass 1 - its 6 K + 3 statistics, its
 // LDS and its registers - is the same code with the option off.  part[b][blk] = sum over the block's pixels of sigma_grad_term, the
 // per-thread fp32 partials (two pixels) added in fp64 in the fixed order pass 1 uses.
-template <int K, bool STRICT>
+template <int K, bool STRICT, bool JOINT>
 __global__ __launch_bounds__(PIX_BLOCK)
 void pixel_sigma_grad_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec, double* __restrict__ part, int P, int ppb,
                              float inv2s2, float invs2, float lconst)
@@ -313,7 +314,7 @@ void pixel_sigma_grad_kernel(const float4* __restrict__ x4, const float4* __rest
     for (int p = blk * ppb + tid; p < pend; p += PIX_BLOCK) {
         PixelTerms<K> t;
         const float4 xv = x4[(size_t)b * P + p];
-        pixel_terms<K, STRICT>(xv, dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
+        pixel_terms<K, STRICT, JOINT>(xv, dec_b, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
         acc += sigma_grad_term<K>(xv, t);
     }
     __shared__ float s_part[PIX_BLOCK];
@@ -400,21 +401,22 @@ void final_out_kernel(const float4* __restrict__ dec, float* __restrict__ pred, 
 int pixel_blocks_per_image(int P) { return (P + 2 * PIX_BLOCK - 1) / (2 * PIX_BLOCK); }   // 2 pixels / thread
 
 hipError_t launch_pixel_pass1(hipStream_t st, const float* x4, const float* dec, float* g, double* part, int B,
-                              int K, int P, float sigma, int strict)
+                              int K, int P, float sigma, int strict, int joint)
 {
     IOD_XSKIP(8);
     const int nblk = pixel_blocks_per_image(P), ppb = (P + nblk - 1) / nblk;
     const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
     switch (K) {
+#define P1(KK, ST, JT) hipLaunchKernelGGL((pixel_pass1_kernel<KK, ST, JT>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
+            (const float4*)x4, (const float4*)dec, (float4*)g, part, P, ppb, inv2s2, invs2, lconst)
 #define CASE(KK) case KK: \
-        if (strict) hipLaunchKernelGGL((pixel_pass1_kernel<KK, true>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
-            (const float4*)x4, (const float4*)dec, (float4*)g, part, P, ppb, inv2s2, invs2, lconst); \
-        else hipLaunchKernelGGL((pixel_pass1_kernel<KK, false>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
-            (const float4*)x4, (const float4*)dec, (float4*)g, part, P, ppb, inv2s2, invs2, lconst); \
+        if (joint) { if (strict) P1(KK, true, true); else P1(KK, false, true); } \
+        else { if (strict) P1(KK, true, false); else P1(KK, false, false); } \
         break;
         FOR_EACH_K(CASE)
 #undef CASE
+#undef P1
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -422,21 +424,22 @@ hipError_t launch_pixel_pass1(hipStream_t st, const float* x4, const float* dec,
 
 // part: B x pixel_blocks_per_image(P) doubles of scratch; out: one float, d LL / d sigma of this evaluation (batch mean, pixel weights in)
 hipError_t launch_pixel_sigma_grad(hipStream_t st, const float* x4, const float* dec, double* part, float* out, int B, int K, int P,
-                                   double sigma_d, int strict)
+                                   double sigma_d, int strict, int joint)
 {
     const int nblk = pixel_blocks_per_image(P), ppb = (P + nblk - 1) / nblk;
     const float sigma = (float)sigma_d;
     const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
     switch (K) {
+#define SG(KK, ST, JT) hipLaunchKernelGGL((pixel_sigma_grad_kernel<KK, ST, JT>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
+            (const float4*)x4, (const float4*)dec, part, P, ppb, inv2s2, invs2, lconst)
 #define CASE(KK) case KK: \
-        if (strict) hipLaunchKernelGGL((pixel_sigma_grad_kernel<KK, true>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
-            (const float4*)x4, (const float4*)dec, part, P, ppb, inv2s2, invs2, lconst); \
-        else hipLaunchKernelGGL((pixel_sigma_grad_kernel<KK, false>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
-            (const float4*)x4, (const float4*)dec, part, P, ppb, inv2s2, invs2, lconst); \
+        if (joint) { if (strict) SG(KK, true, true); else SG(KK, false, true); } \
+        else { if (strict) SG(KK, true, false); else SG(KK, false, false); } \
         break;
         FOR_EACH_K(CASE)
 #undef CASE
+#undef SG
         default: return hipErrorInvalidValue;
     }
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -456,7 +459,7 @@ hipError_t launch_pixel_finalize_elbo(hipStream_t st, const double* part, int B,
 
 hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec, const float* lnstat,
                               const float* lin, float* enc, int B, int K, int S, float sigma, float* enc_sh, unsigned chmask, int strict,
-                              int stable)
+                              int stable, int joint)
 {
     IOD_XSKIP(8);
     const int P = S * S;
@@ -464,8 +467,9 @@ hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec,
     const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
     switch (K) {
-#define P2S(KQ, SP, ST, SB) hipLaunchKernelGGL((pixel_pass2_kernel<KQ, SP, ST, SB>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
+#define P2J(KQ, SP, ST, SB, JT) hipLaunchKernelGGL((pixel_pass2_kernel<KQ, SP, ST, SB, JT>), dim3(nblk, B), dim3(PIX_BLOCK), 0, st, \
             (const float4*)x4, (const float4*)dec, lnstat, lin, enc, enc_sh, P, S, ppb, inv2s2, invs2, lconst, chmask)
+#define P2S(KQ, SP, ST, SB) do { if (joint) P2J(KQ, SP, ST, SB, true); else P2J(KQ, SP, ST, SB, false); } while (0)
 #define P2(KQ, SP, ST) do { if (stable) P2S(KQ, SP, ST, true); else P2S(KQ, SP, ST, false); } while (0)
 #define CASE(KK) case KK: \
         if (enc_sh) { if (strict) P2(KK, true, true); else P2(KK, true, false); } \
@@ -475,6 +479,7 @@ hipError_t launch_pixel_pass2(hipStream_t st, const float* x4, const float* dec,
 #undef CASE
 #undef P2
 #undef P2S
+#undef P2J
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

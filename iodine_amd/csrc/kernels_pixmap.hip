@@ -25,7 +25,7 @@
 
 #define PMAP_BLOCK 256
 
-template <int K, bool STRICT>
+template <int K, bool STRICT, bool JOINT>
 __global__ __launch_bounds__(PMAP_BLOCK)
 void pixel_like_maps_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec, float* __restrict__ ll, float* __restrict__ kll,
                             int P, float inv2s2, float lconst)
@@ -50,6 +50,29 @@ void pixel_like_maps_kernel(const float4* __restrict__ x4, const float4* __restr
     const float rden = pt_rcp<STRICT>(den);
 #pragma unroll
     for (int k = 0; k < K; ++k) lm[k] = logf(lm[k] * rden + 1e-12f);
+    if constexpr (JOINT) {
+        // option joint_likelihood: kll as below, ll (B,1,P) = logsumexp_k(log(m_k + 1e-12) + sum_c l_kc), s_k summed in channel order
+        float sk[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) sk[k] = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float d = xs[c] - mu[k][c];
+                const float l = -(d * d) * inv2s2 + lconst;
+                if (kll) kll[(((size_t)b * K + k) * 3 + c) * P + p] = l;
+                sk[k] += l;
+            }
+        float amax = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < K; ++k) { sk[k] += lm[k]; amax = fmaxf(amax, sk[k]); }
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) s += pt_exp_bounded<STRICT>(sk[k] - amax);
+        if (ll) ll[(size_t)b * P + p] = amax + logf(s);
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float a[K], amax = -INFINITY;
@@ -70,7 +93,7 @@ void pixel_like_maps_kernel(const float4* __restrict__ x4, const float4* __restr
 
 // gx + b * gx_bs: the (3, P) planes of image b; gw + b * gw_bs: its (P) plane.  The strides let one frame of a batch-first clip (B, F, 3, P)
 // be written in place.
-template <int K, bool STRICT>
+template <int K, bool STRICT, bool JOINT>
 __global__ __launch_bounds__(PMAP_BLOCK)
 void pixel_input_grad_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec, float* __restrict__ gx, size_t gx_bs,
                              float* __restrict__ gw, size_t gw_bs, int P, float inv2s2, float invs2, float lconst, float coef, int first_x,
@@ -81,7 +104,7 @@ void pixel_input_grad_kernel(const float4* __restrict__ x4, const float4* __rest
     if (p >= P) return;
     PixelTerms<K> t;
     const float4 xv = x4[(size_t)b * P + p];
-    pixel_terms<K, STRICT>(xv, dec + (size_t)b * K * P, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
+    pixel_terms<K, STRICT, JOINT>(xv, dec + (size_t)b * K * P, (size_t)P, (size_t)p, inv2s2, invs2, lconst, t);
     if (gx) {
         float* o = gx + (size_t)b * gx_bs + p;
 #pragma unroll
@@ -103,7 +126,7 @@ void pixel_input_grad_kernel(const float4* __restrict__ x4, const float4* __rest
 #define FOR_EACH_K(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 
 hipError_t launch_pixel_like_maps(hipStream_t st, const float* x4, const float* dec, float* ll, float* kll, int B, int K, int P, float sigma,
-                                  int strict)
+                                  int strict, int joint)
 {
     if (!x4 || !dec || B < 1 || P < 1) return hipErrorInvalidValue;
     if (!ll && !kll) return hipSuccess;
@@ -111,19 +134,21 @@ hipError_t launch_pixel_like_maps(hipStream_t st, const float* x4, const float* 
     const float inv2s2 = 1.f / (2.f * sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
     switch (K) {
+#define LM(KK, ST, JT) hipLaunchKernelGGL((pixel_like_maps_kernel<KK, ST, JT>), grid, dim3(PMAP_BLOCK), 0, st, (const float4*)x4, (const float4*)dec, ll, kll, P, inv2s2, lconst)
 #define CASE(KK) case KK: \
-        if (strict) hipLaunchKernelGGL((pixel_like_maps_kernel<KK, true>), grid, dim3(PMAP_BLOCK), 0, st, (const float4*)x4, (const float4*)dec, ll, kll, P, inv2s2, lconst); \
-        else hipLaunchKernelGGL((pixel_like_maps_kernel<KK, false>), grid, dim3(PMAP_BLOCK), 0, st, (const float4*)x4, (const float4*)dec, ll, kll, P, inv2s2, lconst); \
+        if (joint) { if (strict) LM(KK, true, true); else LM(KK, false, true); } \
+        else { if (strict) LM(KK, true, false); else LM(KK, false, false); } \
         break;
         FOR_EACH_K(CASE)
 #undef CASE
+#undef LM
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
 hipError_t launch_pixel_input_grad(hipStream_t st, const float* x4, const float* dec, float* gx, size_t gx_bs, float* gw, size_t gw_bs, int B,
-                                   int K, int P, float sigma, int strict, float coef, int first_x, int first_w)
+                                   int K, int P, float sigma, int strict, float coef, int first_x, int first_w, int joint)
 {
     if (!x4 || !dec || B < 1 || P < 1) return hipErrorInvalidValue;
     if (!gx && !gw) return hipSuccess;
@@ -131,12 +156,14 @@ hipError_t launch_pixel_input_grad(hipStream_t st, const float* x4, const float*
     const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
     switch (K) {
+#define IG(KK, ST, JT) hipLaunchKernelGGL((pixel_input_grad_kernel<KK, ST, JT>), grid, dim3(PMAP_BLOCK), 0, st, (const float4*)x4, (const float4*)dec, gx, gx_bs, gw, gw_bs, P, inv2s2, invs2, lconst, coef, first_x, first_w)
 #define CASE(KK) case KK: \
-        if (strict) hipLaunchKernelGGL((pixel_input_grad_kernel<KK, true>), grid, dim3(PMAP_BLOCK), 0, st, (const float4*)x4, (const float4*)dec, gx, gx_bs, gw, gw_bs, P, inv2s2, invs2, lconst, coef, first_x, first_w); \
-        else hipLaunchKernelGGL((pixel_input_grad_kernel<KK, false>), grid, dim3(PMAP_BLOCK), 0, st, (const float4*)x4, (const float4*)dec, gx, gx_bs, gw, gw_bs, P, inv2s2, invs2, lconst, coef, first_x, first_w); \
+        if (joint) { if (strict) IG(KK, true, true); else IG(KK, false, true); } \
+        else { if (strict) IG(KK, true, false); else IG(KK, false, false); } \
         break;
         FOR_EACH_K(CASE)
 #undef CASE
+#undef IG
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -3,7 +3,7 @@
 // running mean / M2 of the rendered image and of the masks, the count of samples in which each slot wins the pixel, and the per-image
 // log-likelihood of every sample.  No sample's NCHW planes are ever written.
 //
-// predictive_accum_kernel<K, STRICT, HAS_X>: grid (ceil(P / PIX_BLOCK), B), one thread owns one pixel of one image for ALL n_s samples of
+// predictive_accum_kernel<K, STRICT, HAS_X, JOINT>: grid (ceil(P / PIX_BLOCK), B), one thread owns one pixel of one image for ALL n_s samples of
 // the launch (block-uniform, in the arguments), no atomics, no LDS except the block sum of the likelihood.  Per sample, in sample order:
 //   * K float4 (pre-sigmoid rgb + logit, [n_s B K][P][4], sample-major) at 16 B per lane, consecutive lanes on consecutive pixels, rendered
 //     with final_out_kernel's arithmetic operation for operation - max over k, expf(w - mx), den in k order, one reciprocal, m[k] *= rden,
@@ -15,7 +15,7 @@
 //     values of pred and the K of mask (IEEE division, no contraction: the update is the same code whatever the chunking);
 //   * votes[b][k*][p] += 1 for the arg-max slot of the sample's mask, strict `>` from -inf upwards like slot_table_kernel: the lowest
 //     index wins a tie, a NaN never wins;
-//   * HAS_X: pixel_terms_core<K, STRICT> on the packed image {r, g, b, w}; w_p ll_sum - what pass 1 sums - goes through a wave sum and a
+//   * HAS_X: pixel_terms_core<K, STRICT, JOINT> (JOINT: option joint_likelihood, the form of ll_sum) on the packed image {r, g, b, w}; w_p ll_sum - what pass 1 sums - goes through a wave sum and a
 //     block sum in fp64 to part[s][b][block]; predictive_ll_kernel adds the blocks in block order and writes ll (S, B) in fp32.
 // The moment state lives in the OUTPUT buffers: a launch whose first sample is not sample 0 reads it, every launch writes it back, and the
 // update is strictly sequential in the sample index, so the result does not depend on how the samples are cut into launches.  Up to
@@ -39,7 +39,7 @@ IOD_DEVINL void welford_step(float v, float n, float& mean, float& m2)
     m2 = m2 + d0 * (v - mean);
 }
 
-template <int K, bool STRICT, bool HAS_X>
+template <int K, bool STRICT, bool HAS_X, bool JOINT>        // JOINT: option joint_likelihood (pixel_terms.h), with HAS_X only
 __global__ __launch_bounds__(PIX_BLOCK)
 void predictive_accum_kernel(const float4* __restrict__ dec, const float4* __restrict__ x4, int B, int P, int s0, int n_s,
                              float* pred_mean, float* pred_m2, float* mask_mean, float* mask_m2, int* votes,
@@ -119,7 +119,7 @@ void predictive_accum_kernel(const float4* __restrict__ dec, const float4* __res
         }
         if constexpr (HAS_X) {
             PixelTerms<K> t;
-            pixel_terms_core<K, STRICT>(xv, d, inv2s2, invs2, lconst, t);
+            pixel_terms_core<K, STRICT, JOINT>(xv, d, inv2s2, invs2, lconst, t);
             double v = valid ? (double)(xv.w * t.ll_sum) : 0.0;
             for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
             if ((tid & 63) == 0) s_red[s & 1][tid >> 6] = v;
@@ -186,7 +186,7 @@ hipError_t launch_predictive_sample(hipStream_t st, const float* pm, const float
 // of scratch and ll = n_s B floats, the chunk's rows of ll (S,B).
 hipError_t launch_predictive_accum(hipStream_t st, const float* dec, const float* x4, int B, int K, int P, int s0, int n_s, float* pred_mean,
                                    float* pred_m2, float* mask_mean, float* mask_m2, int* votes, double* part, float* ll, float sigma,
-                                   int strict)
+                                   int strict, int joint)
 {
     if (!pred_mean || !pred_m2 || !mask_mean || !mask_m2 || !votes || n_s < 1 || s0 < 0 || B < 1 || B > 65535) return hipErrorInvalidValue;
     if (x4 && (!part || !ll)) return hipErrorInvalidValue;
@@ -195,10 +195,12 @@ hipError_t launch_predictive_accum(hipStream_t st, const float* dec, const float
     const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
     switch (K) {
-#define PA(KK, ST, HX) hipLaunchKernelGGL((predictive_accum_kernel<KK, ST, HX>), grid, dim3(PIX_BLOCK), 0, st, (const float4*)dec, \
+#define PA(KK, ST, HX, JT) hipLaunchKernelGGL((predictive_accum_kernel<KK, ST, HX, JT>), grid, dim3(PIX_BLOCK), 0, st, (const float4*)dec, \
         (const float4*)x4, B, P, s0, n_s, pred_mean, pred_m2, mask_mean, mask_m2, votes, part, inv2s2, invs2, lconst)
 #define CASE(KK) case KK: \
-        if (!x4) PA(KK, false, false); else if (strict) PA(KK, true, true); else PA(KK, false, true); \
+        if (!x4) PA(KK, false, false, false); \
+        else if (joint) { if (strict) PA(KK, true, true, true); else PA(KK, false, true, true); } \
+        else { if (strict) PA(KK, true, true, false); else PA(KK, false, true, false); } \
         break;
         FOR_EACH_K(CASE)
 #undef CASE

@@ -49,8 +49,9 @@ IOD_DEVINL void l0_store12(unsigned char* dst, const float (&v)[12], float scale
     *reinterpret_cast<uint4*>(dst + 32) = make_uint4(lo[2], lo[3], lo[4], lo[5]);
 }
 
-template <int K, bool ALLCH, bool STABLE>                    // ALLCH: every encoding channel present (chmask = 0x1ffff) - no per-channel selects
+template <int K, bool ALLCH, bool STABLE, bool JOINT>        // ALLCH: every encoding channel present (chmask = 0x1ffff) - no per-channel selects
                                                              // STABLE: option stable_encoding (mask_post, pixel_terms.h)
+                                                             // JOINT: option joint_likelihood (pixel_terms_core, pixel_terms.h)
 __global__ __launch_bounds__(448)
 void refine_l0_fused_kernel(const float4* __restrict__ x4, const float4* __restrict__ dec, const float* __restrict__ lnstat,
                             const float* __restrict__ lin, const uint2* __restrict__ wk, const float* __restrict__ wkmeta,
@@ -295,7 +296,7 @@ void refine_l0_fused_kernel(const float4* __restrict__ x4, const float4* __restr
                     }
                     tm.like = xv.x;
 #else
-                    pixel_terms_core<K>(xv, dv, inv2s2, invs2, lconst, tm);
+                    pixel_terms_core<K, false, JOINT>(xv, dv, inv2s2, invs2, lconst, tm);
 #endif
                     psum = mask_post_den<K, STABLE>(tm, smax);
                 }
@@ -348,15 +349,15 @@ void refine_l0_fused_kernel(const float4* __restrict__ x4, const float4* __restr
 #endif
 }
 
-template <int K, bool STABLE>
+template <int K, bool STABLE, bool JOINT>
 hipError_t l0_launch(hipStream_t st, const float* x4, const float* dec, const float* lnstat, const float* lin, const void* wk, const float* wkmeta,
                      const void* ws, const float* wsmeta, const float* bias, float* out, float* enck, float* encs, int B, int S, float sigma,
                      unsigned chmask)
 {
     constexpr size_t lds = (size_t)2 * (K + 1) * L0_PLB + 16 + (size_t)3 * (K + 1) * 64 + 64 * 4 + 64 * 4 + 64;
     static std::atomic<unsigned> attr_devs{0}, attr_devs2{0};
-    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, true, STABLE>, (int)lds, attr_devs); e != hipSuccess) return e;
-    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, false, STABLE>, (int)lds, attr_devs2); e != hipSuccess) return e;
+    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, true, STABLE, JOINT>, (int)lds, attr_devs); e != hipSuccess) return e;
+    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, false, STABLE, JOINT>, (int)lds, attr_devs2); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int Sc = S / 2, nunits = B * (Sc / 16) * (Sc / 2);
@@ -364,10 +365,10 @@ hipError_t l0_launch(hipStream_t st, const float* x4, const float* dec, const fl
     const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
     if ((chmask & 0x1ffffu) == 0x1ffffu)
-        hipLaunchKernelGGL((refine_l0_fused_kernel<K, true, STABLE>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
+        hipLaunchKernelGGL((refine_l0_fused_kernel<K, true, STABLE, JOINT>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
                            (const uint2*)wk, wkmeta, (const uint2*)ws, wsmeta, bias, out, enck, encs, S, nunits, inv2s2, invs2, lconst, chmask);
     else
-        hipLaunchKernelGGL((refine_l0_fused_kernel<K, false, STABLE>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
+        hipLaunchKernelGGL((refine_l0_fused_kernel<K, false, STABLE, JOINT>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
                            (const uint2*)wk, wkmeta, (const uint2*)ws, wsmeta, bias, out, enck, encs, S, nunits, inv2s2, invs2, lconst, chmask);
 #ifdef IODINE_TILE_PROF
     {
@@ -399,16 +400,18 @@ bool refine_l0_fused_ok(int S, int c, int K) { return c == 64 && S >= 32 && S % 
 // enck / encs (both or neither): also write the split encoding (pixel_pass2's layout) - training.
 hipError_t launch_refine_l0_fused(hipStream_t st, const float* x4, const float* dec, const float* lnstat, const float* lin, const void* wk,
                                   const float* wkmeta, const void* ws, const float* wsmeta, const float* bias, float* out, float* enck,
-                                  float* encs, int B, int K, int S, int c, float sigma, unsigned chmask, int stable)
+                                  float* encs, int B, int K, int S, int c, float sigma, unsigned chmask, int stable, int joint)
 {
     IOD_XSKIP(512);
     if (!refine_l0_fused_ok(S, c, K) || (enck == nullptr) != (encs == nullptr)) return hipErrorInvalidValue;
     switch (K) {
+#define L0_ARGS st, x4, dec, lnstat, lin, wk, wkmeta, ws, wsmeta, bias, out, enck, encs, B, S, sigma, chmask
 #define L0_CASE(KK) case KK: \
-        return stable ? l0_launch<KK, true>(st, x4, dec, lnstat, lin, wk, wkmeta, ws, wsmeta, bias, out, enck, encs, B, S, sigma, chmask) \
-                      : l0_launch<KK, false>(st, x4, dec, lnstat, lin, wk, wkmeta, ws, wsmeta, bias, out, enck, encs, B, S, sigma, chmask);
+        if (joint) return stable ? l0_launch<KK, true, true>(L0_ARGS) : l0_launch<KK, false, true>(L0_ARGS); \
+        return stable ? l0_launch<KK, true, false>(L0_ARGS) : l0_launch<KK, false, false>(L0_ARGS);
         L0_CASE(1) L0_CASE(2) L0_CASE(3) L0_CASE(4) L0_CASE(5) L0_CASE(6) L0_CASE(7) L0_CASE(8) L0_CASE(9)
 #undef L0_CASE
+#undef L0_ARGS
         default: return hipErrorInvalidValue;
     }
 }

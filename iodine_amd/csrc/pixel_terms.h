@@ -14,6 +14,7 @@ struct PixelTerms {
     float pk[K];          // exp(sum_c l_kc)  (un-stabilised, as the reference)
     float ls[K];          // sum_c l_kc as rounded: the argument pk was built from (option stable_encoding, mask_post below)
     float ll_sum;         // sum_c logsumexp_k(log(m_k + 1e-12) + l_kc)   (raw, like pk / like / loo: they describe the scene, not the objective)
+                          // JOINT (option joint_likelihood): logsumexp_k(log(m_k + 1e-12) + sum_c l_kc), one mixture over the RGB vector
     float like;           // exp(ll_sum)
     float mix;            // sum_k m_k * pk_k
     float loo[K];         // leave-one-out likelihood (iodine.py:321-328), see pixel_terms
@@ -37,7 +38,13 @@ template <bool STRICT> IOD_DEVINL float pt_sigmoid(float v) { return pt_rcp<STRI
 // (iodine_set_pixel_weights; x_to_nhwc4_kernel writes an exact 1.f without weights).  LL = mean_b sum_p w_p sum_c logsumexp_k(..), so w
 // multiplies the two gradients and nothing else in here: it is folded into the per-channel 1 / s that both are built from (three
 // multiplies per pixel; by 1.f they are exact, so unweighted calls keep their bits).  The caller weights its own sum of ll_sum.
-template <int K, bool STRICT = false>
+// JOINT (option joint_likelihood; false: the reference's form above, a K-component mixture per colour channel): the paper's mixture over
+// the whole RGB vector, LL_p = log sum_k (m_k + 1e-12) prod_c N(x_c; mu_kc, sigma).  With s_k = sum_c l_kc (summed in the order of lsum,
+// so pk, ls, mix, loo and channel 8 keep their bits) and a_k = log(m_k + 1e-12) + s_k there is ONE softmax over the slots, not three:
+//   ll_sum = max_k a_k + log sum_k exp(a_k - max)      r_k = exp(a_k - max) / sum_j exp(a_j - max)
+//   g1[k][c] = w r_k (x_c - mu_kc) / sigma^2           g2[k] = w r_k / (m_k + 1e-12)
+// A template parameter, not an argument: the default form's instantiations are the code they were, registers and bits.
+template <int K, bool STRICT = false, bool JOINT = false>
 IOD_DEVINL void pixel_terms_core(const float4 xv, const float4 (&dv)[K], float inv2s2, float invs2, float lconst, PixelTerms<K>& t)
 {
     // No fp contraction in here: pass 1 (layer-norm statistics) and pass 2 (the values that get normalised) inline this function
@@ -72,28 +79,54 @@ IOD_DEVINL void pixel_terms_core(const float4 xv, const float4 (&dv)[K], float i
 #pragma unroll
     for (int k = 0; k < K; ++k) lsum[k] = 0.f;
     t.ll_sum = 0.f;
+    if constexpr (!JOINT) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < 3; ++c) {
+            float a[K];
+            float amax = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float d = xs[c] - t.mu[k][c];
+                const float l = -(d * d) * inv2s2 + lconst;
+                lsum[k] += l;
+                a[k] = lm[k] + l;
+                amax = fmaxf(amax, a[k]);
+            }
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < K; ++k) { a[k] = pt_exp_bounded<STRICT>(a[k] - amax); s += a[k]; }
+            t.ll_sum += amax + logf(s);
+            const float rs = pt_rcp<STRICT>(s) * xv.w;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float r = a[k] * rs;                         // w x responsibility of slot k for channel c
+                t.g1[k][c] = r * (xs[c] - t.mu[k][c]) * invs2;
+                t.g2[k] += r * rme[k];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const float d = xs[c] - t.mu[k][c];
+                lsum[k] += -(d * d) * inv2s2 + lconst;
+            }
         float a[K];
         float amax = -INFINITY;
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float d = xs[c] - t.mu[k][c];
-            const float l = -(d * d) * inv2s2 + lconst;
-            lsum[k] += l;
-            a[k] = lm[k] + l;
-            amax = fmaxf(amax, a[k]);
-        }
+        for (int k = 0; k < K; ++k) { a[k] = lm[k] + lsum[k]; amax = fmaxf(amax, a[k]); }
         float s = 0.f;
 #pragma unroll
         for (int k = 0; k < K; ++k) { a[k] = pt_exp_bounded<STRICT>(a[k] - amax); s += a[k]; }
-        t.ll_sum += amax + logf(s);
+        t.ll_sum = amax + logf(s);
         const float rs = pt_rcp<STRICT>(s) * xv.w;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const float r = a[k] * rs;                         // w x responsibility of slot k for channel c
-            t.g1[k][c] = r * (xs[c] - t.mu[k][c]) * invs2;
-            t.g2[k] += r * rme[k];
+            const float r = a[k] * rs;                             // w x responsibility of slot k for the pixel
+#pragma unroll
+            for (int c = 0; c < 3; ++c) t.g1[k][c] = r * (xs[c] - t.mu[k][c]) * invs2;
+            t.g2[k] = r * rme[k];
         }
     }
     t.like = expf(t.ll_sum);
@@ -152,6 +185,7 @@ IOD_DEVINL float mask_post(const PixelTerms<K>& t, int k, float smax, float den)
 
 // The statistic of option sigma_grad: d/dsigma [ w sum_c logsumexp_k(log(m_k + 1e-12) + l_kc) ] x sigma
 //   = sum_{k,c} g1_kc (x_c - mu_kc) - 3 w        (g1 already holds w r_kc (x_c - mu_kc) / sigma^2; the -3 w is d(-3 log sigma) x sigma)
+// The joint form has the same expression (its g1 holds w r_k (x_c - mu_kc) / sigma^2 and sum_k r_k = 1 as well).
 // The caller sums it over the pixels and divides by sigma once.
 template <int K>
 IOD_DEVINL float sigma_grad_term(const float4 xv, const PixelTerms<K>& t)
@@ -165,12 +199,12 @@ IOD_DEVINL float sigma_grad_term(const float4 xv, const PixelTerms<K>& t)
     return q - 3.f * xv.w;
 }
 
-template <int K, bool STRICT = false>
+template <int K, bool STRICT = false, bool JOINT = false>
 IOD_DEVINL void pixel_terms(const float4 xv, const float4* __restrict__ dec, size_t slot_stride, size_t p,
                             float inv2s2, float invs2, float lconst, PixelTerms<K>& t)
 {
     float4 dv[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) dv[k] = dec[(size_t)k * slot_stride + p];
-    pixel_terms_core<K, STRICT>(xv, dv, inv2s2, invs2, lconst, t);
+    pixel_terms_core<K, STRICT, JOINT>(xv, dv, inv2s2, invs2, lconst, t);
 }

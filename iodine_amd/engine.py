@@ -535,6 +535,10 @@ def make_parser():
     ap.add_argument('--stable-encoding', action='store_true',
                     help='mask_posterior channel of the refinement input as a max-subtracted softmax (model.stable_encoding): finite where the '
                          "reference's un-stabilised form is 0 / 0, which a small or shrinking sigma reaches")
+    ap.add_argument('--likelihood', choices=['per_channel', 'joint'], default=None,
+                    help="form of the pixel likelihood (model.likelihood): 'per_channel', the reference's K-component mixture for each colour "
+                         "channel, or 'joint', the paper's one mixture per pixel over the RGB vector; without the flag the model keeps its own (ARCH.LIKELIHOOD, else 'per_channel').  Not written into state_dict (which keeps "
+                         "the reference's layout): pass it again with --resume")
     ap.add_argument('--learn-input-gain', action='store_true',
                     help='learn a per-channel gain and offset applied to every batch before the model (six parameters in their own param '
                          'group, trained through the gradient into the image); saved as the checkpoint entry input_gain')
@@ -609,6 +613,10 @@ def main(argv=None):
         model.sigma = args.sigma
     model.beta, model.iter_weights = args.beta, args.iter_weights
     model.stable_encoding = args.stable_encoding
+    if args.likelihood is not None:
+        model.likelihood = args.likelihood
+    if rank == 0:
+        print('objective: likelihood {}, sigma {}, beta {}, iter_weights {}'.format(model.likelihood, model.sigma, model.beta, model.iter_weights))
     optimizer = make_optimizer(model, base_lr=args.lr, max_grad_norm=args.clip)
     log_sigma = make_log_sigma(model.sigma, device) if args.learn_sigma else None
     if args.resume:

@@ -66,6 +66,16 @@ evaluation, the two attributes of iodine.py:210-216 - an anomaly map, a per-slot
 raw under ``weights=`` (the weighted LL is ``sum_p w_p sum_c log_likelihood``), and they come from a kernel of their own, so their sum
 over channels and pixels matches the reported LL to float32 rounding, not bitwise.  ``False`` (default): both are None, no launch runs.
 
+Form of the likelihood: ``model.likelihood = 'per_channel'`` (default) is the reference's objective, a K-component mixture for each colour
+channel, ``LL_p = sum_c log sum_k (m_k + 1e-12) N(x_c; mu_kc, sigma)``; ``'joint'`` is the IODINE paper's, one mixture per pixel over the
+RGB vector, ``LL_p = log sum_k (m_k + 1e-12) prod_c N(x_c; mu_kc, sigma)`` (library option ``joint_likelihood``).  The attribute is read
+when a call starts, like ``sigma``, and everything that reports or differentiates a likelihood follows it: ``forward``, ``encode``,
+``reconstruct``, ``elbo``, ``weighted_elbo``, ``predictive``, ``elbo_terms``, the gradients into ``x``, ``weights=`` and a learnable
+``sigma``.  In joint mode ``model.log_likelihood`` is (B, 1, S, S) and ``dLL/dx`` / ``dLL/dw`` hold one responsibility ``r_k`` per slot in
+place of ``r_kc``; ``K_log_likelihood`` and the mask_posterior / leave-one-out channels of the refinement input (already joint over RGB in
+the reference) are the same.  A ``backward()`` of a pass that ran in the other form is refused by the library.  The mode is not part of
+``state_dict``.
+
 Multi-sample evaluation: ``model.predictive(x, samples=S)`` draws S latents from one posterior (default: the one the last ``reconstruct`` /
 ``encode`` / ``forward`` left) and returns a ``Predictive`` - per-pixel mean and variance of the rendered image and of the masks, per-slot vote
 counts with their arg-max and agreement, and with an image the per-sample log-likelihoods, the importance-weighted bound, the Monte-Carlo ELBO and
@@ -238,6 +248,9 @@ class IODINE(nn.Module):
         self.iter_weights = None        # loss weights of the T + 1 ELBO evaluations of forward: None / 'linspace', 'uniform', 'last', a sequence
         self.stable_encoding = False    # True: the mask_posterior channel of the refinement input as a max-subtracted softmax over the slots
                                         # (option stable_encoding) - finite where the reference's exp(s_k) / sum_j exp(s_j) is 0 / 0
+        self.likelihood = getattr(ARCH, 'LIKELIHOOD', 'per_channel')    # 'per_channel' (the reference: a K-component mixture for each colour
+                                        # channel) or 'joint' (the paper: one mixture per pixel over the RGB vector, option joint_likelihood);
+                                        # read when a call starts, by everything that reports or differentiates a likelihood
         self.use_layernorm = ARCH.LAYERNORM
         self.use_stop_gradient = getattr(ARCH, 'STOP_GRADIENT', False)
 
@@ -267,13 +280,29 @@ class IODINE(nn.Module):
         self.trajectory = None          # reconstruct(x, trajectory=True): dict of per-iteration outputs, else None
         self.objects = None             # reconstruct(x, objects=True): dict(table, segmentation, kl) of the returned decode, else None
         self.likelihood_maps = False    # True: every call that evaluates an ELBO also leaves the two per-pixel maps below (iodine.py:210-216)
-        self.log_likelihood = None      # (B, 3, S, S)    logsumexp_k(log(mask + 1e-12) + K_log_likelihood) of the last ELBO evaluation
+        self.log_likelihood = None      # (B, 3, S, S)    logsumexp_k(log(mask + 1e-12) + K_log_likelihood) of the last ELBO evaluation;
+                                        # likelihood 'joint': (B, 1, S, S), logsumexp_k(log(mask + 1e-12) + K_log_likelihood.sum(2))
         self.K_log_likelihood = None    # (B, K, 3, S, S) gaussian_log_likelihood(x[:, None], mean, sigma); both float32, detached, raw
 
         self._session = Session(self._cfg, self.named_parameters)      # the library handle and all that mirrors it (_session.py)
         self._last_ig = None            # (d / d x, d / d w) the last differentiable call accumulated, for its autograd node
         self._state = None              # _RefineState of the last encode / reconstruct: see refinement_state
         self._seed, self._draws = 0, 0  # Philox key (manual_seed) and stream id - one per eps draw - of the library's normal generator
+
+    LIKELIHOODS = ('per_channel', 'joint')
+
+    @property
+    def likelihood(self):
+        return self._likelihood
+
+    @likelihood.setter
+    def likelihood(self, value):
+        if value not in self.LIKELIHOODS:
+            raise ValueError(f"IODINE.likelihood must be 'per_channel' or 'joint', got {value!r}")
+        self._likelihood = value
+
+    def _joint(self):
+        return self._likelihood == 'joint'
 
     # ---- bookkeeping identical to the reference -------------------------------------------------
     def get_input_size(self):
@@ -386,6 +415,10 @@ class IODINE(nn.Module):
         Training at 2 is differentiated consistently, its gradients are outside the 1e-3 budget.  tests/f16x1_reference.py defines the mode."""
         if key == 'stable_encoding':                # the same switch as the attribute, which every call reads
             self.stable_encoding = bool(value)
+        if key == 'joint_likelihood':               # likewise: model.likelihood is what every call sends
+            if value not in (0, 1):
+                raise ValueError(f'IODINE.set_option: joint_likelihood must be 0 (per_channel) or 1 (joint), got {value!r}')
+            self.likelihood = 'joint' if value else 'per_channel'
         self._session.set_option(key, value)
 
     def profile_read(self, category: str, reset: bool = True):
@@ -446,7 +479,7 @@ class IODINE(nn.Module):
         self.z, self.mean, self.mask, self.mask_logits = z, mean, mask, logits
         self.log_likelihood = self.K_log_likelihood = None
         if self.likelihood_maps:                            # (one more per-pixel launch; off: none)
-            ll, kll = torch.empty((B, 3, S, S), **f), torch.empty((B, K, 3, S, S), **f)
+            ll, kll = torch.empty((B, 1 if self._session.joint else 3, S, S), **f), torch.empty((B, K, 3, S, S), **f)
             self._session.call('iodine_last_likelihood', B, ll, kll)
             self.log_likelihood, self.K_log_likelihood = ll, kll
         logger.update(image=x[0] if x.dim() == 4 else x[0, frame], pred=pred[0], kl=terms[1], likelihood=terms[2])
@@ -500,7 +533,7 @@ class IODINE(nn.Module):
                 _, _, self._state.h, self._state.c = merge(sts, (FIRST, FIRST, CAT0, CAT0))
             return merge(outs, (CAT0,) * 4)
         ses = self._bind(dev)
-        ses.prepare(dev, B, 0, K, T, frames, obj, stable_encoding=self.stable_encoding)
+        ses.prepare(dev, B, 0, K, T, frames, obj, stable_encoding=self.stable_encoding, joint_likelihood=self._joint())
         eps = self._eps(eps, B, dev)
         xs = ses.stage('x', x)
         L, S = self.dim_latent, self.img_size
@@ -785,7 +818,8 @@ class IODINE(nn.Module):
         if st is not None and st.h is None and st.serial is not None and st.serial == ses.call_serial:
             self.refinement_state()
         # sigma of this call; beta / iteration weights play no part
-        ses.prepare(dev, W, 0, K, T, objective=(sigma,) + tuple(ses.objective[1:]), stable_encoding=self.stable_encoding)
+        ses.prepare(dev, W, 0, K, T, objective=(sigma,) + tuple(ses.objective[1:]), stable_encoding=self.stable_encoding,
+                    joint_likelihood=self._joint())
         f = dict(device=dev, dtype=torch.float32)
         z = torch.empty((S, B, K, L), **f)
         pmean, pm2 = torch.empty((B, 3, Si, Si), **f), torch.empty((B, 3, Si, Si), **f)
@@ -905,7 +939,7 @@ class IODINE(nn.Module):
         dev, B = x.device, x.shape[0]
         input_grad = input_grad if save else 0
         ses = self._bind(dev)
-        ses.prepare(dev, B, 2 if save else 0, K, T, None, obj, save and sigma_grad, input_grad, self.stable_encoding)
+        ses.prepare(dev, B, 2 if save else 0, K, T, None, obj, save and sigma_grad, input_grad, self.stable_encoding, self._joint())
         eps = self._normals(eps, (B, K, self.dim_latent), dev)
         if pm is not None:
             pm = ses.stage('e.pm', pm.detach().to(torch.float32).contiguous())
@@ -1073,7 +1107,7 @@ class IODINE(nn.Module):
         K, T = _args.run_shape(self.K, self.n_iters)
         obj = _args.read_objective(self.sigma, self.beta, self.iter_weights, T)
         ses = self._bind(dev)
-        ses.prepare(dev, B, 1, K, T, x.shape[1] if x.dim() == 5 else 0, obj, sigma_grad, input_grad, self.stable_encoding)
+        ses.prepare(dev, B, 1, K, T, x.shape[1] if x.dim() == 5 else 0, obj, sigma_grad, input_grad, self.stable_encoding, self._joint())
         loss, elbo_iter = ses.out('t.loss', ()), ses.out('t.elbo', (T + 1, 3))
         xs, eps = ses.stage('x', x), ses.stage('eps', eps)
         ses.call_serial += 1
