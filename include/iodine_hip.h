@@ -820,7 +820,10 @@ void iodine_linspace_host(int n, float* out);
  * modes 5 / 6: split-fp16 stride-2 forward / data gradient of the refinement stack, modes 13 / 14: their exact-fp32 forms
  * (v_mfma_f32_32x32x2_f32, conv_precision 0), modes 15 / 16: the weight-stationary stride-2 conv c -> c of refinement layers 1 ..
  * (c = 64; split-fp16 / exact fp32), mode 17: mode 10 with ONE fp16 MFMA per product (conv_precision 2: same arguments, epilogues
- * and launch_cell_max side buffer). */
+ * and launch_cell_max side buffer).  Any other mode runs the gather kernel, as mode 1 does. */
+enum { IODINE_CONV_TILE_F32 = 0, IODINE_CONV_GATHER = 1, IODINE_CONV_TILE_F16 = 2, IODINE_CONV_S2_FWD = 5, IODINE_CONV_S2_DGRAD = 6, IODINE_CONV_WS = 9,
+       IODINE_CONV_WS_B = 10 /* the same kernel */, IODINE_CONV_WINO = 11 /* experiment libraries only */, IODINE_CONV_WS_F32 = 12,
+       IODINE_CONV_S2_FWD_F32 = 13, IODINE_CONV_S2_DGRAD_F32 = 14, IODINE_CONV_S2WS = 15, IODINE_CONV_S2WS_F32 = 16, IODINE_CONV_WS_1P = 17 };
 int iodine_op_conv3x3(void* stream, int mode, const float* in_nhwc, const float* w_oihw, const float* bias,
                       const float* aux, float* out_nhwc, int n, int ih, int iw, int w_o, int w_i, int cin_pad,
                       int cout, int stride, int epi, int transpose_flip);
@@ -830,12 +833,14 @@ int iodine_op_dec_out(void* stream, const float* in_nhwc, const float* w_oihw, c
  * (dec_out_stream_f16x3_kernel, per-cell max side buffer), 1 = row-streaming kernel without halo recompute
  * (dec_out_rows_f16x3_kernel, s in {32, 64, 128}), 2 = the tiled kernel without a side buffer, 3 = the row-streaming kernel on
  * exact fp32 MFMA (conv_precision 0). */
+enum { IODINE_DEC_OUT_TILES = 0, IODINE_DEC_OUT_ROWS = 1, IODINE_DEC_OUT_TILES_NOMAX = 2, IODINE_DEC_OUT_ROWS_F32 = 3 };
 int iodine_op_dec_out_f16x3(void* stream, const float* in_nhwc, const float* w_oihw, const float* bias, float* out_nhwc4,
                             int n, int s, int c, int variant);
 /* weight + bias gradient of a 3x3 conv (kernel-level tests): in_nhwc [n][s][s][ci_pad] (ci_real of them meaningful),
  * d_nhwc [n][so][so][co] with so = s (stride 1) or s/2 (stride 2); gw_oihw [co][ci_real][3][3] and gb [co] are
  * ACCUMULATED into.  Split-fp16 kernels (stride 1: decoder stack, stride 2: refinement stack); stride -2 selects the
  * exact-fp32 form of the stride-2 kernel (conv_precision 0). */
+enum { IODINE_WGRAD_STRIDE2_F32 = -2 };
 int iodine_op_conv3x3_wgrad(void* stream, const float* in_nhwc, const float* d_nhwc, float* gw_oihw, float* gb, int n,
                             int s, int ci_pad, int ci_real, int co, int stride);
 
@@ -854,6 +859,7 @@ int iodine_op_conv3x3_wgrad_f32(void* stream, const float* in_nhwc, const float*
  * Modes 0 / 2, tests only: elu | 0x100 | (mask << 9) hands the kernels the per-channel mask of input channels that can be non-zero (bit c =
  * channel c; ci <= 22), as the library does for the first refinement layer of an ARCH.ENCODING subset - channel groups that are zero in
  * the input AND the weights are skipped; the result must equal the unmasked call. */
+enum { IODINE_GEN_FWD = 0, IODINE_GEN_DGRAD = 1, IODINE_GEN_WGRAD = 2 };    /* mode of every generic-path entry below (the broadcast layer: 0 / 1) */
 int iodine_op_gen_conv(void* stream, int mode, const float* in_nhwc, const float* w_oihw, const float* bias, const float* aux,
                        float* out_nhwc, float* gb, int n, int si, int ci, int ldc, int co, int k, int s, int elu);
 
@@ -929,11 +935,13 @@ int iodine_op_pixel_encode(void* stream, const float* x_nchw, const float* w_or_
  * or B^T (tb).  forms 1 - 3: the fp32-MFMA kernel for A^T B with B [K][N] and M, N multiples of 32 -- 1: A [K][M]; 2: A row-major [M][K];
  * 3: A [K][M] and C written through the broadcast layer's weight map, row = latent channel, column = tap * mode_c + co ->
  * C[(co * ldc + row) * 9 + tap] with N = 9 mode_c and ldc = L + 2.  beta = 0: C is not read. */
+enum { IODINE_SGEMM_DISPATCH = 0, IODINE_SGEMM_MFMA = 1, IODINE_SGEMM_MFMA_ROWMAJOR = 2, IODINE_SGEMM_MFMA_L0MAP = 3 };
 int iodine_op_sgemm(void* stream, int form, int ta, int tb, int M, int N, int K, float alpha, const float* A, int lda, const float* B, int ldb,
                     float beta, float* C, int ldc, int mode_c);
 
 /* dst[c] += alpha * sum_r src[r * ld + c].  form 0: one block per column; form 1: the streaming form for tall contiguous matrices, only
  * where the library takes it (ld == cols, rows >= 8192, cols % 4 == 0, cols <= 256, 256 % (cols / 4) == 0). */
+enum { IODINE_COLSUM_BLOCK = 0, IODINE_COLSUM_TALL = 1 };
 int iodine_op_colsum(void* stream, int form, const float* src, int rows, int cols, int ld, float alpha, float* dst);
 
 /* one step of the refinement head (iodine.py:481-503, 642-643) from reference-shaped parameters.  in[14]: mlp.weight [H][C], mlp.bias [H],
@@ -941,6 +949,7 @@ int iodine_op_colsum(void* stream, int form, const float* src, int rows, int col
  * feat [N][PL][C], latent [N][4L], h_prev, c_prev [N][H].  out[10]: h, c [N][H], pm, plv [N][L] (IN / OUT: the update is added),
  * d_mean, d_logvar [N][L], pooled [N][C], s [N][H] (MLP pre-activation), gates [N][4H] (post-activation i, f, g, o), xin [N][H + 4L]; the last
  * six may be NULL.  H, L multiples of 4, C divides 256.  form 0: single launch; form 1: three launches (pre, gate GEMM, post). */
+enum { IODINE_HEAD_ONE_LAUNCH = 0, IODINE_HEAD_THREE_LAUNCHES = 1 };
 int iodine_op_refine_head(void* stream, int form, const float* const* in, float* const* out, int N, int PL, int C, int H, int L);
 
 /* which form the library runs at these (padded) widths: 0 single launch, 1 three launches, -1 refused at create time.  Host arithmetic. */
@@ -952,6 +961,7 @@ int iodine_op_refine_head_form(int C, int H, int L, int prefer_split);
  * step T - 1, or [T][N][L] with seed_stride = N L floats), gl (device scalar; NULL = 0), wtab (device, T + 1 loss weights), dh_in, dc_in [N][H].
  * out[7]: ddm, ddv [T][N][L], dgates [T][N][4H], ds [T][N][H], dpooled [T][N][Cr], optional dh_out, dc_out [N][H].  gl, the carries and
  * seed_stride need seed_m / seed_v.  B: the batch size in the loss weight -(i + 2) / (T + 1) / B. */
+enum { IODINE_BPTT_FUSED = 0, IODINE_BPTT_SEQUENCE = 1 };
 int iodine_op_head_bptt(void* stream, int form, const float* const* in, float* const* out, int T, int N, int B, int L, int H, int Cr,
                         long long seed_stride);
 

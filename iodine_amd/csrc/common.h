@@ -48,20 +48,8 @@ extern int g_iod_xskip;
 #define IOD_XSKIP(bit) do { } while (0)
 #endif
 
-// ---- packed conv-weight geometry (shared by host packer and kernels) ------------------
-// A 3x3 conv with CIN (padded) input channels is cut into chunks of CC channels.  Inside a
-// chunk the reduction index is organised in "quads" q = tap * (CC/4) + cig: 4 consecutive
-// input channels (cig*4 .. +3) at filter tap `tap` (= dy*3+dx).  Quads are consumed in
-// pairs by v_mfma_f32_32x32x2_f32: lanes 0-31 feed quad 2g, lanes 32-63 quad 2g+1, element
-// s of the quad at MFMA step s.  wpk[chunk][q][co] is a float4 over the quad's 4 channels.
-__host__ __device__ constexpr int conv_cc(int cin) { return cin == 20 ? 20 : (cin >= 16 ? 16 : cin); }
-__host__ __device__ constexpr int conv_nq(int cin) { return 9 * (conv_cc(cin) / 4); }
-__host__ __device__ constexpr int conv_nqp(int cin) { return (conv_nq(cin) + 1) & ~1; }
-__host__ __device__ constexpr int conv_nchunk(int cin) { return cin / conv_cc(cin); }
-// float4 elements in a packed weight tensor
-__host__ __device__ constexpr size_t conv_wpk_elems(int cin, int cout) {
-    return (size_t)conv_nchunk(cin) * conv_nqp(cin) * cout;
-}
+// ---- packed-weight geometry: the extent and index order of every weight pack (shared by host packers and kernels)
+#include "pack_geom.h"
 
 // EPI_L0ROWS: data-gradient form whose result is not stored but reduced to per-row left / interior / right sums
 // (rows_p[n][y][tile x][3][C]): the input of the broadcast layer's backward when nothing else needs d(pre-activation 0)
@@ -326,7 +314,6 @@ hipError_t launch_conv3x3_wgrad_f32_ws(hipStream_t st, const float* a, const flo
 // exact-fp32 weight gradient of the output conv c -> 4 in GEMM form (part: [nparts][9][c][4], part_b: [nbias_parts][4])
 hipError_t launch_dec_out_wgrad_f32(hipStream_t st, const float* a, const float* g, float* part, float* part_b, int N, int S, int c,
                                     int* nparts, int* nbias_parts);
-inline size_t conv_ws_wpk_bytes(int C) { return (size_t)(C / 16) * (C / 32) * 9 * 2 * 64 * 16; }
 inline size_t conv_ws_tmax_floats(int N, int S) { return (size_t)N * (S / 16) * (S / 8) * 4; }
 
 // tools/experiments/kernels_wino.hip (experiment, only in libraries built by tools/wino_variants.sh): Winograd F(2x2, 3x3) form
@@ -377,7 +364,7 @@ hipError_t launch_gen_conv_wgrad(hipStream_t st, const float* in, const float* d
 // kernels_gensplit.hip: split-fp16 (3 x v_mfma_f32_16x16x32_f16) form of the stride-1 conv C -> C, forward and data gradient (option
 // gen_conv_precision 1).  gen_split_cch: 32 / 16 = covered (k in {3, 5, 7}, C a multiple of 16, slice + halo fit the LDS), 0 = stays on fp32
 int gen_split_cch(int k, int C);
-size_t gen_split_pack_bytes(int k, int C);                  // one direction's slice images; the scales: C / 16 floats
+size_t gen_split_pack_bytes(int k, int C);                  // wpk_gen_split_bytes at the chunk width gen_split_cch chooses (0: not covered)
 hipError_t launch_gen_split_pack(hipStream_t st, const float* wt, int k, int C, int dgrad, void* dst, float* meta);
 hipError_t launch_gen_split_conv(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias, const float* aux,
                                  float* out, int N, int S, int C, int k, int elu);
@@ -414,7 +401,6 @@ hipError_t launch_conv3x3_s2_wgrad_f16x3(hipStream_t st, const float* a, const f
                                          int S, int ci_real, int nco, int* nparts, int* cipad, int* nbias_parts,
                                          const float* a2 = nullptr, int kdiv = 0, int f32 = 0);
 // kernels_refl0.hip: encoding (pixel_pass2's channels) + first refinement layer (conv k3 s2 17 -> 64, ELU) for all slots of an image
-size_t refine_l0_wpk_bytes(int O);
 bool refine_l0_fused_ok(int S, int c, int K);
 hipError_t launch_refine_l0_fused(hipStream_t st, const float* x4, const float* dec, const float* lnstat, const float* lin, const void* wk,
                                   const float* wkmeta, const void* ws, const float* wsmeta, const float* bias, float* out, float* enck,

@@ -132,48 +132,48 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
 {
     if (!h || !key) return IODINE_ERR_INVALID;
     if (h->shim) return pad_set_option(h, key, value);
-    if (!strcmp(key, "stop_after_iters")) { h->stop_after = (int)value; return IODINE_OK; }
-    if (!strcmp(key, "profile")) { h->profile = (int)value; return IODINE_OK; }
-    if (!strcmp(key, "graph")) { h->graph = value != 0; if (!h->graph) drop_graphs(h); return IODINE_OK; }
+    if (!strcmp(key, "stop_after_iters")) { h->opt.stop_after = (int)value; return IODINE_OK; }
+    if (!strcmp(key, "profile")) { h->opt.profile = (int)value; return IODINE_OK; }
+    if (!strcmp(key, "graph")) { h->opt.graph = value != 0; if (!h->opt.graph) drop_graphs(h); return IODINE_OK; }
 #ifdef IODINE_XSKIP_HOOK
     if (!strcmp(key, "xskip")) { g_iod_xskip = (int)value; return IODINE_OK; }       // timing-only ablation builds (common.h)
 #endif
-    if (!strcmp(key, "out_bwd_fused")) { h->out_bwd_fused = value != 0; return IODINE_OK; }
-    if (!strcmp(key, "save_for_backward")) { h->save_bwd = value != 0; return IODINE_OK; }
-    if (!strcmp(key, "fuse_l0")) { h->fuse_l0 = value != 0; return IODINE_OK; }
-    if (!strcmp(key, "sigma_grad")) { h->sigma_grad = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "out_bwd_fused")) { h->opt.out_bwd_fused = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "save_for_backward")) { h->opt.save_bwd = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "fuse_l0")) { h->opt.fuse_l0 = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "sigma_grad")) { h->opt.sigma_grad = value != 0; return IODINE_OK; }
     if (!strcmp(key, "input_grad")) {
         if (value != 0 && value != 1 && value != 2 && value != 3) return h->fail(IODINE_ERR_INVALID, "option input_grad: 0, 1 (image), 2 (pixel weights) or 3 (both)");
-        h->input_grad = (int)value;                    // (the next compute call re-plans the workspace: ensure_workspace keys on it)
+        h->opt.input_grad = (int)value;                    // (the next compute call re-plans the workspace: ensure_workspace keys on it)
         return IODINE_OK;
     }
-    if (!strcmp(key, "stable_encoding")) { h->stable_enc = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "stable_encoding")) { h->opt.stable_enc = value != 0; return IODINE_OK; }
     if (!strcmp(key, "joint_likelihood")) {
         if (value != 0 && value != 1) return h->fail(IODINE_ERR_INVALID, "option joint_likelihood: 0 (a mixture per colour channel, the reference) or 1 (one mixture per pixel over RGB)");
         // a saved pass ran in the other form and iodine_train_backward_frames decodes earlier evaluations again: it is discarded, not mixed
-        if (h->joint_ll != (int)value && (h->calls.fwd_done || h->calls.diff_kind)) { h->calls.saved_passes_gone(); h->calls.form_changed = true; }
-        h->joint_ll = (int)value;
+        if (h->opt.joint_ll != (int)value && (h->calls.fwd_done || h->calls.diff_kind)) { h->calls.saved_passes_gone(); h->calls.form_changed = true; }
+        h->opt.joint_ll = (int)value;
         return IODINE_OK;
     }
-    if (!strcmp(key, "refine_split")) { h->refine_split = value != 0; return IODINE_OK; }
-    if (!strcmp(key, "head_fused")) { h->head_fused = value != 0; return IODINE_OK; }
-    if (!strcmp(key, "refine_bwd_fused")) { h->refine_bwd_fused = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "refine_split")) { h->opt.refine_split = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "head_fused")) { h->opt.head_fused = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "refine_bwd_fused")) { h->opt.refine_bwd_fused = value != 0; return IODINE_OK; }
     if (!strcmp(key, "profile_stride")) {
         if (value < 1) return h->fail(IODINE_ERR_INVALID, "profile_stride must be >= 1");
-        h->profile_stride = (int)value; return IODINE_OK;
+        h->opt.profile_stride = (int)value; return IODINE_OK;
     }
-    if (!strcmp(key, "head_mfma")) { h->head_mfma = value != 0; return IODINE_OK; }
-    if (!strcmp(key, "refine_l0_fused")) { h->refine_l0_fused = value != 0; return IODINE_OK; }
-    if (!strcmp(key, "refine_ws")) { h->refine_ws = value != 0; return IODINE_OK; }
-    if (!strcmp(key, "dec_out_rows")) { h->dec_out_rows = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "head_mfma")) { h->opt.head_mfma = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "refine_l0_fused")) { h->opt.refine_l0_fused = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "refine_ws")) { h->opt.refine_ws = value != 0; return IODINE_OK; }
+    if (!strcmp(key, "dec_out_rows")) { h->opt.dec_out_rows = value != 0; return IODINE_OK; }
     if (!strcmp(key, "wgrad_accum")) {
-        if (h->wgrad_accum != (value != 0)) { h->buf = Buffers(); h->calls.arena_gone(); }   // the arena is re-planned
-        h->wgrad_accum = value != 0; return IODINE_OK;
+        if (h->opt.wgrad_accum != (value != 0)) { h->buf = Buffers(); h->calls.arena_gone(); }   // the arena is re-planned
+        h->opt.wgrad_accum = value != 0; return IODINE_OK;
     }
     if (!strcmp(key, "conv_variant")) {
         if (value != 1 && value != 6) return h->fail(IODINE_ERR_INVALID, "conv_variant must be 1 (LDS-tiled) or 6 (weight-stationary)");
-        if (((int)value == 6) != (h->variant == 6)) h->params_set = false;   // the other kernel's weight packs are not kept up to date
-        h->variant = (int)value;
+        if (((int)value == 6) != (h->opt.variant == 6)) h->params_set = false;   // the other kernel's weight packs are not kept up to date
+        h->opt.variant = (int)value;
         return IODINE_OK;
     }
     if (!strcmp(key, "conv_precision")) {
@@ -181,14 +181,14 @@ int iodine_set_option(iodine_handle* h, const char* key, double value)
             return h->fail(IODINE_ERR_INVALID, "conv_precision must be 0 (f32), 1 (f16x3) or 2 (f16x3 with single-product fp16 weight-stationary decoder convs)");
         // the other path's weight packs are not kept up to date (1 and 2 read the same packs; a switch between them invalidates the parameters
         // all the same, so that a saved forward pass is never finished at another precision)
-        if (h->precision != (int)value) h->params_set = false;
-        h->precision = (int)value;
+        if (h->opt.precision != (int)value) h->params_set = false;
+        h->opt.precision = (int)value;
         return IODINE_OK;
     }
     if (!strcmp(key, "gen_conv_precision")) {
         if (value != 0 && value != 1) return h->fail(IODINE_ERR_INVALID, "gen_conv_precision must be 0 (f32) or 1 (f16x3)");
-        if (h->gen_precision != (int)value) h->params_set = false;    // the split packs are built by iodine_set_params
-        h->gen_precision = (int)value;
+        if (h->opt.gen_precision != (int)value) h->params_set = false;    // the split packs are built by iodine_set_params
+        h->opt.gen_precision = (int)value;
         return IODINE_OK;
     }
     return h->fail(IODINE_ERR_INVALID, std::string("unknown option ") + key);
@@ -214,8 +214,8 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
     h->calls.compute_begins();                             // the arena is re-used: a saved training forward is gone
     hipStream_t st = (hipStream_t)stream;
     const int B = batch, N = B * h->K, T = h->T;
-    const bool partial = h->stop_after >= 0 && h->stop_after <= T;     // debug: stop before the final sample/decode
-    const int n_it = partial ? h->stop_after : T;
+    const bool partial = h->opt.stop_after >= 0 && h->opt.stop_after <= T;     // debug: stop before the final sample/decode
+    const int n_it = partial ? h->opt.stop_after : T;
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         const size_t eps_stride = (size_t)N * h->L;
@@ -227,7 +227,7 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
             HIPCHK(h, hipMemcpyAsync(b.h[0], state_in[2], sizeof(float) * (size_t)N * h->H, hipMemcpyDeviceToDevice, st));
             HIPCHK(h, hipMemcpyAsync(b.c[0], state_in[3], sizeof(float) * (size_t)N * h->H, hipMemcpyDeviceToDevice, st));
         } else
-            HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, h->L, h->H));
+            HIPCHK(h, launch_posterior_init(st, h->head.init_mean, h->head.init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, h->L, h->H));
         const size_t P = (size_t)h->P;
         for (int i = 0; i < n_it; ++i) {
             int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true);
@@ -243,7 +243,7 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
             // z = posterior.sample(); decode(z)   (iodine.py:103,110).  The decoder writes into the (now free) gradient
             // buffer so that buf.dec_out keeps the outputs of the LAST elbo() call: the reference's self.mean / self.mask
             // and its logger entries are those (iodine.py:226-239), not the final decode.
-            HIPCHK(h, launch_dec_v(st, b.pm, b.plv, eps + (size_t)T * eps_stride, nullptr, h->wcls, b.z[T], b.V, N, h->L, h->Cd));
+            HIPCHK(h, launch_dec_v(st, b.pm, b.plv, eps + (size_t)T * eps_stride, nullptr, h->dec.wcls, b.z[T], b.V, N, h->L, h->Cd));
             const int r = decoder_forward(h, st, N, b.z[T], b.g);
             if (r) return r;
             HIPCHK(h, launch_final_out(st, b.g, pred, mask, mean, nullptr, B, h->K, h->P));
@@ -268,7 +268,7 @@ int iodine_reconstruct_seq(iodine_handle* h, void* stream, int batch, const floa
     h->calls.last_elbo_batch = B;
     h->calls.state_iter = n_it;                                  // buf.h / buf.c [n_it]: the LSTM state after the last update (iodine_last_refine_state)
     // (host state, outside the graphed body) did this call leave the encoding in the workspace?  ref_conv_fwd: l0f && !keep_enc skips it
-    h->calls.enc_valid = n_it > 0 && (h->stop_after >= 0 || !ref_form(h).l0f);
+    h->calls.enc_valid = n_it > 0 && (h->opt.stop_after >= 0 || !ref_form(h).l0f);
     return IODINE_OK;
 }
 
@@ -301,7 +301,7 @@ int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, flo
     if (h && h->shim) return pad_decode(h, stream, batch, z, pred, mask, mean);
     int rc = decode_check(h, batch, z);
     if (rc) return rc;
-    const bool save = h->save_bwd != 0;                    // option save_for_backward: keep what iodine_decode_backward reads (workspace mode 2)
+    const bool save = h->opt.save_bwd != 0;                    // option save_for_backward: keep what iodine_decode_backward reads (workspace mode 2)
     rc = ensure_workspace(h, batch, save ? 2 : 0);
     if (rc) return rc;
     h->calls.compute_begins(true);                         // (a decode touches neither buf.h / buf.c nor the posterior)
@@ -313,7 +313,7 @@ int iodine_decode(iodine_handle* h, void* stream, int batch, const float* z, flo
         // and z kept in buf.z[0].  The launches are the same.
         float* out = save ? b.dec_out : b.g;
         if (save) HIPCHK(h, hipMemcpyAsync(b.z[0], z, sizeof(float) * (size_t)N * h->L, hipMemcpyDeviceToDevice, st));
-        HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, z, h->wcls, nullptr, b.V, N, h->L, h->Cd));
+        HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, z, h->dec.wcls, nullptr, b.V, N, h->L, h->Cd));
         const int r = decoder_forward(h, st, N, z, out);
         if (r) return r;
         HIPCHK(h, launch_final_out(st, out, pred, mask, mean, nullptr, batch, h->K, h->P));
@@ -345,7 +345,7 @@ int iodine_scene_edit(iodine_handle* h, void* stream, int batch, const float* z,
     Buffers& b = h->buf;
     const int K = h->K, L = h->L;
     const size_t P = (size_t)h->P;
-    HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, z, h->wcls, nullptr, b.V, batch * K, L, h->Cd));
+    HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, z, h->dec.wcls, nullptr, b.V, batch * K, L, h->Cd));
     if (int r = decoder_forward(h, st, batch * K, z, b.dec_out)) return r;
     if (base_pred || base_mask || base_mean) HIPCHK(h, launch_final_out(st, b.dec_out, base_pred, base_mask, base_mean, nullptr, batch, K, h->P));
     // chunks of consecutive edits with at most W * K replacements each (removals ride along: they need no decode)
@@ -363,7 +363,7 @@ int iodine_scene_edit(iodine_handle* h, void* stream, int batch, const float* z,
                 HIPCHK(h, hipMemcpyAsync(b.z[0] + (size_t)r * L, z_new + (size_t)e * L, sizeof(float) * (size_t)(f - e) * L, hipMemcpyDeviceToDevice, st));
                 r += f - e; e = f;
             }
-            HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, b.z[0], h->wcls, nullptr, b.V, rows, L, h->Cd));
+            HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, b.z[0], h->dec.wcls, nullptr, b.V, rows, L, h->Cd));
             if (int r = decoder_forward(h, st, rows, b.z[0], b.g)) return r;
         }
         for (int f0 = e0, r = 0; f0 < e1; f0 += SCENE_EDIT_MAX) {
@@ -415,16 +415,16 @@ int iodine_predictive(iodine_handle* h, void* stream, int batch, int n_samples, 
     if (used_spare) h->calls.enc_valid = false;
     const bool like = x && ll;                             // (x without ll: nothing to score)
     if (like) HIPCHK(h, launch_x_to_nhwc4(st, x, b.x4, B, h->P, 1, pw.w, 0));
-    const float *pm = post_mean ? post_mean : h->init_mean, *plv = post_mean ? post_logvar : h->init_logvar;
+    const float *pm = post_mean ? post_mean : h->head.init_mean, *plv = post_mean ? post_logvar : h->head.init_logvar;
     const int per_chunk = W / B;                           // >= 1 whole samples per chunk
     for (int s0 = 0; s0 < n_samples; s0 += per_chunk) {
         const int n_s = std::min(per_chunk, n_samples - s0);
         float* zc = z ? z + (size_t)s0 * N * L : b.z[0];  // (buf.z[0] holds W K rows)
         HIPCHK(h, launch_predictive_sample(st, pm, plv, eps + (size_t)s0 * N * L, zc, n_s, N, L, post_mean ? L : 0));
-        HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, zc, h->wcls, nullptr, b.V, n_s * N, L, h->Cd));
+        HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, zc, h->dec.wcls, nullptr, b.V, n_s * N, L, h->Cd));
         if (int r = decoder_forward(h, st, n_s * N, zc, b.g)) return r;
         PROF(h, st, "predictive", launch_predictive_accum(st, b.g, like ? b.x4 : nullptr, B, K, h->P, s0, n_s, s_pm, s_p2, s_mm, s_m2, s_vt, b.part,
-                                                         like ? ll + (size_t)s0 * B : nullptr, (float)h->obj.sigma, h->precision == 0, h->joint_ll));
+                                                         like ? ll + (size_t)s0 * B : nullptr, (float)h->obj.sigma, h->opt.precision == 0, h->opt.joint_ll));
     }
     return IODINE_OK;
 }
@@ -437,7 +437,7 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     const PixelWeights pw(h);                              // (one image per batch entry: weights (B, P) either way)
     int rc = elbo_check(h, batch, x, eps, post_mean, post_logvar);
     if (rc) return rc;
-    const bool save = h->save_bwd != 0;                    // option save_for_backward: keep what iodine_elbo_backward reads (workspace mode 2)
+    const bool save = h->opt.save_bwd != 0;                    // option save_for_backward: keep what iodine_elbo_backward reads (workspace mode 2)
     rc = ensure_workspace(h, batch, save ? 2 : 0);
     if (rc) return rc;
     h->calls.compute_begins();                             // (the initial posterior below zeroes buf.h[0] / c[0])
@@ -451,9 +451,9 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
             HIPCHK(h, hipMemcpyAsync(b.pm, post_mean, sizeof(float) * (size_t)N * h->L, hipMemcpyDeviceToDevice, st));
             HIPCHK(h, hipMemcpyAsync(b.plv, post_logvar, sizeof(float) * (size_t)N * h->L, hipMemcpyDeviceToDevice, st));
         } else {
-            HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, h->L, h->H));
+            HIPCHK(h, launch_posterior_init(st, h->head.init_mean, h->head.init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, h->L, h->H));
         }
-        const int r = elbo_and_gradients(h, st, B, eps, 0, false, false, 0.f, save && h->sigma_grad, save ? h->input_grad : 0, 1.f / (float)B);
+        const int r = elbo_and_gradients(h, st, B, eps, 0, false, false, 0.f, save && h->opt.sigma_grad, save ? h->opt.input_grad : 0, 1.f / (float)B);
         if (r) return r;
         if (terms) HIPCHK(h, hipMemcpyAsync(terms, b.scal, sizeof(float) * 3, hipMemcpyDeviceToDevice, st));
         // kept for iodine_elbo_backward: z (buf.z[0]), the activations, dec_out, d(B * ELBO) / d dec_out (buf.g), the posterior (buf.pm / plv)
@@ -467,8 +467,8 @@ int iodine_elbo(iodine_handle* h, void* stream, int batch, const float* x, const
     cs.last_elbo_iter = 0;
     cs.last_elbo_batch = B;
     if (save) { cs.diff_kind = 2; cs.diff_batch = B; cs.diff_init = post_mean == nullptr; cs.diff_obj = h->obj; }
-    cs.sgrad_n = save && h->sigma_grad ? 1 : 0;
-    cs.ig_bits = save ? h->input_grad : 0; cs.ig_frames = 0; cs.ig_wpf = 0;
+    cs.sgrad_n = save && h->opt.sigma_grad ? 1 : 0;
+    cs.ig_bits = save ? h->opt.input_grad : 0; cs.ig_frames = 0; cs.ig_wpf = 0;
     return IODINE_OK;
 }
 
@@ -499,13 +499,13 @@ int iodine_decode_backward(iodine_handle* h, void* stream, int batch, const floa
     auto body = [&]() -> int {
         Buffers& b = h->buf;
         if (flat_grads) HIPCHK(h, launch_zero_fill(st, h->gacc_arena, h->gacc_total));
-        PROF(h, st, "render_bwd", launch_render_bwd(st, b.dec_out, g_pred, g_mask, g_mean, b.g, B, h->K, h->P, h->precision == 0));
+        PROF(h, st, "render_bwd", launch_render_bwd(st, b.dec_out, g_pred, g_mask, g_mean, b.g, B, h->K, h->P, h->opt.precision == 0));
         float* dpre0 = nullptr;
         // ONE decoder pass with factor 1: data gradient down to the class sums of the broadcast layer, every decoder weight gradient on the way
         const int r = decoder_backward_data(h, st, N, &dpre0, flat_grads != nullptr, 1.f, 0, true);
         if (r) return r;
         if (dz)
-            HIPCHK(h, launch_dz_plain(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, h->L, h->Cd, dz, nullptr, nullptr, nullptr,
+            HIPCHK(h, launch_dz_plain(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen.ident : h->dec.wclsT, N, h->L, h->Cd, dz, nullptr, nullptr, nullptr,
                                       1.f, nullptr, nullptr, 1.f));
         return flat_grads ? diff_flat_out(h, st, nullptr, flat_grads, accumulate) : IODINE_OK;
     };
@@ -536,7 +536,7 @@ int iodine_elbo_backward(iodine_handle* h, void* stream, const float* grad_out_d
         const int r = decoder_backward_data(h, st, N, &dpre0, flat_grads != nullptr, 1.f / (float)B, 0, true);
         if (r) return r;
         // d ELBO / d lambda (iodine.py:193,220: batch means) into the slots the refinement loop uses for them
-        HIPCHK(h, launch_dz_plain(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT, N, h->L, h->Cd, nullptr, b.pm, b.plv, b.latent[0],
+        HIPCHK(h, launch_dz_plain(st, b.Rc, dec_path(h) == DEC_GENERIC ? h->gen.ident : h->dec.wclsT, N, h->L, h->Cd, nullptr, b.pm, b.plv, b.latent[0],
                                   1.f / (float)B, b.g_pm[0], b.g_plv[0], (float)obj.beta));
         if (flat_grads && h->calls.diff_init) {                  // lambda = init_mean / init_logvar repeated over (B, K): iodine.py:615-616
             HIPCHK(h, launch_colsum(st, b.g_pm[0], N, h->L, h->L, 1.f, h->gacc[ps.init_mean]));
@@ -626,7 +626,7 @@ int iodine_last_likelihood(iodine_handle* h, void* stream, int count, float* log
     // the image that evaluation scored: frame last_elbo_iter of a clip (x4 is frame-major), else the one image
     const float* x4 = b.x4 + (b.F > 1 ? (size_t)h->calls.last_elbo_iter * b.B * h->P * 4 : 0);
     HIPCHK(h, launch_pixel_like_maps((hipStream_t)stream, x4, b.dec_out, log_likelihood, k_log_likelihood, count, K, h->P, (float)h->obj.sigma,
-                                     h->precision == 0, h->joint_ll));
+                                     h->opt.precision == 0, h->opt.joint_ll));
     return IODINE_OK;
 }
 
@@ -635,7 +635,7 @@ int iodine_logger_scalars(iodine_handle* h, void* stream, float* out2)
     if (!h || !out2) return IODINE_ERR_INVALID;
     if (h->shim) return pad_logger_scalars(h, stream, out2);
     if (!h->params_set) return h->fail(IODINE_ERR_STATE, "iodine_set_params has not been called");
-    HIPCHK(h, launch_mean2((hipStream_t)stream, h->init_mean, h->init_logvar, h->Lreal > 0 ? h->Lreal : h->L, out2));
+    HIPCHK(h, launch_mean2((hipStream_t)stream, h->head.init_mean, h->head.init_logvar, h->Lreal > 0 ? h->Lreal : h->L, out2));
     return IODINE_OK;
 }
 

@@ -24,7 +24,7 @@ int reconstruct_check(iodine_handle* h, int batch, const float* x, const float* 
                  h->frames, h->T, h->T, h->T, h->S, h->S, h->S, h->S);
         return h->fail(IODINE_ERR_INVALID, m);
     }
-    if (traj && h->stop_after >= 0 && h->stop_after <= h->T)
+    if (traj && h->opt.stop_after >= 0 && h->opt.stop_after <= h->T)
         return h->fail(IODINE_ERR_INVALID, "iodine_reconstruct_seq: a trajectory has T + 1 entries, the last one the final decode - not "
                                            "available with option stop_after_iters (which skips it)");
     if (int rc = check_ready(h, batch)) return rc;

@@ -18,16 +18,32 @@ struct Arena {
     }
 };
 
+// several small device-to-device copies, transposes [R][Cc] -> [Cc][R] and sums of two vectors, collected and issued as ONE launch
+struct CopyBatch {
+    hipStream_t st;
+    MultiCopy mc;
+    explicit CopyBatch(hipStream_t s) : st(s) { mc.count = 0; }
+    hipError_t flush() { const hipError_t e = launch_multi_copy(st, mc); mc.count = 0; return e; }
+    hipError_t copy(float* dst, const float* src, size_t count, int op = 0, int cols = 0, const float* src2 = nullptr) {
+        if (mc.count == MCOPY_MAX) if (const hipError_t e = flush(); e != hipSuccess) return e;
+        mc.src[mc.count] = src; mc.src2[mc.count] = src2; mc.dst[mc.count] = dst; mc.n[mc.count] = (int)count; mc.op[mc.count] = op;
+        mc.cols[mc.count] = cols; ++mc.count;
+        return hipSuccess;
+    }
+    hipError_t transpose(float* dst, const float* src, int R, int Cc) { return copy(dst, src, (size_t)R * Cc, 1, Cc); }
+    hipError_t add2(float* dst, const float* a, const float* b2, int count) { return copy(dst, a, (size_t)count, 2, 0, b2); }
+};
+
 // bracket one launch expression with profiler events (no-op unless profiling is on)
 #define PROF(h, st, cat, expr)                                                       \
     do {                                                                             \
         hipEvent_t e0_ = nullptr, e1_ = nullptr;                                     \
         ProfCat* pc_ = nullptr;                                                      \
-        if ((h)->profile > 1) { pc_ = (h)->prof_cat(cat); pc_->seen_win++; }         \
-        else if ((h)->profile == 1 && !strncmp(cat, "conv_tile_", 10)) {             \
+        if ((h)->opt.profile > 1) { pc_ = (h)->prof_cat(cat); pc_->seen_win++; }         \
+        else if ((h)->opt.profile == 1 && !strncmp(cat, "conv_tile_", 10)) {             \
             pc_ = (h)->prof_cat(cat);                                                \
             pc_->seen_win++;                                                         \
-            if (pc_->seen++ % (unsigned long long)(h)->profile_stride) pc_ = nullptr;    \
+            if (pc_->seen++ % (unsigned long long)(h)->opt.profile_stride) pc_ = nullptr;    \
         }                                                                            \
         if (pc_) {                                                                   \
             if (pc_->used == pc_->ev.size()) {                                       \
@@ -117,7 +133,7 @@ std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, s
 template <typename F>
 int run_graphed(iodine_handle* h, hipStream_t st, const std::vector<uintptr_t>& key, F&& body)
 {
-    if (!h->graph || h->profile) return body();
+    if (!h->opt.graph || h->opt.profile) return body();
     if (!st) return h->fail(IODINE_ERR_INVALID, "option graph=1 needs a non-default stream (the legacy null stream cannot be captured)");
     for (auto& g : h->graphs)
         if (g.key == key) {

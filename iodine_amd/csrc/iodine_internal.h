@@ -133,17 +133,98 @@ struct CallState {
 };
 #pragma GCC visibility pop
 
+// A weight pack (pack_geom.h: extent and index order) with the meta block that holds its power-of-two scale (nullptr: an fp32 pack)
+struct Pack { void* data = nullptr; float* meta = nullptr; };
+
+// What iodine_set_option sets.  conv_precision / conv_variant / gen_conv_precision invalidate the parameters (the packs follow dec_path)
+struct Options {
+    int precision = 1;                          // 0: exact fp32 MFMA, 1: 3 x fp16 MFMA split (fp32-class accuracy), 2: hi.hi alone on DEC_WS_F16
+    int variant = 6;                            // split-fp16 stride-1 conv: 6 = weight-stationary persistent kernel (power-of-two image sizes;
+                                                // other sizes use 1), 1 = LDS-tiled 16x16 tiles (2 blocks/CU)
+    int gen_precision = 0;                      // gen_conv_precision 1 (kernels_gensplit.hip): the generic decoder's C -> C layers on split fp16
+    int out_bwd_fused = 1;                      // training: output conv data + weight gradient in one pass over the activation
+    int fuse_l0 = 1;                            // inference: layer-1 data gradient reduces straight to the layer-0 row sums
+    int dec_out_rows = 1;                       // output conv forward: row-streaming kernel without halo recompute (S in {32, 64, 128}); 0 = 16 x 16 tiles
+    int wgrad_accum = 0;                        // 1: the decoder's partial weight-gradient tiles accumulate over the T + 1 passes of a training step
+                                                // and are reduced once per layer and step.  Measured equal to the default (round 5): kept as an option
+    int refine_split = 1;                       // first refinement layer split into a per-slot and a per-image part (split-fp16 path)
+    int refine_l0_fused = 1;                    // encoding + first refinement layer in one kernel (kernels_refl0.hip); 0: pixel_pass2 + two convs
+    int refine_ws = 1;                          // forward stride-2 convs of refinement layers 1 .. on the weight-stationary kernel (kernels_refws.hip)
+    int refine_bwd_fused = 1;                   // training backward: data gradient of refinement layer 1 + weight gradient of layer 0 in one
+                                                // launch, d(pre-activation 0) never stored (kernels_refbwd.hip; 0 = the two launches)
+    int head_mfma = 1;                          // LSTM gate pre-activations of the refinement head as one fp32-MFMA GEMM over all slots
+    int head_fused = 1;                         // training backward: the head's BPTT recurrence as ONE launch (0 = 9 launches per iteration)
+    int sigma_grad = 0;                         // a training forward / a saved elbo also leaves d LL_e / d sigma of every evaluation (one more
+                                                // per-pixel kernel per evaluation; off: no launch differs)
+    int input_grad = 0;                         // bit 1 image, bit 2 pixel weights - a training forward / a saved elbo also accumulates
+                                                // sum_e a_e d LL_e / d x (d w) (kernels_pixmap.hip; 0: no launch, no buffer)
+    int stable_enc = 0;                         // stable_encoding: channel 8 of the encoding as a max-subtracted softmax (pixel_terms.h)
+    int joint_ll = 0;                           // joint_likelihood: one mixture per pixel over the RGB vector (pixel_terms.h), every launch
+                                                // of the per-pixel terms takes it; a change discards the saved passes (iodine_set_option)
+    int save_bwd = 0;                           // save_for_backward: a decode / elbo keeps what its backward reads (calls.diff_*)
+    int graph = 0;                              // hipGraph replay of the fixed-shape launch sequences: one instantiated graph per distinct argument tuple
+    int stop_after = -1;                        // stop_after_iters
+    int profile = 0;                            // 0 off, 1 the dominant conv kernels ("conv_tile_*") only, 2 every category
+    int profile_stride = 1;                     // level 1: bracket every n-th launch of a category only - an event pair costs ~12 us of idle GPU
+                                                // (tools/step_timeline.py); a stride coprime to the layer count samples every layer
+};
+
+// The packs below are parameter-derived device buffers the handle owns (h->owned).  Each group is allocated by one alloc_* function of
+// iodine_params.cpp, next to the pack_* function of iodine_set_params that fills it; a launch site (iodine_dispatch.cpp) reads a pack only
+// on the path / behind the predicate named here.
+
+// the tuned decoder: layers 1 .. Dd-1 (index 0 unused) per DecPath, the broadcast layer and the output conv
+struct DecPacks {
+    float *wcls = nullptr, *wclsT = nullptr, *cmap = nullptr;    // broadcast layer (launch_dec_l0_prepare)
+    std::vector<float*> bias;                   // bias copies of layers 1 .. (generic path too)
+    std::vector<Pack> ws_f, ws_b;               // DEC_WS_F16 / DEC_WS_F32 (the same buffers: fp16 split with meta, or fp32): forward / data gradient
+    std::vector<Pack> tile_f, tile_b;           // DEC_TILE_F16
+    std::vector<float*> tile32_f, tile32_b;     // DEC_TILE_F32
+    struct Out {
+        float* bias = nullptr;
+        Pack gemm, dgrad;                       // dec_f16(path): GEMM form / data-gradient form, one shared scale
+        float *taps = nullptr, *dgrad32 = nullptr;   // exact fp32: round-1 tap form, LDS-tile f32 pack of the data gradient
+        float* rows32 = nullptr;                // exact fp32, row-streaming forward (Cd 32 / 64 only, else nullptr)
+    } out;
+};
+// the tuned refinement conv stack, per RefFamily and ref_pack_* predicate (iodine_dispatch.cpp)
+struct RefPacks {
+    std::vector<float*> bias;                   // every family (generic too)
+    std::vector<float*> gather_f, gather_b;     // REF_GATHER: LDS-tile f32 packs, forward [0 ..] / data gradient [1 ..]
+    std::vector<Pack> s2_f, s2_b;               // REF_S2_F16 / REF_S2_F32: stride-2 tile packs, forward [0 ..] / data gradient [1 ..]
+    float *wk = nullptr, *wsh = nullptr;        // split first layer: weights in the internal channel order [Cr][12][9], [Cr][8][9]
+    Pack split_k, split_sh;                     // ... and their stride-2 tile packs (two 16-channel convs)
+    Pack l0k, l0s;                              // ref_pack_l0f: operands of the fused encoding + first layer (kernels_refl0.hip)
+    std::vector<Pack> ws;                       // ref_pack_ws: layers 1 .. in the weight-stationary layout (kernels_refws.hip)
+    Pack bwd01;                                 // ref_pack_bwd01: layer 1's weights as the A operand of the fused layer-1 / layer-0 backward
+    float* g20 = nullptr;                       // [Cr][20][9] weight gradient in the internal order
+    float *w17 = nullptr, *g17 = nullptr;       // ARCH.ENCODING subsets: [Cr][17][kr * kr] expanded weights / gradient scratch
+};
+// the refinement head as the forward reads it, and raw copies for the GEMMs of its backward
+struct HeadPacks {
+    float *mlp_wT = nullptr, *mlp_b = nullptr, *wihT = nullptr, *whhT = nullptr, *lstm_b = nullptr;   // [W_ih^T ; W_hh^T] are one block
+    float *wmT = nullptr, *bm = nullptr, *wvT = nullptr, *bv = nullptr, *init_mean = nullptr, *init_logvar = nullptr;
+    float *raw_mlp_w = nullptr, *raw_wih = nullptr, *raw_whh = nullptr, *raw_wm = nullptr, *raw_wv = nullptr;
+};
+// GENERIC fallback path (kernels_generic.hip): KERNEL_SIZE other than 3 or CONV_CHAN other than 32 / 64.  Weights re-packed to
+// [tap][ci][co]; the broadcast layer is materialised; nothing of the tuned conv kernels runs.
+struct GenPacks {
+    std::vector<float*> wdec, wref;             // [layer]: DEC_GENERIC / REF_GENERIC
+    float *wout = nullptr, *cterm = nullptr, *ident = nullptr;   // output conv pack, [P][Cd] bias + coordinate term of decoder layer 0, [9 Cd][L] identity
+    // option gen_conv_precision 1 (kernels_gensplit.hip): split-fp16 slice images + per-slice inverse scales of the decoder's C -> C layers,
+    // forward / data gradient; allocated by the first iodine_set_params that needs them.  split_on: the packs are current and the shape is covered
+    bool split_on = false;
+    std::vector<Pack> split_f, split_b;
+};
+
 struct iodine_handle {
     iodine_config cfg;
+    Options opt;
     Objective obj;                              // current; initially (ARCH.SIGMA, 1, default weighting)
     CallState calls;                            // what the calls so far have left in the arena
     std::list<WeightTable> wtabs;               // every distinct weight table this handle was given (content-addressed, never rewritten)
     int wgen_next = 1;                          // generation of the next new table: counts up for the life of the handle, never re-used
     std::string err;
-    int profile = 0;                            // 0 off, 1 the dominant conv kernels ("conv_tile_*") only, 2 every category
-    int profile_stride = 1;                     // level 1: bracket every n-th launch of a category only - an event pair costs ~12 us of idle GPU
-                                                // (a barrier packet in front of the kernel and one behind it: tools/step_timeline.py), 54 pairs per cfg3
-                                                // training step = 0.8 ms of the step being measured; a stride coprime to the layer count samples every layer
     std::vector<ProfCat> prof;
     ProfCat* prof_cat(const char* name) {
         for (auto& c : prof) if (c.name == name) return &c;
@@ -154,90 +235,34 @@ struct iodine_handle {
     std::vector<ParamInfo> params;
     ParamSlots slot;
     bool params_set = false;
-    int stop_after = -1;
     int frames = 0;                             // iodine_set_frames: 0 = x is one image per batch entry, E = a clip of E frames, one per ELBO evaluation
     // iodine_set_pixel_weights: per-pixel observation weights of the NEXT compute call that takes x.  One-shot: that call takes them
     // (PixelWeights below) before anything else, so they are gone whether it succeeds or not.  The caller's memory, read on the call's stream.
     const float* pix_w = nullptr;
     int pix_w_per_frame = 0;                    // 1: (B, frames, P), one weight image per frame; 0: (B, P), the same for every frame
+    int ig_call_wpf = 0;                        // (the running call's pixel weights are per frame: read by elbo_and_gradients inside the call)
 
     // parameter-derived device buffers (owned)
     float* lin = nullptr;                       // linspace(-1,1,S)
-    float *wcls = nullptr, *wclsT = nullptr, *cmap = nullptr;
-    std::vector<float*> dec_wf, dec_wb, dec_b;  // packed fwd / dgrad weights + bias copies for layers 1..Dd-1
-    std::vector<float*> dec_wf16, dec_wb16, dec_wmeta;   // split-fp16 packs (+ {scale, 1/scale, scale_b, 1/scale_b})
-    std::vector<float*> dec_wsf, dec_wsb;                // the same weights in the register layout of the weight-stationary conv
-    int precision = 1;                          // 0: exact fp32 MFMA, 1: 3 x fp16 MFMA split (fp32-class accuracy)
-    int out_bwd_fused = 1;                      // training: output conv data + weight gradient in one pass over the activation
-    int fuse_l0 = 1;                            // inference: layer-1 data gradient reduces straight to the layer-0 row sums
-    int refine_split = 1;                       // first refinement layer split into a per-slot and a per-image part (split-fp16 path)
-    int head_fused = 1;                         // training backward: the head's BPTT recurrence as ONE launch (0 = 9 launches per iteration)
-    int refine_bwd_fused = 1;                   // training backward: data gradient of refinement layer 1 + weight gradient of layer 0 in one
-                                                // launch, d(pre-activation 0) never stored (kernels_refbwd.hip; 0 = the two launches)
-    int variant = 6;                            // split-fp16 stride-1 conv: 6 = weight-stationary persistent kernel (power-of-two image sizes;
-                                                // other sizes use 1), 1 = LDS-tiled 16x16 tiles (2 blocks/CU)
-    float* dec_out_w32 = nullptr;               // fp32 operand of the row-streaming output conv (conv_precision 0)
-    float *dec_out_w = nullptr, *dec_out_b = nullptr, *dec_out_wb = nullptr, *dec_out_w16 = nullptr, *dec_out_meta = nullptr,
-          *dec_out_wb16 = nullptr;               // split-fp16 pack of the output conv for its data gradient
-    std::vector<float*> ref_w, ref_b;
-    float *mlp_wT = nullptr, *mlp_b = nullptr, *wihT = nullptr, *whhT = nullptr, *lstm_b = nullptr;
-    float *wmT = nullptr, *bm = nullptr, *wvT = nullptr, *bv = nullptr, *init_mean = nullptr, *init_logvar = nullptr;
-    // training: raw copies used by the head backward GEMMs, strided-dgrad packs, gradient accumulators
-    float *raw_mlp_w = nullptr, *raw_wih = nullptr, *raw_whh = nullptr, *raw_wm = nullptr, *raw_wv = nullptr;
-    std::vector<float*> ref_wb;
-    std::vector<float*> ref_wf16, ref_wb16, ref_wmeta;     // split-fp16 packs of the stride-2 convs (+ {scale, 1/scale} x {fwd, dgrad})
-    float *ref_wk = nullptr, *ref_wsh = nullptr;           // split first layer: weights in the internal channel order [Cr][12][9], [Cr][8][9]
-    float *ref_wk16 = nullptr, *ref_wsh16 = nullptr, *ref_wkmeta = nullptr, *ref_wshmeta = nullptr;   // and their packs
-    float* ref_g20 = nullptr;                              // [Cr][20][9] weight gradient in the internal order
-    unsigned* elbo_counter = nullptr;                      // ticket of pixel_finalize_elbo_kernel (zero between launches)
-    int head_mfma = 1;                                     // LSTM gate pre-activations of the refinement head as one fp32-MFMA GEMM over all slots
-    int refine_l0_fused = 1;                               // encoding + first refinement layer in one kernel (kernels_refl0.hip); 0: pixel_pass2 + two convs
-    void *ref_l0k = nullptr, *ref_l0s = nullptr; float *ref_l0kmeta = nullptr, *ref_l0smeta = nullptr;     // its weight packs
-    int wgrad_accum = 0;                                   // 1: the decoder's partial weight-gradient tiles accumulate over the T + 1 passes of a training
-                                                           // step (alpha = pass weight) and are reduced once per layer and step.  Measured (round 5, same
-                                                           // process A/B): cfg3 48.197 vs 48.200 ms, cfg2 6.55 vs 6.53 ms - the read-modify-write of the
-                                                           // partial tiles in the kernels' tails costs what the 20 saved reduce launches cost: NOT adopted,
-                                                           // kept as an option (off: no extra workspace)
-    int dec_out_rows = 1;                                  // output conv forward: row-streaming kernel without halo recompute (S in {32, 64, 128}); 0 = 16 x 16 tiles
-    int refine_ws = 1;                                     // forward stride-2 convs of refinement layers 1 .. on the weight-stationary kernel (kernels_refws.hip)
-    std::vector<float*> ref_wsf, ref_wsf_meta;             // their weights in its register layout
-    float *ref_w1ws = nullptr, *ref_w1ws_meta = nullptr;   // layer 1's weights in the register layout of the fused layer-1/0 backward
+    unsigned* elbo_counter = nullptr;           // ticket of pixel_finalize_elbo_kernel (zero between launches)
+    DecPacks dec;
+    RefPacks ref;
+    HeadPacks head;
+    GenPacks gen;
     // ARCH.ENCODING subsets: reference input channel j of the first refinement layer = internal channel enc_map[j] (code order of
     // iodine.py:277-340); n_in < 17 -> weights expanded to / gradients gathered from the 17 internal channels
     int n_in = 17;
     int enc_map[17];
-    unsigned enc_chmask = 0x1ffffu;                        // bit c: internal channel c is part of the encoding (absent ones are written as 0)
-    float *ref_w17 = nullptr, *ref_g17 = nullptr;          // [Cr][17][kr * kr]
-    // GENERIC fallback path (kernels_generic.hip): KERNEL_SIZE other than 3 or CONV_CHAN other than 32 / 64.  Weights re-packed to
-    // [tap][ci][co]; the broadcast layer is materialised; nothing of the tuned conv kernels runs.
-    bool generic = false;                                  // the DECODER runs on the generic path
-    bool gen_ref = false;                                  // the REFINEMENT conv stack runs on the generic path (round 5: decided separately -
-                                                           // the reference's default ARCH has REF.KERNEL_SIZE 3 / 32 channels beside DEC.KERNEL_SIZE 5)
-    int kd = 3, kr = 3;                                    // DEC / REF kernel sizes
-    int rs = 2;                                            // REF.STRIDE (round 6: other strides run on the generic path's kernels)
-    std::vector<float*> gen_wdec, gen_wref;                // [layer]: packed weights
-    float *gen_wout = nullptr, *gen_cterm = nullptr, *gen_ident = nullptr;   // output conv pack, [P][Cd] bias + coordinate term of decoder layer 0, [9 Cd][L] identity
-    // option gen_conv_precision 1 (kernels_gensplit.hip): split-fp16 slice images + per-slice inverse scales of the decoder's C -> C layers,
-    // forward / data gradient; allocated by the first iodine_set_params that needs them.  gen_split: the packs are current and the shape is covered
-    int gen_precision = 0;
-    bool gen_split = false;
-    std::vector<void*> gs_wf, gs_wb;
-    std::vector<float*> gs_mf, gs_mb;
+    unsigned enc_chmask = 0x1ffffu;             // bit c: internal channel c is part of the encoding (absent ones are written as 0)
+    bool generic = false;                       // the DECODER runs on the generic path
+    bool gen_ref = false;                       // the REFINEMENT conv stack runs on the generic path (round 5: decided separately -
+                                                // the reference's default ARCH has REF.KERNEL_SIZE 3 / 32 channels beside DEC.KERNEL_SIZE 5)
+    int kd = 3, kr = 3;                         // DEC / REF kernel sizes
+    int rs = 2;                                 // REF.STRIDE (round 6: other strides run on the generic path's kernels)
     std::vector<float*> gacc;                   // one per parameter, reference shapes (slices of gacc_arena)
     float* gacc_arena = nullptr;
     size_t gacc_total = 0;
-    int sigma_grad = 0;                         // option sigma_grad: a training forward / a saved elbo also leaves d LL_e / d sigma of every
-                                                // evaluation (one more per-pixel kernel per evaluation; off: no launch differs)
-    int input_grad = 0;                         // option input_grad: bit 1 image, bit 2 pixel weights - a training forward / a saved elbo also
-                                                // accumulates sum_e a_e d LL_e / d x (d w) (kernels_pixmap.hip; 0: no launch, no buffer)
-    int ig_call_wpf = 0;                        // (the running call's pixel weights are per frame: read by elbo_and_gradients inside the call)
-    int stable_enc = 0;                         // option stable_encoding: channel 8 of the encoding as a max-subtracted softmax (pixel_terms.h)
-    int joint_ll = 0;                           // option joint_likelihood: one mixture per pixel over the RGB vector (pixel_terms.h), every launch
-                                                // of the per-pixel terms takes it; a change discards the saved passes (iodine_set_option)
-    int save_bwd = 0;                           // option save_for_backward: a decode / elbo keeps what its backward reads (calls.diff_*)
-    // hipGraph replay of the fixed-shape launch sequences (option "graph"): one instantiated graph per distinct argument tuple
-    int graph = 0;
-    std::vector<GraphEntry> graphs;
+    std::vector<GraphEntry> graphs;             // option graph
     std::vector<std::vector<uintptr_t>> seen_keys;       // argument tuples that ran eagerly once (the next call captures)
     unsigned long long graph_clock = 0;
     long long graph_replays = 0, graph_captures = 0;

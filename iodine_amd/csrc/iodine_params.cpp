@@ -6,14 +6,24 @@ std::string g_create_error;
 
 namespace {
 
-template <typename T>
-hipError_t dev_alloc(iodine_handle* h, T** p, size_t n)
-{
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) { *p = (T*)q; h->owned.push_back(q); }
-    return e;
-}
+// The device buffers of iodine_create: one hipMalloc each, owned by the handle (iodine_destroy frees h->owned).  The first failure is kept
+// and turns every later request into a no-op, so the alloc_* functions below read as plain lists; iodine_create looks at `err` once.
+struct DevAlloc {
+    iodine_handle* h;
+    const char* group = "";                     // what was being allocated when `err` was set, for the message
+    hipError_t err = hipSuccess;
+    void in(const char* g) { if (err == hipSuccess) group = g; }
+    void* bytes(size_t n) {
+        void* q = nullptr;
+        if (err == hipSuccess && (err = hipMalloc(&q, std::max(n, sizeof(float)))) == hipSuccess) h->owned.push_back(q);
+        return err == hipSuccess ? q : nullptr;
+    }
+    float* f32(size_t bytes_) { return (float*)bytes(bytes_); }
+    float* floats(size_t n) { return f32(n * sizeof(float)); }
+    // a pack of `n` bytes (pack_geom.h) with the meta block it is given (second: its data-gradient half), or one of its own
+    Pack pack(size_t n) { void* d = bytes(n); return Pack{d, floats(WPK_META_FLOATS)}; }
+    Pack pack(size_t n, float* meta, bool second = false) { return Pack{bytes(n), meta && second ? meta + 2 : meta}; }
+};
 
 std::string validate(const iodine_config& c)
 {
@@ -59,81 +69,80 @@ std::string validate(const iodine_config& c)
 
 // ---- iodine_set_params: what it queues, and its five groups of packs
 
-// Plain copies (biases, raw weights of the head backward) are collected and issued as one launch; (round 5) the head's transposes
-// [R][Cc] -> [Cc][R] and the bias sum ride in the same launch.  The split-fp16 packs (power-of-two scale + layout per tensor and direction)
-// are collected too and issued as one batched launch at the end.
-struct ParamPacker {
-    hipStream_t st;
-    MultiCopy mc;
+// Plain copies (biases, raw weights of the head backward), the head's transposes and the bias sum ride in one launch (CopyBatch).  The
+// split-fp16 packs (power-of-two scale + layout per tensor and direction) are collected too and issued as one batched launch at the end.
+struct ParamPacker : CopyBatch {
     std::vector<PackJob> pj;
-    explicit ParamPacker(hipStream_t s) : st(s) { mc.count = 0; }
-    hipError_t flush() { const hipError_t e = launch_multi_copy(st, mc); mc.count = 0; return e; }
-    hipError_t copy(float* dst, const float* src, size_t count) {
-        if (mc.count == MCOPY_MAX) {
-            const hipError_t e = flush();
-            if (e != hipSuccess) return e;
-        }
-        mc.src[mc.count] = src; mc.src2[mc.count] = nullptr; mc.dst[mc.count] = dst; mc.n[mc.count] = (int)count; mc.op[mc.count] = 0;
-        mc.cols[mc.count] = 0; ++mc.count;
+    using CopyBatch::CopyBatch;
+    // jobs of the batched pack (kernels_pack.hip): the scale goes to p.meta, the pack to p.data
+    hipError_t job(int kind, const float* src, const Pack& p, int p0, int p1 = 0, int p2 = 0, int p3 = 0, int p4 = 0) {
+        pj.push_back(PackJob{src, p.data, p.meta, kind, {p0, p1, p2, p3, p4}});
         return hipSuccess;
     }
-    hipError_t transpose(float* dst, const float* src, int R, int Cc) {
-        const hipError_t e = copy(dst, src, (size_t)R * Cc);
-        if (e == hipSuccess) { mc.op[mc.count - 1] = 1; mc.cols[mc.count - 1] = Cc; }
-        return e;
-    }
-    hipError_t add2(float* dst, const float* a, const float* b2, int count) {
-        const hipError_t e = copy(dst, a, (size_t)count);
-        if (e == hipSuccess) { mc.op[mc.count - 1] = 2; mc.src2[mc.count - 1] = b2; }
-        return e;
-    }
-    hipError_t ws(const float* src, int C, int tflip, float* meta, void* dst) {
-        pj.push_back(PackJob{src, dst, meta, 0, {C, tflip, 0, 0, 0}});
-        return hipSuccess;
-    }
-    hipError_t f16(const float* src, int O, int I, int cin, int cout, int tflip, float* meta, void* dst) {
-        pj.push_back(PackJob{src, dst, meta, 1, {O, I, cin, cout, tflip}});
-        return hipSuccess;
-    }
+    hipError_t ws(const float* src, int C, int tflip, const Pack& p) { return job(0, src, p, C, tflip); }
+    hipError_t f16(const float* src, int O, int I, int cin, int cout, int tflip, const Pack& p) { return job(1, src, p, O, I, cin, cout, tflip); }
 };
+
+// ---- DEC_GENERIC.  Allocated here (iodine_create, on that path only), filled below, read by decoder_forward / decoder_backward_generic
+void alloc_decoder_generic(iodine_handle* h, DevAlloc& da)
+{
+    GenPacks& g = h->gen;
+    const int L = h->L, Cd = h->Cd, k = h->kd;
+    da.in("generic decoder packs");
+    g.wdec.assign(h->Dd, nullptr);
+    for (int l = 0; l < h->Dd; ++l) g.wdec[l] = da.f32(wpk_gen_bytes(k, l == 0 ? L + 2 : Cd, Cd));
+    g.wout = da.f32(wpk_gen_bytes(k, Cd, 4)); g.cterm = da.floats((size_t)h->P * Cd); g.ident = da.floats((size_t)9 * Cd * L);
+}
+
+// gen_conv_precision 1: the slice images of layers 1 .., both directions - by the first iodine_set_params that needs them
+int alloc_gen_split(iodine_handle* h)
+{
+    GenPacks& g = h->gen;
+    if (!g.split_f.empty()) return IODINE_OK;
+    DevAlloc da{h};
+    g.split_f.assign(h->Dd, Pack()); g.split_b.assign(h->Dd, Pack());
+    const size_t pb = gen_split_pack_bytes(h->kd, h->Cd), mb = sizeof(float) * wpk_gen_split_meta_floats(h->Cd);
+    for (int l = 1; l < h->Dd; ++l)
+        for (Pack* p : {&g.split_f[l], &g.split_b[l]}) { p->data = da.bytes(pb); p->meta = da.f32(mb); }
+    if (da.err == hipSuccess) return IODINE_OK;
+    g.split_f.clear(); g.split_b.clear();                          // (what was allocated stays in `owned`; the next call starts over)
+    return h->fail(IODINE_ERR_HIP, std::string("hipMalloc of the split weight packs: ") + hipGetErrorString(da.err));
+}
 
 // fallback path: [tap][ci][co] packs of every conv, plain bias copies
 int pack_decoder_generic(iodine_handle* h, ParamPacker& pk, const float* const* dev)
 {
     hipStream_t st = pk.st;
     const ParamSlots& ps = h->slot;
+    GenPacks& g = h->gen;
     const int L = h->L, Cd = h->Cd;
     for (int l = 0; l < h->Dd; ++l) {
-        HIPCHK(h, launch_gen_pack_weights(st, dev[ps.dec_w[l]], Cd, l == 0 ? L + 2 : Cd, h->kd, h->gen_wdec[l]));
-        if (l > 0) HIPCHK(h, pk.copy(h->dec_b[l], dev[ps.dec_b[l]], Cd));
+        HIPCHK(h, launch_gen_pack_weights(st, dev[ps.dec_w[l]], Cd, l == 0 ? L + 2 : Cd, h->kd, g.wdec[l]));
+        if (l > 0) HIPCHK(h, pk.copy(h->dec.bias[l], dev[ps.dec_b[l]], Cd));
     }
     // bias + the conv of the two coordinate channels of the broadcast layer: the same map for every slot-image
-    HIPCHK(h, launch_gen_l0_coord(st, h->gen_wdec[0], dev[ps.dec_b[0]], h->lin, L, h->S, Cd, h->kd, h->gen_cterm));
-    HIPCHK(h, launch_gen_pack_weights(st, dev[ps.out_w], 4, Cd, h->kd, h->gen_wout));
-    HIPCHK(h, pk.copy(h->dec_out_b, dev[ps.out_b], 4));
-    HIPCHK(h, launch_gen_identity(st, h->gen_ident, 9 * Cd, L));
+    HIPCHK(h, launch_gen_l0_coord(st, g.wdec[0], dev[ps.dec_b[0]], h->lin, L, h->S, Cd, h->kd, g.cterm));
+    HIPCHK(h, launch_gen_pack_weights(st, dev[ps.out_w], 4, Cd, h->kd, g.wout));
+    HIPCHK(h, pk.copy(h->dec.out.bias, dev[ps.out_b], 4));
+    HIPCHK(h, launch_gen_identity(st, g.ident, 9 * Cd, L));
     // gen_conv_precision 1: hi / lo slice images of the C -> C layers, both directions (from the packs above; stream order)
-    h->gen_split = h->gen_precision == 1 && gen_split_cch(h->kd, Cd) != 0 && h->Dd > 1;
-    if (h->gen_split) {
-        if (h->gs_wf.empty()) {
-            h->gs_wf.assign(h->Dd, nullptr); h->gs_wb.assign(h->Dd, nullptr); h->gs_mf.assign(h->Dd, nullptr); h->gs_mb.assign(h->Dd, nullptr);
-            const size_t pb = gen_split_pack_bytes(h->kd, Cd), mb = sizeof(float) * (size_t)(Cd / 16);
-            for (int l = 1; l < h->Dd; ++l)
-                for (void** q : {&h->gs_wf[l], &h->gs_wb[l], (void**)&h->gs_mf[l], (void**)&h->gs_mb[l]}) {
-                    const hipError_t e_ = hipMalloc(q, q == &h->gs_wf[l] || q == &h->gs_wb[l] ? pb : mb);
-                    if (e_ != hipSuccess) {                            // (what was allocated stays in `owned`; the next call starts over)
-                        h->gs_wf.clear(); h->gs_wb.clear(); h->gs_mf.clear(); h->gs_mb.clear();
-                        return h->fail(IODINE_ERR_HIP, std::string("hipMalloc of the split weight packs: ") + hipGetErrorString(e_));
-                    }
-                    h->owned.push_back(*q);
-                }
-        }
+    g.split_on = h->opt.gen_precision == 1 && gen_split_cch(h->kd, Cd) != 0 && h->Dd > 1;
+    if (g.split_on) {
+        if (int rc = alloc_gen_split(h)) return rc;
         for (int l = 1; l < h->Dd; ++l) {
-            HIPCHK(h, launch_gen_split_pack(st, h->gen_wdec[l], h->kd, Cd, 0, h->gs_wf[l], h->gs_mf[l]));
-            HIPCHK(h, launch_gen_split_pack(st, h->gen_wdec[l], h->kd, Cd, 1, h->gs_wb[l], h->gs_mb[l]));
+            HIPCHK(h, launch_gen_split_pack(st, g.wdec[l], h->kd, Cd, 0, g.split_f[l].data, g.split_f[l].meta));
+            HIPCHK(h, launch_gen_split_pack(st, g.wdec[l], h->kd, Cd, 1, g.split_b[l].data, g.split_b[l].meta));
         }
     }
     return IODINE_OK;
+}
+
+// ---- REF_GENERIC.  Allocated on that family only; read by ref_conv_fwd / ref_conv_dgrad (biases, w17: alloc_refine_tuned)
+void alloc_refine_generic(iodine_handle* h, DevAlloc& da)
+{
+    da.in("generic refinement packs");
+    h->gen.wref.assign(h->Dr, nullptr);
+    for (int l = 0; l < h->Dr; ++l) h->gen.wref[l] = da.f32(wpk_gen_bytes(h->kr, l == 0 ? 17 : h->Cr, h->Cr));
 }
 
 // the generic refinement stack: the same packs, the first layer from its 17 internal channels
@@ -144,55 +153,98 @@ int pack_refine_generic(iodine_handle* h, ParamPacker& pk, const float* const* d
     const int Cr = h->Cr;
     for (int l = 0; l < h->Dr; ++l) {
         const float* w = dev[ps.ref_w[l]];
-        if (l == 0 && h->n_in < 17) { HIPCHK(h, launch_enc_expand_weights(st, w, Cr, h->n_in, h->enc_map, h->ref_w17, h->kr * h->kr)); w = h->ref_w17; }
-        HIPCHK(h, launch_gen_pack_weights(st, w, Cr, l == 0 ? 17 : Cr, h->kr, h->gen_wref[l]));
-        HIPCHK(h, pk.copy(h->ref_b[l], dev[ps.ref_b[l]], Cr));
+        if (l == 0 && h->n_in < 17) { HIPCHK(h, launch_enc_expand_weights(st, w, Cr, h->n_in, h->enc_map, h->ref.w17, h->kr * h->kr)); w = h->ref.w17; }
+        HIPCHK(h, launch_gen_pack_weights(st, w, Cr, l == 0 ? 17 : Cr, h->kr, h->gen.wref[l]));
+        HIPCHK(h, pk.copy(h->ref.bias[l], dev[ps.ref_b[l]], Cr));
     }
     return IODINE_OK;
 }
 
-// the tuned decoder: only the selected path's packs - the ones dec_conv_fwd / dec_conv_dgrad read - are maintained (a change of
+// ---- the tuned decoder.  Every path's packs are allocated for every handle (conv_precision / conv_variant change the path; the bias
+// copies serve the generic path too); read by dec_conv_fwd / dec_conv_dgrad / dec_out_dgrad / decoder_forward on the path named in DecPacks
+void alloc_decoder_tuned(iodine_handle* h, DevAlloc& da)
+{
+    DecPacks& d = h->dec;
+    const int L = h->L, Cd = h->Cd, Dd = h->Dd;
+    da.in("decoder packs");
+    d.wcls = da.floats((size_t)9 * L * Cd); d.wclsT = da.floats((size_t)9 * L * Cd); d.cmap = da.floats((size_t)h->P * Cd);
+    d.bias.assign(Dd, nullptr); d.tile32_f.assign(Dd, nullptr); d.tile32_b.assign(Dd, nullptr);
+    for (auto* v : {&d.ws_f, &d.ws_b, &d.tile_f, &d.tile_b}) v->assign(Dd, Pack());
+    for (int l = 1; l < Dd; ++l) {
+        float* meta = da.floats(WPK_META_FLOATS);                   // one block per layer: the forward pair, then the data gradient's
+        d.ws_f[l] = da.pack(wpk_ws_bytes(Cd), meta); d.ws_b[l] = da.pack(wpk_ws_bytes(Cd), meta, true);
+        d.tile32_f[l] = da.f32(wpk_tile_f32_bytes(Cd, Cd)); d.tile32_b[l] = da.f32(wpk_tile_f32_bytes(Cd, Cd));
+        d.bias[l] = da.floats((size_t)Cd);
+        d.tile_f[l] = da.pack(wpk_tile_f16_bytes(Cd, Cd), meta); d.tile_b[l] = da.pack(wpk_tile_f16_bytes(Cd, Cd), meta, true);
+    }
+    d.out.taps = da.f32(wpk_out_taps_bytes(Cd));
+    if (Cd == 64 || Cd == 32) d.out.rows32 = da.f32(wpk_out_rows32_bytes(Cd));
+    d.out.bias = da.floats((size_t)4);
+    d.out.dgrad32 = da.f32(wpk_tile_f32_bytes(4, Cd));
+    d.out.gemm = da.pack(wpk_out_gemm_bytes(Cd));
+    d.out.dgrad = da.pack(wpk_out_dgrad_bytes(Cd), d.out.gemm.meta);      // (one scale for both forms)
+}
+
+// only the selected path's packs - the ones dec_conv_fwd / dec_conv_dgrad read - are maintained (a change of
 // conv_variant / conv_precision invalidates the parameters)
 int pack_decoder_tuned(iodine_handle* h, ParamPacker& pk, const float* const* dev, DecPath path)
 {
     hipStream_t st = pk.st;
     const ParamSlots& ps = h->slot;
+    DecPacks& d = h->dec;
     const int L = h->L, Cd = h->Cd;
-    HIPCHK(h, launch_dec_l0_prepare(st, dev[ps.dec_w[0]], dev[ps.dec_b[0]], h->lin, Cd, L, h->S, h->wcls, h->wclsT, h->cmap));
+    HIPCHK(h, launch_dec_l0_prepare(st, dev[ps.dec_w[0]], dev[ps.dec_b[0]], h->lin, Cd, L, h->S, d.wcls, d.wclsT, d.cmap));
     for (int l = 1; l < h->Dd; ++l) {
         const float* w = dev[ps.dec_w[l]];
-        switch (path) {
-        case DEC_WS_F16:                                       // weight-stationary register layout
-            HIPCHK(h, pk.ws(w, Cd, 0, h->dec_wmeta[l], h->dec_wsf[l]));
-            HIPCHK(h, pk.ws(w, Cd, 1, h->dec_wmeta[l] + 2, h->dec_wsb[l]));
-            break;
-        case DEC_TILE_F16:
-            HIPCHK(h, pk.f16(w, Cd, Cd, Cd, Cd, 0, h->dec_wmeta[l], h->dec_wf16[l]));
-            HIPCHK(h, pk.f16(w, Cd, Cd, Cd, Cd, 1, h->dec_wmeta[l] + 2, h->dec_wb16[l]));
-            break;
+        switch (path) {                                        // (forward, then the data gradient: the transposed conv)
+        case DEC_WS_F16: HIPCHK(h, pk.ws(w, Cd, 0, d.ws_f[l])); HIPCHK(h, pk.ws(w, Cd, 1, d.ws_b[l])); break;       // weight-stationary register layout
+        case DEC_TILE_F16: HIPCHK(h, pk.f16(w, Cd, Cd, Cd, Cd, 0, d.tile_f[l])); HIPCHK(h, pk.f16(w, Cd, Cd, Cd, Cd, 1, d.tile_b[l])); break;
         case DEC_WS_F32:                                       // the same register layout, fp32
-            HIPCHK(h, launch_pack_conv_weights_ws32(st, w, Cd, 0, h->dec_wsf[l]));
-            HIPCHK(h, launch_pack_conv_weights_ws32(st, w, Cd, 1, h->dec_wsb[l]));
+            HIPCHK(h, launch_pack_conv_weights_ws32(st, w, Cd, 0, d.ws_f[l].data)); HIPCHK(h, launch_pack_conv_weights_ws32(st, w, Cd, 1, d.ws_b[l].data));
             break;
         case DEC_TILE_F32:
-            HIPCHK(h, launch_pack_conv_weights(st, w, Cd, Cd, Cd, Cd, 0, h->dec_wf[l]));
-            HIPCHK(h, launch_pack_conv_weights(st, w, Cd, Cd, Cd, Cd, 1, h->dec_wb[l]));
+            HIPCHK(h, launch_pack_conv_weights(st, w, Cd, Cd, Cd, Cd, 0, d.tile32_f[l])); HIPCHK(h, launch_pack_conv_weights(st, w, Cd, Cd, Cd, Cd, 1, d.tile32_b[l]));
             break;
         case DEC_GENERIC: break;
         }
-        HIPCHK(h, pk.copy(h->dec_b[l], dev[ps.dec_b[l]], Cd));
+        HIPCHK(h, pk.copy(d.bias[l], dev[ps.dec_b[l]], Cd));
     }
-    HIPCHK(h, pk.copy(h->dec_out_b, dev[ps.out_b], 4));
+    HIPCHK(h, pk.copy(d.out.bias, dev[ps.out_b], 4));
     if (dec_f16(path)) {
         // split-fp16 GEMM-form packs of the output conv, forward and data gradient (one scale): two more jobs of the batched pack
-        pk.pj.push_back(PackJob{dev[ps.out_w], h->dec_out_w16, h->dec_out_meta, 3, {Cd, 0, 0, 0, 0}});
-        pk.pj.push_back(PackJob{dev[ps.out_w], h->dec_out_wb16, h->dec_out_meta, 4, {Cd, 1, 0, 0, 0}});
+        HIPCHK(h, pk.job(3, dev[ps.out_w], d.out.gemm, Cd, 0));
+        HIPCHK(h, pk.job(4, dev[ps.out_w], d.out.dgrad, Cd, 1));
     } else {                                                   // exact-fp32 forms of the output conv
-        HIPCHK(h, launch_pack_dec_out(st, dev[ps.out_w], h->dec_out_w, Cd));
-        HIPCHK(h, launch_pack_conv_weights(st, dev[ps.out_w], 4, Cd, 4, Cd, 1, h->dec_out_wb));
-        if (h->dec_out_w32) HIPCHK(h, launch_pack_dec_out_rows32(st, dev[ps.out_w], Cd, h->dec_out_w32));
+        HIPCHK(h, launch_pack_dec_out(st, dev[ps.out_w], d.out.taps, Cd));
+        HIPCHK(h, launch_pack_conv_weights(st, dev[ps.out_w], 4, Cd, 4, Cd, 1, d.out.dgrad32));
+        if (d.out.rows32) HIPCHK(h, launch_pack_dec_out_rows32(st, dev[ps.out_w], Cd, d.out.rows32));
     }
     return IODINE_OK;
+}
+
+// ---- the tuned refinement conv stack.  The packs of every tuned family are allocated for every handle (ref_family() changes with
+// conv_precision; biases and w17 / g17 serve the generic family too), the optional ones by ref_pack_*(); read by ref_conv_fwd / ref_conv_wgrad /
+// ref_conv_dgrad behind the family and the same predicates
+void alloc_refine_tuned(iodine_handle* h, DevAlloc& da)
+{
+    RefPacks& r = h->ref;
+    const int Cr = h->Cr, Dr = h->Dr;
+    da.in("refinement packs");
+    for (auto* v : {&r.bias, &r.gather_f, &r.gather_b}) v->assign(Dr, nullptr);
+    for (auto* v : {&r.s2_f, &r.s2_b, &r.ws}) v->assign(Dr, Pack());
+    for (int l = 0; l < Dr; ++l) {
+        r.gather_f[l] = da.f32(wpk_tile_f32_bytes(l == 0 ? 20 : Cr, Cr)); r.bias[l] = da.floats((size_t)Cr);
+        r.s2_f[l] = da.pack(wpk_s2_tile_bytes(l == 0 ? 32 : Cr, Cr));   // (its meta: the forward pair, then the data gradient's)
+        if (l == 0) continue;
+        r.gather_b[l] = da.f32(wpk_tile_f32_bytes(Cr, Cr)); r.s2_b[l] = da.pack(wpk_s2_tile_bytes(Cr, Cr), r.s2_f[l].meta, true);
+        if (ref_pack_ws(h)) r.ws[l] = da.pack(wpk_ws_bytes(Cr));
+    }
+    // split first layer: one 16-channel chunk each for the per-slot (12 real) and the per-image (8 real) channels
+    r.wk = da.floats((size_t)Cr * 12 * 9); r.wsh = da.floats((size_t)Cr * 8 * 9); r.g20 = da.floats((size_t)Cr * 20 * 9);
+    if (ref_pack_bwd01(h)) r.bwd01 = da.pack(wpk_ws_bytes(Cr));
+    r.w17 = da.floats((size_t)Cr * 17 * h->kr * h->kr); r.g17 = da.floats((size_t)Cr * 17 * h->kr * h->kr);
+    r.split_k = da.pack(wpk_s2_tile_bytes(16, Cr)); r.split_sh = da.pack(wpk_s2_tile_bytes(16, Cr));
+    if (Cr % 16 == 0) { r.l0k = da.pack(wpk_l0_bytes(Cr)); r.l0s = da.pack(wpk_l0_bytes(Cr)); }      // (ref_pack_l0f is "these exist")
 }
 
 // the tuned refinement conv stack: every pack of the family, whatever the per-form options say (they do not invalidate the parameters)
@@ -200,44 +252,61 @@ int pack_refine_tuned(iodine_handle* h, ParamPacker& pk, const float* const* dev
 {
     hipStream_t st = pk.st;
     const ParamSlots& ps = h->slot;
+    RefPacks& r = h->ref;
     const int Cr = h->Cr;
     // first layer: the reference weight has n_in input channels (ARCH.ENCODING subset); the kernels see 17
     const float* w0 = dev[ps.ref_w[0]];
-    if (h->n_in < 17) { HIPCHK(h, launch_enc_expand_weights(st, w0, Cr, h->n_in, h->enc_map, h->ref_w17)); w0 = h->ref_w17; }
+    if (h->n_in < 17) { HIPCHK(h, launch_enc_expand_weights(st, w0, Cr, h->n_in, h->enc_map, r.w17)); w0 = r.w17; }
     for (int l = 0; l < h->Dr; ++l) {
-        if (fam == REF_GATHER) HIPCHK(h, launch_pack_conv_weights(st, l == 0 ? w0 : dev[ps.ref_w[l]], Cr, l == 0 ? 17 : Cr, l == 0 ? 20 : Cr, Cr, 0, h->ref_w[l]));
-        HIPCHK(h, pk.copy(h->ref_b[l], dev[ps.ref_b[l]], Cr));
+        if (fam == REF_GATHER) HIPCHK(h, launch_pack_conv_weights(st, l == 0 ? w0 : dev[ps.ref_w[l]], Cr, l == 0 ? 17 : Cr, l == 0 ? 20 : Cr, Cr, 0, r.gather_f[l]));
+        HIPCHK(h, pk.copy(r.bias[l], dev[ps.ref_b[l]], Cr));
     }
     switch (fam) {
-    case REF_GATHER: for (int l = 1; l < h->Dr; ++l) HIPCHK(h, launch_pack_conv_weights(st, dev[ps.ref_w[l]], Cr, Cr, Cr, Cr, 2, h->ref_wb[l])); break;
+    case REF_GATHER: for (int l = 1; l < h->Dr; ++l) HIPCHK(h, launch_pack_conv_weights(st, dev[ps.ref_w[l]], Cr, Cr, Cr, Cr, 2, r.gather_b[l])); break;
     case REF_S2_F16: case REF_S2_F32: {
         // split fp16: jobs of the batched pack; exact fp32: fp32 weights in the same LDS-tile / register layouts, in the same buffers
         const bool f16 = fam == REF_S2_F16;
-        auto tile = [&](const float* w, int I, int cin, int tflip, float* meta, void* dst) {
-            return f16 ? pk.f16(w, Cr, I, cin, Cr, tflip, meta, dst) : launch_pack_conv_weights_s2f32(st, w, Cr, I, cin, Cr, tflip, dst);
+        auto tile = [&](const float* w, int I, int cin, int tflip, const Pack& p) {
+            return f16 ? pk.f16(w, Cr, I, cin, Cr, tflip, p) : launch_pack_conv_weights_s2f32(st, w, Cr, I, cin, Cr, tflip, p.data);
         };
         for (int l = 0; l < h->Dr; ++l) {
             const float* w = l == 0 ? w0 : dev[ps.ref_w[l]];
-            HIPCHK(h, tile(w, l == 0 ? 17 : Cr, l == 0 ? 32 : Cr, 0, h->ref_wmeta[l], h->ref_wf16[l]));
-            if (l > 0) HIPCHK(h, tile(w, Cr, Cr, 2, h->ref_wmeta[l] + 2, h->ref_wb16[l]));
+            HIPCHK(h, tile(w, l == 0 ? 17 : Cr, l == 0 ? 32 : Cr, 0, r.s2_f[l]));
+            if (l > 0) HIPCHK(h, tile(w, Cr, Cr, 2, r.s2_b[l]));
         }
         // split first layer (refine_split): the same weights in the internal channel order, packed as two 16-channel convs
-        HIPCHK(h, launch_ref_split_weights(st, w0, Cr, h->ref_wk, h->ref_wsh));
-        HIPCHK(h, tile(h->ref_wk, 12, 16, 0, h->ref_wkmeta, h->ref_wk16));
-        HIPCHK(h, tile(h->ref_wsh, 8, 16, 0, h->ref_wshmeta, h->ref_wsh16));
+        HIPCHK(h, launch_ref_split_weights(st, w0, Cr, r.wk, r.wsh));
+        HIPCHK(h, tile(r.wk, 12, 16, 0, r.split_k));
+        HIPCHK(h, tile(r.wsh, 8, 16, 0, r.split_sh));
         if (f16 && ref_pack_l0f(h)) {                          // fused encoding + layer 0: both parts as K = 16 MFMA operands
-            pk.pj.push_back(PackJob{h->ref_wk, h->ref_l0k, h->ref_l0kmeta, 2, {Cr, 12, 0, 0, 0}});
-            pk.pj.push_back(PackJob{h->ref_wsh, h->ref_l0s, h->ref_l0smeta, 2, {Cr, 8, 0, 0, 0}});
+            HIPCHK(h, pk.job(2, r.wk, r.l0k, Cr, 12));
+            HIPCHK(h, pk.job(2, r.wsh, r.l0s, Cr, 8));
         }
         for (int l = 1; l < h->Dr && ref_pack_ws(h); ++l)       // weight-stationary forward of layers 1 ..
-            HIPCHK(h, f16 ? pk.ws(dev[ps.ref_w[l]], Cr, 0, h->ref_wsf_meta[l], h->ref_wsf[l]) : launch_pack_conv_weights_ws32(st, dev[ps.ref_w[l]], Cr, 0, h->ref_wsf[l]));
+            HIPCHK(h, f16 ? pk.ws(dev[ps.ref_w[l]], Cr, 0, r.ws[l]) : launch_pack_conv_weights_ws32(st, dev[ps.ref_w[l]], Cr, 0, r.ws[l].data));
         if (f16 && ref_pack_bwd01(h))                          // fused layer-1 / layer-0 backward: W1 as the transposed conv's A operand
-            HIPCHK(h, pk.ws(dev[ps.ref_w[1]], Cr, 1, h->ref_w1ws_meta, h->ref_w1ws));
+            HIPCHK(h, pk.ws(dev[ps.ref_w[1]], Cr, 1, r.bwd01));
         break;
     }
     case REF_GENERIC: break;                                   // (pack_refine_generic)
     }
     return IODINE_OK;
+}
+
+// ---- the refinement head: allocated for every handle, read by refine_step and the head's backward (iodine_train.cpp)
+void alloc_head(iodine_handle* h, DevAlloc& da)
+{
+    HeadPacks& d = h->head;
+    const size_t L = h->L, Cr = h->Cr, H = h->H;
+    da.in("refinement head");
+    d.mlp_wT = da.floats(Cr * H); d.mlp_b = da.floats(H);
+    d.wihT = da.floats((H + 4 * L + H) * 4 * H);             // [W_ih^T ; W_hh^T] contiguous: one K-major operand for the gate GEMM (head_mfma)
+    d.whhT = d.wihT ? d.wihT + (H + 4 * L) * 4 * H : nullptr;
+    d.lstm_b = da.floats(4 * H);
+    d.wmT = da.floats(H * L); d.bm = da.floats(L); d.wvT = da.floats(H * L); d.bv = da.floats(L);
+    d.init_mean = da.floats(L); d.init_logvar = da.floats(L);
+    d.raw_mlp_w = da.floats(H * Cr); d.raw_wih = da.floats(4 * H * (H + 4 * L)); d.raw_whh = da.floats(4 * H * H);
+    d.raw_wm = da.floats(L * H); d.raw_wv = da.floats(L * H);
 }
 
 // raw copies of the head's weights for its backward GEMMs, then the head as the forward reads it - the same on every path
@@ -246,23 +315,23 @@ int pack_head(iodine_handle* h, ParamPacker& pk, const float* const* dev)
     const ParamSlots& ps = h->slot;
     const int L = h->L, Cr = h->Cr, H = h->H;
     auto copy_raw = [&](float* dst, int slot) { return pk.copy(dst, dev[slot], h->params[slot].numel()); };
-    HIPCHK(h, copy_raw(h->raw_mlp_w, ps.mlp_w));
-    HIPCHK(h, copy_raw(h->raw_wih, ps.wih));
-    HIPCHK(h, copy_raw(h->raw_whh, ps.whh));
-    HIPCHK(h, copy_raw(h->raw_wm, ps.wm));
-    HIPCHK(h, copy_raw(h->raw_wv, ps.wv));
+    HIPCHK(h, copy_raw(h->head.raw_mlp_w, ps.mlp_w));
+    HIPCHK(h, copy_raw(h->head.raw_wih, ps.wih));
+    HIPCHK(h, copy_raw(h->head.raw_whh, ps.whh));
+    HIPCHK(h, copy_raw(h->head.raw_wm, ps.wm));
+    HIPCHK(h, copy_raw(h->head.raw_wv, ps.wv));
     // head
-    HIPCHK(h, pk.transpose(h->mlp_wT, dev[ps.mlp_w], H, Cr));
-    HIPCHK(h, pk.copy(h->mlp_b, dev[ps.mlp_b], H));
-    HIPCHK(h, pk.transpose(h->wihT, dev[ps.wih], 4 * H, H + 4 * L));
-    HIPCHK(h, pk.transpose(h->whhT, dev[ps.whh], 4 * H, H));
-    HIPCHK(h, pk.add2(h->lstm_b, dev[ps.bih], dev[ps.bhh], 4 * H));
-    HIPCHK(h, pk.transpose(h->wmT, dev[ps.wm], L, H));
-    HIPCHK(h, pk.transpose(h->wvT, dev[ps.wv], L, H));
-    HIPCHK(h, pk.copy(h->bm, dev[ps.bm], L));
-    HIPCHK(h, pk.copy(h->bv, dev[ps.bv], L));
-    HIPCHK(h, pk.copy(h->init_mean, dev[ps.init_mean], L));
-    HIPCHK(h, pk.copy(h->init_logvar, dev[ps.init_logvar], L));
+    HIPCHK(h, pk.transpose(h->head.mlp_wT, dev[ps.mlp_w], H, Cr));
+    HIPCHK(h, pk.copy(h->head.mlp_b, dev[ps.mlp_b], H));
+    HIPCHK(h, pk.transpose(h->head.wihT, dev[ps.wih], 4 * H, H + 4 * L));
+    HIPCHK(h, pk.transpose(h->head.whhT, dev[ps.whh], 4 * H, H));
+    HIPCHK(h, pk.add2(h->head.lstm_b, dev[ps.bih], dev[ps.bhh], 4 * H));
+    HIPCHK(h, pk.transpose(h->head.wmT, dev[ps.wm], L, H));
+    HIPCHK(h, pk.transpose(h->head.wvT, dev[ps.wv], L, H));
+    HIPCHK(h, pk.copy(h->head.bm, dev[ps.bm], L));
+    HIPCHK(h, pk.copy(h->head.bv, dev[ps.bv], L));
+    HIPCHK(h, pk.copy(h->head.init_mean, dev[ps.init_mean], L));
+    HIPCHK(h, pk.copy(h->head.init_logvar, dev[ps.init_logvar], L));
     return IODINE_OK;
 }
 
@@ -318,88 +387,27 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
         iodine_destroy(h);
         return IODINE_ERR_HIP;
     };
-#define ALLOC(ptr, n) do { hipError_t e_ = dev_alloc(h, &(ptr), (n)); if (e_ != hipSuccess) return bail(e_, "hipMalloc " #ptr); } while (0)
-    const int L = h->L, Cd = h->Cd, Cr = h->Cr, H = h->H;
-    ALLOC(h->lin, (size_t)h->S);
-    ALLOC(h->wcls, (size_t)9 * L * Cd);
-    ALLOC(h->wclsT, (size_t)9 * L * Cd);
-    ALLOC(h->cmap, (size_t)h->P * Cd);
-    h->dec_wf.assign(h->Dd, nullptr); h->dec_wb.assign(h->Dd, nullptr); h->dec_b.assign(h->Dd, nullptr);
-    h->dec_wf16.assign(h->Dd, nullptr); h->dec_wb16.assign(h->Dd, nullptr); h->dec_wmeta.assign(h->Dd, nullptr);
-    h->dec_wsf.assign(h->Dd, nullptr); h->dec_wsb.assign(h->Dd, nullptr);
-    for (int l = 1; l < h->Dd; ++l) {
-        ALLOC(h->dec_wsf[l], conv_ws_wpk_bytes(Cd) / 4);
-        ALLOC(h->dec_wsb[l], conv_ws_wpk_bytes(Cd) / 4);
-        ALLOC(h->dec_wf[l], conv_wpk_elems(Cd, Cd) * 4);
-        ALLOC(h->dec_wb[l], conv_wpk_elems(Cd, Cd) * 4);
-        ALLOC(h->dec_b[l], (size_t)Cd);
-        ALLOC(h->dec_wf16[l], (size_t)(Cd / 16) * 9 * 2 * 2 * Cd * 4);      // fp16 x 8 per uint4 = 4 floats
-        ALLOC(h->dec_wb16[l], (size_t)(Cd / 16) * 9 * 2 * 2 * Cd * 4);
-        ALLOC(h->dec_wmeta[l], (size_t)4);
-    }
-    ALLOC(h->dec_out_w, (size_t)9 * Cd * 4);
-    if (Cd == 64 || Cd == 32) ALLOC(h->dec_out_w32, (size_t)2 * (Cd / 2) * 64);
-    ALLOC(h->dec_out_b, (size_t)4);
-    ALLOC(h->dec_out_wb, conv_wpk_elems(4, Cd) * 4);
-    ALLOC(h->dec_out_w16, (size_t)(Cd / 16) * 2 * 2 * 64 * 4);            // GEMM-form pack: [chunk][hi/lo][kh][64][8 fp16]
-    ALLOC(h->dec_out_meta, (size_t)4);
-    ALLOC(h->dec_out_wb16, (size_t)3 * 2 * 2 * Cd * 4);
-    // refinement conv stack: the packs of every tuned family (ref_family() changes with conv_precision), the optional ones by ref_pack_*()
-    for (auto* v : {&h->ref_w, &h->ref_b, &h->ref_wb, &h->ref_wf16, &h->ref_wb16, &h->ref_wmeta, &h->ref_wsf, &h->ref_wsf_meta}) v->assign(h->Dr, nullptr);
-    for (int l = 0; l < h->Dr; ++l) {
-        ALLOC(h->ref_w[l], conv_wpk_elems(l == 0 ? 20 : Cr, Cr) * 4); ALLOC(h->ref_b[l], (size_t)Cr);
-        ALLOC(h->ref_wf16[l], (size_t)((l == 0 ? 32 : Cr) / 16) * 9 * 2 * 2 * Cr * 4); ALLOC(h->ref_wmeta[l], (size_t)4);
-        if (l == 0) continue;
-        ALLOC(h->ref_wb[l], conv_wpk_elems(Cr, Cr) * 4); ALLOC(h->ref_wb16[l], (size_t)(Cr / 16) * 9 * 2 * 2 * Cr * 4);
-        if (ref_pack_ws(h)) { ALLOC(h->ref_wsf[l], conv_ws_wpk_bytes(Cr) / 4); ALLOC(h->ref_wsf_meta[l], (size_t)4); }
-    }
-    ALLOC(h->mlp_wT, (size_t)Cr * H); ALLOC(h->mlp_b, (size_t)H);
-    ALLOC(h->wihT, (size_t)(H + 4 * L + H) * 4 * H);         // [W_ih^T ; W_hh^T] contiguous: one K-major operand for the gate GEMM (head_mfma)
-    h->whhT = h->wihT + (size_t)(H + 4 * L) * 4 * H;
-    ALLOC(h->lstm_b, (size_t)4 * H);
-    ALLOC(h->wmT, (size_t)H * L); ALLOC(h->bm, (size_t)L); ALLOC(h->wvT, (size_t)H * L); ALLOC(h->bv, (size_t)L);
-    ALLOC(h->init_mean, (size_t)L); ALLOC(h->init_logvar, (size_t)L);
-    ALLOC(h->raw_mlp_w, (size_t)H * Cr); ALLOC(h->raw_wih, (size_t)4 * H * (H + 4 * L)); ALLOC(h->raw_whh, (size_t)4 * H * H);
-    ALLOC(h->raw_wm, (size_t)L * H); ALLOC(h->raw_wv, (size_t)L * H);
-    // split first layer: one 16-channel chunk each for the per-slot (12 real) and the per-image (8 real) channels
-    ALLOC(h->ref_wk, (size_t)Cr * 12 * 9); ALLOC(h->ref_wsh, (size_t)Cr * 8 * 9); ALLOC(h->ref_g20, (size_t)Cr * 20 * 9);
-    if (ref_pack_bwd01(h)) { ALLOC(h->ref_w1ws, conv_ws_wpk_bytes(Cr) / 4); ALLOC(h->ref_w1ws_meta, (size_t)4); }
-    ALLOC(h->ref_w17, (size_t)Cr * 17 * h->kr * h->kr); ALLOC(h->ref_g17, (size_t)Cr * 17 * h->kr * h->kr);
-    if (dec_path(h) == DEC_GENERIC) {
-        const int kkd = h->kd * h->kd;
-        h->gen_wdec.assign(h->Dd, nullptr);
-        for (int l = 0; l < h->Dd; ++l) ALLOC(h->gen_wdec[l], (size_t)kkd * (l == 0 ? L + 2 : Cd) * Cd);
-        ALLOC(h->gen_wout, (size_t)kkd * Cd * 4); ALLOC(h->gen_cterm, (size_t)h->P * Cd); ALLOC(h->gen_ident, (size_t)9 * Cd * L);
-    }
-    if (ref_family(h) == REF_GENERIC) {
-        const int kkr = h->kr * h->kr;
-        h->gen_wref.assign(h->Dr, nullptr);
-        for (int l = 0; l < h->Dr; ++l) ALLOC(h->gen_wref[l], (size_t)kkr * (l == 0 ? 17 : Cr) * Cr);
-    }
-    ALLOC(h->ref_wk16, (size_t)9 * 2 * 2 * Cr * 4); ALLOC(h->ref_wsh16, (size_t)9 * 2 * 2 * Cr * 4);
-    ALLOC(h->ref_wkmeta, (size_t)4); ALLOC(h->ref_wshmeta, (size_t)4);
-    {
-        float* c_ = nullptr;
-        ALLOC(c_, (size_t)4);
-        h->elbo_counter = reinterpret_cast<unsigned*>(c_);
-        if (hipError_t e_ = hipMemset(c_, 0, 16); e_ != hipSuccess) return bail(e_, "hipMemset elbo_counter");
-    }
-    if (Cr % 16 == 0) {
-        float *pk = nullptr, *ps = nullptr;
-        ALLOC(pk, refine_l0_wpk_bytes(Cr) / 4); ALLOC(ps, refine_l0_wpk_bytes(Cr) / 4); ALLOC(h->ref_l0kmeta, (size_t)4); ALLOC(h->ref_l0smeta, (size_t)4);
-        h->ref_l0k = pk; h->ref_l0s = ps;
-    }
+    DevAlloc da{h, "lin, elbo_counter"};
+    h->lin = da.floats((size_t)h->S);
+    h->elbo_counter = (unsigned*)da.floats(4);
+    alloc_decoder_tuned(h, da);
+    alloc_refine_tuned(h, da);
+    alloc_head(h, da);
+    if (dec_path(h) == DEC_GENERIC) alloc_decoder_generic(h, da);
+    if (ref_family(h) == REF_GENERIC) alloc_refine_generic(h, da);
     // gradient accumulators: ONE buffer, parameters back to back in named_parameters() order (the layout the wrapper's
     // flat gradient buffer has too), so that zeroing and the final scale-and-add are one launch each
     h->gacc.assign(h->params.size(), nullptr);
     h->gacc_total = 0;
     for (size_t i = 0; i < h->params.size(); ++i) h->gacc_total += h->params[i].numel();
-    ALLOC(h->gacc_arena, h->gacc_total);
+    da.in("gradient accumulators");
+    h->gacc_arena = da.floats(h->gacc_total);
+    if (da.err != hipSuccess) return bail(da.err, (std::string("hipMalloc, ") + da.group).c_str());
     {
         size_t off = 0;
         for (size_t i = 0; i < h->params.size(); ++i) { h->gacc[i] = h->gacc_arena + off; off += h->params[i].numel(); }
     }
-#undef ALLOC
+    if (hipError_t e_ = hipMemset(h->elbo_counter, 0, 16); e_ != hipSuccess) return bail(e_, "hipMemset elbo_counter");
     std::vector<float> lin(h->S);
     iodine_linspace_host(h->S, lin.data());
     hipError_t e = hipMemcpy(h->lin, lin.data(), sizeof(float) * h->S, hipMemcpyHostToDevice);

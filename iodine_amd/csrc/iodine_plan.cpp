@@ -148,7 +148,7 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
         b.wg_part = a.take<float>(part_elems);
         b.wg_part_b = a.take<float>((size_t)512 * 64);
         b.wg_acc.assign(h->Dd, nullptr); b.wg_acc_b.assign(h->Dd, nullptr);
-        if (h->wgrad_accum && !gen_dec && mode == 1) {      // (a single pass has nothing to accumulate over: shared scratch)
+        if (h->opt.wgrad_accum && !gen_dec && mode == 1) {      // (a single pass has nothing to accumulate over: shared scratch)
             b.wg_acc[0] = a.take<float>((size_t)1024 * 2 * 9 * Cd * 4);       // dec_out_bwd_fused: <= 1024 blocks x KS <= 2 tiles of [9][Cd][4]
             b.wg_acc_b[0] = a.take<float>((size_t)1024 * 4);
             for (int l = 1; l < h->Dd; ++l) {
@@ -189,7 +189,7 @@ void plan(const iodine_handle* h, int B, int mode, Arena& a, Buffers& b)
     b.sg_part = a.take<double>((size_t)B * pixel_blocks_per_image(P));
     b.sgrad = a.take<float>((size_t)T + 1);
     // option input_grad: carved only while a bit is set, behind everything else - with the option off the plan is what it was
-    b.ig = h->input_grad;
+    b.ig = h->opt.input_grad;
     b.ig_x = (b.ig & 1) ? a.take<float>((size_t)b.F * B * 3 * P) : nullptr;
     b.ig_w = (b.ig & 2) ? a.take<float>((size_t)b.F * B * P) : nullptr;
     b.bytes = (a.off + 255) & ~(size_t)255;
@@ -208,7 +208,7 @@ void drop_graphs(iodine_handle* h)
 int ensure_workspace(iodine_handle* h, int B, int mode)
 {
     if (h->buf.B == B && h->buf.mode == mode && h->buf.K == h->K && h->buf.T == h->T && h->buf.F == (h->frames > 0 ? h->frames : 1) &&
-        h->buf.ig == h->input_grad && h->buf.bytes > 0)
+        h->buf.ig == h->opt.input_grad && h->buf.bytes > 0)
         return IODINE_OK;
     Arena q(nullptr); Buffers tmp; plan(h, B, mode, q, tmp);
     void* base = nullptr;
@@ -258,8 +258,8 @@ std::vector<uintptr_t> graph_key(const iodine_handle* h, int entry, int batch, s
     if (!o) o = &h->obj;
     uint64_t sb, bb;
     memcpy(&sb, &o->sigma, 8); memcpy(&bb, &o->beta, 8);
-    std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->K, (uintptr_t)h->T, (uintptr_t)h->stop_after, (uintptr_t)h->precision,
-                                (uintptr_t)h->variant, (uintptr_t)h->fuse_l0, (uintptr_t)h->out_bwd_fused, (uintptr_t)h->refine_split, (uintptr_t)(h->head_fused | (h->refine_bwd_fused << 1) | (h->refine_ws << 2) | (h->refine_l0_fused << 3) | (h->head_mfma << 4) | (h->wgrad_accum << 5) | (h->dec_out_rows << 6) | (h->gen_precision << 7) | (h->sigma_grad << 8) | (h->stable_enc << 9) | (h->input_grad << 10) | (h->joint_ll << 12)),
+    std::vector<uintptr_t> k = {(uintptr_t)entry, (uintptr_t)batch, (uintptr_t)h->K, (uintptr_t)h->T, (uintptr_t)h->opt.stop_after, (uintptr_t)h->opt.precision,
+                                (uintptr_t)h->opt.variant, (uintptr_t)h->opt.fuse_l0, (uintptr_t)h->opt.out_bwd_fused, (uintptr_t)h->opt.refine_split, (uintptr_t)(h->opt.head_fused | (h->opt.refine_bwd_fused << 1) | (h->opt.refine_ws << 2) | (h->opt.refine_l0_fused << 3) | (h->opt.head_mfma << 4) | (h->opt.wgrad_accum << 5) | (h->opt.dec_out_rows << 6) | (h->opt.gen_precision << 7) | (h->opt.sigma_grad << 8) | (h->opt.stable_enc << 9) | (h->opt.input_grad << 10) | (h->opt.joint_ll << 12)),
                                 (uintptr_t)(h->ws_user ? h->ws_user : h->ws_own), (uintptr_t)h->frames};
     k.push_back((uintptr_t)sb); k.push_back((uintptr_t)bb); k.push_back((uintptr_t)o->wgen);
     k.push_back((uintptr_t)(pw ? pw->w : nullptr)); k.push_back((uintptr_t)(pw ? pw->per_frame : 0));

@@ -54,12 +54,12 @@ int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x
             HIPCHK(h, hipMemcpyAsync(b.h[0], state_in[2], sizeof(float) * (size_t)N * h->H, hipMemcpyDeviceToDevice, st));
             HIPCHK(h, hipMemcpyAsync(b.c[0], state_in[3], sizeof(float) * (size_t)N * h->H, hipMemcpyDeviceToDevice, st));
         } else
-            HIPCHK(h, launch_posterior_init(st, h->init_mean, h->init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, L, h->H));
+            HIPCHK(h, launch_posterior_init(st, h->head.init_mean, h->head.init_logvar, b.pm, b.plv, b.h[0], b.c[0], N, L, h->H));
         int fj = 0;                                        // next entry of the list of chosen evaluations
         for (int i = 0; i <= T; ++i) {
             // d loss / d (B * ELBO_i) = -w_i / B; the default weighting keeps its closed form
             const float alpha = h->obj.whost ? -h->obj.whost[i] / (float)B : -((float)(i + 1) / (float)(T + 1)) / (float)B;
-            int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, true, alpha, h->sigma_grad != 0, h->input_grad, -alpha);
+            int r = elbo_and_gradients(h, st, B, eps + (size_t)i * eps_stride, i, true, true, alpha, h->opt.sigma_grad != 0, h->opt.input_grad, -alpha);
             if (r) return r;
             if (fr && fj < fr->n && fr->idx[fj] == i) {
                 // what this evaluation decoded and the lambda it sampled from (buf.pm / plv: the refinement step below moves them on);
@@ -110,8 +110,8 @@ int train_forward_impl(iodine_handle* h, void* stream, int batch, const float* x
     cs.fwd_split = ref_form(h).split;      // layout of the saved refinement inputs (refine_split is part of the graph key)
     cs.last_elbo_iter = T;
     cs.last_elbo_batch = B;
-    cs.sgrad_n = h->sigma_grad ? T + 1 : 0;
-    cs.ig_bits = h->input_grad; cs.ig_frames = h->frames > 0 ? h->frames : 0; cs.ig_wpf = h->ig_call_wpf;
+    cs.sgrad_n = h->opt.sigma_grad ? T + 1 : 0;
+    cs.ig_bits = h->opt.input_grad; cs.ig_frames = h->frames > 0 ? h->frames : 0; cs.ig_wpf = h->ig_call_wpf;
     return IODINE_OK;
 }
 
@@ -137,13 +137,13 @@ int aux_seeds_final(iodine_handle* h, hipStream_t st, const AuxCot* aux, BpttSee
     Buffers& b = h->buf;
     const int B = h->calls.fwd_batch, N = B * h->K, T = h->T, L = h->L;
     const bool dec = aux->mean || aux->mask || aux->logits;
-    const float* const wl = dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT;
+    const float* const wl = dec_path(h) == DEC_GENERIC ? h->gen.ident : h->dec.wclsT;
     if (dec) {
         // evaluation T's decoder activations and dec_out are still in the arena: the forward's last launches were that evaluation's own
         // decoder backward, which only reads them, and any compute call since would have cleared fwd_done.  ONE decoder pass with
         // factor 1: every decoder weight gradient, and the class sums of the broadcast layer for dz
         PROF(h, st, "render_bwd", launch_render_bwd_logits(st, b.dec_out, nullptr, aux->mask, aux->mean, aux->logits, b.g, B, h->K, h->P,
-                                                           h->precision == 0));
+                                                           h->opt.precision == 0));
         float* dpre0 = nullptr;
         if (int r = decoder_backward_data(h, st, N, &dpre0, true, 1.f, T, true)) return r;
     }
@@ -160,7 +160,7 @@ int aux_seeds_frames(iodine_handle* h, hipStream_t st, const AuxCot* aux, const 
     const ParamSlots& ps = h->slot;
     const size_t NL = (size_t)N * L, NP = (size_t)N * h->P;
     const bool dec = aux->mean || aux->mask || aux->logits;
-    const float* const wl = dec_path(h) == DEC_GENERIC ? h->gen_ident : h->wclsT;
+    const float* const wl = dec_path(h) == DEC_GENERIC ? h->gen.ident : h->dec.wclsT;
     // Cotangents on chosen evaluations.  Evaluation T (last in the list) first, on the kept activations like the final state's
     // cotangents (aux_seeds_final) - and added to them where both are given: the rendering backward is linear in the cotangents, so the
     // second set is rendered into the (free) ping-pong buffer and added before the ONE decoder pass.
@@ -170,10 +170,10 @@ int aux_seeds_frames(iodine_handle* h, hipStream_t st, const AuxCot* aux, const 
     const bool decf = t_mean || t_mask || t_logits;
     if (dec)
         PROF(h, st, "render_bwd", launch_render_bwd_logits(st, b.dec_out, nullptr, aux->mask, aux->mean, aux->logits, b.g, B, h->K, h->P,
-                                                           h->precision == 0));
+                                                           h->opt.precision == 0));
     if (decf)
         PROF(h, st, "render_bwd", launch_render_bwd_logits(st, b.dec_out, nullptr, t_mask, t_mean, t_logits, dec ? b.dpre[0] : b.g, B, h->K,
-                                                           h->P, h->precision == 0));
+                                                           h->P, h->opt.precision == 0));
     if (dec && decf) HIPCHK(h, launch_axpy_dev(st, b.dpre[0], 1.f, nullptr, b.g, (int)(NP * 4), 1));
     float* dpre0 = nullptr;
     if (dec || decf)
@@ -195,10 +195,10 @@ int aux_seeds_frames(iodine_handle* h, hipStream_t st, const AuxCot* aux, const 
         const bool deci = c_mean || c_mask || c_logits;
         if (!deci && !c_z && !c_pm && !c_plv) continue;
         if (deci) {
-            HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, b.z[i], h->wcls, nullptr, b.V, N, L, h->Cd));
+            HIPCHK(h, launch_dec_v(st, nullptr, nullptr, nullptr, b.z[i], h->dec.wcls, nullptr, b.V, N, L, h->Cd));
             if (int r = decoder_forward(h, st, N, b.z[i])) return r;
             PROF(h, st, "render_bwd", launch_render_bwd_logits(st, b.dec_out, nullptr, c_mask, c_mean, c_logits, b.g, B, h->K, h->P,
-                                                               h->precision == 0));
+                                                               h->opt.precision == 0));
             if (int r = decoder_backward_data(h, st, N, &dpre0, true, 1.f, i, true)) return r;
         }
         HIPCHK(h, launch_latent_seed(st, deci ? b.Rc : nullptr, wl, N, L, h->Cd, c_z, c_pm, c_plv, b.z[i], b.latent[i],
@@ -232,18 +232,18 @@ int head_bptt(iodine_handle* h, hipStream_t st, const AuxCot* aux, const Objecti
     const int B = h->calls.fwd_batch, N = B * h->K, T = h->T, L = h->L, H = h->H, Cr = h->Cr;
     const float *cot_h = aux ? aux->lstm_h : nullptr, *cot_c = aux ? aux->lstm_c : nullptr;
     float *gs_h = aux && aux->g_state ? aux->g_state[2] : nullptr, *gs_c = aux && aux->g_state ? aux->g_state[3] : nullptr;
-    if (h->head_fused && head_bptt_fits(L, H, Cr)) {
+    if (h->opt.head_fused && head_bptt_fits(L, H, Cr)) {
         // the whole BPTT recurrence of the head in one launch (rows are independent: a block walks i = T-1 .. 0 for its rows)
-        PROF(h, st, "head_bwd", launch_head_bptt(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->raw_wm, h->raw_wv, h->raw_whh,
-                                                 h->raw_wih, h->raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr,
+        PROF(h, st, "head_bwd", launch_head_bptt(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->head.raw_wm, h->head.raw_wv, h->head.raw_whh,
+                                                 h->head.raw_wih, h->head.raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr,
                                                  s.seed_m, s.seed_v, aux ? aux->gl : nullptr, obj.wtab, cot_h, cot_c, gs_h, gs_c,
                                                  s.seed_stride));
     } else {
         // the same recurrence as a launch sequence (9 launches per iteration)
         float* const ch[2] = {b.carry_h[0], b.carry_h[1]};
         float* const cc[2] = {b.carry_c[0], b.carry_c[1]};
-        HIPCHK(h, launch_head_bptt_unfused(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->raw_wm, h->raw_wv, h->raw_whh, h->raw_wih,
-                                           h->raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr, aux != nullptr, s.seed_m, s.seed_v,
+        HIPCHK(h, launch_head_bptt_unfused(st, b.g_pm[0], b.g_plv[0], b.gates[0], b.c[0], b.u[0], h->head.raw_wm, h->head.raw_wv, h->head.raw_whh, h->head.raw_wih,
+                                           h->head.raw_mlp_w, b.ddm, b.ddv, b.dgates, b.ds, b.dpooled, T, N, B, L, H, Cr, aux != nullptr, s.seed_m, s.seed_v,
                                            aux ? aux->gl : nullptr, obj.whost, cot_h, cot_c, gs_h, gs_c, s.seed_stride, b.dc1, b.dxin, ch, cc));
     }
     return IODINE_OK;

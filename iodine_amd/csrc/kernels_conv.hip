@@ -462,7 +462,7 @@ hipError_t launch_pack_conv_weights_f16(hipStream_t st, const float* src, int O,
                                         float* meta, void* dst)
 {
     hipLaunchKernelGGL(weight_scale_kernel, dim3(1), dim3(1024), 0, st, src, O * I * 9, meta);
-    const size_t total = (size_t)(cin / 16) * 9 * 2 * 2 * cout * 8;
+    const size_t total = wpk_tile_f16_vecs(cin, cout) * 8;
     hipLaunchKernelGGL(pack_conv_weights_f16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, O, I,
                        cin, cout, tflip, meta, (_Float16*)dst);
     return hipGetLastError();
@@ -488,7 +488,7 @@ void conv3x3_tile_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
     constexpr int HALO = 18, NPX = HALO * (TH + 2);
     constexpr int PXS = 80;                              // bytes per staged pixel: 32 hi + 32 lo + 16 pad
     constexpr int IN_BYTES = (NPX + 1) * PXS;            // +1 pixel: dump slot for idle lanes
-    constexpr int W_U4 = 9 * 2 * 2 * COUT;               // uint4 (8 x fp16) per chunk
+    constexpr int W_U4 = (int)wpk_tile_f16_vecs(16, COUT);   // uint4 (8 x fp16) per chunk
     constexpr int NIN = (NPX * 4 + 255) / 256;           // float4 loads per thread per chunk (6)
     constexpr int NW = (W_U4 + 255) / 256;               // uint4 loads per thread per chunk
 
@@ -881,7 +881,7 @@ template <int CIN, int COUT, int EPI, int TH>
 static hipError_t launch_tile_f16x3_inst(hipStream_t st, const float* in, const void* wpk, const float* wmeta,
                                          const float* bias, const float* aux, float* out, int N, int S, int rev)
 {
-    constexpr size_t lds_stage = (size_t)(18 * (TH + 2) + 1) * 80 + (size_t)9 * 2 * 2 * COUT * 16 + 16;
+    constexpr size_t lds_stage = (size_t)(18 * (TH + 2) + 1) * 80 + wpk_tile_f16_bytes(16, COUT) + 16;   // halo + one chunk of the pack
     constexpr size_t lds_epi = (size_t)4 * (TH * 4) * (COUT + 4) * 4;              // output tile, transposed for contiguous stores
     constexpr size_t lds = lds_stage > lds_epi ? lds_stage : lds_epi;
     static std::atomic<unsigned> attr_devs{0};                             // devices this instance is configured on

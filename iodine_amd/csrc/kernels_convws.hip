@@ -23,8 +23,7 @@
 #include <cstdio>
 #include <vector>
 
-// ---- packed weights: [cout group][chunk of 32 cin][tap][hi/lo][lane][8 fp16] = the A operand of v_mfma_f32_16x16x32_f16
-// (lane l: row = cout 16 cg + l % 16, k = cin 32 c + 8 (l / 16) .. + 7), pre-scaled by meta[0] (weight_scale_kernel) -------
+// ---- packed weights (wpk_ws_vecs), pre-scaled by meta[0] (weight_scale_kernel) -------
 __global__ void pack_conv_weights_ws_kernel(const float* __restrict__ src, int C, int tflip, const float* __restrict__ meta,
                                             _Float16* __restrict__ dst)
 {
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(1024) void weight_scale_ws_kernel(const float* __re
 hipError_t launch_pack_conv_weights_ws(hipStream_t st, const float* src, int C, int tflip, float* meta, void* dst)
 {
     hipLaunchKernelGGL(weight_scale_ws_kernel, dim3(1), dim3(1024), 0, st, src, C * C * 9, meta);
-    const size_t total = (size_t)(C / 16) * (C / 32) * 9 * 2 * 64 * 8;
+    const size_t total = wpk_ws_vecs(C) * 8;
     hipLaunchKernelGGL(pack_conv_weights_ws_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, C, tflip,
                        meta, (_Float16*)dst);
     return hipGetLastError();
@@ -797,7 +796,7 @@ hipError_t launch_conv3x3_ws_f16x3(hipStream_t st, const float* in, const void* 
 // cin 32 c + 16 half + 4 (l / 16) + j for the j-th MFMA over a 16-byte activation fragment (K index of that MFMA = l / 16)
 __global__ void pack_conv_weights_ws32_kernel(const float* __restrict__ src, int C, int tflip, float* __restrict__ dst)
 {
-    const size_t total = (size_t)(C / 16) * (C / 32) * 9 * 2 * 64 * 4;
+    const size_t total = wpk_ws_vecs(C) * 4;
     const int nchunk = C / 32;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int j = idx & 3;
@@ -815,7 +814,7 @@ __global__ void pack_conv_weights_ws32_kernel(const float* __restrict__ src, int
 
 hipError_t launch_pack_conv_weights_ws32(hipStream_t st, const float* src, int C, int tflip, void* dst)
 {
-    const size_t total = (size_t)(C / 16) * (C / 32) * 9 * 2 * 64 * 4;
+    const size_t total = wpk_ws_vecs(C) * 4;
     hipLaunchKernelGGL(pack_conv_weights_ws32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, C, tflip, (float*)dst);
     return hipGetLastError();
 }

@@ -42,7 +42,7 @@ struct GSplitGeo {
 };
 
 // bytes of one slice image (hi + lo) and of the kernel's LDS
-inline size_t gsplit_slice_bytes(int k, int C, int cch) { const int tpm = 32 / cch; return (size_t)(C / cch) * ((k * k + tpm - 1) / tpm) * 2048; }
+inline size_t gsplit_slice_bytes(int k, int C, int cch) { return wpk_gen_split_slice_bytes(k, C, cch); }
 inline size_t gsplit_lds_bytes(int k, int C, int cch)
 {
     const int tw = 16 + k - 1, npxp = (tw * tw + 15) / 16 * 16;
@@ -481,7 +481,7 @@ int gen_split_cch(int k, int C)
 size_t gen_split_pack_bytes(int k, int C)
 {
     const int cch = gen_split_cch(k, C);
-    return cch ? (size_t)(C / 16) * gsplit_slice_bytes(k, C, cch) : 0;
+    return cch ? wpk_gen_split_bytes(k, C, cch) : 0;
 }
 
 // wt: the generic pack [tap][ci][co] of a C -> C layer; dgrad = 1: the slices of the data gradient (flipped taps, reduction over co)

@@ -29,7 +29,7 @@ void dec_out_stream_f16x3_kernel(const float* __restrict__ in, const uint4* __re
 {
     constexpr int NCHUNK = C / 16;
     constexpr int HALO = 18, NPX = HALO * HALO;                     // 324 halo pixels = 11 row-blocks of 32 (last partial)
-    constexpr int W_U4 = NCHUNK * 2 * 2 * 64;                       // [chunk][term hi/lo][kh][64 columns] uint4
+    constexpr int W_U4 = (int)wpk_out_gemm_vecs(C);                 // [chunk][term hi/lo][kh][64 columns] uint4
     constexpr int PSTR = 36;                                        // floats per pixel in the P tile
     constexpr int NLD = NCHUNK * 2;                                 // float4 loads per lane and row-block
 
@@ -197,7 +197,7 @@ hipError_t launch_dec_out_stream_f16x3(hipStream_t st, const float* in, const vo
     const int tiles = S / 16, ntiles = N * tiles * tiles;
     const int blocks = ntiles < 512 ? ntiles : 512;                 // two resident blocks per CU (63 KB LDS each), persistent
 #define DO_LAUNCH(CC, TMF) hipLaunchKernelGGL((dec_out_stream_f16x3_kernel<CC, TMF>), dim3(blocks), dim3(256),                                \
-                                              (size_t)(CC / 16) * 2 * 2 * 64 * 16 + 324 * 36 * 4, st, in, reinterpret_cast<const uint4*>(wpk), \
+                                              wpk_out_gemm_bytes(CC) + 324 * 36 * 4, st, in, reinterpret_cast<const uint4*>(wpk), \
                                               wmeta, bias, reinterpret_cast<float4*>(out), S, tiles, ntiles, tmax)
     if (C == 64) { if (tmax) DO_LAUNCH(64, true); else DO_LAUNCH(64, false); }
     else if (C == 32) { if (tmax) DO_LAUNCH(32, true); else DO_LAUNCH(32, false); }
@@ -411,11 +411,10 @@ void dec_out_rows_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
 
 bool dec_out_rows_ok(int S, int C, const float* tmax) { return tmax && (S == 32 || S == 64 || S == 128) && (C == 64 || C == 32); }
 
-// fp32 weights of the F32 form: dst[(nt * (C / 2) + ks) * 64 + lane] = W[column nt * 32 + lane % 32 (= tap * 4 + co, zero from 36)][channel of
-// (k-step ks, half wave lane / 32) = 16 (ks / 8) + 8 (lane / 32) + ks % 8]
+// fp32 weights of the F32 form (wpk_out_rows32_floats)
 __global__ void pack_dec_out_rows32_kernel(const float* __restrict__ w /*[4][C][3][3]*/, int C, float* __restrict__ dst)
 {
-    const int total = 2 * (C / 2) * 64;
+    const int total = (int)wpk_out_rows32_floats(C);
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int lane = idx & 63, ks = (idx >> 6) % (C / 2), nt = (idx >> 6) / (C / 2);
         const int j = nt * 32 + (lane & 31), ci = 16 * (ks / 8) + 8 * (lane >> 5) + ks % 8;
@@ -488,7 +487,7 @@ void dec_out_dgrad_f16x3_kernel(const float4* __restrict__ g, const uint4* __res
 {
     constexpr int NT = C / 32;
     constexpr int HALO = 18, NPX = HALO * HALO;
-    constexpr int W_U4 = 3 * 2 * 2 * C;
+    constexpr int W_U4 = (int)wpk_out_dgrad_vecs(C);
     constexpr int EPS = (C + 4) * 4;                                // bytes per transposed pixel
     constexpr int SEGS = C / 4, PPI = 64 / SEGS, NEP = 32 / PPI;    // per 32-pixel half tile of a wave
 
@@ -606,11 +605,11 @@ hipError_t launch_dec_out_dgrad_f16x3(hipStream_t st, const float* g, const void
     if (S % 16 != 0) return hipErrorInvalidValue;
     const int tiles = S / 16;
     if (C == 64) {
-        constexpr size_t lds = (size_t)324 * 16 + 3 * 2 * 2 * 64 * 16 + 16 + 4 * 32 * (64 + 4) * 4;
+        constexpr size_t lds = (size_t)324 * 16 + wpk_out_dgrad_bytes(64) + 16 + 4 * 32 * (64 + 4) * 4;
         hipLaunchKernelGGL((dec_out_dgrad_f16x3_kernel<64>), dim3(N * tiles * tiles), dim3(256), lds, st, (const float4*)g,
                            (const uint4*)wpk, wmeta, aux, out, tmax, S, tiles);
     } else if (C == 32) {
-        constexpr size_t lds = (size_t)324 * 16 + 3 * 2 * 2 * 32 * 16 + 16 + 4 * 32 * (32 + 4) * 4;
+        constexpr size_t lds = (size_t)324 * 16 + wpk_out_dgrad_bytes(32) + 16 + 4 * 32 * (32 + 4) * 4;
         hipLaunchKernelGGL((dec_out_dgrad_f16x3_kernel<32>), dim3(N * tiles * tiles), dim3(256), lds, st, (const float4*)g,
                            (const uint4*)wpk, wmeta, aux, out, tmax, S, tiles);
     } else {

@@ -229,7 +229,7 @@ void dec_out_bwd_fused_f16x3_kernel(const float* __restrict__ a, const float* __
     constexpr int NB_UNITS = TH * 8 * A4, NBU = NB_UNITS / 256;
     constexpr int NG_UNITS = (TH + 2) * 9;
     constexpr int HW = 18;                               // fp32 gradient halo: 6 rows x 18 columns
-    constexpr int W_U4 = 3 * 2 * 2 * C;                  // packed data-gradient weights (pack_dec_out_dgrad_kernel)
+    constexpr int W_U4 = (int)wpk_out_dgrad_vecs(C);     // packed data-gradient weights (pack_dec_out_dgrad_kernel)
     constexpr int EPD = C + 4;                           // dwords per transposed pixel
     constexpr int NDW = 2 * NTT;                         // waves that own a 32 channel x 32 pixel block of the data gradient
     static_assert(NB_UNITS % 256 == 0, "activation tile units");

@@ -405,7 +405,7 @@ namespace {
 // element e of slot (term, kh, co) = input channel 16 chunk + 8 kh + 4 term + e (tflip as in pack_f16_element)
 __global__ void pack_conv_weights_s2f32_kernel(const float* __restrict__ src, int O, int I, int cin, int cout, int tflip, float* __restrict__ dst)
 {
-    const size_t total = (size_t)(cin / 16) * 9 * 2 * 2 * cout * 4;
+    const size_t total = wpk_tile_f16_vecs(cin, cout) * 4;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int e = idx & 3;
         size_t r = idx >> 2;
@@ -426,7 +426,7 @@ __global__ void pack_conv_weights_s2f32_kernel(const float* __restrict__ src, in
 
 hipError_t launch_pack_conv_weights_s2f32(hipStream_t st, const float* src, int O, int I, int cin, int cout, int tflip, void* dst)
 {
-    const size_t total = (size_t)(cin / 16) * 9 * 2 * 2 * cout * 4;
+    const size_t total = wpk_tile_f16_vecs(cin, cout) * 4;
     hipLaunchKernelGGL(pack_conv_weights_s2f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, O, I, cin, cout, tflip,
                        (float*)dst);
     return hipGetLastError();

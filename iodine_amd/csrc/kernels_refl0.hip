@@ -392,8 +392,6 @@ hipError_t l0_launch(hipStream_t st, const float* x4, const float* dec, const fl
 
 }  // namespace
 
-size_t refine_l0_wpk_bytes(int O) { return (size_t)(O / 16) * 9 * 2 * 64 * 8; }
-
 bool refine_l0_fused_ok(int S, int c, int K) { return c == 64 && S >= 32 && S % 32 == 0 && K >= 1 && K <= 9; }
 
 // Encoding + first refinement layer for all K slots of B images: out [B K][S/2][S/2][64] = ELU(conv_s2(encoding) + bias).

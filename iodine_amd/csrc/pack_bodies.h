@@ -3,8 +3,9 @@
 // write the same bits.
 #pragma once
 #include "device.h"
+#include "pack_geom.h"
 
-// element idx of the weight-stationary register layout (kernels_convws.hip): [cout group][chunk of 32 cin][tap][hi/lo][lane][8 fp16]
+// element idx of the weight-stationary register layout (wpk_ws_vecs)
 IOD_DEVINL _Float16 pack_ws_element(const float* __restrict__ src, int C, int tflip, float scale, size_t idx)
 {
     const int nchunk = C / 32;
@@ -22,9 +23,9 @@ IOD_DEVINL _Float16 pack_ws_element(const float* __restrict__ src, int C, int tf
     const _Float16 hi = (_Float16)v;
     return hl == 0 ? hi : (_Float16)(v - (float)hi);
 }
-IOD_DEVINL size_t pack_ws_total(int C) { return (size_t)(C / 16) * (C / 32) * 9 * 2 * 64 * 8; }
+IOD_DEVINL size_t pack_ws_total(int C) { return wpk_ws_vecs(C) * 8; }
 
-// element idx of the LDS-tile layout (kernels_conv.hip): [chunk of 16 cin][tap][hi/lo][k half][cout][8 fp16]
+// element idx of the LDS-tile layout (wpk_tile_f16_vecs)
 IOD_DEVINL _Float16 pack_f16_element(const float* __restrict__ src, int O, int I, int cout, int tflip, float scale, size_t idx)
 {
     const int e = idx & 7;
@@ -43,9 +44,9 @@ IOD_DEVINL _Float16 pack_f16_element(const float* __restrict__ src, int O, int I
     const _Float16 hi = (_Float16)v;
     return term == 0 ? hi : (_Float16)(v - (float)hi);
 }
-IOD_DEVINL size_t pack_f16_total(int cin, int cout) { return (size_t)(cin / 16) * 9 * 2 * 2 * cout * 8; }
+IOD_DEVINL size_t pack_f16_total(int cin, int cout) { return wpk_tile_f16_vecs(cin, cout) * 8; }
 
-// element idx of the fused first refinement layer's operand (kernels_refl0.hip): [O / 16][9 taps][hi / lo][64 lanes] x 4 fp16
+// element idx of the fused first refinement layer's operand (wpk_l0_vecs)
 IOD_DEVINL _Float16 pack_l0_element(const float* __restrict__ w, int CINW, float scale, size_t idx)
 {
     const int j = idx & 3, lane = (idx >> 2) & 63, hl = (idx >> 8) & 1, tap = (int)((idx >> 9) % 9), g = (int)((idx >> 9) / 9);
@@ -54,9 +55,9 @@ IOD_DEVINL _Float16 pack_l0_element(const float* __restrict__ w, int CINW, float
     const _Float16 hi = (_Float16)v;
     return hl == 0 ? hi : (_Float16)(v - (float)hi);
 }
-IOD_DEVINL size_t pack_l0_total(int O) { return (size_t)(O / 16) * 9 * 2 * 64 * 4; }
+IOD_DEVINL size_t pack_l0_total(int O) { return wpk_l0_vecs(O) * 4; }
 
-// element idx of the output conv's GEMM-form operand (kernels_conv.hip: pack_dec_out_gemm_kernel)
+// element idx of the output conv's GEMM-form operand (wpk_out_gemm_vecs; kernels_conv.hip: pack_dec_out_gemm_kernel)
 IOD_DEVINL _Float16 pack_out_gemm_element(const float* __restrict__ w, int C, float scale, size_t idx)
 {
     const int e = idx & 7;
@@ -70,9 +71,9 @@ IOD_DEVINL _Float16 pack_out_gemm_element(const float* __restrict__ w, int C, fl
     const _Float16 hi = (_Float16)v;
     return term == 0 ? hi : (_Float16)(v - (float)hi);
 }
-IOD_DEVINL size_t pack_out_gemm_total(int C) { return (size_t)(C / 16) * 2 * 2 * 64 * 8; }
+IOD_DEVINL size_t pack_out_gemm_total(int C) { return wpk_out_gemm_vecs(C) * 8; }
 
-// element idx of the output conv's data-gradient operand (kernels_out.hip: pack_dec_out_dgrad_kernel)
+// element idx of the output conv's data-gradient operand (wpk_out_dgrad_vecs; kernels_out.hip: pack_dec_out_dgrad_kernel)
 IOD_DEVINL _Float16 pack_out_dgrad_element(const float* __restrict__ w, int C, float scale, size_t idx)
 {
     const int e = idx & 7;
@@ -86,7 +87,7 @@ IOD_DEVINL _Float16 pack_out_dgrad_element(const float* __restrict__ w, int C, f
     const _Float16 hi = (_Float16)v;
     return term == 0 ? hi : (_Float16)(v - (float)hi);
 }
-IOD_DEVINL size_t pack_out_dgrad_total(int C) { return (size_t)3 * 2 * 2 * C * 8; }
+IOD_DEVINL size_t pack_out_dgrad_total(int C) { return wpk_out_dgrad_vecs(C) * 8; }
 
 // max |w| of a tensor (block of 1024 threads) -> meta[0] = power-of-two scale with max * scale in [2^12, 2^13), meta[1] = 1 / scale
 IOD_DEVINL void weight_scale_block(const float* __restrict__ w, int n, float* __restrict__ meta, float* s_red /*[16]*/)

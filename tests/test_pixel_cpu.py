@@ -41,9 +41,12 @@ def test_header_binding_and_refusals():
     assert 'iodine_op_pixel_encode' in _lib.EXPORTS
     # the production launchers, in the library's order
     body = ops[ops.index('int iodine_op_pixel_encode('):ops.index('int iodine_op_conv3x3_wgrad_f32(')]
-    order = [body.index(n) for n in ('launch_x_to_nhwc4(', 'launch_pixel_pass1(', 'launch_pixel_finalize_elbo(', 'launch_pixel_sigma_grad(',
-                                     'launch_pixel_pass2(', 'launch_final_out(', 'hipStreamSynchronize(', 'hipFree(')]
+    order = [body.index(n) for n in ('OpScratch scr(', 'launch_x_to_nhwc4(', 'launch_pixel_pass1(', 'launch_pixel_finalize_elbo(',
+                                     'launch_pixel_sigma_grad(', 'launch_pixel_pass2(', 'launch_final_out(', 'return op_done(')]
     assert order == sorted(order)
+    # ... where op_done synchronises and the scratch frees itself when the entry returns, behind that wait
+    assert 'hipStreamSynchronize(' in ops[ops.index('int op_done('):ops.index('constexpr size_t META_BYTES')]
+    assert 'hipFree(' in ops[ops.index('~OpScratch()'):].split('\n')[0]
     L = _lib.lib()
     assert hasattr(L, 'iodine_op_pixel_encode') and L.iodine_abi_version() == 3              # additive
     # refused on the host, before anything is allocated or launched (host tensors: a launch would not survive them)

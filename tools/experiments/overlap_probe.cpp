@@ -38,8 +38,8 @@ int main(int argc, char** argv)
     float* enc = dev_rand((size_t)N * S * S * 20, -1.f, 1.f, 7);
     float* w20 = dev_rand((size_t)C * 17 * 9, -0.1f, 0.1f, 8);
     // packs
-    char* wsp; CK(hipMalloc((void**)&wsp, conv_ws_wpk_bytes(C) + 64));
-    float* wsmeta = (float*)(wsp + conv_ws_wpk_bytes(C));
+    char* wsp; CK(hipMalloc((void**)&wsp, wpk_ws_bytes(C) + 64));
+    float* wsmeta = (float*)(wsp + wpk_ws_bytes(C));
     CK(launch_pack_conv_weights_ws(0, w, C, 0, wsmeta, wsp));
     float *tin, *tout; CK(hipMalloc((void**)&tin, conv_ws_tmax_floats(N, S) * 4)); CK(hipMalloc((void**)&tout, conv_ws_tmax_floats(N, S) * 4));
     CK(launch_cell_max(0, act, tin, N, S, C));

@@ -45,8 +45,8 @@ int main(int argc, char** argv)
     float* wo = dev_rand((size_t)4 * C * 9, -0.1f, 0.1f, 5);
     float* bias = dev_rand(C, -0.1f, 0.1f, 6);
     float* o4; CK(hipMalloc((void**)&o4, (size_t)N * S * S * 4 * 4));
-    char* wsp; CK(hipMalloc((void**)&wsp, conv_ws_wpk_bytes(C) + 64));
-    float* wsmeta = (float*)(wsp + conv_ws_wpk_bytes(C));
+    char* wsp; CK(hipMalloc((void**)&wsp, wpk_ws_bytes(C) + 64));
+    float* wsmeta = (float*)(wsp + wpk_ws_bytes(C));
     CK(launch_pack_conv_weights_ws(0, w, C, 0, wsmeta, wsp));
     char* op; CK(hipMalloc((void**)&op, 1 << 20)); float* ometa; CK(hipMalloc((void**)&ometa, 64));
     CK(launch_pack_dec_out_gemm(0, wo, C, ometa, op));
