@@ -2,23 +2,10 @@
 // per-device caches.  Device-side helpers are in device.h.
 #pragma once
 #include "device.h"
+#include "launch.h"
 #include <algorithm>
 #include <atomic>
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) belongs to (function, device): every launcher instance keeps a bit mask of
-// the devices it has configured (`devs`, a function-local static) instead of one process-wide flag, so a second device in the
-// same process - tests, one handle per device - gets the attribute too.  Idempotent, so a race between two threads is benign.
-inline hipError_t iod_set_max_lds(const void* fn, int bytes, std::atomic<unsigned>& devs)
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned bit = 1u << (dev & 31);
-    if (devs.load(std::memory_order_acquire) & bit) return hipSuccess;
-    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) devs.fetch_or(bit, std::memory_order_release);
-    return e;
-}
 // compute units of the CURRENT device (persistent grids are sized from it), cached per device
 inline hipError_t iod_cu_count(int* n_cu)
 {

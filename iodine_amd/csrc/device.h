@@ -66,26 +66,8 @@ IOD_DEVINL float wave_max_f32(float v)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-// Phase timing of the tile / weight-gradient kernels (tools/tile_phase_prof.md; build with IODINE_EXTRA_HIPCC_FLAGS=-DIODINE_TILE_PROF): thread 0 of every
-// block accumulates the s_memtime deltas between phase boundaries and writes them to a per-kernel __device__ buffer
-// [block][8]; compiled out of the product library.
-#ifdef IODINE_TILE_PROF
-constexpr int TP_MAXBLK = 16384;
-#define TP_DECL unsigned long long tp_last = __builtin_amdgcn_s_memtime(); unsigned tp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define TP_STAMP(slot)                                                                      \
-    do {                                                                                    \
-        const unsigned long long tp_now = __builtin_amdgcn_s_memtime();                     \
-        tp_acc[slot] += (unsigned)(tp_now - tp_last);                                       \
-        tp_last = tp_now;                                                                   \
-    } while (0)
-#define TP_FLUSH(buf)                                                                       \
-    if (threadIdx.x == 0 && blockIdx.x < TP_MAXBLK)                                         \
-        for (int i_ = 0; i_ < 8; ++i_) buf[blockIdx.x * 8 + i_] = tp_acc[i_]
-#else
-#define TP_DECL
-#define TP_STAMP(slot)
-#define TP_FLUSH(buf)
-#endif
+// phase-timing macros TP_DECL / TP_STAMP / TP_FLUSH (empty in the product library) and the host report
+#include "tile_prof.h"
 
 // ---- helpers of the split-fp16 kernels ------------------------------------------------
 // out[e] = in[(e + r) & 3] with conditional moves only (a runtime-indexed vector would be demoted to scratch)

@@ -170,12 +170,9 @@ static hipError_t launch_tile_inst(hipStream_t st, const float* in, const float*
     constexpr int CC = conv_cc(CIN);
     constexpr int CP = (CC == 4) ? 4 : CC + 4;
     constexpr size_t lds = (size_t)(18 * 18 * CP) * 4 + (size_t)conv_nqp(CIN) * COUT * 16;
-    static std::atomic<unsigned> attr_devs{0};                             // devices this instance is configured on
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_tile_kernel<CIN, COUT, EPI>, (int)lds, attr_devs); e != hipSuccess) return e;
     const int tiles = S / 16;
-    hipLaunchKernelGGL((conv3x3_tile_kernel<CIN, COUT, EPI>), dim3(N * tiles * tiles), dim3(256), lds, st, in,
-                       reinterpret_cast<const float4*>(wpk), bias, aux, out, S, tiles);
-    return hipGetLastError();
+    return iod_launch<conv3x3_tile_kernel<CIN, COUT, EPI>>(st, dim3(N * tiles * tiles), dim3(256), lds, (int)lds, in, reinterpret_cast<const float4*>(wpk),
+                                                           bias, aux, out, S, tiles);
 }
 
 hipError_t launch_conv3x3_tile(hipStream_t st, const float* in, const float* wpk, const float* bias,
@@ -884,28 +881,14 @@ static hipError_t launch_tile_f16x3_inst(hipStream_t st, const float* in, const 
     constexpr size_t lds_stage = (size_t)(18 * (TH + 2) + 1) * 80 + wpk_tile_f16_bytes(16, COUT) + 16;   // halo + one chunk of the pack
     constexpr size_t lds_epi = (size_t)4 * (TH * 4) * (COUT + 4) * 4;              // output tile, transposed for contiguous stores
     constexpr size_t lds = lds_stage > lds_epi ? lds_stage : lds_epi;
-    static std::atomic<unsigned> attr_devs{0};                             // devices this instance is configured on
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_tile_f16x3_kernel<CIN, COUT, EPI, TH>, (int)lds, attr_devs); e != hipSuccess) return e;
-    const int tiles = S / 16;
-    hipLaunchKernelGGL((conv3x3_tile_f16x3_kernel<CIN, COUT, EPI, TH>), dim3(N * tiles * tiles * (16 / TH)), dim3(256), lds, st, in,
-                       reinterpret_cast<const uint4*>(wpk), wmeta, bias, aux, out, S, tiles, rev);
+    const int tiles = S / 16, blocks = N * tiles * tiles * (16 / TH);
+    const hipError_t e = iod_launch<conv3x3_tile_f16x3_kernel<CIN, COUT, EPI, TH>>(st, dim3(blocks), dim3(256), lds, (int)lds, in,
+                                                                                   reinterpret_cast<const uint4*>(wpk), wmeta, bias, aux, out, S, tiles, rev);
 #ifdef IODINE_TILE_PROF
-    {
-        const int nb = std::min(N * tiles * tiles * (16 / TH), TP_MAXBLK);
-        std::vector<unsigned> hp((size_t)nb * 8);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(g_tile_prof), hp.size() * sizeof(unsigned));
-        static const char* names[8] = {"start", "load-wait+max", "barrier1", "split+lds-write", "barrier2", "prefetch-issue",
-                                       "taps(lds-read+mfma)", "epilogue"};
-        double sum[8] = {0}, tot = 0;
-        for (int b2 = 0; b2 < nb; ++b2) for (int i = 0; i < 8; ++i) sum[i] += hp[(size_t)b2 * 8 + i];
-        for (int i = 0; i < 8; ++i) tot += sum[i] / nb;
-        fprintf(stderr, "[tile prof] memtime ticks per block (wave 0), total %.0f:", tot);
-        for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.0f |", names[i], sum[i] / nb);
-        fprintf(stderr, "\n");
-    }
+    static const char* names[8] = {"start", "load-wait+max", "barrier1", "split+lds-write", "barrier2", "prefetch-issue", "taps(lds-read+mfma)", "epilogue"};
+    tp_report(st, HIP_SYMBOL(g_tile_prof), blocks, "[tile prof] memtime ticks per block (wave 0)", names, 8);
 #endif
-    return hipGetLastError();
+    return e;
 }
 
 hipError_t launch_conv3x3_tile_f16x3(hipStream_t st, const float* in, const void* wpk, const float* wmeta,

@@ -80,6 +80,7 @@ hipError_t launch_cell_max(hipStream_t st, const float* x, float* tmax, int N, i
 __device__ unsigned g_ws_prof[TP_MAXBLK * 8];
 __device__ unsigned long long g_ws_ts[TP_MAXBLK * 16];
 __device__ unsigned long long g_ws_se[TP_MAXBLK * 2];       // [block]: s_memtime at the block's start / end
+static void ws_prof_dump(hipStream_t st, int blocks, int ntiles);       // host: below launch_ws_inst
 #endif
 
 // sum over the pixel lanes of the whole-pixel layout (lane = pl * SEGS + seg): all lanes with the same seg, result in every
@@ -212,6 +213,7 @@ void conv3x3_ws_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
     const int tiles_x = S >> 4, tiles_y = S >> 3, lg_tx = lgS - 4, lg_tpi = 2 * lgS - 7;
     // XCD-aware persistent schedule: block b runs on XCD b % 8 (observed; speed only).  Every XCD gets one contiguous eighth
     // of the tile list, so that the blocks sharing an L2 work on neighbouring tiles / the same slot-images.
+    // (the schedule of xcd_span, xcd_sched.h, spelled out: through the function the compiler orders these scalar instructions differently)
     const int nblk = gridDim.x;
     const int xcd = blockIdx.x & 7, bix = blockIdx.x >> 3, bpx = (nblk + 7) >> 3;
     const int per_xcd = (ntiles + 7) >> 3;
@@ -699,82 +701,78 @@ static hipError_t launch_ws_inst(hipStream_t st, const float* in, const void* wp
 {
     constexpr size_t buf_in = (size_t)(18 * 10 + 1) * ws_pxb(C), buf_out = (size_t)128 * (C * 4 + 32);
     constexpr size_t lds = 2 * (buf_in > buf_out ? buf_in : buf_out);
-    static std::atomic<unsigned> attr_devs{0};                             // devices this instance is configured on
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_ws_f16x3_kernel<C, EPI, F32, NPROD>, (int)lds, attr_devs); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     int lgS = 0;
     while ((1 << lgS) < S) ++lgS;
     const int ntiles = N * (S / 16) * (S / 8);
-    const int per_xcd = (ntiles + 7) / 8;
     int bpc = ws_bpc(C, EPI);                                                   // persistent blocks per CU (see ws_bpc)
 #ifdef WS_TUNE_ENV
     if (const char* e = getenv("IODINE_WS_BPC")) bpc = atoi(e);
 #endif
-    const int bpx = std::min(per_xcd, std::max(1, bpc * n_cu / 8));
-    hipLaunchKernelGGL((conv3x3_ws_f16x3_kernel<C, EPI, F32, NPROD>), dim3(8 * bpx), dim3(256), lds, st, in,
-                       reinterpret_cast<const uint4*>(wpk), wmeta, bias, aux, out, tmax_in, tmax_out, S, lgS, ntiles, rev);
+    const int blocks = iod_xcd_grid(ntiles, bpc, n_cu);
+    const hipError_t e = iod_launch<conv3x3_ws_f16x3_kernel<C, EPI, F32, NPROD>>(st, dim3(blocks), dim3(256), lds, (int)lds, in,
+                                                                                 reinterpret_cast<const uint4*>(wpk), wmeta, bias, aux, out, tmax_in,
+                                                                                 tmax_out, S, lgS, ntiles, rev);
 #ifdef IODINE_TILE_PROF
-    {
-        const int nb = std::min(8 * bpx, TP_MAXBLK);
-        std::vector<unsigned> hp((size_t)nb * 8);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(g_ws_prof), hp.size() * sizeof(unsigned));
-        static const char* names[8] = {"bookkeeping", "stage-barrier", "taps+staging-hooks", "epi-barrier", "tile->lds+barrier", "epilogue",
-                                       "-", "-"};
-        double sum[8] = {0}, tot = 0;
-        for (int b2 = 0; b2 < nb; ++b2) for (int i = 0; i < 8; ++i) sum[i] += hp[(size_t)b2 * 8 + i];
-        for (int i = 0; i < 8; ++i) tot += sum[i] / nb;
-        fprintf(stderr, "[ws prof] memtime ticks per block (wave 0, %d tiles), total %.0f:", (ntiles + 8 * bpx - 1) / (8 * bpx), tot);
-        for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.0f |", names[i], sum[i] / nb);
-        fprintf(stderr, "\n");
-        if (getenv("IODINE_WS_TS")) {
-            std::vector<unsigned long long> ts((size_t)nb * 16);
-            (void)hipMemcpyFromSymbol(ts.data(), HIP_SYMBOL(g_ws_ts), ts.size() * sizeof(unsigned long long));
-            for (int b2 = 0; b2 < 4 && b2 + 256 < nb; ++b2) {
-                const unsigned long long base = ts[(size_t)b2 * 16];
-                fprintf(stderr, "blk %d   :", b2);
-                for (int i = 0; i < 16; ++i) fprintf(stderr, " %lld", (long long)(ts[(size_t)b2 * 16 + i] - base));
-                fprintf(stderr, "\nblk %d :", b2 + 256);
-                for (int i = 0; i < 16; ++i) fprintf(stderr, " %lld", (long long)(ts[(size_t)(b2 + 256) * 16 + i] - base));
-                fprintf(stderr, "\n");
-            }
-        }
-        if (getenv("IODINE_WS_SE")) {                         // start / end of every block relative to the first start; pairs sharing a CU
-            std::vector<unsigned long long> se((size_t)nb * 2);
-            (void)hipMemcpyFromSymbol(se.data(), HIP_SYMBOL(g_ws_se), se.size() * sizeof(unsigned long long));
-            unsigned long long t0 = ~0ull;
-            for (int b2 = 0; b2 < nb; ++b2) t0 = std::min(t0, se[(size_t)b2 * 2]);
-            std::vector<long long> st_(nb), en_(nb);
-            for (int b2 = 0; b2 < nb; ++b2) { st_[b2] = (long long)(se[(size_t)b2 * 2] - t0); en_[b2] = (long long)(se[(size_t)b2 * 2 + 1] - t0); }
-            std::vector<long long> es(en_), ss(st_);
-            std::sort(es.begin(), es.end()); std::sort(ss.begin(), ss.end());
-            fprintf(stderr, "[ws prof] block start: median %lld max %lld | block end: min %lld p25 %lld median %lld p75 %lld max %lld\n", ss[nb / 2], ss[nb - 1],
-                    es[0], es[nb / 4], es[nb / 2], es[3 * nb / 4], es[nb - 1]);
-            // pairs on the same CU (same xcc / se / sh / cu bits of HW_ID)
-            int shown = 0;
-            for (int a = 0; a < nb && shown < 6; ++a)
-                for (int c2 = a + 1; c2 < nb; ++c2) {
-                    const unsigned ha = hp[(size_t)a * 8 + 6], hc = hp[(size_t)c2 * 8 + 6];
-                    if ((hp[(size_t)a * 8 + 7] & 0xf) == (hp[(size_t)c2 * 8 + 7] & 0xf) && ((ha >> 8) & 0xff) == ((hc >> 8) & 0xff)) {
-                        fprintf(stderr, "  CU pair blocks %d / %d: start %lld / %lld end %lld / %lld (wave slots %u / %u)\n", a, c2, st_[a], st_[c2], en_[a], en_[c2],
-                                ha & 0xf, hc & 0xf);
-                        ++shown;
-                        break;
-                    }
-                }
-        }
-        if (getenv("IODINE_WS_HWID")) {
-            for (int b2 = 0; b2 < nb; ++b2) {
-                const unsigned hw = hp[(size_t)b2 * 8 + 6], xc = hp[(size_t)b2 * 8 + 7];
-                fprintf(stderr, "blk %d xcc %u se %u sh %u cu %u simd %u wave %u\n", b2, xc & 0xf, (hw >> 13) & 7, (hw >> 12) & 1, (hw >> 8) & 0xf,
-                        (hw >> 4) & 3, hw & 0xf);
-            }
+    ws_prof_dump(st, blocks, ntiles);
+#endif
+    return e;
+}
+
+#ifdef IODINE_TILE_PROF
+// the phase report of the launch that just went out, and what IODINE_WS_TS / IODINE_WS_SE / IODINE_WS_HWID ask for on top
+static void ws_prof_dump(hipStream_t st, int blocks, int ntiles)
+{
+    static const char* names[8] = {"bookkeeping", "stage-barrier", "taps+staging-hooks", "epi-barrier", "tile->lds+barrier", "epilogue", "-", "-"};
+    const std::vector<unsigned> hp = tp_report(st, HIP_SYMBOL(g_ws_prof), blocks,
+                                               tp_title("[ws prof] memtime ticks per block (wave 0, %d tiles)", (ntiles + blocks - 1) / blocks).c_str(), names, 8);
+    const int nb = (int)(hp.size() / 8);
+    if (getenv("IODINE_WS_TS")) {
+        std::vector<unsigned long long> ts((size_t)nb * 16);
+        (void)hipMemcpyFromSymbol(ts.data(), HIP_SYMBOL(g_ws_ts), ts.size() * sizeof(unsigned long long));
+        for (int b2 = 0; b2 < 4 && b2 + 256 < nb; ++b2) {
+            const unsigned long long base = ts[(size_t)b2 * 16];
+            fprintf(stderr, "blk %d   :", b2);
+            for (int i = 0; i < 16; ++i) fprintf(stderr, " %lld", (long long)(ts[(size_t)b2 * 16 + i] - base));
+            fprintf(stderr, "\nblk %d :", b2 + 256);
+            for (int i = 0; i < 16; ++i) fprintf(stderr, " %lld", (long long)(ts[(size_t)(b2 + 256) * 16 + i] - base));
+            fprintf(stderr, "\n");
         }
     }
-#endif
-    return hipGetLastError();
+    if (getenv("IODINE_WS_SE")) {                         // start / end of every block relative to the first start; pairs sharing a CU
+        std::vector<unsigned long long> se((size_t)nb * 2);
+        (void)hipMemcpyFromSymbol(se.data(), HIP_SYMBOL(g_ws_se), se.size() * sizeof(unsigned long long));
+        unsigned long long t0 = ~0ull;
+        for (int b2 = 0; b2 < nb; ++b2) t0 = std::min(t0, se[(size_t)b2 * 2]);
+        std::vector<long long> st_(nb), en_(nb);
+        for (int b2 = 0; b2 < nb; ++b2) { st_[b2] = (long long)(se[(size_t)b2 * 2] - t0); en_[b2] = (long long)(se[(size_t)b2 * 2 + 1] - t0); }
+        std::vector<long long> es(en_), ss(st_);
+        std::sort(es.begin(), es.end()); std::sort(ss.begin(), ss.end());
+        fprintf(stderr, "[ws prof] block start: median %lld max %lld | block end: min %lld p25 %lld median %lld p75 %lld max %lld\n", ss[nb / 2], ss[nb - 1],
+                es[0], es[nb / 4], es[nb / 2], es[3 * nb / 4], es[nb - 1]);
+        // pairs on the same CU (same xcc / se / sh / cu bits of HW_ID)
+        int shown = 0;
+        for (int a = 0; a < nb && shown < 6; ++a)
+            for (int c2 = a + 1; c2 < nb; ++c2) {
+                const unsigned ha = hp[(size_t)a * 8 + 6], hc = hp[(size_t)c2 * 8 + 6];
+                if ((hp[(size_t)a * 8 + 7] & 0xf) == (hp[(size_t)c2 * 8 + 7] & 0xf) && ((ha >> 8) & 0xff) == ((hc >> 8) & 0xff)) {
+                    fprintf(stderr, "  CU pair blocks %d / %d: start %lld / %lld end %lld / %lld (wave slots %u / %u)\n", a, c2, st_[a], st_[c2], en_[a], en_[c2],
+                            ha & 0xf, hc & 0xf);
+                    ++shown;
+                    break;
+                }
+            }
+    }
+    if (getenv("IODINE_WS_HWID")) {
+        for (int b2 = 0; b2 < nb; ++b2) {
+            const unsigned hw = hp[(size_t)b2 * 8 + 6], xc = hp[(size_t)b2 * 8 + 7];
+            fprintf(stderr, "blk %d xcc %u se %u sh %u cu %u simd %u wave %u\n", b2, xc & 0xf, (hw >> 13) & 7, (hw >> 12) & 1, (hw >> 8) & 0xf,
+                    (hw >> 4) & 3, hw & 0xf);
+        }
+    }
 }
+#endif
 
 hipError_t launch_conv3x3_ws_f16x3(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias,
                                    const float* aux, float* out, const float* tmax_in, float* tmax_out, int N, int S, int c,
@@ -783,12 +781,13 @@ hipError_t launch_conv3x3_ws_f16x3(hipStream_t st, const float* in, const void* 
     // power-of-two image sizes only; the per-cell max of the INPUT (tmax_in, launch_cell_max or the producer's epilogue) is required
     if (S < 16 || (S & (S - 1)) != 0 || !tmax_in || (epi != EPI_L0ROWS && epi != EPI_L0ROWSX && !tmax_out)) return hipErrorInvalidValue;
     if (products != 1 && products != 3) return hipErrorInvalidValue;
-#define WS_CASE(CC, EP) if (c == CC && epi == EP) return products == 1 ? launch_ws_inst<CC, EP, false, 1>(st, in, wpk, wmeta, bias, aux, out, tmax_in, tmax_out, N, S, rev) \
-                                                                      : launch_ws_inst<CC, EP>(st, in, wpk, wmeta, bias, aux, out, tmax_in, tmax_out, N, S, rev);
-    WS_CASE(64, EPI_BIAS_ELU) WS_CASE(64, EPI_MUL_ELUGRAD) WS_CASE(64, EPI_L0ROWS) WS_CASE(64, EPI_L0ROWSX)
-    WS_CASE(32, EPI_BIAS_ELU) WS_CASE(32, EPI_MUL_ELUGRAD) WS_CASE(32, EPI_L0ROWS) WS_CASE(32, EPI_L0ROWSX)
-#undef WS_CASE
-    return hipErrorInvalidValue;
+    return iod_dispatch<64, 32>(c, [&](auto cc) {
+        return iod_dispatch<EPI_BIAS_ELU, EPI_MUL_ELUGRAD, EPI_L0ROWS, EPI_L0ROWSX>(epi, [&](auto ep) {
+            return iod_dispatch<3, 1>(products, [&](auto np) {
+                return launch_ws_inst<cc, ep, false, np>(st, in, wpk, wmeta, bias, aux, out, tmax_in, tmax_out, N, S, rev);
+            });
+        });
+    });
 }
 
 // ---- exact-fp32 form (option conv_precision 0): the same kernel with fp32 weights in the 144 registers and v_mfma_f32_16x16x4_f32 ----
@@ -823,9 +822,9 @@ hipError_t launch_conv3x3_ws_f32(hipStream_t st, const float* in, const void* wp
                                  int N, int S, int c, int epi, int rev)
 {
     if (S < 16 || (S & (S - 1)) != 0) return hipErrorInvalidValue;
-#define WS_CASE(CC, EP) if (c == CC && epi == EP) return launch_ws_inst<CC, EP, true>(st, in, wpk, nullptr, bias, aux, out, nullptr, nullptr, N, S, rev);
-    WS_CASE(64, EPI_BIAS_ELU) WS_CASE(64, EPI_MUL_ELUGRAD) WS_CASE(64, EPI_L0ROWS) WS_CASE(64, EPI_L0ROWSX)
-    WS_CASE(32, EPI_BIAS_ELU) WS_CASE(32, EPI_MUL_ELUGRAD) WS_CASE(32, EPI_L0ROWS) WS_CASE(32, EPI_L0ROWSX)
-#undef WS_CASE
-    return hipErrorInvalidValue;
+    return iod_dispatch<64, 32>(c, [&](auto cc) {
+        return iod_dispatch<EPI_BIAS_ELU, EPI_MUL_ELUGRAD, EPI_L0ROWS, EPI_L0ROWSX>(epi, [&](auto ep) {
+            return launch_ws_inst<cc, ep, true>(st, in, wpk, nullptr, bias, aux, out, nullptr, nullptr, N, S, rev);
+        });
+    });
 }

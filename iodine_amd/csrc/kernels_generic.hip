@@ -848,85 +848,59 @@ inline size_t gen_mfma_lds(int k, int Ck, int ldin, int s)
 
 inline int npair_out(int Ci, int k) { return ((Ci + 31) / 32) * ((4 * k * k + 31) / 32); }
 
-template <int KS, int NP>
-hipError_t gen_wgrad_out_launch_np(hipStream_t st, const float* in, const float* g, float* part, int N, int S, int Ci, int ldc, int nsl, size_t lds)
-{
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_out_kernel<KS, NP>, 80 * 1024, attr_devs); e != hipSuccess) return e;
-    hipLaunchKernelGGL((gen_wgrad_out_kernel<KS, NP>), dim3(nsl), dim3(256), lds, st, in, g, part, N, S, Ci, ldc, nsl);
-    return hipGetLastError();
-}
-template <int KS>
-hipError_t gen_wgrad_out_launch_ks(hipStream_t st, const float* in, const float* g, float* part, int N, int S, int Ci, int ldc, int nsl, int np,
-                                   size_t lds)
-{
-    switch (np) {
-    case 1: return gen_wgrad_out_launch_np<KS, 1>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
-    case 2: return gen_wgrad_out_launch_np<KS, 2>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
-    case 4: return gen_wgrad_out_launch_np<KS, 4>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
-    default: return gen_wgrad_out_launch_np<KS, 8>(st, in, g, part, N, S, Ci, ldc, nsl, lds);
-    }
-}
+// (k and np as gen_conv_tier chose them: k in {3, 5, 7}, np in {1, 2, 4, 8})
 inline hipError_t gen_wgrad_out_launch(hipStream_t st, const float* in, const float* g, float* part, int N, int S, int Ci, int ldc, int k, int nsl,
                                        int np, size_t lds)
 {
-    if (k == 3) return gen_wgrad_out_launch_ks<3>(st, in, g, part, N, S, Ci, ldc, nsl, np, lds);
-    if (k == 5) return gen_wgrad_out_launch_ks<5>(st, in, g, part, N, S, Ci, ldc, nsl, np, lds);
-    return gen_wgrad_out_launch_ks<7>(st, in, g, part, N, S, Ci, ldc, nsl, np, lds);
+    return iod_dispatch<3, 5, 7>(k, [&](auto ks) {
+        return iod_dispatch<1, 2, 4, 8>(np, [&](auto npc) {
+            return iod_launch<gen_wgrad_out_kernel<ks, npc>>(st, dim3(nsl), dim3(256), lds, 80 * 1024, in, g, part, N, S, Ci, ldc, nsl);
+        });
+    });
 }
 
 template <int KS, int CCH, bool SPLIT>
 hipError_t gen_mfma_launch_cch(hipStream_t st, const float* in, const float* wt, const float* bias, const float* aux, float* out, int N, int S,
                                int Ck, int ldin, int Cn, int ldout, int flip, int sT, int sK, int sN, int elu, size_t lds, int seg)
 {
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)gen_conv_mfma_kernel<KS, CCH, SPLIT>, 160 * 1024, attr_devs); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int ncg = (Cn + 15) / 16, tiles = (S + 15) / 16, ntiles = N * tiles * tiles;
     const int per_cu = lds <= 80 * 1024 ? 2 : 1;
     const int nb = std::max(1, std::min(ntiles, per_cu * n_cu / ncg));
-    hipLaunchKernelGGL((gen_conv_mfma_kernel<KS, CCH, SPLIT>), dim3(ncg * nb), dim3(256), lds, st, in, wt, bias, aux, out, S, Ck, ldin, Cn, ldout,
-                       flip, sT, sK, sN, elu, ncg, tiles, ntiles, seg);
+    const hipError_t e = iod_launch<gen_conv_mfma_kernel<KS, CCH, SPLIT>>(st, dim3(ncg * nb), dim3(256), lds, 160 * 1024, in, wt, bias, aux, out, S, Ck,
+                                                                          ldin, Cn, ldout, flip, sT, sK, sN, elu, ncg, tiles, ntiles, seg);
 #ifdef IODINE_TILE_PROF
-    if (getenv("IODINE_GEN_PROF")) {
-        const int nbk = std::min(ncg * nb, TP_MAXBLK);
-        std::vector<unsigned> hp((size_t)nbk * 8);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(g_gen_prof), hp.size() * sizeof(unsigned));
-        static const char* names[8] = {"weights/loop", "tile prologue", "fetch issue", "k-steps", "commit", "barrier", "epilogue", "-"};
-        double sum[8] = {0}, tot = 0;
-        for (int b2 = 0; b2 < nbk; ++b2) for (int i = 0; i < 8; ++i) sum[i] += hp[(size_t)b2 * 8 + i];
-        for (int i = 0; i < 8; ++i) tot += sum[i] / nbk;
-        fprintf(stderr, "[gen prof k%d cch%d Ck%d Cn%d] ticks per block (%d tiles), total %.0f:", KS, CCH, Ck, Cn, (ntiles + nb - 1) / nb, tot);
-        for (int i = 0; i < 7; ++i) fprintf(stderr, " %s %.0f |", names[i], sum[i] / nbk);
-        fprintf(stderr, "\n");
-    }
+    static const char* names[7] = {"weights/loop", "tile prologue", "fetch issue", "k-steps", "commit", "barrier", "epilogue"};
+    if (getenv("IODINE_GEN_PROF"))
+        tp_report(st, HIP_SYMBOL(g_gen_prof), ncg * nb,
+                  tp_title("[gen prof k%d cch%d Ck%d Cn%d] ticks per block (%d tiles)", KS, CCH, Ck, Cn, (ntiles + nb - 1) / nb).c_str(), names, 7);
 #endif
-    return hipGetLastError();
+    return e;
 }
 
 template <int KS, bool SPLIT>
 hipError_t gen_mfma_launch_split(hipStream_t st, const float* in, const float* wt, const float* bias, const float* aux, float* out, int N, int S,
                                  int Ck, int ldin, int Cn, int ldout, int flip, int sT, int sK, int sN, int elu, const GenTierSel& sel)
 {
-    switch (sel.tier) {
-    case GEN_TIER_MFMA_CCH16:
-        if constexpr (KS < 7)
-            return gen_mfma_launch_cch<KS, 16, SPLIT>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel.lds, sel.seg);
-        return hipErrorInvalidValue;
-    case GEN_TIER_MFMA_CCH8:
-        return gen_mfma_launch_cch<KS, 8, SPLIT>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel.lds, sel.seg);
-    default:
-        return gen_mfma_launch_cch<KS, 4, SPLIT>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel.lds, sel.seg);
-    }
+    // (the callers switch on the three MFMA tiers before they come here)
+    return iod_dispatch<GEN_TIER_MFMA_CCH16, GEN_TIER_MFMA_CCH8, GEN_TIER_MFMA_CCH4>(sel.tier, [&](auto tier) {
+        constexpr int CCH = tier == GEN_TIER_MFMA_CCH16 ? 16 : tier == GEN_TIER_MFMA_CCH8 ? 8 : 4;
+        if constexpr (KS < 7 || CCH < 16)
+            return gen_mfma_launch_cch<KS, CCH, SPLIT>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel.lds, sel.seg);
+        else
+            return hipErrorInvalidValue;
+    });
 }
-template <int KS>
-hipError_t gen_mfma_launch(hipStream_t st, const float* in, const float* wt, const float* bias, const float* aux, float* out, int N, int S,
-                           int Ck, int ldin, int Cn, int ldout, int flip, int sT, int sK, int sN, int elu, const GenTierSel& sel)
+// (k as gen_conv_tier admits it to the MFMA tiers: 3, 5 or 7)
+inline hipError_t gen_mfma_launch(hipStream_t st, const float* in, const float* wt, const float* bias, const float* aux, float* out, int N, int S,
+                                  int Ck, int ldin, int Cn, int ldout, int flip, int sT, int sK, int sN, int elu, int k, const GenTierSel& sel)
 {
-    if (sel.seg) return gen_mfma_launch_split<KS, true>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel);
-    return gen_mfma_launch_split<KS, false>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel);
+    return iod_dispatch<3, 5, 7>(k, [&](auto ks) {
+        return iod_dispatch_bool(sel.seg != 0, [&](auto split) {
+            return gen_mfma_launch_split<ks, split>(st, in, wt, bias, aux, out, N, S, Ck, ldin, Cn, ldout, flip, sT, sK, sN, elu, sel);
+        });
+    });
 }
 
 inline GenTier gen_mfma_tier(int cch) { return cch == 16 ? GEN_TIER_MFMA_CCH16 : cch == 8 ? GEN_TIER_MFMA_CCH8 : GEN_TIER_MFMA_CCH4; }
@@ -983,9 +957,7 @@ hipError_t launch_gen_conv_fwd(hipStream_t st, const float* in, const float* wt,
     switch (sel.tier) {
     case GEN_TIER_MFMA_CCH16: case GEN_TIER_MFMA_CCH8: case GEN_TIER_MFMA_CCH4:
         // [tap][ci][co] pack: W(tap, k = ci, n = co)
-        if (k == 3) return gen_mfma_launch<3>(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, sel);
-        if (k == 5) return gen_mfma_launch<5>(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, sel);
-        return gen_mfma_launch<7>(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, sel);
+        return gen_mfma_launch(st, in, wt, bias, nullptr, out, N, Si, Ci, ldc, Co, Co, 0, Ci * Co, Co, 1, elu, k, sel);
     case GEN_TIER_S2_MFMA:
         return launch_gen_s2_fwd(st, in, wt, bias, out, N, Si, Ci, ldc, Co, k, elu, chmask);
     default: break;                                            // the scalar kernel
@@ -1003,9 +975,7 @@ hipError_t launch_gen_conv_dgrad(hipStream_t st, const float* dout, const float*
     switch (sel.tier) {
     case GEN_TIER_MFMA_CCH16: case GEN_TIER_MFMA_CCH8: case GEN_TIER_MFMA_CCH4:
         // correlation of dout with the flipped kernel: reduction over co, W(tap, k = co, n = ci) = wt[(KK - 1 - tap)][ci][co]
-        if (k == 3) return gen_mfma_launch<3>(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, sel);
-        if (k == 5) return gen_mfma_launch<5>(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, sel);
-        return gen_mfma_launch<7>(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, sel);
+        return gen_mfma_launch(st, dout, wt, nullptr, aux, din, N, Si, Co, Co, Ci, ldi, 1, ldi * Co, 1, Co, 0, k, sel);
     case GEN_TIER_S2_MFMA:
         return launch_gen_s2_dgrad(st, dout, wt, aux, din, N, Si, Ci, ldi, Co, k);
     default: break;                                            // the scalar kernel
@@ -1047,41 +1017,23 @@ hipError_t launch_gen_conv_wgrad(hipStream_t st, const float* in, const float* d
         if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
         const int nsl = std::max(1, std::min(GEN_WGRAD_SLICES_MAX, 2 * n_cu / (k * ngrp)));
         const dim3 grid_r((unsigned)(k * nsl * ngrp));
-        static std::atomic<unsigned> d3{0}, d5{0}, d7{0};
-        if (k == 3) {
-            if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_rows_kernel<3>, 80 * 1024, d3); e != hipSuccess) return e;
-            hipLaunchKernelGGL((gen_wgrad_rows_kernel<3>), grid_r, dim3(256), lds, st, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
-        } else if (k == 5) {
-            if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_rows_kernel<5>, 80 * 1024, d5); e != hipSuccess) return e;
-            hipLaunchKernelGGL((gen_wgrad_rows_kernel<5>), grid_r, dim3(256), lds, st, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
+        if (hipError_t e = iod_dispatch<3, 5, 7>(k, [&](auto ks) {
+                return iod_launch<gen_wgrad_rows_kernel<ks>>(st, grid_r, dim3(256), lds, 80 * 1024, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
+            }); e != hipSuccess) return e;
 #ifdef IODINE_TILE_PROF
-            if (getenv("IODINE_GEN_PROF")) {
-                const int nbk = std::min((int)grid_r.x, TP_MAXBLK);
-                std::vector<unsigned> hp((size_t)nbk * 8);
-                (void)hipStreamSynchronize(st);
-                (void)hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(g_genw_prof), hp.size() * sizeof(unsigned));
-                static const char* names[8] = {"prologue", "commit", "barrier 1", "fetch issue", "MFMA blocks", "barrier 2", "-", "-"};
-                double sum[8] = {0}, tot = 0;
-                for (int b2 = 0; b2 < nbk; ++b2) for (int i = 0; i < 8; ++i) sum[i] += hp[(size_t)b2 * 8 + i];
-                for (int i = 0; i < 8; ++i) tot += sum[i] / nbk;
-                fprintf(stderr, "[gen wgrad rows prof] ticks per block (%d slices), total %.0f:", nsl, tot);
-                for (int i = 0; i < 6; ++i) fprintf(stderr, " %s %.0f |", names[i], sum[i] / nbk);
-                fprintf(stderr, "\n");
-            }
+        static const char* names[6] = {"prologue", "commit", "barrier 1", "fetch issue", "MFMA blocks", "barrier 2"};
+        if (getenv("IODINE_GEN_PROF"))
+            tp_report(st, HIP_SYMBOL(g_genw_prof), (int)grid_r.x, tp_title("[gen wgrad rows prof] ticks per block (%d slices)", nsl).c_str(), names, 6);
 #endif
-        } else {
-            if (hipError_t e = iod_set_max_lds((const void*)gen_wgrad_rows_kernel<7>, 80 * 1024, d7); e != hipSuccess) return e;
-            hipLaunchKernelGGL((gen_wgrad_rows_kernel<7>), grid_r, dim3(256), lds, st, in, dout, scratch, N, Si, Ci, ldc, Co, nsl);
-        }
         hipLaunchKernelGGL(gen_conv_wgrad_reduce_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, scratch, nsl, Ci, Ci_dst, Co,
                            k * k, alpha, gw, gb);
         return hipGetLastError();
     }
     case GEN_TIER_WGRAD_MFMA: {
         const dim3 grid((unsigned)(k * k * GEN_WGRAD_SLICES * ngrp));
-        if (k == 3) hipLaunchKernelGGL((gen_wgrad_mfma_kernel<3>), grid, dim3(256), 0, st, in, dout, scratch, N, Si, Ci, ldc, Co, GEN_WGRAD_SLICES);
-        else if (k == 5) hipLaunchKernelGGL((gen_wgrad_mfma_kernel<5>), grid, dim3(256), 0, st, in, dout, scratch, N, Si, Ci, ldc, Co, GEN_WGRAD_SLICES);
-        else hipLaunchKernelGGL((gen_wgrad_mfma_kernel<7>), grid, dim3(256), 0, st, in, dout, scratch, N, Si, Ci, ldc, Co, GEN_WGRAD_SLICES);
+        if (hipError_t e = iod_dispatch<3, 5, 7>(k, [&](auto ks) {
+                return iod_launch<gen_wgrad_mfma_kernel<ks>>(st, grid, dim3(256), 0, 0, in, dout, scratch, N, Si, Ci, ldc, Co, GEN_WGRAD_SLICES);
+            }); e != hipSuccess) return e;
         hipLaunchKernelGGL(gen_conv_wgrad_reduce_kernel, dim3((unsigned)((per + 31) / 32)), dim3(256), 0, st, scratch, GEN_WGRAD_SLICES, Ci, Ci_dst, Co,
                            k * k, alpha, gw, gb);
         return hipGetLastError();

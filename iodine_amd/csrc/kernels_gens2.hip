@@ -216,15 +216,6 @@ inline int gs2_cch(int mode, int ks, int K, int nn, size_t* lds_out, int nr = 1)
     return 0;
 }
 
-template <int MODE, int C4N, int NR>
-hipError_t gs2_launch_c(hipStream_t st, dim3 grid, size_t lds, const float* in, const float* wt, const float* bias, const float* aux, float* out,
-                        const Gs2Geom& g)
-{
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)gen_s2_conv_kernel<MODE, C4N, NR>, 72 * 1024, attr_devs); e != hipSuccess) return e;
-    hipLaunchKernelGGL((gen_s2_conv_kernel<MODE, C4N, NR>), grid, dim3(256), lds, st, in, wt, bias, aux, out, g);
-    return hipGetLastError();
-}
 // geometry + launch: 8 x 16 positions per block (NR = 2) when the position grid has more than 4 rows and the taller halo fits beside the same
 // weight chunk, else 4 x 16
 template <int MODE>
@@ -240,10 +231,11 @@ hipError_t gs2_launch(hipStream_t st, int N, int nz, int ygrid, const float* in,
     g.tiles_y = (g.Sout + GS2_TR * nr - 1) / (GS2_TR * nr);
     const dim3 grid((unsigned)(N * g.tiles_x * g.tiles_y), (unsigned)ygrid, (unsigned)nz);
     const size_t lds = nr == 2 ? lds2 : lds1;
-#define GS2_CASE(C4, R) if (g.cch == 4 * C4 && nr == R) return gs2_launch_c<MODE, C4, R>(st, grid, lds, in, wt, bias, aux, out, g);
-    GS2_CASE(4, 2) GS2_CASE(2, 2) GS2_CASE(1, 2) GS2_CASE(4, 1) GS2_CASE(2, 1) GS2_CASE(1, 1)
-#undef GS2_CASE
-    return hipErrorInvalidValue;
+    return iod_dispatch<16, 8, 4>(g.cch, [&](auto cch) {
+        return iod_dispatch<2, 1>(nr, [&](auto r) {
+            return iod_launch<gen_s2_conv_kernel<MODE, cch / 4, r>>(st, grid, dim3(256), lds, 72 * 1024, in, wt, bias, aux, out, g);
+        });
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -408,20 +400,15 @@ hipError_t launch_gen_s2_wgrad(hipStream_t st, const float* in, const float* dou
     const int Cip = (ncig * 16 + 31) / 32 * 32 + 8, Cop = ncog * 16 + 16, AC = 2 * (GS2_TC - 1) + k;
     const size_t lds = (size_t)(GS2_TR * AC * Cip + GS2_TR * GS2_TC * Cop) * sizeof(float);
     if (lds > 72 * 1024) return hipErrorInvalidValue;
-    static std::atomic<unsigned> d3{0}, d5{0}, d7{0};
-    if (hipError_t e = k == 3 ? iod_set_max_lds((const void*)gen_s2_wgrad_kernel<3>, 72 * 1024, d3)
-                     : k == 5 ? iod_set_max_lds((const void*)gen_s2_wgrad_kernel<5>, 72 * 1024, d5)
-                              : iod_set_max_lds((const void*)gen_s2_wgrad_kernel<7>, 72 * 1024, d7); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int nslab = N * ((So + GS2_TC - 1) / GS2_TC) * ((So + GS2_TR - 1) / GS2_TR);
     const int nsl = std::max(1, std::min(std::min(nsl_max, nslab), std::max(1, 2 * n_cu / (k * npg))));
     const dim3 grid((unsigned)(k * npg * nsl));
-    if (k == 3) hipLaunchKernelGGL((gen_s2_wgrad_kernel<3>), grid, dim3(256), lds, st, in, dout, part, N, Si, So, Ci, ldc, Co, nsl, npg, cimask);
-    else if (k == 5) hipLaunchKernelGGL((gen_s2_wgrad_kernel<5>), grid, dim3(256), lds, st, in, dout, part, N, Si, So, Ci, ldc, Co, nsl, npg, cimask);
-    else hipLaunchKernelGGL((gen_s2_wgrad_kernel<7>), grid, dim3(256), lds, st, in, dout, part, N, Si, So, Ci, ldc, Co, nsl, npg, cimask);
     *nsl_out = nsl;
-    return hipGetLastError();
+    return iod_dispatch<3, 5, 7>(k, [&](auto ks) {                  // (gen_s2_mfma_ok: k is 3, 5 or 7)
+        return iod_launch<gen_s2_wgrad_kernel<ks>>(st, grid, dim3(256), lds, 72 * 1024, in, dout, part, N, Si, So, Ci, ldc, Co, nsl, npg, cimask);
+    });
 }
 
 bool gen_s2_wgrad_ok(int k, int Ci, int ldc, int Co)

@@ -277,25 +277,14 @@ template <int KS, int CCH>
 hipError_t gsplit_launch(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias, const float* aux, float* out,
                          int N, int S, int C, int elu)
 {
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)gsplit_conv_kernel<KS, CCH>, 160 * 1024, attr_devs); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const size_t lds = gsplit_lds_bytes(KS, C, CCH);
     const int ncg = C / 16, tiles = (S + 15) / 16, ntiles = N * tiles * tiles;
     const int per_cu = lds <= 80 * 1024 ? 2 : 1;
     const int nb = std::max(1, std::min(ntiles, per_cu * n_cu / ncg));
-    hipLaunchKernelGGL((gsplit_conv_kernel<KS, CCH>), dim3(ncg * nb), dim3(256), lds, st, in, reinterpret_cast<const uint4*>(wpk), wmeta, bias, aux,
-                       out, S, C, elu, ncg, tiles, ntiles);
-    return hipGetLastError();
-}
-
-template <int KS>
-hipError_t gsplit_launch_ks(hipStream_t st, const float* in, const void* wpk, const float* wmeta, const float* bias, const float* aux, float* out,
-                            int N, int S, int C, int elu, int cch)
-{
-    if (cch == 32) return gsplit_launch<KS, 32>(st, in, wpk, wmeta, bias, aux, out, N, S, C, elu);
-    return gsplit_launch<KS, 16>(st, in, wpk, wmeta, bias, aux, out, N, S, C, elu);
+    return iod_launch<gsplit_conv_kernel<KS, CCH>>(st, dim3(ncg * nb), dim3(256), lds, 160 * 1024, in, reinterpret_cast<const uint4*>(wpk), wmeta, bias,
+                                                   aux, out, S, C, elu, ncg, tiles, ntiles);
 }
 
 
@@ -497,17 +486,6 @@ hipError_t launch_gen_split_pack(hipStream_t st, const float* wt, int k, int C, 
 // split weight + bias gradient: covered where the forward kernel is and the (ci, co) tile pairs fit four waves' registers (C <= 64)
 bool gen_split_wgrad_ok(int k, int C) { return gen_split_cch(k, C) != 0 && C <= 64 && (k < 7 || C <= 32) && gsplit_wgrad_lds_bytes(C) <= 160 * 1024; }
 
-namespace {
-template <int KS, int NP>
-hipError_t gsplit_wgrad_launch(hipStream_t st, const float* in, const float* dout, float* part, int N, int S, int C, int nsl)
-{
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)gsplit_wgrad_kernel<KS, NP>, 160 * 1024, attr_devs); e != hipSuccess) return e;
-    hipLaunchKernelGGL((gsplit_wgrad_kernel<KS, NP>), dim3(KS * nsl), dim3(256), gsplit_wgrad_lds_bytes(C), st, in, dout, part, N, S, C, nsl);
-    return hipGetLastError();
-}
-}  // namespace
-
 // gw [C][C][k][k] += alpha dW, gb [C] += alpha db; scratch: gen_wgrad_scratch_floats(C, C, k) floats (partials of <= GEN_WGRAD_SLICES_MAX slices)
 hipError_t launch_gen_split_wgrad(hipStream_t st, const float* in, const float* dout, float* scratch, int N, int S, int C, int k, float alpha,
                                   float* gw, float* gb)
@@ -518,11 +496,16 @@ hipError_t launch_gen_split_wgrad(hipStream_t st, const float* in, const float* 
     const long long U = (long long)N * ((S + 7) / 8) * ((S + GSW_SEG - 1) / GSW_SEG);
     const int per_cu = gsplit_wgrad_lds_bytes(C) <= 80 * 1024 ? 2 : 1;
     const int nsl = (int)std::max<long long>(1, std::min<long long>(std::min(GEN_WGRAD_SLICES_MAX, per_cu * n_cu / k), U));
-    const bool one = (C / 16) * (C / 16) <= 4;               // one tile pair per wave
-    hipError_t e;
-    if (k == 3) e = one ? gsplit_wgrad_launch<3, 1>(st, in, dout, scratch, N, S, C, nsl) : gsplit_wgrad_launch<3, 4>(st, in, dout, scratch, N, S, C, nsl);
-    else if (k == 5) e = one ? gsplit_wgrad_launch<5, 1>(st, in, dout, scratch, N, S, C, nsl) : gsplit_wgrad_launch<5, 4>(st, in, dout, scratch, N, S, C, nsl);
-    else e = gsplit_wgrad_launch<7, 1>(st, in, dout, scratch, N, S, C, nsl);
+    const int np = (C / 16) * (C / 16) <= 4 ? 1 : 4;         // tile pairs per wave (7 x 7: C <= 32, always one)
+    const hipError_t e = iod_dispatch<3, 5, 7>(k, [&](auto ks) {
+        return iod_dispatch<1, 4>(np, [&](auto npc) {
+            if constexpr (ks < 7 || npc == 1)
+                return iod_launch<gsplit_wgrad_kernel<ks, npc>>(st, dim3(ks * nsl), dim3(256), gsplit_wgrad_lds_bytes(C), 160 * 1024, in, dout, scratch,
+                                                                N, S, C, nsl);
+            else
+                return hipErrorInvalidValue;
+        });
+    });
     if (e != hipSuccess) return e;
     return launch_gen_wgrad_reduce(st, scratch, nsl, C, C, C, k * k, alpha, gw, gb);
 }
@@ -533,7 +516,7 @@ hipError_t launch_gen_split_conv(hipStream_t st, const float* in, const void* wp
 {
     const int cch = gen_split_cch(k, C);
     if (!cch) return hipErrorInvalidValue;
-    if (k == 3) return gsplit_launch_ks<3>(st, in, wpk, wmeta, bias, aux, out, N, S, C, elu, cch);
-    if (k == 5) return gsplit_launch_ks<5>(st, in, wpk, wmeta, bias, aux, out, N, S, C, elu, cch);
-    return gsplit_launch_ks<7>(st, in, wpk, wmeta, bias, aux, out, N, S, C, elu, cch);
+    return iod_dispatch<3, 5, 7>(k, [&](auto ks) {               // (gen_split_cch: k is 3, 5 or 7, cch 32 or 16)
+        return iod_dispatch<32, 16>(cch, [&](auto cc) { return gsplit_launch<ks, cc>(st, in, wpk, wmeta, bias, aux, out, N, S, C, elu); });
+    });
 }

@@ -289,18 +289,11 @@ hipError_t launch_head_bptt(hipStream_t st, const float* g_pm, const float* g_pl
     const size_t lds = head_bptt_lds(L, H);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid((N + HB - 1) / HB), block(64 * HKG);
-    if (seed_m) {                                                           // auxiliary cotangents: the seeded instance
-        static std::atomic<unsigned> attr_devs_seed{0};
-        if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<true>, 160 * 1024, attr_devs_seed); e != hipSuccess) return e;
-        hipLaunchKernelGGL(head_bptt_kernel<true>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
-                           ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, seed_m, seed_v, gl_dev, wtab, dh_in, dc_in, dh_out, dc_out, seed_stride);
-        return hipGetLastError();
-    }
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)head_bptt_kernel<false>, 160 * 1024, attr_devs); e != hipSuccess) return e;
-    hipLaunchKernelGGL(head_bptt_kernel<false>, grid, block, lds, st, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp,
-                       ddm, ddv, dgates, ds, dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr, wtab, nullptr, nullptr, nullptr, nullptr, (size_t)0);
-    return hipGetLastError();
+    if (seed_m)                                                             // auxiliary cotangents: the seeded instance
+        return iod_launch<head_bptt_kernel<true>>(st, grid, block, lds, 160 * 1024, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp, ddm, ddv, dgates, ds,
+                                                  dpooled, T, N, B, L, H, Cr, seed_m, seed_v, gl_dev, wtab, dh_in, dc_in, dh_out, dc_out, seed_stride);
+    return iod_launch<head_bptt_kernel<false>>(st, grid, block, lds, 160 * 1024, g_pm, g_plv, gates, cst, u, Wm, Wv, Whh, Wih, Wmlp, ddm, ddv, dgates, ds,
+                                               dpooled, T, N, B, L, H, Cr, nullptr, nullptr, nullptr, wtab, nullptr, nullptr, nullptr, nullptr, (size_t)0);
 }
 
 // The same recurrence as a launch sequence: per iteration 2 scale (+ 2 seed adds), 5 SGEMMs and the two pointwise kernels; what runs when

@@ -894,23 +894,17 @@ hipError_t launch_refine_head(hipStream_t st, const float* feat, int N, int PL, 
                                   : (refine_head_lds_bytes(C, H, L, 0) <= HEAD_LDS_MAX ? 0 : -1);
     if (form < 0) return hipErrorInvalidValue;
     const size_t lds = refine_head_lds_bytes(C, H, L, form);
-    static std::atomic<unsigned> attr_devs[3];                             // devices each instance is configured on
-#define HEAD_LAUNCH(STG) do {                                                                                                        \
-        if (hipError_t e = iod_set_max_lds((const void*)refine_head_kernel<STG>, (int)HEAD_LDS_MAX, attr_devs[STG]); e != hipSuccess) return e;  \
-        hipLaunchKernelGGL(refine_head_kernel<STG>, dim3(N), dim3(1024), lds, st, feat, PL, C, H, L, mlp_wT, mlp_b, wihT, whhT,      \
-                           lstm_b, wmT, bm, wvT, bv, latent, h_prev, c_prev, h_out, c_out, pm, plv, sv_pooled, sv_s,                 \
-                           sv_gates, sv_xin, d_mean, d_logvar, xh, gp);                                                              \
-    } while (0)
+    auto stage = [&](auto stg) {
+        return iod_launch<refine_head_kernel<stg>>(st, dim3(N), dim3(1024), lds, (int)HEAD_LDS_MAX, feat, PL, C, H, L, mlp_wT, mlp_b, wihT, whhT, lstm_b, wmT, bm,
+                                                   wvT, bv, latent, h_prev, c_prev, h_out, c_out, pm, plv, sv_pooled, sv_s, sv_gates, sv_xin, d_mean, d_logvar,
+                                                   xh, gp);
+    };
+    using std::integral_constant;
+    if (form != 1) return stage(integral_constant<int, 0>{});
     const int Kg = H + 4 * L + H, Np = (N + 31) / 32 * 32;
-    if (form == 1) {
-        HEAD_LAUNCH(1);
-        if (hipError_t e = launch_sgemm_tn_mfma(st, Np, 4 * H, Kg, 1.f, xh, Kg, wihT, 4 * H, 0.f, gp, 4 * H, 0, 0, 1); e != hipSuccess) return e;
-        HEAD_LAUNCH(2);
-    } else {
-        HEAD_LAUNCH(0);
-    }
-#undef HEAD_LAUNCH
-    return hipGetLastError();
+    if (hipError_t e = stage(integral_constant<int, 1>{}); e != hipSuccess) return e;
+    if (hipError_t e = launch_sgemm_tn_mfma(st, Np, 4 * H, Kg, 1.f, xh, Kg, wihT, 4 * H, 0.f, gp, 4 * H, 0, 0, 1); e != hipSuccess) return e;
+    return stage(integral_constant<int, 2>{});
 }
 
 // -----------------------------------------------------------------------------------------------

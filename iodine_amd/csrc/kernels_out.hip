@@ -236,7 +236,8 @@ void dec_out_rows_f16x3_kernel(const float* __restrict__ in, const uint4* __rest
     const int lane = tid & 63, kh = lane >> 5, li = lane & 31;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int SPR = 128 / S;                                        // rows per step
-    // XCD-aware: block b runs on XCD b % 8; every XCD gets one contiguous eighth of the row ranges (neighbours share a halo row in L2)
+    // XCD-aware: block b runs on XCD b % 8 (the convention of xcd_sched.h; this kernel is not persistent: the grid is padded to a multiple
+    // of 8 and surplus blocks leave); every XCD gets one contiguous eighth of the row ranges (neighbours share a halo row in L2)
     const int per_xcd = (nblk + 7) >> 3;
     const int vb = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
     if (vb >= nblk) return;
@@ -442,17 +443,12 @@ hipError_t launch_dec_out_rows_f16x3(hipStream_t st, const float* in, const void
     const int nblk = (rows_total + rpb - 1) / rpb;
     const int grid = ((nblk + 7) / 8) * 8;
     constexpr size_t lds = (size_t)4 * 128 * 36 * 4;
-#define DO_ROWS(CC, FF)                                                                                                                     \
-    {                                                                                                                                       \
-        static std::atomic<unsigned> attr_devs{0};                                                                                          \
-        if (hipError_t e = iod_set_max_lds((const void*)dec_out_rows_f16x3_kernel<CC, FF>, (int)lds, attr_devs); e != hipSuccess) return e; \
-        hipLaunchKernelGGL((dec_out_rows_f16x3_kernel<CC, FF>), dim3(grid), dim3(256), lds, st, in, reinterpret_cast<const uint4*>(wpk),    \
-                           wmeta, bias, out, S, rows_total, rpb, nblk, tmax);                                                               \
-    }
-    if (C == 64) { if (f32) DO_ROWS(64, true) else DO_ROWS(64, false) }
-    else { if (f32) DO_ROWS(32, true) else DO_ROWS(32, false) }
-#undef DO_ROWS
-    return hipGetLastError();
+    return iod_dispatch<64, 32>(C, [&](auto cc) {                   // (dec_out_rows_ok: C is 64 or 32)
+        return iod_dispatch_bool(f32 != 0, [&](auto f) {
+            return iod_launch<dec_out_rows_f16x3_kernel<cc, f>>(st, dim3(grid), dim3(256), lds, (int)lds, in, reinterpret_cast<const uint4*>(wpk), wmeta,
+                                                                bias, out, S, rows_total, rpb, nblk, tmax);
+        });
+    });
 }
 
 // =========================================================================================

@@ -91,6 +91,7 @@ void refine_bwd01_kernel(const float* __restrict__ rd1, const uint4* __restrict_
 
     // persistent, XCD-aware schedule (block b runs on XCD b % 8, observed; speed only): every XCD walks one contiguous eighth of
     // the tile list, so that blocks sharing an L2 work on neighbouring tiles (their halos overlap)
+    // (the schedule of xcd_span, xcd_sched.h, spelled out: through the function the compiler orders these scalar instructions differently)
     const int nblk = gridDim.x;
     const int xcd = blockIdx.x & 7, bix = blockIdx.x >> 3, bpx = (nblk + 7) >> 3;
     const int per_xcd = (ntiles + 7) >> 3;
@@ -487,8 +488,6 @@ hipError_t launch_refine_bwd01(hipStream_t st, const float* rd1, const void* wpk
 {
     IOD_XSKIP(1024);
     if (!refine_bwd01_ok(S, c) || kdiv < 1) return hipErrorInvalidValue;
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)refine_bwd01_kernel, (int)RB_LDS, attr_devs); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int Sm = S / 2, tiles_x = Sm / 16, tiles_y = Sm / RB_TH, ntiles = NT * tiles_x * tiles_y;
@@ -498,31 +497,18 @@ hipError_t launch_refine_bwd01(hipStream_t st, const float* rd1, const void* wpk
     const unsigned magic = kdiv == 1 ? 0u : (unsigned)((((unsigned long long)1 << 32) + kdiv - 1) / kdiv);     // (2^32 does not fit: 0 = "one slot")
     for (int i = 0; i < NT && kdiv > 1; ++i)
         if ((unsigned)(((unsigned long long)i * magic) >> 32) != (unsigned)(i / kdiv)) return hipErrorInvalidValue;
-    const int per_xcd = (ntiles + 7) / 8;
-    const int bpx = std::min(per_xcd, std::max(1, n_cu / 8));
-    const int blocks = 8 * bpx;
-    hipLaunchKernelGGL(refine_bwd01_kernel, dim3(blocks), dim3(512), RB_LDS, st, rd1, reinterpret_cast<const uint4*>(wpk), wmeta, act0,
-                       enck, encs, part, part_b, Sm, lgSm, ntiles, magic);
+    const int blocks = iod_xcd_grid(ntiles, 1, n_cu);
+    const hipError_t e = iod_launch<refine_bwd01_kernel>(st, dim3(blocks), dim3(512), RB_LDS, (int)RB_LDS, rd1, reinterpret_cast<const uint4*>(wpk),
+                                                         wmeta, act0, enck, encs, part, part_b, Sm, lgSm, ntiles, magic);
 #ifdef IODINE_TILE_PROF
-    {
-        const int nb = std::min(blocks, TP_MAXBLK);
-        std::vector<unsigned> hp((size_t)2 * TP_MAXBLK * 8);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(g_rb_prof), hp.size() * sizeof(unsigned));
-        static const char* cn[8] = {"loop", "enc-pack", "rd-store+load-issue", "frag+mfma", "enc-wait+max", "barrier", "-", "-"};
-        static const char* pn[8] = {"loop", "d-pack", "lds-frag+mfma+elu+max", "barrier", "-", "-", "-", "-"};
-        for (int role = 0; role < 2; ++role) {
-            double sum[8] = {0}, tot = 0;
-            for (int b2 = 0; b2 < nb; ++b2) for (int i = 0; i < 8; ++i) sum[i] += hp[((size_t)role * TP_MAXBLK + b2) * 8 + i];
-            for (int i = 0; i < 8; ++i) tot += sum[i] / nb;
-            fprintf(stderr, "[refbwd01 prof] %s ticks per block (%d tiles), total %.0f:", role ? "producer" : "consumer", (ntiles + blocks - 1) / blocks, tot);
-            for (int i = 0; i < 6; ++i) fprintf(stderr, " %s %.0f |", role ? pn[i] : cn[i], sum[i] / nb);
-            fprintf(stderr, "\n");
-        }
-    }
+    static const char* cn[6] = {"loop", "enc-pack", "rd-store+load-issue", "frag+mfma", "enc-wait+max", "barrier"};
+    static const char* pn[6] = {"loop", "d-pack", "lds-frag+mfma+elu+max", "barrier", "-", "-"};
+    const int per_blk = (ntiles + blocks - 1) / blocks;
+    tp_report(st, HIP_SYMBOL(g_rb_prof), blocks, tp_title("[refbwd01 prof] consumer ticks per block (%d tiles)", per_blk).c_str(), cn, 6);
+    tp_report(st, HIP_SYMBOL(g_rb_prof), blocks, tp_title("[refbwd01 prof] producer ticks per block (%d tiles)", per_blk).c_str(), pn, 6, TP_MAXBLK);
 #endif
     *nparts = blocks * 2;
     *cipad = RB_CIR;
     *nbias_parts = blocks;
-    return hipGetLastError();
+    return e;
 }

@@ -350,7 +350,7 @@ void conv3x3_s2_f16x3_kernel(const float* __restrict__ in, const uint4* __restri
         conv_s2_body<CIN_REAL, CIN, COUT, 0, 0, F32>(in, wpk, wmeta, bias, aux, out, Sc, tiles, kdiv, smem_s2, (int)blockIdx.x);
     } else {
         // The four parity classes of a coarse tile read the SAME staged input: their blocks are made neighbours in dispatch order ON
-        // ONE XCD (block b runs on XCD b % 8, observed; speed only), so that three of the four reads hit that XCD's L2 instead of
+        // ONE XCD (block b runs on XCD b % 8, the convention of xcd_sched.h; observed; speed only), so that three of the four reads hit that XCD's L2 instead of
         // coming from HBM at different times (round 3: 1.42x the algorithmic bytes).  b = 8 (4 q + class) + xcd, tile = 8 q + xcd.
         const int b = (int)blockIdx.x, xcd = b & 7, r = b >> 3, tile = (r >> 2) * 8 + xcd;
         if (tile >= kdiv) return;                            // (kdiv carries the tile count in this mode; block-uniform)
@@ -368,14 +368,11 @@ hipError_t launch_s2_inst(hipStream_t st, const float* in, const void* wpk, cons
                           const float* aux, float* out, int N, int Sc, int kdiv = 0)
 {
     constexpr size_t lds = (size_t)(17 * 17 + 1) * 80 + (size_t)4 * 4 * COUT * 16 + 16;
-    static std::atomic<unsigned> attr_devs{0};                             // devices this instance is configured on
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_s2_f16x3_kernel<CIN_REAL, CIN, COUT, MODE, F32>, (int)lds, attr_devs); e != hipSuccess) return e;
     const int tiles = (Sc + 15) / 16;
     const int ntiles = N * tiles * tiles;
     if (MODE == 1) kdiv = ntiles;                                          // data gradient: 1-D grid, see the kernel
-    hipLaunchKernelGGL((conv3x3_s2_f16x3_kernel<CIN_REAL, CIN, COUT, MODE, F32>), dim3(MODE == 0 ? ntiles : ((ntiles + 7) / 8) * 32),
-                       dim3(256), lds, st, in, reinterpret_cast<const uint4*>(wpk), wmeta, bias, aux, out, Sc, tiles, kdiv);
-    return hipGetLastError();
+    return iod_launch<conv3x3_s2_f16x3_kernel<CIN_REAL, CIN, COUT, MODE, F32>>(st, dim3(MODE == 0 ? ntiles : ((ntiles + 7) / 8) * 32), dim3(256), lds, (int)lds,
+                                                                               in, reinterpret_cast<const uint4*>(wpk), wmeta, bias, aux, out, Sc, tiles, kdiv);
 }
 
 }  // namespace
@@ -808,16 +805,13 @@ hipError_t launch_s2_wgrad32_inst(hipStream_t st, const float* a, const float* d
     constexpr int MT = CI / 32, NTT = NCO / 32, KS = 4 / (MT * NTT);
     constexpr size_t lds = (size_t)(CI * (2 * TH + 1) * 33 + NCO * (TH * 16 + 1)) * 4;
     static_assert(lds >= 256 * 16, "bias reduction reuses the planes");
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_s2_wgrad_f32_kernel<CI_REAL, CI, NCO, TH>, (int)lds, attr_devs); e != hipSuccess) return e;
     const int tiles_x = (Sc + 15) / 16, tiles_y = (Sc + TH - 1) / TH, ntiles = N * tiles_x * tiles_y;
     const int blocks = ntiles < 512 ? ntiles : 512;
-    hipLaunchKernelGGL((conv3x3_s2_wgrad_f32_kernel<CI_REAL, CI, NCO, TH>), dim3(blocks), dim3(256), lds, st, a, d, part,
-                       part_b, Sc, ntiles, tiles_x, tiles_y, a2, kdiv);
     *nparts = blocks * KS;
     *cipad = CI;
     *nbias_parts = blocks;
-    return hipGetLastError();
+    return iod_launch<conv3x3_s2_wgrad_f32_kernel<CI_REAL, CI, NCO, TH>>(st, dim3(blocks), dim3(256), lds, (int)lds, a, d, part, part_b, Sc, ntiles, tiles_x,
+                                                                         tiles_y, a2, kdiv);
 }
 
 template <int CI_REAL, int CI, int NCO, int TH>
@@ -827,16 +821,13 @@ hipError_t launch_s2_wgrad_inst(hipStream_t st, const float* a, const float* d, 
     constexpr int MT = CI / 32, NTT = NCO / 32, KS = 4 / (MT * NTT);
     constexpr size_t lds = (size_t)(2 * CI * (2 * TH + 1) * 20 + 2 * NCO * (TH * 8 + 4)) * 4 + 32;
     static_assert(lds >= 256 * 16, "bias reduction reuses the planes");
-    static std::atomic<unsigned> attr_devs{0};                             // devices this instance is configured on
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_s2_wgrad_f16x3_kernel<CI_REAL, CI, NCO, TH>, (int)lds, attr_devs); e != hipSuccess) return e;
     const int tiles_x = (Sc + 15) / 16, tiles_y = (Sc + TH - 1) / TH, ntiles = N * tiles_x * tiles_y;
     const int blocks = ntiles < 512 ? ntiles : 512;
-    hipLaunchKernelGGL((conv3x3_s2_wgrad_f16x3_kernel<CI_REAL, CI, NCO, TH>), dim3(blocks), dim3(256), lds, st, a, d, part,
-                       part_b, Sc, ntiles, tiles_x, tiles_y, a2, kdiv);
     *nparts = blocks * KS;
     *cipad = CI;
     *nbias_parts = blocks;
-    return hipGetLastError();
+    return iod_launch<conv3x3_s2_wgrad_f16x3_kernel<CI_REAL, CI, NCO, TH>>(st, dim3(blocks), dim3(256), lds, (int)lds, a, d, part, part_b, Sc, ntiles, tiles_x,
+                                                                           tiles_y, a2, kdiv);
 }
 
 }  // namespace

@@ -355,39 +355,27 @@ hipError_t l0_launch(hipStream_t st, const float* x4, const float* dec, const fl
                      unsigned chmask)
 {
     constexpr size_t lds = (size_t)2 * (K + 1) * L0_PLB + 16 + (size_t)3 * (K + 1) * 64 + 64 * 4 + 64 * 4 + 64;
-    static std::atomic<unsigned> attr_devs{0}, attr_devs2{0};
-    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, true, STABLE, JOINT>, (int)lds, attr_devs); e != hipSuccess) return e;
-    if (hipError_t e = iod_set_max_lds((const void*)refine_l0_fused_kernel<K, false, STABLE, JOINT>, (int)lds, attr_devs2); e != hipSuccess) return e;
+    // both forms are configured on every call, whichever is launched (a later, captured call may take the other one)
+    if (hipError_t e = iod_configure<refine_l0_fused_kernel<K, true, STABLE, JOINT>>((int)lds); e != hipSuccess) return e;
+    if (hipError_t e = iod_configure<refine_l0_fused_kernel<K, false, STABLE, JOINT>>((int)lds); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int Sc = S / 2, nunits = B * (Sc / 16) * (Sc / 2);
     const int blocks = std::min(nunits, n_cu);
     const float inv2s2 = 1.f / (2.f * sigma * sigma), invs2 = 1.f / (sigma * sigma);
     const float lconst = (float)(-log((double)sigma) - 0.5 * log(2.0 * M_PI));
-    if ((chmask & 0x1ffffu) == 0x1ffffu)
-        hipLaunchKernelGGL((refine_l0_fused_kernel<K, true, STABLE, JOINT>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
-                           (const uint2*)wk, wkmeta, (const uint2*)ws, wsmeta, bias, out, enck, encs, S, nunits, inv2s2, invs2, lconst, chmask);
-    else
-        hipLaunchKernelGGL((refine_l0_fused_kernel<K, false, STABLE, JOINT>), dim3(blocks), dim3(448), lds, st, (const float4*)x4, (const float4*)dec, lnstat, lin,
-                           (const uint2*)wk, wkmeta, (const uint2*)ws, wsmeta, bias, out, enck, encs, S, nunits, inv2s2, invs2, lconst, chmask);
+    const hipError_t e = iod_dispatch_bool((chmask & 0x1ffffu) == 0x1ffffu, [&](auto all) {      // max_lds 0: configured above
+        return iod_launch<refine_l0_fused_kernel<K, all, STABLE, JOINT>>(st, dim3(blocks), dim3(448), lds, 0, (const float4*)x4, (const float4*)dec, lnstat, lin,
+                                                                         (const uint2*)wk, wkmeta, (const uint2*)ws, wsmeta, bias, out, enck, encs, S, nunits,
+                                                                         inv2s2, invs2, lconst, chmask);
+    });
 #ifdef IODINE_TILE_PROF
-    {
-        const int nb = std::min(blocks, TP_MAXBLK);
-        std::vector<unsigned> hp((size_t)2 * TP_MAXBLK * 8);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(g_l0_prof), hp.size() * sizeof(unsigned));
-        static const char* pn[5] = {"loop", "convert / work", "barrier", "mfma / -", "barrier"};
-        for (int role = 0; role < 2; ++role) {
-            double sum[8] = {0}, tot = 0;
-            for (int b2 = 0; b2 < nb; ++b2) for (int i = 0; i < 8; ++i) sum[i] += hp[((size_t)role * TP_MAXBLK + b2) * 8 + i];
-            for (int i = 0; i < 8; ++i) tot += sum[i] / nb;
-            fprintf(stderr, "[refl0 prof] %s ticks per block (%d units), total %.0f:", role ? "producer" : "consumer", (nunits + blocks - 1) / blocks, tot);
-            for (int i = 0; i < 5; ++i) fprintf(stderr, " %s %.0f |", pn[i], sum[i] / nb);
-            fprintf(stderr, "\n");
-        }
-    }
+    static const char* pn[5] = {"loop", "convert / work", "barrier", "mfma / -", "barrier"};
+    const int per_blk = (nunits + blocks - 1) / blocks;
+    tp_report(st, HIP_SYMBOL(g_l0_prof), blocks, tp_title("[refl0 prof] consumer ticks per block (%d units)", per_blk).c_str(), pn, 5);
+    tp_report(st, HIP_SYMBOL(g_l0_prof), blocks, tp_title("[refl0 prof] producer ticks per block (%d units)", per_blk).c_str(), pn, 5, TP_MAXBLK);
 #endif
-    return hipGetLastError();
+    return e;
 }
 
 }  // namespace
@@ -402,14 +390,11 @@ hipError_t launch_refine_l0_fused(hipStream_t st, const float* x4, const float* 
 {
     IOD_XSKIP(512);
     if (!refine_l0_fused_ok(S, c, K) || (enck == nullptr) != (encs == nullptr)) return hipErrorInvalidValue;
-    switch (K) {
-#define L0_ARGS st, x4, dec, lnstat, lin, wk, wkmeta, ws, wsmeta, bias, out, enck, encs, B, S, sigma, chmask
-#define L0_CASE(KK) case KK: \
-        if (joint) return stable ? l0_launch<KK, true, true>(L0_ARGS) : l0_launch<KK, false, true>(L0_ARGS); \
-        return stable ? l0_launch<KK, true, false>(L0_ARGS) : l0_launch<KK, false, false>(L0_ARGS);
-        L0_CASE(1) L0_CASE(2) L0_CASE(3) L0_CASE(4) L0_CASE(5) L0_CASE(6) L0_CASE(7) L0_CASE(8) L0_CASE(9)
-#undef L0_CASE
-#undef L0_ARGS
-        default: return hipErrorInvalidValue;
-    }
+    return iod_dispatch<1, 2, 3, 4, 5, 6, 7, 8, 9>(K, [&](auto kk) {
+        return iod_dispatch_bool(stable != 0, [&](auto stb) {
+            return iod_dispatch_bool(joint != 0, [&](auto jnt) {
+                return l0_launch<kk, stb, jnt>(st, x4, dec, lnstat, lin, wk, wkmeta, ws, wsmeta, bias, out, enck, encs, B, S, sigma, chmask);
+            });
+        });
+    });
 }

@@ -260,18 +260,12 @@ hipError_t launch_conv3x3_s2ws_f16x3(hipStream_t st, const float* in, const void
     IOD_XSKIP(512);
     if (!conv3x3_s2ws_ok(S, c) || !bias) return hipErrorInvalidValue;
     constexpr size_t lds = (size_t)2 * RW_BUFB + 32 + 64 * 4;
-    static std::atomic<unsigned> attr_devs{0}, attr_devs32{0};
-    if (hipError_t e = f32 ? iod_set_max_lds((const void*)conv3x3_s2ws_f16x3_kernel<64, true>, (int)lds, attr_devs32)
-                           : iod_set_max_lds((const void*)conv3x3_s2ws_f16x3_kernel<64>, (int)lds, attr_devs); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int Sc = S / 2, tiles_x = (Sc + 15) / 16, tiles_y = (Sc + 1) / 2, ntiles = N * tiles_x * tiles_y;
     const int blocks = std::min(ntiles, 2 * n_cu);
-    if (f32)
-        hipLaunchKernelGGL((conv3x3_s2ws_f16x3_kernel<64, true>), dim3(blocks), dim3(256), lds, st, in, reinterpret_cast<const uint4*>(wpk), wmeta, bias,
-                           out, Sc, tiles_x, tiles_y, ntiles);
-    else
-    hipLaunchKernelGGL((conv3x3_s2ws_f16x3_kernel<64>), dim3(blocks), dim3(256), lds, st, in, reinterpret_cast<const uint4*>(wpk), wmeta, bias,
-                       out, Sc, tiles_x, tiles_y, ntiles);
-    return hipGetLastError();
+    return iod_dispatch_bool(f32 != 0, [&](auto f) {
+        return iod_launch<conv3x3_s2ws_f16x3_kernel<64, f>>(st, dim3(blocks), dim3(256), lds, (int)lds, in, reinterpret_cast<const uint4*>(wpk), wmeta,
+                                                            bias, out, Sc, tiles_x, tiles_y, ntiles);
+    });
 }

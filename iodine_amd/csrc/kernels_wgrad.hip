@@ -111,15 +111,11 @@ static hipError_t launch_wgrad_tile_inst(hipStream_t st, const float* a, const f
 {
     constexpr int MT = CI / 32, NTT = (NCO + 31) / 32, KS = 4 / (MT * NTT);
     constexpr size_t lds = (size_t)(10 * 18 * CI + 8 * 16 * NCO) * 4;
-    static std::atomic<unsigned> attr_devs{0};                             // devices this instance is configured on
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_wgrad_tile_kernel<CI, NCO>, (int)lds, attr_devs); e != hipSuccess) return e;
     const int tiles_x = S / 16, tiles_y = S / 8, ntiles = N * tiles_x * tiles_y;
     const int blocks = wgrad_tile_blocks(N, S);
-    hipLaunchKernelGGL((conv3x3_wgrad_tile_kernel<CI, NCO>), dim3(blocks), dim3(256), lds, st, a, d, part, part_b, S,
-                       ntiles, tiles_x, tiles_y);
     *nparts = blocks * KS;
     *ncop = NTT * 32;
-    return hipGetLastError();
+    return iod_launch<conv3x3_wgrad_tile_kernel<CI, NCO>>(st, dim3(blocks), dim3(256), lds, (int)lds, a, d, part, part_b, S, ntiles, tiles_x, tiles_y);
 }
 
 hipError_t launch_conv3x3_wgrad_tile(hipStream_t st, const float* a, const float* d, float* part, float* part_b, int N,

@@ -48,6 +48,7 @@ void conv3x3_wgrad_f32_ws_kernel(const float* __restrict__ a, const float* __res
 #define W32_SGPR_SETTLE(rsrc) asm volatile("s_nop 4" :: "s"(rsrc) : "memory")
 
     // persistent, XCD-aware schedule (block b runs on XCD b % 8: observed, used for locality only)
+    // (the schedule of xcd_span, xcd_sched.h, spelled out: through the function the compiler orders these scalar instructions differently)
     const int nblk = gridDim.x;
     const int xcd = blockIdx.x & 7, bix = blockIdx.x >> 3, bpx = (nblk + 7) >> 3;
     const int per_xcd = (ntiles + 7) >> 3;
@@ -187,10 +188,7 @@ void conv3x3_wgrad_f32_ws_kernel(const float* __restrict__ a, const float* __res
 
 int wgrad_f32_ws_blocks(int N, int S, int n_cu)
 {
-    const int nt = N * (S / 4) * (S / 16);
-    const int per_xcd = (nt + 7) / 8;
-    const int bpx = std::min(per_xcd, std::max(1, 2 * n_cu / 8));       // two persistent blocks per CU
-    return 8 * bpx;
+    return iod_xcd_grid(N * (S / 4) * (S / 16), 2, n_cu);               // two persistent blocks per CU
 }
 
 template <int C>
@@ -199,18 +197,15 @@ static hipError_t launch_wgrad_f32_ws_inst(hipStream_t st, const float* a, const
 {
     constexpr int KS = 4 / ((C / 32) * (C / 32));
     constexpr size_t lds = (size_t)(C / 32) * (6 * 18 + 4 * 16) * 128;
-    static std::atomic<unsigned> attr_devs{0};
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_wgrad_f32_ws_kernel<C>, (int)lds, attr_devs); e != hipSuccess) return e;
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int ntiles = N * (S / 4) * (S / 16);
     int blocks = wgrad_f32_ws_blocks(N, S, n_cu);
     if (blocks > 512) blocks = 512;                                      // capacity of the partial-tile buffers (plan(): 512 blocks)
-    hipLaunchKernelGGL((conv3x3_wgrad_f32_ws_kernel<C>), dim3(blocks), dim3(256), lds, st, a, d, part, part_b, S, ntiles, alpha, accum);
     *nparts = blocks * KS;
     *ncop = C;
     *nbias_parts = blocks;
-    return hipGetLastError();
+    return iod_launch<conv3x3_wgrad_f32_ws_kernel<C>>(st, dim3(blocks), dim3(256), lds, (int)lds, a, d, part, part_b, S, ntiles, alpha, accum);
 }
 
 // a, d: NHWC [N][S][S][c]; part: [nparts][9][c][c], part_b: [nbias_parts][c] (reduced by launch_wgrad_reduce)
@@ -255,7 +250,7 @@ void dec_out_wgrad_f32_kernel(const float* __restrict__ a, const float* __restri
 #define OW_BLOAD4(dst, voff, rsrc, soff) \
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory")
 
-    const int nblk = gridDim.x;
+    const int nblk = gridDim.x;                                         // (xcd_span of xcd_sched.h, spelled out as above)
     const int xcd = blockIdx.x & 7, bix = blockIdx.x >> 3, bpx = (nblk + 7) >> 3;
     const int per_xcd = (ntiles + 7) >> 3;
     const int t_begin = xcd * per_xcd, t_end = min(ntiles, t_begin + per_xcd);
@@ -366,9 +361,7 @@ static hipError_t launch_dec_out_wgrad_f32_inst(hipStream_t st, const float* a, 
     int n_cu = 0;
     if (hipError_t e = iod_cu_count(&n_cu); e != hipSuccess) return e;
     const int ntiles = N * (S / 4) * (S / 16);
-    const int per_xcd = (ntiles + 7) / 8;
-    const int bpx = std::min(per_xcd, std::max(1, 4 * n_cu / 8));       // four persistent blocks per CU
-    const int blocks = std::min(8 * bpx, 1024);                         // (capacity of the partial-tile buffers)
+    const int blocks = std::min(iod_xcd_grid(ntiles, 4, n_cu), 1024);   // four persistent blocks per CU (capacity of the partial-tile buffers)
     hipLaunchKernelGGL((dec_out_wgrad_f32_kernel<C>), dim3(blocks), dim3(256), lds, st, a, g, part, part_b, S, ntiles);
     *nparts = blocks * KS;
     *nbias_parts = blocks;

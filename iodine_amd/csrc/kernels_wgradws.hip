@@ -4,6 +4,10 @@
 #include <vector>
 #include <cstdio>
 
+#ifdef IODINE_TILE_PROF
+__device__ unsigned g_wgrad_prof[TP_MAXBLK * 8];            // [block][phase]: consumer wave 0 in 0-1, producer wave 4 in 2-7
+#endif
+
 // =========================================================================================
 // Warp-specialised form of conv3x3_wgrad_f16x3_kernel (same arithmetic, same partial-tile output).
 // The one-role kernel spends 42 % of a tile waiting for its global loads and 31 % splitting / transposing them into
@@ -50,6 +54,7 @@ void conv3x3_wgrad_f16x3_ws_kernel(const float* __restrict__ a, const float* __r
     // the plain order (tile = block + q * blocks) neighbouring tiles sat on different XCDs and every halo was fetched from memory again:
     // PMC at the cfg2 shapes 286 MB per launch against 210 MB of operands + partial tiles (profiles/r06_pmc_dsprites.json).  Needs a grid
     // that is a multiple of 8; the tile -> block map only changes WHICH partial tile a product lands in (fixed: results stay deterministic).
+    // (xcd_span(.., xcd_order) of xcd_sched.h, spelled out: through the function the compiler orders these scalar instructions differently)
     const bool xcd_order = (gridDim.x & 7) == 0;
     const int bpx = xcd_order ? (int)(gridDim.x >> 3) : (int)gridDim.x;              // tile stride of a block
     const int per_xcd = (ntiles + 7) >> 3;
@@ -490,29 +495,18 @@ static hipError_t launch_wgrad_f16_ws_inst(hipStream_t st, const float* a, const
     constexpr size_t buf = true ? (size_t)6 * 20 * (2 * CI * 2 + 64) + (size_t)4 * 16 * (2 * NCO * 2 + 64)
                               : (size_t)(2 * CI * 76 + 2 * NCO * 36) * 4;
     constexpr size_t lds = 2 * buf + 26 * 4 + 32;
-    static std::atomic<unsigned> attr_devs{0};                             // devices this instance is configured on
-    if (hipError_t e = iod_set_max_lds((const void*)conv3x3_wgrad_f16x3_ws_kernel<CI, NCO, TR>, (int)lds, attr_devs); e != hipSuccess) return e;
     const int tiles_x = S / 16, tiles_y = S / 4, ntiles = N * tiles_x * tiles_y;
     const int blocks = ntiles < 256 ? ntiles : 256;
-    hipLaunchKernelGGL((conv3x3_wgrad_f16x3_ws_kernel<CI, NCO, TR>), dim3(blocks), dim3(512), lds, st, a, d, part, part_b, S,
-                       ntiles, tiles_x, tiles_y, alpha, accum);
+    const hipError_t e = iod_launch<conv3x3_wgrad_f16x3_ws_kernel<CI, NCO, TR>>(st, dim3(blocks), dim3(512), lds, (int)lds, a, d, part, part_b, S,
+                                                                                ntiles, tiles_x, tiles_y, alpha, accum);
 #ifdef IODINE_TILE_PROF
-    {
-        std::vector<unsigned> hp((size_t)blocks * 8);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(g_wgrad_prof), hp.size() * sizeof(unsigned));
-        static const char* names[8] = {"C:mfma-phase", "C:barrier", "P:load-issue", "P:split+lds-write", "P:load-wait+max", "P:barrier", "-", "P:loop-edge"};
-        double sum[8] = {0};
-        for (int b2 = 0; b2 < blocks; ++b2) for (int i = 0; i < 8; ++i) sum[i] += hp[(size_t)b2 * 8 + i];
-        fprintf(stderr, "[wgrad ws prof <%d,%d>] memtime ticks per TILE:", CI, NCO);
-        for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.0f |", names[i], sum[i] / (double)ntiles);
-        fprintf(stderr, "\n");
-    }
+    static const char* names[8] = {"C:mfma-phase", "C:barrier", "P:load-issue", "P:split+lds-write", "P:load-wait+max", "P:barrier", "-", "P:loop-edge"};
+    tp_report(st, HIP_SYMBOL(g_wgrad_prof), blocks, tp_title("[wgrad ws prof <%d,%d>] memtime ticks per TILE", CI, NCO).c_str(), names, 8, 0, ntiles);
 #endif
     *nparts = blocks;                                                       // (round 6: the KS K-split sets of a block are summed before the write)
     *ncop = NTT * 32;
     *nbias = blocks;
-    return hipGetLastError();
+    return e;
 }
 
 // variant 1: transposing stagers + v_alignbit shifts; variant 2: natural-order staging + ds_read_b64_tr_b16
