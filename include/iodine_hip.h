@@ -542,6 +542,51 @@ int iodine_slot_table(void* stream, const float* mask, const float* mean_or_null
 int iodine_seg_overlap(void* stream, const unsigned char* seg_a, const unsigned char* seg_b, int batch, int slots_a, int slots_b,
                        int pixels, int* table);
 
+/* Refinement restarts (IODINE.restarts): inference is stochastic and multi-stable, so the same images are refined C times - C chains - and
+ * the chains are scored, labelled and folded into one labelling.  Two stateless entries in the contract of the two above: no handle, no
+ * workspace, no allocation, no synchronise, everything on `stream`, no float atomics.  P = size * size; row c B + b of a (C,B,..) tensor is
+ * chain c of image b, as iodine_reconstruct returns the decodes of x repeated chain-major.
+ *
+ * iodine_chain_score: x (B,3,S,S) fp32, w_or_null (B,S,S) fp32 observation weights (NULL = 1), mask (C,B,K,1,S,S), mean (C,B,K,3,S,S) fp32
+ *   (device) -> ll_or_null (C,B) fp32, seg_or_null (C,B,S,S) uint8 (device, overwritten; either may be NULL, not both).
+ *     ll[c][b] = sum_p w_p LL_p,  l_kc = -(x_c - mu_kc)^2 / (2 sigma^2) - ln sigma - ln(2 pi) / 2          (iodine.py:213-216, 661-666)
+ *     joint = 0:  LL_p = sum_c logsumexp_k(log(m_k + 1e-12) + l_kc)       joint = 1:  LL_p = logsumexp_k(log(m_k + 1e-12) + sum_c l_kc)
+ *   the likelihood of the state a reconstruct RETURNS, which its elbo terms (lambda_0 .. lambda_{T-1}) never score.  fp32 per pixel; each
+ *   logsumexp runs over the slots in index order with the maximum so far subtracted from every exponent (the sum is rescaled when the
+ *   maximum rises), w_p LL_p is formed and added in fp64 - per thread in pixel order, per wave in a fixed butterfly, across waves in index
+ *   order - and rounded to fp32 once: the same input gives the same bits on every call.
+ *     seg[c][b][p] = argmax_k m_k, comparing `v > best` from slot 0 upwards: the LOWEST index wins a tie and a NaN never wins - the rules,
+ *   and for the same masks the bits, of iodine_slot_table's map.
+ *   One thread owns a pixel of an image and loops over the chains of its block, so every mask and mean plane is read once and x / w once
+ *   per block of chains; 16-byte loads where P % 4 == 0 and x, w, mask, mean are 16-byte and seg 4-byte aligned, scalar loads otherwise.
+ *   IODINE_ERR_INVALID, before anything touches the device, the argument named in iodine_last_error(NULL): x, mask or mean NULL, chains
+ *   outside 1..1024, batch < 1 (or chains * batch >= 2^31), slots outside 1..16, size outside 1..1024, sigma <= 0 or NaN, joint other
+ *   than 0 / 1, ll_or_null and seg_or_null both NULL.
+ *
+ * iodine_chain_consensus: seg (C,B,P) uint8 (e.g. the seg above), perm (C,B,K) int32 - slot i of chain c is slot perm[c][b][i] of the
+ *   common labelling (iodine_seg_overlap of every chain against one of them, 1 - IoU into iodine_assign) -, ref_or_null (B) int32 - each
+ *   image's reference chain -, mask_or_null (C,B,K,1,S,S) fp32.  The relabelled label of chain c at pixel p is t = perm[c][b][seg[c][b][p]].
+ *   Outputs, device, overwritten, each may be NULL (not all):
+ *     votes (B,K,P) int32      votes[b][j][p] = #{c : t_c(p) = j}
+ *     consensus (B,P) uint8    argmax_j votes, `v > best` from 0 upwards from a best of 0: the lowest index on a tie
+ *     agreement (B,P) fp32     (float)votes[winner] / (float)C
+ *     match (C,B) fp32         (float)((double)#{p : t_c(p) = t_ref[b](p)} / (double)P); needs ref
+ *     mask_mean (B,K,1,P) fp32 mask_mean[b][j][p] = (sum_c sum_{i : perm[c][b][i] = j} mask[c][b][i][p]) / (float)C, added in fp32 from 0 in
+ *                              chain order (i ascending within a chain) and divided once; needs mask
+ *   Index safety: a label >= K, or a perm entry outside 0..K-1, leaves that pixel of that chain out of every count (and such a slot out of
+ *   mask_mean); a ref[b] outside 0..C-1 leaves match[.][b] = 0; device data is never used as an index unchecked.  WITH SUCH A PIXEL THE
+ *   VOTES SUM TO LESS THAN C, and a pixel no chain votes on reads consensus 0, agreement 0.  Counts are integers and exact; perm is not
+ *   required to be a permutation.  16-byte accesses where P % 4 == 0 and the pointers are aligned for them (seg, consensus 4 bytes; mask,
+ *   votes, agreement, mask_mean 16), element-wise otherwise.
+ *   IODINE_ERR_INVALID, before anything touches the device, the argument named in iodine_last_error(NULL): seg or perm NULL, chains
+ *   outside 1..1024, batch < 1 (or chains * batch >= 2^31), slots outside 1..16, size outside 1..1024, match without ref, mask_mean
+ *   without mask, every output NULL. */
+int iodine_chain_score(void* stream, const float* x, const float* w_or_null, const float* mask, const float* mean, int chains, int batch,
+                       int slots, int size, double sigma, int joint, float* ll_or_null, unsigned char* seg_or_null);
+int iodine_chain_consensus(void* stream, const unsigned char* seg, const int* perm, const int* ref_or_null, const float* mask_or_null,
+                           int chains, int batch, int slots, int size, int* votes_or_null, unsigned char* consensus_or_null,
+                           float* agreement_or_null, float* match_or_null, float* mask_mean_or_null);
+
 /* Slots matched to ground-truth masks: the K slots are exchangeable, so a loss (or a metric) against G object masks needs a minimum-cost
  * assignment of objects to slots per image.  Five stateless entries - no handle, no workspace, no synchronise - of which a training step
  * uses three: a per-pixel pass (iodine_mask_overlap), a tiny pass (iodine_mask_match), a per-pixel pass (iodine_mask_match_backward).

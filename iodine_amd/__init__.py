@@ -2,10 +2,10 @@
 ``IODINE.forward / reconstruct`` module API.  Heavy imports are lazy so that
 ``iodine_amd.synth`` can be used without the HIP library being built."""
 
-__all__ = ['IODINE', 'Predictive', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse', 'matching', 'figures',
+__all__ = ['IODINE', 'Predictive', 'Restarts', 'chains', 'chain_score', 'chain_consensus', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse', 'matching', 'figures',
            'slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS', 'latent_kl', 'rank_dims', 'Traversal',
            'pack_gt', 'overlap', 'assign', 'match_masks', 'matched_mask_loss', 'segmentation_scores', 'SegmentationEvaluator',
-           'PALETTE', 'sheet', 'layout', 'matched_colors', 'decomposition', 'trajectory_sheet', 'encode_png', 'write_png']
+           'PALETTE', 'sheet', 'layout', 'matched_colors', 'decomposition', 'trajectory_sheet', 'restarts_sheet', 'encode_png', 'write_png']
 
 
 def __getattr__(name):
@@ -15,6 +15,12 @@ def __getattr__(name):
     if name == 'Predictive':                                  # (what ``IODINE.predictive`` returns)
         from .model import Predictive
         return Predictive
+    if name == 'Restarts':                                    # (what ``IODINE.restarts`` returns)
+        from .model import Restarts
+        return Restarts
+    if name in ('chain_score', 'chain_consensus'):
+        from . import chains
+        return getattr(chains, name)
     if name in ('slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS'):
         from . import objects
         return getattr(objects, name)
@@ -24,7 +30,7 @@ def __getattr__(name):
     if name in ('pack_gt', 'overlap', 'assign', 'match_masks', 'matched_mask_loss', 'segmentation_scores', 'SegmentationEvaluator'):
         from . import matching
         return getattr(matching, name)
-    if name in ('PALETTE', 'sheet', 'layout', 'matched_colors', 'decomposition', 'trajectory_sheet', 'encode_png', 'write_png'):
+    if name in ('PALETTE', 'sheet', 'layout', 'matched_colors', 'decomposition', 'trajectory_sheet', 'restarts_sheet', 'encode_png', 'write_png'):
         from . import figures
         return getattr(figures, name)
     raise AttributeError(name)

@@ -121,6 +121,9 @@ _SYMBOLS = {
     # object tables, iodine_amd.objects
     'iodine_slot_table': ([_vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp],),
     'iodine_seg_overlap': ([_vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp],),
+    # refinement restarts, iodine_amd.chains / IODINE.restarts (a build without them raises on it)
+    'iodine_chain_score': ([_vp] * 5 + [_ci] * 4 + [_dbl, _ci, _vp, _vp],),
+    'iodine_chain_consensus': ([_vp] * 5 + [_ci] * 4 + [_vp] * 5,),
     # IODINE.edit, iodine_amd.traverse (a build without it raises on them)
     'iodine_scene_edit': ([_vp, _vp, _ci, _vp, _ci, _CIP, _CIP, _CIP, _vp, _ci] + [_vp] * 6,),
     # kernel-level tests of the per-pixel mixture kernels

@@ -234,6 +234,12 @@ hipError_t launch_slot_table(hipStream_t st, const float* mask, const float* mea
                              unsigned char* seg);
 hipError_t launch_seg_overlap(hipStream_t st, const unsigned char* seg_a, const unsigned char* seg_b, int B, int Ka, int Kb, int P,
                               int* table);
+// kernels_chains.hip: refinement restarts - C decodes of the same images scored and labelled, C labellings folded into one (stateless)
+hipError_t launch_chain_score(hipStream_t st, const float* x, const float* w, const float* mask, const float* mean, int C, int B, int K,
+                              int S, double sigma, int joint, float* ll, unsigned char* seg);
+hipError_t launch_chain_consensus(hipStream_t st, const unsigned char* seg, const int* perm, const int* ref, const float* mask, int C,
+                                  int B, int K, int S, int* votes, unsigned char* consensus, float* agreement, float* match,
+                                  float* mask_mean);
 // kernels_sheet.hip: decomposition sheets - panels of a few scenes as one uint8 HWC picture (stateless).  W = the sheet's width;
 // sheet_form: bit 0 = 16-byte loads, bit 1 = word stores, what the launcher will take for these pointers.
 struct iodine_sheet_spec;

@@ -76,6 +76,38 @@ int iodine_seg_overlap(void* stream, const unsigned char* seg_a, const unsigned 
     return launched("iodine_seg_overlap", launch_seg_overlap((hipStream_t)stream, seg_a, seg_b, batch, slots_a, slots_b, pixels, table));
 }
 
+int iodine_chain_score(void* stream, const float* x, const float* w_or_null, const float* mask, const float* mean, int chains, int batch,
+                       int slots, int size, double sigma, int joint, float* ll_or_null, unsigned char* seg_or_null)
+{
+    const char* bad = !x ? "x is NULL" : !mask ? "mask is NULL" : !mean ? "mean is NULL"
+        : (chains < 1 || chains > 1024) ? "chains must be in 1..1024" : batch < 1 ? "batch must be >= 1"
+        : (long long)chains * batch > 0x7fffffffLL ? "chains * batch must be below 2^31"
+        : (slots < 1 || slots > 16) ? "slots must be in 1..16" : (size < 1 || size > 1024) ? "size must be in 1..1024"
+        : !(sigma > 0.0) ? "sigma must be > 0" : (joint != 0 && joint != 1) ? "joint must be 0 (per channel) or 1 (joint over RGB)"
+        : (!ll_or_null && !seg_or_null) ? "ll_or_null and seg_or_null are both NULL: nothing to compute" : nullptr;
+    if (bad) { g_create_error = std::string("iodine_chain_score: ") + bad; return IODINE_ERR_INVALID; }
+    return launched("iodine_chain_score", launch_chain_score((hipStream_t)stream, x, w_or_null, mask, mean, chains, batch, slots, size, sigma,
+                                                             joint, ll_or_null, seg_or_null));
+}
+
+int iodine_chain_consensus(void* stream, const unsigned char* seg, const int* perm, const int* ref_or_null, const float* mask_or_null,
+                           int chains, int batch, int slots, int size, int* votes_or_null, unsigned char* consensus_or_null,
+                           float* agreement_or_null, float* match_or_null, float* mask_mean_or_null)
+{
+    const char* bad = !seg ? "seg is NULL" : !perm ? "perm is NULL"
+        : (chains < 1 || chains > 1024) ? "chains must be in 1..1024" : batch < 1 ? "batch must be >= 1"
+        : (long long)chains * batch > 0x7fffffffLL ? "chains * batch must be below 2^31"
+        : (slots < 1 || slots > 16) ? "slots must be in 1..16" : (size < 1 || size > 1024) ? "size must be in 1..1024"
+        : (match_or_null && !ref_or_null) ? "match needs ref, which is NULL"
+        : (mask_mean_or_null && !mask_or_null) ? "mask_mean needs mask, which is NULL"
+        : (!votes_or_null && !consensus_or_null && !agreement_or_null && !match_or_null && !mask_mean_or_null)
+              ? "votes, consensus, agreement, match and mask_mean are all NULL: nothing to compute" : nullptr;
+    if (bad) { g_create_error = std::string("iodine_chain_consensus: ") + bad; return IODINE_ERR_INVALID; }
+    return launched("iodine_chain_consensus", launch_chain_consensus((hipStream_t)stream, seg, perm, ref_or_null, mask_or_null, chains, batch, slots,
+                                                                     size, votes_or_null, consensus_or_null, agreement_or_null, match_or_null,
+                                                                     mask_mean_or_null));
+}
+
 int iodine_mask_overlap(void* stream, const float* mask, const unsigned char* gt, int batch, int slots, int n_gt, int size, float eps,
                         float* inter, float* nll_or_null, float* mask_area, int* gt_area)
 {

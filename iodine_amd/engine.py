@@ -380,7 +380,7 @@ def make_log_sigma(sigma, device):
     return torch.full((), math.log(float(sigma)), dtype=torch.float32, device=device, requires_grad=True)
 
 
-def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, bound_samples=0):
+def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, bound_samples=0, restarts=0):
     """eval.py:14-28 with the ARI evaluator of lib/eval/ari_eval.py (works under no_grad, unlike the reference).  With
     several ranks every rank evaluates its shard; the samples DistributedSampler appended to pad the shards to equal length
     are dropped (they duplicate the first images) and ``evaluator.global_mean`` holds the ARI over the whole dataset.
@@ -389,25 +389,50 @@ def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, 
     ``bound_samples`` = S > 0: after each batch's ``reconstruct`` one ``model.predictive(x, samples=S)`` from the posterior it left; the
     dataset means of the S-sample importance-weighted bound and of the S-sample Monte-Carlo ELBO (per image, nats) are left in
     ``evaluator.iwae`` / ``evaluator.elbo_mc`` (over all ranks, like ``global_mean``).  0 (default): no launch is added and neither
-    attribute is set."""
+    attribute is set.
+    ``restarts`` = C > 1: every batch is refined C times (``model.restarts(x, chains=C)``) and the evaluators, which keep calling
+    ``model.reconstruct``, get the best chain's decode per image through a thin proxy; ``evaluator.stability``, ``evaluator.best_score`` and
+    ``evaluator.first_score`` are the dataset means (over all ranks) of ``Restarts.stability``, of the best chain's score and of chain 0's -
+    what selecting gains, next to the metric.  ``bound_samples`` then samples around the chosen posterior.  0 or 1 (default): the path and
+    the bits of an evaluation without it, and none of the three attributes."""
     if isinstance(bound_samples, bool) or int(bound_samples) != bound_samples or bound_samples < 0:
         raise ValueError(f'evaluate: bound_samples must be an integer >= 0; got {bound_samples!r}')
+    if isinstance(restarts, bool) or int(restarts) != restarts or restarts < 0:
+        raise ValueError(f'evaluate: restarts must be an integer >= 0; got {restarts!r}')
     saved = (model.K, model.n_iters)
     if slots is not None:
         model.K = slots
     if iters is not None:
         model.n_iters = iters
     try:
-        return _evaluate(model, dataloader, device, evaluator, int(bound_samples))
+        return _evaluate(model, dataloader, device, evaluator, int(bound_samples), int(restarts))
     finally:
         model.K, model.n_iters = saved
 
 
-def _evaluate(model, dataloader, device, evaluator, bound_samples=0):
+class _BestOfRestarts:
+    """What ``evaluate(restarts=C)`` hands the evaluators in place of the model: ``reconstruct(x)`` runs ``model.restarts(x, chains=C)`` and
+    returns the best chain's decode per image; everything else is the model's.  ``rows``: per image (stability, best score, chain 0's)."""
+
+    def __init__(self, model, chains):
+        self._model, self._chains, self.rows = model, chains, []
+
+    def __getattr__(self, name):
+        return getattr(self._model, name)
+
+    def reconstruct(self, x):
+        res = self._model.restarts(x, chains=self._chains)
+        best = res.score.gather(0, res.best.view(1, -1))[0]
+        self.rows.extend(zip(res.stability.tolist(), best.tolist(), res.score[0].tolist()))
+        return res.pred, res.mask, res.mean
+
+
+def _evaluate(model, dataloader, device, evaluator, bound_samples=0, restarts=0):
     evaluator = evaluator or ARIEvaluator()
     evaluator.reset()
     bounds = []                                                              # per image: (iwae, elbo_mc)
     model.eval()
+    scored = _BestOfRestarts(model, restarts) if restarts > 1 else model     # (what the evaluators call reconstruct on)
     dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
     world = torch.distributed.get_world_size() if dist_on else 1
     rank = torch.distributed.get_rank() if dist_on else 0
@@ -417,9 +442,9 @@ def _evaluate(model, dataloader, device, evaluator, bound_samples=0):
         for data in dataloader:
             image, masks = data[0], data[1]
             if torch.is_tensor(masks):                                       # a ResidentDataset batch: packed on the device, with counts
-                evaluator.evaluate(model, (image.to(device), masks, data[2]))
+                evaluator.evaluate(scored, (image.to(device), masks, data[2]))
             else:
-                evaluator.evaluate(model, (image.to(device), [m.numpy() for m in masks]))
+                evaluator.evaluate(scored, (image.to(device), [m.numpy() for m in masks]))
             if bound_samples:
                 out = model.predictive(image.to(device), samples=bound_samples)
                 bounds.extend(zip(out.iwae.tolist(), out.elbo_mc.tolist()))
@@ -434,6 +459,14 @@ def _evaluate(model, dataloader, device, evaluator, bound_samples=0):
             torch.distributed.all_reduce(tot)
         n = max(float(tot[2]), 1.0)
         evaluator.iwae, evaluator.elbo_mc = float(tot[0]) / n, float(tot[1]) / n
+    if restarts > 1:
+        rows = scored.rows[:mine]
+        tot = torch.tensor([sum(q[i] for q in rows) for i in range(3)] + [float(len(rows))], dtype=torch.float64,
+                           device=device if dist_on and torch.distributed.get_backend() == 'nccl' else 'cpu')
+        if world > 1:
+            torch.distributed.all_reduce(tot)
+        n = max(float(tot[3]), 1.0)
+        evaluator.stability, evaluator.best_score, evaluator.first_score = (float(tot[i]) / n for i in range(3))
     stats = torch.tensor([float(sum(evaluator.aris)), float(len(evaluator.aris))], dtype=torch.float64,
                          device=device if dist_on and torch.distributed.get_backend() == 'nccl' else 'cpu')
     if world > 1:
@@ -545,6 +578,9 @@ def make_parser():
     ap.add_argument('--eval-samples', type=int, default=0, metavar='S',
                     help='also report the S-sample importance-weighted bound (IWAE) and the S-sample Monte-Carlo ELBO of the evaluation set, '
                          'per image in nats (one model.predictive call per batch; 0: off)')
+    ap.add_argument('--eval-restarts', type=int, default=0, metavar='C',
+                    help='evaluate the best of C refinement chains per image (IODINE.restarts) and report the stability of the chains and '
+                         'the gain of selecting; 0 / 1 = one chain, the usual evaluation')
     ap.add_argument('--mask-loss', type=float, default=0.0, metavar='W',
                     help='supervised masks: add W * matched_mask_loss(model.mask, ground truth) to every step whose batch carries masks '
                          '(ground-truth objects assigned to slots on the device; 0: off)')
@@ -661,7 +697,7 @@ def main(argv=None):
         from .matching import SegmentationEvaluator
         evaluator = SegmentationEvaluator()
     ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
-                  bound_samples=args.eval_samples)
+                  bound_samples=args.eval_samples, restarts=args.eval_restarts)
     _report(args, rank, losses, ev)
     _final_sheet(args, model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, rank)
 
@@ -706,7 +742,7 @@ def _main_resident(args, arch, model, optimizer, ds, device, rank, world, log_si
         from .matching import SegmentationEvaluator
         evaluator = SegmentationEvaluator()
     ev = evaluate(model, store.batches(args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
-                  bound_samples=args.eval_samples)
+                  bound_samples=args.eval_samples, restarts=args.eval_restarts)
     _report(args, rank, losses, ev)
     _final_sheet(args, model, store.batches(args.batch, shuffle=False, rank=rank, world_size=world), device, rank)
 
@@ -716,6 +752,9 @@ def _report(args, rank, losses, ev):
         print('first loss {:.2f} -> last loss {:.2f}; Ari over all ranks: {}'.format(losses[0], losses[-1], ev.global_mean))
         if args.metrics:
             print('mIoU {:.4f}, SC {:.4f}, mSC {:.4f} over all ranks'.format(*[ev.global_means[n] for n in ('mious', 'scs', 'mscs')]))
+        if args.eval_restarts > 1:
+            print('best of {} chains per image: stability {:.4f}, score {:.3f} (chain 0 alone: {:.3f})'.format(
+                args.eval_restarts, ev.stability, ev.best_score, ev.first_score))
         if args.eval_samples:
             print('{}-sample bounds per image: IWAE {:.3f}, Monte-Carlo ELBO {:.3f}'.format(args.eval_samples, ev.iwae, ev.elbo_mc))
 

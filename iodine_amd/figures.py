@@ -4,7 +4,8 @@
 ``pred (*, 3, S, S)`` and the input ``x`` - into one ``uint8 (H, W, 3)`` picture in one launch of ``iodine_render_sheet``: a row per scene
 (or per refinement iteration, or per frame), a panel per entry of ``panels``.  Only the finished picture crosses to the host
 (``encode_png`` / ``write_png``: 8-bit RGB PNG through ``zlib`` and ``struct``).  ``decomposition`` runs a model and draws its figure,
-``trajectory_sheet`` draws the refinement figure of one image from ``model.trajectory``, ``matched_colors`` gives slots and ground-truth
+``trajectory_sheet`` draws the refinement figure of one image from ``model.trajectory``, ``restarts_sheet`` the chains of one image from
+``model.restarts`` with matched colours, ``matched_colors`` gives slots and ground-truth
 masks the same palette entries so that the ``seg`` and ``gt`` panels compare by eye, ``layout`` is the host arithmetic of the panel boxes.
 
 Panels: ``'image'``, ``'pred'``, ``'seg'`` (palette colour of the argmax slot), ``'overlay'`` (the image blended with ``seg``, segment edges
@@ -262,6 +263,27 @@ def trajectory_sheet(trajectory, image=0, x=None, gt=None, **kw):
     if 'panels' not in kw:
         kw['panels'] = (('image',) if x is not None else ()) + ('pred',) + (('gt',) if gt is not None else ()) + ('seg', 'slots')
     return sheet(mask, mean=mean, pred=pred, x=None if x is None else x.to(mask.device), gt=gt, **kw)
+
+
+def restarts_sheet(res, image=0, x=None, **kw):
+    """The multi-stability figure of image ``image`` from ``model.restarts(x, chains=C, keep_decodes=True)``: one row per chain, C rows,
+    with the slot colours following ``res.perm`` - slot i of chain c takes the palette entry of the slot of the best chain it is matched
+    to, so that equal objects have equal colours down the rows.  ``x``: that image ``(3, S, S)``, or the batch ``(B, 3, S, S)``; without it
+    the default panels drop ``'image'``.  The existing ``sheet``, one launch; ``**kw`` goes to it."""
+    if getattr(res, 'decodes', None) is None or getattr(res, 'perm', None) is None:
+        raise ValueError('restarts_sheet: need the result of model.restarts(x, consensus=True, keep_decodes=True)')
+    pred, mask, mean = res.decodes
+    B = int(mask.shape[1])
+    b = int(image)
+    if not 0 <= b < B:
+        raise ValueError(f'restarts_sheet: image must be an index in 0..{B - 1}; got {image!r}')
+    if x is not None and x.dim() == 4:
+        x = x[b]
+    if 'colors' not in kw:
+        kw['colors'] = res.perm[:, b].clamp(0, NONE_COLOR).to(torch.uint8)        # (an unmatched slot, -1, would not occur: K rows, K columns)
+    if 'panels' not in kw:
+        kw['panels'] = (('image',) if x is not None else ()) + ('pred', 'seg', 'slots')
+    return sheet(mask[:, b], mean=mean[:, b], pred=pred[:, b], x=None if x is None else x.to(mask.device), **kw)
 
 
 def quantise(v: torch.Tensor) -> torch.Tensor:

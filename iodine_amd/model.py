@@ -206,6 +206,51 @@ class Predictive:
                  samples=FIRST, ll=CAT1, log_w=CAT1, iwae=CAT0, elbo_mc=CAT0, elbo=CAT0)
 
 
+@dataclasses.dataclass
+class Restarts:
+    """What ``IODINE.restarts`` returns: C refinement chains of the same B images, the best one per image, and how far the chains agree.
+    ``pred (B, 3, S, S)``, ``mask (B, K, 1, S, S)``, ``mean (B, K, 3, S, S)``, ``z``, ``post_mean``, ``post_logvar (B, K, L)`` - those of chain
+    ``best[b]``, rows ``best[b] B + b`` of the one ``reconstruct`` over the batch repeated chain-major; ``best (B)`` int64; ``ll (C, B)``
+    float32 - the (weighted) log-likelihood of each chain's returned decode -, ``kl (C, B)`` float64 - KL(lambda_T || N(0, 1)) -, ``score (C,
+    B)`` float64 = ll - beta kl; ``segmentation (C, B, S, S)`` uint8 - every chain's arg-max map.  With ``consensus=True`` also ``perm (C, B,
+    K)`` int32 - slot i of chain c is slot ``perm[c, b, i]`` of the best chain's labelling (the identity for the best chain itself) -,
+    ``overlap (C, B, K, K)`` int32 - the contingency table of every chain's map against the best chain's -, ``votes (B, K, S, S)`` int32,
+    ``consensus (B, S, S)`` uint8, ``agreement (B, S, S)``, ``mask_mean (B, K, 1, S, S)``, ``match (C, B)`` - the share of pixels on which a
+    chain, relabelled, agrees with the best - and ``stability (B)`` - the mean of ``match`` over the chains other than the best, 1 for one
+    chain; else None.  ``decodes``: with ``keep_decodes=True`` the ``(pred (C, B, 3, S, S), mask (C, B, K, 1, S, S), mean (C, B, K, 3, S, S))``
+    of every chain (views of the one call's outputs, for ``figures.restarts_sheet``), else None.  Detached tensors."""
+    pred: torch.Tensor
+    mask: torch.Tensor
+    mean: torch.Tensor
+    z: torch.Tensor
+    post_mean: torch.Tensor
+    post_logvar: torch.Tensor
+    best: torch.Tensor
+    score: torch.Tensor
+    ll: torch.Tensor
+    kl: torch.Tensor
+    segmentation: torch.Tensor
+    chains: int
+    perm: Optional[torch.Tensor] = None
+    overlap: Optional[torch.Tensor] = None
+    votes: Optional[torch.Tensor] = None
+    consensus: Optional[torch.Tensor] = None
+    agreement: Optional[torch.Tensor] = None
+    mask_mean: Optional[torch.Tensor] = None
+    match: Optional[torch.Tensor] = None
+    stability: Optional[torch.Tensor] = None
+    decodes: Optional[tuple] = None
+
+    def ari(self):
+        """``(C, B)`` float64 on the host: the adjusted Rand index of every chain's map against the best chain's, from ``overlap`` through
+        ``ari.compute_ari`` (1 for the best chain itself).  One copy to the host, made when called."""
+        if self.overlap is None:
+            raise RuntimeError('Restarts.ari: the overlap tables are part of the consensus step - call restarts(..., consensus=True)')
+        from .ari import compute_ari
+        t = self.overlap.cpu().numpy()
+        return torch.tensor([[compute_ari(t[c, b]) for b in range(t.shape[1])] for c in range(t.shape[0])], dtype=torch.float64)
+
+
 def sample_bounds(ll, z, eps, post_mean, post_logvar):
     """The float64 host arithmetic behind ``Predictive``: per-sample log-likelihoods ``ll (S, B)``, the samples ``z`` and their noise ``eps
     (S, B, K, L)`` and the posterior (B, K, L) -> (log_w (S, B), iwae, elbo_mc, elbo (B)).  With z = mu + exp(logvar / 2) eps the
@@ -838,6 +883,89 @@ class IODINE(nn.Module):
         if x is not None:
             out.ll = ll
             out.log_w, out.iwae, out.elbo_mc, out.elbo = sample_bounds(ll, z, eps, pm, plv)
+        return out
+
+    MAX_CHAINS = 1024
+
+    def _check_restarts(self, x, chains, eps, state, trajectory):
+        """The host-only refusals of ``restarts`` -> (C, K, T); every one a ValueError, before any device work."""
+        if isinstance(chains, bool) or not isinstance(chains, numbers.Integral) or not 1 <= chains <= self.MAX_CHAINS:
+            raise ValueError(f'IODINE.restarts: chains must be an integer in 1..{self.MAX_CHAINS}; got {chains!r}')
+        if state is not None or trajectory:
+            raise ValueError('IODINE.restarts: state= and trajectory= are not supported - every chain starts from the initial posterior and '
+                             'only the returned decode of a chain is scored')
+        c, s = self.img_channels, self.img_size
+        if not torch.is_tensor(x) or x.dim() != 4 or tuple(x.shape[1:]) != (c, s, s) or x.shape[0] < 1:
+            clip = ' (a clip is not supported: the final decode of a clip has no frame of its own to be scored against)' if torch.is_tensor(x) and x.dim() == 5 else ''
+            raise ValueError(f'IODINE.restarts: x must be images of shape (B, {c}, {s}, {s}){clip}; got '
+                             f'{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}')
+        K, T = _args.run_shape(self.K, self.n_iters)
+        want = (int(chains), T + 1, int(x.shape[0]), K, self.dim_latent)
+        if eps is not None and (not torch.is_tensor(eps) or tuple(eps.shape) != want):
+            raise ValueError(f'IODINE.restarts: eps must have shape {want} (chains, T + 1, B, K, L); got '
+                             f'{tuple(eps.shape) if torch.is_tensor(eps) else type(eps).__name__}')
+        return int(chains), K, T
+
+    @torch.no_grad()
+    def restarts(self, x, chains=8, eps=None, weights=None, consensus=True, state=None, trajectory=False, keep_decodes=False):
+        """``chains`` refinement chains per image from the same initial posterior with different noise, the best one per image, and how
+        far the chains agree - inference is stochastic and multi-stable, and a single ``reconstruct`` shows one mode.  Returns a ``Restarts``.
+
+        Run: ONE ``reconstruct`` over the batch repeated chain-major (row ``c B + b`` is chain c of image b; above ``max_batch()`` the
+        usual chunks of independent images).  ``eps``: (C, T + 1, B, K, L), or None for one draw of that shape from the model's generator;
+        chain c is the computation ``reconstruct(x, eps[c])`` runs.  ``weights``: the per-pixel observation weights of every chain and of
+        the score, as everywhere else.
+        Score: ``ll[c, b]`` = the (weighted) log-likelihood of the decode the chain RETURNS (``iodine_chain_score``, with ``model.sigma``
+        and ``model.likelihood``; ``elbo_terms`` scores lambda_0 .. lambda_{T-1} only), ``kl[c, b]`` = KL(lambda_T || N(0, 1)) in closed form,
+        ``score = ll - model.beta kl``; ``best[b] = argmax_c score``, the lowest chain on a tie, a NaN never wins, 0 if every score is NaN.
+        Select: ``pred, mask, mean, z, post_mean, post_logvar`` of the best chain per image, gathered on the device without a
+        synchronisation; ``model.posterior.mean / logvar`` are the chosen lambda_T, so ``predictive`` and ``elbo`` continue from the chosen
+        mode; ``model.objects``, ``model.trajectory`` and the refinement state are None afterwards.  Every other per-call attribute
+        (``model.z / mean / mask / mask_logits``, ``elbo_terms``, the likelihood maps, the logger) is that of the underlying C B call.
+        Align and fold (``consensus=True``): the overlap of every chain's arg-max map with the best chain's (``overlap_table``, one launch),
+        ``1 - slot_iou`` into ``matching.assign`` for ``perm``, and ``iodine_chain_consensus`` for votes, consensus, agreement, match and the
+        mean relabelled mask.  ``keep_decodes=True`` also hands back every chain's decode (``Restarts.decodes``; no copy).
+
+        NOT differentiable.  ``state=`` / ``trajectory=`` and a clip ``x`` are refused (ValueError), like every other bad argument, before
+        any device work."""
+        C, K, T = self._check_restarts(x, chains, eps, state, trajectory)
+        sigma, beta, _ = _args.read_objective(self.sigma, self.beta, self.iter_weights, T)
+        xc = _args.check_x(x, self.img_channels, self.img_size)
+        w = _args.check_weights(weights, xc, self.img_size, 'restarts')
+        dev, B, L, S = xc.device, int(xc.shape[0]), self.dim_latent, self.img_size
+        self._bind(dev)                                     # (a CPU tensor is refused here, after the argument checks)
+        from . import chains as _chains
+        if eps is None:                                     # one draw for all chains; a copy: the generator's buffer is the session's
+            eps = self._normals(None, (C, T + 1, B, K, L), dev).clone()
+        eps = eps.detach().to(device=dev, dtype=torch.float32)
+        pred, mask, mean, z = self._reconstruct(xc.repeat(C, 1, 1, 1), eps.permute(1, 0, 2, 3, 4).reshape(T + 1, C * B, K, L),
+                                                weights=None if w is None else w.repeat(C, 1, 1))
+        pm, plv = self.posterior.mean, self.posterior.logvar
+        ll, seg = _chains.chain_score(xc, mask.view(C, B, K, 1, S, S), mean.view(C, B, K, 3, S, S), sigma, weights=w, joint=self._joint())
+        pm64, plv64 = pm.double(), plv.double()             # (C B, K, L): tiny; fp64 keeps exp(lv) - 1 - lv near lv = 0, as _read_objects
+        kl = (0.5 * (plv64.exp() + pm64 * pm64 - 1.0 - plv64).sum((-2, -1))).view(C, B)
+        score = ll.double() - beta * kl
+        key = torch.where(torch.isnan(score), torch.full_like(score, -float('inf')), score)
+        best = ((key == key.max(0).values).cumsum(0) == 0).sum(0)           # the first chain that holds the maximum; 0 if all are NaN
+        rows = best * B + torch.arange(B, device=dev)
+        out = Restarts(*(t.index_select(0, rows) for t in (pred, mask, mean, z, pm, plv)), best, score, ll, kl, seg, C)
+        self.posterior.mean, self.posterior.logvar = out.post_mean, out.post_logvar
+        self.objects, self.trajectory, self._state = None, None, None
+        if keep_decodes:
+            out.decodes = (pred.view(C, B, 3, S, S), mask.view(C, B, K, 1, S, S), mean.view(C, B, K, 3, S, S))
+        if consensus:
+            from .matching import assign
+            from .objects import overlap_table, slot_iou
+            seg_best = seg.view(C * B, S, S).index_select(0, rows)
+            out.overlap = overlap_table(seg, seg_best.unsqueeze(0).expand(C, B, S, S).contiguous(), K, K)
+            perm = assign((1.0 - slot_iou(out.overlap)).float())[0]
+            perm.view(C * B, K)[rows] = torch.arange(K, dtype=torch.int32, device=dev)     # the common labelling IS the best chain's
+            out.perm = perm
+            cons = _chains.chain_consensus(seg, perm, best.to(torch.int32), mask.view(C, B, K, 1, S, S))
+            out.votes, out.consensus, out.agreement, out.match, out.mask_mean = cons
+            m64 = cons.match.double()
+            own = m64.gather(0, best.view(1, B))[0]
+            out.stability = ((m64.sum(0) - own) / (C - 1)).float() if C > 1 else torch.ones(B, dtype=torch.float32, device=dev)
         return out
 
     _STALE = ('IODINE: backward of a stale {0} - the library keeps the saved state of ONE differentiable call and another forward / '
