@@ -77,7 +77,9 @@ typedef struct iodine_handle iodine_handle;
 int iodine_abi_version(void);
 
 /* IODINE(ARCH) -- iodine.py:8-52.  Builds the parameter table and the packed-weight buffers on the
- * current HIP device.  On failure *out is NULL and iodine_last_error(NULL) holds the reason. */
+ * current HIP device.  On failure *out is NULL and iodine_last_error(NULL) holds the reason.
+ * iodine_last_error(NULL) returns the message of the CALLING THREAD's last failed iodine_create or handle-free call (valid until that
+ * thread's next such failure); with a handle, the message of the handle's last failure (a handle is used from one thread at a time). */
 int iodine_create(const iodine_config* cfg, iodine_handle** out);
 void iodine_destroy(iodine_handle* h);
 const char* iodine_last_error(const iodine_handle* h);

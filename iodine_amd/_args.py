@@ -8,6 +8,26 @@ import torch
 from . import _lib
 
 
+def all_tensors(values, message):
+    """ValueError(message) unless every entry of ``values`` is a torch tensor"""
+    if any(not isinstance(t, torch.Tensor) for t in values):
+        raise ValueError(message)
+
+
+def one_device(tensors, message):
+    """RuntimeError(message) unless the tensors share one ROCm device (the stateless kernels have no CPU path)"""
+    if tensors[0].device.type != 'cuda' or any(t.device != tensors[0].device for t in tensors[1:]):
+        raise RuntimeError(message)
+
+
+def lead_count(lead, message):
+    """The product of the leading dimensions ``lead``, ValueError(message) when it is < 1"""
+    n = math.prod(int(d) for d in lead)
+    if n < 1:
+        raise ValueError(message)
+    return n
+
+
 def run_shape(K, T):
     """(K, T) of the call that is starting - ``model.K`` / ``model.n_iters``, read like the reference reads them on every call
     (iodine.py:81-83,123-126,279,312) -, checked on the host before any device work."""

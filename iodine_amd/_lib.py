@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # IODINE_HIP_LIB selects another build of the same library (tools/ab_libs.sh: same-box A/B of two builds)
 LIB_PATH = os.environ.get('IODINE_HIP_LIB') or os.path.join(_HERE, 'libiodine_hip.so')
@@ -166,9 +168,8 @@ def lib() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(f'{LIB_PATH} is missing: build it with `python -m iodine_amd.build` '
                            '(there is no CPU / PyTorch fallback for this path)')
-    # torch must be imported first: its bundled libamdhip64 (same soname) then serves both torch and this
+    # torch is imported first (above): its bundled libamdhip64 (same soname) then serves both torch and this
     # library, so streams and device pointers are shared within ONE HIP runtime instance.
-    import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
     for name, (argtypes, *restype) in _SYMBOLS.items():
         fn = getattr(L, name, None)
@@ -197,6 +198,30 @@ def ptr(t):
         return None
     assert t.is_contiguous(), 'tensor must be contiguous'
     return C.c_void_p(t.data_ptr())
+
+
+def stream():
+    """The current torch stream, as the entry points take it."""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def fn(symbol):
+    """The entry point ``symbol`` of the loaded library (a build loaded through IODINE_HIP_LIB may predate it: that is an error)."""
+    f = getattr(lib(), symbol, None)
+    if f is None:
+        raise RuntimeError(f'IODINE: this build of libiodine_hip.so has no {symbol}')
+    return f
+
+
+def call(symbol, device, *args):
+    """``symbol(stream, *args)``: the one place a handle-free entry point is invoked - on the current stream with ``device`` current;
+    tensors and None go as pointers, everything else (numbers, ``byref``, raw ``c_void_p``) as given.  Raises on a non-zero status.
+    (The entry points that take a handle go through ``Session.call``.)"""
+    f = fn(symbol)
+    args = [ptr(a) if a is None or torch.is_tensor(a) else a for a in args]
+    with torch.cuda.device(device):
+        rc = f(stream(), *args)
+    check(rc, None, symbol)
 
 
 def ptrs(tensors, ctype=C.c_void_p):

@@ -63,14 +63,9 @@ class Session:
         return h
 
     def stream(self):
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _lib.stream()
 
-    @staticmethod
-    def _fn(symbol):
-        fn = getattr(_lib.lib(), symbol, None)      # (a build loaded through IODINE_HIP_LIB may predate the entry point)
-        if fn is None:
-            raise RuntimeError(f'IODINE: this build of libiodine_hip.so has no {symbol}')
-        return fn
+    _fn = staticmethod(_lib.fn)
 
     def _set(self, symbol, *args):
         _lib.check(self._fn(symbol)(self.handle, *args), self.handle, symbol)
@@ -152,14 +147,13 @@ class Session:
         return h
 
     # ---- calls --------------------------------------------------------------------------------------------------------------------
-    def call(self, symbol, *args, handle=True):
-        """``symbol(handle, stream, *args)`` (``handle=False``: without the handle) on the current stream with the session's device
-        current; tensors and None go as pointers, everything else as given.  With option ``graph`` the call goes to a private non-default
-        stream (the legacy null stream cannot be captured), ordered after / before the caller's.  Raises on a non-zero status."""
+    def call(self, symbol, *args):
+        """``symbol(handle, stream, *args)`` on the current stream with the session's device current; tensors and None go as pointers,
+        everything else as given.  With option ``graph`` the call goes to a private non-default stream (the legacy null stream cannot be
+        captured), ordered after / before the caller's.  Raises on a non-zero status.  (Handle-free entry points: ``_lib.call``.)"""
         fn = self._fn(symbol)
         args = [_lib.ptr(a) if torch.is_tensor(a) else a for a in args]
-        head = (self.handle,) if handle else ()
-        run = lambda: _lib.check(fn(*head, self.stream(), *args), self.handle if handle else None, symbol)
+        run = lambda: _lib.check(fn(self.handle, self.stream(), *args), self.handle, symbol)
         with torch.cuda.device(self.device):
             if not self.graph_on():
                 return run()

@@ -7,8 +7,6 @@ masks are binarised by argmax over K, the (N_gt x K) table of pixel co-occurrenc
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -46,10 +44,7 @@ def ari_tables(mask: torch.Tensor, gt_masks) -> np.ndarray:
         gt = gt.to(mask.device)
     table = torch.empty((B, G, K), dtype=torch.int32, device=mask.device)
     mk = mask.detach().to(torch.float32).contiguous()
-    with torch.cuda.device(mask.device):
-        rc = _lib.lib().iodine_ari_table(C.c_void_p(torch.cuda.current_stream().cuda_stream), _lib.ptr(mk), _lib.ptr(gt),
-                                         B, K, G, S * S, _lib.ptr(table))
-    _lib.check(rc, None, 'iodine_ari_table')
+    _lib.call('iodine_ari_table', mask.device, mk, gt, B, K, G, S * S, table)
     return table.cpu().numpy()
 
 

@@ -12,19 +12,14 @@ like ``objects.slot_table`` there is no CPU path.  tests/restarts_reference.py i
 from __future__ import annotations
 
 import collections
-import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .objects import MAX_SIZE, MAX_SLOTS
 
 MAX_CHAINS = 1024
 Consensus = collections.namedtuple('Consensus', 'votes consensus agreement match mask_mean')
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def chain_score(x, mask, mean, sigma, weights=None, joint=False, ll=True, segmentation=True):
@@ -34,8 +29,7 @@ def chain_score(x, mask, mean, sigma, weights=None, joint=False, ll=True, segmen
     log-density of ``x_c`` around ``mean_kc`` at scale ``sigma``; ``seg = argmax_k mask`` with the lowest index on a tie (the map of
     ``slot_table``).  Bitwise reproducible."""
     tensors = (x, mask, mean) + ((weights,) if weights is not None else ())
-    if any(not isinstance(t, torch.Tensor) for t in tensors):
-        raise ValueError('chain_score: x, mask, mean (and weights) must be torch tensors')
+    _args.all_tensors(tensors, 'chain_score: x, mask, mean (and weights) must be torch tensors')
     if mask.dim() != 6 or mask.shape[3] != 1 or mask.shape[4] != mask.shape[5]:
         raise ValueError(f'chain_score: mask must be (C, B, K, 1, S, S), got {tuple(mask.shape)}')
     Cn, B, K, S = (int(mask.shape[i]) for i in (0, 1, 2, 5))
@@ -52,17 +46,13 @@ def chain_score(x, mask, mean, sigma, weights=None, joint=False, ll=True, segmen
     sigma = float(sigma)
     if not sigma > 0.0:
         raise ValueError(f'chain_score: sigma must be > 0; got {sigma!r}')
-    if mask.device.type != 'cuda' or any(t.device != mask.device for t in tensors):
-        raise RuntimeError('chain_score needs x, mask, mean (and weights) on one ROCm device (no CPU fallback)')
+    _args.one_device((mask,) + tensors, 'chain_score needs x, mask, mean (and weights) on one ROCm device (no CPU fallback)')
     dev = mask.device
     xs, mk, mn = (t.detach().to(torch.float32).contiguous() for t in (x, mask, mean))
     w = None if weights is None else weights.detach().to(torch.float32).contiguous()
     out_ll = torch.empty((Cn, B), dtype=torch.float32, device=dev) if ll else None
     seg = torch.empty((Cn, B, S, S), dtype=torch.uint8, device=dev) if segmentation else None
-    with torch.cuda.device(dev):
-        rc = _lib.lib().iodine_chain_score(_stream(), _lib.ptr(xs), _lib.ptr(w), _lib.ptr(mk), _lib.ptr(mn), Cn, B, K, S, sigma,
-                                           int(bool(joint)), _lib.ptr(out_ll), _lib.ptr(seg))
-    _lib.check(rc, None, 'iodine_chain_score')
+    _lib.call('iodine_chain_score', dev, xs, w, mk, mn, Cn, B, K, S, sigma, int(bool(joint)), out_ll, seg)
     return out_ll, seg
 
 
@@ -74,8 +64,7 @@ def chain_consensus(seg, perm, ref=None, mask=None):
     t_c = t_ref[b], ``mask_mean[b, j]`` the mean over the chains of the soft mask each maps to j.  A label >= K or a perm / ref entry outside
     its range leaves that pixel (chain) out of every count: the votes then sum to less than C."""
     given = (seg, perm) + tuple(t for t in (ref, mask) if t is not None)
-    if any(not isinstance(t, torch.Tensor) for t in given):
-        raise ValueError('chain_consensus: seg, perm (and ref, mask) must be torch tensors')
+    _args.all_tensors(given, 'chain_consensus: seg, perm (and ref, mask) must be torch tensors')
     if seg.dim() != 4 or seg.dtype != torch.uint8 or seg.shape[2] != seg.shape[3]:
         raise ValueError(f'chain_consensus: seg must be uint8 (C, B, S, S), got {seg.dtype} {tuple(seg.shape)}')
     Cn, B, S = int(seg.shape[0]), int(seg.shape[1]), int(seg.shape[3])
@@ -89,8 +78,7 @@ def chain_consensus(seg, perm, ref=None, mask=None):
         raise ValueError(f'chain_consensus: ref must be int32 ({B},), got {ref.dtype} {tuple(ref.shape)}')
     if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (Cn, B, K, 1, S, S)):
         raise ValueError(f'chain_consensus: mask must be float32 {(Cn, B, K, 1, S, S)}, got {mask.dtype} {tuple(mask.shape)}')
-    if seg.device.type != 'cuda' or any(t.device != seg.device for t in given):
-        raise RuntimeError('chain_consensus needs seg, perm (and ref, mask) on one ROCm device (no CPU fallback)')
+    _args.one_device(given, 'chain_consensus needs seg, perm (and ref, mask) on one ROCm device (no CPU fallback)')
     dev = seg.device
     sg, pr = seg.contiguous(), perm.contiguous()
     rf = None if ref is None else ref.contiguous()
@@ -100,8 +88,5 @@ def chain_consensus(seg, perm, ref=None, mask=None):
     agree = torch.empty((B, S, S), dtype=torch.float32, device=dev)
     match = torch.empty((Cn, B), dtype=torch.float32, device=dev) if rf is not None else None
     mmean = torch.empty((B, K, 1, S, S), dtype=torch.float32, device=dev) if mk is not None else None
-    with torch.cuda.device(dev):
-        rc = _lib.lib().iodine_chain_consensus(_stream(), _lib.ptr(sg), _lib.ptr(pr), _lib.ptr(rf), _lib.ptr(mk), Cn, B, K, S, _lib.ptr(votes),
-                                               _lib.ptr(cons), _lib.ptr(agree), _lib.ptr(match), _lib.ptr(mmean))
-    _lib.check(rc, None, 'iodine_chain_consensus')
+    _lib.call('iodine_chain_consensus', dev, sg, pr, rf, mk, Cn, B, K, S, votes, cons, agree, match, mmean)
     return Consensus(votes, cons, agree, match, mmean)

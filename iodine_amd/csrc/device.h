@@ -1,5 +1,6 @@
-// Device-side helpers shared by every kernel file of libiodine_hip.so (gfx950 only): vector types, ELU / sigmoid, the wave
-// maximum, the split-fp16 scale and split helpers, the compile-time loop, the raw-buffer descriptor and the phase-timing
+// Device-side helpers shared by every kernel file of libiodine_hip.so (gfx950 only): vector types, ELU / sigmoid, the one- or
+// four-float load (vec_load), the butterfly wave sum / minimum / maximum of the stateless kernels (wave_sum, wave_min, wave_max), the
+// DPP wave maximum, the split-fp16 scale and split helpers, the compile-time loop, the raw-buffer descriptor and the phase-timing
 // macros.  A helper that two kernel files need lives here, once; common.h (host side: launchers, geometry) includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -45,6 +46,45 @@ IOD_DEVINL float elu1_fast(float v) { return v > 0.f ? v : __expf(v) - 1.f; }
 // derivative of ELU expressed through its OUTPUT a = ELU(x): a > 0 ? 1 : a + 1
 IOD_DEVINL float elu1_grad_from_out(float a) { return a > 0.f ? 1.f : a + 1.f; }
 IOD_DEVINL float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
+
+// v[0..W-1] = p[0..W-1]: one 16-byte load for W = 4 (p 16-byte aligned: the launcher decides), one float for W = 1
+template <int W> IOD_DEVINL void vec_load(const float* __restrict__ p, float (&v)[W])
+{
+    if constexpr (W == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+        v[0] = *p;
+    }
+}
+
+// Sum / minimum / maximum over the 64 lanes of a wave in a fixed xor butterfly, valid in every lane: the form of the stateless kernels
+// (objects, chains, match), whose fp64 sums are reproducible to the bit because the order is fixed.  Off the hot path, where the DPP
+// form of wave_max_f32 below is used.
+IOD_DEVINL double wave_sum(double v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+IOD_DEVINL unsigned wave_sum(unsigned v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (unsigned)__shfl_xor((int)v, d, 64);
+    return v;
+}
+IOD_DEVINL int wave_min(int v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
+    return v;
+}
+IOD_DEVINL int wave_max(int v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
 
 // max over the 64 lanes of a wave, returned to every lane.  DPP steps inside the 16-lane rows, row broadcasts across
 // them and one v_readlane - about a dozen VALU instructions; the __shfl_xor butterfly it replaces is six dependent

@@ -3,7 +3,8 @@
 // logger scalars, debug copy and profile read.  See include/iodine_hip.h for the ABI and the reference call sites each entry point replaces.
 // The rest of the host layer: iodine_dispatch.cpp - path selectors and launch sequences; iodine_plan.cpp - parameter table, workspace plan,
 // graph key; iodine_checks.cpp - the host-only refusals; iodine_params.cpp - create / destroy / set_params; iodine_train.cpp - the training
-// forward and backward; iodine_pad.cpp - handles at a padded width; iodine_ops.cpp - the entry points that take no handle.
+// forward and backward; iodine_pad.cpp - handles at a padded width; iodine_ops.cpp - the product entry points that
+// take no handle; iodine_testops.cpp - the kernel-test entries (iodine_op_*); iodine_sheet.cpp - decomposition sheets.
 #include "iodine_internal.h"
 
 extern "C" {

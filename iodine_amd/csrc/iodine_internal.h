@@ -11,12 +11,20 @@
 #include <cstring>
 #include <list>
 #include <string>
+#include <utility>
 #include <vector>
 
 // (hidden: nothing declared here is part of the library's dynamic symbol table)
 #pragma GCC visibility push(hidden)
 
-extern std::string g_create_error;          // message of a failed iodine_create / handle-free entry point (iodine_last_error(NULL))
+// Message of the calling thread's last failed iodine_create / handle-free entry point (iodine_last_error(NULL)).  One slot per thread -
+// these entry points hold no handle, so two threads may be refused at once - and one writer: every refusal below goes through free_fail.
+extern thread_local std::string g_create_error;
+inline int free_fail(int rc, std::string msg) { g_create_error = std::move(msg); return rc; }
+inline int free_hip(const char* who, hipError_t e)          // the end of a handle-free launch: "who: <HIP's text>" unless it succeeded
+{
+    return e == hipSuccess ? IODINE_OK : free_fail(IODINE_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+}
 
 struct ParamInfo {
     std::string name;

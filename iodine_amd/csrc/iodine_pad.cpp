@@ -164,11 +164,10 @@ int pad_create(iodine_handle* h)
     iodine_config pc = h->cfg;
     pc.dim_latent = sh->Lp; pc.ref_mlp_units = sh->Hp;
     const int rc = iodine_create(&pc, &sh->inner);
-    if (rc) return rc;                                                  // (g_create_error holds the inner message)
+    if (rc) return rc;                                                  // (the thread's error slot holds the inner message)
     sh->inner->Lreal = sh->L;
     const int rb = shim_build(h);
-    if (rb) g_create_error = h->err;
-    return rb;
+    return rb ? free_fail(rb, h->err) : IODINE_OK;
 }
 
 void pad_destroy(iodine_handle* h)

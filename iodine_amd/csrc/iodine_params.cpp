@@ -2,7 +2,7 @@
 // parameter table's readers and iodine_set_params, which refreshes the packs the selected kernels read (iodine_dispatch.cpp).
 #include "iodine_internal.h"
 
-std::string g_create_error;
+thread_local std::string g_create_error;
 
 namespace {
 
@@ -342,9 +342,9 @@ extern "C" {
 int iodine_create(const iodine_config* cfg, iodine_handle** out)
 {
     if (out) *out = nullptr;
-    if (!cfg || !out) { g_create_error = "null argument"; return IODINE_ERR_INVALID; }
+    if (!cfg || !out) return free_fail(IODINE_ERR_INVALID, "null argument");
     const std::string why = validate(*cfg);
-    if (!why.empty()) { g_create_error = why; return IODINE_ERR_INVALID; }
+    if (!why.empty()) return free_fail(IODINE_ERR_INVALID, why);
     iodine_handle* h = new iodine_handle();
     h->cfg = *cfg;
     h->obj.sigma = cfg->sigma;
@@ -383,9 +383,8 @@ int iodine_create(const iodine_config* cfg, iodine_handle** out)
     build_param_table(h);
 
     auto bail = [&](hipError_t e, const char* what) {
-        g_create_error = std::string(what) + ": " + hipGetErrorString(e);
         iodine_destroy(h);
-        return IODINE_ERR_HIP;
+        return free_hip(what, e);
     };
     DevAlloc da{h, "lin, elbo_counter"};
     h->lin = da.floats((size_t)h->S);

@@ -61,7 +61,7 @@ extern "C" {
 int iodine_sheet_size(const iodine_sheet_spec* spec, int* height, int* width)
 {
     std::string why = !height || !width ? "height or width is NULL" : sheet_spec_error(spec);
-    if (!why.empty()) { g_create_error = "iodine_sheet_size: " + why; return IODINE_ERR_INVALID; }
+    if (!why.empty()) return free_fail(IODINE_ERR_INVALID, "iodine_sheet_size: " + why);
     long long H, W;
     sheet_dims(*spec, H, W);
     *height = (int)H;
@@ -73,7 +73,7 @@ int iodine_sheet_form(const iodine_sheet_spec* spec, const float* x, const float
                       const unsigned char* gt, const unsigned char* sheet)
 {
     const std::string why = sheet_call_error(spec, x, pred, mask, mean, gt, sheet);
-    if (!why.empty()) { g_create_error = "iodine_sheet_form: " + why; return -1; }
+    if (!why.empty()) return free_fail(-1, "iodine_sheet_form: " + why);
     long long H, W;
     sheet_dims(*spec, H, W);
     return sheet_form(*spec, x, pred, mask, mean, gt, sheet, (int)W);
@@ -84,12 +84,10 @@ int iodine_render_sheet(void* stream, const iodine_sheet_spec* spec, const float
                         unsigned char* sheet)
 {
     const std::string why = sheet_call_error(spec, x, pred, mask, mean, gt, sheet);
-    if (!why.empty()) { g_create_error = "iodine_render_sheet: " + why; return IODINE_ERR_INVALID; }
+    if (!why.empty()) return free_fail(IODINE_ERR_INVALID, "iodine_render_sheet: " + why);
     long long H, W;
     sheet_dims(*spec, H, W);
-    const hipError_t e = launch_render_sheet((hipStream_t)stream, *spec, x, pred, mask, mean, gt, slot_color, gt_color, sheet, (int)W);
-    if (e != hipSuccess) { g_create_error = std::string("iodine_render_sheet: ") + hipGetErrorString(e); return IODINE_ERR_HIP; }
-    return IODINE_OK;
+    return free_hip("iodine_render_sheet", launch_render_sheet((hipStream_t)stream, *spec, x, pred, mask, mean, gt, slot_color, gt_color, sheet, (int)W));
 }
 
 }  // extern "C"

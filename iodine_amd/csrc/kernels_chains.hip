@@ -29,29 +29,6 @@ static constexpr int CHN_TARGET_BLOCKS = 256;                 // one block of 16
 static constexpr int CNS_THREADS = 256;
 static constexpr int CNS_MAX_SLOTS = 16;
 
-template <int W> IOD_DEVINL void chn_load(const float* __restrict__ p, float (&v)[W])
-{
-    if constexpr (W == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
-IOD_DEVINL double chn_wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-IOD_DEVINL unsigned chn_wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (unsigned)__shfl_xor((int)v, d, 64);
-    return v;
-}
-
 // one term of a running logsumexp: (mx, s) stand for mx + log s; every exponent is <= 0.  From (-inf, 0) the first term gives (a, 1).
 IOD_DEVINL void chn_lse_step(float a, float& mx, float& s)
 {
@@ -89,8 +66,8 @@ void chain_score_kernel(const float* __restrict__ x, const float* __restrict__ w
             float xs[3][W], wt[W];
             if (ll) {
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) chn_load<W>(xb + ch * sP + p0, xs[ch]);
-                if (wb) chn_load<W>(wb + p0, wt);
+                for (int ch = 0; ch < 3; ++ch) vec_load<W>(xb + ch * sP + p0, xs[ch]);
+                if (wb) vec_load<W>(wb + p0, wt);
             }
             float mx[NS][W], sm[NS][W], bv[W];
             int best[W];
@@ -103,14 +80,14 @@ void chain_score_kernel(const float* __restrict__ x, const float* __restrict__ w
 #pragma unroll 2
             for (int k = 0; k < K; ++k) {
                 float m[W];
-                chn_load<W>(mb + (size_t)k * sP + p0, m);
+                vec_load<W>(mb + (size_t)k * sP + p0, m);
 #pragma unroll
                 for (int j = 0; j < W; ++j)
                     if (m[j] > bv[j]) { bv[j] = m[j]; best[j] = k; }
                 if (!ll) continue;
                 float mu[3][W];
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) chn_load<W>(ub + ((size_t)k * 3 + ch) * sP + p0, mu[ch]);
+                for (int ch = 0; ch < 3; ++ch) vec_load<W>(ub + ((size_t)k * 3 + ch) * sP + p0, mu[ch]);
 #pragma unroll
                 for (int j = 0; j < W; ++j) {
                     const float lm = logf(m[j] + 1e-12f);
@@ -145,7 +122,7 @@ void chain_score_kernel(const float* __restrict__ x, const float* __restrict__ w
             }
         }
         if (!ll) continue;                                    // (block-uniform: no barrier is skipped by a part of the block)
-        acc = chn_wave_sum(acc);
+        acc = wave_sum(acc);
         const int set = (c - c0) & 1;
         if ((tid & 63) == 0) s_red[set][tid >> 6] = acc;
         __syncthreads();
@@ -283,7 +260,7 @@ void chain_votes_kernel(const unsigned char* __restrict__ seg, const int* __rest
                     const int i = __ffs((int)bits) - 1;                         // < K by construction
                     bits &= bits - 1;
                     float m[W];
-                    chn_load<W>(mask + (((size_t)c * B + b) * K + i) * sP + p0, m);
+                    vec_load<W>(mask + (((size_t)c * B + b) * K + i) * sP + p0, m);
 #pragma unroll
                     for (int n = 0; n < W; ++n) acc[n] += m[n];
                 }
@@ -337,7 +314,7 @@ void chain_match_kernel(const unsigned char* __restrict__ seg, const int* __rest
             n += (ta < (unsigned)K && ta == tr) ? 1u : 0u;
         }
     }
-    n = chn_wave_sum(n);
+    n = wave_sum(n);
     if ((tid & 63) == 0) s_cnt[tid >> 6] = n;
     __syncthreads();
     if (tid != 0) return;

@@ -22,19 +22,6 @@ static constexpr int MT_WAVES = MT_THREADS / 64;
 static constexpr int MT_MAX = IOD_ASSIGN_MAX;               // slots and gt rows per image
 static constexpr int MT_BWD_THREADS = 256;
 
-IOD_DEVINL double mt_wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-IOD_DEVINL unsigned mt_wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (unsigned)__shfl_xor((int)v, d, 64);
-    return v;
-}
-
 // W = 4: P % 4 == 0, mask 16-byte and gt 4-byte aligned (launch_mask_overlap decides); W = 1: anything.
 template <int W>
 __global__ __launch_bounds__(MT_THREADS)
@@ -94,13 +81,13 @@ void mask_overlap_kernel(const float* __restrict__ mask, const unsigned char* __
 
     // wave step: fixed butterflies; block step: one thread per column, waves in index order
     const int wv = tid >> 6;
-    a_area = mt_wave_sum(a_area);
+    a_area = wave_sum(a_area);
 #pragma unroll
     for (int g = 0; g < MT_MAX; ++g) {
         if (g < G) {
-            a_i[g] = mt_wave_sum(a_i[g]);
-            a_n[g] = mt_wave_sum(a_n[g]);
-            cnt[g] = mt_wave_sum(cnt[g]);
+            a_i[g] = wave_sum(a_i[g]);
+            a_n[g] = wave_sum(a_n[g]);
+            cnt[g] = wave_sum(cnt[g]);
             if ((tid & 63) == 0) { s_d[wv][g] = a_i[g]; s_d[wv][MT_MAX + g] = a_n[g]; s_n[wv][g] = cnt[g]; }
         }
     }

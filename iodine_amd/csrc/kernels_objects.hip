@@ -16,46 +16,11 @@ static constexpr int OBJ_THREADS = 1024;
 static constexpr int OBJ_WAVES = OBJ_THREADS / 64;
 static constexpr int OBJ_COLS = 14;
 
-template <int W> IOD_DEVINL void obj_load(const float* __restrict__ p, float (&v)[W])
-{
-    if constexpr (W == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
 // fixed tree over the W terms of one vector
 template <int W> IOD_DEVINL float obj_tree(const float (&v)[W])
 {
     if constexpr (W == 4) return (v[0] + v[1]) + (v[2] + v[3]);
     else return v[0];
-}
-
-IOD_DEVINL double obj_wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-IOD_DEVINL unsigned obj_wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (unsigned)__shfl_xor((int)v, d, 64);
-    return v;
-}
-IOD_DEVINL int obj_wave_min(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    return v;
-}
-IOD_DEVINL int obj_wave_max(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
 }
 
 // W = 4: P % 4 == 0, S >= 4 and every base pointer aligned for its vector (launch_slot_table decides); W = 1: anything.
@@ -99,7 +64,7 @@ void slot_table_kernel(const float* __restrict__ mask, const float* __restrict__
 #pragma unroll 4
         for (int kk = 0; kk < K; ++kk) {
             float m[W];
-            obj_load<W>(mb + (size_t)kk * P + p0, m);
+            vec_load<W>(mb + (size_t)kk * P + p0, m);
 #pragma unroll
             for (int j = 0; j < W; ++j) {
                 if (m[j] > bv[j]) { bv[j] = m[j]; best[j] = kk; }
@@ -123,9 +88,9 @@ void slot_table_kernel(const float* __restrict__ mask, const float* __restrict__
         a_cy += (double)obj_tree<W>(ty);
         if (cb) {
             float c0[W], c1[W], c2[W];
-            obj_load<W>(cb + p0, c0);
-            obj_load<W>(cb + (size_t)P + p0, c1);
-            obj_load<W>(cb + 2 * (size_t)P + p0, c2);
+            vec_load<W>(cb + p0, c0);
+            vec_load<W>(cb + (size_t)P + p0, c1);
+            vec_load<W>(cb + 2 * (size_t)P + p0, c2);
 #pragma unroll
             for (int j = 0; j < W; ++j) { c0[j] *= mk[j]; c1[j] *= mk[j]; c2[j] *= mk[j]; }
             a_r += (double)obj_tree<W>(c0);
@@ -144,10 +109,10 @@ void slot_table_kernel(const float* __restrict__ mask, const float* __restrict__
     }
 
     // wave step: fixed butterflies; block step: thread 0, waves in index order
-    a_area = obj_wave_sum(a_area); a_cx = obj_wave_sum(a_cx); a_cy = obj_wave_sum(a_cy);
-    a_r = obj_wave_sum(a_r); a_g = obj_wave_sum(a_g); a_b = obj_wave_sum(a_b);
-    cnt = obj_wave_sum(cnt); sc = obj_wave_sum(sc); sr = obj_wave_sum(sr);
-    x0 = obj_wave_min(x0); y0 = obj_wave_min(y0); x1 = obj_wave_max(x1); y1 = obj_wave_max(y1);
+    a_area = wave_sum(a_area); a_cx = wave_sum(a_cx); a_cy = wave_sum(a_cy);
+    a_r = wave_sum(a_r); a_g = wave_sum(a_g); a_b = wave_sum(a_b);
+    cnt = wave_sum(cnt); sc = wave_sum(sc); sr = wave_sum(sr);
+    x0 = wave_min(x0); y0 = wave_min(y0); x1 = wave_max(x1); y1 = wave_max(y1);
     peak = wave_max_f32(peak);
     const int wv = tid >> 6;
     if ((tid & 63) == 0) {

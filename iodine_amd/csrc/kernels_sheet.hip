@@ -32,16 +32,6 @@ struct sheet_inputs {
     const unsigned char* gt_color;
 };
 
-template <int L> IOD_DEVINL void sht_load(const float* __restrict__ p, float (&v)[L])
-{
-    if constexpr (L == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
 // clamp to [0, 1] with a NaN going to 0, then round half up
 IOD_DEVINL unsigned sht_quant(float v)
 {
@@ -105,7 +95,7 @@ void sheet_kernel(const iodine_sheet_spec sp, const sheet_inputs in, unsigned ch
 #pragma unroll 4
             for (int kk = 0; kk < K; ++kk) {
                 float m[L];
-                sht_load<L>(mb + (size_t)kk * P + v * L, m);
+                vec_load<L>(mb + (size_t)kk * P + v * L, m);
 #pragma unroll
                 for (int j = 0; j < L; ++j)
                     if (m[j] > bv[j]) { bv[j] = m[j]; best[j] = kk; }
@@ -130,9 +120,9 @@ void sheet_kernel(const iodine_sheet_spec sp, const sheet_inputs in, unsigned ch
                              : kind == IODINE_SHEET_PRED ? in.pred + (size_t)r * 3 * P
                                                          : in.mean + ((size_t)r * K + slot) * 3 * P;
             float c0[L], c1[L], c2[L];
-            sht_load<L>(src + p0 + q0, c0);
-            sht_load<L>(src + (size_t)P + p0 + q0, c1);
-            sht_load<L>(src + 2 * (size_t)P + p0 + q0, c2);
+            vec_load<L>(src + p0 + q0, c0);
+            vec_load<L>(src + (size_t)P + p0 + q0, c1);
+            vec_load<L>(src + 2 * (size_t)P + p0 + q0, c2);
 #pragma unroll
             for (int j = 0; j < L; ++j) out[j] = sht_pack(sht_quant(c0[j]), sht_quant(c1[j]), sht_quant(c2[j]));
             break;
@@ -149,9 +139,9 @@ void sheet_kernel(const iodine_sheet_spec sp, const sheet_inputs in, unsigned ch
         case IODINE_SHEET_OVERLAY: {
             const float* src = in.x + (size_t)r * 3 * P;
             float c0[L], c1[L], c2[L];
-            sht_load<L>(src + p0 + q0, c0);
-            sht_load<L>(src + (size_t)P + p0 + q0, c1);
-            sht_load<L>(src + 2 * (size_t)P + p0 + q0, c2);
+            vec_load<L>(src + p0 + q0, c0);
+            vec_load<L>(src + (size_t)P + p0 + q0, c1);
+            vec_load<L>(src + 2 * (size_t)P + p0 + q0, c2);
 #pragma unroll
             for (int j = 0; j < L; ++j) {
                 const int q = q0 + j;
@@ -198,8 +188,8 @@ void sheet_kernel(const iodine_sheet_spec sp, const sheet_inputs in, unsigned ch
             const float* xs = in.x + (size_t)r * 3 * P + p0 + q0;
             const float* ps = in.pred + (size_t)r * 3 * P + p0 + q0;
             float a0[L], a1[L], a2[L], b0[L], b1[L], b2[L];
-            sht_load<L>(xs, a0); sht_load<L>(xs + (size_t)P, a1); sht_load<L>(xs + 2 * (size_t)P, a2);
-            sht_load<L>(ps, b0); sht_load<L>(ps + (size_t)P, b1); sht_load<L>(ps + 2 * (size_t)P, b2);
+            vec_load<L>(xs, a0); vec_load<L>(xs + (size_t)P, a1); vec_load<L>(xs + 2 * (size_t)P, a2);
+            vec_load<L>(ps, b0); vec_load<L>(ps + (size_t)P, b1); vec_load<L>(ps + 2 * (size_t)P, b2);
 #pragma unroll
             for (int j = 0; j < L; ++j) {
                 const float s = __fadd_rn(__fadd_rn(fabsf(__fsub_rn(a0[j], b0[j])), fabsf(__fsub_rn(a1[j], b1[j]))),
@@ -212,8 +202,8 @@ void sheet_kernel(const iodine_sheet_spec sp, const sheet_inputs in, unsigned ch
         case IODINE_SHEET_SLOT_MASKED: {
             const float* mu = in.mean + ((size_t)r * K + slot) * 3 * P + p0 + q0;
             float m[L], c0[L], c1[L], c2[L];
-            sht_load<L>(in.mask + ((size_t)r * K + slot) * P + p0 + q0, m);
-            sht_load<L>(mu, c0); sht_load<L>(mu + (size_t)P, c1); sht_load<L>(mu + 2 * (size_t)P, c2);
+            vec_load<L>(in.mask + ((size_t)r * K + slot) * P + p0 + q0, m);
+            vec_load<L>(mu, c0); vec_load<L>(mu + (size_t)P, c1); vec_load<L>(mu + 2 * (size_t)P, c2);
 #pragma unroll
             for (int j = 0; j < L; ++j) {
                 const float om = __fsub_rn(1.f, m[j]);
@@ -225,7 +215,7 @@ void sheet_kernel(const iodine_sheet_spec sp, const sheet_inputs in, unsigned ch
         }
         default: {                                            // IODINE_SHEET_SLOT_MASK (the entry point refuses unknown kinds)
             float m[L];
-            sht_load<L>(in.mask + ((size_t)r * K + slot) * P + p0 + q0, m);
+            vec_load<L>(in.mask + ((size_t)r * K + slot) * P + p0 + q0, m);
 #pragma unroll
             for (int j = 0; j < L; ++j) { const unsigned g = sht_quant(m[j]); out[j] = sht_pack(g, g, g); }
             break;

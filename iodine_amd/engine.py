@@ -517,10 +517,7 @@ def save_sheet(model, data, path, device, images=8, scale=1, trajectory=None, dr
         x = x[:, 0]
     n = 1 if trajectory is not None else max(1, min(int(images), int(x.shape[0])))
     eps = torch.empty((model.n_iters + 1, n, model.K, model.dim_latent), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        rc = _lib.lib().iodine_randn(torch.cuda.current_stream().cuda_stream, _lib.ptr(eps), eps.numel(), model._seed,
-                                     (SHEET_STREAM + int(draw)) & (2 ** 64 - 1))
-    _lib.check(rc, None, 'iodine_randn')
+    _lib.call('iodine_randn', device, eps, eps.numel(), model._seed, (SHEET_STREAM + int(draw)) & (2 ** 64 - 1))
     gt = data[1] if _has_masks(data) and x.dim() == 4 and data[0].dim() == 4 else None
     model.eval()
     out = figures.decomposition(model, x, gt=gt, n=n, trajectory=trajectory, eps=eps, scale=scale)

@@ -38,10 +38,6 @@ MAX_PANELS = 64
 FORM_VECTOR_LOADS, FORM_WORD_STORES = 1, 2                   # bits of ``sheet_form``
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def expand_panels(panels, K: int, slot_mode: str = 'masked'):
     """The panel list as ``[(kind name, slot)]``: ``'slots'`` becomes K panels of ``slot_mode``, a bare name gets slot 0."""
     if slot_mode not in SLOT_MODES:
@@ -166,9 +162,7 @@ def sheet(mask, mean=None, pred=None, x=None, gt=None, panels=('image', 'pred', 
 
 def render_into(out, sp, tensors):
     """One launch of ``iodine_render_sheet`` into ``out`` (uint8, H W 3 bytes, contiguous) for a prepared spec; returns ``out``."""
-    with torch.cuda.device(out.device):
-        rc = _lib.lib().iodine_render_sheet(_stream(), C.byref(sp), *[_lib.ptr(t) for t in tensors], _lib.ptr(out))
-    _lib.check(rc, None, 'iodine_render_sheet')
+    _lib.call('iodine_render_sheet', out.device, C.byref(sp), *tensors, out)
     return out
 
 

@@ -19,12 +19,11 @@ the other stateless kernels there is no CPU path."""
 from __future__ import annotations
 
 import collections
-import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .ari import compute_ari
 from .objects import MAX_SIZE, MAX_SLOTS, SLOT_COLUMNS, slot_table
 
@@ -32,10 +31,6 @@ KINDS = {'iou': 0, 'ce': 1}
 Overlap = collections.namedtuple('Overlap', 'inter nll mask_area gt_area')
 Match = collections.namedtuple('Match', 'assign cost iou stats')
 Scores = collections.namedtuple('Scores', 'miou sc msc')
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _kind(name, what):
@@ -53,10 +48,8 @@ def _eps(eps, who):
 
 def _check_pair(mask, gt, who):
     """(lead, B, K, G, S) of ``mask (*, K, 1, S, S)`` float32 and ``gt (*, G, S, S)`` uint8 on one ROCm device"""
-    if not isinstance(mask, torch.Tensor) or not isinstance(gt, torch.Tensor):
-        raise ValueError(f'{who}: mask and gt must be torch tensors (pack_gt packs the loader\'s tuple)')
-    if mask.device.type != 'cuda' or gt.device != mask.device:
-        raise RuntimeError(f'{who} needs mask and gt on one ROCm device (no CPU fallback)')
+    _args.all_tensors((mask, gt), f'{who}: mask and gt must be torch tensors (pack_gt packs the loader\'s tuple)')
+    _args.one_device((mask, gt), f'{who} needs mask and gt on one ROCm device (no CPU fallback)')
     if mask.dim() < 5 or mask.shape[-3] != 1 or mask.shape[-1] != mask.shape[-2]:
         raise ValueError(f'{who}: mask must be (*, K, 1, S, S) with at least one leading dimension, got {tuple(mask.shape)}')
     if mask.dtype != torch.float32:
@@ -69,12 +62,7 @@ def _check_pair(mask, gt, who):
     G = int(gt.shape[-3])
     if not 1 <= K <= MAX_SLOTS or not 1 <= G <= MAX_SLOTS or not 1 <= S <= MAX_SIZE:
         raise ValueError(f'{who}: K and G must be in 1..{MAX_SLOTS} and S in 1..{MAX_SIZE}, got K = {K}, G = {G}, S = {S}')
-    B = 1
-    for d in lead:
-        B *= int(d)
-    if B < 1:
-        raise ValueError(f'{who}: empty leading dimensions {lead}')
-    return lead, B, K, G, S
+    return lead, _args.lead_count(lead, f'{who}: empty leading dimensions {lead}'), K, G, S
 
 
 def pack_gt(gt_masks, size=None, device=None):
@@ -118,10 +106,7 @@ def _overlap(mk, g8, B, K, G, S, eps, nll):
     nl = torch.empty((B, G, K), dtype=torch.float32, device=dev) if nll else None
     area = torch.empty((B, K), dtype=torch.float32, device=dev)
     n = torch.empty((B, G), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().iodine_mask_overlap(_stream(), _lib.ptr(mk), _lib.ptr(g8), B, K, G, S, eps, _lib.ptr(inter), _lib.ptr(nl),
-                                            _lib.ptr(area), _lib.ptr(n))
-    _lib.check(rc, None, 'iodine_mask_overlap')
+    _lib.call('iodine_mask_overlap', dev, mk, g8, B, K, G, S, eps, inter, nl, area, n)
     return inter, nl, area, n
 
 
@@ -133,10 +118,7 @@ def _match(stats, B, K, G, match_kind, loss_kind, want_cost):
     coef = torch.empty((B, G, 2), dtype=torch.float32, device=dev)
     cost = torch.empty((B, G, K), dtype=torch.float32, device=dev) if want_cost else None
     iou = torch.empty((B, G, K), dtype=torch.float32, device=dev) if want_cost else None
-    with torch.cuda.device(dev):
-        rc = _lib.lib().iodine_mask_match(_stream(), _lib.ptr(inter), _lib.ptr(nl), _lib.ptr(area), _lib.ptr(n), B, K, G, match_kind,
-                                          loss_kind, _lib.ptr(asg), _lib.ptr(loss), _lib.ptr(coef), _lib.ptr(cost), _lib.ptr(iou))
-    _lib.check(rc, None, 'iodine_mask_match')
+    _lib.call('iodine_mask_match', dev, inter, nl, area, n, B, K, G, match_kind, loss_kind, asg, loss, coef, cost, iou)
     return asg, loss, coef, cost, iou
 
 
@@ -163,11 +145,7 @@ def assign(cost, row_valid=None):
     lead, G, K = tuple(cost.shape[:-2]), int(cost.shape[-2]), int(cost.shape[-1])
     if not 1 <= G <= MAX_SLOTS or not 1 <= K <= MAX_SLOTS:
         raise ValueError(f'assign: G and K must be in 1..{MAX_SLOTS}, got {G}, {K}')
-    B = 1
-    for d in lead:
-        B *= int(d)
-    if B < 1:
-        raise ValueError(f'assign: empty leading dimensions {lead}')
+    B = _args.lead_count(lead, f'assign: empty leading dimensions {lead}')
     rv = None
     if row_valid is not None:
         if not isinstance(row_valid, torch.Tensor) or tuple(row_valid.shape) != lead + (G,):
@@ -176,9 +154,7 @@ def assign(cost, row_valid=None):
     c = cost.detach().contiguous()
     asg = torch.empty(lead + (G,), dtype=torch.int32, device=c.device)
     total = torch.empty(lead, dtype=torch.float32, device=c.device)
-    with torch.cuda.device(c.device):
-        rc = _lib.lib().iodine_assign(_stream(), _lib.ptr(c), _lib.ptr(rv), B, G, K, _lib.ptr(asg), _lib.ptr(total))
-    _lib.check(rc, None, 'iodine_assign')
+    _lib.call('iodine_assign', c.device, c, rv, B, G, K, asg, total)
     return asg, total
 
 
@@ -215,10 +191,7 @@ class _MatchedMaskLoss(torch.autograd.Function):
         (B, K, G, S), loss_kind, eps, shape = ctx.args
         gl = grad_loss.detach().to(torch.float32).contiguous()
         grad = torch.empty(shape, dtype=torch.float32, device=mk.device)
-        with torch.cuda.device(mk.device):
-            rc = _lib.lib().iodine_mask_match_backward(_stream(), _lib.ptr(mk), _lib.ptr(gt), _lib.ptr(asg), _lib.ptr(coef), _lib.ptr(gl),
-                                                       B, K, G, S, loss_kind, eps, _lib.ptr(grad))
-        _lib.check(rc, None, 'iodine_mask_match_backward')
+        _lib.call('iodine_mask_match_backward', mk.device, mk, gt, asg, coef, gl, B, K, G, S, loss_kind, eps, grad)
         return grad, None, None, None, None, None
 
 
@@ -245,9 +218,7 @@ def _hard_tables(mask, gt):
     lead, B, K, G, S = _check_pair(mask, gt, 'segmentation_scores')
     mk, g8 = mask.detach().contiguous(), gt.contiguous()
     table = torch.empty((B, G, K), dtype=torch.int32, device=mk.device)
-    with torch.cuda.device(mk.device):
-        rc = _lib.lib().iodine_ari_table(_stream(), _lib.ptr(mk), _lib.ptr(g8), B, K, G, S * S, _lib.ptr(table))
-    _lib.check(rc, None, 'iodine_ari_table')
+    _lib.call('iodine_ari_table', mk.device, mk, g8, B, K, G, S * S, table)
     hard = slot_table(mk.view(B, K, 1, S, S))[..., SLOT_COLUMNS.index('hard_area')]
     return table.cpu().to(torch.int64), hard.cpu().to(torch.float64)
 

@@ -438,7 +438,7 @@ class IODINE(nn.Module):
         s = self._bind(device)
         if eps is None:
             out = s.out('eps', shape)
-            s.call('iodine_randn', out, out.numel(), self._seed, self._draws, handle=False)
+            _lib.call('iodine_randn', device, out, out.numel(), self._seed, self._draws)
             self._draws += 1
             return out
         if tuple(eps.shape) != shape:

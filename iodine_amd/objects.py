@@ -9,11 +9,9 @@ slot permutation between the two segmentations - what following the slots from f
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 # columns of the table, in order (include/iodine_hip.h, iodine_slot_table)
 SLOT_COLUMNS = ('soft_area', 'hard_area', 'soft_cx', 'soft_cy', 'hard_cx', 'hard_cy', 'x0', 'y0', 'x1', 'y1', 'r', 'g', 'b', 'peak')
@@ -21,19 +19,14 @@ MAX_SLOTS = 16
 MAX_SIZE = 1024
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def slot_table(mask: torch.Tensor, mean=None, segmentation: bool = False):
     """``mask (*, K, 1, S, S)``, ``mean (*, K, 3, S, S)`` or None -> ``table (*, K, 14)`` float32 on the device, columns ``SLOT_COLUMNS``;
     with ``segmentation=True`` the pair ``(table, seg (*, S, S) uint8)``, ``seg = argmax_K mask`` with the lowest index winning a tie.
     Any leading dimensions: ``(B, ...)`` or the ``(T + 1, B, ...)`` of a trajectory.  Empty slots read ``hard_area`` 0 and -1 in the hard
     centroid and the box; without ``mean`` the colour columns are 0."""
-    if not isinstance(mask, torch.Tensor) or (mean is not None and not isinstance(mean, torch.Tensor)):
-        raise ValueError('slot_table: mask (and mean) must be torch tensors')
-    if mask.device.type != 'cuda' or (mean is not None and mean.device != mask.device):
-        raise RuntimeError('slot_table needs mask (and mean) on one ROCm device (no CPU fallback)')
+    given = (mask,) if mean is None else (mask, mean)
+    _args.all_tensors(given, 'slot_table: mask (and mean) must be torch tensors')
+    _args.one_device(given, 'slot_table needs mask (and mean) on one ROCm device (no CPU fallback)')
     if mask.dim() < 4 or mask.shape[-3] != 1 or mask.shape[-1] != mask.shape[-2]:
         raise ValueError(f'slot_table: mask must be (*, K, 1, S, S), got {tuple(mask.shape)}')
     lead, K, S = tuple(mask.shape[:-4]), int(mask.shape[-4]), int(mask.shape[-1])
@@ -41,19 +34,13 @@ def slot_table(mask: torch.Tensor, mean=None, segmentation: bool = False):
         raise ValueError(f'slot_table: K must be in 1..{MAX_SLOTS} and S in 1..{MAX_SIZE}, got K = {K}, S = {S}')
     if mean is not None and tuple(mean.shape) != lead + (K, 3, S, S):
         raise ValueError(f'slot_table: mean must be {lead + (K, 3, S, S)} for this mask, got {tuple(mean.shape)}')
-    B = 1
-    for d in lead:
-        B *= int(d)
-    if B < 1:
-        raise ValueError(f'slot_table: empty leading dimensions {lead}')
+    B = _args.lead_count(lead, f'slot_table: empty leading dimensions {lead}')
     dev = mask.device
     mk = mask.detach().to(torch.float32).contiguous()
     mn = None if mean is None else mean.detach().to(torch.float32).contiguous()
     table = torch.empty(lead + (K, len(SLOT_COLUMNS)), dtype=torch.float32, device=dev)
     seg = torch.empty(lead + (S, S), dtype=torch.uint8, device=dev) if segmentation else None
-    with torch.cuda.device(dev):
-        rc = _lib.lib().iodine_slot_table(_stream(), _lib.ptr(mk), _lib.ptr(mn), B, K, S, _lib.ptr(table), _lib.ptr(seg))
-    _lib.check(rc, None, 'iodine_slot_table')
+    _lib.call('iodine_slot_table', dev, mk, mn, B, K, S, table, seg)
     return (table, seg) if segmentation else table
 
 
@@ -61,10 +48,8 @@ def overlap_table(seg_a: torch.Tensor, seg_b: torch.Tensor, ka: int, kb: int) ->
     """Two label maps ``(*, S, S)`` uint8 of one shape, as ``slot_table`` returns them -> ``(*, ka, kb)`` int32 on the device,
     ``[..., i, j] = #{p : seg_a = i and seg_b = j}``.  The last two dimensions are always the pixels of one map (a flat ``(B, P)`` map goes
     in as ``(B, 1, P)``).  Pixels labelled ``>= ka`` in ``seg_a`` or ``>= kb`` in ``seg_b`` are left out."""
-    if not isinstance(seg_a, torch.Tensor) or not isinstance(seg_b, torch.Tensor):
-        raise ValueError('overlap_table: seg_a and seg_b must be torch tensors')
-    if seg_a.device.type != 'cuda' or seg_b.device != seg_a.device:
-        raise RuntimeError('overlap_table needs both maps on one ROCm device (no CPU fallback)')
+    _args.all_tensors((seg_a, seg_b), 'overlap_table: seg_a and seg_b must be torch tensors')
+    _args.one_device((seg_a, seg_b), 'overlap_table needs both maps on one ROCm device (no CPU fallback)')
     if seg_a.dtype != torch.uint8 or seg_b.dtype != torch.uint8:
         raise ValueError(f'overlap_table: the maps must be uint8, got {seg_a.dtype} and {seg_b.dtype}')
     if seg_a.shape != seg_b.shape or seg_a.dim() < 2:
@@ -74,16 +59,13 @@ def overlap_table(seg_a: torch.Tensor, seg_b: torch.Tensor, ka: int, kb: int) ->
         raise ValueError(f'overlap_table: ka and kb must be in 1..{MAX_SLOTS}, got {ka}, {kb}')
     lead = tuple(seg_a.shape[:-2])
     P = int(seg_a.shape[-2]) * int(seg_a.shape[-1])
-    B = 1
-    for d in lead:
-        B *= int(d)
-    if B < 1 or not 1 <= P <= MAX_SIZE * MAX_SIZE:
-        raise ValueError(f'overlap_table: need at least one map of 1..{MAX_SIZE * MAX_SIZE} pixels, got {tuple(seg_a.shape)}')
+    few = f'overlap_table: need at least one map of 1..{MAX_SIZE * MAX_SIZE} pixels, got {tuple(seg_a.shape)}'
+    B = _args.lead_count(lead, few)
+    if not 1 <= P <= MAX_SIZE * MAX_SIZE:
+        raise ValueError(few)
     a, b = seg_a.contiguous(), seg_b.contiguous()
     table = torch.empty(lead + (ka, kb), dtype=torch.int32, device=a.device)
-    with torch.cuda.device(a.device):
-        rc = _lib.lib().iodine_seg_overlap(_stream(), _lib.ptr(a), _lib.ptr(b), B, ka, kb, P, _lib.ptr(table))
-    _lib.check(rc, None, 'iodine_seg_overlap')
+    _lib.call('iodine_seg_overlap', a.device, a, b, B, ka, kb, P, table)
     return table
 
 

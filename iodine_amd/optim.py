@@ -67,9 +67,7 @@ class _GradNorm:
 
     def norm(self, ptrs, offs, n, total, max_norm, dev):
         self.buffers(dev, total)
-        rc = _lib.lib().iodine_grad_norm(C.c_void_p(torch.cuda.current_stream().cuda_stream), _lib.ptr(ptrs), _lib.ptr(offs), n,
-                                         total, max_norm, _lib.ptr(self.scratch), self.scratch.numel() * 8, _lib.ptr(self.out4))
-        _lib.check(rc, None, 'iodine_grad_norm')
+        _lib.call('iodine_grad_norm', dev, ptrs, offs, n, total, max_norm, self.scratch, self.scratch.numel() * 8, self.out4)
 
 
 _standalone = {}        # device -> _GradNorm of clip_grad_norm_
@@ -95,11 +93,8 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0):
         raise RuntimeError('clip_grad_norm_: all gradients must live on one device')
     gn = _standalone.setdefault(dev, _GradNorm())
     ptrs, offs, total = gn.table([p.grad for p in ps])
-    with torch.cuda.device(dev):
-        gn.norm(ptrs, offs, len(ps), total, max_norm, dev)
-        rc = _lib.lib().iodine_grad_scale(C.c_void_p(torch.cuda.current_stream().cuda_stream), _lib.ptr(ptrs), _lib.ptr(offs),
-                                          len(ps), total, C.c_void_p(gn.out4.data_ptr() + 4))
-    _lib.check(rc, None, 'iodine_grad_scale')
+    gn.norm(ptrs, offs, len(ps), total, max_norm, dev)
+    _lib.call('iodine_grad_scale', dev, ptrs, offs, len(ps), total, C.c_void_p(gn.out4.data_ptr() + 4))
     for p in ps:
         torch.autograd.graph.increment_version(p.grad)        # written through raw pointers
     return gn.out4[0].clone()
@@ -154,7 +149,6 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        L = _lib.lib()
         # The reference builds ONE PARAM GROUP PER PARAMETER (lib/solver/build.py:10-14); groups that share their
         # hyper-parameters and step count are fused into a single launch (one launch per step for the reference layout).
         buckets = {}
@@ -188,21 +182,16 @@ class FusedAdam(torch.optim.Optimizer):
                 ptrs, offs, total = self._table(key[:4] + (dev,), every)
             else:
                 ptrs, offs, total = self._gradnorm.table([p.grad for p in every])
-            with torch.cuda.device(dev):
-                self._gradnorm.norm(ptrs, offs, len(every), total, self.max_grad_norm, dev)
-            out4, skip = _lib.ptr(self._gradnorm.out4), int(self.nonfinite == 'skip')
+            self._gradnorm.norm(ptrs, offs, len(every), total, self.max_grad_norm, dev)
+            clipped = (self._gradnorm.out4, int(self.nonfinite == 'skip'))
         for key, ps in buckets.items():
             lr, (b1, b2), eps, wd, t0, dev = key
             t = t0 + 1
             ptrs, offs, total = self._table(key[:4] + (dev,), ps)
-            with torch.cuda.device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                if clip:
-                    rc = L.iodine_adam_step_clipped(stream, _lib.ptr(ptrs), _lib.ptr(offs), len(ps), total, lr, b1, b2, eps, wd, t,
-                                                    out4, skip)
-                else:
-                    rc = L.iodine_adam_step(stream, _lib.ptr(ptrs), _lib.ptr(offs), len(ps), total, lr, b1, b2, eps, wd, t)
-            _lib.check(rc, None, 'iodine_adam_step_clipped' if clip else 'iodine_adam_step')
+            if clip:
+                _lib.call('iodine_adam_step_clipped', dev, ptrs, offs, len(ps), total, lr, b1, b2, eps, wd, t, *clipped)
+            else:
+                _lib.call('iodine_adam_step', dev, ptrs, offs, len(ps), total, lr, b1, b2, eps, wd, t)
             for p in ps:
                 st = self.state[p]
                 st['step'] = st['step'] + 1 if torch.is_tensor(st['step']) else t     # int steps: checkpoints of old torch

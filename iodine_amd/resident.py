@@ -17,7 +17,6 @@ with the bits of ``synth.make_images`` without the host (``iodine_synth_scenes``
 store may be held on the CPU (ingest, save, load), but batches come from a ROCm device only."""
 from __future__ import annotations
 
-import ctypes as C
 import os
 
 import numpy as np
@@ -29,10 +28,6 @@ from .objects import MAX_SLOTS
 
 KINDS = {'uniform': 0, 'blobs': 1}
 MAX_WORKERS = 16
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ---- bit-words ----------------------------------------------------------------------------------------------------------------------
@@ -184,9 +179,7 @@ def epoch_order(n: int, seed: int, epoch: int, device) -> torch.Tensor:
     if device.type != 'cuda':
         raise RuntimeError('resident: the epoch order is drawn on a ROCm device (no CPU fallback)')
     keys = torch.empty((n,), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        rc = _lib.lib().iodine_randn(_stream(), _lib.ptr(keys), n, int(seed), int(epoch))
-    _lib.check(rc, None, 'iodine_randn')
+    _lib.call('iodine_randn', device, keys, n, int(seed), int(epoch))
     return torch.argsort(keys, stable=True).cpu()
 
 
@@ -343,10 +336,8 @@ class ResidentDataset:
         x = torch.empty(lead + (3, S, S), dtype=torch.float32, device=self.device)
         G = max(1, int(counts.max()))
         gt = torch.empty(lead + (G, S, S), dtype=torch.uint8, device=self.device) if self.masks is not None and counts.max() > 0 else None
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().iodine_batch_gather(_stream(), _lib.ptr(dev_idx), int(dev_idx.numel()), _lib.ptr(self.images), self.image_kind,
-                                                _lib.ptr(self.masks) if gt is not None else None, S, G, _lib.ptr(x), _lib.ptr(gt))
-        _lib.check(rc, None, 'iodine_batch_gather')
+        _lib.call('iodine_batch_gather', self.device, dev_idx, int(dev_idx.numel()), self.images, self.image_kind,
+                  self.masks if gt is not None else None, S, G, x, gt)
         return x, gt, counts
 
     def batches(self, batch_size, shuffle=True, seed=0, epoch=0, rank=0, world_size=1, drop_last=False):
@@ -378,10 +369,8 @@ def synth_scenes(n, size, seed=0, kind='blobs', max_objects=6, frames=0, device=
     blobs = kind == 'blobs'
     masks = torch.empty(lead + (S, S), dtype=torch.uint16, device=device) if blobs else None
     n_gt = torch.zeros((n,), dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        rc = _lib.lib().iodine_synth_scenes(_stream(), n, S, int(seed), int(seed_step), int(stream), int(stream_step), KINDS[kind],
-                                            int(max_objects), F, _lib.ptr(images), _lib.ptr(masks), _lib.ptr(n_gt))
-    _lib.check(rc, None, 'iodine_synth_scenes')
+    _lib.call('iodine_synth_scenes', device, n, S, int(seed), int(seed_step), int(stream), int(stream_step), KINDS[kind], int(max_objects), F,
+              images, masks, n_gt)
     return images, masks, n_gt
 
 

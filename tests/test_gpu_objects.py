@@ -78,6 +78,19 @@ def test_two_calls_are_bitwise_equal(shape):
     assert torch.equal(objects.slot_table(md, cd).view(torch.int32), table.view(torch.int32))      # without the map: the same table
 
 
+def test_side_stream_gives_the_same_bits():
+    """the launch follows the caller's current stream: B = 2, K = 3, S = 16 on a side stream against the default stream"""
+    mask, mean = _inputs(2, 3, 16, seed=7)
+    md, cd = mask.to(DEV), mean.to(DEV)
+    table, seg = objects.slot_table(md, cd, segmentation=True)
+    side = torch.cuda.Stream(device=DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        t2, s2 = objects.slot_table(md, cd, segmentation=True)
+    side.synchronize()
+    assert torch.equal(t2.view(torch.int32), table.view(torch.int32)) and torch.equal(s2, seg)
+
+
 def test_leading_dimensions_and_mean_none():
     """(T+1, B, ...) inputs give (T+1, B, K, 14); without mean the colour columns are 0 and every other column keeps its bits"""
     md, cd, _, _, table, seg = _case(2, 7, 16)

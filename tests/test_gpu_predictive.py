@@ -175,7 +175,7 @@ def test_chunk_invariance(name):
     votes = torch.empty(B, K, Si, Si, device=DEV, dtype=torch.int32)
     wc = w.reshape(B, Si, Si).contiguous()
     _lib.check(_lib.lib().iodine_set_pixel_weights(m._handle, _lib.ptr(wc), 0), m._handle)
-    rc = _lib.lib().iodine_predictive(m._handle, m._stream(), B, S_MAX, _lib.ptr(c['pm']), _lib.ptr(c['plv']), _lib.ptr(c['eps']), _lib.ptr(c['x']), B,
+    rc = _lib.lib().iodine_predictive(m._handle, _lib.stream(), B, S_MAX, _lib.ptr(c['pm']), _lib.ptr(c['plv']), _lib.ptr(c['eps']), _lib.ptr(c['x']), B,
                                       _lib.ptr(z), _lib.ptr(pmean), _lib.ptr(pm2), _lib.ptr(mmean), _lib.ptr(mm2), _lib.ptr(votes), _lib.ptr(ll))
     _lib.check(rc, m._handle, 'iodine_predictive')
     for got, want in ((z, full.z), (pmean, full.pred_mean), (pm2 / S_MAX, full.pred_var), (mmean, full.mask_mean), (mm2 / S_MAX, full.mask_var),
@@ -184,7 +184,7 @@ def test_chunk_invariance(name):
     # outputs the caller does not ask for keep their running state in the workspace: the others are the same bits
     v2 = torch.empty_like(votes)
     m2b = torch.empty_like(mm2)
-    rc = _lib.lib().iodine_predictive(m._handle, m._stream(), B, S_MAX, _lib.ptr(c['pm']), _lib.ptr(c['plv']), _lib.ptr(c['eps']), None, B,
+    rc = _lib.lib().iodine_predictive(m._handle, _lib.stream(), B, S_MAX, _lib.ptr(c['pm']), _lib.ptr(c['plv']), _lib.ptr(c['eps']), None, B,
                                       None, None, None, None, _lib.ptr(m2b), _lib.ptr(v2), None)
     _lib.check(rc, m._handle, 'iodine_predictive')
     assert torch.equal(v2, full.votes) and torch.equal(m2b, mm2)
@@ -273,7 +273,7 @@ def test_raw_entry_refuses_before_any_launch():
     eps2 = c['eps'][:2].contiguous()
 
     def call(n=2, batch=B, chunk=0, x=c['x'], ll=pll, eps=eps2, plv=c['plv']):
-        return _lib.lib().iodine_predictive(m._handle, m._stream(), batch, n, _lib.ptr(c['pm']), _lib.ptr(plv), _lib.ptr(eps), _lib.ptr(x), chunk,
+        return _lib.lib().iodine_predictive(m._handle, _lib.stream(), batch, n, _lib.ptr(c['pm']), _lib.ptr(plv), _lib.ptr(eps), _lib.ptr(x), chunk,
                                             _lib.ptr(pz), _lib.ptr(pmean), None, None, None, _lib.ptr(pv), _lib.ptr(ll))
     err = lambda: _lib.lib().iodine_last_error(m._handle).decode()
     assert call(n=0) == 1 and 'n_samples' in err()

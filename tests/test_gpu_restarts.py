@@ -120,6 +120,19 @@ def test_chain_score_unaligned_pointers(S, K, Cn, B):
     assert (err <= 1e-6 * scale).all() and np.array_equal(seg_o.cpu().numpy(), want_seg) and torch.equal(seg_o, seg)
 
 
+def test_chain_score_on_a_side_stream_gives_the_same_bits():
+    """the launch follows the caller's current stream: C = 2 chains on a side stream against the default stream"""
+    d = _decodes(16, 3, 2, 1)
+    x, mask, mean, w = (d[n].to(DEV) for n in ('x', 'mask', 'mean', 'w'))
+    ll, seg = chains.chain_score(x, mask, mean, 0.1, weights=w)
+    side = torch.cuda.Stream(device=DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        ll2, seg2 = chains.chain_score(x, mask, mean, 0.1, weights=w)
+    side.synchronize()
+    assert torch.equal(ll2.view(torch.int32), ll.view(torch.int32)) and torch.equal(seg2, seg)
+
+
 def test_chain_score_ties_and_nan():
     """exact ties go to the lowest index; a NaN plane never wins (and a pixel of NaNs alone reads 0)"""
     S, K = 16, 4

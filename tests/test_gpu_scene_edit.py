@@ -119,7 +119,7 @@ def test_three_chunks_through_the_c_entry():
     m.decode(z)                                              # workspace of B images on the handle
     pred = torch.empty(E, 3, S, S, device=DEV)
     arr = lambda v: (C.c_int * E)(*v)
-    rc = _lib.lib().iodine_scene_edit(m._handle, m._stream(), B, _lib.ptr(z), E, arr(image), arr(slot), arr([0] * E), _lib.ptr(zn), B,
+    rc = _lib.lib().iodine_scene_edit(m._handle, _lib.stream(), B, _lib.ptr(z), E, arr(image), arr(slot), arr([0] * E), _lib.ptr(zn), B,
                                       _lib.ptr(pred), None, None, None, None, None)
     _lib.check(rc, m._handle, 'iodine_scene_edit')
     assert torch.equal(pred, ref[0])
@@ -172,7 +172,7 @@ def test_removal_at_one_slot_raises_and_names_the_edit():
     m.decode(z)
     one = (C.c_int * 1)(0)
     rm = (C.c_int * 1)(1)
-    rc = _lib.lib().iodine_scene_edit(m._handle, m._stream(), 2, _lib.ptr(z), 1, one, one, rm, None, 0, None, None, None, None, None, None)
+    rc = _lib.lib().iodine_scene_edit(m._handle, _lib.stream(), 2, _lib.ptr(z), 1, one, one, rm, None, 0, None, None, None, None, None, None)
     assert rc == 1
     assert b'edit 0' in _lib.lib().iodine_last_error(m._handle)
 
@@ -239,7 +239,7 @@ def test_raw_entry_refuses_bad_lists_before_any_launch():
     pbase = torch.full((B, 3, S, S), -7.0, device=DEV)
     arr = lambda v: (C.c_int * len(v))(*v)
     call = lambda image, slot, kind, chunk=0, n=2, znew=zn: _lib.lib().iodine_scene_edit(
-        m._handle, m._stream(), B, _lib.ptr(z), n, arr(image), arr(slot), arr(kind), _lib.ptr(znew), chunk, _lib.ptr(poison), _lib.ptr(pmask), None,
+        m._handle, _lib.stream(), B, _lib.ptr(z), n, arr(image), arr(slot), arr(kind), _lib.ptr(znew), chunk, _lib.ptr(poison), _lib.ptr(pmask), None,
         _lib.ptr(pbase), None, None)
     err = lambda: _lib.lib().iodine_last_error(m._handle).decode()
     assert call([0, B], [0, 0], [0, 0]) == 1 and 'edit 1: image' in err()
@@ -277,7 +277,7 @@ def test_call_state_reconstruct_edit_decode():
     # the last elbo()'s decoder output was overwritten by the base decode: the library says so instead of rendering the wrong scene
     S = m.img_size
     buf = torch.empty(B, 3, S, S, device=DEV)
-    rc = _lib.lib().iodine_last_elbo_outputs(m._handle, m._stream(), B, None, None, None, None, _lib.ptr(buf))
+    rc = _lib.lib().iodine_last_elbo_outputs(m._handle, _lib.stream(), B, None, None, None, None, _lib.ptr(buf))
     assert rc == 3                                                               # IODINE_ERR_STATE
 
 

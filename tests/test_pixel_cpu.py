@@ -34,7 +34,7 @@ def _call(L, x, w, dec, pm, plv, lin, B, K, S, Lat, sigma, beta, flags, chmask, 
 
 def test_header_binding_and_refusals():
     header = open(os.path.join(ROOT, 'include', 'iodine_hip.h')).read()
-    ops = open(os.path.join(ROOT, 'iodine_amd', 'csrc', 'iodine_ops.cpp')).read()
+    ops = open(os.path.join(ROOT, 'iodine_amd', 'csrc', 'iodine_testops.cpp')).read()
     assert re.search(r'int iodine_op_pixel_encode\(void\* stream, const float\* x_nchw, const float\* w_or_null, const float\* dec_out_nhwc4, '
                      r'const float\* pm, const float\* plv,\s+const float\* lin, int batch, int slots, int size, int latent, float sigma, float beta, '
                      r'int flags, unsigned chmask,\s+int repeat, float\* const\* out\);', header)
