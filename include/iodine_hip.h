@@ -667,6 +667,42 @@ int iodine_synth_scenes(void* stream, int n, int size, unsigned long long seed, 
                         unsigned long long stream_step, int kind, int max_objects, int frames, float* images,
                         unsigned short* masks_or_null, unsigned char* n_gt_or_null);
 
+/* Windowed batches (iodine_amd/windows.py): the store keeps its frames at their native H x W and every item of a batch is a window of its
+ * frame resampled to size x size on the device - crop, antialiased resize, mirror and colour gain in one launch.  Stateless like the two
+ * entries above: no handle, no workspace, one launch, no synchronise, no atomics, deterministic.
+ *
+ * iodine_batch_window: item j is a window of store entry index[j] (a frame of a clip is an entry, as for iodine_batch_gather).
+ *   images, image_kind 0: uint8 (N,H,W,3), v = (float)u / 255.f (IEEE division);  image_kind 1: float32 (N,3,H,W), v as stored.
+ *   masks_or_null uint16 (N,H,W), bit g = inside mask g.  H = src_h, W = src_w, S = size.
+ *   windows (count,8) fp32 in device memory: y0, x0, h, w, flip, gain_r, gain_g, gain_b - y0, x0, h, w in source pixels, fractional values
+ *   allowed, h, w > 0, the window inside the frame, h / S <= 4 and w / S <= 4, flip 0 or 1, gains >= 0.
+ *   THE RULE (tests/window_reference.py states it in fp64): crop, then resize with a triangle filter, separably - PIL's BILINEAR with
+ *   antialiasing on the cut-out window.  Per axis (rows; columns alike with x0, w, W):
+ *     scale = h / S, support = max(scale, 1), centre = y0 + (i + 0.5) scale;
+ *     taps = the whole rows r of [lo, hi), lo = max(floor(y0), 0, int(centre - support + 0.5)), hi = min(ceil(y0 + h), H,
+ *     int(centre + support + 0.5)), int truncating: the taps are clamped to the window rounded outward to whole pixels, so a window is
+ *     resampled as if it had been cut out first; at most 9 of them;
+ *     weight of r = max(0, 1 - |r + 0.5 - centre| / support), normalised by the sum over the taps.
+ *   x[j][c][i][k] = clamp(gain_c * sum_r sum_q wy_r wx_q v[r][q][c], 0, 1), columns first, then rows.
+ *   gt[j][g][i][k] = bit g of the word of source pixel (floor(centre_y(i)), floor(centre_x(k))), clamped to the frame (PIL's NEAREST).
+ *   flip = 1: output column k holds what column S - 1 - k would have held, image and masks.
+ *   Coordinates, tap ranges and weights are computed in fp64 without contraction (a fused multiply-add changes which tap a border falls
+ *   on), the weights rounded to fp32 once; both passes accumulate in fp32.  Hence at scale 1 with whole y0, x0 the taps weigh {1, 0}: a
+ *   plain crop, a whole-pixel shift and a mirror with gains 1 give, bit for bit, the slice (or mirrored slice) of what iodine_batch_gather
+ *   writes for the same frame, and the identity window the gather itself.
+ *   x (count,3,S,S) fp32 and gt_or_null (count,planes,S,S) uint8 0/1 are written completely; gt is left alone when either of masks_or_null /
+ *   gt_or_null is NULL.  One block per (item, tile of output rows): column and row tap tables and the horizontal pass of the tile's source
+ *   rows are staged in LDS.  uint8 frames with W % 4 == 0 and a 4-byte aligned store are read as whole dwords, byte-wise otherwise.
+ *   Traffic per item: the window's pixels once (3 bytes, or 12, + 2 for the word of S * S of them) plus the rows two row tiles share, read;
+ *   (12 + planes) S * S written.  Offsets are 64-bit throughout.
+ *   THE INDICES AND WINDOWS ARE NOT CHECKED ON THE DEVICE: the caller validates them on the host before the launch (windows.py does).
+ *   The kernel clamps every tap into the frame, so a bad window gives wrong pixels, never a read outside the store.
+ * IODINE_ERR_INVALID, before anything touches the device, with the entry's name in iodine_last_error(NULL): a NULL required pointer,
+ * count < 1, src_h / src_w outside 1..4096, size outside 1..512, planes outside 1..16, a kind other than 0 / 1. */
+int iodine_batch_window(void* stream, const long long* index, int count, const void* images, int image_kind,
+                        const unsigned short* masks_or_null, int src_h, int src_w, const float* windows /* (count, 8) device */,
+                        int size, int planes, float* x, unsigned char* gt_or_null);
+
 /* Decomposition figures (iodine_amd/figures.py): image, reconstruction, segmentation and one panel per slot, for a few scenes or for the
  * refinement iterations of one scene, assembled on the device into one uint8 picture.  Stateless: no handle, no workspace, one launch, no
  * atomics, no scratch, no synchronise.

@@ -141,6 +141,8 @@ _SYMBOLS = {
     # device-resident datasets, iodine_amd.resident
     'iodine_batch_gather': ([_vp, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _vp],),
     'iodine_synth_scenes': ([_vp, _ci, _ci] + [_ull] * 4 + [_ci, _ci, _ci, _vp, _vp, _vp],),
+    # windowed batches, iodine_amd.windows
+    'iodine_batch_window': ([_vp, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _vp, _ci, _ci, _vp, _vp],),
     # decomposition sheets, iodine_amd.figures
     'iodine_sheet_size': ([C.POINTER(SheetSpec), _CIP, _CIP],),
     'iodine_sheet_form': ([C.POINTER(SheetSpec)] + [_vp] * 6,),

@@ -257,6 +257,9 @@ hipError_t launch_batch_gather(hipStream_t st, const long long* index, int count
 hipError_t launch_synth_scenes(hipStream_t st, int n, int S, unsigned long long seed, unsigned long long seed_step, unsigned long long stream,
                                unsigned long long stream_step, int kind, int max_objects, int frames, float* images, unsigned short* masks,
                                unsigned char* n_gt);
+// kernels_window.hip: a batch cut out of native-size frames - crop, antialiased resize, flip and colour gain per item (stateless)
+hipError_t launch_batch_window(hipStream_t st, const long long* index, int count, const void* images, int kind, const unsigned short* masks,
+                               int H, int W, const float* windows, int S, int planes, float* x, unsigned char* gt);
 hipError_t launch_assign(hipStream_t st, const float* cost, const unsigned char* row_valid, int B, int G, int K, int* assign,
                          float* total);
 hipError_t launch_mask_match(hipStream_t st, const float* inter, const float* nll, const float* mask_area, const int* gt_area, int B,

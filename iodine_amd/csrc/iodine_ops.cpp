@@ -160,6 +160,18 @@ int iodine_batch_gather(void* stream, const long long* index, int count, const v
     return free_hip("iodine_batch_gather", launch_batch_gather((hipStream_t)stream, index, count, images, image_kind, masks_or_null, size, planes, x, gt_or_null));
 }
 
+int iodine_batch_window(void* stream, const long long* index, int count, const void* images, int image_kind,
+                        const unsigned short* masks_or_null, int src_h, int src_w, const float* windows, int size, int planes, float* x,
+                        unsigned char* gt_or_null)
+{
+    if (!index || !images || !windows || !x || count < 1 || src_h < 1 || src_h > 4096 || src_w < 1 || src_w > 4096 || size < 1 || size > 512 ||
+        planes < 1 || planes > 16 || (image_kind != 0 && image_kind != 1))
+        return free_fail(IODINE_ERR_INVALID, "iodine_batch_window: bad argument (index, images, windows, x required, count >= 1, src_h and src_w in "
+                         "1..4096, size in 1..512, planes in 1..16, image_kind 0 = uint8 HWC / 1 = float32 CHW)");
+    return free_hip("iodine_batch_window", launch_batch_window((hipStream_t)stream, index, count, images, image_kind, masks_or_null, src_h, src_w,
+                                                               windows, size, planes, x, gt_or_null));
+}
+
 int iodine_synth_scenes(void* stream, int n, int size, unsigned long long seed, unsigned long long seed_step, unsigned long long stream_id,
                         unsigned long long stream_step, int kind, int max_objects, int frames, float* images,
                         unsigned short* masks_or_null, unsigned char* n_gt_or_null)

@@ -590,6 +590,14 @@ def make_parser():
                          'ingested once - and written to CACHE.npz, or loaded from it when it exists -, without a data set the synthetic scenes '
                          '(or, with --clip-frames, clips) are generated on the device; training and evaluation then run without host work '
                          'per batch')
+    ap.add_argument('--augment', metavar='SPEC',
+                    help='with --resident: train on random windows cut on the device (iodine_amd.windows.Augment) - a comma-separated list of '
+                         'flip, scale=LO:HI, ratio=LO:HI, translate=PIXELS|full, gain=G, e.g. flip,scale=0.7:1,ratio=0.8:1.25,translate=8,'
+                         'gain=0.1; evaluation keeps the centre window')
+    ap.add_argument('--native-frames', action='store_true',
+                    help='with --resident and --clevr: keep the frames at their native size (FrameStore.from_clevr; --resident CACHE.npz '
+                         'caches that store) and cut the centre crop, or the --augment windows, on the device')
+    ap.add_argument('--crop', type=int, default=192, metavar='PIXELS', help='with --native-frames: the side of the centre crop (192)')
     ap.add_argument('--traverse', metavar='OUT.npz',
                     help='instead of training: after loading (--resume), reconstruct the first batch, traverse the latent units of image 0 '
                          '(each slot, the units with the largest KL, moved along the posterior) and save the grids; see save_traversal')
@@ -627,6 +635,14 @@ def main(argv=None):
     from .data import CLEVR, MultiDSprites, make_dataloader
     from .model import clevr6_arch, dsprites_arch
     args = make_parser().parse_args(argv)
+    if (args.augment or args.native_frames) and args.resident is None:
+        raise SystemExit('--augment / --native-frames cut their windows from a device-resident store: add --resident')
+    if args.native_frames and not args.clevr:
+        raise SystemExit('--native-frames ingests a CLEVR folder at its native size: add --clevr')
+    try:
+        args.augment = parse_augment(args.augment) if args.augment else None   # (a bad spec is refused before any work)
+    except ValueError as e:
+        raise SystemExit(str(e))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank, local = int(os.environ.get('RANK', '0')), int(os.environ.get('LOCAL_RANK', '0'))
     if world > 1:
@@ -716,20 +732,84 @@ def _resident_store(args, arch, ds, device, rank, frames=0):
     return store
 
 
+def parse_augment(spec):
+    """``--augment SPEC`` -> the keyword arguments of ``windows.Augment``: a comma-separated list of ``flip``, ``scale=LO:HI`` (or one
+    number), ``ratio=LO:HI``, ``translate=PIXELS`` or ``translate=full``, ``gain=G``.  A ``ValueError`` names the entry it cannot read;
+    the ranges themselves are ``Augment``'s to check."""
+    kw = {}
+    for entry in (e.strip() for e in str(spec).split(',')):
+        key, eq, value = entry.partition('=')
+        if key not in ('flip', 'scale', 'ratio', 'translate', 'gain'):
+            raise ValueError(f'--augment: unknown entry {entry!r} (flip, scale=LO:HI, ratio=LO:HI, translate=PIXELS|full, gain=G)')
+        if key in kw:
+            raise ValueError(f'--augment: {key} is given twice')
+        if key == 'flip':
+            if eq:
+                raise ValueError(f'--augment: flip takes no value; got {entry!r}')
+            kw[key] = True
+            continue
+        try:
+            if key == 'translate' and value == 'full':
+                kw[key] = 'full'
+            elif key in ('scale', 'ratio'):
+                parts = [float(p) for p in value.split(':')]
+                if len(parts) not in (1, 2):
+                    raise ValueError
+                kw[key] = (parts[0], parts[-1])
+            else:
+                kw[key] = float(value)
+        except ValueError:
+            raise ValueError(f'--augment: cannot read {entry!r} ({key}={"LO:HI" if key in ("scale", "ratio") else "NUMBER"})') from None
+    return kw
+
+
+def _native_store(args, device, ds, rank):
+    """the store of ``--native-frames``: the CLEVR folder at its native size (or its cache loaded)"""
+    from .windows import FrameStore
+    log = print if rank == 0 else (lambda *a: None)
+    cache = args.resident or None
+    if cache and os.path.exists(cache):
+        log(f'resident: loading {cache}')
+        return FrameStore.load(cache, device)
+    frames = FrameStore.from_clevr(ds, device, log=log)
+    if cache and rank == 0:
+        frames.save(cache)
+        log(f'resident: wrote {cache}')
+    return frames
+
+
 def _main_resident(args, arch, model, optimizer, ds, device, rank, world, log_sigma, input_gain):
-    """``main`` from a device-resident store: the same training and evaluation calls, batches from ``ResidentDataset.batches``"""
+    """``main`` from a device-resident store: the same training and evaluation calls, batches from ``ResidentDataset.batches`` - or, with
+    ``--augment`` / ``--native-frames``, from ``FrameStore.batches`` (iodine_amd.windows)"""
     if args.clip_frames and args.mask_loss:
         raise SystemExit('--mask-loss trains on still images; it cannot be combined with --clip-frames')
     if args.clip_frames:
         clip_chunks(args.clip_frames, arch.ITERS)
         if args.clevr or args.dsprites:
             raise SystemExit('--clip-frames trains on synthetic clips; it cannot be combined with --clevr / --dsprites')
-    store = _resident_store(args, arch, ds, device, rank)
-    train_store = _resident_store(args, arch, ds, device, rank, frames=args.clip_frames) if args.clip_frames else store
-    if rank == 0:
-        print('resident: {} items of {} x {}, {} images, {:.1f} MiB on {}'.format(len(store), store.size, store.size,
-              'uint8' if store.image_kind == 0 else 'float32', (store.nbytes() + (train_store.nbytes() if train_store is not store else 0)) / 2 ** 20, device))
-    losses = train(model, optimizer, train_store.batches(args.batch, shuffle=True, rank=rank, world_size=world), device, args.steps,
+    if args.native_frames:
+        from .windows import Augment, Center
+        frames = _native_store(args, device, ds, rank)
+        if rank == 0:
+            print('resident: {} frames of {} x {}, uint8 images, {:.1f} MiB on {}; windows of {} -> {}'.format(
+                len(frames), frames.height, frames.width, frames.nbytes() / 2 ** 20, device, args.crop, arch.IMG_SIZE))
+        policy = Augment(crop=args.crop, **args.augment) if args.augment is not None else Center(args.crop)
+        train_batches = frames.batches(args.batch, arch.IMG_SIZE, policy, shuffle=True, rank=rank, world_size=world)
+        eval_batches = lambda: frames.batches(args.batch, arch.IMG_SIZE, Center(args.crop), shuffle=False, rank=rank, world_size=world)
+    else:
+        store = _resident_store(args, arch, ds, device, rank)
+        train_store = _resident_store(args, arch, ds, device, rank, frames=args.clip_frames) if args.clip_frames else store
+        if rank == 0:
+            print('resident: {} items of {} x {}, {} images, {:.1f} MiB on {}'.format(len(store), store.size, store.size,
+                  'uint8' if store.image_kind == 0 else 'float32', (store.nbytes() + (train_store.nbytes() if train_store is not store else 0)) / 2 ** 20, device))
+        if args.augment is not None:
+            from .windows import Augment, FrameStore
+            train_batches = FrameStore.from_resident(train_store).batches(args.batch, store.size, Augment(**args.augment), shuffle=True,
+                                                                          rank=rank, world_size=world)
+        else:
+            train_batches = train_store.batches(args.batch, shuffle=True, rank=rank, world_size=world)
+        eval_batches = lambda: store.batches(args.batch, shuffle=False, rank=rank, world_size=world)
+    losses = train(model, optimizer, train_batches, device, args.steps,
                    checkpoint_path=args.save, log=print if rank == 0 else (lambda *a: None), beta=args.beta,
                    beta_warmup_steps=args.beta_warmup, bptt=args.bptt if args.clip_frames else None, ignore_border=args.ignore_border,
                    log_sigma=log_sigma, input_gain=input_gain, mask_loss=args.mask_loss, mask_loss_kind=args.mask_loss_kind,
@@ -738,10 +818,9 @@ def _main_resident(args, arch, model, optimizer, ds, device, rank, world, log_si
     if args.metrics:
         from .matching import SegmentationEvaluator
         evaluator = SegmentationEvaluator()
-    ev = evaluate(model, store.batches(args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
-                  bound_samples=args.eval_samples, restarts=args.eval_restarts)
+    ev = evaluate(model, eval_batches(), device, evaluator=evaluator, bound_samples=args.eval_samples, restarts=args.eval_restarts)
     _report(args, rank, losses, ev)
-    _final_sheet(args, model, store.batches(args.batch, shuffle=False, rank=rank, world_size=world), device, rank)
+    _final_sheet(args, model, eval_batches(), device, rank)
 
 
 def _report(args, rank, losses, ev):
