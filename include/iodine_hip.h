@@ -544,6 +544,47 @@ int iodine_slot_table(void* stream, const float* mask, const float* mean_or_null
 int iodine_seg_overlap(void* stream, const unsigned char* seg_a, const unsigned char* seg_b, int batch, int slots_a, int slots_b,
                        int pixels, int* table);
 
+/* Connected components of segmentation maps: the OBJECTS of a map, where the entries above read one slot as one object (a slot that
+ * grabbed two objects, a background cut into pieces and the speckle of an argmax map along object borders are all "one slot").  Integers
+ * only: every output is exact and the same input gives the same bits on every call and every stream.
+ *   seg (B,S,S) uint8 (the seg of iodine_slot_table), pixel p = row * S + col.  A pixel is VALID if seg[p] < slots; an invalid pixel
+ *   belongs to no component and separates its neighbours.  Two valid pixels are joined if they hold the same value and are 4-neighbours
+ *   (connectivity 4) or 8-neighbours (connectivity 8); the components are the classes of that relation.  first(c) is the smallest p of
+ *   component c, area(c) its pixel count, slot(c) its value.  c is KEPT if area(c) >= min_area and SMALL otherwise; the kept components
+ *   of an image are numbered 0, 1, .. in increasing first(c) - the raster order in which scipy.ndimage.label numbers.
+ * Outputs, all overwritten (device memory for iodine_seg_components, host memory for iodine_seg_components_host):
+ *   labels (B,S,S) int32            id of the pixel's kept component; -1 in small components and at invalid pixels
+ *   area_map_or_null (B,S,S) int32  area of the pixel's component, small ones included; 0 at invalid pixels
+ *   count (B,4) int32               kept components, small components, pixels in small components, invalid pixels
+ *   per_slot_or_null (B,slots,4) int32   per slot: kept components, small components, area of its largest component (0 if none), its
+ *                                   pixels in small components
+ *   table_or_null (B,M,8) int32, M = max_components: row i < M describes kept component i: slot, area, sum_col, sum_row, x0, y0, x1, y1
+ *                                   (inclusive box; centroid = sum / area on the caller's side; the sums fit int32 up to S = 1024).  Rows
+ *                                   from the number of kept components upwards are all -1; ids >= M appear in labels and count only.
+ *   clean_or_null (B,S,S) uint8     kept and invalid pixels keep seg.  A small component c takes slot(d) of one kept component d: the
+ *                                   candidates are the kept components that contain a 4-neighbour of a pixel of c (the 4-neighbourhood
+ *                                   whatever connectivity is); d has the largest area, and the smaller first(d) on a tie.  A small
+ *                                   component without a kept 4-neighbour is left as it is.  ONE pass over the components of seg, not
+ *                                   iterated: clean may still hold components below min_area (specks enclosed by specks, or specks that
+ *                                   took different slots), and two kept regions of one slot may have grown together.
+ * iodine_seg_components: no handle, no allocation, no synchronise, everything on `stream`.  Union-find with atomic-minimum merges (every
+ *   retry strictly lowers a root; no loop waits for "nothing changed", so every launch ends for any input).  Images up to
+ *   IODINE_COMPONENTS_LDS_MAX_SIZE run one block per image with the parent array in LDS; larger ones merge 64 x 64 tiles in LDS and then
+ *   across the tile borders in `labels`.  scratch: device memory of iodine_seg_components_scratch_bytes(batch, size) bytes (host-only query,
+ *   0 for batch < 1 or size outside 1..1024), any alignment, contents irrelevant before and after.
+ * iodine_seg_components_host: one image on host pointers, a plain serial flood fill of the same rule (csrc/components_host.h).
+ * IODINE_ERR_INVALID, before anything touches the device, with the entry's name in iodine_last_error(NULL): seg, labels or count NULL,
+ *   batch outside 1..65535, slots outside 1..16, size outside 1..1024, connectivity other than 4 / 8, min_area < 1, max_components < 1 with
+ *   a table or < 0 without, scratch NULL or scratch_bytes below the query. */
+#define IODINE_COMPONENTS_LDS_MAX_SIZE 128
+size_t iodine_seg_components_scratch_bytes(int batch, int size);
+int iodine_seg_components(void* stream, const unsigned char* seg, int batch, int slots, int size, int connectivity, int min_area,
+                          int max_components, int* labels, int* area_map_or_null, int* count, int* per_slot_or_null,
+                          int* table_or_null, unsigned char* clean_or_null, void* scratch, size_t scratch_bytes);
+int iodine_seg_components_host(const unsigned char* seg, int slots, int size, int connectivity, int min_area, int max_components,
+                               int* labels, int* area_map_or_null, int* count, int* per_slot_or_null, int* table_or_null,
+                               unsigned char* clean_or_null);
+
 /* Refinement restarts (IODINE.restarts): inference is stochastic and multi-stable, so the same images are refined C times - C chains - and
  * the chains are scored, labelled and folded into one labelling.  Two stateless entries in the contract of the two above: no handle, no
  * workspace, no allocation, no synchronise, everything on `stream`, no float atomics.  P = size * size; row c B + b of a (C,B,..) tensor is

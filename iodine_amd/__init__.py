@@ -3,7 +3,7 @@
 ``iodine_amd.synth`` can be used without the HIP library being built."""
 
 __all__ = ['IODINE', 'Predictive', 'Restarts', 'chains', 'chain_score', 'chain_consensus', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse', 'matching', 'figures',
-           'slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS', 'latent_kl', 'rank_dims', 'Traversal',
+           'slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS', 'components', 'clean_segmentation', 'seg_to_mask', 'Components', 'latent_kl', 'rank_dims', 'Traversal',
            'pack_gt', 'overlap', 'assign', 'match_masks', 'matched_mask_loss', 'segmentation_scores', 'SegmentationEvaluator',
            'PALETTE', 'sheet', 'layout', 'matched_colors', 'decomposition', 'trajectory_sheet', 'restarts_sheet', 'encode_png', 'write_png']
 
@@ -21,7 +21,7 @@ def __getattr__(name):
     if name in ('chain_score', 'chain_consensus'):
         from . import chains
         return getattr(chains, name)
-    if name in ('slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS'):
+    if name in ('slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS', 'components', 'clean_segmentation', 'seg_to_mask', 'Components'):
         from . import objects
         return getattr(objects, name)
     if name in ('latent_kl', 'rank_dims', 'Traversal'):      # (``iodine_amd.traverse`` is the module; the function is ``traverse.traverse``)

@@ -123,6 +123,10 @@ _SYMBOLS = {
     # object tables, iodine_amd.objects
     'iodine_slot_table': ([_vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp],),
     'iodine_seg_overlap': ([_vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp],),
+    # connected components, iodine_amd.objects.components
+    'iodine_seg_components_scratch_bytes': ([_ci, _ci], _sz),
+    'iodine_seg_components': ([_vp, _vp] + [_ci] * 6 + [_vp] * 7 + [_sz],),
+    'iodine_seg_components_host': ([_vp] + [_ci] * 5 + [_vp] * 6,),
     # refinement restarts, iodine_amd.chains / IODINE.restarts (a build without them raises on it)
     'iodine_chain_score': ([_vp] * 5 + [_ci] * 4 + [_dbl, _ci, _vp, _vp],),
     'iodine_chain_consensus': ([_vp] * 5 + [_ci] * 4 + [_vp] * 5,),

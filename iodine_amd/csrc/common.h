@@ -234,6 +234,10 @@ hipError_t launch_slot_table(hipStream_t st, const float* mask, const float* mea
                              unsigned char* seg);
 hipError_t launch_seg_overlap(hipStream_t st, const unsigned char* seg_a, const unsigned char* seg_b, int B, int Ka, int Kb, int P,
                               int* table);
+// kernels_components.hip: connected components of segmentation maps (stateless; scratch of seg_components_scratch_bytes, host-only query)
+size_t seg_components_scratch_bytes(int B, int S);
+hipError_t launch_seg_components(hipStream_t st, const unsigned char* seg, int B, int slots, int S, int conn, int min_area, int M,
+                                 int* labels, int* area_map, int* count, int* per_slot, int* table, unsigned char* clean, void* scratch);
 // kernels_chains.hip: refinement restarts - C decodes of the same images scored and labelled, C labellings folded into one (stateless)
 hipError_t launch_chain_score(hipStream_t st, const float* x, const float* w, const float* mask, const float* mean, int C, int B, int K,
                               int S, double sigma, int joint, float* ll, unsigned char* seg);

@@ -3,6 +3,7 @@
 // (iodine_internal.h).  The kernel-test entries (iodine_op_*) are in iodine_testops.cpp.  See include/iodine_hip.h.
 #include "iodine_internal.h"
 #include "assign.h"
+#include "components_host.h"
 
 extern "C" {
 
@@ -64,6 +65,47 @@ int iodine_seg_overlap(void* stream, const unsigned char* seg_a, const unsigned 
         pixels > 1024 * 1024)
         return free_fail(IODINE_ERR_INVALID, "iodine_seg_overlap: bad argument (three pointers required, batch >= 1, slots_a / slots_b in 1..16, pixels in 1..1024^2)");
     return free_hip("iodine_seg_overlap", launch_seg_overlap((hipStream_t)stream, seg_a, seg_b, batch, slots_a, slots_b, pixels, table));
+}
+
+size_t iodine_seg_components_scratch_bytes(int batch, int size)
+{
+    return batch < 1 || size < 1 || size > 1024 ? 0 : seg_components_scratch_bytes(batch, size);
+}
+
+// what both component entries refuse (batch and scratch are the device entry's own)
+static const char* seg_components_bad(const unsigned char* seg, int slots, int size, int connectivity, int min_area, int max_components,
+                                      const int* labels, const int* count, const int* table)
+{
+    return !seg ? "seg is NULL" : !labels ? "labels is NULL" : !count ? "count is NULL"
+        : (slots < 1 || slots > 16) ? "slots must be in 1..16" : (size < 1 || size > 1024) ? "size must be in 1..1024"
+        : (connectivity != 4 && connectivity != 8) ? "connectivity must be 4 or 8" : min_area < 1 ? "min_area must be >= 1"
+        : (table && max_components < 1) ? "max_components must be >= 1 with a table" : max_components < 0 ? "max_components must be >= 0"
+        : nullptr;
+}
+
+int iodine_seg_components(void* stream, const unsigned char* seg, int batch, int slots, int size, int connectivity, int min_area,
+                          int max_components, int* labels, int* area_map_or_null, int* count, int* per_slot_or_null,
+                          int* table_or_null, unsigned char* clean_or_null, void* scratch, size_t scratch_bytes)
+{
+    const char* bad = seg_components_bad(seg, slots, size, connectivity, min_area, max_components, labels, count, table_or_null);
+    if (!bad)
+        bad = (batch < 1 || batch > 65535) ? "batch must be in 1..65535" : !scratch ? "scratch is NULL"
+            : scratch_bytes < seg_components_scratch_bytes(batch, size) ? "scratch is smaller than iodine_seg_components_scratch_bytes" : nullptr;
+    if (bad) return free_fail(IODINE_ERR_INVALID, std::string("iodine_seg_components: ") + bad);
+    return free_hip("iodine_seg_components", launch_seg_components((hipStream_t)stream, seg, batch, slots, size, connectivity, min_area,
+                                                                   max_components, labels, area_map_or_null, count, per_slot_or_null,
+                                                                   table_or_null, clean_or_null, scratch));
+}
+
+int iodine_seg_components_host(const unsigned char* seg, int slots, int size, int connectivity, int min_area, int max_components,
+                               int* labels, int* area_map_or_null, int* count, int* per_slot_or_null, int* table_or_null,
+                               unsigned char* clean_or_null)
+{
+    if (const char* bad = seg_components_bad(seg, slots, size, connectivity, min_area, max_components, labels, count, table_or_null))
+        return free_fail(IODINE_ERR_INVALID, std::string("iodine_seg_components_host: ") + bad);
+    iod_components_host(seg, slots, size, connectivity, min_area, max_components, labels, area_map_or_null, count, per_slot_or_null,
+                        table_or_null, clean_or_null);
+    return IODINE_OK;
 }
 
 int iodine_chain_score(void* stream, const float* x, const float* w_or_null, const float* mask, const float* mean, int chains, int batch,

@@ -380,7 +380,7 @@ def make_log_sigma(sigma, device):
     return torch.full((), math.log(float(sigma)), dtype=torch.float32, device=device, requires_grad=True)
 
 
-def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, bound_samples=0, restarts=0):
+def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, bound_samples=0, restarts=0, min_component_area=0):
     """eval.py:14-28 with the ARI evaluator of lib/eval/ari_eval.py (works under no_grad, unlike the reference).  With
     several ranks every rank evaluates its shard; the samples DistributedSampler appended to pad the shards to equal length
     are dropped (they duplicate the first images) and ``evaluator.global_mean`` holds the ARI over the whole dataset.
@@ -394,18 +394,24 @@ def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, 
     ``model.reconstruct``, get the best chain's decode per image through a thin proxy; ``evaluator.stability``, ``evaluator.best_score`` and
     ``evaluator.first_score`` are the dataset means (over all ranks) of ``Restarts.stability``, of the best chain's score and of chain 0's -
     what selecting gains, next to the metric.  ``bound_samples`` then samples around the chosen posterior.  0 or 1 (default): the path and
-    the bits of an evaluation without it, and none of the three attributes."""
+    the bits of an evaluation without it, and none of the three attributes.
+    ``min_component_area`` = N > 0: beside the evaluator's own scores, the argmax map of every decode is split into connected components
+    (``iodine_amd.objects.components``) and ``evaluator.cleaned`` holds the dataset means (over all ranks) of ``components_per_slot`` (per
+    non-empty slot), ``small_pixel_share`` (valid pixels in components below N) and of ``SegmentationEvaluator``'s ``aris / mious / scs /
+    mscs`` on the maps with those components absorbed.  0 (default): no launch is added, no attribute is set."""
     if isinstance(bound_samples, bool) or int(bound_samples) != bound_samples or bound_samples < 0:
         raise ValueError(f'evaluate: bound_samples must be an integer >= 0; got {bound_samples!r}')
     if isinstance(restarts, bool) or int(restarts) != restarts or restarts < 0:
         raise ValueError(f'evaluate: restarts must be an integer >= 0; got {restarts!r}')
+    if isinstance(min_component_area, bool) or int(min_component_area) != min_component_area or min_component_area < 0:
+        raise ValueError(f'evaluate: min_component_area must be an integer >= 0; got {min_component_area!r}')
     saved = (model.K, model.n_iters)
     if slots is not None:
         model.K = slots
     if iters is not None:
         model.n_iters = iters
     try:
-        return _evaluate(model, dataloader, device, evaluator, int(bound_samples), int(restarts))
+        return _evaluate(model, dataloader, device, evaluator, int(bound_samples), int(restarts), int(min_component_area))
     finally:
         model.K, model.n_iters = saved
 
@@ -427,12 +433,50 @@ class _BestOfRestarts:
         return res.pred, res.mask, res.mean
 
 
-def _evaluate(model, dataloader, device, evaluator, bound_samples=0, restarts=0):
+class _CleanedMaps:
+    """What ``evaluate(min_component_area=N)`` hands the evaluators in place of the model (or of ``_BestOfRestarts``): ``reconstruct(x)`` is
+    the wrapped one, and beside it the argmax map of the returned masks goes through ``objects.components(min_area=N, clean=True)`` - the
+    map is taken from the masks, so the best chain of a restart is read like a plain decode.  ``component_rows``: per image (components
+    per non-empty slot, share of the valid pixels in small components); ``replay.reconstruct(x)`` returns the same decode with the cleaned
+    map as a hard mask, for a second evaluator on the same batch."""
+
+    def __init__(self, inner, min_area):
+        self._inner, self._min_area, self.component_rows, self._last = inner, min_area, [], None
+        self.replay = self._Replay(self)
+
+    def __getattr__(self, name):
+        return getattr(self._inner, name)
+
+    def reconstruct(self, x):
+        from .objects import components, seg_to_mask, slot_table
+        pred, mask, mean = self._inner.reconstruct(x)
+        K, P = int(mask.shape[-4]), int(mask.shape[-1]) ** 2
+        comp = components(slot_table(mask, segmentation=True)[1], K, min_area=self._min_area, max_components=0, clean=True)
+        per_slot, count = comp.per_slot.cpu().double(), comp.count.cpu().double()
+        n = per_slot[..., 0] + per_slot[..., 1]                               # components of every slot
+        self.component_rows.extend(zip((n.sum(-1) / (n > 0).sum(-1).clamp_min(1)).tolist(),
+                                       (count[:, 2] / (P - count[:, 3]).clamp_min(1)).tolist()))
+        self._last = (pred, seg_to_mask(comp.clean, K), mean)
+        return pred, mask, mean
+
+    class _Replay:
+        def __init__(self, owner):
+            self._owner = owner
+
+        def reconstruct(self, x):
+            return self._owner._last
+
+
+def _evaluate(model, dataloader, device, evaluator, bound_samples=0, restarts=0, min_component_area=0):
     evaluator = evaluator or ARIEvaluator()
     evaluator.reset()
     bounds = []                                                              # per image: (iwae, elbo_mc)
     model.eval()
     scored = _BestOfRestarts(model, restarts) if restarts > 1 else model     # (what the evaluators call reconstruct on)
+    cleaned = None
+    if min_component_area:
+        from .matching import SegmentationEvaluator
+        scored, cleaned = _CleanedMaps(scored, min_component_area), SegmentationEvaluator()
     dist_on = torch.distributed.is_available() and torch.distributed.is_initialized()
     world = torch.distributed.get_world_size() if dist_on else 1
     rank = torch.distributed.get_rank() if dist_on else 0
@@ -442,9 +486,12 @@ def _evaluate(model, dataloader, device, evaluator, bound_samples=0, restarts=0)
         for data in dataloader:
             image, masks = data[0], data[1]
             if torch.is_tensor(masks):                                       # a ResidentDataset batch: packed on the device, with counts
-                evaluator.evaluate(scored, (image.to(device), masks, data[2]))
+                batch = (image.to(device), masks, data[2])
             else:
-                evaluator.evaluate(scored, (image.to(device), [m.numpy() for m in masks]))
+                batch = (image.to(device), [m.numpy() for m in masks])
+            evaluator.evaluate(scored, batch)
+            if cleaned is not None:                                          # the same decode, its map cleaned
+                cleaned.evaluate(scored.replay, batch)
             if bound_samples:
                 out = model.predictive(image.to(device), samples=bound_samples)
                 bounds.extend(zip(out.iwae.tolist(), out.elbo_mc.tolist()))
@@ -479,6 +526,14 @@ def _evaluate(model, dataloader, device, evaluator, bound_samples=0, restarts=0)
             torch.distributed.all_reduce(more)
         evaluator.global_means = {name: (float(s / c) if float(c) > 0 else 0.0) for name, (s, c) in zip(lists, more)}
         evaluator.global_means['aris'] = evaluator.global_mean
+    if cleaned is not None:                                                  # the same reductions over the cleaned maps' lists and the rows
+        rows = scored.component_rows[:mine]
+        cols = [[q[0] for q in rows], [q[1] for q in rows]] + [[v for v in getattr(cleaned, name)[:mine] if v == v] for name in cleaned.per_image]
+        tot = torch.tensor([[float(sum(v)), float(len(v))] for v in cols], dtype=torch.float64, device=stats.device)
+        if world > 1:
+            torch.distributed.all_reduce(tot)
+        names = ('components_per_slot', 'small_pixel_share') + tuple(cleaned.per_image)
+        evaluator.cleaned = {name: (float(s / c) if float(c) > 0 else 0.0) for name, (s, c) in zip(names, tot)}
     return evaluator
 
 
@@ -585,6 +640,10 @@ def make_parser():
     ap.add_argument('--mask-match', choices=['iou', 'ce'], default='iou', help='with --mask-loss: the cost the assignment minimises')
     ap.add_argument('--metrics', action='store_true',
                     help='evaluate with SegmentationEvaluator: matched mIoU, segmentation covering (SC) and mSC beside the ARI')
+    ap.add_argument('--min-component-area', type=int, default=0, metavar='N',
+                    help='with --metrics: also split every argmax map into connected components (iodine_amd.objects.components) and report '
+                         'the components per non-empty slot, the share of pixels in components below N pixels, and ARI / mIoU / SC / mSC of '
+                         'the maps with those components absorbed by a neighbour (0: off)')
     ap.add_argument('--resident', nargs='?', const='', default=None, metavar='CACHE.npz',
                     help='keep the data set in device memory and assemble every batch there (iodine_amd.resident): --clevr / --dsprites are '
                          'ingested once - and written to CACHE.npz, or loaded from it when it exists -, without a data set the synthetic scenes '
@@ -639,6 +698,8 @@ def main(argv=None):
         raise SystemExit('--augment / --native-frames cut their windows from a device-resident store: add --resident')
     if args.native_frames and not args.clevr:
         raise SystemExit('--native-frames ingests a CLEVR folder at its native size: add --clevr')
+    if args.min_component_area < 0 or (args.min_component_area and not args.metrics):
+        raise SystemExit('--min-component-area N >= 0 reports beside the scores of --metrics: add --metrics')
     try:
         args.augment = parse_augment(args.augment) if args.augment else None   # (a bad spec is refused before any work)
     except ValueError as e:
@@ -710,7 +771,7 @@ def main(argv=None):
         from .matching import SegmentationEvaluator
         evaluator = SegmentationEvaluator()
     ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
-                  bound_samples=args.eval_samples, restarts=args.eval_restarts)
+                  bound_samples=args.eval_samples, restarts=args.eval_restarts, min_component_area=args.min_component_area)
     _report(args, rank, losses, ev)
     _final_sheet(args, model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, rank)
 
@@ -818,7 +879,8 @@ def _main_resident(args, arch, model, optimizer, ds, device, rank, world, log_si
     if args.metrics:
         from .matching import SegmentationEvaluator
         evaluator = SegmentationEvaluator()
-    ev = evaluate(model, eval_batches(), device, evaluator=evaluator, bound_samples=args.eval_samples, restarts=args.eval_restarts)
+    ev = evaluate(model, eval_batches(), device, evaluator=evaluator, bound_samples=args.eval_samples, restarts=args.eval_restarts,
+                  min_component_area=args.min_component_area)
     _report(args, rank, losses, ev)
     _final_sheet(args, model, eval_batches(), device, rank)
 
@@ -828,6 +890,11 @@ def _report(args, rank, losses, ev):
         print('first loss {:.2f} -> last loss {:.2f}; Ari over all ranks: {}'.format(losses[0], losses[-1], ev.global_mean))
         if args.metrics:
             print('mIoU {:.4f}, SC {:.4f}, mSC {:.4f} over all ranks'.format(*[ev.global_means[n] for n in ('mious', 'scs', 'mscs')]))
+        if args.min_component_area:
+            print('connected components: {:.3f} per non-empty slot, {:.4%} of the pixels in components below {} pixels; those absorbed: '
+                  'Ari {}, mIoU {:.4f}, SC {:.4f}, mSC {:.4f}'.format(ev.cleaned['components_per_slot'], ev.cleaned['small_pixel_share'],
+                                                                       args.min_component_area,
+                                                                       *[ev.cleaned[n] for n in ('aris', 'mious', 'scs', 'mscs')]))
         if args.eval_restarts > 1:
             print('best of {} chains per image: stability {:.4f}, score {:.3f} (chain 0 alone: {:.3f})'.format(
                 args.eval_restarts, ev.stability, ev.best_score, ev.first_score))

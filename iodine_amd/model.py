@@ -616,7 +616,7 @@ class IODINE(nn.Module):
         iteration i then scores, differentiates and encodes frame i.  ``state`` / ``keep_state`` / ``weights``: see ``reconstruct``."""
         return self._reconstruct(x, eps, want_images=False, state=state, keep_state=keep_state, weights=weights)[3]
 
-    def reconstruct(self, x, eps=None, trajectory=False, state=None, keep_state=False, weights=None, objects=False):
+    def reconstruct(self, x, eps=None, trajectory=False, state=None, keep_state=False, weights=None, objects=False, components=False):
         """pred (B,3,S,S), mask (B,K,1,S,S), mean (B,K,3,S,S).  iodine.py:107-112.
 
         ``x``: images (B, 3, S, S), or a clip (B, T, 3, S, S), batch first: ELBO evaluation i uses frame ``x[:, i]`` for the
@@ -646,11 +646,39 @@ class IODINE(nn.Module):
         batch needs nothing special) and the per-slot KL of the final posterior against N(0, 1), ``0.5 sum_L(exp(lv) + m^2 - 1 - lv)`` -
         the usual "is this slot used" signal.  With ``trajectory=True`` as well, ``model.trajectory`` gains ``table (T+1,B,K,14)`` and
         ``segmentation (T+1,B,S,S)`` of every entry; entry T is ``model.objects``.  Every encode / reconstruct without it sets
-        ``model.objects = None``, adds no launch and returns the same bits."""
+        ``model.objects = None``, adds no launch and returns the same bits.
+
+        ``components=True`` or a dict of ``connectivity`` / ``min_area`` / ``max_components`` / ``clean`` (needs ``objects=True``, else
+        ValueError) adds ``model.objects['components']``: ``iodine_amd.objects.components`` of ``model.objects['segmentation']`` - the
+        connected components of the map, one more call after the table's, so a chunked batch gives the same result; with
+        ``trajectory=True`` also ``model.trajectory['components']`` over every entry.  Without it there is no such key and no launch."""
+        want_components = components is not None and components is not False
+        if want_components:                           # refused before any device work
+            if not objects:
+                raise ValueError("IODINE.reconstruct: components= reads model.objects['segmentation'] and needs objects=True")
+            components = {} if components is True else dict(components)
+            unknown = sorted(set(components) - {'connectivity', 'min_area', 'max_components', 'clean'})
+            if unknown:
+                raise ValueError(f'IODINE.reconstruct: components= takes connectivity, min_area, max_components and clean; got {unknown}')
         pred, mask, mean, _ = self._reconstruct(x, eps, state=state, trajectory=trajectory, keep_state=keep_state, weights=weights)
         if objects:
             self._read_objects(mask, mean, trajectory)
+            if want_components:
+                self._read_components(components, trajectory)
         return pred, mask, mean
+
+    @torch.no_grad()
+    def _read_components(self, options, trajectory):
+        """``model.objects['components']`` (and the trajectory's) of a finished reconstruct(objects=True): see there."""
+        from .objects import components
+        K = int(self.objects['table'].shape[-2])      # the slots of the masks the map was taken from
+        if trajectory:                                # one call over all T + 1 entries; the last is the returned decode
+            comp = components(self.trajectory['segmentation'], K, **options)
+            self.trajectory['components'] = comp
+            comp = type(comp)(*(None if t is None else t[-1] for t in comp))
+        else:
+            comp = components(self.objects['segmentation'], K, **options)
+        self.objects['components'] = comp
 
     @torch.no_grad()
     def _read_objects(self, mask, mean, trajectory):

@@ -6,8 +6,15 @@
 ``ari.compute_ari`` takes, between two runs or two frames instead of against ground truth; ``slot_iou`` is the intersection over union
 that follows from its row and column sums, and ``matching.assign(1 - slot_iou(overlap_table(a, b, K, K)).float())`` (on the device) is the
 slot permutation between the two segmentations - what following the slots from frame to frame needs.  The kernels are stateless and need no model; like ``ari.ari_tables`` there is no CPU path.
+
+``components`` reads a map as objects instead of slots: the connected components of every label (``iodine_seg_components``), numbered as
+``scipy.ndimage.label`` numbers them, with their areas, boxes and coordinate sums, the counts per slot, and on request the map with the
+components below ``min_area`` absorbed by a neighbour (``clean_segmentation``); ``seg_to_mask`` turns such a map back into a hard mask
+for everything that takes masks.  This one has a CPU path (``iodine_seg_components_host``, the same rule, serial).
 """
 from __future__ import annotations
+
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -17,6 +24,22 @@ from . import _args, _lib
 SLOT_COLUMNS = ('soft_area', 'hard_area', 'soft_cx', 'soft_cy', 'hard_cx', 'hard_cy', 'x0', 'y0', 'x1', 'y1', 'r', 'g', 'b', 'peak')
 MAX_SLOTS = 16
 MAX_SIZE = 1024
+# connected components (include/iodine_hip.h, iodine_seg_components): the columns of table, count and per_slot, in order
+COMPONENT_COLUMNS = ('slot', 'area', 'sum_col', 'sum_row', 'x0', 'y0', 'x1', 'y1')
+COUNT_COLUMNS = ('kept', 'small', 'small_pixels', 'invalid_pixels')
+PER_SLOT_COLUMNS = ('kept', 'small', 'largest_area', 'small_pixels')
+COMPONENTS_LDS_MAX_SIZE = 128   # IODINE_COMPONENTS_LDS_MAX_SIZE: up to here one block per image holds the parent array in LDS
+MAX_COMPONENT_BATCH = 65535     # maps in one device call
+
+
+class Components(NamedTuple):
+    """what ``components`` returns; ``table``, ``area_map`` and ``clean`` are None where they were not asked for"""
+    labels: torch.Tensor
+    count: torch.Tensor
+    per_slot: torch.Tensor
+    table: Optional[torch.Tensor]
+    area_map: Optional[torch.Tensor]
+    clean: Optional[torch.Tensor]
 
 
 def slot_table(mask: torch.Tensor, mean=None, segmentation: bool = False):
@@ -67,6 +90,90 @@ def overlap_table(seg_a: torch.Tensor, seg_b: torch.Tensor, ka: int, kb: int) ->
     table = torch.empty(lead + (ka, kb), dtype=torch.int32, device=a.device)
     _lib.call('iodine_seg_overlap', a.device, a, b, B, ka, kb, P, table)
     return table
+
+
+def _check_components(seg, slots, connectivity, min_area, max_components, table):
+    """host-side checks of ``components``: what the entry point would refuse, as ValueError -> (lead, S, ints)"""
+    _args.all_tensors((seg,), 'components: seg must be a torch tensor')
+    if seg.dtype != torch.uint8 or seg.dim() < 2 or seg.shape[-1] != seg.shape[-2]:
+        raise ValueError(f'components: seg must be uint8 (*, S, S), got {seg.dtype} {tuple(seg.shape)}')
+    values = (slots, connectivity, min_area, max_components)
+    if any(isinstance(v, bool) or int(v) != v for v in values):
+        raise ValueError(f'components: slots, connectivity, min_area and max_components must be integers, got {values!r}')
+    slots, connectivity, min_area, max_components = (int(v) for v in values)
+    S = int(seg.shape[-1])
+    if not 1 <= slots <= MAX_SLOTS or not 1 <= S <= MAX_SIZE:
+        raise ValueError(f'components: slots must be in 1..{MAX_SLOTS} and S in 1..{MAX_SIZE}, got slots = {slots}, S = {S}')
+    if connectivity not in (4, 8):
+        raise ValueError(f'components: connectivity must be 4 or 8, got {connectivity}')
+    if min_area < 1:
+        raise ValueError(f'components: min_area must be >= 1, got {min_area}')
+    if max_components < (1 if table else 0):
+        raise ValueError(f'components: max_components must be >= {1 if table else 0}, got {max_components}')
+    return tuple(seg.shape[:-2]), S, slots, connectivity, min_area, max_components
+
+
+def components(seg: torch.Tensor, slots: int, connectivity: int = 4, min_area: int = 1, max_components: int = 64,
+               area_map: bool = False, clean: bool = False) -> Components:
+    """Connected components of label maps ``seg (*, S, S)`` uint8, as ``slot_table(..., segmentation=True)`` returns them: the rule of
+    ``iodine_seg_components`` (include/iodine_hip.h).  A pixel is valid if ``seg < slots``; equal valid 4- / 8-neighbours are joined; a
+    component of at least ``min_area`` pixels is kept and numbered in the raster order of its first pixel (as ``scipy.ndimage.label``
+    numbers), any other is small.  Returns ``Components``, all int32 on seg's device:
+
+    - ``labels (*, S, S)``: id of the kept component, -1 for small and invalid pixels;
+    - ``count (*, 4)``: ``COUNT_COLUMNS``;  ``per_slot (*, slots, 4)``: ``PER_SLOT_COLUMNS``;
+    - ``table (*, max_components, 8)``: ``COMPONENT_COLUMNS`` of kept component i in row i, -1 in the rows beyond the kept count
+      (``max_components=0``: None); centroids are ``sum_col / area``, ``sum_row / area``;
+    - ``area_map (*, S, S)`` with ``area_map=True``: area of the pixel's component, small ones included (else None);
+    - ``clean (*, S, S)`` uint8 with ``clean=True``: every small component takes the slot of its largest kept 4-neighbour component (the
+      smaller first pixel on a tie; none: unchanged).  One pass, not iterated (else None).
+
+    A device tensor runs ``iodine_seg_components`` on the current stream (one allocation of scratch, no synchronise); a CPU tensor goes
+    image by image through ``iodine_seg_components_host``, the same rule."""
+    lead, S, slots, connectivity, min_area, M = _check_components(seg, slots, connectivity, min_area, max_components, max_components != 0)
+    B = _args.lead_count(lead, f'components: empty leading dimensions {lead}')
+    dev = seg.device
+    if dev.type not in ('cuda', 'cpu'):
+        raise RuntimeError(f'components: seg must be on a ROCm device or on the CPU, got {dev}')
+    sg = seg.detach().contiguous()
+
+    def new(*shape, dtype=torch.int32):
+        return torch.empty(lead + shape, dtype=dtype, device=dev)
+    labels, count, per_slot = new(S, S), new(4), new(slots, 4)
+    table = new(M, 8) if M else None
+    amap = new(S, S) if area_map else None
+    cl = new(S, S, dtype=torch.uint8) if clean else None
+    if dev.type == 'cuda':
+        if B > MAX_COMPONENT_BATCH:
+            raise ValueError(f'components: at most {MAX_COMPONENT_BATCH} maps a call, got {B}')
+        nbytes = _lib.fn('iodine_seg_components_scratch_bytes')(B, S)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _lib.call('iodine_seg_components', dev, sg, B, slots, S, connectivity, min_area, M, labels, amap, count, per_slot, table, cl,
+                  scratch, nbytes)
+    else:
+        host = _lib.fn('iodine_seg_components_host')
+        flat = [None if t is None else t.view((B,) + tuple(t.shape[len(lead):])) for t in (sg, labels, amap, count, per_slot, table, cl)]
+        for b in range(B):
+            s, *outs = [None if t is None else _lib.ptr(t[b]) for t in flat]
+            _lib.check(host(s, slots, S, connectivity, min_area, M, *outs), None, 'iodine_seg_components_host')
+    return Components(labels, count, per_slot, table, amap, cl)
+
+
+def clean_segmentation(seg: torch.Tensor, slots: int, min_area: int, connectivity: int = 4) -> torch.Tensor:
+    """``seg (*, S, S)`` uint8 with every component below ``min_area`` pixels given to its largest kept 4-neighbour component:
+    ``components(..., clean=True).clean`` (one pass, see there)."""
+    return components(seg, slots, connectivity=connectivity, min_area=min_area, max_components=0, clean=True).clean
+
+
+def seg_to_mask(seg: torch.Tensor, slots: int) -> torch.Tensor:
+    """A label map ``(*, S, S)`` uint8 as a hard mask ``(*, slots, 1, S, S)`` float32, 1 where ``seg == k`` (a pixel ``>= slots`` is 0 in
+    every plane): what ``ari_tables``, ``segmentation_scores``, ``slot_table`` and ``figures.sheet`` take.  Plain torch ops."""
+    _args.all_tensors((seg,), 'seg_to_mask: seg must be a torch tensor')
+    if seg.dtype != torch.uint8 or seg.dim() < 2 or isinstance(slots, bool) or int(slots) != slots or not 1 <= int(slots) <= MAX_SLOTS:
+        raise ValueError(f'seg_to_mask: seg must be uint8 (*, S, S) and slots an integer in 1..{MAX_SLOTS}, got {seg.dtype} '
+                         f'{tuple(seg.shape)}, slots = {slots!r}')
+    k = torch.arange(int(slots), dtype=torch.uint8, device=seg.device).view((int(slots), 1, 1, 1))
+    return (seg.unsqueeze(-3).unsqueeze(-3) == k).to(torch.float32)
 
 
 def slot_iou(table) -> torch.Tensor:
