@@ -630,6 +630,82 @@ int iodine_chain_consensus(void* stream, const unsigned char* seg, const int* pe
                            int chains, int batch, int slots, int size, int* votes_or_null, unsigned char* consensus_or_null,
                            float* agreement_or_null, float* match_or_null, float* mask_mean_or_null);
 
+/* Adaptive refinement (IODINE.reconstruct_adaptive): refine every image until ITS posterior stops improving, drop it from the batch, go on
+ * with the rest - the cost of a call follows the sum of the per-image iteration counts, not batch x max.  One handle entry and the two
+ * stateless device steps it is made of (no handle, no workspace, no allocation, no synchronise, no atomics; everything on `stream`).
+ *
+ * The stopping rule (tests/adaptive_reference.py is its definition, numpy float64).  ll_i(b), kl_i(b): the fp32 per-image terms of ELBO
+ * evaluation i; s_i(b) = (double)ll_i(b) - beta * (double)kl_i(b); R = check_every.  Decisions are taken after t = R, 2R, .. < max_iters
+ * updates only.  After t updates image b stops when  t >= budget[b]  (with a budget), or when  t >= max(min_iters, 2)  and
+ *     s_{t-1} - s_{t-2} < tol + rtol * |s_{t-2}|
+ * evaluated in fp64 in exactly that order - one multiply, one add, one subtract, one compare, no fused multiply-add (the kernel uses the
+ * round-to-nearest intrinsics), so the device agrees with numpy bit for bit.  A NaN on either side makes the comparison false: the image
+ * continues.  At t = max_iters every remaining image stops.  tol may be any finite number or +-inf (-inf: never stop early; +inf: stop at
+ * the first permitted check).  Each evaluation draws fresh noise: s is a one-sample estimate, tol has to sit above that noise, and with
+ * check_every > 1 only evaluations t - 1 and t - 2 are compared. */
+typedef struct iodine_adaptive_ctl {
+    int max_iters;                       /* >= 1: the updates an image gets at most */
+    int min_iters;                       /* 1..max_iters: no stop by the score before this many updates (and never before 2) */
+    int check_every;                     /* R >= 1: updates per round */
+    double tol, rtol;                    /* tol: not NaN; rtol >= 0 */
+} iodine_adaptive_ctl;
+/* iodine_adaptive_select: the decisions after one round.  All pointers device memory.
+ *   terms (rounds, n, 2) fp32 = {ll, kl} of the round's evaluations t - rounds .. t - 1 for the n active images in their current layout (the
+ *   handle's workspace lays a round at batch n out like this); idx_in (n) int32 = their original indices in 0..batch-1 (NULL: position =
+ *   index, the first round); t = updates done; ctl and beta as above; budget_or_null (batch) int32.  With rounds = 1 and a decision by the
+ *   score, s_{t-2} is read from row t - 2 of the traces, where the round before left it.
+ *   -> idx_out / pos_out (n): original index / position in the current layout of the images that continue, in ascending order of position
+ *   (a stable compaction); stop_idx / stop_pos (n): the same pair for those that stop; counts[2] = {continue, stop}; iters[orig] = t for
+ *   the images that stop; ll, kl (max_iters, batch) fp32 traces: rows t - rounds .. t - 1, column orig, of every image active in the round.
+ *   idx_out must not be idx_in.  An idx_in entry outside 0..batch-1 addresses nothing and is listed as stopped.
+ *   One block; a wave64 ballot / popcount scan, looped over n with the running offsets carried in LDS: no atomics, the same order and the
+ *   same bits on every call, any n >= 1.
+ *   IODINE_ERR_INVALID before anything touches the device (iodine_last_error(NULL) names the argument): a NULL among terms, ctl, the
+ *   outputs; n < 1 or n > batch; rounds outside 1..t; t > max_iters; min_iters outside 1..max_iters; check_every < 1; tol NaN; rtol < 0 or
+ *   NaN; beta NaN; idx_out == idx_in.
+ *
+ * iodine_adaptive_move: a table of 1..16 row gathers / scatters (host memory) in ONE launch.  Entry: row r < rows of row_floats floats
+ *   goes from src row src_index[r] to dst row dst_index[r] (a NULL index: r); src_rows / dst_rows are the extents in rows of the two arrays
+ *   (0 = rows) - an index outside its extent moves nothing.  float4 accesses where row_floats % 4 == 0 and src and dst are 16-byte
+ *   aligned, scalar otherwise, per entry.  Rows of one entry with the same destination are the caller's mistake (last writer unknown).
+ *   Source and destination of one entry never alias: a parallel in-place compaction would read rows other blocks have overwritten, so an
+ *   entry whose ranges [src, src + src_rows row_floats) and [dst, dst + dst_rows row_floats) overlap is refused; use a second buffer.
+ *   IODINE_ERR_INVALID before anything touches the device: table NULL, n_entries outside 1..16, an entry with src or dst NULL,
+ *   row_floats < 1, rows < 1, an extent below rows where there is no index, overlapping ranges. */
+typedef struct iodine_move_entry {
+    const float* src; float* dst;
+    long long row_floats;
+    const int* src_index; const int* dst_index;      /* device, int32, or NULL */
+    int rows, src_rows, dst_rows;
+} iodine_move_entry;
+int iodine_adaptive_select(void* stream, const float* terms, const int* idx_in, int n, int rounds, int t, int batch,
+                           const iodine_adaptive_ctl* ctl, double beta, const int* budget_or_null, int* idx_out, int* pos_out,
+                           int* stop_idx, int* stop_pos, int* counts, int* iters, float* ll, float* kl);
+int iodine_adaptive_move(void* stream, const iodine_move_entry* table, int n_entries);
+/* iodine_reconstruct_adaptive: iodine_reconstruct_seq with a per-image iteration count.  The handle's run shape must be (slots, iters =
+ * ctl->check_every): a round is check_every iterations (the last one what is left up to max_iters) on the first n_active rows of the
+ * workspace, each exactly the loop body of iodine_reconstruct_seq; after it one iodine_adaptive_select, one 8-byte read-back of the two
+ * counts (pinned memory, a synchronise on the call's stream - never of the device) and one iodine_adaptive_move: the stopped rows of
+ * (post_mean, post_logvar, h, c) go straight to the caller's tensors at their original index, the continuing rows of the state, of the
+ * packed image and of the next round's noise are gathered to the front of second buffers (owned by the handle, grown on demand).  While no
+ * image has stopped the noise is read in place.  After the last round one sample + decode over all `batch` images, from the caller's
+ * post_mean / post_logvar with eps[max_iters] - the last row for every image - gives pred / mask / mean / z.
+ *   x (B,3,S,S); eps (max_iters + 1, B, K, L); budget_or_null (B) int32 device, values in 1..max_iters (the caller's contract);
+ *   state_in: NULL or {post_mean, post_logvar, h, c} as iodine_reconstruct_seq takes it.
+ *   -> pred, mask, mean, z (each may be NULL); post_mean, post_logvar (B,K,L), lstm_h, lstm_c (B,K,MLP_UNITS), iters (B) int32, ll, kl
+ *   (max_iters, B) fp32, all required: image b holds what iodine_reconstruct_seq + iodine_last_refine_state give for it at iters[b]
+ *   iterations with the noise rows {0 .. iters[b] - 1, max_iters}, bit for bit; ll / kl are pre-filled with NaN by the entry, so rows
+ *   iters[b] .. of column b read NaN.  active_out_or_null: host ints, ceil(max_iters / check_every) of them: the batch each round ran at
+ *   (0 for rounds that did not run).  Pixel weights (iodine_set_pixel_weights) are taken like by every call that packs x.
+ * The call synchronises its stream; it is never captured in a hipGraph (option "graph": it runs eagerly) and refuses with IODINE_ERR_STATE
+ * on a stream that is being captured.  Clips (iodine_set_frames > 0) are refused.  Afterwards the workspace holds no evaluation of the
+ * whole batch: iodine_last_refine_state / iodine_last_elbo_outputs / iodine_last_posterior refuse until the next compute call.
+ * Profile categories: "adaptive_select", "adaptive_move" (the two launches between rounds). */
+int iodine_reconstruct_adaptive(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const iodine_adaptive_ctl* ctl,
+                                const int* budget_or_null, const float* const* state_in, float* pred, float* mask, float* mean, float* z,
+                                float* post_mean, float* post_logvar, float* lstm_h, float* lstm_c, int* iters, float* ll, float* kl,
+                                int* active_out_or_null);
+
 /* Slots matched to ground-truth masks: the K slots are exchangeable, so a loss (or a metric) against G object masks needs a minimum-cost
  * assignment of objects to slots per image.  Five stateless entries - no handle, no workspace, no synchronise - of which a training step
  * uses three: a per-pixel pass (iodine_mask_overlap), a tiny pass (iodine_mask_match), a per-pixel pass (iodine_mask_match_backward).

@@ -2,7 +2,7 @@
 ``IODINE.forward / reconstruct`` module API.  Heavy imports are lazy so that
 ``iodine_amd.synth`` can be used without the HIP library being built."""
 
-__all__ = ['IODINE', 'Predictive', 'Restarts', 'chains', 'chain_score', 'chain_consensus', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse', 'matching', 'figures',
+__all__ = ['IODINE', 'Predictive', 'Restarts', 'Adaptive', 'adaptive', 'chains', 'chain_score', 'chain_consensus', 'synth', 'parallel', 'optim', 'ari', 'checkpoint', 'data', 'engine', 'objects', 'traverse', 'matching', 'figures',
            'slot_table', 'overlap_table', 'slot_iou', 'SLOT_COLUMNS', 'components', 'clean_segmentation', 'seg_to_mask', 'Components', 'latent_kl', 'rank_dims', 'Traversal',
            'pack_gt', 'overlap', 'assign', 'match_masks', 'matched_mask_loss', 'segmentation_scores', 'SegmentationEvaluator',
            'PALETTE', 'sheet', 'layout', 'matched_colors', 'decomposition', 'trajectory_sheet', 'restarts_sheet', 'encode_png', 'write_png']
@@ -18,6 +18,9 @@ def __getattr__(name):
     if name == 'Restarts':                                    # (what ``IODINE.restarts`` returns)
         from .model import Restarts
         return Restarts
+    if name == 'Adaptive':                                    # (what ``IODINE.reconstruct_adaptive`` returns)
+        from .adaptive import Adaptive
+        return Adaptive
     if name in ('chain_score', 'chain_consensus'):
         from . import chains
         return getattr(chains, name)

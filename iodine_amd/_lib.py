@@ -38,6 +38,17 @@ class SheetSpec(C.Structure):
     ]
 
 
+class AdaptiveCtl(C.Structure):
+    """``iodine_adaptive_ctl`` (include/iodine_hip.h): the controls of the adaptive stopping rule"""
+    _fields_ = [('max_iters', C.c_int), ('min_iters', C.c_int), ('check_every', C.c_int), ('tol', C.c_double), ('rtol', C.c_double)]
+
+
+class MoveEntry(C.Structure):
+    """``iodine_move_entry`` (include/iodine_hip.h): one row gather / scatter of ``iodine_adaptive_move``"""
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('row_floats', C.c_longlong), ('src_index', C.c_void_p), ('dst_index', C.c_void_p),
+                ('rows', C.c_int), ('src_rows', C.c_int), ('dst_rows', C.c_int)]
+
+
 _vp, _ci, _cf, _dbl, _ll, _ull, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_longlong, C.c_ulonglong, C.c_size_t
 _FP, _VPP, _CIP = C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.POINTER(C.c_int)
 
@@ -130,6 +141,10 @@ _SYMBOLS = {
     # refinement restarts, iodine_amd.chains / IODINE.restarts (a build without them raises on it)
     'iodine_chain_score': ([_vp] * 5 + [_ci] * 4 + [_dbl, _ci, _vp, _vp],),
     'iodine_chain_consensus': ([_vp] * 5 + [_ci] * 4 + [_vp] * 5,),
+    # adaptive refinement, iodine_amd.adaptive / IODINE.reconstruct_adaptive (a build without them raises on it)
+    'iodine_adaptive_select': ([_vp, _vp, _vp, _ci, _ci, _ci, _ci, C.POINTER(AdaptiveCtl), _dbl] + [_vp] * 9,),
+    'iodine_adaptive_move': ([_vp, C.POINTER(MoveEntry), _ci],),
+    'iodine_reconstruct_adaptive': ([_vp, _vp, _ci, _vp, _vp, C.POINTER(AdaptiveCtl), _vp, _VPP] + [_vp] * 11 + [_CIP],),
     # IODINE.edit, iodine_amd.traverse (a build without it raises on them)
     'iodine_scene_edit': ([_vp, _vp, _ci, _vp, _ci, _CIP, _CIP, _CIP, _vp, _ci] + [_vp] * 6,),
     # kernel-level tests of the per-pixel mixture kernels

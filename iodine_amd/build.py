@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, 'libiodine_hip.so')
-SOURCES = ['kernels_conv.hip', 'kernels_convws.hip', 'kernels_out.hip', 'kernels_pixel.hip', 'kernels_pixmap.hip', 'kernels_render.hip', 'kernels_misc.hip', 'kernels_clip.hip', 'kernels_objects.hip', 'kernels_components.hip', 'kernels_chains.hip', 'kernels_sheet.hip', 'kernels_match.hip', 'kernels_batch.hip', 'kernels_window.hip', 'kernels_edit.hip', 'kernels_predictive.hip', 'kernels_train.hip', 'kernels_wgrad.hip', 'kernels_gemm.hip', 'kernels_headbwd.hip', 'kernels_outbwd.hip', 'kernels_wgradws.hip', 'kernels_wgrad32.hip', 'kernels_refine.hip', 'kernels_refbwd.hip', 'kernels_refws.hip', 'kernels_refl0.hip', 'kernels_pack.hip', 'kernels_generic.hip', 'kernels_gensplit.hip', 'kernels_gens2.hip', 'kernels_genl0.hip', 'iodine_api.cpp', 'iodine_dispatch.cpp', 'iodine_plan.cpp', 'iodine_checks.cpp', 'iodine_params.cpp', 'iodine_train.cpp', 'iodine_pad.cpp', 'iodine_ops.cpp', 'iodine_testops.cpp', 'iodine_sheet.cpp']
+SOURCES = ['kernels_conv.hip', 'kernels_convws.hip', 'kernels_out.hip', 'kernels_pixel.hip', 'kernels_pixmap.hip', 'kernels_render.hip', 'kernels_misc.hip', 'kernels_clip.hip', 'kernels_objects.hip', 'kernels_components.hip', 'kernels_chains.hip', 'kernels_adaptive.hip', 'kernels_sheet.hip', 'kernels_match.hip', 'kernels_batch.hip', 'kernels_window.hip', 'kernels_edit.hip', 'kernels_predictive.hip', 'kernels_train.hip', 'kernels_wgrad.hip', 'kernels_gemm.hip', 'kernels_headbwd.hip', 'kernels_outbwd.hip', 'kernels_wgradws.hip', 'kernels_wgrad32.hip', 'kernels_refine.hip', 'kernels_refbwd.hip', 'kernels_refws.hip', 'kernels_refl0.hip', 'kernels_pack.hip', 'kernels_generic.hip', 'kernels_gensplit.hip', 'kernels_gens2.hip', 'kernels_genl0.hip', 'iodine_api.cpp', 'iodine_dispatch.cpp', 'iodine_plan.cpp', 'iodine_checks.cpp', 'iodine_params.cpp', 'iodine_train.cpp', 'iodine_pad.cpp', 'iodine_ops.cpp', 'iodine_adaptive.cpp', 'iodine_testops.cpp', 'iodine_sheet.cpp']
 
 
 def _headers():

@@ -244,6 +244,17 @@ hipError_t launch_chain_score(hipStream_t st, const float* x, const float* w, co
 hipError_t launch_chain_consensus(hipStream_t st, const unsigned char* seg, const int* perm, const int* ref, const float* mask, int C,
                                   int B, int K, int S, int* votes, unsigned char* consensus, float* agreement, float* match,
                                   float* mask_mean);
+// kernels_adaptive.hip: adaptive refinement - which of the n active images stop after t updates (one block, stable compaction), and the
+// row gather / scatter that follows them (stateless).  AdaptiveRule: the controls of tests/adaptive_reference.py with the objective's beta.
+// MoveEntry: row r of `rows` goes from src row src_index[r] to dst row dst_index[r] (NULL: r); src_rows / dst_rows = the arrays' extents in
+// rows, an index outside them moves nothing; vec is the launcher's (float4 where the row size and both pointers allow it)
+struct AdaptiveRule { int max_iters, min_iters, check_every; double tol, rtol, beta; };
+struct MoveEntry { const float* src; float* dst; long long row_floats; const int* src_index; const int* dst_index; int rows, src_rows, dst_rows, vec; };
+constexpr int ADAPTIVE_MOVE_MAX = 16;
+hipError_t launch_adaptive_select(hipStream_t st, const float* terms, const int* idx_in, int n, int R, int t, int B, const AdaptiveRule& rule,
+                                  const int* budget, int* idx_out, int* pos_out, int* stop_idx, int* stop_pos, int* counts, int* iters,
+                                  float* ll, float* kl);
+hipError_t launch_adaptive_move(hipStream_t st, const MoveEntry* entries, int count);
 // kernels_sheet.hip: decomposition sheets - panels of a few scenes as one uint8 HWC picture (stateless).  W = the sheet's width;
 // sheet_form: bit 0 = 16-byte loads, bit 1 = word stores, what the launcher will take for these pointers.
 struct iodine_sheet_spec;

@@ -225,6 +225,10 @@ struct GenPacks {
     std::vector<Pack> split_f, split_b;
 };
 
+// the second buffers of iodine_reconstruct_adaptive (iodine_adaptive.cpp): one device block and the pinned pair of counts, made by the first
+// adaptive call, grown on demand, freed by iodine_destroy
+struct AdaptiveScratch { void* dev = nullptr; size_t bytes = 0; int* counts_host = nullptr; };
+
 struct iodine_handle {
     iodine_config cfg;
     Options opt;
@@ -285,6 +289,7 @@ struct iodine_handle {
     void* ws_user = nullptr; size_t ws_user_bytes = 0;
     void* ws_own = nullptr; size_t ws_own_bytes = 0;
     Buffers buf;
+    AdaptiveScratch adapt;
 
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -329,6 +334,10 @@ struct AuxCot { const float *gl, *mean, *mask, *logits, *z, *pm, *plv, *lstm_h, 
 int set_params_check(iodine_handle* h, const float* const* dev, int n);
 int reconstruct_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* const* state_in, float* const* traj);
 int decode_check(iodine_handle* h, int batch, const float* z);
+// (iodine_adaptive.cpp; the outputs the rounds write to are required: only their nullness matters here)
+int adaptive_check(iodine_handle* h, int batch, const float* x, const float* eps, const iodine_adaptive_ctl* ctl, const float* const* state_in,
+                   const void* post_mean, const void* post_logvar, const void* lstm_h, const void* lstm_c, const void* iters, const void* ll,
+                   const void* kl);
 int scene_edit_check(iodine_handle* h, int batch, const float* z, int n_edits, const int* image, const int* slot, const int* kind,
                      const float* z_new, int chunk_images);
 int elbo_check(iodine_handle* h, int batch, const float* x, const float* eps, const float* post_mean, const float* post_logvar);
@@ -364,6 +373,10 @@ int pad_set_objective(iodine_handle* h, double sigma, double beta, const double*
 int pad_set_option(iodine_handle* h, const char* key, double value);
 int pad_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, float* pred, float* mask, float* mean,
                         float* z, float* post_mean, float* post_logvar, float* elbo_iter, const float* const* state_in, float* const* traj);
+int pad_reconstruct_adaptive(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const iodine_adaptive_ctl* ctl,
+                             const int* budget_or_null, const float* const* state_in, float* pred, float* mask, float* mean, float* z,
+                             float* post_mean, float* post_logvar, float* lstm_h, float* lstm_c, int* iters, float* ll, float* kl,
+                             int* active_out_or_null);
 int pad_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c, bool train = false);
 int pad_decode(iodine_handle* h, void* stream, int batch, const float* z, float* pred, float* mask, float* mean);
 int pad_scene_edit(iodine_handle* h, void* stream, int batch, const float* z, int n_edits, const int* image, const int* slot, const int* kind,

@@ -247,6 +247,38 @@ int pad_reconstruct_seq(iodine_handle* h, void* stream, int batch, const float* 
     return IODINE_OK;
 }
 
+// as pad_reconstruct_seq; the LSTM state comes back too (sh->gh / gc: sh->hs / cs hold the initial one)
+int pad_reconstruct_adaptive(iodine_handle* h, void* stream, int batch, const float* x, const float* eps, const iodine_adaptive_ctl* ctl,
+                             const int* budget_or_null, const float* const* state_in, float* pred, float* mask, float* mean, float* z,
+                             float* post_mean, float* post_logvar, float* lstm_h, float* lstm_c, int* iters, float* ll, float* kl,
+                             int* active_out_or_null)
+{
+    PadShim* sh = h->shim;
+    iodine_handle* in = sh->inner;
+    PendingWeights once(in);
+    if (int rc = adaptive_check(in, batch, x, eps, ctl, state_in, post_mean, post_logvar, lstm_h, lstm_c, iters, ll, kl)) return shim_fail(h, rc);
+    hipStream_t st = (hipStream_t)stream;
+    const long long N = (long long)batch * in->K, R = (long long)(ctl->max_iters + 1) * N;
+    if (int r = shim_scratch(h, std::max((size_t)R * sh->Lp, (size_t)N * sh->Hp))) return r;
+    HIPCHK(h, launch_resize_rows(st, eps, sh->eps, R, sh->L, sh->Lp));
+    const float* pstate[4] = {sh->pm_in, sh->plv_in, sh->hs, sh->cs};
+    if (state_in) {
+        HIPCHK(h, launch_resize_rows(st, state_in[0], sh->pm_in, N, sh->L, sh->Lp));
+        HIPCHK(h, launch_resize_rows(st, state_in[1], sh->plv_in, N, sh->L, sh->Lp));
+        HIPCHK(h, launch_resize_rows(st, state_in[2], sh->hs, N, sh->H, sh->Hp));
+        HIPCHK(h, launch_resize_rows(st, state_in[3], sh->cs, N, sh->H, sh->Hp));
+    }
+    const int rc = iodine_reconstruct_adaptive(in, stream, batch, x, sh->eps, ctl, budget_or_null, state_in ? pstate : nullptr, pred, mask, mean,
+                                               z ? sh->z : nullptr, sh->pm, sh->plv, sh->gh, sh->gc, iters, ll, kl, active_out_or_null);
+    if (rc) return shim_fail(h, rc);
+    if (z) HIPCHK(h, launch_resize_rows(st, sh->z, z, N, sh->Lp, sh->L));
+    HIPCHK(h, launch_resize_rows(st, sh->pm, post_mean, N, sh->Lp, sh->L));
+    HIPCHK(h, launch_resize_rows(st, sh->plv, post_logvar, N, sh->Lp, sh->L));
+    HIPCHK(h, launch_resize_rows(st, sh->gh, lstm_h, N, sh->Hp, sh->H));
+    HIPCHK(h, launch_resize_rows(st, sh->gc, lstm_c, N, sh->Hp, sh->H));
+    return IODINE_OK;
+}
+
 // (train: iodine_last_train_state - the same read-out after a training forward)
 int pad_last_refine_state(iodine_handle* h, void* stream, int count, float* lstm_h, float* lstm_c, bool train)
 {

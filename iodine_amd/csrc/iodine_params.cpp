@@ -423,6 +423,8 @@ void iodine_destroy(iodine_handle* h)
     for (auto& t : h->wtabs) if (t.dev) (void)hipFree(t.dev);
     for (auto& c : h->prof) for (auto& e : c.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     if (h->ws_own) (void)hipFree(h->ws_own);
+    if (h->adapt.dev) (void)hipFree(h->adapt.dev);
+    if (h->adapt.counts_host) (void)hipHostFree(h->adapt.counts_host);
     drop_graphs(h);
     delete h;
 }

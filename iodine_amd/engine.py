@@ -380,7 +380,8 @@ def make_log_sigma(sigma, device):
     return torch.full((), math.log(float(sigma)), dtype=torch.float32, device=device, requires_grad=True)
 
 
-def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, bound_samples=0, restarts=0, min_component_area=0):
+def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, bound_samples=0, restarts=0, min_component_area=0,
+             adaptive=None):
     """eval.py:14-28 with the ARI evaluator of lib/eval/ari_eval.py (works under no_grad, unlike the reference).  With
     several ranks every rank evaluates its shard; the samples DistributedSampler appended to pad the shards to equal length
     are dropped (they duplicate the first images) and ``evaluator.global_mean`` holds the ARI over the whole dataset.
@@ -398,20 +399,29 @@ def evaluate(model, dataloader, device, evaluator=None, slots=None, iters=None, 
     ``min_component_area`` = N > 0: beside the evaluator's own scores, the argmax map of every decode is split into connected components
     (``iodine_amd.objects.components``) and ``evaluator.cleaned`` holds the dataset means (over all ranks) of ``components_per_slot`` (per
     non-empty slot), ``small_pixel_share`` (valid pixels in components below N) and of ``SegmentationEvaluator``'s ``aris / mious / scs /
-    mscs`` on the maps with those components absorbed.  0 (default): no launch is added, no attribute is set."""
+    mscs`` on the maps with those components absorbed.  0 (default): no launch is added, no attribute is set.
+    ``adaptive`` = dict(tol=, rtol=, max_iters=, min_iters=, check_every=) (any subset that names a tolerance): the evaluators get the decodes
+    of ``model.reconstruct_adaptive(x, **adaptive)`` - every image refined until its ELBO estimate stops improving - and
+    ``evaluator.adaptive`` holds, over all ranks, ``mean_iters``, ``hist`` (images per iteration count, index 0 .. max_iters), ``at_max``
+    (the share of images that ran to max_iters) and ``max_iters``.  Not together with ``restarts``.  None (default): the usual path."""
     if isinstance(bound_samples, bool) or int(bound_samples) != bound_samples or bound_samples < 0:
         raise ValueError(f'evaluate: bound_samples must be an integer >= 0; got {bound_samples!r}')
     if isinstance(restarts, bool) or int(restarts) != restarts or restarts < 0:
         raise ValueError(f'evaluate: restarts must be an integer >= 0; got {restarts!r}')
     if isinstance(min_component_area, bool) or int(min_component_area) != min_component_area or min_component_area < 0:
         raise ValueError(f'evaluate: min_component_area must be an integer >= 0; got {min_component_area!r}')
+    if adaptive is not None:
+        if not isinstance(adaptive, dict) or set(adaptive) - {'tol', 'rtol', 'max_iters', 'min_iters', 'check_every'}:
+            raise ValueError(f'evaluate: adaptive must be a dict of tol, rtol, max_iters, min_iters, check_every; got {adaptive!r}')
+        if restarts > 1:
+            raise ValueError('evaluate: adaptive= and restarts= do not combine (every chain of a restart runs the fixed iteration count)')
     saved = (model.K, model.n_iters)
     if slots is not None:
         model.K = slots
     if iters is not None:
         model.n_iters = iters
     try:
-        return _evaluate(model, dataloader, device, evaluator, int(bound_samples), int(restarts), int(min_component_area))
+        return _evaluate(model, dataloader, device, evaluator, int(bound_samples), int(restarts), int(min_component_area), adaptive)
     finally:
         model.K, model.n_iters = saved
 
@@ -430,6 +440,23 @@ class _BestOfRestarts:
         res = self._model.restarts(x, chains=self._chains)
         best = res.score.gather(0, res.best.view(1, -1))[0]
         self.rows.extend(zip(res.stability.tolist(), best.tolist(), res.score[0].tolist()))
+        return res.pred, res.mask, res.mean
+
+
+class _AdaptiveDecodes:
+    """What ``evaluate(adaptive=...)`` hands the evaluators in place of the model: ``reconstruct(x)`` runs ``model.reconstruct_adaptive(x,
+    **options)`` and returns its decode; everything else is the model's.  ``iters``: per image, the updates it received."""
+
+    def __init__(self, model, options):
+        self._model, self._options, self.iters, self.max_iters = model, dict(options), [], 0
+
+    def __getattr__(self, name):
+        return getattr(self._model, name)
+
+    def reconstruct(self, x):
+        res = self._model.reconstruct_adaptive(x, **self._options)
+        self.iters.extend(res.iters.tolist())
+        self.max_iters = int(res.ll.shape[0])
         return res.pred, res.mask, res.mean
 
 
@@ -467,12 +494,13 @@ class _CleanedMaps:
             return self._owner._last
 
 
-def _evaluate(model, dataloader, device, evaluator, bound_samples=0, restarts=0, min_component_area=0):
+def _evaluate(model, dataloader, device, evaluator, bound_samples=0, restarts=0, min_component_area=0, adaptive=None):
     evaluator = evaluator or ARIEvaluator()
     evaluator.reset()
     bounds = []                                                              # per image: (iwae, elbo_mc)
     model.eval()
     scored = _BestOfRestarts(model, restarts) if restarts > 1 else model     # (what the evaluators call reconstruct on)
+    adapted = scored = _AdaptiveDecodes(model, adaptive) if adaptive is not None else scored
     cleaned = None
     if min_component_area:
         from .matching import SegmentationEvaluator
@@ -514,6 +542,16 @@ def _evaluate(model, dataloader, device, evaluator, bound_samples=0, restarts=0,
             torch.distributed.all_reduce(tot)
         n = max(float(tot[3]), 1.0)
         evaluator.stability, evaluator.best_score, evaluator.first_score = (float(tot[i]) / n for i in range(3))
+    if adaptive is not None:                                                 # images per iteration count, over all ranks
+        M = adapted.max_iters
+        hist = torch.zeros(M + 1, dtype=torch.float64, device=device if dist_on and torch.distributed.get_backend() == 'nccl' else 'cpu')
+        for t in adapted.iters[:mine]:
+            hist[t] += 1
+        if world > 1:
+            torch.distributed.all_reduce(hist)
+        n = max(float(hist.sum()), 1.0)
+        evaluator.adaptive = dict(mean_iters=float((hist * torch.arange(M + 1, dtype=torch.float64, device=hist.device)).sum()) / n,
+                                  hist=[int(v) for v in hist.tolist()], at_max=float(hist[M]) / n, max_iters=M)
     stats = torch.tensor([float(sum(evaluator.aris)), float(len(evaluator.aris))], dtype=torch.float64,
                          device=device if dist_on and torch.distributed.get_backend() == 'nccl' else 'cpu')
     if world > 1:
@@ -633,6 +671,13 @@ def make_parser():
     ap.add_argument('--eval-restarts', type=int, default=0, metavar='C',
                     help='evaluate the best of C refinement chains per image (IODINE.restarts) and report the stability of the chains and '
                          'the gain of selecting; 0 / 1 = one chain, the usual evaluation')
+    ap.add_argument('--eval-adaptive-rtol', type=float, default=None, metavar='X',
+                    help='evaluate with adaptive refinement (IODINE.reconstruct_adaptive): an image stops once its ELBO estimate rises by less '
+                         'than tol + X |ELBO| between two evaluations; reports the mean and histogram of the iteration counts and the share '
+                         'of images at the maximum beside the usual metrics')
+    ap.add_argument('--eval-adaptive-tol', type=float, default=None, metavar='Y', help='with adaptive evaluation: the absolute tolerance in nats')
+    ap.add_argument('--eval-max-iters', type=int, default=None, metavar='N', help='with adaptive evaluation: the most updates per image (default: ITERS)')
+    ap.add_argument('--eval-check-every', type=int, default=1, metavar='R', help='with adaptive evaluation: updates per round')
     ap.add_argument('--mask-loss', type=float, default=0.0, metavar='W',
                     help='supervised masks: add W * matched_mask_loss(model.mask, ground truth) to every step whose batch carries masks '
                          '(ground-truth objects assigned to slots on the device; 0: off)')
@@ -771,7 +816,8 @@ def main(argv=None):
         from .matching import SegmentationEvaluator
         evaluator = SegmentationEvaluator()
     ev = evaluate(model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, evaluator=evaluator,
-                  bound_samples=args.eval_samples, restarts=args.eval_restarts, min_component_area=args.min_component_area)
+                  bound_samples=args.eval_samples, restarts=args.eval_restarts, min_component_area=args.min_component_area,
+                  adaptive=_adaptive_options(args))
     _report(args, rank, losses, ev)
     _final_sheet(args, model, make_dataloader(ds, args.batch, shuffle=False, rank=rank, world_size=world), device, rank)
 
@@ -880,9 +926,23 @@ def _main_resident(args, arch, model, optimizer, ds, device, rank, world, log_si
         from .matching import SegmentationEvaluator
         evaluator = SegmentationEvaluator()
     ev = evaluate(model, eval_batches(), device, evaluator=evaluator, bound_samples=args.eval_samples, restarts=args.eval_restarts,
-                  min_component_area=args.min_component_area)
+                  min_component_area=args.min_component_area, adaptive=_adaptive_options(args))
     _report(args, rank, losses, ev)
     _final_sheet(args, model, eval_batches(), device, rank)
+
+
+def _adaptive_options(args):
+    """the ``adaptive=`` of ``evaluate`` from the --eval-adaptive-* flags (None: not asked for)"""
+    if args.eval_adaptive_rtol is None and args.eval_adaptive_tol is None:
+        return None
+    opts = dict(rtol=args.eval_adaptive_rtol or 0.0, check_every=args.eval_check_every)
+    if args.eval_adaptive_tol is not None:
+        opts['tol'] = args.eval_adaptive_tol
+    elif not opts['rtol'] > 0:
+        opts['tol'] = 0.0
+    if args.eval_max_iters is not None:
+        opts['max_iters'] = args.eval_max_iters
+    return opts
 
 
 def _report(args, rank, losses, ev):
@@ -898,6 +958,10 @@ def _report(args, rank, losses, ev):
         if args.eval_restarts > 1:
             print('best of {} chains per image: stability {:.4f}, score {:.3f} (chain 0 alone: {:.3f})'.format(
                 args.eval_restarts, ev.stability, ev.best_score, ev.first_score))
+        if getattr(ev, 'adaptive', None):
+            a = ev.adaptive
+            print('adaptive refinement: {:.3f} iterations per image (max {}), {:.2%} of the images at the maximum; images per count 0..{}: {}'.format(
+                a['mean_iters'], a['max_iters'], a['at_max'], a['max_iters'], a['hist']))
         if args.eval_samples:
             print('{}-sample bounds per image: IWAE {:.3f}, Monte-Carlo ELBO {:.3f}'.format(args.eval_samples, ev.iwae, ev.elbo_mc))
 

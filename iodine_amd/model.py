@@ -82,6 +82,12 @@ counts with their arg-max and agreement, and with an image the per-sample log-li
 the closed-form-KL ELBO per image (``iodine_predictive``: the samples share one decoder pass per chunk and one per-pixel kernel keeps the running
 moments; nothing per sample is written).  Not in the reference, which scores and renders one draw (iodine.py:103, 171).
 
+Adaptive refinement: ``model.reconstruct_adaptive(x, tol=..., rtol=..., max_iters=..., budget=...)`` refines every image until its own ELBO
+estimate stops improving, drops it from the batch between rounds of ``check_every`` iterations and returns an ``adaptive.Adaptive`` with the
+per-image iteration counts - image b is bit for bit what ``reconstruct`` gives at ``n_iters = iters[b]``, at the cost of ``sum(iters)``
+image-iterations (``iodine_reconstruct_adaptive``; the rule is defined by tests/adaptive_reference.py).  Not in the reference, which runs
+``ARCH.ITERS`` iterations for every image (iodine.py:85).
+
 Extensions over the reference: every entry point takes an optional ``eps`` tensor of shape
 (T+1, B, K, L) replacing the ``torch.randn_like`` draws of ``Gaussian.sample``
 (iodine.py:632) in call order, so that results can be compared with the CPU oracle.  Without
@@ -93,6 +99,7 @@ still shows from ATen are autograd's own fills: ``loss.backward()`` seeds the sc
 from __future__ import annotations
 
 import dataclasses
+import math
 import numbers
 from typing import Optional
 
@@ -996,7 +1003,123 @@ class IODINE(nn.Module):
             out.stability = ((m64.sum(0) - own) / (C - 1)).float() if C > 1 else torch.ones(B, dtype=torch.float32, device=dev)
         return out
 
-    _STALE = ('IODINE: backward of a stale {0} - the library keeps the saved state of ONE differentiable call and another forward / '
+    def _check_adaptive(self, x, tol, rtol, max_iters, min_iters, check_every, budget, eps):
+        """The host-only refusals of ``reconstruct_adaptive`` -> (ctl, K, budget as int32 on the host or None); every one a ValueError,
+        before any device work."""
+        from . import adaptive as _ad
+        who = 'IODINE.reconstruct_adaptive'
+        c, s = self.img_channels, self.img_size
+        if not torch.is_tensor(x) or x.dim() != 4 or tuple(x.shape[1:]) != (c, s, s) or x.shape[0] < 1:
+            clip = ' (a clip is not supported: its frames belong to fixed iterations)' if torch.is_tensor(x) and x.dim() == 5 else ''
+            raise ValueError(f'{who}: x must be images of shape (B, {c}, {s}, {s}){clip}; got '
+                             f'{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}')
+        given_r = not isinstance(rtol, bool) and isinstance(rtol, (int, float)) and rtol > 0
+        if tol is None and budget is None and not given_r:
+            raise ValueError(f'{who}: give at least one of tol, rtol (> 0) or budget - without any the call is a fixed reconstruct')
+        K, T = _args.run_shape(self.K, self.n_iters if max_iters is None else max_iters)
+        # no tol: the relative rule alone (tol 0) where rtol is given, else only the budget stops an image early (tol -inf)
+        ctl = _ad.controls(T, min_iters, check_every, (0.0 if given_r else -math.inf) if tol is None else tol, rtol, who)
+        B = int(x.shape[0])
+        if budget is not None:
+            if (not torch.is_tensor(budget) or budget.is_floating_point() or budget.is_complex() or budget.dtype == torch.bool
+                    or tuple(budget.shape) != (B,)):
+                raise ValueError(f'{who}: budget must be an integer tensor of shape ({B},); got '
+                                 f'{(budget.dtype, tuple(budget.shape)) if torch.is_tensor(budget) else type(budget).__name__}')
+            budget = budget.detach().to(device='cpu', dtype=torch.int64)
+            if int(budget.min()) < 1 or int(budget.max()) > T:
+                raise ValueError(f'{who}: budget values must be in 1..max_iters = {T}; got {int(budget.min())}..{int(budget.max())}')
+            budget = budget.to(torch.int32)
+        want = (T + 1, B, K, self.dim_latent)
+        if eps is not None and (not torch.is_tensor(eps) or tuple(eps.shape) != want):
+            raise ValueError(f'{who}: eps must have shape {want} (max_iters + 1, B, K, L); got '
+                             f'{tuple(eps.shape) if torch.is_tensor(eps) else type(eps).__name__}')
+        return ctl, K, budget
+
+    @torch.no_grad()
+    def reconstruct_adaptive(self, x, tol=None, rtol=0.0, max_iters=None, min_iters=2, check_every=1, budget=None, eps=None, state=None,
+                             weights=None):
+        """``reconstruct`` with a per-image iteration count: every image is refined until ITS ELBO estimate stops improving, then leaves
+        the batch - the later iterations run on the images still moving, so the cost follows ``sum(iters)``, not ``B max_iters``.  Returns
+        an ``iodine_amd.adaptive.Adaptive``; ``Adaptive.iters`` is a diagnostic of its own ("iterations to converge" per image).
+
+        The rule (tests/adaptive_reference.py defines it, in float64): with ``s_i = ll_i - model.beta kl_i`` of ELBO evaluation i of an
+        image (the per-image terms ``trajectory['ll'] / ['kl']`` hold), after t in {check_every, 2 check_every, ..} < max_iters updates the
+        image stops when ``t >= budget[b]``, or when ``t >= max(min_iters, 2)`` and ``s_{t-1} - s_{t-2} < tol + rtol |s_{t-2}|``; a NaN or
+        an infinity that makes either side NaN keeps the image running; at ``max_iters`` (default ``model.n_iters``) everything stops.
+        EVERY EVALUATION DRAWS FRESH NOISE: s is a one-sample estimate of the ELBO, so ``tol`` has to sit above that noise or images stop
+        by chance (it may be negative: "stop once the estimate no longer rises by more than the noise"), and with ``check_every > 1`` only
+        evaluations t - 1 and t - 2 are compared, not the gain of the whole round.  ``tol=-inf``: never stop early; ``+inf``: stop at the
+        first permitted check.  ``tol=None``: 0 with an ``rtol > 0``, else the budget alone decides.  ``budget``: integer tensor (B,) with
+        values in 1..max_iters, an iteration allowance per image (rounded up to a multiple of ``check_every``).
+
+        For image b with t = iters[b]: ``pred, mask, mean, z, post_mean, post_logvar`` and the LSTM state are, bit for bit, what
+        ``reconstruct`` + ``refinement_state()`` give with ``n_iters = t`` and the noise rows ``cat(eps[:t], eps[max_iters:])`` - the final
+        sample of every image uses the LAST row of ``eps (max_iters + 1, B, K, L)`` -; ``ll[:t, b]`` / ``kl[:t, b]`` are that call's
+        trajectory, the rows from t on NaN.  ``state`` / ``weights``: as ``reconstruct`` (``max_iters`` FURTHER iterations at most).
+        Batches above ``max_batch()`` run in chunks and are merged (``active`` adds up over the chunks).
+
+        Afterwards ``model.posterior`` holds the final posteriors and ``refinement_state()`` returns the full-batch (post_mean,
+        post_logvar, h, c) of this call; ``elbo_terms``, ``trajectory`` and ``objects`` are None.  ``model.z / mean / mask / mask_logits``,
+        the likelihood maps and the logger are LEFT AS THEY WERE: they describe "the last ELBO evaluation", and no single evaluation is
+        the last for all images here.  NOT differentiable; never part of a hipGraph (with option ``graph`` the call runs eagerly - it
+        reads two counts back after every round).  A clip ``x`` and every other bad argument is a ValueError before any device work."""
+        from . import adaptive as _ad
+        ctl, K, budget = self._check_adaptive(x, tol, rtol, max_iters, min_iters, check_every, budget, eps)
+        M, R = int(ctl.max_iters), int(ctl.check_every)
+        # (the handle runs at T = check_every; inference reads no iteration weights, so the default table is what it is given)
+        obj = _args.read_objective(self.sigma, self.beta, None, R)
+        xc = _args.check_x(x, self.img_channels, self.img_size)
+        w = _args.check_weights(weights, xc, self.img_size, 'reconstruct_adaptive')
+        dev, B, L, H = xc.device, int(xc.shape[0]), self.dim_latent, int(self._cfg.ref_mlp_units)
+        self._bind(dev)                                     # (a CPU tensor is refused here, after the argument checks)
+        state = _args.check_state(state, B, K, L, H, dev)
+        if eps is None:
+            eps = self._normals(None, (M + 1, B, K, L), dev).clone()
+        eps = eps.detach().to(device=dev, dtype=torch.float32).contiguous()
+        bud = None if budget is None else budget.to(dev)
+        self.trajectory, self._state, self.objects, self.elbo_terms = None, None, None, None
+        runs = split(B, self.max_batch(K=K, T=R))
+        parts = []
+        for s, e, _ in runs:                                # chunks of independent images; eps (max_iters + 1, B, K, L) is cut along B
+            one = len(runs) == 1
+            parts.append(self._adaptive_call(xc if one else xc[s:e].contiguous(), eps if one else cut(eps, s, e, 1).contiguous(),
+                                             cut(w, s, e), state and tuple(t[s:e].contiguous() for t in state),
+                                             None if bud is None else bud[s:e].contiguous(), ctl, K, obj))
+        out = parts[0] if len(parts) == 1 else merge(parts, (CAT0,) * 9 + (CAT1, CAT1))
+        pred, mask, mean, z, pm, plv, h, c, iters, ll, kl = out
+        active = [sum(col) for col in zip(*(p.active for p in parts))]
+        self.posterior.mean, self.posterior.logvar = pm, plv
+        self._state = _RefineState(pm, plv, h, c)           # fetched: no workspace read is needed later
+        return _ad.Adaptive(pred, mask, mean, z, pm, plv, iters, ll, kl, ll.double() - obj[1] * kl.double(), active)
+
+    class _AdaptivePart(tuple):
+        active = ()
+
+    def _adaptive_call(self, x, eps, w, state, budget, ctl, K, obj):
+        """One library call of ``reconstruct_adaptive`` (a whole batch, or a chunk of one) -> (pred, mask, mean, z, post_mean, post_logvar, h,
+        c, iters, ll, kl) with ``.active``."""
+        import ctypes as C
+        dev, B, L, S, H = x.device, int(x.shape[0]), self.dim_latent, self.img_size, int(self._cfg.ref_mlp_units)
+        M, R = int(ctl.max_iters), int(ctl.check_every)
+        ses = self._bind(dev)
+        ses.prepare(dev, B, 0, K, R, 0, obj, stable_encoding=self.stable_encoding, joint_likelihood=self._joint())
+        f = dict(device=dev, dtype=torch.float32)
+        pred, mask, mean = torch.empty((B, 3, S, S), **f), torch.empty((B, K, 1, S, S), **f), torch.empty((B, K, 3, S, S), **f)
+        z, pm, plv = (torch.empty((B, K, L), **f) for _ in range(3))
+        h, c = (torch.empty((B, K, H), **f) for _ in range(2))
+        iters = torch.empty((B,), device=dev, dtype=torch.int32)
+        ll, kl = (torch.empty((M, B), **f) for _ in range(2))
+        active = (C.c_int * (-(-M // R)))()
+        ses.call_serial += 1
+        ws = ses.send_weights(w)                            # (ws: alive until the call is queued)
+        ses.call('iodine_reconstruct_adaptive', B, x, eps, C.byref(ctl), budget, None if state is None else _lib.ptrs(list(state)),
+                 pred, mask, mean, z, pm, plv, h, c, iters, ll, kl, active)
+        del ws
+        part = self._AdaptivePart((pred, mask, mean, z, pm, plv, h, c, iters, ll, kl))
+        part.active = list(active)
+        return part
+
+    _STALE = ('IODINE: backward of a stale {0} -the library keeps the saved state of ONE differentiable call and another forward / '
               'reconstruct / decode / elbo call has re-used it since, or it was differentiated already (the reference would hold a second '
               'autograd graph; call backward() before the next model call)')
 
